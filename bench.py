@@ -30,6 +30,23 @@ FP32_PEAK_TFLOPS = 157.3                         # MI355X_MICROARCH.md: vector =
 MFMA_FLOP = 2048                                 # one v_mfma_f32_16x16x4_f32: 16 x 16 x 4 x 2
 MFMA_F16_FLOP = 16384                            # one v_mfma_f32_16x16x32_f16: 16 x 16 x 32 x 2
 VALU_FLOP_PER_LANE = 2.0                         # estimate: the VALU mix is ~half packed FMA (4), ~half packed add/mul (2), rest 0-1
+DUMP_BYTES = 64_000_000 - 4096                   # --dump-outputs: at most 64 MB in all (less room for the .npy header)
+DUMP_SEED = 7
+
+
+def dump_outputs(dirname, feats):
+    """--dump-outputs: the features of the timed path's last step as DIR/features.npy (float32, (windows, 2000, 44)).  A batch larger
+    than DUMP_BYTES is written as a fixed sample of windows (seeded, in ascending order), so that two builds given the same arguments
+    write the same windows."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    n = feats.shape[0]
+    keep = min(n, DUMP_BYTES // (feats[0].numel() * feats.element_size()))
+    if keep < n:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, keep, replace=False))
+        feats = feats.index_select(0, torch.from_numpy(idx).to(feats.device))
+    np.save(os.path.join(dirname, "features.npy"), feats.float().cpu().numpy())
 
 
 def csrc_digest():
@@ -522,9 +539,16 @@ def main():
                     help="drive the WHOLE N-rank path (self-launch, shard, C2 + C3, gathers, JSON with n_gpus = N) with every rank on GPU 0 and "
                          "the exchange over gloo: the only thing left untested for an N-GPU box is RCCL itself.  Not a measurement.")
     ap.add_argument("--cpu-budget", type=float, default=16.0)
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="c2 only: after the timed steps, write the features of the last step (rank 0) as DIR/features.npy, float32; "
+                         "a fixed seeded sample of the windows when the batch exceeds 64 MB")
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.dump_outputs and args.config != "c2":
+        ap.error("--dump-outputs writes the C2 workload's features (--config c2)")
     if args.config == "c5":
         if args.gpus != 1:
             ap.error("--config c5 is a single-GPU measurement")
@@ -564,7 +588,7 @@ def main():
     dev = torch.device("cuda", local)
 
     if args.config == "c3":
-        res = bench_c3(dev, rank, world, use_dist, max(1, min(args.steps, 20)), min(args.warmup, 3), nrec=args.c3_recordings)
+        res = bench_c3(dev, rank, world, use_dist, args.steps, min(args.warmup, 3), nrec=args.c3_recordings)
         if args.dry_run_gloo:
             res["config"]["dry_run"] = "every rank on GPU 0, exchange over gloo: a path test, not a measurement"
         if rank == 0:
@@ -608,6 +632,8 @@ def main():
     core_ms, norm_ms, ncalls = tf.timing(local)
     tf.set_timing(False, local)
     fused = tf.check(local)                                   # raises if a kernel reported a failed internal wait
+    if args.dump_outputs and rank == 0:                       # (after the timed region: `out` holds the last timed step's features)
+        dump_outputs(args.dump_outputs, out)
     if args.pmc_child:                                        # (under rocprofv3 --pmc: the parent reads the counters)
         return
     if use_dist:

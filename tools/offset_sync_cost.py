@@ -1,6 +1,6 @@
-import sys, time
+import os, sys, time
 import numpy as np, torch
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from heart_sounds_segmentation_amd import FSST, synth
 tf = FSST(1000, synth.kaiser_window(128, 0.5), truncate_freq=(25, 200), stack=True)
 out = torch.empty((1024, 2000, 44), dtype=torch.float32, device="cuda")

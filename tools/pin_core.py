@@ -10,9 +10,9 @@ from their seeds) plus the signals of tests/known_answers.py and two PCG / noise
 ``tests/golden/core_ssq.npz``: for every case ``<tag>__x``, ``__fs``, ``__window`` and the core's raw outputs
 ``__s`` (complex128 (nf, nt)), ``__f``, ``__t`` exactly as returned (no cast, no truncation).
 
-Once that file is committed, tests/test_oracle.py::test_oracle_matches_real_ssq_core (CPU) and
-tests/test_gpu_parity.py::test_hip_matches_real_ssq_core (-m gpu) compare the C oracle and the HIP path with it and stop
-skipping.  Nothing of the reference is copied: the file holds inputs and numeric outputs only.
+Once that file is committed, tests/test_oracle.py::test_oracle_matches_real_ssq_core (CPU) stops skipping and compares the
+C oracle with it, and tests/test_gpu_parity.py::test_hip_matches_oracle_and_pinned_core (-m gpu), which checks the HIP path
+against the oracle on these cases meanwhile, compares the HIP path with it as well.  Nothing of the reference is copied: the file holds inputs and numeric outputs only.
 
 The build container and the GPU boxes have no ``ssq``: there this script exits with code 3.
 """

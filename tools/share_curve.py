@@ -2,10 +2,11 @@
 """N PROCESSES sharing one GPU, each running the reference's dataset loop -- one 2000-sample CPU frame per FSST.__call__
 (/root/reference/hss/datasets/heart_sounds.py:166-168; /root/reference/main.py:206 forks os.cpu_count() DataLoader workers) -- for a fixed time:
 windows/s per process and in all, the share of calls whose team launch gave itself up, median / p99 of a call, every 16th result compared with
-the two-launch path's.  usage: share_curve.py [procs ...]   (default 1 3 8 32)"""
+the two-launch path's.  usage: share_curve.py [procs ...]   (default 1 3 6; at most 6: more processes may not have one shared GPU open at once)"""
 import os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+MAX_PROCS = 6                                            # processes with the GPU open at one time, on a GPU shared with other people's work
 
 
 def worker(rank, seconds, q, go):
@@ -39,7 +40,9 @@ def worker(rank, seconds, q, go):
 
 if __name__ == "__main__":
     import torch.multiprocessing as mp
-    counts = [int(a) for a in sys.argv[1:]] or [1, 3, 8, 32]
+    counts = [int(a) for a in sys.argv[1:]] or [1, 3, 6]
+    if not all(1 <= c <= MAX_PROCS for c in counts):
+        sys.exit(f"share_curve.py: process counts must be 1 .. {MAX_PROCS}, got {counts}")
     seconds = float(os.environ.get("SHARE_SECONDS", "4"))
     ctx = mp.get_context("spawn")
     rc = 0

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Several PROCESSES sharing one GPU, each running team-kernel execs of random small batches back to back (the DataLoader-worker
 situation, /root/reference/main.py:202-218): no exec may report a failed wait, and every result must equal the two-launch path's.
-usage: team_stress.py [procs=4] [iters=300]"""
+usage: team_stress.py [procs=4, at most 6] [iters=300]"""
 import os, sys, time
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -33,6 +33,8 @@ def worker(rank, iters, q, go):
 if __name__ == "__main__":
     import torch.multiprocessing as mp
     procs = int(sys.argv[1]) if len(sys.argv) > 1 else 4
+    if not 1 <= procs <= 6:                                        # processes with the GPU open at one time, on a GPU shared with other people's work
+        sys.exit(f"team_stress.py: procs must be 1 .. 6, got {procs}")
     iters = int(sys.argv[2]) if len(sys.argv) > 2 else 300
     ctx = mp.get_context("spawn")
     q = ctx.Queue()

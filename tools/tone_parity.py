@@ -1,5 +1,5 @@
-import sys, numpy as np, torch
-sys.path.insert(0, "/root/repo")
+import os, sys, numpy as np, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import oracle
 from heart_sounds_segmentation_amd import FSST, synth
 from tests import parity
