@@ -18,6 +18,7 @@ HEADER = os.path.join(os.path.dirname(_PKG), "include", "hssfsst.h")
 
 MODE_RAW, MODE_ABS, MODE_STACK, MODE_STACK_UNNORM = 0, 1, 2, 3
 E_INVAL, E_NODEVICE, E_UNSUPPORTED, E_NOMEM, E_HIP = -1, -2, -3, -4, -5
+DTYPE_F32, DTYPE_F64 = 0, 1
 
 _lock = threading.Lock()
 _lib = None
@@ -227,6 +228,14 @@ def lib():
         L.hssfsst_pack_recordings.restype = c_i64
         L.hssfsst_resample.argtypes = [dp, c_i64, c_i64, dp]
         L.hssfsst_resample.restype = c_int
+        L.hssfsst_resample_plan_create.argtypes = [ctypes.POINTER(vp), c_int, c_i64, c_i64]
+        L.hssfsst_resample_plan_create.restype = c_int
+        L.hssfsst_resample_plan_destroy.argtypes = [vp]
+        L.hssfsst_resample_plan_destroy.restype = c_int
+        L.hssfsst_resample_plan_info.argtypes = [vp, vp, vp, ip, ip, ip, ip]
+        L.hssfsst_resample_plan_info.restype = c_int
+        L.hssfsst_resample_exec.argtypes = [vp, vp, c_int, c_i64, c_i64, vp, c_int, c_i64, c_int, vp, c_int, vp, c_int, vp]
+        L.hssfsst_resample_exec.restype = c_int
         L.hssfsst_device_count.restype = c_int
         L.hssfsst_version.restype = c_int
         L.hssfsst_last_error.restype = ctypes.c_char_p

@@ -18,6 +18,12 @@ How it is fed (round 3; round 2 moved 77.7 k windows/s from host recordings agai
     the previous group is transformed (``hssfsst_exec_list`` writes straight into the group's rows of the arena);
   * host-returned features leave the device group by group on a third stream, overlapping the next group's transform.
 
+With ``resample=Resample(num)`` the builder is the reference's ``Compose([Resample(num), FSST(...)])`` under ``framing=True``
+(heart_sounds.py:166-168,199-212): every ``frame_len``-sample frame is resampled to ``num`` samples on the device (list form of
+``hssfsst_resample_exec`` over the packed group), the ``(frames, num)`` buffer goes through the transform, and items are
+``(num, 2K)`` features with ``(num,)`` labels ``round(Resample(frame of (y - 1))) - 1`` -- the reference's double shift kept --
+computed on the device from a second packed upload of the label tracks.
+
 Multi-GPU (BASELINE config C3): ``rank`` / ``world`` split the RECORDINGS in contiguous
 blocks (``dist.shard_bounds``), so framing stays local to a rank and concatenating the ranks' item lists in rank
 order is the single-process list; ``gather_features`` reassembles the feature tensor on every rank with one
@@ -65,14 +71,30 @@ class CorpusBuilder:
     buffers and hipMalloc of gigabytes cost more than the transform itself)."""
 
     def __init__(self, fsst, stride: int = 1000, frame_len: int = 2000, device: Optional[torch.device] = None,
-                 windows_per_launch: int = 4096, pin_host: bool = True):
+                 windows_per_launch: int = 4096, pin_host: bool = True, resample=None):
         self.fsst, self.stride, self.frame_len = fsst, int(stride), int(frame_len)
+        self.resample = resample                          # a Resample: frames are resampled to resample.num samples first
         self.dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         self.wpl, self.pin_host = int(windows_per_launch), bool(pin_host)
         self._cap_samples = self._cap_frames = self._cap_ring = 0
+        self._cap_rs = self._cap_lab = 0
         self._bufs = None
 
-    def _ensure(self, max_samples: int, max_frames: int, C: int, need_ring: bool) -> None:
+    def _ensure_resample(self, max_samples: int, max_frames: int, num: int, need_labels: bool) -> None:
+        """Device buffer of a group's resampled frames; pinned / device staging of its label tracks."""
+        b, dev = self._bufs, self.dev
+        if max_frames * num > self._cap_rs:
+            b["rs_d"] = torch.empty(max_frames * num, dtype=torch.float32, device=dev)
+            self._cap_rs = max_frames * num
+        if need_labels and max_samples > self._cap_lab:
+            b["lab_h"] = [torch.empty(max_samples, dtype=torch.float32, pin_memory=True) for _ in range(2)]
+            b["lab_d"] = [torch.empty(max_samples, dtype=torch.float32, device=dev) for _ in range(2)]
+            b["lab_starts"] = np.empty(max_frames, dtype=np.int64)
+            self._cap_lab = max_samples
+        elif need_labels and b["lab_starts"].shape[0] < max_frames:
+            b["lab_starts"] = np.empty(max_frames, dtype=np.int64)
+
+    def _ensure(self, max_samples: int, max_frames: int, C: int, need_ring: bool, item_len: Optional[int] = None) -> None:
         dev = self.dev
         if self._bufs is None:
             self._bufs = {"up": torch.cuda.Stream(dev), "down": torch.cuda.Stream(dev),
@@ -87,8 +109,9 @@ class CorpusBuilder:
             b["start_h"] = [torch.empty(max_frames, dtype=torch.int64, pin_memory=True) for _ in range(2)]
             b["start_d"] = [torch.empty(max_frames, dtype=torch.int64, device=dev) for _ in range(2)]
             self._cap_frames = max_frames
-        if need_ring and max_frames * C > self._cap_ring:
-            b["ring_d"] = [torch.empty((max_frames, self.frame_len, C), dtype=torch.float32, device=dev) for _ in range(2)]
+        item_len = self.frame_len if item_len is None else item_len
+        if need_ring and (max_frames * C > self._cap_ring or b["ring_d"][0].shape[1] != item_len):
+            b["ring_d"] = [torch.empty((max_frames, item_len, C), dtype=torch.float32, device=dev) for _ in range(2)]
             self._cap_ring = max_frames * C
 
     def build(self, recordings: Iterable[Tuple[torch.Tensor, Optional[torch.Tensor]]], keep_on_device: bool = False,
@@ -96,6 +119,10 @@ class CorpusBuilder:
         """See ``build_features``.  ``out``: a feature arena of a previous call to write into (same shape, device arena
         for ``keep_on_device`` else host)."""
         fsst, stride, frame_len, dev = self.fsst, self.stride, self.frame_len, self.dev
+        rsm = self.resample
+        if rsm is not None and dev.type != "cuda":
+            raise ValueError("CorpusBuilder.build: resample= runs on a HIP device; the builder's device is not one")
+        out_len = int(rsm.num) if rsm is not None else frame_len     # samples per item after the optional resampling
         recs: Sequence = recordings if isinstance(recordings, (list, tuple)) else list(recordings)
         # argument errors are properties of the WHOLE call and are raised before the list is cut to this rank's shard: a rank that
         # raised alone left the others waiting in the gather that follows
@@ -128,7 +155,7 @@ class CorpusBuilder:
                 g0, acc = i + 1, 0
         if g0 < len(recs):
             groups.append((g0, len(recs)))
-        labels = torch.empty((total, frame_len), dtype=torch.int64) if have_labels else None
+        labels = torch.empty((total, out_len), dtype=torch.int64) if have_labels and rsm is None else None
 
         def fill_labels(a: int, b: int, row: int) -> None:
             for i in range(a, b):
@@ -158,7 +185,7 @@ class CorpusBuilder:
 
         plan = fsst._plan(fsst._device_index(torch.empty(0, device=dev)))
         C = plan.ofps
-        shape = (total, frame_len, C)
+        shape = (total, out_len, C)
         if out is not None and (tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous()
                                 or out.is_cuda != bool(keep_on_device)):
             raise ValueError(f"CorpusBuilder.build: out must be a contiguous float32 {shape} arena "
@@ -173,11 +200,17 @@ class CorpusBuilder:
                 except RuntimeError:                      # page-locking that much memory can be refused: pageable then
                     feats = torch.empty(shape, dtype=torch.float32)
         if total == 0:
+            if have_labels and rsm is not None:
+                labels = torch.empty((0, out_len), dtype=torch.int64)
             return FrameItems(feats, labels)
         max_samples = max(sum(int(recs[i][0].shape[0]) for i in range(a, b)) for a, b in groups)
         max_frames = max(sum(nfr[a:b]) for a, b in groups)
-        self._ensure(max_samples, max_frames, C, not keep_on_device)
+        self._ensure(max_samples, max_frames, C, not keep_on_device, out_len)
+        dev_labels = have_labels and rsm is not None     # labels resampled on the device: (total, num) device arena, copied once
+        if rsm is not None:
+            self._ensure_resample(max_samples, max_frames, out_len, dev_labels)
         B = self._bufs
+        lab_d = torch.empty((total, out_len), dtype=torch.int64, device=dev) if dev_labels else None
         main, up, down = torch.cuda.current_stream(dev), B["up"], B["down"]
         stage_h, stage_d, start_h, start_d = B["stage_h"], B["stage_d"], B["start_h"], B["start_d"]
         up_done, used, ring_free = B["up_done"], B["used"], B["ring_free"]
@@ -192,6 +225,9 @@ class CorpusBuilder:
         held = [x if (x.dtype == torch.float32 and x.is_contiguous() and not x.is_cuda) else x.detach().to("cpu", torch.float32).contiguous()
                 for x, _ in recs]
         ptrs_np = np.asarray([x.data_ptr() for x in held], dtype=np.uint64)
+        if dev_labels:                                   # the label tracks (y - 1), exact in float32, packed like the signals
+            held_y = [(y.reshape(-1) - 1).to("cpu", torch.float32).contiguous() for _, y in recs]
+            yptrs_np = np.asarray([y.data_ptr() for y in held_y], dtype=np.uint64)
         pos_np = np.concatenate([[0], np.cumsum(lens_np)])
         fr_np = np.concatenate([[0], np.cumsum(nfr_np)])
         L = _lib.lib()
@@ -208,9 +244,18 @@ class CorpusBuilder:
                                             ctypes.c_void_p(start_h[buf].data_ptr()), int(start_h[buf].numel()), 0)
             if got != nf:
                 _lib.check(int(got) if got < 0 else _lib.E_INVAL, "hssfsst_pack_recordings")
+            if dev_labels:
+                lab_h, lst = B["lab_h"][buf], B["lab_starts"]
+                got = L.hssfsst_pack_recordings(ctypes.c_void_p(yptrs_np[a:b].ctypes.data), ctypes.c_void_p(lens_np[a:b].ctypes.data), b - a,
+                                                stride, frame_len, ctypes.c_void_p(lab_h.data_ptr()), int(lab_h.numel()),
+                                                ctypes.c_void_p(lst.ctypes.data), int(lst.shape[0]), 0)
+                if got != nf:
+                    _lib.check(int(got) if got < 0 else _lib.E_INVAL, "hssfsst_pack_recordings")
             with torch.cuda.stream(up):
                 stage_d[buf][:pos].copy_(stage_h[buf][:pos], non_blocking=True)
                 start_d[buf][:nf].copy_(start_h[buf][:nf], non_blocking=True)
+                if dev_labels:
+                    B["lab_d"][buf][:pos].copy_(B["lab_h"][buf][:pos], non_blocking=True)
                 up_done[buf].record(up)
             return pos, nf
 
@@ -226,7 +271,14 @@ class CorpusBuilder:
                 if gi >= 2:
                     main.wait_event(ring_free[buf])
                 dst = ring_d[buf][:nf]
-            fsst.frames(stage_d[buf][:pos], start_d[buf][:nf], frame_len, out=dst)
+            if rsm is None:
+                fsst.frames(stage_d[buf][:pos], start_d[buf][:nf], frame_len, out=dst)
+            else:
+                rs = B["rs_d"][:nf * out_len].view(nf, out_len)
+                rsm.frames(stage_d[buf][:pos], start_d[buf][:nf], frame_len, out=rs)
+                fsst.batch(rs, out=dst)
+                if dev_labels:
+                    rsm.frames(B["lab_d"][buf][:pos], start_d[buf][:nf], frame_len, labels=True, out=lab_d[row:row + nf])
             used[buf].record(main)
             if not keep_on_device:
                 down.wait_stream(main)
@@ -235,27 +287,31 @@ class CorpusBuilder:
                     ring_free[buf].record(down)
             if gi + 1 < len(groups):
                 sizes = pack(gi + 1)                     # host packing + upload of the next group overlap this transform
-            if labels is not None:                       # (host work, also overlapped)
+            if labels is not None and not dev_labels:    # (host work, also overlapped)
                 fill_labels(groups[gi][0], groups[gi][1], row)
             row += nf
         if not keep_on_device:
             down.synchronize()
         main.synchronize()
         fsst.check()
+        if dev_labels:
+            labels = lab_d.cpu()
         return FrameItems(feats, labels)
 
 
 def build_features(recordings: Iterable[Tuple[torch.Tensor, Optional[torch.Tensor]]], fsst,
                    stride: int = 1000, frame_len: int = 2000, device: Optional[torch.device] = None,
                    keep_on_device: bool = False, rank: Optional[int] = None,
-                   world: Optional[int] = None, windows_per_launch: int = 4096, pin_host: bool = True) -> FrameItems:
+                   world: Optional[int] = None, windows_per_launch: int = 4096, pin_host: bool = True,
+                   resample=None) -> FrameItems:
     """``recordings``: iterable of ``(x (T,) float32, y (T,) int64 labels in 1..4 or None)``.
     Returns what the reference dataset would hold in ``self.data`` (``in_memory=True, framing=True``);
     with ``world`` > 1 only the part of it that comes from this rank's block of recordings.
     ``keep_on_device=True`` leaves the features on the GPU (a GPU consumer follows: BASELINE config C4);
     otherwise they are returned in host memory (pinned when ``pin_host``), as the reference's CPU tensors.
+    ``resample=Resample(num)``: every frame is resampled to ``num`` samples before the transform (see the module notes).
     (One-shot form of ``CorpusBuilder``, which keeps its staging buffers between calls.)"""
-    return CorpusBuilder(fsst, stride, frame_len, device, windows_per_launch, pin_host).build(
+    return CorpusBuilder(fsst, stride, frame_len, device, windows_per_launch, pin_host, resample).build(
         recordings, keep_on_device=keep_on_device, rank=rank, world=world)
 
 

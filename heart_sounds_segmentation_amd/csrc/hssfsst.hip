@@ -32,6 +32,7 @@
 #include "fsst_dft.hpp"
 #include "fsst_gather.hpp"
 #include "fourier_resample.hpp"
+#include "fourier_resample_gpu.hpp"
 #include <cstdlib>
 
 namespace {
@@ -1861,6 +1862,266 @@ int hssfsst_moments_merge(hssfsst_plan* p, const float* feats, int64_t batch, in
     hipLaunchKernelGGL(hssfsst::fsst_moments_merge_kernel, dim3(static_cast<unsigned>(batch)), dim3(hssfsst::kMomThreads), 0,
                        static_cast<hipStream_t>(stream), feats, state, n, p->K);
     HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+}  // extern "C"
+
+// Device resampler (hssfsst.h: hssfsst_resample_plan_create): the chirps, the convolution kernels' spectra and the twiddle
+// table of one (n, num), made on the host in fp64 (csrc/fourier_resample_gpu.hpp), plus the staging of host buffers.
+struct hssfsst_resample_plan {
+    int device = -1;
+    int64_t n = 0, num = 0;
+    int M1 = 1, M2 = 1, Mt = 1;
+    double2* d_tab = nullptr;                            // c1[n] | B1[M1] | c2[num] | B2[M2] | tw[max(Mt / 2, 1)]
+    const double2 *c1 = nullptr, *B1 = nullptr, *c2 = nullptr, *B2 = nullptr, *tw = nullptr;
+    void* d_x = nullptr; size_t x_cap = 0;               // bytes: a host input, staged
+    void* d_y = nullptr; size_t y_cap = 0;               // bytes: a host output, staged
+    void* d_lab = nullptr; size_t lab_cap = 0;           // int64: host labels, staged
+    void* d_starts = nullptr; size_t starts_cap = 0;     // int64: host frame starts, staged
+    void* d_work = nullptr; size_t work_cap = 0;         // double2: the large tier's convolutions [chunk][max(M1, M2)]
+};
+
+namespace {
+
+constexpr int64_t kRsMaxLen = int64_t(1) << 26;          // n, num: convolutions of up to 2^27 points (2 GiB per signal)
+constexpr size_t kRsWorkBytes = size_t(256) << 20;       // large tier: signals per chunk bounded by this much scratch
+
+int pow2_at_least(int64_t v)
+{
+    int m = 1;
+    while (m < v) m <<= 1;
+    return m;
+}
+
+// chirp conj(w) and the bit-reversed spectrum / M of the wrapped chirp w, for a DFT of N points on M (sign: +1 forward)
+void bluestein_tables(int64_t N, int M, double sgn, hssfsst::resample_detail::cd* c, hssfsst::resample_detail::cd* B)
+{
+    using hssfsst::resample_detail::cd;
+    std::vector<cd> w(static_cast<size_t>(N)), b(static_cast<size_t>(M), cd(0.0, 0.0));
+    for (int64_t m = 0; m < N; ++m) {
+        const int64_t r = (m * m) % (2 * N);             // m^2 reduced mod 2N keeps the angle exact
+        const double ang = sgn * M_PI * static_cast<double>(r) / static_cast<double>(N);
+        w[static_cast<size_t>(m)] = cd(std::cos(ang), std::sin(ang));
+        c[m] = std::conj(w[static_cast<size_t>(m)]);
+    }
+    b[0] = w[0];
+    for (int64_t m = 1; m < N; ++m) b[static_cast<size_t>(m)] = b[static_cast<size_t>(M - m)] = w[static_cast<size_t>(m)];
+    hssfsst::resample_detail::fft_pow2(b, false);
+    int lg = 0;
+    while ((1 << lg) < M) ++lg;
+    for (int j = 0; j < M; ++j) {
+        int r = 0;
+        for (int k = 0; k < lg; ++k) r |= ((j >> k) & 1) << (lg - 1 - k);
+        B[j] = b[static_cast<size_t>(r)] / static_cast<double>(M);
+    }
+}
+
+int rs_launch_check(const char* what)
+{
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(HSSFSST_EHIP, "resample_exec: launch of %s failed: %s", what, hipGetErrorString(e));
+    return 0;
+}
+
+unsigned rs_grid(long long total) { return static_cast<unsigned>((total + hssfsst::kRsThreads - 1) / hssfsst::kRsThreads); }
+
+}  // namespace
+
+extern "C" {
+
+int hssfsst_resample_plan_create(hssfsst_resample_plan** out, int device, int64_t n, int64_t num)
+{
+    if (!out) return fail(HSSFSST_EINVAL, "resample_plan_create: out is NULL");
+    *out = nullptr;
+    if (n < 1 || num < 1 || device < 0)
+        return fail(HSSFSST_EINVAL, "resample_plan_create: bad argument (device=%d n=%lld num=%lld)", device, static_cast<long long>(n),
+                    static_cast<long long>(num));
+    if (n > kRsMaxLen || num > kRsMaxLen)
+        return fail(HSSFSST_EUNSUPPORTED, "resample_plan_create: lengths above %lld samples are not supported (n=%lld num=%lld)",
+                    static_cast<long long>(kRsMaxLen), static_cast<long long>(n), static_cast<long long>(num));
+    int ndev = 0;
+    hipError_t e = hipGetDeviceCount(&ndev);
+    if (e != hipSuccess || ndev <= 0) {
+        (void)hipGetLastError();
+        return fail(HSSFSST_ENODEVICE, "resample_plan_create: no HIP device (%s); this library has no CPU path",
+                    e == hipSuccess ? "device count 0" : hipGetErrorString(e));
+    }
+    if (device >= ndev) return fail(HSSFSST_EINVAL, "resample_plan_create: device %d out of range [0,%d)", device, ndev);
+    DEVICE_SCOPE(device);
+    using hssfsst::resample_detail::cd;
+    static_assert(sizeof(cd) == sizeof(double2), "std::complex<double> and double2 share a layout");
+    hssfsst_resample_plan* p = new (std::nothrow) hssfsst_resample_plan();
+    if (!p) return fail(HSSFSST_ENOMEM, "resample_plan_create: host allocation failed");
+    p->device = device; p->n = n; p->num = num;
+    p->M1 = pow2_at_least(2 * n - 1);
+    p->M2 = pow2_at_least(2 * num - 1);
+    p->Mt = p->M1 > p->M2 ? p->M1 : p->M2;
+    const size_t ntw = static_cast<size_t>(p->Mt > 1 ? p->Mt / 2 : 1);
+    const size_t o_B1 = static_cast<size_t>(n), o_c2 = o_B1 + p->M1, o_B2 = o_c2 + static_cast<size_t>(num), o_tw = o_B2 + p->M2;
+    const size_t total = o_tw + ntw;
+    try {
+        std::vector<cd> tab(total);
+        bluestein_tables(n, p->M1, 1.0, tab.data(), tab.data() + o_B1);
+        bluestein_tables(num, p->M2, -1.0, tab.data() + o_c2, tab.data() + o_B2);
+        for (size_t k = 0; k < ntw; ++k) {
+            const double ang = -2.0 * M_PI * static_cast<double>(k) / static_cast<double>(p->Mt);
+            tab[o_tw + k] = cd(std::cos(ang), std::sin(ang));
+        }
+        e = hipMalloc(reinterpret_cast<void**>(&p->d_tab), total * sizeof(double2));
+        if (e != hipSuccess) { p->d_tab = nullptr; delete p; return fail(HSSFSST_ENOMEM, "resample_plan_create: hipMalloc: %s", hipGetErrorString(e)); }
+        e = hipMemcpy(p->d_tab, tab.data(), total * sizeof(double2), hipMemcpyHostToDevice);
+        if (e != hipSuccess) { (void)hipFree(p->d_tab); delete p; return fail(HSSFSST_EHIP, "resample_plan_create: table upload: %s", hipGetErrorString(e)); }
+    } catch (const std::bad_alloc&) {
+        if (p->d_tab) (void)hipFree(p->d_tab);
+        delete p;
+        return fail(HSSFSST_ENOMEM, "resample_plan_create: out of host memory");
+    }
+    p->c1 = p->d_tab; p->B1 = p->d_tab + o_B1; p->c2 = p->d_tab + o_c2; p->B2 = p->d_tab + o_B2; p->tw = p->d_tab + o_tw;
+    *out = p;
+    return 0;
+}
+
+int hssfsst_resample_plan_destroy(hssfsst_resample_plan* p)
+{
+    if (!p) return 0;
+    DeviceGuard device_guard_(p->device);
+    for (void* d : {static_cast<void*>(p->d_tab), p->d_x, p->d_y, p->d_lab, p->d_starts, p->d_work})
+        if (d) (void)hipFree(d);
+    delete p;
+    return 0;
+}
+
+int hssfsst_resample_plan_info(const hssfsst_resample_plan* p, int64_t* n, int64_t* num, int* m1, int* m2, int* lds_tier, int* device)
+{
+    if (!p) return fail(HSSFSST_EINVAL, "resample_plan_info: plan is NULL");
+    if (n) *n = p->n;
+    if (num) *num = p->num;
+    if (m1) *m1 = p->M1;
+    if (m2) *m2 = p->M2;
+    if (lds_tier) *lds_tier = p->Mt <= hssfsst::kRsLdsMax ? 1 : 0;
+    if (device) *device = p->device;
+    return 0;
+}
+
+int hssfsst_resample_exec(hssfsst_resample_plan* p, const void* x, int x_dtype, int64_t x_len, int64_t x_stride,
+                          const int64_t* starts, int starts_on_device, int64_t batch, int x_on_device,
+                          void* y, int y_dtype, int64_t* labels, int out_on_device, void* stream)
+{
+    if (!p || !x || (!y && !labels) || batch < 0 || x_len < 1)
+        return fail(HSSFSST_EINVAL, "resample_exec: bad argument (batch=%lld x_len=%lld)", static_cast<long long>(batch),
+                    static_cast<long long>(x_len));
+    if ((x_dtype != HSSFSST_DTYPE_F32 && x_dtype != HSSFSST_DTYPE_F64) || (y && y_dtype != HSSFSST_DTYPE_F32 && y_dtype != HSSFSST_DTYPE_F64))
+        return fail(HSSFSST_EINVAL, "resample_exec: unknown dtype (x %d, y %d)", x_dtype, y_dtype);
+    if (batch > 0x7fffffffLL) return fail(HSSFSST_EINVAL, "resample_exec: batch %lld too large", static_cast<long long>(batch));
+    const int64_t n = p->n, num = p->num;
+    if (batch == 0) return 0;
+    if (!starts) {
+        if (batch > 1 && x_stride < 1) return fail(HSSFSST_EINVAL, "resample_exec: signal stride %lld < 1", static_cast<long long>(x_stride));
+        const int64_t span = (batch - 1) * (batch > 1 ? x_stride : 0) + n;
+        if (span > x_len)
+            return fail(HSSFSST_EINVAL, "resample_exec: %lld signals of %lld samples, stride %lld, need %lld samples, x holds %lld",
+                        static_cast<long long>(batch), static_cast<long long>(n), static_cast<long long>(x_stride),
+                        static_cast<long long>(span), static_cast<long long>(x_len));
+        if (!x_on_device) x_len = span;                  // (only that much is staged)
+    } else if (!starts_on_device) {
+        if (x_len < n) return fail(HSSFSST_EINVAL, "resample_exec: x holds %lld samples, a signal %lld", static_cast<long long>(x_len),
+                                   static_cast<long long>(n));
+        for (int64_t b = 0; b < batch; ++b)
+            if (starts[b] < 0 || starts[b] > x_len - n)
+                return fail(HSSFSST_EINVAL, "resample_exec: signal %lld starts at %lld, outside [0, %lld]", static_cast<long long>(b),
+                            static_cast<long long>(starts[b]), static_cast<long long>(x_len - n));
+    }
+    DEVICE_SCOPE(p->device);
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const size_t xsz = x_dtype == HSSFSST_DTYPE_F64 ? sizeof(double) : sizeof(float);
+    const size_t ysz = y_dtype == HSSFSST_DTYPE_F64 ? sizeof(double) : sizeof(float);
+    const size_t nout = static_cast<size_t>(batch) * static_cast<size_t>(num);
+    int rc;
+    hssfsst::ResampleArgs a{};
+    a.x = x;
+    if (!x_on_device) {
+        if ((rc = grow(&p->d_x, &p->x_cap, static_cast<size_t>(x_len) * xsz, 1)) != 0) return rc;
+        HIP_TRY(hipMemcpyAsync(p->d_x, x, static_cast<size_t>(x_len) * xsz, hipMemcpyHostToDevice, st));
+        a.x = p->d_x;
+    }
+    a.starts = reinterpret_cast<const long long*>(starts);
+    if (starts && !starts_on_device) {
+        if ((rc = grow(&p->d_starts, &p->starts_cap, static_cast<size_t>(batch), sizeof(long long))) != 0) return rc;
+        HIP_TRY(hipMemcpyAsync(p->d_starts, starts, static_cast<size_t>(batch) * sizeof(long long), hipMemcpyHostToDevice, st));
+        a.starts = static_cast<const long long*>(p->d_starts);
+    }
+    a.y = y;
+    a.labels = reinterpret_cast<long long*>(labels);
+    if (!out_on_device) {
+        if (y) {
+            if ((rc = grow(&p->d_y, &p->y_cap, nout * ysz, 1)) != 0) return rc;
+            a.y = p->d_y;
+        }
+        if (labels) {
+            if ((rc = grow(&p->d_lab, &p->lab_cap, nout, sizeof(long long))) != 0) return rc;
+            a.labels = static_cast<long long*>(p->d_lab);
+        }
+    }
+    a.x_stride = x_stride;
+    a.n = n; a.num = num;
+    const int64_t N = n < num ? n : num;
+    a.nyq = N / 2 + 1;
+    a.nyq_bin = (N % 2 == 0 && n != num) ? N / 2 : -1;
+    a.nyq_scale = num < n ? 2.0 : 0.5;
+    a.inv_n = 1.0 / static_cast<double>(n);
+    a.x_f64 = x_dtype == HSSFSST_DTYPE_F64; a.y_f64 = y_dtype == HSSFSST_DTYPE_F64; a.num_even = num % 2 == 0;
+    a.M1 = p->M1; a.M2 = p->M2; a.Mt = p->Mt;
+    a.c1 = p->c1; a.B1 = p->B1; a.c2 = p->c2; a.B2 = p->B2; a.tw = p->tw;
+    a.b0 = 0;
+    if (p->Mt <= hssfsst::kRsLdsMax) {
+        static std::atomic<unsigned long long> lds_ok{0};
+        if ((rc = allow_full_lds(hssfsst::resample_lds_kernel, p->device, lds_ok)) != 0) return rc;
+        hipLaunchKernelGGL(hssfsst::resample_lds_kernel, dim3(static_cast<unsigned>(batch)), dim3(hssfsst::kRsThreads),
+                           static_cast<size_t>(p->Mt) * sizeof(double2), st, a);
+        if ((rc = rs_launch_check("resample_lds_kernel")) != 0) return rc;
+    } else {
+        const long long Mw = p->Mt;
+        const long long per = static_cast<long long>(kRsWorkBytes / (static_cast<size_t>(Mw) * sizeof(double2)));
+        const long long chunk = per < 1 ? 1 : (per < batch ? per : batch);
+        if ((rc = grow(&p->d_work, &p->work_cap, static_cast<size_t>(chunk) * static_cast<size_t>(Mw), sizeof(double2))) != 0) return rc;
+        double2* work = static_cast<double2*>(p->d_work);
+        // one convolution of M points: global DIF stages down to the block length, the block kernel, global DIT stages back up
+        auto conv = [&](long long cb, int M, const double2* B) -> int {
+            const int S = M < hssfsst::kRsBlock ? M : hssfsst::kRsBlock;
+            const long long nb = cb * (M / 2);
+            for (int len = M; len > S; len >>= 1) {
+                hipLaunchKernelGGL(hssfsst::resample_dif_pass_kernel, dim3(rs_grid(nb)), dim3(hssfsst::kRsThreads), 0, st, work, Mw, M, len, p->tw, p->Mt, nb);
+                if (int r = rs_launch_check("resample_dif_pass_kernel")) return r;
+            }
+            hipLaunchKernelGGL(hssfsst::resample_block_kernel, dim3(static_cast<unsigned>(cb * (M / S))), dim3(hssfsst::kRsThreads), 0, st,
+                               work, Mw, M, S, B, p->tw, p->Mt);
+            if (int r = rs_launch_check("resample_block_kernel")) return r;
+            for (int len = 2 * S; len <= M; len <<= 1) {
+                hipLaunchKernelGGL(hssfsst::resample_dit_pass_kernel, dim3(rs_grid(nb)), dim3(hssfsst::kRsThreads), 0, st, work, Mw, M, len, p->tw, p->Mt, nb);
+                if (int r = rs_launch_check("resample_dit_pass_kernel")) return r;
+            }
+            return 0;
+        };
+        for (long long b0 = 0; b0 < batch; b0 += chunk) {
+            const long long cb = batch - b0 < chunk ? batch - b0 : chunk;
+            a.b0 = b0;
+            const long long t1 = cb * p->M1, t2 = cb * p->M2, t3 = cb * num;
+            hipLaunchKernelGGL(hssfsst::resample_load_kernel, dim3(rs_grid(t1)), dim3(hssfsst::kRsThreads), 0, st, a, work, Mw, t1);
+            if ((rc = rs_launch_check("resample_load_kernel")) != 0) return rc;
+            if ((rc = conv(cb, p->M1, p->B1)) != 0) return rc;
+            hipLaunchKernelGGL(hssfsst::resample_mid_kernel, dim3(rs_grid(t2)), dim3(hssfsst::kRsThreads), 0, st, a, work, Mw, t2);
+            if ((rc = rs_launch_check("resample_mid_kernel")) != 0) return rc;
+            if ((rc = conv(cb, p->M2, p->B2)) != 0) return rc;
+            hipLaunchKernelGGL(hssfsst::resample_store_kernel, dim3(rs_grid(t3)), dim3(hssfsst::kRsThreads), 0, st, a, work, Mw, t3);
+            if ((rc = rs_launch_check("resample_store_kernel")) != 0) return rc;
+        }
+    }
+    if (!out_on_device) {
+        if (y) HIP_TRY(hipMemcpyAsync(y, a.y, nout * ysz, hipMemcpyDeviceToHost, st));
+        if (labels) HIP_TRY(hipMemcpyAsync(labels, a.labels, nout * sizeof(long long), hipMemcpyDeviceToHost, st));
+    }
+    if (!out_on_device || !x_on_device) HIP_TRY(hipStreamSynchronize(st));
     return 0;
 }
 

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define HSSFSST_VERSION 208
+#define HSSFSST_VERSION 209
 
 /* status codes */
 #define HSSFSST_OK 0
@@ -241,6 +241,40 @@ int64_t hssfsst_pack_recordings(const float* const* ptrs, const int64_t* lens, i
  * scipy.signal.resample(x, num) for a real 1-D sequence (Fourier method, window=None): y[0..num) from x[0..n).
  * Used by the dataset for the label path (hss/datasets/heart_sounds.py:202-207: round(Resample(y)) - 1). */
 int hssfsst_resample(const double* x, int64_t n, int64_t num, double* y);
+
+/* Device counterpart of hssfsst_resample (Resample.__call__, hss/transforms/resample.py:13-21) for BATCHES of signals:
+ * scipy.signal.resample(x, num) for real x of n samples, computed in fp64 on the device whatever the input / output dtypes
+ * (Bluestein convolutions on power-of-two FFTs, csrc/fourier_resample_gpu.hpp).  A resample plan holds what depends only on
+ * (n, num): chirps, the convolution kernels' spectra, the twiddle table; it is single-stream and single-thread like the
+ * transform's plan.  n < 1, num < 1 or a NULL `out` give HSSFSST_EINVAL before any device is touched; lengths above 2^26
+ * samples HSSFSST_EUNSUPPORTED. */
+typedef struct hssfsst_resample_plan hssfsst_resample_plan;
+#define HSSFSST_DTYPE_F32 0
+#define HSSFSST_DTYPE_F64 1
+int hssfsst_resample_plan_create(hssfsst_resample_plan** out, int device, int64_t n, int64_t num);
+int hssfsst_resample_plan_destroy(hssfsst_resample_plan* plan);
+
+/* Plan geometry: the lengths, the two convolution lengths (powers of two >= 2n - 1 and >= 2num - 1) and the tier its execs
+ * take: lds_tier = 1 when both fit one workgroup's LDS (<= 8192 points: one launch per exec), 0 for the multi-pass tier
+ * through global scratch (whole recordings).  Any output pointer may be NULL. */
+int hssfsst_resample_plan_info(const hssfsst_resample_plan* plan, int64_t* n, int64_t* num, int* m1, int* m2, int* lds_tier,
+                               int* device);
+
+/* y[b][0 .. num) = resample(signal b) for `batch` signals of the plan's n samples, read from ONE buffer x of x_len samples
+ * (x_dtype HSSFSST_DTYPE_F32 / F64):
+ *   starts == NULL: signal b = x + b * x_stride (x_stride < n: overlapping frames of one recording, read in place, as
+ *                   hssfsst_exec_frames); (batch - 1) * x_stride + n <= x_len;
+ *   starts != NULL: signal b = x + starts[b] (as hssfsst_exec_list); 0 <= starts[b] <= x_len - n, checked when `starts` is host
+ *                   memory (starts_on_device = 0), trusted when it is device memory.
+ * y: [batch][num] of y_dtype (the fp64 result cast), or NULL.  labels: int64 [batch][num], or NULL: the dataset's label rule
+ * round(Resample(y)) - 1 (hss/datasets/heart_sounds.py:205-206), i.e. the fp64 result cast to float32, rounded half to even,
+ * minus 1.  At least one of y / labels.  x_on_device / out_on_device (for y and labels alike): 1 = device pointers on the plan's
+ * device, 0 = host pointers, staged through the plan's device buffers.  Enqueued on `stream` (hipStream_t, NULL = default)
+ * without synchronising when every buffer is on the device; with a host buffer the call returns when the results are in
+ * place. */
+int hssfsst_resample_exec(hssfsst_resample_plan* plan, const void* x, int x_dtype, int64_t x_len, int64_t x_stride,
+                          const int64_t* starts, int starts_on_device, int64_t batch, int x_on_device,
+                          void* y, int y_dtype, int64_t* labels, int out_on_device, void* stream);
 
 int hssfsst_device_count(void);
 int hssfsst_version(void);
