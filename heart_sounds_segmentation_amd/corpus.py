@@ -24,6 +24,12 @@ With ``resample=Resample(num)`` the builder is the reference's ``Compose([Resamp
 ``(num, 2K)`` features with ``(num,)`` labels ``round(Resample(frame of (y - 1))) - 1`` -- the reference's double shift kept --
 computed on the device from a second packed upload of the label tracks.
 
+Whole recordings (``build_recordings``): the reference's OTHER way to feed the model, ``DavidSpringerHSS(in_memory=False)``
+(heart_sounds.py:175-184,199-212) and ``PhysionetChallenge2016`` (:85-106), transform each whole recording in its own call.  Here a
+corpus of them is transformed in groups of at most ``max_samples`` samples, one ``hssfsst_exec_ragged`` call per group (signals of
+different lengths: one transform launch plus the z-score), uploads double-buffered as above.  Items are the lazy dataset's
+``(features (T, 2K) or (T, K), y unchanged or None)``: every recording, the short ones included, and no label shift.
+
 Multi-GPU (BASELINE config C3): ``rank`` / ``world`` split the RECORDINGS in contiguous
 blocks (``dist.shard_bounds``), so framing stays local to a rank and concatenating the ranks' item lists in rank
 order is the single-process list; ``gather_features`` reassembles the feature tensor on every rank with one
@@ -113,6 +119,114 @@ class CorpusBuilder:
         if need_ring and (max_frames * C > self._cap_ring or b["ring_d"][0].shape[1] != item_len):
             b["ring_d"] = [torch.empty((max_frames, item_len, C), dtype=torch.float32, device=dev) for _ in range(2)]
             self._cap_ring = max_frames * C
+
+    def build_recordings(self, recordings: Iterable[Tuple[torch.Tensor, Optional[torch.Tensor]]], keep_on_device: bool = False,
+                         max_samples: int = 1 << 25) -> "RecordingItems":
+        """See the module function ``build_recordings``."""
+        fsst, dev = self.fsst, self.dev
+        if self.resample is not None:
+            raise ValueError("CorpusBuilder.build_recordings: resample= is not supported for whole recordings (every recording length "
+                             "needs a resample plan of its own); resample the recordings first")
+        if not (getattr(fsst, "stack", False) or getattr(fsst, "abs", False)):
+            raise ValueError("CorpusBuilder.build_recordings: the transform must have stack=True or abs=True (time-major float32 "
+                             "features); for the raw complex transform call FSST.ragged")
+        if dev.type != "cuda":
+            raise ValueError("CorpusBuilder.build_recordings: the builder's device is not a HIP device")
+        recs: Sequence = recordings if isinstance(recordings, (list, tuple)) else list(recordings)
+        xs = []
+        for i, (x, _) in enumerate(recs):
+            t = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))
+            if t.ndim == 2 and t.shape[-1] == 1:
+                t = t[:, 0]
+            if t.ndim != 1 or t.shape[0] < 1:
+                raise ValueError(f"CorpusBuilder.build_recordings: recording {i} has shape {tuple(x.shape)}; expected (T,) or (T, 1), T >= 1")
+            xs.append(t)
+        ys = [y if (y is None or isinstance(y, torch.Tensor)) else torch.as_tensor(np.asarray(y)) for _, y in recs]
+        lens_np = np.asarray([int(t.shape[0]) for t in xs], dtype=np.int64)
+        total = int(lens_np.sum())
+        offsets = torch.from_numpy(np.concatenate([[0], np.cumsum(lens_np)]).astype(np.int64))
+        from .transforms.synchrosqueeze import RaggedFeatures
+        plan = fsst._plan(fsst._device_index(torch.empty(0, device=dev)))
+        C, K = plan.ofps, plan.K
+        if keep_on_device:
+            feats = torch.empty((total, C), dtype=torch.float32, device=dev)
+        else:
+            try:
+                feats = torch.empty((total, C), dtype=torch.float32, pin_memory=bool(self.pin_host and total > 0))
+            except RuntimeError:                          # page-locking that much memory can be refused: pageable then
+                feats = torch.empty((total, C), dtype=torch.float32)
+        items = RecordingItems(RaggedFeatures(feats, offsets, K, False), ys)
+        if total == 0:
+            return items
+        # groups of at most max_samples samples (a longer recording is a group of its own)
+        groups: List[Tuple[int, int]] = []
+        g0, acc = 0, 0
+        for i, T in enumerate(lens_np.tolist()):
+            if acc > 0 and acc + T > max_samples:
+                groups.append((g0, i))
+                g0, acc = i, 0
+            acc += T
+        groups.append((g0, len(xs)))
+        pos_np = np.concatenate([[0], np.cumsum(lens_np)])
+        max_group = max(int(pos_np[b] - pos_np[a]) for a, b in groups)
+        self._ensure(max_group, 0, C, False)
+        B = self._bufs
+        if not keep_on_device and (B.get("rec_ring") is None or B["rec_ring"][0].numel() < max_group * C):
+            B["rec_ring"] = [torch.empty(max_group * C, dtype=torch.float32, device=dev) for _ in range(2)]
+        main, up, down = torch.cuda.current_stream(dev), B["up"], B["down"]
+        stage_h, stage_d = B["stage_h"], B["stage_d"]
+        up_done, used, ring_free = B["up_done"], B["used"], B["ring_free"]
+        up.wait_stream(main)
+        from . import _lib
+        import ctypes
+        held = [t if (t.dtype == torch.float32 and t.is_contiguous() and not t.is_cuda) else t.detach().to("cpu", torch.float32).contiguous()
+                for t in xs]                               # (device recordings are staged through the host like the rest: rare)
+        ptrs_np = np.asarray([t.data_ptr() for t in held], dtype=np.uint64)
+        L = _lib.lib()
+        starts_np = np.empty(len(xs), dtype=np.int64)
+
+        def pack(gi: int) -> int:
+            """Host side of group gi: recordings back to back into pinned staging (one threaded native call); upload on `up`."""
+            a, b = groups[gi]
+            buf = gi & 1
+            if gi >= 2:
+                used[buf].synchronize()                  # the transform of group gi - 2 no longer reads this staging buffer
+            n = int(pos_np[b] - pos_np[a])
+            got = L.hssfsst_pack_recordings(ctypes.c_void_p(ptrs_np[a:b].ctypes.data), ctypes.c_void_p(lens_np[a:b].ctypes.data), b - a,
+                                            0x7fffffff, 1, ctypes.c_void_p(stage_h[buf].data_ptr()), int(stage_h[buf].numel()),
+                                            ctypes.c_void_p(starts_np[a:b].ctypes.data), b - a, 0)
+            if got != b - a:
+                _lib.check(int(got) if got < 0 else _lib.E_INVAL, "hssfsst_pack_recordings")
+            with torch.cuda.stream(up):
+                stage_d[buf][:n].copy_(stage_h[buf][:n], non_blocking=True)
+                up_done[buf].record(up)
+            return n
+
+        n = pack(0)
+        for gi, (a, b) in enumerate(groups):
+            buf = gi & 1
+            r0, r1 = int(pos_np[a]), int(pos_np[b])
+            main.wait_event(up_done[buf])
+            if keep_on_device:
+                dst = feats[r0:r1]
+            else:
+                if gi >= 2:
+                    main.wait_event(ring_free[buf])
+                dst = B["rec_ring"][buf][:n * C].view(n, C)
+            fsst.ragged(stage_d[buf][:n], lengths=lens_np[a:b], out=dst)
+            used[buf].record(main)
+            if not keep_on_device:
+                down.wait_stream(main)
+                with torch.cuda.stream(down):
+                    feats[r0:r1].copy_(dst, non_blocking=True)
+                    ring_free[buf].record(down)
+            if gi + 1 < len(groups):
+                n = pack(gi + 1)                         # host packing + upload of the next group overlap this transform
+        if not keep_on_device:
+            down.synchronize()
+        main.synchronize()
+        fsst.check()
+        return items
 
     def build(self, recordings: Iterable[Tuple[torch.Tensor, Optional[torch.Tensor]]], keep_on_device: bool = False,
               rank: Optional[int] = None, world: Optional[int] = None, out: Optional[torch.Tensor] = None) -> FrameItems:
@@ -313,6 +427,42 @@ def build_features(recordings: Iterable[Tuple[torch.Tensor, Optional[torch.Tenso
     (One-shot form of ``CorpusBuilder``, which keeps its staging buffers between calls.)"""
     return CorpusBuilder(fsst, stride, frame_len, device, windows_per_launch, pin_host, resample).build(
         recordings, keep_on_device=keep_on_device, rank=rank, world=world)
+
+
+class RecordingItems(_SequenceABC):
+    """The lazy dataset's items for a whole corpus -- ``[ds[i] for i in range(len(ds))]`` of
+    ``DavidSpringerHSS(in_memory=False, transform=Compose([FSST(...)]))`` (heart_sounds.py:175-184) -- as views of one feature arena:
+    item i is ``(features (T_i, C), labels_i)`` with the recording's labels as given (or None)."""
+
+    def __init__(self, features, labels: List[Optional[torch.Tensor]]):
+        self.features = features                          # RaggedFeatures: arena (sum T_i, C), offsets
+        self.labels = labels
+
+    def __len__(self) -> int:
+        return len(self.labels)
+
+    def __getitem__(self, i):
+        if isinstance(i, slice):
+            return [self[j] for j in range(*i.indices(len(self)))]
+        if i < 0:
+            i += len(self)
+        if not 0 <= i < len(self):
+            raise IndexError(i)
+        return self.features[i], self.labels[i]
+
+
+def build_recordings(recordings: Iterable[Tuple[torch.Tensor, Optional[torch.Tensor]]], fsst, device: Optional[torch.device] = None,
+                     keep_on_device: bool = False, pin_host: bool = True, max_samples: int = 1 << 25, resample=None) -> RecordingItems:
+    """``recordings``: iterable of ``(x (T,) float32, y (T,) labels or None)``, any lengths.  Returns what the reference's lazy
+    dataset (``in_memory=False``) hands out item by item: ``(fsst(x), y)`` for EVERY recording (no ``frame_len`` skip, labels
+    unchanged -- no ``- 1``), as views of one arena on the device (``keep_on_device``) or in (pinned) host memory.  ``fsst`` must
+    have ``stack=True`` or ``abs=True``.  Groups of at most ``max_samples`` samples go through one ``FSST.ragged`` call each.
+    ``resample=`` is refused: every recording length would need a resample plan of its own."""
+    if resample is not None:
+        raise ValueError("build_recordings: resample= is not supported for whole recordings (every recording length needs a "
+                         "resample plan of its own); resample the recordings first")
+    return CorpusBuilder(fsst, device=device, pin_host=pin_host).build_recordings(recordings, keep_on_device=keep_on_device,
+                                                                                 max_samples=max_samples)
 
 
 def gather_features(items, group=None, out_device: Optional[torch.device] = None) -> torch.Tensor:

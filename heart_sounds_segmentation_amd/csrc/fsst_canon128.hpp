@@ -639,6 +639,9 @@ struct CanonParams {
     unsigned* status;     // FUSED: device status word
     const unsigned* gate; // non-null: this launch is the fallback of a team-kernel exec: it runs only if *gate == gate_val
     unsigned gate_val;
+    const RaggedSignal* rsig;   // RAGGED only: as Core128Params
+    const int2* rchunk;
+    int rnchunks;
 };
 
 constexpr int kCanonCtlFloats = 16 + 192;                            // [0] work counter, [16..207] wide-store offsets
@@ -664,16 +667,18 @@ __device__ __forceinline__ void canon_fetch(const float* xsig, int n, int t0, in
 __device__ unsigned long long g_fuse_probe[8];      // [0] A tickets [1] cycles in A [2] B tickets [3] B: wait for statistics
                                                     // [4] B: loads issued -> data there [5] B: arithmetic + stores issued [6] resolver
 #endif
-template <int KLO, int KC, bool FUSED>
+// RAGGED (hssfsst_exec_ragged): signals of different lengths, chunk list from the host -- as fsst_core128_kernel<.., RAGGED>.
+template <int KLO, int KC, bool FUSED, bool RAGGED = false>
 __global__ __launch_bounds__(64 * 16, HSS_MW128) void fsst_canon_kernel(CanonParams p)
 {
+    static_assert(!(RAGGED && FUSED), "ragged lists: the two-launch kernel");
     using C = CanonCfg<KLO, KC>;
     constexpr int WPB = 16, K = KC, GPCF = kCanonTileFrames / 16;
     constexpr int ATAB = kCanonLdsTabFloats;
     constexpr int CTL = FUSED ? kCanonCtlFusedFloats : kCanonCtlFloats;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     if (p.gate != nullptr && *p.gate != p.gate_val) return;          // (uniform: the team kernel this launch backs up did not give up)
-    const int n = p.n;
+    int n = p.n;                                         // (RAGGED: per chunk, as ncols, cend, ngroups)
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     float* atab = smem;
@@ -692,7 +697,7 @@ __global__ __launch_bounds__(64 * 16, HSS_MW128) void fsst_canon_kernel(CanonPar
     int* tq = flag + kCanonFlagWords;
 
     for (int i = threadIdx.x; i < ATAB; i += 64 * WPB) atab[i] = p.atab[i];
-    const int ncols = p.ncols, cend = p.col0 + p.ncols;
+    int ncols = p.ncols, cend = p.col0 + p.ncols;
     if (lane < kCanonFlagWords) flag[lane] = 0;
     if (lane < kCanonTieWords) tq[lane] = 0;
     if (threadIdx.x < (FUSED ? 8 : 1)) next_q[threadIdx.x] = 0;
@@ -712,11 +717,11 @@ __global__ __launch_bounds__(64 * 16, HSS_MW128) void fsst_canon_kernel(CanonPar
     const int nc0 = p.nsig * p.reg.npc[0];
     const int nc1 = nc0 + p.nsig * p.reg.npc[1];
     const int nchunks = nc1 + p.nsig * p.reg.npc[2];
-    const int ngroups = (ncols + 15) >> 4;
+    int ngroups = (ncols + 15) >> 4;
     const int nk = (FUSED && p.nsig > static_cast<int>(blockIdx.x)) ? (p.nsig - static_cast<int>(blockIdx.x) + static_cast<int>(gridDim.x) - 1) / static_cast<int>(gridDim.x) : 0;
     const int NC = (ngroups + GPCF - 1) / GPCF;
     const int lead = min(8, NC);
-    const int nwork = FUSED ? 2 * NC * nk : nchunks;
+    const int nwork = FUSED ? 2 * NC * nk : RAGGED ? p.rnchunks : nchunks;
     auto draw = [&]() -> int {
         int q = 0;
         if (lane == 0) q = __hip_atomic_fetch_add(next_q, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -740,6 +745,7 @@ __global__ __launch_bounds__(64 * 16, HSS_MW128) void fsst_canon_kernel(CanonPar
     int grp0, ngrp;
     long long ksig = 0;
     bool zpass = false;
+    long long rxo = 0, roo = 0, rpo = 0;                 // RAGGED: the chunk's signal in the packed input, output, partials
     if constexpr (FUSED) {
         int c;
         if (chunk < NC) {
@@ -760,6 +766,14 @@ __global__ __launch_bounds__(64 * 16, HSS_MW128) void fsst_canon_kernel(CanonPar
         b = static_cast<long long>(blockIdx.x) + ksig * gridDim.x;
         grp0 = c * GPCF;
         ngrp = min(GPCF, ngroups - grp0);
+    } else if constexpr (RAGGED) {
+        const int2 cd = p.rchunk[chunk];
+        const RaggedSignal* rs = p.rsig + cd.x;
+        rxo = rs->xoff; roo = rs->ooff; rpo = rs->poff;
+        n = rs->n; ncols = n; cend = n; ngroups = (n + 15) >> 4;
+        b = 0;
+        grp0 = cd.y & ((1 << kRaggedGroupBits) - 1);
+        ngrp = (cd.y >> kRaggedGroupBits) + 1;
     } else {
         const int rg = (chunk < nc0) ? 0 : (chunk < nc1) ? 1 : 2;
         const int local = chunk - ((rg == 0) ? 0 : (rg == 1) ? nc0 : nc1);
@@ -841,10 +855,10 @@ __global__ __launch_bounds__(64 * 16, HSS_MW128) void fsst_canon_kernel(CanonPar
 #endif
         }
     } else {
-    const float* xsig = p.x + b * p.xstride;
+    const float* xsig = RAGGED ? p.x + rxo : p.x + b * p.xstride;
     // per-signal bases once per ticket (uniform): the group loop then adds 32-bit offsets (was: a 64-bit multiply per group)
-    float* out_sig = p.out + b * static_cast<long long>(ncols) * (2 * K);
-    float* part_sig = FUSED ? nullptr : p.partials + b * static_cast<long long>(ngroups) * kPartFloats;
+    float* out_sig = RAGGED ? p.out + roo : p.out + b * static_cast<long long>(ncols) * (2 * K);
+    float* part_sig = FUSED ? nullptr : RAGGED ? p.partials + rpo : p.partials + b * static_cast<long long>(ngroups) * kPartFloats;
     const int cg0 = p.col0 >> 4;                         // (the host sends only column ranges that start on a group boundary)
     for (int gcur = grp0; gcur < grp0 + ngrp;) {
         // the ALIGNED tile of the signal that holds group gcur: aligned in absolute columns, so that a column-range exec

@@ -27,7 +27,9 @@
 // is the same as in fsst_kernels.hpp and follows oracle/fsst_oracle.c steps 4-7.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <cstdlib>
+#include <vector>
 
 #include "fsst_kernels.hpp"
 
@@ -58,6 +60,14 @@ struct Core128Regions {
     int npc[3];           // chunks per signal
 };
 
+// One signal of a ragged exec: its samples at x + xoff (n of them), its features at out + ooff (n x floats-per-sample in the
+// mode's layout), its statistics partials at partials + poff ((n + 15) / 16 of them).  Every column of it is an output column.
+struct RaggedSignal {
+    long long xoff, ooff, poff;
+    int n, pad;
+};
+constexpr int kRaggedGroupBits = 24;         // groups of a signal below 2^24 (n < 2^28: the host allows n * 2 nf < 2^31)
+
 struct Core128Params {
     const float* x;       // [batch][n]
     float* out;
@@ -85,7 +95,13 @@ struct Core128Params {
     unsigned* arrive;         // [nsig] blocks of the channel that have delivered (the last one merges and normalises, and clears it)
     double* pieces;           // [nsig][groups][4] the groups' float64 sums (chunk_moments' pieces, fsst_kernels.hpp)
     float* mirror;            // the caller's pinned host buffer for the step's features (device view), or null
+    // RAGGED kernel only (hssfsst_exec_ragged): signals of different lengths; x / out / partials are the bases of the packed
+    // input, output and partials, the chunk list is made on the host (core128_ragged_chunks)
+    const RaggedSignal* rsig;     // [nsig] per-signal extents
+    const int2* rchunk;                // [rnchunks] {signal, first group | (groups - 1) << 24}
+    int rnchunks;
 };
+
 
 // Chunk pattern for `ngroups` 16-frame groups per signal: 8-group chunks, then 4-group chunks over the last
 // quarter or so, then 2-group chunks at the very end (each chunk costs a counter draw, a tile staging and a
@@ -126,6 +142,25 @@ inline Core128Regions core128_regions(int ngroups, long long nsig = -1)
     return r;
 }
 __host__ __device__ inline int core128_chunks_per_signal(const Core128Regions& r) { return r.npc[0] + r.npc[1] + r.npc[2]; }
+
+// Chunk list of a ragged exec: each signal cut as core128_regions(its groups, 1) cuts it alone, and the list ordered by region
+// across signals -- every 8-group chunk first, then the 4-group ones, then the 2- / 1-group ones -- so the small chunks stay in
+// the tail as in a dense launch.  Entry {signal, first group | (groups - 1) << kRaggedGroupBits}.
+inline void core128_ragged_chunks(const int* ngroups, long long nsig, std::vector<int2>& out)
+{
+    out.clear();
+    std::vector<Core128Regions> regs(static_cast<size_t>(nsig));
+    for (long long s = 0; s < nsig; ++s) regs[s] = core128_regions(ngroups[s], 1);
+    for (int rg = 0; rg < 3; ++rg)
+        for (long long s = 0; s < nsig; ++s) {
+            const Core128Regions& r = regs[s];
+            for (int c = 0; c < r.npc[rg]; ++c) {
+                const int g0 = r.g0[rg] + c * r.gpc[rg];
+                const int ng = std::min(r.gpc[rg], ngroups[s] - g0);
+                out.push_back(make_int2(static_cast<int>(s), g0 | ((ng - 1) << kRaggedGroupBits)));
+            }
+        }
+}
 
 
 // cos / sin of 2*pi*j/16, j = 0..7
@@ -885,11 +920,16 @@ __device__ unsigned long long g_stream_probe[kStreamProbeWaves * 8];      // [wa
 constexpr unsigned kPairSpinLimit = 1u << 24;       // looks at the partner's phase word before a pair's wait ends on its own (~1 s)
 constexpr int kPairFloats = 4 + 64 + 3 * 256;  // [0..1] phase words, [2] the pair's ticket, [3] the odd wave's list count, [4..67] its per-lane
                                              // max |V|^2, then its list of additions (PairList: 256 cells, 256 values)
-template <int NT, int RQ, int FPW, bool FAST, int WPB, int S1C, bool FUSED = false, bool STREAM = false, bool PAIR = false>
+// RAGGED (hssfsst_exec_ragged: signals of different lengths in one launch): a chunk's signal, first group and groups come from
+// the host-made list p.rchunk, and the signal's length, input, output and partials from p.rsig; everything else -- staging,
+// transform, ties, epilogue -- is the plain kernel's, on that signal alone (reads past its own length see zeros).
+template <int NT, int RQ, int FPW, bool FAST, int WPB, int S1C, bool FUSED = false, bool STREAM = false, bool PAIR = false,
+          bool RAGGED = false>
 __global__ __launch_bounds__(64 * WPB, (NT == 32 ? 2 : WPB == 16 ? HSS_MW128 : WPB == 12 ? 3 : 2)) void fsst_core128_kernel(Core128Params p)
 {
     static_assert(!STREAM || (FAST && !FUSED), "the streaming step: wide-store epilogue, no per-signal z-score");
     static_assert(!PAIR || (RQ == 16 && !FUSED && WPB % 2 == 0), "wave pairs: two passes, whole pairs");
+    static_assert(!RAGGED || (!FUSED && !STREAM), "ragged lists: the plain kernel");
     // (FUSED && !FAST: the general epilogue's STACK mode -- any K, nwin 256 / 512 -- with the linear z-score sweep of
     //  fsst_normalize_kernel as the B ticket; the host sends only STACK execs whose signal blocks are 16-byte aligned)
     constexpr int NWIN = NT * RQ, NPASS = RQ / 8, KST = RQ / 4;
@@ -900,7 +940,8 @@ __global__ __launch_bounds__(64 * WPB, (NT == 32 ? 2 : WPB == 16 ? HSS_MW128 : W
     constexpr int XS = ((FPW + NWIN - 1 + 3) / 4) * 4;
     using avec = float __attribute__((ext_vector_type(KST)));          // one tap's A operand, all k-steps
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int K = p.K, klo = p.klo, n = p.n;
+    const int K = p.K, klo = p.klo;
+    int n = p.n;                                         // (RAGGED: per chunk, as ncols, cend, ngroups)
     const int LDF = plane_ldf(K);
     const int OLD = own_ld(klo, K, RQ);
     const int s0 = (S1C >= 0) ? 0 : own_s0(klo, RQ), s1 = (S1C >= 0) ? S1C : own_s1(klo, K, RQ);
@@ -990,7 +1031,7 @@ __global__ __launch_bounds__(64 * WPB, (NT == 32 ? 2 : WPB == 16 ? HSS_MW128 : W
         for (int i = threadIdx.x; i < ATAB / 4; i += 64 * WPB)
             reinterpret_cast<float4*>(atab)[i] = reinterpret_cast<const float4*>(p.atab)[i];
     }
-    const int ncols = p.ncols, cend = p.col0 + p.ncols;   // output rows are relative to col0
+    int ncols = p.ncols, cend = p.col0 + p.ncols;         // output rows are relative to col0
     for (int i = lane; i < 16 * LDF; i += 64) disp_base[i] = f2{0.0f, 0.0f};
     if (lane < 4) flag[lane] = 0;
     for (int i = lane; i < tie_words(NWIN); i += 64) tq[i] = 0;
@@ -1026,7 +1067,7 @@ __global__ __launch_bounds__(64 * WPB, (NT == 32 ? 2 : WPB == 16 ? HSS_MW128 : W
     const int nc0 = p.nsig * p.reg.npc[0];               // (the host keeps nsig * chunks per signal below 2^31)
     const int nc1 = nc0 + p.nsig * p.reg.npc[1];
     const int nchunks = nc1 + p.nsig * p.reg.npc[2];
-    const int ngroups = (ncols + 15) >> 4;
+    int ngroups = (ncols + 15) >> 4;
     // FUSED work list of this block (wave-uniform): signals blockIdx, blockIdx + grid, ... (nk of them), each cut into
     // NC chunks of FPW / 16 groups; see "Fused z-score" below for the order of the 2 NC nk tickets
     constexpr int GPCF = FPW / 16;
@@ -1035,7 +1076,7 @@ __global__ __launch_bounds__(64 * WPB, (NT == 32 ? 2 : WPB == 16 ? HSS_MW128 : W
     const int lead = min(8, NC);
     const int st_ch = STREAM ? static_cast<int>(blockIdx.x) / p.bpc : 0;              // STREAM: this block's channel and
     const int st_part = STREAM ? static_cast<int>(blockIdx.x) - st_ch * p.bpc : 0;    // its first group
-    const int nwork = STREAM ? (st_part < ngroups ? (ngroups - st_part + p.bpc - 1) / p.bpc : 0) : FUSED ? 2 * NC * nk : nchunks;
+    const int nwork = STREAM ? (st_part < ngroups ? (ngroups - st_part + p.bpc - 1) / p.bpc : 0) : FUSED ? 2 * NC * nk : RAGGED ? p.rnchunks : nchunks;
     auto draw = [&]() -> int {                           // next work item of this block, or nwork when none is left
         int q = 0;
         if (lane == 0) q = __hip_atomic_fetch_add(next_q, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -1051,6 +1092,9 @@ __global__ __launch_bounds__(64 * WPB, (NT == 32 ? 2 : WPB == 16 ? HSS_MW128 : W
         pair_sync();
         return __builtin_amdgcn_readfirstlane(pw[2]);
     };
+    const float* const rx = p.x;                         // RAGGED: the packed buffers (p.x / out / partials move to a chunk's signal)
+    float* const rout = p.out;
+    float* const rpart = p.partials;
     int chunk = draw_pair();
     bool first_tile = STREAM;                            // STREAM: the first ticket's samples are in `pre`
     const float* myA = atab + lane * KST;
@@ -1110,6 +1154,16 @@ __global__ __launch_bounds__(64 * WPB, (NT == 32 ? 2 : WPB == 16 ? HSS_MW128 : W
         ngrp = min(GPCF, ngroups - grp0);
     } else if constexpr (STREAM) {
         b = st_ch; grp0 = st_part + chunk * p.bpc; ngrp = 1;
+    } else if constexpr (RAGGED) {
+        // the chunk's signal becomes "signal 0" of a launch of its own: bases moved to it, its length as n and columns
+        const int2 cd = p.rchunk[chunk];
+        const RaggedSignal* rs = p.rsig + cd.x;
+        const long long xoff = rs->xoff, ooff = rs->ooff, poff = rs->poff;
+        n = rs->n; ncols = n; cend = n; ngroups = (n + 15) >> 4;
+        p.x = rx + xoff; p.out = rout + ooff; p.partials = rpart + poff;
+        b = 0;
+        grp0 = cd.y & ((1 << kRaggedGroupBits) - 1);
+        ngrp = (cd.y >> kRaggedGroupBits) + 1;
     } else {
         const int rg = (chunk < nc0) ? 0 : (chunk < nc1) ? 1 : 2;
         const int local = chunk - ((rg == 0) ? 0 : (rg == 1) ? nc0 : nc1);

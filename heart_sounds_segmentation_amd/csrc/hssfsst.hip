@@ -31,6 +31,7 @@
 #endif
 #include "fsst_dft.hpp"
 #include "fsst_gather.hpp"
+#include "fsst_ragged.hpp"
 #include "fourier_resample.hpp"
 #include "fourier_resample_gpu.hpp"
 #include <cstdlib>
@@ -255,6 +256,7 @@ struct hssfsst_plan {
     int zpath_pref = 0;                                      // HSSFSST_ZPATH_*: preference among the z-score paths
     int last_zpath = 0;                                      // ... which one: 1 = one CU per signal, 2 = team kernel
     int core128_slots = 0;                    // resident blocks of the core kernel on this device (0 = not queried yet)
+    int ragged_slots = 0;                     // the same for its ragged instantiation
     int stream_slots = 0;                     // the same for the streaming-step kernel
     unsigned* d_stream_arrive = nullptr; int stream_arrive_cap = 0;   // streaming step: blocks delivered per channel
     double* d_stream_pieces = nullptr; long long stream_pieces_cap = 0;   // and the groups' float64 sums [channels][groups][4]
@@ -272,6 +274,14 @@ struct hssfsst_plan {
     unsigned deferred_launch = 0, deferred_first = 0;        // the host looks at the pinned give-up word afterwards and redoes the exec itself
     long long* d_starts = nullptr; size_t starts_cap = 0;    // frame-list staging (hssfsst_exec_list with host starts)
     float* d_frames = nullptr;    size_t frames_cap = 0;     // frames gathered from a list, dense [batch][n]
+    // hssfsst_exec_ragged: the list's tables -- RaggedSignal[batch], z-score unit starts int[batch + 1], chunk list int2[] -- made
+    // on the host (h_rtab, pinned) and uploaded in one copy to d_rtab; kept while the next list has the same lengths and offsets (rkey)
+    void* d_rtab = nullptr;       size_t rtab_cap = 0;       // bytes
+    unsigned char* h_rtab = nullptr; size_t h_rtab_cap = 0, rtab_bytes = 0;
+    std::vector<long long> rkey;
+    size_t rtab_unit = 0, rtab_chunk = 0;                    // byte offsets of the unit starts and of the chunk list in the tables
+    long long rtab_nchunks = 0, rtab_nunits = 0;
+    hipEvent_t rtab_ev = nullptr;                            // the last upload of h_rtab (h_rtab is not rewritten before it is done)
     int timing = 0;               // the exec being queued records kernel events
     int timing_every = 0;         // hssfsst_plan_set_timing(n): every n-th exec is timed (0: off)
     unsigned timing_seq = 0;
@@ -346,27 +356,29 @@ inline size_t core128_lds_bytes(const hssfsst_plan* pl, int rq, int nt, int wpb,
 }
 
 int ensure_status(hssfsst_plan* pl);
-template <int NT, int RQ, bool FAST, int WPB, int S1C = -1, bool PAIR = false>
+template <int NT, int RQ, bool FAST, int WPB, int S1C = -1, bool PAIR = false, bool RAGGED = false>
 int launch_core128_wpb(hssfsst_plan* pl, const hssfsst::Core128Params& cp, int64_t nchunks, hipStream_t st)
 {
     size_t lds = core128_lds_bytes(pl, RQ, NT, WPB, PAIR);
 #ifdef HSS_LDS_PAD                                       // development: one block per CU whatever its size
     if (lds < 100 * 1024) lds = 100 * 1024;
 #endif
-    auto kern = hssfsst::fsst_core128_kernel<NT, RQ, kFpw128, FAST, WPB, S1C, false, false, PAIR>;
+    auto kern = hssfsst::fsst_core128_kernel<NT, RQ, kFpw128, FAST, WPB, S1C, false, false, PAIR, RAGGED>;
     static std::atomic<unsigned long long> lds_ok{0};
     if (int rc = allow_full_lds(kern, pl->device, lds_ok)) return rc;
-    if (pl->core128_slots == 0) {                        // persistent grid = what is resident at once
+    int& slots = RAGGED ? pl->ragged_slots : pl->core128_slots;
+    if (slots == 0) {                                    // persistent grid = what is resident at once
         int per_cu = 0, cus = 0;
         HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kern), 64 * WPB, lds));
         HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, pl->device));
         if (per_cu < 1) per_cu = 1;
         if (cus < 1) cus = 1;
-        pl->core128_slots = per_cu * cus;
+        slots = per_cu * cus;
     }
     int64_t blocks = nchunks;                            // small launches: one chunk per block, spread over the CUs
-    if (blocks > pl->core128_slots) blocks = pl->core128_slots;
-    name_kernel(pl, WPB, blocks, "fsst_core128_kernel<%d, %d, %d, %s, %d, %d, false%s>", NT, RQ, kFpw128, FAST ? "true" : "false", WPB, S1C, PAIR ? ", pairs" : "");
+    if (blocks > slots) blocks = slots;
+    name_kernel(pl, WPB, blocks, "fsst_core128_kernel<%d, %d, %d, %s, %d, %d, false%s%s>", NT, RQ, kFpw128, FAST ? "true" : "false", WPB, S1C,
+                PAIR ? ", pairs" : "", RAGGED ? ", ragged" : "");
     if constexpr (PAIR) {                                // (a pair's bounded wait reports through the status word)
         if (int rcs = ensure_status(pl)) return rcs;
         hssfsst::Core128Params cq = cp;
@@ -676,15 +688,30 @@ hssfsst::CanonParams canon_params(const hssfsst_plan* pl, const hssfsst::Core128
     return q;
 }
 
-template <int KLO, int KC>
+template <int KLO, int KC, bool RAGGED = false>
 int launch_canon_band(hssfsst_plan* pl, const hssfsst::Core128Params& cp, int64_t nchunks, hipStream_t st)
 {
     constexpr int WPB = 16;
     const size_t lds = (hssfsst::kCanonLdsTabFloats + hssfsst::kCanonCtlFloats + static_cast<size_t>(WPB) * hssfsst::CanonCfg<KLO, KC>::wave_floats()) * sizeof(float);
     static_assert((hssfsst::kCanonLdsTabFloats + hssfsst::kCanonCtlFloats + 16 * hssfsst::CanonCfg<KLO, KC>::wave_floats()) * sizeof(float) <= 160 * 1024, "16 wave regions must fit");
-    auto kern = hssfsst::fsst_canon_kernel<KLO, KC, false>;
+    auto kern = hssfsst::fsst_canon_kernel<KLO, KC, false, RAGGED>;
     static std::atomic<unsigned long long> lds_ok{0};
     if (int rc = allow_full_lds(kern, pl->device, lds_ok)) return rc;
+    if constexpr (RAGGED) {
+        int per_cu = 0, cus = 0;
+        if (pl->ragged_slots == 0) {
+            HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kern), 64 * WPB, lds));
+            HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, pl->device));
+            pl->ragged_slots = (per_cu < 1 ? 1 : per_cu) * (cus < 1 ? 1 : cus);
+        }
+        const int64_t blocks = nchunks < pl->ragged_slots ? nchunks : pl->ragged_slots;
+        name_kernel(pl, WPB, blocks, "fsst_canon_kernel<%d, %d, false, ragged>", KLO, KC);
+        hssfsst::CanonParams q = canon_params(pl, cp);
+        q.rsig = cp.rsig; q.rchunk = cp.rchunk; q.rnchunks = cp.rnchunks;
+        hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(blocks)), dim3(64 * WPB), lds, st, q);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    }
     if (pl->canon_slots == 0) {
         int per_cu = 0, cus = 0;
         HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kern), 64 * WPB, lds));
@@ -766,6 +793,54 @@ int plan_next_event(hssfsst_plan* p, hipEvent_t* out_ev)
     }
     *out_ev = p->ev[p->ev_used++];
     return 0;
+}
+
+// The plain (two-launch) core kernel for a plan of the MFMA kernel: as many waves per block as fit the 160 KiB of LDS beside
+// the shared tables.  RAGGED: the instantiations of hssfsst_exec_ragged (the same ladder, chunk list from the host).
+template <bool RAGGED>
+int launch_core128_plain(hssfsst_plan* pl, const hssfsst::Core128Params& cp, int64_t nchunks, hipStream_t st, bool fast, bool canon)
+{
+    const int rq = pl->rq, nt = pl->nt;
+    const size_t fixed = (hssfsst::core128_atab_floats(rq, nt) + hssfsst::kCtlFloats) * sizeof(float);
+    const size_t per_wave = static_cast<size_t>(hssfsst::wave_lds_floats(kFpw128, pl->klo, pl->K, rq, nt)) * sizeof(float);
+    const size_t room = 160 * 1024;
+    if (nt == 16 && rq == 8) {
+#ifdef HSS_WPB_CANON
+        if (fast && canon) return launch_core128_wpb<16, 8, true, HSS_WPB_CANON, 3, false, RAGGED>(pl, cp, nchunks, st);
+#endif
+        if (fast && canon) return launch_core128_wpb<16, 8, true, 16, 3, false, RAGGED>(pl, cp, nchunks, st);
+        if (fast) return launch_core128_wpb<16, 8, true, 16, -1, false, RAGGED>(pl, cp, nchunks, st);   // K <= 24: 16 regions always fit
+        if (fixed + 16 * per_wave <= room) return launch_core128_wpb<16, 8, false, 16, -1, false, RAGGED>(pl, cp, nchunks, st);
+        if (fixed + 8 * per_wave <= room) return launch_core128_wpb<16, 8, false, 8, -1, false, RAGGED>(pl, cp, nchunks, st);
+        if (fixed + 4 * per_wave <= room) return launch_core128_wpb<16, 8, false, 4, -1, false, RAGGED>(pl, cp, nchunks, st);
+#ifndef HSS_DEV_ONLY128
+    } else if (nt == 16 && rq == 16) {                                               // nwin = 256
+        // (wave pairs -- fsst_mfma128.hpp "PAIR" -- lose here: 16 waves at 128 registers spill, core 0.770 vs 0.587 ms per 1024
+        //  windows; 12 waves at 170 registers: 0.739 ms)
+        // (8 waves per block at most: two per SIMD, up to 256 VGPRs, no scratch)
+        if (fast && fixed + 8 * per_wave <= room) return launch_core128_wpb<16, 16, true, 8, -1, false, RAGGED>(pl, cp, nchunks, st);
+        if (!fast && canon && fixed + 8 * per_wave <= room) return launch_core128_wpb<16, 16, false, 8, 3, false, RAGGED>(pl, cp, nchunks, st);
+        if (!fast && fixed + 8 * per_wave <= room) return launch_core128_wpb<16, 16, false, 8, -1, false, RAGGED>(pl, cp, nchunks, st);
+        if (!fast && fixed + 4 * per_wave <= room) return launch_core128_wpb<16, 16, false, 4, -1, false, RAGGED>(pl, cp, nchunks, st);
+        if (fast && fixed + 4 * per_wave <= room) return launch_core128_wpb<16, 16, true, 4, -1, false, RAGGED>(pl, cp, nchunks, st);
+    } else {                                                                         // nt == 32, rq == 16: nwin = 512
+        if (!debug_switches().no_pair) {                                             // (two waves per SIMD at most: 32-point spectra in registers)
+            if (fast && core128_lds_bytes(pl, 16, 32, 8, true) <= room) return launch_core128_wpb<32, 16, true, 8, -1, true, RAGGED>(pl, cp, nchunks, st);
+            if (!fast && core128_lds_bytes(pl, 16, 32, 8, true) <= room) return launch_core128_wpb<32, 16, false, 8, -1, true, RAGGED>(pl, cp, nchunks, st);
+            if (!fast && core128_lds_bytes(pl, 16, 32, 6, true) <= room) return launch_core128_wpb<32, 16, false, 6, -1, true, RAGGED>(pl, cp, nchunks, st);
+            if (!fast && core128_lds_bytes(pl, 16, 32, 4, true) <= room) return launch_core128_wpb<32, 16, false, 4, -1, true, RAGGED>(pl, cp, nchunks, st);
+        }
+        if (fast && fixed + 8 * per_wave <= room) return launch_core128_wpb<32, 16, true, 8, -1, false, RAGGED>(pl, cp, nchunks, st);
+        if (!fast && fixed + 8 * per_wave <= room) return launch_core128_wpb<32, 16, false, 8, -1, false, RAGGED>(pl, cp, nchunks, st);
+        if (!fast && fixed + 6 * per_wave <= room) return launch_core128_wpb<32, 16, false, 6, -1, false, RAGGED>(pl, cp, nchunks, st);
+        if (fast && fixed + 4 * per_wave <= room) return launch_core128_wpb<32, 16, true, 4, -1, false, RAGGED>(pl, cp, nchunks, st);
+        if (!fast && fixed + 4 * per_wave <= room) return launch_core128_wpb<32, 16, false, 4, -1, false, RAGGED>(pl, cp, nchunks, st);
+        if (!fast && fixed + 3 * per_wave <= room) return launch_core128_wpb<32, 16, false, 3, -1, false, RAGGED>(pl, cp, nchunks, st);
+        if (!fast && fixed + 2 * per_wave <= room) return launch_core128_wpb<32, 16, false, 2, -1, false, RAGGED>(pl, cp, nchunks, st);
+        if (fast && fixed + 2 * per_wave <= room) return launch_core128_wpb<32, 16, true, 2, -1, false, RAGGED>(pl, cp, nchunks, st);
+#endif
+    }
+    return fail(HSSFSST_EUNSUPPORTED, "LDS request %zu B per wave exceeds the 160 KiB budget", per_wave);
 }
 
 int launch_core128(hssfsst_plan* pl, const float* dx, long long xstride, float* dout, float* partials, int n, int col0,
@@ -872,44 +947,8 @@ int launch_core128(hssfsst_plan* pl, const float* dx, long long xstride, float* 
         if (rc == 1) { *did_fuse = true; pl->last_zpath = 1; return 0; }
     }
 #endif
-    if (nt == 16 && rq == 8) {
-        if (canon16) return launch_canon(pl, cp, nchunks, st);
-#ifdef HSS_WPB_CANON
-        if (fast && canon) return launch_core128_wpb<16, 8, true, HSS_WPB_CANON, 3>(pl, cp, nchunks, st);
-#endif
-        if (fast && canon) return launch_core128_wpb<16, 8, true, 16, 3>(pl, cp, nchunks, st);
-        if (fast) return launch_core128_wpb<16, 8, true, 16>(pl, cp, nchunks, st);   // K <= 24: 16 regions always fit
-        if (fixed + 16 * per_wave <= room) return launch_core128_wpb<16, 8, false, 16>(pl, cp, nchunks, st);
-        if (fixed + 8 * per_wave <= room) return launch_core128_wpb<16, 8, false, 8>(pl, cp, nchunks, st);
-        if (fixed + 4 * per_wave <= room) return launch_core128_wpb<16, 8, false, 4>(pl, cp, nchunks, st);
-#ifndef HSS_DEV_ONLY128
-    } else if (nt == 16 && rq == 16) {                                               // nwin = 256
-        // (wave pairs -- fsst_mfma128.hpp "PAIR" -- lose here: 16 waves at 128 registers spill, core 0.770 vs 0.587 ms per 1024
-        //  windows; 12 waves at 170 registers: 0.739 ms)
-        // (8 waves per block at most: two per SIMD, up to 256 VGPRs, no scratch)
-        if (fast && fixed + 8 * per_wave <= room) return launch_core128_wpb<16, 16, true, 8>(pl, cp, nchunks, st);
-        if (!fast && canon && fixed + 8 * per_wave <= room) return launch_core128_wpb<16, 16, false, 8, 3>(pl, cp, nchunks, st);
-        if (!fast && fixed + 8 * per_wave <= room) return launch_core128_wpb<16, 16, false, 8>(pl, cp, nchunks, st);
-        if (!fast && fixed + 4 * per_wave <= room) return launch_core128_wpb<16, 16, false, 4>(pl, cp, nchunks, st);
-        if (fast && fixed + 4 * per_wave <= room) return launch_core128_wpb<16, 16, true, 4>(pl, cp, nchunks, st);
-    } else {                                                                         // nt == 32, rq == 16: nwin = 512
-        if (!debug_switches().no_pair) {                                             // (two waves per SIMD at most: 32-point spectra in registers)
-            if (fast && core128_lds_bytes(pl, 16, 32, 8, true) <= room) return launch_core128_wpb<32, 16, true, 8, -1, true>(pl, cp, nchunks, st);
-            if (!fast && core128_lds_bytes(pl, 16, 32, 8, true) <= room) return launch_core128_wpb<32, 16, false, 8, -1, true>(pl, cp, nchunks, st);
-            if (!fast && core128_lds_bytes(pl, 16, 32, 6, true) <= room) return launch_core128_wpb<32, 16, false, 6, -1, true>(pl, cp, nchunks, st);
-            if (!fast && core128_lds_bytes(pl, 16, 32, 4, true) <= room) return launch_core128_wpb<32, 16, false, 4, -1, true>(pl, cp, nchunks, st);
-        }
-        if (fast && fixed + 8 * per_wave <= room) return launch_core128_wpb<32, 16, true, 8>(pl, cp, nchunks, st);
-        if (!fast && fixed + 8 * per_wave <= room) return launch_core128_wpb<32, 16, false, 8>(pl, cp, nchunks, st);
-        if (!fast && fixed + 6 * per_wave <= room) return launch_core128_wpb<32, 16, false, 6>(pl, cp, nchunks, st);
-        if (fast && fixed + 4 * per_wave <= room) return launch_core128_wpb<32, 16, true, 4>(pl, cp, nchunks, st);
-        if (!fast && fixed + 4 * per_wave <= room) return launch_core128_wpb<32, 16, false, 4>(pl, cp, nchunks, st);
-        if (!fast && fixed + 3 * per_wave <= room) return launch_core128_wpb<32, 16, false, 3>(pl, cp, nchunks, st);
-        if (!fast && fixed + 2 * per_wave <= room) return launch_core128_wpb<32, 16, false, 2>(pl, cp, nchunks, st);
-        if (fast && fixed + 2 * per_wave <= room) return launch_core128_wpb<32, 16, true, 2>(pl, cp, nchunks, st);
-#endif
-    }
-    return fail(HSSFSST_EUNSUPPORTED, "LDS request %zu B per wave exceeds the 160 KiB budget", per_wave);
+    if (canon16) return launch_canon(pl, cp, nchunks, st);
+    return launch_core128_plain<false>(pl, cp, nchunks, st, fast, canon);
 }
 
 }  // namespace
@@ -1279,6 +1318,9 @@ int hssfsst_plan_destroy(hssfsst_plan* p)
     for (auto& b : p->pin_pool) if (b.h) (void)hipHostFree(b.h);
     if (p->d_starts) (void)hipFree(p->d_starts);
     if (p->d_frames) (void)hipFree(p->d_frames);
+    if (p->d_rtab) (void)hipFree(p->d_rtab);
+    if (p->h_rtab) (void)hipHostFree(p->h_rtab);
+    if (p->rtab_ev) (void)hipEventDestroy(p->rtab_ev);
     for (auto& ev : p->ev) if (ev) (void)hipEventDestroy(ev);
     for (auto& ev : p->sync_ev) if (ev) (void)hipEventDestroy(ev);
     if (p->aux) (void)hipStreamDestroy(p->aux);
@@ -1851,6 +1893,168 @@ int hssfsst_exec_list(hssfsst_plan* p, const float* x, int64_t x_len, const int6
         d_starts = p->d_starts;
     }
     return exec_impl(p, x, batch, n, 1, d_starts, static_cast<size_t>(x_len), 0, n, x_on_device, out, out_on_device, stream);
+}
+
+// Signals of different lengths in one exec (hssfsst.h).  Plans of the MFMA kernel (nwin 128 / 256 / 512): ONE core launch for the
+// whole list (fsst_core128_kernel<.., RAGGED>: a host-made chunk list, each signal cut as it would be alone) and, for STACK, one
+// statistics and one z-score launch (fsst_ragged.hpp).  Other plans: one exec per signal on the caller's stream.
+int hssfsst_exec_ragged(hssfsst_plan* p, const float* x, int64_t x_len, const int64_t* starts, const int64_t* lens, int64_t batch,
+                        int x_on_device, float* out, int out_on_device, void* stream)
+{
+    // argument errors first, and all of them before the plan or a device is looked at
+    if (batch < 0 || batch > 0x7fffffffLL) return fail(HSSFSST_EINVAL, "exec_ragged: batch = %lld", static_cast<long long>(batch));
+    if (batch > 0 && (!x || !starts || !lens || !out))
+        return fail(HSSFSST_EINVAL, "exec_ragged: NULL %s", !x ? "x" : !starts ? "starts" : !lens ? "lens" : "out");
+    for (int64_t i = 0; i < batch; ++i) {
+        if (lens[i] < 1) return fail(HSSFSST_EINVAL, "exec_ragged: signal %lld has length %lld", static_cast<long long>(i), static_cast<long long>(lens[i]));
+        if (starts[i] < 0 || x_len < lens[i] || starts[i] > x_len - lens[i])
+            return fail(HSSFSST_EINVAL, "exec_ragged: signal %lld ([%lld, %lld + %lld)) lies outside x[0, %lld)", static_cast<long long>(i),
+                        static_cast<long long>(starts[i]), static_cast<long long>(starts[i]), static_cast<long long>(lens[i]),
+                        static_cast<long long>(x_len));
+    }
+    if (!p) return fail(HSSFSST_EINVAL, "exec_ragged: plan is NULL");
+    for (int64_t i = 0; i < batch; ++i)
+        if (lens[i] >= (0x7fffffffLL + 2 * p->nf - 1) / (2 * p->nf))          // (n * 2 nf >= 2^31 - 1, as exec_impl)
+            return fail(HSSFSST_EINVAL, "exec_ragged: signal %lld too long (n = %lld)", static_cast<long long>(i), static_cast<long long>(lens[i]));
+    if (batch == 0 || p->K == 0) return 0;
+    const int ofps = out_floats_per_sample(p);
+    if (p->d_atab == nullptr) {
+        // the generic and any-length kernels: one exec per signal (the kernels of hssfsst_exec, on the caller's stream)
+        long long off = 0;
+        for (int64_t i = 0; i < batch; ++i) {
+            const int n = static_cast<int>(lens[i]);
+            if (int rc = exec_impl(p, x + starts[i], 1, n, n, nullptr, 0, 0, n, x_on_device, out + off * ofps, out_on_device, stream)) return rc;
+            off += n;
+        }
+        return 0;
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    DEVICE_SCOPE(p->device);
+    if (p->h_status && *p->h_status != 0u) {             // (as exec_impl: an earlier exec's wait gave up and nobody was told yet)
+        const unsigned code = *p->h_status;
+        *p->h_status = 0u;
+        return fail(HSSFSST_EHIP, "exec: a wait inside a previous exec's z-score kernel gave up (code %u); the results of that "
+                    "exec are invalid", code);
+    }
+    // host input: the extent the list covers, uploaded once
+    long long xlo = starts[0], xhi = starts[0] + lens[0];
+    for (int64_t i = 1; i < batch; ++i) {
+        xlo = std::min<long long>(xlo, starts[i]);
+        xhi = std::max<long long>(xhi, starts[i] + lens[i]);
+    }
+    if (x_on_device) xlo = 0;
+    long long cols = 0, groups = 0;
+    for (int64_t i = 0; i < batch; ++i) { cols += lens[i]; groups += (lens[i] + 15) / 16; }
+    const size_t no = static_cast<size_t>(cols) * ofps;
+    int rc;
+
+    // the tables (kept while the list's lengths and offsets stay the same)
+    const size_t sig_bytes = static_cast<size_t>(batch) * sizeof(hssfsst::RaggedSignal);
+    bool same = p->d_rtab != nullptr && p->rkey.size() == static_cast<size_t>(2 * batch);
+    for (int64_t i = 0; same && i < batch; ++i) same = p->rkey[2 * i] == lens[i] && p->rkey[2 * i + 1] == starts[i] - xlo;
+    if (!same) {
+        if (p->rtab_ev) HIP_TRY(hipEventSynchronize(p->rtab_ev));      // (the previous upload may still read h_rtab)
+        std::vector<int> ng(static_cast<size_t>(batch));
+        for (int64_t i = 0; i < batch; ++i) ng[i] = static_cast<int>((lens[i] + 15) / 16);
+        std::vector<int2> chunks;
+        hssfsst::core128_ragged_chunks(ng.data(), batch, chunks);
+        if (chunks.size() >= 0x7fffffffull) return fail(HSSFSST_EINVAL, "exec_ragged: %zu chunks exceed the launch limit; split the list", chunks.size());
+        p->rtab_unit = (sig_bytes + 15) & ~size_t(15);
+        p->rtab_chunk = (p->rtab_unit + static_cast<size_t>(batch + 1) * sizeof(int) + 15) & ~size_t(15);
+        p->rtab_bytes = p->rtab_chunk + chunks.size() * sizeof(int2);
+        if (p->rtab_bytes > p->h_rtab_cap) {
+            if (p->h_rtab) { HIP_TRY(hipHostFree(p->h_rtab)); p->h_rtab = nullptr; p->h_rtab_cap = 0; }
+            const size_t cap = p->rtab_bytes + p->rtab_bytes / 2;
+            void* hp = nullptr;
+            HIP_TRY(hipHostMalloc(&hp, cap, hipHostMallocDefault));
+            p->h_rtab = static_cast<unsigned char*>(hp); p->h_rtab_cap = cap;
+        }
+        std::memset(p->h_rtab, 0, p->rtab_chunk);
+        auto* rs = reinterpret_cast<hssfsst::RaggedSignal*>(p->h_rtab);
+        int* unit0 = reinterpret_cast<int*>(p->h_rtab + p->rtab_unit);
+        long long o = 0, g = 0, u = 0;
+        p->rkey.resize(static_cast<size_t>(2 * batch));
+        for (int64_t i = 0; i < batch; ++i) {
+            rs[i].xoff = starts[i] - xlo; rs[i].ooff = o * ofps; rs[i].poff = g * hssfsst::kPartFloats;
+            rs[i].n = static_cast<int>(lens[i]); rs[i].pad = 0;
+            unit0[i] = static_cast<int>(u);
+            u += (lens[i] * 2 * p->K + hssfsst::kRaggedUnitFloats - 1) / hssfsst::kRaggedUnitFloats;
+            o += lens[i]; g += ng[i];
+            p->rkey[2 * i] = lens[i]; p->rkey[2 * i + 1] = starts[i] - xlo;
+        }
+        unit0[batch] = static_cast<int>(u);
+        std::memcpy(p->h_rtab + p->rtab_chunk, chunks.data(), chunks.size() * sizeof(int2));
+        p->rtab_nchunks = static_cast<long long>(chunks.size());
+        p->rtab_nunits = u;
+        if ((rc = grow(&p->d_rtab, &p->rtab_cap, p->rtab_bytes, 1)) != 0) { p->rkey.clear(); return rc; }
+        if (!p->rtab_ev) HIP_TRY(hipEventCreateWithFlags(&p->rtab_ev, hipEventDisableTiming));
+        HIP_TRY(hipMemcpyAsync(p->d_rtab, p->h_rtab, p->rtab_bytes, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipEventRecord(p->rtab_ev, st));
+    }
+    const auto* d_rsig = static_cast<const hssfsst::RaggedSignal*>(p->d_rtab);
+    const int* d_unit0 = reinterpret_cast<const int*>(static_cast<const unsigned char*>(p->d_rtab) + p->rtab_unit);
+    const int2* d_chunks = reinterpret_cast<const int2*>(static_cast<const unsigned char*>(p->d_rtab) + p->rtab_chunk);
+
+    const float* dx = x;
+    float* dout = out;
+    if (!x_on_device) {
+        const size_t nx = static_cast<size_t>(xhi - xlo);
+        if ((rc = grow(reinterpret_cast<void**>(&p->d_xstage), &p->xstage_cap, nx, sizeof(float))) != 0) return rc;
+        HIP_TRY(hipMemcpyAsync(p->d_xstage, x + xlo, nx * sizeof(float), hipMemcpyHostToDevice, st));
+        dx = p->d_xstage;
+    }
+    if (!out_on_device) {
+        if ((rc = grow(reinterpret_cast<void**>(&p->d_ostage), &p->ostage_cap, no, sizeof(float))) != 0) return rc;
+        dout = p->d_ostage;
+    }
+    if (p->mode == HSSFSST_MODE_STACK) {
+        if ((rc = grow(reinterpret_cast<void**>(&p->d_partials), &p->partials_cap, static_cast<size_t>(groups) * hssfsst::kPartFloats, sizeof(float))) != 0) return rc;
+        if ((rc = grow(reinterpret_cast<void**>(&p->d_stats), &p->stats_cap, static_cast<size_t>(batch) * 4, sizeof(float))) != 0) return rc;
+    }
+
+    p->timing_closed = false;
+    p->timing = (p->timing_every > 0 && (p->timing_seq++ % static_cast<unsigned>(p->timing_every)) == 0u) ? 1 : 0;
+    hipEvent_t evt = nullptr;
+    if (p->timing) { if ((rc = plan_next_event(p, &evt)) != 0) return rc; HIP_TRY(hipEventRecord(evt, st)); }
+    hssfsst::Core128Params cp{};
+    cp.x = dx; cp.out = dout; cp.partials = p->d_partials; cp.atab = p->d_atab;
+    cp.wtab = p->d_wtab; cp.twtab = p->d_wtab + 2 * p->nwin; cp.r2scale = p->r2scale;
+    cp.n = 1; cp.klo = p->klo; cp.K = p->K; cp.mode = p->mode; cp.nsig = static_cast<int>(std::min<int64_t>(batch, 0x7fffffff));
+    cp.col0 = 0; cp.ncols = 1; cp.xstride = 0;
+    cp.rsig = d_rsig; cp.rchunk = d_chunks; cp.rnchunks = static_cast<int>(p->rtab_nchunks);
+    const bool fast = (p->mode == HSSFSST_MODE_STACK || p->mode == HSSFSST_MODE_STACK_UNNORM) && (p->K & 1) == 0 && p->K <= 24;
+    const bool canon = hssfsst::own_s0(p->klo, p->rq) == 0 && hssfsst::own_s1(p->klo, p->K, p->rq) == 3;
+    // (the canonical-class band in STACK modes takes the canonical kernel's arithmetic, as every single exec of it does; the
+    //  general kernels give other -- equally accurate -- bits there)
+    if (fast && p->nt == 16 && p->rq == 8 && plan_is_canon(p))
+        rc = canon_dispatch(p, [&](auto KL, auto KN) { return launch_canon_band<decltype(KL)::value, decltype(KN)::value, true>(p, cp, p->rtab_nchunks, st); });
+    else
+        rc = launch_core128_plain<true>(p, cp, p->rtab_nchunks, st, fast, canon);
+    if (rc != 0) return rc;
+    p->last_fused = 0;
+    p->last_zpath = 0;
+    if (p->timing) { if ((rc = plan_next_event(p, &evt)) != 0) return rc; HIP_TRY(hipEventRecord(evt, st)); }
+    if (p->mode == HSSFSST_MODE_STACK) {
+        float4* stats = reinterpret_cast<float4*>(p->d_stats);
+        hipLaunchKernelGGL(hssfsst::fsst_ragged_stats_kernel, dim3(static_cast<unsigned>(batch)), dim3(64), 0, st, p->d_partials, d_rsig, stats, p->K);
+        const long long zgrid = std::min<long long>(p->rtab_nunits, 65536);
+        hipLaunchKernelGGL(hssfsst::fsst_ragged_normalize_kernel, dim3(static_cast<unsigned>(zgrid)), dim3(256), 0, st, dout, d_rsig, d_unit0,
+                           stats, static_cast<int>(batch), p->K);
+        HIP_TRY(hipGetLastError());
+    }
+    if (p->timing) {
+        if ((rc = plan_next_event(p, &evt)) != 0) return rc;
+        HIP_TRY(hipEventRecord(evt, st));
+        p->ev_chunks.push_back(1);
+    }
+    if (!out_on_device) {
+        HIP_TRY(hipMemcpyAsync(out, dout, no * sizeof(float), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (p->d_status && (rc = hssfsst_plan_check(p)) != 0) return rc;
+    } else if (!x_on_device) {
+        HIP_TRY(hipStreamSynchronize(st));               // the host source may be reused by the caller
+    }
+    return 0;
 }
 
 int hssfsst_moments_merge(hssfsst_plan* p, const float* feats, int64_t batch, int n, double* state, void* stream)

@@ -11,6 +11,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+from collections.abc import Sequence as _SequenceABC
 from typing import Optional
 
 import numpy as np
@@ -75,6 +76,54 @@ class _Plan:
             pass
 
 
+class RaggedFeatures(_SequenceABC):
+    """The features of ``FSST.ragged``: signals of different lengths, packed back to back in ONE arena.
+
+    ``data``: the arena -- ``(sum T_i, C)`` float32 for ``abs`` / ``stack`` (C = K / 2K), ``(K * sum T_i,)`` complex64 for the raw
+    transform (signal i's ``(K, T_i)`` block at ``K * offsets[i]``); ``offsets``: int64 ``(B + 1,)`` in samples.  ``len``, iteration
+    and ``[i]`` work as on a list; item i is a view with exactly the shape, dtype and device ``FSST.__call__`` / ``FSST.batch`` give
+    for signal i alone."""
+
+    def __init__(self, data: torch.Tensor, offsets: torch.Tensor, K: int, raw: bool):
+        self.data = data
+        self.offsets = offsets
+        self._off = [int(v) for v in offsets.tolist()]
+        self._K, self._raw = int(K), bool(raw)
+
+    def __len__(self) -> int:
+        return len(self._off) - 1
+
+    def __getitem__(self, i):
+        if isinstance(i, slice):
+            return [self[j] for j in range(*i.indices(len(self)))]
+        if i < 0:
+            i += len(self)
+        if not 0 <= i < len(self):
+            raise IndexError(i)
+        a, b = self._off[i], self._off[i + 1]
+        if self._raw:
+            return self.data[self._K * a:self._K * b].view(self._K, b - a)
+        return self.data[a:b]
+
+    def lengths(self) -> torch.Tensor:
+        """``(B,)`` int64 signal lengths."""
+        return self.offsets[1:] - self.offsets[:-1]
+
+    def padded(self, padding_value: float = 0.0) -> torch.Tensor:
+        """``abs`` / ``stack``: ``(B, T_max, C)`` with ``padding_value`` past each signal's end -- what
+        ``torch.nn.utils.rnn.pad_sequence(list(self), batch_first=True, padding_value=...)`` gives, in one scatter."""
+        if self._raw:
+            raise ValueError("RaggedFeatures.padded: the raw transform is frequency-major (K, T); pad the items yourself")
+        B = len(self)
+        lens = self.lengths().to(self.data.device)
+        T = int(lens.max()) if B else 0
+        out = torch.full((B, T, int(self.data.shape[1])), float(padding_value), dtype=self.data.dtype, device=self.data.device)
+        if B and T:
+            mask = torch.arange(T, device=self.data.device)[None, :] < lens[:, None]
+            out[mask] = self.data                        # (row-major mask order == the arena's signal-major order)
+        return out
+
+
 class FSST:
     """
     Fourier Synchrosqueezed Transform (MI355X / HIP implementation).
@@ -110,6 +159,7 @@ class FSST:
         self.device = device
         self._plans = {}
         self._cuda_seen = False
+        self._ragged_stage = None                      # pinned staging of ragged() host lists (kept between calls)
 
     # ------------------------------------------------------------------ plan / geometry
     def _mode(self) -> int:
@@ -147,6 +197,7 @@ class FSST:
         st = self.__dict__.copy()
         st["_plans"] = {}
         st["_cuda_seen"] = False
+        st["_ragged_stage"] = None
         return st
 
     def band(self):
@@ -319,6 +370,104 @@ class FSST:
                                           ctypes.c_void_p(stream) if stream else None)
         _lib.check(rc, "hssfsst_exec_list")
         return out
+
+    def ragged(self, xs, lengths=None, out: Optional[torch.Tensor] = None) -> RaggedFeatures:
+        """Extension: transform signals of DIFFERENT lengths in one call (``hssfsst_exec_ragged``) -- whole recordings, as the
+        reference's lazy dataset and PhysioNet loader transform them one call each (hss/datasets/heart_sounds.py:85-106,175-184).
+
+        ``xs``: a sequence of 1-D signals (``(T_i,)`` or ``(T_i, 1)``, float32 / float64, all on the CPU or all on one cuda device),
+        or ONE packed 1-D buffer with ``lengths`` (its signals back to back).  float64 is rounded to float32 first, as ``__call__``
+        does.  Returns a ``RaggedFeatures`` on the input's device whose item i equals ``self.batch(xs[i][None])[0]`` bit for bit.
+        ``out``: an arena to write into (``RaggedFeatures.data``'s shape, dtype and device)."""
+        raw = not (self.abs or self.stack)
+        # ---- arguments, all checked before a plan (or the GPU) is touched
+        if isinstance(xs, torch.Tensor) or isinstance(xs, np.ndarray):
+            if lengths is None:
+                raise ValueError("FSST.ragged: a single tensor is a packed buffer and needs lengths=; pass a list for separate signals")
+            buf = xs if isinstance(xs, torch.Tensor) else torch.as_tensor(xs)
+            if buf.ndim == 2 and buf.shape[-1] == 1:
+                buf = buf[:, 0]
+            if buf.ndim != 1:
+                raise ValueError(f"FSST.ragged: a packed buffer must be 1-D, got {tuple(buf.shape)}")
+            lens = np.asarray(lengths.cpu() if isinstance(lengths, torch.Tensor) else lengths, dtype=np.int64).reshape(-1)
+            if lens.size and int(lens.min()) < 1:
+                raise ValueError("FSST.ragged: every length must be >= 1")
+            if int(lens.sum()) != int(buf.shape[0]):
+                raise ValueError(f"FSST.ragged: lengths sum to {int(lens.sum())}, the buffer holds {int(buf.shape[0])} samples")
+            sigs = None
+            on_dev, odev = buf.is_cuda, buf.device
+            if buf.is_complex():
+                raise ValueError("FSST.ragged: real input expected")
+        else:
+            if lengths is not None:
+                raise ValueError("FSST.ragged: lengths= goes with one packed buffer, not with a list of signals")
+            sigs = []
+            for i, x in enumerate(xs):
+                t = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))
+                if t.ndim == 2 and t.shape[-1] == 1:
+                    t = t[:, 0]
+                if t.ndim != 1:
+                    raise ValueError(f"FSST.ragged: signal {i} has shape {tuple(x.shape)}; expected (T,) or (T, 1)")
+                if t.is_complex():
+                    raise ValueError(f"FSST.ragged: signal {i} is complex; real input expected")
+                if t.shape[0] < 1:
+                    raise ValueError(f"FSST.ragged: signal {i} is empty")
+                sigs.append(t)
+            devs = {t.device for t in sigs}
+            if len(devs) > 1:
+                raise ValueError(f"FSST.ragged: the signals lie on different devices {sorted(str(d) for d in devs)}; "
+                                 "pass all on the CPU or all on one cuda device")
+            odev = devs.pop() if devs else torch.device("cpu")
+            on_dev = odev.type == "cuda"
+            lens = np.asarray([int(t.shape[0]) for t in sigs], dtype=np.int64)
+        B, total = int(lens.size), int(lens.sum())
+        offsets = torch.from_numpy(np.concatenate([[0], np.cumsum(lens)]).astype(np.int64))
+        klo, K = self.band()
+        C = K if self.abs else 2 * K
+        shape, dt = ((K * total,), torch.complex64) if raw else ((total, C), torch.float32)
+        if out is not None and (tuple(out.shape) != shape or out.dtype != dt or out.device != odev or not out.is_contiguous()):
+            raise ValueError(f"FSST.ragged: out must be a contiguous {dt} tensor of shape {shape} on {odev}")
+        if B == 0:
+            return RaggedFeatures(out if out is not None else torch.empty(shape, dtype=dt, device=odev), offsets, K, raw)
+        # ---- pack
+        dev = self._device_index(torch.empty(0, device=odev) if on_dev else None)
+        plan = self._plan(dev)
+        L = _lib.lib()
+        if sigs is None:
+            X = buf.detach().to(torch.float32).contiguous()
+            starts = offsets[:-1].numpy()
+        elif on_dev:
+            X = torch.cat([t.detach().to(torch.float32) for t in sigs]) if B > 1 else sigs[0].detach().to(torch.float32).contiguous()
+            starts = offsets[:-1].numpy()
+        else:
+            # host list: one native call copies the signals (threaded) into a pinned staging buffer, from which the library's one
+            # upload is a DMA
+            held = [t.detach() if (t.dtype == torch.float32 and t.is_contiguous()) else t.detach().to(torch.float32).contiguous() for t in sigs]
+            stage = getattr(self, "_ragged_stage", None)
+            if stage is None or stage.numel() < total:
+                try:
+                    stage = torch.empty(max(total, 1 << 16), dtype=torch.float32, pin_memory=True)
+                except RuntimeError:
+                    stage = torch.empty(max(total, 1 << 16), dtype=torch.float32)
+                self._ragged_stage = stage
+            ptrs = np.asarray([t.data_ptr() for t in held], dtype=np.uint64)
+            starts = np.empty(B, dtype=np.int64)
+            got = L.hssfsst_pack_recordings(ctypes.c_void_p(ptrs.ctypes.data), ctypes.c_void_p(lens.ctypes.data), B, 0x7fffffff, 1,
+                                            ctypes.c_void_p(stage.data_ptr()), int(stage.numel()), ctypes.c_void_p(starts.ctypes.data), B, 0)
+            if got != B:
+                _lib.check(int(got) if got < 0 else _lib.E_INVAL, "hssfsst_pack_recordings")
+            X = stage
+        if out is None:
+            out = torch.empty(shape, dtype=dt, device=odev)
+        if K > 0:
+            stream = torch.cuda.current_stream(dev).cuda_stream if on_dev else None
+            lens_c = np.ascontiguousarray(lens)
+            starts_c = np.ascontiguousarray(starts, dtype=np.int64)
+            rc = L.hssfsst_exec_ragged(plan.handle, ctypes.c_void_p(X.data_ptr()), int(X.numel()), ctypes.c_void_p(starts_c.ctypes.data),
+                                       ctypes.c_void_p(lens_c.ctypes.data), B, 1 if on_dev else 0, ctypes.c_void_p(out.data_ptr()),
+                                       1 if on_dev else 0, ctypes.c_void_p(stream) if stream else None)
+            _lib.check(rc, "hssfsst_exec_ragged")
+        return RaggedFeatures(out, offsets, K, raw)
 
     def check(self, device_index: Optional[int] = None) -> int:
         """Extension: waits for the device and raises ``RuntimeError`` if a kernel reported a failed internal wait

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define HSSFSST_VERSION 209
+#define HSSFSST_VERSION 210
 
 /* status codes */
 #define HSSFSST_OK 0
@@ -112,6 +112,23 @@ int hssfsst_pinned_release(hssfsst_plan* plan, float* buf);
  * features) and take the kernels of hssfsst_exec.  out: [batch][n][...] as hssfsst_exec. */
 int hssfsst_exec_list(hssfsst_plan* plan, const float* x, int64_t x_len, const int64_t* starts, int starts_on_device,
                       int64_t batch, int n, int x_on_device, float* out, int out_on_device, void* stream);
+
+/* B signals of DIFFERENT lengths in one exec -- the reference's lazy dataset and PhysioNet loader transform whole recordings, one
+ * call each (hss/datasets/heart_sounds.py:85-106,175-184,199-212).  Signal i is x[starts[i] .. starts[i] + lens[i]) and its
+ * features land at out + out_floats_per_sample * (lens[0] + ... + lens[i-1]) in the mode's per-signal layout (RAW (K, len)
+ * complex64, ABS (len, K), STACK (len, 2K) z-scored over that signal's own columns).  starts / lens: int64 HOST arrays.  Signals
+ * may overlap or touch in x; a frame never reads samples of another signal (outside its own [0, len) it sees zeros, as in a
+ * single exec).  For every i the result is bit-identical to hssfsst_exec(plan, x + starts[i], 1, lens[i], ...).
+ * Argument errors -- a NULL pointer, batch < 0, lens[i] < 1, a signal outside [0, x_len), a signal over the per-signal limit
+ * len * 2 nf < 2^31 -- return HSSFSST_EINVAL before any device is touched (all but the last are checked before the plan is
+ * looked at); batch == 0 does nothing.  Offsets into the packed output are 64-bit: the total may exceed 2^31 floats.
+ * Host x: the extent the list covers is uploaded in one copy; host out: the features come back in one copy (pinned memory
+ * makes both DMA).  Plans of the MFMA kernel (window length 128 / 256 / 512, every band and mode): one transform launch for
+ * the whole list (chunk list made on the host, kept while the next call has the same lengths and offsets) and, for STACK, one
+ * statistics and one z-score launch.  Other window lengths (the generic nwin 32 / 64 kernel, the any-length kernel): one
+ * hssfsst_exec per signal on `stream`, inside the library -- correct, not batched.  Synchronisation as hssfsst_exec. */
+int hssfsst_exec_ragged(hssfsst_plan* plan, const float* x, int64_t x_len, const int64_t* starts, const int64_t* lens,
+                        int64_t batch, int x_on_device, float* out, int out_on_device, void* stream);
 
 /* Device-side health of the plan's asynchronous work.  The single-launch z-score kernels contain waits on other
  * waves (of the same CU: the one-CU-per-signal kernel; of other CUs of a team: the team kernel, see hssfsst_plan_fallbacks).
