@@ -18,7 +18,7 @@ HEADER = os.path.join(os.path.dirname(_PKG), "include", "hssfsst.h")
 
 MODE_RAW, MODE_ABS, MODE_STACK, MODE_STACK_UNNORM = 0, 1, 2, 3
 E_INVAL, E_NODEVICE, E_UNSUPPORTED, E_NOMEM, E_HIP = -1, -2, -3, -4, -5
-DTYPE_F32, DTYPE_F64 = 0, 1
+DTYPE_F32, DTYPE_F64, DTYPE_F16, DTYPE_BF16 = 0, 1, 2, 3
 
 _lock = threading.Lock()
 _lib = None
@@ -176,6 +176,10 @@ def lib():
         dp = ctypes.POINTER(ctypes.c_double)
         L.hssfsst_plan_create.argtypes = [ctypes.POINTER(vp), c_int, c_int, dp, c_dbl, c_int, c_dbl, c_dbl, c_int]
         L.hssfsst_plan_create.restype = c_int
+        L.hssfsst_plan_create_ex.argtypes = [ctypes.POINTER(vp), c_int, c_int, dp, c_dbl, c_int, c_dbl, c_dbl, c_int, c_int]
+        L.hssfsst_plan_create_ex.restype = c_int
+        L.hssfsst_plan_out_dtype.argtypes = [vp, ip]
+        L.hssfsst_plan_out_dtype.restype = c_int
         L.hssfsst_plan_destroy.argtypes = [vp]
         L.hssfsst_plan_destroy.restype = c_int
         L.hssfsst_plan_info.argtypes = [vp, ip, ip, ip, ip, ip, ip, ip]

@@ -55,7 +55,7 @@ class FrameItems(_SequenceABC):
     on the reference's list)."""
 
     def __init__(self, features: torch.Tensor, labels: Optional[torch.Tensor]):
-        self.features = features                          # (frames, n, 2K) float32, device or host
+        self.features = features                          # (frames, n, 2K) float32 (or the transform's out_dtype), device or host
         self.labels = labels                              # (frames, n) int64 on the host, or None
 
     def __len__(self) -> int:
@@ -100,7 +100,8 @@ class CorpusBuilder:
         elif need_labels and b["lab_starts"].shape[0] < max_frames:
             b["lab_starts"] = np.empty(max_frames, dtype=np.int64)
 
-    def _ensure(self, max_samples: int, max_frames: int, C: int, need_ring: bool, item_len: Optional[int] = None) -> None:
+    def _ensure(self, max_samples: int, max_frames: int, C: int, need_ring: bool, item_len: Optional[int] = None,
+                dtype: torch.dtype = torch.float32) -> None:
         dev = self.dev
         if self._bufs is None:
             self._bufs = {"up": torch.cuda.Stream(dev), "down": torch.cuda.Stream(dev),
@@ -116,8 +117,8 @@ class CorpusBuilder:
             b["start_d"] = [torch.empty(max_frames, dtype=torch.int64, device=dev) for _ in range(2)]
             self._cap_frames = max_frames
         item_len = self.frame_len if item_len is None else item_len
-        if need_ring and (max_frames * C > self._cap_ring or b["ring_d"][0].shape[1] != item_len):
-            b["ring_d"] = [torch.empty((max_frames, item_len, C), dtype=torch.float32, device=dev) for _ in range(2)]
+        if need_ring and (max_frames * C > self._cap_ring or b["ring_d"][0].shape[1] != item_len or b["ring_d"][0].dtype != dtype):
+            b["ring_d"] = [torch.empty((max_frames, item_len, C), dtype=dtype, device=dev) for _ in range(2)]
             self._cap_ring = max_frames * C
 
     def build_recordings(self, recordings: Iterable[Tuple[torch.Tensor, Optional[torch.Tensor]]], keep_on_device: bool = False,
@@ -147,14 +148,14 @@ class CorpusBuilder:
         offsets = torch.from_numpy(np.concatenate([[0], np.cumsum(lens_np)]).astype(np.int64))
         from .transforms.synchrosqueeze import RaggedFeatures
         plan = fsst._plan(fsst._device_index(torch.empty(0, device=dev)))
-        C, K = plan.ofps, plan.K
+        C, K, fdt = plan.ofps, plan.K, plan.out_dtype     # (fdt: the features' element type -- a half STACK transform's out_dtype)
         if keep_on_device:
-            feats = torch.empty((total, C), dtype=torch.float32, device=dev)
+            feats = torch.empty((total, C), dtype=fdt, device=dev)
         else:
             try:
-                feats = torch.empty((total, C), dtype=torch.float32, pin_memory=bool(self.pin_host and total > 0))
+                feats = torch.empty((total, C), dtype=fdt, pin_memory=bool(self.pin_host and total > 0))
             except RuntimeError:                          # page-locking that much memory can be refused: pageable then
-                feats = torch.empty((total, C), dtype=torch.float32)
+                feats = torch.empty((total, C), dtype=fdt)
         items = RecordingItems(RaggedFeatures(feats, offsets, K, False), ys)
         if total == 0:
             return items
@@ -171,8 +172,8 @@ class CorpusBuilder:
         max_group = max(int(pos_np[b] - pos_np[a]) for a, b in groups)
         self._ensure(max_group, 0, C, False)
         B = self._bufs
-        if not keep_on_device and (B.get("rec_ring") is None or B["rec_ring"][0].numel() < max_group * C):
-            B["rec_ring"] = [torch.empty(max_group * C, dtype=torch.float32, device=dev) for _ in range(2)]
+        if not keep_on_device and (B.get("rec_ring") is None or B["rec_ring"][0].numel() < max_group * C or B["rec_ring"][0].dtype != fdt):
+            B["rec_ring"] = [torch.empty(max_group * C, dtype=fdt, device=dev) for _ in range(2)]
         main, up, down = torch.cuda.current_stream(dev), B["up"], B["down"]
         stage_h, stage_d = B["stage_h"], B["stage_d"]
         up_done, used, ring_free = B["up_done"], B["used"], B["ring_free"]
@@ -298,28 +299,28 @@ class CorpusBuilder:
             return FrameItems(feats, labels)
 
         plan = fsst._plan(fsst._device_index(torch.empty(0, device=dev)))
-        C = plan.ofps
+        C, fdt = plan.ofps, plan.out_dtype              # (fdt: the features' element type -- a half STACK transform's out_dtype)
         shape = (total, out_len, C)
-        if out is not None and (tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous()
+        if out is not None and (tuple(out.shape) != shape or out.dtype != fdt or not out.is_contiguous()
                                 or out.is_cuda != bool(keep_on_device)):
-            raise ValueError(f"CorpusBuilder.build: out must be a contiguous float32 {shape} arena "
+            raise ValueError(f"CorpusBuilder.build: out must be a contiguous {fdt} {shape} arena "
                              f"{'on the device' if keep_on_device else 'in host memory'}")
         feats = out
         if feats is None:
             if keep_on_device:
-                feats = torch.empty(shape, dtype=torch.float32, device=dev)
+                feats = torch.empty(shape, dtype=fdt, device=dev)
             else:
                 try:
-                    feats = torch.empty(shape, dtype=torch.float32, pin_memory=bool(self.pin_host and total > 0))
+                    feats = torch.empty(shape, dtype=fdt, pin_memory=bool(self.pin_host and total > 0))
                 except RuntimeError:                      # page-locking that much memory can be refused: pageable then
-                    feats = torch.empty(shape, dtype=torch.float32)
+                    feats = torch.empty(shape, dtype=fdt)
         if total == 0:
             if have_labels and rsm is not None:
                 labels = torch.empty((0, out_len), dtype=torch.int64)
             return FrameItems(feats, labels)
         max_samples = max(sum(int(recs[i][0].shape[0]) for i in range(a, b)) for a, b in groups)
         max_frames = max(sum(nfr[a:b]) for a, b in groups)
-        self._ensure(max_samples, max_frames, C, not keep_on_device, out_len)
+        self._ensure(max_samples, max_frames, C, not keep_on_device, out_len, fdt)
         dev_labels = have_labels and rsm is not None     # labels resampled on the device: (total, num) device arena, copied once
         if rsm is not None:
             self._ensure_resample(max_samples, max_frames, out_len, dev_labels)

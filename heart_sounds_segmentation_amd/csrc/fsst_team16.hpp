@@ -107,7 +107,7 @@ constexpr int t16_pslots()
 
 struct Team16Params {
     const float* x;       // [nsig][xstride]
-    float* out;           // [nsig][ncols][2 KC]
+    float* out;           // [nsig][ncols][2 KC] elements of the kernel's output type (float, or 2-byte halves)
     const float* atab;    // f16 operand table + float64 twiddles (kCanonAtabFloats floats), then the offset table (kCanonZcFloats)
     const double* wtab;   // float64 {w, dw'}[128]                } rounding-tie path
     const double* twtab;  // float64 {cos, sin}(2 pi m / 128)     }
@@ -163,11 +163,28 @@ __device__ __forceinline__ f2 held_zscore(f2 m)
     return e;
 }
 
-// WPB waves per block (one block per CU), DEPTH group images held per wave (registers): (16, 2) is what the library launches
-template <int KLO, int KC, int WPB, int DEPTH>
+// One float4 of z-scores (lo = elements 0, 1; hi = 2, 3) as OT = _Float16 / __bf16 (half-precision STACK plans, HSSFSST_DTYPE_F16 /
+// BF16), a streaming store of 8 bytes: the float32 values rounded to nearest even by the compiler's conversion -- v_cvt_pk_f16_f32 /
+// v_cvt_pk_bf16_f32, which keep NaN a NaN.  (The float32 kernel stores its float4 as it always has: see the two store sites.)
+template <class OT>
+__device__ __forceinline__ void team16_store4(char* dst, f2 lo, f2 hi)
+{
+    static_assert(sizeof(OT) == 2, "2-byte output elements");
+    using o2 = OT __attribute__((ext_vector_type(2)));
+    using w2 = unsigned __attribute__((ext_vector_type(2)));
+    const w2 w = {__builtin_bit_cast(unsigned, __builtin_convertvector(lo, o2)), __builtin_bit_cast(unsigned, __builtin_convertvector(hi, o2))};
+    __builtin_nontemporal_store(w, reinterpret_cast<w2*>(dst));
+}
+
+// WPB waves per block (one block per CU), DEPTH group images held per wave (registers): (16, 2) is what the library launches.
+// OT: the output element type -- float, or _Float16 / __bf16 for half-precision STACK plans (p.out then points to 2-byte elements,
+// 8-byte aligned).  Only the two store sites depend on it: the transform, the statistics and the z-score in registers are the float32
+// ones, and for OT = float the kernel's code is that of the four-parameter kernel before OT existed (instruction for instruction).
+template <int KLO, int KC, int WPB, int DEPTH, class OT = float>
 // (amdgpu_num_vgpr(52): the attribute counts in register PAIRS on this target -- 104 allocatable registers; v104 .. v127 are the held images')
 __global__ __launch_bounds__(64 * WPB, WPB / 4) __attribute__((amdgpu_num_vgpr(52))) void fsst_team16_kernel(Team16Params p)
 {
+    constexpr int OB = static_cast<int>(sizeof(OT));     // bytes per output element
 #ifdef HSS_T16_BLKPROBE
     const unsigned pb_entry = static_cast<unsigned>(wall_clock64());       // (absolute: the 100 MHz counter is the chip's)
 #endif
@@ -266,7 +283,7 @@ __global__ __launch_bounds__(64 * WPB, WPB / 4) __attribute__((amdgpu_num_vgpr(5
     constexpr int nwords = kT16SlotWords;                      // tagged words per signal in the mailbox
     gu64* mail = (gu64*)(p.mail) + static_cast<size_t>(team) * static_cast<size_t>(p.slots) * nwords;
     const int nblocks = (G + kStatBlock - 1) / kStatBlock;
-    const unsigned sig_bytes = static_cast<unsigned>(ncols) * (2 * K * 4);         // a signal's feature block (at most 128 groups: 32 bits)
+    const unsigned sig_bytes = static_cast<unsigned>(ncols) * (2 * K * OB);        // a signal's feature block (at most 128 groups: 32 bits)
 
     f2 tiny = {1.0e-37f, 0.0f};
     asm volatile("" : "+s"(tiny));
@@ -431,8 +448,8 @@ __global__ __launch_bounds__(64 * WPB, WPB / 4) __attribute__((amdgpu_num_vgpr(5
         const unsigned cofs = cls_lds[lane_r];
         const char* tb = reinterpret_cast<const char*>(fin + 3 * (ko_h & smask));
         char* obase = reinterpret_cast<char*>(P()->out) + static_cast<unsigned long long>(static_cast<unsigned>(team + ko_h * nteams)) * sig_bytes +
-                      static_cast<unsigned>(g_h * (16 * 2 * K * 4));                                                          // (wave-uniform)
-        const unsigned voff = static_cast<unsigned>(lane_r) * 16u;
+                      static_cast<unsigned>(g_h * (16 * 2 * K * OB));                                                         // (wave-uniform)
+        const unsigned voff = static_cast<unsigned>(lane_r) * (4u * OB);
         const int nvalid = min(16, ncols - g_h * 16);
         auto put = [&](auto I) {
             constexpr int i = decltype(I)::value;
@@ -442,7 +459,8 @@ __global__ __launch_bounds__(64 * WPB, WPB / 4) __attribute__((amdgpu_num_vgpr(5
 #if defined(HSS_T16_ABLATE) && HSS_T16_ABLATE >= 2      // development: the arithmetic without the stores
             { f2 l2 = lo, h2 = hi; asm volatile("" :: "v"(l2), "v"(h2)); }
 #else
-            __builtin_nontemporal_store(f4{lo.x, lo.y, hi.x, hi.y}, reinterpret_cast<f4*>(obase + (voff + 1024u * static_cast<unsigned>(i))));
+            if constexpr (OB == 4) __builtin_nontemporal_store(f4{lo.x, lo.y, hi.x, hi.y}, reinterpret_cast<f4*>(obase + (voff + 1024u * static_cast<unsigned>(i))));
+            else team16_store4<OT>(obase + (voff + (256u * OB) * static_cast<unsigned>(i)), lo, hi);
 #endif
         };
         if (__builtin_expect(nvalid == 16, 1)) {
@@ -650,8 +668,8 @@ __global__ __launch_bounds__(64 * WPB, WPB / 4) __attribute__((amdgpu_num_vgpr(5
                         const float4 t1 = *reinterpret_cast<const float4*>(tb + ((cofs >> 8) & 0xffu));
                         const float4 t2 = *reinterpret_cast<const float4*>(tb + ((cofs >> 16) & 0xffu));
                         char* ob = reinterpret_cast<char*>(P()->out) + static_cast<unsigned long long>(static_cast<unsigned>(team + ko_o * nteams)) * sig_bytes +
-                                   static_cast<unsigned>(g_o * (16 * 2 * K * 4));                                              // (wave-uniform)
-                        const unsigned voff = static_cast<unsigned>(lane_r) * 16u;
+                                   static_cast<unsigned>(g_o * (16 * 2 * K * OB));                                             // (wave-uniform)
+                        const unsigned voff = static_cast<unsigned>(lane_r) * (4u * OB);
                         const int nvalid = min(16, ncols - g_o * 16);
                         auto put = [&](auto I, float4 tt) {
                             constexpr int i = decltype(I)::value;
@@ -660,7 +678,8 @@ __global__ __launch_bounds__(64 * WPB, WPB / 4) __attribute__((amdgpu_num_vgpr(5
 #if defined(HSS_T16_ABLATE) && HSS_T16_ABLATE >= 2      // development: the arithmetic without the stores
                             { f2 l2 = l, h2 = h; asm volatile("" :: "v"(l2), "v"(h2)); }
 #else
-                            __builtin_nontemporal_store(f4{l.x, l.y, h.x, h.y}, reinterpret_cast<f4*>(ob + (voff + 1024u * static_cast<unsigned>(i))));
+                            if constexpr (OB == 4) __builtin_nontemporal_store(f4{l.x, l.y, h.x, h.y}, reinterpret_cast<f4*>(ob + (voff + 1024u * static_cast<unsigned>(i))));
+                            else team16_store4<OT>(ob + (voff + (256u * OB) * static_cast<unsigned>(i)), l, h);
 #endif
                         };
                         const float4 tts[3] = {t0, t1, t2};

@@ -20,6 +20,7 @@
 #include <new>
 #include <thread>
 #include <vector>
+#include <type_traits>
 
 #include "fsst_kernels.hpp"
 #include "fsst_mfma128.hpp"
@@ -32,6 +33,7 @@
 #include "fsst_dft.hpp"
 #include "fsst_gather.hpp"
 #include "fsst_ragged.hpp"
+#include "fsst_half.hpp"
 #include "fourier_resample.hpp"
 #include "fourier_resample_gpu.hpp"
 #include <cstdlib>
@@ -223,6 +225,9 @@ constexpr int kFpw128 = HSS_FPW128;      // frames per wave tile of the nwin = 1
 struct hssfsst_plan {
     int device = -1;
     int nwin = 0, R = 0, nf = 0, klo = 0, K = 0, mode = 0;
+    int out_dtype = HSSFSST_DTYPE_F32;                       // HSSFSST_DTYPE_F32, or F16 / BF16 (STACK only): element type of every exec's `out`
+    size_t out_es = sizeof(float);                           // ... its size in bytes
+    float* d_f32 = nullptr;       size_t f32_cap = 0;        // half plans: float32 features of the paths whose z-score is a second sweep (floats)
     double fs = 0.0;
     float* d_ctab = nullptr;      // generic kernel: class-folded scalar tables
     float* d_dtab = nullptr;      // any-length kernel (fsst_dft.hpp): A operand [source block][k-step][64 lanes]
@@ -555,10 +560,23 @@ int ensure_team_words(hssfsst_plan* pl, hipStream_t st)
 
 // Team kernel at four waves per SIMD (fsst_team16.hpp): canonical band, STACK, one 16-frame group per ticket, one group image
 // held in registers.  Returns 1 when it launched, 0 when this exec should take another path, < 0 on error.
-template <int KLO, int KC, int WPB, int DEPTH>
-int launch_team16(hssfsst_plan* pl, const hssfsst::Core128Params& cp, int64_t batch, int ngroups, hipStream_t st)
+// the team kernel of output type OT: the float32 kernel, or the half-precision one (fsst_team16.hpp)
+template <int KLO, int KC, int WPB, int DEPTH, class OT>
+constexpr auto team16_kernel()
+{
+    return &hssfsst::fsst_team16_kernel<KLO, KC, WPB, DEPTH, OT>;
+}
+template <class OT>
+constexpr const char* out_type_suffix() { return sizeof(OT) == 4 ? "" : std::is_same<OT, _Float16>::value ? ", f16" : ", bf16"; }
+
+// OT = _Float16 / __bf16: a half plan's team launch; it stores its z-scores as 2-byte elements at hout (8-byte aligned, else 0)
+template <int KLO, int KC, int WPB, int DEPTH, class OT = float>
+int launch_team16(hssfsst_plan* pl, const hssfsst::Core128Params& cp, int64_t batch, int ngroups, hipStream_t st, void* hout = nullptr)
 {
     using namespace hssfsst;
+    if constexpr (sizeof(OT) == 2) {
+        if (hout == nullptr || (reinterpret_cast<uintptr_t>(hout) & 7) != 0) return 0;
+    }
     const int G = ngroups;
     if (G < 1 || G > kFusedMaxGroups) return 0;             // (the resolver's LDS copy of a signal's partials: 128 groups)
     // (at least 84 KiB: one block per CU whatever its size -- the teams count on it)
@@ -567,7 +585,7 @@ int launch_team16(hssfsst_plan* pl, const hssfsst::Core128Params& cp, int64_t ba
     size_t lds = (kCanonLdsTabFloats + t16_ctl_floats(PSLOTS, MS) + static_cast<size_t>(WPB) * CanonCfg<KLO, KC>::wave_floats(t16_planes<KLO, KC>())) * sizeof(float);
     if (lds > static_cast<size_t>(kMaxLdsBytes)) return 0;
     if (lds < 84 * 1024) lds = 84 * 1024;
-    auto kern = fsst_team16_kernel<KLO, KC, WPB, DEPTH>;
+    auto kern = team16_kernel<KLO, KC, WPB, DEPTH, OT>();
     static std::atomic<unsigned long long> lds_ok{0};
     if (int rc = allow_full_lds(kern, pl->device, lds_ok)) return rc;
     if (pl->team16_cus == 0) {
@@ -617,7 +635,7 @@ int launch_team16(hssfsst_plan* pl, const hssfsst::Core128Params& cp, int64_t ba
         pl->team_seq = 1;
     }
     Team16Params tp{};
-    tp.x = cp.x; tp.out = cp.out; tp.atab = pl->d_atab16; tp.wtab = cp.wtab; tp.twtab = cp.twtab;
+    tp.x = cp.x; tp.out = sizeof(OT) == 4 ? cp.out : static_cast<float*>(hout); tp.atab = pl->d_atab16; tp.wtab = cp.wtab; tp.twtab = cp.twtab;
     tp.mail = pl->d_mail; tp.status = pl->d_status; tp.r2scale_s = pl->canon_r2s; tp.inv_c = pl->canon_inv_c;
     tp.n = cp.n; tp.nsig = cp.nsig; tp.col0 = cp.col0; tp.ncols = cp.ncols; tp.xstride = cp.xstride;
     tp.team = T; tp.cpc_shift = cpc_shift; tp.slots = slots; tp.seq = pl->team_seq;
@@ -643,7 +661,7 @@ int launch_team16(hssfsst_plan* pl, const hssfsst::Core128Params& cp, int64_t ba
         pl->done_total += static_cast<unsigned>(grid);
         pl->flag_launch = pl->team_launch;
     }
-    name_kernel(pl, WPB, grid, "fsst_team16_kernel<%d, %d, %d, %d> teams of %d", KLO, KC, WPB, DEPTH, T);
+    name_kernel(pl, WPB, grid, "fsst_team16_kernel<%d, %d, %d, %d%s> teams of %d", KLO, KC, WPB, DEPTH, out_type_suffix<OT>(), T);
     hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(grid)), dim3(64 * WPB), lds, st, tp);
     HIP_TRY(hipGetLastError());
     return 1;
@@ -843,9 +861,13 @@ int launch_core128_plain(hssfsst_plan* pl, const hssfsst::Core128Params& cp, int
     return fail(HSSFSST_EUNSUPPORTED, "LDS request %zu B per wave exceeds the 160 KiB budget", per_wave);
 }
 
+// hout != nullptr (half plans): the team kernel stores the features there as 2-byte elements; every other kernel writes float32
+// features to dout for a second, out-of-place z-score sweep (exec_impl) -- the single-launch kernels that normalise in float32 in
+// place (one CU per signal, fsst_core128_kernel's fused epilogues) are not taken
 int launch_core128(hssfsst_plan* pl, const float* dx, long long xstride, float* dout, float* partials, int n, int col0,
-                   int ncols, int64_t batch, hipStream_t st, bool try_fused, bool* did_fuse)
+                   int ncols, int64_t batch, hipStream_t st, bool try_fused, bool* did_fuse, void* hout = nullptr)
 {
+    const bool half = hout != nullptr;
     hssfsst::Core128Params cp{};
     cp.xstride = xstride;
     cp.x = dx; cp.out = dout; cp.partials = partials; cp.atab = pl->d_atab;
@@ -883,7 +905,12 @@ int launch_core128(hssfsst_plan* pl, const float* dx, long long xstride, float* 
         const bool paused = pl->team_pause > 0 && !team_only;
         if (paused && canon16 && !no_team) --pl->team_pause;
         if (!no_team && canon16 && !paused) {
-            rc = canon_dispatch(pl, [&](auto KL, auto KN) { return launch_team16<decltype(KL)::value, decltype(KN)::value, HSS_T16_WPB, HSS_T16_DEPTH>(pl, cp, batch, ngroups, st); });
+            rc = canon_dispatch(pl, [&](auto KL, auto KN) {
+                constexpr int kl = decltype(KL)::value, kn = decltype(KN)::value;
+                if (pl->out_dtype == HSSFSST_DTYPE_F16) return launch_team16<kl, kn, HSS_T16_WPB, HSS_T16_DEPTH, _Float16>(pl, cp, batch, ngroups, st, hout);
+                if (pl->out_dtype == HSSFSST_DTYPE_BF16) return launch_team16<kl, kn, HSS_T16_WPB, HSS_T16_DEPTH, __bf16>(pl, cp, batch, ngroups, st, hout);
+                return launch_team16<kl, kn, HSS_T16_WPB, HSS_T16_DEPTH>(pl, cp, batch, ngroups, st);
+            });
             if (rc == 1) {
                 // the team kernel may give the launch up (its blocks wait for each other; other processes on the GPU can keep
                 // them apart: fsst_team16.hpp "Progress"): the same exec is queued behind it, every kernel of it gated on the
@@ -909,7 +936,7 @@ int launch_core128(hssfsst_plan* pl, const float* dx, long long xstride, float* 
                 // ONE gated launch where the one-CU-per-signal kernel applies (signals of 16 .. 32 chunks; its batch
                 // conditions are about speed only): 4 us behind the team kernel instead of 11 for transform + statistics +
                 // z-score launches -- a third of a 50-window exec
-                const int rc1 = launch_canon_fused(pl, cp, batch, ngroups, st, true);
+                const int rc1 = half ? 0 : launch_canon_fused(pl, cp, batch, ngroups, st, true);
                 if (rc1 < 0) { pl->gate = nullptr; return rc1; }
                 if (rc1 == 1) { pl->gate = nullptr; *did_fuse = true; return 0; }
                 const int rc2 = launch_canon(pl, cp, nchunks, st);
@@ -919,14 +946,14 @@ int launch_core128(hssfsst_plan* pl, const float* dx, long long xstride, float* 
             }
             if (rc < 0) return rc;
         }
-        if (!team_only) {
+        if (!team_only && !half) {
             rc = canon16 ? launch_canon_fused(pl, cp, batch, ngroups, st)
                  : canon ? launch_fused128<3>(pl, cp, batch, ngroups, st) : launch_fused128<-1>(pl, cp, batch, ngroups, st);
         }
         if (rc < 0) return rc;
         if (rc == 1) { *did_fuse = true; pl->last_zpath = 1; return 0; }
     }
-    if (try_fused && !fast && rq == 8 && nt == 16 && pl->mode == HSSFSST_MODE_STACK && pl->zpath_pref != HSSFSST_ZPATH_TEAM &&
+    if (try_fused && !half && !fast && rq == 8 && nt == 16 && pl->mode == HSSFSST_MODE_STACK && pl->zpath_pref != HSSFSST_ZPATH_TEAM &&
         fixed + 16 * per_wave <= room) {
         // nwin 128, a band the wide-store epilogue does not take (odd K or K > 24)
         const int rc = launch_fused_general<16, 8, 16, -1>(pl, cp, batch, (ncols + 15) / 16, st);
@@ -934,7 +961,7 @@ int launch_core128(hssfsst_plan* pl, const float* dx, long long xstride, float* 
         if (rc == 1) { *did_fuse = true; pl->last_zpath = 1; return 0; }
     }
 #ifndef HSS_DEV_ONLY128
-    if (try_fused && !fast && rq == 16 && pl->mode == HSSFSST_MODE_STACK && pl->zpath_pref != HSSFSST_ZPATH_TEAM) {
+    if (try_fused && !half && !fast && rq == 16 && pl->mode == HSSFSST_MODE_STACK && pl->zpath_pref != HSSFSST_ZPATH_TEAM) {
         // nwin 256 / 512 (general epilogue): one CU per signal, the z-score as tickets of the same launch; waves per block
         // as on the two-launch path (what fits the LDS: 8 for the canonical band at 256 points, 3 at 512)
         const int ngroups = (ncols + 15) / 16;
@@ -1023,10 +1050,22 @@ double hssfsst_update_variance(double x, double m, double var, int64_t k)
 int hssfsst_plan_create(hssfsst_plan** out, int device, int nwin, const double* window, double fs,
                         int has_band, double f_lo, double f_hi, int mode)
 {
+    return hssfsst_plan_create_ex(out, device, nwin, window, fs, has_band, f_lo, f_hi, mode, HSSFSST_DTYPE_F32);
+}
+
+int hssfsst_plan_create_ex(hssfsst_plan** out, int device, int nwin, const double* window, double fs,
+                           int has_band, double f_lo, double f_hi, int mode, int out_dtype)
+{
     if (!out) return fail(HSSFSST_EINVAL, "plan_create: out is NULL");
     *out = nullptr;
     if (!window || nwin < 1 || !(fs > 0.0) || mode < 0 || mode > HSSFSST_MODE_STACK_UNNORM)
         return fail(HSSFSST_EINVAL, "plan_create: bad argument (nwin=%d fs=%g mode=%d)", nwin, fs, mode);
+    // (before any device is touched) half-precision output is the z-scored STACK features' only: RAW stays complex64, ABS and the
+    // streaming STACK_UNNORM stay float32; float64 output does not exist
+    if (out_dtype != HSSFSST_DTYPE_F32 && out_dtype != HSSFSST_DTYPE_F16 && out_dtype != HSSFSST_DTYPE_BF16)
+        return fail(HSSFSST_EINVAL, "plan_create: output dtype %d is not HSSFSST_DTYPE_F32 / F16 / BF16", out_dtype);
+    if (out_dtype != HSSFSST_DTYPE_F32 && mode != HSSFSST_MODE_STACK)
+        return fail(HSSFSST_EINVAL, "plan_create: half-precision output (dtype %d) is for HSSFSST_MODE_STACK only, not mode %d", out_dtype, mode);
     if (nwin > 65535) return fail(HSSFSST_EUNSUPPORTED, "plan_create: window length %d exceeds 65535", nwin);
     const bool force_dft = debug_switches().force_dft;    // cross-check: every length on the any-length kernel
     const bool radix_len = nwin == 32 || nwin == 64 || nwin == 128 || nwin == 256 || nwin == 512;
@@ -1043,6 +1082,7 @@ int hssfsst_plan_create(hssfsst_plan** out, int device, int nwin, const double* 
     hssfsst_plan* p = new (std::nothrow) hssfsst_plan();
     if (!p) return fail(HSSFSST_ENOMEM, "plan_create: host allocation failed");
     p->device = device; p->nwin = nwin; p->R = nwin / 32; p->nf = nwin / 2 + 1; p->mode = mode; p->fs = fs;
+    p->out_dtype = out_dtype; p->out_es = out_dtype == HSSFSST_DTYPE_F32 ? sizeof(float) : 2;
     if (has_band) band_rows(nwin, fs, f_lo, f_hi, &p->klo, &p->K);
     else { p->klo = 0; p->K = p->nf; }
 
@@ -1306,6 +1346,7 @@ int hssfsst_plan_destroy(hssfsst_plan* p)
     if (p->d_stream_arrive) (void)hipFree(p->d_stream_arrive);
     if (p->d_stream_pieces) (void)hipFree(p->d_stream_pieces);
     if (p->d_partials) (void)hipFree(p->d_partials);
+    if (p->d_f32) (void)hipFree(p->d_f32);
     if (p->h_status) (void)hipHostFree(const_cast<unsigned*>(p->h_status));
     if (p->d_mail) (void)hipFree(p->d_mail);
     if (p->d_arrive) (void)hipFree(p->d_arrive);
@@ -1342,6 +1383,13 @@ int hssfsst_plan_info(const hssfsst_plan* p, int* nwin, int* nf, int* klo, int* 
     return 0;
 }
 
+
+int hssfsst_plan_out_dtype(const hssfsst_plan* p, int* out_dtype)
+{
+    if (!p || !out_dtype) return fail(HSSFSST_EINVAL, "plan_out_dtype: bad argument");
+    *out_dtype = p->out_dtype;
+    return 0;
+}
 
 int hssfsst_plan_last_exec_fused(const hssfsst_plan* p) { return (p && p->last_fused) ? p->last_zpath : 0; }
 
@@ -1534,7 +1582,9 @@ static int exec_impl(hssfsst_plan* p, const float* x, int64_t batch, int n, int6
     if (static_cast<long long>(n) * 2 * p->nf >= 0x7fffffffLL) return fail(HSSFSST_EINVAL, "exec: signal too long (n = %d)", n);
     // input extent: `batch` signals of n samples whose starts are x_stride apart (they may overlap)
     const size_t nx = d_starts ? x_len : static_cast<size_t>(batch > 0 ? batch - 1 : 0) * static_cast<size_t>(x_stride) + n;
-    const size_t no = static_cast<size_t>(batch) * ncols * ofps;
+    const size_t no = static_cast<size_t>(batch) * ncols * ofps;               // output elements
+    const size_t es = p->out_es, no_f = (no * es + sizeof(float) - 1) / sizeof(float);   // their bytes per element; floats that hold them
+    const bool half = es != sizeof(float);
 
     const float* dx = x;
     float* dout = out;
@@ -1547,7 +1597,7 @@ static int exec_impl(hssfsst_plan* p, const float* x, int64_t batch, int n, int6
     const bool tiny_in = !x_on_device && nx <= (static_cast<size_t>(1) << 16);
     // (STACK: only where the team kernel will take the exec -- its features are written once; a z-score that is a second pass would
     //  read and rewrite them in place over PCIe: signals of more than 128 groups keep the device staging buffer + one copy)
-    const bool tiny_out = tiny_in && !out_on_device && no <= (static_cast<size_t>(1) << 21) &&
+    const bool tiny_out = tiny_in && !out_on_device && no_f <= (static_cast<size_t>(1) << 21) &&
                           (p->mode != HSSFSST_MODE_STACK || (plan_is_canon(p) && (col0 & 15) == 0 && !debug_switches().no_team &&
                                                              p->zpath_pref != HSSFSST_ZPATH_ONE_CU && p->zpath_pref != HSSFSST_ZPATH_TWO_LAUNCH &&
                                                              (p->team_pause == 0 || p->zpath_pref == HSSFSST_ZPATH_TEAM) &&
@@ -1589,14 +1639,21 @@ static int exec_impl(hssfsst_plan* p, const float* x, int64_t batch, int n, int6
     if (tiny_out) {
         if (pin_d) dout = pin_d;
         else {
-            if ((rc = pin(&p->h_opin, &p->d_opin, &p->opin_cap, no)) != 0) return rc;
+            if ((rc = pin(&p->h_opin, &p->d_opin, &p->opin_cap, no_f)) != 0) return rc;
             dout = p->d_opin;
         }
         p->defer_fallback = p->zpath_pref != HSSFSST_ZPATH_ONE_CU && !d_starts;
         p->deferred_launch = 0u;
     } else if (!out_on_device) {
-        if ((rc = grow(reinterpret_cast<void**>(&p->d_ostage), &p->ostage_cap, no, sizeof(float))) != 0) return rc;
+        if ((rc = grow(reinterpret_cast<void**>(&p->d_ostage), &p->ostage_cap, no_f, sizeof(float))) != 0) return rc;
         dout = p->d_ostage;
+    }
+    // half plans: dout receives 2-byte elements; the kernels that write float32 features (every path but the team kernel, and the
+    // gated fallback behind a team launch) write them to the plan's float32 scratch, and the z-score sweep goes from there to dout
+    float* kout = dout;
+    if (half) {
+        if ((rc = grow(reinterpret_cast<void**>(&p->d_f32), &p->f32_cap, no, sizeof(float))) != 0) return rc;
+        kout = p->d_f32;
     }
     if (p->mode == HSSFSST_MODE_STACK)
     {
@@ -1643,7 +1700,8 @@ static int exec_impl(hssfsst_plan* p, const float* x, int64_t batch, int n, int6
     for (int64_t c0 = 0; c0 < batch; c0 += chunk, ++ci) {
         const int64_t cb = (batch - c0 < chunk) ? batch - c0 : chunk;
         const float* cx = dx + c0 * x_stride;
-        float* cout = dout + c0 * per;
+        float* cout = kout + c0 * per;
+        void* hcout = half ? static_cast<void*>(reinterpret_cast<char*>(dout) + static_cast<size_t>(c0 * per) * es) : nullptr;
         hssfsst::CoreParams cp;
         cp.x = cx; cp.out = cout; cp.partials = p->d_partials ? p->d_partials + c0 * nblk * hssfsst::kPartFloats : nullptr; cp.ctab = p->d_ctab;
         cp.n = n; cp.klo = p->klo; cp.K = p->K; cp.mode = p->mode; cp.nblk = nblk; cp.col0 = col0; cp.ncols = ncols; cp.xstride = x_stride;
@@ -1693,7 +1751,8 @@ static int exec_impl(hssfsst_plan* p, const float* x, int64_t batch, int n, int6
             };
             rc = (G == 4) ? launch(hssfsst::fsst_dft_kernel<4>) : (G == 2) ? launch(hssfsst::fsst_dft_kernel<2>) : launch(hssfsst::fsst_dft_kernel<1>);
         } else if (use128) {
-            rc = launch_core128(p, cx, x_stride, cout, cp.partials, n, col0, ncols, cb, st, !no_fused && !piped && p->zpath_pref != HSSFSST_ZPATH_TWO_LAUNCH, &did_fuse);
+            rc = launch_core128(p, cx, x_stride, cout, cp.partials, n, col0, ncols, cb, st, !no_fused && !piped && p->zpath_pref != HSSFSST_ZPATH_TWO_LAUNCH, &did_fuse,
+                                hcout);
         } else switch (p->R) {
             case 1: rc = launch_core<1>(p, cp, cblocks, st); break;
             case 2: rc = launch_core<2>(p, cp, cblocks, st); break;
@@ -1742,6 +1801,14 @@ static int exec_impl(hssfsst_plan* p, const float* x, int64_t batch, int n, int6
             if (!fused)
                 hipLaunchKernelGGL(hssfsst::fsst_stats_kernel, dim3(static_cast<unsigned>(cb)), dim3(64), 0, zs,
                                    cp.partials, cstats, nblk, fpp, ncols, p->K, gate, gate_val);
+            if (half) {                                  // out of place: float32 scratch -> 2-byte elements (fsst_half.hpp)
+                auto sweep = [&](auto* o) {
+                    hipLaunchKernelGGL(hssfsst::fsst_normalize_to_kernel<std::remove_pointer_t<decltype(o)>>, dim3(static_cast<unsigned>(zgrid)), dim3(256), 0, zs,
+                                       cout, o, cstats, fused ? cp.partials : nullptr, nblk, fpp, ncols, p->K, static_cast<int>(cb), slices,
+                                       gate, gate_val);
+                };
+                if (p->out_dtype == HSSFSST_DTYPE_F16) sweep(static_cast<_Float16*>(hcout)); else sweep(static_cast<__bf16*>(hcout));
+            } else
             hipLaunchKernelGGL(hssfsst::fsst_normalize_kernel, dim3(static_cast<unsigned>(zgrid)), dim3(256), 0, zs,
                                cout, cstats, fused ? cp.partials : nullptr, nblk, fpp, ncols, p->K, static_cast<int>(cb), slices,
                                gate, gate_val);
@@ -1813,9 +1880,9 @@ static int exec_impl(hssfsst_plan* p, const float* x, int64_t batch, int n, int6
                 return fail(HSSFSST_EHIP, "fused z-score: a wait inside the kernel gave up (code %u); results of that exec are invalid", code);
             }
         } else if (p->d_status && (rc = hssfsst_plan_check(p)) != 0) return rc;
-        if (!pin_d) std::memcpy(out, p->h_opin, no * sizeof(float));
+        if (!pin_d) std::memcpy(out, p->h_opin, no * es);
     } else if (!out_on_device) {
-        HIP_TRY(hipMemcpyAsync(out, dout, no * sizeof(float), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(out, dout, no * es, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         if (p->d_status && (rc = hssfsst_plan_check(p)) != 0) return rc;
     } else if (!x_on_device) {
@@ -1839,7 +1906,7 @@ int hssfsst_exec_pinned(hssfsst_plan* p, const float* x, int n, float** out)
     *out = nullptr;
     if (p->K == 0) return 1;
     DEVICE_SCOPE(p->device);
-    const size_t no = static_cast<size_t>(n) * out_floats_per_sample(p);
+    const size_t no = static_cast<size_t>(n) * out_floats_per_sample(p);      // elements (2 bytes each in a half plan); caps count elements
     hssfsst_plan::PinBuf* b = nullptr;
     for (auto& c : p->pin_pool) if (!c.used && c.cap >= no) { b = &c; break; }
     if (!b) {
@@ -1853,7 +1920,7 @@ int hssfsst_exec_pinned(hssfsst_plan* p, const float* x, int n, float** out)
         size_t c = 1 << 12;
         while (c < no) c *= 2;
         void* hp = nullptr; void* dp = nullptr;
-        HIP_TRY(hipHostMalloc(&hp, c * sizeof(float), hipHostMallocMapped));
+        HIP_TRY(hipHostMalloc(&hp, c * p->out_es, hipHostMallocMapped));
         HIP_TRY(hipHostGetDevicePointer(&dp, hp, 0));
         b->h = static_cast<float*>(hp); b->d = static_cast<float*>(dp); b->cap = c;
     }
@@ -1923,7 +1990,8 @@ int hssfsst_exec_ragged(hssfsst_plan* p, const float* x, int64_t x_len, const in
         long long off = 0;
         for (int64_t i = 0; i < batch; ++i) {
             const int n = static_cast<int>(lens[i]);
-            if (int rc = exec_impl(p, x + starts[i], 1, n, n, nullptr, 0, 0, n, x_on_device, out + off * ofps, out_on_device, stream)) return rc;
+            float* o = reinterpret_cast<float*>(reinterpret_cast<char*>(out) + static_cast<size_t>(off) * ofps * p->out_es);
+            if (int rc = exec_impl(p, x + starts[i], 1, n, n, nullptr, 0, 0, n, x_on_device, o, out_on_device, stream)) return rc;
             off += n;
         }
         return 0;
@@ -1945,7 +2013,9 @@ int hssfsst_exec_ragged(hssfsst_plan* p, const float* x, int64_t x_len, const in
     if (x_on_device) xlo = 0;
     long long cols = 0, groups = 0;
     for (int64_t i = 0; i < batch; ++i) { cols += lens[i]; groups += (lens[i] + 15) / 16; }
-    const size_t no = static_cast<size_t>(cols) * ofps;
+    const size_t no = static_cast<size_t>(cols) * ofps;                       // output elements
+    const size_t es = p->out_es, no_f = (no * es + sizeof(float) - 1) / sizeof(float);
+    const bool half = es != sizeof(float);
     int rc;
 
     // the tables (kept while the list's lengths and offsets stay the same)
@@ -2004,8 +2074,13 @@ int hssfsst_exec_ragged(hssfsst_plan* p, const float* x, int64_t x_len, const in
         dx = p->d_xstage;
     }
     if (!out_on_device) {
-        if ((rc = grow(reinterpret_cast<void**>(&p->d_ostage), &p->ostage_cap, no, sizeof(float))) != 0) return rc;
+        if ((rc = grow(reinterpret_cast<void**>(&p->d_ostage), &p->ostage_cap, no_f, sizeof(float))) != 0) return rc;
         dout = p->d_ostage;
+    }
+    float* kout = dout;                                  // (half plans: the float32 features go to the plan's scratch, as in exec_impl)
+    if (half) {
+        if ((rc = grow(reinterpret_cast<void**>(&p->d_f32), &p->f32_cap, no, sizeof(float))) != 0) return rc;
+        kout = p->d_f32;
     }
     if (p->mode == HSSFSST_MODE_STACK) {
         if ((rc = grow(reinterpret_cast<void**>(&p->d_partials), &p->partials_cap, static_cast<size_t>(groups) * hssfsst::kPartFloats, sizeof(float))) != 0) return rc;
@@ -2017,7 +2092,7 @@ int hssfsst_exec_ragged(hssfsst_plan* p, const float* x, int64_t x_len, const in
     hipEvent_t evt = nullptr;
     if (p->timing) { if ((rc = plan_next_event(p, &evt)) != 0) return rc; HIP_TRY(hipEventRecord(evt, st)); }
     hssfsst::Core128Params cp{};
-    cp.x = dx; cp.out = dout; cp.partials = p->d_partials; cp.atab = p->d_atab;
+    cp.x = dx; cp.out = kout; cp.partials = p->d_partials; cp.atab = p->d_atab;
     cp.wtab = p->d_wtab; cp.twtab = p->d_wtab + 2 * p->nwin; cp.r2scale = p->r2scale;
     cp.n = 1; cp.klo = p->klo; cp.K = p->K; cp.mode = p->mode; cp.nsig = static_cast<int>(std::min<int64_t>(batch, 0x7fffffff));
     cp.col0 = 0; cp.ncols = 1; cp.xstride = 0;
@@ -2038,6 +2113,13 @@ int hssfsst_exec_ragged(hssfsst_plan* p, const float* x, int64_t x_len, const in
         float4* stats = reinterpret_cast<float4*>(p->d_stats);
         hipLaunchKernelGGL(hssfsst::fsst_ragged_stats_kernel, dim3(static_cast<unsigned>(batch)), dim3(64), 0, st, p->d_partials, d_rsig, stats, p->K);
         const long long zgrid = std::min<long long>(p->rtab_nunits, 65536);
+        if (half) {                                      // out of place: float32 scratch -> 2-byte elements (fsst_half.hpp)
+            auto sweep = [&](auto* o) {
+                hipLaunchKernelGGL(hssfsst::fsst_ragged_normalize_to_kernel<std::remove_pointer_t<decltype(o)>>, dim3(static_cast<unsigned>(zgrid)), dim3(256), 0, st,
+                                   kout, o, d_rsig, d_unit0, stats, static_cast<int>(batch), p->K);
+            };
+            if (p->out_dtype == HSSFSST_DTYPE_F16) sweep(reinterpret_cast<_Float16*>(dout)); else sweep(reinterpret_cast<__bf16*>(dout));
+        } else
         hipLaunchKernelGGL(hssfsst::fsst_ragged_normalize_kernel, dim3(static_cast<unsigned>(zgrid)), dim3(256), 0, st, dout, d_rsig, d_unit0,
                            stats, static_cast<int>(batch), p->K);
         HIP_TRY(hipGetLastError());
@@ -2048,7 +2130,7 @@ int hssfsst_exec_ragged(hssfsst_plan* p, const float* x, int64_t x_len, const in
         p->ev_chunks.push_back(1);
     }
     if (!out_on_device) {
-        HIP_TRY(hipMemcpyAsync(out, dout, no * sizeof(float), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(out, dout, no * es, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         if (p->d_status && (rc = hssfsst_plan_check(p)) != 0) return rc;
     } else if (!x_on_device) {

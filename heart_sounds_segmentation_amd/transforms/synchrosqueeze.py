@@ -33,25 +33,30 @@ def _release_pinned(plan, addr: int) -> None:
 _LENT_TYPES = {}
 
 
-def _lent_type(nfl: int):
-    """ctypes float array type over a LENT pinned pool buffer: the numpy array / tensor made from an instance keeps it alive, and when the last
-    view of the result is gone the instance's ``__del__`` hands the buffer back (``hssfsst_pinned_release``).  (A subclass with ``__del__``
-    + ``np.frombuffer`` + ``torch.from_numpy`` costs 1.4 us per call; ``weakref.finalize`` + ``torch.frombuffer`` + ``view`` cost 3.3.)"""
-    T = _LENT_TYPES.get(nfl)
+def _lent_type(nfl: int, elem=ctypes.c_float):
+    """ctypes array type (``nfl`` elements of ``elem``: float, or a 2-byte integer for a half-precision plan's elements) over a LENT
+    pinned pool buffer: the numpy array / tensor made from an instance keeps it alive, and when the last view of the result is gone the
+    instance's ``__del__`` hands the buffer back (``hssfsst_pinned_release``).  (A subclass with ``__del__`` + ``np.frombuffer`` +
+    ``torch.from_numpy`` costs 1.4 us per call; ``weakref.finalize`` + ``torch.frombuffer`` + ``view`` cost 3.3.)"""
+    T = _LENT_TYPES.get((nfl, elem))
     if T is None:
-        class _Lent(ctypes.c_float * nfl):
+        class _Lent(elem * nfl):
             _plan = None
 
             def __del__(self):
                 _release_pinned(self._plan, ctypes.addressof(self))
-        T = _LENT_TYPES[nfl] = _Lent
+        T = _LENT_TYPES[(nfl, elem)] = _Lent
     return T
+
+
+# output element types of STACK features (hssfsst_plan_create_ex): torch dtype -> HSSFSST_DTYPE_*
+_OUT_DTYPES = {torch.float32: _lib.DTYPE_F32, torch.float16: _lib.DTYPE_F16, torch.bfloat16: _lib.DTYPE_BF16}
 
 
 class _Plan:
     """Owner of one ``hssfsst_plan*`` (created lazily in the calling process: fork-safe)."""
 
-    def __init__(self, device_index: int, window: np.ndarray, fs: float, band, mode: int):
+    def __init__(self, device_index: int, window: np.ndarray, fs: float, band, mode: int, out_dtype: torch.dtype = torch.float32):
         _lib.guard_fork()
         L = _lib.lib()
         self._L = L
@@ -59,13 +64,15 @@ class _Plan:
         w = np.ascontiguousarray(window, dtype=np.float64).ravel()
         has_band = 1 if band else 0
         lo, hi = (float(band[0]), float(band[1])) if band else (0.0, 0.0)
-        rc = L.hssfsst_plan_create(ctypes.byref(self.handle), int(device_index), int(w.size),
-                                   w.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), float(fs),
-                                   has_band, lo, hi, int(mode))
-        _lib.check(rc, "hssfsst_plan_create")
+        rc = L.hssfsst_plan_create_ex(ctypes.byref(self.handle), int(device_index), int(w.size),
+                                      w.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), float(fs),
+                                      has_band, lo, hi, int(mode), _OUT_DTYPES[out_dtype])
+        _lib.check(rc, "hssfsst_plan_create_ex")
         vals = [ctypes.c_int() for _ in range(7)]
         _lib.check(L.hssfsst_plan_info(self.handle, *[ctypes.byref(v) for v in vals]), "hssfsst_plan_info")
         self.nwin, self.nf, self.klo, self.K, self.ofps, self.mode, self.device = [v.value for v in vals]
+        # the element type of the plan's time-major features (RAW is complex64 whatever this says)
+        self.out_dtype = out_dtype
         self.pid = os.getpid()
 
     def __del__(self):
@@ -79,7 +86,7 @@ class _Plan:
 class RaggedFeatures(_SequenceABC):
     """The features of ``FSST.ragged``: signals of different lengths, packed back to back in ONE arena.
 
-    ``data``: the arena -- ``(sum T_i, C)`` float32 for ``abs`` / ``stack`` (C = K / 2K), ``(K * sum T_i,)`` complex64 for the raw
+    ``data``: the arena -- ``(sum T_i, C)`` float32 for ``abs`` / ``stack`` (C = K / 2K; ``stack`` in the transform's ``out_dtype``), ``(K * sum T_i,)`` complex64 for the raw
     transform (signal i's ``(K, T_i)`` block at ``K * offsets[i]``); ``offsets``: int64 ``(B + 1,)`` in samples.  ``len``, iteration
     and ``[i]`` work as on a list; item i is a view with exactly the shape, dtype and device ``FSST.__call__`` / ``FSST.batch`` give
     for signal i alone."""
@@ -134,8 +141,12 @@ class FSST:
         abs: return ``abs(s).t()`` -> float32 ``(n, K)``.
         stack: return the z-scored real and imaginary parts stacked -> float32 ``(n, 2K)``.
         truncate_freq: ``(lo, hi)`` in Hz, inclusive; keeps K rows.  None/empty keeps all.
-        dtype: kept for signature parity (the reference only uses it for ``f``/``t``).
+        dtype: kept for signature parity (the reference only uses it for ``f``/``t``; not the features' type).
         device (extension): torch device for the computation; default ``cuda`` (current device).
+        out_dtype (extension): element type of the ``stack`` features -- ``torch.float32`` (default), ``torch.float16`` or
+            ``torch.bfloat16``.  A half type is written by the kernels themselves and equals the float32 result cast with
+            ``.to(out_dtype)`` bit for bit (NaN where float32 has NaN).  Only with ``stack=True`` and not ``abs``: ``ValueError``
+            otherwise.  ``unnormalized()`` stays float32.
     Precedence as in ``__call__`` (synchrosqueeze.py:56-65): truncate, then ``abs`` wins over
     ``stack``, else the raw complex64 ``(K, n)`` spectrum.
     """
@@ -149,7 +160,13 @@ class FSST:
         truncate_freq: Optional[tuple] = None,
         dtype: torch.dtype = torch.float32,
         device: Optional[torch.device] = None,
+        out_dtype: torch.dtype = torch.float32,
     ):
+        if out_dtype not in _OUT_DTYPES:
+            raise ValueError(f"FSST: out_dtype must be torch.float32, torch.float16 or torch.bfloat16, got {out_dtype}")
+        if out_dtype != torch.float32 and (abs or not stack):
+            raise ValueError(f"FSST: out_dtype={out_dtype} is for the z-scored stack features only (stack=True, abs=False); "
+                             "abs and the raw transform stay float32 / complex64")
         self.fs: float = fs
         self.window: npt.NDArray = window
         self.abs = abs
@@ -157,6 +174,7 @@ class FSST:
         self.truncate_freq = truncate_freq
         self.dtype = dtype
         self.device = device
+        self.out_dtype = out_dtype
         self._plans = {}
         self._cuda_seen = False
         self._ragged_stage = None                      # pinned staging of ragged() host lists (kept between calls)
@@ -183,13 +201,17 @@ class FSST:
             return d.index if d.index is not None else torch.cuda.current_device()
         return torch.cuda.current_device()
 
+    def _stack_dtype(self) -> torch.dtype:
+        return getattr(self, "out_dtype", torch.float32)
+
     def _plan(self, device_index: int, mode: Optional[int] = None) -> _Plan:
         mode = self._mode() if mode is None else mode
-        key = (os.getpid(), device_index, mode)
+        odt = self._stack_dtype() if mode == _lib.MODE_STACK else torch.float32      # (unnormalized(): float32 whatever out_dtype)
+        key = (os.getpid(), device_index, mode, odt)
         plan = self._plans.get(key)
         if plan is None:
             band = tuple(self.truncate_freq) if self.truncate_freq else None
-            plan = _Plan(device_index, np.asarray(self.window), float(self.fs), band, mode)
+            plan = _Plan(device_index, np.asarray(self.window), float(self.fs), band, mode, odt)
             self._plans[key] = plan
         return plan
 
@@ -237,7 +259,7 @@ class FSST:
         elif m == _lib.MODE_ABS:
             shape, dt = (B, n, K), torch.float32
         else:
-            shape, dt = (B, n, 2 * K), torch.float32
+            shape, dt = (B, n, 2 * K), plan.out_dtype
         if out is None:
             out = torch.empty(shape, dtype=dt, device=odev)
         elif (tuple(out.shape) != shape or out.dtype != dt or out.device != odev
@@ -273,7 +295,7 @@ class FSST:
         float32 (dataset frames, heart_sounds.py:167,181) or float64 (visualisation script).
         A CPU tensor returns a CPU tensor, a cuda tensor (extension) stays on the device.
 
-        Returns: ``stack`` -> float32 ``(n, 2K)``; ``abs`` -> float32 ``(n, K)``; otherwise
+        Returns: ``stack`` -> ``(n, 2K)`` of ``out_dtype`` (float32 by default); ``abs`` -> float32 ``(n, K)``; otherwise
         complex64 ``(K, n)``.
         """
         # the dataset loop's call -- a CPU float32 (n,) / (n, 1) frame, once per 2000 samples (heart_sounds.py:166-168,199-201) --
@@ -294,7 +316,12 @@ class FSST:
                 # out after 64 frames and gets freshly allocated tensors filled by a copy, as before (hssfsst.h: hssfsst_exec_pinned)
                 ptr = ctypes.c_void_p()
                 rc = L.hssfsst_exec_pinned(plan.handle, x.data_ptr(), n, ctypes.byref(ptr))
+                half = plan.out_dtype is not torch.float32 and m == _lib.MODE_STACK
                 if rc == 0:
+                    if half:                             # (2-byte elements: numpy has no bfloat16 -- the bits, viewed as the dtype)
+                        buf = _lent_type(n * plan.ofps, ctypes.c_int16).from_address(ptr.value)
+                        buf._plan = plan
+                        return torch.from_numpy(np.frombuffer(buf, dtype=np.int16).reshape(n, 2 * K)).view(plan.out_dtype)
                     buf = _lent_type(n * plan.ofps).from_address(ptr.value)
                     buf._plan = plan
                     if m == _lib.MODE_RAW:
@@ -303,7 +330,7 @@ class FSST:
                 if rc < 0:
                     _lib.check(rc, "hssfsst_exec_pinned")
                 out = (torch.empty((K, n), dtype=torch.complex64) if m == _lib.MODE_RAW
-                       else torch.empty((n, K if m == _lib.MODE_ABS else 2 * K), dtype=torch.float32))
+                       else torch.empty((n, K if m == _lib.MODE_ABS else 2 * K), dtype=plan.out_dtype if half else torch.float32))
                 _lib.check(L.hssfsst_exec_frames(plan.handle, x.data_ptr(), 1, n, n, 0, n, 0, out.data_ptr(), 0, None),
                            "hssfsst_exec_frames")
                 return out
@@ -355,7 +382,7 @@ class FSST:
         elif m == _lib.MODE_ABS:
             shape, dt = (B, n, K), torch.float32
         else:
-            shape, dt = (B, n, 2 * K), torch.float32
+            shape, dt = (B, n, 2 * K), plan.out_dtype
         if out is None:
             out = torch.empty(shape, dtype=dt, device=x.device)
         elif tuple(out.shape) != shape or out.dtype != dt or out.device != x.device or not out.is_contiguous():
@@ -424,7 +451,7 @@ class FSST:
         offsets = torch.from_numpy(np.concatenate([[0], np.cumsum(lens)]).astype(np.int64))
         klo, K = self.band()
         C = K if self.abs else 2 * K
-        shape, dt = ((K * total,), torch.complex64) if raw else ((total, C), torch.float32)
+        shape, dt = ((K * total,), torch.complex64) if raw else ((total, C), self._stack_dtype() if self.stack and not self.abs else torch.float32)
         if out is not None and (tuple(out.shape) != shape or out.dtype != dt or out.device != odev or not out.is_contiguous()):
             raise ValueError(f"FSST.ragged: out must be a contiguous {dt} tensor of shape {shape} on {odev}")
         if B == 0:

@@ -60,6 +60,32 @@ int hssfsst_plan_create(hssfsst_plan** out, int device, int nwin, const double* 
                         int has_band, double f_lo, double f_hi, int mode);
 int hssfsst_plan_destroy(hssfsst_plan* plan);
 
+/* Element types of a plan's output and of the resample execs' buffers.  F16 / BF16 (IEEE binary16 / bfloat16, 2 bytes): the
+ * STACK features written in half precision straight from the kernels -- see hssfsst_plan_create_ex. */
+#define HSSFSST_DTYPE_F32 0
+#define HSSFSST_DTYPE_F64 1
+#define HSSFSST_DTYPE_F16 2
+#define HSSFSST_DTYPE_BF16 3
+
+/* hssfsst_plan_create with the element type of every exec's output: hssfsst_plan_create(...) is exactly
+ * hssfsst_plan_create_ex(..., HSSFSST_DTYPE_F32).  out_dtype F16 / BF16 is for HSSFSST_MODE_STACK only (RAW stays complex64, ABS
+ * and STACK_UNNORM float32); an unknown out_dtype, F64, or F16 / BF16 with another mode return HSSFSST_EINVAL before any device
+ * is touched.  A half plan's features are the float32 plan's, each rounded to nearest even (what Tensor.to(dtype) does; NaN
+ * where float32 has NaN, e.g. the 0 / 0 z-score of an all-zero signal).  On a half plan every exec entry point --
+ * hssfsst_exec, _exec_cols, _exec_frames, _exec_list, _exec_ragged, _exec_pinned -- writes 2-byte elements through its `out`
+ * pointer (declared float*: pass the buffer's address); counts and layouts are unchanged (out_floats_per_sample counts
+ * elements, ragged offsets are 64-bit element offsets) and the pinned pool lends buffers of n x 2K x 2 bytes.
+ * Where the features are written: the team kernel (canonical bands, hssfsst_plan_last_exec_fused == 2) stores 2-byte z-scores
+ * from its registers; every other path writes the un-normalised float32 features to a device scratch of the plan (4 bytes x
+ * the exec's element count, kept and grown like the plan's other buffers; allocated for team execs too, for the gated fallback)
+ * and an out-of-place z-score sweep writes the 2-byte result.  The one-CU-per-signal kernels, which normalise float32 in place,
+ * are not taken by half plans (HSSFSST_ZPATH_ONE_CU then means two launches). */
+int hssfsst_plan_create_ex(hssfsst_plan** out, int device, int nwin, const double* window, double fs,
+                           int has_band, double f_lo, double f_hi, int mode, int out_dtype);
+
+/* The plan's output element type (HSSFSST_DTYPE_*). */
+int hssfsst_plan_out_dtype(const hssfsst_plan* plan, int* out_dtype);
+
 /* Plan geometry: nf = nwin/2+1 one-sided rows, klo = first kept row, K = number of kept rows,
  * out_floats_per_sample = floats written per input sample (RAW 2K, ABS K, STACK 2K).
  * Any output pointer may be NULL. */
@@ -68,7 +94,7 @@ int hssfsst_plan_info(const hssfsst_plan* plan, int* nwin, int* nf, int* klo, in
 
 /* Replaces the call ssq.fsst(x, fs, window) (synchrosqueeze.py:48) AND the epilogue :50-65 for
  * `batch` independent signals of `n` samples each (x: float32 [batch][n], contiguous).
- * out: float32, batch * n * out_floats_per_sample elements, laid out per mode (see HSSFSST_MODE_*),
+ * out: float32 (2-byte elements on a half plan: hssfsst_plan_create_ex), batch * n * out_floats_per_sample elements, laid out per mode (see HSSFSST_MODE_*),
  * each signal's block contiguous.  x_on_device / out_on_device: 1 = device pointer on the plan's
  * device, 0 = host pointer.  stream: hipStream_t or NULL.
  * A call with a host `out` returns when the features are in `out`.  For small execs (the dataset loop's one frame per call) it learns that
@@ -266,8 +292,6 @@ int hssfsst_resample(const double* x, int64_t n, int64_t num, double* y);
  * transform's plan.  n < 1, num < 1 or a NULL `out` give HSSFSST_EINVAL before any device is touched; lengths above 2^26
  * samples HSSFSST_EUNSUPPORTED. */
 typedef struct hssfsst_resample_plan hssfsst_resample_plan;
-#define HSSFSST_DTYPE_F32 0
-#define HSSFSST_DTYPE_F64 1
 int hssfsst_resample_plan_create(hssfsst_resample_plan** out, int device, int64_t n, int64_t num);
 int hssfsst_resample_plan_destroy(hssfsst_resample_plan* plan);
 
