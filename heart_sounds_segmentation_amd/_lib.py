@@ -242,6 +242,10 @@ def lib():
         L.hssfsst_resample_plan_info.restype = c_int
         L.hssfsst_resample_exec.argtypes = [vp, vp, c_int, c_i64, c_i64, vp, c_int, c_i64, c_int, vp, c_int, vp, c_int, vp]
         L.hssfsst_resample_exec.restype = c_int
+        L.hssfsst_resample_plan_create_ragged.argtypes = [ctypes.POINTER(vp), c_int, c_i64]
+        L.hssfsst_resample_plan_create_ragged.restype = c_int
+        L.hssfsst_resample_exec_ragged.argtypes = [vp, vp, c_int, c_i64, vp, vp, c_i64, c_int, vp, c_int, vp, c_int, vp]
+        L.hssfsst_resample_exec_ragged.restype = c_int
         L.hssfsst_device_count.restype = c_int
         L.hssfsst_version.restype = c_int
         L.hssfsst_last_error.restype = ctypes.c_char_p

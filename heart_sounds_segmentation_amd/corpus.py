@@ -30,6 +30,13 @@ corpus of them is transformed in groups of at most ``max_samples`` samples, one 
 different lengths: one transform launch plus the z-score), uploads double-buffered as above.  Items are the lazy dataset's
 ``(features (T, 2K) or (T, K), y unchanged or None)``: every recording, the short ones included, and no label shift.
 
+Whole recordings resampled (``build_resampled_recordings``): the lazy dataset with ``Compose([Resample(num), FSST(...)])`` (heart_sounds.py:
+175-184,199-212), where every item is ``(FSST(Resample(num)(x)), round(Resample(num)(y)) - 1)`` of ``num`` samples.  Groups of at most
+``max_samples`` input samples are packed and uploaded as above (label tracks in a second staging pair); each group is ONE ragged
+resample call (``hssfsst_resample_exec_ragged``: recordings of different lengths, every one to ``num``) into a ``(count, num)``
+buffer, one ``FSST.batch`` call on it, and one ragged call with the label rule on the tracks.  Items are views of one
+``(count, num, C)`` arena (``FrameItems``).  ``build_recordings(resample=)`` keeps refusing: its items keep their own lengths.
+
 Multi-GPU (BASELINE config C3): ``rank`` / ``world`` split the RECORDINGS in contiguous
 blocks (``dist.shard_bounds``), so framing stays local to a rank and concatenating the ranks' item lists in rank
 order is the single-process list; ``gather_features`` reassembles the feature tensor on every rank with one
@@ -228,6 +235,133 @@ class CorpusBuilder:
         main.synchronize()
         fsst.check()
         return items
+
+    def build_resampled_recordings(self, recordings: Iterable[Tuple[torch.Tensor, Optional[torch.Tensor]]], keep_on_device: bool = False,
+                                   max_samples: int = 1 << 25) -> FrameItems:
+        """See the module function ``build_resampled_recordings`` (the builder's ``resample`` is the ``Resample``)."""
+        fsst, dev, rsm = self.fsst, self.dev, self.resample
+        name = "CorpusBuilder.build_resampled_recordings"
+        # ---- arguments, all checked before a plan (or the GPU) is touched
+        if rsm is None:
+            raise ValueError(f"{name}: the builder has no resample= (a Resample(num))")
+        if not (getattr(fsst, "stack", False) or getattr(fsst, "abs", False)):
+            raise ValueError(f"{name}: the transform must have stack=True or abs=True (time-major float32 features)")
+        if dev.type != "cuda":
+            raise ValueError(f"{name}: the builder's device is not a HIP device")
+        num = int(rsm.num)
+        if num < 1:
+            raise ValueError(f"{name}: Resample.num must be >= 1, got {num}")
+        recs: Sequence = recordings if isinstance(recordings, (list, tuple)) else list(recordings)
+        xs, ys = [], []
+        for i, (x, y) in enumerate(recs):
+            t = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))
+            if t.ndim == 2 and t.shape[-1] == 1:
+                t = t[:, 0]
+            if t.ndim != 1 or t.shape[0] < 1 or t.is_complex():
+                raise ValueError(f"{name}: recording {i} has shape {tuple(t.shape)} ({t.dtype}); expected real (T,) or (T, 1), T >= 1")
+            if y is not None:
+                y = (y if isinstance(y, torch.Tensor) else torch.as_tensor(np.asarray(y))).reshape(-1)
+                if y.shape[0] != t.shape[0] or y.is_complex():
+                    raise ValueError(f"{name}: the labels of recording {i} are {tuple(y.shape)} ({y.dtype}), the recording {tuple(t.shape)}")
+            xs.append(t)
+            ys.append(y)
+        has = [y is not None for y in ys]
+        if 0 < sum(has) < len(has):
+            raise ValueError(f"{name}: some recordings carry labels and some do not; pass labels for all or for none")
+        have_labels = len(has) > 0 and all(has)
+        lens_np = np.asarray([int(t.shape[0]) for t in xs], dtype=np.int64)
+        count = len(xs)
+        plan = fsst._plan(fsst._device_index(torch.empty(0, device=dev)))
+        C, fdt = plan.ofps, plan.out_dtype               # (fdt: the features' element type -- a half STACK transform's out_dtype)
+        shape = (count, num, C)
+        if keep_on_device:
+            feats = torch.empty(shape, dtype=fdt, device=dev)
+        else:
+            try:
+                feats = torch.empty(shape, dtype=fdt, pin_memory=bool(self.pin_host and count > 0))
+            except RuntimeError:                          # page-locking that much memory can be refused: pageable then
+                feats = torch.empty(shape, dtype=fdt)
+        if count == 0:
+            return FrameItems(feats, None)
+        # groups of at most max_samples input samples (a longer recording is a group of its own)
+        groups: List[Tuple[int, int]] = []
+        g0, acc = 0, 0
+        for i, T in enumerate(lens_np.tolist()):
+            if acc > 0 and acc + T > max_samples:
+                groups.append((g0, i))
+                g0, acc = i, 0
+            acc += T
+        groups.append((g0, count))
+        pos_np = np.concatenate([[0], np.cumsum(lens_np)])
+        max_group = max(int(pos_np[b] - pos_np[a]) for a, b in groups)
+        max_cnt = max(b - a for a, b in groups)
+        self._ensure(max_group, max_cnt, C, not keep_on_device, num, fdt)
+        self._ensure_resample(max_group, max_cnt, num, have_labels)
+        B = self._bufs
+        lab_d = torch.empty((count, num), dtype=torch.int64, device=dev) if have_labels else None
+        main, up, down = torch.cuda.current_stream(dev), B["up"], B["down"]
+        stage_h, stage_d = B["stage_h"], B["stage_d"]
+        up_done, used, ring_free = B["up_done"], B["used"], B["ring_free"]
+        up.wait_stream(main)                             # (the staging buffers may still be read by an earlier call's work)
+        from . import _lib
+        import ctypes
+        held = [t if (t.dtype == torch.float32 and t.is_contiguous() and not t.is_cuda) else t.detach().to("cpu", torch.float32).contiguous()
+                for t in xs]                               # (device recordings are staged through the host like the rest: rare)
+        ptrs_np = np.asarray([t.data_ptr() for t in held], dtype=np.uint64)
+        if have_labels:                                  # the label tracks as given (no shift), exact in float32, packed like the signals
+            held_y = [y.to("cpu", torch.float32).contiguous() for y in ys]
+            yptrs_np = np.asarray([y.data_ptr() for y in held_y], dtype=np.uint64)
+        L = _lib.lib()
+        starts_np = np.empty(count, dtype=np.int64)
+
+        def pack(gi: int) -> int:
+            """Host side of group gi: recordings (and label tracks) back to back into pinned staging; upload on `up`."""
+            a, b = groups[gi]
+            buf = gi & 1
+            if gi >= 2:
+                used[buf].synchronize()                  # the calls of group gi - 2 no longer read this staging pair
+            n = int(pos_np[b] - pos_np[a])
+            for ptrs, dst in ((ptrs_np, stage_h[buf]),) + (((yptrs_np, B["lab_h"][buf]),) if have_labels else ()):
+                got = L.hssfsst_pack_recordings(ctypes.c_void_p(ptrs[a:b].ctypes.data), ctypes.c_void_p(lens_np[a:b].ctypes.data), b - a,
+                                                0x7fffffff, 1, ctypes.c_void_p(dst.data_ptr()), int(dst.numel()),
+                                                ctypes.c_void_p(starts_np[a:b].ctypes.data), b - a, 0)
+                if got != b - a:
+                    _lib.check(int(got) if got < 0 else _lib.E_INVAL, "hssfsst_pack_recordings")
+            with torch.cuda.stream(up):
+                stage_d[buf][:n].copy_(stage_h[buf][:n], non_blocking=True)
+                if have_labels:
+                    B["lab_d"][buf][:n].copy_(B["lab_h"][buf][:n], non_blocking=True)
+                up_done[buf].record(up)
+            return n
+
+        n = pack(0)
+        for gi, (a, b) in enumerate(groups):
+            buf = gi & 1
+            main.wait_event(up_done[buf])
+            if keep_on_device:
+                dst = feats[a:b]
+            else:
+                if gi >= 2:
+                    main.wait_event(ring_free[buf])
+                dst = B["ring_d"][buf][:b - a]
+            rs = B["rs_d"][:(b - a) * num].view(b - a, num)
+            rsm.ragged(stage_d[buf][:n], lengths=lens_np[a:b], out=rs)
+            fsst.batch(rs, out=dst)
+            if have_labels:
+                rsm.ragged(B["lab_d"][buf][:n], lengths=lens_np[a:b], labels=True, out=lab_d[a:b])
+            used[buf].record(main)
+            if not keep_on_device:
+                down.wait_stream(main)
+                with torch.cuda.stream(down):
+                    feats[a:b].copy_(dst, non_blocking=True)
+                    ring_free[buf].record(down)
+            if gi + 1 < len(groups):
+                n = pack(gi + 1)                         # host packing + upload of the next group overlap these calls
+        if not keep_on_device:
+            down.synchronize()
+        main.synchronize()
+        fsst.check()
+        return FrameItems(feats, lab_d.cpu() if have_labels else None)
 
     def build(self, recordings: Iterable[Tuple[torch.Tensor, Optional[torch.Tensor]]], keep_on_device: bool = False,
               rank: Optional[int] = None, world: Optional[int] = None, out: Optional[torch.Tensor] = None) -> FrameItems:
@@ -458,12 +592,26 @@ def build_recordings(recordings: Iterable[Tuple[torch.Tensor, Optional[torch.Ten
     dataset (``in_memory=False``) hands out item by item: ``(fsst(x), y)`` for EVERY recording (no ``frame_len`` skip, labels
     unchanged -- no ``- 1``), as views of one arena on the device (``keep_on_device``) or in (pinned) host memory.  ``fsst`` must
     have ``stack=True`` or ``abs=True``.  Groups of at most ``max_samples`` samples go through one ``FSST.ragged`` call each.
-    ``resample=`` is refused: every recording length would need a resample plan of its own."""
+    ``resample=`` is refused here: with a ``Resample`` every item has ``num`` samples -- call ``build_resampled_recordings``."""
     if resample is not None:
         raise ValueError("build_recordings: resample= is not supported for whole recordings (every recording length needs a "
                          "resample plan of its own); resample the recordings first")
     return CorpusBuilder(fsst, device=device, pin_host=pin_host).build_recordings(recordings, keep_on_device=keep_on_device,
                                                                                  max_samples=max_samples)
+
+
+def build_resampled_recordings(recordings: Iterable[Tuple[torch.Tensor, Optional[torch.Tensor]]], fsst, resample,
+                               device: Optional[torch.device] = None, keep_on_device: bool = False, pin_host: bool = True,
+                               max_samples: int = 1 << 25) -> FrameItems:
+    """``recordings``: iterable of ``(x (T,) float32, y (T,) labels or None)``, any lengths; ``resample``: a ``Resample(num)``.
+    Returns what the reference's lazy dataset with ``Compose([resample, fsst])`` hands out item by item (``in_memory=False``,
+    heart_sounds.py:175-184,199-212): ``(features (num, C), labels (num,) int64)`` for EVERY recording, the labels
+    ``round(resample(y)) - 1`` of the track as given (no other shift), or None -- as a ``FrameItems`` over one ``(count, num, C)``
+    arena on the device (``keep_on_device``) or in (pinned) host memory, and a ``(count, num)`` host label arena.  Labels for all
+    recordings or for none.  Groups of at most ``max_samples`` input samples go through one ``Resample.ragged`` call and one
+    ``FSST.batch`` call each: the features are bit-identical to ``fsst.batch(resample.ragged(xs))``."""
+    return CorpusBuilder(fsst, device=device, pin_host=pin_host, resample=resample).build_resampled_recordings(
+        recordings, keep_on_device=keep_on_device, max_samples=max_samples)
 
 
 def gather_features(items, group=None, out_device: Optional[torch.device] = None) -> torch.Tensor:

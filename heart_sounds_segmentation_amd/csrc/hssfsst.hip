@@ -7,6 +7,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -36,6 +37,7 @@
 #include "fsst_half.hpp"
 #include "fourier_resample.hpp"
 #include "fourier_resample_gpu.hpp"
+#include "fourier_resample_ragged.hpp"
 #include <cstdlib>
 
 namespace {
@@ -2166,6 +2168,13 @@ struct hssfsst_resample_plan {
     void* d_lab = nullptr; size_t lab_cap = 0;           // int64: host labels, staged
     void* d_starts = nullptr; size_t starts_cap = 0;     // int64: host frame starts, staged
     void* d_work = nullptr; size_t work_cap = 0;         // double2: the large tier's convolutions [chunk][max(M1, M2)]
+    // ragged plans (hssfsst_resample_plan_create_ragged, n = 0): d_tab holds c2 | B2 only; the twiddle table is its own buffer,
+    // grown to the largest M of a call; the list's descriptors are made on the host and uploaded once per call
+    bool ragged = false;
+    double2* d_tw = nullptr; int tw_M = 0;               // tw[k] = exp(-2 pi i k / tw_M), k < tw_M / 2
+    void* d_desc = nullptr; size_t desc_cap = 0;         // bytes: RaggedResampleSig[count] | table lengths (int64)
+    std::vector<unsigned char> h_desc;                   // their host copy (not rewritten before desc_ev: the upload reads it)
+    hipEvent_t desc_ev = nullptr;
 };
 
 namespace {
@@ -2272,8 +2281,9 @@ int hssfsst_resample_plan_destroy(hssfsst_resample_plan* p)
 {
     if (!p) return 0;
     DeviceGuard device_guard_(p->device);
-    for (void* d : {static_cast<void*>(p->d_tab), p->d_x, p->d_y, p->d_lab, p->d_starts, p->d_work})
+    for (void* d : {static_cast<void*>(p->d_tab), p->d_x, p->d_y, p->d_lab, p->d_starts, p->d_work, static_cast<void*>(p->d_tw), p->d_desc})
         if (d) (void)hipFree(d);
+    if (p->desc_ev) (void)hipEventDestroy(p->desc_ev);
     delete p;
     return 0;
 }
@@ -2283,9 +2293,9 @@ int hssfsst_resample_plan_info(const hssfsst_resample_plan* p, int64_t* n, int64
     if (!p) return fail(HSSFSST_EINVAL, "resample_plan_info: plan is NULL");
     if (n) *n = p->n;
     if (num) *num = p->num;
-    if (m1) *m1 = p->M1;
+    if (m1) *m1 = p->ragged ? 0 : p->M1;
     if (m2) *m2 = p->M2;
-    if (lds_tier) *lds_tier = p->Mt <= hssfsst::kRsLdsMax ? 1 : 0;
+    if (lds_tier) *lds_tier = !p->ragged && p->Mt <= hssfsst::kRsLdsMax ? 1 : 0;
     if (device) *device = p->device;
     return 0;
 }
@@ -2300,6 +2310,7 @@ int hssfsst_resample_exec(hssfsst_resample_plan* p, const void* x, int x_dtype, 
     if ((x_dtype != HSSFSST_DTYPE_F32 && x_dtype != HSSFSST_DTYPE_F64) || (y && y_dtype != HSSFSST_DTYPE_F32 && y_dtype != HSSFSST_DTYPE_F64))
         return fail(HSSFSST_EINVAL, "resample_exec: unknown dtype (x %d, y %d)", x_dtype, y_dtype);
     if (batch > 0x7fffffffLL) return fail(HSSFSST_EINVAL, "resample_exec: batch %lld too large", static_cast<long long>(batch));
+    if (p->ragged) return fail(HSSFSST_EINVAL, "resample_exec: a ragged plan (hssfsst_resample_plan_create_ragged) takes hssfsst_resample_exec_ragged");
     const int64_t n = p->n, num = p->num;
     if (batch == 0) return 0;
     if (!starts) {
@@ -2402,6 +2413,290 @@ int hssfsst_resample_exec(hssfsst_resample_plan* p, const void* x, int x_dtype, 
             hipLaunchKernelGGL(hssfsst::resample_store_kernel, dim3(rs_grid(t3)), dim3(hssfsst::kRsThreads), 0, st, a, work, Mw, t3);
             if ((rc = rs_launch_check("resample_store_kernel")) != 0) return rc;
         }
+    }
+    if (!out_on_device) {
+        if (y) HIP_TRY(hipMemcpyAsync(y, a.y, nout * ysz, hipMemcpyDeviceToHost, st));
+        if (labels) HIP_TRY(hipMemcpyAsync(labels, a.labels, nout * sizeof(long long), hipMemcpyDeviceToHost, st));
+    }
+    if (!out_on_device || !x_on_device) HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+int hssfsst_resample_plan_create_ragged(hssfsst_resample_plan** out, int device, int64_t num)
+{
+    if (!out) return fail(HSSFSST_EINVAL, "resample_plan_create_ragged: out is NULL");
+    *out = nullptr;
+    if (num < 1 || device < 0)
+        return fail(HSSFSST_EINVAL, "resample_plan_create_ragged: bad argument (device=%d num=%lld)", device, static_cast<long long>(num));
+    if (num > kRsMaxLen)
+        return fail(HSSFSST_EUNSUPPORTED, "resample_plan_create_ragged: lengths above %lld samples are not supported (num=%lld)",
+                    static_cast<long long>(kRsMaxLen), static_cast<long long>(num));
+    int ndev = 0;
+    hipError_t e = hipGetDeviceCount(&ndev);
+    if (e != hipSuccess || ndev <= 0) {
+        (void)hipGetLastError();
+        return fail(HSSFSST_ENODEVICE, "resample_plan_create_ragged: no HIP device (%s); this library has no CPU path",
+                    e == hipSuccess ? "device count 0" : hipGetErrorString(e));
+    }
+    if (device >= ndev) return fail(HSSFSST_EINVAL, "resample_plan_create_ragged: device %d out of range [0,%d)", device, ndev);
+    DEVICE_SCOPE(device);
+    using hssfsst::resample_detail::cd;
+    hssfsst_resample_plan* p = new (std::nothrow) hssfsst_resample_plan();
+    if (!p) return fail(HSSFSST_ENOMEM, "resample_plan_create_ragged: host allocation failed");
+    p->ragged = true;
+    p->device = device; p->n = 0; p->num = num;
+    p->M1 = 0;
+    p->M2 = pow2_at_least(2 * num - 1);
+    p->Mt = p->M2;
+    const size_t total = static_cast<size_t>(num) + static_cast<size_t>(p->M2);
+    try {
+        std::vector<cd> tab(total);
+        bluestein_tables(num, p->M2, -1.0, tab.data(), tab.data() + num);
+        e = hipMalloc(reinterpret_cast<void**>(&p->d_tab), total * sizeof(double2));
+        if (e != hipSuccess) { p->d_tab = nullptr; delete p; return fail(HSSFSST_ENOMEM, "resample_plan_create_ragged: hipMalloc: %s", hipGetErrorString(e)); }
+        e = hipMemcpy(p->d_tab, tab.data(), total * sizeof(double2), hipMemcpyHostToDevice);
+        if (e != hipSuccess) { (void)hipFree(p->d_tab); delete p; return fail(HSSFSST_EHIP, "resample_plan_create_ragged: table upload: %s", hipGetErrorString(e)); }
+    } catch (const std::bad_alloc&) {
+        if (p->d_tab) (void)hipFree(p->d_tab);
+        delete p;
+        return fail(HSSFSST_ENOMEM, "resample_plan_create_ragged: out of host memory");
+    }
+    p->c2 = p->d_tab; p->B2 = p->d_tab + num;
+    *out = p;
+    return 0;
+}
+
+}  // extern "C"
+
+namespace {
+
+// the ragged plan's twiddle table, grown to Mt points: exp(-2 pi i k / Mt), k < Mt / 2, made on the host as the dense plan's.
+// A larger table holds the same bits at the indices a smaller one uses (k 2^j / (Mt 2^j) is exact): results do not depend on it.
+int rs_ragged_twiddles(hssfsst_resample_plan* p, int Mt)
+{
+    using hssfsst::resample_detail::cd;
+    if (Mt <= p->tw_M) return 0;
+    const size_t ntw = static_cast<size_t>(Mt > 1 ? Mt / 2 : 1);
+    double2* d = nullptr;
+    try {
+        std::vector<cd> tw(ntw);
+        for (size_t k = 0; k < ntw; ++k) {
+            const double ang = -2.0 * M_PI * static_cast<double>(k) / static_cast<double>(Mt);
+            tw[k] = cd(std::cos(ang), std::sin(ang));
+        }
+        hipError_t e = hipMalloc(reinterpret_cast<void**>(&d), ntw * sizeof(double2));
+        if (e != hipSuccess) return fail(HSSFSST_ENOMEM, "resample_exec_ragged: hipMalloc of the twiddle table: %s", hipGetErrorString(e));
+        e = hipMemcpy(d, tw.data(), ntw * sizeof(double2), hipMemcpyHostToDevice);
+        if (e != hipSuccess) { (void)hipFree(d); return fail(HSSFSST_EHIP, "resample_exec_ragged: twiddle upload: %s", hipGetErrorString(e)); }
+    } catch (const std::bad_alloc&) {
+        if (d) (void)hipFree(d);
+        return fail(HSSFSST_ENOMEM, "resample_exec_ragged: out of host memory");
+    }
+    if (p->d_tw) HIP_TRY(hipFree(p->d_tw));              // (hipFree waits for the device: no earlier launch still reads it)
+    p->d_tw = d; p->tw_M = Mt;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int hssfsst_resample_exec_ragged(hssfsst_resample_plan* p, const void* x, int x_dtype, int64_t x_len, const int64_t* starts,
+                                 const int64_t* lens, int64_t count, int x_on_device, void* y, int y_dtype, int64_t* labels,
+                                 int out_on_device, void* stream)
+{
+    using hssfsst::RaggedResampleSig;
+    if (!p || !x || !starts || !lens || (!y && !labels) || count < 0 || x_len < 0)
+        return fail(HSSFSST_EINVAL, "resample_exec_ragged: bad argument (count=%lld x_len=%lld)", static_cast<long long>(count),
+                    static_cast<long long>(x_len));
+    if (!p->ragged) return fail(HSSFSST_EINVAL, "resample_exec_ragged: a dense plan (hssfsst_resample_plan_create) takes hssfsst_resample_exec");
+    if ((x_dtype != HSSFSST_DTYPE_F32 && x_dtype != HSSFSST_DTYPE_F64) || (y && y_dtype != HSSFSST_DTYPE_F32 && y_dtype != HSSFSST_DTYPE_F64))
+        return fail(HSSFSST_EINVAL, "resample_exec_ragged: unknown dtype (x %d, y %d)", x_dtype, y_dtype);
+    if (count > 0x7fffffffLL) return fail(HSSFSST_EINVAL, "resample_exec_ragged: count %lld too large", static_cast<long long>(count));
+    bool too_long = false;
+    long long xlo = x_len, xhi = 0;
+    for (int64_t i = 0; i < count; ++i) {
+        if (lens[i] < 1) return fail(HSSFSST_EINVAL, "resample_exec_ragged: signal %lld has %lld samples", static_cast<long long>(i),
+                                     static_cast<long long>(lens[i]));
+        if (starts[i] < 0 || starts[i] > x_len - lens[i])
+            return fail(HSSFSST_EINVAL, "resample_exec_ragged: signal %lld spans [%lld, %lld), outside [0, %lld]", static_cast<long long>(i),
+                        static_cast<long long>(starts[i]), static_cast<long long>(starts[i]) + static_cast<long long>(lens[i]),
+                        static_cast<long long>(x_len));
+        too_long = too_long || lens[i] > kRsMaxLen;
+        xlo = std::min<long long>(xlo, starts[i]);
+        xhi = std::max<long long>(xhi, starts[i] + lens[i]);
+    }
+    if (too_long) return fail(HSSFSST_EUNSUPPORTED, "resample_exec_ragged: signals above %lld samples are not supported", static_cast<long long>(kRsMaxLen));
+    if (count == 0) return 0;
+    if (x_on_device) xlo = 0;
+    const int64_t num = p->num;
+    const int M2 = p->M2;
+    DEVICE_SCOPE(p->device);
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    int rc;
+
+    // ---- the plan of the call, on the host: the list by length (a class of equal M1 is a contiguous run, equal lengths adjacent,
+    // ties in list order), cut into chunks of at most kRsWorkBytes of work and tables (at least one signal each)
+    struct Chunk { long long d0, cnt, Mw, t0, ntab, elems; };
+    std::vector<Chunk> chunks;
+    std::vector<long long> ord, tabM, tabOff, tabN;
+    std::vector<int> M1s;
+    const long long budget = static_cast<long long>(kRsWorkBytes / sizeof(double2));
+    try {
+        ord.resize(static_cast<size_t>(count));
+        for (int64_t i = 0; i < count; ++i) ord[static_cast<size_t>(i)] = i;
+        std::stable_sort(ord.begin(), ord.end(), [&](long long a, long long b) { return lens[a] < lens[b]; });
+        M1s.resize(static_cast<size_t>(count));
+        for (int64_t i = 0; i < count; ++i) M1s[static_cast<size_t>(i)] = pow2_at_least(2 * lens[ord[static_cast<size_t>(i)]] - 1);
+        Chunk c{0, 0, 0, 0, 0, 0};
+        long long tab_elems = 0;
+        for (long long d = 0; d < count; ++d) {
+            const long long n = lens[ord[static_cast<size_t>(d)]], M1 = M1s[static_cast<size_t>(d)];
+            const long long Mw = std::max<long long>(M1, M2);
+            bool fresh = c.cnt == 0 || n != lens[ord[static_cast<size_t>(d - 1)]];
+            if (c.cnt > 0 && (c.cnt + 1) * Mw + tab_elems + (fresh ? M1 : 0) > budget) {
+                c.elems = c.cnt * c.Mw + tab_elems;
+                chunks.push_back(c);
+                c = Chunk{d, 0, 0, static_cast<long long>(tabN.size()), 0, 0};
+                tab_elems = 0;
+                fresh = true;
+            }
+            if (fresh) {
+                tabN.push_back(n); tabM.push_back(M1); tabOff.push_back(tab_elems);
+                tab_elems += M1;
+                ++c.ntab;
+            }
+            ++c.cnt;
+            c.Mw = Mw;
+        }
+        c.elems = c.cnt * c.Mw + tab_elems;
+        chunks.push_back(c);
+        // descriptors: RaggedResampleSig[count] in sorted order, then the table lengths
+        if (p->desc_ev) HIP_TRY(hipEventSynchronize(p->desc_ev));    // (the previous upload may still read h_desc)
+        const size_t sig_bytes = static_cast<size_t>(count) * sizeof(RaggedResampleSig);
+        p->h_desc.resize(sig_bytes + tabN.size() * sizeof(long long));
+        auto* sig = reinterpret_cast<RaggedResampleSig*>(p->h_desc.data());
+        for (const Chunk& ch : chunks) {
+            long long u = ch.t0 - 1;
+            for (long long d = ch.d0; d < ch.d0 + ch.cnt; ++d) {
+                const long long i = ord[static_cast<size_t>(d)];
+                if (d == ch.d0 || lens[i] != lens[ord[static_cast<size_t>(d - 1)]]) ++u;
+                sig[d] = RaggedResampleSig{starts[i] - xlo, lens[i], M1s[static_cast<size_t>(d)], tabOff[static_cast<size_t>(u)], i};
+            }
+        }
+        std::memcpy(p->h_desc.data() + sig_bytes, tabN.data(), tabN.size() * sizeof(long long));
+    } catch (const std::bad_alloc&) {
+        return fail(HSSFSST_ENOMEM, "resample_exec_ragged: out of host memory");
+    }
+    int Mt = M2;
+    for (int m : M1s) Mt = std::max(Mt, m);
+    if ((rc = rs_ragged_twiddles(p, Mt)) != 0) return rc;
+    if ((rc = grow(&p->d_desc, &p->desc_cap, p->h_desc.size(), 1)) != 0) return rc;
+    HIP_TRY(hipMemcpyAsync(p->d_desc, p->h_desc.data(), p->h_desc.size(), hipMemcpyHostToDevice, st));
+    if (!p->desc_ev) HIP_TRY(hipEventCreateWithFlags(&p->desc_ev, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(p->desc_ev, st));
+    const auto* dsig = static_cast<const RaggedResampleSig*>(p->d_desc);
+    const auto* dtn = reinterpret_cast<const long long*>(static_cast<const unsigned char*>(p->d_desc) + static_cast<size_t>(count) * sizeof(RaggedResampleSig));
+    long long max_elems = 0;
+    for (const Chunk& ch : chunks) max_elems = std::max(max_elems, ch.elems);
+    if ((rc = grow(&p->d_work, &p->work_cap, static_cast<size_t>(max_elems), sizeof(double2))) != 0) return rc;
+
+    // ---- staging of host buffers, as hssfsst_resample_exec
+    const size_t xsz = x_dtype == HSSFSST_DTYPE_F64 ? sizeof(double) : sizeof(float);
+    const size_t ysz = y_dtype == HSSFSST_DTYPE_F64 ? sizeof(double) : sizeof(float);
+    const size_t nout = static_cast<size_t>(count) * static_cast<size_t>(num);
+    hssfsst::RaggedResampleArgs a{};
+    a.x = x;
+    if (!x_on_device) {
+        const size_t bytes = static_cast<size_t>(xhi - xlo) * xsz;
+        if ((rc = grow(&p->d_x, &p->x_cap, bytes, 1)) != 0) return rc;
+        HIP_TRY(hipMemcpyAsync(p->d_x, static_cast<const unsigned char*>(x) + static_cast<size_t>(xlo) * xsz, bytes, hipMemcpyHostToDevice, st));
+        a.x = p->d_x;
+    }
+    a.y = y;
+    a.labels = reinterpret_cast<long long*>(labels);
+    if (!out_on_device) {
+        if (y) {
+            if ((rc = grow(&p->d_y, &p->y_cap, nout * ysz, 1)) != 0) return rc;
+            a.y = p->d_y;
+        }
+        if (labels) {
+            if ((rc = grow(&p->d_lab, &p->lab_cap, nout, sizeof(long long))) != 0) return rc;
+            a.labels = static_cast<long long*>(p->d_lab);
+        }
+    }
+    a.num = num; a.M2 = M2; a.c2 = p->c2;
+    a.x_f64 = x_dtype == HSSFSST_DTYPE_F64; a.y_f64 = y_dtype == HSSFSST_DTYPE_F64; a.num_even = num % 2 == 0;
+    const double2* tw = p->d_tw;
+    const int twM = p->tw_M;
+    double2* work = static_cast<double2*>(p->d_work);
+
+    // global DIF stages of convolutions of M points down to the block length (cnt of them at w, stride Mw)
+    auto dif = [&](double2* w, long long Mw, long long cnt, int M) -> int {
+        const int S = M < hssfsst::kRsBlock ? M : hssfsst::kRsBlock;
+        const long long nb = cnt * (M / 2);
+        for (int len = M; len > S; len >>= 1) {
+            hipLaunchKernelGGL(hssfsst::resample_dif_pass_kernel, dim3(rs_grid(nb)), dim3(hssfsst::kRsThreads), 0, st, w, Mw, M, len, tw, twM, nb);
+            if (int r = rs_launch_check("resample_dif_pass_kernel")) return r;
+        }
+        return 0;
+    };
+    auto dit = [&](double2* w, long long Mw, long long cnt, int M) -> int {
+        const int S = M < hssfsst::kRsBlock ? M : hssfsst::kRsBlock;
+        const long long nb = cnt * (M / 2);
+        for (int len = 2 * S; len <= M; len <<= 1) {
+            hipLaunchKernelGGL(hssfsst::resample_dit_pass_kernel, dim3(rs_grid(nb)), dim3(hssfsst::kRsThreads), 0, st, w, Mw, M, len, tw, twM, nb);
+            if (int r = rs_launch_check("resample_dit_pass_kernel")) return r;
+        }
+        return 0;
+    };
+    for (const Chunk& ch : chunks) {
+        const long long Mw = ch.Mw, cnt = ch.cnt;
+        const RaggedResampleSig* csig = dsig + ch.d0;
+        double2* tabs = work + cnt * Mw;
+        // B1 / M1 of every distinct length of the chunk, one class of equal M1 at a time
+        for (long long u = ch.t0; u < ch.t0 + ch.ntab;) {
+            long long v = u;
+            while (v < ch.t0 + ch.ntab && tabM[static_cast<size_t>(v)] == tabM[static_cast<size_t>(u)]) ++v;
+            const int M = static_cast<int>(tabM[static_cast<size_t>(u)]), S = M < hssfsst::kRsBlock ? M : hssfsst::kRsBlock;
+            double2* t0 = tabs + tabOff[static_cast<size_t>(u)];
+            const long long tot = (v - u) * M;
+            hipLaunchKernelGGL(hssfsst::resample_ragged_table_kernel, dim3(rs_grid(tot)), dim3(hssfsst::kRsThreads), 0, st, t0, dtn + u, M, tot);
+            if ((rc = rs_launch_check("resample_ragged_table_kernel")) != 0) return rc;
+            if ((rc = dif(t0, M, v - u, M)) != 0) return rc;
+            hipLaunchKernelGGL(hssfsst::resample_ragged_table_block_kernel, dim3(static_cast<unsigned>((v - u) * (M / S))), dim3(hssfsst::kRsThreads),
+                               0, st, t0, M, S, tw, twM);
+            if ((rc = rs_launch_check("resample_ragged_table_block_kernel")) != 0) return rc;
+            u = v;
+        }
+        const long long t1 = cnt * Mw;
+        hipLaunchKernelGGL(hssfsst::resample_ragged_load_kernel, dim3(rs_grid(t1)), dim3(hssfsst::kRsThreads), 0, st, a, csig, work, Mw, t1);
+        if ((rc = rs_launch_check("resample_ragged_load_kernel")) != 0) return rc;
+        // the first convolution, one class of equal M1 at a time
+        for (long long e0 = 0; e0 < cnt;) {
+            long long e1 = e0;
+            const int M = M1s[static_cast<size_t>(ch.d0 + e0)], S = M < hssfsst::kRsBlock ? M : hssfsst::kRsBlock;
+            while (e1 < cnt && M1s[static_cast<size_t>(ch.d0 + e1)] == M) ++e1;
+            double2* w = work + e0 * Mw;
+            if ((rc = dif(w, Mw, e1 - e0, M)) != 0) return rc;
+            hipLaunchKernelGGL(hssfsst::resample_ragged_block_kernel, dim3(static_cast<unsigned>((e1 - e0) * (M / S))), dim3(hssfsst::kRsThreads),
+                               0, st, w, Mw, M, S, csig + e0, tabs, tw, twM);
+            if ((rc = rs_launch_check("resample_ragged_block_kernel")) != 0) return rc;
+            if ((rc = dit(w, Mw, e1 - e0, M)) != 0) return rc;
+            e0 = e1;
+        }
+        // the inverse side, once over the chunk
+        const long long t2 = cnt * M2, t3 = cnt * num;
+        hipLaunchKernelGGL(hssfsst::resample_ragged_mid_kernel, dim3(rs_grid(t2)), dim3(hssfsst::kRsThreads), 0, st, a, csig, work, Mw, t2);
+        if ((rc = rs_launch_check("resample_ragged_mid_kernel")) != 0) return rc;
+        if ((rc = dif(work, Mw, cnt, M2)) != 0) return rc;
+        const int S2 = M2 < hssfsst::kRsBlock ? M2 : hssfsst::kRsBlock;
+        hipLaunchKernelGGL(hssfsst::resample_block_kernel, dim3(static_cast<unsigned>(cnt * (M2 / S2))), dim3(hssfsst::kRsThreads), 0, st,
+                           work, Mw, M2, S2, p->B2, tw, twM);
+        if ((rc = rs_launch_check("resample_block_kernel")) != 0) return rc;
+        if ((rc = dit(work, Mw, cnt, M2)) != 0) return rc;
+        hipLaunchKernelGGL(hssfsst::resample_ragged_store_kernel, dim3(rs_grid(t3)), dim3(hssfsst::kRsThreads), 0, st, a, csig, work, Mw, t3);
+        if ((rc = rs_launch_check("resample_ragged_store_kernel")) != 0) return rc;
     }
     if (!out_on_device) {
         if (y) HIP_TRY(hipMemcpyAsync(y, a.y, nout * ysz, hipMemcpyDeviceToHost, st));

@@ -9,8 +9,10 @@ not imported.  Same constructor, same call signature, same output type (a fresh 
 Extensions, mirroring ``FSST``: ``Resample(num, device=...)`` computes ``__call__`` on that GPU (still a fresh CPU tensor of
 ``dtype``); ``batch`` / ``frames`` resample many signals at once on the device (``hssfsst_resample_exec``,
 csrc/fourier_resample_gpu.hpp: fp64 on the device whatever the dtypes), reading overlapping frames in place; and
-``resample_labels_batch`` is the dataset's label rule for a batch, on the device.  Without ``device`` the call is the host
-helper, as before.
+``resample_labels_batch`` is the dataset's label rule for a batch, on the device.  ``ragged`` / ``resample_labels_ragged`` do the
+same for signals of different lengths in one call (``hssfsst_resample_exec_ragged``, csrc/fourier_resample_ragged.hpp: one ragged
+plan per (process, device, num); the forward tables of every length are made on the device).  Without ``device`` the call is the
+host helper, as before.
 """
 from __future__ import annotations
 
@@ -54,6 +56,41 @@ class _ResamplePlan:
             ctypes.c_void_p(labels.data_ptr()) if labels is not None else None, 1 if on_dev else 0,
             ctypes.c_void_p(stream) if stream else None)
         _lib.check(rc, "hssfsst_resample_exec")
+
+    def __del__(self):
+        try:
+            if getattr(self, "handle", None) and self.handle.value and self.pid == os.getpid():
+                self._L.hssfsst_resample_plan_destroy(self.handle)
+        except Exception:
+            pass
+
+
+class _RaggedResamplePlan:
+    """Owner of one ragged ``hssfsst_resample_plan*`` (any input lengths -> num) for (device, num), created lazily in the calling
+    process (fork-safe), like ``_ResamplePlan``."""
+
+    def __init__(self, device_index: int, num: int):
+        _lib.guard_fork()
+        L = _lib.lib()
+        self._L = L
+        self.handle = ctypes.c_void_p()
+        _lib.check(L.hssfsst_resample_plan_create_ragged(ctypes.byref(self.handle), int(device_index), int(num)),
+                   "hssfsst_resample_plan_create_ragged")
+        self.num, self.device, self.pid = int(num), int(device_index), os.getpid()
+
+    def exec(self, x: torch.Tensor, starts: np.ndarray, lens: np.ndarray, y: Optional[torch.Tensor],
+             labels: Optional[torch.Tensor]) -> None:
+        """x: one float32 / float64 buffer (host or device); starts / lens: int64 host arrays; y / labels on x's side."""
+        on_dev = x.is_cuda
+        stream = torch.cuda.current_stream(self.device).cuda_stream if on_dev else None
+        ydt = _lib.DTYPE_F64 if (y is not None and y.dtype == torch.float64) else _lib.DTYPE_F32
+        rc = self._L.hssfsst_resample_exec_ragged(
+            self.handle, ctypes.c_void_p(x.data_ptr()), _lib.DTYPE_F64 if x.dtype == torch.float64 else _lib.DTYPE_F32,
+            int(x.numel()), ctypes.c_void_p(starts.ctypes.data), ctypes.c_void_p(lens.ctypes.data), int(lens.size), 1 if on_dev else 0,
+            ctypes.c_void_p(y.data_ptr()) if y is not None else None, ydt,
+            ctypes.c_void_p(labels.data_ptr()) if labels is not None else None, 1 if on_dev else 0,
+            ctypes.c_void_p(stream) if stream else None)
+        _lib.check(rc, "hssfsst_resample_exec_ragged")
 
     def __del__(self):
         try:
@@ -193,6 +230,81 @@ class Resample:
         plan.exec(x, T, 0, starts, B, None if labels else res, res if labels else None)
         return res
 
+    def ragged(self, xs, lengths=None, dtype: torch.dtype = torch.float32, out: Optional[torch.Tensor] = None,
+               labels: bool = False) -> torch.Tensor:
+        """Extension: resample signals of DIFFERENT lengths, every one to ``num`` samples, in one call (``hssfsst_resample_exec_ragged``)
+        -- whole recordings, as the reference's lazy dataset resamples them one call each (hss/datasets/heart_sounds.py:175-184,199-212).
+
+        ``xs``: a sequence of 1-D signals (``(T_i,)`` or ``(T_i, 1)``, all on the CPU or all on one cuda device), or ONE packed 1-D
+        buffer with ``lengths`` (its signals back to back), as ``FSST.ragged``.  Dtypes as ``batch``: float32 / float64 are read as
+        they are, other real dtypes as float64.  Returns ``(len(xs), num)`` of ``dtype`` (float32 / float64) on the input's device,
+        or with ``labels=True`` the int64 label rule of ``resample_labels`` for every signal.  Row i is within 1e-12 of
+        ``Resample(num)(xs[i])`` and does not depend on the other signals.  ``out`` optionally receives the result."""
+        # ---- arguments, all checked before a plan (or the GPU) is touched
+        if isinstance(xs, (torch.Tensor, np.ndarray)):
+            if lengths is None:
+                raise ValueError("Resample.ragged: a single tensor is a packed buffer and needs lengths=; pass a list for separate signals")
+            buf = xs if isinstance(xs, torch.Tensor) else torch.as_tensor(xs)
+            if buf.ndim == 2 and buf.shape[-1] == 1:
+                buf = buf[:, 0]
+            if buf.ndim != 1:
+                raise ValueError(f"Resample.ragged: a packed buffer must be 1-D, got {tuple(buf.shape)}")
+            if buf.is_complex():
+                raise ValueError("Resample.ragged: complex input is not supported")
+            lens = np.asarray(lengths.cpu() if isinstance(lengths, torch.Tensor) else lengths, dtype=np.int64).reshape(-1)
+            if lens.size and int(lens.min()) < 1:
+                raise ValueError("Resample.ragged: every length must be >= 1")
+            if int(lens.sum()) != int(buf.shape[0]):
+                raise ValueError(f"Resample.ragged: lengths sum to {int(lens.sum())}, the buffer holds {int(buf.shape[0])} samples")
+            X = _as_real(buf).contiguous()
+        else:
+            if lengths is not None:
+                raise ValueError("Resample.ragged: lengths= goes with one packed buffer, not with a list of signals")
+            sigs = []
+            for i, x in enumerate(xs):
+                t = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))
+                if t.ndim == 2 and t.shape[-1] == 1:
+                    t = t[:, 0]
+                if t.ndim != 1:
+                    raise ValueError(f"Resample.ragged: signal {i} has shape {tuple(t.shape)}; expected (T,) or (T, 1)")
+                if t.is_complex():
+                    raise ValueError(f"Resample.ragged: signal {i} is complex; real input expected")
+                if t.shape[0] < 1:
+                    raise ValueError(f"Resample.ragged: signal {i} is empty")
+                sigs.append(_as_real(t))
+            devs = {t.device for t in sigs}
+            if len(devs) > 1:
+                raise ValueError(f"Resample.ragged: the signals lie on different devices {sorted(str(d) for d in devs)}; "
+                                 "pass all on the CPU or all on one cuda device")
+            lens = np.asarray([int(t.shape[0]) for t in sigs], dtype=np.int64)
+            odev = devs.pop() if devs else torch.device("cpu")
+            if not sigs:
+                X = torch.empty(0, dtype=torch.float32, device=odev)
+            elif len(sigs) == 1:
+                X = sigs[0].contiguous()
+            else:                                          # (float32 with float64: float64, exactly)
+                X = torch.cat([t.reshape(-1) for t in sigs])
+        num = int(self.num)
+        if num < 1:
+            raise ValueError(f"Resample.ragged: need at least one output sample (num={num})")
+        if not labels and dtype not in (torch.float32, torch.float64):
+            raise ValueError(f"Resample.ragged: dtype must be float32 or float64, got {dtype}")
+        B = int(lens.size)
+        res = self._out(B, torch.int64 if labels else dtype, X.device, out)
+        if B == 0:
+            return res
+        # ---- one call
+        dev = self._device_index(X)
+        key = ("ragged", os.getpid(), dev, num)
+        if not hasattr(self, "_plans"):
+            self._plans = {}
+        plan = self._plans.get(key)
+        if plan is None:
+            plan = self._plans[key] = _RaggedResamplePlan(dev, num)
+        starts = np.ascontiguousarray(np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64))
+        plan.exec(X, starts, np.ascontiguousarray(lens), None if labels else res, res if labels else None)
+        return res
+
     def lds_tier(self, n: int, device_index: Optional[int] = None) -> bool:
         """Extension: True when (n, num) runs the one-launch LDS kernel, False for the multi-pass tier (whole recordings)."""
         dev = self._device_index() if device_index is None else device_index
@@ -241,6 +353,13 @@ def resample_labels_batch(Y: torch.Tensor, t: Resample) -> torch.Tensor:
     X = t._frames_view(Y)
     res = t._run(X, torch.float32, None, labels=True)
     return res[0] if _as_real(Y).ndim == 1 else res
+
+
+def resample_labels_ragged(ys, t: Resample) -> torch.Tensor:
+    """Extension: ``resample_labels`` for a list of label tracks of DIFFERENT lengths in one device call (``Resample.ragged``) --
+    ``(len(ys), num)`` int64 on the tracks' device.  Equal to ``resample_labels`` track by track except where a resampled value
+    sits on a .5 tie."""
+    return t.ragged(ys, labels=True)
 
 
 def resample_labels(y: torch.Tensor, t: Resample) -> torch.Tensor:

@@ -317,6 +317,25 @@ int hssfsst_resample_exec(hssfsst_resample_plan* plan, const void* x, int x_dtyp
                           const int64_t* starts, int starts_on_device, int64_t batch, int x_on_device,
                           void* y, int y_dtype, int64_t* labels, int out_on_device, void* stream);
 
+/* Ragged resampling: a LIST of signals of different lengths, every one resampled to `num` samples in one call (the reference's
+ * lazy dataset with Compose([Resample(num), FSST(...)]) resamples each whole recording, hss/datasets/heart_sounds.py:175-184,199-212).
+ * A ragged plan holds only what depends on num (the inverse chirp and its spectrum, the twiddle table); the forward tables of
+ * every length are made on the device per call, in fp64 (csrc/fourier_resample_ragged.hpp), one per distinct length.
+ * hssfsst_resample_plan_info reports n = 0 and m1 = 0 for it.  num < 1 or device < 0: HSSFSST_EINVAL; num > 2^26:
+ * HSSFSST_EUNSUPPORTED (both before any device is touched). */
+int hssfsst_resample_plan_create_ragged(hssfsst_resample_plan** out, int device, int64_t num);
+
+/* y[i][0 .. num) = resample(x[starts[i] .. starts[i] + lens[i])) for i < count; starts / lens are HOST arrays, x holds x_len
+ * samples.  Dtypes, the label rule, host or device buffers, staging and synchronisation as hssfsst_resample_exec.  Each row is
+ * within 1e-12 max(|ref|, 1) of hssfsst_resample and of the dense plan of its length (not bit-identical to the dense plan, whose
+ * forward table comes from a host FFT), and deterministic: the same bits whatever its neighbours, its place in the list and the
+ * chunking.  Argument errors (NULL pointers, lens[i] < 1, a span outside [0, x_len], an unknown dtype, neither y nor labels, a
+ * dense plan) return HSSFSST_EINVAL, a length above 2^26 HSSFSST_EUNSUPPORTED, before any device work; count == 0 does nothing.
+ * A ragged plan passed to hssfsst_resample_exec returns HSSFSST_EINVAL. */
+int hssfsst_resample_exec_ragged(hssfsst_resample_plan* plan, const void* x, int x_dtype, int64_t x_len, const int64_t* starts,
+                                 const int64_t* lens, int64_t count, int x_on_device, void* y, int y_dtype, int64_t* labels,
+                                 int out_on_device, void* stream);
+
 int hssfsst_device_count(void);
 int hssfsst_version(void);
 const char* hssfsst_last_error(void);
