@@ -17,7 +17,9 @@
 #include <dlfcn.h>
 #include <cctype>
 #include <string>
+#include <array>
 #include <atomic>
+#include <memory>
 #include <new>
 #include <thread>
 #include <vector>
@@ -80,7 +82,6 @@ struct DebugSwitches {
     int team = 0;                 // CUs per team (0: chosen by the library)
     unsigned team_spin_us = 500;  // bound of a wait inside the team kernel
     int oneplane_kb = 40;         // generic kernel: one shared LDS plane above this many KB
-    int chunks = 0;               // STACK: k-chunk two-stream pipeline (0 / 1: off)
     int zgrid = 0, zslices = 0;   // z-score sweep geometry (0: chosen by the library)
 };
 const DebugSwitches& debug_switches()
@@ -96,11 +97,11 @@ const DebugSwitches& debug_switches()
             else if (key == "force_generic") d.force_generic = on; else if (key == "no_mfma256") d.no_mfma256 = on;
             else if (key == "split_stats") d.split_stats = on; else if (key == "no_stream_fuse") d.no_stream_fuse = on; else if (key == "no_pair") d.no_pair = on; else if (key == "team") d.team = iv;
             else if (key == "team_spin_us") d.team_spin_us = static_cast<unsigned>(iv > 0 ? iv : 500);
-            else if (key == "oneplane_kb") d.oneplane_kb = iv; else if (key == "chunks") d.chunks = iv;
+            else if (key == "oneplane_kb") d.oneplane_kb = iv;
             else if (key == "zgrid") d.zgrid = iv; else if (key == "zslices") d.zslices = iv;
         };
         static const char* const keys[] = {"no_fused", "no_canon", "no_team", "team_only", "team_force_fallback", "force_dft", "force_generic",
-                                           "no_mfma256", "split_stats", "no_stream_fuse", "no_pair", "team", "team_spin_us", "oneplane_kb", "chunks", "zgrid", "zslices"};
+                                           "no_mfma256", "split_stats", "no_stream_fuse", "no_pair", "team", "team_spin_us", "oneplane_kb", "zgrid", "zslices"};
         for (const char* k : keys) {                       // HSSFSST_<KEY>
             std::string name = "HSSFSST_";
             for (const char* c = k; *c; ++c) name += static_cast<char>(std::toupper(static_cast<unsigned char>(*c)));
@@ -147,6 +148,20 @@ struct DeviceGuard {
     DeviceGuard device_guard_(dev);                                                            \
     if (device_guard_.err != hipSuccess)                                                       \
         return fail(HSSFSST_EHIP, "selecting device %d failed: %s", (dev), hipGetErrorString(device_guard_.err))
+
+// the plan creates' device argument: a HIP device must exist (this library has no CPU path) and `device` must be one
+int check_device(const char* what, int device)
+{
+    int ndev = 0;
+    const hipError_t e = hipGetDeviceCount(&ndev);
+    if (e != hipSuccess || ndev <= 0) {
+        (void)hipGetLastError();
+        return fail(HSSFSST_ENODEVICE, "%s: no HIP device (%s); this library has no CPU path", what,
+                    e == hipSuccess ? "device count 0" : hipGetErrorString(e));
+    }
+    if (device < 0 || device >= ndev) return fail(HSSFSST_EINVAL, "%s: device %d out of range [0,%d)", what, device, ndev);
+    return 0;
+}
 
 // Knot slopes of the not-a-knot cubic spline through (1..n, w): the derivative window of
 // ssq.fsst's instantaneous-frequency estimator before its fs/(2*pi) scaling (MATLAB fsst.m, local
@@ -222,6 +237,70 @@ constexpr int kTile = 64;
 #endif
 constexpr int kFpw128 = HSS_FPW128;      // frames per wave tile of the nwin = 128 kernel
 
+// A plan's device buffer: capacity in elements of T; grow() frees the old block and allocates a larger one (contents are not
+// kept), upload() makes a fresh block holding a host table.  Freed with its owner.
+template <class T>
+struct DevBuf {
+    T* p = nullptr;
+    size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    T* get() const { return p; }
+    int grow(size_t need)
+    {
+        if (need <= cap) return 0;
+        if (p) { HIP_TRY(hipFree(p)); p = nullptr; cap = 0; }
+        void* v = nullptr;
+        const hipError_t e = hipMalloc(&v, need * sizeof(T));
+        if (e != hipSuccess) return fail(HSSFSST_ENOMEM, "hipMalloc(%zu B): %s", need * sizeof(T), hipGetErrorString(e));
+        p = static_cast<T*>(v);
+        cap = need;
+        return 0;
+    }
+    int upload(const T* host, size_t n)                 // (into an empty or smaller buffer: grow() makes it fresh)
+    {
+        if (int rc = grow(n)) return rc;
+        HIP_TRY(hipMemcpy(p, host, n * sizeof(T), hipMemcpyHostToDevice));
+        return 0;
+    }
+};
+
+// A plan's pinned host buffer.  Mapped (the staging of small execs, the lent pool): hipHostMallocMapped with its device alias d,
+// a power of two from 4096 elements; otherwise default flags, no alias, 1.5x what is needed.  Capacity in elements of es bytes.
+template <class T>
+struct PinnedBuf {
+    T* h = nullptr;
+    T* d = nullptr;
+    size_t cap = 0;
+    bool mapped = true;
+    PinnedBuf() = default;
+    explicit PinnedBuf(bool mapped_) : mapped(mapped_) {}
+    PinnedBuf(const PinnedBuf&) = delete;
+    PinnedBuf& operator=(const PinnedBuf&) = delete;
+    ~PinnedBuf() { if (h) (void)hipHostFree(h); }
+    int grow(size_t need, size_t es)
+    {
+        if (need <= cap) return 0;
+        if (h) { HIP_TRY(hipHostFree(h)); h = nullptr; d = nullptr; cap = 0; }
+        size_t c = need + need / 2;
+        if (mapped) for (c = size_t(1) << 12; c < need; c *= 2) {}
+        void* hp = nullptr;
+        HIP_TRY(hipHostMalloc(&hp, c * es, mapped ? hipHostMallocMapped : hipHostMallocDefault));
+        void* dp = nullptr;
+        const hipError_t e = mapped ? hipHostGetDevicePointer(&dp, hp, 0) : hipSuccess;
+        if (e != hipSuccess) {
+            (void)hipHostFree(hp);
+            return fail(HSSFSST_EHIP, "hipHostGetDevicePointer: %s", hipGetErrorString(e));
+        }
+        h = static_cast<T*>(hp); d = static_cast<T*>(dp); cap = c;
+        return 0;
+    }
+};
+
+constexpr size_t kPinPoolMax = 64;                       // hssfsst_exec_pinned: buffers lent at a time (hssfsst.h)
+
 }  // namespace
 
 struct hssfsst_plan {
@@ -229,26 +308,26 @@ struct hssfsst_plan {
     int nwin = 0, R = 0, nf = 0, klo = 0, K = 0, mode = 0;
     int out_dtype = HSSFSST_DTYPE_F32;                       // HSSFSST_DTYPE_F32, or F16 / BF16 (STACK only): element type of every exec's `out`
     size_t out_es = sizeof(float);                           // ... its size in bytes
-    float* d_f32 = nullptr;       size_t f32_cap = 0;        // half plans: float32 features of the paths whose z-score is a second sweep (floats)
+    DevBuf<float> d_f32;                                     // half plans: float32 features of the paths whose z-score is a second sweep
     double fs = 0.0;
-    float* d_ctab = nullptr;      // generic kernel: class-folded scalar tables
-    float* d_dtab = nullptr;      // any-length kernel (fsst_dft.hpp): A operand [source block][k-step][64 lanes]
+    DevBuf<float> d_ctab;         // generic kernel: class-folded scalar tables
+    DevBuf<float> d_dtab;         // any-length kernel (fsst_dft.hpp): A operand [source block][k-step][64 lanes]
     int dft = 0;                  // 1: this plan runs the any-length kernel
     float r2scale = 0.0f;         // 4 nwin max |(w + i dw') / 2|^2: error-bound scale of the rounding-tie path
-    double* d_wtab = nullptr;     // float64 {w, dw' in bin units}[nwin], then {cos, sin}(2 pi m / nwin)[nwin]: rounding-tie path
-    float* d_atab = nullptr;      // nwin == 128 / 256 / 512: MFMA A-operand constants [pass][taps][64 lanes][k-step]
+    DevBuf<double> d_wtab;        // float64 {w, dw' in bin units}[nwin], then {cos, sin}(2 pi m / nwin)[nwin]: rounding-tie path
+    DevBuf<float> d_atab;         // nwin == 128 / 256 / 512: MFMA A-operand constants [pass][taps][64 lanes][k-step]
     int rq = 0;                   // first-stage radix of the MFMA kernel, 0 = generic kernel
-    float* d_atab16 = nullptr;    // canonical-band kernels (fsst_canon128.hpp): f16 split A operand [16 taps][64 lanes][8 halves]
+    DevBuf<float> d_atab16;       // canonical-band kernels (fsst_canon128.hpp): f16 split A operand [16 taps][64 lanes][8 halves]
     float canon_inv_c = 0.0f;     // ... 1 / (power-of-two scale of those constants)
     float canon_r2s = 0.0f;       // ... r2scale x scale^2
     int canon_slots = 0;          // resident blocks of fsst_canon_kernel<.., false> (0 = not queried yet)
     int nt = 16;                  // taps (per-lane FFT size) of the MFMA kernel: nwin = nt * rq
-    float* d_partials = nullptr;  size_t partials_cap = 0;   // floats (kPartFloats per statistics piece)
+    DevBuf<float> d_partials;                                // kPartFloats per statistics piece
     unsigned* d_status = nullptr;                            // fused z-score: status word (0 = ok) as the device sees it ...
     volatile unsigned* h_status = nullptr;                   // ... and the same word in pinned host memory: read without a sync
-    unsigned long long* d_mail = nullptr; size_t mail_cap = 0;   // team kernel: mailboxes [teams][slots][32 blocks][8] (8-byte words)
+    DevBuf<unsigned long long> d_mail;                       // team kernel: mailboxes [teams][slots][32 blocks][8] (8-byte words)
     unsigned team_seq = 0;                                   // launch sequence number (upper half of the mailbox tags)
-    unsigned* d_arrive = nullptr; unsigned arrive_total = 0; // team kernel: [0] arrival counter (and its value after the launches so far), [1] abort word, [2] blocks done
+    DevBuf<unsigned> d_arrive; unsigned arrive_total = 0;    // team kernel: [0] arrival counter (and its value after the launches so far), [1] abort word, [2] blocks done
     unsigned done_total = 0;                                 // ... [2]'s value after the flagged launches so far
     bool flag_done = false; unsigned flag_launch = 0;        // exec_impl asks the next team launch to say in pinned host memory (h_fallback[2]) when its last wave is done; that launch
     unsigned team_launch = 0;                                // identity of the last team launch (never 0)
@@ -265,26 +344,27 @@ struct hssfsst_plan {
     int core128_slots = 0;                    // resident blocks of the core kernel on this device (0 = not queried yet)
     int ragged_slots = 0;                     // the same for its ragged instantiation
     int stream_slots = 0;                     // the same for the streaming-step kernel
-    unsigned* d_stream_arrive = nullptr; int stream_arrive_cap = 0;   // streaming step: blocks delivered per channel
-    double* d_stream_pieces = nullptr; long long stream_pieces_cap = 0;   // and the groups' float64 sums [channels][groups][4]
+    DevBuf<unsigned> d_stream_arrive;         // streaming step: blocks delivered per channel
+    DevBuf<double> d_stream_pieces;           // and the groups' float64 sums [channels][groups][4]
     int fused_slots = 0;                      // CUs usable by the fused kernel (0 = not queried yet, -1 = none)
-    float* d_stats = nullptr;     size_t stats_cap = 0;      // floats (4 per signal)
-    float* d_xstage = nullptr;    size_t xstage_cap = 0;     // floats
-    float* d_ostage = nullptr;    size_t ostage_cap = 0;     // floats
+    DevBuf<float> d_stats;                                   // 4 per signal
+    DevBuf<float> d_xstage, d_ostage;                        // a host input / output, staged
     // small host-to-host execs (the unchanged dataset loop: one 2000-sample frame per call): pinned, device-mapped staging that the
     // kernels read and write in place
-    float* h_xpin = nullptr; float* d_xpin = nullptr; size_t xpin_cap = 0;
-    float* h_opin = nullptr; float* d_opin = nullptr; size_t opin_cap = 0;
-    struct PinBuf { float* h; float* d; size_t cap; bool used; };
-    std::vector<PinBuf> pin_pool;                        // hssfsst_exec_pinned: pinned, device-mapped result buffers lent to the caller
+    PinnedBuf<float> xpin, opin;
+    struct PoolBuf { PinnedBuf<float> buf; bool used = false; };
+    std::array<PoolBuf, kPinPoolMax> pin_pool;              // hssfsst_exec_pinned: pinned, device-mapped result buffers lent to the caller
+    std::mutex pin_mu;                                       // ... guards `used` and the buffers' replacement (hssfsst_pinned_release may
+                                                             // come from another host thread)
     bool defer_fallback = false;                             // this exec synchronises before it returns: no gated launches behind a team launch,
     unsigned deferred_launch = 0, deferred_first = 0;        // the host looks at the pinned give-up word afterwards and redoes the exec itself
-    long long* d_starts = nullptr; size_t starts_cap = 0;    // frame-list staging (hssfsst_exec_list with host starts)
-    float* d_frames = nullptr;    size_t frames_cap = 0;     // frames gathered from a list, dense [batch][n]
+    DevBuf<long long> d_starts;                              // frame-list staging (hssfsst_exec_list with host starts)
+    DevBuf<float> d_frames;                                  // frames gathered from a list, dense [batch][n]
     // hssfsst_exec_ragged: the list's tables -- RaggedSignal[batch], z-score unit starts int[batch + 1], chunk list int2[] -- made
     // on the host (h_rtab, pinned) and uploaded in one copy to d_rtab; kept while the next list has the same lengths and offsets (rkey)
-    void* d_rtab = nullptr;       size_t rtab_cap = 0;       // bytes
-    unsigned char* h_rtab = nullptr; size_t h_rtab_cap = 0, rtab_bytes = 0;
+    DevBuf<unsigned char> d_rtab;
+    PinnedBuf<unsigned char> h_rtab{false};
+    size_t rtab_bytes = 0;
     std::vector<long long> rkey;
     size_t rtab_unit = 0, rtab_chunk = 0;                    // byte offsets of the unit starts and of the chunk list in the tables
     long long rtab_nchunks = 0, rtab_nunits = 0;
@@ -296,8 +376,6 @@ struct hssfsst_plan {
     std::vector<hipEvent_t> ev;   // per timed exec: (before, after) per core launch + one closing event
     size_t ev_used = 0;           // events used since timing was enabled
     std::vector<int> ev_chunks;   // core launches of each timed exec
-    hipStream_t aux = nullptr;    // side stream: z-score of chunk i overlaps the core of chunk i+1
-    std::vector<hipEvent_t> sync_ev;
 };
 
 namespace {
@@ -400,8 +478,6 @@ int launch_core128_wpb(hssfsst_plan* pl, const hssfsst::Core128Params& cp, int64
 // One rolling step in ONE launch (fsst_core128_kernel<.., STREAM>, fsst_mfma128.hpp): the chunk's groups, one per ticket, blocks
 // bound to channels; tape append, transform, running-moments merge and normalisation.  Returns 1 when it launched, 0 when the
 // step should take the three-launch route (a shape whose plain transform would not be this kernel's one-group chunks).
-int ensure_status(hssfsst_plan* pl);
-
 template <int NT, int RQ, int WPB, bool PAIR>
 int launch_stream(hssfsst_plan* pl, float* tape_at, long long tape_len, const float* x_new_dev, long long x_stride, int channels, int chunk,
                   float* out, double* state, float* mirror, hipStream_t st)
@@ -420,27 +496,23 @@ int launch_stream(hssfsst_plan* pl, float* tape_at, long long tape_len, const fl
         HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, pl->device));
         pl->stream_slots = (per_cu < 1 ? 1 : per_cu) * (cus < 1 ? 1 : cus);
     }
-    if (state && pl->stream_arrive_cap < channels) {
-        if (pl->d_stream_arrive) { HIP_TRY(hipFree(pl->d_stream_arrive)); pl->d_stream_arrive = nullptr; pl->stream_arrive_cap = 0; }
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&pl->d_stream_arrive), static_cast<size_t>(channels) * sizeof(unsigned)));
-        HIP_TRY(hipMemsetAsync(pl->d_stream_arrive, 0, static_cast<size_t>(channels) * sizeof(unsigned), st));
-        pl->stream_arrive_cap = channels;
+    if (state && pl->d_stream_arrive.cap < static_cast<size_t>(channels)) {
+        if (int rc = pl->d_stream_arrive.grow(static_cast<size_t>(channels))) return rc;
+        HIP_TRY(hipMemsetAsync(pl->d_stream_arrive.get(), 0, static_cast<size_t>(channels) * sizeof(unsigned), st));
     }
-    if (state && pl->stream_pieces_cap < static_cast<long long>(channels) * ngroups) {
-        if (pl->d_stream_pieces) { HIP_TRY(hipFree(pl->d_stream_pieces)); pl->d_stream_pieces = nullptr; pl->stream_pieces_cap = 0; }
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&pl->d_stream_pieces), static_cast<size_t>(channels) * ngroups * 4 * sizeof(double)));
-        pl->stream_pieces_cap = static_cast<long long>(channels) * ngroups;
+    if (state) {
+        if (int rc = pl->d_stream_pieces.grow(static_cast<size_t>(channels) * ngroups * 4)) return rc;
     }
     if (int rcs = ensure_status(pl)) return rcs;
     int bpc = pl->stream_slots / channels;                // blocks per channel: spread a small step over the chip
     if (bpc > ngroups) bpc = ngroups;
     if (bpc < 1) bpc = 1;
     hssfsst::Core128Params cp{};
-    cp.x = tape_at; cp.xstride = tape_len; cp.out = out; cp.partials = nullptr; cp.atab = pl->d_atab;
-    cp.wtab = pl->d_wtab; cp.twtab = pl->d_wtab + 2 * pl->nwin; cp.r2scale = pl->r2scale;
+    cp.x = tape_at; cp.xstride = tape_len; cp.out = out; cp.partials = nullptr; cp.atab = pl->d_atab.get();
+    cp.wtab = pl->d_wtab.get(); cp.twtab = pl->d_wtab.get() + 2 * pl->nwin; cp.r2scale = pl->r2scale;
     cp.n = pl->nwin - 1 + chunk; cp.klo = pl->klo; cp.K = pl->K; cp.mode = pl->mode; cp.nsig = channels;
     cp.col0 = pl->nwin / 2; cp.ncols = chunk; cp.reg = reg;
-    cp.xnew = x_new_dev; cp.xnew_stride = x_stride; cp.hist = pl->nwin - 1; cp.bpc = bpc; cp.state = state; cp.arrive = pl->d_stream_arrive; cp.pieces = pl->d_stream_pieces; cp.mirror = mirror;
+    cp.xnew = x_new_dev; cp.xnew_stride = x_stride; cp.hist = pl->nwin - 1; cp.bpc = bpc; cp.state = state; cp.arrive = pl->d_stream_arrive.get(); cp.pieces = pl->d_stream_pieces.get(); cp.mirror = mirror;
     const long long grid = static_cast<long long>(channels) * bpc;
     cp.status = pl->d_status;
     name_kernel(pl, WPB, grid, "fsst_core128_kernel<%d, %d, %d, true, %d, -1, false, stream%s>", NT, RQ, kFpw128, WPB, PAIR ? ", pairs" : "");
@@ -448,18 +520,6 @@ int launch_stream(hssfsst_plan* pl, float* tape_at, long long tape_len, const fl
     HIP_TRY(hipGetLastError());
     return 1;
 }
-
-int grow(void** ptr, size_t* cap, size_t need, size_t elem)
-{
-    if (need <= *cap) return 0;
-    if (*ptr) { HIP_TRY(hipFree(*ptr)); *ptr = nullptr; *cap = 0; }
-    hipError_t e = hipMalloc(ptr, need * elem);
-    if (e != hipSuccess) { *ptr = nullptr; return fail(HSSFSST_ENOMEM, "hipMalloc(%zu B): %s", need * elem, hipGetErrorString(e)); }
-    *cap = need;
-    return 0;
-}
-
-int ensure_status(hssfsst_plan* pl);
 
 // Fused z-score launch (nwin = 128, STACK, wide-store epilogue; fsst_mfma128.hpp "Fused z-score"): one persistent block
 // per CU, every CU owns whole signals.  Returns 1 when it launched, 0 when this exec should take the two-kernel path
@@ -545,9 +605,9 @@ int ensure_status(hssfsst_plan* pl)
 // Team kernels: [0] arrival counter, [1] abort word on the device; the identity of the last launch that gave up in pinned host memory.
 int ensure_team_words(hssfsst_plan* pl, hipStream_t st)
 {
-    if (pl->d_arrive) return 0;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&pl->d_arrive), 4 * sizeof(unsigned)));
-    HIP_TRY(hipMemsetAsync(pl->d_arrive, 0, 4 * sizeof(unsigned), st));
+    if (pl->d_arrive.get()) return 0;
+    if (int rc = pl->d_arrive.grow(4)) return rc;
+    HIP_TRY(hipMemsetAsync(pl->d_arrive.get(), 0, 4 * sizeof(unsigned), st));
     pl->arrive_total = 0;
     pl->done_total = 0;
     void* h = nullptr;
@@ -627,18 +687,18 @@ int launch_team16(hssfsst_plan* pl, const hssfsst::Core128Params& cp, int64_t ba
     int rc;
     if ((rc = ensure_status(pl)) != 0) return rc;
     const size_t words = static_cast<size_t>(nteams) * slots * kT16SlotWords;
-    if (words > pl->mail_cap) {
-        if ((rc = grow(reinterpret_cast<void**>(&pl->d_mail), &pl->mail_cap, words, sizeof(unsigned long long))) != 0) return rc;
-        HIP_TRY(hipMemsetAsync(pl->d_mail, 0, pl->mail_cap * sizeof(unsigned long long), st));
+    if (words > pl->d_mail.cap) {
+        if ((rc = pl->d_mail.grow(words)) != 0) return rc;
+        HIP_TRY(hipMemsetAsync(pl->d_mail.get(), 0, pl->d_mail.cap * sizeof(unsigned long long), st));
         pl->team_seq = 0;
     }
     if (++pl->team_seq > 0xffffu) {                      // tags would repeat: start over from clean mailboxes
-        HIP_TRY(hipMemsetAsync(pl->d_mail, 0, pl->mail_cap * sizeof(unsigned long long), st));
+        HIP_TRY(hipMemsetAsync(pl->d_mail.get(), 0, pl->d_mail.cap * sizeof(unsigned long long), st));
         pl->team_seq = 1;
     }
     Team16Params tp{};
-    tp.x = cp.x; tp.out = sizeof(OT) == 4 ? cp.out : static_cast<float*>(hout); tp.atab = pl->d_atab16; tp.wtab = cp.wtab; tp.twtab = cp.twtab;
-    tp.mail = pl->d_mail; tp.status = pl->d_status; tp.r2scale_s = pl->canon_r2s; tp.inv_c = pl->canon_inv_c;
+    tp.x = cp.x; tp.out = sizeof(OT) == 4 ? cp.out : static_cast<float*>(hout); tp.atab = pl->d_atab16.get(); tp.wtab = cp.wtab; tp.twtab = cp.twtab;
+    tp.mail = pl->d_mail.get(); tp.status = pl->d_status; tp.r2scale_s = pl->canon_r2s; tp.inv_c = pl->canon_inv_c;
     tp.n = cp.n; tp.nsig = cp.nsig; tp.col0 = cp.col0; tp.ncols = cp.ncols; tp.xstride = cp.xstride;
     tp.team = T; tp.cpc_shift = cpc_shift; tp.slots = slots; tp.seq = pl->team_seq;
     {   // the two float64 divisions of stats_finish (correctly rounded here as there: the same bits)
@@ -649,17 +709,17 @@ int launch_team16(hssfsst_plan* pl, const hssfsst::Core128Params& cp, int64_t ba
     tp.spin_ticks = (spin_us < 10u ? 10u : spin_us > 10000000u ? 10000000u : spin_us) * 100u;
     if ((rc = ensure_team_words(pl, st)) != 0) return rc;
     if (++pl->team_launch == 0u) pl->team_launch = 1u;
-    tp.abort_word = pl->d_arrive + 1; tp.fallbacks = pl->d_fallback; tp.launch = pl->team_launch;
+    tp.abort_word = pl->d_arrive.get() + 1; tp.fallbacks = pl->d_fallback; tp.launch = pl->team_launch;
     const bool force_fallback = debug_switches().team_force_fallback;   // tests: every team launch finds itself given up
     if (force_fallback) {
-        HIP_TRY(hipMemcpyAsync(pl->d_arrive + 1, &pl->team_launch, sizeof(unsigned), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(pl->d_arrive.get() + 1, &pl->team_launch, sizeof(unsigned), hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(pl->d_fallback, &pl->team_launch, sizeof(unsigned), hipMemcpyHostToDevice, st));
     }
-    tp.arrive = pl->d_arrive; tp.arrive_base = pl->arrive_total;
+    tp.arrive = pl->d_arrive.get(); tp.arrive_base = pl->arrive_total;
     pl->arrive_total += static_cast<unsigned>(grid);     // (a plan is single-stream: every block of the earlier launches has arrived)
     pl->flag_launch = 0u;
     if (pl->flag_done && !force_fallback) {              // (hssfsst_exec_pinned & co: the host waits for this exec alone)
-        tp.done = pl->d_arrive + 2; tp.done_base = pl->done_total; tp.host_done = pl->d_fallback + 2;
+        tp.done = pl->d_arrive.get() + 2; tp.done_base = pl->done_total; tp.host_done = pl->d_fallback + 2;
         pl->done_total += static_cast<unsigned>(grid);
         pl->flag_launch = pl->team_launch;
     }
@@ -679,7 +739,7 @@ constexpr int kCanonKlo = kCanonBands[0][0], kCanonK = kCanonBands[0][1];
 
 int canon_band(const hssfsst_plan* pl)                   // index into kCanonBands, or -1
 {
-    if (debug_switches().no_canon || !pl->d_atab16 || pl->nwin != 128) return -1;     // (no_canon: A/B and cross-check tests)
+    if (debug_switches().no_canon || !pl->d_atab16.get() || pl->nwin != 128) return -1;     // (no_canon: A/B and cross-check tests)
     if (!(pl->mode == HSSFSST_MODE_STACK || pl->mode == HSSFSST_MODE_STACK_UNNORM)) return -1;
     for (int i = 0; i < static_cast<int>(sizeof(kCanonBands) / sizeof(kCanonBands[0])); ++i)
         if (pl->klo == kCanonBands[i][0] && pl->K == kCanonBands[i][1]) return i;
@@ -700,7 +760,7 @@ int canon_dispatch(const hssfsst_plan* pl, F&& f)
 hssfsst::CanonParams canon_params(const hssfsst_plan* pl, const hssfsst::Core128Params& cp)
 {
     hssfsst::CanonParams q{};
-    q.x = cp.x; q.out = cp.out; q.partials = cp.partials; q.atab = pl->d_atab16; q.wtab = cp.wtab; q.twtab = cp.twtab;
+    q.x = cp.x; q.out = cp.out; q.partials = cp.partials; q.atab = pl->d_atab16.get(); q.wtab = cp.wtab; q.twtab = cp.twtab;
     q.r2scale_s = pl->canon_r2s; q.inv_c = pl->canon_inv_c;
     q.n = cp.n; q.mode = cp.mode; q.nsig = cp.nsig; q.col0 = cp.col0; q.ncols = cp.ncols; q.xstride = cp.xstride; q.reg = cp.reg;
     q.status = cp.status;
@@ -815,6 +875,43 @@ int plan_next_event(hssfsst_plan* p, hipEvent_t* out_ev)
     return 0;
 }
 
+// hssfsst_plan_timing: every timing_every-th exec records an event in front of its core launch, one behind it and a closing one
+// behind its z-score -- or only the first two when one kernel did everything (ev_chunks -1)
+void timing_begin(hssfsst_plan* p)
+{
+    p->timing_closed = false;
+    p->timing = (p->timing_every > 0 && (p->timing_seq++ % static_cast<unsigned>(p->timing_every)) == 0u) ? 1 : 0;
+}
+int timing_event(hssfsst_plan* p, hipStream_t st)
+{
+    if (!p->timing) return 0;
+    hipEvent_t evt = nullptr;
+    if (int rc = plan_next_event(p, &evt)) return rc;
+    HIP_TRY(hipEventRecord(evt, st));
+    return 0;
+}
+int timing_core_done(hssfsst_plan* p, hipStream_t st)   // (the team path has recorded it already, right behind the team kernel)
+{
+    if (p->timing && p->timing_closed) { p->timing_closed = false; return 0; }
+    return timing_event(p, st);
+}
+int timing_end(hssfsst_plan* p, hipStream_t st, bool one_kernel)
+{
+    if (!p->timing) return 0;
+    if (!one_kernel)
+        if (int rc = timing_event(p, st)) return rc;
+    p->ev_chunks.push_back(one_kernel ? -1 : 1);
+    return 0;
+}
+
+// f(o) with a half plan's output `out` as what it holds: _Float16* or __bf16*
+template <class F>
+void half_dispatch(const hssfsst_plan* p, void* out, F&& f)
+{
+    if (p->out_dtype == HSSFSST_DTYPE_F16) f(static_cast<_Float16*>(out));
+    else f(static_cast<__bf16*>(out));
+}
+
 // The plain (two-launch) core kernel for a plan of the MFMA kernel: as many waves per block as fit the 160 KiB of LDS beside
 // the shared tables.  RAGGED: the instantiations of hssfsst_exec_ragged (the same ladder, chunk list from the host).
 template <bool RAGGED>
@@ -872,8 +969,8 @@ int launch_core128(hssfsst_plan* pl, const float* dx, long long xstride, float* 
     const bool half = hout != nullptr;
     hssfsst::Core128Params cp{};
     cp.xstride = xstride;
-    cp.x = dx; cp.out = dout; cp.partials = partials; cp.atab = pl->d_atab;
-    cp.wtab = pl->d_wtab; cp.twtab = pl->d_wtab + 2 * pl->nwin; cp.r2scale = pl->r2scale;
+    cp.x = dx; cp.out = dout; cp.partials = partials; cp.atab = pl->d_atab.get();
+    cp.wtab = pl->d_wtab.get(); cp.twtab = pl->d_wtab.get() + 2 * pl->nwin; cp.r2scale = pl->r2scale;
     cp.n = n; cp.klo = pl->klo; cp.K = pl->K; cp.mode = pl->mode; cp.nsig = static_cast<int>(batch);
     cp.col0 = col0; cp.ncols = ncols;
     cp.reg = hssfsst::core128_regions((ncols + 15) / 16, batch);
@@ -918,12 +1015,8 @@ int launch_core128(hssfsst_plan* pl, const float* dx, long long xstride, float* 
                 // them apart: fsst_team16.hpp "Progress"): the same exec is queued behind it, every kernel of it gated on the
                 // abort word -- a few microseconds of empty launches when nothing went wrong
                 pl->last_zpath = 2;
-                if (pl->timing) {                        // the kernel's own time: the closing event goes in front of the gated launches
-                    hipEvent_t evt = nullptr;
-                    if (int rce = plan_next_event(pl, &evt)) return rce;
-                    HIP_TRY(hipEventRecord(evt, st));
-                    pl->timing_closed = true;
-                }
+                if (int rce = timing_event(pl, st)) return rce;      // the kernel's own time: the closing event goes in front of the gated launches
+                pl->timing_closed = pl->timing != 0;
 #ifdef HSS_NO_GATE                                        // development: what the gated launch behind every team launch costs (UNSAFE: no fallback)
                 if (true) {
 #else
@@ -934,7 +1027,7 @@ int launch_core128(hssfsst_plan* pl, const float* dx, long long xstride, float* 
                     *did_fuse = true;
                     return 0;
                 }
-                pl->gate = pl->d_arrive + 1; pl->gate_val = pl->team_launch;
+                pl->gate = pl->d_arrive.get() + 1; pl->gate_val = pl->team_launch;
                 // ONE gated launch where the one-CU-per-signal kernel applies (signals of 16 .. 32 chunks; its batch
                 // conditions are about speed only): 4 us behind the team kernel instead of 11 for transform + statistics +
                 // z-score launches -- a third of a 50-window exec
@@ -1071,17 +1164,10 @@ int hssfsst_plan_create_ex(hssfsst_plan** out, int device, int nwin, const doubl
     if (nwin > 65535) return fail(HSSFSST_EUNSUPPORTED, "plan_create: window length %d exceeds 65535", nwin);
     const bool force_dft = debug_switches().force_dft;    // cross-check: every length on the any-length kernel
     const bool radix_len = nwin == 32 || nwin == 64 || nwin == 128 || nwin == 256 || nwin == 512;
-    int ndev = 0;
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev <= 0) {
-        (void)hipGetLastError();
-        return fail(HSSFSST_ENODEVICE, "plan_create: no HIP device (%s); this library has no CPU path",
-                    e == hipSuccess ? "device count 0" : hipGetErrorString(e));
-    }
-    if (device < 0 || device >= ndev) return fail(HSSFSST_EINVAL, "plan_create: device %d out of range [0,%d)", device, ndev);
+    if (int rc = check_device("plan_create", device)) return rc;
     DEVICE_SCOPE(device);
 
-    hssfsst_plan* p = new (std::nothrow) hssfsst_plan();
+    std::unique_ptr<hssfsst_plan> p(new (std::nothrow) hssfsst_plan());    // (every error path frees what was made, under device_guard_)
     if (!p) return fail(HSSFSST_ENOMEM, "plan_create: host allocation failed");
     p->device = device; p->nwin = nwin; p->R = nwin / 32; p->nf = nwin / 2 + 1; p->mode = mode; p->fs = fs;
     p->out_dtype = out_dtype; p->out_es = out_dtype == HSSFSST_DTYPE_F32 ? sizeof(float) : 2;
@@ -1091,7 +1177,7 @@ int hssfsst_plan_create_ex(hssfsst_plan** out, int device, int nwin, const doubl
     // derivative window in BIN units: dw * nwin/fs with dw = slope * fs/(2 pi)  =>  slope * nwin/(2 pi)
     std::vector<double> dwb(nwin);
     int rc = spline_knot_slopes(window, nwin, dwb.data());
-    if (rc != 0) { delete p; return fail(rc, "plan_create: singular spline system"); }
+    if (rc != 0) return fail(rc, "plan_create: singular spline system");
     for (int i = 0; i < nwin; ++i) dwb[i] *= static_cast<double>(nwin) / (2.0 * M_PI);
 
     p->dft = (!radix_len || force_dft) ? 1 : 0;
@@ -1119,10 +1205,7 @@ int hssfsst_plan_create_ex(hssfsst_plan** out, int device, int nwin, const doubl
             }
         }
     }
-    e = hipMalloc(reinterpret_cast<void**>(&p->d_ctab), tab.size() * sizeof(float));
-    if (e != hipSuccess) { delete p; return fail(HSSFSST_ENOMEM, "plan_create: hipMalloc: %s", hipGetErrorString(e)); }
-    e = hipMemcpy(p->d_ctab, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(p->d_ctab); delete p; return fail(HSSFSST_EHIP, "plan_create: hipMemcpy: %s", hipGetErrorString(e)); }
+    if ((rc = p->d_ctab.upload(tab.data(), tab.size())) != 0) return rc;
     {   // float64 tables of the rounding-tie path: the window pair and the twiddles
         std::vector<double> wt(static_cast<size_t>(4) * nwin);
         double cmax2 = 0.0;
@@ -1156,13 +1239,7 @@ int hssfsst_plan_create_ex(hssfsst_plan** out, int device, int nwin, const doubl
                                 (sub & 1) ? sg * (wv * sn + dv * c) : sg * (wv * c - dv * sn);
                         }
         }
-        e = hipMalloc(reinterpret_cast<void**>(&p->d_wtab), wt.size() * sizeof(double));
-        if (e == hipSuccess) e = hipMemcpy(p->d_wtab, wt.data(), wt.size() * sizeof(double), hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            if (p->d_wtab) (void)hipFree(p->d_wtab);
-            (void)hipFree(p->d_ctab); delete p;
-            return fail(HSSFSST_EHIP, "plan_create: float64 table upload: %s", hipGetErrorString(e));
-        }
+        if ((rc = p->d_wtab.upload(wt.data(), wt.size())) != 0) return rc;
     }
     const bool force_generic = debug_switches().force_generic;
     const bool mfma_long = !debug_switches().no_mfma256;   // A/B: nwin 256 / 512 on the generic kernel
@@ -1175,11 +1252,9 @@ int hssfsst_plan_create_ex(hssfsst_plan** out, int device, int nwin, const doubl
         // (k' (n + m) is reduced modulo N in integers before the angle is formed)
         const int nf = p->nf, nk4 = (nwin + 3) / 4, nblk4 = (nf + 3) / 4, m = nwin / 2;
         const size_t per_wave = static_cast<size_t>(hssfsst::dft_wave_lds_floats(nk4, p->K > 0 ? p->K : 1)) * sizeof(float);
-        if (per_wave > static_cast<size_t>(kMaxLdsBytes)) {
-            (void)hipFree(p->d_ctab); (void)hipFree(p->d_wtab); delete p;
+        if (per_wave > static_cast<size_t>(kMaxLdsBytes))
             return fail(HSSFSST_EUNSUPPORTED, "plan_create: window length %d with %d kept rows needs %zu B of LDS per wave (> 160 KiB): "
                                               "narrow the band", nwin, p->K, per_wave);
-        }
         std::vector<float> dt(static_cast<size_t>(nblk4) * nk4 * 64, 0.0f);
         for (int blk = 0; blk < nblk4; ++blk)
             for (int ks = 0; ks < nk4; ++ks)
@@ -1191,13 +1266,7 @@ int hssfsst_plan_create_ex(hssfsst_plan** out, int device, int nwin, const doubl
                     const double amp = (sub < 2) ? window[n] : dwb[n];
                     dt[(static_cast<size_t>(blk) * nk4 + ks) * 64 + l] = static_cast<float>(amp * ((sub & 1) ? std::sin(ang) : std::cos(ang)));
                 }
-        e = hipMalloc(reinterpret_cast<void**>(&p->d_dtab), dt.size() * sizeof(float));
-        if (e == hipSuccess) e = hipMemcpy(p->d_dtab, dt.data(), dt.size() * sizeof(float), hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            if (p->d_dtab) (void)hipFree(p->d_dtab);
-            (void)hipFree(p->d_ctab); (void)hipFree(p->d_wtab); delete p;
-            return fail(HSSFSST_EHIP, "plan_create: DFT table upload (%zu B): %s", dt.size() * sizeof(float), hipGetErrorString(e));
-        }
+        if ((rc = p->d_dtab.upload(dt.data(), dt.size())) != 0) return rc;
     }
     const int nt0 = (nwin == 512) ? 32 : 16, rq0 = nwin / nt0;
     if (use_mfma) {                                      // enough wave regions of this band must fit beside the A table
@@ -1235,13 +1304,7 @@ int hssfsst_plan_create_ex(hssfsst_plan** out, int device, int nwin, const doubl
             hssfsst::core128_store_offsets(p->klo, p->K > 0 ? p->K : 2, offs, rq);
             std::memcpy(at.data() + atab_floats, offs, sizeof(offs));
         }
-        e = hipMalloc(reinterpret_cast<void**>(&p->d_atab), at.size() * sizeof(float));
-        if (e == hipSuccess) e = hipMemcpy(p->d_atab, at.data(), at.size() * sizeof(float), hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            if (p->d_atab) (void)hipFree(p->d_atab);
-            (void)hipFree(p->d_ctab); (void)hipFree(p->d_wtab); delete p;
-            return fail(HSSFSST_EHIP, "plan_create: A-table upload: %s", hipGetErrorString(e));
-        }
+        if ((rc = p->d_atab.upload(at.data(), at.size())) != 0) return rc;
         if (nwin == 128) {
             // fsst_canon128.hpp: the same constants C_r[n, q] as pairs of halves c1 + c2, scaled by 2^sc into [2^13, 2^14).
             // Entry (tap n, lane l = (kk, row i), half h): fold term q = kk + 4 (h >> 2), c1 for even h, c2 for odd h
@@ -1261,7 +1324,7 @@ int hssfsst_plan_create_ex(hssfsst_plan** out, int device, int nwin, const doubl
             if (cmax > 0.0 && std::isfinite(cmax)) (void)std::frexp(cmax, &ex);          // cmax = f 2^ex, f in [0.5, 1)
             const int sc = 14 - ex;                                                       // cmax 2^sc in [2^13, 2^14)
             const double cs = std::ldexp(1.0, sc);
-            // (+ the float64 twiddles of the rounding-tie path, 2 kB: the kernels copy the whole table into LDS)
+            // (+ the float64 twiddles of the rounding-tie path, 2 kB: the kernels copy the whole table into LDS); then the offsets below
             std::vector<unsigned short> ht(static_cast<size_t>(hssfsst::kCanonAtabFloats) * 2);
             static_assert(hssfsst::kCanonAtabFloats == 16 * 64 * 4 + 4 * 128, "f16 operand table + 128 {cos, sin} doubles");
             for (int i = 0; i < 128; ++i) {
@@ -1322,17 +1385,13 @@ int hssfsst_plan_create_ex(hssfsst_plan** out, int device, int nwin, const doubl
             }
             p->canon_inv_c = static_cast<float>(std::ldexp(1.0, -sc));
             p->canon_r2s = static_cast<float>(static_cast<double>(p->r2scale) * cs * cs);
-            e = hipMalloc(reinterpret_cast<void**>(&p->d_atab16), ht.size() * sizeof(unsigned short) + zc.size() * sizeof(float));
-            if (e == hipSuccess) e = hipMemcpy(p->d_atab16, ht.data(), ht.size() * sizeof(unsigned short), hipMemcpyHostToDevice);
-            if (e == hipSuccess) e = hipMemcpy(p->d_atab16 + hssfsst::kCanonAtabFloats, zc.data(), zc.size() * sizeof(float), hipMemcpyHostToDevice);
-            if (e != hipSuccess) {
-                if (p->d_atab16) (void)hipFree(p->d_atab16);
-                (void)hipFree(p->d_atab); (void)hipFree(p->d_ctab); (void)hipFree(p->d_wtab); delete p;
-                return fail(HSSFSST_EHIP, "plan_create: f16 A-table upload: %s", hipGetErrorString(e));
-            }
+            std::vector<float> t16(static_cast<size_t>(hssfsst::kCanonAtabFloats) + zc.size());
+            std::memcpy(t16.data(), ht.data(), ht.size() * sizeof(unsigned short));
+            std::memcpy(t16.data() + hssfsst::kCanonAtabFloats, zc.data(), zc.size() * sizeof(float));
+            if ((rc = p->d_atab16.upload(t16.data(), t16.size())) != 0) return rc;
         }
     }
-    *out = p;
+    *out = p.release();
     return 0;
 }
 
@@ -1340,34 +1399,11 @@ int hssfsst_plan_destroy(hssfsst_plan* p)
 {
     if (!p) return 0;
     DeviceGuard device_guard_(p->device);
-    if (p->d_ctab) (void)hipFree(p->d_ctab);
-    if (p->d_wtab) (void)hipFree(p->d_wtab);
-    if (p->d_dtab) (void)hipFree(p->d_dtab);
-    if (p->d_atab) (void)hipFree(p->d_atab);
-    if (p->d_atab16) (void)hipFree(p->d_atab16);
-    if (p->d_stream_arrive) (void)hipFree(p->d_stream_arrive);
-    if (p->d_stream_pieces) (void)hipFree(p->d_stream_pieces);
-    if (p->d_partials) (void)hipFree(p->d_partials);
-    if (p->d_f32) (void)hipFree(p->d_f32);
     if (p->h_status) (void)hipHostFree(const_cast<unsigned*>(p->h_status));
-    if (p->d_mail) (void)hipFree(p->d_mail);
-    if (p->d_arrive) (void)hipFree(p->d_arrive);
     if (p->h_fallback) (void)hipHostFree(const_cast<unsigned*>(p->h_fallback));
-    if (p->d_stats) (void)hipFree(p->d_stats);
-    if (p->d_xstage) (void)hipFree(p->d_xstage);
-    if (p->d_ostage) (void)hipFree(p->d_ostage);
-    if (p->h_xpin) (void)hipHostFree(p->h_xpin);
-    if (p->h_opin) (void)hipHostFree(p->h_opin);
-    for (auto& b : p->pin_pool) if (b.h) (void)hipHostFree(b.h);
-    if (p->d_starts) (void)hipFree(p->d_starts);
-    if (p->d_frames) (void)hipFree(p->d_frames);
-    if (p->d_rtab) (void)hipFree(p->d_rtab);
-    if (p->h_rtab) (void)hipHostFree(p->h_rtab);
     if (p->rtab_ev) (void)hipEventDestroy(p->rtab_ev);
     for (auto& ev : p->ev) if (ev) (void)hipEventDestroy(ev);
-    for (auto& ev : p->sync_ev) if (ev) (void)hipEventDestroy(ev);
-    if (p->aux) (void)hipStreamDestroy(p->aux);
-    delete p;
+    delete p;                                            // (the buffers free themselves)
     return 0;
 }
 
@@ -1550,6 +1586,63 @@ int hssfsst_exec_cols(hssfsst_plan* p, const float* x, int64_t batch, int n, int
     return hssfsst_exec_frames(p, x, batch, n, static_cast<int64_t>(n), col0, ncols, x_on_device, out, out_on_device, stream);
 }
 
+// ---- what every exec entry point shares
+
+// A wait inside an EARLIER exec's kernel gave up (pinned status word, no synchronisation): that exec's features are invalid and
+// the caller of a device-output exec has not been told yet -- refuse, once, until the plan is checked.
+static int take_pending_status(hssfsst_plan* p, const char* what)
+{
+    if (!p->h_status || *p->h_status == 0u) return 0;
+    const unsigned code = *p->h_status;
+    *p->h_status = 0u;
+    return fail(HSSFSST_EHIP, "%s: a wait inside a previous exec's z-score kernel gave up (code %u); the results of that exec are invalid",
+                what, code);
+}
+
+// nx floats of a host input into the plan's device staging buffer; *dx then points there
+static int stage_input(hssfsst_plan* p, const float* x, size_t nx, const float** dx, hipStream_t st)
+{
+    if (int rc = p->d_xstage.grow(nx)) return rc;
+    HIP_TRY(hipMemcpyAsync(p->d_xstage.get(), x, nx * sizeof(float), hipMemcpyHostToDevice, st));
+    *dx = p->d_xstage.get();
+    return 0;
+}
+
+// The device side of an exec's `no` output elements: *dout (staged when the output is a host one), *kout where the kernels write
+// float32 features (half plans: the plan's float32 scratch, from which the z-score sweep writes the 2-byte elements to *dout), and
+// for STACK the statistics partials (`pieces` of them) and statistics of `nsig` signals.
+static int exec_buffers(hssfsst_plan* p, size_t no, bool stage_out, size_t pieces, int64_t nsig, float** dout, float** kout)
+{
+    int rc;
+    if (stage_out) {
+        if ((rc = p->d_ostage.grow((no * p->out_es + sizeof(float) - 1) / sizeof(float))) != 0) return rc;
+        *dout = p->d_ostage.get();
+    }
+    *kout = *dout;
+    if (p->out_es != sizeof(float)) {
+        if ((rc = p->d_f32.grow(no)) != 0) return rc;
+        *kout = p->d_f32.get();
+    }
+    if (p->mode == HSSFSST_MODE_STACK) {
+        if ((rc = p->d_partials.grow(pieces * hssfsst::kPartFloats)) != 0) return rc;
+        if ((rc = p->d_stats.grow(static_cast<size_t>(nsig) * 4)) != 0) return rc;
+    }
+    return 0;
+}
+
+// The end of an exec: a host output is copied back, the stream synchronised and the plan checked; a host input is only waited for
+// (the caller may reuse it)
+static int exec_finish(hssfsst_plan* p, void* out, const void* dout, size_t bytes, int x_on_device, int out_on_device, hipStream_t st)
+{
+    if (!out_on_device) {
+        HIP_TRY(hipMemcpyAsync(out, dout, bytes, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return hssfsst_plan_check(p);
+    }
+    if (!x_on_device) HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
 // The one exec: `batch` signals of n samples, signal b at x + b * x_stride, or -- d_starts != nullptr (device array) --
 // at x + d_starts[b] inside a buffer of x_len samples.  A frame list is first gathered into a dense [batch][n] staging
 // buffer (fsst_gather_frames_kernel: 8 kB read + 8 kB written per frame, against 360 kB of output) and then takes the
@@ -1566,16 +1659,10 @@ static int exec_impl(hssfsst_plan* p, const float* x, int64_t batch, int n, int6
     if (batch == 0 || p->K == 0) return 0;
     hipStream_t st = static_cast<hipStream_t>(stream);
     DEVICE_SCOPE(p->device);
-    // a wait inside an EARLIER exec's kernel gave up (pinned status word, no synchronisation): that exec's features are
-    // invalid and the caller of a device-output exec has not been told yet -- refuse until the plan is checked
-    if (p->h_status && *p->h_status != 0u) {
-        const unsigned code = *p->h_status;
-        *p->h_status = 0u;
-        return fail(HSSFSST_EHIP, "exec: a wait inside a previous exec's z-score kernel gave up (code %u); the results of that "
-                    "exec are invalid", code);
-    }
+    int rc;
+    if ((rc = take_pending_status(p, "exec")) != 0) return rc;
     const int ofps = out_floats_per_sample(p);
-    const bool use128 = (p->d_atab != nullptr);
+    const bool use128 = (p->d_atab.get() != nullptr);
     // statistics partials per signal: one per 16-frame group (MFMA kernel) / per 64-frame tile (generic kernel)
     const int fpp = (use128 || p->dft) ? 16 : kTile;
     const int nblk = (ncols + fpp - 1) / fpp;
@@ -1590,7 +1677,6 @@ static int exec_impl(hssfsst_plan* p, const float* x, int64_t batch, int n, int6
 
     const float* dx = x;
     float* dout = out;
-    int rc;
     // Small host-to-host execs -- the reference's dataset loop calls the transform once per 2000-sample frame with CPU tensors
     // (/root/reference/hss/datasets/heart_sounds.py:166-168,199-201) -- do not go through hipMemcpyAsync from / to pageable memory
     // (two staged copies by the runtime, ~0.03 ms of a 0.068 ms call): the samples are copied into a pinned, device-mapped buffer
@@ -1604,36 +1690,27 @@ static int exec_impl(hssfsst_plan* p, const float* x, int64_t batch, int n, int6
                                                              p->zpath_pref != HSSFSST_ZPATH_ONE_CU && p->zpath_pref != HSSFSST_ZPATH_TWO_LAUNCH &&
                                                              (p->team_pause == 0 || p->zpath_pref == HSSFSST_ZPATH_TEAM) &&
                                                              (ncols + 15) / 16 <= hssfsst::kFusedMaxGroups));
-    auto pin = [&](float** h, float** d, size_t* cap, size_t need) -> int {
-        if (*cap >= need) return 0;
-        if (*h) { HIP_TRY(hipStreamSynchronize(st)); HIP_TRY(hipHostFree(*h)); *h = nullptr; *d = nullptr; *cap = 0; }
-        size_t c = 1 << 12;
-        while (c < need) c *= 2;
-        void* hp = nullptr; void* dp = nullptr;
-        HIP_TRY(hipHostMalloc(&hp, c * sizeof(float), hipHostMallocMapped));
-        HIP_TRY(hipHostGetDevicePointer(&dp, hp, 0));
-        *h = static_cast<float*>(hp); *d = static_cast<float*>(dp); *cap = c;
-        return 0;
+    auto pin = [&](PinnedBuf<float>& b, size_t need) -> int {
+        if (b.h && b.cap < need) HIP_TRY(hipStreamSynchronize(st));     // (earlier work on the stream may still use the old block)
+        return b.grow(need, sizeof(float));
     };
     if (tiny_in) {
-        if ((rc = pin(&p->h_xpin, &p->d_xpin, &p->xpin_cap, nx)) != 0) return rc;
-        std::memcpy(p->h_xpin, x, nx * sizeof(float));
-        dx = p->d_xpin;
+        if ((rc = pin(p->xpin, nx)) != 0) return rc;
+        std::memcpy(p->xpin.h, x, nx * sizeof(float));
+        dx = p->xpin.d;
     } else if (!x_on_device) {
-        if ((rc = grow(reinterpret_cast<void**>(&p->d_xstage), &p->xstage_cap, nx, sizeof(float))) != 0) return rc;
-        HIP_TRY(hipMemcpyAsync(p->d_xstage, x, nx * sizeof(float), hipMemcpyHostToDevice, st));
-        dx = p->d_xstage;
+        if ((rc = stage_input(p, x, nx, &dx, st)) != 0) return rc;
     }
     if (d_starts) {
         const size_t nd = static_cast<size_t>(batch) * n;
-        if ((rc = grow(reinterpret_cast<void**>(&p->d_frames), &p->frames_cap, nd, sizeof(float))) != 0) return rc;
+        if ((rc = p->d_frames.grow(nd)) != 0) return rc;
         const long long quads = (static_cast<long long>(n) + 3) / 4;
         long long blocks = (static_cast<long long>(batch) * quads + 255) / 256;
         if (blocks > 65536) blocks = 65536;
         hipLaunchKernelGGL(hssfsst::fsst_gather_frames_kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, st,
-                           dx, d_starts, p->d_frames, static_cast<long long>(batch), n);
+                           dx, d_starts, p->d_frames.get(), static_cast<long long>(batch), n);
         HIP_TRY(hipGetLastError());
-        dx = p->d_frames;
+        dx = p->d_frames.get();
         x_stride = n;
     }
     if (pin_d && !tiny_out) return 1;                    // (not an exec whose features are written once: the caller takes the copying call)
@@ -1641,196 +1718,126 @@ static int exec_impl(hssfsst_plan* p, const float* x, int64_t batch, int n, int6
     if (tiny_out) {
         if (pin_d) dout = pin_d;
         else {
-            if ((rc = pin(&p->h_opin, &p->d_opin, &p->opin_cap, no_f)) != 0) return rc;
-            dout = p->d_opin;
+            if ((rc = pin(p->opin, no_f)) != 0) return rc;
+            dout = p->opin.d;
         }
         p->defer_fallback = p->zpath_pref != HSSFSST_ZPATH_ONE_CU && !d_starts;
         p->deferred_launch = 0u;
-    } else if (!out_on_device) {
-        if ((rc = grow(reinterpret_cast<void**>(&p->d_ostage), &p->ostage_cap, no_f, sizeof(float))) != 0) return rc;
-        dout = p->d_ostage;
     }
-    // half plans: dout receives 2-byte elements; the kernels that write float32 features (every path but the team kernel, and the
-    // gated fallback behind a team launch) write them to the plan's float32 scratch, and the z-score sweep goes from there to dout
-    float* kout = dout;
-    if (half) {
-        if ((rc = grow(reinterpret_cast<void**>(&p->d_f32), &p->f32_cap, no, sizeof(float))) != 0) return rc;
-        kout = p->d_f32;
-    }
-    if (p->mode == HSSFSST_MODE_STACK)
-    {
-        if ((rc = grow(reinterpret_cast<void**>(&p->d_partials), &p->partials_cap, static_cast<size_t>(nblocks) * hssfsst::kPartFloats, sizeof(float))) != 0) return rc;
-        if ((rc = grow(reinterpret_cast<void**>(&p->d_stats), &p->stats_cap, static_cast<size_t>(batch) * 4, sizeof(float))) != 0) return rc;
-    }
+    float* kout = nullptr;
+    if ((rc = exec_buffers(p, no, !tiny_out && !out_on_device, static_cast<size_t>(nblocks), batch, &dout, &kout)) != 0) return rc;
 
-    auto next_event = [&](hipEvent_t* out_ev) -> int { return plan_next_event(p, out_ev); };
-    int timed_chunks = 0;
-    p->timing_closed = false;
-    p->timing = (p->timing_every > 0 && (p->timing_seq++ % static_cast<unsigned>(p->timing_every)) == 0u) ? 1 : 0;
-    // STACK: core (FP32-issue-bound) then the z-score sweep (HBM-bound, in place).  An optional
-    // pipeline (HSSFSST_CHUNKS=k) cuts the batch into k chunks and runs the sweep of chunk i on a side
-    // stream while the core of chunk i+1 runs on the caller's stream.  Measured on MI355X
-    // (tools/chunk_sweep.sh): the overlap LOSES -- the saturating sweep back-pressures the core's own
-    // stores (core 0.25 -> 0.32-0.41 ms per 1024 windows) -- and keeping a chunk inside the 256 MiB
-    // Infinity Cache does not speed the sweep up either, so the default is k = 1.
-    // Also measured and rejected (git history): fusing the z-score into the
-    // core launch -- "last ticket normalises the signal" (write-through stores + one agent acquire:
-    // 0.62 ms; with an L2 write-back release per block: 0.99 ms) and "blocks of a signal wait for each
-    // other, then normalise their own tiles" (bounded spin + fix-up kernel: 0.58 ms) -- both
-    // bit-identical to, and slower than, the two-pass 0.37 ms per 1024 windows.
-    const int64_t per = static_cast<int64_t>(ncols) * ofps;
-    int64_t nchunks = 1;
-    if (p->mode == HSSFSST_MODE_STACK) {
-        if (debug_switches().chunks > 0) nchunks = debug_switches().chunks;
-        if (nchunks > batch) nchunks = batch;
-    }
-    const int64_t chunk = (batch + nchunks - 1) / nchunks;
-    const bool piped = nchunks > 1;
+    timing_begin(p);
+    // STACK: core (FP32-issue-bound) then the z-score sweep (HBM-bound, in place).  Measured and rejected (git history, DESIGN.md
+    // section 4.3): a k-chunk two-stream pipeline that overlaps the sweep of one chunk with the core of the next -- the saturating
+    // sweep back-pressures the core's own stores (core 0.25 -> 0.32-0.41 ms per 1024 windows); fusing the z-score into the
+    // core launch -- "last ticket normalises the signal" (write-through stores + one agent acquire: 0.62 ms; with an L2
+    // write-back release per block: 0.99 ms) and "blocks of a signal wait for each other, then normalise their own tiles"
+    // (bounded spin + fix-up kernel: 0.58 ms) -- both bit-identical to, and slower than, the two-pass 0.37 ms per 1024 windows.
     // a host-output exec of one team launch: the launch's last wave says "done" in pinned host memory and this call waits for that word
     // instead of synchronising the stream (below)
-    p->flag_done = tiny_out && p->defer_fallback && !p->timing && nchunks == 1;
+    p->flag_done = tiny_out && p->defer_fallback && !p->timing;
     p->flag_launch = 0u;
-    if (piped) {
-        if (!p->aux) HIP_TRY(hipStreamCreateWithFlags(&p->aux, hipStreamNonBlocking));
-        while (static_cast<int64_t>(p->sync_ev.size()) < nchunks + 1) {
-            hipEvent_t e2 = nullptr;
-            HIP_TRY(hipEventCreateWithFlags(&e2, hipEventDisableTiming));
-            p->sync_ev.push_back(e2);
+    hssfsst::CoreParams cp;
+    cp.x = dx; cp.out = kout; cp.partials = p->d_partials.get(); cp.ctab = p->d_ctab.get();
+    cp.n = n; cp.klo = p->klo; cp.K = p->K; cp.mode = p->mode; cp.nblk = nblk; cp.col0 = col0; cp.ncols = ncols; cp.xstride = x_stride;
+    cp.wtab = p->d_wtab.get(); cp.twtab = p->d_wtab.get() + 2 * p->nwin; cp.r2scale = p->r2scale;
+    if ((rc = timing_event(p, st)) != 0) return rc;
+    bool did_fuse = false;
+    const bool no_fused = debug_switches().no_fused;      // A/B and bit-equality tests
+    if (p->dft) {
+        hssfsst::DftParams dp{};
+        dp.x = dx; dp.out = kout; dp.partials = cp.partials; dp.atab = p->d_dtab.get();
+        dp.wtab = p->d_wtab.get(); dp.twtab = p->d_wtab.get() + 2 * p->nwin;
+        dp.n = n; dp.nwin = p->nwin; dp.nf = p->nf; dp.klo = p->klo; dp.K = p->K; dp.mode = p->mode; dp.col0 = col0; dp.ncols = ncols;
+        dp.nk4 = (p->nwin + 3) / 4; dp.nblk4 = (p->nf + 3) / 4;
+        dp.nitems = nblocks; dp.xstride = x_stride; dp.r2scale = p->r2scale;
+        // groups per work item: 4 when four planes fit the LDS of a wave (each A-operand load then feeds four MFMAs),
+        // else 2, else 1; then as many waves per block as fit (at most 8)
+        // largest tile that still leaves >= 16 waves resident per CU (the MFMA chains are dependent: latency is hidden
+        // by waves, not by the tile), else whatever keeps the most waves (measured: nwin 100 is fastest with small tiles)
+        int G = 1, best_waves = -1;
+        for (int cand = 4; cand >= 1; cand >>= 1) {
+            const size_t pw = static_cast<size_t>(hssfsst::dft_wave_lds_floats(dp.nk4, p->K, cand)) * sizeof(float);
+            int w = static_cast<int>(static_cast<size_t>(kMaxLdsBytes) / pw);
+            if (w > 8) w = 8;
+            if (w < 1) continue;
+            int per_cu = static_cast<int>(static_cast<size_t>(kMaxLdsBytes) / (pw * w)) * w;
+            if (per_cu > 32) per_cu = 32;
+            if (per_cu >= 16) { G = cand; best_waves = per_cu; break; }
+            if (per_cu > best_waves) { G = cand; best_waves = per_cu; }
         }
-    }
-    int ci = 0;
-    for (int64_t c0 = 0; c0 < batch; c0 += chunk, ++ci) {
-        const int64_t cb = (batch - c0 < chunk) ? batch - c0 : chunk;
-        const float* cx = dx + c0 * x_stride;
-        float* cout = kout + c0 * per;
-        void* hcout = half ? static_cast<void*>(reinterpret_cast<char*>(dout) + static_cast<size_t>(c0 * per) * es) : nullptr;
-        hssfsst::CoreParams cp;
-        cp.x = cx; cp.out = cout; cp.partials = p->d_partials ? p->d_partials + c0 * nblk * hssfsst::kPartFloats : nullptr; cp.ctab = p->d_ctab;
-        cp.n = n; cp.klo = p->klo; cp.K = p->K; cp.mode = p->mode; cp.nblk = nblk; cp.col0 = col0; cp.ncols = ncols; cp.xstride = x_stride;
-        cp.wtab = p->d_wtab; cp.twtab = p->d_wtab + 2 * p->nwin; cp.r2scale = p->r2scale;
-        const long long cblocks = static_cast<long long>(cb) * nblk;
-        hipEvent_t evt = nullptr;
-        if (p->timing) { if ((rc = next_event(&evt)) != 0) return rc; HIP_TRY(hipEventRecord(evt, st)); }
-        bool did_fuse = false;
-        const bool no_fused = debug_switches().no_fused;  // A/B and bit-equality tests
-        if (p->dft) {
-            hssfsst::DftParams dp{};
-            dp.x = cx; dp.out = cout; dp.partials = cp.partials; dp.atab = p->d_dtab;
-            dp.wtab = p->d_wtab; dp.twtab = p->d_wtab + 2 * p->nwin;
-            dp.n = n; dp.nwin = p->nwin; dp.nf = p->nf; dp.klo = p->klo; dp.K = p->K; dp.mode = p->mode; dp.col0 = col0; dp.ncols = ncols;
-            dp.nk4 = (p->nwin + 3) / 4; dp.nblk4 = (p->nf + 3) / 4;
-            dp.nitems = static_cast<long long>(cb) * nblk; dp.xstride = x_stride; dp.r2scale = p->r2scale;
-            // groups per work item: 4 when four planes fit the LDS of a wave (each A-operand load then feeds four MFMAs),
-            // else 2, else 1; then as many waves per block as fit (at most 8)
-            // largest tile that still leaves >= 16 waves resident per CU (the MFMA chains are dependent: latency is hidden
-            // by waves, not by the tile), else whatever keeps the most waves (measured: nwin 100 is fastest with small tiles)
-            int G = 1, best_waves = -1;
-            for (int cand = 4; cand >= 1; cand >>= 1) {
-                const size_t pw = static_cast<size_t>(hssfsst::dft_wave_lds_floats(dp.nk4, p->K, cand)) * sizeof(float);
-                int w = static_cast<int>(static_cast<size_t>(kMaxLdsBytes) / pw);
-                if (w > 8) w = 8;
-                if (w < 1) continue;
-                int per_cu = static_cast<int>(static_cast<size_t>(kMaxLdsBytes) / (pw * w)) * w;
-                if (per_cu > 32) per_cu = 32;
-                if (per_cu >= 16) { G = cand; best_waves = per_cu; break; }
-                if (per_cu > best_waves) { G = cand; best_waves = per_cu; }
-            }
-            if (ncols <= 16) G = 1;
-            const size_t per_wave = static_cast<size_t>(hssfsst::dft_wave_lds_floats(dp.nk4, p->K, G)) * sizeof(float);
-            int waves = static_cast<int>(static_cast<size_t>(kMaxLdsBytes) / per_wave);
-            if (waves > 8) waves = 8;
-            if (waves < 1) return fail(HSSFSST_EUNSUPPORTED, "exec: LDS request %zu B per wave exceeds 160 KiB", per_wave);
-            const int ntiles = (ncols + 16 * G - 1) / (16 * G);
-            dp.nitems = static_cast<long long>(cb) * ntiles;
-            long long blocks = (dp.nitems + waves - 1) / waves;
-            if (blocks > 256 * 64) blocks = 256 * 64;                       // grid-stride beyond that
-            auto launch = [&](auto kern) -> int {
-                static std::atomic<unsigned long long> lds_ok{0};
-                if (int r2 = allow_full_lds(kern, p->device, lds_ok)) return r2;
-                name_kernel(p, waves, blocks, "fsst_dft_kernel<%d>", G);
-                hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(blocks)), dim3(64 * waves), per_wave * waves, st, dp);
-                return (hipGetLastError() == hipSuccess) ? 0 : fail(HSSFSST_EHIP, "exec: fsst_dft_kernel launch failed");
-            };
-            rc = (G == 4) ? launch(hssfsst::fsst_dft_kernel<4>) : (G == 2) ? launch(hssfsst::fsst_dft_kernel<2>) : launch(hssfsst::fsst_dft_kernel<1>);
-        } else if (use128) {
-            rc = launch_core128(p, cx, x_stride, cout, cp.partials, n, col0, ncols, cb, st, !no_fused && !piped && p->zpath_pref != HSSFSST_ZPATH_TWO_LAUNCH, &did_fuse,
-                                hcout);
-        } else switch (p->R) {
-            case 1: rc = launch_core<1>(p, cp, cblocks, st); break;
-            case 2: rc = launch_core<2>(p, cp, cblocks, st); break;
+        if (ncols <= 16) G = 1;
+        const size_t per_wave = static_cast<size_t>(hssfsst::dft_wave_lds_floats(dp.nk4, p->K, G)) * sizeof(float);
+        int waves = static_cast<int>(static_cast<size_t>(kMaxLdsBytes) / per_wave);
+        if (waves > 8) waves = 8;
+        if (waves < 1) return fail(HSSFSST_EUNSUPPORTED, "exec: LDS request %zu B per wave exceeds 160 KiB", per_wave);
+        const int ntiles = (ncols + 16 * G - 1) / (16 * G);
+        dp.nitems = static_cast<long long>(batch) * ntiles;
+        long long blocks = (dp.nitems + waves - 1) / waves;
+        if (blocks > 256 * 64) blocks = 256 * 64;                       // grid-stride beyond that
+        auto launch = [&](auto kern) -> int {
+            static std::atomic<unsigned long long> lds_ok{0};
+            if (int r2 = allow_full_lds(kern, p->device, lds_ok)) return r2;
+            name_kernel(p, waves, blocks, "fsst_dft_kernel<%d>", G);
+            hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(blocks)), dim3(64 * waves), per_wave * waves, st, dp);
+            return (hipGetLastError() == hipSuccess) ? 0 : fail(HSSFSST_EHIP, "exec: fsst_dft_kernel launch failed");
+        };
+        rc = (G == 4) ? launch(hssfsst::fsst_dft_kernel<4>) : (G == 2) ? launch(hssfsst::fsst_dft_kernel<2>) : launch(hssfsst::fsst_dft_kernel<1>);
+    } else if (use128) {
+        rc = launch_core128(p, dx, x_stride, kout, cp.partials, n, col0, ncols, batch, st, !no_fused && p->zpath_pref != HSSFSST_ZPATH_TWO_LAUNCH, &did_fuse,
+                            half ? dout : nullptr);
+    } else switch (p->R) {
+        case 1: rc = launch_core<1>(p, cp, nblocks, st); break;
+        case 2: rc = launch_core<2>(p, cp, nblocks, st); break;
 #ifndef HSS_DEV_ONLY128
-            case 4: rc = launch_core<4>(p, cp, cblocks, st); break;
-            case 8: rc = launch_core<8>(p, cp, cblocks, st); break;
-            case 16: rc = launch_core<16>(p, cp, cblocks, st); break;
+        case 4: rc = launch_core<4>(p, cp, nblocks, st); break;
+        case 8: rc = launch_core<8>(p, cp, nblocks, st); break;
+        case 16: rc = launch_core<16>(p, cp, nblocks, st); break;
 #endif
-            default: rc = fail(HSSFSST_EUNSUPPORTED, "exec: unsupported radix %d", p->R);
+        default: rc = fail(HSSFSST_EUNSUPPORTED, "exec: unsupported radix %d", p->R);
+    }
+    if (rc != 0) return rc;
+    if ((rc = timing_core_done(p, st)) != 0) return rc;
+    const unsigned* gate = p->gate;                      // non-null: a team launch went first; what follows is its gated fallback
+    const unsigned gate_val = p->gate_val;
+    p->gate = nullptr;
+    p->last_fused = (did_fuse || gate != nullptr) ? 1 : 0;
+    if (p->mode == HSSFSST_MODE_STACK && !did_fuse) {
+        float4* stats = reinterpret_cast<float4*>(p->d_stats.get());
+        const int zgrid_env = debug_switches().zgrid;
+        const bool split_stats = debug_switches().split_stats;   // A/B: separate statistics launch
+        int64_t zgrid = zgrid_env > 0 ? zgrid_env : 4096;
+        // small batches: several blocks per signal, else one block per signal would leave most CUs idle
+        int slices = 1;
+        const int zslices_env = debug_switches().zslices;
+        if (zslices_env > 0) {
+            slices = zslices_env;
+            zgrid = batch * slices;
+        } else if (zgrid_env <= 0 && batch < 1024) {
+            slices = static_cast<int>(1024 / batch);
+            if (slices > 32) slices = 32;
         }
-        if (rc != 0) return rc;
-        if (p->timing) {
-            if (p->timing_closed) p->timing_closed = false;
-            else { if ((rc = next_event(&evt)) != 0) return rc; HIP_TRY(hipEventRecord(evt, st)); }
-            ++timed_chunks;
-        }
-        const unsigned* gate = p->gate;                  // non-null: a team launch went first; what follows is its gated fallback
-        const unsigned gate_val = p->gate_val;
-        p->gate = nullptr;
-        p->last_fused = (did_fuse || gate != nullptr) ? 1 : 0;
-        if (p->mode == HSSFSST_MODE_STACK && !did_fuse) {
-            hipStream_t zs = st;
-            if (piped) {
-                HIP_TRY(hipEventRecord(p->sync_ev[ci], st));
-                HIP_TRY(hipStreamWaitEvent(p->aux, p->sync_ev[ci], 0));
-                zs = p->aux;
-            }
-            float4* cstats = reinterpret_cast<float4*>(p->d_stats) + c0;
-            const int zgrid_env = debug_switches().zgrid;
-            const bool split_stats = debug_switches().split_stats;   // A/B: separate statistics launch
-            int64_t zgrid = zgrid_env > 0 ? zgrid_env : (piped ? 512 : 4096);
-            // small batches: several blocks per signal, else one block per signal would leave most CUs idle
-            int slices = 1;
-            const int zslices_env = debug_switches().zslices;
-            if (zslices_env > 0) {
-                slices = zslices_env;
-                zgrid = cb * slices;
-            } else if (zgrid_env <= 0 && !piped && cb < 1024) {
-                slices = static_cast<int>(1024 / cb);
-                if (slices > 32) slices = 32;
-            }
-            if (zgrid > cb * slices) zgrid = cb * slices;
-            // big batches, a block per signal: it reduces the signal's partials itself (no separate statistics
-            // launch, 4-7 us per step); otherwise a tiny kernel does all reductions at once
-            const bool fused = !split_stats && slices == 1 && zgrid == cb && cb >= 512;
-            if (!fused)
-                hipLaunchKernelGGL(hssfsst::fsst_stats_kernel, dim3(static_cast<unsigned>(cb)), dim3(64), 0, zs,
-                                   cp.partials, cstats, nblk, fpp, ncols, p->K, gate, gate_val);
-            if (half) {                                  // out of place: float32 scratch -> 2-byte elements (fsst_half.hpp)
-                auto sweep = [&](auto* o) {
-                    hipLaunchKernelGGL(hssfsst::fsst_normalize_to_kernel<std::remove_pointer_t<decltype(o)>>, dim3(static_cast<unsigned>(zgrid)), dim3(256), 0, zs,
-                                       cout, o, cstats, fused ? cp.partials : nullptr, nblk, fpp, ncols, p->K, static_cast<int>(cb), slices,
-                                       gate, gate_val);
-                };
-                if (p->out_dtype == HSSFSST_DTYPE_F16) sweep(static_cast<_Float16*>(hcout)); else sweep(static_cast<__bf16*>(hcout));
-            } else
-            hipLaunchKernelGGL(hssfsst::fsst_normalize_kernel, dim3(static_cast<unsigned>(zgrid)), dim3(256), 0, zs,
-                               cout, cstats, fused ? cp.partials : nullptr, nblk, fpp, ncols, p->K, static_cast<int>(cb), slices,
+        if (zgrid > batch * slices) zgrid = batch * slices;
+        // big batches, a block per signal: it reduces the signal's partials itself (no separate statistics
+        // launch, 4-7 us per step); otherwise a tiny kernel does all reductions at once
+        const bool fused = !split_stats && slices == 1 && zgrid == batch && batch >= 512;
+        if (!fused)
+            hipLaunchKernelGGL(hssfsst::fsst_stats_kernel, dim3(static_cast<unsigned>(batch)), dim3(64), 0, st,
+                               cp.partials, stats, nblk, fpp, ncols, p->K, gate, gate_val);
+        if (half)                                        // out of place: float32 scratch -> 2-byte elements (fsst_half.hpp)
+            half_dispatch(p, dout, [&](auto* o) {
+                hipLaunchKernelGGL(hssfsst::fsst_normalize_to_kernel<std::remove_pointer_t<decltype(o)>>, dim3(static_cast<unsigned>(zgrid)), dim3(256), 0, st,
+                                   kout, o, stats, fused ? cp.partials : nullptr, nblk, fpp, ncols, p->K, static_cast<int>(batch), slices,
+                                   gate, gate_val);
+            });
+        else
+            hipLaunchKernelGGL(hssfsst::fsst_normalize_kernel, dim3(static_cast<unsigned>(zgrid)), dim3(256), 0, st,
+                               kout, stats, fused ? cp.partials : nullptr, nblk, fpp, ncols, p->K, static_cast<int>(batch), slices,
                                gate, gate_val);
-            HIP_TRY(hipGetLastError());
-        }
+        HIP_TRY(hipGetLastError());
     }
-    if (piped && p->mode == HSSFSST_MODE_STACK) {          // the caller's stream owns the result again
-        HIP_TRY(hipEventRecord(p->sync_ev[nchunks], p->aux));
-        HIP_TRY(hipStreamWaitEvent(st, p->sync_ev[nchunks], 0));
-    }
-    if (p->timing) {
-        if (p->last_fused && timed_chunks == 1) {
-            p->ev_chunks.push_back(-1);                  // one kernel did everything: its two events are the whole exec
-        } else {
-            hipEvent_t evt = nullptr;
-            if ((rc = next_event(&evt)) != 0) return rc;
-            HIP_TRY(hipEventRecord(evt, st));
-            p->ev_chunks.push_back(timed_chunks);
-        }
-    }
+    if ((rc = timing_end(p, st, p->last_fused != 0)) != 0) return rc;
     if (tiny_out) {
         // The team launch of this exec, if it was asked to (flag_done): its last wave stores the launch's identity to h_fallback[2] behind a
         // system-scope release of every wave's stores -- the features are in pinned host memory by then.  Waiting for that word instead of
@@ -1854,7 +1861,7 @@ static int exec_impl(hssfsst_plan* p, const float* x, int64_t batch, int n, int6
         if (!seen) {
             HIP_TRY(hipStreamSynchronize(st));
             if (fl != 0u) {                               // (the blocks of a given-up launch did not all count themselves in: start the count over)
-                HIP_TRY(hipMemsetAsync(p->d_arrive + 2, 0, sizeof(unsigned), st));
+                HIP_TRY(hipMemsetAsync(p->d_arrive.get() + 2, 0, sizeof(unsigned), st));
                 p->done_total = 0;
             }
         }
@@ -1882,14 +1889,8 @@ static int exec_impl(hssfsst_plan* p, const float* x, int64_t batch, int n, int6
                 return fail(HSSFSST_EHIP, "fused z-score: a wait inside the kernel gave up (code %u); results of that exec are invalid", code);
             }
         } else if (p->d_status && (rc = hssfsst_plan_check(p)) != 0) return rc;
-        if (!pin_d) std::memcpy(out, p->h_opin, no * es);
-    } else if (!out_on_device) {
-        HIP_TRY(hipMemcpyAsync(out, dout, no * es, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        if (p->d_status && (rc = hssfsst_plan_check(p)) != 0) return rc;
-    } else if (!x_on_device) {
-        HIP_TRY(hipStreamSynchronize(st));   // the host source may be reused by the caller
-    }
+        if (!pin_d) std::memcpy(out, p->opin.h, no * es);
+    } else return exec_finish(p, out, dout, no * es, x_on_device, out_on_device, st);
     return 0;
 }
 
@@ -1900,8 +1901,9 @@ int hssfsst_exec_frames(hssfsst_plan* p, const float* x, int64_t batch, int n, i
 }
 
 // The dataset loop's call without the copy into the caller's tensor: the kernels store the features into a pinned, device-mapped buffer
-// of the plan's pool and the caller is LENT that buffer (hssfsst.h).
-constexpr size_t kPinPoolMax = 64;
+// of the plan's pool and the caller is LENT that buffer (hssfsst.h).  hssfsst_pinned_release may run on another host thread at the same
+// time (whichever drops the caller's last reference): the pool is a fixed array, and pin_mu guards the choice of a buffer, its
+// replacement and every `used` flag; the exec itself runs on a reserved buffer with the lock released.
 int hssfsst_exec_pinned(hssfsst_plan* p, const float* x, int n, float** out)
 {
     if (!p || !x || !out || n < 1) return fail(HSSFSST_EINVAL, "exec_pinned: bad argument");
@@ -1909,34 +1911,32 @@ int hssfsst_exec_pinned(hssfsst_plan* p, const float* x, int n, float** out)
     if (p->K == 0) return 1;
     DEVICE_SCOPE(p->device);
     const size_t no = static_cast<size_t>(n) * out_floats_per_sample(p);      // elements (2 bytes each in a half plan); caps count elements
-    hssfsst_plan::PinBuf* b = nullptr;
-    for (auto& c : p->pin_pool) if (!c.used && c.cap >= no) { b = &c; break; }
-    if (!b) {
-        for (auto& c : p->pin_pool) if (!c.used) { b = &c; break; }       // (a free one that is too small is replaced)
+    hssfsst_plan::PoolBuf* b = nullptr;
+    {
+        std::lock_guard<std::mutex> lock(p->pin_mu);
+        for (auto& c : p->pin_pool) if (!c.used && c.buf.cap >= no) { b = &c; break; }
         if (!b) {
-            if (p->pin_pool.size() >= kPinPoolMax) return 1;               // every buffer is still in the caller's hands: take the copying call
-            p->pin_pool.push_back({nullptr, nullptr, 0, false});
-            b = &p->pin_pool.back();
+            for (auto& c : p->pin_pool) if (!c.used) { b = &c; break; }   // (a free one that is too small, or none yet, is replaced)
+            if (!b) return 1;                                              // every buffer is still in the caller's hands: take the copying call
+            if (int rc = b->buf.grow(no, p->out_es)) return rc;
         }
-        if (b->h) { HIP_TRY(hipHostFree(b->h)); b->h = nullptr; b->d = nullptr; b->cap = 0; }
-        size_t c = 1 << 12;
-        while (c < no) c *= 2;
-        void* hp = nullptr; void* dp = nullptr;
-        HIP_TRY(hipHostMalloc(&hp, c * p->out_es, hipHostMallocMapped));
-        HIP_TRY(hipHostGetDevicePointer(&dp, hp, 0));
-        b->h = static_cast<float*>(hp); b->d = static_cast<float*>(dp); b->cap = c;
+        b->used = true;
     }
-    const int rc = exec_impl(p, x, 1, n, static_cast<int64_t>(n), nullptr, 0, 0, n, 0, b->h, 0, nullptr, b->d);
-    if (rc != 0) return rc;
-    b->used = true;
-    *out = b->h;
+    const int rc = exec_impl(p, x, 1, n, static_cast<int64_t>(n), nullptr, 0, 0, n, 0, b->buf.h, 0, nullptr, b->buf.d);
+    if (rc != 0) {
+        std::lock_guard<std::mutex> lock(p->pin_mu);
+        b->used = false;
+        return rc;
+    }
+    *out = b->buf.h;
     return 0;
 }
 
 int hssfsst_pinned_release(hssfsst_plan* p, float* buf)
 {
     if (!p || !buf) return fail(HSSFSST_EINVAL, "pinned_release: bad argument");
-    for (auto& c : p->pin_pool) if (c.h == buf) { c.used = false; return 0; }
+    std::lock_guard<std::mutex> lock(p->pin_mu);
+    for (auto& c : p->pin_pool) if (c.buf.h == buf) { c.used = false; return 0; }
     return fail(HSSFSST_EINVAL, "pinned_release: not a buffer of this plan's pool");
 }
 
@@ -1956,10 +1956,10 @@ int hssfsst_exec_list(hssfsst_plan* p, const float* x, int64_t x_len, const int6
                             static_cast<long long>(starts[b]), static_cast<long long>(x_len - n));
         DEVICE_SCOPE(p->device);
         int rc;
-        if ((rc = grow(reinterpret_cast<void**>(&p->d_starts), &p->starts_cap, static_cast<size_t>(batch), sizeof(long long))) != 0) return rc;
-        HIP_TRY(hipMemcpyAsync(p->d_starts, starts, static_cast<size_t>(batch) * sizeof(long long), hipMemcpyHostToDevice,
+        if ((rc = p->d_starts.grow(static_cast<size_t>(batch))) != 0) return rc;
+        HIP_TRY(hipMemcpyAsync(p->d_starts.get(), starts, static_cast<size_t>(batch) * sizeof(long long), hipMemcpyHostToDevice,
                                static_cast<hipStream_t>(stream)));
-        d_starts = p->d_starts;
+        d_starts = p->d_starts.get();
     }
     return exec_impl(p, x, batch, n, 1, d_starts, static_cast<size_t>(x_len), 0, n, x_on_device, out, out_on_device, stream);
 }
@@ -1987,7 +1987,7 @@ int hssfsst_exec_ragged(hssfsst_plan* p, const float* x, int64_t x_len, const in
             return fail(HSSFSST_EINVAL, "exec_ragged: signal %lld too long (n = %lld)", static_cast<long long>(i), static_cast<long long>(lens[i]));
     if (batch == 0 || p->K == 0) return 0;
     const int ofps = out_floats_per_sample(p);
-    if (p->d_atab == nullptr) {
+    if (p->d_atab.get() == nullptr) {
         // the generic and any-length kernels: one exec per signal (the kernels of hssfsst_exec, on the caller's stream)
         long long off = 0;
         for (int64_t i = 0; i < batch; ++i) {
@@ -2000,12 +2000,8 @@ int hssfsst_exec_ragged(hssfsst_plan* p, const float* x, int64_t x_len, const in
     }
     hipStream_t st = static_cast<hipStream_t>(stream);
     DEVICE_SCOPE(p->device);
-    if (p->h_status && *p->h_status != 0u) {             // (as exec_impl: an earlier exec's wait gave up and nobody was told yet)
-        const unsigned code = *p->h_status;
-        *p->h_status = 0u;
-        return fail(HSSFSST_EHIP, "exec: a wait inside a previous exec's z-score kernel gave up (code %u); the results of that "
-                    "exec are invalid", code);
-    }
+    int rc;
+    if ((rc = take_pending_status(p, "exec")) != 0) return rc;
     // host input: the extent the list covers, uploaded once
     long long xlo = starts[0], xhi = starts[0] + lens[0];
     for (int64_t i = 1; i < batch; ++i) {
@@ -2016,13 +2012,11 @@ int hssfsst_exec_ragged(hssfsst_plan* p, const float* x, int64_t x_len, const in
     long long cols = 0, groups = 0;
     for (int64_t i = 0; i < batch; ++i) { cols += lens[i]; groups += (lens[i] + 15) / 16; }
     const size_t no = static_cast<size_t>(cols) * ofps;                       // output elements
-    const size_t es = p->out_es, no_f = (no * es + sizeof(float) - 1) / sizeof(float);
-    const bool half = es != sizeof(float);
-    int rc;
+    const bool half = p->out_es != sizeof(float);
 
     // the tables (kept while the list's lengths and offsets stay the same)
     const size_t sig_bytes = static_cast<size_t>(batch) * sizeof(hssfsst::RaggedSignal);
-    bool same = p->d_rtab != nullptr && p->rkey.size() == static_cast<size_t>(2 * batch);
+    bool same = p->d_rtab.get() != nullptr && p->rkey.size() == static_cast<size_t>(2 * batch);
     for (int64_t i = 0; same && i < batch; ++i) same = p->rkey[2 * i] == lens[i] && p->rkey[2 * i + 1] == starts[i] - xlo;
     if (!same) {
         if (p->rtab_ev) HIP_TRY(hipEventSynchronize(p->rtab_ev));      // (the previous upload may still read h_rtab)
@@ -2034,16 +2028,10 @@ int hssfsst_exec_ragged(hssfsst_plan* p, const float* x, int64_t x_len, const in
         p->rtab_unit = (sig_bytes + 15) & ~size_t(15);
         p->rtab_chunk = (p->rtab_unit + static_cast<size_t>(batch + 1) * sizeof(int) + 15) & ~size_t(15);
         p->rtab_bytes = p->rtab_chunk + chunks.size() * sizeof(int2);
-        if (p->rtab_bytes > p->h_rtab_cap) {
-            if (p->h_rtab) { HIP_TRY(hipHostFree(p->h_rtab)); p->h_rtab = nullptr; p->h_rtab_cap = 0; }
-            const size_t cap = p->rtab_bytes + p->rtab_bytes / 2;
-            void* hp = nullptr;
-            HIP_TRY(hipHostMalloc(&hp, cap, hipHostMallocDefault));
-            p->h_rtab = static_cast<unsigned char*>(hp); p->h_rtab_cap = cap;
-        }
-        std::memset(p->h_rtab, 0, p->rtab_chunk);
-        auto* rs = reinterpret_cast<hssfsst::RaggedSignal*>(p->h_rtab);
-        int* unit0 = reinterpret_cast<int*>(p->h_rtab + p->rtab_unit);
+        if ((rc = p->h_rtab.grow(p->rtab_bytes, 1)) != 0) return rc;
+        std::memset(p->h_rtab.h, 0, p->rtab_chunk);
+        auto* rs = reinterpret_cast<hssfsst::RaggedSignal*>(p->h_rtab.h);
+        int* unit0 = reinterpret_cast<int*>(p->h_rtab.h + p->rtab_unit);
         long long o = 0, g = 0, u = 0;
         p->rkey.resize(static_cast<size_t>(2 * batch));
         for (int64_t i = 0; i < batch; ++i) {
@@ -2055,47 +2043,29 @@ int hssfsst_exec_ragged(hssfsst_plan* p, const float* x, int64_t x_len, const in
             p->rkey[2 * i] = lens[i]; p->rkey[2 * i + 1] = starts[i] - xlo;
         }
         unit0[batch] = static_cast<int>(u);
-        std::memcpy(p->h_rtab + p->rtab_chunk, chunks.data(), chunks.size() * sizeof(int2));
+        std::memcpy(p->h_rtab.h + p->rtab_chunk, chunks.data(), chunks.size() * sizeof(int2));
         p->rtab_nchunks = static_cast<long long>(chunks.size());
         p->rtab_nunits = u;
-        if ((rc = grow(&p->d_rtab, &p->rtab_cap, p->rtab_bytes, 1)) != 0) { p->rkey.clear(); return rc; }
+        if ((rc = p->d_rtab.grow(p->rtab_bytes)) != 0) { p->rkey.clear(); return rc; }
         if (!p->rtab_ev) HIP_TRY(hipEventCreateWithFlags(&p->rtab_ev, hipEventDisableTiming));
-        HIP_TRY(hipMemcpyAsync(p->d_rtab, p->h_rtab, p->rtab_bytes, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(p->d_rtab.get(), p->h_rtab.h, p->rtab_bytes, hipMemcpyHostToDevice, st));
         HIP_TRY(hipEventRecord(p->rtab_ev, st));
     }
-    const auto* d_rsig = static_cast<const hssfsst::RaggedSignal*>(p->d_rtab);
-    const int* d_unit0 = reinterpret_cast<const int*>(static_cast<const unsigned char*>(p->d_rtab) + p->rtab_unit);
-    const int2* d_chunks = reinterpret_cast<const int2*>(static_cast<const unsigned char*>(p->d_rtab) + p->rtab_chunk);
+    const auto* d_rsig = reinterpret_cast<const hssfsst::RaggedSignal*>(p->d_rtab.get());
+    const int* d_unit0 = reinterpret_cast<const int*>(p->d_rtab.get() + p->rtab_unit);
+    const int2* d_chunks = reinterpret_cast<const int2*>(p->d_rtab.get() + p->rtab_chunk);
 
     const float* dx = x;
     float* dout = out;
-    if (!x_on_device) {
-        const size_t nx = static_cast<size_t>(xhi - xlo);
-        if ((rc = grow(reinterpret_cast<void**>(&p->d_xstage), &p->xstage_cap, nx, sizeof(float))) != 0) return rc;
-        HIP_TRY(hipMemcpyAsync(p->d_xstage, x + xlo, nx * sizeof(float), hipMemcpyHostToDevice, st));
-        dx = p->d_xstage;
-    }
-    if (!out_on_device) {
-        if ((rc = grow(reinterpret_cast<void**>(&p->d_ostage), &p->ostage_cap, no_f, sizeof(float))) != 0) return rc;
-        dout = p->d_ostage;
-    }
-    float* kout = dout;                                  // (half plans: the float32 features go to the plan's scratch, as in exec_impl)
-    if (half) {
-        if ((rc = grow(reinterpret_cast<void**>(&p->d_f32), &p->f32_cap, no, sizeof(float))) != 0) return rc;
-        kout = p->d_f32;
-    }
-    if (p->mode == HSSFSST_MODE_STACK) {
-        if ((rc = grow(reinterpret_cast<void**>(&p->d_partials), &p->partials_cap, static_cast<size_t>(groups) * hssfsst::kPartFloats, sizeof(float))) != 0) return rc;
-        if ((rc = grow(reinterpret_cast<void**>(&p->d_stats), &p->stats_cap, static_cast<size_t>(batch) * 4, sizeof(float))) != 0) return rc;
-    }
+    float* kout = nullptr;
+    if (!x_on_device && (rc = stage_input(p, x + xlo, static_cast<size_t>(xhi - xlo), &dx, st)) != 0) return rc;
+    if ((rc = exec_buffers(p, no, !out_on_device, static_cast<size_t>(groups), batch, &dout, &kout)) != 0) return rc;
 
-    p->timing_closed = false;
-    p->timing = (p->timing_every > 0 && (p->timing_seq++ % static_cast<unsigned>(p->timing_every)) == 0u) ? 1 : 0;
-    hipEvent_t evt = nullptr;
-    if (p->timing) { if ((rc = plan_next_event(p, &evt)) != 0) return rc; HIP_TRY(hipEventRecord(evt, st)); }
+    timing_begin(p);
+    if ((rc = timing_event(p, st)) != 0) return rc;
     hssfsst::Core128Params cp{};
-    cp.x = dx; cp.out = kout; cp.partials = p->d_partials; cp.atab = p->d_atab;
-    cp.wtab = p->d_wtab; cp.twtab = p->d_wtab + 2 * p->nwin; cp.r2scale = p->r2scale;
+    cp.x = dx; cp.out = kout; cp.partials = p->d_partials.get(); cp.atab = p->d_atab.get();
+    cp.wtab = p->d_wtab.get(); cp.twtab = p->d_wtab.get() + 2 * p->nwin; cp.r2scale = p->r2scale;
     cp.n = 1; cp.klo = p->klo; cp.K = p->K; cp.mode = p->mode; cp.nsig = static_cast<int>(std::min<int64_t>(batch, 0x7fffffff));
     cp.col0 = 0; cp.ncols = 1; cp.xstride = 0;
     cp.rsig = d_rsig; cp.rchunk = d_chunks; cp.rnchunks = static_cast<int>(p->rtab_nchunks);
@@ -2110,35 +2080,23 @@ int hssfsst_exec_ragged(hssfsst_plan* p, const float* x, int64_t x_len, const in
     if (rc != 0) return rc;
     p->last_fused = 0;
     p->last_zpath = 0;
-    if (p->timing) { if ((rc = plan_next_event(p, &evt)) != 0) return rc; HIP_TRY(hipEventRecord(evt, st)); }
+    if ((rc = timing_core_done(p, st)) != 0) return rc;
     if (p->mode == HSSFSST_MODE_STACK) {
-        float4* stats = reinterpret_cast<float4*>(p->d_stats);
-        hipLaunchKernelGGL(hssfsst::fsst_ragged_stats_kernel, dim3(static_cast<unsigned>(batch)), dim3(64), 0, st, p->d_partials, d_rsig, stats, p->K);
+        float4* stats = reinterpret_cast<float4*>(p->d_stats.get());
+        hipLaunchKernelGGL(hssfsst::fsst_ragged_stats_kernel, dim3(static_cast<unsigned>(batch)), dim3(64), 0, st, p->d_partials.get(), d_rsig, stats, p->K);
         const long long zgrid = std::min<long long>(p->rtab_nunits, 65536);
-        if (half) {                                      // out of place: float32 scratch -> 2-byte elements (fsst_half.hpp)
-            auto sweep = [&](auto* o) {
+        if (half)                                        // out of place: float32 scratch -> 2-byte elements (fsst_half.hpp)
+            half_dispatch(p, dout, [&](auto* o) {
                 hipLaunchKernelGGL(hssfsst::fsst_ragged_normalize_to_kernel<std::remove_pointer_t<decltype(o)>>, dim3(static_cast<unsigned>(zgrid)), dim3(256), 0, st,
                                    kout, o, d_rsig, d_unit0, stats, static_cast<int>(batch), p->K);
-            };
-            if (p->out_dtype == HSSFSST_DTYPE_F16) sweep(reinterpret_cast<_Float16*>(dout)); else sweep(reinterpret_cast<__bf16*>(dout));
-        } else
-        hipLaunchKernelGGL(hssfsst::fsst_ragged_normalize_kernel, dim3(static_cast<unsigned>(zgrid)), dim3(256), 0, st, dout, d_rsig, d_unit0,
-                           stats, static_cast<int>(batch), p->K);
+            });
+        else
+            hipLaunchKernelGGL(hssfsst::fsst_ragged_normalize_kernel, dim3(static_cast<unsigned>(zgrid)), dim3(256), 0, st, dout, d_rsig, d_unit0,
+                               stats, static_cast<int>(batch), p->K);
         HIP_TRY(hipGetLastError());
     }
-    if (p->timing) {
-        if ((rc = plan_next_event(p, &evt)) != 0) return rc;
-        HIP_TRY(hipEventRecord(evt, st));
-        p->ev_chunks.push_back(1);
-    }
-    if (!out_on_device) {
-        HIP_TRY(hipMemcpyAsync(out, dout, no * es, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        if (p->d_status && (rc = hssfsst_plan_check(p)) != 0) return rc;
-    } else if (!x_on_device) {
-        HIP_TRY(hipStreamSynchronize(st));               // the host source may be reused by the caller
-    }
-    return 0;
+    if ((rc = timing_end(p, st, false)) != 0) return rc;
+    return exec_finish(p, out, dout, no * p->out_es, x_on_device, out_on_device, st);
 }
 
 int hssfsst_moments_merge(hssfsst_plan* p, const float* feats, int64_t batch, int n, double* state, void* stream)
@@ -2161,18 +2119,16 @@ struct hssfsst_resample_plan {
     int device = -1;
     int64_t n = 0, num = 0;
     int M1 = 1, M2 = 1, Mt = 1;
-    double2* d_tab = nullptr;                            // c1[n] | B1[M1] | c2[num] | B2[M2] | tw[max(Mt / 2, 1)]
+    DevBuf<double2> d_tab;                               // c1[n] | B1[M1] | c2[num] | B2[M2] | tw[max(Mt / 2, 1)]
     const double2 *c1 = nullptr, *B1 = nullptr, *c2 = nullptr, *B2 = nullptr, *tw = nullptr;
-    void* d_x = nullptr; size_t x_cap = 0;               // bytes: a host input, staged
-    void* d_y = nullptr; size_t y_cap = 0;               // bytes: a host output, staged
-    void* d_lab = nullptr; size_t lab_cap = 0;           // int64: host labels, staged
-    void* d_starts = nullptr; size_t starts_cap = 0;     // int64: host frame starts, staged
-    void* d_work = nullptr; size_t work_cap = 0;         // double2: the large tier's convolutions [chunk][max(M1, M2)]
+    DevBuf<unsigned char> d_x, d_y;                      // a host input / output, staged
+    DevBuf<long long> d_lab, d_starts;                   // host labels / frame starts, staged
+    DevBuf<double2> d_work;                              // the large tier's convolutions [chunk][max(M1, M2)]
     // ragged plans (hssfsst_resample_plan_create_ragged, n = 0): d_tab holds c2 | B2 only; the twiddle table is its own buffer,
     // grown to the largest M of a call; the list's descriptors are made on the host and uploaded once per call
     bool ragged = false;
-    double2* d_tw = nullptr; int tw_M = 0;               // tw[k] = exp(-2 pi i k / tw_M), k < tw_M / 2
-    void* d_desc = nullptr; size_t desc_cap = 0;         // bytes: RaggedResampleSig[count] | table lengths (int64)
+    DevBuf<double2> d_tw; int tw_M = 0;                  // tw[k] = exp(-2 pi i k / tw_M), k < tw_M / 2
+    DevBuf<unsigned char> d_desc;                        // RaggedResampleSig[count] | table lengths (int64)
     std::vector<unsigned char> h_desc;                   // their host copy (not rewritten before desc_ev: the upload reads it)
     hipEvent_t desc_ev = nullptr;
 };
@@ -2221,6 +2177,85 @@ int rs_launch_check(const char* what)
 
 unsigned rs_grid(long long total) { return static_cast<unsigned>((total + hssfsst::kRsThreads - 1) / hssfsst::kRsThreads); }
 
+int rs_check_dtypes(const char* what, int x_dtype, const void* y, int y_dtype)
+{
+    if ((x_dtype != HSSFSST_DTYPE_F32 && x_dtype != HSSFSST_DTYPE_F64) || (y && y_dtype != HSSFSST_DTYPE_F32 && y_dtype != HSSFSST_DTYPE_F64))
+        return fail(HSSFSST_EINVAL, "%s: unknown dtype (x %d, y %d)", what, x_dtype, y_dtype);
+    return 0;
+}
+
+// A resample exec's host buffers: x_bytes of x staged in front of the launches; y (nout elements of ysz bytes) and labels (nout) given
+// device buffers that rs_finish copies back.  Args: ResampleArgs or RaggedResampleArgs.
+template <class Args>
+int rs_stage(hssfsst_resample_plan* p, Args& a, const void* x, size_t x_bytes, int x_on_device, void* y, size_t ysz, int64_t* labels,
+             size_t nout, int out_on_device, hipStream_t st)
+{
+    int rc;
+    a.x = x;
+    if (!x_on_device) {
+        if ((rc = p->d_x.grow(x_bytes)) != 0) return rc;
+        HIP_TRY(hipMemcpyAsync(p->d_x.get(), x, x_bytes, hipMemcpyHostToDevice, st));
+        a.x = p->d_x.get();
+    }
+    a.y = y;
+    a.labels = reinterpret_cast<long long*>(labels);
+    if (!out_on_device) {
+        if (y) {
+            if ((rc = p->d_y.grow(nout * ysz)) != 0) return rc;
+            a.y = p->d_y.get();
+        }
+        if (labels) {
+            if ((rc = p->d_lab.grow(nout)) != 0) return rc;
+            a.labels = p->d_lab.get();
+        }
+    }
+    return 0;
+}
+
+template <class Args>
+int rs_finish(const Args& a, void* y, size_t ysz, int64_t* labels, size_t nout, int x_on_device, int out_on_device, hipStream_t st)
+{
+    if (!out_on_device) {
+        if (y) HIP_TRY(hipMemcpyAsync(y, a.y, nout * ysz, hipMemcpyDeviceToHost, st));
+        if (labels) HIP_TRY(hipMemcpyAsync(labels, a.labels, nout * sizeof(long long), hipMemcpyDeviceToHost, st));
+    }
+    if (!out_on_device || !x_on_device) HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+// Convolutions of M points, cnt of them at w (stride Mw), against a twiddle table of twM points: global DIF stages down to the block
+// length S, a block kernel (the caller's), global DIT stages back up
+int rs_dif(hipStream_t st, double2* w, long long Mw, long long cnt, int M, const double2* tw, int twM)
+{
+    const int S = M < hssfsst::kRsBlock ? M : hssfsst::kRsBlock;
+    const long long nb = cnt * (M / 2);
+    for (int len = M; len > S; len >>= 1) {
+        hipLaunchKernelGGL(hssfsst::resample_dif_pass_kernel, dim3(rs_grid(nb)), dim3(hssfsst::kRsThreads), 0, st, w, Mw, M, len, tw, twM, nb);
+        if (int r = rs_launch_check("resample_dif_pass_kernel")) return r;
+    }
+    return 0;
+}
+int rs_dit(hipStream_t st, double2* w, long long Mw, long long cnt, int M, const double2* tw, int twM)
+{
+    const int S = M < hssfsst::kRsBlock ? M : hssfsst::kRsBlock;
+    const long long nb = cnt * (M / 2);
+    for (int len = 2 * S; len <= M; len <<= 1) {
+        hipLaunchKernelGGL(hssfsst::resample_dit_pass_kernel, dim3(rs_grid(nb)), dim3(hssfsst::kRsThreads), 0, st, w, Mw, M, len, tw, twM, nb);
+        if (int r = rs_launch_check("resample_dit_pass_kernel")) return r;
+    }
+    return 0;
+}
+// ... with the plain block kernel: one kernel B (bit-reversed spectrum / M) for all of them
+int rs_conv(hipStream_t st, double2* w, long long Mw, long long cnt, int M, const double2* B, const double2* tw, int twM)
+{
+    const int S = M < hssfsst::kRsBlock ? M : hssfsst::kRsBlock;
+    if (int r = rs_dif(st, w, Mw, cnt, M, tw, twM)) return r;
+    hipLaunchKernelGGL(hssfsst::resample_block_kernel, dim3(static_cast<unsigned>(cnt * (M / S))), dim3(hssfsst::kRsThreads), 0, st,
+                       w, Mw, M, S, B, tw, twM);
+    if (int r = rs_launch_check("resample_block_kernel")) return r;
+    return rs_dit(st, w, Mw, cnt, M, tw, twM);
+}
+
 }  // namespace
 
 extern "C" {
@@ -2235,18 +2270,11 @@ int hssfsst_resample_plan_create(hssfsst_resample_plan** out, int device, int64_
     if (n > kRsMaxLen || num > kRsMaxLen)
         return fail(HSSFSST_EUNSUPPORTED, "resample_plan_create: lengths above %lld samples are not supported (n=%lld num=%lld)",
                     static_cast<long long>(kRsMaxLen), static_cast<long long>(n), static_cast<long long>(num));
-    int ndev = 0;
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev <= 0) {
-        (void)hipGetLastError();
-        return fail(HSSFSST_ENODEVICE, "resample_plan_create: no HIP device (%s); this library has no CPU path",
-                    e == hipSuccess ? "device count 0" : hipGetErrorString(e));
-    }
-    if (device >= ndev) return fail(HSSFSST_EINVAL, "resample_plan_create: device %d out of range [0,%d)", device, ndev);
+    if (int rc = check_device("resample_plan_create", device)) return rc;
     DEVICE_SCOPE(device);
     using hssfsst::resample_detail::cd;
     static_assert(sizeof(cd) == sizeof(double2), "std::complex<double> and double2 share a layout");
-    hssfsst_resample_plan* p = new (std::nothrow) hssfsst_resample_plan();
+    std::unique_ptr<hssfsst_resample_plan> p(new (std::nothrow) hssfsst_resample_plan());
     if (!p) return fail(HSSFSST_ENOMEM, "resample_plan_create: host allocation failed");
     p->device = device; p->n = n; p->num = num;
     p->M1 = pow2_at_least(2 * n - 1);
@@ -2263,17 +2291,13 @@ int hssfsst_resample_plan_create(hssfsst_resample_plan** out, int device, int64_
             const double ang = -2.0 * M_PI * static_cast<double>(k) / static_cast<double>(p->Mt);
             tab[o_tw + k] = cd(std::cos(ang), std::sin(ang));
         }
-        e = hipMalloc(reinterpret_cast<void**>(&p->d_tab), total * sizeof(double2));
-        if (e != hipSuccess) { p->d_tab = nullptr; delete p; return fail(HSSFSST_ENOMEM, "resample_plan_create: hipMalloc: %s", hipGetErrorString(e)); }
-        e = hipMemcpy(p->d_tab, tab.data(), total * sizeof(double2), hipMemcpyHostToDevice);
-        if (e != hipSuccess) { (void)hipFree(p->d_tab); delete p; return fail(HSSFSST_EHIP, "resample_plan_create: table upload: %s", hipGetErrorString(e)); }
+        if (int rc = p->d_tab.upload(reinterpret_cast<const double2*>(tab.data()), total)) return rc;
     } catch (const std::bad_alloc&) {
-        if (p->d_tab) (void)hipFree(p->d_tab);
-        delete p;
         return fail(HSSFSST_ENOMEM, "resample_plan_create: out of host memory");
     }
-    p->c1 = p->d_tab; p->B1 = p->d_tab + o_B1; p->c2 = p->d_tab + o_c2; p->B2 = p->d_tab + o_B2; p->tw = p->d_tab + o_tw;
-    *out = p;
+    const double2* t = p->d_tab.get();
+    p->c1 = t; p->B1 = t + o_B1; p->c2 = t + o_c2; p->B2 = t + o_B2; p->tw = t + o_tw;
+    *out = p.release();
     return 0;
 }
 
@@ -2281,10 +2305,8 @@ int hssfsst_resample_plan_destroy(hssfsst_resample_plan* p)
 {
     if (!p) return 0;
     DeviceGuard device_guard_(p->device);
-    for (void* d : {static_cast<void*>(p->d_tab), p->d_x, p->d_y, p->d_lab, p->d_starts, p->d_work, static_cast<void*>(p->d_tw), p->d_desc})
-        if (d) (void)hipFree(d);
     if (p->desc_ev) (void)hipEventDestroy(p->desc_ev);
-    delete p;
+    delete p;                                            // (the buffers free themselves)
     return 0;
 }
 
@@ -2307,8 +2329,7 @@ int hssfsst_resample_exec(hssfsst_resample_plan* p, const void* x, int x_dtype, 
     if (!p || !x || (!y && !labels) || batch < 0 || x_len < 1)
         return fail(HSSFSST_EINVAL, "resample_exec: bad argument (batch=%lld x_len=%lld)", static_cast<long long>(batch),
                     static_cast<long long>(x_len));
-    if ((x_dtype != HSSFSST_DTYPE_F32 && x_dtype != HSSFSST_DTYPE_F64) || (y && y_dtype != HSSFSST_DTYPE_F32 && y_dtype != HSSFSST_DTYPE_F64))
-        return fail(HSSFSST_EINVAL, "resample_exec: unknown dtype (x %d, y %d)", x_dtype, y_dtype);
+    if (int rc = rs_check_dtypes("resample_exec", x_dtype, y, y_dtype)) return rc;
     if (batch > 0x7fffffffLL) return fail(HSSFSST_EINVAL, "resample_exec: batch %lld too large", static_cast<long long>(batch));
     if (p->ragged) return fail(HSSFSST_EINVAL, "resample_exec: a ragged plan (hssfsst_resample_plan_create_ragged) takes hssfsst_resample_exec_ragged");
     const int64_t n = p->n, num = p->num;
@@ -2336,29 +2357,12 @@ int hssfsst_resample_exec(hssfsst_resample_plan* p, const void* x, int x_dtype, 
     const size_t nout = static_cast<size_t>(batch) * static_cast<size_t>(num);
     int rc;
     hssfsst::ResampleArgs a{};
-    a.x = x;
-    if (!x_on_device) {
-        if ((rc = grow(&p->d_x, &p->x_cap, static_cast<size_t>(x_len) * xsz, 1)) != 0) return rc;
-        HIP_TRY(hipMemcpyAsync(p->d_x, x, static_cast<size_t>(x_len) * xsz, hipMemcpyHostToDevice, st));
-        a.x = p->d_x;
-    }
+    if ((rc = rs_stage(p, a, x, static_cast<size_t>(x_len) * xsz, x_on_device, y, ysz, labels, nout, out_on_device, st)) != 0) return rc;
     a.starts = reinterpret_cast<const long long*>(starts);
     if (starts && !starts_on_device) {
-        if ((rc = grow(&p->d_starts, &p->starts_cap, static_cast<size_t>(batch), sizeof(long long))) != 0) return rc;
-        HIP_TRY(hipMemcpyAsync(p->d_starts, starts, static_cast<size_t>(batch) * sizeof(long long), hipMemcpyHostToDevice, st));
-        a.starts = static_cast<const long long*>(p->d_starts);
-    }
-    a.y = y;
-    a.labels = reinterpret_cast<long long*>(labels);
-    if (!out_on_device) {
-        if (y) {
-            if ((rc = grow(&p->d_y, &p->y_cap, nout * ysz, 1)) != 0) return rc;
-            a.y = p->d_y;
-        }
-        if (labels) {
-            if ((rc = grow(&p->d_lab, &p->lab_cap, nout, sizeof(long long))) != 0) return rc;
-            a.labels = static_cast<long long*>(p->d_lab);
-        }
+        if ((rc = p->d_starts.grow(static_cast<size_t>(batch))) != 0) return rc;
+        HIP_TRY(hipMemcpyAsync(p->d_starts.get(), starts, static_cast<size_t>(batch) * sizeof(long long), hipMemcpyHostToDevice, st));
+        a.starts = p->d_starts.get();
     }
     a.x_stride = x_stride;
     a.n = n; a.num = num;
@@ -2381,45 +2385,23 @@ int hssfsst_resample_exec(hssfsst_resample_plan* p, const void* x, int x_dtype, 
         const long long Mw = p->Mt;
         const long long per = static_cast<long long>(kRsWorkBytes / (static_cast<size_t>(Mw) * sizeof(double2)));
         const long long chunk = per < 1 ? 1 : (per < batch ? per : batch);
-        if ((rc = grow(&p->d_work, &p->work_cap, static_cast<size_t>(chunk) * static_cast<size_t>(Mw), sizeof(double2))) != 0) return rc;
-        double2* work = static_cast<double2*>(p->d_work);
-        // one convolution of M points: global DIF stages down to the block length, the block kernel, global DIT stages back up
-        auto conv = [&](long long cb, int M, const double2* B) -> int {
-            const int S = M < hssfsst::kRsBlock ? M : hssfsst::kRsBlock;
-            const long long nb = cb * (M / 2);
-            for (int len = M; len > S; len >>= 1) {
-                hipLaunchKernelGGL(hssfsst::resample_dif_pass_kernel, dim3(rs_grid(nb)), dim3(hssfsst::kRsThreads), 0, st, work, Mw, M, len, p->tw, p->Mt, nb);
-                if (int r = rs_launch_check("resample_dif_pass_kernel")) return r;
-            }
-            hipLaunchKernelGGL(hssfsst::resample_block_kernel, dim3(static_cast<unsigned>(cb * (M / S))), dim3(hssfsst::kRsThreads), 0, st,
-                               work, Mw, M, S, B, p->tw, p->Mt);
-            if (int r = rs_launch_check("resample_block_kernel")) return r;
-            for (int len = 2 * S; len <= M; len <<= 1) {
-                hipLaunchKernelGGL(hssfsst::resample_dit_pass_kernel, dim3(rs_grid(nb)), dim3(hssfsst::kRsThreads), 0, st, work, Mw, M, len, p->tw, p->Mt, nb);
-                if (int r = rs_launch_check("resample_dit_pass_kernel")) return r;
-            }
-            return 0;
-        };
+        if ((rc = p->d_work.grow(static_cast<size_t>(chunk) * static_cast<size_t>(Mw))) != 0) return rc;
+        double2* work = p->d_work.get();
         for (long long b0 = 0; b0 < batch; b0 += chunk) {
             const long long cb = batch - b0 < chunk ? batch - b0 : chunk;
             a.b0 = b0;
             const long long t1 = cb * p->M1, t2 = cb * p->M2, t3 = cb * num;
             hipLaunchKernelGGL(hssfsst::resample_load_kernel, dim3(rs_grid(t1)), dim3(hssfsst::kRsThreads), 0, st, a, work, Mw, t1);
             if ((rc = rs_launch_check("resample_load_kernel")) != 0) return rc;
-            if ((rc = conv(cb, p->M1, p->B1)) != 0) return rc;
+            if ((rc = rs_conv(st, work, Mw, cb, p->M1, p->B1, p->tw, p->Mt)) != 0) return rc;
             hipLaunchKernelGGL(hssfsst::resample_mid_kernel, dim3(rs_grid(t2)), dim3(hssfsst::kRsThreads), 0, st, a, work, Mw, t2);
             if ((rc = rs_launch_check("resample_mid_kernel")) != 0) return rc;
-            if ((rc = conv(cb, p->M2, p->B2)) != 0) return rc;
+            if ((rc = rs_conv(st, work, Mw, cb, p->M2, p->B2, p->tw, p->Mt)) != 0) return rc;
             hipLaunchKernelGGL(hssfsst::resample_store_kernel, dim3(rs_grid(t3)), dim3(hssfsst::kRsThreads), 0, st, a, work, Mw, t3);
             if ((rc = rs_launch_check("resample_store_kernel")) != 0) return rc;
         }
     }
-    if (!out_on_device) {
-        if (y) HIP_TRY(hipMemcpyAsync(y, a.y, nout * ysz, hipMemcpyDeviceToHost, st));
-        if (labels) HIP_TRY(hipMemcpyAsync(labels, a.labels, nout * sizeof(long long), hipMemcpyDeviceToHost, st));
-    }
-    if (!out_on_device || !x_on_device) HIP_TRY(hipStreamSynchronize(st));
-    return 0;
+    return rs_finish(a, y, ysz, labels, nout, x_on_device, out_on_device, st);
 }
 
 int hssfsst_resample_plan_create_ragged(hssfsst_resample_plan** out, int device, int64_t num)
@@ -2431,17 +2413,10 @@ int hssfsst_resample_plan_create_ragged(hssfsst_resample_plan** out, int device,
     if (num > kRsMaxLen)
         return fail(HSSFSST_EUNSUPPORTED, "resample_plan_create_ragged: lengths above %lld samples are not supported (num=%lld)",
                     static_cast<long long>(kRsMaxLen), static_cast<long long>(num));
-    int ndev = 0;
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev <= 0) {
-        (void)hipGetLastError();
-        return fail(HSSFSST_ENODEVICE, "resample_plan_create_ragged: no HIP device (%s); this library has no CPU path",
-                    e == hipSuccess ? "device count 0" : hipGetErrorString(e));
-    }
-    if (device >= ndev) return fail(HSSFSST_EINVAL, "resample_plan_create_ragged: device %d out of range [0,%d)", device, ndev);
+    if (int rc = check_device("resample_plan_create_ragged", device)) return rc;
     DEVICE_SCOPE(device);
     using hssfsst::resample_detail::cd;
-    hssfsst_resample_plan* p = new (std::nothrow) hssfsst_resample_plan();
+    std::unique_ptr<hssfsst_resample_plan> p(new (std::nothrow) hssfsst_resample_plan());
     if (!p) return fail(HSSFSST_ENOMEM, "resample_plan_create_ragged: host allocation failed");
     p->ragged = true;
     p->device = device; p->n = 0; p->num = num;
@@ -2452,17 +2427,12 @@ int hssfsst_resample_plan_create_ragged(hssfsst_resample_plan** out, int device,
     try {
         std::vector<cd> tab(total);
         bluestein_tables(num, p->M2, -1.0, tab.data(), tab.data() + num);
-        e = hipMalloc(reinterpret_cast<void**>(&p->d_tab), total * sizeof(double2));
-        if (e != hipSuccess) { p->d_tab = nullptr; delete p; return fail(HSSFSST_ENOMEM, "resample_plan_create_ragged: hipMalloc: %s", hipGetErrorString(e)); }
-        e = hipMemcpy(p->d_tab, tab.data(), total * sizeof(double2), hipMemcpyHostToDevice);
-        if (e != hipSuccess) { (void)hipFree(p->d_tab); delete p; return fail(HSSFSST_EHIP, "resample_plan_create_ragged: table upload: %s", hipGetErrorString(e)); }
+        if (int rc = p->d_tab.upload(reinterpret_cast<const double2*>(tab.data()), total)) return rc;
     } catch (const std::bad_alloc&) {
-        if (p->d_tab) (void)hipFree(p->d_tab);
-        delete p;
         return fail(HSSFSST_ENOMEM, "resample_plan_create_ragged: out of host memory");
     }
-    p->c2 = p->d_tab; p->B2 = p->d_tab + num;
-    *out = p;
+    p->c2 = p->d_tab.get(); p->B2 = p->d_tab.get() + num;
+    *out = p.release();
     return 0;
 }
 
@@ -2477,23 +2447,18 @@ int rs_ragged_twiddles(hssfsst_resample_plan* p, int Mt)
     using hssfsst::resample_detail::cd;
     if (Mt <= p->tw_M) return 0;
     const size_t ntw = static_cast<size_t>(Mt > 1 ? Mt / 2 : 1);
-    double2* d = nullptr;
     try {
         std::vector<cd> tw(ntw);
         for (size_t k = 0; k < ntw; ++k) {
             const double ang = -2.0 * M_PI * static_cast<double>(k) / static_cast<double>(Mt);
             tw[k] = cd(std::cos(ang), std::sin(ang));
         }
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&d), ntw * sizeof(double2));
-        if (e != hipSuccess) return fail(HSSFSST_ENOMEM, "resample_exec_ragged: hipMalloc of the twiddle table: %s", hipGetErrorString(e));
-        e = hipMemcpy(d, tw.data(), ntw * sizeof(double2), hipMemcpyHostToDevice);
-        if (e != hipSuccess) { (void)hipFree(d); return fail(HSSFSST_EHIP, "resample_exec_ragged: twiddle upload: %s", hipGetErrorString(e)); }
+        p->tw_M = 0;                                     // (upload's hipFree of the old table waits for the device: no earlier launch still reads it)
+        if (int rc = p->d_tw.upload(reinterpret_cast<const double2*>(tw.data()), ntw)) return rc;
     } catch (const std::bad_alloc&) {
-        if (d) (void)hipFree(d);
         return fail(HSSFSST_ENOMEM, "resample_exec_ragged: out of host memory");
     }
-    if (p->d_tw) HIP_TRY(hipFree(p->d_tw));              // (hipFree waits for the device: no earlier launch still reads it)
-    p->d_tw = d; p->tw_M = Mt;
+    p->tw_M = Mt;
     return 0;
 }
 
@@ -2510,8 +2475,7 @@ int hssfsst_resample_exec_ragged(hssfsst_resample_plan* p, const void* x, int x_
         return fail(HSSFSST_EINVAL, "resample_exec_ragged: bad argument (count=%lld x_len=%lld)", static_cast<long long>(count),
                     static_cast<long long>(x_len));
     if (!p->ragged) return fail(HSSFSST_EINVAL, "resample_exec_ragged: a dense plan (hssfsst_resample_plan_create) takes hssfsst_resample_exec");
-    if ((x_dtype != HSSFSST_DTYPE_F32 && x_dtype != HSSFSST_DTYPE_F64) || (y && y_dtype != HSSFSST_DTYPE_F32 && y_dtype != HSSFSST_DTYPE_F64))
-        return fail(HSSFSST_EINVAL, "resample_exec_ragged: unknown dtype (x %d, y %d)", x_dtype, y_dtype);
+    if (int rc = rs_check_dtypes("resample_exec_ragged", x_dtype, y, y_dtype)) return rc;
     if (count > 0x7fffffffLL) return fail(HSSFSST_EINVAL, "resample_exec_ragged: count %lld too large", static_cast<long long>(count));
     bool too_long = false;
     long long xlo = x_len, xhi = 0;
@@ -2591,65 +2555,28 @@ int hssfsst_resample_exec_ragged(hssfsst_resample_plan* p, const void* x, int x_
     int Mt = M2;
     for (int m : M1s) Mt = std::max(Mt, m);
     if ((rc = rs_ragged_twiddles(p, Mt)) != 0) return rc;
-    if ((rc = grow(&p->d_desc, &p->desc_cap, p->h_desc.size(), 1)) != 0) return rc;
-    HIP_TRY(hipMemcpyAsync(p->d_desc, p->h_desc.data(), p->h_desc.size(), hipMemcpyHostToDevice, st));
+    if ((rc = p->d_desc.grow(p->h_desc.size())) != 0) return rc;
+    HIP_TRY(hipMemcpyAsync(p->d_desc.get(), p->h_desc.data(), p->h_desc.size(), hipMemcpyHostToDevice, st));
     if (!p->desc_ev) HIP_TRY(hipEventCreateWithFlags(&p->desc_ev, hipEventDisableTiming));
     HIP_TRY(hipEventRecord(p->desc_ev, st));
-    const auto* dsig = static_cast<const RaggedResampleSig*>(p->d_desc);
-    const auto* dtn = reinterpret_cast<const long long*>(static_cast<const unsigned char*>(p->d_desc) + static_cast<size_t>(count) * sizeof(RaggedResampleSig));
+    const auto* dsig = reinterpret_cast<const RaggedResampleSig*>(p->d_desc.get());
+    const auto* dtn = reinterpret_cast<const long long*>(p->d_desc.get() + static_cast<size_t>(count) * sizeof(RaggedResampleSig));
     long long max_elems = 0;
     for (const Chunk& ch : chunks) max_elems = std::max(max_elems, ch.elems);
-    if ((rc = grow(&p->d_work, &p->work_cap, static_cast<size_t>(max_elems), sizeof(double2))) != 0) return rc;
+    if ((rc = p->d_work.grow(static_cast<size_t>(max_elems))) != 0) return rc;
 
     // ---- staging of host buffers, as hssfsst_resample_exec
     const size_t xsz = x_dtype == HSSFSST_DTYPE_F64 ? sizeof(double) : sizeof(float);
     const size_t ysz = y_dtype == HSSFSST_DTYPE_F64 ? sizeof(double) : sizeof(float);
     const size_t nout = static_cast<size_t>(count) * static_cast<size_t>(num);
     hssfsst::RaggedResampleArgs a{};
-    a.x = x;
-    if (!x_on_device) {
-        const size_t bytes = static_cast<size_t>(xhi - xlo) * xsz;
-        if ((rc = grow(&p->d_x, &p->x_cap, bytes, 1)) != 0) return rc;
-        HIP_TRY(hipMemcpyAsync(p->d_x, static_cast<const unsigned char*>(x) + static_cast<size_t>(xlo) * xsz, bytes, hipMemcpyHostToDevice, st));
-        a.x = p->d_x;
-    }
-    a.y = y;
-    a.labels = reinterpret_cast<long long*>(labels);
-    if (!out_on_device) {
-        if (y) {
-            if ((rc = grow(&p->d_y, &p->y_cap, nout * ysz, 1)) != 0) return rc;
-            a.y = p->d_y;
-        }
-        if (labels) {
-            if ((rc = grow(&p->d_lab, &p->lab_cap, nout, sizeof(long long))) != 0) return rc;
-            a.labels = static_cast<long long*>(p->d_lab);
-        }
-    }
+    if ((rc = rs_stage(p, a, static_cast<const unsigned char*>(x) + (x_on_device ? 0 : static_cast<size_t>(xlo) * xsz), static_cast<size_t>(xhi - xlo) * xsz,
+                       x_on_device, y, ysz, labels, nout, out_on_device, st)) != 0) return rc;
     a.num = num; a.M2 = M2; a.c2 = p->c2;
     a.x_f64 = x_dtype == HSSFSST_DTYPE_F64; a.y_f64 = y_dtype == HSSFSST_DTYPE_F64; a.num_even = num % 2 == 0;
-    const double2* tw = p->d_tw;
+    const double2* tw = p->d_tw.get();
     const int twM = p->tw_M;
-    double2* work = static_cast<double2*>(p->d_work);
-
-    // global DIF stages of convolutions of M points down to the block length (cnt of them at w, stride Mw)
-    auto dif = [&](double2* w, long long Mw, long long cnt, int M) -> int {
-        const int S = M < hssfsst::kRsBlock ? M : hssfsst::kRsBlock;
-        const long long nb = cnt * (M / 2);
-        for (int len = M; len > S; len >>= 1) {
-            hipLaunchKernelGGL(hssfsst::resample_dif_pass_kernel, dim3(rs_grid(nb)), dim3(hssfsst::kRsThreads), 0, st, w, Mw, M, len, tw, twM, nb);
-            if (int r = rs_launch_check("resample_dif_pass_kernel")) return r;
-        }
-        return 0;
-    };
-    auto dit = [&](double2* w, long long Mw, long long cnt, int M) -> int {
-        const int S = M < hssfsst::kRsBlock ? M : hssfsst::kRsBlock;
-        const long long nb = cnt * (M / 2);
-        for (int len = 2 * S; len <= M; len <<= 1) {
-            hipLaunchKernelGGL(hssfsst::resample_dit_pass_kernel, dim3(rs_grid(nb)), dim3(hssfsst::kRsThreads), 0, st, w, Mw, M, len, tw, twM, nb);
-            if (int r = rs_launch_check("resample_dit_pass_kernel")) return r;
-        }
-        return 0;
-    };
+    double2* work = p->d_work.get();
     for (const Chunk& ch : chunks) {
         const long long Mw = ch.Mw, cnt = ch.cnt;
         const RaggedResampleSig* csig = dsig + ch.d0;
@@ -2663,7 +2590,7 @@ int hssfsst_resample_exec_ragged(hssfsst_resample_plan* p, const void* x, int x_
             const long long tot = (v - u) * M;
             hipLaunchKernelGGL(hssfsst::resample_ragged_table_kernel, dim3(rs_grid(tot)), dim3(hssfsst::kRsThreads), 0, st, t0, dtn + u, M, tot);
             if ((rc = rs_launch_check("resample_ragged_table_kernel")) != 0) return rc;
-            if ((rc = dif(t0, M, v - u, M)) != 0) return rc;
+            if ((rc = rs_dif(st, t0, M, v - u, M, tw, twM)) != 0) return rc;
             hipLaunchKernelGGL(hssfsst::resample_ragged_table_block_kernel, dim3(static_cast<unsigned>((v - u) * (M / S))), dim3(hssfsst::kRsThreads),
                                0, st, t0, M, S, tw, twM);
             if ((rc = rs_launch_check("resample_ragged_table_block_kernel")) != 0) return rc;
@@ -2678,32 +2605,22 @@ int hssfsst_resample_exec_ragged(hssfsst_resample_plan* p, const void* x, int x_
             const int M = M1s[static_cast<size_t>(ch.d0 + e0)], S = M < hssfsst::kRsBlock ? M : hssfsst::kRsBlock;
             while (e1 < cnt && M1s[static_cast<size_t>(ch.d0 + e1)] == M) ++e1;
             double2* w = work + e0 * Mw;
-            if ((rc = dif(w, Mw, e1 - e0, M)) != 0) return rc;
+            if ((rc = rs_dif(st, w, Mw, e1 - e0, M, tw, twM)) != 0) return rc;
             hipLaunchKernelGGL(hssfsst::resample_ragged_block_kernel, dim3(static_cast<unsigned>((e1 - e0) * (M / S))), dim3(hssfsst::kRsThreads),
                                0, st, w, Mw, M, S, csig + e0, tabs, tw, twM);
             if ((rc = rs_launch_check("resample_ragged_block_kernel")) != 0) return rc;
-            if ((rc = dit(w, Mw, e1 - e0, M)) != 0) return rc;
+            if ((rc = rs_dit(st, w, Mw, e1 - e0, M, tw, twM)) != 0) return rc;
             e0 = e1;
         }
         // the inverse side, once over the chunk
         const long long t2 = cnt * M2, t3 = cnt * num;
         hipLaunchKernelGGL(hssfsst::resample_ragged_mid_kernel, dim3(rs_grid(t2)), dim3(hssfsst::kRsThreads), 0, st, a, csig, work, Mw, t2);
         if ((rc = rs_launch_check("resample_ragged_mid_kernel")) != 0) return rc;
-        if ((rc = dif(work, Mw, cnt, M2)) != 0) return rc;
-        const int S2 = M2 < hssfsst::kRsBlock ? M2 : hssfsst::kRsBlock;
-        hipLaunchKernelGGL(hssfsst::resample_block_kernel, dim3(static_cast<unsigned>(cnt * (M2 / S2))), dim3(hssfsst::kRsThreads), 0, st,
-                           work, Mw, M2, S2, p->B2, tw, twM);
-        if ((rc = rs_launch_check("resample_block_kernel")) != 0) return rc;
-        if ((rc = dit(work, Mw, cnt, M2)) != 0) return rc;
+        if ((rc = rs_conv(st, work, Mw, cnt, M2, p->B2, tw, twM)) != 0) return rc;
         hipLaunchKernelGGL(hssfsst::resample_ragged_store_kernel, dim3(rs_grid(t3)), dim3(hssfsst::kRsThreads), 0, st, a, csig, work, Mw, t3);
         if ((rc = rs_launch_check("resample_ragged_store_kernel")) != 0) return rc;
     }
-    if (!out_on_device) {
-        if (y) HIP_TRY(hipMemcpyAsync(y, a.y, nout * ysz, hipMemcpyDeviceToHost, st));
-        if (labels) HIP_TRY(hipMemcpyAsync(labels, a.labels, nout * sizeof(long long), hipMemcpyDeviceToHost, st));
-    }
-    if (!out_on_device || !x_on_device) HIP_TRY(hipStreamSynchronize(st));
-    return 0;
+    return rs_finish(a, y, ysz, labels, nout, x_on_device, out_on_device, st);
 }
 
 int hssfsst_resample(const double* x, int64_t n, int64_t num, double* y)
@@ -2794,9 +2711,9 @@ int hssfsst_normalize_running(hssfsst_plan* p, float* feats, int64_t batch, int 
     if (batch > 0x7fffffffLL || static_cast<long long>(n) * 2 * p->K >= 0x7fffffffLL) return fail(HSSFSST_EINVAL, "normalize_running: too large");
     DEVICE_SCOPE(p->device);
     int rc;
-    if ((rc = grow(reinterpret_cast<void**>(&p->d_stats), &p->stats_cap, static_cast<size_t>(batch) * 4, sizeof(float))) != 0) return rc;
+    if ((rc = p->d_stats.grow(static_cast<size_t>(batch) * 4)) != 0) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    float4* stats = reinterpret_cast<float4*>(p->d_stats);
+    float4* stats = reinterpret_cast<float4*>(p->d_stats.get());
     hipLaunchKernelGGL(hssfsst::fsst_stats_from_state_kernel, dim3(static_cast<unsigned>((batch + 63) / 64)), dim3(64), 0, st,
                        state, stats, static_cast<int>(batch));
     const int64_t zgrid = batch < 4096 ? batch : 4096;
@@ -2820,22 +2737,20 @@ int hssfsst_stream_step(hssfsst_plan* p, float* tape, int64_t tape_len, int64_t 
     if (hist + chunk > 0x7fffffffLL || static_cast<long long>(chunk) * 2 * p->K >= 0x7fffffffLL)
         return fail(HSSFSST_EINVAL, "stream_step: chunk too large");
     if (p->K == 0) return 0;
-    if (p->h_status && *p->h_status != 0u) {             // an earlier step's wait between blocks gave up (see hssfsst_plan_check)
-        const unsigned code = *p->h_status;
-        *p->h_status = 0u;
+    if (int rc = take_pending_status(p, "stream_step")) {     // an earlier step's wait between blocks gave up (see hssfsst_plan_check)
         // (a step that gave up may have left its channels' arrival counters short of a full round: later steps would never
         //  normalise -- start them from zero again)
-        if (p->d_stream_arrive && p->stream_arrive_cap > 0) {
+        if (p->d_stream_arrive.cap > 0) {
             DEVICE_SCOPE(p->device);
-            (void)hipMemsetAsync(p->d_stream_arrive, 0, static_cast<size_t>(p->stream_arrive_cap) * sizeof(unsigned), static_cast<hipStream_t>(stream));
+            (void)hipMemsetAsync(p->d_stream_arrive.get(), 0, p->d_stream_arrive.cap * sizeof(unsigned), static_cast<hipStream_t>(stream));
         }
-        return fail(HSSFSST_EHIP, "stream_step: an earlier step gave up waiting inside its launch (code %u); its output is invalid", code);
+        return rc;
     }
     hipStream_t st = static_cast<hipStream_t>(stream);
     DEVICE_SCOPE(p->device);
     // one launch for the whole step where the transform is the wide-store MFMA kernel in one-group chunks (nwin 256 / 512, an even
     // band of <= 24 rows: BASELINE config 5); host samples are copied into the tape first and the kernel reads them there
-    const bool one_launch = p->d_atab != nullptr && p->rq == 16 && (p->K & 1) == 0 && p->K <= 24 && !debug_switches().no_stream_fuse &&
+    const bool one_launch = p->d_atab.get() != nullptr && p->rq == 16 && (p->K & 1) == 0 && p->K <= 24 && !debug_switches().no_stream_fuse &&
                             (reinterpret_cast<uintptr_t>(out) & 15) == 0 &&
                             static_cast<long long>(channels) * ((chunk + 15) / 16) < 0x7fffffffLL;
     int launched = 0;

@@ -339,16 +339,15 @@ np.savez(sys.argv[1], *outs)
 
 
 def test_kernel_variants_agree(tmp_path):
-    """The library's alternative execution paths must reproduce the default one: the 2-stream chunk
-    pipeline bit-exactly; the generic VALU kernel (forced for nwin = 128 and 256) to the parity tolerance."""
+    """The library's alternative execution paths must reproduce the default one: the generic VALU kernel
+    (forced for nwin = 128 and 256) to the parity tolerance."""
     paths = {}
-    for tag, env in (("default", {}), ("piped", {"HSSFSST_CHUNKS": "3"}), ("generic", {"HSSFSST_FORCE_GENERIC": "1"})):
+    for tag, env in (("default", {}), ("generic", {"HSSFSST_FORCE_GENERIC": "1"})):
         out = str(tmp_path / f"{tag}.npz")
         _run_child(env, _CHILD.replace("sys.argv[1]", repr(out)))
         paths[tag] = np.load(out)
     ref = paths["default"]
     for k in ref.files:
-        assert np.array_equal(ref[k], paths["piped"][k], equal_nan=True), ("piped", k)
         g = paths["generic"][k]
         scale = np.abs(ref[k]).max()
         colerr = np.abs(g - ref[k]).reshape(ref[k].shape[0], -1)
@@ -887,6 +886,44 @@ def test_pinned_result_buffers_are_lent_and_returned():
     assert r1.dtype == torch.complex64 and r1.shape == (22, 2000) and torch.equal(r1, r2)
     a1 = FSST(1000, KAISER, truncate_freq=BAND, abs=True)(X[1])
     assert a1.shape == (2000, 22) and torch.equal(a1, FSST(1000, KAISER, truncate_freq=BAND, abs=True).batch(X[1:2].cuda())[0].cpu())
+
+
+def test_pinned_release_from_another_thread():
+    """A lent result may die on another host thread (a consumer, a queue, the garbage collector): its hssfsst_pinned_release then runs
+    while the producer thread is inside hssfsst_exec_pinned of the same plan.  Producer: one frame per call, each result handed over a
+    queue; consumer: compares it with the batched features bit for bit and drops it -- the only library call it makes is that release."""
+    import queue
+    import threading
+    tf = FSST(1000, KAISER, truncate_freq=BAND, stack=True)
+    X = torch.from_numpy(synth.pcg_windows(200, 2000, seed=91))
+    want = tf.batch(X.cuda()).cpu()                                  # (before any thread starts: one plan, one exec thread)
+    frames = [X[i].reshape(2000, 1).contiguous() for i in range(200)]
+    q = queue.Queue(maxsize=8)
+    bad, errors = [], []
+
+    def produce():
+        try:
+            for i in range(200):
+                q.put((i, tf(frames[i])))
+        except BaseException as e:                                   # (reported by the test thread)
+            errors.append(e)
+        finally:
+            q.put(None)
+
+    def consume():
+        while (item := q.get()) is not None:
+            i, y = item
+            if not torch.equal(y, want[i]):
+                bad.append(i)
+            del item, y                                              # the last reference: the buffer goes back to the pool here
+
+    threads = [threading.Thread(target=produce), threading.Thread(target=consume)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join(timeout=300)
+    assert not any(t.is_alive() for t in threads) and not errors, errors
+    assert bad == []
 
 
 def test_one_window_calls_return_only_finished_results():
