@@ -83,15 +83,11 @@ struct CanonCfg {
     // error bound then decides between float32 and float64.
     static constexpr float thr(int s, int half)
     {
-#ifdef HSS_NO_TIES
-        return need(s, half) <= 1 ? 0.5f : static_cast<float>(need(s, half)) - 0.5f;
-#else
         const int nd = need(s, half);
         return (nd <= 1 ? 0.5f : static_cast<float>(nd) - 0.5f) - static_cast<float>(1 + (nd <= 1 ? 0 : nd)) * kTieMargin;
-#endif
     }
     static_assert(KLO >= 1, "row 0 is its own twin: acc_source / canon_put want the band above it");
-    static constexpr int wave_floats(int planes = 1) { return 2 * kCanonRecs + planes * 2 * 16 * LD + kCanonFlagWords + kCanonTieWords; }
+    static constexpr int wave_floats() { return 2 * kCanonRecs + 2 * 16 * LD + kCanonFlagWords + kCanonTieWords; }
 };
 
 // Host side of the f16 operand table: entry (tap n, lane l, half h): lane l = (kk, row i); h -> fold term q = kk + 4 (h >> 2),
@@ -99,10 +95,7 @@ struct CanonCfg {
 // in the fp32 table of fsst_core128_kernel.  `cs` = 2^sc scales the constants into [2^13, 2^14).
 // (built in hssfsst.hip: canon_build_atab)
 
-#ifndef HSS_OFFERR
-#define HSS_OFFERR 0.0625f
-#endif
-constexpr float kOffsetErr2 = HSS_OFFERR;                   // (5e-7 / 2e-6)^2: V = V' + mean x Yc is good to 4e-7 R' + 1.2e-7 |mean Yc|, and |mean Yc| <= |V| + R':
+constexpr float kOffsetErr2 = 0.0625f;                     // (5e-7 / 2e-6)^2: V = V' + mean x Yc is good to 4e-7 R' + 1.2e-7 |mean Yc|, and |mean Yc| <= |V| + R':
                                                          // the tie bound of such a tile is tau^2 = 4e-12 (1 + |shift|)^2 (R'^2 + kOffsetErr2 |V|^2) / |V|^2
 // One tile's scale, as the kernels hand it around (wave-uniform).
 struct CanonTile {
@@ -215,11 +208,7 @@ __device__ __forceinline__ CanonMove canon_decide(int kpi, float num, float den,
     const float s1 = 1.0f + fabsf(shift);
     asm volatile("" : "+v"(fr));                        // (see displaced_source: keeps the two product chains unpacked)
     CanonMove m;
-#ifndef HSS_NO_TIES
     m.tie = fr * fr * den < (kTieErr2 * kCanonErrMul) * s1 * s1 * fmaf(eoff, den, R2) && den > kTieFloor2 * R2;     // too close to call in float32
-#else
-    m.tie = false;
-#endif
     const float r = truncf(a + copysignf(0.5f, a));     // MATLAB round: half away from zero
     m.row = static_cast<int>(r) & (NWIN - 1);
     return m;
@@ -254,17 +243,10 @@ __device__ __forceinline__ bool canon_put(f2* row0, int kpi, int row, f2 V)
 template <int KLO, int KC, int TAPB = 4, bool OFFS = true, class XSig = const float*>
 __device__ __forceinline__ void canon_group(const u2* xrec, const float* atab, f2* own_base, int* flag, int* tq,
                                             const double* wtab, const double* twtab, const CanonTile& tile, f2 tiny, int lane_o,
-                                            XSig xsig, int n, int tg, const float* zc, unsigned long long* cp = nullptr)
+                                            XSig xsig, int n, int tg, const float* zc)
 {
     using C = CanonCfg<KLO, KC>;
     constexpr int NT = 16, RQ = 8, NWIN = 128;
-#ifdef HSS_CANON_PROBE                                   // development: issue-time stamps at the phase boundaries of a group
-    unsigned long long cp_last = __builtin_readcyclecounter();
-#define CPROBE(k) do { __builtin_amdgcn_sched_barrier(0); const unsigned long long now_ = __builtin_readcyclecounter(); \
-                       if (cp) cp[k] += now_ - cp_last; cp_last = now_; __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define CPROBE(k) do { } while (0)
-#endif
     const int g = (lane_o >> 4) & 3, j = lane_o & 15;    // (& 3: see canon_stats)
     const double* tw_lds = reinterpret_cast<const double*>(atab + kCanonOpFloats);   // the twiddles' copy in LDS (twtab: in HBM)
     (void)twtab;
@@ -310,12 +292,8 @@ __device__ __forceinline__ void canon_group(const u2* xrec, const float* atab, f
         });
         __builtin_amdgcn_sched_barrier(0);
     });
-    CPROBE(0);
-#if !defined(HSS_CANON_ABLATE) || HSS_CANON_ABLATE < 5
     fft_n<NT>(za);
     fft_n<NT>(zb);
-#endif
-    CPROBE(1);
     // ("Offsets" above) a tile staged without its mean: + mean x the spectrum of the all-ones frame, ONE block between the spectra and
     // the source stage under one wave-uniform branch (round 4 added it to the mixed pairs of every stripe under eight branches, which
     // cost the plain path of the team kernel 4 %).  Interior groups: 32 constants per lane group from the first frame's copy in LDS; a group
@@ -424,14 +402,7 @@ __device__ __forceinline__ void canon_group(const u2* xrec, const float* atab, f
     unsigned defer = 0u;                                 // bit 2 s + class: a source of stripe s <= 2 whose destination was not stored yet ("One plane")
     float mx = 0.0f;                                     // largest |V|^2 among this lane's stored cells ("Exact groups")
     bool visited = false;                                // (wave-uniform) some stripe took the rare path: only then are the flags in LDS worth a look
-#if defined(HSS_CANON_ABLATE) && HSS_CANON_ABLATE >= 4
-    {   f2 accz = {0.0f, 0.0f};
-        static_for<NT>([&](auto I) { accz += za[decltype(I)::value] + zb[decltype(I)::value]; });
-        ownA[0] = accz.x; ownA[1] = accz.y; mx = 1.0e30f; }
-    static_for<0>([&](auto SS) {
-#else
     static_for<NT / 2>([&](auto SS) {
-#endif
         constexpr int s = decltype(SS)::value;
         constexpr bool STA = C::stored(s, 0), STB = C::stored(s, 1);
         constexpr float TA = C::thr(s, 0), TB = C::thr(s, 1);
@@ -442,14 +413,10 @@ __device__ __forceinline__ void canon_group(const u2* xrec, const float* atab, f
         if constexpr (STA) { ownA[16 * s] = a1.x; ownA[16 * s + 1] = a2.x; mx = fmaxf(mx, dna.x); }
         if constexpr (STB) { ownB[16 * s] = b1.x; ownB[16 * s + 1] = b2.x; mx = fmaxf(mx, dnb.x); }
         const bool ma = fabsf(dna.y) >= TA * dna.x, mb = fabsf(dnb.y) >= TB * dnb.x;
-#if defined(HSS_CANON_ABLATE) && HSS_CANON_ABLATE >= 3      // development (tools/canon_ablate.sh): results invalid
-        if ((ma | mb) && tile.R2s == 123.0f) {
-#else
         // (unlikely: the rare path is laid out behind the hot code, no taken branch over it; the test is the wave's, not the lane's, so that
         //  `visited` is a scalar)
         if (__builtin_expect(__builtin_amdgcn_ballot_w64(ma | mb) != 0ull, 0)) {
             visited = true;
-#endif
             f2* cellA = reinterpret_cast<f2*>((float*)(ownA + 16 * s));
             f2* cellB = reinterpret_cast<f2*>((float*)(ownB + 16 * s));
             const int kA = rAi + RQ * s, kB = rBi + RQ * s;
@@ -491,7 +458,6 @@ __device__ __forceinline__ void canon_group(const u2* xrec, const float* atab, f
             }
         }
     });
-    CPROBE(2);
     wave_sync();
     // the tie flag is set by the rare path only: a group that never went there skips the trip to LDS and its wait
     int f_ties = 0;
@@ -504,7 +470,6 @@ __device__ __forceinline__ void canon_group(const u2* xrec, const float* atab, f
         return (gi >= 0 && gi < n) ? static_cast<double>(xs[gi]) : 0.0;
     };
     bool exact = false;
-#ifndef HSS_NO_EXACT
     // ---- "Exact groups" (fsst_mfma128.hpp): no stored cell reaches kExactTheta R of the tile -> look again with the R of
     //      the group's own 143 samples (a quiet group beside a loud burst) -> still none: float64 for the whole group
     if (__builtin_expect(__builtin_amdgcn_ballot_w64(mx > kExactTheta2 * tile.R2s) == 0ull && tile.R2s > 0.0f, 0)) {
@@ -520,7 +485,6 @@ __device__ __forceinline__ void canon_group(const u2* xrec, const float* atab, f
         const float R2g = tile.r2s * __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(piece_sums(e2, 0.0f, 0.0f, 0.0f))));
         exact = __builtin_amdgcn_ballot_w64(mx > kExactTheta2 * R2g) == 0ull && R2g > 0.0f;
     }
-#endif
     if (__builtin_expect(exact, 0)) {
         // (the float32 contributions are dropped: every cell of the group comes from the float64 pass)
         for (int i = lane_o; i < 16 * C::LD; i += 64) own_base[i] = f2{0.0f, 0.0f};
@@ -538,8 +502,6 @@ __device__ __forceinline__ void canon_group(const u2* xrec, const float* atab, f
         wave_sync();
         HSS_RARE_VMEM_DONE();
     }
-    CPROBE(3);
-#undef CPROBE
 }
 // Statistics partial of the group in the own plane (see "Statistics" in fsst_kernels.hpp): pivoted sums over the kept cells
 // of the nvalid valid frames, computed on the SCALED plane values and scaled back afterwards -- a power of two, so the
@@ -663,13 +625,9 @@ __device__ __forceinline__ void canon_fetch(const float* xsig, int n, int t0, in
 // fsst_canon_kernel: work distribution, tickets and the FUSED z-score exactly as fsst_core128_kernel (see there:
 // "Work distribution", "Fused z-score"); the body of a transform chunk is canon_group + canon_stats + canon_image.
 // ------------------------------------------------------------------------------------------------
-#ifdef HSS_FUSE_PROBE      // development (tools/fuse_probe2.py): shader-clock totals per ticket kind over all waves of the FUSED kernel
-__device__ unsigned long long g_fuse_probe[8];      // [0] A tickets [1] cycles in A [2] B tickets [3] B: wait for statistics
-                                                    // [4] B: loads issued -> data there [5] B: arithmetic + stores issued [6] resolver
-#endif
 // RAGGED (hssfsst_exec_ragged): signals of different lengths, chunk list from the host -- as fsst_core128_kernel<.., RAGGED>.
 template <int KLO, int KC, bool FUSED, bool RAGGED = false>
-__global__ __launch_bounds__(64 * 16, HSS_MW128) void fsst_canon_kernel(CanonParams p)
+__global__ __launch_bounds__(64 * 16, 4) void fsst_canon_kernel(CanonParams p)
 {
     static_assert(!(RAGGED && FUSED), "ragged lists: the two-launch kernel");
     using C = CanonCfg<KLO, KC>;
@@ -733,14 +691,7 @@ __global__ __launch_bounds__(64 * 16, HSS_MW128) void fsst_canon_kernel(CanonPar
     int chunk = draw();
     f2 tiny = {1.0e-37f, 0.0f};
     asm volatile("" : "+s"(tiny));
-#ifdef HSS_FUSE_PROBE
-    unsigned long long fp[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#define FPROBE_NOW() __builtin_readcyclecounter()
-#endif
     while (chunk < nwork) {
-#ifdef HSS_FUSE_PROBE
-    const unsigned long long fp_t0 = FPROBE_NOW();
-#endif
     long long b;
     int grp0, ngrp;
     long long ksig = 0;
@@ -806,9 +757,6 @@ __global__ __launch_bounds__(64 * 16, HSS_MW128) void fsst_canon_kernel(CanonPar
             __builtin_amdgcn_s_sleep(4);
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-#ifdef HSS_FUSE_PROBE
-        const unsigned long long fp_t1 = FPROBE_NOW();
-#endif
         const float4 st = fin_stats[sl];
         const unsigned cls = cls_lds[lane_o];
         const float4* base0 = reinterpret_cast<const float4*>(p.out + (b * static_cast<long long>(ncols) + grp0 * 16) * CC);
@@ -833,10 +781,6 @@ __global__ __launch_bounds__(64 * 16, HSS_MW128) void fsst_canon_kernel(CanonPar
                 mu[i][0] = f2{m0, m0}; rs[i][0] = f2{r0, r0};
                 mu[i][1] = f2{m1, m1}; rs[i][1] = f2{r1, r1};
             }
-#ifdef HSS_FUSE_PROBE
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            const unsigned long long fp_t2 = FPROBE_NOW();
-#endif
 #pragma unroll
             for (int q = 0; q < GPCF; ++q) {
                 const int lim = glim(q);
@@ -849,10 +793,6 @@ __global__ __launch_bounds__(64 * 16, HSS_MW128) void fsst_canon_kernel(CanonPar
                     }
                 }
             }
-#ifdef HSS_FUSE_PROBE
-            const unsigned long long fp_t3 = FPROBE_NOW();
-            fp[2] += 1; fp[3] += fp_t1 - fp_t0; fp[4] += fp_t2 - fp_t1; fp[5] += fp_t3 - fp_t2;
-#endif
         }
     } else {
     const float* xsig = RAGGED ? p.x + rxo : p.x + b * p.xstride;
@@ -876,21 +816,12 @@ __global__ __launch_bounds__(64 * 16, HSS_MW128) void fsst_canon_kernel(CanonPar
             const int tg = p.col0 + gidx * 16;
             canon_group<KLO, KC>(xrec + (gidx + cg0 - tbase) * 16, atab, own_base, flag, tq, p.wtab, p.twtab, tile, tiny, lane_o, xsig, n, tg, p.atab + kCanonAtabFloats);
             const int nvalid = min(16, cend - tg);
-#if defined(HSS_CANON_ABLATE) && HSS_CANON_ABLATE >= 2
-            if (p.mode == 77) {
-#else
             if (p.mode == kModeStack) {
-#endif
                 f2 piv;
                 const float w = canon_stats<KLO, KC>(own_base, nvalid, tile.inv, lane_o, piv);
                 if constexpr (FUSED) store_partial(part_lds + ((static_cast<int>(ksig) & 1) * kFusedMaxGroups + gidx) * kPartFloats, w, piv.x, piv.y);
                 else store_partial(part_sig + gidx * kPartFloats, w, piv.x, piv.y);
             }
-#if defined(HSS_CANON_ABLATE) && HSS_CANON_ABLATE >= 1
-            if (tg == 123456789) {
-#else
-            {
-#endif
             f4 o[3];
             canon_image<KLO, KC>(own_base, ppk_lds, tile.inv, lane_o, o);
             float4* dst4 = reinterpret_cast<float4*>(out_sig + (tg - p.col0) * (2 * K)) + lane_o;
@@ -904,11 +835,8 @@ __global__ __launch_bounds__(64 * 16, HSS_MW128) void fsst_canon_kernel(CanonPar
             // The instruction comes from inline assembly (no builtin carries the scope bits of a 16-byte store), so the two things
             // the compiler does for its own stores are done by hand: the wait state of the store-data hazard (s_nop), and the
             // s_waitcnt vmcnt(0) in front of the release on the delivery counter below.
-#ifndef HSS_A_STORE_POLICY
-#define HSS_A_STORE_POLICY "sc1"
-#endif
             auto put = [&](int i) {
-                if constexpr (FUSED) { asm volatile("global_store_dwordx4 %0, %1, off " HSS_A_STORE_POLICY "\n\ts_nop 1" :: "v"(dst4 + 64 * i), "v"(o[i]) : "memory"); }
+                if constexpr (FUSED) { asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" :: "v"(dst4 + 64 * i), "v"(o[i]) : "memory"); }
                 else __builtin_nontemporal_store(o[i], reinterpret_cast<f4*>(dst4 + 64 * i));
             };
             if (__builtin_expect(nvalid == 16, 1)) {
@@ -925,15 +853,10 @@ __global__ __launch_bounds__(64 * 16, HSS_MW128) void fsst_canon_kernel(CanonPar
                 for (int i = 0; i < 3; ++i)
                     if (lane_o + 64 * i < lim) put(i);
             }
-            }
             wave_sync();
         }
         gcur = gstop;
     }
-#ifdef HSS_FUSE_PROBE
-    const unsigned long long fp_ta = FPROBE_NOW();
-    fp[0] += 1; fp[1] += fp_ta - fp_t0;
-#endif
     if constexpr (FUSED) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // (the compiler does not count the stores issued from inline assembly)
         const int sl = static_cast<int>(ksig) & 1;
@@ -950,17 +873,11 @@ __global__ __launch_bounds__(64 * 16, HSS_MW128) void fsst_canon_kernel(CanonPar
                 __hip_atomic_store(ready + (static_cast<int>(ksig) & 3), static_cast<unsigned>(ksig) + 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
             }
             wave_sync();
-#ifdef HSS_FUSE_PROBE
-            fp[6] += FPROBE_NOW() - fp_ta;
-#endif
         }
     }
     }
     chunk = draw();
     }
-#ifdef HSS_FUSE_PROBE
-    if (FUSED && lane == 0) for (int k = 0; k < 7; ++k) atomicAdd(g_fuse_probe + k, fp[k]);
-#endif
 }
 
 }  // namespace hssfsst

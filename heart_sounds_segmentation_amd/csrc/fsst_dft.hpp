@@ -220,7 +220,6 @@ __global__ __launch_bounds__(512) void fsst_dft_kernel(DftParams p)
             if (lane == 0) tq[0] = 0;
             wave_sync();
         }
-#ifndef HSS_NO_EXACT
         // ---- "Exact groups" (fsst_mfma128.hpp): the tile is redone in float64 when none of its kept cells reaches
         //      kExactTheta R (the band holds only the far leakage of something outside it: float32 resolves ~4e-7 of the
         //      frame's spectrum norm, not of the band), or when the tie queue overflowed (cells it had no room for were
@@ -265,7 +264,6 @@ __global__ __launch_bounds__(512) void fsst_dft_kernel(DftParams p)
                 wave_sync();
             }
         }
-#endif
 
         // ---- epilogue for these F frames, one 16-frame group (= one statistics partial) at a time
         for (int q = 0; q < G; ++q) {

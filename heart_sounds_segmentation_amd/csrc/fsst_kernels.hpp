@@ -28,15 +28,6 @@
 //   * MFMA is deliberately unused: at fp32 the matrix pipe has no rate advantage and the only
 //     dense contraction (the folded first stage) is K <= 16 deep.
 #pragma once
-// Development hooks (phase ablations, clock probes, alternative tilings: -DHSS_ABLATE, -DHSS_CANON_ABLATE, -DHSS_T16_ABLATE, -DHSS_*_PROBE,
-// -DHSS_NO_TIES, -DHSS_NO_EXACT, -DHSS_T16_NO_LAGPRIO, -DHSS_DEV_ONLY128 ...) change results or timing and exist for tools/ only: a build
-// that carries one must say so with -DHSS_DEV (tools/dev.sh does); the library that ships is compiled without any of them.
-#if !defined(HSS_DEV) && (defined(HSS_ABLATE) || defined(HSS_CANON_ABLATE) || defined(HSS_T16_ABLATE) || defined(HSS_FUSE_PROBE) || \
-                          defined(HSS_STREAM_PROBE) || defined(HSS_CLOCKPROBE) || defined(HSS_CANON_PROBE) || defined(HSS_NO_TIES) || \
-                          defined(HSS_NO_EXACT) || defined(HSS_T16_NO_LAGPRIO) || defined(HSS_DEV_ONLY128) || defined(HSS_TAIL_ENV) || \
-                          defined(HSS_LDS_PAD) || defined(HSS_WPB_CANON) || defined(HSS_NO_GATE) || defined(HSS_T16_PLANES) || defined(HSS_T16_BLKPROBE))
-#error "development hook without -DHSS_DEV: the shipped library carries none (tools/dev.sh builds development libraries)"
-#endif
 #include <hip/hip_runtime.h>
 
 #include <utility>
@@ -624,7 +615,6 @@ __global__ __launch_bounds__(TILE, 2) void fsst_core_kernel(CoreParams p)
     }
     __syncthreads();
     float* acc = own;
-#ifndef HSS_NO_EXACT
     // ---- "Exact groups" (fsst_mfma128.hpp): no kept cell of the tile reaches 1e-2 R (R^2 = the bound of the tile's spectrum
     //      norms: the band holds only the far leakage of something outside it, and float32 resolves ~4e-7 of the frame's
     //      spectrum norm, not of the band) -> every lane redoes its frame in float64: all one-sided sources, float64 DFT
@@ -662,7 +652,6 @@ __global__ __launch_bounds__(TILE, 2) void fsst_core_kernel(CoreParams p)
             }
         }
     }
-#endif
 
     const int valid = min(TILE, p.col0 + ncols - t0);
     if (p.mode == kModeRaw) {
@@ -747,10 +736,7 @@ __global__ __launch_bounds__(256) void fsst_normalize_kernel(float* out, const f
             int c = static_cast<int>((static_cast<unsigned>(i0 + tid) * 4u) % static_cast<unsigned>(C));
             const int dc = static_cast<int>(1024u % static_cast<unsigned>(C));
             const bool rowwrap = (C & 3) != 0;
-#ifndef HSS_NORM_UNROLL
-#define HSS_NORM_UNROLL 4
-#endif
-#pragma unroll HSS_NORM_UNROLL
+#pragma unroll 4
             for (int i = i0 + tid; i < i1; i += 256) {
                 float4 v = b4[i];                        // (streaming load / store hints measured here: 0.147 vs 0.119 ms, worse)
                 int c1 = c + 1, c2 = c + 2, c3 = c + 3;

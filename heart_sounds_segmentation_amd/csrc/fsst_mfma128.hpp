@@ -33,10 +33,6 @@
 
 #include "fsst_kernels.hpp"
 
-#ifndef HSS_MW128
-#define HSS_MW128 4
-#endif
-
 namespace hssfsst {
 
 using f2 = float __attribute__((ext_vector_type(2)));
@@ -105,19 +101,13 @@ struct Core128Params {
 
 // Chunk pattern for `ngroups` 16-frame groups per signal: 8-group chunks, then 4-group chunks over the last
 // quarter or so, then 2-group chunks at the very end (each chunk costs a counter draw, a tile staging and a
-// statistics reduction, so the small ones are kept to the tail).  Measured (tools/tail_sweep.sh): (16, 6) 0.1691 ms,
+// statistics reduction, so the small ones are kept to the tail).  Measured (tail4, tail2): (16, 6) 0.1691 ms,
 // (24, 2) 0.1683, (32, 6) 0.1701, (8, 4) 0.1738, 8-group chunks only 0.1749.
 inline Core128Regions core128_regions(int ngroups, long long nsig = -1)
 {
     Core128Regions r{};
-#ifdef HSS_TAIL_ENV                                      // development only (tools/tail_sweep.sh)
-    static const int env2 = std::getenv("HSSFSST_TAIL2") ? std::atoi(std::getenv("HSSFSST_TAIL2")) : 6;
-    static const int env4 = std::getenv("HSSFSST_TAIL4") ? std::atoi(std::getenv("HSSFSST_TAIL4")) : 16;
-    const int tail2 = ngroups >= 32 ? env2 : 0, tail4 = ngroups >= 32 ? env4 : 0;
-#else
     const int tail2 = ngroups >= 32 ? 6 : 0;             // groups wanted as 2-group chunks
     const int tail4 = ngroups >= 32 ? 16 : 0;            // groups wanted as 4-group chunks
-#endif
     if (ngroups < 32) {
         // short signals / streaming steps (a rolling transform adds 8 groups per step): parallelism matters more than
         // the per-chunk overhead -- 2-group chunks up to 8 groups, 4-group chunks up to 31; and single groups when
@@ -452,11 +442,7 @@ __device__ __forceinline__ void displaced_source(f2* row_disp, int* flag, int* t
     // (opaque: otherwise the two independent product chains below are packed into v_pk_mul_f32 pairs whose operand
     //  shuffles and hazard nops cost more than the five plain multiplies)
     asm volatile("" : "+v"(fr));
-#ifdef HSS_NO_TIES                                       // development: cost of the tie path (tools/ab_bench.py)
-    if (false) {
-#else
     if (fr * fr * den < (kTieErr2 * ERRMUL) * s1 * s1 * R2 && den > kTieFloor2 * R2) {     // too close to call in float32
-#endif
         __hip_atomic_fetch_or(reinterpret_cast<unsigned*>(tq) + (kpi >> 1), 1u << (((kpi & 1) << 4) + j), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         flag[1] = 1;
         return;
@@ -860,11 +846,7 @@ __device__ __forceinline__ void process_stripe(f2 XA, f2 PA, f2 XB, f2 PB, f2 ti
     }
     // (the threshold sits kTieMargin below 1/2 so that a cell whose |shift| is within the margin of 1/2 -- a rounding
     //  tie as well -- reaches the rare path and its float64 decision)
-#ifdef HSS_NO_TIES
-    constexpr float kStay = 0.5f;
-#else
     constexpr float kStay = 0.5f - kTieMargin;
-#endif
     const bool ma = fabsf(dna.y) >= kStay * dna.x, mb = fabsf(dnb.y) >= kStay * dnb.x;
     if (ma | mb) {                                      // skipped when no lane moved (execz)
         if (ma) displaced_source<NWIN, 1, LIST>(row_disp, flag, tq, klo, K, rA + RQ * S, j, dna.y, dna.x, f2{a1.x, a2.x}, R2, ownA, store, pl);
@@ -902,13 +884,6 @@ constexpr unsigned kSpinLimit = 1u << 18;          // polls before a wait gives 
 // a group's samples come from the tape or, from index hist on, straight from the step's new samples, which the group's wave also
 // appends to the tape (nobody reads the tape there during the step); the block that delivers last for its channel (one counter
 // per channel in HBM) runs the arithmetic of fsst_stream_finish_kernel on the channel's chunk.
-#ifdef HSS_STREAM_PROBE      // development (tools/stream_probe.py): 100 MHz ticks from a wave's start to its phase boundaries, kept per wave, written at the end
-constexpr int kStreamProbeWaves = 2048;
-__device__ unsigned long long g_stream_probe[kStreamProbeWaves * 8];      // [wave of the last launch][stamp]
-#define SPROBE(k) do { if constexpr (STREAM) sprobe[k] = wall_clock64() - sprobe_t0; } while (0)
-#else
-#define SPROBE(k) do { } while (0)
-#endif
 // PAIR (nwin 256 / 512, whose transform is two passes over the same 16 frames): TWO waves share one wave region -- wave 2 r does
 // pass 0 of region r's group, wave 2 r + 1 pass 1, at the same time; the passes write disjoint columns of the own plane, and the
 // odd wave LISTS its additions into the displaced plane instead of making them (PairList): the even wave replays the list behind
@@ -925,7 +900,7 @@ constexpr int kPairFloats = 4 + 64 + 3 * 256;  // [0..1] phase words, [2] the pa
 // transform, ties, epilogue -- is the plain kernel's, on that signal alone (reads past its own length see zeros).
 template <int NT, int RQ, int FPW, bool FAST, int WPB, int S1C, bool FUSED = false, bool STREAM = false, bool PAIR = false,
           bool RAGGED = false>
-__global__ __launch_bounds__(64 * WPB, (NT == 32 ? 2 : WPB == 16 ? HSS_MW128 : WPB == 12 ? 3 : 2)) void fsst_core128_kernel(Core128Params p)
+__global__ __launch_bounds__(64 * WPB, (NT == 32 ? 2 : WPB == 16 ? 4 : WPB == 12 ? 3 : 2)) void fsst_core128_kernel(Core128Params p)
 {
     static_assert(!STREAM || (FAST && !FUSED), "the streaming step: wide-store epilogue, no per-signal z-score");
     static_assert(!PAIR || (RQ == 16 && !FUSED && WPB % 2 == 0), "wave pairs: two passes, whole pairs");
@@ -949,13 +924,6 @@ __global__ __launch_bounds__(64 * WPB, (NT == 32 ? 2 : WPB == 16 ? HSS_MW128 : W
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int g = lane >> 4, j = lane & 15;
-#ifdef HSS_STREAM_PROBE
-    const unsigned long long sprobe_t0 = wall_clock64();
-    unsigned long long sprobe[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#endif
-#ifdef HSS_CLOCKPROBE
-    const unsigned long long probe_c0 = __builtin_readcyclecounter(), probe_r0 = wall_clock64();
-#endif
     float* atab = smem;                                                      // [pass][NT taps][64 lanes][KST]
     int* next_q = reinterpret_cast<int*>(smem + ATAB);                       // block's work counter
     unsigned* done_a = reinterpret_cast<unsigned*>(smem + ATAB) + 1;         // FUSED: [2] groups delivered (monotone)
@@ -1061,7 +1029,6 @@ __global__ __launch_bounds__(64 * WPB, (NT == 32 ? 2 : WPB == 16 ? HSS_MW128 : W
         }
     }
     __syncthreads();
-    SPROBE(0);
 
     // chunk bookkeeping (wave-uniform)
     const int nc0 = p.nsig * p.reg.npc[0];               // (the host keeps nsig * chunks per signal below 2^31)
@@ -1322,7 +1289,6 @@ __global__ __launch_bounds__(64 * WPB, (NT == 32 ? 2 : WPB == 16 ? HSS_MW128 : W
     const TileEnergy te = stage_tile(t0);
     const float R2 = p.r2scale * te.E;
     wave_sync();
-    SPROBE(5);
     if constexpr (STREAM) {
         // the group's 16 new samples (hist + 16 grp0 + lane: the last sample of its frame `lane`) go to the tape; the groups of a
         // channel cover the chunk once
@@ -1381,17 +1347,8 @@ __global__ __launch_bounds__(64 * WPB, (NT == 32 ? 2 : WPB == 16 ? HSS_MW128 : W
                 zb[bitrev_n<NT>(g0 + i)] = f2{acc[i].z, acc[i].w};
             });
         });
-#if !defined(HSS_ABLATE) || HSS_ABLATE < 4
         fft_n<NT>(za);
         fft_n<NT>(zb);
-#endif
-#if defined(HSS_ABLATE) && HSS_ABLATE >= 3
-        {   // development only: keep the spectra alive without the source stage
-            f2 acc = {0.0f, 0.0f};
-            static_for<NT>([&](auto I) { acc += za[decltype(I)::value] + zb[decltype(I)::value]; });
-            if (s1 >= 0 && isg0) own_base[j * OLD] = acc;
-        }
-#else
         // ---- one-sided sources of this lane: classes rA (array a) and rB (array b)
         bool listed = false;
         if constexpr (PAIR && pz == 1) {
@@ -1450,7 +1407,6 @@ __global__ __launch_bounds__(64 * WPB, (NT == 32 ? 2 : WPB == 16 ? HSS_MW128 : W
         if constexpr (pz == 0) {
             if (s1 == NT / 2 && isg0) own_base[j * OLD + NWIN / 2 - RQ * s0] = f2{2.0f * za[NT / 2].x, 0.0f};
         }
-#endif
         };
         if constexpr (PAIR) {
             for (int attempt = 0; attempt < 2; ++attempt) {
@@ -1490,13 +1446,11 @@ __global__ __launch_bounds__(64 * WPB, (NT == 32 ? 2 : WPB == 16 ? HSS_MW128 : W
             static_for<NPASS>(one_pass);
             wave_sync();
         }
-        SPROBE(6);
         if (!PAIR || role == 0) {                            // (PAIR: the odd wave waits at the sync that ends the group)
         // one LDS round trip for both per-group flags (dirty displaced plane, queued rounding ties)
         int f_dirty = flag[0];
         const int f_ties = flag[1];
         bool exact = false;
-#ifndef HSS_NO_EXACT
         // ---- "Exact groups": no stored cell reaches kExactTheta R of the tile -> the R of the group's own samples -> float64
         if (__builtin_amdgcn_ballot_w64(mx > kExactTheta2 * R2) == 0ull && R2 > 0.0f) {
             float e2 = 0.0f;
@@ -1507,7 +1461,6 @@ __global__ __launch_bounds__(64 * WPB, (NT == 32 ? 2 : WPB == 16 ? HSS_MW128 : W
             exact = __builtin_amdgcn_ballot_w64(mx > kExactTheta2 * R2g) == 0ull && R2g > 0.0f;
         }
         if (te.dcdom) exact = true;                      // (an offset with little on top: tile_energy, fsst_kernels.hpp)
-#endif
         if (exact) {
             for (int i = lane_o; i < 16 * LDF; i += 64) disp_base[i] = f2{0.0f, 0.0f};
             if (lane_o < 2) flag[lane_o] = 0;
@@ -1574,10 +1527,6 @@ __global__ __launch_bounds__(64 * WPB, (NT == 32 ? 2 : WPB == 16 ? HSS_MW128 : W
             float4* dst4 = reinterpret_cast<float4*>(p.out + (b * static_cast<long long>(ncols) + tr) * C) + lane_o;
             const int lim = nvalid * (K >> 1);
             f4 o[3];
-#if defined(HSS_ABLATE) && HSS_ABLATE >= 1
-            if (tg == 123456789)
-#endif
-            {
 #pragma unroll
             for (int i = 0; i < 3; ++i) {
                 const unsigned pk = ppk_lds[i * 64 + lane_o];
@@ -1630,7 +1579,6 @@ __global__ __launch_bounds__(64 * WPB, (NT == 32 ? 2 : WPB == 16 ? HSS_MW128 : W
                     }
                 }
             }
-            }
         } else if (p.mode == kModeRaw) {
             float2* dst = reinterpret_cast<float2*>(p.out) + (b * K) * static_cast<long long>(ncols) + tr;
             int e0 = lane_o;                                 // opaque per GROUP (see the general epilogue below)
@@ -1668,13 +1616,8 @@ __global__ __launch_bounds__(64 * WPB, (NT == 32 ? 2 : WPB == 16 ? HSS_MW128 : W
                     if (isabs) {
                         dst[4 * i] = sqrtf(fmaf(v.x, v.x, v.y * v.y));
                     } else {
-#if defined(HSS_ABLATE) && HSS_ABLATE >= 1
-                        if (tg == 123456789)
-#endif
-                        {
                         dst[4 * i] = v.x;
                         dsti[4 * i] = v.y;
-                        }
                         const f2 d = v - piv;
                         st_s += d;
                         st_q = pk_fma(d, d, st_q);
@@ -1721,7 +1664,6 @@ __global__ __launch_bounds__(64 * WPB, (NT == 32 ? 2 : WPB == 16 ? HSS_MW128 : W
     }
     chunk = draw_pair();
     }
-    SPROBE(1);
     if constexpr (STREAM) {
         if (p.state != nullptr) {
             // the channel's last block to get here merges the chunk into the running moments and normalises it
@@ -1737,7 +1679,6 @@ __global__ __launch_bounds__(64 * WPB, (NT == 32 ? 2 : WPB == 16 ? HSS_MW128 : W
                 last_sh[0] = last ? 1u : 0u;
             }
             __syncthreads();
-            SPROBE(2);
             if (last_sh[0] != 0u) {
                 float4* st_sh = reinterpret_cast<float4*>(smem + 4);
                 float* cbase = p.out + static_cast<long long>(st_ch) * ncols * (2 * K);
@@ -1758,33 +1699,11 @@ __global__ __launch_bounds__(64 * WPB, (NT == 32 ? 2 : WPB == 16 ? HSS_MW128 : W
                     }
                 }
                 __syncthreads();
-                SPROBE(3);
                 stream_normalize_apply<64 * WPB, NPF>(cbase, ncols, K, static_cast<int>(threadIdx.x), *st_sh, cpre, AgentLoad4(),
                                                       p.mirror ? p.mirror + static_cast<long long>(st_ch) * ncols * (2 * K) : nullptr);
-                SPROBE(4);
             }
         }
     }
-#ifdef HSS_STREAM_PROBE
-    if constexpr (STREAM) {
-        sprobe[7] = wall_clock64() - sprobe_t0;
-        const int wid = static_cast<int>(blockIdx.x) * WPB + wv;
-        if (lane == 0 && wid < kStreamProbeWaves)
-            for (int k = 0; k < 8; ++k) g_stream_probe[wid * 8 + k] = sprobe[k];
-    }
-#endif
-#ifdef HSS_CLOCKPROBE
-    // development only (STACK_UNNORM, tools/clock_probe.py): HSS_CLOCKPROBE=1 -- shader-clock ticks and 100 MHz ticks one
-    // wave in the middle of the grid lived; =2 -- start / end time (100 MHz ticks, low 32 bits) of every wave
-    if (HSS_CLOCKPROBE == 1 && blockIdx.x == gridDim.x / 2 && wv == 0 && lane == 0) {
-        p.out[0] = static_cast<float>(__builtin_readcyclecounter() - probe_c0);
-        p.out[1] = static_cast<float>(wall_clock64() - probe_r0);
-    }
-    if (HSS_CLOCKPROBE == 2 && lane == 0) {
-        unsigned* o = reinterpret_cast<unsigned*>(p.out) + 2 * (static_cast<size_t>(blockIdx.x) * WPB + wv);
-        o[0] = static_cast<unsigned>(probe_r0); o[1] = static_cast<unsigned>(wall_clock64());
-    }
-#endif
 }
 
 }  // namespace hssfsst

@@ -61,16 +61,10 @@
 #include "fsst_mfma128.hpp"
 #include "fsst_canon128.hpp"
 
-#ifndef HSS_T16_TAPB
-#define HSS_T16_TAPB 2
-#endif
 namespace hssfsst {
 
 using gu64 = __attribute__((address_space(1))) unsigned long long;
 
-#ifdef HSS_T16_BLKPROBE      // development (tools/blk_probe.py): per wave of the LAST launch: waits, -, ticks waited, ticks resolving, resolves
-__device__ unsigned g_t16_blk[256 * 16 * 8];
-#endif
 constexpr int kT16PartFloats = 6;            // a group's statistics partial in the CU's LDS: S1re S2re S1im S2im p_re p_im
 constexpr int kT16BlockWords = 8;            // tagged 8-byte words per BLOCK of kStatBlock groups in the mailbox: the block's four
                                              // float64 sums (sum re, sum re^2, sum im, sum im^2), each as {high, low} half
@@ -84,18 +78,12 @@ constexpr int kT16StatFloats = 12;           // a signal's statistics in LDS: th
 constexpr int t16_ctl_base(int slots) { return 16 + 64 + 192 + 2 * slots + kT16StatFloats * slots; }
 // ... then the partials of the CU's own groups, PSLOTS signals deep: [PSLOTS][kT16MaxCpc][6] floats + [PSLOTS][2] block counters
 constexpr int t16_ctl_floats(int pslots, int slots) { return t16_ctl_base(slots) + pslots * (kT16MaxCpc * kT16PartFloats + 2); }
-// what the LDS beside the tables and 16 wave regions leaves: partials 32 signals deep and 64 statistics slots where they fit
-// own planes per wave: two where the LDS has room for them (the second one holds the previous step's image: "Two planes" below)
-#ifndef HSS_T16_PLANES
-#define HSS_T16_PLANES 1                     // (2: a second own plane per wave -- a third held group at no instruction; measured +0.9 % on the queued kernel,
-#endif                                       //  profiles/r06_team_waits.txt: the resolves are started by the first wave that needs them, whatever the depth)
+// what the LDS beside the tables and 16 wave regions leaves: partials 32 signals deep and 64 statistics slots where they fit.
+// One own plane per wave: a second one, holding the previous step's image (a third held group at no instruction), measured
+// +0.9 % on the queued kernel (profiles/r06_team_waits.txt: the resolves are started by the first wave that needs them, whatever
+// the depth).
 template <int KLO, int KC>
-constexpr int t16_planes()
-{
-    return HSS_T16_PLANES >= 2 && 160 * 1024 / 4 - kCanonLdsTabFloats - 16 * CanonCfg<KLO, KC>::wave_floats(2) >= t16_ctl_floats(16, kT16MaxSlots / 2) ? 2 : 1;
-}
-template <int KLO, int KC>
-constexpr int t16_room() { return 160 * 1024 / 4 - kCanonLdsTabFloats - 16 * CanonCfg<KLO, KC>::wave_floats(t16_planes<KLO, KC>()); }
+constexpr int t16_room() { return 160 * 1024 / 4 - kCanonLdsTabFloats - 16 * CanonCfg<KLO, KC>::wave_floats(); }
 template <int KLO, int KC>
 constexpr int t16_slots() { return t16_room<KLO, KC>() >= t16_ctl_floats(16, kT16MaxSlots) ? kT16MaxSlots : kT16MaxSlots / 2; }
 template <int KLO, int KC>
@@ -185,9 +173,6 @@ template <int KLO, int KC, int WPB, int DEPTH, class OT = float>
 __global__ __launch_bounds__(64 * WPB, WPB / 4) __attribute__((amdgpu_num_vgpr(52))) void fsst_team16_kernel(Team16Params p)
 {
     constexpr int OB = static_cast<int>(sizeof(OT));     // bytes per output element
-#ifdef HSS_T16_BLKPROBE
-    const unsigned pb_entry = static_cast<unsigned>(wall_clock64());       // (absolute: the 100 MHz counter is the chip's)
-#endif
     using C = CanonCfg<KLO, KC>;
     static_assert(WPB % 4 == 0 && DEPTH >= 1 && DEPTH <= 2, "whole waves per SIMD; two held groups (v104 .. v127)");
     static_assert(DEPTH == 2, "the kernel is compiled for 104 allocatable registers + 24 fixed ones");
@@ -208,11 +193,10 @@ __global__ __launch_bounds__(64 * WPB, WPB / 4) __attribute__((amdgpu_num_vgpr(5
     static_assert(PSLOTS >= 16, "the CU's own partials need LDS beside the wave regions");
     float* part_lds = smem + ATAB + t16_ctl_base(MS);                        // [PSLOTS][kT16MaxCpc][6]
     int* pcnt_lds = reinterpret_cast<int*>(part_lds + PSLOTS * kT16MaxCpc * kT16PartFloats);   // [PSLOTS][2] partials delivered per block
-    constexpr int PLANES = t16_planes<KLO, KC>();
-    float* wbase = smem + ATAB + t16_ctl_floats(PSLOTS, MS) + wv * C::wave_floats(PLANES);
+    float* wbase = smem + ATAB + t16_ctl_floats(PSLOTS, MS) + wv * C::wave_floats();
     u2* xrec = reinterpret_cast<u2*>(wbase);
-    f2* own_first = reinterpret_cast<f2*>(wbase + 2 * kCanonRecs);
-    int* flag = reinterpret_cast<int*>(own_first + PLANES * 16 * C::LD);
+    f2* own_base = reinterpret_cast<f2*>(wbase + 2 * kCanonRecs);
+    int* flag = reinterpret_cast<int*>(own_base + 16 * C::LD);
     int* tq = flag + kCanonFlagWords;
 
     // Block identity = ARRIVAL number ("Giving up" above).  Asked for FIRST: the trip to the counter (1.5-2 us) runs beside the table's loads, not behind them
@@ -333,10 +317,6 @@ __global__ __launch_bounds__(64 * WPB, WPB / 4) __attribute__((amdgpu_num_vgpr(5
     };
     auto draw = [&](int after_ko) { draw_ask(after_ko); draw_take(); };
 
-#ifdef HSS_T16_BLKPROBE
-    unsigned pb_miss = 0u, pb_blocked = 0u, pb_fin = 0u, pb_nfin = 0u;
-    const unsigned long long pb_c0 = __builtin_readcyclecounter(), pb_r0 = wall_clock64();
-#endif
     auto stats_ready = [&](int ko) -> bool {             // the CU already has this signal's statistics
         unsigned have = 0u;
         if (lane == 0) have = __hip_atomic_load(ready + (ko & smask), __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -403,31 +383,13 @@ __global__ __launch_bounds__(64 * WPB, WPB / 4) __attribute__((amdgpu_num_vgpr(5
     // a wave cannot go on without a signal's statistics: a sibling's result, or this wave resolves (a wave that finds the launch
     // given up does not come back)
     auto signal_statistics = [&](int ko) {
-#if defined(HSS_T16_ABLATE) && (HSS_T16_ABLATE == 1 || HSS_T16_ABLATE == 2)      // development: nobody waits, nobody resolves (results invalid)
-        return;
-#endif
         if (stats_ready(ko)) return;
         int lane_r = lane;
         asm volatile("" : "+v"(lane_r));
         const unsigned t0 = static_cast<unsigned>(wall_clock64());
-#ifdef HSS_T16_BLKPROBE
-        ++pb_miss;
-        struct Fin { unsigned& acc; unsigned t; __device__ ~Fin() { acc += static_cast<unsigned>(wall_clock64()) - t; } } fin_{pb_blocked, t0};
-#endif
-#if defined(HSS_T16_ABLATE) && HSS_T16_ABLATE == 3      // development: the resolver resolves, nobody else waits (results invalid)
-        if (try_claim(ko)) resolve_owned(ko, t0, lane_r);
-        return;
-#endif
         for (unsigned spins = 0;; ++spins) {
             if ((spins & 15u) == 0u && try_claim(ko)) {
-#ifdef HSS_T16_BLKPROBE
-                const unsigned tr = static_cast<unsigned>(wall_clock64());
-                resolve_owned(ko, t0, lane_r);
-                pb_fin += static_cast<unsigned>(wall_clock64()) - tr; ++pb_nfin;
-                return;
-#else
                 resolve_owned(ko, t0, lane_r); return;
-#endif
             }
             if ((spins & 31u) == 31u && expired(t0)) { gave_up(); leave(); }
             if (is_dead()) leave();
@@ -456,12 +418,8 @@ __global__ __launch_bounds__(64 * WPB, WPB / 4) __attribute__((amdgpu_num_vgpr(5
             const float4 tt = *reinterpret_cast<const float4*>(tb + ((cofs >> (8 * i)) & 0xffu));
             const f2 lo = held_zscore<6 * sl + 2 * i>(f2{tt.x, tt.y});
             const f2 hi = held_zscore<6 * sl + 2 * i + 1>(f2{tt.z, tt.w});
-#if defined(HSS_T16_ABLATE) && HSS_T16_ABLATE >= 2      // development: the arithmetic without the stores
-            { f2 l2 = lo, h2 = hi; asm volatile("" :: "v"(l2), "v"(h2)); }
-#else
             if constexpr (OB == 4) __builtin_nontemporal_store(f4{lo.x, lo.y, hi.x, hi.y}, reinterpret_cast<f4*>(obase + (voff + 1024u * static_cast<unsigned>(i))));
             else team16_store4<OT>(obase + (voff + (256u * OB) * static_cast<unsigned>(i)), lo, hi);
-#endif
         };
         if (__builtin_expect(nvalid == 16, 1)) {
             static_for<3>([&](auto I) {
@@ -506,15 +464,6 @@ __global__ __launch_bounds__(64 * WPB, WPB / 4) __attribute__((amdgpu_num_vgpr(5
         ko = ko_d; g = g_d; c_valid = true; d_valid = false;
     };
     int slot = 0;                                        // the slot this step fills (steps take the slots in turn)
-    // Two planes (where the LDS has them: the displaced plane's 47 kB, fsst_canon128.hpp "One plane").  The steps write the planes in
-    // turn, and a step's image stays in its plane for a whole step: it moves into the registers at the END OF THE NEXT step, when the
-    // other plane holds that step's image.  A group's statistics are therefore wanted THREE steps after its partial was published
-    // instead of two -- a third held group at no instruction and no register (a third image in registers spilled, parked in global
-    // memory it cost 6 %: profiles/r05_team_diet.txt) --, which is what the waits for statistics, 4-5 % of the kernel, were short of.
-    int cur = 0;                                         // the plane this step transforms into
-    bool p_valid = false;                                // the OTHER plane holds the previous step's image: group (p_ko, p_g), scale p_inv
-    int p_ko = 0, p_g = 0;
-    float p_inv = 0.0f;
     draw(-1);
     if (saw_dead || abort_seen == P()->launch) return;
     if (d_valid) { land(); draw(-1); }                   // (the second ticket is transformed and published before the wave's first wait)
@@ -529,15 +478,12 @@ __global__ __launch_bounds__(64 * WPB, WPB / 4) __attribute__((amdgpu_num_vgpr(5
         asm volatile("" : "+v"(lane_o));
         const unsigned b = static_cast<unsigned>(team + ko * nteams);
         const int tg = P()->col0 + g * 16;
-#ifndef HSS_T16_NO_LAGPRIO
         {   // a group of a signal the CU's ticket counter has left behind is what other waves will soon wait for: it goes first
             // (what the wave's own next ticket says about the counter -- a group time old, but no trip to LDS)
             const int lag = (d_valid ? ko_d : ko + 2) - ko;
             if (lag >= 2) __builtin_amdgcn_s_setprio(2); else if (lag == 1) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0);      // (3 / 2: slower; off: +2.8 %)
         }
-#endif
-        f2* own_base = own_first + cur * (16 * C::LD);
-        canon_group<KLO, KC, HSS_T16_TAPB, true>(xrec + ((g + cg0) & 3) * 16, atab, own_base, flag, tq, P()->wtab, P()->twtab, tile, tiny, lane_o,
+        canon_group<KLO, KC, 2, true>(xrec + ((g + cg0) & 3) * 16, atab, own_base, flag, tq, P()->wtab, P()->twtab, tile, tiny, lane_o,
                                            [&]() -> const float* { return P()->x + static_cast<unsigned long long>(b) * static_cast<unsigned>(P()->xstride); }, n, tg, P()->atab + kCanonAtabFloats);
         const float inv_cur = tile.inv;
         const int ko_cur = ko, g_cur = g;
@@ -634,7 +580,6 @@ __global__ __launch_bounds__(64 * WPB, WPB / 4) __attribute__((amdgpu_num_vgpr(5
         // per float4 of the image its offsets, then its cells -- it was eleven, one behind the other, a tenth of the wave's time per group):
         // first the words that only depend on the lane and the slot -- is the leaving group's signal resolved, which statistics entry and
         // which cells each of the lane's three float4 takes --, then, behind one wait, the statistics entries and the new image's cells.
-        // (with two planes the image that moves in is the PREVIOUS step's, from the other plane)
         auto move_in = [&](const f2* src_plane, float inv_src, int ko_src, int g_src) {
             int ko_o = 0, g_o = 0;
             static_for<DEPTH>([&](auto S) { if (slot == decltype(S)::value) { ko_o = ko_hs[decltype(S)::value]; g_o = g_hs[decltype(S)::value]; } });
@@ -645,9 +590,7 @@ __global__ __launch_bounds__(64 * WPB, WPB / 4) __attribute__((amdgpu_num_vgpr(5
             const unsigned pk0 = ppk_lds[lane_r], pk1 = ppk_lds[64 + lane_r], pk2 = ppk_lds[128 + lane_r];
             const unsigned have = __hip_atomic_load(ready + (ko_o & smask), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);   // (every lane: a broadcast read)
             if (full) {
-#if !(defined(HSS_T16_ABLATE) && (HSS_T16_ABLATE == 1 || HSS_T16_ABLATE == 2))
                 if (static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(have))) != static_cast<unsigned>(ko_o) + 1u) signal_statistics(ko_o);
-#endif
             } else ++nheld;
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
             unsigned obase = static_cast<unsigned>(reinterpret_cast<size_t>((lds_float*)reinterpret_cast<const float*>(src_plane)));
@@ -675,12 +618,8 @@ __global__ __launch_bounds__(64 * WPB, WPB / 4) __attribute__((amdgpu_num_vgpr(5
                             constexpr int i = decltype(I)::value;
                             const f2 l = held_zscore<6 * sl + 2 * i>(f2{tt.x, tt.y});
                             const f2 h = held_zscore<6 * sl + 2 * i + 1>(f2{tt.z, tt.w});
-#if defined(HSS_T16_ABLATE) && HSS_T16_ABLATE >= 2      // development: the arithmetic without the stores
-                            { f2 l2 = l, h2 = h; asm volatile("" :: "v"(l2), "v"(h2)); }
-#else
                             if constexpr (OB == 4) __builtin_nontemporal_store(f4{l.x, l.y, h.x, h.y}, reinterpret_cast<f4*>(ob + (voff + 1024u * static_cast<unsigned>(i))));
                             else team16_store4<OT>(ob + (voff + (256u * OB) * static_cast<unsigned>(i)), l, h);
-#endif
                         };
                         const float4 tts[3] = {t0, t1, t2};
                         if (__builtin_expect(nvalid == 16, 1)) {
@@ -703,44 +642,8 @@ __global__ __launch_bounds__(64 * WPB, WPB / 4) __attribute__((amdgpu_num_vgpr(5
             });
             slot = (slot + 1 == DEPTH) ? 0 : slot + 1;
         };
-        if constexpr (PLANES == 2) {
-            if (p_valid) move_in(own_first + (cur ^ 1) * (16 * C::LD), p_inv, p_ko, p_g);
-            p_valid = true; p_inv = inv_cur; p_ko = ko_cur; p_g = g_cur;
-            cur ^= 1;
-        } else
-            move_in(own_base, inv_cur, ko_cur, g_cur);
+        move_in(own_base, inv_cur, ko_cur, g_cur);
         wave_sync();
-    }
-    // ---- the list is done: the image that still sits in its plane moves in (the oldest held group leaves for it) ...
-    if constexpr (PLANES == 2) {
-        if (p_valid) {
-            int ko_o = 0, g_o = 0;
-            static_for<DEPTH>([&](auto S) { if (slot == decltype(S)::value) { ko_o = ko_hs[decltype(S)::value]; g_o = g_hs[decltype(S)::value]; } });
-            (void)g_o;
-            const f2* src_plane = own_first + (cur ^ 1) * (16 * C::LD);
-            const bool full = nheld == DEPTH;
-            if (full) signal_statistics(ko_o); else ++nheld;
-            static_for<DEPTH>([&](auto S) {
-                constexpr int sl = decltype(S)::value;
-                if (slot == sl) {
-                    if (full) emit_held(S, ko_hs[sl], g_hs[sl]);
-                    int lane_r = lane;
-                    asm volatile("" : "+v"(lane_r));
-                    unsigned obase = static_cast<unsigned>(reinterpret_cast<size_t>((lds_float*)reinterpret_cast<const float*>(src_plane)));
-                    const f2 sc = {p_inv, p_inv};
-                    static_for<3>([&](auto I) {
-                        constexpr int i = decltype(I)::value;
-                        const unsigned pk = ppk_lds[i * 64 + lane_r];
-                        const lds_float* q0 = (const lds_float*)static_cast<size_t>(obase + (pk & 0xffffu));
-                        const lds_float* q1 = (const lds_float*)static_cast<size_t>(obase + (pk >> 16));
-                        held_put<6 * sl + 2 * i>(f2{q0[0], q0[2]}, sc);
-                        held_put<6 * sl + 2 * i + 1>(f2{q1[0], q1[2]}, sc);
-                    });
-                    ko_hs[sl] = p_ko; g_hs[sl] = p_g;
-                }
-            });
-            slot = (slot + 1 == DEPTH) ? 0 : slot + 1;
-        }
     }
     // ---- the list is done: the held groups leave, oldest first
     for (int i = 0; i < nheld; ++i) {
@@ -770,13 +673,6 @@ __global__ __launch_bounds__(64 * WPB, WPB / 4) __attribute__((amdgpu_num_vgpr(5
             }
         }
     }
-#ifdef HSS_T16_BLKPROBE
-    if (lane == 0 && virt < 256) {
-        unsigned* e = g_t16_blk + (virt * 16 + wv) * 8;
-        e[0] = pb_miss; e[1] = pb_entry; e[7] = static_cast<unsigned>(wall_clock64()); e[2] = pb_blocked; e[3] = pb_fin; e[4] = pb_nfin;
-        e[5] = static_cast<unsigned>(__builtin_readcyclecounter() - pb_c0); e[6] = static_cast<unsigned>(wall_clock64() - pb_r0);
-    }
-#endif
 }
 
 }  // namespace hssfsst

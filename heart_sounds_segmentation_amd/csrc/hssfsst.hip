@@ -15,8 +15,7 @@
 #include <chrono>
 #include <mutex>
 #include <dlfcn.h>
-#include <cctype>
-#include <string>
+#include <cstdlib>
 #include <array>
 #include <atomic>
 #include <memory>
@@ -29,10 +28,6 @@
 #include "fsst_mfma128.hpp"
 #include "fsst_canon128.hpp"
 #include "fsst_team16.hpp"
-#ifndef HSS_T16_WPB
-#define HSS_T16_WPB 16
-#define HSS_T16_DEPTH 2
-#endif
 #include "fsst_dft.hpp"
 #include "fsst_gather.hpp"
 #include "fsst_ragged.hpp"
@@ -63,10 +58,10 @@ int fail(int code, const char* fmt, ...)
                         __FILE__, __LINE__);                                                   \
     } while (0)
 
-// Development / A-B switches, read ONCE per process (first use) from the environment: HSSFSST_DEBUG="key[=value],key,..." with the
-// keys below, or -- the older spelling the tests and tools use -- one variable per key, HSSFSST_<KEY in capitals>[=value].
-// Defaults are the measured best; no switch changes a result (every path gives the same bits, which is what most of them
-// exist to show).  Nothing else in the library reads the environment.
+// A-B and test switches, read ONCE per process (first use) from the environment, one variable per key: HSSFSST_<KEY in capitals>
+// is on when set to an empty string, a non-zero number or a word that starts with y or t (HSSFSST_FORCE_GENERIC: a value that
+// starts with 1).  Defaults are the measured best; no switch changes a result (every path gives the same bits, which is what most
+// of them exist to show).  Nothing else in the library reads the environment.
 struct DebugSwitches {
     bool no_fused = false;        // z-score always as a second kernel
     bool no_canon = false;        // the canonical band on the general kernels (fsst_mfma128.hpp)
@@ -75,52 +70,27 @@ struct DebugSwitches {
     bool team_force_fallback = false;   // every team launch finds itself given up (tests of the gated fallback)
     bool force_dft = false;       // every window length on the any-length kernel
     bool force_generic = false;   // every radix length on the generic VALU kernel
-    bool no_mfma256 = false;      // nwin 256 / 512 on the generic kernel
-    bool split_stats = false;     // a separate statistics launch on the two-launch path
     bool no_stream_fuse = false;  // a streaming step as copy + transform + merge-and-normalise launches
     bool no_pair = false;         // nwin 256 / 512: one wave per wave region (no wave pairs)
-    int team = 0;                 // CUs per team (0: chosen by the library)
-    unsigned team_spin_us = 500;  // bound of a wait inside the team kernel
-    int oneplane_kb = 40;         // generic kernel: one shared LDS plane above this many KB
-    int zgrid = 0, zslices = 0;   // z-score sweep geometry (0: chosen by the library)
 };
 const DebugSwitches& debug_switches()
 {
     static const DebugSwitches sw = [] {
-        DebugSwitches d;
-        auto set = [&](const std::string& key, const char* val) {
-            const int iv = val ? std::atoi(val) : 0;
-            const bool on = !val || val[0] == '\0' || iv != 0 || val[0] == 'y' || val[0] == 't';
-            if (key == "no_fused") d.no_fused = on; else if (key == "no_canon") d.no_canon = on;
-            else if (key == "no_team") d.no_team = on; else if (key == "team_only") d.team_only = on;
-            else if (key == "team_force_fallback") d.team_force_fallback = on; else if (key == "force_dft") d.force_dft = on;
-            else if (key == "force_generic") d.force_generic = on; else if (key == "no_mfma256") d.no_mfma256 = on;
-            else if (key == "split_stats") d.split_stats = on; else if (key == "no_stream_fuse") d.no_stream_fuse = on; else if (key == "no_pair") d.no_pair = on; else if (key == "team") d.team = iv;
-            else if (key == "team_spin_us") d.team_spin_us = static_cast<unsigned>(iv > 0 ? iv : 500);
-            else if (key == "oneplane_kb") d.oneplane_kb = iv;
-            else if (key == "zgrid") d.zgrid = iv; else if (key == "zslices") d.zslices = iv;
+        auto on = [](const char* name) {
+            const char* v = std::getenv(name);
+            return v != nullptr && (v[0] == '\0' || std::atoi(v) != 0 || v[0] == 'y' || v[0] == 't');
         };
-        static const char* const keys[] = {"no_fused", "no_canon", "no_team", "team_only", "team_force_fallback", "force_dft", "force_generic",
-                                           "no_mfma256", "split_stats", "no_stream_fuse", "no_pair", "team", "team_spin_us", "oneplane_kb", "zgrid", "zslices"};
-        for (const char* k : keys) {                       // HSSFSST_<KEY>
-            std::string name = "HSSFSST_";
-            for (const char* c = k; *c; ++c) name += static_cast<char>(std::toupper(static_cast<unsigned char>(*c)));
-            if (const char* v = std::getenv(name.c_str())) set(k, (name == "HSSFSST_FORCE_GENERIC" && v[0] != '1') ? "0" : v);
-        }
-        if (const char* all = std::getenv("HSSFSST_DEBUG")) {   // HSSFSST_DEBUG="no_fused,team=16"
-            std::string item;
-            for (const char* c = all;; ++c) {
-                if (*c == ',' || *c == '\0') {
-                    if (!item.empty()) {
-                        const size_t eq = item.find('=');
-                        if (eq == std::string::npos) set(item, nullptr);
-                        else set(item.substr(0, eq), item.c_str() + eq + 1);
-                    }
-                    item.clear();
-                    if (*c == '\0') break;
-                } else if (*c != ' ') item += *c;
-            }
-        }
+        DebugSwitches d;
+        d.no_fused = on("HSSFSST_NO_FUSED");
+        d.no_canon = on("HSSFSST_NO_CANON");
+        d.no_team = on("HSSFSST_NO_TEAM");
+        d.team_only = on("HSSFSST_TEAM_ONLY");
+        d.team_force_fallback = on("HSSFSST_TEAM_FORCE_FALLBACK");
+        d.force_dft = on("HSSFSST_FORCE_DFT");
+        const char* fg = std::getenv("HSSFSST_FORCE_GENERIC");
+        d.force_generic = fg != nullptr && fg[0] == '1';
+        d.no_stream_fuse = on("HSSFSST_NO_STREAM_FUSE");
+        d.no_pair = on("HSSFSST_NO_PAIR");
         return d;
     }();
     return sw;
@@ -232,10 +202,7 @@ void band_rows(int nwin, double fs, double f_lo, double f_hi, int* klo, int* K)
 }
 
 constexpr int kTile = 64;
-#ifndef HSS_FPW128
-#define HSS_FPW128 64
-#endif
-constexpr int kFpw128 = HSS_FPW128;      // frames per wave tile of the nwin = 128 kernel
+constexpr int kFpw128 = 64;      // frames per wave tile of the nwin = 128 kernel
 
 // A plan's device buffer: capacity in elements of T; grow() frees the old block and allocates a larger one (contents are not
 // kept), upload() makes a fresh block holding a host table.  Freed with its owner.
@@ -416,9 +383,8 @@ int launch_core(hssfsst_plan* pl, hssfsst::CoreParams cp, long long nblocks, hip
     cp.oneplane = 0;
     // wide band: own and displaced values share one plane.  Needed above 160 KiB (nwin 512, > ~150 kept rows) and
     // already worth it above 40 KiB, where LDS is what limits the resident waves (measured, 1024 x 2000, band
-    // [25,200] Hz: nwin 256 core 2.25 -> 1.44 ms, nwin 512 18.9 -> 9.4 ms; HSSFSST_ONEPLANE_KB overrides)
-    const int one_thr = debug_switches().oneplane_kb;
-    if (lds > static_cast<size_t>(one_thr) * 1024) {
+    // [25,200] Hz: nwin 256 core 2.25 -> 1.44 ms, nwin 512 18.9 -> 9.4 ms)
+    if (lds > 40 * 1024) {
         lds = (static_cast<size_t>(XS) + static_cast<size_t>(2 * pl->K) * (kTile + 1)) * sizeof(float);
         cp.oneplane = 1;
     }
@@ -445,9 +411,6 @@ template <int NT, int RQ, bool FAST, int WPB, int S1C = -1, bool PAIR = false, b
 int launch_core128_wpb(hssfsst_plan* pl, const hssfsst::Core128Params& cp, int64_t nchunks, hipStream_t st)
 {
     size_t lds = core128_lds_bytes(pl, RQ, NT, WPB, PAIR);
-#ifdef HSS_LDS_PAD                                       // development: one block per CU whatever its size
-    if (lds < 100 * 1024) lds = 100 * 1024;
-#endif
     auto kern = hssfsst::fsst_core128_kernel<NT, RQ, kFpw128, FAST, WPB, S1C, false, false, PAIR, RAGGED>;
     static std::atomic<unsigned long long> lds_ok{0};
     if (int rc = allow_full_lds(kern, pl->device, lds_ok)) return rc;
@@ -644,7 +607,7 @@ int launch_team16(hssfsst_plan* pl, const hssfsst::Core128Params& cp, int64_t ba
     // (at least 84 KiB: one block per CU whatever its size -- the teams count on it)
     constexpr int PSLOTS = t16_pslots<KLO, KC>();        // signals whose partials a CU keeps in LDS at a time
     constexpr int MS = t16_slots<KLO, KC>();             // statistics / mailbox slots the kernel's LDS has room for
-    size_t lds = (kCanonLdsTabFloats + t16_ctl_floats(PSLOTS, MS) + static_cast<size_t>(WPB) * CanonCfg<KLO, KC>::wave_floats(t16_planes<KLO, KC>())) * sizeof(float);
+    size_t lds = (kCanonLdsTabFloats + t16_ctl_floats(PSLOTS, MS) + static_cast<size_t>(WPB) * CanonCfg<KLO, KC>::wave_floats()) * sizeof(float);
     if (lds > static_cast<size_t>(kMaxLdsBytes)) return 0;
     if (lds < 84 * 1024) lds = 84 * 1024;
     auto kern = team16_kernel<KLO, KC, WPB, DEPTH, OT>();
@@ -658,17 +621,15 @@ int launch_team16(hssfsst_plan* pl, const hssfsst::Core128Params& cp, int64_t ba
     }
     if (pl->team16_cus < 1) return 0;
     // team size: the smallest power of two that leaves a CU at most 16 groups of a signal (its 16 waves then have all of them in
-    // flight at once and the kernel's progress argument holds); HSSFSST_TEAM=n overrides upwards (A/B)
-    const int team_env = debug_switches().team;
+    // flight at once and the kernel's progress argument holds)
     int T = 1;
     while ((WPB / 2) * T < G) T *= 2;                    // (cpc <= WPB is the kernel's progress argument; cpc <= WPB / 2 measured faster:
                                                          //  a signal's groups are handed out within half a round of the CU's waves)
-    if (team_env > T) { int t2 = T; while (2 * t2 <= team_env && 2 * t2 <= G) t2 *= 2; T = t2; }
     if (T > pl->team16_cus || T > 64) return 0;
     int cpc = 1, cpc_shift = 0;                          // list positions per CU and signal (power of two; surplus ones are skipped)
     while (cpc * T < G) { cpc *= 2; ++cpc_shift; }
     if (cpc > WPB || cpc > kT16MaxCpc || G / T < 1) return 0;
-    if (cpc < 4 && T > 1) return 0;                      // (a CU publishes whole blocks of four groups: HSSFSST_TEAM beyond G / 4)
+    if (cpc < 4 && T > 1) return 0;                      // (a CU publishes whole blocks of four groups)
     // as many teams as the chip has room for, but no more than there are signals: the dataset loop's one frame per call
     // (/root/reference/hss/datasets/heart_sounds.py:166-168) starts one team's 16 blocks, not 256 of which 240 find nothing to do
     int nteams = pl->team16_cus / T;
@@ -678,7 +639,7 @@ int launch_team16(hssfsst_plan* pl, const hssfsst::Core128Params& cp, int64_t ba
     if (cp.xstride < 1 || cp.xstride > 0x7fffffffLL || batch > 0x7fffffffLL) return 0;      // (the kernel's 32-bit signal index and stride)
     // slots: a CU runs at most held_pos list positions ahead of its oldest unresolved signal = lead signals; a slot is reused
     // 2 lead + 2 signals later at the earliest (fsst_team16.hpp "Progress")
-    const int held_pos = WPB * (DEPTH + 2 + t16_planes<KLO, KC>());   // list positions a CU's waves hold: DEPTH held (+ one in its plane) + transformed + landed + drawn each
+    const int held_pos = WPB * (DEPTH + 3);             // list positions a CU's waves hold: DEPTH held + transformed + landed + drawn each
     const int lead = (held_pos + G / T - 1) / (G / T) + 1;
     int slots = 8;
     while (slots < 2 * lead + 2) slots *= 2;
@@ -705,8 +666,7 @@ int launch_team16(hssfsst_plan* pl, const hssfsst::Core128Params& cp, int64_t ba
         const double total = static_cast<double>(KC) * static_cast<double>(cp.ncols);
         tp.inv_total = 1.0 / total; tp.inv_total1 = 1.0 / (total - 1.0);
     }
-    const unsigned spin_us = debug_switches().team_spin_us;
-    tp.spin_ticks = (spin_us < 10u ? 10u : spin_us > 10000000u ? 10000000u : spin_us) * 100u;
+    tp.spin_ticks = 500u * 100u;                         // a wait gives up after 500 us (100 MHz ticks)
     if ((rc = ensure_team_words(pl, st)) != 0) return rc;
     if (++pl->team_launch == 0u) pl->team_launch = 1u;
     tp.abort_word = pl->d_arrive.get() + 1; tp.fallbacks = pl->d_fallback; tp.launch = pl->team_launch;
@@ -922,15 +882,11 @@ int launch_core128_plain(hssfsst_plan* pl, const hssfsst::Core128Params& cp, int
     const size_t per_wave = static_cast<size_t>(hssfsst::wave_lds_floats(kFpw128, pl->klo, pl->K, rq, nt)) * sizeof(float);
     const size_t room = 160 * 1024;
     if (nt == 16 && rq == 8) {
-#ifdef HSS_WPB_CANON
-        if (fast && canon) return launch_core128_wpb<16, 8, true, HSS_WPB_CANON, 3, false, RAGGED>(pl, cp, nchunks, st);
-#endif
         if (fast && canon) return launch_core128_wpb<16, 8, true, 16, 3, false, RAGGED>(pl, cp, nchunks, st);
         if (fast) return launch_core128_wpb<16, 8, true, 16, -1, false, RAGGED>(pl, cp, nchunks, st);   // K <= 24: 16 regions always fit
         if (fixed + 16 * per_wave <= room) return launch_core128_wpb<16, 8, false, 16, -1, false, RAGGED>(pl, cp, nchunks, st);
         if (fixed + 8 * per_wave <= room) return launch_core128_wpb<16, 8, false, 8, -1, false, RAGGED>(pl, cp, nchunks, st);
         if (fixed + 4 * per_wave <= room) return launch_core128_wpb<16, 8, false, 4, -1, false, RAGGED>(pl, cp, nchunks, st);
-#ifndef HSS_DEV_ONLY128
     } else if (nt == 16 && rq == 16) {                                               // nwin = 256
         // (wave pairs -- fsst_mfma128.hpp "PAIR" -- lose here: 16 waves at 128 registers spill, core 0.770 vs 0.587 ms per 1024
         //  windows; 12 waves at 170 registers: 0.739 ms)
@@ -955,7 +911,6 @@ int launch_core128_plain(hssfsst_plan* pl, const hssfsst::Core128Params& cp, int
         if (!fast && fixed + 3 * per_wave <= room) return launch_core128_wpb<32, 16, false, 3, -1, false, RAGGED>(pl, cp, nchunks, st);
         if (!fast && fixed + 2 * per_wave <= room) return launch_core128_wpb<32, 16, false, 2, -1, false, RAGGED>(pl, cp, nchunks, st);
         if (fast && fixed + 2 * per_wave <= room) return launch_core128_wpb<32, 16, true, 2, -1, false, RAGGED>(pl, cp, nchunks, st);
-#endif
     }
     return fail(HSSFSST_EUNSUPPORTED, "LDS request %zu B per wave exceeds the 160 KiB budget", per_wave);
 }
@@ -1004,11 +959,11 @@ int launch_core128(hssfsst_plan* pl, const float* dx, long long xstride, float* 
         const bool paused = pl->team_pause > 0 && !team_only;
         if (paused && canon16 && !no_team) --pl->team_pause;
         if (!no_team && canon16 && !paused) {
-            rc = canon_dispatch(pl, [&](auto KL, auto KN) {
+            rc = canon_dispatch(pl, [&](auto KL, auto KN) {      // (16 waves per block, two held groups per wave)
                 constexpr int kl = decltype(KL)::value, kn = decltype(KN)::value;
-                if (pl->out_dtype == HSSFSST_DTYPE_F16) return launch_team16<kl, kn, HSS_T16_WPB, HSS_T16_DEPTH, _Float16>(pl, cp, batch, ngroups, st, hout);
-                if (pl->out_dtype == HSSFSST_DTYPE_BF16) return launch_team16<kl, kn, HSS_T16_WPB, HSS_T16_DEPTH, __bf16>(pl, cp, batch, ngroups, st, hout);
-                return launch_team16<kl, kn, HSS_T16_WPB, HSS_T16_DEPTH>(pl, cp, batch, ngroups, st);
+                if (pl->out_dtype == HSSFSST_DTYPE_F16) return launch_team16<kl, kn, 16, 2, _Float16>(pl, cp, batch, ngroups, st, hout);
+                if (pl->out_dtype == HSSFSST_DTYPE_BF16) return launch_team16<kl, kn, 16, 2, __bf16>(pl, cp, batch, ngroups, st, hout);
+                return launch_team16<kl, kn, 16, 2>(pl, cp, batch, ngroups, st);
             });
             if (rc == 1) {
                 // the team kernel may give the launch up (its blocks wait for each other; other processes on the GPU can keep
@@ -1017,11 +972,7 @@ int launch_core128(hssfsst_plan* pl, const float* dx, long long xstride, float* 
                 pl->last_zpath = 2;
                 if (int rce = timing_event(pl, st)) return rce;      // the kernel's own time: the closing event goes in front of the gated launches
                 pl->timing_closed = pl->timing != 0;
-#ifdef HSS_NO_GATE                                        // development: what the gated launch behind every team launch costs (UNSAFE: no fallback)
-                if (true) {
-#else
                 if (pl->defer_fallback) {                // (exec_impl: a host-output exec synchronises anyway and checks the give-up word then)
-#endif
                     if (pl->deferred_launch == 0u) pl->deferred_first = pl->team_launch;
                     pl->deferred_launch = pl->team_launch;
                     *did_fuse = true;
@@ -1055,7 +1006,6 @@ int launch_core128(hssfsst_plan* pl, const float* dx, long long xstride, float* 
         if (rc < 0) return rc;
         if (rc == 1) { *did_fuse = true; pl->last_zpath = 1; return 0; }
     }
-#ifndef HSS_DEV_ONLY128
     if (try_fused && !half && !fast && rq == 16 && pl->mode == HSSFSST_MODE_STACK && pl->zpath_pref != HSSFSST_ZPATH_TEAM) {
         // nwin 256 / 512 (general epilogue): one CU per signal, the z-score as tickets of the same launch; waves per block
         // as on the two-launch path (what fits the LDS: 8 for the canonical band at 256 points, 3 at 512)
@@ -1068,7 +1018,6 @@ int launch_core128(hssfsst_plan* pl, const float* dx, long long xstride, float* 
         if (rc < 0) return rc;
         if (rc == 1) { *did_fuse = true; pl->last_zpath = 1; return 0; }
     }
-#endif
     if (canon16) return launch_canon(pl, cp, nchunks, st);
     return launch_core128_plain<false>(pl, cp, nchunks, st, fast, canon);
 }
@@ -1076,38 +1025,8 @@ int launch_core128(hssfsst_plan* pl, const float* dx, long long xstride, float* 
 }  // namespace
 
 extern "C" {
-#ifdef HSS_FUSE_PROBE
-// development: read and clear the ticket probes of fsst_canon_kernel<.., true> (fsst_canon128.hpp)
-int hssfsst_dev_fuse_probe(unsigned long long* out8)
-{
-    unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (hipDeviceSynchronize() != hipSuccess) return -1;
-    if (hipMemcpyFromSymbol(out8, HIP_SYMBOL(hssfsst::g_fuse_probe), sizeof(z)) != hipSuccess) return -1;
-    if (hipMemcpyToSymbol(HIP_SYMBOL(hssfsst::g_fuse_probe), z, sizeof(z)) != hipSuccess) return -1;
-    return 0;
-}
-#endif
-
-#ifdef HSS_STREAM_PROBE
-int hssfsst_dev_stream_probe(unsigned long long* out, int nwaves)      // out[nwaves][8] of the last launch; cleared
-{
-    if (nwaves > hssfsst::kStreamProbeWaves) nwaves = hssfsst::kStreamProbeWaves;
-    if (hipDeviceSynchronize() != hipSuccess) return -1;
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(hssfsst::g_stream_probe), sizeof(unsigned long long) * 8 * nwaves) != hipSuccess) return -1;
-    std::vector<unsigned long long> z(static_cast<size_t>(hssfsst::kStreamProbeWaves) * 8, 0ull);
-    if (hipMemcpyToSymbol(HIP_SYMBOL(hssfsst::g_stream_probe), z.data(), z.size() * sizeof(unsigned long long)) != hipSuccess) return -1;
-    return 0;
-}
-#endif
 
 int hssfsst_version(void) { return HSSFSST_VERSION; }
-#ifdef HSS_T16_BLKPROBE      // development only (tools/blk_probe.py)
-int hssfsst_dev_t16_blk(unsigned* out)
-{
-    if (hipDeviceSynchronize() != hipSuccess) return -1;
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(hssfsst::g_t16_blk), sizeof(unsigned) * 256 * 16 * 8) == hipSuccess ? 0 : -2;
-}
-#endif
 const char* hssfsst_last_error(void) { return g_err; }
 
 int hssfsst_device_count(void)
@@ -1242,8 +1161,7 @@ int hssfsst_plan_create_ex(hssfsst_plan** out, int device, int nwin, const doubl
         if ((rc = p->d_wtab.upload(wt.data(), wt.size())) != 0) return rc;
     }
     const bool force_generic = debug_switches().force_generic;
-    const bool mfma_long = !debug_switches().no_mfma256;   // A/B: nwin 256 / 512 on the generic kernel
-    bool use_mfma = !p->dft && (nwin == 128 || ((nwin == 256 || nwin == 512) && mfma_long)) && !force_generic;
+    bool use_mfma = !p->dft && (nwin == 128 || nwin == 256 || nwin == 512) && !force_generic;
     if (p->dft) {
         // A[i][k] of v_mfma_f32_16x16x4_f32 for source block blk, k-step ks: lane l holds row i = l & 15, k = l >> 4.
         // Row i: source k' = 4 blk + (i >> 2), component i & 3 of {V.re, V.im, Vd'.re, Vd'.im}; tap n = 4 ks + k:
@@ -1790,11 +1708,9 @@ static int exec_impl(hssfsst_plan* p, const float* x, int64_t batch, int n, int6
     } else switch (p->R) {
         case 1: rc = launch_core<1>(p, cp, nblocks, st); break;
         case 2: rc = launch_core<2>(p, cp, nblocks, st); break;
-#ifndef HSS_DEV_ONLY128
         case 4: rc = launch_core<4>(p, cp, nblocks, st); break;
         case 8: rc = launch_core<8>(p, cp, nblocks, st); break;
         case 16: rc = launch_core<16>(p, cp, nblocks, st); break;
-#endif
         default: rc = fail(HSSFSST_EUNSUPPORTED, "exec: unsupported radix %d", p->R);
     }
     if (rc != 0) return rc;
@@ -1805,23 +1721,17 @@ static int exec_impl(hssfsst_plan* p, const float* x, int64_t batch, int n, int6
     p->last_fused = (did_fuse || gate != nullptr) ? 1 : 0;
     if (p->mode == HSSFSST_MODE_STACK && !did_fuse) {
         float4* stats = reinterpret_cast<float4*>(p->d_stats.get());
-        const int zgrid_env = debug_switches().zgrid;
-        const bool split_stats = debug_switches().split_stats;   // A/B: separate statistics launch
-        int64_t zgrid = zgrid_env > 0 ? zgrid_env : 4096;
+        int64_t zgrid = 4096;
         // small batches: several blocks per signal, else one block per signal would leave most CUs idle
         int slices = 1;
-        const int zslices_env = debug_switches().zslices;
-        if (zslices_env > 0) {
-            slices = zslices_env;
-            zgrid = batch * slices;
-        } else if (zgrid_env <= 0 && batch < 1024) {
+        if (batch < 1024) {
             slices = static_cast<int>(1024 / batch);
             if (slices > 32) slices = 32;
         }
         if (zgrid > batch * slices) zgrid = batch * slices;
         // big batches, a block per signal: it reduces the signal's partials itself (no separate statistics
         // launch, 4-7 us per step); otherwise a tiny kernel does all reductions at once
-        const bool fused = !split_stats && slices == 1 && zgrid == batch && batch >= 512;
+        const bool fused = slices == 1 && zgrid == batch && batch >= 512;
         if (!fused)
             hipLaunchKernelGGL(hssfsst::fsst_stats_kernel, dim3(static_cast<unsigned>(batch)), dim3(64), 0, st,
                                cp.partials, stats, nblk, fpp, ncols, p->K, gate, gate_val);

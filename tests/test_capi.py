@@ -26,8 +26,8 @@ def test_every_declared_symbol_is_exported(built_lib):
 
 
 def test_exported_symbols_are_exactly_the_header(built_lib):
-    """The shipped library exports the C ABI of include/hssfsst.h and nothing else under that prefix: no development entry
-    points (hssfsst_dev_*: they exist only in -DHSS_DEV builds, tools/dev.sh)."""
+    """The shipped library exports the C ABI of include/hssfsst.h and nothing else under that prefix: no entry point that the
+    header does not declare."""
     import shutil
     import subprocess
     nm = shutil.which("nm") or "/opt/rocm/lib/llvm/bin/llvm-nm"

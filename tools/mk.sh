@@ -1,5 +1,11 @@
 #!/bin/bash
-# usage: tools/mk.sh <output.so> [extra hipcc flags]  -- builds libhssfsst from anywhere
+# usage: tools/mk.sh <output.so> [extra hipcc flags]  -- builds libhssfsst with the release flags of _lib.build() (from anywhere; a relative
+# output path is taken from the current directory) and prints VGPRs, scratch bytes per lane and SGPR spills of every kernel
+set -o pipefail
 out=$1; shift
 R=$(cd "$(dirname "$0")/.." && pwd)                     # the repository this script lives in
-cd "$R/heart_sounds_segmentation_amd/csrc" && hipcc --offload-arch=gfx950 -O3 -std=c++17 -shared -fPIC "$@" -o "$out" hssfsst.hip -Rpass-analysis=kernel-resource-usage 2>&1 | grep -E "error|core128" -A9 | grep -E "error|VGPRs:|Scratch|Occupancy"
+hipcc --offload-arch=gfx950 -O3 -std=c++17 -shared -fPIC "$@" -o "$out" "$R/heart_sounds_segmentation_amd/csrc/hssfsst.hip" \
+      -Rpass-analysis=kernel-resource-usage 2>&1 |
+    grep -E "error|Function Name|VGPRs:|ScratchSize|SGPRs Spill" | grep -v "AGPRs\|VGPRs Spill" | sed 's/.*remark: *//; s/ \[-Rpass.*//' |
+    awk '/error/{print} /Function Name/{n=$3} /^ *VGPRs:/{v=$2} /ScratchSize/{sc=$3} /SGPRs Spill/{printf "%-100s vgpr %3s scratch %4s sgpr-spill %s\n", substr(n,1,100), v, sc, $3}' |
+    sed 's/_ZN7hssfsst//'

@@ -1,5 +1,5 @@
 #!/bin/bash
-# usage: bash tools/pmc_lib.sh <tag> lib.so [lib2.so ...]  -- per-16-frame-group instruction mix of the team kernel of development builds
+# usage: bash tools/pmc_lib.sh <tag> lib.so [lib2.so ...]  -- per-16-frame-group instruction mix of the team kernel of any builds (tools/mk.sh)
 # (rocprofv3 --pmc, two passes per build, 8 execs of the C2 workload each; per group = per dispatch / 128000)
 tag=$1; shift
 R=$(pwd); cd /tmp && export TMPDIR=/tmp; cd $R

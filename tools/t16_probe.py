@@ -39,18 +39,6 @@ def main():
         t = (ms[0] + ms[1]) / cnt.value
         print(f"round {rd}: {B}x{n} {t:.4f} ms/exec (core {ms[0] / cnt.value:.4f})  {B / t / 1e3:.3f} Mwin/s  {(8000 + 352000) * (n / 2000) * B / (t * 1e-3) / 8e12 * 100:.2f}% of 8 TB/s  "
               f"zpath={L.hssfsst_plan_last_exec_fused(plan)} fallbacks={fb}  wall {_wall:.4f} ms/exec", flush=True)
-        if hasattr(L, "hssfsst_dev_t16_probe"):
-            buf = (ctypes.c_ulonglong * 16)()
-            L.hssfsst_dev_t16_probe(buf)
-            wv = max(buf[12], 1)
-            if os.environ.get("T16_WAITS"):
-                if buf[6]:
-                    print(f"   resolves {buf[6]}: copy {buf[4] / buf[6] / 100:.2f} us in {buf[7] / buf[6]:.2f} looks, sums {buf[5] / buf[6] / 100:.2f} us each", flush=True)
-                print(f"   per wave: blocked {buf[0] / wv / 100:.1f} us in {buf[1] / wv:.1f} waits ({buf[0] / max(buf[1], 1) / 100:.2f} us each), found ready {buf[2] / wv:.1f} times, lifetime {buf[3] / wv / 100:.1f} us", flush=True)
-                continue
-            names = ["transform", "land", "stats+publish+draw", "emit", "wait(all)", "resolver poll", "resolver compute", "image", "loop top"]
-            print("   per wave (cycles): " + "  ".join(f"{nm} {buf[k] / wv:.0f}" for k, nm in enumerate(names)) +
-                  f" | lifetime {buf[11] / wv:.0f} resolves/wave {buf[9] / wv:.2f} groups/wave {buf[10] / wv:.1f}", flush=True)
 
 
 if __name__ == "__main__":
