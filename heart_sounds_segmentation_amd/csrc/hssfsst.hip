@@ -296,13 +296,11 @@ struct hssfsst_plan {
     unsigned team_seq = 0;                                   // launch sequence number (upper half of the mailbox tags)
     DevBuf<unsigned> d_arrive; unsigned arrive_total = 0;    // team kernel: [0] arrival counter (and its value after the launches so far), [1] abort word, [2] blocks done
     unsigned done_total = 0;                                 // ... [2]'s value after the flagged launches so far
-    bool flag_done = false; unsigned flag_launch = 0;        // exec_impl asks the next team launch to say in pinned host memory (h_fallback[2]) when its last wave is done; that launch
     unsigned team_launch = 0;                                // identity of the last team launch (never 0)
     volatile unsigned* h_fallback = nullptr; unsigned* d_fallback = nullptr;   // pinned host word: identity of the last team launch that gave up
     unsigned seen_fallback = 0; int fallbacks = 0;           // ... as last seen by the host, and how many distinct ones
     int giveups_in_a_row = 0, team_pause = 0;                // a GPU shared with many processes: after kTeamGiveUps give-ups in a row the team kernel sits out
                                                              // the plan's next kTeamPause execs that would take it (each give-up costs its 0.5 ms bound first)
-    const unsigned* gate = nullptr; unsigned gate_val = 0;   // set by a team launch: the two-launch kernels that follow it in the same exec are its gated fallback
     int team16_cus = 0;                                      // CUs usable by the team kernel (fsst_team16.hpp; 0 = not queried yet, -1 = none)
     char last_kernel[112] = "";                              // the transform kernel of the last exec: instantiation, waves per block, grid (hssfsst_plan_last_kernel)
     int last_fused = 0;                                      // the last exec ran a single-launch z-score kernel
@@ -323,8 +321,6 @@ struct hssfsst_plan {
     std::array<PoolBuf, kPinPoolMax> pin_pool;              // hssfsst_exec_pinned: pinned, device-mapped result buffers lent to the caller
     std::mutex pin_mu;                                       // ... guards `used` and the buffers' replacement (hssfsst_pinned_release may
                                                              // come from another host thread)
-    bool defer_fallback = false;                             // this exec synchronises before it returns: no gated launches behind a team launch,
-    unsigned deferred_launch = 0, deferred_first = 0;        // the host looks at the pinned give-up word afterwards and redoes the exec itself
     DevBuf<long long> d_starts;                              // frame-list staging (hssfsst_exec_list with host starts)
     DevBuf<float> d_frames;                                  // frames gathered from a list, dense [batch][n]
     // hssfsst_exec_ragged: the list's tables -- RaggedSignal[batch], z-score unit starts int[batch + 1], chunk list int2[] -- made
@@ -336,10 +332,8 @@ struct hssfsst_plan {
     size_t rtab_unit = 0, rtab_chunk = 0;                    // byte offsets of the unit starts and of the chunk list in the tables
     long long rtab_nchunks = 0, rtab_nunits = 0;
     hipEvent_t rtab_ev = nullptr;                            // the last upload of h_rtab (h_rtab is not rewritten before it is done)
-    int timing = 0;               // the exec being queued records kernel events
     int timing_every = 0;         // hssfsst_plan_set_timing(n): every n-th exec is timed (0: off)
     unsigned timing_seq = 0;
-    bool timing_closed = false;   // the exec being queued has already recorded its closing kernel event (team path: right behind the team kernel)
     std::vector<hipEvent_t> ev;   // per timed exec: (before, after) per core launch + one closing event
     size_t ev_used = 0;           // events used since timing was enabled
     std::vector<int> ev_chunks;   // core launches of each timed exec
@@ -361,21 +355,63 @@ int allow_full_lds(Kern kern, int device, std::atomic<unsigned long long>& done)
     return 0;
 }
 
+// Resident blocks of `kern` (threads per block, dynamic LDS) on the plan's device, asked once and kept in `cache` (0 = not asked
+// yet; launchers that share a cache share the first answer).  whole_cus: one block per CU -- the CU count, or -1 when the kernel
+// does not fit; otherwise blocks per CU x CUs, each factor at least 1.
+template <class Kern>
+int resident_blocks(const hssfsst_plan* pl, int& cache, Kern kern, int threads, size_t lds, bool whole_cus)
+{
+    if (cache != 0) return 0;
+    int per_cu = 0, cus = 0;
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kern), threads, lds));
+    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, pl->device));
+    cache = whole_cus ? ((per_cu >= 1 && cus >= 1) ? cus : -1) : std::max(per_cu, 1) * std::max(cus, 1);
+    return 0;
+}
+
+// One exec's launch state: made on the stack by exec_impl / hssfsst_exec_ragged and handed to the launchers.  Nothing of it
+// outlives the exec; what the C ABI reports afterwards goes to the plan in one place (exec_report).
+struct ExecCtx {
+    hipStream_t st = nullptr;
+    // in
+    int zpref = HSSFSST_ZPATH_AUTO;           // the z-score path preference this exec runs under (the plan's; ONE_CU for a redo)
+    bool host_waits = false;                  // this exec synchronises before it returns: no gated launches behind a team launch, the host
+                                              // looks at the pinned give-up word afterwards and redoes the exec itself
+    bool want_done_word = false;              // the team launch is asked to say in pinned host memory (h_fallback[2]) when its last wave is done
+    // set by launch_core128 behind a team launch: the kernels that follow it in the same exec are its gated fallback
+    const unsigned* gate = nullptr; unsigned gate_val = 0;
+    // out
+    unsigned team_launch = 0;                 // identity of this exec's team launch (at most one), or 0
+    unsigned flagged_launch = 0;              // ... when it was asked for its done word, else 0
+    bool fused = false;                       // the z-score was part of the launches so far (no statistics + z-score launches to add)
+    int zpath = 0;                            // ... by which path: 1 = one CU per signal, 2 = team kernel
+    char kernel[sizeof(hssfsst_plan::last_kernel)] = "";     // the transform kernel: instantiation, waves per block, grid
+    bool timing = false;                      // this exec records kernel events
+    bool timing_closed = false;               // ... and has recorded its closing kernel event already (team path: right behind the team kernel)
+};
+
 // which kernel instantiation the exec that is being queued runs (hssfsst_plan_last_kernel: the dispatch made observable)
-void name_kernel(hssfsst_plan* pl, int waves, long long grid, const char* fmt, ...)
+void name_kernel(char (&name)[sizeof(hssfsst_plan::last_kernel)], int waves, long long grid, const char* fmt, ...)
 {
     va_list ap;
     va_start(ap, fmt);
-    const int k = vsnprintf(pl->last_kernel, sizeof(pl->last_kernel), fmt, ap);
+    const int k = vsnprintf(name, sizeof(name), fmt, ap);
     va_end(ap);
-    if (k > 0 && static_cast<size_t>(k) < sizeof(pl->last_kernel))
-        snprintf(pl->last_kernel + k, sizeof(pl->last_kernel) - static_cast<size_t>(k), " [%d waves/block, grid %lld]", waves, grid);
+    if (k > 0 && static_cast<size_t>(k) < sizeof(name))
+        snprintf(name + k, sizeof(name) - static_cast<size_t>(k), " [%d waves/block, grid %lld]", waves, grid);
+}
+
+void exec_report(hssfsst_plan* p, const ExecCtx& cx)
+{
+    std::memcpy(p->last_kernel, cx.kernel, sizeof(p->last_kernel));
+    p->last_fused = (cx.fused || cx.team_launch != 0u) ? 1 : 0;      // (a team launch whose gated fallback is two launches counts as fused too)
+    p->last_zpath = cx.zpath;
 }
 
 int out_floats_per_sample(const hssfsst_plan* p) { return p->mode == HSSFSST_MODE_ABS ? p->K : 2 * p->K; }
 
 template <int R>
-int launch_core(hssfsst_plan* pl, hssfsst::CoreParams cp, long long nblocks, hipStream_t st)
+int launch_core(hssfsst_plan* pl, ExecCtx& cx, hssfsst::CoreParams cp, long long nblocks)
 {
     constexpr int NWIN = 32 * R;
     constexpr int XS = ((kTile + NWIN - 1 + 3) / 4) * 4;
@@ -392,8 +428,8 @@ int launch_core(hssfsst_plan* pl, hssfsst::CoreParams cp, long long nblocks, hip
     auto kern = hssfsst::fsst_core_kernel<R, kTile>;
     static std::atomic<unsigned long long> lds_ok{0};
     if (int rc = allow_full_lds(kern, pl->device, lds_ok)) return rc;
-    name_kernel(pl, 1, nblocks, "fsst_core_kernel<%d, %d>", R, kTile);
-    hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(nblocks)), dim3(kTile), lds, st, cp);
+    name_kernel(cx.kernel, 1, nblocks, "fsst_core_kernel<%d, %d>", R, kTile);
+    hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(nblocks)), dim3(kTile), lds, cx.st, cp);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -408,32 +444,25 @@ inline size_t core128_lds_bytes(const hssfsst_plan* pl, int rq, int nt, int wpb,
 
 int ensure_status(hssfsst_plan* pl);
 template <int NT, int RQ, bool FAST, int WPB, int S1C = -1, bool PAIR = false, bool RAGGED = false>
-int launch_core128_wpb(hssfsst_plan* pl, const hssfsst::Core128Params& cp, int64_t nchunks, hipStream_t st)
+int launch_core128_wpb(hssfsst_plan* pl, ExecCtx& cx, const hssfsst::Core128Params& cp, int64_t nchunks)
 {
     size_t lds = core128_lds_bytes(pl, RQ, NT, WPB, PAIR);
     auto kern = hssfsst::fsst_core128_kernel<NT, RQ, kFpw128, FAST, WPB, S1C, false, false, PAIR, RAGGED>;
     static std::atomic<unsigned long long> lds_ok{0};
     if (int rc = allow_full_lds(kern, pl->device, lds_ok)) return rc;
     int& slots = RAGGED ? pl->ragged_slots : pl->core128_slots;
-    if (slots == 0) {                                    // persistent grid = what is resident at once
-        int per_cu = 0, cus = 0;
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kern), 64 * WPB, lds));
-        HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, pl->device));
-        if (per_cu < 1) per_cu = 1;
-        if (cus < 1) cus = 1;
-        slots = per_cu * cus;
-    }
+    if (int rc = resident_blocks(pl, slots, kern, 64 * WPB, lds, false)) return rc;     // persistent grid = what is resident at once
     int64_t blocks = nchunks;                            // small launches: one chunk per block, spread over the CUs
     if (blocks > slots) blocks = slots;
-    name_kernel(pl, WPB, blocks, "fsst_core128_kernel<%d, %d, %d, %s, %d, %d, false%s%s>", NT, RQ, kFpw128, FAST ? "true" : "false", WPB, S1C,
+    name_kernel(cx.kernel, WPB, blocks, "fsst_core128_kernel<%d, %d, %d, %s, %d, %d, false%s%s>", NT, RQ, kFpw128, FAST ? "true" : "false", WPB, S1C,
                 PAIR ? ", pairs" : "", RAGGED ? ", ragged" : "");
     if constexpr (PAIR) {                                // (a pair's bounded wait reports through the status word)
         if (int rcs = ensure_status(pl)) return rcs;
         hssfsst::Core128Params cq = cp;
         cq.status = pl->d_status;
-        hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(blocks)), dim3(64 * WPB), lds, st, cq);
+        hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(blocks)), dim3(64 * WPB), lds, cx.st, cq);
     } else
-    hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(blocks)), dim3(64 * WPB), lds, st, cp);
+    hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(blocks)), dim3(64 * WPB), lds, cx.st, cp);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -453,12 +482,7 @@ int launch_stream(hssfsst_plan* pl, float* tape_at, long long tape_len, const fl
     auto kern = hssfsst::fsst_core128_kernel<NT, RQ, kFpw128, true, WPB, -1, false, true, PAIR>;
     static std::atomic<unsigned long long> lds_ok{0};
     if (int rc = allow_full_lds(kern, pl->device, lds_ok)) return rc;
-    if (pl->stream_slots == 0) {
-        int per_cu = 0, cus = 0;
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kern), 64 * WPB, lds));
-        HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, pl->device));
-        pl->stream_slots = (per_cu < 1 ? 1 : per_cu) * (cus < 1 ? 1 : cus);
-    }
+    if (int rc = resident_blocks(pl, pl->stream_slots, kern, 64 * WPB, lds, false)) return rc;
     if (state && pl->d_stream_arrive.cap < static_cast<size_t>(channels)) {
         if (int rc = pl->d_stream_arrive.grow(static_cast<size_t>(channels))) return rc;
         HIP_TRY(hipMemsetAsync(pl->d_stream_arrive.get(), 0, static_cast<size_t>(channels) * sizeof(unsigned), st));
@@ -478,7 +502,7 @@ int launch_stream(hssfsst_plan* pl, float* tape_at, long long tape_len, const fl
     cp.xnew = x_new_dev; cp.xnew_stride = x_stride; cp.hist = pl->nwin - 1; cp.bpc = bpc; cp.state = state; cp.arrive = pl->d_stream_arrive.get(); cp.pieces = pl->d_stream_pieces.get(); cp.mirror = mirror;
     const long long grid = static_cast<long long>(channels) * bpc;
     cp.status = pl->d_status;
-    name_kernel(pl, WPB, grid, "fsst_core128_kernel<%d, %d, %d, true, %d, -1, false, stream%s>", NT, RQ, kFpw128, WPB, PAIR ? ", pairs" : "");
+    name_kernel(pl->last_kernel, WPB, grid, "fsst_core128_kernel<%d, %d, %d, true, %d, -1, false, stream%s>", NT, RQ, kFpw128, WPB, PAIR ? ", pairs" : "");
     hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(grid)), dim3(64 * WPB), lds, st, cp);
     HIP_TRY(hipGetLastError());
     return 1;
@@ -488,7 +512,7 @@ int launch_stream(hssfsst_plan* pl, float* tape_at, long long tape_len, const fl
 // per CU, every CU owns whole signals.  Returns 1 when it launched, 0 when this exec should take the two-kernel path
 // (signal too long for the LDS partials, or a batch that would leave CUs idle for a whole signal), < 0 on error.
 template <int S1C>
-int launch_fused128(hssfsst_plan* pl, hssfsst::Core128Params cp, int64_t batch, int ngroups, hipStream_t st)
+int launch_fused128(hssfsst_plan* pl, ExecCtx& cx, hssfsst::Core128Params cp, int64_t batch, int ngroups)
 {
     constexpr int WPB = 16;
     if (ngroups > hssfsst::kFusedMaxGroups || (ngroups + kFpw128 / 16 - 1) / (kFpw128 / 16) < hssfsst::kFusedMinChunks) return 0;
@@ -498,12 +522,7 @@ int launch_fused128(hssfsst_plan* pl, hssfsst::Core128Params cp, int64_t batch, 
     auto kern = hssfsst::fsst_core128_kernel<16, 8, kFpw128, true, WPB, S1C, true>;
     static std::atomic<unsigned long long> lds_ok{0};
     if (int rc = allow_full_lds(kern, pl->device, lds_ok)) return rc;
-    if (pl->fused_slots == 0) {
-        int per_cu = 0, cus = 0;
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kern), 64 * WPB, lds));
-        HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, pl->device));
-        pl->fused_slots = (per_cu >= 1 && cus >= 1) ? cus : -1;       // one block per CU
-    }
+    if (int rc = resident_blocks(pl, pl->fused_slots, kern, 64 * WPB, lds, true)) return rc;       // one block per CU
     if (pl->fused_slots < 1) return 0;
     // signals are dealt to the blocks round-robin and a signal is never split: the last round must be nearly full
     // (a quarter-full last round of 4 costs 4 / 3.25 = 23 %), otherwise the chunk-balanced two-kernel path wins
@@ -512,8 +531,8 @@ int launch_fused128(hssfsst_plan* pl, hssfsst::Core128Params cp, int64_t batch, 
     if (batch < grid || rounds * grid * 100 > batch * 112) return 0;
     if (int rcs = ensure_status(pl)) return rcs;
     cp.status = pl->d_status;
-    name_kernel(pl, WPB, grid, "fsst_core128_kernel<16, 8, %d, true, %d, %d, true>", kFpw128, WPB, S1C);
-    hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(grid)), dim3(64 * WPB), lds, st, cp);
+    name_kernel(cx.kernel, WPB, grid, "fsst_core128_kernel<16, 8, %d, true, %d, %d, true>", kFpw128, WPB, S1C);
+    hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(grid)), dim3(64 * WPB), lds, cx.st, cp);
     HIP_TRY(hipGetLastError());
     return 1;
 }
@@ -521,7 +540,7 @@ int launch_fused128(hssfsst_plan* pl, hssfsst::Core128Params cp, int64_t batch, 
 // The same for the general epilogue (any K: nwin 256 / 512, or nwin 128 with an odd or wide band), STACK only.  The z-score
 // tickets sweep a chunk as float4s: every signal's feature block has to start on a 16-byte boundary.
 template <int NT, int RQ, int WPB, int S1C>
-int launch_fused_general(hssfsst_plan* pl, hssfsst::Core128Params cp, int64_t batch, int ngroups, hipStream_t st)
+int launch_fused_general(hssfsst_plan* pl, ExecCtx& cx, hssfsst::Core128Params cp, int64_t batch, int ngroups)
 {
     if (ngroups > hssfsst::kFusedMaxGroups || (ngroups + kFpw128 / 16 - 1) / (kFpw128 / 16) < hssfsst::kFusedMinChunks) return 0;
     if (((static_cast<long long>(cp.ncols) * 2 * pl->K) & 3) != 0 || (reinterpret_cast<uintptr_t>(cp.out) & 15) != 0) return 0;
@@ -531,20 +550,15 @@ int launch_fused_general(hssfsst_plan* pl, hssfsst::Core128Params cp, int64_t ba
     auto kern = hssfsst::fsst_core128_kernel<NT, RQ, kFpw128, false, WPB, S1C, true>;
     static std::atomic<unsigned long long> lds_ok{0};
     if (int rc = allow_full_lds(kern, pl->device, lds_ok)) return rc;
-    if (pl->fused_slots == 0) {
-        int per_cu = 0, cus = 0;
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kern), 64 * WPB, lds));
-        HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, pl->device));
-        pl->fused_slots = (per_cu >= 1 && cus >= 1) ? cus : -1;       // one block per CU
-    }
+    if (int rc = resident_blocks(pl, pl->fused_slots, kern, 64 * WPB, lds, true)) return rc;       // one block per CU
     if (pl->fused_slots < 1) return 0;
     const int64_t grid = pl->fused_slots;
     const int64_t rounds = (batch + grid - 1) / grid;
     if (batch < grid || rounds * grid * 100 > batch * 112) return 0;  // (as launch_fused128: a nearly full last round)
     if (int rcs = ensure_status(pl)) return rcs;
     cp.status = pl->d_status;
-    name_kernel(pl, WPB, grid, "fsst_core128_kernel<%d, %d, %d, false, %d, %d, true>", NT, RQ, kFpw128, WPB, S1C);
-    hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(grid)), dim3(64 * WPB), lds, st, cp);
+    name_kernel(cx.kernel, WPB, grid, "fsst_core128_kernel<%d, %d, %d, false, %d, %d, true>", NT, RQ, kFpw128, WPB, S1C);
+    hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(grid)), dim3(64 * WPB), lds, cx.st, cp);
     HIP_TRY(hipGetLastError());
     return 1;
 }
@@ -596,9 +610,10 @@ constexpr const char* out_type_suffix() { return sizeof(OT) == 4 ? "" : std::is_
 
 // OT = _Float16 / __bf16: a half plan's team launch; it stores its z-scores as 2-byte elements at hout (8-byte aligned, else 0)
 template <int KLO, int KC, int WPB, int DEPTH, class OT = float>
-int launch_team16(hssfsst_plan* pl, const hssfsst::Core128Params& cp, int64_t batch, int ngroups, hipStream_t st, void* hout = nullptr)
+int launch_team16(hssfsst_plan* pl, ExecCtx& cx, const hssfsst::Core128Params& cp, int64_t batch, int ngroups, void* hout = nullptr)
 {
     using namespace hssfsst;
+    hipStream_t st = cx.st;
     if constexpr (sizeof(OT) == 2) {
         if (hout == nullptr || (reinterpret_cast<uintptr_t>(hout) & 7) != 0) return 0;
     }
@@ -613,12 +628,7 @@ int launch_team16(hssfsst_plan* pl, const hssfsst::Core128Params& cp, int64_t ba
     auto kern = team16_kernel<KLO, KC, WPB, DEPTH, OT>();
     static std::atomic<unsigned long long> lds_ok{0};
     if (int rc = allow_full_lds(kern, pl->device, lds_ok)) return rc;
-    if (pl->team16_cus == 0) {
-        int per_cu = 0, cus = 0;
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kern), 64 * WPB, lds));
-        HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, pl->device));
-        pl->team16_cus = (per_cu >= 1 && cus >= 1) ? cus : -1;
-    }
+    if (int rc = resident_blocks(pl, pl->team16_cus, kern, 64 * WPB, lds, true)) return rc;
     if (pl->team16_cus < 1) return 0;
     // team size: the smallest power of two that leaves a CU at most 16 groups of a signal (its 16 waves then have all of them in
     // flight at once and the kernel's progress argument holds)
@@ -677,15 +687,15 @@ int launch_team16(hssfsst_plan* pl, const hssfsst::Core128Params& cp, int64_t ba
     }
     tp.arrive = pl->d_arrive.get(); tp.arrive_base = pl->arrive_total;
     pl->arrive_total += static_cast<unsigned>(grid);     // (a plan is single-stream: every block of the earlier launches has arrived)
-    pl->flag_launch = 0u;
-    if (pl->flag_done && !force_fallback) {              // (hssfsst_exec_pinned & co: the host waits for this exec alone)
+    if (cx.want_done_word && !force_fallback) {          // (hssfsst_exec_pinned & co: the host waits for this exec alone)
         tp.done = pl->d_arrive.get() + 2; tp.done_base = pl->done_total; tp.host_done = pl->d_fallback + 2;
         pl->done_total += static_cast<unsigned>(grid);
-        pl->flag_launch = pl->team_launch;
+        cx.flagged_launch = pl->team_launch;
     }
-    name_kernel(pl, WPB, grid, "fsst_team16_kernel<%d, %d, %d, %d%s> teams of %d", KLO, KC, WPB, DEPTH, out_type_suffix<OT>(), T);
+    name_kernel(cx.kernel, WPB, grid, "fsst_team16_kernel<%d, %d, %d, %d%s> teams of %d", KLO, KC, WPB, DEPTH, out_type_suffix<OT>(), T);
     hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(grid)), dim3(64 * WPB), lds, st, tp);
     HIP_TRY(hipGetLastError());
+    cx.team_launch = pl->team_launch;
     return 1;
 }
 
@@ -717,19 +727,19 @@ int canon_dispatch(const hssfsst_plan* pl, F&& f)
     }
 }
 
-hssfsst::CanonParams canon_params(const hssfsst_plan* pl, const hssfsst::Core128Params& cp)
+hssfsst::CanonParams canon_params(const hssfsst_plan* pl, const ExecCtx& cx, const hssfsst::Core128Params& cp)
 {
     hssfsst::CanonParams q{};
     q.x = cp.x; q.out = cp.out; q.partials = cp.partials; q.atab = pl->d_atab16.get(); q.wtab = cp.wtab; q.twtab = cp.twtab;
     q.r2scale_s = pl->canon_r2s; q.inv_c = pl->canon_inv_c;
     q.n = cp.n; q.mode = cp.mode; q.nsig = cp.nsig; q.col0 = cp.col0; q.ncols = cp.ncols; q.xstride = cp.xstride; q.reg = cp.reg;
     q.status = cp.status;
-    q.gate = pl->gate; q.gate_val = pl->gate_val;
+    q.gate = cx.gate; q.gate_val = cx.gate_val;
     return q;
 }
 
 template <int KLO, int KC, bool RAGGED = false>
-int launch_canon_band(hssfsst_plan* pl, const hssfsst::Core128Params& cp, int64_t nchunks, hipStream_t st)
+int launch_canon_band(hssfsst_plan* pl, ExecCtx& cx, const hssfsst::Core128Params& cp, int64_t nchunks)
 {
     constexpr int WPB = 16;
     const size_t lds = (hssfsst::kCanonLdsTabFloats + hssfsst::kCanonCtlFloats + static_cast<size_t>(WPB) * hssfsst::CanonCfg<KLO, KC>::wave_floats()) * sizeof(float);
@@ -737,50 +747,31 @@ int launch_canon_band(hssfsst_plan* pl, const hssfsst::Core128Params& cp, int64_
     auto kern = hssfsst::fsst_canon_kernel<KLO, KC, false, RAGGED>;
     static std::atomic<unsigned long long> lds_ok{0};
     if (int rc = allow_full_lds(kern, pl->device, lds_ok)) return rc;
-    if constexpr (RAGGED) {
-        int per_cu = 0, cus = 0;
-        if (pl->ragged_slots == 0) {
-            HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kern), 64 * WPB, lds));
-            HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, pl->device));
-            pl->ragged_slots = (per_cu < 1 ? 1 : per_cu) * (cus < 1 ? 1 : cus);
-        }
-        const int64_t blocks = nchunks < pl->ragged_slots ? nchunks : pl->ragged_slots;
-        name_kernel(pl, WPB, blocks, "fsst_canon_kernel<%d, %d, false, ragged>", KLO, KC);
-        hssfsst::CanonParams q = canon_params(pl, cp);
-        q.rsig = cp.rsig; q.rchunk = cp.rchunk; q.rnchunks = cp.rnchunks;
-        hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(blocks)), dim3(64 * WPB), lds, st, q);
-        HIP_TRY(hipGetLastError());
-        return 0;
-    }
-    if (pl->canon_slots == 0) {
-        int per_cu = 0, cus = 0;
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kern), 64 * WPB, lds));
-        HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, pl->device));
-        if (per_cu < 1) per_cu = 1;
-        if (cus < 1) cus = 1;
-        pl->canon_slots = per_cu * cus;
-    }
-    int64_t blocks = nchunks;
-    if (blocks > pl->canon_slots) blocks = pl->canon_slots;
+    int& slots = RAGGED ? pl->ragged_slots : pl->canon_slots;
+    if (int rc = resident_blocks(pl, slots, kern, 64 * WPB, lds, false)) return rc;
+    int64_t blocks = nchunks < slots ? nchunks : slots;
     // (a gated launch -- the fallback behind a team launch -- almost always finds its gate closed: a quarter of the chip keeps
     //  the empty launch at ~2 us instead of ~4; when it does run, the GPU is shared anyway)
-    if (pl->gate != nullptr && blocks > 64) blocks = 64;
-    if (pl->gate == nullptr) name_kernel(pl, WPB, blocks, "fsst_canon_kernel<%d, %d, false>", KLO, KC);
-    hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(blocks)), dim3(64 * WPB), lds, st, canon_params(pl, cp));
+    if (cx.gate != nullptr && blocks > 64) blocks = 64;
+    if (cx.gate == nullptr) name_kernel(cx.kernel, WPB, blocks, "fsst_canon_kernel<%d, %d, false%s>", KLO, KC, RAGGED ? ", ragged" : "");
+    hssfsst::CanonParams q = canon_params(pl, cx, cp);
+    if constexpr (RAGGED) { q.rsig = cp.rsig; q.rchunk = cp.rchunk; q.rnchunks = cp.rnchunks; }
+    hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(blocks)), dim3(64 * WPB), lds, cx.st, q);
     HIP_TRY(hipGetLastError());
     return 0;
 }
-int launch_canon(hssfsst_plan* pl, const hssfsst::Core128Params& cp, int64_t nchunks, hipStream_t st)
+int launch_canon(hssfsst_plan* pl, ExecCtx& cx, const hssfsst::Core128Params& cp, int64_t nchunks)
 {
-    return canon_dispatch(pl, [&](auto KL, auto KN) { return launch_canon_band<decltype(KL)::value, decltype(KN)::value>(pl, cp, nchunks, st); });
+    return canon_dispatch(pl, [&](auto KL, auto KN) { return launch_canon_band<decltype(KL)::value, decltype(KN)::value>(pl, cx, cp, nchunks); });
 }
 
 // One CU per signal with the z-score in the same launch (see launch_fused128): 1 = launched, 0 = take another path
-// gated = the fallback queued behind a team launch (pl->gate set): any batch size -- the block count is what a launch that
+// gated = the fallback queued behind a team launch (cx.gate set): any batch size -- the block count is what a launch that
 // almost always finds its gate closed should cost, not what would be fast.
 template <int KLO, int KC>
-int launch_canon_fused_band(hssfsst_plan* pl, hssfsst::Core128Params cp, int64_t batch, int ngroups, hipStream_t st, bool gated)
+int launch_canon_fused_band(hssfsst_plan* pl, ExecCtx& cx, hssfsst::Core128Params cp, int64_t batch, int ngroups)
 {
+    const bool gated = cx.gate != nullptr;
     constexpr int WPB = 16, GPC = hssfsst::kCanonTileFrames / 16;
     if (ngroups > hssfsst::kFusedMaxGroups || (ngroups + GPC - 1) / GPC < hssfsst::kFusedMinChunks) return 0;
     constexpr size_t lds = (hssfsst::kCanonLdsTabFloats + hssfsst::kCanonCtlFusedFloats + static_cast<size_t>(WPB) * hssfsst::CanonCfg<KLO, KC>::wave_floats()) * sizeof(float);
@@ -790,12 +781,7 @@ int launch_canon_fused_band(hssfsst_plan* pl, hssfsst::Core128Params cp, int64_t
     auto kern = hssfsst::fsst_canon_kernel<KLO, KC, true>;
     static std::atomic<unsigned long long> lds_ok{0};
     if (int rc = allow_full_lds(kern, pl->device, lds_ok)) return rc;
-    if (pl->fused_slots == 0) {
-        int per_cu = 0, cus = 0;
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kern), 64 * WPB, lds));
-        HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, pl->device));
-        pl->fused_slots = (per_cu >= 1 && cus >= 1) ? cus : -1;
-    }
+    if (int rc = resident_blocks(pl, pl->fused_slots, kern, 64 * WPB, lds, true)) return rc;
     if (pl->fused_slots < 1) return 0;
     int64_t grid = pl->fused_slots;
     const int64_t rounds = (batch + grid - 1) / grid;
@@ -804,15 +790,15 @@ int launch_canon_fused_band(hssfsst_plan* pl, hssfsst::Core128Params cp, int64_t
     else if (batch < grid || rounds * grid * 100 > batch * 112) return 0;
     if (int rcs = ensure_status(pl)) return rcs;
     cp.status = pl->d_status;
-    if (!gated) name_kernel(pl, WPB, grid, "fsst_canon_kernel<%d, %d, true>", KLO, KC);
-    hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(grid)), dim3(64 * WPB), lds, st, canon_params(pl, cp));
+    if (!gated) name_kernel(cx.kernel, WPB, grid, "fsst_canon_kernel<%d, %d, true>", KLO, KC);
+    hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(grid)), dim3(64 * WPB), lds, cx.st, canon_params(pl, cx, cp));
     HIP_TRY(hipGetLastError());
     return 1;
     }
 }
-int launch_canon_fused(hssfsst_plan* pl, const hssfsst::Core128Params& cp, int64_t batch, int ngroups, hipStream_t st, bool gated = false)
+int launch_canon_fused(hssfsst_plan* pl, ExecCtx& cx, const hssfsst::Core128Params& cp, int64_t batch, int ngroups)
 {
-    return canon_dispatch(pl, [&](auto KL, auto KN) { return launch_canon_fused_band<decltype(KL)::value, decltype(KN)::value>(pl, cp, batch, ngroups, st, gated); });
+    return canon_dispatch(pl, [&](auto KL, auto KN) { return launch_canon_fused_band<decltype(KL)::value, decltype(KN)::value>(pl, cx, cp, batch, ngroups); });
 }
 
 // What the host has just learnt about the plan's team launches: `gave_up` of them (seen since the last look) among `total` it knows to have
@@ -837,29 +823,27 @@ int plan_next_event(hssfsst_plan* p, hipEvent_t* out_ev)
 
 // hssfsst_plan_timing: every timing_every-th exec records an event in front of its core launch, one behind it and a closing one
 // behind its z-score -- or only the first two when one kernel did everything (ev_chunks -1)
-void timing_begin(hssfsst_plan* p)
+void timing_begin(hssfsst_plan* p, ExecCtx& cx)
 {
-    p->timing_closed = false;
-    p->timing = (p->timing_every > 0 && (p->timing_seq++ % static_cast<unsigned>(p->timing_every)) == 0u) ? 1 : 0;
+    cx.timing = p->timing_every > 0 && (p->timing_seq++ % static_cast<unsigned>(p->timing_every)) == 0u;
 }
-int timing_event(hssfsst_plan* p, hipStream_t st)
+int timing_event(hssfsst_plan* p, const ExecCtx& cx)
 {
-    if (!p->timing) return 0;
+    if (!cx.timing) return 0;
     hipEvent_t evt = nullptr;
     if (int rc = plan_next_event(p, &evt)) return rc;
-    HIP_TRY(hipEventRecord(evt, st));
+    HIP_TRY(hipEventRecord(evt, cx.st));
     return 0;
 }
-int timing_core_done(hssfsst_plan* p, hipStream_t st)   // (the team path has recorded it already, right behind the team kernel)
+int timing_core_done(hssfsst_plan* p, const ExecCtx& cx)   // (the team path has recorded it already, right behind the team kernel)
 {
-    if (p->timing && p->timing_closed) { p->timing_closed = false; return 0; }
-    return timing_event(p, st);
+    return cx.timing_closed ? 0 : timing_event(p, cx);
 }
-int timing_end(hssfsst_plan* p, hipStream_t st, bool one_kernel)
+int timing_end(hssfsst_plan* p, const ExecCtx& cx, bool one_kernel)
 {
-    if (!p->timing) return 0;
+    if (!cx.timing) return 0;
     if (!one_kernel)
-        if (int rc = timing_event(p, st)) return rc;
+        if (int rc = timing_event(p, cx)) return rc;
     p->ev_chunks.push_back(one_kernel ? -1 : 1);
     return 0;
 }
@@ -875,51 +859,67 @@ void half_dispatch(const hssfsst_plan* p, void* out, F&& f)
 // The plain (two-launch) core kernel for a plan of the MFMA kernel: as many waves per block as fit the 160 KiB of LDS beside
 // the shared tables.  RAGGED: the instantiations of hssfsst_exec_ragged (the same ladder, chunk list from the host).
 template <bool RAGGED>
-int launch_core128_plain(hssfsst_plan* pl, const hssfsst::Core128Params& cp, int64_t nchunks, hipStream_t st, bool fast, bool canon)
+int launch_core128_plain(hssfsst_plan* pl, ExecCtx& cx, const hssfsst::Core128Params& cp, int64_t nchunks, bool fast, bool canon)
 {
     const int rq = pl->rq, nt = pl->nt;
     const size_t fixed = (hssfsst::core128_atab_floats(rq, nt) + hssfsst::kCtlFloats) * sizeof(float);
     const size_t per_wave = static_cast<size_t>(hssfsst::wave_lds_floats(kFpw128, pl->klo, pl->K, rq, nt)) * sizeof(float);
     const size_t room = 160 * 1024;
     if (nt == 16 && rq == 8) {
-        if (fast && canon) return launch_core128_wpb<16, 8, true, 16, 3, false, RAGGED>(pl, cp, nchunks, st);
-        if (fast) return launch_core128_wpb<16, 8, true, 16, -1, false, RAGGED>(pl, cp, nchunks, st);   // K <= 24: 16 regions always fit
-        if (fixed + 16 * per_wave <= room) return launch_core128_wpb<16, 8, false, 16, -1, false, RAGGED>(pl, cp, nchunks, st);
-        if (fixed + 8 * per_wave <= room) return launch_core128_wpb<16, 8, false, 8, -1, false, RAGGED>(pl, cp, nchunks, st);
-        if (fixed + 4 * per_wave <= room) return launch_core128_wpb<16, 8, false, 4, -1, false, RAGGED>(pl, cp, nchunks, st);
+        if (fast && canon) return launch_core128_wpb<16, 8, true, 16, 3, false, RAGGED>(pl, cx, cp, nchunks);
+        if (fast) return launch_core128_wpb<16, 8, true, 16, -1, false, RAGGED>(pl, cx, cp, nchunks);   // K <= 24: 16 regions always fit
+        if (fixed + 16 * per_wave <= room) return launch_core128_wpb<16, 8, false, 16, -1, false, RAGGED>(pl, cx, cp, nchunks);
+        if (fixed + 8 * per_wave <= room) return launch_core128_wpb<16, 8, false, 8, -1, false, RAGGED>(pl, cx, cp, nchunks);
+        if (fixed + 4 * per_wave <= room) return launch_core128_wpb<16, 8, false, 4, -1, false, RAGGED>(pl, cx, cp, nchunks);
     } else if (nt == 16 && rq == 16) {                                               // nwin = 256
         // (wave pairs -- fsst_mfma128.hpp "PAIR" -- lose here: 16 waves at 128 registers spill, core 0.770 vs 0.587 ms per 1024
         //  windows; 12 waves at 170 registers: 0.739 ms)
         // (8 waves per block at most: two per SIMD, up to 256 VGPRs, no scratch)
-        if (fast && fixed + 8 * per_wave <= room) return launch_core128_wpb<16, 16, true, 8, -1, false, RAGGED>(pl, cp, nchunks, st);
-        if (!fast && canon && fixed + 8 * per_wave <= room) return launch_core128_wpb<16, 16, false, 8, 3, false, RAGGED>(pl, cp, nchunks, st);
-        if (!fast && fixed + 8 * per_wave <= room) return launch_core128_wpb<16, 16, false, 8, -1, false, RAGGED>(pl, cp, nchunks, st);
-        if (!fast && fixed + 4 * per_wave <= room) return launch_core128_wpb<16, 16, false, 4, -1, false, RAGGED>(pl, cp, nchunks, st);
-        if (fast && fixed + 4 * per_wave <= room) return launch_core128_wpb<16, 16, true, 4, -1, false, RAGGED>(pl, cp, nchunks, st);
+        if (fast && fixed + 8 * per_wave <= room) return launch_core128_wpb<16, 16, true, 8, -1, false, RAGGED>(pl, cx, cp, nchunks);
+        if (!fast && canon && fixed + 8 * per_wave <= room) return launch_core128_wpb<16, 16, false, 8, 3, false, RAGGED>(pl, cx, cp, nchunks);
+        if (!fast && fixed + 8 * per_wave <= room) return launch_core128_wpb<16, 16, false, 8, -1, false, RAGGED>(pl, cx, cp, nchunks);
+        if (!fast && fixed + 4 * per_wave <= room) return launch_core128_wpb<16, 16, false, 4, -1, false, RAGGED>(pl, cx, cp, nchunks);
+        if (fast && fixed + 4 * per_wave <= room) return launch_core128_wpb<16, 16, true, 4, -1, false, RAGGED>(pl, cx, cp, nchunks);
     } else {                                                                         // nt == 32, rq == 16: nwin = 512
         if (!debug_switches().no_pair) {                                             // (two waves per SIMD at most: 32-point spectra in registers)
-            if (fast && core128_lds_bytes(pl, 16, 32, 8, true) <= room) return launch_core128_wpb<32, 16, true, 8, -1, true, RAGGED>(pl, cp, nchunks, st);
-            if (!fast && core128_lds_bytes(pl, 16, 32, 8, true) <= room) return launch_core128_wpb<32, 16, false, 8, -1, true, RAGGED>(pl, cp, nchunks, st);
-            if (!fast && core128_lds_bytes(pl, 16, 32, 6, true) <= room) return launch_core128_wpb<32, 16, false, 6, -1, true, RAGGED>(pl, cp, nchunks, st);
-            if (!fast && core128_lds_bytes(pl, 16, 32, 4, true) <= room) return launch_core128_wpb<32, 16, false, 4, -1, true, RAGGED>(pl, cp, nchunks, st);
+            if (fast && core128_lds_bytes(pl, 16, 32, 8, true) <= room) return launch_core128_wpb<32, 16, true, 8, -1, true, RAGGED>(pl, cx, cp, nchunks);
+            if (!fast && core128_lds_bytes(pl, 16, 32, 8, true) <= room) return launch_core128_wpb<32, 16, false, 8, -1, true, RAGGED>(pl, cx, cp, nchunks);
+            if (!fast && core128_lds_bytes(pl, 16, 32, 6, true) <= room) return launch_core128_wpb<32, 16, false, 6, -1, true, RAGGED>(pl, cx, cp, nchunks);
+            if (!fast && core128_lds_bytes(pl, 16, 32, 4, true) <= room) return launch_core128_wpb<32, 16, false, 4, -1, true, RAGGED>(pl, cx, cp, nchunks);
         }
-        if (fast && fixed + 8 * per_wave <= room) return launch_core128_wpb<32, 16, true, 8, -1, false, RAGGED>(pl, cp, nchunks, st);
-        if (!fast && fixed + 8 * per_wave <= room) return launch_core128_wpb<32, 16, false, 8, -1, false, RAGGED>(pl, cp, nchunks, st);
-        if (!fast && fixed + 6 * per_wave <= room) return launch_core128_wpb<32, 16, false, 6, -1, false, RAGGED>(pl, cp, nchunks, st);
-        if (fast && fixed + 4 * per_wave <= room) return launch_core128_wpb<32, 16, true, 4, -1, false, RAGGED>(pl, cp, nchunks, st);
-        if (!fast && fixed + 4 * per_wave <= room) return launch_core128_wpb<32, 16, false, 4, -1, false, RAGGED>(pl, cp, nchunks, st);
-        if (!fast && fixed + 3 * per_wave <= room) return launch_core128_wpb<32, 16, false, 3, -1, false, RAGGED>(pl, cp, nchunks, st);
-        if (!fast && fixed + 2 * per_wave <= room) return launch_core128_wpb<32, 16, false, 2, -1, false, RAGGED>(pl, cp, nchunks, st);
-        if (fast && fixed + 2 * per_wave <= room) return launch_core128_wpb<32, 16, true, 2, -1, false, RAGGED>(pl, cp, nchunks, st);
+        if (fast && fixed + 8 * per_wave <= room) return launch_core128_wpb<32, 16, true, 8, -1, false, RAGGED>(pl, cx, cp, nchunks);
+        if (!fast && fixed + 8 * per_wave <= room) return launch_core128_wpb<32, 16, false, 8, -1, false, RAGGED>(pl, cx, cp, nchunks);
+        if (!fast && fixed + 6 * per_wave <= room) return launch_core128_wpb<32, 16, false, 6, -1, false, RAGGED>(pl, cx, cp, nchunks);
+        if (fast && fixed + 4 * per_wave <= room) return launch_core128_wpb<32, 16, true, 4, -1, false, RAGGED>(pl, cx, cp, nchunks);
+        if (!fast && fixed + 4 * per_wave <= room) return launch_core128_wpb<32, 16, false, 4, -1, false, RAGGED>(pl, cx, cp, nchunks);
+        if (!fast && fixed + 3 * per_wave <= room) return launch_core128_wpb<32, 16, false, 3, -1, false, RAGGED>(pl, cx, cp, nchunks);
+        if (!fast && fixed + 2 * per_wave <= room) return launch_core128_wpb<32, 16, false, 2, -1, false, RAGGED>(pl, cx, cp, nchunks);
+        if (fast && fixed + 2 * per_wave <= room) return launch_core128_wpb<32, 16, true, 2, -1, false, RAGGED>(pl, cx, cp, nchunks);
     }
     return fail(HSSFSST_EUNSUPPORTED, "LDS request %zu B per wave exceeds the 160 KiB budget", per_wave);
+}
+
+// Is the team kernel wanted for a STACK exec of columns [col0, col0 + ncols) under the preference zpref?  Stated once: exec_impl
+// asks before it decides where the features are written, launch_core128 before it launches.  Yes: the canonical band, a range that
+// starts on a 16-frame group boundary (tiles are aligned in absolute columns), signals of at most 128 groups, and not switched off
+// (HSSFSST_NO_TEAM, a preference for another path).  Paused: it would be, but the team kernel sits execs out after give-ups in a
+// row (note_team_outcome) -- unless team_only, the caller's "team kernel or two launches", overrides the pause; the pause counts
+// execs of any length.  No side effect (launch_core128 counts a paused exec off where it skips it), and nothing of
+// launch_team16's geometry: an exec wanted here may still be declined there.
+enum class Team { No, Paused, Yes };
+Team team_wanted(const hssfsst_plan* pl, int zpref, int col0, int ncols, bool team_only)
+{
+    if (!plan_is_canon(pl) || (col0 & 15) != 0 || debug_switches().no_team || zpref == HSSFSST_ZPATH_ONE_CU || zpref == HSSFSST_ZPATH_TWO_LAUNCH)
+        return Team::No;
+    if (pl->team_pause > 0 && !team_only) return Team::Paused;
+    return (ncols + 15) / 16 <= hssfsst::kFusedMaxGroups ? Team::Yes : Team::No;
 }
 
 // hout != nullptr (half plans): the team kernel stores the features there as 2-byte elements; every other kernel writes float32
 // features to dout for a second, out-of-place z-score sweep (exec_impl) -- the single-launch kernels that normalise in float32 in
 // place (one CU per signal, fsst_core128_kernel's fused epilogues) are not taken
-int launch_core128(hssfsst_plan* pl, const float* dx, long long xstride, float* dout, float* partials, int n, int col0,
-                   int ncols, int64_t batch, hipStream_t st, bool try_fused, bool* did_fuse, void* hout = nullptr)
+int launch_core128(hssfsst_plan* pl, ExecCtx& cx, const float* dx, long long xstride, float* dout, float* partials, int n, int col0,
+                   int ncols, int64_t batch, bool try_fused, void* hout = nullptr)
 {
     const bool half = hout != nullptr;
     hssfsst::Core128Params cp{};
@@ -940,7 +940,6 @@ int launch_core128(hssfsst_plan* pl, const float* dx, long long xstride, float* 
     // bands that start in stripe 0 of the own plane and end in stripe 3 (the canonical [25, 200] Hz at fs = 1000 for
     // nwin 128 and 256) get kernels with compile-time stripe tests
     const bool canon = hssfsst::own_s0(pl->klo, rq) == 0 && hssfsst::own_s1(pl->klo, pl->K, rq) == 3;
-    *did_fuse = false;
     // (tiles are aligned in absolute columns: a column range must start on a 16-frame group boundary -- on a 64-frame tile
     //  boundary for the team kernel, whose chunks are whole tiles; other ranges take fsst_core128_kernel)
     const bool canon16 = fast && nt == 16 && rq == 8 && plan_is_canon(pl) && (col0 & 15) == 0;
@@ -950,76 +949,69 @@ int launch_core128(hssfsst_plan* pl, const float* dx, long long xstride, float* 
         // fast as one CU per signal on full batches and 1.3-1.8x faster on small or ragged ones (profiles/r04_batch_sweep.txt): it
         // goes first wherever it applies -- the canonical band, signals of at most 128 groups; one CU per signal (the tile makes a
         // round trip through HBM inside the launch) for the other even bands of <= 24 rows, and as the team kernel's gated fallback
-        const bool env_no_team = debug_switches().no_team, env_team_only = debug_switches().team_only;      // A/B and tests
-        const bool no_team = env_no_team || pl->zpath_pref == HSSFSST_ZPATH_ONE_CU;
-        const bool team_only = env_team_only || pl->zpath_pref == HSSFSST_ZPATH_TEAM;
+        const bool team_only = debug_switches().team_only || cx.zpref == HSSFSST_ZPATH_TEAM;      // (the switch: A/B and tests)
         int rc = 0;
         // (the host learns of give-ups where it synchronises anyway -- host-output execs, hssfsst_plan_fallbacks, hssfsst_plan_check -- and lets
         //  the team kernel sit out a while when they come in a row: note_team_outcome)
-        const bool paused = pl->team_pause > 0 && !team_only;
-        if (paused && canon16 && !no_team) --pl->team_pause;
-        if (!no_team && canon16 && !paused) {
+        const Team team = team_wanted(pl, cx.zpref, col0, ncols, team_only);
+        if (team == Team::Paused) --pl->team_pause;
+        if (team == Team::Yes) {
             rc = canon_dispatch(pl, [&](auto KL, auto KN) {      // (16 waves per block, two held groups per wave)
                 constexpr int kl = decltype(KL)::value, kn = decltype(KN)::value;
-                if (pl->out_dtype == HSSFSST_DTYPE_F16) return launch_team16<kl, kn, 16, 2, _Float16>(pl, cp, batch, ngroups, st, hout);
-                if (pl->out_dtype == HSSFSST_DTYPE_BF16) return launch_team16<kl, kn, 16, 2, __bf16>(pl, cp, batch, ngroups, st, hout);
-                return launch_team16<kl, kn, 16, 2>(pl, cp, batch, ngroups, st);
+                if (pl->out_dtype == HSSFSST_DTYPE_F16) return launch_team16<kl, kn, 16, 2, _Float16>(pl, cx, cp, batch, ngroups, hout);
+                if (pl->out_dtype == HSSFSST_DTYPE_BF16) return launch_team16<kl, kn, 16, 2, __bf16>(pl, cx, cp, batch, ngroups, hout);
+                return launch_team16<kl, kn, 16, 2>(pl, cx, cp, batch, ngroups);
             });
             if (rc == 1) {
                 // the team kernel may give the launch up (its blocks wait for each other; other processes on the GPU can keep
                 // them apart: fsst_team16.hpp "Progress"): the same exec is queued behind it, every kernel of it gated on the
                 // abort word -- a few microseconds of empty launches when nothing went wrong
-                pl->last_zpath = 2;
-                if (int rce = timing_event(pl, st)) return rce;      // the kernel's own time: the closing event goes in front of the gated launches
-                pl->timing_closed = pl->timing != 0;
-                if (pl->defer_fallback) {                // (exec_impl: a host-output exec synchronises anyway and checks the give-up word then)
-                    if (pl->deferred_launch == 0u) pl->deferred_first = pl->team_launch;
-                    pl->deferred_launch = pl->team_launch;
-                    *did_fuse = true;
+                cx.zpath = 2;
+                if (int rce = timing_event(pl, cx)) return rce;      // the kernel's own time: the closing event goes in front of the gated launches
+                cx.timing_closed = cx.timing;
+                if (cx.host_waits) {                     // (exec_impl: a host-output exec synchronises anyway and checks the give-up word then)
+                    cx.fused = true;
                     return 0;
                 }
-                pl->gate = pl->d_arrive.get() + 1; pl->gate_val = pl->team_launch;
+                cx.gate = pl->d_arrive.get() + 1; cx.gate_val = cx.team_launch;
                 // ONE gated launch where the one-CU-per-signal kernel applies (signals of 16 .. 32 chunks; its batch
                 // conditions are about speed only): 4 us behind the team kernel instead of 11 for transform + statistics +
                 // z-score launches -- a third of a 50-window exec
-                const int rc1 = half ? 0 : launch_canon_fused(pl, cp, batch, ngroups, st, true);
-                if (rc1 < 0) { pl->gate = nullptr; return rc1; }
-                if (rc1 == 1) { pl->gate = nullptr; *did_fuse = true; return 0; }
-                const int rc2 = launch_canon(pl, cp, nchunks, st);
-                if (rc2 != 0) { pl->gate = nullptr; return rc2; }
-                *did_fuse = false;                       // (exec_impl adds the gated statistics + z-score launches)
-                return 0;
+                const int rc1 = half ? 0 : launch_canon_fused(pl, cx, cp, batch, ngroups);
+                if (rc1 < 0) return rc1;
+                if (rc1 == 1) { cx.fused = true; return 0; }
+                return launch_canon(pl, cx, cp, nchunks);    // (exec_impl adds the gated statistics + z-score launches)
             }
             if (rc < 0) return rc;
         }
         if (!team_only && !half) {
-            rc = canon16 ? launch_canon_fused(pl, cp, batch, ngroups, st)
-                 : canon ? launch_fused128<3>(pl, cp, batch, ngroups, st) : launch_fused128<-1>(pl, cp, batch, ngroups, st);
+            rc = canon16 ? launch_canon_fused(pl, cx, cp, batch, ngroups)
+                 : canon ? launch_fused128<3>(pl, cx, cp, batch, ngroups) : launch_fused128<-1>(pl, cx, cp, batch, ngroups);
         }
         if (rc < 0) return rc;
-        if (rc == 1) { *did_fuse = true; pl->last_zpath = 1; return 0; }
+        if (rc == 1) { cx.fused = true; cx.zpath = 1; return 0; }
     }
-    if (try_fused && !half && !fast && rq == 8 && nt == 16 && pl->mode == HSSFSST_MODE_STACK && pl->zpath_pref != HSSFSST_ZPATH_TEAM &&
+    if (try_fused && !half && !fast && rq == 8 && nt == 16 && pl->mode == HSSFSST_MODE_STACK && cx.zpref != HSSFSST_ZPATH_TEAM &&
         fixed + 16 * per_wave <= room) {
         // nwin 128, a band the wide-store epilogue does not take (odd K or K > 24)
-        const int rc = launch_fused_general<16, 8, 16, -1>(pl, cp, batch, (ncols + 15) / 16, st);
+        const int rc = launch_fused_general<16, 8, 16, -1>(pl, cx, cp, batch, (ncols + 15) / 16);
         if (rc < 0) return rc;
-        if (rc == 1) { *did_fuse = true; pl->last_zpath = 1; return 0; }
+        if (rc == 1) { cx.fused = true; cx.zpath = 1; return 0; }
     }
-    if (try_fused && !half && !fast && rq == 16 && pl->mode == HSSFSST_MODE_STACK && pl->zpath_pref != HSSFSST_ZPATH_TEAM) {
+    if (try_fused && !half && !fast && rq == 16 && pl->mode == HSSFSST_MODE_STACK && cx.zpref != HSSFSST_ZPATH_TEAM) {
         // nwin 256 / 512 (general epilogue): one CU per signal, the z-score as tickets of the same launch; waves per block
         // as on the two-launch path (what fits the LDS: 8 for the canonical band at 256 points, 3 at 512)
         const int ngroups = (ncols + 15) / 16;
         int rc = 0;
         if (nt == 16 && fixed + 8 * per_wave <= room)
-            rc = canon ? launch_fused_general<16, 16, 8, 3>(pl, cp, batch, ngroups, st) : launch_fused_general<16, 16, 8, -1>(pl, cp, batch, ngroups, st);
+            rc = canon ? launch_fused_general<16, 16, 8, 3>(pl, cx, cp, batch, ngroups) : launch_fused_general<16, 16, 8, -1>(pl, cx, cp, batch, ngroups);
         // (512 points: two launches, on wave pairs: 2.6 ms per 1024 windows against 3.0 for the single launch, whose
         //  instantiations are gone)
         if (rc < 0) return rc;
-        if (rc == 1) { *did_fuse = true; pl->last_zpath = 1; return 0; }
+        if (rc == 1) { cx.fused = true; cx.zpath = 1; return 0; }
     }
-    if (canon16) return launch_canon(pl, cp, nchunks, st);
-    return launch_core128_plain<false>(pl, cp, nchunks, st, fast, canon);
+    if (canon16) return launch_canon(pl, cx, cp, nchunks);
+    return launch_core128_plain<false>(pl, cx, cp, nchunks, fast, canon);
 }
 
 }  // namespace
@@ -1454,7 +1446,6 @@ int hssfsst_plan_set_timing(hssfsst_plan* p, int enable)
 {
     if (!p) return fail(HSSFSST_EINVAL, "plan_set_timing: plan is NULL");
     p->timing_every = enable > 0 ? enable : 0;
-    p->timing = 0;
     p->timing_seq = 0;
     p->ev_used = 0;
     p->ev_chunks.clear();
@@ -1561,6 +1552,93 @@ static int exec_finish(hssfsst_plan* p, void* out, const void* dout, size_t byte
     return 0;
 }
 
+// The any-length kernel (fsst_dft.hpp) for one exec: its tile search and launch
+static int launch_dft(hssfsst_plan* p, ExecCtx& cx, const float* dx, float* kout, int64_t batch, int n, int64_t x_stride, int col0, int ncols)
+{
+    hssfsst::DftParams dp{};
+    dp.x = dx; dp.out = kout; dp.partials = p->d_partials.get(); dp.atab = p->d_dtab.get();
+    dp.wtab = p->d_wtab.get(); dp.twtab = p->d_wtab.get() + 2 * p->nwin;
+    dp.n = n; dp.nwin = p->nwin; dp.nf = p->nf; dp.klo = p->klo; dp.K = p->K; dp.mode = p->mode; dp.col0 = col0; dp.ncols = ncols;
+    dp.nk4 = (p->nwin + 3) / 4; dp.nblk4 = (p->nf + 3) / 4;
+    dp.xstride = x_stride; dp.r2scale = p->r2scale;
+    // groups per work item: 4 when four planes fit the LDS of a wave (each A-operand load then feeds four MFMAs),
+    // else 2, else 1; then as many waves per block as fit (at most 8)
+    // largest tile that still leaves >= 16 waves resident per CU (the MFMA chains are dependent: latency is hidden
+    // by waves, not by the tile), else whatever keeps the most waves (measured: nwin 100 is fastest with small tiles)
+    int G = 1, best_waves = -1;
+    for (int cand = 4; cand >= 1; cand >>= 1) {
+        const size_t pw = static_cast<size_t>(hssfsst::dft_wave_lds_floats(dp.nk4, p->K, cand)) * sizeof(float);
+        int w = static_cast<int>(static_cast<size_t>(kMaxLdsBytes) / pw);
+        if (w > 8) w = 8;
+        if (w < 1) continue;
+        int per_cu = static_cast<int>(static_cast<size_t>(kMaxLdsBytes) / (pw * w)) * w;
+        if (per_cu > 32) per_cu = 32;
+        if (per_cu >= 16) { G = cand; best_waves = per_cu; break; }
+        if (per_cu > best_waves) { G = cand; best_waves = per_cu; }
+    }
+    if (ncols <= 16) G = 1;
+    const size_t per_wave = static_cast<size_t>(hssfsst::dft_wave_lds_floats(dp.nk4, p->K, G)) * sizeof(float);
+    int waves = static_cast<int>(static_cast<size_t>(kMaxLdsBytes) / per_wave);
+    if (waves > 8) waves = 8;
+    if (waves < 1) return fail(HSSFSST_EUNSUPPORTED, "exec: LDS request %zu B per wave exceeds 160 KiB", per_wave);
+    const int ntiles = (ncols + 16 * G - 1) / (16 * G);
+    dp.nitems = static_cast<long long>(batch) * ntiles;
+    long long blocks = (dp.nitems + waves - 1) / waves;
+    if (blocks > 256 * 64) blocks = 256 * 64;                       // grid-stride beyond that
+    auto launch = [&](auto kern) -> int {
+        static std::atomic<unsigned long long> lds_ok{0};
+        if (int r2 = allow_full_lds(kern, p->device, lds_ok)) return r2;
+        name_kernel(cx.kernel, waves, blocks, "fsst_dft_kernel<%d>", G);
+        hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(blocks)), dim3(64 * waves), per_wave * waves, cx.st, dp);
+        return (hipGetLastError() == hipSuccess) ? 0 : fail(HSSFSST_EHIP, "exec: fsst_dft_kernel launch failed");
+    };
+    return (G == 4) ? launch(hssfsst::fsst_dft_kernel<4>) : (G == 2) ? launch(hssfsst::fsst_dft_kernel<2>) : launch(hssfsst::fsst_dft_kernel<1>);
+}
+
+// The end of an exec whose kernels stored the features to pinned host memory (exec_impl: tiny_out): waits for them.  *redo: the
+// exec's team launch gave itself up and the caller computes the exec again without the team kernel.
+static int finish_pinned_exec(hssfsst_plan* p, const ExecCtx& cx, bool* redo)
+{
+    // The team launch of this exec, if it was asked to (want_done_word): its last wave stores the launch's identity to h_fallback[2] behind a
+    // system-scope release of every wave's stores -- the features are in pinned host memory by then.  Waiting for that word instead of
+    // the stream's completion signal spares the end-of-kernel cache flush and the signal's way to the host: 6 us of a 35 us call
+    // (tools/sync_latency.hip).  A launch that gave itself up never stores it: the give-up word ends the wait, as does a bound.
+    bool seen = false;
+    const unsigned fl = cx.flagged_launch;
+    if (fl != 0u && p->h_fallback) {
+        const auto t0 = std::chrono::steady_clock::now();
+        for (unsigned it = 0;; ++it) {
+            if (p->h_fallback[2] == fl) { seen = true; break; }
+            if (p->h_fallback[0] == fl) break;                                   // given up: the usual way below
+            if ((it & 255u) == 255u && std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(2000)) break;
+            __builtin_ia32_pause();
+        }
+        std::atomic_thread_fence(std::memory_order_acquire);
+    }
+    if (!seen) {
+        HIP_TRY(hipStreamSynchronize(cx.st));
+        if (fl != 0u) {                               // (the blocks of a given-up launch did not all count themselves in: start the count over)
+            HIP_TRY(hipMemsetAsync(p->d_arrive.get() + 2, 0, sizeof(unsigned), cx.st));
+            p->done_total = 0;
+        }
+    }
+    if (cx.host_waits && cx.team_launch != 0u) {
+        // no gated kernels were queued behind this exec's team launch: if that launch gave itself up (pinned word, written with
+        // system scope before the kernel ended), the exec is computed now by the kernels that would have been queued
+        const bool gave = p->h_fallback && p->h_fallback[0] == cx.team_launch;      // (launch identities count up; 0 is never one)
+        note_team_outcome(p, gave);
+        if (gave) { *redo = true; return 0; }
+    }
+    if (seen) {                                       // (the status word is pinned host memory too: written before the wave that wrote it counted itself in)
+        if (p->h_status && *p->h_status != 0u) {
+            const unsigned code = *p->h_status;
+            *p->h_status = 0u;
+            return fail(HSSFSST_EHIP, "fused z-score: a wait inside the kernel gave up (code %u); results of that exec are invalid", code);
+        }
+    } else if (p->d_status) return hssfsst_plan_check(p);
+    return 0;
+}
+
 // The one exec: `batch` signals of n samples, signal b at x + b * x_stride, or -- d_starts != nullptr (device array) --
 // at x + d_starts[b] inside a buffer of x_len samples.  A frame list is first gathered into a dense [batch][n] staging
 // buffer (fsst_gather_frames_kernel: 8 kB read + 8 kB written per frame, against 360 kB of output) and then takes the
@@ -1568,8 +1646,11 @@ static int exec_finish(hssfsst_plan* p, void* out, const void* dout, size_t byte
 // addressing mode in them cost spilled registers.
 // (pin_d != nullptr: `out` is a pinned buffer of the plan's pool and pin_d its device alias -- hssfsst_exec_pinned: the kernels store the
 //  features there and nothing is copied; returns 1 when this exec is not one the kernels can write straight to host memory)
+// (redo: the second pass of a host-output exec whose team launch gave up -- no team kernel, no direct-to-host output: it runs as
+//  under HSSFSST_ZPATH_ONE_CU)
 static int exec_impl(hssfsst_plan* p, const float* x, int64_t batch, int n, int64_t x_stride, const long long* d_starts,
-                     size_t x_len, int col0, int ncols, int x_on_device, float* out, int out_on_device, void* stream, float* pin_d = nullptr)
+                     size_t x_len, int col0, int ncols, int x_on_device, float* out, int out_on_device, void* stream, float* pin_d = nullptr,
+                     bool redo = false)
 {
     if (!p || !x || !out || batch < 0 || n < 1 || col0 < 0 || ncols < 1 || col0 > n - ncols || x_stride < 1)
         return fail(HSSFSST_EINVAL, "exec: bad argument (batch=%lld n=%d stride=%lld col0=%d ncols=%d)",
@@ -1579,6 +1660,9 @@ static int exec_impl(hssfsst_plan* p, const float* x, int64_t batch, int n, int6
     DEVICE_SCOPE(p->device);
     int rc;
     if ((rc = take_pending_status(p, "exec")) != 0) return rc;
+    ExecCtx cx;
+    cx.st = st;
+    cx.zpref = redo ? HSSFSST_ZPATH_ONE_CU : p->zpath_pref;
     const int ofps = out_floats_per_sample(p);
     const bool use128 = (p->d_atab.get() != nullptr);
     // statistics partials per signal: one per 16-frame group (MFMA kernel) / per 64-frame tile (generic kernel)
@@ -1602,12 +1686,10 @@ static int exec_impl(hssfsst_plan* p, const float* x, int64_t batch, int n, int6
     // second pass over the features) the kernels store it into a pinned buffer too -- the mechanism of hssfsst_stream_step.
     const bool tiny_in = !x_on_device && nx <= (static_cast<size_t>(1) << 16);
     // (STACK: only where the team kernel will take the exec -- its features are written once; a z-score that is a second pass would
-    //  read and rewrite them in place over PCIe: signals of more than 128 groups keep the device staging buffer + one copy)
+    //  read and rewrite them in place over PCIe: signals of more than 128 groups keep the device staging buffer + one copy;
+    //  the HSSFSST_TEAM_ONLY switch overrides a pause at the launch only: a paused exec under it keeps the staging buffer too)
     const bool tiny_out = tiny_in && !out_on_device && no_f <= (static_cast<size_t>(1) << 21) &&
-                          (p->mode != HSSFSST_MODE_STACK || (plan_is_canon(p) && (col0 & 15) == 0 && !debug_switches().no_team &&
-                                                             p->zpath_pref != HSSFSST_ZPATH_ONE_CU && p->zpath_pref != HSSFSST_ZPATH_TWO_LAUNCH &&
-                                                             (p->team_pause == 0 || p->zpath_pref == HSSFSST_ZPATH_TEAM) &&
-                                                             (ncols + 15) / 16 <= hssfsst::kFusedMaxGroups));
+                          (p->mode != HSSFSST_MODE_STACK || team_wanted(p, cx.zpref, col0, ncols, cx.zpref == HSSFSST_ZPATH_TEAM) == Team::Yes);
     auto pin = [&](PinnedBuf<float>& b, size_t need) -> int {
         if (b.h && b.cap < need) HIP_TRY(hipStreamSynchronize(st));     // (earlier work on the stream may still use the old block)
         return b.grow(need, sizeof(float));
@@ -1632,20 +1714,18 @@ static int exec_impl(hssfsst_plan* p, const float* x, int64_t batch, int n, int6
         x_stride = n;
     }
     if (pin_d && !tiny_out) return 1;                    // (not an exec whose features are written once: the caller takes the copying call)
-    p->defer_fallback = false;
     if (tiny_out) {
         if (pin_d) dout = pin_d;
         else {
             if ((rc = pin(p->opin, no_f)) != 0) return rc;
             dout = p->opin.d;
         }
-        p->defer_fallback = p->zpath_pref != HSSFSST_ZPATH_ONE_CU && !d_starts;
-        p->deferred_launch = 0u;
+        cx.host_waits = cx.zpref != HSSFSST_ZPATH_ONE_CU && !d_starts;
     }
     float* kout = nullptr;
     if ((rc = exec_buffers(p, no, !tiny_out && !out_on_device, static_cast<size_t>(nblocks), batch, &dout, &kout)) != 0) return rc;
 
-    timing_begin(p);
+    timing_begin(p, cx);
     // STACK: core (FP32-issue-bound) then the z-score sweep (HBM-bound, in place).  Measured and rejected (git history, DESIGN.md
     // section 4.3): a k-chunk two-stream pipeline that overlaps the sweep of one chunk with the core of the next -- the saturating
     // sweep back-pressures the core's own stores (core 0.25 -> 0.32-0.41 ms per 1024 windows); fusing the z-score into the
@@ -1654,72 +1734,29 @@ static int exec_impl(hssfsst_plan* p, const float* x, int64_t batch, int n, int6
     // (bounded spin + fix-up kernel: 0.58 ms) -- both bit-identical to, and slower than, the two-pass 0.37 ms per 1024 windows.
     // a host-output exec of one team launch: the launch's last wave says "done" in pinned host memory and this call waits for that word
     // instead of synchronising the stream (below)
-    p->flag_done = tiny_out && p->defer_fallback && !p->timing;
-    p->flag_launch = 0u;
+    cx.want_done_word = cx.host_waits && !cx.timing;
     hssfsst::CoreParams cp;
     cp.x = dx; cp.out = kout; cp.partials = p->d_partials.get(); cp.ctab = p->d_ctab.get();
     cp.n = n; cp.klo = p->klo; cp.K = p->K; cp.mode = p->mode; cp.nblk = nblk; cp.col0 = col0; cp.ncols = ncols; cp.xstride = x_stride;
     cp.wtab = p->d_wtab.get(); cp.twtab = p->d_wtab.get() + 2 * p->nwin; cp.r2scale = p->r2scale;
-    if ((rc = timing_event(p, st)) != 0) return rc;
-    bool did_fuse = false;
+    if ((rc = timing_event(p, cx)) != 0) return rc;
     const bool no_fused = debug_switches().no_fused;      // A/B and bit-equality tests
     if (p->dft) {
-        hssfsst::DftParams dp{};
-        dp.x = dx; dp.out = kout; dp.partials = cp.partials; dp.atab = p->d_dtab.get();
-        dp.wtab = p->d_wtab.get(); dp.twtab = p->d_wtab.get() + 2 * p->nwin;
-        dp.n = n; dp.nwin = p->nwin; dp.nf = p->nf; dp.klo = p->klo; dp.K = p->K; dp.mode = p->mode; dp.col0 = col0; dp.ncols = ncols;
-        dp.nk4 = (p->nwin + 3) / 4; dp.nblk4 = (p->nf + 3) / 4;
-        dp.nitems = nblocks; dp.xstride = x_stride; dp.r2scale = p->r2scale;
-        // groups per work item: 4 when four planes fit the LDS of a wave (each A-operand load then feeds four MFMAs),
-        // else 2, else 1; then as many waves per block as fit (at most 8)
-        // largest tile that still leaves >= 16 waves resident per CU (the MFMA chains are dependent: latency is hidden
-        // by waves, not by the tile), else whatever keeps the most waves (measured: nwin 100 is fastest with small tiles)
-        int G = 1, best_waves = -1;
-        for (int cand = 4; cand >= 1; cand >>= 1) {
-            const size_t pw = static_cast<size_t>(hssfsst::dft_wave_lds_floats(dp.nk4, p->K, cand)) * sizeof(float);
-            int w = static_cast<int>(static_cast<size_t>(kMaxLdsBytes) / pw);
-            if (w > 8) w = 8;
-            if (w < 1) continue;
-            int per_cu = static_cast<int>(static_cast<size_t>(kMaxLdsBytes) / (pw * w)) * w;
-            if (per_cu > 32) per_cu = 32;
-            if (per_cu >= 16) { G = cand; best_waves = per_cu; break; }
-            if (per_cu > best_waves) { G = cand; best_waves = per_cu; }
-        }
-        if (ncols <= 16) G = 1;
-        const size_t per_wave = static_cast<size_t>(hssfsst::dft_wave_lds_floats(dp.nk4, p->K, G)) * sizeof(float);
-        int waves = static_cast<int>(static_cast<size_t>(kMaxLdsBytes) / per_wave);
-        if (waves > 8) waves = 8;
-        if (waves < 1) return fail(HSSFSST_EUNSUPPORTED, "exec: LDS request %zu B per wave exceeds 160 KiB", per_wave);
-        const int ntiles = (ncols + 16 * G - 1) / (16 * G);
-        dp.nitems = static_cast<long long>(batch) * ntiles;
-        long long blocks = (dp.nitems + waves - 1) / waves;
-        if (blocks > 256 * 64) blocks = 256 * 64;                       // grid-stride beyond that
-        auto launch = [&](auto kern) -> int {
-            static std::atomic<unsigned long long> lds_ok{0};
-            if (int r2 = allow_full_lds(kern, p->device, lds_ok)) return r2;
-            name_kernel(p, waves, blocks, "fsst_dft_kernel<%d>", G);
-            hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(blocks)), dim3(64 * waves), per_wave * waves, st, dp);
-            return (hipGetLastError() == hipSuccess) ? 0 : fail(HSSFSST_EHIP, "exec: fsst_dft_kernel launch failed");
-        };
-        rc = (G == 4) ? launch(hssfsst::fsst_dft_kernel<4>) : (G == 2) ? launch(hssfsst::fsst_dft_kernel<2>) : launch(hssfsst::fsst_dft_kernel<1>);
+        rc = launch_dft(p, cx, dx, kout, batch, n, x_stride, col0, ncols);
     } else if (use128) {
-        rc = launch_core128(p, dx, x_stride, kout, cp.partials, n, col0, ncols, batch, st, !no_fused && p->zpath_pref != HSSFSST_ZPATH_TWO_LAUNCH, &did_fuse,
+        rc = launch_core128(p, cx, dx, x_stride, kout, cp.partials, n, col0, ncols, batch, !no_fused && cx.zpref != HSSFSST_ZPATH_TWO_LAUNCH,
                             half ? dout : nullptr);
     } else switch (p->R) {
-        case 1: rc = launch_core<1>(p, cp, nblocks, st); break;
-        case 2: rc = launch_core<2>(p, cp, nblocks, st); break;
-        case 4: rc = launch_core<4>(p, cp, nblocks, st); break;
-        case 8: rc = launch_core<8>(p, cp, nblocks, st); break;
-        case 16: rc = launch_core<16>(p, cp, nblocks, st); break;
+        case 1: rc = launch_core<1>(p, cx, cp, nblocks); break;
+        case 2: rc = launch_core<2>(p, cx, cp, nblocks); break;
+        case 4: rc = launch_core<4>(p, cx, cp, nblocks); break;
+        case 8: rc = launch_core<8>(p, cx, cp, nblocks); break;
+        case 16: rc = launch_core<16>(p, cx, cp, nblocks); break;
         default: rc = fail(HSSFSST_EUNSUPPORTED, "exec: unsupported radix %d", p->R);
     }
     if (rc != 0) return rc;
-    if ((rc = timing_core_done(p, st)) != 0) return rc;
-    const unsigned* gate = p->gate;                      // non-null: a team launch went first; what follows is its gated fallback
-    const unsigned gate_val = p->gate_val;
-    p->gate = nullptr;
-    p->last_fused = (did_fuse || gate != nullptr) ? 1 : 0;
-    if (p->mode == HSSFSST_MODE_STACK && !did_fuse) {
+    if ((rc = timing_core_done(p, cx)) != 0) return rc;
+    if (p->mode == HSSFSST_MODE_STACK && !cx.fused) {       // (cx.gate non-null: a team launch went first; what follows is its gated fallback)
         float4* stats = reinterpret_cast<float4*>(p->d_stats.get());
         int64_t zgrid = 4096;
         // small batches: several blocks per signal, else one block per signal would leave most CUs idle
@@ -1734,71 +1771,26 @@ static int exec_impl(hssfsst_plan* p, const float* x, int64_t batch, int n, int6
         const bool fused = slices == 1 && zgrid == batch && batch >= 512;
         if (!fused)
             hipLaunchKernelGGL(hssfsst::fsst_stats_kernel, dim3(static_cast<unsigned>(batch)), dim3(64), 0, st,
-                               cp.partials, stats, nblk, fpp, ncols, p->K, gate, gate_val);
+                               cp.partials, stats, nblk, fpp, ncols, p->K, cx.gate, cx.gate_val);
         if (half)                                        // out of place: float32 scratch -> 2-byte elements (fsst_half.hpp)
             half_dispatch(p, dout, [&](auto* o) {
                 hipLaunchKernelGGL(hssfsst::fsst_normalize_to_kernel<std::remove_pointer_t<decltype(o)>>, dim3(static_cast<unsigned>(zgrid)), dim3(256), 0, st,
                                    kout, o, stats, fused ? cp.partials : nullptr, nblk, fpp, ncols, p->K, static_cast<int>(batch), slices,
-                                   gate, gate_val);
+                                   cx.gate, cx.gate_val);
             });
         else
             hipLaunchKernelGGL(hssfsst::fsst_normalize_kernel, dim3(static_cast<unsigned>(zgrid)), dim3(256), 0, st,
                                kout, stats, fused ? cp.partials : nullptr, nblk, fpp, ncols, p->K, static_cast<int>(batch), slices,
-                               gate, gate_val);
+                               cx.gate, cx.gate_val);
         HIP_TRY(hipGetLastError());
     }
-    if ((rc = timing_end(p, st, p->last_fused != 0)) != 0) return rc;
+    exec_report(p, cx);
+    if ((rc = timing_end(p, cx, p->last_fused != 0)) != 0) return rc;
     if (tiny_out) {
-        // The team launch of this exec, if it was asked to (flag_done): its last wave stores the launch's identity to h_fallback[2] behind a
-        // system-scope release of every wave's stores -- the features are in pinned host memory by then.  Waiting for that word instead of
-        // the stream's completion signal spares the end-of-kernel cache flush and the signal's way to the host: 6 us of a 35 us call
-        // (tools/sync_latency.hip).  A launch that gave itself up never stores it: the give-up word ends the wait, as does a bound.
-        bool seen = false;
-        const unsigned fl = (p->flag_done && p->flag_launch != 0u && p->flag_launch == p->deferred_launch && p->deferred_first == p->deferred_launch)
-                            ? p->flag_launch : 0u;
-        p->flag_done = false;
-        p->flag_launch = 0u;
-        if (fl != 0u && p->h_fallback) {
-            const auto t0 = std::chrono::steady_clock::now();
-            for (unsigned it = 0;; ++it) {
-                if (p->h_fallback[2] == fl) { seen = true; break; }
-                if (p->h_fallback[0] == fl) break;                                   // given up: the usual way below
-                if ((it & 255u) == 255u && std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(2000)) break;
-                __builtin_ia32_pause();
-            }
-            std::atomic_thread_fence(std::memory_order_acquire);
-        }
-        if (!seen) {
-            HIP_TRY(hipStreamSynchronize(st));
-            if (fl != 0u) {                               // (the blocks of a given-up launch did not all count themselves in: start the count over)
-                HIP_TRY(hipMemsetAsync(p->d_arrive.get() + 2, 0, sizeof(unsigned), st));
-                p->done_total = 0;
-            }
-        }
-        p->defer_fallback = false;
-        if (p->deferred_launch != 0u) {
-            // no gated kernels were queued behind this exec's team launch: if that launch gave itself up (pinned word, written with
-            // system scope before the kernel ended), the exec is computed now by the kernels that would have been queued
-            const unsigned dl = p->deferred_launch, df = p->deferred_first;
-            p->deferred_launch = 0u;
-            const unsigned gu = p->h_fallback ? p->h_fallback[0] : 0u;      // (launch identities count up; 0 is never one)
-            const bool gave = gu != 0u && (df <= dl ? (gu >= df && gu <= dl) : (gu >= df || gu <= dl));
-            note_team_outcome(p, gave);
-            if (gave) {
-                const int keep = p->zpath_pref;
-                p->zpath_pref = HSSFSST_ZPATH_ONE_CU;
-                rc = exec_impl(p, x, batch, n, x_stride, d_starts, x_len, col0, ncols, x_on_device, out, out_on_device, stream);      // (copies into `out`: a pool buffer is host memory too)
-                p->zpath_pref = keep;
-                return rc;
-            }
-        }
-        if (seen) {                                       // (the status word is pinned host memory too: written before the wave that wrote it counted itself in)
-            if (p->h_status && *p->h_status != 0u) {
-                const unsigned code = *p->h_status;
-                *p->h_status = 0u;
-                return fail(HSSFSST_EHIP, "fused z-score: a wait inside the kernel gave up (code %u); results of that exec are invalid", code);
-            }
-        } else if (p->d_status && (rc = hssfsst_plan_check(p)) != 0) return rc;
+        bool gave_up = false;
+        if ((rc = finish_pinned_exec(p, cx, &gave_up)) != 0) return rc;
+        if (gave_up)                                      // (copies into `out`: a pool buffer is host memory too)
+            return exec_impl(p, x, batch, n, x_stride, d_starts, x_len, col0, ncols, x_on_device, out, out_on_device, stream, nullptr, true);
         if (!pin_d) std::memcpy(out, p->opin.h, no * es);
     } else return exec_finish(p, out, dout, no * es, x_on_device, out_on_device, st);
     return 0;
@@ -1971,8 +1963,10 @@ int hssfsst_exec_ragged(hssfsst_plan* p, const float* x, int64_t x_len, const in
     if (!x_on_device && (rc = stage_input(p, x + xlo, static_cast<size_t>(xhi - xlo), &dx, st)) != 0) return rc;
     if ((rc = exec_buffers(p, no, !out_on_device, static_cast<size_t>(groups), batch, &dout, &kout)) != 0) return rc;
 
-    timing_begin(p);
-    if ((rc = timing_event(p, st)) != 0) return rc;
+    ExecCtx cx;
+    cx.st = st;
+    timing_begin(p, cx);
+    if ((rc = timing_event(p, cx)) != 0) return rc;
     hssfsst::Core128Params cp{};
     cp.x = dx; cp.out = kout; cp.partials = p->d_partials.get(); cp.atab = p->d_atab.get();
     cp.wtab = p->d_wtab.get(); cp.twtab = p->d_wtab.get() + 2 * p->nwin; cp.r2scale = p->r2scale;
@@ -1984,13 +1978,11 @@ int hssfsst_exec_ragged(hssfsst_plan* p, const float* x, int64_t x_len, const in
     // (the canonical-class band in STACK modes takes the canonical kernel's arithmetic, as every single exec of it does; the
     //  general kernels give other -- equally accurate -- bits there)
     if (fast && p->nt == 16 && p->rq == 8 && plan_is_canon(p))
-        rc = canon_dispatch(p, [&](auto KL, auto KN) { return launch_canon_band<decltype(KL)::value, decltype(KN)::value, true>(p, cp, p->rtab_nchunks, st); });
+        rc = canon_dispatch(p, [&](auto KL, auto KN) { return launch_canon_band<decltype(KL)::value, decltype(KN)::value, true>(p, cx, cp, p->rtab_nchunks); });
     else
-        rc = launch_core128_plain<true>(p, cp, p->rtab_nchunks, st, fast, canon);
+        rc = launch_core128_plain<true>(p, cx, cp, p->rtab_nchunks, fast, canon);
     if (rc != 0) return rc;
-    p->last_fused = 0;
-    p->last_zpath = 0;
-    if ((rc = timing_core_done(p, st)) != 0) return rc;
+    if ((rc = timing_core_done(p, cx)) != 0) return rc;
     if (p->mode == HSSFSST_MODE_STACK) {
         float4* stats = reinterpret_cast<float4*>(p->d_stats.get());
         hipLaunchKernelGGL(hssfsst::fsst_ragged_stats_kernel, dim3(static_cast<unsigned>(batch)), dim3(64), 0, st, p->d_partials.get(), d_rsig, stats, p->K);
@@ -2005,7 +1997,8 @@ int hssfsst_exec_ragged(hssfsst_plan* p, const float* x, int64_t x_len, const in
                                stats, static_cast<int>(batch), p->K);
         HIP_TRY(hipGetLastError());
     }
-    if ((rc = timing_end(p, st, false)) != 0) return rc;
+    exec_report(p, cx);
+    if ((rc = timing_end(p, cx, false)) != 0) return rc;
     return exec_finish(p, out, dout, no * p->out_es, x_on_device, out_on_device, st);
 }
 

@@ -734,6 +734,45 @@ def test_zpath_preference_is_bit_identical(batch):
         tf.set_zpath("fastest")
 
 
+def test_timing_counts_execs_and_splits_by_zpath():
+    """hssfsst_plan_timing (FSST.timing) after set_timing(True) and k execs: n_calls == k on every z-score path; an exec whose
+    z-score was part of its one launch (team kernel, one CU per signal) reports kernel time only -- the second component is
+    exactly zero, also where the team launch has gated launches queued behind it -- and two launches report a positive
+    z-score time.  The dataset loop's call (one CPU frame: the team launch, its features stored to pinned host memory) counts
+    the same way."""
+    k = 3
+    X = torch.from_numpy(synth.pcg_windows(512, 2000, seed=11)).cuda()
+    tf = FSST(1000, KAISER, truncate_freq=BAND, stack=True)
+    full_chip = torch.cuda.get_device_properties(0).multi_processor_count == 256
+    for zp, want in (("team", 2), ("one_cu", 1), ("two_launch", 0)):
+        tf.set_zpath(zp)
+        tf.batch(X)                                      # (untimed: buffers, occupancy queries)
+        tf.set_timing(True)
+        for _ in range(k):
+            tf.batch(X)
+        core, norm, n_calls = tf.timing()
+        path = tf.check()
+        tf.set_timing(False)
+        if full_chip:
+            assert path == want, (zp, path)
+        assert n_calls == k, (zp, n_calls)
+        assert core > 0.0, (zp, core)
+        if path != 0:
+            assert norm == 0.0, (zp, norm)
+        else:
+            assert norm > 0.0, (zp, norm)
+    tf.set_zpath("auto")
+    one = torch.from_numpy(synth.pcg_windows(1, 2000, seed=12)[0]).reshape(2000, 1)
+    tf(one)
+    tf.set_timing(True)
+    for _ in range(k):
+        tf(one)
+    core, norm, n_calls = tf.timing()
+    tf.set_timing(False)
+    assert n_calls == k and core > 0.0 and norm == 0.0, (core, norm, n_calls)
+    assert tf.last_kernel().startswith("fsst_team16_kernel<4, 22, 16, 2>"), tf.last_kernel()
+
+
 @pytest.mark.parametrize("n,batch", [(2000, 300), (1999, 7), (130, 33), (4000, 5)])
 def test_second_canonical_band(oracle_mod, n, batch):
     """The canonical-class kernels are a template over the kept band, not one benchmark point: [25, 400] Hz at fs = 2000 (rows
