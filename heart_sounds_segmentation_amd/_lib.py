@@ -246,6 +246,15 @@ def lib():
         L.hssfsst_resample_plan_create_ragged.restype = c_int
         L.hssfsst_resample_exec_ragged.argtypes = [vp, vp, c_int, c_i64, vp, vp, c_i64, c_int, vp, c_int, vp, c_int, vp]
         L.hssfsst_resample_exec_ragged.restype = c_int
+        fpp = ctypes.POINTER(ctypes.c_void_p)
+        L.hssfsst_segmenter_create.argtypes = [ctypes.POINTER(vp), c_int, c_int, c_int, fpp, fpp, vp, vp]
+        L.hssfsst_segmenter_create.restype = c_int
+        L.hssfsst_segmenter_destroy.argtypes = [vp]
+        L.hssfsst_segmenter_destroy.restype = c_int
+        L.hssfsst_segmenter_info.argtypes = [vp, ip, ip, ip, ip]
+        L.hssfsst_segmenter_info.restype = c_int
+        L.hssfsst_segmenter_exec.argtypes = [vp, vp, c_int, c_i64, c_i64, vp, vp, vp, vp]
+        L.hssfsst_segmenter_exec.restype = c_int
         L.hssfsst_device_count.restype = c_int
         L.hssfsst_version.restype = c_int
         L.hssfsst_last_error.restype = ctypes.c_char_p

@@ -8,13 +8,21 @@ BiLSTM(in -> 2xH) -> ReLU -> Dropout(0.2) -> BiLSTM(2H -> 2xH), seeded with the 
 (h, c) -> ReLU -> Dropout -> Linear(2H -> 4) -> LogSoftmax over classes (segmenter.py:70-87).
 Stock ``nn.LSTM`` (MIOpen): plumbing, not the product.  Pinned by tests/golden/segmenter.npz, which
 was produced by the reference class itself (tests/golden/make_golden.py).
+
+``SegmenterHead.hip()`` gives the same forward pass as HIP kernels behind the C ABI (include/hssfsst.h:
+hssfsst_segmenter_exec; csrc/segmenter_lstm.hpp), inference only: ``segment(fsst, head.hip(), windows)`` is
+config 4 with nothing leaving the device and no torch op between the FSST kernel and the log-probs.
 """
 from __future__ import annotations
 
 from typing import Optional
 
+import ctypes
+
 import torch
 from torch import nn
+
+from . import _lib
 
 
 class SegmenterHead(nn.Module):
@@ -60,7 +68,92 @@ class SegmenterHead(nn.Module):
         y, _ = self.lstm_2(self.drop(torch.relu(y)), carry)
         return torch.log_softmax(self.linear(self.drop(torch.relu(y))), dim=2)
 
+    def hip(self, device=None) -> "HipSegmenter":
+        """This module's forward pass as HIP kernels: a callable holding a segmenter plan made from the CURRENT
+        ``state_dict``, ``h0`` and ``c0`` (weights changed afterwards do not reach it: call ``hip()`` again).  Inference
+        only: a module in training mode is refused with RuntimeError (dropout would be active); no CPU path: without a
+        GPU, RuntimeError.  ``device`` defaults to the module's device when that is a GPU, else the current one."""
+        return HipSegmenter(self, device)
 
-def segment(fsst, head: SegmenterHead, windows: torch.Tensor) -> torch.Tensor:
-    """windows (B, n) -> HIP FSST features (B, n, 2K), kept on the device -> (B, n, 4) log-probs."""
+
+_LSTM_KEYS = ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0",
+              "weight_ih_l0_reverse", "weight_hh_l0_reverse", "bias_ih_l0_reverse", "bias_hh_l0_reverse")
+_DTYPES = {torch.float32: _lib.DTYPE_F32, torch.float16: _lib.DTYPE_F16, torch.bfloat16: _lib.DTYPE_BF16}
+
+
+class HipSegmenter:
+    """What ``SegmenterHead.hip()`` returns.  ``seg(feats)``: feats a (B, T, F) float32 / float16 / bfloat16 tensor on
+    the plan's GPU -> (B, T, 4) float32 log-probs on the same device, no autograd graph, enqueued on the current stream.
+    The module's ``h0`` / ``c0`` fix B (the reference ties the model to one batch size, segmenter.py:38-41): another B
+    raises ValueError unless ``h0`` and ``c0`` of shape (2, B, H) are passed to the call."""
+
+    def __init__(self, head: SegmenterHead, device=None):
+        if head.training:
+            raise RuntimeError("SegmenterHead.hip(): the module is in training mode; the HIP path is inference only "
+                               "(dropout is the identity): call .eval() first")
+        sd = {k: v.detach().to("cpu", torch.float32).contiguous() for k, v in head.state_dict().items()}
+        self.input_size, self.hidden_size = head.lstm_1.input_size, head.lstm_1.hidden_size
+        if device is None:
+            device = head.h0.device if head.h0.device.type == "cuda" else "cuda"
+        self._plan = None
+        L = _lib.lib()
+        _lib.guard_fork()
+        if not torch.cuda.is_available():
+            raise RuntimeError("SegmenterHead.hip(): no GPU; the segmenter kernels have no CPU path")
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError(f"SegmenterHead.hip(): device {self.device} is not a GPU; there is no CPU path")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+
+        def ptrs(prefix):
+            return (ctypes.c_void_p * 8)(*[sd[f"{prefix}.{k}"].data_ptr() for k in _LSTM_KEYS])
+        plan = ctypes.c_void_p()
+        _lib.check(L.hssfsst_segmenter_create(ctypes.byref(plan), self.device.index, self.input_size, self.hidden_size,
+                                              ptrs("lstm_1"), ptrs("lstm_2"), sd["linear.weight"].data_ptr(),
+                                              sd["linear.bias"].data_ptr()), "hssfsst_segmenter_create")
+        self._plan = plan
+        self.h0 = head.h0.detach().to(self.device, torch.float32).contiguous().clone()
+        self.c0 = head.c0.detach().to(self.device, torch.float32).contiguous().clone()
+
+    def __del__(self):
+        if getattr(self, "_plan", None):
+            try:
+                _lib.lib().hssfsst_segmenter_destroy(self._plan)
+            except Exception:
+                pass
+            self._plan = None
+
+    def __call__(self, feats: torch.Tensor, h0: Optional[torch.Tensor] = None, c0: Optional[torch.Tensor] = None) -> torch.Tensor:
+        if feats.dim() != 3 or feats.shape[2] != self.input_size or feats.shape[0] < 1 or feats.shape[1] < 1:
+            raise ValueError(f"HipSegmenter: features of shape (B, T, {self.input_size}) expected, got {tuple(feats.shape)}")
+        if feats.device != self.device:
+            raise ValueError(f"HipSegmenter: features on {feats.device}, the plan on {self.device}")
+        if feats.dtype not in _DTYPES:
+            raise ValueError(f"HipSegmenter: float32, float16 or bfloat16 features expected, got {feats.dtype}")
+        B, T = int(feats.shape[0]), int(feats.shape[1])
+        if (h0 is None) != (c0 is None):
+            raise ValueError("HipSegmenter: pass both h0 and c0, or neither")
+        if h0 is None:
+            if self.h0.shape[1] != B:
+                raise ValueError(f"HipSegmenter: batch {B}, but the module's h0 / c0 were made for batch {self.h0.shape[1]} "
+                                 "(pass h0 and c0 of shape (2, B, H) to the call)")
+            h0, c0 = self.h0, self.c0
+        else:
+            want = (2, B, self.hidden_size)
+            if tuple(h0.shape) != want or tuple(c0.shape) != want:
+                raise ValueError(f"HipSegmenter: h0 and c0 of shape {want} expected, got {tuple(h0.shape)} and {tuple(c0.shape)}")
+            h0 = h0.detach().to(self.device, torch.float32).contiguous()
+            c0 = c0.detach().to(self.device, torch.float32).contiguous()
+        feats = feats.detach().contiguous()
+        out = torch.empty((B, T, 4), dtype=torch.float32, device=self.device)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        _lib.check(_lib.lib().hssfsst_segmenter_exec(self._plan, feats.data_ptr(), _DTYPES[feats.dtype], B, T, h0.data_ptr(),
+                                                     c0.data_ptr(), out.data_ptr(), stream), "hssfsst_segmenter_exec")
+        return out
+
+
+def segment(fsst, head, windows: torch.Tensor) -> torch.Tensor:
+    """windows (B, n) -> HIP FSST features (B, n, 2K), kept on the device -> (B, n, 4) log-probs.  ``head``: a
+    ``SegmenterHead`` (stock ``nn.LSTM``) or what its ``hip()`` returns (the HIP kernels)."""
     return head(fsst.batch(windows))

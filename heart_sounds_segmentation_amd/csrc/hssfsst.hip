@@ -35,6 +35,7 @@
 #include "fourier_resample.hpp"
 #include "fourier_resample_gpu.hpp"
 #include "fourier_resample_ragged.hpp"
+#include "segmenter_lstm.hpp"
 #include <cstdlib>
 
 namespace {
@@ -2712,6 +2713,200 @@ int hssfsst_stream_step(hssfsst_plan* p, float* tape, int64_t tape_len, int64_t 
         HIP_TRY(hipStreamSynchronize(st));
     }
     return 0;
+}
+
+}  // extern "C"
+
+// BiLSTM segmenter (hssfsst.h: hssfsst_segmenter_create): the model's weights, uploaded once in the layouts the kernels of
+// csrc/segmenter_lstm.hpp consume, plus the scratch of its execs (owned by the plan, grown on demand, freed with it).
+struct hssfsst_segmenter {
+    int device = -1;
+    int F = 0, H = 0;
+    struct Layer {
+        int F = 0, Fp = 0;                               // input width and its multiple of 32
+        DevBuf<float> d_wt;                              // [dir][Fp][4 Hp]: W_ih^T, columns in (unit tile, gate, unit) order
+        DevBuf<float> d_bias;                            // [dir][4 Hp]: b_ih + b_hh, same order
+        DevBuf<hssfsst::seg_h8> d_whh;                   // [dir][wave][K block][tile x gate][lane]{hi, lo}: W_hh x wscale, split f16
+        float inv_scale = 1.0f;                          // 1 / (wscale x kSegHScale)
+    } layer[2];
+    DevBuf<float> d_lin;                                 // linear.weight (4, 2H) | linear.bias (4)
+    DevBuf<float> d_pre;                                 // [dir][batch tile][Tc][gate tile][lane][4]: one chunk's input projection
+    DevBuf<float> d_y1, d_y2;                            // (B, T, 2H): the layers' outputs
+    DevBuf<float> d_state;                               // [h, c][dir][Bp][Hp]: carried from chunk to chunk and from layer 1 to layer 2
+};
+
+namespace {
+
+constexpr size_t kSegPreBytes = size_t(128) << 20;       // bound of the projection scratch: sets the steps per chunk
+constexpr int kSegMaxChunk = 4096;                       // ... and no launch walks more steps than this
+
+// src: {weight_ih, weight_hh, bias_ih, bias_hh} x {forward, reverse} of one nn.LSTM layer, as in its state_dict
+int seg_upload_layer(hssfsst_segmenter::Layer& L, int F, int H, const float* const* src)
+{
+    constexpr int Hp = hssfsst::kSegHp, N = 4 * Hp;
+    L.F = F;
+    L.Fp = (F + 31) / 32 * 32;
+    std::vector<float> wt(static_cast<size_t>(2) * L.Fp * N, 0.0f), bias(static_cast<size_t>(2) * N, 0.0f);
+    float wmax = 0.0f;
+    for (int d = 0; d < 2; ++d) {
+        const float* whh = src[4 * d + 1];
+        for (size_t i = 0; i < static_cast<size_t>(4) * H * H; ++i) wmax = std::fmax(wmax, std::fabs(whh[i]));
+    }
+    // power-of-two scale that puts the largest |W_hh| in [2^12, 2^13): the lo halves of the split are normal f16 numbers down to
+    // weights 2^-26 times the largest one, and a sum of 256 products with |h| x 2^10 stays far below the f32 range
+    int e = 0;
+    float wscale = 1.0f;
+    if (wmax > 0.0f && std::isfinite(wmax)) { (void)std::frexp(wmax, &e); wscale = std::ldexp(1.0f, 13 - e); }
+    L.inv_scale = 1.0f / (wscale * hssfsst::kSegHScale);
+    std::vector<_Float16> stream(static_cast<size_t>(2) * hssfsst::kSegWaves * hssfsst::kSegKb * 8 * 64 * 16, static_cast<_Float16>(0.0f));
+    for (int d = 0; d < 2; ++d) {
+        const float *wih = src[4 * d], *whh = src[4 * d + 1], *bih = src[4 * d + 2], *bhh = src[4 * d + 3];
+        for (int ut = 0; ut < Hp / 16; ++ut)
+            for (int g = 0; g < 4; ++g)
+                for (int c = 0; c < 16; ++c) {
+                    const int u = ut * 16 + c, n = (ut * 4 + g) * 16 + c;
+                    if (u >= H) continue;
+                    const size_t row = static_cast<size_t>(g) * H + u;
+                    bias[static_cast<size_t>(d) * N + n] = bih[row] + bhh[row];
+                    for (int k = 0; k < F; ++k) wt[(static_cast<size_t>(d) * L.Fp + k) * N + n] = wih[row * F + k];
+                }
+        for (int w = 0; w < hssfsst::kSegWaves; ++w)
+            for (int kb = 0; kb < hssfsst::kSegKb; ++kb)
+                for (int q = 0; q < 8; ++q)
+                    for (int lane = 0; lane < 64; ++lane) {
+                        const int u = (w * 2 + (q >> 2)) * 16 + (lane & 15), g = q & 3;
+                        if (u >= H) continue;
+                        _Float16* dst = stream.data() + ((((static_cast<size_t>(d) * hssfsst::kSegWaves + w) * hssfsst::kSegKb + kb) * 8 + q) * 64 + lane) * 16;
+                        for (int j = 0; j < 8; ++j) {
+                            const int k = kb * 32 + 8 * (lane >> 4) + j;
+                            if (k >= H) continue;
+                            const float v = whh[(static_cast<size_t>(g) * H + u) * H + k] * wscale;
+                            const _Float16 hi = static_cast<_Float16>(v);
+                            dst[j] = hi;
+                            dst[8 + j] = static_cast<_Float16>(v - static_cast<float>(hi));
+                        }
+                    }
+    }
+    if (int rc = L.d_wt.upload(wt.data(), wt.size())) return rc;
+    if (int rc = L.d_bias.upload(bias.data(), bias.size())) return rc;
+    return L.d_whh.upload(reinterpret_cast<const hssfsst::seg_h8*>(stream.data()), stream.size() / 8);
+}
+
+int seg_launch_check(const char* what)
+{
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(HSSFSST_EHIP, "segmenter_exec: launch of %s failed: %s", what, hipGetErrorString(e));
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int hssfsst_segmenter_create(hssfsst_segmenter** out, int device, int input_size, int hidden, const float* const* lstm_1,
+                             const float* const* lstm_2, const float* linear_weight, const float* linear_bias)
+{
+    if (!out) return fail(HSSFSST_EINVAL, "segmenter_create: out is NULL");
+    *out = nullptr;
+    if (input_size < 1 || hidden < 1 || device < 0 || !lstm_1 || !lstm_2 || !linear_weight || !linear_bias)
+        return fail(HSSFSST_EINVAL, "segmenter_create: bad argument (device=%d input_size=%d hidden=%d, or a NULL array)", device, input_size, hidden);
+    for (int i = 0; i < 8; ++i)
+        if (!lstm_1[i] || !lstm_2[i]) return fail(HSSFSST_EINVAL, "segmenter_create: bad argument (weight array %d of a layer is NULL)", i);
+    if (hidden > hssfsst::kSegHp)
+        return fail(HSSFSST_EUNSUPPORTED, "segmenter_create: hidden sizes above %d are not supported (hidden=%d)", hssfsst::kSegHp, hidden);
+    if (input_size > (1 << 20)) return fail(HSSFSST_EUNSUPPORTED, "segmenter_create: input sizes above 2^20 are not supported (input_size=%d)", input_size);
+    if (int rc = check_device("segmenter_create", device)) return rc;
+    DEVICE_SCOPE(device);
+    std::unique_ptr<hssfsst_segmenter> p(new (std::nothrow) hssfsst_segmenter());
+    if (!p) return fail(HSSFSST_ENOMEM, "segmenter_create: host allocation failed");
+    p->device = device; p->F = input_size; p->H = hidden;
+    try {
+        if (int rc = seg_upload_layer(p->layer[0], input_size, hidden, lstm_1)) return rc;
+        if (int rc = seg_upload_layer(p->layer[1], 2 * hidden, hidden, lstm_2)) return rc;
+        std::vector<float> lin(static_cast<size_t>(8) * hidden + 4);
+        std::memcpy(lin.data(), linear_weight, static_cast<size_t>(8) * hidden * sizeof(float));
+        std::memcpy(lin.data() + static_cast<size_t>(8) * hidden, linear_bias, 4 * sizeof(float));
+        if (int rc = p->d_lin.upload(lin.data(), lin.size())) return rc;
+    } catch (const std::bad_alloc&) {
+        return fail(HSSFSST_ENOMEM, "segmenter_create: out of host memory");
+    }
+    *out = p.release();
+    return 0;
+}
+
+int hssfsst_segmenter_destroy(hssfsst_segmenter* p)
+{
+    if (!p) return 0;
+    DeviceGuard device_guard_(p->device);
+    delete p;                                            // (the buffers free themselves)
+    return 0;
+}
+
+int hssfsst_segmenter_info(const hssfsst_segmenter* p, int* input_size, int* hidden, int* max_hidden, int* device)
+{
+    if (max_hidden) *max_hidden = hssfsst::kSegHp;       // (a property of the library: answered for a NULL plan too)
+    if (!p) return fail(HSSFSST_EINVAL, "segmenter_info: plan is NULL");
+    if (input_size) *input_size = p->F;
+    if (hidden) *hidden = p->H;
+    if (device) *device = p->device;
+    return 0;
+}
+
+int hssfsst_segmenter_exec(hssfsst_segmenter* p, const void* feats, int feats_dtype, int64_t batch, int64_t steps, const float* h0,
+                           const float* c0, float* logp, void* stream)
+{
+    if (!p || !feats || !h0 || !c0 || !logp || batch < 1 || steps < 1)
+        return fail(HSSFSST_EINVAL, "segmenter_exec: bad argument (batch=%lld steps=%lld, or a NULL pointer)", static_cast<long long>(batch),
+                    static_cast<long long>(steps));
+    if (feats_dtype != HSSFSST_DTYPE_F32 && feats_dtype != HSSFSST_DTYPE_F16 && feats_dtype != HSSFSST_DTYPE_BF16)
+        return fail(HSSFSST_EINVAL, "segmenter_exec: unknown feature dtype %d", feats_dtype);
+    if (batch > 16 * 32768 || steps > 0x7fffffffLL / 8)
+        return fail(HSSFSST_EINVAL, "segmenter_exec: batch %lld or steps %lld too large", static_cast<long long>(batch), static_cast<long long>(steps));
+    DEVICE_SCOPE(p->device);
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const int B = static_cast<int>(batch), T = static_cast<int>(steps), H = p->H;
+    const int nbt = (B + hssfsst::kSegRows - 1) / hssfsst::kSegRows, Bp = nbt * hssfsst::kSegRows;
+    const size_t step_bytes = static_cast<size_t>(2) * nbt * hssfsst::kSegGateTiles * hssfsst::kSegTileFloats * sizeof(float);
+    int Tc = static_cast<int>(std::max<size_t>(1, kSegPreBytes / step_bytes));
+    Tc = std::min(std::min(Tc, kSegMaxChunk), T);
+    int rc;
+    if ((rc = p->d_pre.grow(step_bytes / sizeof(float) * Tc)) != 0) return rc;
+    const size_t ylen = static_cast<size_t>(B) * T * 2 * H;
+    if ((rc = p->d_y1.grow(ylen)) != 0) return rc;
+    if ((rc = p->d_y2.grow(ylen)) != 0) return rc;
+    const size_t nstate = static_cast<size_t>(4) * Bp * hssfsst::kSegHp;
+    if ((rc = p->d_state.grow(nstate)) != 0) return rc;
+    hipLaunchKernelGGL(hssfsst::seg_state_init_kernel, dim3(static_cast<unsigned>((nstate + 255) / 256)), dim3(256), 0, st, h0, c0,
+                       p->d_state.get(), B, H, Bp);
+    if ((rc = seg_launch_check("seg_state_init_kernel")) != 0) return rc;
+    for (int l = 0; l < 2; ++l) {
+        const hssfsst_segmenter::Layer& L = p->layer[l];
+        hssfsst::SegProjArgs pa{};
+        pa.x = l ? static_cast<const void*>(p->d_y1.get()) : feats;
+        pa.x_dtype = l ? HSSFSST_DTYPE_F32 : feats_dtype;
+        pa.relu = l;
+        pa.B = B; pa.T = T; pa.F = L.F; pa.Fp = L.Fp;
+        pa.wt = L.d_wt.get(); pa.bias = L.d_bias.get(); pa.pre = p->d_pre.get(); pa.Tc = Tc;
+        hssfsst::SegRecArgs ra{};
+        ra.pre = p->d_pre.get(); ra.whh = L.d_whh.get(); ra.state = p->d_state.get();
+        ra.y = l ? p->d_y2.get() : p->d_y1.get();
+        ra.B = B; ra.T = T; ra.H = H; ra.Bp = Bp; ra.Tc = Tc; ra.inv_scale = L.inv_scale;
+        // the forward direction takes its chunks upwards, the reverse direction the mirrored ones downwards: both walk n steps per launch
+        for (int t0 = 0; t0 < T; t0 += Tc) {
+            const int n = std::min(Tc, T - t0);
+            pa.n = ra.n = n;
+            pa.t0[0] = ra.t0[0] = t0;
+            pa.t0[1] = ra.t0[1] = T - t0 - n;
+            hipLaunchKernelGGL(hssfsst::seg_proj_kernel, dim3(4 * hssfsst::kSegHp / 64, static_cast<unsigned>(nbt * ((n + 7) / 8)), 2), dim3(256), 0, st, pa);
+            if ((rc = seg_launch_check("seg_proj_kernel")) != 0) return rc;
+            hipLaunchKernelGGL(hssfsst::seg_rec_kernel, dim3(static_cast<unsigned>(nbt), 2), dim3(64 * hssfsst::kSegWaves), 0, st, ra);
+            if ((rc = seg_launch_check("seg_rec_kernel")) != 0) return rc;
+        }
+    }
+    const long long rows = static_cast<long long>(B) * T;
+    hipLaunchKernelGGL(hssfsst::seg_head_kernel, dim3(static_cast<unsigned>((rows + 3) / 4)), dim3(256), 0, st, p->d_y2.get(), p->d_lin.get(),
+                       p->d_lin.get() + static_cast<size_t>(8) * H, logp, rows, 2 * H);
+    return seg_launch_check("seg_head_kernel");
 }
 
 }  // extern "C"

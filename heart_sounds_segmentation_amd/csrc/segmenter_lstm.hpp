@@ -1,0 +1,326 @@
+// segmenter_lstm.hpp -- inference kernels of the BiLSTM segmenter (hssfsst.h: hssfsst_segmenter_exec).
+//
+// The reference's HeartSoundSegmenter.forward (hss/model/segmenter.py:70-87): BiLSTM -> ReLU -> BiLSTM seeded with the first
+// layer's final (h, c) -> ReLU -> Linear(2H -> 4) -> log_softmax.  Three kernels per layer chunk plus one head pass:
+//
+//   seg_proj_kernel   pre[dir][batch tile][t][gate tile][lane] = x[b, t, :] . W_ih^T + b_ih + b_hh for both directions, exact f32
+//                     matrix instruction (v_mfma_f32_16x16x4_f32), LDS tiled, parallel over time; written in the register
+//                     image of the recurrence's accumulators so that kernel reads one float4 per lane and tile;
+//   seg_rec_kernel    the recurrence: one workgroup per (direction, 16 batch rows), 8 waves, loops over the chunk's steps itself;
+//                     h (as split f16 operands, in LDS) and c (registers) never leave the CU; h . W_hh^T as f16 hi + lo products
+//                     (hi.hi + hi.lo + lo.hi) on v_mfma_f32_16x16x32_f16 with W_hh streamed from L2 in the order the waves eat it;
+//                     no workgroup waits for another one;
+//   seg_head_kernel   ReLU -> Linear -> log_softmax, one wave per (b, t).
+//
+// Every hidden size runs on the one padded geometry kSegHp = 256 units (16 unit tiles x 4 gates, K = 256): padded units have zero
+// weights and zero state, so they stay exactly zero (i = f = o = 1/2, g = 0, c' = c / 2 = 0).
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace hssfsst {
+
+constexpr int kSegHp = 256;                    // padded hidden size == the supported maximum
+constexpr int kSegRows = 16;                   // batch rows of one workgroup (the matrix instruction's M)
+constexpr int kSegWaves = 8;                   // waves of a recurrence workgroup; each owns two unit tiles (x 4 gates)
+constexpr int kSegKb = kSegHp / 32;            // K blocks of the recurrent product
+constexpr int kSegGateTiles = 4 * kSegHp / 16; // 16-column tiles of a direction's 4 Hp gate columns: tile = unit tile * 4 + gate
+constexpr int kSegTileFloats = 256;            // one 16 x 16 tile as the accumulator image [lane 64][4]
+constexpr float kSegHScale = 1024.0f;          // power-of-two scale of h before the f16 split (|h| < 1)
+
+using seg_h8 = _Float16 __attribute__((ext_vector_type(8)));
+using seg_f4 = float __attribute__((ext_vector_type(4)));
+
+// element type of a layer input: 0 float32, 2 float16, 3 bfloat16 (HSSFSST_DTYPE_*), converted on load
+__device__ __forceinline__ float seg_load_x(const void* x, size_t i, int dtype)
+{
+    if (dtype == 2) return static_cast<float>(static_cast<const _Float16*>(x)[i]);
+    if (dtype == 3) return static_cast<float>(static_cast<const __bf16*>(x)[i]);
+    return static_cast<const float*>(x)[i];
+}
+
+struct SegProjArgs {
+    const void* x;          // (B, T, F) of x_dtype
+    int x_dtype, relu;      // relu: rectify on load (layer 2 reads layer 1's un-rectified output)
+    int B, T, F, Fp;        // Fp = F rounded up to 32: rows of wt
+    const float* wt;        // [dir][Fp][4 Hp]: W_ih transposed, columns permuted to (unit tile, gate, unit), zero padded
+    const float* bias;      // [dir][4 Hp]: b_ih + b_hh, same column order
+    float* pre;             // [dir][batch tile][Tc][gate tile][lane][4]
+    int Tc, n;              // chunk pitch of pre and the steps of this launch
+    int t0[2];              // first time step of the launch's chunk, per direction
+};
+
+// Block = 4 waves: 8 time steps x 16 batch rows (M = 128) by 64 gate columns; wave w: steps 2w, 2w + 1, all four column tiles.
+// Grid (16 column blocks, batch tiles x ceil(n / 8), 2 directions).
+__global__ __launch_bounds__(256) void seg_proj_kernel(SegProjArgs a)
+{
+    constexpr int KB = 32, AS = KB + 1, BS = 80;
+    __shared__ float As[128 * AS];
+    __shared__ __attribute__((aligned(16))) float Bs[KB * BS];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int dir = blockIdx.z;
+    const int tblocks = (a.n + 7) / 8;
+    const int bt = blockIdx.y / tblocks, tb = blockIdx.y - bt * tblocks;
+    const int n0 = blockIdx.x * 64;
+    const float* wt = a.wt + static_cast<size_t>(dir) * a.Fp * (4 * kSegHp);
+    seg_f4 acc[2][4];
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) acc[j][i] = seg_f4{0.0f, 0.0f, 0.0f, 0.0f};
+    for (int k0 = 0; k0 < a.Fp; k0 += KB) {
+        // A: row m = step * 16 + batch row, 32 consecutive k per 32 threads
+#pragma unroll 4
+        for (int i = 0; i < 16; ++i) {
+            const int m = (tid >> 5) + 8 * i, k = k0 + (tid & 31);
+            const int tl = tb * 8 + (m >> 4), b = bt * kSegRows + (m & 15);
+            float v = 0.0f;
+            if (tl < a.n && b < a.B && k < a.F) {
+                v = seg_load_x(a.x, (static_cast<size_t>(b) * a.T + (a.t0[dir] + tl)) * a.F + k, a.x_dtype);
+                if (a.relu) v = fmaxf(v, 0.0f);
+            }
+            As[m * AS + (tid & 31)] = v;
+        }
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int e = tid + 256 * i, k = e >> 4, c4 = (e & 15) * 4;
+            const float4 v = *reinterpret_cast<const float4*>(wt + static_cast<size_t>(k0 + k) * (4 * kSegHp) + n0 + c4);
+            *reinterpret_cast<float4*>(&Bs[k * BS + c4]) = v;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int kk = 0; kk < KB / 4; ++kk) {
+            const int k = kk * 4 + (lane >> 4);
+            const float a0 = As[((2 * w) * 16 + (lane & 15)) * AS + k], a1 = As[((2 * w + 1) * 16 + (lane & 15)) * AS + k];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const float b = Bs[k * BS + i * 16 + (lane & 15)];
+                acc[0][i] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b, acc[0][i], 0, 0, 0);
+                acc[1][i] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b, acc[1][i], 0, 0, 0);
+            }
+        }
+        __syncthreads();
+    }
+    // accumulator image: lane l, register r = row 4 (l >> 4) + r (batch row), column l & 15
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int tl = tb * 8 + 2 * w + j;
+        if (tl >= a.n) continue;
+        const int nbt = (a.B + kSegRows - 1) / kSegRows;
+        float* dst = a.pre + ((static_cast<size_t>(dir) * nbt + bt) * a.Tc + tl) * (kSegGateTiles * kSegTileFloats);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int col = n0 + i * 16;
+            const float bv = a.bias[dir * (4 * kSegHp) + col + (lane & 15)];
+            seg_f4 v = acc[j][i];
+            v += bv;
+            *reinterpret_cast<seg_f4*>(dst + (col >> 4) * kSegTileFloats + lane * 4) = v;
+        }
+    }
+}
+
+// state[0 = h, 1 = c][dir][padded batch][Hp] <- h0, c0 (2, B, H); the padding is zero
+__global__ __launch_bounds__(256) void seg_state_init_kernel(const float* h0, const float* c0, float* state, int B, int H, int Bp)
+{
+    const size_t per = static_cast<size_t>(2) * Bp * kSegHp;
+    const size_t i = static_cast<size_t>(blockIdx.x) * 256 + threadIdx.x;
+    if (i >= 2 * per) return;
+    const int which = static_cast<int>(i / per);
+    const size_t r = i - which * per;
+    const int u = static_cast<int>(r % kSegHp);
+    const int b = static_cast<int>((r / kSegHp) % Bp);
+    const int dir = static_cast<int>(r / (static_cast<size_t>(kSegHp) * Bp));
+    float v = 0.0f;
+    if (b < B && u < H) v = (which ? c0 : h0)[(static_cast<size_t>(dir) * B + b) * H + u];
+    state[i] = v;
+}
+
+struct SegRecArgs {
+    const float* pre;       // [dir][batch tile][Tc][gate tile][lane][4]
+    const seg_h8* whh;      // [dir][wave][K block][tile x gate][lane]{hi, lo}: W_hh x wscale, split, in consumption order
+    float* state;           // [h, c][dir][Bp][Hp]: read at the start, written at the end (chunks and layers chain through it)
+    float* y;               // (B, T, 2 H) float32 layer output, un-rectified
+    int B, T, H, Bp, Tc, n;
+    int t0[2];
+    float inv_scale;        // 1 / (wscale x kSegHScale)
+};
+
+__device__ __forceinline__ float seg_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
+__device__ __forceinline__ float seg_tanh(float x) { return 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(-2.0f * x)) - 1.0f; }
+
+// h of one lane's (unit, 4 rows) into the split-f16 A-operand image: [K block][k quarter][row 16][8 halves], hi and lo planes
+__device__ __forceinline__ void seg_put_h(_Float16* hi, _Float16* lo, int unit, int row0, seg_f4 h)
+{
+    const int base = ((unit >> 3) * kSegRows) * 8 + (unit & 7);          // ((kb * 4 + quarter) * 16 + row) * 8 + j
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const float v = h[r] * kSegHScale;
+        const _Float16 x1 = static_cast<_Float16>(v);
+        const _Float16 x2 = static_cast<_Float16>(v - static_cast<float>(x1));
+        hi[base + (row0 + r) * 8] = x1;
+        lo[base + (row0 + r) * 8] = x2;
+    }
+}
+
+// Grid (batch tiles, 2 directions), block 512.  Direction 0 walks the chunk's steps upwards, direction 1 downwards.
+__global__ __launch_bounds__(512) void seg_rec_kernel(SegRecArgs a)
+{
+    constexpr int HB = kSegKb * 4 * kSegRows * 8;                       // halves of one plane of the h image
+    __shared__ __attribute__((aligned(16))) _Float16 hbuf[2][2][HB];   // [buffer][hi, lo]
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int bt = blockIdx.x, dir = blockIdx.y;
+    const int nbt = gridDim.x;
+    const int row0 = (lane >> 4) * 4, b0 = bt * kSegRows;
+    const size_t plane = static_cast<size_t>(2) * a.Bp * kSegHp;
+    float* hst = a.state + (static_cast<size_t>(dir) * a.Bp + b0) * kSegHp;
+    float* cst = hst + plane;
+
+    seg_f4 c[2], h[2];
+#pragma unroll
+    for (int tl = 0; tl < 2; ++tl) {
+        const int unit = (w * 2 + tl) * 16 + (lane & 15);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            h[tl][r] = hst[(row0 + r) * kSegHp + unit];
+            c[tl][r] = cst[(row0 + r) * kSegHp + unit];
+        }
+        seg_put_h(hbuf[0][0], hbuf[0][1], unit, row0, h[tl]);
+    }
+
+    // this wave's weight stream: per K block 8 (tile, gate) fragments of {hi, lo} x 64 lanes
+    const seg_h8* const wq0 = a.whh + ((static_cast<size_t>(dir) * kSegWaves + w) * kSegKb * 8 * 64 + lane) * 2;
+    const seg_h8* wq = wq0;
+    const float* prew = a.pre + (static_cast<size_t>(dir) * nbt + bt) * a.Tc * (kSegGateTiles * kSegTileFloats)
+                        + (w * 8) * kSegTileFloats + lane * 4;
+    auto pre_at = [&](int s) { return prew + static_cast<size_t>(dir ? a.n - 1 - s : s) * (kSegGateTiles * kSegTileFloats); };
+
+    seg_h8 wres[8][2];                                                  // K block 0 of every tile: resident for the whole launch
+    seg_h8 wb[2][4][2];                                                 // the rest streams: double buffer of half a K block
+    seg_f4 pn[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        wres[q][0] = wq[q * 128];
+        wres[q][1] = wq[q * 128 + 1];
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        wb[0][q][0] = wq[(8 + q) * 128];
+        wb[0][q][1] = wq[(8 + q) * 128 + 1];
+    }
+#pragma unroll
+    for (int q = 0; q < 8; ++q) pn[q] = *reinterpret_cast<const seg_f4*>(pre_at(0) + q * kSegTileFloats);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+
+    int cur = 0;
+    for (int s = 0; s < a.n; ++s) {
+        // (the stream's addresses do not change from step to step: hidden from the compiler, which would otherwise hoist the
+        // loads out of the time loop and spill what it cannot hold)
+        int zero = 0;
+        asm volatile("" : "+v"(zero));
+        wq = wq0 + zero;
+        seg_f4 acc[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) acc[q] = seg_f4{0.0f, 0.0f, 0.0f, 0.0f};
+        const seg_h8* ahi = reinterpret_cast<const seg_h8*>(hbuf[cur][0]) + lane;
+        const seg_h8* alo = reinterpret_cast<const seg_h8*>(hbuf[cur][1]) + lane;
+        {
+            const seg_h8 xh = ahi[0], xl = alo[0];
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                acc[q] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xh, wres[q][0], acc[q], 0, 0, 0);
+                acc[q] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xh, wres[q][1], acc[q], 0, 0, 0);
+                acc[q] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xl, wres[q][0], acc[q], 0, 0, 0);
+            }
+        }
+#pragma unroll
+        for (int i = 2; i < 2 * kSegKb; ++i) {                          // half K blocks: fragments 4 (i & 1) .. + 3 of block i / 2
+            const int nb = (i + 1) & 1, cb = i & 1;
+            const int ni = i + 1 < 2 * kSegKb ? i + 1 : 2;              // (the last one fetches the next step's first: same weights)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                wb[nb][q][0] = wq[(ni * 4 + q) * 128];
+                wb[nb][q][1] = wq[(ni * 4 + q) * 128 + 1];
+            }
+            __builtin_amdgcn_sched_barrier(0);                          // (the loads stay ahead of the products they overlap)
+            const seg_h8 xh = ahi[(i >> 1) * 64], xl = alo[(i >> 1) * 64];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int g = 4 * (i & 1) + q;
+                acc[g] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xh, wb[cb][q][0], acc[g], 0, 0, 0);
+                acc[g] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xh, wb[cb][q][1], acc[g], 0, 0, 0);
+                acc[g] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xl, wb[cb][q][0], acc[g], 0, 0, 0);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        const int t = a.t0[dir] + (dir ? a.n - 1 - s : s);
+#pragma unroll
+        for (int tl = 0; tl < 2; ++tl) {
+            const int unit = (w * 2 + tl) * 16 + (lane & 15);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float gi = seg_sigmoid(fmaf(acc[tl * 4 + 0][r], a.inv_scale, pn[tl * 4 + 0][r]));
+                const float gf = seg_sigmoid(fmaf(acc[tl * 4 + 1][r], a.inv_scale, pn[tl * 4 + 1][r]));
+                const float gg = seg_tanh(fmaf(acc[tl * 4 + 2][r], a.inv_scale, pn[tl * 4 + 2][r]));
+                const float go = seg_sigmoid(fmaf(acc[tl * 4 + 3][r], a.inv_scale, pn[tl * 4 + 3][r]));
+                c[tl][r] = fmaf(gf, c[tl][r], gi * gg);
+                h[tl][r] = go * seg_tanh(c[tl][r]);
+                const int b = b0 + row0 + r;
+                if (b < a.B && unit < a.H) a.y[(static_cast<size_t>(b) * a.T + t) * (2 * a.H) + dir * a.H + unit] = h[tl][r];
+            }
+            seg_put_h(hbuf[cur ^ 1][0], hbuf[cur ^ 1][1], unit, row0, h[tl]);
+        }
+        if (s + 1 < a.n) {                                               // the next step's pre: a barrier and a product away from its use
+            const float* pp = pre_at(s + 1);
+#pragma unroll
+            for (int q = 0; q < 8; ++q) pn[q] = *reinterpret_cast<const seg_f4*>(pp + q * kSegTileFloats);
+        }
+        // every wave has read hbuf[cur] before it wrote hbuf[cur ^ 1]: one barrier per step.  (Not __syncthreads: that would
+        // also wait for the weight and pre loads in flight for the next step.)
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        cur ^= 1;
+    }
+#pragma unroll
+    for (int tl = 0; tl < 2; ++tl) {
+        const int unit = (w * 2 + tl) * 16 + (lane & 15);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            hst[(row0 + r) * kSegHp + unit] = h[tl][r];
+            cst[(row0 + r) * kSegHp + unit] = c[tl][r];
+        }
+    }
+}
+
+// logp[b, t, :] = log_softmax(W . relu(y[b, t, :]) + bias): one wave per row, four rows per block
+__global__ __launch_bounds__(256) void seg_head_kernel(const float* y, const float* lw, const float* lb, float* logp, long long rows, int H2)
+{
+    const int lane = threadIdx.x & 63;
+    const long long row = static_cast<long long>(blockIdx.x) * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const float* yr = y + row * H2;
+    float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;
+    for (int k = lane; k < H2; k += 64) {
+        const float v = fmaxf(yr[k], 0.0f);
+        s0 = fmaf(v, lw[k], s0);
+        s1 = fmaf(v, lw[H2 + k], s1);
+        s2 = fmaf(v, lw[2 * H2 + k], s2);
+        s3 = fmaf(v, lw[3 * H2 + k], s3);
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        s0 += __shfl_xor(s0, m);
+        s1 += __shfl_xor(s1, m);
+        s2 += __shfl_xor(s2, m);
+        s3 += __shfl_xor(s3, m);
+    }
+    if (lane == 0) {
+        s0 += lb[0]; s1 += lb[1]; s2 += lb[2]; s3 += lb[3];
+        const float mx = fmaxf(fmaxf(s0, s1), fmaxf(s2, s3));
+        const float lse = mx + logf(expf(s0 - mx) + expf(s1 - mx) + expf(s2 - mx) + expf(s3 - mx));
+        *reinterpret_cast<float4*>(logp + row * 4) = make_float4(s0 - lse, s1 - lse, s2 - lse, s3 - lse);
+    }
+}
+
+}  // namespace hssfsst

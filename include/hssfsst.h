@@ -336,6 +336,39 @@ int hssfsst_resample_exec_ragged(hssfsst_resample_plan* plan, const void* x, int
                                  const int64_t* lens, int64_t count, int x_on_device, void* y, int y_dtype, int64_t* labels,
                                  int out_on_device, void* stream);
 
+/* BiLSTM segmenter, inference only: the forward pass of the reference's HeartSoundSegmenter (hss/model/segmenter.py:70-87) on the
+ * device -- lstm_1 (bidirectional, input_size -> 2 x hidden, initial state h0 / c0) -> ReLU -> lstm_2 (2 x hidden -> 2 x hidden,
+ * initial state = lstm_1's final (h_n, c_n) per direction) -> ReLU -> Linear(2 x hidden -> 4) -> log_softmax; dropout is the
+ * identity (eval mode).  PyTorch's LSTM cell: gate rows i, f, g, o; both biases added; c' = sigmoid(f) c + sigmoid(i) tanh(g),
+ * h' = sigmoid(o) tanh(c').  Kernels: csrc/segmenter_lstm.hpp (input projection on the exact f32 matrix instruction; the
+ * recurrence as one persistent workgroup per direction and 16 batch rows, recurrent product on split-f16 operands with float32
+ * accumulation; no workgroup waits for another one, so a row's result does not depend on its neighbours or the batch size).
+ *   lstm_1, lstm_2   eight float32 HOST arrays each, in state_dict order: weight_ih (4 hidden, in), weight_hh (4 hidden, hidden),
+ *                    bias_ih (4 hidden), bias_hh (4 hidden) of the forward direction, then the same four of the reverse direction
+ *                    (the *_reverse keys); `in` is input_size for lstm_1 and 2 hidden for lstm_2
+ *   linear_weight    (4, 2 hidden), linear_bias (4): float32 host arrays
+ * The arrays are copied (re-laid out for the kernels) at creation: later changes of the caller's weights do not reach the plan.
+ * NULL pointers, input_size < 1, hidden < 1 or device < 0 return HSSFSST_EINVAL, hidden > 256 HSSFSST_EUNSUPPORTED, both before
+ * any device is touched.  Single-stream and single-thread like the other plans; its scratch belongs to it: one chunk of projected
+ * inputs (at most 128 MiB, or one time step if that is more), both layers' outputs (2 x batch x steps x 2 hidden x 4 bytes) and
+ * the carried state, grown on demand and kept. */
+typedef struct hssfsst_segmenter hssfsst_segmenter;
+int hssfsst_segmenter_create(hssfsst_segmenter** out, int device, int input_size, int hidden, const float* const* lstm_1,
+                             const float* const* lstm_2, const float* linear_weight, const float* linear_bias);
+int hssfsst_segmenter_destroy(hssfsst_segmenter* plan);
+
+/* Plan geometry; max_hidden (the largest supported hidden size) is answered for a NULL plan too, which otherwise is
+ * HSSFSST_EINVAL.  Any output pointer may be NULL. */
+int hssfsst_segmenter_info(const hssfsst_segmenter* plan, int* input_size, int* hidden, int* max_hidden, int* device);
+
+/* logp (batch, steps, 4) float32 = the model on feats (batch, steps, input_size), contiguous, of feats_dtype HSSFSST_DTYPE_F32 /
+ * F16 / BF16 (half features are converted on load: the result is bit-identical to the float32 call on the converted features);
+ * h0, c0: (2, batch, hidden) float32.  All DEVICE pointers on the plan's device.  Any batch >= 1, any steps >= 1; the time axis is
+ * walked in chunks (forward ascending, reverse descending) with the state carried on the device.  Enqueued on `stream`
+ * (hipStream_t, NULL = default) without synchronising. */
+int hssfsst_segmenter_exec(hssfsst_segmenter* plan, const void* feats, int feats_dtype, int64_t batch, int64_t steps,
+                           const float* h0, const float* c0, float* logp, void* stream);
+
 int hssfsst_device_count(void);
 int hssfsst_version(void);
 const char* hssfsst_last_error(void);

@@ -68,6 +68,10 @@ with torch.no_grad():
     e2e = timed(lambda: segment(tf, head, X50), 20, 3)
     fonly = timed(lambda: tf.batch(X50), 50, 5)
 res["C4_end_to_end_batch50"] = {"ms": round(e2e * 1e3, 3), "windows_per_s": round(50 / e2e, 1), "fsst_only_ms": round(fonly * 1e3, 4)}
+# ... and the same call with the BiLSTM as HIP kernels (SegmenterHead.hip(); tools/segmenter_bench.py interleaves the two)
+hip_head = head.hip()
+e2e_hip = timed(lambda: segment(tf, hip_head, X50), 20, 3)
+res["C4_end_to_end_batch50_hip_segmenter"] = {"ms": round(e2e_hip * 1e3, 3), "windows_per_s": round(50 / e2e_hip, 1)}
 # C5: 64 channels x 4 kHz, 128 new samples per step, nwin 512 (same 128 ms window, same 22 bins)
 from scipy.signal import get_window
 w512 = get_window(("kaiser", 0.5), 512, fftbins=False)
