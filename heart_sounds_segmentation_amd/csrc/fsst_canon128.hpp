@@ -93,7 +93,7 @@ struct CanonCfg {
 // Host side of the f16 operand table: entry (tap n, lane l, half h): lane l = (kk, row i); h -> fold term q = kk + 4 (h >> 2),
 // product h & 3 = {x1 c1, x1 c2, x2 c1, x2 c2} -> the constant's half c1 (h even) or c2 (h odd).  Row i -> (class, re / im) as
 // in the fp32 table of fsst_core128_kernel.  `cs` = 2^sc scales the constants into [2^13, 2^14).
-// (built in hssfsst.hip: canon_build_atab)
+// (built in fsst_tables.hpp: canon_table)
 
 constexpr float kOffsetErr2 = 0.0625f;                     // (5e-7 / 2e-6)^2: V = V' + mean x Yc is good to 4e-7 R' + 1.2e-7 |mean Yc|, and |mean Yc| <= |V| + R':
                                                          // the tie bound of such a tile is tau^2 = 4e-12 (1 + |shift|)^2 (R'^2 + kOffsetErr2 |V|^2) / |V|^2
@@ -113,7 +113,7 @@ struct CanonTile {
 // every such group to the float64 path (2.59 vs 0.208 ms per 1024 windows).  The transform is linear, so a tile whose mean
 // carries at least half of its energy is staged WITHOUT it (records and scale of x - mean over the samples inside the signal:
 // the fold then works at the resolution of the content) and the mean's own spectrum is added where the sources are formed:
-// Z of a lane's two spectra += mean x Z of the all-ones frame, float64 on the host (hssfsst.hip): ONE table row per bin
+// Z of a lane's two spectra += mean x Z of the all-ones frame, float64 on the host (fsst_tables.hpp): ONE table row per bin
 // for interior frames, a table of the 64 + 63 frames whose window reaches over the start / the end of the signal (both at once
 // for signals shorter than a window: ones = left + right - interior).  32 packed multiply-adds per lane and group, for such
 // tiles only, in one block between the spectra and the source stage.  (The mean's FOLD as the matrix instructions' C operand was tried first: its taps are as large as the offset,

@@ -36,7 +36,9 @@
 #include "fourier_resample_gpu.hpp"
 #include "fourier_resample_ragged.hpp"
 #include "segmenter_lstm.hpp"
-#include <cstdlib>
+#include "fsst_tables.hpp"
+
+namespace tables = hssfsst::tables;
 
 namespace {
 
@@ -134,74 +136,6 @@ int check_device(const char* what, int device)
     return 0;
 }
 
-// Knot slopes of the not-a-knot cubic spline through (1..n, w): the derivative window of
-// ssq.fsst's instantaneous-frequency estimator before its fs/(2*pi) scaling (MATLAB fsst.m, local
-// function dtwin).  Tridiagonal system (unit spacing):
-//     s0 + 2 s1 = (5 d0 + d1)/2;  s_{i-1} + 4 s_i + s_{i+1} = 3 (w_{i+1} - w_{i-1});
-//     2 s_{n-2} + s_{n-1} = (5 d_{n-2} + d_{n-3})/2,            d_i = w_{i+1} - w_i
-// solved by Gaussian elimination with partial pivoting specialised to tridiagonal matrices
-// (second super-diagonal as fill-in), O(n).
-int spline_knot_slopes(const double* w, int n, double* s)
-{
-    if (n < 1) return HSSFSST_EINVAL;
-    if (n == 1) { s[0] = 0.0; return 0; }
-    if (n == 2) { s[0] = s[1] = w[1] - w[0]; return 0; }
-    if (n == 3) {
-        const double d0 = w[1] - w[0], d1 = w[2] - w[1];
-        s[0] = d0 - 0.5 * (d1 - d0); s[1] = 0.5 * (d0 + d1); s[2] = d1 + 0.5 * (d1 - d0);
-        return 0;
-    }
-    std::vector<double> dl(n, 0.0), d(n, 0.0), du(n, 0.0), du2(n, 0.0), b(n, 0.0);
-    d[0] = 1.0; du[0] = 2.0; b[0] = (5.0 * (w[1] - w[0]) + (w[2] - w[1])) / 2.0;
-    for (int i = 1; i < n - 1; ++i) {
-        dl[i] = 1.0; d[i] = 4.0; du[i] = 1.0; b[i] = 3.0 * (w[i + 1] - w[i - 1]);
-    }
-    dl[n - 1] = 2.0; d[n - 1] = 1.0;
-    b[n - 1] = (5.0 * (w[n - 1] - w[n - 2]) + (w[n - 2] - w[n - 3])) / 2.0;
-    for (int i = 0; i < n - 1; ++i) {            // row i+1 has sub-diagonal dl[i+1]
-        if (std::fabs(d[i]) >= std::fabs(dl[i + 1])) {
-            if (d[i] == 0.0) return HSSFSST_EINVAL;
-            const double f = dl[i + 1] / d[i];
-            d[i + 1] -= f * du[i];
-            if (i + 2 < n) du[i + 1] -= f * du2[i];
-            b[i + 1] -= f * b[i];
-        } else {                                 // swap rows i and i+1
-            const double f = d[i] / dl[i + 1];
-            const double di = dl[i + 1], dui = d[i + 1], du2i = (i + 2 < n) ? du[i + 1] : 0.0;
-            const double bi = b[i + 1];
-            d[i + 1] = du[i] - f * dui;
-            if (i + 2 < n) du[i + 1] = du2[i] - f * du2i;
-            b[i + 1] = b[i] - f * bi;
-            d[i] = di; du[i] = dui; du2[i] = du2i; b[i] = bi;
-        }
-    }
-    if (d[n - 1] == 0.0) return HSSFSST_EINVAL;
-    s[n - 1] = b[n - 1] / d[n - 1];
-    s[n - 2] = (b[n - 2] - du[n - 2] * s[n - 1]) / d[n - 2];
-    for (int i = n - 3; i >= 0; --i) s[i] = (b[i] - du[i] * s[i + 1] - du2[i] * s[i + 2]) / d[i];
-    return 0;
-}
-
-// FSST._truncate_frequencies (synchrosqueeze.py:91-111): f is a float32 tensor (:52) compared
-// with the Python bounds in float32, both inclusive; f_k = k*fs/nwin, Nyquist row = fs/2.
-void band_rows(int nwin, double fs, double f_lo, double f_hi, int* klo, int* K)
-{
-    const int nf = nwin / 2 + 1;
-    const double res = fs / static_cast<double>(nwin);
-    int first = -1, cnt = 0;
-    for (int k = 0; k < nf; ++k) {
-        double fk = res * k;
-        if ((nwin % 2) == 0 && k == nwin / 2) fk = fs / 2.0;
-        const float f32 = static_cast<float>(fk);
-        if (f32 >= static_cast<float>(f_lo) && f32 <= static_cast<float>(f_hi)) {
-            if (first < 0) first = k;
-            ++cnt;
-        }
-    }
-    *klo = first < 0 ? 0 : first;
-    *K = cnt;
-}
-
 constexpr int kTile = 64;
 constexpr int kFpw128 = 64;      // frames per wave tile of the nwin = 128 kernel
 
@@ -269,6 +203,9 @@ struct PinnedBuf {
 
 constexpr size_t kPinPoolMax = 64;                       // hssfsst_exec_pinned: buffers lent at a time (hssfsst.h)
 
+// The kernels a plan runs (choose_family): generic VALU (nwin 32 / 64, and the fallback of 128 / 256 / 512), any-length, MFMA
+enum class Family { Generic, Dft, Mfma };
+
 }  // namespace
 
 struct hssfsst_plan {
@@ -277,10 +214,9 @@ struct hssfsst_plan {
     int out_dtype = HSSFSST_DTYPE_F32;                       // HSSFSST_DTYPE_F32, or F16 / BF16 (STACK only): element type of every exec's `out`
     size_t out_es = sizeof(float);                           // ... its size in bytes
     DevBuf<float> d_f32;                                     // half plans: float32 features of the paths whose z-score is a second sweep
-    double fs = 0.0;
     DevBuf<float> d_ctab;         // generic kernel: class-folded scalar tables
     DevBuf<float> d_dtab;         // any-length kernel (fsst_dft.hpp): A operand [source block][k-step][64 lanes]
-    int dft = 0;                  // 1: this plan runs the any-length kernel
+    Family family = Family::Generic;      // (rq, nt and the LDS bytes below belong to Family::Mfma)
     float r2scale = 0.0f;         // 4 nwin max |(w + i dw') / 2|^2: error-bound scale of the rounding-tie path
     DevBuf<double> d_wtab;        // float64 {w, dw' in bin units}[nwin], then {cos, sin}(2 pi m / nwin)[nwin]: rounding-tie path
     DevBuf<float> d_atab;         // nwin == 128 / 256 / 512: MFMA A-operand constants [pass][taps][64 lanes][k-step]
@@ -290,6 +226,11 @@ struct hssfsst_plan {
     float canon_r2s = 0.0f;       // ... r2scale x scale^2
     int canon_slots = 0;          // resident blocks of fsst_canon_kernel<.., false> (0 = not queried yet)
     int nt = 16;                  // taps (per-lane FFT size) of the MFMA kernel: nwin = nt * rq
+    // what follows from the fields above, stated once at creation (choose_family, set_derived_facts):
+    bool fast = false;            // the wide-store epilogue applies: STACK modes, even K <= 24
+    bool stripes03 = false;       // MFMA plans: the band starts in stripe 0 of the own plane and ends in stripe 3 (the canonical [25, 200] Hz at fs = 1000, nwin 128 / 256)
+    size_t lds_fixed = 0, lds_per_wave = 0;   // MFMA plans: LDS bytes of the core kernel beside its wave regions, and of one wave region
+    int canon_idx = -1;           // index of the band in kCanonBands when the canonical-band kernels apply, else -1
     DevBuf<float> d_partials;                                // kPartFloats per statistics piece
     unsigned* d_status = nullptr;                            // fused z-score: status word (0 = ok) as the device sees it ...
     volatile unsigned* h_status = nullptr;                   // ... and the same word in pinned host memory: read without a sync
@@ -435,19 +376,27 @@ int launch_core(hssfsst_plan* pl, ExecCtx& cx, hssfsst::CoreParams cp, long long
     return 0;
 }
 
-// floats of LDS of a core launch: WPB waves, PAIR: two waves per wave region (fsst_mfma128.hpp "PAIR")
-inline size_t core128_lds_bytes(const hssfsst_plan* pl, int rq, int nt, int wpb, bool pair)
+// bytes of LDS of a core launch of an MFMA plan: WPB waves, PAIR: two waves per wave region (fsst_mfma128.hpp "PAIR")
+inline size_t core128_lds_bytes(const hssfsst_plan* pl, int wpb, bool pair)
 {
     const size_t regions = pair ? wpb / 2 : wpb;
-    return (hssfsst::core128_atab_floats(rq, nt) + hssfsst::kCtlFloats + regions *
-            (static_cast<size_t>(hssfsst::wave_lds_floats(kFpw128, pl->klo, pl->K, rq, nt)) + (pair ? hssfsst::kPairFloats : 0))) * sizeof(float);
+    return pl->lds_fixed + regions * (pl->lds_per_wave + (pair ? hssfsst::kPairFloats * sizeof(float) : 0));
+}
+
+// the Core128Params every launch of an MFMA plan starts from: the plan-constant fields
+hssfsst::Core128Params core128_params(const hssfsst_plan* pl)
+{
+    hssfsst::Core128Params cp{};
+    cp.atab = pl->d_atab.get(); cp.wtab = pl->d_wtab.get(); cp.twtab = pl->d_wtab.get() + 2 * pl->nwin; cp.r2scale = pl->r2scale;
+    cp.klo = pl->klo; cp.K = pl->K; cp.mode = pl->mode;
+    return cp;
 }
 
 int ensure_status(hssfsst_plan* pl);
 template <int NT, int RQ, bool FAST, int WPB, int S1C = -1, bool PAIR = false, bool RAGGED = false>
 int launch_core128_wpb(hssfsst_plan* pl, ExecCtx& cx, const hssfsst::Core128Params& cp, int64_t nchunks)
 {
-    size_t lds = core128_lds_bytes(pl, RQ, NT, WPB, PAIR);
+    size_t lds = core128_lds_bytes(pl, WPB, PAIR);
     auto kern = hssfsst::fsst_core128_kernel<NT, RQ, kFpw128, FAST, WPB, S1C, false, false, PAIR, RAGGED>;
     static std::atomic<unsigned long long> lds_ok{0};
     if (int rc = allow_full_lds(kern, pl->device, lds_ok)) return rc;
@@ -457,13 +406,12 @@ int launch_core128_wpb(hssfsst_plan* pl, ExecCtx& cx, const hssfsst::Core128Para
     if (blocks > slots) blocks = slots;
     name_kernel(cx.kernel, WPB, blocks, "fsst_core128_kernel<%d, %d, %d, %s, %d, %d, false%s%s>", NT, RQ, kFpw128, FAST ? "true" : "false", WPB, S1C,
                 PAIR ? ", pairs" : "", RAGGED ? ", ragged" : "");
+    hssfsst::Core128Params cq = cp;
     if constexpr (PAIR) {                                // (a pair's bounded wait reports through the status word)
         if (int rcs = ensure_status(pl)) return rcs;
-        hssfsst::Core128Params cq = cp;
         cq.status = pl->d_status;
-        hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(blocks)), dim3(64 * WPB), lds, cx.st, cq);
-    } else
-    hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(blocks)), dim3(64 * WPB), lds, cx.st, cp);
+    }
+    hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(blocks)), dim3(64 * WPB), lds, cx.st, cq);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -478,7 +426,7 @@ int launch_stream(hssfsst_plan* pl, float* tape_at, long long tape_len, const fl
     const int ngroups = (chunk + 15) / 16;
     const hssfsst::Core128Regions reg = hssfsst::core128_regions(ngroups, channels);
     if (!(reg.npc[0] == 0 && reg.npc[1] == 0 && reg.gpc[2] == 1)) return 0;      // (the plain kernel's chunks are not single groups)
-    const size_t lds = core128_lds_bytes(pl, RQ, NT, WPB, PAIR);
+    const size_t lds = core128_lds_bytes(pl, WPB, PAIR);
     if (lds > kMaxLdsBytes) return 0;
     auto kern = hssfsst::fsst_core128_kernel<NT, RQ, kFpw128, true, WPB, -1, false, true, PAIR>;
     static std::atomic<unsigned long long> lds_ok{0};
@@ -495,11 +443,9 @@ int launch_stream(hssfsst_plan* pl, float* tape_at, long long tape_len, const fl
     int bpc = pl->stream_slots / channels;                // blocks per channel: spread a small step over the chip
     if (bpc > ngroups) bpc = ngroups;
     if (bpc < 1) bpc = 1;
-    hssfsst::Core128Params cp{};
-    cp.x = tape_at; cp.xstride = tape_len; cp.out = out; cp.partials = nullptr; cp.atab = pl->d_atab.get();
-    cp.wtab = pl->d_wtab.get(); cp.twtab = pl->d_wtab.get() + 2 * pl->nwin; cp.r2scale = pl->r2scale;
-    cp.n = pl->nwin - 1 + chunk; cp.klo = pl->klo; cp.K = pl->K; cp.mode = pl->mode; cp.nsig = channels;
-    cp.col0 = pl->nwin / 2; cp.ncols = chunk; cp.reg = reg;
+    hssfsst::Core128Params cp = core128_params(pl);
+    cp.x = tape_at; cp.xstride = tape_len; cp.out = out; cp.partials = nullptr;
+    cp.n = pl->nwin - 1 + chunk; cp.nsig = channels; cp.col0 = pl->nwin / 2; cp.ncols = chunk; cp.reg = reg;
     cp.xnew = x_new_dev; cp.xnew_stride = x_stride; cp.hist = pl->nwin - 1; cp.bpc = bpc; cp.state = state; cp.arrive = pl->d_stream_arrive.get(); cp.pieces = pl->d_stream_pieces.get(); cp.mirror = mirror;
     const long long grid = static_cast<long long>(channels) * bpc;
     cp.status = pl->d_status;
@@ -509,18 +455,18 @@ int launch_stream(hssfsst_plan* pl, float* tape_at, long long tape_len, const fl
     return 1;
 }
 
-// Fused z-score launch (nwin = 128, STACK, wide-store epilogue; fsst_mfma128.hpp "Fused z-score"): one persistent block
-// per CU, every CU owns whole signals.  Returns 1 when it launched, 0 when this exec should take the two-kernel path
-// (signal too long for the LDS partials, or a batch that would leave CUs idle for a whole signal), < 0 on error.
-template <int S1C>
-int launch_fused128(hssfsst_plan* pl, ExecCtx& cx, hssfsst::Core128Params cp, int64_t batch, int ngroups)
+// Fused z-score launch (STACK; fsst_mfma128.hpp "Fused z-score"): one persistent block per CU, every CU owns whole signals.  FAST: the
+// wide-store epilogue (nwin 128, even K <= 24); otherwise the general one (any K: nwin 256, or nwin 128 with an odd or wide band), whose
+// z-score tickets sweep a chunk as float4s: every signal's feature block has to start on a 16-byte boundary.  Returns 1 when it launched, 0 when
+// this exec should take the two-kernel path (signal too long for the LDS partials, or a batch that would leave CUs idle for a whole signal), < 0 on error.
+template <int NT, int RQ, bool FAST, int WPB, int S1C>
+int launch_fused(hssfsst_plan* pl, ExecCtx& cx, hssfsst::Core128Params cp, int64_t batch, int ngroups)
 {
-    constexpr int WPB = 16;
     if (ngroups > hssfsst::kFusedMaxGroups || (ngroups + kFpw128 / 16 - 1) / (kFpw128 / 16) < hssfsst::kFusedMinChunks) return 0;
-    const size_t lds = (hssfsst::core128_atab_floats(8, 16) + hssfsst::kCtlFusedFloats + static_cast<size_t>(WPB) *
-                        hssfsst::wave_lds_floats(kFpw128, pl->klo, pl->K, 8, 16)) * sizeof(float);
+    if (!FAST && (((static_cast<long long>(cp.ncols) * 2 * pl->K) & 3) != 0 || (reinterpret_cast<uintptr_t>(cp.out) & 15) != 0)) return 0;
+    const size_t lds = core128_lds_bytes(pl, WPB, false) + (FAST ? hssfsst::kCtlFusedFloats - hssfsst::kCtlFloats : 0) * sizeof(float);
     if (lds > static_cast<size_t>(kMaxLdsBytes)) return 0;
-    auto kern = hssfsst::fsst_core128_kernel<16, 8, kFpw128, true, WPB, S1C, true>;
+    auto kern = hssfsst::fsst_core128_kernel<NT, RQ, kFpw128, FAST, WPB, S1C, true>;
     static std::atomic<unsigned long long> lds_ok{0};
     if (int rc = allow_full_lds(kern, pl->device, lds_ok)) return rc;
     if (int rc = resident_blocks(pl, pl->fused_slots, kern, 64 * WPB, lds, true)) return rc;       // one block per CU
@@ -532,33 +478,7 @@ int launch_fused128(hssfsst_plan* pl, ExecCtx& cx, hssfsst::Core128Params cp, in
     if (batch < grid || rounds * grid * 100 > batch * 112) return 0;
     if (int rcs = ensure_status(pl)) return rcs;
     cp.status = pl->d_status;
-    name_kernel(cx.kernel, WPB, grid, "fsst_core128_kernel<16, 8, %d, true, %d, %d, true>", kFpw128, WPB, S1C);
-    hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(grid)), dim3(64 * WPB), lds, cx.st, cp);
-    HIP_TRY(hipGetLastError());
-    return 1;
-}
-
-// The same for the general epilogue (any K: nwin 256 / 512, or nwin 128 with an odd or wide band), STACK only.  The z-score
-// tickets sweep a chunk as float4s: every signal's feature block has to start on a 16-byte boundary.
-template <int NT, int RQ, int WPB, int S1C>
-int launch_fused_general(hssfsst_plan* pl, ExecCtx& cx, hssfsst::Core128Params cp, int64_t batch, int ngroups)
-{
-    if (ngroups > hssfsst::kFusedMaxGroups || (ngroups + kFpw128 / 16 - 1) / (kFpw128 / 16) < hssfsst::kFusedMinChunks) return 0;
-    if (((static_cast<long long>(cp.ncols) * 2 * pl->K) & 3) != 0 || (reinterpret_cast<uintptr_t>(cp.out) & 15) != 0) return 0;
-    const size_t lds = (hssfsst::core128_atab_floats(RQ, NT) + hssfsst::kCtlFloats + static_cast<size_t>(WPB) *
-                        hssfsst::wave_lds_floats(kFpw128, pl->klo, pl->K, RQ, NT)) * sizeof(float);
-    if (lds > static_cast<size_t>(kMaxLdsBytes)) return 0;
-    auto kern = hssfsst::fsst_core128_kernel<NT, RQ, kFpw128, false, WPB, S1C, true>;
-    static std::atomic<unsigned long long> lds_ok{0};
-    if (int rc = allow_full_lds(kern, pl->device, lds_ok)) return rc;
-    if (int rc = resident_blocks(pl, pl->fused_slots, kern, 64 * WPB, lds, true)) return rc;       // one block per CU
-    if (pl->fused_slots < 1) return 0;
-    const int64_t grid = pl->fused_slots;
-    const int64_t rounds = (batch + grid - 1) / grid;
-    if (batch < grid || rounds * grid * 100 > batch * 112) return 0;  // (as launch_fused128: a nearly full last round)
-    if (int rcs = ensure_status(pl)) return rcs;
-    cp.status = pl->d_status;
-    name_kernel(cx.kernel, WPB, grid, "fsst_core128_kernel<%d, %d, %d, false, %d, %d, true>", NT, RQ, kFpw128, WPB, S1C);
+    name_kernel(cx.kernel, WPB, grid, "fsst_core128_kernel<%d, %d, %d, %s, %d, %d, true>", NT, RQ, kFpw128, FAST ? "true" : "false", WPB, S1C);
     hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(grid)), dim3(64 * WPB), lds, cx.st, cp);
     HIP_TRY(hipGetLastError());
     return 1;
@@ -706,22 +626,13 @@ int launch_team16(hssfsst_plan* pl, ExecCtx& cx, const hssfsst::Core128Params& c
 // PhysioNet 2016's native rate (/root/reference/hss/datasets/heart_sounds.py:36-113 loads them un-resampled).  Every other band keeps
 // fsst_core128_kernel.  (A third band is one line here: the template takes any even band of <= 24 rows inside rows 0..31.)
 constexpr int kCanonBands[][2] = {{4, 22}, {2, 24}};
-constexpr int kCanonKlo = kCanonBands[0][0], kCanonK = kCanonBands[0][1];
 
-int canon_band(const hssfsst_plan* pl)                   // index into kCanonBands, or -1
-{
-    if (debug_switches().no_canon || !pl->d_atab16.get() || pl->nwin != 128) return -1;     // (no_canon: A/B and cross-check tests)
-    if (!(pl->mode == HSSFSST_MODE_STACK || pl->mode == HSSFSST_MODE_STACK_UNNORM)) return -1;
-    for (int i = 0; i < static_cast<int>(sizeof(kCanonBands) / sizeof(kCanonBands[0])); ++i)
-        if (pl->klo == kCanonBands[i][0] && pl->K == kCanonBands[i][1]) return i;
-    return -1;
-}
-bool plan_is_canon(const hssfsst_plan* pl) { return canon_band(pl) >= 0; }
+bool plan_is_canon(const hssfsst_plan* pl) { return pl->canon_idx >= 0; }
 // f(KLO, KC) with the plan's band as integral constants
 template <class F>
 int canon_dispatch(const hssfsst_plan* pl, F&& f)
 {
-    switch (canon_band(pl)) {
+    switch (pl->canon_idx) {
     case 0: return f(std::integral_constant<int, kCanonBands[0][0]>{}, std::integral_constant<int, kCanonBands[0][1]>{});
     case 1: return f(std::integral_constant<int, kCanonBands[1][0]>{}, std::integral_constant<int, kCanonBands[1][1]>{});
     default: return fail(HSSFSST_EINVAL, "canon_dispatch: not a canonical-class plan");
@@ -766,7 +677,7 @@ int launch_canon(hssfsst_plan* pl, ExecCtx& cx, const hssfsst::Core128Params& cp
     return canon_dispatch(pl, [&](auto KL, auto KN) { return launch_canon_band<decltype(KL)::value, decltype(KN)::value>(pl, cx, cp, nchunks); });
 }
 
-// One CU per signal with the z-score in the same launch (see launch_fused128): 1 = launched, 0 = take another path
+// One CU per signal with the z-score in the same launch (see launch_fused): 1 = launched, 0 = take another path
 // gated = the fallback queued behind a team launch (cx.gate set): any batch size -- the block count is what a launch that
 // almost always finds its gate closed should cost, not what would be fast.
 template <int KLO, int KC>
@@ -860,12 +771,11 @@ void half_dispatch(const hssfsst_plan* p, void* out, F&& f)
 // The plain (two-launch) core kernel for a plan of the MFMA kernel: as many waves per block as fit the 160 KiB of LDS beside
 // the shared tables.  RAGGED: the instantiations of hssfsst_exec_ragged (the same ladder, chunk list from the host).
 template <bool RAGGED>
-int launch_core128_plain(hssfsst_plan* pl, ExecCtx& cx, const hssfsst::Core128Params& cp, int64_t nchunks, bool fast, bool canon)
+int launch_core128_plain(hssfsst_plan* pl, ExecCtx& cx, const hssfsst::Core128Params& cp, int64_t nchunks)
 {
     const int rq = pl->rq, nt = pl->nt;
-    const size_t fixed = (hssfsst::core128_atab_floats(rq, nt) + hssfsst::kCtlFloats) * sizeof(float);
-    const size_t per_wave = static_cast<size_t>(hssfsst::wave_lds_floats(kFpw128, pl->klo, pl->K, rq, nt)) * sizeof(float);
-    const size_t room = 160 * 1024;
+    const bool fast = pl->fast, canon = pl->stripes03;
+    const size_t fixed = pl->lds_fixed, per_wave = pl->lds_per_wave, room = 160 * 1024;
     if (nt == 16 && rq == 8) {
         if (fast && canon) return launch_core128_wpb<16, 8, true, 16, 3, false, RAGGED>(pl, cx, cp, nchunks);
         if (fast) return launch_core128_wpb<16, 8, true, 16, -1, false, RAGGED>(pl, cx, cp, nchunks);   // K <= 24: 16 regions always fit
@@ -883,10 +793,10 @@ int launch_core128_plain(hssfsst_plan* pl, ExecCtx& cx, const hssfsst::Core128Pa
         if (fast && fixed + 4 * per_wave <= room) return launch_core128_wpb<16, 16, true, 4, -1, false, RAGGED>(pl, cx, cp, nchunks);
     } else {                                                                         // nt == 32, rq == 16: nwin = 512
         if (!debug_switches().no_pair) {                                             // (two waves per SIMD at most: 32-point spectra in registers)
-            if (fast && core128_lds_bytes(pl, 16, 32, 8, true) <= room) return launch_core128_wpb<32, 16, true, 8, -1, true, RAGGED>(pl, cx, cp, nchunks);
-            if (!fast && core128_lds_bytes(pl, 16, 32, 8, true) <= room) return launch_core128_wpb<32, 16, false, 8, -1, true, RAGGED>(pl, cx, cp, nchunks);
-            if (!fast && core128_lds_bytes(pl, 16, 32, 6, true) <= room) return launch_core128_wpb<32, 16, false, 6, -1, true, RAGGED>(pl, cx, cp, nchunks);
-            if (!fast && core128_lds_bytes(pl, 16, 32, 4, true) <= room) return launch_core128_wpb<32, 16, false, 4, -1, true, RAGGED>(pl, cx, cp, nchunks);
+            if (fast && core128_lds_bytes(pl, 8, true) <= room) return launch_core128_wpb<32, 16, true, 8, -1, true, RAGGED>(pl, cx, cp, nchunks);
+            if (!fast && core128_lds_bytes(pl, 8, true) <= room) return launch_core128_wpb<32, 16, false, 8, -1, true, RAGGED>(pl, cx, cp, nchunks);
+            if (!fast && core128_lds_bytes(pl, 6, true) <= room) return launch_core128_wpb<32, 16, false, 6, -1, true, RAGGED>(pl, cx, cp, nchunks);
+            if (!fast && core128_lds_bytes(pl, 4, true) <= room) return launch_core128_wpb<32, 16, false, 4, -1, true, RAGGED>(pl, cx, cp, nchunks);
         }
         if (fast && fixed + 8 * per_wave <= room) return launch_core128_wpb<32, 16, true, 8, -1, false, RAGGED>(pl, cx, cp, nchunks);
         if (!fast && fixed + 8 * per_wave <= room) return launch_core128_wpb<32, 16, false, 8, -1, false, RAGGED>(pl, cx, cp, nchunks);
@@ -923,29 +833,18 @@ int launch_core128(hssfsst_plan* pl, ExecCtx& cx, const float* dx, long long xst
                    int ncols, int64_t batch, bool try_fused, void* hout = nullptr)
 {
     const bool half = hout != nullptr;
-    hssfsst::Core128Params cp{};
-    cp.xstride = xstride;
-    cp.x = dx; cp.out = dout; cp.partials = partials; cp.atab = pl->d_atab.get();
-    cp.wtab = pl->d_wtab.get(); cp.twtab = pl->d_wtab.get() + 2 * pl->nwin; cp.r2scale = pl->r2scale;
-    cp.n = n; cp.klo = pl->klo; cp.K = pl->K; cp.mode = pl->mode; cp.nsig = static_cast<int>(batch);
-    cp.col0 = col0; cp.ncols = ncols;
-    cp.reg = hssfsst::core128_regions((ncols + 15) / 16, batch);
+    const int ngroups = (ncols + 15) / 16;
+    hssfsst::Core128Params cp = core128_params(pl);
+    cp.x = dx; cp.xstride = xstride; cp.out = dout; cp.partials = partials;
+    cp.n = n; cp.nsig = static_cast<int>(batch); cp.col0 = col0; cp.ncols = ncols;
+    cp.reg = hssfsst::core128_regions(ngroups, batch);
     const int64_t nchunks = batch * hssfsst::core128_chunks_per_signal(cp.reg);
-    const bool fast = (pl->mode == HSSFSST_MODE_STACK || pl->mode == HSSFSST_MODE_STACK_UNNORM) &&
-                      (pl->K & 1) == 0 && pl->K <= 24;
-    // waves per block: as many wave regions as fit the 160 KiB of LDS beside the shared tables
     const int rq = pl->rq, nt = pl->nt;
-    const size_t fixed = (hssfsst::core128_atab_floats(rq, nt) + hssfsst::kCtlFloats) * sizeof(float);
-    const size_t per_wave = static_cast<size_t>(hssfsst::wave_lds_floats(kFpw128, pl->klo, pl->K, rq, nt)) * sizeof(float);
-    const size_t room = 160 * 1024;
-    // bands that start in stripe 0 of the own plane and end in stripe 3 (the canonical [25, 200] Hz at fs = 1000 for
-    // nwin 128 and 256) get kernels with compile-time stripe tests
-    const bool canon = hssfsst::own_s0(pl->klo, rq) == 0 && hssfsst::own_s1(pl->klo, pl->K, rq) == 3;
+    const bool fast = pl->fast, canon = pl->stripes03;
     // (tiles are aligned in absolute columns: a column range must start on a 16-frame group boundary -- on a 64-frame tile
     //  boundary for the team kernel, whose chunks are whole tiles; other ranges take fsst_core128_kernel)
     const bool canon16 = fast && nt == 16 && rq == 8 && plan_is_canon(pl) && (col0 & 15) == 0;
     if (try_fused && fast && nt == 16 && rq == 8 && pl->mode == HSSFSST_MODE_STACK) {
-        const int ngroups = (ncols + 15) / 16;
         // two single-launch z-score kernels.  The team kernel (fsst_team16.hpp: features written once, from registers) is at least as
         // fast as one CU per signal on full batches and 1.3-1.8x faster on small or ragged ones (profiles/r04_batch_sweep.txt): it
         // goes first wherever it applies -- the canonical band, signals of at most 128 groups; one CU per signal (the tile makes a
@@ -987,32 +886,76 @@ int launch_core128(hssfsst_plan* pl, ExecCtx& cx, const float* dx, long long xst
         }
         if (!team_only && !half) {
             rc = canon16 ? launch_canon_fused(pl, cx, cp, batch, ngroups)
-                 : canon ? launch_fused128<3>(pl, cx, cp, batch, ngroups) : launch_fused128<-1>(pl, cx, cp, batch, ngroups);
+                 : canon ? launch_fused<16, 8, true, 16, 3>(pl, cx, cp, batch, ngroups) : launch_fused<16, 8, true, 16, -1>(pl, cx, cp, batch, ngroups);
         }
         if (rc < 0) return rc;
         if (rc == 1) { cx.fused = true; cx.zpath = 1; return 0; }
     }
-    if (try_fused && !half && !fast && rq == 8 && nt == 16 && pl->mode == HSSFSST_MODE_STACK && cx.zpref != HSSFSST_ZPATH_TEAM &&
-        fixed + 16 * per_wave <= room) {
-        // nwin 128, a band the wide-store epilogue does not take (odd K or K > 24)
-        const int rc = launch_fused_general<16, 8, 16, -1>(pl, cx, cp, batch, (ncols + 15) / 16);
-        if (rc < 0) return rc;
-        if (rc == 1) { cx.fused = true; cx.zpath = 1; return 0; }
-    }
-    if (try_fused && !half && !fast && rq == 16 && pl->mode == HSSFSST_MODE_STACK && cx.zpref != HSSFSST_ZPATH_TEAM) {
-        // nwin 256 / 512 (general epilogue): one CU per signal, the z-score as tickets of the same launch; waves per block
-        // as on the two-launch path (what fits the LDS: 8 for the canonical band at 256 points, 3 at 512)
-        const int ngroups = (ncols + 15) / 16;
+    if (try_fused && !half && !fast && nt == 16 && pl->mode == HSSFSST_MODE_STACK && cx.zpref != HSSFSST_ZPATH_TEAM) {
+        // the general epilogue: one CU per signal, the z-score as tickets of the same launch.  nwin 128, a band the wide-store epilogue does
+        // not take (odd K or K > 24): 16 waves per block; nwin 256: as on the two-launch path (what fits the LDS: 8 for the canonical band).
+        // (512 points: two launches, on wave pairs: 2.6 ms per 1024 windows against 3.0 for the single launch, whose instantiations are gone)
         int rc = 0;
-        if (nt == 16 && fixed + 8 * per_wave <= room)
-            rc = canon ? launch_fused_general<16, 16, 8, 3>(pl, cx, cp, batch, ngroups) : launch_fused_general<16, 16, 8, -1>(pl, cx, cp, batch, ngroups);
-        // (512 points: two launches, on wave pairs: 2.6 ms per 1024 windows against 3.0 for the single launch, whose
-        //  instantiations are gone)
+        if (rq == 8 && core128_lds_bytes(pl, 16, false) <= kMaxLdsBytes) rc = launch_fused<16, 8, false, 16, -1>(pl, cx, cp, batch, ngroups);
+        else if (rq == 16 && core128_lds_bytes(pl, 8, false) <= kMaxLdsBytes)
+            rc = canon ? launch_fused<16, 16, false, 8, 3>(pl, cx, cp, batch, ngroups) : launch_fused<16, 16, false, 8, -1>(pl, cx, cp, batch, ngroups);
         if (rc < 0) return rc;
         if (rc == 1) { cx.fused = true; cx.zpath = 1; return 0; }
     }
     if (canon16) return launch_canon(pl, cx, cp, nchunks);
-    return launch_core128_plain<false>(pl, cx, cp, nchunks, fast, canon);
+    return launch_core128_plain<false>(pl, cx, cp, nchunks);
+}
+
+// Plan creation, step 1: which kernels the plan runs, with the MFMA kernels' shape nwin = nt x rq and LDS bytes.
+int choose_family(hssfsst_plan* p)
+{
+    const int nwin = p->nwin;
+    // (force_dft, cross-check: every length on the any-length kernel)
+    if (!(nwin == 32 || nwin == 64 || tables::mfma_length(nwin)) || debug_switches().force_dft) {
+        p->family = Family::Dft;
+        const size_t per_wave = static_cast<size_t>(hssfsst::dft_wave_lds_floats((nwin + 3) / 4, p->K > 0 ? p->K : 1)) * sizeof(float);
+        if (per_wave <= static_cast<size_t>(kMaxLdsBytes)) return 0;
+        return fail(HSSFSST_EUNSUPPORTED, "plan_create: window length %d with %d kept rows needs %zu B of LDS per wave (> 160 KiB): "
+                                          "narrow the band", nwin, p->K, per_wave);
+    }
+    if (!tables::mfma_length(nwin) || debug_switches().force_generic) return 0;
+    // enough wave regions of this band must fit beside the A table (long windows with very wide bands: generic kernel)
+    const int nt = tables::mfma_taps(nwin), rq = nwin / nt, min_waves = (nwin == 512) ? 2 : 4;
+    const size_t fixed = (hssfsst::core128_atab_floats(rq, nt) + hssfsst::kCtlFloats) * sizeof(float);
+    const size_t per_wave = static_cast<size_t>(hssfsst::wave_lds_floats(kFpw128, p->klo, p->K, rq, nt)) * sizeof(float);
+    if (fixed + min_waves * per_wave > 160 * 1024) return 0;
+    p->family = Family::Mfma; p->rq = rq; p->nt = nt; p->lds_fixed = fixed; p->lds_per_wave = per_wave;
+    return 0;
+}
+
+// Step 2: the constant tables (fsst_tables.hpp) that the plan's kernels read.  Every plan has the generic table (zeros for the
+// any-length kernel) and the float64 tables of the rounding-tie path; the canonical-band tables exist for every MFMA plan of nwin 128.
+int upload_tables(hssfsst_plan* p, const double* window, const double* dwb)
+{
+    const int nwin = p->nwin;
+    auto up = [](auto& buf, const auto& host) { return buf.upload(host.data(), host.size()); };
+    if (int rc = up(p->d_ctab, tables::generic_table(window, dwb, nwin, p->family != Family::Dft))) return rc;
+    if (int rc = up(p->d_wtab, tables::tie_table(window, dwb, nwin, &p->r2scale))) return rc;
+    if (p->family == Family::Dft) return up(p->d_dtab, tables::dft_table(window, dwb, nwin));
+    if (p->family != Family::Mfma) return 0;
+    if (int rc = up(p->d_atab, tables::mfma_table(window, dwb, nwin, p->klo, p->K))) return rc;
+    if (nwin != 128) return 0;
+    int sc = 0;
+    if (int rc = up(p->d_atab16, tables::canon_table(window, dwb, &sc))) return rc;
+    p->canon_inv_c = static_cast<float>(std::ldexp(1.0, -sc));
+    p->canon_r2s = static_cast<float>(static_cast<double>(p->r2scale) * std::ldexp(1.0, sc) * std::ldexp(1.0, sc));
+    return 0;
+}
+
+// Step 3: what the exec paths would otherwise work out per call
+void set_derived_facts(hssfsst_plan* p)
+{
+    const bool stack = p->mode == HSSFSST_MODE_STACK || p->mode == HSSFSST_MODE_STACK_UNNORM;
+    p->fast = stack && (p->K & 1) == 0 && p->K <= 24;
+    p->stripes03 = p->family == Family::Mfma && hssfsst::own_s0(p->klo, p->rq) == 0 && hssfsst::own_s1(p->klo, p->K, p->rq) == 3;
+    if (debug_switches().no_canon || !p->d_atab16.get() || !stack) return;      // (no_canon: A/B and cross-check tests)
+    for (int i = 0; i < static_cast<int>(sizeof(kCanonBands) / sizeof(kCanonBands[0])); ++i)
+        if (p->klo == kCanonBands[i][0] && p->K == kCanonBands[i][1]) p->canon_idx = i;
 }
 
 }  // namespace
@@ -1032,17 +975,14 @@ int hssfsst_device_count(void)
 int hssfsst_dtwin(const double* window, int nwin, double fs, double* dwindow)
 {
     if (!window || !dwindow || nwin < 1 || !(fs > 0.0)) return fail(HSSFSST_EINVAL, "hssfsst_dtwin: bad argument");
-    const int rc = spline_knot_slopes(window, nwin, dwindow);
-    if (rc != 0) return fail(rc, "hssfsst_dtwin: singular spline system");
-    const double scale = fs / (2.0 * M_PI);
-    for (int i = 0; i < nwin; ++i) dwindow[i] *= scale;
+    if (int rc = tables::dwindow(window, nwin, fs / (2.0 * M_PI), dwindow)) return fail(rc, "hssfsst_dtwin: singular spline system");
     return 0;
 }
 
 int hssfsst_band(int nwin, double fs, double f_lo, double f_hi, int* klo, int* K)
 {
     if (nwin < 1 || !(fs > 0.0) || !klo || !K) return fail(HSSFSST_EINVAL, "hssfsst_band: bad argument");
-    band_rows(nwin, fs, f_lo, f_hi, klo, K);
+    tables::band_rows(nwin, fs, f_lo, f_hi, klo, K);
     return 0;
 }
 
@@ -1074,234 +1014,19 @@ int hssfsst_plan_create_ex(hssfsst_plan** out, int device, int nwin, const doubl
     if (out_dtype != HSSFSST_DTYPE_F32 && mode != HSSFSST_MODE_STACK)
         return fail(HSSFSST_EINVAL, "plan_create: half-precision output (dtype %d) is for HSSFSST_MODE_STACK only, not mode %d", out_dtype, mode);
     if (nwin > 65535) return fail(HSSFSST_EUNSUPPORTED, "plan_create: window length %d exceeds 65535", nwin);
-    const bool force_dft = debug_switches().force_dft;    // cross-check: every length on the any-length kernel
-    const bool radix_len = nwin == 32 || nwin == 64 || nwin == 128 || nwin == 256 || nwin == 512;
     if (int rc = check_device("plan_create", device)) return rc;
     DEVICE_SCOPE(device);
-
     std::unique_ptr<hssfsst_plan> p(new (std::nothrow) hssfsst_plan());    // (every error path frees what was made, under device_guard_)
     if (!p) return fail(HSSFSST_ENOMEM, "plan_create: host allocation failed");
-    p->device = device; p->nwin = nwin; p->R = nwin / 32; p->nf = nwin / 2 + 1; p->mode = mode; p->fs = fs;
+    p->device = device; p->nwin = nwin; p->R = nwin / 32; p->nf = nwin / 2 + 1; p->mode = mode;
     p->out_dtype = out_dtype; p->out_es = out_dtype == HSSFSST_DTYPE_F32 ? sizeof(float) : 2;
-    if (has_band) band_rows(nwin, fs, f_lo, f_hi, &p->klo, &p->K);
+    if (has_band) tables::band_rows(nwin, fs, f_lo, f_hi, &p->klo, &p->K);
     else { p->klo = 0; p->K = p->nf; }
-
-    // derivative window in BIN units: dw * nwin/fs with dw = slope * fs/(2 pi)  =>  slope * nwin/(2 pi)
-    std::vector<double> dwb(nwin);
-    int rc = spline_knot_slopes(window, nwin, dwb.data());
-    if (rc != 0) return fail(rc, "plan_create: singular spline system");
-    for (int i = 0; i < nwin; ++i) dwb[i] *= static_cast<double>(nwin) / (2.0 * M_PI);
-
-    p->dft = (!radix_len || force_dft) ? 1 : 0;
-    const int R = p->dft ? 2 : p->R;                      // (the class-folded tables below are only read by the radix kernels)
-    const int ncls = R / 2 + 1;
-    std::vector<float> tab(static_cast<size_t>(ncls) * 32 * 4 * R, 0.0f);
-    if (!p->dft)
-    for (int r = 0; r < ncls; ++r) {
-        const bool packed = (r == 0) || (2 * r == R);
-        for (int n = 0; n < 32; ++n) {
-            float* row = tab.data() + (static_cast<size_t>(r) * 32 + n) * 4 * R;
-            for (int q = 0; q < R; ++q) {
-                const double ang = -2.0 * M_PI * (static_cast<double>(r) * q / R + static_cast<double>(r) * n / nwin);
-                const double c = std::cos(ang), s = std::sin(ang);
-                const double wv = window[n + 32 * q], dv = dwb[n + 32 * q];
-                if (packed) {            // 0.5 (w + i dw') * phase
-                    row[q] = static_cast<float>(0.5 * (wv * c - dv * s));
-                    row[R + q] = static_cast<float>(0.5 * (wv * s + dv * c));
-                } else {                 // w * phase | dw' * phase
-                    row[q] = static_cast<float>(wv * c);
-                    row[R + q] = static_cast<float>(wv * s);
-                    row[2 * R + q] = static_cast<float>(dv * c);
-                    row[3 * R + q] = static_cast<float>(dv * s);
-                }
-            }
-        }
-    }
-    if ((rc = p->d_ctab.upload(tab.data(), tab.size())) != 0) return rc;
-    {   // float64 tables of the rounding-tie path: the window pair and the twiddles
-        std::vector<double> wt(static_cast<size_t>(4) * nwin);
-        double cmax2 = 0.0;
-        for (int i = 0; i < nwin; ++i) cmax2 = std::fmax(cmax2, 0.25 * (window[i] * window[i] + dwb[i] * dwb[i]));
-        p->r2scale = static_cast<float>(4.0 * nwin * cmax2);
-        for (int i = 0; i < nwin; ++i) {
-            wt[2 * i] = window[i]; wt[2 * i + 1] = dwb[i];
-            const double ang = 2.0 * M_PI * static_cast<double>(i) / static_cast<double>(nwin);
-            wt[2 * nwin + 2 * i] = std::cos(ang); wt[2 * nwin + 2 * i + 1] = std::sin(ang);
-        }
-        if (nwin == 128 || nwin == 256 || nwin == 512) {
-            // MFMA kernels, heavily undecided groups (resolve_group_f64, fsst_mfma128.hpp): the A operand of the fold -- the
-            // constants C_r[n, q] of the float32 table below, [pass][tap][k-step][lane] -- in float64 for
-            // v_mfma_f64_16x16x4_f64, behind the twiddles (16 / 64 / 128 kB).  The float64 instruction hands lane group g the
-            // rows g, g + 4, g + 8, g + 12 of D (measured: tools/mfma_f64_layout.hip) where the float32 one hands it rows
-            // 4 g .. 4 g + 3: row i of A is class pair 4 pz + (i & 3), component i >> 2.
-            const int nt = (nwin == 512) ? 32 : 16, rq = nwin / nt, npass = rq / 8, kst = rq / 4;
-            wt.resize(static_cast<size_t>(4) * nwin + static_cast<size_t>(hssfsst::fold64_doubles(rq, nt)));
-            for (int pz = 0; pz < npass; ++pz)
-                for (int n = 0; n < nt; ++n)
-                    for (int ks = 0; ks < kst; ++ks)
-                        for (int l = 0; l < 64; ++l) {
-                            const int i = l & 15, q = (l >> 4) + 4 * ks;
-                            const int gg = i & 3, sub = i >> 2, m = 4 * pz + gg;
-                            const int r = (sub < 2) ? m : (m ? rq - m : rq / 2);
-                            const double ang = -2.0 * M_PI * (static_cast<double>(r) * q / rq + static_cast<double>(r) * n / nwin);
-                            const double c = std::cos(ang), sn = std::sin(ang);
-                            const double sg = (r & 1) ? -0.5 : 0.5;
-                            const double wv = window[n + nt * q], dv = dwb[n + nt * q];
-                            wt[static_cast<size_t>(4) * nwin + (((pz * nt + n) * kst) + ks) * 64 + l] =
-                                (sub & 1) ? sg * (wv * sn + dv * c) : sg * (wv * c - dv * sn);
-                        }
-        }
-        if ((rc = p->d_wtab.upload(wt.data(), wt.size())) != 0) return rc;
-    }
-    const bool force_generic = debug_switches().force_generic;
-    bool use_mfma = !p->dft && (nwin == 128 || nwin == 256 || nwin == 512) && !force_generic;
-    if (p->dft) {
-        // A[i][k] of v_mfma_f32_16x16x4_f32 for source block blk, k-step ks: lane l holds row i = l & 15, k = l >> 4.
-        // Row i: source k' = 4 blk + (i >> 2), component i & 3 of {V.re, V.im, Vd'.re, Vd'.im}; tap n = 4 ks + k:
-        //   V  [k'] = sum_n x[t + n] w  [n] e^{-2 pi i k' (n + m) / N},  m = floor(N / 2) (the modified-STFT phase, step 5)
-        //   Vd'[k'] = sum_n x[t + n] dw'[n] e^{-2 pi i k' (n + m) / N}
-        // (k' (n + m) is reduced modulo N in integers before the angle is formed)
-        const int nf = p->nf, nk4 = (nwin + 3) / 4, nblk4 = (nf + 3) / 4, m = nwin / 2;
-        const size_t per_wave = static_cast<size_t>(hssfsst::dft_wave_lds_floats(nk4, p->K > 0 ? p->K : 1)) * sizeof(float);
-        if (per_wave > static_cast<size_t>(kMaxLdsBytes))
-            return fail(HSSFSST_EUNSUPPORTED, "plan_create: window length %d with %d kept rows needs %zu B of LDS per wave (> 160 KiB): "
-                                              "narrow the band", nwin, p->K, per_wave);
-        std::vector<float> dt(static_cast<size_t>(nblk4) * nk4 * 64, 0.0f);
-        for (int blk = 0; blk < nblk4; ++blk)
-            for (int ks = 0; ks < nk4; ++ks)
-                for (int l = 0; l < 64; ++l) {
-                    const int i = l & 15, n = 4 * ks + (l >> 4), kp = 4 * blk + (i >> 2), sub = i & 3;
-                    if (kp >= nf || n >= nwin) continue;
-                    const long long red = (static_cast<long long>(kp) * (n + m)) % nwin;
-                    const double ang = -2.0 * M_PI * static_cast<double>(red) / static_cast<double>(nwin);
-                    const double amp = (sub < 2) ? window[n] : dwb[n];
-                    dt[(static_cast<size_t>(blk) * nk4 + ks) * 64 + l] = static_cast<float>(amp * ((sub & 1) ? std::sin(ang) : std::cos(ang)));
-                }
-        if ((rc = p->d_dtab.upload(dt.data(), dt.size())) != 0) return rc;
-    }
-    const int nt0 = (nwin == 512) ? 32 : 16, rq0 = nwin / nt0;
-    if (use_mfma) {                                      // enough wave regions of this band must fit beside the A table
-        const int min_waves = (nwin == 512) ? 2 : 4;
-        const size_t need = (hssfsst::core128_atab_floats(rq0, nt0) + hssfsst::kCtlFloats + min_waves *
-                             static_cast<size_t>(hssfsst::wave_lds_floats(kFpw128, p->klo, p->K, rq0, nt0))) * sizeof(float);
-        if (need > 160 * 1024) use_mfma = false;         // (long windows with very wide bands: generic kernel)
-    }
-    if (use_mfma) {
-        // A[i][k] of v_mfma_f32_16x16x4_f32 for pass pz, tap n, k-step ks: lane l holds row i = l & 15, k = l >> 4.
-        // Row i: lane group gg = i >> 2 owns class pair m = 4 pz + gg: ca = m, cb = (m ? RQ - m : RQ / 2); sub = i & 3:
-        // {ca re, ca im, cb re, cb im}.  Entry = component of
-        //   C_r[n, q] = (-1)^r * 0.5 (w + i dw')[n + NT q] * exp(-2 pi i (r q / RQ + r n / nwin)),  q = k + 4 ks.
-        const int nt = nt0, rq = rq0, npass = rq / 8, kst = rq / 4;
-        p->rq = rq; p->nt = nt;
-        const int atab_floats = hssfsst::core128_atab_floats(rq, nt);
-        std::vector<float> at(atab_floats + 6 * 64);      // A table, then the FAST epilogue's store offsets (ints)
-        for (int pz = 0; pz < npass; ++pz)
-            for (int n = 0; n < nt; ++n)
-                for (int ks = 0; ks < kst; ++ks)
-                    for (int l = 0; l < 64; ++l) {
-                        const int i = l & 15, q = (l >> 4) + 4 * ks;
-                        const int gg = i >> 2, sub = i & 3, m = 4 * pz + gg;
-                        const int r = (sub < 2) ? m : (m ? rq - m : rq / 2);
-                        const double ang = -2.0 * M_PI * (static_cast<double>(r) * q / rq + static_cast<double>(r) * n / nwin);
-                        const double c = std::cos(ang), sn = std::sin(ang);
-                        const double sg = (r & 1) ? -0.5 : 0.5;
-                        const double wv = window[n + nt * q], dv = dwb[n + nt * q];
-                        const double re = sg * (wv * c - dv * sn), im = sg * (wv * sn + dv * c);
-                        at[((pz * nt + n) * 64 + l) * kst + ks] = static_cast<float>((sub & 1) ? im : re);      // [pass][tap][lane][k-step]: the kernel's LDS layout
-                    }
-        static_assert(sizeof(int) == sizeof(float), "offset table shares the float buffer");
-        {
-            int offs[6 * 64];
-            hssfsst::core128_store_offsets(p->klo, p->K > 0 ? p->K : 2, offs, rq);
-            std::memcpy(at.data() + atab_floats, offs, sizeof(offs));
-        }
-        if ((rc = p->d_atab.upload(at.data(), at.size())) != 0) return rc;
-        if (nwin == 128) {
-            // fsst_canon128.hpp: the same constants C_r[n, q] as pairs of halves c1 + c2, scaled by 2^sc into [2^13, 2^14).
-            // Entry (tap n, lane l = (kk, row i), half h): fold term q = kk + 4 (h >> 2), c1 for even h, c2 for odd h
-            // (products x1 c1, x1 c2, x2 c1, x2 c2 against the sample record {x1, x1, x2, x2}).
-            auto comp = [&](int n, int i, int q) -> double {
-                const int gg = i >> 2, sub = i & 3, m = gg;
-                const int r = (sub < 2) ? m : (m ? 8 - m : 4);
-                const double ang = -2.0 * M_PI * (static_cast<double>(r) * q / 8 + static_cast<double>(r) * n / nwin);
-                const double c = std::cos(ang), sn = std::sin(ang);
-                const double sg = (r & 1) ? -0.5 : 0.5;
-                const double wv = window[n + 16 * q], dv = dwb[n + 16 * q];
-                return (sub & 1) ? sg * (wv * sn + dv * c) : sg * (wv * c - dv * sn);
-            };
-            double cmax = 0.0;
-            for (int n = 0; n < 16; ++n) for (int i = 0; i < 16; ++i) for (int q = 0; q < 8; ++q) cmax = std::fmax(cmax, std::fabs(comp(n, i, q)));
-            int ex = 0;
-            if (cmax > 0.0 && std::isfinite(cmax)) (void)std::frexp(cmax, &ex);          // cmax = f 2^ex, f in [0.5, 1)
-            const int sc = 14 - ex;                                                       // cmax 2^sc in [2^13, 2^14)
-            const double cs = std::ldexp(1.0, sc);
-            // (+ the float64 twiddles of the rounding-tie path, 2 kB: the kernels copy the whole table into LDS); then the offsets below
-            std::vector<unsigned short> ht(static_cast<size_t>(hssfsst::kCanonAtabFloats) * 2);
-            static_assert(hssfsst::kCanonAtabFloats == 16 * 64 * 4 + 4 * 128, "f16 operand table + 128 {cos, sin} doubles");
-            for (int i = 0; i < 128; ++i) {
-                const double ang = 2.0 * M_PI * static_cast<double>(i) / 128.0;
-                const double cs2[2] = {std::cos(ang), std::sin(ang)};
-                std::memcpy(ht.data() + static_cast<size_t>(16) * 64 * 8 + static_cast<size_t>(i) * 8, cs2, sizeof(cs2));
-            }
-            for (int n = 0; n < 16; ++n)
-                for (int l = 0; l < 64; ++l)
-                    for (int h = 0; h < 8; ++h) {
-                        const int i = l & 15, kk = l >> 4, q = kk + 4 * (h >> 2);
-                        const double v = comp(n, i, q) * cs;
-                        const _Float16 c1 = static_cast<_Float16>(v);
-                        const _Float16 c2 = static_cast<_Float16>(v - static_cast<double>(c1));
-                        const _Float16 pick = (h & 1) ? c2 : c1;
-                        unsigned short bits;
-                        std::memcpy(&bits, &pick, sizeof(bits));
-                        ht[(static_cast<size_t>(n) * 64 + l) * 8 + h] = bits;
-                    }
-            // fsst_canon128.hpp "Offsets": what a frame of ones contributes to the spectra the source stage starts from.
-            //   Zc[k] = (-1)^k 0.5 sum_{m inside the signal} (w + i dw')[m] e^{-2 pi i k m / 128}  (x cs: plane units),
-            // lane group g holds the classes g and (g ? 8 - g : 4): za[s] = Z[8 s + g], zb[s] = Z[8 s + (g ? 8 - g : 4)], s = 0..15.
-            // Frame 0 = interior (every m), 1 + t = the frame of output column t < 64 (m >= 64 - t), 65 + r = the frame r < 63 samples
-            // before the end (m <= r + 64).  Layout (fsst_canon128.hpp kCanonZcFloats): interior [g][za[0..15] | zb[0..15] | -];
-            // left edge [g][entry][t]; right edge [g][entry][r], r = 63 .. 79 = the interior once more
-            std::vector<float> zc(static_cast<size_t>(hssfsst::kCanonZcFloats), 0.0f);
-            float* zleft = zc.data() + hssfsst::kCanonYcFrame;
-            float* zright = zleft + 4 * 32 * 64 * 2;
-            for (int fr = 0; fr < 1 + 64 + 63; ++fr) {
-                const int m0 = (fr >= 1 && fr <= 64) ? 64 - (fr - 1) : 0;
-                const int m1 = (fr >= 65) ? (fr - 65) + 64 : 127;
-                double zr[128], zi[128];
-                for (int k = 0; k < 128; ++k) {
-                    double re = 0.0, im = 0.0;
-                    for (int m = m0; m <= m1; ++m) {
-                        const double ang = -2.0 * M_PI * static_cast<double>((k * m) % 128) / 128.0;
-                        const double c = std::cos(ang), sn = std::sin(ang);
-                        re += window[m] * c - dwb[m] * sn;
-                        im += window[m] * sn + dwb[m] * c;
-                    }
-                    const double sg = (k & 1) ? -0.5 : 0.5;
-                    zr[k] = sg * re * cs; zi[k] = sg * im * cs;
-                }
-                for (int gg = 0; gg < 4; ++gg)
-                    for (int s16 = 0; s16 < 16; ++s16) {
-                        const int ks[2] = {8 * s16 + gg, 8 * s16 + (gg ? 8 - gg : 4)};       // the lane group's two classes: za[s], zb[s]
-                        for (int ab = 0; ab < 2; ++ab) {
-                            const int ent = ab * 16 + s16;
-                            const float vr = static_cast<float>(zr[ks[ab]]), vi = static_cast<float>(zi[ks[ab]]);
-                            auto put = [&](float* e) { e[0] = vr; e[1] = vi; };
-                            if (fr == 0) {
-                                put(zc.data() + (gg * hssfsst::kCanonYcGroup + ent) * 2);
-                                for (int r = 63; r < hssfsst::kCanonYcRight; ++r) put(zright + ((gg * 32 + ent) * hssfsst::kCanonYcRight + r) * 2);
-                            } else if (fr <= 64) put(zleft + ((gg * 32 + ent) * 64 + (fr - 1)) * 2);
-                            else put(zright + ((gg * 32 + ent) * hssfsst::kCanonYcRight + (fr - 65)) * 2);
-                        }
-                    }
-            }
-            p->canon_inv_c = static_cast<float>(std::ldexp(1.0, -sc));
-            p->canon_r2s = static_cast<float>(static_cast<double>(p->r2scale) * cs * cs);
-            std::vector<float> t16(static_cast<size_t>(hssfsst::kCanonAtabFloats) + zc.size());
-            std::memcpy(t16.data(), ht.data(), ht.size() * sizeof(unsigned short));
-            std::memcpy(t16.data() + hssfsst::kCanonAtabFloats, zc.data(), zc.size() * sizeof(float));
-            if ((rc = p->d_atab16.upload(t16.data(), t16.size())) != 0) return rc;
-        }
-    }
+    std::vector<double> dwb(nwin);                        // derivative window in bin units
+    if (int rc = tables::dwindow(window, nwin, static_cast<double>(nwin) / (2.0 * M_PI), dwb.data())) return fail(rc, "plan_create: singular spline system");
+    if (int rc = choose_family(p.get())) return rc;
+    if (int rc = upload_tables(p.get(), window, dwb.data())) return rc;
+    set_derived_facts(p.get());
     *out = p.release();
     return 0;
 }
@@ -1665,9 +1390,8 @@ static int exec_impl(hssfsst_plan* p, const float* x, int64_t batch, int n, int6
     cx.st = st;
     cx.zpref = redo ? HSSFSST_ZPATH_ONE_CU : p->zpath_pref;
     const int ofps = out_floats_per_sample(p);
-    const bool use128 = (p->d_atab.get() != nullptr);
-    // statistics partials per signal: one per 16-frame group (MFMA kernel) / per 64-frame tile (generic kernel)
-    const int fpp = (use128 || p->dft) ? 16 : kTile;
+    // statistics partials per signal: one per 16-frame group (MFMA and any-length kernels) / per 64-frame tile (generic kernel)
+    const int fpp = p->family == Family::Generic ? kTile : 16;
     const int nblk = (ncols + fpp - 1) / fpp;
     const long long nblocks = static_cast<long long>(batch) * nblk;
     if (nblocks > 0x7fffffffLL) return fail(HSSFSST_EINVAL, "exec: batch*tiles = %lld exceeds the grid limit; split the batch", nblocks);
@@ -1742,9 +1466,9 @@ static int exec_impl(hssfsst_plan* p, const float* x, int64_t batch, int n, int6
     cp.wtab = p->d_wtab.get(); cp.twtab = p->d_wtab.get() + 2 * p->nwin; cp.r2scale = p->r2scale;
     if ((rc = timing_event(p, cx)) != 0) return rc;
     const bool no_fused = debug_switches().no_fused;      // A/B and bit-equality tests
-    if (p->dft) {
+    if (p->family == Family::Dft) {
         rc = launch_dft(p, cx, dx, kout, batch, n, x_stride, col0, ncols);
-    } else if (use128) {
+    } else if (p->family == Family::Mfma) {
         rc = launch_core128(p, cx, dx, x_stride, kout, cp.partials, n, col0, ncols, batch, !no_fused && cx.zpref != HSSFSST_ZPATH_TWO_LAUNCH,
                             half ? dout : nullptr);
     } else switch (p->R) {
@@ -1890,7 +1614,7 @@ int hssfsst_exec_ragged(hssfsst_plan* p, const float* x, int64_t x_len, const in
             return fail(HSSFSST_EINVAL, "exec_ragged: signal %lld too long (n = %lld)", static_cast<long long>(i), static_cast<long long>(lens[i]));
     if (batch == 0 || p->K == 0) return 0;
     const int ofps = out_floats_per_sample(p);
-    if (p->d_atab.get() == nullptr) {
+    if (p->family != Family::Mfma) {
         // the generic and any-length kernels: one exec per signal (the kernels of hssfsst_exec, on the caller's stream)
         long long off = 0;
         for (int64_t i = 0; i < batch; ++i) {
@@ -1968,20 +1692,16 @@ int hssfsst_exec_ragged(hssfsst_plan* p, const float* x, int64_t x_len, const in
     cx.st = st;
     timing_begin(p, cx);
     if ((rc = timing_event(p, cx)) != 0) return rc;
-    hssfsst::Core128Params cp{};
-    cp.x = dx; cp.out = kout; cp.partials = p->d_partials.get(); cp.atab = p->d_atab.get();
-    cp.wtab = p->d_wtab.get(); cp.twtab = p->d_wtab.get() + 2 * p->nwin; cp.r2scale = p->r2scale;
-    cp.n = 1; cp.klo = p->klo; cp.K = p->K; cp.mode = p->mode; cp.nsig = static_cast<int>(std::min<int64_t>(batch, 0x7fffffff));
-    cp.col0 = 0; cp.ncols = 1; cp.xstride = 0;
+    hssfsst::Core128Params cp = core128_params(p);
+    cp.x = dx; cp.out = kout; cp.partials = p->d_partials.get();
+    cp.n = 1; cp.nsig = static_cast<int>(std::min<int64_t>(batch, 0x7fffffff)); cp.col0 = 0; cp.ncols = 1; cp.xstride = 0;
     cp.rsig = d_rsig; cp.rchunk = d_chunks; cp.rnchunks = static_cast<int>(p->rtab_nchunks);
-    const bool fast = (p->mode == HSSFSST_MODE_STACK || p->mode == HSSFSST_MODE_STACK_UNNORM) && (p->K & 1) == 0 && p->K <= 24;
-    const bool canon = hssfsst::own_s0(p->klo, p->rq) == 0 && hssfsst::own_s1(p->klo, p->K, p->rq) == 3;
     // (the canonical-class band in STACK modes takes the canonical kernel's arithmetic, as every single exec of it does; the
     //  general kernels give other -- equally accurate -- bits there)
-    if (fast && p->nt == 16 && p->rq == 8 && plan_is_canon(p))
+    if (p->fast && p->nt == 16 && p->rq == 8 && plan_is_canon(p))
         rc = canon_dispatch(p, [&](auto KL, auto KN) { return launch_canon_band<decltype(KL)::value, decltype(KN)::value, true>(p, cx, cp, p->rtab_nchunks); });
     else
-        rc = launch_core128_plain<true>(p, cx, cp, p->rtab_nchunks, fast, canon);
+        rc = launch_core128_plain<true>(p, cx, cp, p->rtab_nchunks);
     if (rc != 0) return rc;
     if ((rc = timing_core_done(p, cx)) != 0) return rc;
     if (p->mode == HSSFSST_MODE_STACK) {
@@ -2160,6 +1880,56 @@ int rs_conv(hipStream_t st, double2* w, long long Mw, long long cnt, int M, cons
     return rs_dit(st, w, Mw, cnt, M, tw, twM);
 }
 
+// The two creates behind their argument checks: the plan on `device` with its tables c1[n] | B1[M1] | c2[num] | B2[M2] | tw[Mt / 2],
+// made on the host and uploaded in one piece.  n = 0: a ragged plan, which holds c2 | B2 only (its twiddles: rs_ragged_twiddles).
+int rs_plan_create(const char* what, hssfsst_resample_plan** out, int device, int64_t n, int64_t num)
+{
+    if (int rc = check_device(what, device)) return rc;
+    DEVICE_SCOPE(device);
+    using hssfsst::resample_detail::cd;
+    static_assert(sizeof(cd) == sizeof(double2), "std::complex<double> and double2 share a layout");
+    std::unique_ptr<hssfsst_resample_plan> p(new (std::nothrow) hssfsst_resample_plan());
+    if (!p) return fail(HSSFSST_ENOMEM, "%s: host allocation failed", what);
+    p->device = device; p->n = n; p->num = num; p->ragged = n == 0;
+    p->M1 = p->ragged ? 0 : pow2_at_least(2 * n - 1); p->M2 = pow2_at_least(2 * num - 1);
+    p->Mt = p->M1 > p->M2 ? p->M1 : p->M2;
+    const size_t o_B1 = static_cast<size_t>(n), o_c2 = o_B1 + p->M1, o_B2 = o_c2 + static_cast<size_t>(num), o_tw = o_B2 + p->M2;
+    const size_t total = o_tw + (p->ragged ? 0 : tables::twiddle_count(p->Mt));
+    try {
+        std::vector<cd> tab(total);
+        if (!p->ragged) {
+            bluestein_tables(n, p->M1, 1.0, tab.data(), tab.data() + o_B1);
+            tables::twiddle_table(p->Mt, tab.data() + o_tw);
+        }
+        bluestein_tables(num, p->M2, -1.0, tab.data() + o_c2, tab.data() + o_B2);
+        if (int rc = p->d_tab.upload(reinterpret_cast<const double2*>(tab.data()), total)) return rc;
+    } catch (const std::bad_alloc&) {
+        return fail(HSSFSST_ENOMEM, "%s: out of host memory", what);
+    }
+    const double2* t = p->d_tab.get();
+    if (!p->ragged) { p->c1 = t; p->B1 = t + o_B1; p->tw = t + o_tw; }
+    p->c2 = t + o_c2; p->B2 = t + o_B2;
+    *out = p.release();
+    return 0;
+}
+
+// the ragged plan's twiddle table, grown to Mt points: exp(-2 pi i k / Mt), k < Mt / 2, made on the host as the dense plan's.
+// A larger table holds the same bits at the indices a smaller one uses (k 2^j / (Mt 2^j) is exact): results do not depend on it.
+int rs_ragged_twiddles(hssfsst_resample_plan* p, int Mt)
+{
+    if (Mt <= p->tw_M) return 0;
+    try {
+        std::vector<hssfsst::resample_detail::cd> tw(tables::twiddle_count(Mt));
+        tables::twiddle_table(Mt, tw.data());
+        p->tw_M = 0;                                     // (upload's hipFree of the old table waits for the device: no earlier launch still reads it)
+        if (int rc = p->d_tw.upload(reinterpret_cast<const double2*>(tw.data()), tw.size())) return rc;
+    } catch (const std::bad_alloc&) {
+        return fail(HSSFSST_ENOMEM, "resample_exec_ragged: out of host memory");
+    }
+    p->tw_M = Mt;
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2174,35 +1944,7 @@ int hssfsst_resample_plan_create(hssfsst_resample_plan** out, int device, int64_
     if (n > kRsMaxLen || num > kRsMaxLen)
         return fail(HSSFSST_EUNSUPPORTED, "resample_plan_create: lengths above %lld samples are not supported (n=%lld num=%lld)",
                     static_cast<long long>(kRsMaxLen), static_cast<long long>(n), static_cast<long long>(num));
-    if (int rc = check_device("resample_plan_create", device)) return rc;
-    DEVICE_SCOPE(device);
-    using hssfsst::resample_detail::cd;
-    static_assert(sizeof(cd) == sizeof(double2), "std::complex<double> and double2 share a layout");
-    std::unique_ptr<hssfsst_resample_plan> p(new (std::nothrow) hssfsst_resample_plan());
-    if (!p) return fail(HSSFSST_ENOMEM, "resample_plan_create: host allocation failed");
-    p->device = device; p->n = n; p->num = num;
-    p->M1 = pow2_at_least(2 * n - 1);
-    p->M2 = pow2_at_least(2 * num - 1);
-    p->Mt = p->M1 > p->M2 ? p->M1 : p->M2;
-    const size_t ntw = static_cast<size_t>(p->Mt > 1 ? p->Mt / 2 : 1);
-    const size_t o_B1 = static_cast<size_t>(n), o_c2 = o_B1 + p->M1, o_B2 = o_c2 + static_cast<size_t>(num), o_tw = o_B2 + p->M2;
-    const size_t total = o_tw + ntw;
-    try {
-        std::vector<cd> tab(total);
-        bluestein_tables(n, p->M1, 1.0, tab.data(), tab.data() + o_B1);
-        bluestein_tables(num, p->M2, -1.0, tab.data() + o_c2, tab.data() + o_B2);
-        for (size_t k = 0; k < ntw; ++k) {
-            const double ang = -2.0 * M_PI * static_cast<double>(k) / static_cast<double>(p->Mt);
-            tab[o_tw + k] = cd(std::cos(ang), std::sin(ang));
-        }
-        if (int rc = p->d_tab.upload(reinterpret_cast<const double2*>(tab.data()), total)) return rc;
-    } catch (const std::bad_alloc&) {
-        return fail(HSSFSST_ENOMEM, "resample_plan_create: out of host memory");
-    }
-    const double2* t = p->d_tab.get();
-    p->c1 = t; p->B1 = t + o_B1; p->c2 = t + o_c2; p->B2 = t + o_B2; p->tw = t + o_tw;
-    *out = p.release();
-    return 0;
+    return rs_plan_create("resample_plan_create", out, device, n, num);
 }
 
 int hssfsst_resample_plan_destroy(hssfsst_resample_plan* p)
@@ -2317,58 +2059,8 @@ int hssfsst_resample_plan_create_ragged(hssfsst_resample_plan** out, int device,
     if (num > kRsMaxLen)
         return fail(HSSFSST_EUNSUPPORTED, "resample_plan_create_ragged: lengths above %lld samples are not supported (num=%lld)",
                     static_cast<long long>(kRsMaxLen), static_cast<long long>(num));
-    if (int rc = check_device("resample_plan_create_ragged", device)) return rc;
-    DEVICE_SCOPE(device);
-    using hssfsst::resample_detail::cd;
-    std::unique_ptr<hssfsst_resample_plan> p(new (std::nothrow) hssfsst_resample_plan());
-    if (!p) return fail(HSSFSST_ENOMEM, "resample_plan_create_ragged: host allocation failed");
-    p->ragged = true;
-    p->device = device; p->n = 0; p->num = num;
-    p->M1 = 0;
-    p->M2 = pow2_at_least(2 * num - 1);
-    p->Mt = p->M2;
-    const size_t total = static_cast<size_t>(num) + static_cast<size_t>(p->M2);
-    try {
-        std::vector<cd> tab(total);
-        bluestein_tables(num, p->M2, -1.0, tab.data(), tab.data() + num);
-        if (int rc = p->d_tab.upload(reinterpret_cast<const double2*>(tab.data()), total)) return rc;
-    } catch (const std::bad_alloc&) {
-        return fail(HSSFSST_ENOMEM, "resample_plan_create_ragged: out of host memory");
-    }
-    p->c2 = p->d_tab.get(); p->B2 = p->d_tab.get() + num;
-    *out = p.release();
-    return 0;
+    return rs_plan_create("resample_plan_create_ragged", out, device, 0, num);
 }
-
-}  // extern "C"
-
-namespace {
-
-// the ragged plan's twiddle table, grown to Mt points: exp(-2 pi i k / Mt), k < Mt / 2, made on the host as the dense plan's.
-// A larger table holds the same bits at the indices a smaller one uses (k 2^j / (Mt 2^j) is exact): results do not depend on it.
-int rs_ragged_twiddles(hssfsst_resample_plan* p, int Mt)
-{
-    using hssfsst::resample_detail::cd;
-    if (Mt <= p->tw_M) return 0;
-    const size_t ntw = static_cast<size_t>(Mt > 1 ? Mt / 2 : 1);
-    try {
-        std::vector<cd> tw(ntw);
-        for (size_t k = 0; k < ntw; ++k) {
-            const double ang = -2.0 * M_PI * static_cast<double>(k) / static_cast<double>(Mt);
-            tw[k] = cd(std::cos(ang), std::sin(ang));
-        }
-        p->tw_M = 0;                                     // (upload's hipFree of the old table waits for the device: no earlier launch still reads it)
-        if (int rc = p->d_tw.upload(reinterpret_cast<const double2*>(tw.data()), ntw)) return rc;
-    } catch (const std::bad_alloc&) {
-        return fail(HSSFSST_ENOMEM, "resample_exec_ragged: out of host memory");
-    }
-    p->tw_M = Mt;
-    return 0;
-}
-
-}  // namespace
-
-extern "C" {
 
 int hssfsst_resample_exec_ragged(hssfsst_resample_plan* p, const void* x, int x_dtype, int64_t x_len, const int64_t* starts,
                                  const int64_t* lens, int64_t count, int x_on_device, void* y, int y_dtype, int64_t* labels,
@@ -2654,7 +2346,7 @@ int hssfsst_stream_step(hssfsst_plan* p, float* tape, int64_t tape_len, int64_t 
     DEVICE_SCOPE(p->device);
     // one launch for the whole step where the transform is the wide-store MFMA kernel in one-group chunks (nwin 256 / 512, an even
     // band of <= 24 rows: BASELINE config 5); host samples are copied into the tape first and the kernel reads them there
-    const bool one_launch = p->d_atab.get() != nullptr && p->rq == 16 && (p->K & 1) == 0 && p->K <= 24 && !debug_switches().no_stream_fuse &&
+    const bool one_launch = p->family == Family::Mfma && p->rq == 16 && p->fast && !debug_switches().no_stream_fuse &&
                             (reinterpret_cast<uintptr_t>(out) & 15) == 0 &&
                             static_cast<long long>(channels) * ((chunk + 15) / 16) < 0x7fffffffLL;
     int launched = 0;
