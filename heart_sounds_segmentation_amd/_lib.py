@@ -272,3 +272,19 @@ def check(rc: int, what: str) -> None:
     if rc == E_INVAL:
         raise ValueError(f"{what}: {msg} (status {rc})")
     raise RuntimeError(f"{what}: {msg} (status {rc})")
+
+
+WHOLE_RECORDINGS = (0x7fffffff, 1)     # the (stride, n) pair under which every recording is one "frame": its start, nothing else
+
+
+def pack_recordings(ptrs, lens, stage, starts, expected: int, stride: int = WHOLE_RECORDINGS[0], n: int = WHOLE_RECORDINGS[1]) -> None:
+    """``hssfsst_pack_recordings``: the host float32 recordings behind ``ptrs`` (uint64 array; ``lens`` int64 array) are copied back
+    to back into the tensor ``stage`` (threaded), and the starts of their ``n``-sample frames at ``stride`` -- by default of the
+    recordings themselves -- are written to the int64 array ``starts``.  ``expected``: the number of starts the caller counted;
+    any other return is the library's error, or a ValueError."""
+    count = int(lens.shape[0])
+    got = lib().hssfsst_pack_recordings(ctypes.c_void_p(ptrs.ctypes.data), ctypes.c_void_p(lens.ctypes.data), count, int(stride), int(n),
+                                        ctypes.c_void_p(stage.data_ptr()), int(stage.numel()),
+                                        ctypes.c_void_p(starts.ctypes.data), int(starts.shape[0]), 0)
+    if got != expected:
+        check(int(got) if got < 0 else E_INVAL, "hssfsst_pack_recordings")

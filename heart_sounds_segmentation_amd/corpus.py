@@ -17,6 +17,9 @@ How it is fed (round 3; round 2 moved 77.7 k windows/s from host recordings agai
   * the recordings of a group are packed into one of two PINNED staging buffers and uploaded on a side stream while
     the previous group is transformed (``hssfsst_exec_list`` writes straight into the group's rows of the arena);
   * host-returned features leave the device group by group on a third stream, overlapping the next group's transform.
+All three builds below are fed by ONE such pipeline, ``CorpusBuilder._pipeline``: it owns the staging buffers, the three streams and
+the events that say when a staging buffer or a half of the device ring may be overwritten.  A build hands it the groups, the arena
+rows each group owns, the pointers to pack and its own launches for one group; nothing else differs between them.
 
 With ``resample=Resample(num)`` the builder is the reference's ``Compose([Resample(num), FSST(...)])`` under ``framing=True``
 (heart_sounds.py:166-168,199-212): every ``frame_len``-sample frame is resampled to ``num`` samples on the device (list form of
@@ -44,12 +47,14 @@ order is the single-process list; ``gather_features`` reassembles the feature te
 """
 from __future__ import annotations
 
+import math
 from collections.abc import Sequence as _SequenceABC
-from typing import Iterable, List, Optional, Sequence, Tuple
+from typing import Callable, Iterable, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
+from . import _lib
 from . import dist as hdist
 from .framing import frame_batch, frame_starts
 
@@ -78,6 +83,35 @@ class FrameItems(_SequenceABC):
         return self.features[i], (self.labels[i] if self.labels is not None else None)
 
 
+class _Group(NamedTuple):
+    """What a build's launches are told about a group: recordings ``a:b`` of the list, rows ``r0:r1`` of the feature arena."""
+    a: int
+    b: int
+    r0: int
+    r1: int
+
+
+def _host_f32(ts) -> Tuple[list, np.ndarray]:
+    """Every tensor as contiguous host float32 (the tensor itself where it already is one), and the array of their addresses for
+    ``_lib.pack_recordings``.  The caller keeps the list alive while the addresses are in use."""
+    held = [t if (t.dtype == torch.float32 and t.is_contiguous() and not t.is_cuda) else t.detach().to("cpu", torch.float32).contiguous()
+            for t in ts]                                  # (device recordings are staged through the host like the rest: rare)
+    return held, np.asarray([t.data_ptr() for t in held], dtype=np.uint64)
+
+
+def _sample_groups(lens_np: np.ndarray, max_samples: int) -> List[Tuple[int, int]]:
+    """Groups ``(a, b)`` of consecutive recordings of at most ``max_samples`` samples (a longer recording is a group of its own)."""
+    groups: List[Tuple[int, int]] = []
+    g0, acc = 0, 0
+    for i, T in enumerate(lens_np.tolist()):
+        if acc > 0 and acc + T > max_samples:
+            groups.append((g0, i))
+            g0, acc = i, 0
+        acc += T
+    groups.append((g0, len(lens_np)))
+    return groups
+
+
 class CorpusBuilder:
     """The builder as an object: keeps its pinned staging buffers, device staging, streams and (when asked) the feature
     arena between calls, so that a second corpus of the same size pays for no allocation (page-locking the host
@@ -89,44 +123,116 @@ class CorpusBuilder:
         self.resample = resample                          # a Resample: frames are resampled to resample.num samples first
         self.dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         self.wpl, self.pin_host = int(windows_per_launch), bool(pin_host)
-        self._cap_samples = self._cap_frames = self._cap_ring = 0
-        self._cap_rs = self._cap_lab = 0
         self._bufs = None
 
-    def _ensure_resample(self, max_samples: int, max_frames: int, num: int, need_labels: bool) -> None:
-        """Device buffer of a group's resampled frames; pinned / device staging of its label tracks."""
-        b, dev = self._bufs, self.dev
-        if max_frames * num > self._cap_rs:
-            b["rs_d"] = torch.empty(max_frames * num, dtype=torch.float32, device=dev)
-            self._cap_rs = max_frames * num
-        if need_labels and max_samples > self._cap_lab:
-            b["lab_h"] = [torch.empty(max_samples, dtype=torch.float32, pin_memory=True) for _ in range(2)]
-            b["lab_d"] = [torch.empty(max_samples, dtype=torch.float32, device=dev) for _ in range(2)]
-            b["lab_starts"] = np.empty(max_frames, dtype=np.int64)
-            self._cap_lab = max_samples
-        elif need_labels and b["lab_starts"].shape[0] < max_frames:
-            b["lab_starts"] = np.empty(max_frames, dtype=np.int64)
-
-    def _ensure(self, max_samples: int, max_frames: int, C: int, need_ring: bool, item_len: Optional[int] = None,
-                dtype: torch.dtype = torch.float32) -> None:
-        dev = self.dev
+    def _staging(self) -> dict:
+        """The streams, the events and every staging buffer made so far (``_buf``), kept between calls."""
         if self._bufs is None:
+            dev = self.dev
             self._bufs = {"up": torch.cuda.Stream(dev), "down": torch.cuda.Stream(dev),
                           "up_done": [torch.cuda.Event() for _ in range(2)], "used": [torch.cuda.Event() for _ in range(2)],
                           "ring_free": [torch.cuda.Event() for _ in range(2)]}
-        b = self._bufs
-        if max_samples > self._cap_samples:
-            b["stage_h"] = [torch.empty(max_samples, dtype=torch.float32, pin_memory=True) for _ in range(2)]
-            b["stage_d"] = [torch.empty(max_samples, dtype=torch.float32, device=dev) for _ in range(2)]
-            self._cap_samples = max_samples
-        if max_frames > self._cap_frames:
-            b["start_h"] = [torch.empty(max_frames, dtype=torch.int64, pin_memory=True) for _ in range(2)]
-            b["start_d"] = [torch.empty(max_frames, dtype=torch.int64, device=dev) for _ in range(2)]
-            self._cap_frames = max_frames
-        item_len = self.frame_len if item_len is None else item_len
-        if need_ring and (max_frames * C > self._cap_ring or b["ring_d"][0].shape[1] != item_len or b["ring_d"][0].dtype != dtype):
-            b["ring_d"] = [torch.empty((max_frames, item_len, C), dtype=dtype, device=dev) for _ in range(2)]
-            self._cap_ring = max_frames * C
+        return self._bufs
+
+    def _buf(self, key: str, numel: int, dtype: torch.dtype = torch.float32, pinned: bool = False, count: int = 2) -> List[torch.Tensor]:
+        """``count`` flat staging buffers ``key`` of at least ``numel`` elements, on the device or in pinned host memory.  They only
+        grow, and their capacity is their own ``numel()``."""
+        B = self._staging()
+        cur = B.get(key)
+        if cur is None or cur[0].numel() < numel or cur[0].dtype != dtype:
+            where = {"pin_memory": True} if pinned else {"device": self.dev}
+            cur = B[key] = [torch.empty(numel, dtype=dtype, **where) for _ in range(count)]
+        return cur
+
+    def _arena(self, shape: Tuple[int, ...], dtype: torch.dtype, keep_on_device: bool) -> torch.Tensor:
+        """A feature arena: on the device, else in pinned host memory (``pin_host``), else pageable."""
+        if keep_on_device:
+            return torch.empty(shape, dtype=dtype, device=self.dev)
+        try:
+            return torch.empty(shape, dtype=dtype, pin_memory=bool(self.pin_host and shape[0] > 0))
+        except RuntimeError:                              # page-locking that much memory can be refused: pageable then
+            return torch.empty(shape, dtype=dtype)
+
+    def _pipeline(self, groups: List[Tuple[int, int]], rows: np.ndarray, ptrs_np: np.ndarray, lens_np: np.ndarray,
+                  feats: torch.Tensor, keep_on_device: bool, launch: Callable, tracks_np: Optional[np.ndarray] = None,
+                  frame: Optional[Tuple[int, int]] = None, after: Optional[Callable] = None) -> None:
+        """The double-buffered feed of every build.  ``groups``: ``(a, b)`` ranges of recordings (at least one); the samples of a
+        group are those of its recordings (``lens_np``, addresses ``ptrs_np``), its rows of ``feats`` are ``rows[a]:rows[b]``.
+        ``tracks_np``: addresses of label tracks of the same lengths, uploaded beside the samples.  ``frame``: the ``(stride,
+        frame_len)`` of a framed build, whose frame starts are uploaded too (one start per arena row); None for whole recordings.
+
+        Per group, ``launch(g, x, starts, tracks, dst)`` enqueues the build's work on the current stream: ``g`` a ``_Group``, ``x`` the
+        packed samples on the device, ``starts`` the frame starts (None unless ``frame``), ``tracks`` the packed label tracks (None
+        unless ``tracks_np``), ``dst`` the group's rows of the arena (``keep_on_device``) or a half of the device ring viewed to
+        their shape, from which they are copied to the host arena on a third stream.  ``after(g)`` is host work of the group that
+        overlaps its launches; it runs once the NEXT group's packing and upload are under way, so that it never delays them."""
+        fsst, dev = self.fsst, self.dev
+        stride, frame_len = frame if frame is not None else _lib.WHOLE_RECORDINGS
+        pos_np = np.concatenate([[0], np.cumsum(lens_np)])
+        item = tuple(feats.shape[1:])                    # one arena row: (C,) or (item_len, C)
+        per_row = math.prod(item)
+        gs = [_Group(a, b, int(rows[a]), int(rows[b])) for a, b in groups]
+        sizes = [int(pos_np[g.b] - pos_np[g.a]) for g in gs]                         # samples of each group
+        counts = [(g.r1 - g.r0) if frame is not None else (g.b - g.a) for g in gs]   # starts the pack call writes for it
+        B = self._staging()
+        stage_h, stage_d = self._buf("stage_h", max(sizes), pinned=True), self._buf("stage_d", max(sizes))
+        if frame is not None:
+            start_h, start_d = self._buf("start_h", max(counts), torch.int64, pinned=True), self._buf("start_d", max(counts), torch.int64)
+        if tracks_np is not None:
+            lab_h, lab_d = self._buf("lab_h", max(sizes), pinned=True), self._buf("lab_d", max(sizes))
+        if not keep_on_device:                           # ONE kind of device ring: two flat halves, viewed per group
+            ring = self._buf("ring", max(g.r1 - g.r0 for g in gs) * per_row, feats.dtype)
+        aside = np.empty(max(counts), dtype=np.int64)    # starts that nobody reads: of whole recordings, of label tracks
+        main, up, down = torch.cuda.current_stream(dev), B["up"], B["down"]
+        up_done, used, ring_free = B["up_done"], B["used"], B["ring_free"]
+        up.wait_stream(main)                             # (the staging buffers may still be read by an earlier call's work)
+
+        # the host side of a group is ONE native call (hssfsst_pack_recordings: threaded copies into the pinned staging
+        # buffer + the frame starts): per recording Python does nothing but hand over a pointer.  (Per-recording copy_ /
+        # numpy calls were 0.29 ms per recording: 115 k windows/s however fast the device is.)
+        def pack(gi: int) -> None:
+            """Host side of group gi: recordings (and label tracks) back to back into pinned staging, frame starts; upload on `up`."""
+            g, buf, n, ns = gs[gi], gi & 1, sizes[gi], counts[gi]
+            if gi >= 2:
+                used[buf].synchronize()                  # the launches of group gi - 2 no longer read this staging pair
+            starts = start_h[buf].numpy() if frame is not None else aside[:ns]
+            _lib.pack_recordings(ptrs_np[g.a:g.b], lens_np[g.a:g.b], stage_h[buf], starts, ns, stride, frame_len)
+            if tracks_np is not None:
+                _lib.pack_recordings(tracks_np[g.a:g.b], lens_np[g.a:g.b], lab_h[buf], aside[:ns], ns, stride, frame_len)
+            with torch.cuda.stream(up):
+                stage_d[buf][:n].copy_(stage_h[buf][:n], non_blocking=True)
+                if frame is not None:
+                    start_d[buf][:ns].copy_(start_h[buf][:ns], non_blocking=True)
+                if tracks_np is not None:
+                    lab_d[buf][:n].copy_(lab_h[buf][:n], non_blocking=True)
+                up_done[buf].record(up)
+
+        pack(0)
+        for gi, g in enumerate(gs):
+            buf, n, ns = gi & 1, sizes[gi], counts[gi]
+            main.wait_event(up_done[buf])
+            if keep_on_device:
+                dst = feats[g.r0:g.r1]
+            else:
+                if gi >= 2:
+                    main.wait_event(ring_free[buf])      # the copy of group gi - 2 has left this half of the ring
+                dst = ring[buf][:(g.r1 - g.r0) * per_row].view((g.r1 - g.r0,) + item)
+            launch(g, stage_d[buf][:n], start_d[buf][:ns] if frame is not None else None,
+                   lab_d[buf][:n] if tracks_np is not None else None, dst)
+            used[buf].record(main)
+            if not keep_on_device:
+                down.wait_stream(main)
+                with torch.cuda.stream(down):
+                    feats[g.r0:g.r1].copy_(dst, non_blocking=True)
+                    ring_free[buf].record(down)
+            if gi + 1 < len(gs):
+                pack(gi + 1)                             # host packing + upload of the next group overlap these launches
+            if after is not None:
+                after(g)                                 # (host work, also overlapped)
+        if not keep_on_device:
+            down.synchronize()
+        main.synchronize()
+        fsst.check()
 
     def build_recordings(self, recordings: Iterable[Tuple[torch.Tensor, Optional[torch.Tensor]]], keep_on_device: bool = False,
                          max_samples: int = 1 << 25) -> "RecordingItems":
@@ -156,84 +262,17 @@ class CorpusBuilder:
         from .transforms.synchrosqueeze import RaggedFeatures
         plan = fsst._plan(fsst._device_index(torch.empty(0, device=dev)))
         C, K, fdt = plan.ofps, plan.K, plan.out_dtype     # (fdt: the features' element type -- a half STACK transform's out_dtype)
-        if keep_on_device:
-            feats = torch.empty((total, C), dtype=fdt, device=dev)
-        else:
-            try:
-                feats = torch.empty((total, C), dtype=fdt, pin_memory=bool(self.pin_host and total > 0))
-            except RuntimeError:                          # page-locking that much memory can be refused: pageable then
-                feats = torch.empty((total, C), dtype=fdt)
+        feats = self._arena((total, C), fdt, keep_on_device)
         items = RecordingItems(RaggedFeatures(feats, offsets, K, False), ys)
         if total == 0:
             return items
-        # groups of at most max_samples samples (a longer recording is a group of its own)
-        groups: List[Tuple[int, int]] = []
-        g0, acc = 0, 0
-        for i, T in enumerate(lens_np.tolist()):
-            if acc > 0 and acc + T > max_samples:
-                groups.append((g0, i))
-                g0, acc = i, 0
-            acc += T
-        groups.append((g0, len(xs)))
-        pos_np = np.concatenate([[0], np.cumsum(lens_np)])
-        max_group = max(int(pos_np[b] - pos_np[a]) for a, b in groups)
-        self._ensure(max_group, 0, C, False)
-        B = self._bufs
-        if not keep_on_device and (B.get("rec_ring") is None or B["rec_ring"][0].numel() < max_group * C or B["rec_ring"][0].dtype != fdt):
-            B["rec_ring"] = [torch.empty(max_group * C, dtype=fdt, device=dev) for _ in range(2)]
-        main, up, down = torch.cuda.current_stream(dev), B["up"], B["down"]
-        stage_h, stage_d = B["stage_h"], B["stage_d"]
-        up_done, used, ring_free = B["up_done"], B["used"], B["ring_free"]
-        up.wait_stream(main)
-        from . import _lib
-        import ctypes
-        held = [t if (t.dtype == torch.float32 and t.is_contiguous() and not t.is_cuda) else t.detach().to("cpu", torch.float32).contiguous()
-                for t in xs]                               # (device recordings are staged through the host like the rest: rare)
-        ptrs_np = np.asarray([t.data_ptr() for t in held], dtype=np.uint64)
-        L = _lib.lib()
-        starts_np = np.empty(len(xs), dtype=np.int64)
+        held, ptrs_np = _host_f32(xs)                   # (held: what the addresses point to, alive until the pipeline is through)
 
-        def pack(gi: int) -> int:
-            """Host side of group gi: recordings back to back into pinned staging (one threaded native call); upload on `up`."""
-            a, b = groups[gi]
-            buf = gi & 1
-            if gi >= 2:
-                used[buf].synchronize()                  # the transform of group gi - 2 no longer reads this staging buffer
-            n = int(pos_np[b] - pos_np[a])
-            got = L.hssfsst_pack_recordings(ctypes.c_void_p(ptrs_np[a:b].ctypes.data), ctypes.c_void_p(lens_np[a:b].ctypes.data), b - a,
-                                            0x7fffffff, 1, ctypes.c_void_p(stage_h[buf].data_ptr()), int(stage_h[buf].numel()),
-                                            ctypes.c_void_p(starts_np[a:b].ctypes.data), b - a, 0)
-            if got != b - a:
-                _lib.check(int(got) if got < 0 else _lib.E_INVAL, "hssfsst_pack_recordings")
-            with torch.cuda.stream(up):
-                stage_d[buf][:n].copy_(stage_h[buf][:n], non_blocking=True)
-                up_done[buf].record(up)
-            return n
+        def launch(g, x, starts, tracks, dst):
+            fsst.ragged(x, lengths=lens_np[g.a:g.b], out=dst)
 
-        n = pack(0)
-        for gi, (a, b) in enumerate(groups):
-            buf = gi & 1
-            r0, r1 = int(pos_np[a]), int(pos_np[b])
-            main.wait_event(up_done[buf])
-            if keep_on_device:
-                dst = feats[r0:r1]
-            else:
-                if gi >= 2:
-                    main.wait_event(ring_free[buf])
-                dst = B["rec_ring"][buf][:n * C].view(n, C)
-            fsst.ragged(stage_d[buf][:n], lengths=lens_np[a:b], out=dst)
-            used[buf].record(main)
-            if not keep_on_device:
-                down.wait_stream(main)
-                with torch.cuda.stream(down):
-                    feats[r0:r1].copy_(dst, non_blocking=True)
-                    ring_free[buf].record(down)
-            if gi + 1 < len(groups):
-                n = pack(gi + 1)                         # host packing + upload of the next group overlap this transform
-        if not keep_on_device:
-            down.synchronize()
-        main.synchronize()
-        fsst.check()
+        # (a recording's rows of the arena are its samples)
+        self._pipeline(_sample_groups(lens_np, max_samples), offsets.numpy(), ptrs_np, lens_np, feats, keep_on_device, launch)
         return items
 
     def build_resampled_recordings(self, recordings: Iterable[Tuple[torch.Tensor, Optional[torch.Tensor]]], keep_on_device: bool = False,
@@ -273,94 +312,24 @@ class CorpusBuilder:
         count = len(xs)
         plan = fsst._plan(fsst._device_index(torch.empty(0, device=dev)))
         C, fdt = plan.ofps, plan.out_dtype               # (fdt: the features' element type -- a half STACK transform's out_dtype)
-        shape = (count, num, C)
-        if keep_on_device:
-            feats = torch.empty(shape, dtype=fdt, device=dev)
-        else:
-            try:
-                feats = torch.empty(shape, dtype=fdt, pin_memory=bool(self.pin_host and count > 0))
-            except RuntimeError:                          # page-locking that much memory can be refused: pageable then
-                feats = torch.empty(shape, dtype=fdt)
+        feats = self._arena((count, num, C), fdt, keep_on_device)
         if count == 0:
             return FrameItems(feats, None)
-        # groups of at most max_samples input samples (a longer recording is a group of its own)
-        groups: List[Tuple[int, int]] = []
-        g0, acc = 0, 0
-        for i, T in enumerate(lens_np.tolist()):
-            if acc > 0 and acc + T > max_samples:
-                groups.append((g0, i))
-                g0, acc = i, 0
-            acc += T
-        groups.append((g0, count))
-        pos_np = np.concatenate([[0], np.cumsum(lens_np)])
-        max_group = max(int(pos_np[b] - pos_np[a]) for a, b in groups)
-        max_cnt = max(b - a for a, b in groups)
-        self._ensure(max_group, max_cnt, C, not keep_on_device, num, fdt)
-        self._ensure_resample(max_group, max_cnt, num, have_labels)
-        B = self._bufs
+        groups = _sample_groups(lens_np, max_samples)
+        rs_d = self._buf("rs_d", max(b - a for a, b in groups) * num, count=1)[0]     # a group's resampled recordings
         lab_d = torch.empty((count, num), dtype=torch.int64, device=dev) if have_labels else None
-        main, up, down = torch.cuda.current_stream(dev), B["up"], B["down"]
-        stage_h, stage_d = B["stage_h"], B["stage_d"]
-        up_done, used, ring_free = B["up_done"], B["used"], B["ring_free"]
-        up.wait_stream(main)                             # (the staging buffers may still be read by an earlier call's work)
-        from . import _lib
-        import ctypes
-        held = [t if (t.dtype == torch.float32 and t.is_contiguous() and not t.is_cuda) else t.detach().to("cpu", torch.float32).contiguous()
-                for t in xs]                               # (device recordings are staged through the host like the rest: rare)
-        ptrs_np = np.asarray([t.data_ptr() for t in held], dtype=np.uint64)
-        if have_labels:                                  # the label tracks as given (no shift), exact in float32, packed like the signals
-            held_y = [y.to("cpu", torch.float32).contiguous() for y in ys]
-            yptrs_np = np.asarray([y.data_ptr() for y in held_y], dtype=np.uint64)
-        L = _lib.lib()
-        starts_np = np.empty(count, dtype=np.int64)
+        held, ptrs_np = _host_f32(xs)
+        # the label tracks as given (no shift), exact in float32, packed like the signals
+        held_y, yptrs_np = _host_f32(ys) if have_labels else (None, None)
 
-        def pack(gi: int) -> int:
-            """Host side of group gi: recordings (and label tracks) back to back into pinned staging; upload on `up`."""
-            a, b = groups[gi]
-            buf = gi & 1
-            if gi >= 2:
-                used[buf].synchronize()                  # the calls of group gi - 2 no longer read this staging pair
-            n = int(pos_np[b] - pos_np[a])
-            for ptrs, dst in ((ptrs_np, stage_h[buf]),) + (((yptrs_np, B["lab_h"][buf]),) if have_labels else ()):
-                got = L.hssfsst_pack_recordings(ctypes.c_void_p(ptrs[a:b].ctypes.data), ctypes.c_void_p(lens_np[a:b].ctypes.data), b - a,
-                                                0x7fffffff, 1, ctypes.c_void_p(dst.data_ptr()), int(dst.numel()),
-                                                ctypes.c_void_p(starts_np[a:b].ctypes.data), b - a, 0)
-                if got != b - a:
-                    _lib.check(int(got) if got < 0 else _lib.E_INVAL, "hssfsst_pack_recordings")
-            with torch.cuda.stream(up):
-                stage_d[buf][:n].copy_(stage_h[buf][:n], non_blocking=True)
-                if have_labels:
-                    B["lab_d"][buf][:n].copy_(B["lab_h"][buf][:n], non_blocking=True)
-                up_done[buf].record(up)
-            return n
-
-        n = pack(0)
-        for gi, (a, b) in enumerate(groups):
-            buf = gi & 1
-            main.wait_event(up_done[buf])
-            if keep_on_device:
-                dst = feats[a:b]
-            else:
-                if gi >= 2:
-                    main.wait_event(ring_free[buf])
-                dst = B["ring_d"][buf][:b - a]
-            rs = B["rs_d"][:(b - a) * num].view(b - a, num)
-            rsm.ragged(stage_d[buf][:n], lengths=lens_np[a:b], out=rs)
+        def launch(g, x, starts, tracks, dst):
+            rs = rs_d[:(g.b - g.a) * num].view(g.b - g.a, num)
+            rsm.ragged(x, lengths=lens_np[g.a:g.b], out=rs)
             fsst.batch(rs, out=dst)
-            if have_labels:
-                rsm.ragged(B["lab_d"][buf][:n], lengths=lens_np[a:b], labels=True, out=lab_d[a:b])
-            used[buf].record(main)
-            if not keep_on_device:
-                down.wait_stream(main)
-                with torch.cuda.stream(down):
-                    feats[a:b].copy_(dst, non_blocking=True)
-                    ring_free[buf].record(down)
-            if gi + 1 < len(groups):
-                n = pack(gi + 1)                         # host packing + upload of the next group overlap these calls
-        if not keep_on_device:
-            down.synchronize()
-        main.synchronize()
-        fsst.check()
+            if tracks is not None:
+                rsm.ragged(tracks, lengths=lens_np[g.a:g.b], labels=True, out=lab_d[g.a:g.b])
+
+        self._pipeline(groups, np.arange(count + 1), ptrs_np, lens_np, feats, keep_on_device, launch, tracks_np=yptrs_np)
         return FrameItems(feats, lab_d.cpu() if have_labels else None)
 
     def build(self, recordings: Iterable[Tuple[torch.Tensor, Optional[torch.Tensor]]], keep_on_device: bool = False,
@@ -439,110 +408,33 @@ class CorpusBuilder:
                                 or out.is_cuda != bool(keep_on_device)):
             raise ValueError(f"CorpusBuilder.build: out must be a contiguous {fdt} {shape} arena "
                              f"{'on the device' if keep_on_device else 'in host memory'}")
-        feats = out
-        if feats is None:
-            if keep_on_device:
-                feats = torch.empty(shape, dtype=fdt, device=dev)
-            else:
-                try:
-                    feats = torch.empty(shape, dtype=fdt, pin_memory=bool(self.pin_host and total > 0))
-                except RuntimeError:                      # page-locking that much memory can be refused: pageable then
-                    feats = torch.empty(shape, dtype=fdt)
+        feats = out if out is not None else self._arena(shape, fdt, keep_on_device)
         if total == 0:
             if have_labels and rsm is not None:
                 labels = torch.empty((0, out_len), dtype=torch.int64)
             return FrameItems(feats, labels)
-        max_samples = max(sum(int(recs[i][0].shape[0]) for i in range(a, b)) for a, b in groups)
-        max_frames = max(sum(nfr[a:b]) for a, b in groups)
-        self._ensure(max_samples, max_frames, C, not keep_on_device, out_len, fdt)
+        fr_np = np.concatenate([[0], np.cumsum(nfr_np)])  # a recording's rows of the arena are its frames
         dev_labels = have_labels and rsm is not None     # labels resampled on the device: (total, num) device arena, copied once
-        if rsm is not None:
-            self._ensure_resample(max_samples, max_frames, out_len, dev_labels)
-        B = self._bufs
         lab_d = torch.empty((total, out_len), dtype=torch.int64, device=dev) if dev_labels else None
-        main, up, down = torch.cuda.current_stream(dev), B["up"], B["down"]
-        stage_h, stage_d, start_h, start_d = B["stage_h"], B["stage_d"], B["start_h"], B["start_d"]
-        up_done, used, ring_free = B["up_done"], B["used"], B["ring_free"]
-        ring_d = B.get("ring_d")
-        up.wait_stream(main)                             # (the staging buffers may still be read by an earlier call's work)
+        if rsm is not None:                              # a group's resampled frames
+            rs_d = self._buf("rs_d", max(int(fr_np[b] - fr_np[a]) for a, b in groups) * out_len, count=1)[0]
+        held, ptrs_np = _host_f32([x for x, _ in recs])
+        # the label tracks (y - 1), exact in float32, packed like the signals
+        held_y, yptrs_np = _host_f32([y.reshape(-1) - 1 for _, y in recs]) if dev_labels else (None, None)
 
-        # the host side of a group is ONE native call (hssfsst_pack_recordings: threaded copies into the pinned staging
-        # buffer + the frame starts): per recording Python does nothing but hand over a pointer.  (Per-recording copy_ /
-        # numpy calls were 0.29 ms per recording: 115 k windows/s however fast the device is.)
-        from . import _lib
-        import ctypes
-        held = [x if (x.dtype == torch.float32 and x.is_contiguous() and not x.is_cuda) else x.detach().to("cpu", torch.float32).contiguous()
-                for x, _ in recs]
-        ptrs_np = np.asarray([x.data_ptr() for x in held], dtype=np.uint64)
-        if dev_labels:                                   # the label tracks (y - 1), exact in float32, packed like the signals
-            held_y = [(y.reshape(-1) - 1).to("cpu", torch.float32).contiguous() for _, y in recs]
-            yptrs_np = np.asarray([y.data_ptr() for y in held_y], dtype=np.uint64)
-        pos_np = np.concatenate([[0], np.cumsum(lens_np)])
-        fr_np = np.concatenate([[0], np.cumsum(nfr_np)])
-        L = _lib.lib()
-
-        def pack(gi: int) -> Tuple[int, int]:
-            """Host side of group gi: recordings back to back into pinned staging, frame starts; upload on `up`."""
-            a, b = groups[gi]
-            buf = gi & 1
-            if gi >= 2:
-                used[buf].synchronize()                  # the transform of group gi - 2 no longer reads this staging pair
-            pos, nf = int(pos_np[b] - pos_np[a]), int(fr_np[b] - fr_np[a])
-            got = L.hssfsst_pack_recordings(ctypes.c_void_p(ptrs_np[a:b].ctypes.data), ctypes.c_void_p(lens_np[a:b].ctypes.data), b - a,
-                                            stride, frame_len, ctypes.c_void_p(stage_h[buf].data_ptr()), int(stage_h[buf].numel()),
-                                            ctypes.c_void_p(start_h[buf].data_ptr()), int(start_h[buf].numel()), 0)
-            if got != nf:
-                _lib.check(int(got) if got < 0 else _lib.E_INVAL, "hssfsst_pack_recordings")
-            if dev_labels:
-                lab_h, lst = B["lab_h"][buf], B["lab_starts"]
-                got = L.hssfsst_pack_recordings(ctypes.c_void_p(yptrs_np[a:b].ctypes.data), ctypes.c_void_p(lens_np[a:b].ctypes.data), b - a,
-                                                stride, frame_len, ctypes.c_void_p(lab_h.data_ptr()), int(lab_h.numel()),
-                                                ctypes.c_void_p(lst.ctypes.data), int(lst.shape[0]), 0)
-                if got != nf:
-                    _lib.check(int(got) if got < 0 else _lib.E_INVAL, "hssfsst_pack_recordings")
-            with torch.cuda.stream(up):
-                stage_d[buf][:pos].copy_(stage_h[buf][:pos], non_blocking=True)
-                start_d[buf][:nf].copy_(start_h[buf][:nf], non_blocking=True)
-                if dev_labels:
-                    B["lab_d"][buf][:pos].copy_(B["lab_h"][buf][:pos], non_blocking=True)
-                up_done[buf].record(up)
-            return pos, nf
-
-        row = 0
-        sizes = pack(0)
-        for gi in range(len(groups)):
-            buf = gi & 1
-            pos, nf = sizes
-            main.wait_event(up_done[buf])
-            if keep_on_device:
-                dst = feats[row:row + nf]
-            else:
-                if gi >= 2:
-                    main.wait_event(ring_free[buf])
-                dst = ring_d[buf][:nf]
+        def launch(g, x, starts, tracks, dst):
             if rsm is None:
-                fsst.frames(stage_d[buf][:pos], start_d[buf][:nf], frame_len, out=dst)
+                fsst.frames(x, starts, frame_len, out=dst)
             else:
-                rs = B["rs_d"][:nf * out_len].view(nf, out_len)
-                rsm.frames(stage_d[buf][:pos], start_d[buf][:nf], frame_len, out=rs)
+                nf = g.r1 - g.r0
+                rs = rs_d[:nf * out_len].view(nf, out_len)
+                rsm.frames(x, starts, frame_len, out=rs)
                 fsst.batch(rs, out=dst)
-                if dev_labels:
-                    rsm.frames(B["lab_d"][buf][:pos], start_d[buf][:nf], frame_len, labels=True, out=lab_d[row:row + nf])
-            used[buf].record(main)
-            if not keep_on_device:
-                down.wait_stream(main)
-                with torch.cuda.stream(down):
-                    feats[row:row + nf].copy_(dst, non_blocking=True)
-                    ring_free[buf].record(down)
-            if gi + 1 < len(groups):
-                sizes = pack(gi + 1)                     # host packing + upload of the next group overlap this transform
-            if labels is not None and not dev_labels:    # (host work, also overlapped)
-                fill_labels(groups[gi][0], groups[gi][1], row)
-            row += nf
-        if not keep_on_device:
-            down.synchronize()
-        main.synchronize()
-        fsst.check()
+                if tracks is not None:
+                    rsm.frames(tracks, starts, frame_len, labels=True, out=lab_d[g.r0:g.r1])
+
+        self._pipeline(groups, fr_np, ptrs_np, lens_np, feats, keep_on_device, launch, tracks_np=yptrs_np, frame=(stride, frame_len),
+                       after=(lambda g: fill_labels(g.a, g.b, g.r0)) if labels is not None else None)
         if dev_labels:
             labels = lab_d.cpu()
         return FrameItems(feats, labels)

@@ -479,10 +479,7 @@ class FSST:
                 self._ragged_stage = stage
             ptrs = np.asarray([t.data_ptr() for t in held], dtype=np.uint64)
             starts = np.empty(B, dtype=np.int64)
-            got = L.hssfsst_pack_recordings(ctypes.c_void_p(ptrs.ctypes.data), ctypes.c_void_p(lens.ctypes.data), B, 0x7fffffff, 1,
-                                            ctypes.c_void_p(stage.data_ptr()), int(stage.numel()), ctypes.c_void_p(starts.ctypes.data), B, 0)
-            if got != B:
-                _lib.check(int(got) if got < 0 else _lib.E_INVAL, "hssfsst_pack_recordings")
+            _lib.pack_recordings(ptrs, lens, stage, starts, B)
             X = stage
         if out is None:
             out = torch.empty(shape, dtype=dt, device=odev)

@@ -346,3 +346,67 @@ def test_build_resampled_recordings_half_features():
     assert same_bits(items.features, f32.features.to(torch.float16))
     host = build_resampled_recordings(recs, tf16, rs, device=DEV, max_samples=40000)
     assert same_bits(host.features, items.features.cpu())
+
+
+@pytest.mark.gpu
+def test_one_builder_serves_every_build_in_turn():
+    """One CorpusBuilder through framed builds and whole-recording builds in turn, host-returned and device-kept: its staging
+    buffers and its device ring are re-used, re-viewed and regrown between calls, and every call has three or more groups, so
+    that the waits on a staging buffer's and a ring half's previous use are live.  Every arena equals the direct transform calls."""
+    from heart_sounds_segmentation_amd.framing import frame_batch
+    num = 500
+    tf = FSST(1000, W128, truncate_freq=(25, 200), stack=True)
+    rs = Resample(num)
+    lens = [5200, 2500, 1999, 4100, 7300, 3000]
+    recs = corpus(lens, 500)
+    xs = [x for x, _ in recs]
+    kept = [(x, y) for x, y in recs if x.shape[0] >= 2000]          # the framed build skips the 1999-sample recording
+    assert sum(max((T - 2000) // 1000, 1) >= 2 for T in lens if T >= 2000) >= 3     # >= 3 groups at windows_per_launch=2
+
+    frames = [frame_batch(x.to(DEV), 1000, 2000) for x, _ in kept]
+    want_framed = torch.cat([tf.batch(F) for F in frames])
+    want_framed_rs = torch.cat([tf.batch(rs.batch(F)) for F in frames])
+    want_whole = [tf(x).cpu() for x in xs]
+    want_whole_rs = tf.batch(rs.ragged([x.to(DEV) for x in xs]))
+    plain_labels = torch.cat([frame_batch(y - 1, 1000, 2000) for _, y in kept])
+    ties = 0
+
+    def labels_follow_the_rule(got, tracks):
+        """``got[i]`` against the host rule round(Resample(num)(track i)) - 1, off the .5 ties."""
+        nonlocal ties
+        assert got.shape == (len(tracks), num) and got.dtype == torch.int64 and not got.is_cuda
+        for i, y in enumerate(tracks):
+            ref = resample_labels(y, Resample(num)).numpy()
+            ok = off_tie(Resample(num)(y).numpy())
+            ties += int((~ok).sum())
+            assert np.array_equal(got[i].numpy()[ok], ref[ok]), i
+
+    framed_tracks = [fr for _, y in kept for fr in frame_batch(y - 1, 1000, 2000)]
+    whole_tracks = [y for _, y in recs]
+
+    b = CorpusBuilder(tf, device=DEV, windows_per_launch=2, resample=rs)
+    for keep in (False, True):
+        it = b.build(recs, keep_on_device=keep)
+        assert it.features.is_cuda == keep and torch.equal(it.features.to(DEV), want_framed_rs)
+        labels_follow_the_rule(it.labels, framed_tracks)
+        it = b.build_resampled_recordings(recs, keep_on_device=keep, max_samples=6000)
+        assert it.features.is_cuda == keep and torch.equal(it.features.to(DEV), want_whole_rs)
+        labels_follow_the_rule(it.labels, whole_tracks)
+
+    b = CorpusBuilder(tf, device=DEV, windows_per_launch=2)
+    it = b.build(recs)
+    assert not it.features.is_cuda and torch.equal(it.features, want_framed.cpu()) and torch.equal(it.labels, plain_labels)
+    def whole_recordings(keep):
+        whole = b.build_recordings(recs, keep_on_device=keep, max_samples=6000)
+        assert len(whole) == len(recs)
+        for i, (f, y) in enumerate(whole):
+            assert f.is_cuda == keep and torch.equal(f.cpu(), want_whole[i]), (keep, i)
+            assert y is recs[i][1]
+
+    whole_recordings(False)
+    it = b.build(recs + recs)                            # the list twice: larger groups, a larger arena (regrow)
+    assert torch.equal(it.features, torch.cat([want_framed, want_framed]).cpu())
+    assert torch.equal(it.labels, torch.cat([plain_labels, plain_labels]))
+    whole_recordings(True)
+    tf.check()
+    print(f"one builder, every build: {ties} label samples within 1e-9 of a .5 tie")
