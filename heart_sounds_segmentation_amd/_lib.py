@@ -255,6 +255,8 @@ def lib():
         L.hssfsst_segmenter_info.restype = c_int
         L.hssfsst_segmenter_exec.argtypes = [vp, vp, c_int, c_i64, c_i64, vp, vp, vp, vp]
         L.hssfsst_segmenter_exec.restype = c_int
+        L.hssfsst_segmenter_exec_ragged.argtypes = [vp, vp, c_int, ctypes.POINTER(c_i64), c_i64, vp, vp, c_int, vp, vp]
+        L.hssfsst_segmenter_exec_ragged.restype = c_int
         L.hssfsst_device_count.restype = c_int
         L.hssfsst_version.restype = c_int
         L.hssfsst_last_error.restype = ctypes.c_char_p

@@ -11,7 +11,9 @@ was produced by the reference class itself (tests/golden/make_golden.py).
 
 ``SegmenterHead.hip()`` gives the same forward pass as HIP kernels behind the C ABI (include/hssfsst.h:
 hssfsst_segmenter_exec; csrc/segmenter_lstm.hpp), inference only: ``segment(fsst, head.hip(), windows)`` is
-config 4 with nothing leaving the device and no torch op between the FSST kernel and the log-probs.
+config 4 with nothing leaving the device and no torch op between the FSST kernel and the log-probs.  Whole recordings of
+different lengths go through ``segment_recordings(fsst, head.hip(), recordings)`` (``HipSegmenter.ragged``,
+hssfsst_segmenter_exec_ragged) in one call.
 """
 from __future__ import annotations
 
@@ -19,10 +21,12 @@ from typing import Optional
 
 import ctypes
 
+import numpy as np
 import torch
 from torch import nn
 
 from . import _lib
+from .transforms.synchrosqueeze import RaggedFeatures
 
 
 class SegmenterHead(nn.Module):
@@ -152,8 +156,91 @@ class HipSegmenter:
                                                      c0.data_ptr(), out.data_ptr(), stream), "hssfsst_segmenter_exec")
         return out
 
+    def ragged(self, feats, h0: Optional[torch.Tensor] = None, c0: Optional[torch.Tensor] = None,
+               max_steps: int = 1 << 23) -> RaggedFeatures:
+        """Whole recordings of DIFFERENT lengths in one call (``hssfsst_segmenter_exec_ragged``).  ``feats``: the non-raw
+        ``RaggedFeatures`` of ``FSST.ragged`` (float32 / float16 / bfloat16, on the plan's GPU), or a list / tuple of ``(T_i, F)``
+        tensors, which is packed into one arena on the device.  Returns a ``RaggedFeatures`` over a ``(sum T, 4)`` float32 arena
+        with the same offsets; item i equals ``self(feats[i][None], h0[:, i:i+1], c0[:, i:i+1])[0]`` bit for bit: forward from
+        the recording's first step, reverse from its own last one, layer 2 seeded at its own ends -- which padding to
+        ``(B, T_max, F)`` cannot give.
+
+        ``h0`` / ``c0``: ``(2, B, H)``, or ``(2, 1, H)`` to start every recording from the same state; omitted, the module's own
+        are used when their batch is B or 1, else ValueError.
+
+        ``max_steps`` bounds the scratch: the list is processed in consecutive groups whose total steps stay within it (a longer
+        recording is a group of its own), all writing into the one output arena; the result does not depend on it.  The layer
+        outputs take 2 x steps x 2H x 4 bytes: 2 x 8.4 M x 480 x 4 B = 32 GB at the default with hidden 240 (plus at most
+        128 MiB of projected inputs and 16 KiB of state per 16 recordings); lower it on a device that is shared."""
+        if isinstance(feats, RaggedFeatures):
+            if feats._raw:
+                raise ValueError("HipSegmenter.ragged: raw (complex, frequency-major) features; the segmenter takes abs or stack features")
+            data, offs = feats.data, list(feats._off)
+        elif isinstance(feats, (list, tuple)):
+            for i, f in enumerate(feats):
+                if not isinstance(f, torch.Tensor) or f.dim() != 2 or f.shape[0] < 1:
+                    raise ValueError(f"HipSegmenter.ragged: item {i} is not a (T, {self.input_size}) tensor with T >= 1")
+            if len({(f.device, f.dtype, int(f.shape[1])) for f in feats}) > 1:
+                raise ValueError("HipSegmenter.ragged: the items differ in device, dtype or width")
+            offs = [0]
+            for f in feats:
+                offs.append(offs[-1] + int(f.shape[0]))
+            data = torch.cat([f.detach() for f in feats]) if feats else torch.empty((0, self.input_size), device=self.device)
+        else:
+            raise ValueError("HipSegmenter.ragged: a RaggedFeatures or a list of (T, F) tensors expected")
+        B = len(offs) - 1
+        if data.dim() != 2 or data.shape[1] != self.input_size or data.shape[0] != offs[-1]:
+            raise ValueError(f"HipSegmenter.ragged: features of shape (sum T, {self.input_size}) expected, got {tuple(data.shape)}")
+        if data.device != self.device:
+            raise ValueError(f"HipSegmenter.ragged: features on {data.device}, the plan on {self.device}")
+        if data.dtype not in _DTYPES:
+            raise ValueError(f"HipSegmenter.ragged: float32, float16 or bfloat16 features expected, got {data.dtype}")
+        if (h0 is None) != (c0 is None):
+            raise ValueError("HipSegmenter.ragged: pass both h0 and c0, or neither")
+        if h0 is None:
+            if self.h0.shape[1] not in (B, 1) and B:
+                raise ValueError(f"HipSegmenter.ragged: {B} recordings, but the module's h0 / c0 were made for batch {self.h0.shape[1]} "
+                                 "(pass h0 and c0 of shape (2, B, H) or (2, 1, H) to the call)")
+            h0, c0 = self.h0, self.c0
+        else:
+            ok = ((2, B, self.hidden_size), (2, 1, self.hidden_size))
+            if tuple(h0.shape) not in ok or tuple(c0.shape) != tuple(h0.shape):
+                raise ValueError(f"HipSegmenter.ragged: h0 and c0 of shape {ok[0]} or {ok[1]} expected, got {tuple(h0.shape)} and {tuple(c0.shape)}")
+            h0 = h0.detach().to(self.device, torch.float32).contiguous()
+            c0 = c0.detach().to(self.device, torch.float32).contiguous()
+        if max_steps < 1:
+            raise ValueError(f"HipSegmenter.ragged: max_steps {max_steps} must be positive")
+        out = torch.empty((offs[-1], 4), dtype=torch.float32, device=self.device)
+        result = RaggedFeatures(out, torch.tensor(offs, dtype=torch.int64), 4, False)
+        if B == 0:
+            return result
+        data = data.detach().contiguous()
+        rows = 1 if h0.shape[1] == 1 else B
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        L = _lib.lib()
+        i = 0
+        while i < B:                                    # consecutive groups of at most max_steps steps
+            j = i + 1
+            while j < B and offs[j + 1] - offs[i] <= max_steps:
+                j += 1
+            sub = np.asarray(offs[i:j + 1], dtype=np.int64) - offs[i]
+            hs, cs = (h0, c0) if rows == 1 else (h0[:, i:j].contiguous(), c0[:, i:j].contiguous())
+            _lib.check(L.hssfsst_segmenter_exec_ragged(self._plan, data[offs[i]:].data_ptr(), _DTYPES[data.dtype],
+                                                       sub.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), j - i, hs.data_ptr(),
+                                                       cs.data_ptr(), 1 if rows == 1 else j - i, out[offs[i]:].data_ptr(), stream),
+                       "hssfsst_segmenter_exec_ragged")
+            i = j
+        return result
+
 
 def segment(fsst, head, windows: torch.Tensor) -> torch.Tensor:
     """windows (B, n) -> HIP FSST features (B, n, 2K), kept on the device -> (B, n, 4) log-probs.  ``head``: a
     ``SegmenterHead`` (stock ``nn.LSTM``) or what its ``hip()`` returns (the HIP kernels)."""
     return head(fsst.batch(windows))
+
+
+def segment_recordings(fsst, seg: HipSegmenter, recordings, **kw) -> RaggedFeatures:
+    """Whole recordings of different lengths (a list of 1-D signals on the GPU) -> ``FSST.ragged`` features, kept on the device
+    -> a ``RaggedFeatures`` of ``(T_i, 4)`` log-probs: ``segment()`` for whole recordings.  ``kw`` goes to
+    ``HipSegmenter.ragged`` (h0, c0, max_steps)."""
+    return seg.ragged(fsst.ragged(recordings), **kw)

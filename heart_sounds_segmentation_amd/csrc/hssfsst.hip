@@ -36,6 +36,7 @@
 #include "fourier_resample_gpu.hpp"
 #include "fourier_resample_ragged.hpp"
 #include "segmenter_lstm.hpp"
+#include "segmenter_layout.hpp"
 #include "fsst_tables.hpp"
 
 namespace tables = hssfsst::tables;
@@ -75,6 +76,7 @@ struct DebugSwitches {
     bool force_generic = false;   // every radix length on the generic VALU kernel
     bool no_stream_fuse = false;  // a streaming step as copy + transform + merge-and-normalise launches
     bool no_pair = false;         // nwin 256 / 512: one wave per wave region (no wave pairs)
+    int seg_ragged_pre_mib = 0;   // ragged segmenter: bound of the projection scratch in MiB (a number; 0 or unset: the dense call's 128)
 };
 const DebugSwitches& debug_switches()
 {
@@ -94,6 +96,8 @@ const DebugSwitches& debug_switches()
         d.force_generic = fg != nullptr && fg[0] == '1';
         d.no_stream_fuse = on("HSSFSST_NO_STREAM_FUSE");
         d.no_pair = on("HSSFSST_NO_PAIR");
+        const char* pm = std::getenv("HSSFSST_SEG_RAGGED_PRE_MIB");
+        d.seg_ragged_pre_mib = pm != nullptr ? std::min(std::max(std::atoi(pm), 0), 1 << 16) : 0;
         return d;
     }();
     return sw;
@@ -2425,6 +2429,14 @@ struct hssfsst_segmenter {
     DevBuf<float> d_pre;                                 // [dir][batch tile][Tc][gate tile][lane][4]: one chunk's input projection
     DevBuf<float> d_y1, d_y2;                            // (B, T, 2H): the layers' outputs
     DevBuf<float> d_state;                               // [h, c][dir][Bp][Hp]: carried from chunk to chunk and from layer 1 to layer 2
+    // hssfsst_segmenter_exec_ragged: the list's layout (segmenter_layout.hpp) and its device tables -- slot_off long long[slots],
+    // slot_len int[slots], slot_rec int[slots], tile_walk int[tiles] -- made on the host (h_tab, pinned), uploaded in one copy and
+    // kept while the next call has the same offsets (tab_key)
+    hssfsst::seglayout::Layout lay;
+    std::vector<int64_t> tab_key;
+    DevBuf<unsigned char> d_tab;
+    PinnedBuf<unsigned char> h_tab{false};
+    hipEvent_t tab_ev = nullptr;                         // the last upload of h_tab (h_tab is not rewritten before it is done)
 };
 
 namespace {
@@ -2491,6 +2503,30 @@ int seg_launch_check(const char* what)
     return 0;
 }
 
+constexpr int64_t kSegMaxSteps = 0x7fffffffLL / 8;       // steps of one dense exec, and of one recording of a ragged one
+constexpr int64_t kSegMaxBatch = 16 * 32768;
+static_assert(hssfsst::seglayout::kSlotRows == hssfsst::kSegRows, "a tile of the layout is the recurrence workgroup's rows");
+
+// One launch pair of a ragged exec: the first `tiles` tiles walk steps s0 .. s0 + n (n: the longest of them, at most Tc, the pitch of pre)
+struct SegRaggedChunk { int s0, n, tiles, Tc; };
+
+// The launches of one layer: tiles finish in order (the layout sorts them), so fewer and fewer take part and the steps per launch
+// that fit the projection scratch grow.
+std::vector<SegRaggedChunk> seg_ragged_chunks(const hssfsst::seglayout::Layout& lay, size_t tile_step_bytes, size_t pre_bytes)
+{
+    std::vector<SegRaggedChunk> out;
+    int live = lay.tiles();
+    for (int s0 = 0; s0 < lay.tile_walk[0];) {
+        while (lay.tile_walk[live - 1] <= s0) --live;
+        const size_t fit = std::max<size_t>(1, pre_bytes / (tile_step_bytes * live));
+        const int Tc = static_cast<int>(std::min<size_t>(fit, kSegMaxChunk));
+        const int n = std::min(Tc, lay.tile_walk[0] - s0);
+        out.push_back({s0, n, live, Tc});
+        s0 += n;
+    }
+    return out;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2530,6 +2566,7 @@ int hssfsst_segmenter_destroy(hssfsst_segmenter* p)
 {
     if (!p) return 0;
     DeviceGuard device_guard_(p->device);
+    if (p->tab_ev) (void)hipEventDestroy(p->tab_ev);
     delete p;                                            // (the buffers free themselves)
     return 0;
 }
@@ -2552,7 +2589,7 @@ int hssfsst_segmenter_exec(hssfsst_segmenter* p, const void* feats, int feats_dt
                     static_cast<long long>(steps));
     if (feats_dtype != HSSFSST_DTYPE_F32 && feats_dtype != HSSFSST_DTYPE_F16 && feats_dtype != HSSFSST_DTYPE_BF16)
         return fail(HSSFSST_EINVAL, "segmenter_exec: unknown feature dtype %d", feats_dtype);
-    if (batch > 16 * 32768 || steps > 0x7fffffffLL / 8)
+    if (batch > kSegMaxBatch || steps > kSegMaxSteps)
         return fail(HSSFSST_EINVAL, "segmenter_exec: batch %lld or steps %lld too large", static_cast<long long>(batch), static_cast<long long>(steps));
     DEVICE_SCOPE(p->device);
     const hipStream_t st = static_cast<hipStream_t>(stream);
@@ -2568,8 +2605,8 @@ int hssfsst_segmenter_exec(hssfsst_segmenter* p, const void* feats, int feats_dt
     if ((rc = p->d_y2.grow(ylen)) != 0) return rc;
     const size_t nstate = static_cast<size_t>(4) * Bp * hssfsst::kSegHp;
     if ((rc = p->d_state.grow(nstate)) != 0) return rc;
-    hipLaunchKernelGGL(hssfsst::seg_state_init_kernel, dim3(static_cast<unsigned>((nstate + 255) / 256)), dim3(256), 0, st, h0, c0,
-                       p->d_state.get(), B, H, Bp);
+    hipLaunchKernelGGL(hssfsst::seg_state_init_kernel<false>, dim3(static_cast<unsigned>((nstate + 255) / 256)), dim3(256), 0, st, h0, c0,
+                       p->d_state.get(), B, H, Bp, static_cast<const int*>(nullptr));
     if ((rc = seg_launch_check("seg_state_init_kernel")) != 0) return rc;
     for (int l = 0; l < 2; ++l) {
         const hssfsst_segmenter::Layer& L = p->layer[l];
@@ -2589,15 +2626,132 @@ int hssfsst_segmenter_exec(hssfsst_segmenter* p, const void* feats, int feats_dt
             pa.n = ra.n = n;
             pa.t0[0] = ra.t0[0] = t0;
             pa.t0[1] = ra.t0[1] = T - t0 - n;
-            hipLaunchKernelGGL(hssfsst::seg_proj_kernel, dim3(4 * hssfsst::kSegHp / 64, static_cast<unsigned>(nbt * ((n + 7) / 8)), 2), dim3(256), 0, st, pa);
+            hipLaunchKernelGGL(hssfsst::seg_proj_kernel<false>, dim3(4 * hssfsst::kSegHp / 64, static_cast<unsigned>(nbt * ((n + 7) / 8)), 2), dim3(256), 0, st, pa);
             if ((rc = seg_launch_check("seg_proj_kernel")) != 0) return rc;
-            hipLaunchKernelGGL(hssfsst::seg_rec_kernel, dim3(static_cast<unsigned>(nbt), 2), dim3(64 * hssfsst::kSegWaves), 0, st, ra);
+            hipLaunchKernelGGL(hssfsst::seg_rec_kernel<false>, dim3(static_cast<unsigned>(nbt), 2), dim3(64 * hssfsst::kSegWaves), 0, st, ra);
             if ((rc = seg_launch_check("seg_rec_kernel")) != 0) return rc;
         }
     }
     const long long rows = static_cast<long long>(B) * T;
     hipLaunchKernelGGL(hssfsst::seg_head_kernel, dim3(static_cast<unsigned>((rows + 3) / 4)), dim3(256), 0, st, p->d_y2.get(), p->d_lin.get(),
                        p->d_lin.get() + static_cast<size_t>(8) * H, logp, rows, 2 * H);
+    return seg_launch_check("seg_head_kernel");
+}
+
+int hssfsst_segmenter_exec_ragged(hssfsst_segmenter* p, const void* feats, int feats_dtype, const int64_t* offsets, int64_t count,
+                                  const float* h0, const float* c0, int state_rows, float* logp, void* stream)
+{
+    namespace seglayout = hssfsst::seglayout;
+    // the list first: what is wrong with it is said before the plan is looked at
+    if (count < 0) return fail(HSSFSST_EINVAL, "segmenter_exec_ragged: count %lld is negative", static_cast<long long>(count));
+    if (count == 0) return 0;
+    if (!offsets) return fail(HSSFSST_EINVAL, "segmenter_exec_ragged: offsets is NULL");
+    if (count > kSegMaxBatch) return fail(HSSFSST_EINVAL, "segmenter_exec_ragged: count %lld too large", static_cast<long long>(count));
+    if (offsets[0] != 0)
+        return fail(HSSFSST_EINVAL, "segmenter_exec_ragged: offsets[0] is %lld, not 0", static_cast<long long>(offsets[0]));
+    if (const int64_t i = seglayout::first_bad_length(offsets, count, kSegMaxSteps); i >= 0) {
+        if (offsets[i + 1] <= offsets[i])
+            return fail(HSSFSST_EINVAL, "segmenter_exec_ragged: offsets do not increase at index %lld (offsets[%lld] = %lld, offsets[%lld] = %lld)",
+                        static_cast<long long>(i + 1), static_cast<long long>(i), static_cast<long long>(offsets[i]),
+                        static_cast<long long>(i + 1), static_cast<long long>(offsets[i + 1]));
+        return fail(HSSFSST_EINVAL, "segmenter_exec_ragged: recording %lld has %lld steps, over the limit of %lld", static_cast<long long>(i),
+                    static_cast<long long>(offsets[i + 1] - offsets[i]), static_cast<long long>(kSegMaxSteps));
+    }
+    if (offsets[count] > 0x7fffffffLL)
+        return fail(HSSFSST_EINVAL, "segmenter_exec_ragged: %lld steps in all, over the limit of 2^31 - 1", static_cast<long long>(offsets[count]));
+    if (state_rows != 1 && state_rows != count)
+        return fail(HSSFSST_EINVAL, "segmenter_exec_ragged: state_rows %d is neither 1 nor count %lld", state_rows, static_cast<long long>(count));
+    if (feats_dtype != HSSFSST_DTYPE_F32 && feats_dtype != HSSFSST_DTYPE_F16 && feats_dtype != HSSFSST_DTYPE_BF16)
+        return fail(HSSFSST_EINVAL, "segmenter_exec_ragged: unknown feature dtype %d", feats_dtype);
+    if (!p || !feats || !h0 || !c0 || !logp)
+        return fail(HSSFSST_EINVAL, "segmenter_exec_ragged: bad argument (%s is NULL)",
+                    !p ? "plan" : !feats ? "feats" : !h0 ? "h0" : !c0 ? "c0" : "logp");
+    DEVICE_SCOPE(p->device);
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const int H = p->H;
+    int rc;
+
+    // the tables (kept while the offsets stay the same)
+    const bool same = p->d_tab.get() != nullptr && p->tab_key.size() == static_cast<size_t>(count + 1) &&
+                      std::equal(p->tab_key.begin(), p->tab_key.end(), offsets);
+    try {
+        if (!same) {
+            p->tab_key.clear();
+            seglayout::build(offsets, count, p->lay);
+        }
+    } catch (const std::bad_alloc&) {
+        return fail(HSSFSST_ENOMEM, "segmenter_exec_ragged: out of host memory");
+    }
+    const seglayout::Layout& lay = p->lay;
+    const size_t slots = static_cast<size_t>(lay.slots()), tiles = static_cast<size_t>(lay.tiles());
+    const size_t o_len = slots * sizeof(long long), o_rec = o_len + slots * sizeof(int), o_walk = o_rec + slots * sizeof(int);
+    const size_t tab_bytes = o_walk + tiles * sizeof(int);
+    if (!same) {
+        if (p->tab_ev) HIP_TRY(hipEventSynchronize(p->tab_ev));          // (the previous upload may still read h_tab)
+        if ((rc = p->h_tab.grow(tab_bytes, 1)) != 0) return rc;
+        std::memcpy(p->h_tab.h, lay.slot_off.data(), o_len);
+        std::memcpy(p->h_tab.h + o_len, lay.slot_len.data(), slots * sizeof(int));
+        std::memcpy(p->h_tab.h + o_rec, lay.slot_rec.data(), slots * sizeof(int));
+        std::memcpy(p->h_tab.h + o_walk, lay.tile_walk.data(), tiles * sizeof(int));
+        if ((rc = p->d_tab.grow(tab_bytes)) != 0) return rc;
+        if (!p->tab_ev) HIP_TRY(hipEventCreateWithFlags(&p->tab_ev, hipEventDisableTiming));
+        HIP_TRY(hipMemcpyAsync(p->d_tab.get(), p->h_tab.h, tab_bytes, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipEventRecord(p->tab_ev, st));
+        try {
+            p->tab_key.assign(offsets, offsets + count + 1);
+        } catch (const std::bad_alloc&) {
+            return fail(HSSFSST_ENOMEM, "segmenter_exec_ragged: out of host memory");
+        }
+    }
+    const auto* d_off = reinterpret_cast<const long long*>(p->d_tab.get());
+    const int* d_len = reinterpret_cast<const int*>(p->d_tab.get() + o_len);
+    const int* d_rec = reinterpret_cast<const int*>(p->d_tab.get() + o_rec);
+    const int* d_walk = reinterpret_cast<const int*>(p->d_tab.get() + o_walk);
+
+    const size_t tile_step_bytes = static_cast<size_t>(2) * hssfsst::kSegGateTiles * hssfsst::kSegTileFloats * sizeof(float);
+    std::vector<SegRaggedChunk> chunks;
+    try {
+        const int mib = debug_switches().seg_ragged_pre_mib;          // (A-B switch of tools/segmenter_ragged_bench.py: same bits)
+        chunks = seg_ragged_chunks(lay, tile_step_bytes, mib > 0 ? static_cast<size_t>(mib) << 20 : kSegPreBytes);
+    } catch (const std::bad_alloc&) {
+        return fail(HSSFSST_ENOMEM, "segmenter_exec_ragged: out of host memory");
+    }
+    size_t pre_floats = 0;
+    for (const SegRaggedChunk& c : chunks) pre_floats = std::max(pre_floats, tile_step_bytes / sizeof(float) * c.tiles * c.Tc);
+    if ((rc = p->d_pre.grow(pre_floats)) != 0) return rc;
+    const size_t ylen = static_cast<size_t>(lay.total) * 2 * H;
+    if ((rc = p->d_y1.grow(ylen)) != 0) return rc;
+    if ((rc = p->d_y2.grow(ylen)) != 0) return rc;
+    const size_t nstate = static_cast<size_t>(4) * slots * hssfsst::kSegHp;
+    if ((rc = p->d_state.grow(nstate)) != 0) return rc;
+    hipLaunchKernelGGL(hssfsst::seg_state_init_kernel<true>, dim3(static_cast<unsigned>((nstate + 255) / 256)), dim3(256), 0, st, h0, c0,
+                       p->d_state.get(), state_rows, H, static_cast<int>(slots), d_rec);
+    if ((rc = seg_launch_check("seg_state_init_kernel<ragged>")) != 0) return rc;
+    for (int l = 0; l < 2; ++l) {
+        const hssfsst_segmenter::Layer& L = p->layer[l];
+        hssfsst::SegProjArgs pa{};
+        pa.x = l ? static_cast<const void*>(p->d_y1.get()) : feats;
+        pa.x_dtype = l ? HSSFSST_DTYPE_F32 : feats_dtype;
+        pa.relu = l;
+        pa.F = L.F; pa.Fp = L.Fp;
+        pa.wt = L.d_wt.get(); pa.bias = L.d_bias.get(); pa.pre = p->d_pre.get();
+        pa.slot_off = d_off; pa.slot_len = d_len; pa.tile_walk = d_walk;
+        hssfsst::SegRecArgs ra{};
+        ra.pre = p->d_pre.get(); ra.whh = L.d_whh.get(); ra.state = p->d_state.get();
+        ra.y = l ? p->d_y2.get() : p->d_y1.get();
+        ra.H = H; ra.Bp = static_cast<int>(slots); ra.inv_scale = L.inv_scale;
+        ra.slot_off = d_off; ra.slot_len = d_len; ra.tile_walk = d_walk;
+        for (const SegRaggedChunk& c : chunks) {
+            pa.n = c.n; pa.Tc = ra.Tc = c.Tc; pa.s0 = ra.s0 = c.s0;
+            hipLaunchKernelGGL(hssfsst::seg_proj_kernel<true>, dim3(4 * hssfsst::kSegHp / 64, static_cast<unsigned>(c.tiles * ((c.n + 7) / 8)), 2),
+                               dim3(256), 0, st, pa);
+            if ((rc = seg_launch_check("seg_proj_kernel<ragged>")) != 0) return rc;
+            hipLaunchKernelGGL(hssfsst::seg_rec_kernel<true>, dim3(static_cast<unsigned>(c.tiles), 2), dim3(64 * hssfsst::kSegWaves), 0, st, ra);
+            if ((rc = seg_launch_check("seg_rec_kernel<ragged>")) != 0) return rc;
+        }
+    }
+    hipLaunchKernelGGL(hssfsst::seg_head_kernel, dim3(static_cast<unsigned>((lay.total + 3) / 4)), dim3(256), 0, st, p->d_y2.get(), p->d_lin.get(),
+                       p->d_lin.get() + static_cast<size_t>(8) * H, logp, lay.total, 2 * H);
     return seg_launch_check("seg_head_kernel");
 }
 

@@ -14,6 +14,13 @@
 //
 // Every hidden size runs on the one padded geometry kSegHp = 256 units (16 unit tiles x 4 gates, K = 256): padded units have zero
 // weights and zero state, so they stay exactly zero (i = f = o = 1/2, g = 0, c' = c / 2 = 0).
+//
+// RAGGED instantiations (hssfsst_segmenter_exec_ragged): the 16 rows of a tile are SLOTS, each holding a whole recording of its own
+// length from an arena (segmenter_layout.hpp: longest first, so the tiles still walking are a prefix).  Everything is indexed by the
+// step s a slot has walked, not by time: slot b is live while s < T_b and stands at t = s (forward) or t = T_b - 1 - s (reverse), so
+// both directions start together and a launch covers steps s0 .. s0 + n of its tiles.  A slot past its end freezes: selects keep c
+// and h (hence the h image), nothing is stored to y, and the state written back is the recording's own final state.  A live row's
+// arithmetic is the dense kernel's, instruction for instruction: a recording's bits are those of the dense call on it alone.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -47,10 +54,17 @@ struct SegProjArgs {
     float* pre;             // [dir][batch tile][Tc][gate tile][lane][4]
     int Tc, n;              // chunk pitch of pre and the steps of this launch
     int t0[2];              // first time step of the launch's chunk, per direction
+    // RAGGED: x is the arena (sum T, F); pre is indexed by step; n is the longest walk of the launch (tile 0's), Tc the pitch
+    const long long* slot_off;   // [slots] first arena row of the slot's recording
+    const int* slot_len;         // [slots] its steps (0: padding slot)
+    const int* tile_walk;        // [tiles] the tile's longest recording
+    int s0;                      // first step of the launch
 };
 
 // Block = 4 waves: 8 time steps x 16 batch rows (M = 128) by 64 gate columns; wave w: steps 2w, 2w + 1, all four column tiles.
-// Grid (16 column blocks, batch tiles x ceil(n / 8), 2 directions).
+// Grid (16 column blocks, batch tiles x ceil(n / 8), 2 directions).  RAGGED: row (step, slot) gathers x[offset + t(step, dir)], zero
+// past the slot's end; blocks past their tile's walk exit at once.
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void seg_proj_kernel(SegProjArgs a)
 {
     constexpr int KB = 32, AS = KB + 1, BS = 80;
@@ -61,6 +75,12 @@ __global__ __launch_bounds__(256) void seg_proj_kernel(SegProjArgs a)
     const int tblocks = (a.n + 7) / 8;
     const int bt = blockIdx.y / tblocks, tb = blockIdx.y - bt * tblocks;
     const int n0 = blockIdx.x * 64;
+    const int nbt = RAGGED ? static_cast<int>(gridDim.y) / tblocks : (a.B + kSegRows - 1) / kSegRows;
+    int nt = a.n;                                                       // steps of this tile in the launch
+    if constexpr (RAGGED) {
+        nt = min(a.n, a.tile_walk[bt] - a.s0);
+        if (tb * 8 >= nt) return;
+    }
     const float* wt = a.wt + static_cast<size_t>(dir) * a.Fp * (4 * kSegHp);
     seg_f4 acc[2][4];
 #pragma unroll
@@ -74,7 +94,14 @@ __global__ __launch_bounds__(256) void seg_proj_kernel(SegProjArgs a)
             const int m = (tid >> 5) + 8 * i, k = k0 + (tid & 31);
             const int tl = tb * 8 + (m >> 4), b = bt * kSegRows + (m & 15);
             float v = 0.0f;
-            if (tl < a.n && b < a.B && k < a.F) {
+            if constexpr (RAGGED) {
+                const int len = a.slot_len[b], s = a.s0 + tl;           // (b is the slot)
+                if (s < len && k < a.F) {
+                    const long long row = a.slot_off[b] + (dir ? len - 1 - s : s);
+                    v = seg_load_x(a.x, static_cast<size_t>(row) * a.F + k, a.x_dtype);
+                    if (a.relu) v = fmaxf(v, 0.0f);
+                }
+            } else if (tl < a.n && b < a.B && k < a.F) {
                 v = seg_load_x(a.x, (static_cast<size_t>(b) * a.T + (a.t0[dir] + tl)) * a.F + k, a.x_dtype);
                 if (a.relu) v = fmaxf(v, 0.0f);
             }
@@ -104,8 +131,7 @@ __global__ __launch_bounds__(256) void seg_proj_kernel(SegProjArgs a)
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const int tl = tb * 8 + 2 * w + j;
-        if (tl >= a.n) continue;
-        const int nbt = (a.B + kSegRows - 1) / kSegRows;
+        if (tl >= nt) continue;
         float* dst = a.pre + ((static_cast<size_t>(dir) * nbt + bt) * a.Tc + tl) * (kSegGateTiles * kSegTileFloats);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -118,8 +144,11 @@ __global__ __launch_bounds__(256) void seg_proj_kernel(SegProjArgs a)
     }
 }
 
-// state[0 = h, 1 = c][dir][padded batch][Hp] <- h0, c0 (2, B, H); the padding is zero
-__global__ __launch_bounds__(256) void seg_state_init_kernel(const float* h0, const float* c0, float* state, int B, int H, int Bp)
+// state[0 = h, 1 = c][dir][padded batch][Hp] <- h0, c0 (2, B, H); the padding is zero.  RAGGED: row b is a slot and takes the state
+// of its recording slot_rec[b] (none: a padding slot, zero); B is the rows of h0 / c0, 1 = the same state for every recording.
+template <bool RAGGED>
+__global__ __launch_bounds__(256) void seg_state_init_kernel(const float* h0, const float* c0, float* state, int B, int H, int Bp,
+                                                             const int* slot_rec)
 {
     const size_t per = static_cast<size_t>(2) * Bp * kSegHp;
     const size_t i = static_cast<size_t>(blockIdx.x) * 256 + threadIdx.x;
@@ -130,7 +159,12 @@ __global__ __launch_bounds__(256) void seg_state_init_kernel(const float* h0, co
     const int b = static_cast<int>((r / kSegHp) % Bp);
     const int dir = static_cast<int>(r / (static_cast<size_t>(kSegHp) * Bp));
     float v = 0.0f;
-    if (b < B && u < H) v = (which ? c0 : h0)[(static_cast<size_t>(dir) * B + b) * H + u];
+    if constexpr (RAGGED) {
+        const int rec = slot_rec[b];
+        if (rec >= 0 && u < H) v = (which ? c0 : h0)[(static_cast<size_t>(dir) * B + (B == 1 ? 0 : rec)) * H + u];
+    } else {
+        if (b < B && u < H) v = (which ? c0 : h0)[(static_cast<size_t>(dir) * B + b) * H + u];
+    }
     state[i] = v;
 }
 
@@ -142,6 +176,11 @@ struct SegRecArgs {
     int B, T, H, Bp, Tc, n;
     int t0[2];
     float inv_scale;        // 1 / (wscale x kSegHScale)
+    // RAGGED: y is (sum T, 2 H) in arena order; Bp the slots; the launch's tiles walk steps s0 .. s0 + min(Tc, walk - s0)
+    const long long* slot_off;
+    const int* slot_len;
+    const int* tile_walk;
+    int s0;
 };
 
 __device__ __forceinline__ float seg_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
@@ -161,7 +200,9 @@ __device__ __forceinline__ void seg_put_h(_Float16* hi, _Float16* lo, int unit, 
     }
 }
 
-// Grid (batch tiles, 2 directions), block 512.  Direction 0 walks the chunk's steps upwards, direction 1 downwards.
+// Grid (batch tiles, 2 directions), block 512.  Direction 0 walks the chunk's steps upwards, direction 1 downwards.  RAGGED: both
+// walk step indices upwards; the trip count is the tile's (uniform in the workgroup), the rows' ends are selects.
+template <bool RAGGED>
 __global__ __launch_bounds__(512) void seg_rec_kernel(SegRecArgs a)
 {
     constexpr int HB = kSegKb * 4 * kSegRows * 8;                       // halves of one plane of the h image
@@ -173,6 +214,16 @@ __global__ __launch_bounds__(512) void seg_rec_kernel(SegRecArgs a)
     const size_t plane = static_cast<size_t>(2) * a.Bp * kSegHp;
     float* hst = a.state + (static_cast<size_t>(dir) * a.Bp + b0) * kSegHp;
     float* cst = hst + plane;
+    const int n = RAGGED ? min(a.Tc, a.tile_walk[bt] - a.s0) : a.n;
+    int rem[4], yrow[4];                                                // RAGGED: row r is live while s < rem[r]; its y row at s = 0
+    if constexpr (RAGGED) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int len = a.slot_len[b0 + row0 + r], off = static_cast<int>(a.slot_off[b0 + row0 + r]);
+            rem[r] = len - a.s0;
+            yrow[r] = dir ? off + rem[r] - 1 : off + a.s0;
+        }
+    }
 
     seg_f4 c[2], h[2];
 #pragma unroll
@@ -191,7 +242,7 @@ __global__ __launch_bounds__(512) void seg_rec_kernel(SegRecArgs a)
     const seg_h8* wq = wq0;
     const float* prew = a.pre + (static_cast<size_t>(dir) * nbt + bt) * a.Tc * (kSegGateTiles * kSegTileFloats)
                         + (w * 8) * kSegTileFloats + lane * 4;
-    auto pre_at = [&](int s) { return prew + static_cast<size_t>(dir ? a.n - 1 - s : s) * (kSegGateTiles * kSegTileFloats); };
+    auto pre_at = [&](int s) { return prew + static_cast<size_t>(!RAGGED && dir ? n - 1 - s : s) * (kSegGateTiles * kSegTileFloats); };
 
     seg_h8 wres[8][2];                                                  // K block 0 of every tile: resident for the whole launch
     seg_h8 wb[2][4][2];                                                 // the rest streams: double buffer of half a K block
@@ -213,7 +264,7 @@ __global__ __launch_bounds__(512) void seg_rec_kernel(SegRecArgs a)
     asm volatile("" ::: "memory");
 
     int cur = 0;
-    for (int s = 0; s < a.n; ++s) {
+    for (int s = 0; s < n; ++s) {
         // (the stream's addresses do not change from step to step: hidden from the compiler, which would otherwise hoist the
         // loads out of the time loop and spill what it cannot hold)
         int zero = 0;
@@ -253,7 +304,7 @@ __global__ __launch_bounds__(512) void seg_rec_kernel(SegRecArgs a)
             }
             __builtin_amdgcn_sched_barrier(0);
         }
-        const int t = a.t0[dir] + (dir ? a.n - 1 - s : s);
+        const int t = RAGGED ? 0 : a.t0[dir] + (dir ? n - 1 - s : s);
 #pragma unroll
         for (int tl = 0; tl < 2; ++tl) {
             const int unit = (w * 2 + tl) * 16 + (lane & 15);
@@ -263,14 +314,24 @@ __global__ __launch_bounds__(512) void seg_rec_kernel(SegRecArgs a)
                 const float gf = seg_sigmoid(fmaf(acc[tl * 4 + 1][r], a.inv_scale, pn[tl * 4 + 1][r]));
                 const float gg = seg_tanh(fmaf(acc[tl * 4 + 2][r], a.inv_scale, pn[tl * 4 + 2][r]));
                 const float go = seg_sigmoid(fmaf(acc[tl * 4 + 3][r], a.inv_scale, pn[tl * 4 + 3][r]));
-                c[tl][r] = fmaf(gf, c[tl][r], gi * gg);
-                h[tl][r] = go * seg_tanh(c[tl][r]);
-                const int b = b0 + row0 + r;
-                if (b < a.B && unit < a.H) a.y[(static_cast<size_t>(b) * a.T + t) * (2 * a.H) + dir * a.H + unit] = h[tl][r];
+                if constexpr (RAGGED) {
+                    const bool live = s < rem[r];
+                    const float cn = fmaf(gf, c[tl][r], gi * gg);
+                    const float hn = go * seg_tanh(cn);
+                    c[tl][r] = live ? cn : c[tl][r];
+                    h[tl][r] = live ? hn : h[tl][r];
+                    const int row = dir ? yrow[r] - s : yrow[r] + s;
+                    if (live && unit < a.H) a.y[static_cast<size_t>(row) * (2 * a.H) + dir * a.H + unit] = hn;
+                } else {
+                    c[tl][r] = fmaf(gf, c[tl][r], gi * gg);
+                    h[tl][r] = go * seg_tanh(c[tl][r]);
+                    const int b = b0 + row0 + r;
+                    if (b < a.B && unit < a.H) a.y[(static_cast<size_t>(b) * a.T + t) * (2 * a.H) + dir * a.H + unit] = h[tl][r];
+                }
             }
             seg_put_h(hbuf[cur ^ 1][0], hbuf[cur ^ 1][1], unit, row0, h[tl]);
         }
-        if (s + 1 < a.n) {                                               // the next step's pre: a barrier and a product away from its use
+        if (s + 1 < n) {                                                 // the next step's pre: a barrier and a product away from its use
             const float* pp = pre_at(s + 1);
 #pragma unroll
             for (int q = 0; q < 8; ++q) pn[q] = *reinterpret_cast<const seg_f4*>(pp + q * kSegTileFloats);

@@ -369,6 +369,27 @@ int hssfsst_segmenter_info(const hssfsst_segmenter* plan, int* input_size, int* 
 int hssfsst_segmenter_exec(hssfsst_segmenter* plan, const void* feats, int feats_dtype, int64_t batch, int64_t steps,
                            const float* h0, const float* c0, float* logp, void* stream);
 
+/* The same model on a LIST of whole recordings of different lengths in one call -- what hssfsst_exec_ragged's STACK features are:
+ * recording i is rows offsets[i] .. offsets[i + 1] of feats (sum T, input_size), and its log-probs land in the same rows of logp
+ * (sum T, 4).  offsets: int64 HOST array of count + 1 step offsets, offsets[0] == 0, strictly increasing.  h0, c0: (2, state_rows,
+ * hidden) float32 with state_rows == count (recording i starts from row i) or 1 (every recording starts from the same state: the
+ * reference model built with batch_size = 1 and fed one recording per step).  feats, h0, c0, logp: DEVICE pointers.
+ * For every i the result is bit-identical to hssfsst_segmenter_exec on that recording alone (batch 1, its own state row): the
+ * forward direction from its first step, the reverse direction from its own last step, lstm_2 seeded with lstm_1's state at the
+ * recording's own ends.  Padding to (count, T_max) cannot give that.
+ * How: recordings are sorted by length into tiles of 16 row slots (csrc/segmenter_layout.hpp), one recurrence workgroup per tile
+ * and direction walks the tile's longest recording and rows past their own end freeze (RAGGED instantiations of
+ * csrc/segmenter_lstm.hpp); independent tiles fill the device.  The order changes the wasted steps, not the bits.
+ * Argument errors return HSSFSST_EINVAL before any device work, the list's before the plan is looked at: count < 0, a NULL
+ * pointer, offsets[0] != 0, an offset that does not increase or a recording over the dense call's step limit (the message names
+ * the index), more than 2^31 - 1 steps in all, state_rows not in {1, count}, an unknown dtype.  count == 0 does nothing and
+ * returns 0.  The device tables are kept while the next call has the same offsets.
+ * Scratch (the plan's, grown on demand and kept, shared with hssfsst_segmenter_exec): both layers' outputs, 2 x sum T x 2 hidden
+ * x 4 bytes; one chunk of projected inputs, at most 128 MiB, or one step of every tile (128 KiB each) if that is more; the
+ * state, 16 KiB per tile.  Enqueued on `stream` without synchronising. */
+int hssfsst_segmenter_exec_ragged(hssfsst_segmenter* plan, const void* feats, int feats_dtype, const int64_t* offsets,
+                                  int64_t count, const float* h0, const float* c0, int state_rows, float* logp, void* stream);
+
 int hssfsst_device_count(void);
 int hssfsst_version(void);
 const char* hssfsst_last_error(void);

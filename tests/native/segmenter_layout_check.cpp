@@ -1,0 +1,86 @@
+// Stand-alone check of the ragged segmenter's slot / tile layout builder (csrc/segmenter_layout.hpp: host only, no HIP), built with
+// -fsanitize=address,undefined by tests/test_segmenter_ragged.py.  Any failed property or sanitizer report ends the run non-zero.
+#include "segmenter_layout.hpp"
+
+#include <cstdio>
+#include <cstdlib>
+#include <vector>
+
+namespace sl = hssfsst::seglayout;
+
+static int failures = 0;
+#define CHECK(cond, ...)                                                     \
+    do {                                                                     \
+        if (!(cond)) { std::printf("FAIL %s: ", name); std::printf(__VA_ARGS__); std::printf("\n"); ++failures; } \
+    } while (0)
+
+static void run_case(const char* name, const std::vector<int>& lens)
+{
+    const int64_t count = static_cast<int64_t>(lens.size());
+    std::vector<int64_t> offsets(lens.size() + 1, 0);                // exactly sized: a read past the end is a report
+    for (size_t i = 0; i < lens.size(); ++i) offsets[i + 1] = offsets[i] + lens[i];
+    CHECK(sl::first_bad_length(offsets.data(), count, int64_t(1) << 28) == -1, "valid offsets refused");
+    sl::Layout lay;
+    sl::build(offsets.data(), count, lay);
+    const int tiles = static_cast<int>((count + sl::kSlotRows - 1) / sl::kSlotRows);
+    CHECK(lay.tiles() == tiles && lay.slots() == tiles * sl::kSlotRows, "%d tiles, %d slots for %lld recordings", lay.tiles(), lay.slots(),
+          static_cast<long long>(count));
+    CHECK(lay.slot_rec.size() == lay.slot_len.size() && lay.slot_off.size() == lay.slot_len.size(), "table sizes differ");
+    CHECK(lay.total == offsets[count], "total %lld", lay.total);
+    // every recording occupies exactly one slot; padding slots have length 0; offsets round-trip
+    std::vector<int> seen(lens.size(), 0);
+    for (int s = 0; s < lay.slots(); ++s) {
+        const int r = lay.slot_rec[s];
+        if (r < 0) {
+            CHECK(lay.slot_len[s] == 0, "padding slot %d has length %d", s, lay.slot_len[s]);
+            CHECK(s >= count, "padding slot %d before the last recording", s);
+            continue;
+        }
+        CHECK(r < count, "slot %d names recording %d", s, r);
+        if (r >= count) continue;
+        ++seen[r];
+        CHECK(lay.slot_off[s] == offsets[r], "slot %d: offset %lld, recording %d starts at %lld", s, lay.slot_off[s], r,
+              static_cast<long long>(offsets[r]));
+        CHECK(lay.slot_off[s] + lay.slot_len[s] == offsets[r + 1], "slot %d: end does not round-trip", s);
+    }
+    for (size_t r = 0; r < seen.size(); ++r) CHECK(seen[r] == 1, "recording %zu occupies %d slots", r, seen[r]);
+    // slot lengths are non-increasing; each tile's walk equals its maximum
+    for (int s = 1; s < lay.slots(); ++s) CHECK(lay.slot_len[s] <= lay.slot_len[s - 1], "slot %d longer than slot %d", s, s - 1);
+    long long walked = 0;
+    for (int t = 0; t < lay.tiles(); ++t) {
+        int mx = 0;
+        for (int j = 0; j < sl::kSlotRows; ++j) mx = lay.slot_len[t * sl::kSlotRows + j] > mx ? lay.slot_len[t * sl::kSlotRows + j] : mx;
+        CHECK(lay.tile_walk[t] == mx && mx > 0, "tile %d walks %d, its longest slot is %d", t, lay.tile_walk[t], mx);
+        walked += static_cast<long long>(sl::kSlotRows) * mx;
+    }
+    const double w = sl::wasted_share(lay);
+    CHECK(w >= 0.0 && w == static_cast<double>(walked) / static_cast<double>(lay.total) - 1.0, "wasted share %g", w);
+    std::printf("%-8s %5lld recordings, %3d tiles, wasted share %.4f\n", name, static_cast<long long>(count), lay.tiles(), w);
+}
+
+int main()
+{
+    run_case("one", {1});
+    run_case("equal16", std::vector<int>(16, 70));
+    run_case("seventeen", {9, 8, 7, 6, 5, 4, 3, 2, 1, 10, 11, 12, 13, 14, 15, 16, 17});
+    run_case("mixed19", {1, 2, 15, 16, 17, 40, 333, 1100, 5, 16, 31, 64, 7, 7, 250, 3, 1, 90, 600});
+    std::vector<int> many(1000);
+    unsigned long long x = 0x9e3779b97f4a7c15ull;
+    for (int& v : many) {
+        x = x * 6364136223846793005ull + 1442695040888963407ull;
+        v = 1 + static_cast<int>((x >> 33) % 60000);
+    }
+    run_case("random1k", many);
+    run_case("three", {5, 5, 5});
+
+    // what the entry point refuses, and at which index
+    const char* name = "bad";
+    const int64_t flat[] = {0, 5, 5}, back[] = {0, 7, 3}, lng[] = {0, 4, 104}, good[] = {0, 4, 9};
+    CHECK(sl::first_bad_length(flat, 2, 1000) == 1, "[0, 5, 5]");
+    CHECK(sl::first_bad_length(back, 2, 1000) == 1, "[0, 7, 3]");
+    CHECK(sl::first_bad_length(lng, 2, 99) == 1, "a recording over the limit");
+    CHECK(sl::first_bad_length(good, 2, 5) == -1, "[0, 4, 9]");
+    if (failures) { std::printf("%d failures\n", failures); return 1; }
+    std::printf("segmenter layout ok\n");
+    return 0;
+}
