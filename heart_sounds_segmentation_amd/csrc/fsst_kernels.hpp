@@ -32,6 +32,8 @@
 
 #include <utility>
 
+#include "fsst_half.hpp"
+
 namespace hssfsst {
 
 constexpr int kModeRaw = 0, kModeAbs = 1, kModeStack = 2, kModeStackUnnorm = 3;
@@ -696,11 +698,14 @@ __global__ __launch_bounds__(TILE, 2) void fsst_core_kernel(CoreParams p)
 
 // grid = any number of blocks of 256 (the host sizes it to a fraction of the chip so the sweep can
 // share the GPU with a concurrently running core kernel); block b handles signals b, b + grid, ...
+// in = float32 [nsignals][n][2K] (16-byte aligned), out = OT [nsignals][n][2K]: float is the in-place sweep (the host passes
+// in == out: no __restrict__ here), a 2-byte OT the out-of-place one of a half plan (fsst_half.hpp).
 // With `partials` != nullptr the block first reduces the signal's nblk fp64 partials itself (the arithmetic of
 // fsst_stats_kernel, same order, same result) instead of reading `stats`: one launch less per transform.
 // `slices` > 1 cuts every signal into that many contiguous pieces, one block each (small batches: a block per
 // signal would leave most of the chip idle); the fused reduction is only used with slices == 1.
-__global__ __launch_bounds__(256) void fsst_normalize_kernel(float* out, const float4* stats, const float* partials,
+template <class OT>
+__global__ __launch_bounds__(256) void fsst_normalize_kernel(const float* in, OT* out, const float4* stats, const float* partials,
                                                              int nblk, int fpp, int n, int K, int nsignals, int slices,
                                                              const unsigned* gate = nullptr, unsigned gate_val = 0u)
 {
@@ -709,6 +714,7 @@ __global__ __launch_bounds__(256) void fsst_normalize_kernel(float* out, const f
     const int tid = threadIdx.x;
     const int C = 2 * K;
     const int total = n * C;                             // per-signal element count (< 2^31, checked on the host)
+    const bool vec = (total & 3) == 0 && zscore_store4_aligned(out);
     for (int unit = blockIdx.x; unit < nsignals * slices; unit += gridDim.x) {
         const int sig = unit / slices, sl = unit - sig * slices;
         float4 st;
@@ -724,12 +730,13 @@ __global__ __launch_bounds__(256) void fsst_normalize_kernel(float* out, const f
             st = stats[sig];
         }
         const float m_re = st.x, i_re = st.y, m_im = st.z, i_im = st.w;
-        float* base = out + static_cast<long long>(sig) * total;
-        if ((total & 3) == 0) {
+        const float* src = in + static_cast<long long>(sig) * total;
+        OT* dst = out + static_cast<long long>(sig) * total;
+        if (vec) {
             // linear float4 sweep of the signal's block (its start is 16-byte aligned because total % 4 == 0); the
             // column of a chunk is tracked incrementally (no integer division in the loop).  When 2K is not a
             // multiple of 4 a float4 can wrap from the end of one row into the next: per-element wrap test.
-            float4* b4 = reinterpret_cast<float4*>(base);
+            const float4* s4 = reinterpret_cast<const float4*>(src);
             const int tot4 = total >> 2;
             const int i0 = static_cast<int>(static_cast<long long>(tot4) * sl / slices);
             const int i1 = static_cast<int>(static_cast<long long>(tot4) * (sl + 1) / slices);
@@ -738,18 +745,18 @@ __global__ __launch_bounds__(256) void fsst_normalize_kernel(float* out, const f
             const bool rowwrap = (C & 3) != 0;
 #pragma unroll 4
             for (int i = i0 + tid; i < i1; i += 256) {
-                float4 v = b4[i];                        // (streaming load / store hints measured here: 0.147 vs 0.119 ms, worse)
+                const float4 v = s4[i];                  // (streaming load / store hints measured here: 0.147 vs 0.119 ms, worse)
                 int c1 = c + 1, c2 = c + 2, c3 = c + 3;
                 if (rowwrap) {
                     if (c1 >= C) c1 -= C;
                     if (c2 >= C) c2 -= C;
                     if (c3 >= C) c3 -= C;
                 }
-                v.x = (c < K) ? (v.x - m_re) * i_re : (v.x - m_im) * i_im;
-                v.y = (c1 < K) ? (v.y - m_re) * i_re : (v.y - m_im) * i_im;
-                v.z = (c2 < K) ? (v.z - m_re) * i_re : (v.z - m_im) * i_im;
-                v.w = (c3 < K) ? (v.w - m_re) * i_re : (v.w - m_im) * i_im;
-                b4[i] = v;
+                zscore_store4<OT>(dst + 4ll * i,
+                                  (c < K) ? (v.x - m_re) * i_re : (v.x - m_im) * i_im,
+                                  (c1 < K) ? (v.y - m_re) * i_re : (v.y - m_im) * i_im,
+                                  (c2 < K) ? (v.z - m_re) * i_re : (v.z - m_im) * i_im,
+                                  (c3 < K) ? (v.w - m_re) * i_re : (v.w - m_im) * i_im);
                 c += dc;
                 if (c >= C) c -= C;
             }
@@ -758,8 +765,8 @@ __global__ __launch_bounds__(256) void fsst_normalize_kernel(float* out, const f
             const int i1 = static_cast<int>(static_cast<long long>(total) * (sl + 1) / slices);
             for (int i = i0 + tid; i < i1; i += 256) {
                 const int c = i % C;
-                const float v = base[i];
-                base[i] = (c < K) ? (v - m_re) * i_re : (v - m_im) * i_im;
+                const float v = src[i];
+                dst[i] = static_cast<OT>((c < K) ? (v - m_re) * i_re : (v - m_im) * i_im);
             }
         }
     }

@@ -25,11 +25,17 @@ __global__ __launch_bounds__(64) void fsst_ragged_stats_kernel(const float* part
 // bisection and z-scores its share of the signal's float4 -- counted from the 16-byte boundary at or below the signal's first
 // feature, so that every full float4 is one aligned load and store; the first and last float4 of a signal may be shared with its
 // neighbours and are done element by element.
-__global__ __launch_bounds__(256) void fsst_ragged_normalize_kernel(float* out, const RaggedSignal* sig, const int* unit0,
+// Signal s's float32 features lie at in + sig[s].ooff, its result goes to out + sig[s].ooff (offsets in elements): float is the
+// in-place sweep (the host passes in == out: no __restrict__ here), a 2-byte OT the out-of-place one of a half plan
+// (fsst_half.hpp) -- there `in` is 16-byte aligned, so with an 8-byte aligned `out` a float4 of `in` and its four OT share their
+// position in the 4-element grid; an unaligned `out` goes element by element throughout.
+template <class OT>
+__global__ __launch_bounds__(256) void fsst_ragged_normalize_kernel(const float* in, OT* out, const RaggedSignal* sig, const int* unit0,
                                                                     const float4* stats, int nsig, int K)
 {
     const int tid = threadIdx.x;
     const int C = 2 * K;
+    const bool vec = zscore_store4_aligned(out);
     const int nunits = unit0[nsig];
     for (int u = blockIdx.x; u < nunits; u += gridDim.x) {
         int lo = 0, hi = nsig;                                   // unit0[lo] <= u < unit0[hi]
@@ -41,9 +47,9 @@ __global__ __launch_bounds__(256) void fsst_ragged_normalize_kernel(float* out, 
         const RaggedSignal rs = sig[s];
         const float4 st = stats[s];
         const float m_re = st.x, i_re = st.y, m_im = st.z, i_im = st.w;
-        float* base = out + rs.ooff;
-        const int a = static_cast<int>((reinterpret_cast<uintptr_t>(base) >> 2) & 3);     // floats below base in its float4
-        float4* b4 = reinterpret_cast<float4*>(base - a);
+        const int a = static_cast<int>((reinterpret_cast<uintptr_t>(in + rs.ooff) >> 2) & 3);   // floats below the signal's first in its float4
+        const float* src = in + (rs.ooff - a);
+        OT* dst = out + (rs.ooff - a);
         const int total = rs.n * C;                              // (< 2^31: checked on the host)
         const int q = static_cast<int>((static_cast<long long>(a) + total + 3) >> 2);
         const int slices = unit0[s + 1] - unit0[s], sl = u - unit0[s];
@@ -56,17 +62,12 @@ __global__ __launch_bounds__(256) void fsst_ragged_normalize_kernel(float* out, 
         auto zs = [&](float v, int col) -> float { return (col < K) ? (v - m_re) * i_re : (v - m_im) * i_im; };
         auto wrap = [&](int col) -> int { if (col >= C) col -= C; if (col >= C) col -= C; return col; };   // (C >= 2: c + 3 < 3 C)
         for (int i = i0 + tid; i < i1; i += 256) {
-            if (e >= 0 && e + 4 <= total) {
-                float4 v = b4[i];
-                v.x = zs(v.x, c);
-                v.y = zs(v.y, wrap(c + 1));
-                v.z = zs(v.z, wrap(c + 2));
-                v.w = zs(v.w, wrap(c + 3));
-                b4[i] = v;
+            if (vec && e >= 0 && e + 4 <= total) {
+                const float4 v = reinterpret_cast<const float4*>(src)[i];
+                zscore_store4<OT>(dst + 4ll * i, zs(v.x, c), zs(v.y, wrap(c + 1)), zs(v.z, wrap(c + 2)), zs(v.w, wrap(c + 3)));
             } else {
-                float* f = reinterpret_cast<float*>(b4 + i);
                 for (int k = 0; k < 4; ++k)
-                    if (e + k >= 0 && e + k < total) f[k] = zs(f[k], wrap(c + k));
+                    if (e + k >= 0 && e + k < total) dst[4ll * i + k] = static_cast<OT>(zs(src[4ll * i + k], wrap(c + k)));
             }
             e += 1024;
             c = wrap(c + dc);

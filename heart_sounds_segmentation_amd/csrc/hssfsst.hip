@@ -62,6 +62,14 @@ int fail(int code, const char* fmt, ...)
                         __FILE__, __LINE__);                                                   \
     } while (0)
 
+// behind a kernel launch of the entry point `entry`
+int launch_check(const char* entry, const char* what)
+{
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(HSSFSST_EHIP, "%s: launch of %s failed: %s", entry, what, hipGetErrorString(e));
+    return 0;
+}
+
 // A-B and test switches, read ONCE per process (first use) from the environment, one variable per key: HSSFSST_<KEY in capitals>
 // is on when set to an empty string, a non-zero number or a word that starts with y or t (HSSFSST_FORCE_GENERIC: a value that
 // starts with 1).  Defaults are the measured best; no switch changes a result (every path gives the same bits, which is what most
@@ -205,6 +213,57 @@ struct PinnedBuf {
     }
 };
 
+// A table that is made on the host for a list and read on the device: a pinned (not mapped) host block, a device block, the event
+// of the last upload (the host block is not rewritten before that copy is done) and the key of the list the device block holds.
+//   if (!t.same(n, key)) { t.begin(bytes, &h); ...fill h...; t.commit(stream, n, key); }     key(i): the i-th of n 64-bit words
+// begin() drops the key first and commit() stores it last, behind the queued copy: whatever fails in between, the next call with
+// the same list makes the table again.  A user without a key (n = 0) uploads at every call.  `what`: the entry point, for errors.
+struct UploadedTable {
+    const char* what;
+    PinnedBuf<unsigned char> h{false};
+    DevBuf<unsigned char> d;
+    hipEvent_t ev = nullptr;
+    std::vector<int64_t> key;
+    size_t bytes = 0;
+    explicit UploadedTable(const char* what_) : what(what_) {}
+    UploadedTable(const UploadedTable&) = delete;
+    UploadedTable& operator=(const UploadedTable&) = delete;
+    ~UploadedTable() { if (ev) (void)hipEventDestroy(ev); }
+    const unsigned char* get() const { return d.get(); }
+    template <class Key>
+    bool same(size_t n, Key&& at) const
+    {
+        if (key.empty() || key.size() != n) return false;
+        for (size_t i = 0; i < n; ++i) if (key[i] != at(i)) return false;
+        return true;
+    }
+    int begin(size_t nbytes, unsigned char** host)
+    {
+        key.clear();
+        if (ev) HIP_TRY(hipEventSynchronize(ev));          // (the previous upload may still read the host block)
+        if (int rc = h.grow(nbytes, 1)) return rc;
+        if (int rc = d.grow(nbytes)) return rc;
+        bytes = nbytes;
+        *host = h.h;
+        return 0;
+    }
+    template <class Key>
+    int commit(hipStream_t st, size_t n, Key&& at)
+    {
+        if (!ev) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        HIP_TRY(hipMemcpyAsync(d.get(), h.h, bytes, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipEventRecord(ev, st));
+        try {
+            key.resize(n);
+        } catch (const std::bad_alloc&) {
+            return fail(HSSFSST_ENOMEM, "%s: out of host memory", what);
+        }
+        for (size_t i = 0; i < n; ++i) key[i] = at(i);
+        return 0;
+    }
+    int commit(hipStream_t st) { return commit(st, 0, [](size_t) { return int64_t(0); }); }
+};
+
 constexpr size_t kPinPoolMax = 64;                       // hssfsst_exec_pinned: buffers lent at a time (hssfsst.h)
 
 // The kernels a plan runs (choose_family): generic VALU (nwin 32 / 64, and the fallback of 128 / 256 / 512), any-length, MFMA
@@ -269,15 +328,13 @@ struct hssfsst_plan {
                                                              // come from another host thread)
     DevBuf<long long> d_starts;                              // frame-list staging (hssfsst_exec_list with host starts)
     DevBuf<float> d_frames;                                  // frames gathered from a list, dense [batch][n]
-    // hssfsst_exec_ragged: the list's tables -- RaggedSignal[batch], z-score unit starts int[batch + 1], chunk list int2[] -- made
-    // on the host (h_rtab, pinned) and uploaded in one copy to d_rtab; kept while the next list has the same lengths and offsets (rkey)
-    DevBuf<unsigned char> d_rtab;
-    PinnedBuf<unsigned char> h_rtab{false};
-    size_t rtab_bytes = 0;
-    std::vector<long long> rkey;
-    size_t rtab_unit = 0, rtab_chunk = 0;                    // byte offsets of the unit starts and of the chunk list in the tables
-    long long rtab_nchunks = 0, rtab_nunits = 0;
-    hipEvent_t rtab_ev = nullptr;                            // the last upload of h_rtab (h_rtab is not rewritten before it is done)
+    // hssfsst_exec_ragged: the list's tables -- RaggedSignal[batch], z-score unit starts int[batch + 1], chunk list int2[] -- in one
+    // block, kept while the next list has the same lengths and offsets; where they lie in it and how many they are
+    UploadedTable rtab{"exec_ragged"};
+    struct RaggedTabs {
+        size_t unit = 0, chunk = 0, bytes = 0;               // byte offsets of the unit starts and of the chunk list, and the block's size
+        long long nchunks = 0, nunits = 0;
+    } rtabs;                                                 // (of rtab's key: written behind its commit)
     int timing_every = 0;         // hssfsst_plan_set_timing(n): every n-th exec is timed (0: off)
     unsigned timing_seq = 0;
     std::vector<hipEvent_t> ev;   // per timed exec: (before, after) per core launch + one closing event
@@ -764,12 +821,107 @@ int timing_end(hssfsst_plan* p, const ExecCtx& cx, bool one_kernel)
     return 0;
 }
 
-// f(o) with a half plan's output `out` as what it holds: _Float16* or __bf16*
+// f(o) with an exec's output `out` as what the plan says it holds: float*, _Float16* or __bf16*
 template <class F>
-void half_dispatch(const hssfsst_plan* p, void* out, F&& f)
+void out_dispatch(const hssfsst_plan* p, void* out, F&& f)
 {
     if (p->out_dtype == HSSFSST_DTYPE_F16) f(static_cast<_Float16*>(out));
-    else f(static_cast<__bf16*>(out));
+    else if (p->out_dtype == HSSFSST_DTYPE_BF16) f(static_cast<__bf16*>(out));
+    else f(static_cast<float*>(out));
+}
+
+// The tables of a ragged exec's list, into the host block h (laid out by t): signal i reads x at starts[i] - xlo, its features
+// are `ofps` floats per sample behind those of the signals before it, its statistics partials one per 16-frame group likewise;
+// its z-score units (fsst_ragged.hpp) follow from its 2K floats per sample.  t.nunits is set here.
+void fill_ragged_tables(unsigned char* h, hssfsst_plan::RaggedTabs& t, const std::vector<int2>& chunks, const int64_t* starts,
+                        const int64_t* lens, int64_t batch, long long xlo, int ofps, int K)
+{
+    std::memset(h, 0, t.chunk);
+    auto* rs = reinterpret_cast<hssfsst::RaggedSignal*>(h);
+    int* unit0 = reinterpret_cast<int*>(h + t.unit);
+    long long o = 0, g = 0, u = 0;
+    for (int64_t i = 0; i < batch; ++i) {
+        rs[i].xoff = starts[i] - xlo; rs[i].ooff = o * ofps; rs[i].poff = g * hssfsst::kPartFloats;
+        rs[i].n = static_cast<int>(lens[i]); rs[i].pad = 0;
+        unit0[i] = static_cast<int>(u);
+        u += (lens[i] * 2 * K + hssfsst::kRaggedUnitFloats - 1) / hssfsst::kRaggedUnitFloats;
+        o += lens[i]; g += (lens[i] + 15) / 16;
+    }
+    unit0[batch] = static_cast<int>(u);
+    std::memcpy(h + t.chunk, chunks.data(), chunks.size() * sizeof(int2));
+    t.nunits = u;
+}
+
+// ... on the device: p->rtab holds them and p->rtabs says where, for the list (lens, starts - xlo); made and uploaded only when
+// that is not the list they were last made for
+int ragged_tables(hssfsst_plan* p, const int64_t* starts, const int64_t* lens, int64_t batch, long long xlo, hipStream_t st)
+{
+    auto key = [&](size_t i) -> int64_t { return (i & 1) ? starts[i >> 1] - xlo : lens[i >> 1]; };
+    const size_t nkey = static_cast<size_t>(2 * batch);
+    if (p->rtab.same(nkey, key)) return 0;
+    std::vector<int> ng(static_cast<size_t>(batch));
+    for (int64_t i = 0; i < batch; ++i) ng[i] = static_cast<int>((lens[i] + 15) / 16);
+    std::vector<int2> chunks;
+    hssfsst::core128_ragged_chunks(ng.data(), batch, chunks);
+    if (chunks.size() >= 0x7fffffffull) return fail(HSSFSST_EINVAL, "exec_ragged: %zu chunks exceed the launch limit; split the list", chunks.size());
+    hssfsst_plan::RaggedTabs t;
+    t.unit = (static_cast<size_t>(batch) * sizeof(hssfsst::RaggedSignal) + 15) & ~size_t(15);
+    t.chunk = (t.unit + static_cast<size_t>(batch + 1) * sizeof(int) + 15) & ~size_t(15);
+    t.bytes = t.chunk + chunks.size() * sizeof(int2);
+    t.nchunks = static_cast<long long>(chunks.size());
+    unsigned char* h = nullptr;
+    if (int rc = p->rtab.begin(t.bytes, &h)) return rc;
+    fill_ragged_tables(h, t, chunks, starts, lens, batch, xlo, out_floats_per_sample(p), p->K);
+    if (int rc = p->rtab.commit(st, nkey, key)) return rc;
+    p->rtabs = t;
+    return 0;
+}
+
+// The z-score of a dense STACK exec whose core launch left it to do: `feats` = the un-normalised float32 features [batch][ncols][2K]
+// with their statistics partials in d_partials, `out` = the exec's output in the plan's element type (float32: feats itself, swept
+// in place; a half plan: out of place from its float32 scratch).  (cx.gate non-null: a team launch went first; these launches are
+// its gated fallback.)
+int launch_zscore(hssfsst_plan* p, const ExecCtx& cx, const float* feats, void* out, int64_t batch, int nblk, int fpp, int ncols)
+{
+    float4* stats = reinterpret_cast<float4*>(p->d_stats.get());
+    const float* partials = p->d_partials.get();
+    int64_t zgrid = 4096;
+    // small batches: several blocks per signal, else one block per signal would leave most CUs idle
+    int slices = 1;
+    if (batch < 1024) {
+        slices = static_cast<int>(1024 / batch);
+        if (slices > 32) slices = 32;
+    }
+    if (zgrid > batch * slices) zgrid = batch * slices;
+    // big batches, a block per signal: it reduces the signal's partials itself (no separate statistics
+    // launch, 4-7 us per step); otherwise a tiny kernel does all reductions at once
+    const bool fused = slices == 1 && zgrid == batch && batch >= 512;
+    if (!fused)
+        hipLaunchKernelGGL(hssfsst::fsst_stats_kernel, dim3(static_cast<unsigned>(batch)), dim3(64), 0, cx.st,
+                           partials, stats, nblk, fpp, ncols, p->K, cx.gate, cx.gate_val);
+    out_dispatch(p, out, [&](auto* o) {
+        hipLaunchKernelGGL(hssfsst::fsst_normalize_kernel<std::remove_pointer_t<decltype(o)>>, dim3(static_cast<unsigned>(zgrid)), dim3(256), 0, cx.st,
+                           feats, o, stats, fused ? partials : nullptr, nblk, fpp, ncols, p->K, static_cast<int>(batch), slices,
+                           cx.gate, cx.gate_val);
+    });
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// The z-score of a ragged STACK exec (fsst_ragged.hpp): per-signal statistics, then one sweep over the list's `nunits` units;
+// feats and out as in launch_zscore, rsig and unit0 the list's device tables
+int launch_zscore_ragged(hssfsst_plan* p, const ExecCtx& cx, const float* feats, void* out, int64_t batch,
+                         const hssfsst::RaggedSignal* rsig, const int* unit0, long long nunits)
+{
+    float4* stats = reinterpret_cast<float4*>(p->d_stats.get());
+    hipLaunchKernelGGL(hssfsst::fsst_ragged_stats_kernel, dim3(static_cast<unsigned>(batch)), dim3(64), 0, cx.st, p->d_partials.get(), rsig, stats, p->K);
+    const long long zgrid = std::min<long long>(nunits, 65536);
+    out_dispatch(p, out, [&](auto* o) {
+        hipLaunchKernelGGL(hssfsst::fsst_ragged_normalize_kernel<std::remove_pointer_t<decltype(o)>>, dim3(static_cast<unsigned>(zgrid)), dim3(256), 0, cx.st,
+                           feats, o, rsig, unit0, stats, static_cast<int>(batch), p->K);
+    });
+    HIP_TRY(hipGetLastError());
+    return 0;
 }
 
 // The plain (two-launch) core kernel for a plan of the MFMA kernel: as many waves per block as fit the 160 KiB of LDS beside
@@ -1041,7 +1193,6 @@ int hssfsst_plan_destroy(hssfsst_plan* p)
     DeviceGuard device_guard_(p->device);
     if (p->h_status) (void)hipHostFree(const_cast<unsigned*>(p->h_status));
     if (p->h_fallback) (void)hipHostFree(const_cast<unsigned*>(p->h_fallback));
-    if (p->rtab_ev) (void)hipEventDestroy(p->rtab_ev);
     for (auto& ev : p->ev) if (ev) (void)hipEventDestroy(ev);
     delete p;                                            // (the buffers free themselves)
     return 0;
@@ -1485,34 +1636,7 @@ static int exec_impl(hssfsst_plan* p, const float* x, int64_t batch, int n, int6
     }
     if (rc != 0) return rc;
     if ((rc = timing_core_done(p, cx)) != 0) return rc;
-    if (p->mode == HSSFSST_MODE_STACK && !cx.fused) {       // (cx.gate non-null: a team launch went first; what follows is its gated fallback)
-        float4* stats = reinterpret_cast<float4*>(p->d_stats.get());
-        int64_t zgrid = 4096;
-        // small batches: several blocks per signal, else one block per signal would leave most CUs idle
-        int slices = 1;
-        if (batch < 1024) {
-            slices = static_cast<int>(1024 / batch);
-            if (slices > 32) slices = 32;
-        }
-        if (zgrid > batch * slices) zgrid = batch * slices;
-        // big batches, a block per signal: it reduces the signal's partials itself (no separate statistics
-        // launch, 4-7 us per step); otherwise a tiny kernel does all reductions at once
-        const bool fused = slices == 1 && zgrid == batch && batch >= 512;
-        if (!fused)
-            hipLaunchKernelGGL(hssfsst::fsst_stats_kernel, dim3(static_cast<unsigned>(batch)), dim3(64), 0, st,
-                               cp.partials, stats, nblk, fpp, ncols, p->K, cx.gate, cx.gate_val);
-        if (half)                                        // out of place: float32 scratch -> 2-byte elements (fsst_half.hpp)
-            half_dispatch(p, dout, [&](auto* o) {
-                hipLaunchKernelGGL(hssfsst::fsst_normalize_to_kernel<std::remove_pointer_t<decltype(o)>>, dim3(static_cast<unsigned>(zgrid)), dim3(256), 0, st,
-                                   kout, o, stats, fused ? cp.partials : nullptr, nblk, fpp, ncols, p->K, static_cast<int>(batch), slices,
-                                   cx.gate, cx.gate_val);
-            });
-        else
-            hipLaunchKernelGGL(hssfsst::fsst_normalize_kernel, dim3(static_cast<unsigned>(zgrid)), dim3(256), 0, st,
-                               kout, stats, fused ? cp.partials : nullptr, nblk, fpp, ncols, p->K, static_cast<int>(batch), slices,
-                               cx.gate, cx.gate_val);
-        HIP_TRY(hipGetLastError());
-    }
+    if (p->mode == HSSFSST_MODE_STACK && !cx.fused && (rc = launch_zscore(p, cx, kout, dout, batch, nblk, fpp, ncols)) != 0) return rc;
     exec_report(p, cx);
     if ((rc = timing_end(p, cx, p->last_fused != 0)) != 0) return rc;
     if (tiny_out) {
@@ -1643,48 +1767,12 @@ int hssfsst_exec_ragged(hssfsst_plan* p, const float* x, int64_t x_len, const in
     long long cols = 0, groups = 0;
     for (int64_t i = 0; i < batch; ++i) { cols += lens[i]; groups += (lens[i] + 15) / 16; }
     const size_t no = static_cast<size_t>(cols) * ofps;                       // output elements
-    const bool half = p->out_es != sizeof(float);
 
-    // the tables (kept while the list's lengths and offsets stay the same)
-    const size_t sig_bytes = static_cast<size_t>(batch) * sizeof(hssfsst::RaggedSignal);
-    bool same = p->d_rtab.get() != nullptr && p->rkey.size() == static_cast<size_t>(2 * batch);
-    for (int64_t i = 0; same && i < batch; ++i) same = p->rkey[2 * i] == lens[i] && p->rkey[2 * i + 1] == starts[i] - xlo;
-    if (!same) {
-        if (p->rtab_ev) HIP_TRY(hipEventSynchronize(p->rtab_ev));      // (the previous upload may still read h_rtab)
-        std::vector<int> ng(static_cast<size_t>(batch));
-        for (int64_t i = 0; i < batch; ++i) ng[i] = static_cast<int>((lens[i] + 15) / 16);
-        std::vector<int2> chunks;
-        hssfsst::core128_ragged_chunks(ng.data(), batch, chunks);
-        if (chunks.size() >= 0x7fffffffull) return fail(HSSFSST_EINVAL, "exec_ragged: %zu chunks exceed the launch limit; split the list", chunks.size());
-        p->rtab_unit = (sig_bytes + 15) & ~size_t(15);
-        p->rtab_chunk = (p->rtab_unit + static_cast<size_t>(batch + 1) * sizeof(int) + 15) & ~size_t(15);
-        p->rtab_bytes = p->rtab_chunk + chunks.size() * sizeof(int2);
-        if ((rc = p->h_rtab.grow(p->rtab_bytes, 1)) != 0) return rc;
-        std::memset(p->h_rtab.h, 0, p->rtab_chunk);
-        auto* rs = reinterpret_cast<hssfsst::RaggedSignal*>(p->h_rtab.h);
-        int* unit0 = reinterpret_cast<int*>(p->h_rtab.h + p->rtab_unit);
-        long long o = 0, g = 0, u = 0;
-        p->rkey.resize(static_cast<size_t>(2 * batch));
-        for (int64_t i = 0; i < batch; ++i) {
-            rs[i].xoff = starts[i] - xlo; rs[i].ooff = o * ofps; rs[i].poff = g * hssfsst::kPartFloats;
-            rs[i].n = static_cast<int>(lens[i]); rs[i].pad = 0;
-            unit0[i] = static_cast<int>(u);
-            u += (lens[i] * 2 * p->K + hssfsst::kRaggedUnitFloats - 1) / hssfsst::kRaggedUnitFloats;
-            o += lens[i]; g += ng[i];
-            p->rkey[2 * i] = lens[i]; p->rkey[2 * i + 1] = starts[i] - xlo;
-        }
-        unit0[batch] = static_cast<int>(u);
-        std::memcpy(p->h_rtab.h + p->rtab_chunk, chunks.data(), chunks.size() * sizeof(int2));
-        p->rtab_nchunks = static_cast<long long>(chunks.size());
-        p->rtab_nunits = u;
-        if ((rc = p->d_rtab.grow(p->rtab_bytes)) != 0) { p->rkey.clear(); return rc; }
-        if (!p->rtab_ev) HIP_TRY(hipEventCreateWithFlags(&p->rtab_ev, hipEventDisableTiming));
-        HIP_TRY(hipMemcpyAsync(p->d_rtab.get(), p->h_rtab.h, p->rtab_bytes, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipEventRecord(p->rtab_ev, st));
-    }
-    const auto* d_rsig = reinterpret_cast<const hssfsst::RaggedSignal*>(p->d_rtab.get());
-    const int* d_unit0 = reinterpret_cast<const int*>(p->d_rtab.get() + p->rtab_unit);
-    const int2* d_chunks = reinterpret_cast<const int2*>(p->d_rtab.get() + p->rtab_chunk);
+    if ((rc = ragged_tables(p, starts, lens, batch, xlo, st)) != 0) return rc;
+    const hssfsst_plan::RaggedTabs& t = p->rtabs;
+    const auto* d_rsig = reinterpret_cast<const hssfsst::RaggedSignal*>(p->rtab.get());
+    const int* d_unit0 = reinterpret_cast<const int*>(p->rtab.get() + t.unit);
+    const int2* d_chunks = reinterpret_cast<const int2*>(p->rtab.get() + t.chunk);
 
     const float* dx = x;
     float* dout = out;
@@ -1699,29 +1787,16 @@ int hssfsst_exec_ragged(hssfsst_plan* p, const float* x, int64_t x_len, const in
     hssfsst::Core128Params cp = core128_params(p);
     cp.x = dx; cp.out = kout; cp.partials = p->d_partials.get();
     cp.n = 1; cp.nsig = static_cast<int>(std::min<int64_t>(batch, 0x7fffffff)); cp.col0 = 0; cp.ncols = 1; cp.xstride = 0;
-    cp.rsig = d_rsig; cp.rchunk = d_chunks; cp.rnchunks = static_cast<int>(p->rtab_nchunks);
+    cp.rsig = d_rsig; cp.rchunk = d_chunks; cp.rnchunks = static_cast<int>(t.nchunks);
     // (the canonical-class band in STACK modes takes the canonical kernel's arithmetic, as every single exec of it does; the
     //  general kernels give other -- equally accurate -- bits there)
     if (p->fast && p->nt == 16 && p->rq == 8 && plan_is_canon(p))
-        rc = canon_dispatch(p, [&](auto KL, auto KN) { return launch_canon_band<decltype(KL)::value, decltype(KN)::value, true>(p, cx, cp, p->rtab_nchunks); });
+        rc = canon_dispatch(p, [&](auto KL, auto KN) { return launch_canon_band<decltype(KL)::value, decltype(KN)::value, true>(p, cx, cp, t.nchunks); });
     else
-        rc = launch_core128_plain<true>(p, cx, cp, p->rtab_nchunks);
+        rc = launch_core128_plain<true>(p, cx, cp, t.nchunks);
     if (rc != 0) return rc;
     if ((rc = timing_core_done(p, cx)) != 0) return rc;
-    if (p->mode == HSSFSST_MODE_STACK) {
-        float4* stats = reinterpret_cast<float4*>(p->d_stats.get());
-        hipLaunchKernelGGL(hssfsst::fsst_ragged_stats_kernel, dim3(static_cast<unsigned>(batch)), dim3(64), 0, st, p->d_partials.get(), d_rsig, stats, p->K);
-        const long long zgrid = std::min<long long>(p->rtab_nunits, 65536);
-        if (half)                                        // out of place: float32 scratch -> 2-byte elements (fsst_half.hpp)
-            half_dispatch(p, dout, [&](auto* o) {
-                hipLaunchKernelGGL(hssfsst::fsst_ragged_normalize_to_kernel<std::remove_pointer_t<decltype(o)>>, dim3(static_cast<unsigned>(zgrid)), dim3(256), 0, st,
-                                   kout, o, d_rsig, d_unit0, stats, static_cast<int>(batch), p->K);
-            });
-        else
-            hipLaunchKernelGGL(hssfsst::fsst_ragged_normalize_kernel, dim3(static_cast<unsigned>(zgrid)), dim3(256), 0, st, dout, d_rsig, d_unit0,
-                               stats, static_cast<int>(batch), p->K);
-        HIP_TRY(hipGetLastError());
-    }
+    if (p->mode == HSSFSST_MODE_STACK && (rc = launch_zscore_ragged(p, cx, kout, dout, batch, d_rsig, d_unit0, t.nunits)) != 0) return rc;
     exec_report(p, cx);
     if ((rc = timing_end(p, cx, false)) != 0) return rc;
     return exec_finish(p, out, dout, no * p->out_es, x_on_device, out_on_device, st);
@@ -1756,9 +1831,7 @@ struct hssfsst_resample_plan {
     // grown to the largest M of a call; the list's descriptors are made on the host and uploaded once per call
     bool ragged = false;
     DevBuf<double2> d_tw; int tw_M = 0;                  // tw[k] = exp(-2 pi i k / tw_M), k < tw_M / 2
-    DevBuf<unsigned char> d_desc;                        // RaggedResampleSig[count] | table lengths (int64)
-    std::vector<unsigned char> h_desc;                   // their host copy (not rewritten before desc_ev: the upload reads it)
-    hipEvent_t desc_ev = nullptr;
+    UploadedTable desc{"resample_exec_ragged"};          // RaggedResampleSig[count] | table lengths (int64); no key: made at every call
 };
 
 namespace {
@@ -1794,13 +1867,6 @@ void bluestein_tables(int64_t N, int M, double sgn, hssfsst::resample_detail::cd
         for (int k = 0; k < lg; ++k) r |= ((j >> k) & 1) << (lg - 1 - k);
         B[j] = b[static_cast<size_t>(r)] / static_cast<double>(M);
     }
-}
-
-int rs_launch_check(const char* what)
-{
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(HSSFSST_EHIP, "resample_exec: launch of %s failed: %s", what, hipGetErrorString(e));
-    return 0;
 }
 
 unsigned rs_grid(long long total) { return static_cast<unsigned>((total + hssfsst::kRsThreads - 1) / hssfsst::kRsThreads); }
@@ -1859,7 +1925,7 @@ int rs_dif(hipStream_t st, double2* w, long long Mw, long long cnt, int M, const
     const long long nb = cnt * (M / 2);
     for (int len = M; len > S; len >>= 1) {
         hipLaunchKernelGGL(hssfsst::resample_dif_pass_kernel, dim3(rs_grid(nb)), dim3(hssfsst::kRsThreads), 0, st, w, Mw, M, len, tw, twM, nb);
-        if (int r = rs_launch_check("resample_dif_pass_kernel")) return r;
+        if (int r = launch_check("resample_exec", "resample_dif_pass_kernel")) return r;
     }
     return 0;
 }
@@ -1869,7 +1935,7 @@ int rs_dit(hipStream_t st, double2* w, long long Mw, long long cnt, int M, const
     const long long nb = cnt * (M / 2);
     for (int len = 2 * S; len <= M; len <<= 1) {
         hipLaunchKernelGGL(hssfsst::resample_dit_pass_kernel, dim3(rs_grid(nb)), dim3(hssfsst::kRsThreads), 0, st, w, Mw, M, len, tw, twM, nb);
-        if (int r = rs_launch_check("resample_dit_pass_kernel")) return r;
+        if (int r = launch_check("resample_exec", "resample_dit_pass_kernel")) return r;
     }
     return 0;
 }
@@ -1880,7 +1946,7 @@ int rs_conv(hipStream_t st, double2* w, long long Mw, long long cnt, int M, cons
     if (int r = rs_dif(st, w, Mw, cnt, M, tw, twM)) return r;
     hipLaunchKernelGGL(hssfsst::resample_block_kernel, dim3(static_cast<unsigned>(cnt * (M / S))), dim3(hssfsst::kRsThreads), 0, st,
                        w, Mw, M, S, B, tw, twM);
-    if (int r = rs_launch_check("resample_block_kernel")) return r;
+    if (int r = launch_check("resample_exec", "resample_block_kernel")) return r;
     return rs_dit(st, w, Mw, cnt, M, tw, twM);
 }
 
@@ -1955,7 +2021,6 @@ int hssfsst_resample_plan_destroy(hssfsst_resample_plan* p)
 {
     if (!p) return 0;
     DeviceGuard device_guard_(p->device);
-    if (p->desc_ev) (void)hipEventDestroy(p->desc_ev);
     delete p;                                            // (the buffers free themselves)
     return 0;
 }
@@ -2030,7 +2095,7 @@ int hssfsst_resample_exec(hssfsst_resample_plan* p, const void* x, int x_dtype, 
         if ((rc = allow_full_lds(hssfsst::resample_lds_kernel, p->device, lds_ok)) != 0) return rc;
         hipLaunchKernelGGL(hssfsst::resample_lds_kernel, dim3(static_cast<unsigned>(batch)), dim3(hssfsst::kRsThreads),
                            static_cast<size_t>(p->Mt) * sizeof(double2), st, a);
-        if ((rc = rs_launch_check("resample_lds_kernel")) != 0) return rc;
+        if ((rc = launch_check("resample_exec", "resample_lds_kernel")) != 0) return rc;
     } else {
         const long long Mw = p->Mt;
         const long long per = static_cast<long long>(kRsWorkBytes / (static_cast<size_t>(Mw) * sizeof(double2)));
@@ -2042,13 +2107,13 @@ int hssfsst_resample_exec(hssfsst_resample_plan* p, const void* x, int x_dtype, 
             a.b0 = b0;
             const long long t1 = cb * p->M1, t2 = cb * p->M2, t3 = cb * num;
             hipLaunchKernelGGL(hssfsst::resample_load_kernel, dim3(rs_grid(t1)), dim3(hssfsst::kRsThreads), 0, st, a, work, Mw, t1);
-            if ((rc = rs_launch_check("resample_load_kernel")) != 0) return rc;
+            if ((rc = launch_check("resample_exec", "resample_load_kernel")) != 0) return rc;
             if ((rc = rs_conv(st, work, Mw, cb, p->M1, p->B1, p->tw, p->Mt)) != 0) return rc;
             hipLaunchKernelGGL(hssfsst::resample_mid_kernel, dim3(rs_grid(t2)), dim3(hssfsst::kRsThreads), 0, st, a, work, Mw, t2);
-            if ((rc = rs_launch_check("resample_mid_kernel")) != 0) return rc;
+            if ((rc = launch_check("resample_exec", "resample_mid_kernel")) != 0) return rc;
             if ((rc = rs_conv(st, work, Mw, cb, p->M2, p->B2, p->tw, p->Mt)) != 0) return rc;
             hipLaunchKernelGGL(hssfsst::resample_store_kernel, dim3(rs_grid(t3)), dim3(hssfsst::kRsThreads), 0, st, a, work, Mw, t3);
-            if ((rc = rs_launch_check("resample_store_kernel")) != 0) return rc;
+            if ((rc = launch_check("resample_exec", "resample_store_kernel")) != 0) return rc;
         }
     }
     return rs_finish(a, y, ysz, labels, nout, x_on_device, out_on_device, st);
@@ -2135,32 +2200,29 @@ int hssfsst_resample_exec_ragged(hssfsst_resample_plan* p, const void* x, int x_
         }
         c.elems = c.cnt * c.Mw + tab_elems;
         chunks.push_back(c);
-        // descriptors: RaggedResampleSig[count] in sorted order, then the table lengths
-        if (p->desc_ev) HIP_TRY(hipEventSynchronize(p->desc_ev));    // (the previous upload may still read h_desc)
-        const size_t sig_bytes = static_cast<size_t>(count) * sizeof(RaggedResampleSig);
-        p->h_desc.resize(sig_bytes + tabN.size() * sizeof(long long));
-        auto* sig = reinterpret_cast<RaggedResampleSig*>(p->h_desc.data());
-        for (const Chunk& ch : chunks) {
-            long long u = ch.t0 - 1;
-            for (long long d = ch.d0; d < ch.d0 + ch.cnt; ++d) {
-                const long long i = ord[static_cast<size_t>(d)];
-                if (d == ch.d0 || lens[i] != lens[ord[static_cast<size_t>(d - 1)]]) ++u;
-                sig[d] = RaggedResampleSig{starts[i] - xlo, lens[i], M1s[static_cast<size_t>(d)], tabOff[static_cast<size_t>(u)], i};
-            }
-        }
-        std::memcpy(p->h_desc.data() + sig_bytes, tabN.data(), tabN.size() * sizeof(long long));
     } catch (const std::bad_alloc&) {
         return fail(HSSFSST_ENOMEM, "resample_exec_ragged: out of host memory");
     }
+    // descriptors: RaggedResampleSig[count] in sorted order, then the table lengths
+    const size_t sig_bytes = static_cast<size_t>(count) * sizeof(RaggedResampleSig);
+    unsigned char* h_desc = nullptr;
+    if ((rc = p->desc.begin(sig_bytes + tabN.size() * sizeof(long long), &h_desc)) != 0) return rc;
+    auto* sig = reinterpret_cast<RaggedResampleSig*>(h_desc);
+    for (const Chunk& ch : chunks) {
+        long long u = ch.t0 - 1;
+        for (long long d = ch.d0; d < ch.d0 + ch.cnt; ++d) {
+            const long long i = ord[static_cast<size_t>(d)];
+            if (d == ch.d0 || lens[i] != lens[ord[static_cast<size_t>(d - 1)]]) ++u;
+            sig[d] = RaggedResampleSig{starts[i] - xlo, lens[i], M1s[static_cast<size_t>(d)], tabOff[static_cast<size_t>(u)], i};
+        }
+    }
+    std::memcpy(h_desc + sig_bytes, tabN.data(), tabN.size() * sizeof(long long));
     int Mt = M2;
     for (int m : M1s) Mt = std::max(Mt, m);
     if ((rc = rs_ragged_twiddles(p, Mt)) != 0) return rc;
-    if ((rc = p->d_desc.grow(p->h_desc.size())) != 0) return rc;
-    HIP_TRY(hipMemcpyAsync(p->d_desc.get(), p->h_desc.data(), p->h_desc.size(), hipMemcpyHostToDevice, st));
-    if (!p->desc_ev) HIP_TRY(hipEventCreateWithFlags(&p->desc_ev, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(p->desc_ev, st));
-    const auto* dsig = reinterpret_cast<const RaggedResampleSig*>(p->d_desc.get());
-    const auto* dtn = reinterpret_cast<const long long*>(p->d_desc.get() + static_cast<size_t>(count) * sizeof(RaggedResampleSig));
+    if ((rc = p->desc.commit(st)) != 0) return rc;
+    const auto* dsig = reinterpret_cast<const RaggedResampleSig*>(p->desc.get());
+    const auto* dtn = reinterpret_cast<const long long*>(p->desc.get() + sig_bytes);
     long long max_elems = 0;
     for (const Chunk& ch : chunks) max_elems = std::max(max_elems, ch.elems);
     if ((rc = p->d_work.grow(static_cast<size_t>(max_elems))) != 0) return rc;
@@ -2189,16 +2251,16 @@ int hssfsst_resample_exec_ragged(hssfsst_resample_plan* p, const void* x, int x_
             double2* t0 = tabs + tabOff[static_cast<size_t>(u)];
             const long long tot = (v - u) * M;
             hipLaunchKernelGGL(hssfsst::resample_ragged_table_kernel, dim3(rs_grid(tot)), dim3(hssfsst::kRsThreads), 0, st, t0, dtn + u, M, tot);
-            if ((rc = rs_launch_check("resample_ragged_table_kernel")) != 0) return rc;
+            if ((rc = launch_check("resample_exec", "resample_ragged_table_kernel")) != 0) return rc;
             if ((rc = rs_dif(st, t0, M, v - u, M, tw, twM)) != 0) return rc;
             hipLaunchKernelGGL(hssfsst::resample_ragged_table_block_kernel, dim3(static_cast<unsigned>((v - u) * (M / S))), dim3(hssfsst::kRsThreads),
                                0, st, t0, M, S, tw, twM);
-            if ((rc = rs_launch_check("resample_ragged_table_block_kernel")) != 0) return rc;
+            if ((rc = launch_check("resample_exec", "resample_ragged_table_block_kernel")) != 0) return rc;
             u = v;
         }
         const long long t1 = cnt * Mw;
         hipLaunchKernelGGL(hssfsst::resample_ragged_load_kernel, dim3(rs_grid(t1)), dim3(hssfsst::kRsThreads), 0, st, a, csig, work, Mw, t1);
-        if ((rc = rs_launch_check("resample_ragged_load_kernel")) != 0) return rc;
+        if ((rc = launch_check("resample_exec", "resample_ragged_load_kernel")) != 0) return rc;
         // the first convolution, one class of equal M1 at a time
         for (long long e0 = 0; e0 < cnt;) {
             long long e1 = e0;
@@ -2208,17 +2270,17 @@ int hssfsst_resample_exec_ragged(hssfsst_resample_plan* p, const void* x, int x_
             if ((rc = rs_dif(st, w, Mw, e1 - e0, M, tw, twM)) != 0) return rc;
             hipLaunchKernelGGL(hssfsst::resample_ragged_block_kernel, dim3(static_cast<unsigned>((e1 - e0) * (M / S))), dim3(hssfsst::kRsThreads),
                                0, st, w, Mw, M, S, csig + e0, tabs, tw, twM);
-            if ((rc = rs_launch_check("resample_ragged_block_kernel")) != 0) return rc;
+            if ((rc = launch_check("resample_exec", "resample_ragged_block_kernel")) != 0) return rc;
             if ((rc = rs_dit(st, w, Mw, e1 - e0, M, tw, twM)) != 0) return rc;
             e0 = e1;
         }
         // the inverse side, once over the chunk
         const long long t2 = cnt * M2, t3 = cnt * num;
         hipLaunchKernelGGL(hssfsst::resample_ragged_mid_kernel, dim3(rs_grid(t2)), dim3(hssfsst::kRsThreads), 0, st, a, csig, work, Mw, t2);
-        if ((rc = rs_launch_check("resample_ragged_mid_kernel")) != 0) return rc;
+        if ((rc = launch_check("resample_exec", "resample_ragged_mid_kernel")) != 0) return rc;
         if ((rc = rs_conv(st, work, Mw, cnt, M2, p->B2, tw, twM)) != 0) return rc;
         hipLaunchKernelGGL(hssfsst::resample_ragged_store_kernel, dim3(rs_grid(t3)), dim3(hssfsst::kRsThreads), 0, st, a, csig, work, Mw, t3);
-        if ((rc = rs_launch_check("resample_ragged_store_kernel")) != 0) return rc;
+        if ((rc = launch_check("resample_exec", "resample_ragged_store_kernel")) != 0) return rc;
     }
     return rs_finish(a, y, ysz, labels, nout, x_on_device, out_on_device, st);
 }
@@ -2317,8 +2379,8 @@ int hssfsst_normalize_running(hssfsst_plan* p, float* feats, int64_t batch, int 
     hipLaunchKernelGGL(hssfsst::fsst_stats_from_state_kernel, dim3(static_cast<unsigned>((batch + 63) / 64)), dim3(64), 0, st,
                        state, stats, static_cast<int>(batch));
     const int64_t zgrid = batch < 4096 ? batch : 4096;
-    hipLaunchKernelGGL(hssfsst::fsst_normalize_kernel, dim3(static_cast<unsigned>(zgrid)), dim3(256), 0, st,
-                       feats, stats, static_cast<const float*>(nullptr), 0, 0, n, p->K, static_cast<int>(batch), 1);
+    hipLaunchKernelGGL(hssfsst::fsst_normalize_kernel<float>, dim3(static_cast<unsigned>(zgrid)), dim3(256), 0, st,
+                       static_cast<const float*>(feats), feats, stats, static_cast<const float*>(nullptr), 0, 0, n, p->K, static_cast<int>(batch), 1);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -2430,19 +2492,12 @@ struct hssfsst_segmenter {
     DevBuf<float> d_y1, d_y2;                            // (B, T, 2H): the layers' outputs
     DevBuf<float> d_state;                               // [h, c][dir][Bp][Hp]: carried from chunk to chunk and from layer 1 to layer 2
     // hssfsst_segmenter_exec_ragged: the list's layout (segmenter_layout.hpp) and its device tables -- slot_off long long[slots],
-    // slot_len int[slots], slot_rec int[slots], tile_walk int[tiles] -- made on the host (h_tab, pinned), uploaded in one copy and
-    // kept while the next call has the same offsets (tab_key)
-    hssfsst::seglayout::Layout lay;
-    std::vector<int64_t> tab_key;
-    DevBuf<unsigned char> d_tab;
-    PinnedBuf<unsigned char> h_tab{false};
-    hipEvent_t tab_ev = nullptr;                         // the last upload of h_tab (h_tab is not rewritten before it is done)
+    // slot_len int[slots], slot_rec int[slots], tile_walk int[tiles] -- in one block, kept while the next call has the same offsets
+    hssfsst::seglayout::Layout lay;                      // (of tab's key: rebuilt between its begin and commit)
+    UploadedTable tab{"segmenter_exec_ragged"};
 };
 
 namespace {
-
-constexpr size_t kSegPreBytes = size_t(128) << 20;       // bound of the projection scratch: sets the steps per chunk
-constexpr int kSegMaxChunk = 4096;                       // ... and no launch walks more steps than this
 
 // src: {weight_ih, weight_hh, bias_ih, bias_hh} x {forward, reverse} of one nn.LSTM layer, as in its state_dict
 int seg_upload_layer(hssfsst_segmenter::Layer& L, int F, int H, const float* const* src)
@@ -2496,35 +2551,64 @@ int seg_upload_layer(hssfsst_segmenter::Layer& L, int F, int H, const float* con
     return L.d_whh.upload(reinterpret_cast<const hssfsst::seg_h8*>(stream.data()), stream.size() / 8);
 }
 
-int seg_launch_check(const char* what)
-{
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(HSSFSST_EHIP, "segmenter_exec: launch of %s failed: %s", what, hipGetErrorString(e));
-    return 0;
-}
-
 constexpr int64_t kSegMaxSteps = 0x7fffffffLL / 8;       // steps of one dense exec, and of one recording of a ragged one
 constexpr int64_t kSegMaxBatch = 16 * 32768;
 static_assert(hssfsst::seglayout::kSlotRows == hssfsst::kSegRows, "a tile of the layout is the recurrence workgroup's rows");
 
-// One launch pair of a ragged exec: the first `tiles` tiles walk steps s0 .. s0 + n (n: the longest of them, at most Tc, the pitch of pre)
-struct SegRaggedChunk { int s0, n, tiles, Tc; };
+constexpr size_t kSegTileStepBytes = static_cast<size_t>(2) * hssfsst::kSegGateTiles * hssfsst::kSegTileFloats * sizeof(float);   // seglayout::Chunk
 
-// The launches of one layer: tiles finish in order (the layout sorts them), so fewer and fewer take part and the steps per launch
-// that fit the projection scratch grow.
-std::vector<SegRaggedChunk> seg_ragged_chunks(const hssfsst::seglayout::Layout& lay, size_t tile_step_bytes, size_t pre_bytes)
+int seg_check_dtype(const char* what, int feats_dtype)
 {
-    std::vector<SegRaggedChunk> out;
-    int live = lay.tiles();
-    for (int s0 = 0; s0 < lay.tile_walk[0];) {
-        while (lay.tile_walk[live - 1] <= s0) --live;
-        const size_t fit = std::max<size_t>(1, pre_bytes / (tile_step_bytes * live));
-        const int Tc = static_cast<int>(std::min<size_t>(fit, kSegMaxChunk));
-        const int n = std::min(Tc, lay.tile_walk[0] - s0);
-        out.push_back({s0, n, live, Tc});
-        s0 += n;
+    if (feats_dtype != HSSFSST_DTYPE_F32 && feats_dtype != HSSFSST_DTYPE_F16 && feats_dtype != HSSFSST_DTYPE_BF16)
+        return fail(HSSFSST_EINVAL, "%s: unknown feature dtype %d", what, feats_dtype);
+    return 0;
+}
+
+// the scratch of an exec, in elements: projection, the two layers' outputs, carried state
+int seg_grow_scratch(hssfsst_segmenter* p, size_t pre, size_t y1, size_t y2, size_t state)
+{
+    if (int rc = p->d_pre.grow(pre)) return rc;
+    if (int rc = p->d_y1.grow(y1)) return rc;
+    if (int rc = p->d_y2.grow(y2)) return rc;
+    return p->d_state.grow(state);
+}
+
+// The two layers of an exec, each one launch pair per chunk.  pa0 / ra0 carry the call's own fields (dense: B, T, Bp; ragged: the
+// slot count and the layout's device tables); the plan's, the layer's and the chunk's are filled in here.
+template <bool RAGGED>
+int seg_run_layers(hssfsst_segmenter* p, hipStream_t st, const void* feats, int feats_dtype, const hssfsst::SegProjArgs& pa0,
+                   const hssfsst::SegRecArgs& ra0, const std::vector<hssfsst::seglayout::Chunk>& chunks)
+{
+    for (int l = 0; l < 2; ++l) {
+        const hssfsst_segmenter::Layer& L = p->layer[l];
+        hssfsst::SegProjArgs pa = pa0;
+        pa.x = l ? static_cast<const void*>(p->d_y1.get()) : feats;
+        pa.x_dtype = l ? HSSFSST_DTYPE_F32 : feats_dtype;
+        pa.relu = l;
+        pa.F = L.F; pa.Fp = L.Fp;
+        pa.wt = L.d_wt.get(); pa.bias = L.d_bias.get(); pa.pre = p->d_pre.get();
+        hssfsst::SegRecArgs ra = ra0;
+        ra.pre = p->d_pre.get(); ra.whh = L.d_whh.get(); ra.state = p->d_state.get();
+        ra.y = l ? p->d_y2.get() : p->d_y1.get();
+        ra.H = p->H; ra.inv_scale = L.inv_scale;
+        for (const hssfsst::seglayout::Chunk& c : chunks) {
+            pa.n = ra.n = c.n;
+            pa.Tc = ra.Tc = c.Tc;
+            if constexpr (RAGGED) {
+                pa.s0 = ra.s0 = c.s0;
+            } else {
+                // the forward direction takes its chunks upwards, the reverse direction the mirrored ones downwards
+                pa.t0[0] = ra.t0[0] = c.s0;
+                pa.t0[1] = ra.t0[1] = ra.T - c.s0 - c.n;
+            }
+            hipLaunchKernelGGL(hssfsst::seg_proj_kernel<RAGGED>, dim3(4 * hssfsst::kSegHp / 64, static_cast<unsigned>(c.tiles * ((c.n + 7) / 8)), 2),
+                               dim3(256), 0, st, pa);
+            if (int rc = launch_check("segmenter_exec", RAGGED ? "seg_proj_kernel<ragged>" : "seg_proj_kernel")) return rc;
+            hipLaunchKernelGGL(hssfsst::seg_rec_kernel<RAGGED>, dim3(static_cast<unsigned>(c.tiles), 2), dim3(64 * hssfsst::kSegWaves), 0, st, ra);
+            if (int rc = launch_check("segmenter_exec", RAGGED ? "seg_rec_kernel<ragged>" : "seg_rec_kernel")) return rc;
+        }
     }
-    return out;
+    return 0;
 }
 
 }  // namespace
@@ -2566,7 +2650,6 @@ int hssfsst_segmenter_destroy(hssfsst_segmenter* p)
 {
     if (!p) return 0;
     DeviceGuard device_guard_(p->device);
-    if (p->tab_ev) (void)hipEventDestroy(p->tab_ev);
     delete p;                                            // (the buffers free themselves)
     return 0;
 }
@@ -2587,55 +2670,34 @@ int hssfsst_segmenter_exec(hssfsst_segmenter* p, const void* feats, int feats_dt
     if (!p || !feats || !h0 || !c0 || !logp || batch < 1 || steps < 1)
         return fail(HSSFSST_EINVAL, "segmenter_exec: bad argument (batch=%lld steps=%lld, or a NULL pointer)", static_cast<long long>(batch),
                     static_cast<long long>(steps));
-    if (feats_dtype != HSSFSST_DTYPE_F32 && feats_dtype != HSSFSST_DTYPE_F16 && feats_dtype != HSSFSST_DTYPE_BF16)
-        return fail(HSSFSST_EINVAL, "segmenter_exec: unknown feature dtype %d", feats_dtype);
+    if (int rc = seg_check_dtype("segmenter_exec", feats_dtype)) return rc;
     if (batch > kSegMaxBatch || steps > kSegMaxSteps)
         return fail(HSSFSST_EINVAL, "segmenter_exec: batch %lld or steps %lld too large", static_cast<long long>(batch), static_cast<long long>(steps));
     DEVICE_SCOPE(p->device);
     const hipStream_t st = static_cast<hipStream_t>(stream);
     const int B = static_cast<int>(batch), T = static_cast<int>(steps), H = p->H;
     const int nbt = (B + hssfsst::kSegRows - 1) / hssfsst::kSegRows, Bp = nbt * hssfsst::kSegRows;
-    const size_t step_bytes = static_cast<size_t>(2) * nbt * hssfsst::kSegGateTiles * hssfsst::kSegTileFloats * sizeof(float);
-    int Tc = static_cast<int>(std::max<size_t>(1, kSegPreBytes / step_bytes));
-    Tc = std::min(std::min(Tc, kSegMaxChunk), T);
+    std::vector<hssfsst::seglayout::Chunk> chunks;
+    try {
+        chunks = hssfsst::seglayout::dense_chunks(T, nbt, kSegTileStepBytes, hssfsst::seglayout::kSegPreBytes);
+    } catch (const std::bad_alloc&) {
+        return fail(HSSFSST_ENOMEM, "segmenter_exec: out of host memory");
+    }
     int rc;
-    if ((rc = p->d_pre.grow(step_bytes / sizeof(float) * Tc)) != 0) return rc;
-    const size_t ylen = static_cast<size_t>(B) * T * 2 * H;
-    if ((rc = p->d_y1.grow(ylen)) != 0) return rc;
-    if ((rc = p->d_y2.grow(ylen)) != 0) return rc;
-    const size_t nstate = static_cast<size_t>(4) * Bp * hssfsst::kSegHp;
-    if ((rc = p->d_state.grow(nstate)) != 0) return rc;
+    const size_t ylen = static_cast<size_t>(B) * T * 2 * H, nstate = static_cast<size_t>(4) * Bp * hssfsst::kSegHp;
+    if ((rc = seg_grow_scratch(p, hssfsst::seglayout::pre_floats(chunks, kSegTileStepBytes), ylen, ylen, nstate)) != 0) return rc;
     hipLaunchKernelGGL(hssfsst::seg_state_init_kernel<false>, dim3(static_cast<unsigned>((nstate + 255) / 256)), dim3(256), 0, st, h0, c0,
                        p->d_state.get(), B, H, Bp, static_cast<const int*>(nullptr));
-    if ((rc = seg_launch_check("seg_state_init_kernel")) != 0) return rc;
-    for (int l = 0; l < 2; ++l) {
-        const hssfsst_segmenter::Layer& L = p->layer[l];
-        hssfsst::SegProjArgs pa{};
-        pa.x = l ? static_cast<const void*>(p->d_y1.get()) : feats;
-        pa.x_dtype = l ? HSSFSST_DTYPE_F32 : feats_dtype;
-        pa.relu = l;
-        pa.B = B; pa.T = T; pa.F = L.F; pa.Fp = L.Fp;
-        pa.wt = L.d_wt.get(); pa.bias = L.d_bias.get(); pa.pre = p->d_pre.get(); pa.Tc = Tc;
-        hssfsst::SegRecArgs ra{};
-        ra.pre = p->d_pre.get(); ra.whh = L.d_whh.get(); ra.state = p->d_state.get();
-        ra.y = l ? p->d_y2.get() : p->d_y1.get();
-        ra.B = B; ra.T = T; ra.H = H; ra.Bp = Bp; ra.Tc = Tc; ra.inv_scale = L.inv_scale;
-        // the forward direction takes its chunks upwards, the reverse direction the mirrored ones downwards: both walk n steps per launch
-        for (int t0 = 0; t0 < T; t0 += Tc) {
-            const int n = std::min(Tc, T - t0);
-            pa.n = ra.n = n;
-            pa.t0[0] = ra.t0[0] = t0;
-            pa.t0[1] = ra.t0[1] = T - t0 - n;
-            hipLaunchKernelGGL(hssfsst::seg_proj_kernel<false>, dim3(4 * hssfsst::kSegHp / 64, static_cast<unsigned>(nbt * ((n + 7) / 8)), 2), dim3(256), 0, st, pa);
-            if ((rc = seg_launch_check("seg_proj_kernel")) != 0) return rc;
-            hipLaunchKernelGGL(hssfsst::seg_rec_kernel<false>, dim3(static_cast<unsigned>(nbt), 2), dim3(64 * hssfsst::kSegWaves), 0, st, ra);
-            if ((rc = seg_launch_check("seg_rec_kernel")) != 0) return rc;
-        }
-    }
+    if ((rc = launch_check("segmenter_exec", "seg_state_init_kernel")) != 0) return rc;
+    hssfsst::SegProjArgs pa{};
+    pa.B = B; pa.T = T;
+    hssfsst::SegRecArgs ra{};
+    ra.B = B; ra.T = T; ra.Bp = Bp;
+    if ((rc = seg_run_layers<false>(p, st, feats, feats_dtype, pa, ra, chunks)) != 0) return rc;
     const long long rows = static_cast<long long>(B) * T;
     hipLaunchKernelGGL(hssfsst::seg_head_kernel, dim3(static_cast<unsigned>((rows + 3) / 4)), dim3(256), 0, st, p->d_y2.get(), p->d_lin.get(),
                        p->d_lin.get() + static_cast<size_t>(8) * H, logp, rows, 2 * H);
-    return seg_launch_check("seg_head_kernel");
+    return launch_check("segmenter_exec", "seg_head_kernel");
 }
 
 int hssfsst_segmenter_exec_ragged(hssfsst_segmenter* p, const void* feats, int feats_dtype, const int64_t* offsets, int64_t count,
@@ -2661,8 +2723,7 @@ int hssfsst_segmenter_exec_ragged(hssfsst_segmenter* p, const void* feats, int f
         return fail(HSSFSST_EINVAL, "segmenter_exec_ragged: %lld steps in all, over the limit of 2^31 - 1", static_cast<long long>(offsets[count]));
     if (state_rows != 1 && state_rows != count)
         return fail(HSSFSST_EINVAL, "segmenter_exec_ragged: state_rows %d is neither 1 nor count %lld", state_rows, static_cast<long long>(count));
-    if (feats_dtype != HSSFSST_DTYPE_F32 && feats_dtype != HSSFSST_DTYPE_F16 && feats_dtype != HSSFSST_DTYPE_BF16)
-        return fail(HSSFSST_EINVAL, "segmenter_exec_ragged: unknown feature dtype %d", feats_dtype);
+    if (int rc = seg_check_dtype("segmenter_exec_ragged", feats_dtype)) return rc;
     if (!p || !feats || !h0 || !c0 || !logp)
         return fail(HSSFSST_EINVAL, "segmenter_exec_ragged: bad argument (%s is NULL)",
                     !p ? "plan" : !feats ? "feats" : !h0 ? "h0" : !c0 ? "c0" : "logp");
@@ -2671,88 +2732,47 @@ int hssfsst_segmenter_exec_ragged(hssfsst_segmenter* p, const void* feats, int f
     const int H = p->H;
     int rc;
 
-    // the tables (kept while the offsets stay the same)
-    const bool same = p->d_tab.get() != nullptr && p->tab_key.size() == static_cast<size_t>(count + 1) &&
-                      std::equal(p->tab_key.begin(), p->tab_key.end(), offsets);
-    try {
-        if (!same) {
-            p->tab_key.clear();
-            seglayout::build(offsets, count, p->lay);
-        }
-    } catch (const std::bad_alloc&) {
-        return fail(HSSFSST_ENOMEM, "segmenter_exec_ragged: out of host memory");
-    }
-    const seglayout::Layout& lay = p->lay;
-    const size_t slots = static_cast<size_t>(lay.slots()), tiles = static_cast<size_t>(lay.tiles());
+    // the tables (kept while the offsets stay the same): their sizes follow from count alone
+    const size_t tiles = static_cast<size_t>((count + seglayout::kSlotRows - 1) / seglayout::kSlotRows), slots = tiles * seglayout::kSlotRows;
     const size_t o_len = slots * sizeof(long long), o_rec = o_len + slots * sizeof(int), o_walk = o_rec + slots * sizeof(int);
-    const size_t tab_bytes = o_walk + tiles * sizeof(int);
-    if (!same) {
-        if (p->tab_ev) HIP_TRY(hipEventSynchronize(p->tab_ev));          // (the previous upload may still read h_tab)
-        if ((rc = p->h_tab.grow(tab_bytes, 1)) != 0) return rc;
-        std::memcpy(p->h_tab.h, lay.slot_off.data(), o_len);
-        std::memcpy(p->h_tab.h + o_len, lay.slot_len.data(), slots * sizeof(int));
-        std::memcpy(p->h_tab.h + o_rec, lay.slot_rec.data(), slots * sizeof(int));
-        std::memcpy(p->h_tab.h + o_walk, lay.tile_walk.data(), tiles * sizeof(int));
-        if ((rc = p->d_tab.grow(tab_bytes)) != 0) return rc;
-        if (!p->tab_ev) HIP_TRY(hipEventCreateWithFlags(&p->tab_ev, hipEventDisableTiming));
-        HIP_TRY(hipMemcpyAsync(p->d_tab.get(), p->h_tab.h, tab_bytes, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipEventRecord(p->tab_ev, st));
-        try {
-            p->tab_key.assign(offsets, offsets + count + 1);
-        } catch (const std::bad_alloc&) {
-            return fail(HSSFSST_ENOMEM, "segmenter_exec_ragged: out of host memory");
-        }
-    }
-    const auto* d_off = reinterpret_cast<const long long*>(p->d_tab.get());
-    const int* d_len = reinterpret_cast<const int*>(p->d_tab.get() + o_len);
-    const int* d_rec = reinterpret_cast<const int*>(p->d_tab.get() + o_rec);
-    const int* d_walk = reinterpret_cast<const int*>(p->d_tab.get() + o_walk);
-
-    const size_t tile_step_bytes = static_cast<size_t>(2) * hssfsst::kSegGateTiles * hssfsst::kSegTileFloats * sizeof(float);
-    std::vector<SegRaggedChunk> chunks;
+    const seglayout::Layout& lay = p->lay;
+    auto key = [&](size_t i) { return offsets[i]; };
+    std::vector<seglayout::Chunk> chunks;
     try {
+        if (!p->tab.same(static_cast<size_t>(count + 1), key)) {
+            unsigned char* h = nullptr;
+            if ((rc = p->tab.begin(o_walk + tiles * sizeof(int), &h)) != 0) return rc;
+            seglayout::build(offsets, count, p->lay);
+            std::memcpy(h, lay.slot_off.data(), o_len);
+            std::memcpy(h + o_len, lay.slot_len.data(), slots * sizeof(int));
+            std::memcpy(h + o_rec, lay.slot_rec.data(), slots * sizeof(int));
+            std::memcpy(h + o_walk, lay.tile_walk.data(), tiles * sizeof(int));
+            if ((rc = p->tab.commit(st, static_cast<size_t>(count + 1), key)) != 0) return rc;
+        }
         const int mib = debug_switches().seg_ragged_pre_mib;          // (A-B switch of tools/segmenter_ragged_bench.py: same bits)
-        chunks = seg_ragged_chunks(lay, tile_step_bytes, mib > 0 ? static_cast<size_t>(mib) << 20 : kSegPreBytes);
+        chunks = seglayout::ragged_chunks(lay, kSegTileStepBytes, mib > 0 ? static_cast<size_t>(mib) << 20 : seglayout::kSegPreBytes);
     } catch (const std::bad_alloc&) {
         return fail(HSSFSST_ENOMEM, "segmenter_exec_ragged: out of host memory");
     }
-    size_t pre_floats = 0;
-    for (const SegRaggedChunk& c : chunks) pre_floats = std::max(pre_floats, tile_step_bytes / sizeof(float) * c.tiles * c.Tc);
-    if ((rc = p->d_pre.grow(pre_floats)) != 0) return rc;
-    const size_t ylen = static_cast<size_t>(lay.total) * 2 * H;
-    if ((rc = p->d_y1.grow(ylen)) != 0) return rc;
-    if ((rc = p->d_y2.grow(ylen)) != 0) return rc;
-    const size_t nstate = static_cast<size_t>(4) * slots * hssfsst::kSegHp;
-    if ((rc = p->d_state.grow(nstate)) != 0) return rc;
+    const auto* d_off = reinterpret_cast<const long long*>(p->tab.get());
+    const int* d_len = reinterpret_cast<const int*>(p->tab.get() + o_len);
+    const int* d_rec = reinterpret_cast<const int*>(p->tab.get() + o_rec);
+    const int* d_walk = reinterpret_cast<const int*>(p->tab.get() + o_walk);
+
+    const size_t ylen = static_cast<size_t>(lay.total) * 2 * H, nstate = static_cast<size_t>(4) * slots * hssfsst::kSegHp;
+    if ((rc = seg_grow_scratch(p, seglayout::pre_floats(chunks, kSegTileStepBytes), ylen, ylen, nstate)) != 0) return rc;
     hipLaunchKernelGGL(hssfsst::seg_state_init_kernel<true>, dim3(static_cast<unsigned>((nstate + 255) / 256)), dim3(256), 0, st, h0, c0,
                        p->d_state.get(), state_rows, H, static_cast<int>(slots), d_rec);
-    if ((rc = seg_launch_check("seg_state_init_kernel<ragged>")) != 0) return rc;
-    for (int l = 0; l < 2; ++l) {
-        const hssfsst_segmenter::Layer& L = p->layer[l];
-        hssfsst::SegProjArgs pa{};
-        pa.x = l ? static_cast<const void*>(p->d_y1.get()) : feats;
-        pa.x_dtype = l ? HSSFSST_DTYPE_F32 : feats_dtype;
-        pa.relu = l;
-        pa.F = L.F; pa.Fp = L.Fp;
-        pa.wt = L.d_wt.get(); pa.bias = L.d_bias.get(); pa.pre = p->d_pre.get();
-        pa.slot_off = d_off; pa.slot_len = d_len; pa.tile_walk = d_walk;
-        hssfsst::SegRecArgs ra{};
-        ra.pre = p->d_pre.get(); ra.whh = L.d_whh.get(); ra.state = p->d_state.get();
-        ra.y = l ? p->d_y2.get() : p->d_y1.get();
-        ra.H = H; ra.Bp = static_cast<int>(slots); ra.inv_scale = L.inv_scale;
-        ra.slot_off = d_off; ra.slot_len = d_len; ra.tile_walk = d_walk;
-        for (const SegRaggedChunk& c : chunks) {
-            pa.n = c.n; pa.Tc = ra.Tc = c.Tc; pa.s0 = ra.s0 = c.s0;
-            hipLaunchKernelGGL(hssfsst::seg_proj_kernel<true>, dim3(4 * hssfsst::kSegHp / 64, static_cast<unsigned>(c.tiles * ((c.n + 7) / 8)), 2),
-                               dim3(256), 0, st, pa);
-            if ((rc = seg_launch_check("seg_proj_kernel<ragged>")) != 0) return rc;
-            hipLaunchKernelGGL(hssfsst::seg_rec_kernel<true>, dim3(static_cast<unsigned>(c.tiles), 2), dim3(64 * hssfsst::kSegWaves), 0, st, ra);
-            if ((rc = seg_launch_check("seg_rec_kernel<ragged>")) != 0) return rc;
-        }
-    }
+    if ((rc = launch_check("segmenter_exec", "seg_state_init_kernel<ragged>")) != 0) return rc;
+    hssfsst::SegProjArgs pa{};
+    pa.slot_off = d_off; pa.slot_len = d_len; pa.tile_walk = d_walk;
+    hssfsst::SegRecArgs ra{};
+    ra.Bp = static_cast<int>(slots);
+    ra.slot_off = d_off; ra.slot_len = d_len; ra.tile_walk = d_walk;
+    if ((rc = seg_run_layers<true>(p, st, feats, feats_dtype, pa, ra, chunks)) != 0) return rc;
     hipLaunchKernelGGL(hssfsst::seg_head_kernel, dim3(static_cast<unsigned>((lay.total + 3) / 4)), dim3(256), 0, st, p->d_y2.get(), p->d_lin.get(),
                        p->d_lin.get() + static_cast<size_t>(8) * H, logp, lay.total, 2 * H);
-    return seg_launch_check("seg_head_kernel");
+    return launch_check("segmenter_exec", "seg_head_kernel");
 }
 
 }  // extern "C"

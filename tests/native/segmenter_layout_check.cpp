@@ -1,7 +1,9 @@
-// Stand-alone check of the ragged segmenter's slot / tile layout builder (csrc/segmenter_layout.hpp: host only, no HIP), built with
-// -fsanitize=address,undefined by tests/test_segmenter_ragged.py.  Any failed property or sanitizer report ends the run non-zero.
+// Stand-alone check of the ragged segmenter's slot / tile layout builder and of the segmenter's launch lists
+// (csrc/segmenter_layout.hpp: host only, no HIP), built with -fsanitize=address,undefined by tests/test_segmenter_ragged.py.
+// Any failed property or sanitizer report ends the run non-zero.
 #include "segmenter_layout.hpp"
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
@@ -58,6 +60,64 @@ static void run_case(const char* name, const std::vector<int>& lens)
     std::printf("%-8s %5lld recordings, %3d tiles, wasted share %.4f\n", name, static_cast<long long>(count), lay.tiles(), w);
 }
 
+// what every launch list promises: steps 0 .. walk once and in order; n <= Tc <= kSegMaxChunk; the projection scratch of a launch
+// within pre_bytes unless it is down to one step
+static void check_chunks(const char* name, const std::vector<sl::Chunk>& chunks, int walk, size_t tile_step_bytes, size_t pre_bytes)
+{
+    int next = 0;
+    for (const sl::Chunk& c : chunks) {
+        CHECK(c.s0 == next && c.n >= 1, "chunk starts at step %d with %d steps, expected step %d", c.s0, c.n, next);
+        CHECK(c.n <= c.Tc && c.Tc <= sl::kSegMaxChunk, "chunk at step %d: n %d, Tc %d", c.s0, c.n, c.Tc);
+        CHECK(c.tiles >= 1, "chunk at step %d has %d tiles", c.s0, c.tiles);
+        CHECK(c.Tc == 1 || static_cast<size_t>(c.tiles) * c.Tc * tile_step_bytes <= pre_bytes, "chunk at step %d: %d tiles x %d steps exceed %zu bytes",
+              c.s0, c.tiles, c.Tc, pre_bytes);
+        next = c.s0 + c.n;
+    }
+    CHECK(next == walk, "chunks end at step %d of %d", next, walk);
+}
+
+// the dense exec's chunk loop as it stood inline in hssfsst_segmenter_exec before the list was a function
+static std::vector<sl::Chunk> inline_dense_loop(int T, int nbt, size_t tile_step_bytes)
+{
+    const size_t step_bytes = tile_step_bytes * nbt;
+    int Tc = static_cast<int>(std::max<size_t>(1, sl::kSegPreBytes / step_bytes));
+    Tc = std::min(std::min(Tc, sl::kSegMaxChunk), T);
+    std::vector<sl::Chunk> out;
+    for (int t0 = 0; t0 < T; t0 += Tc) out.push_back({t0, std::min(Tc, T - t0), nbt, Tc});
+    return out;
+}
+
+static void run_dense(int T, int nbt, size_t tile_step_bytes)
+{
+    char name[64];
+    std::snprintf(name, sizeof(name), "dense T=%d nbt=%d", T, nbt);
+    const std::vector<sl::Chunk> got = sl::dense_chunks(T, nbt, tile_step_bytes, sl::kSegPreBytes), want = inline_dense_loop(T, nbt, tile_step_bytes);
+    check_chunks(name, got, T, tile_step_bytes, sl::kSegPreBytes);
+    CHECK(got.size() == want.size(), "%zu chunks, the inline loop made %zu", got.size(), want.size());
+    for (size_t i = 0; i < got.size() && i < want.size(); ++i)
+        CHECK(got[i].s0 == want[i].s0 && got[i].n == want[i].n && got[i].tiles == want[i].tiles && got[i].Tc == want[i].Tc,
+              "chunk %zu: {%d, %d, %d, %d}, the inline loop made {%d, %d, %d, %d}", i, got[i].s0, got[i].n, got[i].tiles, got[i].Tc,
+              want[i].s0, want[i].n, want[i].tiles, want[i].Tc);
+    for (const sl::Chunk& c : got) CHECK(c.tiles == nbt, "a dense launch of %d of %d tiles", c.tiles, nbt);
+    std::printf("%-24s %zu launches per layer\n", name, got.size());
+}
+
+static void run_ragged(const char* name, const std::vector<int>& lens, size_t tile_step_bytes, size_t pre_bytes)
+{
+    std::vector<int64_t> offsets(lens.size() + 1, 0);
+    for (size_t i = 0; i < lens.size(); ++i) offsets[i + 1] = offsets[i] + lens[i];
+    sl::Layout lay;
+    sl::build(offsets.data(), static_cast<int64_t>(lens.size()), lay);
+    const std::vector<sl::Chunk> chunks = sl::ragged_chunks(lay, tile_step_bytes, pre_bytes);
+    check_chunks(name, chunks, lay.tile_walk[0], tile_step_bytes, pre_bytes);
+    for (const sl::Chunk& c : chunks) {                              // the launch's tiles: exactly those still walking at its first step
+        int live = 0;
+        for (int w : lay.tile_walk) live += w > c.s0 ? 1 : 0;
+        CHECK(c.tiles == live, "chunk at step %d takes %d tiles, %d still walk", c.s0, c.tiles, live);
+    }
+    std::printf("%-24s %zu launches per layer\n", name, chunks.size());
+}
+
 int main()
 {
     run_case("one", {1});
@@ -72,6 +132,24 @@ int main()
     }
     run_case("random1k", many);
     run_case("three", {5, 5, 5});
+
+    // the launch lists: tile_step = 128 KiB is the library's (2 directions x 64 gate tiles x 256 floats), the small one reaches kSegMaxChunk
+    const size_t tile_step = size_t(2) * 64 * 256 * sizeof(float);
+    run_dense(1, 1, tile_step);
+    run_dense(70, 2, tile_step);
+    run_dense(1024, 1, tile_step);
+    run_dense(1025, 1, tile_step);
+    run_dense(5000, 3, tile_step);
+    run_dense(9, 2000, tile_step);                                   // more tiles than steps fit: one step per launch
+    run_dense(10000, 1, 1024);
+    run_dense(4096, 1, 1024);
+    run_dense(4097, 2, 1024);
+    run_ragged("ragged seventeen 1MiB", {9, 8, 7, 6, 5, 4, 3, 2, 1, 10, 11, 12, 13, 14, 15, 16, 17}, tile_step, size_t(1) << 20);
+    run_ragged("ragged seventeen", {9, 8, 7, 6, 5, 4, 3, 2, 1, 10, 11, 12, 13, 14, 15, 16, 17}, tile_step, sl::kSegPreBytes);
+    run_ragged("ragged mixed19 1MiB", {1, 2, 15, 16, 17, 40, 333, 1100, 5, 16, 31, 64, 7, 7, 250, 3, 1, 90, 600}, tile_step, size_t(1) << 20);
+    run_ragged("ragged random1k", many, tile_step, sl::kSegPreBytes);
+    run_ragged("ragged random1k small", many, 1024, sl::kSegPreBytes);
+    run_ragged("ragged one", {1}, tile_step, size_t(1) << 16);       // the bound below one step of one tile: Tc = 1
 
     // what the entry point refuses, and at which index
     const char* name = "bad";

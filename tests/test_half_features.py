@@ -176,6 +176,13 @@ def test_other_windows_and_bands(dt):
     for w, band in cases:
         f32, fh = pair(band, 1000, w, dt)
         assert same_as_cast(fh.batch(X), f32.batch(X), dt), (len(w), band, fh.last_kernel())
+    # the element-by-element path of the sweep: an odd band and an odd n, 129 * 42 elements per signal, not a multiple of 4
+    f32, fh = pair((25, 190), 1000, W128, dt)
+    assert fh.band()[1] % 2 == 1
+    f32.set_zpath("two_launch")
+    fh.set_zpath("two_launch")
+    X = torch.from_numpy(synth.pcg_windows(3, 129, seed=22)).to(DEV)
+    assert same_as_cast(fh.batch(X), f32.batch(X), dt), fh.last_kernel()
 
 
 @pytest.mark.gpu
@@ -214,13 +221,20 @@ def test_frames_list_and_column_ranges(dt):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("dt", HALF)
-@pytest.mark.parametrize("nwin", [128, 64, 100])
-def test_ragged_mixed_lengths(dt, nwin):
+@pytest.mark.parametrize("nwin,band,lens", [pytest.param(128, (25, 200), (1, 127, 2000, 35500, 60001), id="128"),
+                                           pytest.param(64, (25, 200), (1, 127, 2000, 35500, 60001), id="64"),
+                                           pytest.param(100, (25, 200), (1, 127, 2000, 35500, 60001), id="100"),
+                                           pytest.param(128, (25, 190), (1, 3, 17, 130), id="128-odd-band")])
+def test_ragged_mixed_lengths(dt, nwin, band, lens):
     """nwin 128: one ragged launch (MFMA kernels); nwin 64 and the any-length kernel (100): one exec per recording inside the
-    library, each writing at its own element offset of the half arena."""
+    library, each writing at its own element offset of the half arena.  The odd band (21 rows, 42 elements per sample): the second
+    and later signals start 2 elements into a 4-element group, so the sweep's head, tail and wrap code runs; and once more into an
+    out= that is not 8-byte aligned."""
     w = W128 if nwin == 128 else synth.kaiser_window(64, 0.5) if nwin == 64 else np.hanning(100)
-    f32, fh = pair(w=w, dt=dt)
-    lens = (1, 127, 2000, 35500, 60001)
+    f32, fh = pair(band=band, w=w, dt=dt)
+    odd = band == (25, 190)
+    if odd:
+        assert fh.band()[1] % 2 == 1
     xs = [torch.from_numpy(synth.recording(T, seed=50 + i)) for i, T in enumerate(lens)]
     for src in (xs, [t.to(DEV) for t in xs]):
         a, b = f32.ragged(src), fh.ragged(src)
@@ -229,6 +243,18 @@ def test_ragged_mixed_lengths(dt, nwin):
             assert same_as_cast(b[i], a[i], dt), (nwin, i)
         pa, pb = a.padded(), b.padded()
         assert pb.dtype == dt and same_as_cast(pb, pa, dt)
+    if odd:
+        dev = [t.to(DEV) for t in xs]
+        r32 = f32.ragged(dev)
+        for i, x in enumerate(dev):                                                  # float32: each signal alone
+            assert torch.equal(r32[i].view(torch.int32), f32.batch(x.reshape(1, -1))[0].view(torch.int32)), i
+        C, n, canary = 2 * fh.band()[1], sum(lens) * 2 * fh.band()[1], 4096
+        buf = torch.full((1 + n + canary,), 1234.0, dtype=dt, device=DEV)
+        out = buf[1:1 + n].view(-1, C)
+        assert out.data_ptr() % 8 != 0
+        fh.ragged(dev, out=out)
+        assert same_as_cast(out, r32.data, dt)
+        assert bool((buf[:1] == 1234.0).all()) and bool((buf[1 + n:] == 1234.0).all())     # (compared in dt: bfloat16 holds 1234 as 1232)
 
 
 @pytest.mark.gpu

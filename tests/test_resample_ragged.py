@@ -247,6 +247,22 @@ def test_bitwise_determinism():
 
 
 @pytest.mark.gpu
+def test_return_to_an_earlier_list():
+    """Lists A, A, B, A on one plan: B has A's count and total but other lengths, so the descriptors keep their size.  Every
+    row equals the signal resampled alone."""
+    t = Resample(50)
+    a = [x.to(DEV) for x in signals([3, 64, 65], 12)]
+    b = [a[2], a[0], a[1]]
+    alone = {id(x): t.ragged([x], dtype=torch.float64)[0] for x in a}
+    for step, xs in enumerate((a, a, b, a)):
+        got = t.ragged(xs, dtype=torch.float64)
+        assert got.shape == (3, 50)
+        for i, x in enumerate(xs):
+            assert same_bits(got[i], alone[id(x)]), (step, i, x.shape[0])
+    assert len([k for k in t._plans if k[0] == "ragged"]) == 1
+
+
+@pytest.mark.gpu
 def test_labels_follow_the_rule():
     lens = [2000, 35500, 4097, 60001, 129, 35500, 2500]
     ys = label_tracks(lens, 21)

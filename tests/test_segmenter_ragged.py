@@ -88,7 +88,9 @@ def test_python_surface_exists():
 def test_layout_builder_under_sanitizers(tmp_path):
     """csrc/segmenter_layout.hpp alone, in a program of its own (tests/native/segmenter_layout_check.cpp) built with
     -fsanitize=address,undefined: lengths [1], 16 equal, 17, the 19 mixed ones, 1 000 pseudo-random; every recording in exactly one
-    slot, padding slots of length 0, non-increasing slot lengths, each tile's walk its maximum, offsets round-trip."""
+    slot, padding slots of length 0, non-increasing slot lengths, each tile's walk its maximum, offsets round-trip.
+    The launch lists of both execs too: steps covered once and in order, n <= Tc <= kSegMaxChunk, the projection scratch within its
+    bound, a launch's tiles those still walking, and the dense list equal to the loop that used to stand inline in the exec."""
     cxx = shutil.which("g++")
     if cxx is None:
         pytest.skip("no g++")
@@ -129,6 +131,22 @@ def test_bit_identity_with_the_per_recording_call(mixed):
         assert torch.equal(rev[len(LENS) - 1 - i], want[i]), (i, LENS[i])
     again = seg.ragged(xs)
     assert torch.equal(again.data, out.data)
+
+
+@pytest.mark.gpu
+def test_return_to_an_earlier_list():
+    """Lists A, A, B, A on one plan: 17 recordings of 1 .. 17 steps and the same reversed -- the same count and total, so the
+    tables keep their size; two tiles, one of them nearly all padding.  Every call equals the per-recording dense call."""
+    head = seeded_head(17, 12, 7, seed=5)
+    seg = head.hip()
+    g = torch.Generator().manual_seed(6)
+    a = [torch.randn(T, 7, generator=g).cuda() for T in range(1, 18)]
+    h0, c0 = seg.h0, seg.c0
+    want = [seg(x[None], h0=h0[:, i:i + 1], c0=c0[:, i:i + 1])[0] for i, x in enumerate(a)]
+    for step, rev in enumerate((False, False, True, False)):
+        out = seg.ragged(a[::-1], h0=h0.flip(1), c0=c0.flip(1)) if rev else seg.ragged(a)
+        for i in range(17):
+            assert torch.equal(out[16 - i if rev else i], want[i]), (step, i)
 
 
 @pytest.mark.gpu
