@@ -24,6 +24,8 @@
 //                           (resample_dif_pass_kernel / resample_dit_pass_kernel, one thread per butterfly over all signals
 //                           of the chunk), the remaining log2(kRsBlock) stages on each side and the pointwise product as ONE
 //                           launch of resample_block_kernel per convolution (contiguous kRsBlock-point blocks in LDS).
+//                           Its steps are templates over the launch's signals: this file's ResampleArgs (a plan's n and tables) or
+//                           fourier_resample_ragged.hpp's RaggedResampleArgs (a list of lengths, one descriptor per signal).
 // A NaN anywhere in a signal reaches every butterfly of the first FFT and so every output sample, as on the host.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -47,6 +49,22 @@ struct ResampleArgs {
     void* y;                         // [batch][num] float32 / float64, or null
     long long* labels;               // [batch][num] int64, or null
     long long b0;                    // first signal of this launch (large tier: chunks of the batch)
+
+    // The signals of a launch as every step sees them: what is asked about signal b, here answered from the plan's host-made
+    // tables (RaggedResampleArgs, fourier_resample_ragged.hpp: from a list's descriptors).  Both have x, y, labels, num,
+    // num_even, M2, c2 and the dtypes as members.
+    __device__ __forceinline__ long long signal(long long d) const { return b0 + d; }          // b of the launch's d-th signal
+    __device__ __forceinline__ long long start(long long b) const { return starts ? starts[b] : b * x_stride; }
+    __device__ __forceinline__ long long len(long long) const { return n; }
+    __device__ __forceinline__ long long row(long long b) const { return b; }
+    __device__ __forceinline__ double scale(long long) const { return inv_n; }                 // 1 / n
+    __device__ __forceinline__ double2 conj_chirp(long long, long long m) const { return c1[m]; }
+    __device__ __forceinline__ long long kept_bins(long long) const { return nyq; }
+    __device__ __forceinline__ long long nyquist_bin(long long) const { return nyq_bin; }
+    __device__ __forceinline__ double nyquist_scale(long long) const { return nyq_scale; }
+    __device__ __forceinline__ long long mid_reads(long long) const { return M1; }             // bins the large tier's middle step reads (>= nyq)
+    // large tier: thread t of the load -> point m of the launch's d-th signal (false: none); a signal takes M1 threads
+    __device__ __forceinline__ bool load_point(long long t, long long, long long& d, long long& m) const { d = t / M1; m = t - d * M1; return true; }
 };
 
 __device__ __forceinline__ double2 rs_add(double2 a, double2 b) { return make_double2(a.x + b.x, a.y + b.y); }
@@ -54,38 +72,42 @@ __device__ __forceinline__ double2 rs_sub(double2 a, double2 b) { return make_do
 __device__ __forceinline__ double2 rs_mul(double2 a, double2 b) { return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
 __device__ __forceinline__ double2 rs_mulc(double2 a, double2 b) { return make_double2(a.x * b.x + a.y * b.y, a.y * b.x - a.x * b.y); }  // a conj(b)
 
-__device__ __forceinline__ double rs_load_x(const ResampleArgs& a, long long b, long long m)
+template <class V>
+__device__ __forceinline__ double rs_load_x(const V& a, long long b, long long m)
 {
-    const long long base = a.starts ? a.starts[b] : b * a.x_stride;
+    const long long base = a.start(b);
     return a.x_f64 ? static_cast<const double*>(a.x)[base + m] : static_cast<double>(static_cast<const float*>(a.x)[base + m]);
 }
 
 // first convolution's input: the chirp-weighted signal, zero above n
-__device__ __forceinline__ double2 rs_conv1_in(const ResampleArgs& a, long long b, long long m)
+template <class V>
+__device__ __forceinline__ double2 rs_conv1_in(const V& a, long long b, long long m)
 {
-    if (m >= a.n) return make_double2(0.0, 0.0);
+    if (m >= a.len(b)) return make_double2(0.0, 0.0);
     const double v = rs_load_x(a, b, m);
-    const double2 c = a.c1[m];
+    const double2 c = a.conj_chirp(b, m);
     return make_double2(v * c.x, v * c.y);
 }
 
 // between the convolutions: bin k of the forward DFT -> the kept half spectrum Y' -> the second convolution's input
-__device__ __forceinline__ double2 rs_mid(const ResampleArgs& a, double2 conv, long long k)
+template <class V>
+__device__ __forceinline__ double2 rs_mid(const V& a, long long b, double2 conv, long long k)
 {
-    if (k >= a.nyq) return make_double2(0.0, 0.0);
-    double2 X = rs_mul(conv, a.c1[k]);
-    if (k == a.nyq_bin) { X.x *= a.nyq_scale; X.y *= a.nyq_scale; }
+    if (k >= a.kept_bins(b)) return make_double2(0.0, 0.0);
+    double2 X = rs_mul(conv, a.conj_chirp(b, k));
+    if (k == a.nyquist_bin(b)) { const double sc = a.nyquist_scale(b); X.x *= sc; X.y *= sc; }
     if (k == 0 || (a.num_even && 2 * k == a.num)) X = make_double2(X.x, 0.0);
     else { X.x *= 2.0; X.y *= 2.0; }
     return rs_mul(X, a.c2[k]);
 }
 
 // last step: sample i of signal b
-__device__ __forceinline__ void rs_store(const ResampleArgs& a, double2 conv, long long b, long long i)
+template <class V>
+__device__ __forceinline__ void rs_store(const V& a, long long b, double2 conv, long long i)
 {
     const double2 c = a.c2[i];
-    const double v = (conv.x * c.x - conv.y * c.y) * a.inv_n;
-    const long long o = b * a.num + i;
+    const double v = (conv.x * c.x - conv.y * c.y) * a.scale(b);
+    const long long o = a.row(b) * a.num + i;
     if (a.y) {
         if (a.y_f64) static_cast<double*>(a.y)[o] = v;
         else static_cast<float*>(a.y)[o] = static_cast<float>(v);
@@ -160,38 +182,43 @@ __global__ __launch_bounds__(kRsThreads) void resample_lds_kernel(ResampleArgs a
     __syncthreads();
     rs_lds_conv(rs_lds, a.M1, a.B1, a.tw, a.Mt);
     // each thread reads and writes only its own indices: no barrier inside
-    for (int k = threadIdx.x; k < a.M2; k += blockDim.x) rs_lds[k] = rs_mid(a, k < a.M1 ? rs_lds[k] : make_double2(0.0, 0.0), k);
+    for (int k = threadIdx.x; k < a.M2; k += blockDim.x) rs_lds[k] = rs_mid(a, b, k < a.M1 ? rs_lds[k] : make_double2(0.0, 0.0), k);
     __syncthreads();
     rs_lds_conv(rs_lds, a.M2, a.B2, a.tw, a.Mt);
-    for (int i = threadIdx.x; i < a.num; i += blockDim.x) rs_store(a, rs_lds[i], b, i);
+    for (int i = threadIdx.x; i < a.num; i += blockDim.x) rs_store(a, b, rs_lds[i], i);
 }
 
 // ---------------------------------------------------------------------------------------------------- large tier
-// work: [chunk][Mw] complex doubles, signal b of the chunk at work + b * Mw.
+// work: [chunk][Mw] complex doubles, signal d of the chunk at work + d * Mw.  V: the chunk's signals (ResampleArgs, RaggedResampleArgs).
 
-__global__ __launch_bounds__(kRsThreads) void resample_load_kernel(ResampleArgs a, double2* work, long long Mw, long long total)
+template <class V>
+__global__ __launch_bounds__(kRsThreads) void resample_load_kernel(V a, double2* work, long long Mw, long long total)
 {
     const long long t = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
     if (t >= total) return;
-    const long long b = t / a.M1, m = t - b * a.M1;
-    work[b * Mw + m] = rs_conv1_in(a, a.b0 + b, m);
+    long long d, m;
+    if (!a.load_point(t, Mw, d, m)) return;
+    work[d * Mw + m] = rs_conv1_in(a, a.signal(d), m);
 }
 
-__global__ __launch_bounds__(kRsThreads) void resample_mid_kernel(ResampleArgs a, double2* work, long long Mw, long long total)
+template <class V>
+__global__ __launch_bounds__(kRsThreads) void resample_mid_kernel(V a, double2* work, long long Mw, long long total)
 {
     const long long t = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
     if (t >= total) return;
-    const long long b = t / a.M2, k = t - b * a.M2;
-    double2* w = work + b * Mw;
-    w[k] = rs_mid(a, k < a.M1 ? w[k] : make_double2(0.0, 0.0), k);
+    const long long M2 = a.M2, d = t / M2, k = t - d * M2;
+    double2* w = work + d * Mw;
+    const long long b = a.signal(d);
+    w[k] = rs_mid(a, b, k < a.mid_reads(b) ? w[k] : make_double2(0.0, 0.0), k);
 }
 
-__global__ __launch_bounds__(kRsThreads) void resample_store_kernel(ResampleArgs a, const double2* work, long long Mw, long long total)
+template <class V>
+__global__ __launch_bounds__(kRsThreads) void resample_store_kernel(V a, const double2* work, long long Mw, long long total)
 {
     const long long t = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
     if (t >= total) return;
-    const long long b = t / a.num, i = t - b * a.num;
-    rs_store(a, work[b * Mw + i], a.b0 + b, i);
+    const long long d = t / a.num, i = t - d * a.num;
+    rs_store(a, a.signal(d), work[d * Mw + i], i);
 }
 
 // one DIF stage of length len over convolutions of M points; total = chunk * M / 2 butterflies
@@ -221,10 +248,16 @@ __global__ __launch_bounds__(kRsThreads) void resample_dit_pass_kernel(double2* 
     w[i + half] = rs_sub(u, v);
 }
 
+// BS, where the kernel B (bit-reversed spectrum / M) of signal b of a launch is: RsSharedB, one B for every signal (a plan's B1 or
+// B2), or fourier_resample_ragged.hpp's RsRaggedB, each signal's own table
+using RsSharedB = const double2* __restrict__;
+__device__ __forceinline__ const double2* rs_kernel_of(RsSharedB B, long long) { return B; }
+
 // the in-LDS middle of a convolution of M points: blocks of S = min(M, kRsBlock) contiguous points, blockIdx.x =
 // signal * (M / S) + block
-__global__ __launch_bounds__(kRsThreads) void resample_block_kernel(double2* work, long long Mw, int M, int S,
-                                                                   const double2* __restrict__ B, const double2* __restrict__ tw, int Mt)
+template <class BS>
+__global__ __launch_bounds__(kRsThreads) void resample_block_kernel(double2* work, long long Mw, int M, int S, BS B,
+                                                                   const double2* __restrict__ tw, int Mt)
 {
     __shared__ double2 s[kRsBlock];
     const int nblk = M / S;
@@ -234,7 +267,7 @@ __global__ __launch_bounds__(kRsThreads) void resample_block_kernel(double2* wor
     for (int m = threadIdx.x; m < S; m += blockDim.x) s[m] = w[m];
     __syncthreads();
     rs_lds_dif(s, S, S, tw, Mt);
-    rs_lds_pointwise(s, S, B, g0);
+    rs_lds_pointwise(s, S, rs_kernel_of(B, b), g0);
     rs_lds_dit(s, S, S, tw, Mt);
     for (int m = threadIdx.x; m < S; m += blockDim.x) w[m] = s[m];
 }

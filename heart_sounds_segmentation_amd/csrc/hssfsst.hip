@@ -33,6 +33,7 @@
 #include "fsst_ragged.hpp"
 #include "fsst_half.hpp"
 #include "fourier_resample.hpp"
+#include "fourier_resample_layout.hpp"
 #include "fourier_resample_gpu.hpp"
 #include "fourier_resample_ragged.hpp"
 #include "segmenter_lstm.hpp"
@@ -40,6 +41,7 @@
 #include "fsst_tables.hpp"
 
 namespace tables = hssfsst::tables;
+namespace rslayout = hssfsst::rslayout;
 
 namespace {
 
@@ -1837,37 +1839,9 @@ struct hssfsst_resample_plan {
 namespace {
 
 constexpr int64_t kRsMaxLen = int64_t(1) << 26;          // n, num: convolutions of up to 2^27 points (2 GiB per signal)
-constexpr size_t kRsWorkBytes = size_t(256) << 20;       // large tier: signals per chunk bounded by this much scratch
-
-int pow2_at_least(int64_t v)
-{
-    int m = 1;
-    while (m < v) m <<= 1;
-    return m;
-}
-
-// chirp conj(w) and the bit-reversed spectrum / M of the wrapped chirp w, for a DFT of N points on M (sign: +1 forward)
-void bluestein_tables(int64_t N, int M, double sgn, hssfsst::resample_detail::cd* c, hssfsst::resample_detail::cd* B)
-{
-    using hssfsst::resample_detail::cd;
-    std::vector<cd> w(static_cast<size_t>(N)), b(static_cast<size_t>(M), cd(0.0, 0.0));
-    for (int64_t m = 0; m < N; ++m) {
-        const int64_t r = (m * m) % (2 * N);             // m^2 reduced mod 2N keeps the angle exact
-        const double ang = sgn * M_PI * static_cast<double>(r) / static_cast<double>(N);
-        w[static_cast<size_t>(m)] = cd(std::cos(ang), std::sin(ang));
-        c[m] = std::conj(w[static_cast<size_t>(m)]);
-    }
-    b[0] = w[0];
-    for (int64_t m = 1; m < N; ++m) b[static_cast<size_t>(m)] = b[static_cast<size_t>(M - m)] = w[static_cast<size_t>(m)];
-    hssfsst::resample_detail::fft_pow2(b, false);
-    int lg = 0;
-    while ((1 << lg) < M) ++lg;
-    for (int j = 0; j < M; ++j) {
-        int r = 0;
-        for (int k = 0; k < lg; ++k) r |= ((j >> k) & 1) << (lg - 1 - k);
-        B[j] = b[static_cast<size_t>(r)] / static_cast<double>(M);
-    }
-}
+using rslayout::bluestein_tables;                        // (the resampler's host arithmetic: csrc/fourier_resample_layout.hpp)
+using rslayout::pow2_at_least;
+constexpr long long kRsWorkElems = static_cast<long long>(rslayout::kRsWorkBytes / sizeof(double2));
 
 unsigned rs_grid(long long total) { return static_cast<unsigned>((total + hssfsst::kRsThreads - 1) / hssfsst::kRsThreads); }
 
@@ -1918,36 +1892,51 @@ int rs_finish(const Args& a, void* y, size_t ysz, int64_t* labels, size_t nout, 
 }
 
 // Convolutions of M points, cnt of them at w (stride Mw), against a twiddle table of twM points: global DIF stages down to the block
-// length S, a block kernel (the caller's), global DIT stages back up
-int rs_dif(hipStream_t st, double2* w, long long Mw, long long cnt, int M, const double2* tw, int twM)
+// length S, the block kernel, global DIT stages back up.  entry: the entry point, for errors
+int rs_dif(const char* entry, hipStream_t st, double2* w, long long Mw, long long cnt, int M, const double2* tw, int twM)
 {
     const int S = M < hssfsst::kRsBlock ? M : hssfsst::kRsBlock;
     const long long nb = cnt * (M / 2);
     for (int len = M; len > S; len >>= 1) {
         hipLaunchKernelGGL(hssfsst::resample_dif_pass_kernel, dim3(rs_grid(nb)), dim3(hssfsst::kRsThreads), 0, st, w, Mw, M, len, tw, twM, nb);
-        if (int r = launch_check("resample_exec", "resample_dif_pass_kernel")) return r;
+        if (int r = launch_check(entry, "resample_dif_pass_kernel")) return r;
     }
     return 0;
 }
-int rs_dit(hipStream_t st, double2* w, long long Mw, long long cnt, int M, const double2* tw, int twM)
+int rs_dit(const char* entry, hipStream_t st, double2* w, long long Mw, long long cnt, int M, const double2* tw, int twM)
 {
     const int S = M < hssfsst::kRsBlock ? M : hssfsst::kRsBlock;
     const long long nb = cnt * (M / 2);
     for (int len = 2 * S; len <= M; len <<= 1) {
         hipLaunchKernelGGL(hssfsst::resample_dit_pass_kernel, dim3(rs_grid(nb)), dim3(hssfsst::kRsThreads), 0, st, w, Mw, M, len, tw, twM, nb);
-        if (int r = launch_check("resample_exec", "resample_dit_pass_kernel")) return r;
+        if (int r = launch_check(entry, "resample_dit_pass_kernel")) return r;
     }
     return 0;
 }
-// ... with the plain block kernel: one kernel B (bit-reversed spectrum / M) for all of them
-int rs_conv(hipStream_t st, double2* w, long long Mw, long long cnt, int M, const double2* B, const double2* tw, int twM)
+// BS: RsSharedB (named by the caller: deduction drops its __restrict__) or RsRaggedB
+template <class BS>
+int rs_conv(const char* entry, hipStream_t st, double2* w, long long Mw, long long cnt, int M, BS B, const double2* tw, int twM)
 {
     const int S = M < hssfsst::kRsBlock ? M : hssfsst::kRsBlock;
-    if (int r = rs_dif(st, w, Mw, cnt, M, tw, twM)) return r;
-    hipLaunchKernelGGL(hssfsst::resample_block_kernel, dim3(static_cast<unsigned>(cnt * (M / S))), dim3(hssfsst::kRsThreads), 0, st,
+    if (int r = rs_dif(entry, st, w, Mw, cnt, M, tw, twM)) return r;
+    hipLaunchKernelGGL(hssfsst::resample_block_kernel<BS>, dim3(static_cast<unsigned>(cnt * (M / S))), dim3(hssfsst::kRsThreads), 0, st,
                        w, Mw, M, S, B, tw, twM);
-    if (int r = launch_check("resample_exec", "resample_block_kernel")) return r;
-    return rs_dit(st, w, Mw, cnt, M, tw, twM);
+    if (int r = launch_check(entry, "resample_block_kernel")) return r;
+    return rs_dit(entry, st, w, Mw, cnt, M, tw, twM);
+}
+
+// The inverse half of a large-tier chunk, cnt signals (a: ResampleArgs or RaggedResampleArgs) whose first convolutions stand in work:
+// the half spectrum in place, the second convolution (M2 points, the plan's B2), the samples and labels
+template <class Args>
+int rs_inverse_half(const char* entry, hipStream_t st, const Args& a, double2* work, long long Mw, long long cnt, const double2* B2,
+                    const double2* tw, int twM)
+{
+    const long long t2 = cnt * a.M2, t3 = cnt * a.num;
+    hipLaunchKernelGGL(hssfsst::resample_mid_kernel<Args>, dim3(rs_grid(t2)), dim3(hssfsst::kRsThreads), 0, st, a, work, Mw, t2);
+    if (int r = launch_check(entry, "resample_mid_kernel")) return r;
+    if (int r = rs_conv<hssfsst::RsSharedB>(entry, st, work, Mw, cnt, a.M2, B2, tw, twM)) return r;
+    hipLaunchKernelGGL(hssfsst::resample_store_kernel<Args>, dim3(rs_grid(t3)), dim3(hssfsst::kRsThreads), 0, st, a, work, Mw, t3);
+    return launch_check(entry, "resample_store_kernel");
 }
 
 // The two creates behind their argument checks: the plan on `device` with its tables c1[n] | B1[M1] | c2[num] | B2[M2] | tw[Mt / 2],
@@ -1997,6 +1986,45 @@ int rs_ragged_twiddles(hssfsst_resample_plan* p, int Mt)
         return fail(HSSFSST_ENOMEM, "resample_exec_ragged: out of host memory");
     }
     p->tw_M = Mt;
+    return 0;
+}
+
+// The forward half of a ragged call's chunk (a.sig: its descriptors; tn: the call's table lengths on the device): B1 / M1 of every
+// distinct length, the chirp-weighted signals, the first convolutions -- tables and convolutions one class of equal M1 at a time
+int rs_ragged_forward_half(hssfsst_resample_plan* p, const rslayout::RaggedPlan& lay, const rslayout::Chunk& ch,
+                           const hssfsst::RaggedResampleArgs& a, const long long* tn, hipStream_t st)
+{
+    constexpr const char* kEntry = "resample_exec_ragged";
+    const double2* tw = p->d_tw.get();
+    const int twM = p->tw_M;
+    double2* work = p->d_work.get();
+    double2* tabs = work + ch.cnt * ch.Mw;
+    int rc;
+    for (long long u = ch.t0; u < ch.t0 + ch.ntab;) {
+        long long v = u;
+        const int M = static_cast<int>(lay.tabs[static_cast<size_t>(u)].M), S = M < hssfsst::kRsBlock ? M : hssfsst::kRsBlock;
+        while (v < ch.t0 + ch.ntab && lay.tabs[static_cast<size_t>(v)].M == M) ++v;
+        double2* t0 = tabs + lay.tabs[static_cast<size_t>(u)].off;
+        const long long tot = (v - u) * M;
+        hipLaunchKernelGGL(hssfsst::resample_ragged_table_kernel, dim3(rs_grid(tot)), dim3(hssfsst::kRsThreads), 0, st, t0, tn + u, M, tot);
+        if ((rc = launch_check(kEntry, "resample_ragged_table_kernel")) != 0) return rc;
+        if ((rc = rs_dif(kEntry, st, t0, M, v - u, M, tw, twM)) != 0) return rc;
+        hipLaunchKernelGGL(hssfsst::resample_ragged_table_block_kernel, dim3(static_cast<unsigned>((v - u) * (M / S))), dim3(hssfsst::kRsThreads),
+                           0, st, t0, M, S, tw, twM);
+        if ((rc = launch_check(kEntry, "resample_ragged_table_block_kernel")) != 0) return rc;
+        u = v;
+    }
+    const long long t1 = ch.cnt * ch.Mw;
+    hipLaunchKernelGGL(hssfsst::resample_load_kernel<hssfsst::RaggedResampleArgs>, dim3(rs_grid(t1)), dim3(hssfsst::kRsThreads), 0, st, a, work, ch.Mw, t1);
+    if ((rc = launch_check(kEntry, "resample_load_kernel")) != 0) return rc;
+    const hssfsst::RaggedResampleSig* sig = lay.sig.data() + ch.d0;
+    for (long long e0 = 0; e0 < ch.cnt;) {
+        long long e1 = e0;
+        const int M = static_cast<int>(sig[e0].M1);
+        while (e1 < ch.cnt && sig[e1].M1 == M) ++e1;
+        if ((rc = rs_conv(kEntry, st, work + e0 * ch.Mw, ch.Mw, e1 - e0, M, hssfsst::RsRaggedB{a.sig + e0, tabs}, tw, twM)) != 0) return rc;
+        e0 = e1;
+    }
     return 0;
 }
 
@@ -2098,22 +2126,16 @@ int hssfsst_resample_exec(hssfsst_resample_plan* p, const void* x, int x_dtype, 
         if ((rc = launch_check("resample_exec", "resample_lds_kernel")) != 0) return rc;
     } else {
         const long long Mw = p->Mt;
-        const long long per = static_cast<long long>(kRsWorkBytes / (static_cast<size_t>(Mw) * sizeof(double2)));
-        const long long chunk = per < 1 ? 1 : (per < batch ? per : batch);
+        const long long chunk = rslayout::dense_chunk(kRsWorkElems, Mw, batch);
         if ((rc = p->d_work.grow(static_cast<size_t>(chunk) * static_cast<size_t>(Mw))) != 0) return rc;
         double2* work = p->d_work.get();
         for (long long b0 = 0; b0 < batch; b0 += chunk) {
-            const long long cb = batch - b0 < chunk ? batch - b0 : chunk;
+            const long long cb = batch - b0 < chunk ? batch - b0 : chunk, t1 = cb * p->M1;
             a.b0 = b0;
-            const long long t1 = cb * p->M1, t2 = cb * p->M2, t3 = cb * num;
-            hipLaunchKernelGGL(hssfsst::resample_load_kernel, dim3(rs_grid(t1)), dim3(hssfsst::kRsThreads), 0, st, a, work, Mw, t1);
+            hipLaunchKernelGGL(hssfsst::resample_load_kernel<hssfsst::ResampleArgs>, dim3(rs_grid(t1)), dim3(hssfsst::kRsThreads), 0, st, a, work, Mw, t1);
             if ((rc = launch_check("resample_exec", "resample_load_kernel")) != 0) return rc;
-            if ((rc = rs_conv(st, work, Mw, cb, p->M1, p->B1, p->tw, p->Mt)) != 0) return rc;
-            hipLaunchKernelGGL(hssfsst::resample_mid_kernel, dim3(rs_grid(t2)), dim3(hssfsst::kRsThreads), 0, st, a, work, Mw, t2);
-            if ((rc = launch_check("resample_exec", "resample_mid_kernel")) != 0) return rc;
-            if ((rc = rs_conv(st, work, Mw, cb, p->M2, p->B2, p->tw, p->Mt)) != 0) return rc;
-            hipLaunchKernelGGL(hssfsst::resample_store_kernel, dim3(rs_grid(t3)), dim3(hssfsst::kRsThreads), 0, st, a, work, Mw, t3);
-            if ((rc = launch_check("resample_exec", "resample_store_kernel")) != 0) return rc;
+            if ((rc = rs_conv<hssfsst::RsSharedB>("resample_exec", st, work, Mw, cb, p->M1, p->B1, p->tw, p->Mt)) != 0) return rc;
+            if ((rc = rs_inverse_half("resample_exec", st, a, work, Mw, cb, p->B2, p->tw, p->Mt)) != 0) return rc;
         }
     }
     return rs_finish(a, y, ysz, labels, nout, x_on_device, out_on_device, st);
@@ -2135,7 +2157,6 @@ int hssfsst_resample_exec_ragged(hssfsst_resample_plan* p, const void* x, int x_
                                  const int64_t* lens, int64_t count, int x_on_device, void* y, int y_dtype, int64_t* labels,
                                  int out_on_device, void* stream)
 {
-    using hssfsst::RaggedResampleSig;
     if (!p || !x || !starts || !lens || (!y && !labels) || count < 0 || x_len < 0)
         return fail(HSSFSST_EINVAL, "resample_exec_ragged: bad argument (count=%lld x_len=%lld)", static_cast<long long>(count),
                     static_cast<long long>(x_len));
@@ -2163,71 +2184,19 @@ int hssfsst_resample_exec_ragged(hssfsst_resample_plan* p, const void* x, int x_
     DEVICE_SCOPE(p->device);
     const hipStream_t st = static_cast<hipStream_t>(stream);
     int rc;
-
-    // ---- the plan of the call, on the host: the list by length (a class of equal M1 is a contiguous run, equal lengths adjacent,
-    // ties in list order), cut into chunks of at most kRsWorkBytes of work and tables (at least one signal each)
-    struct Chunk { long long d0, cnt, Mw, t0, ntab, elems; };
-    std::vector<Chunk> chunks;
-    std::vector<long long> ord, tabM, tabOff, tabN;
-    std::vector<int> M1s;
-    const long long budget = static_cast<long long>(kRsWorkBytes / sizeof(double2));
-    try {
-        ord.resize(static_cast<size_t>(count));
-        for (int64_t i = 0; i < count; ++i) ord[static_cast<size_t>(i)] = i;
-        std::stable_sort(ord.begin(), ord.end(), [&](long long a, long long b) { return lens[a] < lens[b]; });
-        M1s.resize(static_cast<size_t>(count));
-        for (int64_t i = 0; i < count; ++i) M1s[static_cast<size_t>(i)] = pow2_at_least(2 * lens[ord[static_cast<size_t>(i)]] - 1);
-        Chunk c{0, 0, 0, 0, 0, 0};
-        long long tab_elems = 0;
-        for (long long d = 0; d < count; ++d) {
-            const long long n = lens[ord[static_cast<size_t>(d)]], M1 = M1s[static_cast<size_t>(d)];
-            const long long Mw = std::max<long long>(M1, M2);
-            bool fresh = c.cnt == 0 || n != lens[ord[static_cast<size_t>(d - 1)]];
-            if (c.cnt > 0 && (c.cnt + 1) * Mw + tab_elems + (fresh ? M1 : 0) > budget) {
-                c.elems = c.cnt * c.Mw + tab_elems;
-                chunks.push_back(c);
-                c = Chunk{d, 0, 0, static_cast<long long>(tabN.size()), 0, 0};
-                tab_elems = 0;
-                fresh = true;
-            }
-            if (fresh) {
-                tabN.push_back(n); tabM.push_back(M1); tabOff.push_back(tab_elems);
-                tab_elems += M1;
-                ++c.ntab;
-            }
-            ++c.cnt;
-            c.Mw = Mw;
-        }
-        c.elems = c.cnt * c.Mw + tab_elems;
-        chunks.push_back(c);
-    } catch (const std::bad_alloc&) {
+    // the call's plan (chunks, tables, descriptors), made on the host and uploaded; the twiddles and the work grown to it
+    rslayout::RaggedPlan lay;
+    if (!rslayout::plan_ragged(starts, lens, count, M2, xlo, kRsWorkElems, lay))
         return fail(HSSFSST_ENOMEM, "resample_exec_ragged: out of host memory");
-    }
-    // descriptors: RaggedResampleSig[count] in sorted order, then the table lengths
-    const size_t sig_bytes = static_cast<size_t>(count) * sizeof(RaggedResampleSig);
     unsigned char* h_desc = nullptr;
-    if ((rc = p->desc.begin(sig_bytes + tabN.size() * sizeof(long long), &h_desc)) != 0) return rc;
-    auto* sig = reinterpret_cast<RaggedResampleSig*>(h_desc);
-    for (const Chunk& ch : chunks) {
-        long long u = ch.t0 - 1;
-        for (long long d = ch.d0; d < ch.d0 + ch.cnt; ++d) {
-            const long long i = ord[static_cast<size_t>(d)];
-            if (d == ch.d0 || lens[i] != lens[ord[static_cast<size_t>(d - 1)]]) ++u;
-            sig[d] = RaggedResampleSig{starts[i] - xlo, lens[i], M1s[static_cast<size_t>(d)], tabOff[static_cast<size_t>(u)], i};
-        }
-    }
-    std::memcpy(h_desc + sig_bytes, tabN.data(), tabN.size() * sizeof(long long));
-    int Mt = M2;
-    for (int m : M1s) Mt = std::max(Mt, m);
-    if ((rc = rs_ragged_twiddles(p, Mt)) != 0) return rc;
+    if ((rc = p->desc.begin(lay.desc_bytes(), &h_desc)) != 0) return rc;
+    rslayout::write_descriptors(lay, h_desc);
+    if ((rc = rs_ragged_twiddles(p, lay.Mt)) != 0) return rc;
     if ((rc = p->desc.commit(st)) != 0) return rc;
-    const auto* dsig = reinterpret_cast<const RaggedResampleSig*>(p->desc.get());
-    const auto* dtn = reinterpret_cast<const long long*>(p->desc.get() + sig_bytes);
-    long long max_elems = 0;
-    for (const Chunk& ch : chunks) max_elems = std::max(max_elems, ch.elems);
-    if ((rc = p->d_work.grow(static_cast<size_t>(max_elems))) != 0) return rc;
-
-    // ---- staging of host buffers, as hssfsst_resample_exec
+    const auto* dsig = reinterpret_cast<const hssfsst::RaggedResampleSig*>(p->desc.get());
+    const auto* dtn = reinterpret_cast<const long long*>(p->desc.get() + lay.sig_bytes());
+    if ((rc = p->d_work.grow(static_cast<size_t>(lay.max_elems))) != 0) return rc;
+    // staging of host buffers, as hssfsst_resample_exec
     const size_t xsz = x_dtype == HSSFSST_DTYPE_F64 ? sizeof(double) : sizeof(float);
     const size_t ysz = y_dtype == HSSFSST_DTYPE_F64 ? sizeof(double) : sizeof(float);
     const size_t nout = static_cast<size_t>(count) * static_cast<size_t>(num);
@@ -2236,51 +2205,10 @@ int hssfsst_resample_exec_ragged(hssfsst_resample_plan* p, const void* x, int x_
                        x_on_device, y, ysz, labels, nout, out_on_device, st)) != 0) return rc;
     a.num = num; a.M2 = M2; a.c2 = p->c2;
     a.x_f64 = x_dtype == HSSFSST_DTYPE_F64; a.y_f64 = y_dtype == HSSFSST_DTYPE_F64; a.num_even = num % 2 == 0;
-    const double2* tw = p->d_tw.get();
-    const int twM = p->tw_M;
-    double2* work = p->d_work.get();
-    for (const Chunk& ch : chunks) {
-        const long long Mw = ch.Mw, cnt = ch.cnt;
-        const RaggedResampleSig* csig = dsig + ch.d0;
-        double2* tabs = work + cnt * Mw;
-        // B1 / M1 of every distinct length of the chunk, one class of equal M1 at a time
-        for (long long u = ch.t0; u < ch.t0 + ch.ntab;) {
-            long long v = u;
-            while (v < ch.t0 + ch.ntab && tabM[static_cast<size_t>(v)] == tabM[static_cast<size_t>(u)]) ++v;
-            const int M = static_cast<int>(tabM[static_cast<size_t>(u)]), S = M < hssfsst::kRsBlock ? M : hssfsst::kRsBlock;
-            double2* t0 = tabs + tabOff[static_cast<size_t>(u)];
-            const long long tot = (v - u) * M;
-            hipLaunchKernelGGL(hssfsst::resample_ragged_table_kernel, dim3(rs_grid(tot)), dim3(hssfsst::kRsThreads), 0, st, t0, dtn + u, M, tot);
-            if ((rc = launch_check("resample_exec", "resample_ragged_table_kernel")) != 0) return rc;
-            if ((rc = rs_dif(st, t0, M, v - u, M, tw, twM)) != 0) return rc;
-            hipLaunchKernelGGL(hssfsst::resample_ragged_table_block_kernel, dim3(static_cast<unsigned>((v - u) * (M / S))), dim3(hssfsst::kRsThreads),
-                               0, st, t0, M, S, tw, twM);
-            if ((rc = launch_check("resample_exec", "resample_ragged_table_block_kernel")) != 0) return rc;
-            u = v;
-        }
-        const long long t1 = cnt * Mw;
-        hipLaunchKernelGGL(hssfsst::resample_ragged_load_kernel, dim3(rs_grid(t1)), dim3(hssfsst::kRsThreads), 0, st, a, csig, work, Mw, t1);
-        if ((rc = launch_check("resample_exec", "resample_ragged_load_kernel")) != 0) return rc;
-        // the first convolution, one class of equal M1 at a time
-        for (long long e0 = 0; e0 < cnt;) {
-            long long e1 = e0;
-            const int M = M1s[static_cast<size_t>(ch.d0 + e0)], S = M < hssfsst::kRsBlock ? M : hssfsst::kRsBlock;
-            while (e1 < cnt && M1s[static_cast<size_t>(ch.d0 + e1)] == M) ++e1;
-            double2* w = work + e0 * Mw;
-            if ((rc = rs_dif(st, w, Mw, e1 - e0, M, tw, twM)) != 0) return rc;
-            hipLaunchKernelGGL(hssfsst::resample_ragged_block_kernel, dim3(static_cast<unsigned>((e1 - e0) * (M / S))), dim3(hssfsst::kRsThreads),
-                               0, st, w, Mw, M, S, csig + e0, tabs, tw, twM);
-            if ((rc = launch_check("resample_exec", "resample_ragged_block_kernel")) != 0) return rc;
-            if ((rc = rs_dit(st, w, Mw, e1 - e0, M, tw, twM)) != 0) return rc;
-            e0 = e1;
-        }
-        // the inverse side, once over the chunk
-        const long long t2 = cnt * M2, t3 = cnt * num;
-        hipLaunchKernelGGL(hssfsst::resample_ragged_mid_kernel, dim3(rs_grid(t2)), dim3(hssfsst::kRsThreads), 0, st, a, csig, work, Mw, t2);
-        if ((rc = launch_check("resample_exec", "resample_ragged_mid_kernel")) != 0) return rc;
-        if ((rc = rs_conv(st, work, Mw, cnt, M2, p->B2, tw, twM)) != 0) return rc;
-        hipLaunchKernelGGL(hssfsst::resample_ragged_store_kernel, dim3(rs_grid(t3)), dim3(hssfsst::kRsThreads), 0, st, a, csig, work, Mw, t3);
-        if ((rc = launch_check("resample_exec", "resample_ragged_store_kernel")) != 0) return rc;
+    for (const rslayout::Chunk& ch : lay.chunks) {
+        a.sig = dsig + ch.d0;
+        if ((rc = rs_ragged_forward_half(p, lay, ch, a, dtn, st)) != 0) return rc;
+        if ((rc = rs_inverse_half("resample_exec_ragged", st, a, p->d_work.get(), ch.Mw, ch.cnt, p->B2, p->d_tw.get(), p->tw_M)) != 0) return rc;
     }
     return rs_finish(a, y, ysz, labels, nout, x_on_device, out_on_device, st);
 }

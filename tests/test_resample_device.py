@@ -165,6 +165,45 @@ def test_strided_list_and_single_frames_agree_bitwise():
     assert torch.equal(one, y32[0].cpu())
 
 
+def same_bits(a, b):
+    return a.shape == b.shape and a.dtype == b.dtype and torch.equal(a.contiguous().view(torch.uint8), b.contiguous().view(torch.uint8))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n,num", [(4097, 1000), (1000, 4097)])
+def test_large_tier_frames_agree_bitwise(n, num):
+    """The large tier with more than one signal: 3 overlapping frames of one 6 000-sample buffer, read in place at stride 950.
+    4097 -> 1000 has the forward convolution (M1 = 16384: two pass launches on each side of the block kernel) above a block and the
+    inverse one (M2 = 2048) below; 1000 -> 4097 has them the other way round (M1 = 2048, M2 = 16384)."""
+    t = Resample(num)
+    assert t.lds_tier(n, 0) is False
+    rng = np.random.default_rng(n + num)
+    buf = torch.from_numpy(rng.standard_normal(6000)).to(DEV)
+    starts = torch.arange(3, dtype=torch.int64) * 950
+    F = buf.as_strided((3, n), (950, 1))
+    strided = t.batch(F, torch.float64)
+    assert strided.shape == (3, num) and strided.dtype == torch.float64
+    assert same_bits(t.frames(buf, starts.to(DEV), n, torch.float64), strided)        # device starts
+    assert same_bits(t.frames(buf, starts, n, torch.float64), strided)                # host starts
+    for i in range(3):
+        assert same_bits(t.batch(F[i:i + 1].contiguous(), torch.float64)[0], strided[i]), i
+        ref = host(F[i].cpu().numpy(), num)
+        assert np.abs(strided[i].cpu().numpy() - ref).max() / max(np.abs(ref).max(), 1.0) <= 1e-12, i
+    assert same_bits(t.batch(F, torch.float32), strided.to(torch.float32))
+    # the label rule, off the .5 ties
+    Y = torch.from_numpy(label_tracks(1, 6000, n)[0])
+    lab = t.frames(Y.to(DEV), starts, n, labels=True)
+    assert lab.shape == (3, num) and lab.dtype == torch.int64
+    assert torch.equal(resample_labels_batch(Y.as_strided((3, n), (950, 1)).to(DEV), t), lab)
+    ties = 0
+    for i, s in enumerate(starts.tolist()):
+        fr = Y[s:s + n]
+        ok = off_tie(t(fr).numpy())
+        ties += int((~ok).sum())
+        assert np.array_equal(lab[i].cpu().numpy()[ok], resample_labels(fr, t).numpy()[ok]), i
+    print(f"large-tier label rule: {ties} samples within 1e-9 of a .5 tie")
+
+
 @pytest.mark.gpu
 def test_label_rule_on_device():
     ties = 0

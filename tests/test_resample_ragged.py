@@ -7,6 +7,8 @@ against the host helper, the golden fixtures and the dense device plan, their de
 import ctypes
 import os
 import pickle
+import shutil
+import subprocess
 
 import numpy as np
 import pytest
@@ -19,7 +21,9 @@ from heart_sounds_segmentation_amd.transforms.resample import resample_labels, r
 
 GOLD = np.load(os.path.join(os.path.dirname(__file__), "golden", "resample.npz"))
 CASES = sorted({k.split("__")[0] for k in GOLD.files if k.endswith("__x")})
-HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "hssfsst.h")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = os.path.join(ROOT, "include", "hssfsst.h")
+CSRC = os.path.join(ROOT, "heart_sounds_segmentation_amd", "csrc")
 W128 = synth.kaiser_window(128, 0.5)
 NEW_ENTRY_POINTS = ("hssfsst_resample_plan_create_ragged", "hssfsst_resample_exec_ragged")
 
@@ -154,6 +158,27 @@ def test_ragged_without_device_raises_like_batch(built_lib):
         Resample(1000).ragged([torch.zeros(2000), torch.zeros(3000)])
 
 
+def test_layout_planner_under_sanitizers(tmp_path):
+    """csrc/fourier_resample_layout.hpp alone, in a program of its own (tests/native/resample_layout_check.cpp) built with
+    -fsanitize=address,undefined: lists [1], 16 equal, LENS and 1 000 pseudo-random lengths, each to num 1, 1 000 and 20 000 under the
+    library's budget, two that force several chunks and one below any signal's work (one signal per chunk).  Chunks, tables,
+    offsets, descriptors, Mt and max_elems equal the loop that used to stand inline in hssfsst_resample_exec_ragged; every signal in
+    exactly one chunk, the order stable, a chunk within the budget unless it holds one signal, each descriptor's table that of its own
+    length, its row its list index, its start taken from the staged span.  The dense chunk rule against its inline form, and
+    bluestein_tables for N in {1, 2, 3, 5, 64, 4097}."""
+    cxx = shutil.which("g++")
+    if cxx is None:
+        pytest.skip("no g++")
+    exe = tmp_path / "resample_layout_check"
+    r = subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", CSRC,
+                        os.path.join(ROOT, "tests", "native", "resample_layout_check.cpp"), "-o", str(exe)],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300,
+                       env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1"))
+    assert r.returncode == 0 and "resample layout ok" in r.stdout, (r.stdout[-1500:], r.stderr[-3000:])
+
+
 # ---------------------------------------------------------------------------------------------------- GPU
 DEV = "cuda:0"
 LENS = [1, 2, 3, 127, 128, 129, 2000, 4096, 4097, 8191, 35500, 60001, 240000, 2000, 129, 35500, 1]
@@ -213,6 +238,32 @@ def test_against_the_dense_device_plan():
         for i, x in enumerate(xs):
             dense = t.batch(x.reshape(1, -1).to(DEV), torch.float64)[0].cpu().numpy()
             assert rel_err(got[i], dense) <= 1e-12, (LENS[i], num)
+
+
+EDGE_LENS = [1, 2, 3, 64, 65, 2048, 2049, 4097, 4097, 5000]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("num", (1, 2, 50, 4097))
+def test_classes_at_the_block_boundaries(num):
+    """One-point convolutions (n = 1, and num = 1), first convolutions below, of and above the 4096-point block (M1 = 128, 256,
+    4096, 8192, 16384), a repeated length on one table, and the second convolution (M2 = 1, 4, 128, 8192) below and above the
+    chunk's largest M1: every row is bitwise the signal resampled alone and within 1e-12 of the host helper, and a float32 list
+    gives the bits of the float64 list of the same values."""
+    xs = signals(EDGE_LENS, 31)
+    xd = [x.to(DEV) for x in xs]
+    t = Resample(num)
+    got = t.ragged(xd, dtype=torch.float64)
+    assert got.shape == (len(EDGE_LENS), num)
+    G = got.cpu().numpy()
+    for i, x in enumerate(xs):
+        assert same_bits(t.ragged([xd[i]], dtype=torch.float64)[0], got[i]), (EDGE_LENS[i], num)
+        err = rel_err(G[i], host(x.numpy(), num))
+        assert err <= 1e-12, (EDGE_LENS[i], num, err)
+    x32 = [x.to(torch.float32) for x in xs]
+    a = t.ragged([x.to(DEV) for x in x32], dtype=torch.float64)
+    b = t.ragged([x.to(DEV, torch.float64) for x in x32], dtype=torch.float64)
+    assert same_bits(a, b)
 
 
 @pytest.mark.gpu
