@@ -37,10 +37,8 @@ using lds_u4 = __attribute__((address_space(3))) u4;
 // untouched; as a builtin, not inline assembly: the pass must see it.)
 #define HSS_RARE_VMEM_DONE() __builtin_amdgcn_s_waitcnt(0x0f70)
 constexpr int kCanonTileFrames = 64;                     // frames per aligned tile (4 groups = one statistics block)
+// (kCanonOpFloats, kCanonAtabFloats, kCanonLdsTabFloats -- the tables in LDS: fsst_launch_shape.hpp)
 constexpr int kCanonRecs = 192;                          // sample records per tile: 64 + 127, rounded up
-constexpr int kCanonOpFloats = 16 * 64 * 4;              // f16 A operand: [16 taps][64 lanes][8 halves] = 16 kB
-constexpr int kCanonAtabFloats = kCanonOpFloats + 4 * 128;   // + {cos, sin}(2 pi m / 128) as float64 (rounding-tie path), 2 kB
-constexpr int kCanonLdsTabFloats = kCanonAtabFloats + 4 * 33 * 2;   // what the kernels keep in LDS: + the interior frame of the offset table ("Offsets"), 1 kB
 constexpr int kCanonErrMul = 4;                          // tau^2 of the rounding-tie bound: 4 kTieErr2 (tau = 2e-6 (1 + |shift|) R / |V|)
 // (rounding ties: the bitmap of fsst_mfma128.hpp, "Rounding ties"; the float64 path reads the signal's own samples)
 constexpr int kCanonFlagWords = 8;                       // [1] the tie bitmap has a bit (the others: spare)

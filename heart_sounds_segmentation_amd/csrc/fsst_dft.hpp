@@ -23,11 +23,6 @@
 
 namespace hssfsst {
 
-// this kernel's rounding-tie queue: {bin | frame << 16, V.re, V.im} per entry (the MFMA kernel's is more compact)
-constexpr int kDftTieQueue = 256;
-constexpr int kDftTieWords = 4 + 3 * kDftTieQueue;
-
-
 struct DftParams {
     const float* x;       // [batch][n] (signal starts xstride apart)
     float* out;
@@ -43,14 +38,7 @@ struct DftParams {
     float r2scale;
 };
 
-// G = 16-frame groups per work item (a tile of 16 G frames): every A-operand load feeds G MFMAs on G independent
-// accumulators (the constants come from L2: one group per item is bound by those loads -- nwin 1024: 1.3 k windows/s).
-__host__ __device__ constexpr int dft_xs_floats(int nk4, int G = 1) { return ((16 * G + 4 * nk4 + 3) / 4) * 4; }
-__host__ __device__ constexpr int dft_wave_lds_floats(int nk4, int K, int G = 1)
-{
-    return dft_xs_floats(nk4, G) + 2 * 16 * G * plane_ldf(K) + 4 + kDftTieWords;
-}
-
+// (G = 16-frame groups per work item, and a wave's LDS floats for it: dft_wave_lds_floats, fsst_launch_shape.hpp)
 // One wave = one tile of G groups at a time (grid-stride over batch x tiles); blockDim = 64 x (waves that fit the LDS).
 template <int G>
 __global__ __launch_bounds__(512) void fsst_dft_kernel(DftParams p)

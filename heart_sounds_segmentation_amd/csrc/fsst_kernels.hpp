@@ -33,6 +33,7 @@
 #include <utility>
 
 #include "fsst_half.hpp"
+#include "fsst_launch_shape.hpp"
 
 namespace hssfsst {
 
@@ -314,7 +315,7 @@ __device__ __forceinline__ double wave_sum(double v)
 // kernel of fsst_mfma128.hpp, whose teams add their pieces in exactly this order.  The float64 cancellation in
 // sum x^2 - (sum x)^2 / N is harmless whenever the float32 features themselves still resolve the spread.
 // ------------------------------------------------------------------------------------------------
-constexpr int kPartFloats = 8;
+// (kPartFloats = 8: fsst_launch_shape.hpp, whose LDS budgets count it)
 constexpr int kStatBlock = 4;              // pieces per block of the summation order (= the groups of one 64-frame chunk of
                                            // the team kernel, which publishes one float64 block sum per chunk)
 

@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "fsst_kernels.hpp"
+#include "fsst_launch_shape.hpp"
 
 namespace hssfsst {
 
@@ -39,22 +40,7 @@ using f2 = float __attribute__((ext_vector_type(2)));
 using f4 = float __attribute__((ext_vector_type(4)));
 using lds_float = __attribute__((address_space(3))) float;
 
-// Work distribution: one persistent block of 16 waves per CU.  The launch is cut into CHUNKS of consecutive 16-frame
-// groups of one signal; the chunk list is ordered by region -- all region-0 chunks of all signals (8 groups each),
-// then region 1 (4 groups), then region 2 (2 groups).  Block B owns chunks B, B + grid, B + 2 grid, ... (the same
-// mix of big and small chunks for every CU) and its waves draw them in that order from a counter in LDS, so the 16
-// waves of a CU finish within one small chunk of each other.  Why: the SIMD arbiter favours the oldest wave, so with
-// equal static work per wave the four waves of a SIMD finished at 114 / 125 / 140 / 162 us, and with one fixed chunk
-// per wave and several rounds of 4-wave blocks the last 20 % of the kernel ran at falling occupancy
-// (profiles/r01_block_timeline.txt).  A ticket counter in HBM instead of LDS costs ~4 ns per draw, serialised
-// chip-wide: 23 552 draws made the kernel 0.29 ms.  The chunk pattern of a signal depends only on the number of
-// columns, not on the batch, and every chunk writes its own statistics partial: results are independent of the
-// batch composition and run-to-run deterministic whichever wave processes a chunk.
-struct Core128Regions {
-    int g0[3];            // first 16-frame group of the region (per signal)
-    int gpc[3];           // groups per chunk
-    int npc[3];           // chunks per signal
-};
+// (Work distribution -- the chunk pattern of a launch, Core128Regions -- and the LDS layout functions: fsst_launch_shape.hpp)
 
 // One signal of a ragged exec: its samples at x + xoff (n of them), its features at out + ooff (n x floats-per-sample in the
 // mode's layout), its statistics partials at partials + poff ((n + 15) / 16 of them).  Every column of it is an output column.
@@ -62,7 +48,6 @@ struct RaggedSignal {
     long long xoff, ooff, poff;
     int n, pad;
 };
-constexpr int kRaggedGroupBits = 24;         // groups of a signal below 2^24 (n < 2^28: the host allows n * 2 nf < 2^31)
 
 struct Core128Params {
     const float* x;       // [batch][n]
@@ -97,60 +82,6 @@ struct Core128Params {
     const int2* rchunk;                // [rnchunks] {signal, first group | (groups - 1) << 24}
     int rnchunks;
 };
-
-
-// Chunk pattern for `ngroups` 16-frame groups per signal: 8-group chunks, then 4-group chunks over the last
-// quarter or so, then 2-group chunks at the very end (each chunk costs a counter draw, a tile staging and a
-// statistics reduction, so the small ones are kept to the tail).  Measured (tail4, tail2): (16, 6) 0.1691 ms,
-// (24, 2) 0.1683, (32, 6) 0.1701, (8, 4) 0.1738, 8-group chunks only 0.1749.
-inline Core128Regions core128_regions(int ngroups, long long nsig = -1)
-{
-    Core128Regions r{};
-    const int tail2 = ngroups >= 32 ? 6 : 0;             // groups wanted as 2-group chunks
-    const int tail4 = ngroups >= 32 ? 16 : 0;            // groups wanted as 4-group chunks
-    if (ngroups < 32) {
-        // short signals / streaming steps (a rolling transform adds 8 groups per step): parallelism matters more than
-        // the per-chunk overhead -- 2-group chunks up to 8 groups, 4-group chunks up to 31; and single groups when
-        // the whole launch is smaller than the chip (one streaming step of 64 channels = 512 groups for 1024 SIMDs:
-        // the step's latency is then one group, not two)
-        const bool tiny = nsig >= 0 && ngroups <= 8 && nsig * ngroups <= 1024;
-        const int gpc = tiny ? 1 : ngroups <= 8 ? 2 : 4;
-        r.g0[0] = 0; r.gpc[0] = 8; r.npc[0] = 0;
-        r.g0[1] = 0; r.gpc[1] = 4; r.npc[1] = gpc == 4 ? (ngroups + 3) / 4 : 0;
-        r.g0[2] = 0; r.gpc[2] = gpc == 1 ? 1 : 2; r.npc[2] = gpc == 1 ? ngroups : gpc == 2 ? (ngroups + 1) / 2 : 0;
-        return r;
-    }
-    int big = ngroups - tail2 - tail4;
-    big -= big % 8;                                      // whole 8-group chunks only
-    if (big < 0) big = 0;
-    int mid = ngroups - big - tail2;
-    if (tail2 > 0) mid -= mid % 4;                       // whole 4-group chunks; the remainder joins the 2-group tail
-    const int rest = ngroups - big - mid;
-    r.g0[0] = 0;          r.gpc[0] = 8; r.npc[0] = big / 8;
-    r.g0[1] = big;        r.gpc[1] = 4; r.npc[1] = (mid + 3) / 4;
-    r.g0[2] = big + mid;  r.gpc[2] = 2; r.npc[2] = (rest + 1) / 2;
-    return r;
-}
-__host__ __device__ inline int core128_chunks_per_signal(const Core128Regions& r) { return r.npc[0] + r.npc[1] + r.npc[2]; }
-
-// Chunk list of a ragged exec: each signal cut as core128_regions(its groups, 1) cuts it alone, and the list ordered by region
-// across signals -- every 8-group chunk first, then the 4-group ones, then the 2- / 1-group ones -- so the small chunks stay in
-// the tail as in a dense launch.  Entry {signal, first group | (groups - 1) << kRaggedGroupBits}.
-inline void core128_ragged_chunks(const int* ngroups, long long nsig, std::vector<int2>& out)
-{
-    out.clear();
-    std::vector<Core128Regions> regs(static_cast<size_t>(nsig));
-    for (long long s = 0; s < nsig; ++s) regs[s] = core128_regions(ngroups[s], 1);
-    for (int rg = 0; rg < 3; ++rg)
-        for (long long s = 0; s < nsig; ++s) {
-            const Core128Regions& r = regs[s];
-            for (int c = 0; c < r.npc[rg]; ++c) {
-                const int g0 = r.g0[rg] + c * r.gpc[rg];
-                const int ng = std::min(r.gpc[rg], ngroups[s] - g0);
-                out.push_back(make_int2(static_cast<int>(s), g0 | ((ng - 1) << kRaggedGroupBits)));
-            }
-        }
-}
 
 
 // cos / sin of 2*pi*j/16, j = 0..7
@@ -239,33 +170,7 @@ __device__ __forceinline__ void fft_n(f2 (&z)[N])
     });
 }
 
-// ---- LDS planes of one 16-frame group (per wave), packed complex (re, im) per cell:
-//   own  [16 frames][own_ld]  columns for rows 8*s0 .. 8*s1+7, the 8-aligned cover of the kept band:
-//                             source k' stores (-1)^k' V[k'] into its column unconditionally
-//                             (address = per-lane base + compile-time offset); sources whose
-//                             8-row stripe lies outside the cover skip the store (wave-uniform);
-//   disp [16 frames][LDF(K)]  kept rows only, zero-initialised: corrections from displaced sources.
-__host__ __device__ constexpr int odd_up(int v) { return (v & 1) ? v : v + 1; }      // odd => b64 conflict-free
-__host__ __device__ constexpr int plane_ldf(int K) { return odd_up(K); }
-// rq = first-stage radix = rows per stripe (8 for nwin = 128, 16 for nwin = 256): source k' = rq * s + r sits in stripe s
-__host__ __device__ constexpr int own_s0(int klo, int rq = 8) { return klo / rq; }
-__host__ __device__ constexpr int own_s1(int klo, int K, int rq = 8) { return (klo + K - 1) / rq; }   // inclusive stripe
-__host__ __device__ constexpr int own_ld(int klo, int K, int rq = 8)
-{
-    return odd_up(rq * (own_s1(klo, K, rq) - own_s0(klo, rq) + 1) + 1);
-}
-// MFMA A-operand constants: [pass][nt taps][k-step][64 lanes] floats, rq / 8 passes of rq / 4 k-steps
-__host__ __device__ constexpr int core128_atab_floats(int rq = 8, int nt = 16) { return (rq / 8) * nt * (rq / 4) * 64; }
 constexpr int kMaxWavesPerBlock = 16;        // 16 = one block owns a whole CU (4 waves per SIMD); fewer when LDS is short
-constexpr int kCtlFloats = 16 + 192;         // block control words in LDS: [0] work counter, [16..207] the wide-store offset
-                                             // table (3 words per lane: held in registers it costs the 16-wave kernels a spill)
-// FUSED kernel: [0] ticket counter, [1..2] groups delivered per signal slot (monotone), [3] a wait gave up, [4..7] epoch
-// of the resolved statistics (4 slots), [8..15] (unused), [16..79] per-lane column classes of the z-score
-// pass, [80..271] the wide-store offset table (3 words per lane; the fused kernel has no register to spare for it),
-// [272..287] four float4 statistics, [288 ..] the statistics partials of two signals [2][kFusedMaxGroups][kPartFloats]
-constexpr int kFusedMaxGroups = 128;         // signals of at most 2048 frames
-constexpr int kFusedMinChunks = 16;          // and of at least 16 chunks: see "Slots" in the kernel
-constexpr int kCtlFusedFloats = 288 + 2 * kFusedMaxGroups * kPartFloats;
 
 // FAST epilogue: byte offsets, inside a wave's own plane, of the two (re,re) / (im,im) pairs that make up
 // float4 number f = lane + 64 i of a 16-frame group's contiguous [16][2K] output image (K even, K <= 24).
@@ -305,7 +210,6 @@ inline void core128_store_offsets(int klo, int K, int* tab /* [6][64] */, int rq
 // round by v_readlane).  The float32 V of a cell inside the stored cover of the own plane is read back from -- and cleared
 // in -- its own column; for a cell outside it V is the float64 DFT's own result, rounded once.
 constexpr int kTieCoop = 6;                  // up to this many undecided cells of a 64-source set the wave resolves one by one
-__host__ __device__ constexpr int tie_words(int nwin) { return nwin / 4; }     // the bitmap (flag[1] = "some bit is set")
 constexpr float kTieMargin = 1.0f / 64.0f;   // the stay-in-row test hands |shift| > 1/2 - this to the rare path
 constexpr float kTieErr2 = 1.0e-12f;         // (1e-6)^2: tau^2 = kTieErr2 (1 + |shift|)^2 R^2 / |V|^2  (4e-7 left 2 of 1000
                                              // random configurations 1.4-1.8x over the gate: tools/fuzz_parity.py 1000 3)
@@ -313,12 +217,6 @@ constexpr float kTieFloor2 = 1.0e-12f;       // (1e-6)^2: cells with |V|^2 below
                                              // estimates the frame's spectrum norm by up to ~5x and that norm is at most
                                              // sqrt(nwin) times the largest bin, so 1e-6 R is < 1e-4 of the largest feature
                                              // (1e-5 R was not: 3 of 2000 random narrow-band configurations failed the gate)
-
-__host__ __device__ constexpr int wave_lds_floats(int fpw, int klo, int K, int rq = 8, int nt = 16)
-{
-    return ((fpw + nt * rq - 1 + 3) / 4) * 4 + 2 * 16 * (own_ld(klo, K, rq) + plane_ldf(K)) + 4   // + dirty flag
-           + tie_words(nt * rq);                                                                     // + tie queues
-}
 
 __device__ __forceinline__ void wave_sync()
 {
@@ -893,8 +791,6 @@ constexpr unsigned kSpinLimit = 1u << 18;          // polls before a wait gives 
 // after a wave's data is seen after it): twice the waves on the same LDS -- 6 instead of 3 per CU for nwin 512 with 90 kept
 // rows -- and half the latency of a lone group (one streaming step).
 constexpr unsigned kPairSpinLimit = 1u << 24;       // looks at the partner's phase word before a pair's wait ends on its own (~1 s)
-constexpr int kPairFloats = 4 + 64 + 3 * 256;  // [0..1] phase words, [2] the pair's ticket, [3] the odd wave's list count, [4..67] its per-lane
-                                             // max |V|^2, then its list of additions (PairList: 256 cells, 256 values)
 // RAGGED (hssfsst_exec_ragged: signals of different lengths in one launch): a chunk's signal, first group and groups come from
 // the host-made list p.rchunk, and the signal's length, input, output and partials from p.rsig; everything else -- staging,
 // transform, ties, epilogue -- is the plain kernel's, on that signal alone (reads past its own length see zeros).

@@ -86,8 +86,8 @@ inline void band_rows(int nwin, double fs, double f_lo, double f_hi, int* klo, i
 }
 
 // the MFMA kernels' window lengths and their taps (per-lane FFT size); the first-stage radix is nwin / taps
-inline bool mfma_length(int nwin) { return nwin == 128 || nwin == 256 || nwin == 512; }
-inline int mfma_taps(int nwin) { return nwin == 512 ? 32 : 16; }
+using hssfsst::mfma_length;          // (fsst_launch_shape.hpp)
+using hssfsst::mfma_taps;
 
 // The fold constant of a window split as nwin = NT taps x RQ fold terms (the first stage of every radix kernel):
 //   C_r[n, q] = (w + i dw')[n + NT q] * exp(-2 pi i (r q / RQ + r n / nwin)),   class r, tap n, fold term q,

@@ -70,7 +70,7 @@ constexpr int kT16BlockWords = 8;            // tagged 8-byte words per BLOCK of
                                              // float64 sums (sum re, sum re^2, sum im, sum im^2), each as {high, low} half
 constexpr int kT16MaxBlocks = kFusedMaxGroups / kStatBlock;      // 32 blocks per signal
 constexpr int kT16SlotWords = kT16MaxBlocks * kT16BlockWords;          // a signal's mailbox slot
-constexpr int kT16MaxCpc = 8;                // groups of a signal per CU (two blocks)
+// (kT16MaxCpc = 8, groups of a signal per CU -- two blocks: fsst_launch_shape.hpp, with the launch's geometry)
 constexpr int kT16MaxSlots = 64;             // statistics slots per CU / mailbox slots per team (signal ordinal mod slots); 32 where the LDS is short
 constexpr int kT16StatFloats = 12;           // a signal's statistics in LDS: three float4 {mean, 1/std} pairs -- (re, re), (re, im), (im, im): the
                                              // z-score of a float4 of the image reads the one its two column pairs need (emit_held)

@@ -23,6 +23,7 @@
 #include <thread>
 #include <vector>
 #include <type_traits>
+#include <utility>
 
 #include "fsst_kernels.hpp"
 #include "fsst_mfma128.hpp"
@@ -151,7 +152,7 @@ int check_device(const char* what, int device)
 }
 
 constexpr int kTile = 64;
-constexpr int kFpw128 = 64;      // frames per wave tile of the nwin = 128 kernel
+using hssfsst::kFpw128;
 
 // A plan's device buffer: capacity in elements of T; grow() frees the old block and allocates a larger one (contents are not
 // kept), upload() makes a fresh block holding a host table.  Freed with its owner.
@@ -281,20 +282,17 @@ struct hssfsst_plan {
     DevBuf<float> d_f32;                                     // half plans: float32 features of the paths whose z-score is a second sweep
     DevBuf<float> d_ctab;         // generic kernel: class-folded scalar tables
     DevBuf<float> d_dtab;         // any-length kernel (fsst_dft.hpp): A operand [source block][k-step][64 lanes]
-    Family family = Family::Generic;      // (rq, nt and the LDS bytes below belong to Family::Mfma)
+    Family family = Family::Generic;
     float r2scale = 0.0f;         // 4 nwin max |(w + i dw') / 2|^2: error-bound scale of the rounding-tie path
     DevBuf<double> d_wtab;        // float64 {w, dw' in bin units}[nwin], then {cos, sin}(2 pi m / nwin)[nwin]: rounding-tie path
     DevBuf<float> d_atab;         // nwin == 128 / 256 / 512: MFMA A-operand constants [pass][taps][64 lanes][k-step]
-    int rq = 0;                   // first-stage radix of the MFMA kernel, 0 = generic kernel
     DevBuf<float> d_atab16;       // canonical-band kernels (fsst_canon128.hpp): f16 split A operand [16 taps][64 lanes][8 halves]
     float canon_inv_c = 0.0f;     // ... 1 / (power-of-two scale of those constants)
     float canon_r2s = 0.0f;       // ... r2scale x scale^2
     int canon_slots = 0;          // resident blocks of fsst_canon_kernel<.., false> (0 = not queried yet)
-    int nt = 16;                  // taps (per-lane FFT size) of the MFMA kernel: nwin = nt * rq
     // what follows from the fields above, stated once at creation (choose_family, set_derived_facts):
-    bool fast = false;            // the wide-store epilogue applies: STACK modes, even K <= 24
-    bool stripes03 = false;       // MFMA plans: the band starts in stripe 0 of the own plane and ends in stripe 3 (the canonical [25, 200] Hz at fs = 1000, nwin 128 / 256)
-    size_t lds_fixed = 0, lds_per_wave = 0;   // MFMA plans: LDS bytes of the core kernel beside its wave regions, and of one wave region
+    hssfsst::MfmaFacts mf;        // nt, rq, fast, stripes03 and the LDS bytes (fsst_launch_shape.hpp; rq = 0 unless Family::Mfma)
+    int plain_row = -1;           // MFMA plans: the row of kCore128Plain that the two-launch path runs, dense and ragged (-1: none fits)
     int canon_idx = -1;           // index of the band in kCanonBands when the canonical-band kernels apply, else -1
     DevBuf<float> d_partials;                                // kPartFloats per statistics piece
     unsigned* d_status = nullptr;                            // fused z-score: status word (0 = ok) as the device sees it ...
@@ -349,7 +347,7 @@ namespace {
 // The dynamic-LDS limit is a property of the kernel instantiation (per device), not of a plan: raise it ONCE to
 // the full 160 KiB, so that plans with different band widths sharing an instantiation cannot lower it under each
 // other and the hot path makes no driver call for it.
-constexpr int kMaxLdsBytes = 160 * 1024;
+using hssfsst::kMaxLdsBytes;
 template <class Kern>
 int allow_full_lds(Kern kern, int device, std::atomic<unsigned long long>& done)
 {
@@ -439,12 +437,7 @@ int launch_core(hssfsst_plan* pl, ExecCtx& cx, hssfsst::CoreParams cp, long long
     return 0;
 }
 
-// bytes of LDS of a core launch of an MFMA plan: WPB waves, PAIR: two waves per wave region (fsst_mfma128.hpp "PAIR")
-inline size_t core128_lds_bytes(const hssfsst_plan* pl, int wpb, bool pair)
-{
-    const size_t regions = pair ? wpb / 2 : wpb;
-    return pl->lds_fixed + regions * (pl->lds_per_wave + (pair ? hssfsst::kPairFloats * sizeof(float) : 0));
-}
+inline size_t core128_lds_bytes(const hssfsst_plan* pl, int wpb, bool pair) { return hssfsst::core128_lds_bytes(pl->mf, wpb, pair); }
 
 // the Core128Params every launch of an MFMA plan starts from: the plan-constant fields
 hssfsst::Core128Params core128_params(const hssfsst_plan* pl)
@@ -534,11 +527,8 @@ int launch_fused(hssfsst_plan* pl, ExecCtx& cx, hssfsst::Core128Params cp, int64
     if (int rc = allow_full_lds(kern, pl->device, lds_ok)) return rc;
     if (int rc = resident_blocks(pl, pl->fused_slots, kern, 64 * WPB, lds, true)) return rc;       // one block per CU
     if (pl->fused_slots < 1) return 0;
-    // signals are dealt to the blocks round-robin and a signal is never split: the last round must be nearly full
-    // (a quarter-full last round of 4 costs 4 / 3.25 = 23 %), otherwise the chunk-balanced two-kernel path wins
     const int64_t grid = pl->fused_slots;
-    const int64_t rounds = (batch + grid - 1) / grid;
-    if (batch < grid || rounds * grid * 100 > batch * 112) return 0;
+    if (!hssfsst::fused_rounds_full(batch, grid)) return 0;
     if (int rcs = ensure_status(pl)) return rcs;
     cp.status = pl->d_status;
     name_kernel(cx.kernel, WPB, grid, "fsst_core128_kernel<%d, %d, %d, %s, %d, %d, true>", NT, RQ, kFpw128, FAST ? "true" : "false", WPB, S1C);
@@ -601,12 +591,10 @@ int launch_team16(hssfsst_plan* pl, ExecCtx& cx, const hssfsst::Core128Params& c
     if constexpr (sizeof(OT) == 2) {
         if (hout == nullptr || (reinterpret_cast<uintptr_t>(hout) & 7) != 0) return 0;
     }
-    const int G = ngroups;
-    if (G < 1 || G > kFusedMaxGroups) return 0;             // (the resolver's LDS copy of a signal's partials: 128 groups)
     // (at least 84 KiB: one block per CU whatever its size -- the teams count on it)
     constexpr int PSLOTS = t16_pslots<KLO, KC>();        // signals whose partials a CU keeps in LDS at a time
     constexpr int MS = t16_slots<KLO, KC>();             // statistics / mailbox slots the kernel's LDS has room for
-    size_t lds = (kCanonLdsTabFloats + t16_ctl_floats(PSLOTS, MS) + static_cast<size_t>(WPB) * CanonCfg<KLO, KC>::wave_floats()) * sizeof(float);
+    size_t lds = canon_lds_bytes(t16_ctl_floats(PSLOTS, MS), CanonCfg<KLO, KC>::wave_floats(), WPB);
     if (lds > static_cast<size_t>(kMaxLdsBytes)) return 0;
     if (lds < 84 * 1024) lds = 84 * 1024;
     auto kern = team16_kernel<KLO, KC, WPB, DEPTH, OT>();
@@ -614,31 +602,9 @@ int launch_team16(hssfsst_plan* pl, ExecCtx& cx, const hssfsst::Core128Params& c
     if (int rc = allow_full_lds(kern, pl->device, lds_ok)) return rc;
     if (int rc = resident_blocks(pl, pl->team16_cus, kern, 64 * WPB, lds, true)) return rc;
     if (pl->team16_cus < 1) return 0;
-    // team size: the smallest power of two that leaves a CU at most 16 groups of a signal (its 16 waves then have all of them in
-    // flight at once and the kernel's progress argument holds)
-    int T = 1;
-    while ((WPB / 2) * T < G) T *= 2;                    // (cpc <= WPB is the kernel's progress argument; cpc <= WPB / 2 measured faster:
-                                                         //  a signal's groups are handed out within half a round of the CU's waves)
-    if (T > pl->team16_cus || T > 64) return 0;
-    int cpc = 1, cpc_shift = 0;                          // list positions per CU and signal (power of two; surplus ones are skipped)
-    while (cpc * T < G) { cpc *= 2; ++cpc_shift; }
-    if (cpc > WPB || cpc > kT16MaxCpc || G / T < 1) return 0;
-    if (cpc < 4 && T > 1) return 0;                      // (a CU publishes whole blocks of four groups)
-    // as many teams as the chip has room for, but no more than there are signals: the dataset loop's one frame per call
-    // (/root/reference/hss/datasets/heart_sounds.py:166-168) starts one team's 16 blocks, not 256 of which 240 find nothing to do
-    int nteams = pl->team16_cus / T;
-    if (batch < nteams) nteams = static_cast<int>(batch);
-    const int grid = nteams * T;
-    if ((batch + nteams - 1) / nteams > 65535) return 0;
-    if (cp.xstride < 1 || cp.xstride > 0x7fffffffLL || batch > 0x7fffffffLL) return 0;      // (the kernel's 32-bit signal index and stride)
-    // slots: a CU runs at most held_pos list positions ahead of its oldest unresolved signal = lead signals; a slot is reused
-    // 2 lead + 2 signals later at the earliest (fsst_team16.hpp "Progress")
-    const int held_pos = WPB * (DEPTH + 3);             // list positions a CU's waves hold: DEPTH held + transformed + landed + drawn each
-    const int lead = (held_pos + G / T - 1) / (G / T) + 1;
-    int slots = 8;
-    while (slots < 2 * lead + 2) slots *= 2;
-    if (slots > MS) return 0;
-    if (lead + 1 > PSLOTS) return 0;                     // (very short signals: more signals in flight per CU than its LDS keeps partials for)
+    const Team16Geometry geo = team16_geometry(ngroups, batch, cp.xstride, pl->team16_cus, WPB, DEPTH, PSLOTS, MS);
+    if (!geo.ok) return 0;
+    const int T = geo.T, nteams = geo.nteams, grid = geo.grid, slots = geo.slots;
     int rc;
     if ((rc = ensure_status(pl)) != 0) return rc;
     const size_t words = static_cast<size_t>(nteams) * slots * kT16SlotWords;
@@ -655,7 +621,7 @@ int launch_team16(hssfsst_plan* pl, ExecCtx& cx, const hssfsst::Core128Params& c
     tp.x = cp.x; tp.out = sizeof(OT) == 4 ? cp.out : static_cast<float*>(hout); tp.atab = pl->d_atab16.get(); tp.wtab = cp.wtab; tp.twtab = cp.twtab;
     tp.mail = pl->d_mail.get(); tp.status = pl->d_status; tp.r2scale_s = pl->canon_r2s; tp.inv_c = pl->canon_inv_c;
     tp.n = cp.n; tp.nsig = cp.nsig; tp.col0 = cp.col0; tp.ncols = cp.ncols; tp.xstride = cp.xstride;
-    tp.team = T; tp.cpc_shift = cpc_shift; tp.slots = slots; tp.seq = pl->team_seq;
+    tp.team = T; tp.cpc_shift = geo.cpc_shift; tp.slots = slots; tp.seq = pl->team_seq;
     {   // the two float64 divisions of stats_finish (correctly rounded here as there: the same bits)
         const double total = static_cast<double>(KC) * static_cast<double>(cp.ncols);
         tp.inv_total = 1.0 / total; tp.inv_total1 = 1.0 / (total - 1.0);
@@ -717,8 +683,8 @@ template <int KLO, int KC, bool RAGGED = false>
 int launch_canon_band(hssfsst_plan* pl, ExecCtx& cx, const hssfsst::Core128Params& cp, int64_t nchunks)
 {
     constexpr int WPB = 16;
-    const size_t lds = (hssfsst::kCanonLdsTabFloats + hssfsst::kCanonCtlFloats + static_cast<size_t>(WPB) * hssfsst::CanonCfg<KLO, KC>::wave_floats()) * sizeof(float);
-    static_assert((hssfsst::kCanonLdsTabFloats + hssfsst::kCanonCtlFloats + 16 * hssfsst::CanonCfg<KLO, KC>::wave_floats()) * sizeof(float) <= 160 * 1024, "16 wave regions must fit");
+    constexpr size_t lds = hssfsst::canon_lds_bytes(hssfsst::kCanonCtlFloats, hssfsst::CanonCfg<KLO, KC>::wave_floats(), WPB);
+    static_assert(lds <= static_cast<size_t>(kMaxLdsBytes), "16 wave regions must fit");
     auto kern = hssfsst::fsst_canon_kernel<KLO, KC, false, RAGGED>;
     static std::atomic<unsigned long long> lds_ok{0};
     if (int rc = allow_full_lds(kern, pl->device, lds_ok)) return rc;
@@ -749,7 +715,7 @@ int launch_canon_fused_band(hssfsst_plan* pl, ExecCtx& cx, hssfsst::Core128Param
     const bool gated = cx.gate != nullptr;
     constexpr int WPB = 16, GPC = hssfsst::kCanonTileFrames / 16;
     if (ngroups > hssfsst::kFusedMaxGroups || (ngroups + GPC - 1) / GPC < hssfsst::kFusedMinChunks) return 0;
-    constexpr size_t lds = (hssfsst::kCanonLdsTabFloats + hssfsst::kCanonCtlFusedFloats + static_cast<size_t>(WPB) * hssfsst::CanonCfg<KLO, KC>::wave_floats()) * sizeof(float);
+    constexpr size_t lds = hssfsst::canon_lds_bytes(hssfsst::kCanonCtlFusedFloats, hssfsst::CanonCfg<KLO, KC>::wave_floats(), WPB);
     // (rows 2..25: 16 wave regions of 8.6 kB and the two signals' partials do not fit the 160 KiB together: team kernel or two launches)
     if constexpr (lds > static_cast<size_t>(kMaxLdsBytes)) return 0;
     else {
@@ -759,10 +725,9 @@ int launch_canon_fused_band(hssfsst_plan* pl, ExecCtx& cx, hssfsst::Core128Param
     if (int rc = resident_blocks(pl, pl->fused_slots, kern, 64 * WPB, lds, true)) return rc;
     if (pl->fused_slots < 1) return 0;
     int64_t grid = pl->fused_slots;
-    const int64_t rounds = (batch + grid - 1) / grid;
     // (gated = behind a team launch: almost always the gate is closed and 64 blocks keep the empty launch short)
     if (gated) grid = batch < 64 ? batch : 64;
-    else if (batch < grid || rounds * grid * 100 > batch * 112) return 0;
+    else if (!hssfsst::fused_rounds_full(batch, grid)) return 0;
     if (int rcs = ensure_status(pl)) return rcs;
     cp.status = pl->d_status;
     if (!gated) name_kernel(cx.kernel, WPB, grid, "fsst_canon_kernel<%d, %d, true>", KLO, KC);
@@ -835,7 +800,8 @@ void out_dispatch(const hssfsst_plan* p, void* out, F&& f)
 // The tables of a ragged exec's list, into the host block h (laid out by t): signal i reads x at starts[i] - xlo, its features
 // are `ofps` floats per sample behind those of the signals before it, its statistics partials one per 16-frame group likewise;
 // its z-score units (fsst_ragged.hpp) follow from its 2K floats per sample.  t.nunits is set here.
-void fill_ragged_tables(unsigned char* h, hssfsst_plan::RaggedTabs& t, const std::vector<int2>& chunks, const int64_t* starts,
+static_assert(sizeof(hssfsst::RaggedChunk) == sizeof(int2) && alignof(hssfsst::RaggedChunk) == alignof(int2), "the kernels read a chunk as int2");
+void fill_ragged_tables(unsigned char* h, hssfsst_plan::RaggedTabs& t, const std::vector<hssfsst::RaggedChunk>& chunks, const int64_t* starts,
                         const int64_t* lens, int64_t batch, long long xlo, int ofps, int K)
 {
     std::memset(h, 0, t.chunk);
@@ -863,7 +829,7 @@ int ragged_tables(hssfsst_plan* p, const int64_t* starts, const int64_t* lens, i
     if (p->rtab.same(nkey, key)) return 0;
     std::vector<int> ng(static_cast<size_t>(batch));
     for (int64_t i = 0; i < batch; ++i) ng[i] = static_cast<int>((lens[i] + 15) / 16);
-    std::vector<int2> chunks;
+    std::vector<hssfsst::RaggedChunk> chunks;
     hssfsst::core128_ragged_chunks(ng.data(), batch, chunks);
     if (chunks.size() >= 0x7fffffffull) return fail(HSSFSST_EINVAL, "exec_ragged: %zu chunks exceed the launch limit; split the list", chunks.size());
     hssfsst_plan::RaggedTabs t;
@@ -887,23 +853,13 @@ int launch_zscore(hssfsst_plan* p, const ExecCtx& cx, const float* feats, void* 
 {
     float4* stats = reinterpret_cast<float4*>(p->d_stats.get());
     const float* partials = p->d_partials.get();
-    int64_t zgrid = 4096;
-    // small batches: several blocks per signal, else one block per signal would leave most CUs idle
-    int slices = 1;
-    if (batch < 1024) {
-        slices = static_cast<int>(1024 / batch);
-        if (slices > 32) slices = 32;
-    }
-    if (zgrid > batch * slices) zgrid = batch * slices;
-    // big batches, a block per signal: it reduces the signal's partials itself (no separate statistics
-    // launch, 4-7 us per step); otherwise a tiny kernel does all reductions at once
-    const bool fused = slices == 1 && zgrid == batch && batch >= 512;
-    if (!fused)
+    const hssfsst::ZscoreShape z = hssfsst::zscore_shape(batch);
+    if (!z.fused)
         hipLaunchKernelGGL(hssfsst::fsst_stats_kernel, dim3(static_cast<unsigned>(batch)), dim3(64), 0, cx.st,
                            partials, stats, nblk, fpp, ncols, p->K, cx.gate, cx.gate_val);
     out_dispatch(p, out, [&](auto* o) {
-        hipLaunchKernelGGL(hssfsst::fsst_normalize_kernel<std::remove_pointer_t<decltype(o)>>, dim3(static_cast<unsigned>(zgrid)), dim3(256), 0, cx.st,
-                           feats, o, stats, fused ? partials : nullptr, nblk, fpp, ncols, p->K, static_cast<int>(batch), slices,
+        hipLaunchKernelGGL(hssfsst::fsst_normalize_kernel<std::remove_pointer_t<decltype(o)>>, dim3(static_cast<unsigned>(z.grid)), dim3(256), 0, cx.st,
+                           feats, o, stats, z.fused ? partials : nullptr, nblk, fpp, ncols, p->K, static_cast<int>(batch), z.slices,
                            cx.gate, cx.gate_val);
     });
     HIP_TRY(hipGetLastError());
@@ -926,46 +882,27 @@ int launch_zscore_ragged(hssfsst_plan* p, const ExecCtx& cx, const float* feats,
     return 0;
 }
 
-// The plain (two-launch) core kernel for a plan of the MFMA kernel: as many waves per block as fit the 160 KiB of LDS beside
-// the shared tables.  RAGGED: the instantiations of hssfsst_exec_ragged (the same ladder, chunk list from the host).
+// The plain (two-launch) core kernel of an MFMA plan: the row of kCore128Plain (fsst_launch_shape.hpp) that plan creation
+// chose, turned into its instantiation by expanding that same table.  RAGGED: the instantiations of hssfsst_exec_ragged (the
+// same rows, chunk list from the host).
+template <bool RAGGED, size_t... I>
+int launch_core128_row(hssfsst_plan* pl, ExecCtx& cx, const hssfsst::Core128Params& cp, int64_t nchunks, std::index_sequence<I...>)
+{
+    using hssfsst::kCore128Plain;
+    int rc = 0;
+    (void)((static_cast<size_t>(pl->plain_row) == I
+            && (rc = launch_core128_wpb<kCore128Plain[I].nt, kCore128Plain[I].rq, kCore128Plain[I].fast, kCore128Plain[I].wpb, kCore128Plain[I].s1c,
+                                        kCore128Plain[I].pair, RAGGED>(pl, cx, cp, nchunks), true)) || ...);
+    return rc;
+}
 template <bool RAGGED>
 int launch_core128_plain(hssfsst_plan* pl, ExecCtx& cx, const hssfsst::Core128Params& cp, int64_t nchunks)
 {
-    const int rq = pl->rq, nt = pl->nt;
-    const bool fast = pl->fast, canon = pl->stripes03;
-    const size_t fixed = pl->lds_fixed, per_wave = pl->lds_per_wave, room = 160 * 1024;
-    if (nt == 16 && rq == 8) {
-        if (fast && canon) return launch_core128_wpb<16, 8, true, 16, 3, false, RAGGED>(pl, cx, cp, nchunks);
-        if (fast) return launch_core128_wpb<16, 8, true, 16, -1, false, RAGGED>(pl, cx, cp, nchunks);   // K <= 24: 16 regions always fit
-        if (fixed + 16 * per_wave <= room) return launch_core128_wpb<16, 8, false, 16, -1, false, RAGGED>(pl, cx, cp, nchunks);
-        if (fixed + 8 * per_wave <= room) return launch_core128_wpb<16, 8, false, 8, -1, false, RAGGED>(pl, cx, cp, nchunks);
-        if (fixed + 4 * per_wave <= room) return launch_core128_wpb<16, 8, false, 4, -1, false, RAGGED>(pl, cx, cp, nchunks);
-    } else if (nt == 16 && rq == 16) {                                               // nwin = 256
-        // (wave pairs -- fsst_mfma128.hpp "PAIR" -- lose here: 16 waves at 128 registers spill, core 0.770 vs 0.587 ms per 1024
-        //  windows; 12 waves at 170 registers: 0.739 ms)
-        // (8 waves per block at most: two per SIMD, up to 256 VGPRs, no scratch)
-        if (fast && fixed + 8 * per_wave <= room) return launch_core128_wpb<16, 16, true, 8, -1, false, RAGGED>(pl, cx, cp, nchunks);
-        if (!fast && canon && fixed + 8 * per_wave <= room) return launch_core128_wpb<16, 16, false, 8, 3, false, RAGGED>(pl, cx, cp, nchunks);
-        if (!fast && fixed + 8 * per_wave <= room) return launch_core128_wpb<16, 16, false, 8, -1, false, RAGGED>(pl, cx, cp, nchunks);
-        if (!fast && fixed + 4 * per_wave <= room) return launch_core128_wpb<16, 16, false, 4, -1, false, RAGGED>(pl, cx, cp, nchunks);
-        if (fast && fixed + 4 * per_wave <= room) return launch_core128_wpb<16, 16, true, 4, -1, false, RAGGED>(pl, cx, cp, nchunks);
-    } else {                                                                         // nt == 32, rq == 16: nwin = 512
-        if (!debug_switches().no_pair) {                                             // (two waves per SIMD at most: 32-point spectra in registers)
-            if (fast && core128_lds_bytes(pl, 8, true) <= room) return launch_core128_wpb<32, 16, true, 8, -1, true, RAGGED>(pl, cx, cp, nchunks);
-            if (!fast && core128_lds_bytes(pl, 8, true) <= room) return launch_core128_wpb<32, 16, false, 8, -1, true, RAGGED>(pl, cx, cp, nchunks);
-            if (!fast && core128_lds_bytes(pl, 6, true) <= room) return launch_core128_wpb<32, 16, false, 6, -1, true, RAGGED>(pl, cx, cp, nchunks);
-            if (!fast && core128_lds_bytes(pl, 4, true) <= room) return launch_core128_wpb<32, 16, false, 4, -1, true, RAGGED>(pl, cx, cp, nchunks);
-        }
-        if (fast && fixed + 8 * per_wave <= room) return launch_core128_wpb<32, 16, true, 8, -1, false, RAGGED>(pl, cx, cp, nchunks);
-        if (!fast && fixed + 8 * per_wave <= room) return launch_core128_wpb<32, 16, false, 8, -1, false, RAGGED>(pl, cx, cp, nchunks);
-        if (!fast && fixed + 6 * per_wave <= room) return launch_core128_wpb<32, 16, false, 6, -1, false, RAGGED>(pl, cx, cp, nchunks);
-        if (fast && fixed + 4 * per_wave <= room) return launch_core128_wpb<32, 16, true, 4, -1, false, RAGGED>(pl, cx, cp, nchunks);
-        if (!fast && fixed + 4 * per_wave <= room) return launch_core128_wpb<32, 16, false, 4, -1, false, RAGGED>(pl, cx, cp, nchunks);
-        if (!fast && fixed + 3 * per_wave <= room) return launch_core128_wpb<32, 16, false, 3, -1, false, RAGGED>(pl, cx, cp, nchunks);
-        if (!fast && fixed + 2 * per_wave <= room) return launch_core128_wpb<32, 16, false, 2, -1, false, RAGGED>(pl, cx, cp, nchunks);
-        if (fast && fixed + 2 * per_wave <= room) return launch_core128_wpb<32, 16, true, 2, -1, false, RAGGED>(pl, cx, cp, nchunks);
-    }
-    return fail(HSSFSST_EUNSUPPORTED, "LDS request %zu B per wave exceeds the 160 KiB budget", per_wave);
+    // (not reached: mfma_facts calls a plan MFMA only when 4 wave regions fit, 2 at 512 points, and the table has a row of that
+    //  many waves for every (nt, rq, fast) -- at 128 points with the wide-store epilogue K <= 24 and 16 regions fit;
+    //  tests/native/launch_shape_check.cpp sweeps every band)
+    if (pl->plain_row < 0) return fail(HSSFSST_EUNSUPPORTED, "LDS request %zu B per wave exceeds the 160 KiB budget", pl->mf.lds_per_wave);
+    return launch_core128_row<RAGGED>(pl, cx, cp, nchunks, std::make_index_sequence<hssfsst::kCore128PlainRows>{});
 }
 
 // Is the team kernel wanted for a STACK exec of columns [col0, col0 + ncols) under the preference zpref?  Stated once: exec_impl
@@ -997,8 +934,8 @@ int launch_core128(hssfsst_plan* pl, ExecCtx& cx, const float* dx, long long xst
     cp.n = n; cp.nsig = static_cast<int>(batch); cp.col0 = col0; cp.ncols = ncols;
     cp.reg = hssfsst::core128_regions(ngroups, batch);
     const int64_t nchunks = batch * hssfsst::core128_chunks_per_signal(cp.reg);
-    const int rq = pl->rq, nt = pl->nt;
-    const bool fast = pl->fast, canon = pl->stripes03;
+    const int rq = pl->mf.rq, nt = pl->mf.nt;
+    const bool fast = pl->mf.fast, canon = pl->mf.stripes03;
     // (tiles are aligned in absolute columns: a column range must start on a 16-frame group boundary -- on a 64-frame tile
     //  boundary for the team kernel, whose chunks are whole tiles; other ranges take fsst_core128_kernel)
     const bool canon16 = fast && nt == 16 && rq == 8 && plan_is_canon(pl) && (col0 & 15) == 0;
@@ -1064,25 +1001,22 @@ int launch_core128(hssfsst_plan* pl, ExecCtx& cx, const float* dx, long long xst
     return launch_core128_plain<false>(pl, cx, cp, nchunks);
 }
 
-// Plan creation, step 1: which kernels the plan runs, with the MFMA kernels' shape nwin = nt x rq and LDS bytes.
+// Plan creation, step 1: which kernels the plan runs, with the MFMA kernels' shape nwin = nt x rq and LDS bytes (mfma_facts).
 int choose_family(hssfsst_plan* p)
 {
     const int nwin = p->nwin;
-    // (force_dft, cross-check: every length on the any-length kernel)
-    if (!(nwin == 32 || nwin == 64 || tables::mfma_length(nwin)) || debug_switches().force_dft) {
+    const bool stack = p->mode == HSSFSST_MODE_STACK || p->mode == HSSFSST_MODE_STACK_UNNORM;
+    // (force_dft, cross-check: every length on the any-length kernel; force_generic: every radix length on the generic one)
+    const bool dft = !(nwin == 32 || nwin == 64 || tables::mfma_length(nwin)) || debug_switches().force_dft;
+    p->mf = hssfsst::mfma_facts(dft || debug_switches().force_generic ? 0 : nwin, p->klo, p->K, stack);
+    if (dft) {
         p->family = Family::Dft;
         const size_t per_wave = static_cast<size_t>(hssfsst::dft_wave_lds_floats((nwin + 3) / 4, p->K > 0 ? p->K : 1)) * sizeof(float);
         if (per_wave <= static_cast<size_t>(kMaxLdsBytes)) return 0;
         return fail(HSSFSST_EUNSUPPORTED, "plan_create: window length %d with %d kept rows needs %zu B of LDS per wave (> 160 KiB): "
                                           "narrow the band", nwin, p->K, per_wave);
     }
-    if (!tables::mfma_length(nwin) || debug_switches().force_generic) return 0;
-    // enough wave regions of this band must fit beside the A table (long windows with very wide bands: generic kernel)
-    const int nt = tables::mfma_taps(nwin), rq = nwin / nt, min_waves = (nwin == 512) ? 2 : 4;
-    const size_t fixed = (hssfsst::core128_atab_floats(rq, nt) + hssfsst::kCtlFloats) * sizeof(float);
-    const size_t per_wave = static_cast<size_t>(hssfsst::wave_lds_floats(kFpw128, p->klo, p->K, rq, nt)) * sizeof(float);
-    if (fixed + min_waves * per_wave > 160 * 1024) return 0;
-    p->family = Family::Mfma; p->rq = rq; p->nt = nt; p->lds_fixed = fixed; p->lds_per_wave = per_wave;
+    if (p->mf.rq != 0) p->family = Family::Mfma;         // (else: not an MFMA length, or too few wave regions of this band fit)
     return 0;
 }
 
@@ -1109,8 +1043,7 @@ int upload_tables(hssfsst_plan* p, const double* window, const double* dwb)
 void set_derived_facts(hssfsst_plan* p)
 {
     const bool stack = p->mode == HSSFSST_MODE_STACK || p->mode == HSSFSST_MODE_STACK_UNNORM;
-    p->fast = stack && (p->K & 1) == 0 && p->K <= 24;
-    p->stripes03 = p->family == Family::Mfma && hssfsst::own_s0(p->klo, p->rq) == 0 && hssfsst::own_s1(p->klo, p->K, p->rq) == 3;
+    if (p->family == Family::Mfma) p->plain_row = hssfsst::core128_plain_row(p->mf, debug_switches().no_pair);
     if (debug_switches().no_canon || !p->d_atab16.get() || !stack) return;      // (no_canon: A/B and cross-check tests)
     for (int i = 0; i < static_cast<int>(sizeof(kCanonBands) / sizeof(kCanonBands[0])); ++i)
         if (p->klo == kCanonBands[i][0] && p->K == kCanonBands[i][1]) p->canon_idx = i;
@@ -1444,35 +1377,16 @@ static int launch_dft(hssfsst_plan* p, ExecCtx& cx, const float* dx, float* kout
     dp.n = n; dp.nwin = p->nwin; dp.nf = p->nf; dp.klo = p->klo; dp.K = p->K; dp.mode = p->mode; dp.col0 = col0; dp.ncols = ncols;
     dp.nk4 = (p->nwin + 3) / 4; dp.nblk4 = (p->nf + 3) / 4;
     dp.xstride = x_stride; dp.r2scale = p->r2scale;
-    // groups per work item: 4 when four planes fit the LDS of a wave (each A-operand load then feeds four MFMAs),
-    // else 2, else 1; then as many waves per block as fit (at most 8)
-    // largest tile that still leaves >= 16 waves resident per CU (the MFMA chains are dependent: latency is hidden
-    // by waves, not by the tile), else whatever keeps the most waves (measured: nwin 100 is fastest with small tiles)
-    int G = 1, best_waves = -1;
-    for (int cand = 4; cand >= 1; cand >>= 1) {
-        const size_t pw = static_cast<size_t>(hssfsst::dft_wave_lds_floats(dp.nk4, p->K, cand)) * sizeof(float);
-        int w = static_cast<int>(static_cast<size_t>(kMaxLdsBytes) / pw);
-        if (w > 8) w = 8;
-        if (w < 1) continue;
-        int per_cu = static_cast<int>(static_cast<size_t>(kMaxLdsBytes) / (pw * w)) * w;
-        if (per_cu > 32) per_cu = 32;
-        if (per_cu >= 16) { G = cand; best_waves = per_cu; break; }
-        if (per_cu > best_waves) { G = cand; best_waves = per_cu; }
-    }
-    if (ncols <= 16) G = 1;
+    const hssfsst::DftShape sh = hssfsst::dft_shape(dp.nk4, p->K, ncols, batch);
+    const int G = sh.G, waves = sh.waves;
     const size_t per_wave = static_cast<size_t>(hssfsst::dft_wave_lds_floats(dp.nk4, p->K, G)) * sizeof(float);
-    int waves = static_cast<int>(static_cast<size_t>(kMaxLdsBytes) / per_wave);
-    if (waves > 8) waves = 8;
     if (waves < 1) return fail(HSSFSST_EUNSUPPORTED, "exec: LDS request %zu B per wave exceeds 160 KiB", per_wave);
-    const int ntiles = (ncols + 16 * G - 1) / (16 * G);
-    dp.nitems = static_cast<long long>(batch) * ntiles;
-    long long blocks = (dp.nitems + waves - 1) / waves;
-    if (blocks > 256 * 64) blocks = 256 * 64;                       // grid-stride beyond that
+    dp.nitems = sh.nitems;
     auto launch = [&](auto kern) -> int {
         static std::atomic<unsigned long long> lds_ok{0};
         if (int r2 = allow_full_lds(kern, p->device, lds_ok)) return r2;
-        name_kernel(cx.kernel, waves, blocks, "fsst_dft_kernel<%d>", G);
-        hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(blocks)), dim3(64 * waves), per_wave * waves, cx.st, dp);
+        name_kernel(cx.kernel, waves, sh.blocks, "fsst_dft_kernel<%d>", G);
+        hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(sh.blocks)), dim3(64 * waves), per_wave * waves, cx.st, dp);
         return (hipGetLastError() == hipSuccess) ? 0 : fail(HSSFSST_EHIP, "exec: fsst_dft_kernel launch failed");
     };
     return (G == 4) ? launch(hssfsst::fsst_dft_kernel<4>) : (G == 2) ? launch(hssfsst::fsst_dft_kernel<2>) : launch(hssfsst::fsst_dft_kernel<1>);
@@ -1792,7 +1706,7 @@ int hssfsst_exec_ragged(hssfsst_plan* p, const float* x, int64_t x_len, const in
     cp.rsig = d_rsig; cp.rchunk = d_chunks; cp.rnchunks = static_cast<int>(t.nchunks);
     // (the canonical-class band in STACK modes takes the canonical kernel's arithmetic, as every single exec of it does; the
     //  general kernels give other -- equally accurate -- bits there)
-    if (p->fast && p->nt == 16 && p->rq == 8 && plan_is_canon(p))
+    if (p->mf.fast && p->mf.nt == 16 && p->mf.rq == 8 && plan_is_canon(p))
         rc = canon_dispatch(p, [&](auto KL, auto KN) { return launch_canon_band<decltype(KL)::value, decltype(KN)::value, true>(p, cx, cp, t.nchunks); });
     else
         rc = launch_core128_plain<true>(p, cx, cp, t.nchunks);
@@ -2340,7 +2254,7 @@ int hssfsst_stream_step(hssfsst_plan* p, float* tape, int64_t tape_len, int64_t 
     DEVICE_SCOPE(p->device);
     // one launch for the whole step where the transform is the wide-store MFMA kernel in one-group chunks (nwin 256 / 512, an even
     // band of <= 24 rows: BASELINE config 5); host samples are copied into the tape first and the kernel reads them there
-    const bool one_launch = p->family == Family::Mfma && p->rq == 16 && p->fast && !debug_switches().no_stream_fuse &&
+    const bool one_launch = p->family == Family::Mfma && p->mf.rq == 16 && p->mf.fast && !debug_switches().no_stream_fuse &&
                             (reinterpret_cast<uintptr_t>(out) & 15) == 0 &&
                             static_cast<long long>(channels) * ((chunk + 15) / 16) < 0x7fffffffLL;
     int launched = 0;
@@ -2367,10 +2281,10 @@ int hssfsst_stream_step(hssfsst_plan* p, float* tape, int64_t tape_len, int64_t 
         }
         // (wave pairs: the step's latency is one group's; regions of a block = 2)
         if (debug_switches().no_pair)
-            launched = (p->nt == 32) ? launch_stream<32, 16, 4, false>(p, tape + (pos - hist), tape_len, xd, x_stride, channels, chunk, out, state, mirror, st)
+            launched = (p->mf.nt == 32) ? launch_stream<32, 16, 4, false>(p, tape + (pos - hist), tape_len, xd, x_stride, channels, chunk, out, state, mirror, st)
                                      : launch_stream<16, 16, 4, false>(p, tape + (pos - hist), tape_len, xd, x_stride, channels, chunk, out, state, mirror, st);
         else
-            launched = (p->nt == 32) ? launch_stream<32, 16, 4, true>(p, tape + (pos - hist), tape_len, xd, x_stride, channels, chunk, out, state, mirror, st)
+            launched = (p->mf.nt == 32) ? launch_stream<32, 16, 4, true>(p, tape + (pos - hist), tape_len, xd, x_stride, channels, chunk, out, state, mirror, st)
                                      : launch_stream<16, 16, 4, true>(p, tape + (pos - hist), tape_len, xd, x_stride, channels, chunk, out, state, mirror, st);
         if (launched < 0) return launched;
         if (launched == 0 && xd)                         // (not this kernel's shape after all: the chunk goes into the tape by a copy)

@@ -280,3 +280,30 @@ def test_lent_buffer_goes_back_when_the_last_view_dies():
     del v
     assert released == [backing.ctypes.data]
     assert sq._lent_type(backing.size) is sq._lent_type(backing.size)      # one array type per result size
+
+
+def test_launch_shapes_under_sanitizers(tmp_path):
+    """csrc/fsst_launch_shape.hpp alone, in a program of its own (tests/native/launch_shape_check.cpp) built with
+    -fsanitize=address,undefined.  The plan facts and the plain-kernel table against the if-ladder they replace, for nwin 128 /
+    256 / 512, every band, stack and not, pairs on and off: the same instantiation, and a row for every MFMA plan.  The team
+    kernel's geometry over groups 0 .. 130, batches around 16, 256 and 65535 x 16, 1 .. 304 CUs, four LDS budgets and four
+    strides: the arithmetic that stood in launch_team16, and for every accepted geometry the conditions the kernel's progress
+    argument names (powers of two, cpc T >= G, cpc <= WPB, whole blocks of four, grid <= CUs, teams <= batch, slots >= 2 lead + 2
+    within the LDS, lead + 1 <= pslots).  Chunk patterns of 1 .. 4 200 groups cover every group once; ragged lists cut each signal
+    as alone, by region.  The z-score rule, the any-length kernel's tile search and the 88 % rule against their inline forms."""
+    import os
+    import shutil
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cxx = shutil.which("g++")
+    if cxx is None:
+        pytest.skip("no g++")
+    exe = tmp_path / "launch_shape_check"
+    r = subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                        "-I", os.path.join(root, "heart_sounds_segmentation_amd", "csrc"),
+                        os.path.join(root, "tests", "native", "launch_shape_check.cpp"), "-o", str(exe)],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300,
+                       env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1"))
+    assert r.returncode == 0 and "launch shape ok" in r.stdout, (r.stdout[-1500:], r.stderr[-3000:])
