@@ -257,6 +257,18 @@ def lib():
         L.hssfsst_segmenter_exec.restype = c_int
         L.hssfsst_segmenter_exec_ragged.argtypes = [vp, vp, c_int, ctypes.POINTER(c_i64), c_i64, vp, vp, c_int, vp, vp]
         L.hssfsst_segmenter_exec_ragged.restype = c_int
+        L.hssfsst_bilstm_create.argtypes = [ctypes.POINTER(vp), c_int, c_int, c_int]
+        L.hssfsst_bilstm_create.restype = c_int
+        L.hssfsst_bilstm_destroy.argtypes = [vp]
+        L.hssfsst_bilstm_destroy.restype = c_int
+        L.hssfsst_bilstm_set_weights.argtypes = [vp, fpp, vp]
+        L.hssfsst_bilstm_set_weights.restype = c_int
+        L.hssfsst_bilstm_stash_floats.argtypes = [vp, c_i64, c_i64, ctypes.POINTER(c_i64)]
+        L.hssfsst_bilstm_stash_floats.restype = c_int
+        L.hssfsst_bilstm_forward.argtypes = [vp, vp, c_i64, c_i64, vp, vp, vp, vp, vp, vp, vp]
+        L.hssfsst_bilstm_forward.restype = c_int
+        L.hssfsst_bilstm_backward.argtypes = [vp, vp, vp, vp, vp, vp, c_i64, c_i64, vp, vp, vp, vp]
+        L.hssfsst_bilstm_backward.restype = c_int
         L.hssfsst_device_count.restype = c_int
         L.hssfsst_version.restype = c_int
         L.hssfsst_last_error.restype = ctypes.c_char_p

@@ -14,6 +14,9 @@ hssfsst_segmenter_exec; csrc/segmenter_lstm.hpp), inference only: ``segment(fsst
 config 4 with nothing leaving the device and no torch op between the FSST kernel and the log-probs.  Whole recordings of
 different lengths go through ``segment_recordings(fsst, head.hip(), recordings)`` (``HipSegmenter.ragged``,
 hssfsst_segmenter_exec_ragged) in one call.
+
+``HipBiLSTM`` is one differentiable bidirectional layer on the HIP recurrences (hssfsst_bilstm_*; csrc/segmenter_train.hpp) and
+``HipSegmenterHead`` the same model built from two of them: what a training script uses instead of the ``nn.LSTM`` model.
 """
 from __future__ import annotations
 
@@ -231,6 +234,164 @@ class HipSegmenter:
                        "hssfsst_segmenter_exec_ragged")
             i = j
         return result
+
+
+class _BiLSTMFunction(torch.autograd.Function):
+    """forward: hssfsst_bilstm_forward (projection + recurrence kernels, which also fill the stash); backward:
+    hssfsst_bilstm_backward (the backward recurrence, which is sequential) and then the time-parallel products as torch.matmul."""
+
+    @staticmethod
+    def forward(ctx, layer, x, h0, c0, *weights):
+        B, T, H = int(x.shape[0]), int(x.shape[1]), layer.hidden_size
+        plan = layer._sync_plan(x.device, weights)
+        L = _lib.lib()
+        x, h0, c0 = x.contiguous(), h0.contiguous(), c0.contiguous()
+        floats = ctypes.c_int64()
+        _lib.check(L.hssfsst_bilstm_stash_floats(plan, B, T, ctypes.byref(floats)), "hssfsst_bilstm_stash_floats")
+        stash = torch.empty(floats.value, dtype=torch.float32, device=x.device)
+        y = torch.empty((B, T, 2 * H), dtype=torch.float32, device=x.device)
+        hn = torch.empty((2, B, H), dtype=torch.float32, device=x.device)
+        cn = torch.empty_like(hn)
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        _lib.check(L.hssfsst_bilstm_forward(plan, x.data_ptr(), B, T, h0.data_ptr(), c0.data_ptr(), y.data_ptr(), hn.data_ptr(),
+                                            cn.data_ptr(), stash.data_ptr(), stream), "hssfsst_bilstm_forward")
+        ctx.layer, ctx.serial = layer, layer._serial
+        ctx.save_for_backward(x, h0, c0, y, stash, *weights)
+        return y, hn, cn
+
+    @staticmethod
+    def backward(ctx, dy, dhn, dcn):
+        layer = ctx.layer
+        if layer._serial != ctx.serial:
+            raise RuntimeError("HipBiLSTM: the layer's weights were repacked for other values between this forward and its "
+                               "backward; the backward recurrence would run against the wrong W_hh")
+        x, h0, c0, y, stash, *weights = ctx.saved_tensors
+        B, T, H = int(x.shape[0]), int(x.shape[1]), layer.hidden_size
+        dy = torch.zeros_like(y) if dy is None else dy.contiguous()
+        dhn = None if dhn is None else dhn.contiguous()
+        dcn = None if dcn is None else dcn.contiguous()
+        dgates = torch.empty((2, B, T, 4 * H), dtype=torch.float32, device=x.device)
+        dh0 = torch.empty((2, B, H), dtype=torch.float32, device=x.device)
+        dc0 = torch.empty_like(dh0)
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        _lib.check(_lib.lib().hssfsst_bilstm_backward(layer._plan, stash.data_ptr(), c0.data_ptr(), dy.data_ptr(),
+                                                      None if dhn is None else dhn.data_ptr(),
+                                                      None if dcn is None else dcn.data_ptr(), B, T, dgates.data_ptr(),
+                                                      dh0.data_ptr(), dc0.data_ptr(), stream), "hssfsst_bilstm_backward")
+        # h before each step: y shifted one step towards the direction's start, with h0 in front
+        hprev = (torch.cat((h0[0].unsqueeze(1), y[:, :-1, :H]), dim=1), torch.cat((y[:, 1:, H:], h0[1].unsqueeze(1)), dim=1))
+        xf = x.reshape(B * T, -1)
+        grads = []
+        for d in range(2):
+            g = dgates[d].reshape(B * T, 4 * H)
+            db = g.sum(0)
+            grads += [g.t() @ xf, g.t() @ hprev[d].reshape(B * T, H), db, db.clone()]
+        dx = None
+        if ctx.needs_input_grad[1]:
+            dx = (dgates[0].reshape(B * T, 4 * H) @ weights[0] + dgates[1].reshape(B * T, 4 * H) @ weights[4]).reshape(x.shape)
+        return (None, dx, dh0, dc0, *grads)
+
+
+class HipBiLSTM(nn.Module):
+    """One bidirectional, batch-first LSTM layer that TRAINS on the HIP kernels: ``y, (hn, cn) = layer(x, (h0, c0))`` with
+    x (B, T, input_size), h0 / c0 (2, B, hidden_size), all float32 on the GPU, differentiable in x, h0, c0 and the weights.
+    The parameters carry ``nn.LSTM``'s names, shapes and initialisation (``weight_ih_l0`` ... ``bias_hh_l0_reverse``), so a
+    ``state_dict`` moves both ways.  The forward pass is the inference kernels' (csrc/segmenter_lstm.hpp) and keeps every step's
+    gates and cell state in a stash; the backward recurrence is a HIP kernel (csrc/segmenter_train.hpp), the weight and input
+    gradients are ``torch.matmul`` on its output.  The weights are repacked on the device (no host synchronisation) whenever a
+    parameter changed since the last forward.  The stash costs 2 x ceil(B / 16) x T x 80 KiB per layer and forward call: about
+    1.3 GB at B 50, T 2000, whatever the hidden size.  hidden_size <= 256.  No CPU path: without a GPU, RuntimeError."""
+
+    def __init__(self, input_size: int, hidden_size: int):
+        super().__init__()
+        self.input_size, self.hidden_size = int(input_size), int(hidden_size)
+        self._take(nn.LSTM(input_size=input_size, hidden_size=hidden_size, bidirectional=True, batch_first=True))
+        self._plan, self._plan_device, self._packed, self._serial = None, None, None, 0
+
+    def _take(self, lstm: nn.LSTM) -> None:
+        for k in _LSTM_KEYS:
+            self.register_parameter(k, getattr(lstm, k))
+
+    @classmethod
+    def from_lstm(cls, lstm: nn.LSTM) -> "HipBiLSTM":
+        """A layer that takes over the parameters of a one-layer bidirectional batch-first ``nn.LSTM``."""
+        if lstm.num_layers != 1 or not lstm.bidirectional or not lstm.batch_first or not lstm.bias or lstm.proj_size:
+            raise ValueError("HipBiLSTM.from_lstm: a one-layer, bidirectional, batch-first nn.LSTM with biases expected")
+        self = cls.__new__(cls)
+        nn.Module.__init__(self)
+        self.input_size, self.hidden_size = lstm.input_size, lstm.hidden_size
+        self._take(lstm)
+        self._plan, self._plan_device, self._packed, self._serial = None, None, None, 0
+        return self
+
+    def __getstate__(self):                                  # (a copy or a pickle makes its own plan on first use)
+        state = self.__dict__.copy()
+        state.update(_plan=None, _plan_device=None, _packed=None)
+        return state
+
+    def __del__(self):
+        if getattr(self, "_plan", None):
+            try:
+                _lib.lib().hssfsst_bilstm_destroy(self._plan)
+            except Exception:
+                pass
+            self._plan = None
+
+    def _sync_plan(self, device, weights):
+        """The plan on ``device`` holding the CURRENT weights: made on first use, repacked when a parameter changed."""
+        L = _lib.lib()
+        if self._plan is None or self._plan_device != device:
+            if self._plan is not None:
+                _lib.check(L.hssfsst_bilstm_destroy(self._plan), "hssfsst_bilstm_destroy")
+                self._plan = None
+            plan = ctypes.c_void_p()
+            _lib.check(L.hssfsst_bilstm_create(ctypes.byref(plan), device.index, self.input_size, self.hidden_size),
+                       "hssfsst_bilstm_create")
+            self._plan, self._plan_device, self._packed = plan, device, None
+        key = tuple((w.data_ptr(), w._version) for w in weights)
+        if key != self._packed:
+            ptrs = (ctypes.c_void_p * 8)(*[w.data_ptr() for w in weights])
+            _lib.check(L.hssfsst_bilstm_set_weights(self._plan, ptrs, torch.cuda.current_stream(device).cuda_stream),
+                       "hssfsst_bilstm_set_weights")
+            self._packed = key
+            self._serial += 1
+        return self._plan
+
+    def forward(self, x: torch.Tensor, state):
+        L = _lib.lib()                                       # (a missing library is said first)
+        del L
+        _lib.guard_fork()
+        if not torch.cuda.is_available():
+            raise RuntimeError("HipBiLSTM: no GPU; the BiLSTM kernels have no CPU path")
+        h0, c0 = state
+        weights = [getattr(self, k) for k in _LSTM_KEYS]
+        if x.device.type != "cuda" or any(t.device != x.device for t in (h0, c0, *weights)):
+            raise RuntimeError(f"HipBiLSTM: input, state and parameters must be on one GPU (input on {x.device}, "
+                               f"parameters on {weights[0].device}); there is no CPU path")
+        if x.dim() != 3 or x.shape[2] != self.input_size or x.shape[0] < 1 or x.shape[1] < 1:
+            raise ValueError(f"HipBiLSTM: input of shape (B, T, {self.input_size}) expected, got {tuple(x.shape)}")
+        want = (2, int(x.shape[0]), self.hidden_size)
+        if tuple(h0.shape) != want or tuple(c0.shape) != want:
+            raise ValueError(f"HipBiLSTM: h0 and c0 of shape {want} expected, got {tuple(h0.shape)} and {tuple(c0.shape)}")
+        if any(t.dtype != torch.float32 for t in (x, h0, c0, *weights)):
+            raise ValueError("HipBiLSTM: float32 input, state and parameters expected (cast half-precision features first)")
+        if any(not w.is_contiguous() for w in weights):
+            raise ValueError("HipBiLSTM: contiguous parameters expected")
+        y, hn, cn = _BiLSTMFunction.apply(self, x, h0, c0, *weights)
+        return y, (hn, cn)
+
+
+class HipSegmenterHead(SegmenterHead):
+    """``SegmenterHead`` whose two BiLSTM layers are ``HipBiLSTM``: the same constructor, ``state_dict`` keys, ``h0`` / ``c0``
+    buffers, random draws and ``forward`` (layer 1 -> ReLU -> Dropout(0.2) -> layer 2 seeded with layer 1's (hn, cn) -> ReLU ->
+    Dropout -> Linear -> log_softmax), in ``train()`` and ``eval()``; everything outside the layers is torch under autograd.
+    A training script swaps the class and moves the module to the GPU; ``hip()`` stays the inference-only plan of the base."""
+
+    def __init__(self, input_size: int = 44, hidden_size: int = 240, batch_size: int = 50,
+                 h0: Optional[torch.Tensor] = None, c0: Optional[torch.Tensor] = None):
+        super().__init__(input_size, hidden_size, batch_size, h0=h0, c0=c0)
+        self.lstm_1 = HipBiLSTM.from_lstm(self.lstm_1)
+        self.lstm_2 = HipBiLSTM.from_lstm(self.lstm_2)
 
 
 def segment(fsst, head, windows: torch.Tensor) -> torch.Tensor:

@@ -39,6 +39,7 @@
 #include "fourier_resample_ragged.hpp"
 #include "segmenter_lstm.hpp"
 #include "segmenter_layout.hpp"
+#include "segmenter_train.hpp"
 #include "fsst_tables.hpp"
 
 namespace tables = hssfsst::tables;
@@ -2615,6 +2616,189 @@ int hssfsst_segmenter_exec_ragged(hssfsst_segmenter* p, const void* feats, int f
     hipLaunchKernelGGL(hssfsst::seg_head_kernel, dim3(static_cast<unsigned>((lay.total + 3) / 4)), dim3(256), 0, st, p->d_y2.get(), p->d_lin.get(),
                        p->d_lin.get() + static_cast<size_t>(8) * H, logp, lay.total, 2 * H);
     return launch_check("segmenter_exec", "seg_head_kernel");
+}
+
+}  // extern "C"
+
+// One trainable BiLSTM layer (hssfsst.h: hssfsst_bilstm_create): the tables of its current weights, packed on the device by
+// hssfsst_bilstm_set_weights (csrc/segmenter_train.hpp), and the scratch of its forward and backward calls.
+struct hssfsst_bilstm {
+    int device = -1;
+    int F = 0, Fp = 0, H = 0;
+    bool packed = false;
+    DevBuf<float> d_wt, d_bias;                          // as hssfsst_segmenter::Layer's
+    DevBuf<hssfsst::seg_h8> d_whh;                       // forward stream: W_hh x wscale, split f16
+    DevBuf<hssfsst::seg_b8> d_bwd;                       // backward stream: W_hh, split bf16, as the B operand of dG . W_hh
+    DevBuf<float> d_scale;                               // {wscale, inv_scale}: made and read on the device only
+    DevBuf<float> d_pre;                                 // one chunk's input projection
+    DevBuf<float> d_state;                               // forward [h, c][dir][Bp][Hp]; backward [dh_rec, dc][dir][Bp][Hp]
+};
+
+namespace {
+
+int bilstm_check_shape(const char* what, int64_t batch, int64_t steps)
+{
+    if (batch < 1 || steps < 1)
+        return fail(HSSFSST_EINVAL, "%s: bad argument (batch=%lld steps=%lld)", what, static_cast<long long>(batch), static_cast<long long>(steps));
+    if (batch > kSegMaxBatch || steps > kSegMaxSteps)
+        return fail(HSSFSST_EINVAL, "%s: batch %lld or steps %lld too large", what, static_cast<long long>(batch), static_cast<long long>(steps));
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int hssfsst_bilstm_create(hssfsst_bilstm** out, int device, int input_size, int hidden)
+{
+    if (!out) return fail(HSSFSST_EINVAL, "bilstm_create: out is NULL");
+    *out = nullptr;
+    if (input_size < 1 || hidden < 1 || device < 0)
+        return fail(HSSFSST_EINVAL, "bilstm_create: bad argument (device=%d input_size=%d hidden=%d)", device, input_size, hidden);
+    if (hidden > hssfsst::kSegHp)
+        return fail(HSSFSST_EUNSUPPORTED, "bilstm_create: hidden sizes above %d are not supported (hidden=%d)", hssfsst::kSegHp, hidden);
+    if (input_size > (1 << 20)) return fail(HSSFSST_EUNSUPPORTED, "bilstm_create: input sizes above 2^20 are not supported (input_size=%d)", input_size);
+    if (int rc = check_device("bilstm_create", device)) return rc;
+    DEVICE_SCOPE(device);
+    std::unique_ptr<hssfsst_bilstm> p(new (std::nothrow) hssfsst_bilstm());
+    if (!p) return fail(HSSFSST_ENOMEM, "bilstm_create: host allocation failed");
+    p->device = device; p->F = input_size; p->H = hidden;
+    p->Fp = (input_size + 31) / 32 * 32;
+    namespace sl = hssfsst::seglayout;
+    if (int rc = p->d_wt.grow(static_cast<size_t>(2) * p->Fp * sl::kGateCols)) return rc;
+    if (int rc = p->d_bias.grow(static_cast<size_t>(2) * sl::kGateCols)) return rc;
+    if (int rc = p->d_whh.grow(static_cast<size_t>(sl::kWtStreamHalves / 8))) return rc;
+    if (int rc = p->d_bwd.grow(static_cast<size_t>(sl::kBwdStreamHalves / 8))) return rc;
+    if (int rc = p->d_scale.grow(2)) return rc;
+    *out = p.release();
+    return 0;
+}
+
+int hssfsst_bilstm_destroy(hssfsst_bilstm* p)
+{
+    if (!p) return 0;
+    DeviceGuard device_guard_(p->device);
+    delete p;
+    return 0;
+}
+
+int hssfsst_bilstm_set_weights(hssfsst_bilstm* p, const float* const* weights, void* stream)
+{
+    if (!p || !weights) return fail(HSSFSST_EINVAL, "bilstm_set_weights: bad argument (%s is NULL)", !p ? "plan" : "weights");
+    for (int i = 0; i < 8; ++i)
+        if (!weights[i]) return fail(HSSFSST_EINVAL, "bilstm_set_weights: bad argument (weight array %d is NULL)", i);
+    DEVICE_SCOPE(p->device);
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    namespace sl = hssfsst::seglayout;
+    hssfsst::SegPackArgs a{};
+    for (int i = 0; i < 8; ++i) a.src[i] = weights[i];
+    a.F = p->F; a.Fp = p->Fp; a.H = p->H;
+    a.scale = p->d_scale.get(); a.wt = p->d_wt.get(); a.bias = p->d_bias.get();
+    a.whh = reinterpret_cast<_Float16*>(p->d_whh.get());
+    a.bwd = reinterpret_cast<__bf16*>(p->d_bwd.get());
+    hipLaunchKernelGGL(hssfsst::seg_pack_scale_kernel, dim3(1), dim3(1024), 0, st, a);
+    if (int rc = launch_check("bilstm_set_weights", "seg_pack_scale_kernel")) return rc;
+    const long long most = std::max<long long>(static_cast<long long>(2) * p->Fp * sl::kGateCols, std::max(sl::kWtStreamHalves, sl::kBwdStreamHalves));
+    hipLaunchKernelGGL(hssfsst::seg_pack_kernel, dim3(static_cast<unsigned>((most + 255) / 256)), dim3(256), 0, st, a);
+    if (int rc = launch_check("bilstm_set_weights", "seg_pack_kernel")) return rc;
+    p->packed = true;
+    return 0;
+}
+
+int hssfsst_bilstm_stash_floats(const hssfsst_bilstm* p, int64_t batch, int64_t steps, int64_t* floats)
+{
+    if (!floats) return fail(HSSFSST_EINVAL, "bilstm_stash_floats: floats is NULL");
+    *floats = 0;
+    (void)p;                                             // (every hidden size runs on the padded geometry: answered for a NULL plan too)
+    if (int rc = bilstm_check_shape("bilstm_stash_floats", batch, steps)) return rc;
+    *floats = hssfsst::seglayout::stash_floats(batch, steps);
+    return 0;
+}
+
+int hssfsst_bilstm_forward(hssfsst_bilstm* p, const float* x, int64_t batch, int64_t steps, const float* h0, const float* c0, float* y,
+                           float* hn, float* cn, float* stash, void* stream)
+{
+    if (!p) return fail(HSSFSST_EINVAL, "bilstm_forward: plan is NULL");
+    if (int rc = bilstm_check_shape("bilstm_forward", batch, steps)) return rc;
+    if (!x || !h0 || !c0 || !y || !hn || !cn || !stash)
+        return fail(HSSFSST_EINVAL, "bilstm_forward: bad argument (%s is NULL)",
+                    !x ? "x" : !h0 ? "h0" : !c0 ? "c0" : !y ? "y" : !hn ? "hn" : !cn ? "cn" : "stash");
+    if (!p->packed) return fail(HSSFSST_EINVAL, "bilstm_forward: no weights yet (call hssfsst_bilstm_set_weights first)");
+    DEVICE_SCOPE(p->device);
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const int B = static_cast<int>(batch), T = static_cast<int>(steps), H = p->H;
+    const int nbt = (B + hssfsst::kSegRows - 1) / hssfsst::kSegRows, Bp = nbt * hssfsst::kSegRows;
+    std::vector<hssfsst::seglayout::Chunk> chunks;
+    try {
+        chunks = hssfsst::seglayout::dense_chunks(T, nbt, kSegTileStepBytes, hssfsst::seglayout::kSegPreBytes);
+    } catch (const std::bad_alloc&) {
+        return fail(HSSFSST_ENOMEM, "bilstm_forward: out of host memory");
+    }
+    int rc;
+    const size_t nstate = static_cast<size_t>(4) * Bp * hssfsst::kSegHp;
+    if ((rc = p->d_pre.grow(hssfsst::seglayout::pre_floats(chunks, kSegTileStepBytes))) != 0) return rc;
+    if ((rc = p->d_state.grow(nstate)) != 0) return rc;
+    hipLaunchKernelGGL(hssfsst::seg_state_init_kernel<false>, dim3(static_cast<unsigned>((nstate + 255) / 256)), dim3(256), 0, st, h0, c0,
+                       p->d_state.get(), B, H, Bp, static_cast<const int*>(nullptr));
+    if ((rc = launch_check("bilstm_forward", "seg_state_init_kernel")) != 0) return rc;
+    hssfsst::SegProjArgs pa{};
+    pa.x = x; pa.x_dtype = HSSFSST_DTYPE_F32; pa.relu = 0;
+    pa.B = B; pa.T = T; pa.F = p->F; pa.Fp = p->Fp;
+    pa.wt = p->d_wt.get(); pa.bias = p->d_bias.get(); pa.pre = p->d_pre.get();
+    hssfsst::SegRecArgs ra{};
+    ra.B = B; ra.T = T; ra.H = H; ra.Bp = Bp;
+    ra.pre = p->d_pre.get(); ra.whh = p->d_whh.get(); ra.state = p->d_state.get(); ra.y = y;
+    ra.stash = stash; ra.inv_scale_dev = p->d_scale.get() + 1;
+    for (const hssfsst::seglayout::Chunk& c : chunks) {
+        pa.n = ra.n = c.n;
+        pa.Tc = ra.Tc = c.Tc;
+        pa.t0[0] = ra.t0[0] = c.s0;
+        pa.t0[1] = ra.t0[1] = T - c.s0 - c.n;
+        hipLaunchKernelGGL(hssfsst::seg_proj_kernel<false>, dim3(4 * hssfsst::kSegHp / 64, static_cast<unsigned>(c.tiles * ((c.n + 7) / 8)), 2),
+                           dim3(256), 0, st, pa);
+        if ((rc = launch_check("bilstm_forward", "seg_proj_kernel")) != 0) return rc;
+        hipLaunchKernelGGL((hssfsst::seg_rec_kernel<false, true>), dim3(static_cast<unsigned>(c.tiles), 2), dim3(64 * hssfsst::kSegWaves), 0, st, ra);
+        if ((rc = launch_check("bilstm_forward", "seg_rec_kernel<train>")) != 0) return rc;
+    }
+    const size_t nout = static_cast<size_t>(4) * B * H;
+    hipLaunchKernelGGL(hssfsst::seg_pair_out_kernel, dim3(static_cast<unsigned>((nout + 255) / 256)), dim3(256), 0, st, p->d_state.get(), hn, cn,
+                       B, H, Bp);
+    return launch_check("bilstm_forward", "seg_pair_out_kernel");
+}
+
+int hssfsst_bilstm_backward(hssfsst_bilstm* p, const float* stash, const float* c0, const float* dy, const float* dhn, const float* dcn,
+                            int64_t batch, int64_t steps, float* dgates, float* dh0, float* dc0, void* stream)
+{
+    if (!p) return fail(HSSFSST_EINVAL, "bilstm_backward: plan is NULL");
+    if (int rc = bilstm_check_shape("bilstm_backward", batch, steps)) return rc;
+    if (!stash || !c0 || !dy || !dgates || !dh0 || !dc0)
+        return fail(HSSFSST_EINVAL, "bilstm_backward: bad argument (%s is NULL)",
+                    !stash ? "stash" : !c0 ? "c0" : !dy ? "dy" : !dgates ? "dgates" : !dh0 ? "dh0" : "dc0");
+    if (!p->packed) return fail(HSSFSST_EINVAL, "bilstm_backward: no weights yet (call hssfsst_bilstm_set_weights first)");
+    DEVICE_SCOPE(p->device);
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const int B = static_cast<int>(batch), T = static_cast<int>(steps), H = p->H;
+    const int nbt = (B + hssfsst::kSegRows - 1) / hssfsst::kSegRows, Bp = nbt * hssfsst::kSegRows;
+    int rc;
+    const size_t nstate = static_cast<size_t>(4) * Bp * hssfsst::kSegHp;
+    if ((rc = p->d_state.grow(nstate)) != 0) return rc;
+    hipLaunchKernelGGL(hssfsst::seg_pair_init_kernel, dim3(static_cast<unsigned>((nstate + 255) / 256)), dim3(256), 0, st, dhn, dcn,
+                       p->d_state.get(), B, H, Bp);
+    if ((rc = launch_check("bilstm_backward", "seg_pair_init_kernel")) != 0) return rc;
+    hssfsst::SegBwdArgs a{};
+    a.stash = stash; a.c0 = c0; a.dy = dy; a.wbwd = p->d_bwd.get(); a.state = p->d_state.get(); a.dgates = dgates;
+    a.B = B; a.T = T; a.H = H; a.Bp = Bp;
+    // at most kSegMaxChunk steps per launch, chained through the carried (dh_rec, dc)
+    for (int s0 = 0; s0 < T; s0 += hssfsst::seglayout::kSegMaxChunk) {
+        a.s0 = s0;
+        a.n = std::min(hssfsst::seglayout::kSegMaxChunk, T - s0);
+        hipLaunchKernelGGL(hssfsst::seg_bwd_rec_kernel, dim3(static_cast<unsigned>(nbt), 2), dim3(64 * hssfsst::kSegWaves), 0, st, a);
+        if ((rc = launch_check("bilstm_backward", "seg_bwd_rec_kernel")) != 0) return rc;
+    }
+    const size_t nout = static_cast<size_t>(4) * B * H;
+    hipLaunchKernelGGL(hssfsst::seg_pair_out_kernel, dim3(static_cast<unsigned>((nout + 255) / 256)), dim3(256), 0, st, p->d_state.get(), dh0, dc0,
+                       B, H, Bp);
+    return launch_check("bilstm_backward", "seg_pair_out_kernel");
 }
 
 }  // extern "C"

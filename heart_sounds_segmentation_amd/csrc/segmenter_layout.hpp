@@ -108,4 +108,75 @@ inline std::vector<Chunk> ragged_chunks(const Layout& lay, size_t tile_step_byte
     return out;
 }
 
+// ---- Index arithmetic of the trainable layer (hssfsst.h: hssfsst_bilstm_*; kernels in segmenter_train.hpp) ----------------------
+// Plain functions of integers, shared by the device-side weight pack, the kernels, the host and tests/native/.  A table's
+// *_source function answers, for element i of the table, which element of the nn.LSTM tensor it holds (-1: padding, zero).
+#if defined(__HIPCC__)
+#define HSSFSST_SEG_HD __host__ __device__
+#else
+#define HSSFSST_SEG_HD
+#endif
+
+constexpr int kHp = 256;                                 // == kSegHp: the padded hidden size of every table
+constexpr int kGateCols = 4 * kHp;                       // gate columns of a direction, in (unit tile, gate, unit) order
+constexpr int kWaves = 8;                                // == kSegWaves
+constexpr long long kWtStreamHalves = 2LL * kWaves * (kHp / 32) * 8 * 64 * 16;       // forward W_hh stream, f16 elements
+constexpr long long kBwdStreamHalves = 2LL * kWaves * (kGateCols / 32) * 2 * 64 * 16; // backward W_hh^T stream, bf16 elements
+
+// gate column n = (unit tile * 4 + gate) * 16 + c  ->  row gate * H + unit of the (4H, .) tensors, -1 for a padded unit
+HSSFSST_SEG_HD inline long long gate_col_row(int n, int H)
+{
+    const int u = (n >> 6) * 16 + (n & 15), g = (n >> 4) & 3;
+    return u < H ? static_cast<long long>(g) * H + u : -1;
+}
+
+// wt [dir][Fp][4 Hp]: element i of one direction's table -> index into weight_ih (4H, F)
+HSSFSST_SEG_HD inline long long wt_source(long long i, int F, int H)
+{
+    const int k = static_cast<int>(i / kGateCols), n = static_cast<int>(i % kGateCols);
+    const long long row = gate_col_row(n, H);
+    return row >= 0 && k < F ? row * F + k : -1;
+}
+
+// forward stream [wave][K block 8][tile x gate 8][lane 64]{hi[8], lo[8]}: element i of one direction -> index into weight_hh
+// (4H, H), *lo = 1 for the low half of the split
+HSSFSST_SEG_HD inline long long fwd_stream_source(long long i, int H, int* lo)
+{
+    const int j = static_cast<int>(i & 7), lane = static_cast<int>(i >> 4) & 63, q = static_cast<int>(i >> 10) & 7;
+    const int kb = static_cast<int>(i >> 13) & 7, w = static_cast<int>(i >> 16) & 7;
+    *lo = static_cast<int>(i >> 3) & 1;
+    const int u = (w * 2 + (q >> 2)) * 16 + (lane & 15), g = q & 3, k = kb * 32 + 8 * (lane >> 4) + j;
+    return u < H && k < H ? (static_cast<long long>(g) * H + u) * H + k : -1;
+}
+
+// backward stream [wave][K block 32][output tile 2][lane 64]{hi[8], lo[8]}: the B operand of dh = dG . W_hh.  The product sums over
+// the gate columns kappa = K block * 32 + 8 (lane >> 4) + j (the order of the dG image) and wave w's output columns are the units
+// (2 w + tile) * 16 + (lane & 15) it owns in the forward pass.
+HSSFSST_SEG_HD inline long long bwd_stream_index(int w, int kb, int ot, int lane, int lo, int j)
+{
+    return ((((static_cast<long long>(w) * (kGateCols / 32) + kb) * 2 + ot) * 64 + lane) * 2 + lo) * 8 + j;
+}
+HSSFSST_SEG_HD inline long long bwd_stream_source(long long i, int H, int* lo)
+{
+    const int j = static_cast<int>(i & 7), lane = static_cast<int>(i >> 4) & 63, ot = static_cast<int>(i >> 10) & 1;
+    const int kb = static_cast<int>(i >> 11) & 31, w = static_cast<int>(i >> 16) & 7;
+    *lo = static_cast<int>(i >> 3) & 1;
+    const int kout = (2 * w + ot) * 16 + (lane & 15);
+    const long long row = gate_col_row(kb * 32 + 8 * (lane >> 4) + j, H);
+    return row >= 0 && kout < H ? row * H + kout : -1;
+}
+
+// The stash of a training forward: [dir][tile][t][wave][unit tile of the wave 2][i, f, g, o, c][lane 64][4 rows], float32
+constexpr int kStashQ = 5;
+constexpr long long kStashStepFloats = static_cast<long long>(kWaves) * 2 * kStashQ * 256;      // one (dir, tile, t): 80 KiB
+HSSFSST_SEG_HD inline long long stash_floats(long long batch, long long steps)
+{
+    return 2 * ((batch + kSlotRows - 1) / kSlotRows) * steps * kStashStepFloats;
+}
+HSSFSST_SEG_HD inline long long stash_index(long long tiles, long long steps, int dir, long long tile, long long t, int w, int tl, int q,
+                                            int lane, int r)
+{
+    return (((dir * tiles + tile) * steps + t) * (kWaves * 2) + (w * 2 + tl)) * (kStashQ * 256) + q * 256 + lane * 4 + r;
+}
+
 }  // namespace hssfsst::seglayout

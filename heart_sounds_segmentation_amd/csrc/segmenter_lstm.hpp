@@ -24,6 +24,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "segmenter_layout.hpp"
+
 namespace hssfsst {
 
 constexpr int kSegHp = 256;                    // padded hidden size == the supported maximum
@@ -181,6 +183,9 @@ struct SegRecArgs {
     const int* slot_len;
     const int* tile_walk;
     int s0;
+    // TRAIN (segmenter_train.hpp): what the backward pass needs of every step, and the scale where the device-side pack left it
+    float* stash;               // [dir][batch tile][T][wave][tile of the wave][i, f, g, o, c][lane][4] (seglayout::stash_index)
+    const float* inv_scale_dev;
 };
 
 __device__ __forceinline__ float seg_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
@@ -202,9 +207,11 @@ __device__ __forceinline__ void seg_put_h(_Float16* hi, _Float16* lo, int unit, 
 
 // Grid (batch tiles, 2 directions), block 512.  Direction 0 walks the chunk's steps upwards, direction 1 downwards.  RAGGED: both
 // walk step indices upwards; the trip count is the tile's (uniform in the workgroup), the rows' ends are selects.
-template <bool RAGGED>
+// TRAIN (dense only): the same arithmetic; each wave also stores the activated gates and c of the cells it holds, per step.
+template <bool RAGGED, bool TRAIN = false>
 __global__ __launch_bounds__(512) void seg_rec_kernel(SegRecArgs a)
 {
+    static_assert(!(RAGGED && TRAIN), "training is dense only");
     constexpr int HB = kSegKb * 4 * kSegRows * 8;                       // halves of one plane of the h image
     __shared__ __attribute__((aligned(16))) _Float16 hbuf[2][2][HB];   // [buffer][hi, lo]
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -215,6 +222,8 @@ __global__ __launch_bounds__(512) void seg_rec_kernel(SegRecArgs a)
     float* hst = a.state + (static_cast<size_t>(dir) * a.Bp + b0) * kSegHp;
     float* cst = hst + plane;
     const int n = RAGGED ? min(a.Tc, a.tile_walk[bt] - a.s0) : a.n;
+    float inv_scale = a.inv_scale;
+    if constexpr (TRAIN) inv_scale = *a.inv_scale_dev;
     int rem[4], yrow[4];                                                // RAGGED: row r is live while s < rem[r]; its y row at s = 0
     if constexpr (RAGGED) {
 #pragma unroll
@@ -308,12 +317,13 @@ __global__ __launch_bounds__(512) void seg_rec_kernel(SegRecArgs a)
 #pragma unroll
         for (int tl = 0; tl < 2; ++tl) {
             const int unit = (w * 2 + tl) * 16 + (lane & 15);
+            [[maybe_unused]] seg_f4 sg[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const float gi = seg_sigmoid(fmaf(acc[tl * 4 + 0][r], a.inv_scale, pn[tl * 4 + 0][r]));
-                const float gf = seg_sigmoid(fmaf(acc[tl * 4 + 1][r], a.inv_scale, pn[tl * 4 + 1][r]));
-                const float gg = seg_tanh(fmaf(acc[tl * 4 + 2][r], a.inv_scale, pn[tl * 4 + 2][r]));
-                const float go = seg_sigmoid(fmaf(acc[tl * 4 + 3][r], a.inv_scale, pn[tl * 4 + 3][r]));
+                const float gi = seg_sigmoid(fmaf(acc[tl * 4 + 0][r], inv_scale, pn[tl * 4 + 0][r]));
+                const float gf = seg_sigmoid(fmaf(acc[tl * 4 + 1][r], inv_scale, pn[tl * 4 + 1][r]));
+                const float gg = seg_tanh(fmaf(acc[tl * 4 + 2][r], inv_scale, pn[tl * 4 + 2][r]));
+                const float go = seg_sigmoid(fmaf(acc[tl * 4 + 3][r], inv_scale, pn[tl * 4 + 3][r]));
                 if constexpr (RAGGED) {
                     const bool live = s < rem[r];
                     const float cn = fmaf(gf, c[tl][r], gi * gg);
@@ -327,7 +337,14 @@ __global__ __launch_bounds__(512) void seg_rec_kernel(SegRecArgs a)
                     h[tl][r] = go * seg_tanh(c[tl][r]);
                     const int b = b0 + row0 + r;
                     if (b < a.B && unit < a.H) a.y[(static_cast<size_t>(b) * a.T + t) * (2 * a.H) + dir * a.H + unit] = h[tl][r];
+                    if constexpr (TRAIN) { sg[0][r] = gi; sg[1][r] = gf; sg[2][r] = gg; sg[3][r] = go; }
                 }
+            }
+            if constexpr (TRAIN) {
+                float* sp = a.stash + seglayout::stash_index(nbt, a.T, dir, bt, t, w, tl, 0, lane, 0);
+#pragma unroll
+                for (int q = 0; q < 4; ++q) *reinterpret_cast<seg_f4*>(sp + q * kSegTileFloats) = sg[q];
+                *reinterpret_cast<seg_f4*>(sp + 4 * kSegTileFloats) = c[tl];
             }
             seg_put_h(hbuf[cur ^ 1][0], hbuf[cur ^ 1][1], unit, row0, h[tl]);
         }

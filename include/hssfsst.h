@@ -390,6 +390,40 @@ int hssfsst_segmenter_exec(hssfsst_segmenter* plan, const void* feats, int feats
 int hssfsst_segmenter_exec_ragged(hssfsst_segmenter* plan, const void* feats, int feats_dtype, const int64_t* offsets,
                                   int64_t count, const float* h0, const float* c0, int state_rows, float* logp, void* stream);
 
+/* One DIFFERENTIABLE bidirectional LSTM layer (batch first, nn.LSTM's cell and gate order): the unit a training program stacks
+ * under autograd -- the segmenter is two of them.  The plan holds the layer's current weights in the kernels' layouts and the
+ * scratch of its calls; the caller owns inputs, outputs and the stash.  Every pointer below is a DEVICE pointer on the plan's
+ * device unless marked host; float32, dense (batch, steps, .) only.  Kernels: csrc/segmenter_train.hpp.  Every call is enqueued on
+ * `stream` without any host synchronisation.  Single-stream and single-thread like the other plans.
+ *   create       input_size < 1, hidden < 1, device < 0 or a NULL out: HSSFSST_EINVAL; hidden > 256: HSSFSST_EUNSUPPORTED; both
+ *                before any device is touched.
+ *   set_weights  weights: HOST array of 8 device pointers in state_dict order (weight_ih (4 hidden, input_size), weight_hh
+ *                (4 hidden, hidden), bias_ih, bias_hh (4 hidden) of the forward direction, then of the reverse one).  Packs them on
+ *                the device into the forward kernels' tables (the arithmetic of hssfsst_segmenter_create, scale included) and the
+ *                split-bf16 operand stream of the backward product.  Call it again whenever the weights changed; forward and
+ *                backward before the first call return HSSFSST_EINVAL.
+ *   stash_floats floats <- the float32 elements of the stash of a (batch, steps) forward: 2 x ceil(batch / 16) x steps x 20480
+ *                (80 KiB per direction, 16 rows and step; 1.3 GB at batch 50 x 2000 steps).  Host only; the plan may be NULL.
+ *   forward      y (batch, steps, 2 hidden), hn, cn (2, batch, hidden) <- the layer on x (batch, steps, input_size) from h0, c0
+ *                (2, batch, hidden), by the projection and recurrence kernels of hssfsst_segmenter_exec.  Every step's
+ *                activated gates and cell state go to `stash`, which the caller keeps until the backward call.
+ *   backward     dy (batch, steps, 2 hidden), dhn, dcn (2, batch, hidden; NULL = zero): the gradients of y, hn, cn.  Writes
+ *                dgates (2, batch, steps, 4 hidden) -- per direction the gradient of the pre-activation gates i, f, g, o, from
+ *                which the weight, bias and input gradients are plain matrix products -- and dh0, dc0 (2, batch, hidden).  The
+ *                recurrent product dgates . W_hh runs on split-bf16 operands (hi.hi + hi.lo + lo.hi) with float32 accumulation.
+ *                The plan's weights must still be those of the forward call.
+ * NULL pointers, batch < 1 or steps < 1 and sizes over the limits of hssfsst_segmenter_exec return HSSFSST_EINVAL before any
+ * device work. */
+typedef struct hssfsst_bilstm hssfsst_bilstm;
+int hssfsst_bilstm_create(hssfsst_bilstm** out, int device, int input_size, int hidden);
+int hssfsst_bilstm_destroy(hssfsst_bilstm* plan);
+int hssfsst_bilstm_set_weights(hssfsst_bilstm* plan, const float* const* weights, void* stream);
+int hssfsst_bilstm_stash_floats(const hssfsst_bilstm* plan, int64_t batch, int64_t steps, int64_t* floats);
+int hssfsst_bilstm_forward(hssfsst_bilstm* plan, const float* x, int64_t batch, int64_t steps, const float* h0, const float* c0,
+                           float* y, float* hn, float* cn, float* stash, void* stream);
+int hssfsst_bilstm_backward(hssfsst_bilstm* plan, const float* stash, const float* c0, const float* dy, const float* dhn,
+                            const float* dcn, int64_t batch, int64_t steps, float* dgates, float* dh0, float* dc0, void* stream);
+
 int hssfsst_device_count(void);
 int hssfsst_version(void);
 const char* hssfsst_last_error(void);
