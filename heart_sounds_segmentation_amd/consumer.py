@@ -92,7 +92,12 @@ class HipSegmenter:
     """What ``SegmenterHead.hip()`` returns.  ``seg(feats)``: feats a (B, T, F) float32 / float16 / bfloat16 tensor on
     the plan's GPU -> (B, T, 4) float32 log-probs on the same device, no autograd graph, enqueued on the current stream.
     The module's ``h0`` / ``c0`` fix B (the reference ties the model to one batch size, segmenter.py:38-41): another B
-    raises ValueError unless ``h0`` and ``c0`` of shape (2, B, H) are passed to the call."""
+    raises ValueError unless ``h0`` and ``c0`` of shape (2, B, H) are passed to the call.
+
+    Limit, here and in ``ragged``: every element of ``h0`` must satisfy ``|h0| < 64`` (``c0``: any finite value).  The kernels feed
+    ``h x 1024`` to the recurrent product in float16, sized for an LSTM's own ``|h| < 1``; an ``h0`` element of 64 or more is
+    infinite there and its row comes back NaN from the first step on, without an error -- ``h0`` is device memory and the call does
+    not synchronise, so nothing checks it.  randn states are far inside; tested up to +-63."""
 
     def __init__(self, head: SegmenterHead, device=None):
         if head.training:
@@ -300,7 +305,9 @@ class HipBiLSTM(nn.Module):
     gates and cell state in a stash; the backward recurrence is a HIP kernel (csrc/segmenter_train.hpp), the weight and input
     gradients are ``torch.matmul`` on its output.  The weights are repacked on the device (no host synchronisation) whenever a
     parameter changed since the last forward.  The stash costs 2 x ceil(B / 16) x T x 80 KiB per layer and forward call: about
-    1.3 GB at B 50, T 2000, whatever the hidden size.  hidden_size <= 256.  No CPU path: without a GPU, RuntimeError."""
+    1.3 GB at B 50, T 2000, whatever the hidden size.  hidden_size <= 256.  ``|h0| < 64`` in every element (the limit of
+    ``HipSegmenter``, for the same reason, unchecked: a larger one makes its row NaN, gradients included); ``c0`` any finite value.
+    No CPU path: without a GPU, RuntimeError."""
 
     def __init__(self, input_size: int, hidden_size: int):
         super().__init__()

@@ -365,7 +365,11 @@ int hssfsst_segmenter_info(const hssfsst_segmenter* plan, int* input_size, int* 
  * F16 / BF16 (half features are converted on load: the result is bit-identical to the float32 call on the converted features);
  * h0, c0: (2, batch, hidden) float32.  All DEVICE pointers on the plan's device.  Any batch >= 1, any steps >= 1; the time axis is
  * walked in chunks (forward ascending, reverse descending) with the state carried on the device.  Enqueued on `stream`
- * (hipStream_t, NULL = default) without synchronising. */
+ * (hipStream_t, NULL = default) without synchronising.
+ * LIMIT: |h0| < 64 in every element (c0: any finite value).  h enters the recurrent product as h x 1024 in float16, which is
+ * sized for an LSTM's own |h| < 1; an h0 element of magnitude 64 or more (exactly: from 64 - 2^-6 on) becomes infinite there
+ * and its batch row is NaN from the first step on.  Nothing checks this: h0 is device memory and the call does not synchronise.
+ * Tested up to +-63. */
 int hssfsst_segmenter_exec(hssfsst_segmenter* plan, const void* feats, int feats_dtype, int64_t batch, int64_t steps,
                            const float* h0, const float* c0, float* logp, void* stream);
 
@@ -373,7 +377,8 @@ int hssfsst_segmenter_exec(hssfsst_segmenter* plan, const void* feats, int feats
  * recording i is rows offsets[i] .. offsets[i + 1] of feats (sum T, input_size), and its log-probs land in the same rows of logp
  * (sum T, 4).  offsets: int64 HOST array of count + 1 step offsets, offsets[0] == 0, strictly increasing.  h0, c0: (2, state_rows,
  * hidden) float32 with state_rows == count (recording i starts from row i) or 1 (every recording starts from the same state: the
- * reference model built with batch_size = 1 and fed one recording per step).  feats, h0, c0, logp: DEVICE pointers.
+ * reference model built with batch_size = 1 and fed one recording per step).  feats, h0, c0, logp: DEVICE pointers.  |h0| < 64
+ * in every element, as for hssfsst_segmenter_exec (unchecked; a larger one makes its recording NaN).
  * For every i the result is bit-identical to hssfsst_segmenter_exec on that recording alone (batch 1, its own state row): the
  * forward direction from its first step, the reverse direction from its own last step, lstm_2 seeded with lstm_1's state at the
  * recording's own ends.  Padding to (count, T_max) cannot give that.
@@ -406,7 +411,8 @@ int hssfsst_segmenter_exec_ragged(hssfsst_segmenter* plan, const void* feats, in
  *                (80 KiB per direction, 16 rows and step; 1.3 GB at batch 50 x 2000 steps).  Host only; the plan may be NULL.
  *   forward      y (batch, steps, 2 hidden), hn, cn (2, batch, hidden) <- the layer on x (batch, steps, input_size) from h0, c0
  *                (2, batch, hidden), by the projection and recurrence kernels of hssfsst_segmenter_exec.  Every step's
- *                activated gates and cell state go to `stash`, which the caller keeps until the backward call.
+ *                activated gates and cell state go to `stash`, which the caller keeps until the backward call.  |h0| < 64 in
+ *                every element, as for hssfsst_segmenter_exec (unchecked; a larger one makes its row NaN, gradients included).
  *   backward     dy (batch, steps, 2 hidden), dhn, dcn (2, batch, hidden; NULL = zero): the gradients of y, hn, cn.  Writes
  *                dgates (2, batch, steps, 4 hidden) -- per direction the gradient of the pre-activation gates i, f, g, o, from
  *                which the weight, bias and input gradients are plain matrix products -- and dh0, dc0 (2, batch, hidden).  The
