@@ -86,26 +86,59 @@ def build(force: bool = False, verbose: bool = False) -> str:
     return LIB_PATH
 
 
+def _llvm_tools(*names) -> dict:
+    """Paths of the llvm tools that look into the built library; RuntimeError when one is missing."""
+    import shutil
+    llvm = "/opt/rocm/lib/llvm/bin"
+    tools = {t: (shutil.which(t) or os.path.join(llvm, t)) for t in names}
+    tools["objcopy"] = shutil.which("objcopy") or shutil.which("llvm-objcopy") or os.path.join(llvm, "llvm-objcopy")
+    for t in tools.values():
+        if not os.path.exists(t):
+            raise RuntimeError(f"check_code_object: {t} not found")
+    return tools
+
+
+def _unbundle(tools: dict, path: str, td: str) -> str:
+    """The gfx950 code object inside the library ``path``, written into the directory ``td``."""
+    fat, obj = os.path.join(td, "fat.bin"), os.path.join(td, "code.o")
+    subprocess.run([tools["objcopy"], "-O", "binary", "--only-section=.hip_fatbin", path, fat], check=True, capture_output=True)
+    subprocess.run([tools["clang-offload-bundler"], "--unbundle", "--type=o", f"--input={fat}", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950",
+                    f"--output={obj}"], check=True, capture_output=True)
+    return obj
+
+
+def kernel_resources(match: str, path: str = None) -> dict:
+    """What the SHIPPED code object says of its kernels whose name contains ``match``: ``llvm-readelf --notes`` of the gfx950 code
+    object inside the library -> {mangled name: {"vgpr_count", "agpr_count", "sgpr_count", "private_segment_fixed_size" (scratch
+    bytes per lane), "group_segment_fixed_size" (LDS bytes)}}.  RuntimeError without the llvm tools."""
+    import re
+    import tempfile
+    tools = _llvm_tools("clang-offload-bundler", "llvm-readelf")
+    with tempfile.TemporaryDirectory() as td:
+        obj = _unbundle(tools, path or LIB_PATH, td)
+        notes = subprocess.run([tools["llvm-readelf"], "--notes", obj], check=True, capture_output=True, text=True).stdout
+    out = {}
+    fields = ("vgpr_count", "agpr_count", "sgpr_count", "private_segment_fixed_size", "group_segment_fixed_size")
+    for blk in re.split(r"\n\s*- \.agpr_count:", notes)[1:]:
+        blk = ".agpr_count:" + blk
+        name = re.search(r"\.name:\s+(\S+)", blk)
+        if not name or match not in name.group(1):
+            continue
+        out[name.group(1)] = {f: int(re.search(r"\." + f + r":\s+(\d+)", blk).group(1)) for f in fields}
+    return out
+
+
 def check_code_object(path: str = None) -> dict:
     """The SHIPPED code object, looked at: fsst_team16_kernel keeps its held images in v104..v127 through inline assembly and compiles for 104
     allocatable registers (fsst_team16.hpp) -- a compiler that stopped honouring the limit, started using AGPRs or outlined a call would corrupt
     features silently.  Disassembles the gfx950 code object inside the library and asserts, for every team kernel: the only instructions
     that name a register >= v104 are the two accessors, all twelve pairs are used, no AGPR, no call, 128 registers reserved.  Returns counts."""
     import re
-    import shutil
     import tempfile
     path = path or LIB_PATH
-    llvm = "/opt/rocm/lib/llvm/bin"
-    tools = {t: (shutil.which(t) or os.path.join(llvm, t)) for t in ("clang-offload-bundler", "llvm-objdump", "llvm-readelf")}
-    objcopy = shutil.which("objcopy") or shutil.which("llvm-objcopy") or os.path.join(llvm, "llvm-objcopy")
-    for t in list(tools.values()) + [objcopy]:
-        if not os.path.exists(t):
-            raise RuntimeError(f"check_code_object: {t} not found")
+    tools = _llvm_tools("clang-offload-bundler", "llvm-objdump", "llvm-readelf")
     with tempfile.TemporaryDirectory() as td:
-        fat, obj = os.path.join(td, "fat.bin"), os.path.join(td, "code.o")
-        subprocess.run([objcopy, "-O", "binary", "--only-section=.hip_fatbin", path, fat], check=True, capture_output=True)
-        subprocess.run([tools["clang-offload-bundler"], "--unbundle", "--type=o", f"--input={fat}", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950",
-                        f"--output={obj}"], check=True, capture_output=True)
+        obj = _unbundle(tools, path, td)
         dis = subprocess.run([tools["llvm-objdump"], "-d", "--mcpu=gfx950", obj], check=True, capture_output=True, text=True).stdout.split("\n")
         notes = subprocess.run([tools["llvm-readelf"], "--notes", obj], check=True, capture_output=True, text=True).stdout
     starts = [i for i, ln in enumerate(dis) if re.match(r"^[0-9a-f]+ <_ZN7hssfsst18fsst_team16_kernel.*>:", ln)]
@@ -269,6 +302,12 @@ def lib():
         L.hssfsst_bilstm_forward.restype = c_int
         L.hssfsst_bilstm_backward.argtypes = [vp, vp, vp, vp, vp, vp, c_i64, c_i64, vp, vp, vp, vp]
         L.hssfsst_bilstm_backward.restype = c_int
+        L.hssfsst_bilstm_stash_floats_ragged.argtypes = [vp, ctypes.POINTER(c_i64), c_i64, ctypes.POINTER(c_i64)]
+        L.hssfsst_bilstm_stash_floats_ragged.restype = c_int
+        L.hssfsst_bilstm_forward_ragged.argtypes = [vp, vp, ctypes.POINTER(c_i64), c_i64, vp, vp, vp, vp, vp, vp, vp]
+        L.hssfsst_bilstm_forward_ragged.restype = c_int
+        L.hssfsst_bilstm_backward_ragged.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.POINTER(c_i64), c_i64, vp, vp, vp, vp]
+        L.hssfsst_bilstm_backward_ragged.restype = c_int
         L.hssfsst_device_count.restype = c_int
         L.hssfsst_version.restype = c_int
         L.hssfsst_last_error.restype = ctypes.c_char_p

@@ -16,7 +16,8 @@ different lengths go through ``segment_recordings(fsst, head.hip(), recordings)`
 hssfsst_segmenter_exec_ragged) in one call.
 
 ``HipBiLSTM`` is one differentiable bidirectional layer on the HIP recurrences (hssfsst_bilstm_*; csrc/segmenter_train.hpp) and
-``HipSegmenterHead`` the same model built from two of them: what a training script uses instead of the ``nn.LSTM`` model.
+``HipSegmenterHead`` the same model built from two of them: what a training script uses instead of the ``nn.LSTM`` model.  Both
+have a ``ragged`` form that trains on whole recordings of different lengths in one call (hssfsst_bilstm_*_ragged).
 """
 from __future__ import annotations
 
@@ -297,6 +298,66 @@ class _BiLSTMFunction(torch.autograd.Function):
         return (None, dx, dh0, dc0, *grads)
 
 
+class _RaggedBiLSTMFunction(torch.autograd.Function):
+    """``_BiLSTMFunction`` on an arena of recordings: hssfsst_bilstm_forward_ragged / hssfsst_bilstm_backward_ragged, then the same
+    time-parallel products as torch.matmul over the arena's rows.  ``offs``: the host offsets, an int64 numpy array."""
+
+    @staticmethod
+    def forward(ctx, layer, offs, x, h0, c0, *weights):
+        B, total, H = len(offs) - 1, int(x.shape[0]), layer.hidden_size
+        plan = layer._sync_plan(x.device, weights)
+        L = _lib.lib()
+        x, h0, c0 = x.contiguous(), h0.contiguous(), c0.contiguous()
+        optr = offs.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
+        floats = ctypes.c_int64()
+        _lib.check(L.hssfsst_bilstm_stash_floats_ragged(plan, optr, B, ctypes.byref(floats)), "hssfsst_bilstm_stash_floats_ragged")
+        stash = torch.empty(floats.value, dtype=torch.float32, device=x.device)
+        y = torch.empty((total, 2 * H), dtype=torch.float32, device=x.device)
+        hn = torch.empty((2, B, H), dtype=torch.float32, device=x.device)
+        cn = torch.empty_like(hn)
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        _lib.check(L.hssfsst_bilstm_forward_ragged(plan, x.data_ptr(), optr, B, h0.data_ptr(), c0.data_ptr(), y.data_ptr(),
+                                                   hn.data_ptr(), cn.data_ptr(), stash.data_ptr(), stream), "hssfsst_bilstm_forward_ragged")
+        ctx.layer, ctx.serial, ctx.offs = layer, layer._serial, offs
+        ctx.save_for_backward(x, h0, c0, y, stash, *weights)
+        return y, hn, cn
+
+    @staticmethod
+    def backward(ctx, dy, dhn, dcn):
+        layer, offs = ctx.layer, ctx.offs
+        if layer._serial != ctx.serial:
+            raise RuntimeError("HipBiLSTM: the layer's weights were repacked for other values between this forward and its "
+                               "backward; the backward recurrence would run against the wrong W_hh")
+        x, h0, c0, y, stash, *weights = ctx.saved_tensors
+        B, total, H = len(offs) - 1, int(x.shape[0]), layer.hidden_size
+        dy = torch.zeros_like(y) if dy is None else dy.contiguous()
+        dhn = None if dhn is None else dhn.contiguous()
+        dcn = None if dcn is None else dcn.contiguous()
+        dgates = torch.empty((2, total, 4 * H), dtype=torch.float32, device=x.device)
+        dh0 = torch.empty((2, B, H), dtype=torch.float32, device=x.device)
+        dc0 = torch.empty_like(dh0)
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        _lib.check(_lib.lib().hssfsst_bilstm_backward_ragged(layer._plan, stash.data_ptr(), c0.data_ptr(), dy.data_ptr(),
+                                                             None if dhn is None else dhn.data_ptr(),
+                                                             None if dcn is None else dcn.data_ptr(),
+                                                             offs.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), B, dgates.data_ptr(),
+                                                             dh0.data_ptr(), dc0.data_ptr(), stream), "hssfsst_bilstm_backward_ragged")
+        # h before each step: y shifted by one arena row, with h0 written at each recording's first (reverse: last) row
+        edges = torch.from_numpy(offs).to(x.device)
+        hf = torch.cat((y.new_zeros(1, H), y[:-1, :H]))
+        hf[edges[:-1]] = h0[0]
+        hr = torch.cat((y[1:, H:], y.new_zeros(1, H)))
+        hr[edges[1:] - 1] = h0[1]
+        grads = []
+        for g, hprev in ((dgates[0], hf), (dgates[1], hr)):
+            db = g.sum(0)
+            grads += [g.t() @ x, g.t() @ hprev, db, db.clone()]
+        dx = None
+        if ctx.needs_input_grad[2]:
+            dx = dgates[0] @ weights[0] + dgates[1] @ weights[4]
+        return (None, None, dx, dh0, dc0, *grads)
+
+
 class HipBiLSTM(nn.Module):
     """One bidirectional, batch-first LSTM layer that TRAINS on the HIP kernels: ``y, (hn, cn) = layer(x, (h0, c0))`` with
     x (B, T, input_size), h0 / c0 (2, B, hidden_size), all float32 on the GPU, differentiable in x, h0, c0 and the weights.
@@ -387,6 +448,46 @@ class HipBiLSTM(nn.Module):
         y, hn, cn = _BiLSTMFunction.apply(self, x, h0, c0, *weights)
         return y, (hn, cn)
 
+    def ragged(self, x: torch.Tensor, offsets, state):
+        """The layer on whole recordings of DIFFERENT lengths in one call: ``y, (hn, cn) = layer.ragged(x, offsets, (h0, c0))``.
+        ``x``: a ``(sum T, input_size)`` float32 arena on the GPU, recording i in rows ``offsets[i] .. offsets[i + 1]``; ``offsets``:
+        a list or an int64 tensor of B + 1 offsets from 0 (read on the host); ``h0`` / ``c0``: ``(2, B, hidden_size)``.  ``y`` is the
+        ``(sum T, 2 hidden_size)`` arena, ``hn`` / ``cn`` ``(2, B, hidden_size)`` in list order.  Differentiable in x, h0, c0 and the
+        weights like the dense call, and recording i gets the bits of ``layer(x_i[None], (h0[:, i:i+1], c0[:, i:i+1]))`` in y, hn,
+        cn, dh0 and dc0: forward from its first step, reverse from its own last one, which padding to ``(B, T_max, F)`` cannot
+        give.  (The weight and input gradients are one ``torch.matmul`` over all rows: the sum of the per-recording ones up to
+        the rounding of a longer sum.)  The stash costs 2 x (sum over tiles of 16 recordings, longest first, of the tile's longest
+        recording) x 80 KiB per layer and call: 5.8 GB per layer for one tile of 35 500-step recordings.  An empty list gives
+        empty results.  ``|h0| < 64``, as for the dense call."""
+        L = _lib.lib()
+        del L
+        _lib.guard_fork()
+        if not torch.cuda.is_available():
+            raise RuntimeError("HipBiLSTM: no GPU; the BiLSTM kernels have no CPU path")
+        h0, c0 = state
+        weights = [getattr(self, k) for k in _LSTM_KEYS]
+        if x.device.type != "cuda" or any(t.device != x.device for t in (h0, c0, *weights)):
+            raise RuntimeError(f"HipBiLSTM.ragged: input, state and parameters must be on one GPU (input on {x.device}, "
+                               f"parameters on {weights[0].device}); there is no CPU path")
+        offs = np.ascontiguousarray(offsets.detach().cpu().numpy() if isinstance(offsets, torch.Tensor) else offsets, dtype=np.int64)
+        if offs.ndim != 1 or offs.shape[0] < 1:
+            raise ValueError("HipBiLSTM.ragged: offsets must be a 1-D sequence of B + 1 step offsets")
+        B = int(offs.shape[0]) - 1
+        if x.dim() != 2 or x.shape[1] != self.input_size or x.shape[0] != int(offs[-1]) or int(offs[0]) != 0:
+            raise ValueError(f"HipBiLSTM.ragged: an arena of shape (offsets[-1], {self.input_size}) and offsets from 0 expected, got "
+                             f"{tuple(x.shape)} and offsets {int(offs[0])} .. {int(offs[-1])}")
+        want = (2, B, self.hidden_size)
+        if tuple(h0.shape) != want or tuple(c0.shape) != want:
+            raise ValueError(f"HipBiLSTM.ragged: h0 and c0 of shape {want} expected, got {tuple(h0.shape)} and {tuple(c0.shape)}")
+        if any(t.dtype != torch.float32 for t in (x, h0, c0, *weights)):
+            raise ValueError("HipBiLSTM.ragged: float32 input, state and parameters expected (cast half-precision features first)")
+        if any(not w.is_contiguous() for w in weights):
+            raise ValueError("HipBiLSTM.ragged: contiguous parameters expected")
+        if B == 0:
+            return x.new_empty((0, 2 * self.hidden_size)), (h0.clone(), c0.clone())
+        y, hn, cn = _RaggedBiLSTMFunction.apply(self, offs, x, h0, c0, *weights)
+        return y, (hn, cn)
+
 
 class HipSegmenterHead(SegmenterHead):
     """``SegmenterHead`` whose two BiLSTM layers are ``HipBiLSTM``: the same constructor, ``state_dict`` keys, ``h0`` / ``c0``
@@ -399,6 +500,73 @@ class HipSegmenterHead(SegmenterHead):
         super().__init__(input_size, hidden_size, batch_size, h0=h0, c0=c0)
         self.lstm_1 = HipBiLSTM.from_lstm(self.lstm_1)
         self.lstm_2 = HipBiLSTM.from_lstm(self.lstm_2)
+
+    def ragged(self, feats, h0: Optional[torch.Tensor] = None, c0: Optional[torch.Tensor] = None) -> RaggedFeatures:
+        """``forward`` on whole recordings of DIFFERENT lengths in one call, for training: layer 1 -> ReLU -> Dropout -> layer 2
+        seeded with layer 1's (hn, cn) -> ReLU -> Dropout -> Linear -> log_softmax, in ``train()`` and ``eval()``, every recording
+        from its own first and last step (``HipBiLSTM.ragged``).  ``feats``: a non-raw ``RaggedFeatures`` (``FSST.ragged``) or a list
+        of ``(T_i, F)`` tensors on the module's GPU; float16 / bfloat16 features are cast to float32 with one torch op (a copy of the
+        arena: half input to the kernels is not there).  Returns a ``RaggedFeatures`` over the ``(sum T, 4)`` arena of log-probs,
+        whose ``data`` carries the autograd graph: ``nll_loss(out.data, torch.cat(labels))`` is the loss over all steps.
+
+        ``h0`` / ``c0``: ``(2, B, H)``, or ``(2, 1, H)`` to start every recording from the same state (expanded in torch, so autograd
+        sums its gradient); omitted, the module's own are used when their batch is B or 1, else ValueError.
+
+        The stash of the two layers costs 2 x 2 x (sum over tiles of the tile's longest recording) x 80 KiB: 5.8 GB per layer for
+        one tile of 35 500-step recordings.  Split the list to bound it."""
+        name = "HipSegmenterHead.ragged"
+        F, H = self.lstm_1.input_size, self.lstm_1.hidden_size
+        L = _lib.lib()
+        del L
+        _lib.guard_fork()
+        if not torch.cuda.is_available():
+            raise RuntimeError(f"{name}: no GPU; the BiLSTM kernels have no CPU path")
+        device = self.linear.weight.device
+        if isinstance(feats, RaggedFeatures):
+            if feats._raw:
+                raise ValueError(f"{name}: raw (complex, frequency-major) features; the segmenter takes abs or stack features")
+            data, offs = feats.data, [int(o) for o in feats._off]
+        elif isinstance(feats, (list, tuple)):
+            for i, f in enumerate(feats):
+                if not isinstance(f, torch.Tensor) or f.dim() != 2 or f.shape[0] < 1:
+                    raise ValueError(f"{name}: item {i} is not a (T, {F}) tensor with T >= 1")
+            if len({(f.device, f.dtype, int(f.shape[1])) for f in feats}) > 1:
+                raise ValueError(f"{name}: the items differ in device, dtype or width")
+            offs = [0]
+            for f in feats:
+                offs.append(offs[-1] + int(f.shape[0]))
+            data = torch.cat(list(feats)) if feats else torch.empty((0, F), device=device)
+        else:
+            raise ValueError(f"{name}: a RaggedFeatures or a list of (T, F) tensors expected")
+        B = len(offs) - 1
+        if data.dim() != 2 or data.shape[1] != F or data.shape[0] != offs[-1]:
+            raise ValueError(f"{name}: features of shape (sum T, {F}) expected, got {tuple(data.shape)}")
+        if data.device != device:
+            raise ValueError(f"{name}: features on {data.device}, the module on {device}")
+        if data.dtype not in _DTYPES:
+            raise ValueError(f"{name}: float32, float16 or bfloat16 features expected, got {data.dtype}")
+        if (h0 is None) != (c0 is None):
+            raise ValueError(f"{name}: pass both h0 and c0, or neither")
+        if h0 is None:
+            if self.h0.shape[1] not in (B, 1) and B:
+                raise ValueError(f"{name}: {B} recordings, but the module's h0 / c0 were made for batch {self.h0.shape[1]} "
+                                 "(pass h0 and c0 of shape (2, B, H) or (2, 1, H) to the call)")
+            h0, c0 = self.h0, self.c0
+        else:
+            ok = ((2, B, H), (2, 1, H))
+            if tuple(h0.shape) not in ok or tuple(c0.shape) != tuple(h0.shape):
+                raise ValueError(f"{name}: h0 and c0 of shape {ok[0]} or {ok[1]} expected, got {tuple(h0.shape)} and {tuple(c0.shape)}")
+            h0, c0 = h0.to(device, torch.float32), c0.to(device, torch.float32)
+        offsets = torch.tensor(offs, dtype=torch.int64)
+        if B == 0:
+            return RaggedFeatures(torch.empty((0, 4), dtype=torch.float32, device=device), offsets, 4, False)
+        if h0.shape[1] != B:
+            h0, c0 = h0.expand(2, B, H), c0.expand(2, B, H)
+        x = data.float()                                     # (half features: the one cast, a float32 copy of the arena)
+        y, carry = self.lstm_1.ragged(x, offs, (h0.contiguous(), c0.contiguous()))
+        y, _ = self.lstm_2.ragged(self.drop(torch.relu(y)), offs, carry)
+        logp = torch.log_softmax(self.linear(self.drop(torch.relu(y))), dim=1)
+        return RaggedFeatures(logp, offsets, 4, False)
 
 
 def segment(fsst, head, windows: torch.Tensor) -> torch.Tensor:

@@ -2407,6 +2407,27 @@ int seg_check_dtype(const char* what, int feats_dtype)
     return 0;
 }
 
+// The list of a ragged call (count >= 1): count + 1 host offsets from 0, strictly increasing, no recording over the dense step
+// limit, fewer than 2^31 steps in all.  One text for every entry point that takes such a list.
+int seg_check_list(const char* what, const int64_t* offsets, int64_t count)
+{
+    namespace seglayout = hssfsst::seglayout;
+    if (!offsets) return fail(HSSFSST_EINVAL, "%s: offsets is NULL", what);
+    if (count > kSegMaxBatch) return fail(HSSFSST_EINVAL, "%s: count %lld too large", what, static_cast<long long>(count));
+    if (offsets[0] != 0) return fail(HSSFSST_EINVAL, "%s: offsets[0] is %lld, not 0", what, static_cast<long long>(offsets[0]));
+    if (const int64_t i = seglayout::first_bad_length(offsets, count, kSegMaxSteps); i >= 0) {
+        if (offsets[i + 1] <= offsets[i])
+            return fail(HSSFSST_EINVAL, "%s: offsets do not increase at index %lld (offsets[%lld] = %lld, offsets[%lld] = %lld)", what,
+                        static_cast<long long>(i + 1), static_cast<long long>(i), static_cast<long long>(offsets[i]),
+                        static_cast<long long>(i + 1), static_cast<long long>(offsets[i + 1]));
+        return fail(HSSFSST_EINVAL, "%s: recording %lld has %lld steps, over the limit of %lld", what, static_cast<long long>(i),
+                    static_cast<long long>(offsets[i + 1] - offsets[i]), static_cast<long long>(kSegMaxSteps));
+    }
+    if (offsets[count] > 0x7fffffffLL)
+        return fail(HSSFSST_EINVAL, "%s: %lld steps in all, over the limit of 2^31 - 1", what, static_cast<long long>(offsets[count]));
+    return 0;
+}
+
 // the scratch of an exec, in elements: projection, the two layers' outputs, carried state
 int seg_grow_scratch(hssfsst_segmenter* p, size_t pre, size_t y1, size_t y2, size_t state)
 {
@@ -2550,20 +2571,7 @@ int hssfsst_segmenter_exec_ragged(hssfsst_segmenter* p, const void* feats, int f
     // the list first: what is wrong with it is said before the plan is looked at
     if (count < 0) return fail(HSSFSST_EINVAL, "segmenter_exec_ragged: count %lld is negative", static_cast<long long>(count));
     if (count == 0) return 0;
-    if (!offsets) return fail(HSSFSST_EINVAL, "segmenter_exec_ragged: offsets is NULL");
-    if (count > kSegMaxBatch) return fail(HSSFSST_EINVAL, "segmenter_exec_ragged: count %lld too large", static_cast<long long>(count));
-    if (offsets[0] != 0)
-        return fail(HSSFSST_EINVAL, "segmenter_exec_ragged: offsets[0] is %lld, not 0", static_cast<long long>(offsets[0]));
-    if (const int64_t i = seglayout::first_bad_length(offsets, count, kSegMaxSteps); i >= 0) {
-        if (offsets[i + 1] <= offsets[i])
-            return fail(HSSFSST_EINVAL, "segmenter_exec_ragged: offsets do not increase at index %lld (offsets[%lld] = %lld, offsets[%lld] = %lld)",
-                        static_cast<long long>(i + 1), static_cast<long long>(i), static_cast<long long>(offsets[i]),
-                        static_cast<long long>(i + 1), static_cast<long long>(offsets[i + 1]));
-        return fail(HSSFSST_EINVAL, "segmenter_exec_ragged: recording %lld has %lld steps, over the limit of %lld", static_cast<long long>(i),
-                    static_cast<long long>(offsets[i + 1] - offsets[i]), static_cast<long long>(kSegMaxSteps));
-    }
-    if (offsets[count] > 0x7fffffffLL)
-        return fail(HSSFSST_EINVAL, "segmenter_exec_ragged: %lld steps in all, over the limit of 2^31 - 1", static_cast<long long>(offsets[count]));
+    if (int rc = seg_check_list("segmenter_exec_ragged", offsets, count)) return rc;
     if (state_rows != 1 && state_rows != count)
         return fail(HSSFSST_EINVAL, "segmenter_exec_ragged: state_rows %d is neither 1 nor count %lld", state_rows, static_cast<long long>(count));
     if (int rc = seg_check_dtype("segmenter_exec_ragged", feats_dtype)) return rc;
@@ -2632,6 +2640,10 @@ struct hssfsst_bilstm {
     DevBuf<float> d_scale;                               // {wscale, inv_scale}: made and read on the device only
     DevBuf<float> d_pre;                                 // one chunk's input projection
     DevBuf<float> d_state;                               // forward [h, c][dir][Bp][Hp]; backward [dh_rec, dc][dir][Bp][Hp]
+    // hssfsst_bilstm_*_ragged: the list's layout and its device tables -- slot_off long long[slots], tile_base long long[tiles + 1],
+    // slot_len int[slots], slot_rec int[slots], tile_walk int[tiles] -- in one block, kept while the next call has the same offsets
+    hssfsst::seglayout::Layout lay;                      // (of tab's key: rebuilt between its begin and commit)
+    UploadedTable tab{"bilstm_ragged"};
 };
 
 namespace {
@@ -2642,6 +2654,43 @@ int bilstm_check_shape(const char* what, int64_t batch, int64_t steps)
         return fail(HSSFSST_EINVAL, "%s: bad argument (batch=%lld steps=%lld)", what, static_cast<long long>(batch), static_cast<long long>(steps));
     if (batch > kSegMaxBatch || steps > kSegMaxSteps)
         return fail(HSSFSST_EINVAL, "%s: batch %lld or steps %lld too large", what, static_cast<long long>(batch), static_cast<long long>(steps));
+    return 0;
+}
+
+// The device tables of a ragged call's list, made and uploaded only when the offsets differ from the last call's (the owner
+// convention of hssfsst_segmenter::tab).  May throw std::bad_alloc.
+struct BilstmTables {
+    const long long *off, *base;
+    const int *len, *rec, *walk;
+    int slots;
+    long long walked;
+};
+int bilstm_ragged_tables(hssfsst_bilstm* p, const int64_t* offsets, int64_t count, hipStream_t st, BilstmTables* out)
+{
+    namespace seglayout = hssfsst::seglayout;
+    const size_t tiles = static_cast<size_t>((count + seglayout::kSlotRows - 1) / seglayout::kSlotRows), slots = tiles * seglayout::kSlotRows;
+    const size_t o_base = slots * sizeof(long long), o_len = o_base + (tiles + 1) * sizeof(long long);
+    const size_t o_rec = o_len + slots * sizeof(int), o_walk = o_rec + slots * sizeof(int);
+    auto key = [&](size_t i) { return offsets[i]; };
+    if (!p->tab.same(static_cast<size_t>(count + 1), key)) {
+        unsigned char* h = nullptr;
+        if (int rc = p->tab.begin(o_walk + tiles * sizeof(int), &h)) return rc;
+        seglayout::build(offsets, count, p->lay);
+        const std::vector<long long> base = seglayout::tile_base(p->lay);
+        std::memcpy(h, p->lay.slot_off.data(), o_base);
+        std::memcpy(h + o_base, base.data(), (tiles + 1) * sizeof(long long));
+        std::memcpy(h + o_len, p->lay.slot_len.data(), slots * sizeof(int));
+        std::memcpy(h + o_rec, p->lay.slot_rec.data(), slots * sizeof(int));
+        std::memcpy(h + o_walk, p->lay.tile_walk.data(), tiles * sizeof(int));
+        if (int rc = p->tab.commit(st, static_cast<size_t>(count + 1), key)) return rc;
+    }
+    out->off = reinterpret_cast<const long long*>(p->tab.get());
+    out->base = reinterpret_cast<const long long*>(p->tab.get() + o_base);
+    out->len = reinterpret_cast<const int*>(p->tab.get() + o_len);
+    out->rec = reinterpret_cast<const int*>(p->tab.get() + o_rec);
+    out->walk = reinterpret_cast<const int*>(p->tab.get() + o_walk);
+    out->slots = static_cast<int>(slots);
+    out->walked = seglayout::stash_floats_ragged(p->lay) / (2 * seglayout::kStashStepFloats);
     return 0;
 }
 
@@ -2761,8 +2810,8 @@ int hssfsst_bilstm_forward(hssfsst_bilstm* p, const float* x, int64_t batch, int
         if ((rc = launch_check("bilstm_forward", "seg_rec_kernel<train>")) != 0) return rc;
     }
     const size_t nout = static_cast<size_t>(4) * B * H;
-    hipLaunchKernelGGL(hssfsst::seg_pair_out_kernel, dim3(static_cast<unsigned>((nout + 255) / 256)), dim3(256), 0, st, p->d_state.get(), hn, cn,
-                       B, H, Bp);
+    hipLaunchKernelGGL(hssfsst::seg_pair_out_kernel<false>, dim3(static_cast<unsigned>((nout + 255) / 256)), dim3(256), 0, st, p->d_state.get(), hn, cn,
+                       B, H, Bp, static_cast<const int*>(nullptr));
     return launch_check("bilstm_forward", "seg_pair_out_kernel");
 }
 
@@ -2782,8 +2831,8 @@ int hssfsst_bilstm_backward(hssfsst_bilstm* p, const float* stash, const float* 
     int rc;
     const size_t nstate = static_cast<size_t>(4) * Bp * hssfsst::kSegHp;
     if ((rc = p->d_state.grow(nstate)) != 0) return rc;
-    hipLaunchKernelGGL(hssfsst::seg_pair_init_kernel, dim3(static_cast<unsigned>((nstate + 255) / 256)), dim3(256), 0, st, dhn, dcn,
-                       p->d_state.get(), B, H, Bp);
+    hipLaunchKernelGGL(hssfsst::seg_pair_init_kernel<false>, dim3(static_cast<unsigned>((nstate + 255) / 256)), dim3(256), 0, st, dhn, dcn,
+                       p->d_state.get(), B, H, Bp, static_cast<const int*>(nullptr));
     if ((rc = launch_check("bilstm_backward", "seg_pair_init_kernel")) != 0) return rc;
     hssfsst::SegBwdArgs a{};
     a.stash = stash; a.c0 = c0; a.dy = dy; a.wbwd = p->d_bwd.get(); a.state = p->d_state.get(); a.dgates = dgates;
@@ -2792,13 +2841,135 @@ int hssfsst_bilstm_backward(hssfsst_bilstm* p, const float* stash, const float* 
     for (int s0 = 0; s0 < T; s0 += hssfsst::seglayout::kSegMaxChunk) {
         a.s0 = s0;
         a.n = std::min(hssfsst::seglayout::kSegMaxChunk, T - s0);
-        hipLaunchKernelGGL(hssfsst::seg_bwd_rec_kernel, dim3(static_cast<unsigned>(nbt), 2), dim3(64 * hssfsst::kSegWaves), 0, st, a);
+        hipLaunchKernelGGL(hssfsst::seg_bwd_rec_kernel<false>, dim3(static_cast<unsigned>(nbt), 2), dim3(64 * hssfsst::kSegWaves), 0, st, a);
         if ((rc = launch_check("bilstm_backward", "seg_bwd_rec_kernel")) != 0) return rc;
     }
     const size_t nout = static_cast<size_t>(4) * B * H;
-    hipLaunchKernelGGL(hssfsst::seg_pair_out_kernel, dim3(static_cast<unsigned>((nout + 255) / 256)), dim3(256), 0, st, p->d_state.get(), dh0, dc0,
-                       B, H, Bp);
+    hipLaunchKernelGGL(hssfsst::seg_pair_out_kernel<false>, dim3(static_cast<unsigned>((nout + 255) / 256)), dim3(256), 0, st, p->d_state.get(), dh0, dc0,
+                       B, H, Bp, static_cast<const int*>(nullptr));
     return launch_check("bilstm_backward", "seg_pair_out_kernel");
+}
+
+int hssfsst_bilstm_stash_floats_ragged(const hssfsst_bilstm* p, const int64_t* offsets, int64_t count, int64_t* floats)
+{
+    if (!floats) return fail(HSSFSST_EINVAL, "bilstm_stash_floats_ragged: floats is NULL");
+    *floats = 0;
+    (void)p;                                             // (as hssfsst_bilstm_stash_floats: answered for a NULL plan too)
+    if (count < 0) return fail(HSSFSST_EINVAL, "bilstm_stash_floats_ragged: count %lld is negative", static_cast<long long>(count));
+    if (count == 0) return 0;
+    if (int rc = seg_check_list("bilstm_stash_floats_ragged", offsets, count)) return rc;
+    try {
+        hssfsst::seglayout::Layout lay;
+        hssfsst::seglayout::build(offsets, count, lay);
+        *floats = hssfsst::seglayout::stash_floats_ragged(lay);
+    } catch (const std::bad_alloc&) {
+        return fail(HSSFSST_ENOMEM, "bilstm_stash_floats_ragged: out of host memory");
+    }
+    return 0;
+}
+
+int hssfsst_bilstm_forward_ragged(hssfsst_bilstm* p, const float* x, const int64_t* offsets, int64_t count, const float* h0, const float* c0,
+                                  float* y, float* hn, float* cn, float* stash, void* stream)
+{
+    namespace seglayout = hssfsst::seglayout;
+    // the list first: what is wrong with it is said before the plan is looked at
+    if (count < 0) return fail(HSSFSST_EINVAL, "bilstm_forward_ragged: count %lld is negative", static_cast<long long>(count));
+    if (count == 0) return 0;
+    if (int rc = seg_check_list("bilstm_forward_ragged", offsets, count)) return rc;
+    if (!p) return fail(HSSFSST_EINVAL, "bilstm_forward_ragged: plan is NULL");
+    if (!x || !h0 || !c0 || !y || !hn || !cn || !stash)
+        return fail(HSSFSST_EINVAL, "bilstm_forward_ragged: bad argument (%s is NULL)",
+                    !x ? "x" : !h0 ? "h0" : !c0 ? "c0" : !y ? "y" : !hn ? "hn" : !cn ? "cn" : "stash");
+    if (!p->packed) return fail(HSSFSST_EINVAL, "bilstm_forward_ragged: no weights yet (call hssfsst_bilstm_set_weights first)");
+    DEVICE_SCOPE(p->device);
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    BilstmTables t{};
+    std::vector<seglayout::Chunk> chunks;
+    int rc;
+    try {
+        if ((rc = bilstm_ragged_tables(p, offsets, count, st, &t)) != 0) return rc;
+        chunks = seglayout::ragged_chunks(p->lay, kSegTileStepBytes, seglayout::kSegPreBytes);
+    } catch (const std::bad_alloc&) {
+        return fail(HSSFSST_ENOMEM, "bilstm_forward_ragged: out of host memory");
+    }
+    const int H = p->H, B = static_cast<int>(count);
+    const size_t nstate = static_cast<size_t>(4) * t.slots * hssfsst::kSegHp;
+    if ((rc = p->d_pre.grow(seglayout::pre_floats(chunks, kSegTileStepBytes))) != 0) return rc;
+    if ((rc = p->d_state.grow(nstate)) != 0) return rc;
+    hipLaunchKernelGGL(hssfsst::seg_state_init_kernel<true>, dim3(static_cast<unsigned>((nstate + 255) / 256)), dim3(256), 0, st, h0, c0,
+                       p->d_state.get(), B, H, t.slots, t.rec);
+    if ((rc = launch_check("bilstm_forward_ragged", "seg_state_init_kernel<ragged>")) != 0) return rc;
+    hssfsst::SegProjArgs pa{};
+    pa.x = x; pa.x_dtype = HSSFSST_DTYPE_F32; pa.relu = 0;
+    pa.F = p->F; pa.Fp = p->Fp;
+    pa.wt = p->d_wt.get(); pa.bias = p->d_bias.get(); pa.pre = p->d_pre.get();
+    pa.slot_off = t.off; pa.slot_len = t.len; pa.tile_walk = t.walk;
+    hssfsst::SegRecArgs ra{};
+    ra.H = H; ra.Bp = t.slots;
+    ra.pre = p->d_pre.get(); ra.whh = p->d_whh.get(); ra.state = p->d_state.get(); ra.y = y;
+    ra.stash = stash; ra.inv_scale_dev = p->d_scale.get() + 1;
+    ra.slot_off = t.off; ra.slot_len = t.len; ra.tile_walk = t.walk; ra.tile_base = t.base; ra.walked = t.walked;
+    for (const seglayout::Chunk& c : chunks) {
+        pa.n = ra.n = c.n;
+        pa.Tc = ra.Tc = c.Tc;
+        pa.s0 = ra.s0 = c.s0;
+        hipLaunchKernelGGL(hssfsst::seg_proj_kernel<true>, dim3(4 * hssfsst::kSegHp / 64, static_cast<unsigned>(c.tiles * ((c.n + 7) / 8)), 2),
+                           dim3(256), 0, st, pa);
+        if ((rc = launch_check("bilstm_forward_ragged", "seg_proj_kernel<ragged>")) != 0) return rc;
+        hipLaunchKernelGGL((hssfsst::seg_rec_kernel<true, true>), dim3(static_cast<unsigned>(c.tiles), 2), dim3(64 * hssfsst::kSegWaves), 0, st, ra);
+        if ((rc = launch_check("bilstm_forward_ragged", "seg_rec_kernel<ragged, train>")) != 0) return rc;
+    }
+    const size_t nout = static_cast<size_t>(4) * t.slots * H;
+    hipLaunchKernelGGL(hssfsst::seg_pair_out_kernel<true>, dim3(static_cast<unsigned>((nout + 255) / 256)), dim3(256), 0, st, p->d_state.get(), hn, cn,
+                       B, H, t.slots, t.rec);
+    return launch_check("bilstm_forward_ragged", "seg_pair_out_kernel<ragged>");
+}
+
+int hssfsst_bilstm_backward_ragged(hssfsst_bilstm* p, const float* stash, const float* c0, const float* dy, const float* dhn, const float* dcn,
+                                   const int64_t* offsets, int64_t count, float* dgates, float* dh0, float* dc0, void* stream)
+{
+    namespace seglayout = hssfsst::seglayout;
+    if (count < 0) return fail(HSSFSST_EINVAL, "bilstm_backward_ragged: count %lld is negative", static_cast<long long>(count));
+    if (count == 0) return 0;
+    if (int rc = seg_check_list("bilstm_backward_ragged", offsets, count)) return rc;
+    if (!p) return fail(HSSFSST_EINVAL, "bilstm_backward_ragged: plan is NULL");
+    if (!stash || !c0 || !dy || !dgates || !dh0 || !dc0)
+        return fail(HSSFSST_EINVAL, "bilstm_backward_ragged: bad argument (%s is NULL)",
+                    !stash ? "stash" : !c0 ? "c0" : !dy ? "dy" : !dgates ? "dgates" : !dh0 ? "dh0" : "dc0");
+    if (!p->packed) return fail(HSSFSST_EINVAL, "bilstm_backward_ragged: no weights yet (call hssfsst_bilstm_set_weights first)");
+    DEVICE_SCOPE(p->device);
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    BilstmTables t{};
+    std::vector<seglayout::BwdChunk> chunks;
+    int rc;
+    try {
+        if ((rc = bilstm_ragged_tables(p, offsets, count, st, &t)) != 0) return rc;
+        chunks = seglayout::ragged_bwd_chunks(p->lay);
+    } catch (const std::bad_alloc&) {
+        return fail(HSSFSST_ENOMEM, "bilstm_backward_ragged: out of host memory");
+    }
+    const int H = p->H, B = static_cast<int>(count);
+    const size_t nstate = static_cast<size_t>(4) * t.slots * hssfsst::kSegHp;
+    if ((rc = p->d_state.grow(nstate)) != 0) return rc;
+    hipLaunchKernelGGL(hssfsst::seg_pair_init_kernel<true>, dim3(static_cast<unsigned>((nstate + 255) / 256)), dim3(256), 0, st, dhn, dcn,
+                       p->d_state.get(), B, H, t.slots, t.rec);
+    if ((rc = launch_check("bilstm_backward_ragged", "seg_pair_init_kernel<ragged>")) != 0) return rc;
+    hssfsst::SegBwdArgs a{};
+    a.stash = stash; a.c0 = c0; a.dy = dy; a.wbwd = p->d_bwd.get(); a.state = p->d_state.get(); a.dgates = dgates;
+    a.B = B; a.H = H; a.Bp = t.slots;
+    a.slot_off = t.off; a.slot_len = t.len; a.slot_rec = t.rec; a.tile_walk = t.walk; a.tile_base = t.base;
+    a.walked = t.walked; a.total = p->lay.total;
+    // highest steps first, at most kSegMaxChunk per launch, chained through the carried (dh_rec, dc); a tile joins at its last step
+    for (const seglayout::BwdChunk& c : chunks) {
+        a.s0 = c.s0;
+        a.n = c.n;
+        hipLaunchKernelGGL(hssfsst::seg_bwd_rec_kernel<true>, dim3(static_cast<unsigned>(c.tiles), 2), dim3(64 * hssfsst::kSegWaves), 0, st, a);
+        if ((rc = launch_check("bilstm_backward_ragged", "seg_bwd_rec_kernel<ragged>")) != 0) return rc;
+    }
+    const size_t nout = static_cast<size_t>(4) * t.slots * H;
+    hipLaunchKernelGGL(hssfsst::seg_pair_out_kernel<true>, dim3(static_cast<unsigned>((nout + 255) / 256)), dim3(256), 0, st, p->d_state.get(), dh0, dc0,
+                       B, H, t.slots, t.rec);
+    return launch_check("bilstm_backward_ragged", "seg_pair_out_kernel<ragged>");
 }
 
 }  // extern "C"

@@ -179,4 +179,41 @@ HSSFSST_SEG_HD inline long long stash_index(long long tiles, long long steps, in
     return (((dir * tiles + tile) * steps + t) * (kWaves * 2) + (w * 2 + tl)) * (kStashQ * 256) + q * 256 + lane * 4 + r;
 }
 
+// The stash of a RAGGED training forward (hssfsst_bilstm_forward_ragged) is indexed by the step s a slot has walked, and a tile's
+// pitch is its own walk: [dir][tile_base[tile] + s][wave][unit tile of the wave 2][i, f, g, o, c][lane 64][4 rows].  A float4 holds
+// four rows, so a step of a tile is stored for all 16 of them; steps past a tile's walk do not exist.
+// tile_base: [tiles + 1] prefix sums of the walks; the last one is the walked steps of one direction.
+inline std::vector<long long> tile_base(const Layout& l)
+{
+    std::vector<long long> out(static_cast<size_t>(l.tiles()) + 1, 0);
+    for (int i = 0; i < l.tiles(); ++i) out[static_cast<size_t>(i) + 1] = out[static_cast<size_t>(i)] + l.tile_walk[static_cast<size_t>(i)];
+    return out;
+}
+inline long long stash_floats_ragged(const Layout& l)
+{
+    long long walked = 0;
+    for (int w : l.tile_walk) walked += w;
+    return 2 * walked * kStashStepFloats;
+}
+// walked: tile_base[tiles]; base: tile_base[tile]; s < the tile's walk
+HSSFSST_SEG_HD inline long long stash_index_ragged(long long walked, long long base, int dir, long long s, int w, int tl, int q, int lane, int r)
+{
+    return (((dir * walked + base + s) * (kWaves * 2)) + (w * 2 + tl)) * (kStashQ * 256) + q * 256 + lane * 4 + r;
+}
+
+// One launch of the ragged backward recurrence: the first `tiles` tiles -- those whose walk exceeds s0 -- walk the steps
+// min(s0 + n, walk) - 1 down to s0.  Highest range first, n <= kSegMaxChunk; a tile enters at the launch that holds its last step.
+struct BwdChunk { int s0, n, tiles; };
+inline std::vector<BwdChunk> ragged_bwd_chunks(const Layout& lay)
+{
+    std::vector<BwdChunk> out;
+    const int top = lay.tile_walk[0];
+    int live = 0;
+    for (int s0 = (top - 1) / kSegMaxChunk * kSegMaxChunk; s0 >= 0; s0 -= kSegMaxChunk) {
+        while (live < lay.tiles() && lay.tile_walk[static_cast<size_t>(live)] > s0) ++live;
+        out.push_back({s0, std::min(kSegMaxChunk, top - s0), live});
+    }
+    return out;
+}
+
 }  // namespace hssfsst::seglayout

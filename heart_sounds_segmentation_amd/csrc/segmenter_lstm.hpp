@@ -186,6 +186,9 @@ struct SegRecArgs {
     // TRAIN (segmenter_train.hpp): what the backward pass needs of every step, and the scale where the device-side pack left it
     float* stash;               // [dir][batch tile][T][wave][tile of the wave][i, f, g, o, c][lane][4] (seglayout::stash_index)
     const float* inv_scale_dev;
+    // RAGGED and TRAIN: the stash is indexed by step, a tile's pitch is its walk (seglayout::stash_index_ragged)
+    const long long* tile_base; // [tiles + 1] prefix sums of tile_walk
+    long long walked;           // tile_base[tiles]
 };
 
 __device__ __forceinline__ float seg_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
@@ -207,11 +210,13 @@ __device__ __forceinline__ void seg_put_h(_Float16* hi, _Float16* lo, int unit, 
 
 // Grid (batch tiles, 2 directions), block 512.  Direction 0 walks the chunk's steps upwards, direction 1 downwards.  RAGGED: both
 // walk step indices upwards; the trip count is the tile's (uniform in the workgroup), the rows' ends are selects.
-// TRAIN (dense only): the same arithmetic; each wave also stores the activated gates and c of the cells it holds, per step.
+// TRAIN: the same arithmetic; each wave also stores the activated gates and c of the cells it holds, per step.
+// RAGGED and TRAIN: a step of the tile is stored for all 16 rows (a float4 of the stash spans four); what an ended row leaves there
+// is finite and never read.  The rows' ends live in LDS and the gates are taken one at a time -- activated, stored, folded into
+// c -- so that no register is held for them: the kernel has none to spare.  A live row's operations are the dense kernel's.
 template <bool RAGGED, bool TRAIN = false>
 __global__ __launch_bounds__(512) void seg_rec_kernel(SegRecArgs a)
 {
-    static_assert(!(RAGGED && TRAIN), "training is dense only");
     constexpr int HB = kSegKb * 4 * kSegRows * 8;                       // halves of one plane of the h image
     __shared__ __attribute__((aligned(16))) _Float16 hbuf[2][2][HB];   // [buffer][hi, lo]
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -224,8 +229,19 @@ __global__ __launch_bounds__(512) void seg_rec_kernel(SegRecArgs a)
     const int n = RAGGED ? min(a.Tc, a.tile_walk[bt] - a.s0) : a.n;
     float inv_scale = a.inv_scale;
     if constexpr (TRAIN) inv_scale = *a.inv_scale_dev;
-    int rem[4], yrow[4];                                                // RAGGED: row r is live while s < rem[r]; its y row at s = 0
-    if constexpr (RAGGED) {
+    [[maybe_unused]] int rem[4], yrow[4];                               // RAGGED: row r is live while s < rem[r]; its y row at s = 0
+    [[maybe_unused]] const int* ends = nullptr;                         // RAGGED and TRAIN: the same two, [rem 16][yrow 16] in LDS
+    [[maybe_unused]] float* sp0 = nullptr;                              // ... and this lane's place in the stash at step s0
+    if constexpr (RAGGED && TRAIN) {
+        __shared__ __attribute__((aligned(16))) int ends_lds[2 * kSegRows];
+        if (tid < kSegRows) {
+            const int len = a.slot_len[b0 + tid], off = static_cast<int>(a.slot_off[b0 + tid]);
+            ends_lds[tid] = len - a.s0;
+            ends_lds[kSegRows + tid] = dir ? off + len - a.s0 - 1 : off + a.s0;
+        }
+        ends = ends_lds + row0;
+        sp0 = a.stash + seglayout::stash_index_ragged(a.walked, a.tile_base[bt], dir, a.s0, w, 0, 0, lane, 0);
+    } else if constexpr (RAGGED) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int len = a.slot_len[b0 + row0 + r], off = static_cast<int>(a.slot_off[b0 + row0 + r]);
@@ -317,34 +333,69 @@ __global__ __launch_bounds__(512) void seg_rec_kernel(SegRecArgs a)
 #pragma unroll
         for (int tl = 0; tl < 2; ++tl) {
             const int unit = (w * 2 + tl) * 16 + (lane & 15);
-            [[maybe_unused]] seg_f4 sg[4];
+            if constexpr (RAGGED && TRAIN) {
+                float* sp = sp0 + static_cast<size_t>(s) * seglayout::kStashStepFloats + tl * (seglayout::kStashQ * kSegTileFloats);
+                seg_f4 u, v;
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float gi = seg_sigmoid(fmaf(acc[tl * 4 + 0][r], inv_scale, pn[tl * 4 + 0][r]));
-                const float gf = seg_sigmoid(fmaf(acc[tl * 4 + 1][r], inv_scale, pn[tl * 4 + 1][r]));
-                const float gg = seg_tanh(fmaf(acc[tl * 4 + 2][r], inv_scale, pn[tl * 4 + 2][r]));
-                const float go = seg_sigmoid(fmaf(acc[tl * 4 + 3][r], inv_scale, pn[tl * 4 + 3][r]));
-                if constexpr (RAGGED) {
-                    const bool live = s < rem[r];
-                    const float cn = fmaf(gf, c[tl][r], gi * gg);
-                    const float hn = go * seg_tanh(cn);
-                    c[tl][r] = live ? cn : c[tl][r];
+                for (int r = 0; r < 4; ++r) u[r] = seg_sigmoid(fmaf(acc[tl * 4 + 0][r], inv_scale, pn[tl * 4 + 0][r]));
+                *reinterpret_cast<seg_f4*>(sp) = u;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) v[r] = seg_tanh(fmaf(acc[tl * 4 + 2][r], inv_scale, pn[tl * 4 + 2][r]));
+                *reinterpret_cast<seg_f4*>(sp + 2 * kSegTileFloats) = v;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) u[r] = u[r] * v[r];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) v[r] = seg_sigmoid(fmaf(acc[tl * 4 + 1][r], inv_scale, pn[tl * 4 + 1][r]));
+                *reinterpret_cast<seg_f4*>(sp + kSegTileFloats) = v;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) u[r] = fmaf(v[r], c[tl][r], u[r]);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) v[r] = seg_sigmoid(fmaf(acc[tl * 4 + 3][r], inv_scale, pn[tl * 4 + 3][r]));
+                *reinterpret_cast<seg_f4*>(sp + 3 * kSegTileFloats) = v;
+                // (the address is hidden like the weight stream's: hoisted, the eight values would be held for the whole launch)
+                const int4 rm = *reinterpret_cast<const int4*>(ends + zero);
+                const int4 yr = *reinterpret_cast<const int4*>(ends + kSegRows + zero);
+                const int rmv[4] = {rm.x, rm.y, rm.z, rm.w}, yrv[4] = {yr.x, yr.y, yr.z, yr.w};
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const bool live = s < rmv[r];
+                    const float hn = v[r] * seg_tanh(u[r]);
+                    c[tl][r] = live ? u[r] : c[tl][r];
                     h[tl][r] = live ? hn : h[tl][r];
-                    const int row = dir ? yrow[r] - s : yrow[r] + s;
+                    const int row = dir ? yrv[r] - s : yrv[r] + s;
                     if (live && unit < a.H) a.y[static_cast<size_t>(row) * (2 * a.H) + dir * a.H + unit] = hn;
-                } else {
-                    c[tl][r] = fmaf(gf, c[tl][r], gi * gg);
-                    h[tl][r] = go * seg_tanh(c[tl][r]);
-                    const int b = b0 + row0 + r;
-                    if (b < a.B && unit < a.H) a.y[(static_cast<size_t>(b) * a.T + t) * (2 * a.H) + dir * a.H + unit] = h[tl][r];
-                    if constexpr (TRAIN) { sg[0][r] = gi; sg[1][r] = gf; sg[2][r] = gg; sg[3][r] = go; }
                 }
-            }
-            if constexpr (TRAIN) {
-                float* sp = a.stash + seglayout::stash_index(nbt, a.T, dir, bt, t, w, tl, 0, lane, 0);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) *reinterpret_cast<seg_f4*>(sp + q * kSegTileFloats) = sg[q];
                 *reinterpret_cast<seg_f4*>(sp + 4 * kSegTileFloats) = c[tl];
+            } else {
+                [[maybe_unused]] seg_f4 sg[4];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float gi = seg_sigmoid(fmaf(acc[tl * 4 + 0][r], inv_scale, pn[tl * 4 + 0][r]));
+                    const float gf = seg_sigmoid(fmaf(acc[tl * 4 + 1][r], inv_scale, pn[tl * 4 + 1][r]));
+                    const float gg = seg_tanh(fmaf(acc[tl * 4 + 2][r], inv_scale, pn[tl * 4 + 2][r]));
+                    const float go = seg_sigmoid(fmaf(acc[tl * 4 + 3][r], inv_scale, pn[tl * 4 + 3][r]));
+                    if constexpr (RAGGED) {
+                        const bool live = s < rem[r];
+                        const float cn = fmaf(gf, c[tl][r], gi * gg);
+                        const float hn = go * seg_tanh(cn);
+                        c[tl][r] = live ? cn : c[tl][r];
+                        h[tl][r] = live ? hn : h[tl][r];
+                        const int row = dir ? yrow[r] - s : yrow[r] + s;
+                        if (live && unit < a.H) a.y[static_cast<size_t>(row) * (2 * a.H) + dir * a.H + unit] = hn;
+                    } else {
+                        c[tl][r] = fmaf(gf, c[tl][r], gi * gg);
+                        h[tl][r] = go * seg_tanh(c[tl][r]);
+                        const int b = b0 + row0 + r;
+                        if (b < a.B && unit < a.H) a.y[(static_cast<size_t>(b) * a.T + t) * (2 * a.H) + dir * a.H + unit] = h[tl][r];
+                        if constexpr (TRAIN) { sg[0][r] = gi; sg[1][r] = gf; sg[2][r] = gg; sg[3][r] = go; }
+                    }
+                }
+                if constexpr (TRAIN) {
+                    float* sp = a.stash + seglayout::stash_index(nbt, a.T, dir, bt, t, w, tl, 0, lane, 0);
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) *reinterpret_cast<seg_f4*>(sp + q * kSegTileFloats) = sg[q];
+                    *reinterpret_cast<seg_f4*>(sp + 4 * kSegTileFloats) = c[tl];
+                }
             }
             seg_put_h(hbuf[cur ^ 1][0], hbuf[cur ^ 1][1], unit, row0, h[tl]);
         }

@@ -5,11 +5,14 @@
 //   seg_pack_kernel         one layer's eight nn.LSTM tensors (device pointers) -> wt, bias and the split-f16 W_hh stream of the
 //                           forward kernels, element for element what seg_upload_layer makes on the host, plus the bf16 hi + lo
 //                           stream of W_hh as the B operand of the backward product (seglayout::bwd_stream_source);
-//   seg_rec_kernel<false, true>   (segmenter_lstm.hpp) the forward recurrence, which also stores i, f, g, o, c of every step;
+//   seg_rec_kernel<., true>   (segmenter_lstm.hpp) the forward recurrence, which also stores i, f, g, o, c of every step;
 //   seg_bwd_rec_kernel      the backward recurrence: one workgroup per (direction, 16 batch rows), 8 waves, walks the steps against
 //                           the forward order; dc and dh_rec stay in registers, dG goes through LDS as the split-bf16 A operand
 //                           image and dh_rec = dG . W_hh runs on v_mfma_f32_16x16x32_bf16 (hi.hi + hi.lo + lo.hi) with W_hh
 //                           streamed from L2 in the order the waves eat it; one barrier per step; no workgroup waits for another.
+//
+// RAGGED instantiations (hssfsst_bilstm_*_ragged): rows are the slots of segmenter_layout.hpp, everything is indexed by the step s a
+// slot has walked, x / y / dy / dgates are arenas of sum T rows and the states come and go in list order through slot_rec.
 //
 // No host synchronisation anywhere: the scale never leaves the device.
 #pragma once
@@ -100,8 +103,11 @@ __global__ __launch_bounds__(256) void seg_pack_kernel(SegPackArgs a)
     }
 }
 
-// state[0][dir][Bp][Hp] <- p0, state[1] <- p1, both (2, B, H), either NULL for zero; the padding is zero
-__global__ __launch_bounds__(256) void seg_pair_init_kernel(const float* p0, const float* p1, float* state, int B, int H, int Bp)
+// state[0][dir][Bp][Hp] <- p0, state[1] <- p1, both (2, B, H), either NULL for zero; the padding is zero.  RAGGED: row b is a slot
+// and takes the row of its recording slot_rec[b] (none: a padding slot, zero).
+template <bool RAGGED>
+__global__ __launch_bounds__(256) void seg_pair_init_kernel(const float* p0, const float* p1, float* state, int B, int H, int Bp,
+                                                            const int* slot_rec)
 {
     const size_t per = static_cast<size_t>(2) * Bp * kSegHp;
     const size_t i = static_cast<size_t>(blockIdx.x) * 256 + threadIdx.x;
@@ -112,21 +118,33 @@ __global__ __launch_bounds__(256) void seg_pair_init_kernel(const float* p0, con
     const int b = static_cast<int>((r / kSegHp) % Bp);
     const int dir = static_cast<int>(r / (static_cast<size_t>(kSegHp) * Bp));
     const float* src = which ? p1 : p0;
-    state[i] = src != nullptr && b < B && u < H ? src[(static_cast<size_t>(dir) * B + b) * H + u] : 0.0f;
+    int row = b;
+    if constexpr (RAGGED) row = slot_rec[b];
+    state[i] = src != nullptr && row >= 0 && row < B && u < H ? src[(static_cast<size_t>(dir) * B + row) * H + u] : 0.0f;
 }
 
-// out0, out1 (2, B, H) <- state[0], state[1]
-__global__ __launch_bounds__(256) void seg_pair_out_kernel(const float* state, float* out0, float* out1, int B, int H, int Bp)
+// out0, out1 (2, B, H) <- state[0], state[1].  RAGGED: one thread per (slot, unit); slot b's state goes to row slot_rec[b] of the
+// outputs, which are in list order.
+template <bool RAGGED>
+__global__ __launch_bounds__(256) void seg_pair_out_kernel(const float* state, float* out0, float* out1, int B, int H, int Bp,
+                                                           const int* slot_rec)
 {
-    const size_t per = static_cast<size_t>(2) * B * H;
+    const int rows = RAGGED ? Bp : B;
+    const size_t per = static_cast<size_t>(2) * rows * H;
     const size_t i = static_cast<size_t>(blockIdx.x) * 256 + threadIdx.x;
     if (i >= 2 * per) return;
     const int which = static_cast<int>(i / per);
     const size_t r = i - which * per;
     const int u = static_cast<int>(r % H);
-    const int b = static_cast<int>((r / H) % B);
-    const int dir = static_cast<int>(r / (static_cast<size_t>(H) * B));
-    (which ? out1 : out0)[r] = state[((static_cast<size_t>(which) * 2 + dir) * Bp + b) * kSegHp + u];
+    const int b = static_cast<int>((r / H) % rows);
+    const int dir = static_cast<int>(r / (static_cast<size_t>(H) * rows));
+    const float v = state[((static_cast<size_t>(which) * 2 + dir) * Bp + b) * kSegHp + u];
+    if constexpr (RAGGED) {
+        const int rec = slot_rec[b];
+        if (rec >= 0 && rec < B) (which ? out1 : out0)[(static_cast<size_t>(dir) * B + rec) * H + u] = v;
+    } else {
+        (which ? out1 : out0)[r] = v;
+    }
 }
 
 struct SegBwdArgs {
@@ -138,6 +156,14 @@ struct SegBwdArgs {
     float* dgates;          // (2, B, T, 4 H), nn.LSTM's gate order
     int B, T, H, Bp;
     int s0, n;              // this launch walks the direction's steps T - 1 - s0 downwards, n of them
+    // RAGGED: dy is (sum T, 2 H) and dgates (2, sum T, 4 H) in arena order; B the recordings (rows of c0), Bp the slots; the stash
+    // is the ragged forward's (seglayout::stash_index_ragged); a tile walks the steps min(s0 + n, walk) - 1 down to s0
+    const long long* slot_off;
+    const int* slot_len;
+    const int* slot_rec;
+    const int* tile_walk;
+    const long long* tile_base;
+    long long walked, total;    // tile_base[tiles] and sum T
 };
 
 // dG of one lane's (unit, gate, 4 rows) into the split-bf16 A-operand image [K block 32][k quarter][row 16][8], hi and lo planes.
@@ -158,6 +184,11 @@ __device__ __forceinline__ void seg_put_dg(__bf16* hi, __bf16* lo, int unit, int
 // Grid (batch tiles, 2 directions), block 512.  Step sigma of a direction is t = sigma (forward) or T - 1 - sigma (reverse); the
 // launch walks sigma = T - 1 - s0 - s for s = 0 .. n - 1.  Wave w owns units (2 w + tl) * 16 + (lane & 15), rows 4 (lane >> 4) + r,
 // as in the forward kernel, so a cell's dc, the dh_rec it receives and its stash never leave the lane.
+// RAGGED: sigma is the step s of the slots.  Row r is live while sigma < len_r and stands at arena row off_r + sigma (forward) or
+// off_r + len_r - 1 - sigma (reverse).  Until then its (dh_rec, dc) stay the seed of its recording through selects, it stores
+// nothing and puts zeros into the dG image, so the product gives it nothing.  The trip count is the tile's, uniform in the
+// workgroup; a live row's operations are the dense kernel's.
+template <bool RAGGED>
 __global__ __launch_bounds__(512) void seg_bwd_rec_kernel(SegBwdArgs a)
 {
     constexpr int GB = kSegBwdKb * 4 * kSegRows * 8;                    // bf16 of one plane of the dG image: 32 KiB
@@ -170,6 +201,21 @@ __global__ __launch_bounds__(512) void seg_bwd_rec_kernel(SegBwdArgs a)
     float* dhst = a.state + (static_cast<size_t>(dir) * a.Bp + b0) * kSegHp;
     float* dcst = dhst + plane;
     const int H4 = 4 * a.H;
+    int n = a.n;
+    if constexpr (RAGGED) n = min(a.n, a.tile_walk[bt] - a.s0);
+    [[maybe_unused]] const int* rows = nullptr;                         // RAGGED: [len 16][first arena row 16][recording 16] in LDS
+    [[maybe_unused]] long long base = 0;
+    if constexpr (RAGGED) {
+        __shared__ __attribute__((aligned(16))) int rows_lds[3 * kSegRows];
+        if (tid < kSegRows) {
+            rows_lds[tid] = a.slot_len[b0 + tid];
+            rows_lds[kSegRows + tid] = static_cast<int>(a.slot_off[b0 + tid]);
+            rows_lds[2 * kSegRows + tid] = a.slot_rec[b0 + tid];
+        }
+        __syncthreads();
+        rows = rows_lds + row0;
+        base = a.tile_base[bt];
+    }
 
     seg_f4 dh[2], dc[2];
 #pragma unroll
@@ -184,7 +230,19 @@ __global__ __launch_bounds__(512) void seg_bwd_rec_kernel(SegBwdArgs a)
 
     auto time_of = [&](int sigma) { return dir ? a.T - 1 - sigma : sigma; };
     auto stash_at = [&](int sigma, int tl) {
-        return a.stash + seglayout::stash_index(nbt, a.T, dir, bt, time_of(sigma), w, tl, 0, lane, 0);
+        if constexpr (RAGGED) return a.stash + seglayout::stash_index_ragged(a.walked, base, dir, sigma, w, tl, 0, lane, 0);
+        else return a.stash + seglayout::stash_index(nbt, a.T, dir, bt, time_of(sigma), w, tl, 0, lane, 0);
+    };
+    // RAGGED: word k of row r's entry (the LDS address is hidden from the compiler: hoisted out of the step loop, the rows' ends
+    // would be held in registers for the whole launch), and the arena row of row r at step sigma, -1 while the row is not live
+    [[maybe_unused]] auto row_word = [&](int k, int r) {
+        int hide = k * kSegRows + r;
+        asm volatile("" : "+v"(hide));
+        return rows[hide];
+    };
+    [[maybe_unused]] auto arena_row = [&](int sigma, int r) {
+        const int len = row_word(0, r), off = row_word(1, r);
+        return sigma < len ? off + (dir ? len - 1 - sigma : sigma) : -1;
     };
     // c before step sigma: the stash of step sigma - 1, or c0
     auto c_before = [&](int sigma, int tl) {
@@ -195,8 +253,13 @@ __global__ __launch_bounds__(512) void seg_bwd_rec_kernel(SegBwdArgs a)
             const int unit = (w * 2 + tl) * 16 + (lane & 15);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const int b = b0 + row0 + r;
-                v[r] = b < a.B && unit < a.H ? a.c0[(static_cast<size_t>(dir) * a.B + b) * a.H + unit] : 0.0f;
+                if constexpr (RAGGED) {
+                    const int rec = row_word(2, r);
+                    v[r] = rec >= 0 && unit < a.H ? a.c0[(static_cast<size_t>(dir) * a.B + rec) * a.H + unit] : 0.0f;
+                } else {
+                    const int b = b0 + row0 + r;
+                    v[r] = b < a.B && unit < a.H ? a.c0[(static_cast<size_t>(dir) * a.B + b) * a.H + unit] : 0.0f;
+                }
             }
         }
         return v;
@@ -206,15 +269,20 @@ __global__ __launch_bounds__(512) void seg_bwd_rec_kernel(SegBwdArgs a)
         const int unit = (w * 2 + tl) * 16 + (lane & 15), t = time_of(sigma);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const int b = b0 + row0 + r;
-            v[r] = b < a.B && unit < a.H ? a.dy[(static_cast<size_t>(b) * a.T + t) * (2 * a.H) + dir * a.H + unit] : 0.0f;
+            if constexpr (RAGGED) {
+                const int row = arena_row(sigma, r);
+                v[r] = row >= 0 && unit < a.H ? a.dy[static_cast<size_t>(row) * (2 * a.H) + dir * a.H + unit] : 0.0f;
+            } else {
+                const int b = b0 + row0 + r;
+                v[r] = b < a.B && unit < a.H ? a.dy[(static_cast<size_t>(b) * a.T + t) * (2 * a.H) + dir * a.H + unit] : 0.0f;
+            }
         }
         return v;
     };
 
     // this wave's weight stream: per K block 2 output tiles of {hi, lo} x 64 lanes
     const seg_b8* const wq0 = a.wbwd + ((static_cast<size_t>(dir) * kSegWaves + w) * kSegBwdKb * 2 * 64 + lane) * 2;
-    const int sig0 = a.T - 1 - a.s0;
+    const int sig0 = RAGGED ? a.s0 + n - 1 : a.T - 1 - a.s0;
 
     // the first step's operands; every later step's are fetched one step ahead, behind the product
     seg_f4 gt[2][4], ct[2], cp[2], dyv[2];
@@ -232,8 +300,16 @@ __global__ __launch_bounds__(512) void seg_bwd_rec_kernel(SegBwdArgs a)
     for (int q = 0; q < 8; ++q) wb[0][q >> 2][(q >> 1) & 1][q & 1] = wq0[(q >> 1) * 64 * 2 + (q & 1)];
 
     int cur = 0;
-    for (int s = 0; s < a.n; ++s) {
+    for (int s = 0; s < n; ++s) {
         const int sigma = sig0 - s, t = time_of(sigma);
+        [[maybe_unused]] int arow[4], lives = 0;                         // RAGGED: the rows' arena rows at this step, -1: not live
+        if constexpr (RAGGED) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                arow[r] = arena_row(sigma, r);
+                lives |= (arow[r] >= 0) << r;
+            }
+        }
 #pragma unroll
         for (int tl = 0; tl < 2; ++tl) {
             const int unit = (w * 2 + tl) * 16 + (lane & 15);
@@ -248,19 +324,31 @@ __global__ __launch_bounds__(512) void seg_bwd_rec_kernel(SegBwdArgs a)
                 dg[0][r] = dcv * gg * gi * (1.0f - gi);
                 dg[2][r] = dcv * gi * (1.0f - gg * gg);
                 dg[1][r] = dcv * cp[tl][r] * gf * (1.0f - gf);
-                dc[tl][r] = dcv * gf;
-                const int b = b0 + row0 + r;
-                if (b < a.B && unit < a.H) {
-                    float* dst = a.dgates + ((static_cast<size_t>(dir) * a.B + b) * a.T + t) * H4 + unit;
+                if constexpr (RAGGED) {
+                    const bool live = arow[r] >= 0;
+                    dc[tl][r] = live ? dcv * gf : dc[tl][r];
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) dst[q * a.H] = dg[q][r];
+                    for (int q = 0; q < 4; ++q) dg[q][r] = live ? dg[q][r] : 0.0f;
+                    if (live && unit < a.H) {
+                        float* dst = a.dgates + (static_cast<size_t>(dir) * a.total + arow[r]) * H4 + unit;
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) dst[q * a.H] = dg[q][r];
+                    }
+                } else {
+                    dc[tl][r] = dcv * gf;
+                    const int b = b0 + row0 + r;
+                    if (b < a.B && unit < a.H) {
+                        float* dst = a.dgates + ((static_cast<size_t>(dir) * a.B + b) * a.T + t) * H4 + unit;
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) dst[q * a.H] = dg[q][r];
+                    }
                 }
             }
 #pragma unroll
             for (int q = 0; q < 4; ++q) seg_put_dg(gbuf[cur][0], gbuf[cur][1], unit, q, row0, dg[q]);
             ct[tl] = cp[tl];                                             // c before this step is c of the next one walked
         }
-        if (s + 1 < a.n) {
+        if (s + 1 < n) {
 #pragma unroll
             for (int tl = 0; tl < 2; ++tl) {
 #pragma unroll
@@ -301,8 +389,17 @@ __global__ __launch_bounds__(512) void seg_bwd_rec_kernel(SegBwdArgs a)
             }
             __builtin_amdgcn_sched_barrier(0);
         }
-        dh[0] = acc[0];
-        dh[1] = acc[1];
+        if constexpr (RAGGED) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const bool live = (lives >> r) & 1;
+                dh[0][r] = live ? acc[0][r] : dh[0][r];
+                dh[1][r] = live ? acc[1][r] : dh[1][r];
+            }
+        } else {
+            dh[0] = acc[0];
+            dh[1] = acc[1];
+        }
         cur ^= 1;
     }
 #pragma unroll

@@ -398,7 +398,7 @@ int hssfsst_segmenter_exec_ragged(hssfsst_segmenter* plan, const void* feats, in
 /* One DIFFERENTIABLE bidirectional LSTM layer (batch first, nn.LSTM's cell and gate order): the unit a training program stacks
  * under autograd -- the segmenter is two of them.  The plan holds the layer's current weights in the kernels' layouts and the
  * scratch of its calls; the caller owns inputs, outputs and the stash.  Every pointer below is a DEVICE pointer on the plan's
- * device unless marked host; float32, dense (batch, steps, .) only.  Kernels: csrc/segmenter_train.hpp.  Every call is enqueued on
+ * device unless marked host; float32.  Kernels: csrc/segmenter_train.hpp.  Every call is enqueued on
  * `stream` without any host synchronisation.  Single-stream and single-thread like the other plans.
  *   create       input_size < 1, hidden < 1, device < 0 or a NULL out: HSSFSST_EINVAL; hidden > 256: HSSFSST_EUNSUPPORTED; both
  *                before any device is touched.
@@ -429,6 +429,27 @@ int hssfsst_bilstm_forward(hssfsst_bilstm* plan, const float* x, int64_t batch, 
                            float* y, float* hn, float* cn, float* stash, void* stream);
 int hssfsst_bilstm_backward(hssfsst_bilstm* plan, const float* stash, const float* c0, const float* dy, const float* dhn,
                             const float* dcn, int64_t batch, int64_t steps, float* dgates, float* dh0, float* dc0, void* stream);
+
+/* The same layer on a LIST of whole recordings of different lengths, one call per pass: recording i is rows offsets[i] ..
+ * offsets[i + 1] of the arenas x (sum T, input_size), y and dy (sum T, 2 hidden) and dgates (2, sum T, 4 hidden); h0, c0, hn, cn,
+ * dhn, dcn, dh0, dc0 are (2, count, hidden) in list order.  offsets: int64 HOST array of count + 1 step offsets, offsets[0] == 0,
+ * strictly increasing -- the list of hssfsst_segmenter_exec_ragged, checked the same way with the same messages, before the plan
+ * is looked at; count == 0 does nothing and returns 0.  For every i, y, hn, cn, dgates, dh0, dc0 are bit-identical to the dense
+ * calls on that recording alone (batch 1): forward from its first step, reverse from its own last one.
+ * How: the slots and tiles of csrc/segmenter_layout.hpp (longest first, 16 per tile); a tile's workgroups walk its longest
+ * recording, forwards in the forward pass and back down in the backward pass, and rows past their own end are held by selects
+ * (RAGGED instantiations of csrc/segmenter_lstm.hpp and csrc/segmenter_train.hpp).  The stash is indexed by (tile, step walked):
+ *   stash_floats_ragged  floats <- 2 x (sum over tiles of the tile's longest recording) x 20480 (80 KiB per direction, tile and
+ *                        step: 5.8 GB for one tile of 35 500-step recordings); equal lengths give hssfsst_bilstm_stash_floats.
+ *                        Host only; the plan may be NULL.
+ * The plan keeps the list's device tables while the next call has the same offsets; a backward call must be given the offsets of
+ * its forward call. */
+int hssfsst_bilstm_stash_floats_ragged(const hssfsst_bilstm* plan, const int64_t* offsets, int64_t count, int64_t* floats);
+int hssfsst_bilstm_forward_ragged(hssfsst_bilstm* plan, const float* x, const int64_t* offsets, int64_t count, const float* h0,
+                                  const float* c0, float* y, float* hn, float* cn, float* stash, void* stream);
+int hssfsst_bilstm_backward_ragged(hssfsst_bilstm* plan, const float* stash, const float* c0, const float* dy, const float* dhn,
+                                   const float* dcn, const int64_t* offsets, int64_t count, float* dgates, float* dh0, float* dc0,
+                                   void* stream);
 
 int hssfsst_device_count(void);
 int hssfsst_version(void);
