@@ -290,6 +290,11 @@ def lib():
         L.hssfsst_segmenter_exec.restype = c_int
         L.hssfsst_segmenter_exec_ragged.argtypes = [vp, vp, c_int, ctypes.POINTER(c_i64), c_i64, vp, vp, c_int, vp, vp]
         L.hssfsst_segmenter_exec_ragged.restype = c_int
+        L.hssfsst_decode_info.argtypes = [ip, ctypes.POINTER(c_i64)]
+        L.hssfsst_decode_info.restype = c_int
+        L.hssfsst_decode_states.argtypes = [vp, ctypes.POINTER(c_i64), c_i64, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
+                                            vp, vp, c_int, vp]
+        L.hssfsst_decode_states.restype = c_int
         L.hssfsst_bilstm_create.argtypes = [ctypes.POINTER(vp), c_int, c_int, c_int]
         L.hssfsst_bilstm_create.restype = c_int
         L.hssfsst_bilstm_destroy.argtypes = [vp]

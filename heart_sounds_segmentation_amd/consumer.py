@@ -18,6 +18,10 @@ hssfsst_segmenter_exec_ragged) in one call.
 ``HipBiLSTM`` is one differentiable bidirectional layer on the HIP recurrences (hssfsst_bilstm_*; csrc/segmenter_train.hpp) and
 ``HipSegmenterHead`` the same model built from two of them: what a training script uses instead of the ``nn.LSTM`` model.  Both
 have a ``ragged`` form that trains on whole recordings of different lengths in one call (hssfsst_bilstm_*_ragged).
+
+``decode_states`` turns log-probs into state sequences: Viterbi decoding under a transition constraint (by default the cardiac
+cycle: stay or advance), one HIP call for a whole list of recordings (hssfsst_decode_states; csrc/segmenter_decode.hpp), with
+``cyclic_transitions`` / ``transitions_from_labels`` for the transitions and ``state_runs`` for the boundaries.
 """
 from __future__ import annotations
 
@@ -575,8 +579,163 @@ def segment(fsst, head, windows: torch.Tensor) -> torch.Tensor:
     return head(fsst.batch(windows))
 
 
-def segment_recordings(fsst, seg: HipSegmenter, recordings, **kw) -> RaggedFeatures:
+def segment_recordings(fsst, seg: HipSegmenter, recordings, decode=None, **kw) -> RaggedFeatures:
     """Whole recordings of different lengths (a list of 1-D signals on the GPU) -> ``FSST.ragged`` features, kept on the device
     -> a ``RaggedFeatures`` of ``(T_i, 4)`` log-probs: ``segment()`` for whole recordings.  ``kw`` goes to
-    ``HipSegmenter.ragged`` (h0, c0, max_steps)."""
-    return seg.ragged(fsst.ragged(recordings), **kw)
+    ``HipSegmenter.ragged`` (h0, c0, max_steps).  ``decode=True`` or ``decode=(A, pi)``: the log-probs go on to ``decode_states``
+    (default or given transitions) and the ``RaggedStates`` of ``(T_i,)`` uint8 state sequences is returned instead."""
+    logp = seg.ragged(fsst.ragged(recordings), **kw)
+    if decode is None or decode is False:
+        return logp
+    if decode is True:
+        return decode_states(logp)
+    A, pi = decode
+    return decode_states(logp, A, pi)
+
+
+# ------------------------------------------------------------------------------------------- log-probs -> state sequences
+class RaggedStates(RaggedFeatures):
+    """What ``decode_states`` returns for a ragged input: a ``RaggedFeatures`` whose arena ``data`` is ``(sum T,)`` uint8 and whose
+    item i is the ``(T_i,)`` state sequence of recording i (a view).  ``scores``: ``(B,)`` float64 on the host when asked for."""
+
+    def __init__(self, data: torch.Tensor, offsets: torch.Tensor):
+        super().__init__(data, offsets, 1, False)
+        self.scores = None
+
+    def padded(self, padding_value: int = 0) -> torch.Tensor:
+        """``(B, T_max)`` uint8 with ``padding_value`` past each recording's end."""
+        B = len(self)
+        lens = self.lengths().to(self.data.device)
+        T = int(lens.max()) if B else 0
+        out = torch.full((B, T), int(padding_value), dtype=self.data.dtype, device=self.data.device)
+        if B and T:
+            out[torch.arange(T, device=self.data.device)[None, :] < lens[:, None]] = self.data
+        return out
+
+
+def cyclic_transitions(stay_logp: float = 0.0, advance_logp: float = 0.0):
+    """``(A, pi)`` of the cardiac cycle S1 -> systole -> S2 -> diastole -> S1: ``A[i][i] = stay_logp``, ``A[i][(i + 1) % 4] =
+    advance_logp``, every other move ``-inf`` (forbidden); ``pi`` uniform (zeros).  float32 numpy arrays (4, 4) and (4,)."""
+    A = np.full((4, 4), -np.inf, dtype=np.float32)
+    for i in range(4):
+        A[i, i] = stay_logp
+        A[i, (i + 1) % 4] = advance_logp
+    return A, np.zeros(4, dtype=np.float32)
+
+
+def transitions_from_labels(labels):
+    """``(A, pi)`` counted from label sequences (a list of 1-D integer tensors or arrays with values 0..3): ``A`` = log of the
+    row-normalised transition counts over consecutive steps, ``pi`` = log of the start-state frequencies; ``-inf`` where never
+    seen.  Host numpy, float64 counts, float32 result.  A state that is never left (no step follows it in any sequence) has an
+    all ``-inf`` row, which ``decode_states`` refuses: such labels do not describe a cycle."""
+    counts, starts = np.zeros((4, 4), dtype=np.float64), np.zeros(4, dtype=np.float64)
+    for k, lab in enumerate(labels):
+        a = lab.detach().cpu().numpy() if isinstance(lab, torch.Tensor) else np.asarray(lab)
+        if a.ndim != 1 or a.size < 1 or a.dtype.kind not in "iu":
+            raise ValueError(f"transitions_from_labels: item {k} is not a non-empty 1-D integer sequence")
+        a = a.astype(np.int64)
+        if a.min() < 0 or a.max() > 3:
+            raise ValueError(f"transitions_from_labels: item {k} has labels outside 0..3")
+        starts[a[0]] += 1
+        np.add.at(counts, (a[:-1], a[1:]), 1)
+    if starts.sum() == 0:
+        raise ValueError("transitions_from_labels: no label sequence")
+    with np.errstate(divide="ignore", invalid="ignore"):
+        rows = counts.sum(axis=1, keepdims=True)
+        A = np.where(counts > 0, np.log(counts / np.where(rows > 0, rows, 1.0)), -np.inf)
+        pi = np.where(starts > 0, np.log(starts / starts.sum()), -np.inf)
+    return A.astype(np.float32), pi.astype(np.float32)
+
+
+def decode_info():
+    """``(segment_steps, max_steps)`` of the decoder (``hssfsst_decode_info``): the steps a workgroup stages at a time and the
+    longest recording it takes.  No device needed."""
+    seg, mx = ctypes.c_int(0), ctypes.c_int64(0)
+    _lib.check(_lib.lib().hssfsst_decode_info(ctypes.byref(seg), ctypes.byref(mx)), "hssfsst_decode_info")
+    return seg.value, mx.value
+
+
+def decode_states(logp, transitions=None, initial=None, return_scores: bool = False):
+    """Viterbi decoding on the device (``hssfsst_decode_states``): log-probs -> the best state sequence 0..3 (S1, systole, S2,
+    diastole) under log transitions ``transitions`` (4, 4) and log initial scores ``initial`` (4,); ``-inf`` = forbidden; default
+    ``cyclic_transitions()``: stay or advance, which a per-step argmax does not respect.
+
+    ``logp``: the ``RaggedFeatures`` of ``HipSegmenter.ragged`` / ``HipSegmenterHead.ragged`` (a ``(sum T, 4)`` arena), a
+    ``(B, T, 4)`` tensor or a ``(T, 4)`` tensor; float32 on a GPU, anything else raises ValueError.  Returns the same kind: a
+    ``RaggedStates`` (item i a ``(T_i,)`` uint8 view of one arena), a ``(B, T)`` or a ``(T,)`` uint8 tensor.  One call, enqueued
+    on the current stream, whatever the lengths; the dense forms are the same call with regular offsets.
+    ``return_scores=True``: also the best paths' scores, float64 ``(B,)`` on the host (a scalar tensor for ``(T, 4)``), which
+    waits for the device.
+
+    Exact arithmetic (include/hssfsst.h): every value is rounded to a multiple of 2^-20 after clamping to +-32768 (NaN counts as
+    -32768), ties go to the smaller state.  The emissions are the caller's: a step whose four emissions are all ``-inf`` makes
+    the score -inf and the path arbitrary (the tie rule's)."""
+    name = "decode_states"
+    if (transitions is None) != (initial is None):
+        raise ValueError(f"{name}: pass both transitions and initial, or neither")
+    if transitions is None:
+        transitions, initial = cyclic_transitions()
+    A = np.ascontiguousarray(transitions.detach().cpu().numpy() if isinstance(transitions, torch.Tensor) else transitions, dtype=np.float32)
+    pi = np.ascontiguousarray(initial.detach().cpu().numpy() if isinstance(initial, torch.Tensor) else initial, dtype=np.float32)
+    if A.shape != (4, 4) or pi.shape != (4,):
+        raise ValueError(f"{name}: transitions (4, 4) and initial (4,) expected, got {A.shape} and {pi.shape}")
+    if isinstance(logp, RaggedFeatures):
+        if logp._raw:
+            raise ValueError(f"{name}: raw features are not log-probs")
+        data, offs, kind = logp.data, [int(o) for o in logp._off], "ragged"
+    elif isinstance(logp, torch.Tensor) and logp.dim() == 3:
+        B, T = int(logp.shape[0]), int(logp.shape[1])
+        data, offs, kind = logp.reshape(B * T, -1) if B * T else logp.reshape(0, logp.shape[2]), [i * T for i in range(B + 1)], "batch"
+        if B and T < 1:
+            raise ValueError(f"{name}: (B, T, 4) log-probs with T >= 1 expected, got {tuple(logp.shape)}")
+    elif isinstance(logp, torch.Tensor) and logp.dim() == 2:
+        data, offs, kind = logp, [0, int(logp.shape[0])], "single"
+        if logp.shape[0] < 1:
+            raise ValueError(f"{name}: (T, 4) log-probs with T >= 1 expected, got {tuple(logp.shape)}")
+    else:
+        raise ValueError(f"{name}: a RaggedFeatures, a (B, T, 4) or a (T, 4) tensor expected")
+    if data.dim() != 2 or data.shape[1] != 4 or data.shape[0] != offs[-1]:
+        raise ValueError(f"{name}: log-probs over 4 states expected, got an arena of shape {tuple(data.shape)}")
+    if data.dtype != torch.float32:
+        raise ValueError(f"{name}: float32 log-probs expected, got {data.dtype}")
+    if data.device.type != "cuda":
+        raise ValueError(f"{name}: log-probs on a GPU expected, got {data.device}; the decoder has no CPU path")
+    L = _lib.lib()
+    _lib.guard_fork()
+    device = data.device
+    data = data.detach().contiguous()
+    count = len(offs) - 1
+    states = torch.empty((offs[-1],), dtype=torch.uint8, device=device)
+    scores = torch.empty((count,), dtype=torch.int64, device=device) if return_scores else None
+    if count:
+        o = np.asarray(offs, dtype=np.int64)
+        with torch.cuda.device(device):
+            stream = torch.cuda.current_stream(device).cuda_stream
+            _lib.check(L.hssfsst_decode_states(data.data_ptr(), o.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), count,
+                                               A.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), pi.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
+                                               states.data_ptr(), scores.data_ptr() if return_scores else None, device.index, stream),
+                       "hssfsst_decode_states")
+    if kind == "ragged":
+        out = RaggedStates(states, torch.tensor(offs, dtype=torch.int64))
+    elif kind == "batch":
+        out = states.view(int(logp.shape[0]), int(logp.shape[1]))
+    else:
+        out = states
+    if not return_scores:
+        return out
+    # (NEG, the score of a recording with an all -inf step, reads as -inf)
+    sc = scores.cpu()
+    val = torch.where(sc == torch.iinfo(torch.int64).min, torch.tensor(float("-inf"), dtype=torch.float64), sc.double() / float(1 << 20))
+    if kind == "ragged":
+        out.scores = val
+    return out, (val[0] if kind == "single" else val)
+
+
+def state_runs(states: torch.Tensor):
+    """The boundaries of a decoded recording: ``(starts int64, state uint8)`` of the runs of equal states in the 1-D ``states``
+    (``torch.unique_consecutive``), on its device.  Run k covers steps ``starts[k] .. starts[k + 1]`` (the last one to the end)."""
+    if not isinstance(states, torch.Tensor) or states.dim() != 1:
+        raise ValueError("state_runs: a 1-D tensor of states expected")
+    vals, counts = torch.unique_consecutive(states, return_counts=True)
+    starts = torch.cumsum(counts, 0) - counts
+    return starts.to(torch.int64), vals.to(torch.uint8)

@@ -40,6 +40,8 @@
 #include "segmenter_lstm.hpp"
 #include "segmenter_layout.hpp"
 #include "segmenter_train.hpp"
+#include "decode_layout.hpp"
+#include "segmenter_decode.hpp"
 #include "fsst_tables.hpp"
 
 namespace tables = hssfsst::tables;
@@ -2624,6 +2626,69 @@ int hssfsst_segmenter_exec_ragged(hssfsst_segmenter* p, const void* feats, int f
     hipLaunchKernelGGL(hssfsst::seg_head_kernel, dim3(static_cast<unsigned>((lay.total + 3) / 4)), dim3(256), 0, st, p->d_y2.get(), p->d_lin.get(),
                        p->d_lin.get() + static_cast<size_t>(8) * H, logp, lay.total, 2 * H);
     return launch_check("segmenter_exec", "seg_head_kernel");
+}
+
+}  // extern "C"
+
+// Viterbi decoding of log-probs into state sequences (hssfsst.h: hssfsst_decode_states; csrc/segmenter_decode.hpp).  Stateless: the
+// quantised transitions and the launch's offsets travel as kernel arguments, kDecodeBatch recordings per launch.
+extern "C" {
+
+int hssfsst_decode_info(int* segment_steps, int64_t* max_steps)
+{
+    if (segment_steps) *segment_steps = hssfsst::declayout::kSegSteps;
+    if (max_steps) *max_steps = hssfsst::declayout::kMaxSteps;
+    return 0;
+}
+
+int hssfsst_decode_states(const float* logp, const int64_t* offsets, int64_t count, const float* transitions, const float* initial,
+                          uint8_t* states, int64_t* scores, int device, void* stream)
+{
+    namespace dl = hssfsst::declayout;
+    if (count < 0) return fail(HSSFSST_EINVAL, "decode_states: count %lld is negative", static_cast<long long>(count));
+    if (!logp || !offsets || !transitions || !initial || !states)
+        return fail(HSSFSST_EINVAL, "decode_states: bad argument (%s is NULL)",
+                    !logp ? "logp" : !offsets ? "offsets" : !transitions ? "transitions" : !initial ? "initial" : "states");
+    if (device < 0) return fail(HSSFSST_EINVAL, "decode_states: device %d is negative", device);
+    if (reinterpret_cast<uintptr_t>(logp) % 16 != 0) return fail(HSSFSST_EINVAL, "decode_states: logp is not 16-byte aligned");
+    for (int i = 0; i < 16; ++i)
+        if (transitions[i] != transitions[i]) return fail(HSSFSST_EINVAL, "decode_states: transitions[%d][%d] is NaN", i / 4, i % 4);
+    for (int i = 0; i < 4; ++i)
+        if (initial[i] != initial[i]) return fail(HSSFSST_EINVAL, "decode_states: initial[%d] is NaN", i);
+    const hssfsst::declayout::Mat qa = dl::quantise_transitions(transitions);
+    const hssfsst::declayout::Vec qp = dl::quantise4(initial);
+    for (int i = 0; i < 4; ++i)
+        if (qa.m[i][0] == dl::kNeg && qa.m[i][1] == dl::kNeg && qa.m[i][2] == dl::kNeg && qa.m[i][3] == dl::kNeg)
+            return fail(HSSFSST_EINVAL, "decode_states: row %d of transitions is all -inf: state %d has no successor", i, i);
+    if (qp.v[0] == dl::kNeg && qp.v[1] == dl::kNeg && qp.v[2] == dl::kNeg && qp.v[3] == dl::kNeg)
+        return fail(HSSFSST_EINVAL, "decode_states: initial is all -inf: no state to start in");
+    if (offsets[0] != 0) return fail(HSSFSST_EINVAL, "decode_states: offsets[0] is %lld, not 0", static_cast<long long>(offsets[0]));
+    for (int64_t i = 0; i < count; ++i)
+        if (offsets[i + 1] <= offsets[i])
+            return fail(HSSFSST_EINVAL, "decode_states: offsets do not increase at index %lld (offsets[%lld] = %lld, offsets[%lld] = %lld)",
+                        static_cast<long long>(i + 1), static_cast<long long>(i), static_cast<long long>(offsets[i]),
+                        static_cast<long long>(i + 1), static_cast<long long>(offsets[i + 1]));
+    for (int64_t i = 0; i < count; ++i)
+        if (offsets[i + 1] - offsets[i] > dl::kMaxSteps)
+            return fail(HSSFSST_EUNSUPPORTED, "decode_states: recording %lld has %lld steps, over the limit of %lld", static_cast<long long>(i),
+                        static_cast<long long>(offsets[i + 1] - offsets[i]), static_cast<long long>(dl::kMaxSteps));
+    if (offsets[count] > 0x7fffffffLL)
+        return fail(HSSFSST_EUNSUPPORTED, "decode_states: %lld steps in all, over the limit of 2^31 - 1", static_cast<long long>(offsets[count]));
+    if (count == 0) return 0;
+    if (int rc = check_device("decode_states", device)) return rc;
+    DEVICE_SCOPE(device);
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    hssfsst::DecodeArgs args{};
+    args.A = qa;
+    args.pi = qp;
+    for (int64_t r0 = 0; r0 < count; r0 += hssfsst::kDecodeBatch) {
+        const int nrec = static_cast<int>(std::min<int64_t>(hssfsst::kDecodeBatch, count - r0));
+        for (int i = 0; i <= nrec; ++i) args.off[i] = offsets[r0 + i];
+        hipLaunchKernelGGL(hssfsst::seg_decode_kernel, dim3(static_cast<unsigned>(nrec)), dim3(dl::kLanes), 0, st, logp, states,
+                           scores ? reinterpret_cast<long long*>(scores) + r0 : nullptr, args);
+        if (int rc = launch_check("decode_states", "seg_decode_kernel")) return rc;
+    }
+    return 0;
 }
 
 }  // extern "C"

@@ -395,6 +395,39 @@ int hssfsst_segmenter_exec(hssfsst_segmenter* plan, const void* feats, int feats
 int hssfsst_segmenter_exec_ragged(hssfsst_segmenter* plan, const void* feats, int feats_dtype, const int64_t* offsets,
                                   int64_t count, const float* h0, const float* c0, int state_rows, float* logp, void* stream);
 
+/* Viterbi decoding: the segmenter's log-probs -> one state 0..3 (S1, systole, S2, diastole) per step, for a LIST of recordings in
+ * one call (csrc/segmenter_decode.hpp; the arithmetic as plain functions: csrc/decode_layout.hpp).  Stateless: no plan.
+ *   logp         (sum T, 4) float32 emissions e, DEVICE, 16-byte aligned: what hssfsst_segmenter_exec_ragged writes
+ *   offsets      int64 HOST array of count + 1 step offsets, offsets[0] == 0, strictly increasing (as hssfsst_segmenter_exec_ragged)
+ *   transitions  A (4, 4) float32, HOST: A[i][j] = log score of moving from state i to state j
+ *   initial      pi (4) float32, HOST: log score of starting in state j
+ *   states       (sum T) uint8, DEVICE: recording i's path in bytes offsets[i] .. offsets[i + 1]
+ *   scores       (count) int64, DEVICE, or NULL: the best path's score in units of 2^-20
+ * -inf in e, A or pi means "forbidden".
+ * Arithmetic, exact.  Every input value x becomes the int64 q(x) = rint(clamp(x, -32768, +32768) x 2^20), rounding half to even;
+ * q(NaN) = q(-32768); +inf clamps to 32768; q(-inf) = NEG, an absorbing element: NEG + anything = NEG, and NEG loses every max.
+ * Everything after that is int64 add and max, which is exactly associative: with T <= 2^26 steps of two terms of at most 2^35 no
+ * sum exceeds 2^62, and the kernel's chunking gives the sequential loop's result bit for bit:
+ *   d_0[j] = q(pi[j]) + q(e[0][j]);   d_t[j] = max_i (d_(t-1)[i] + q(A[i][j])) + q(e[t][j])  for t >= 1;
+ *   the backpointer psi_t[j] is the SMALLEST i that attains the max; the end state is the SMALLEST j that attains max_j d_(T-1)[j];
+ *   the path follows the backpointers from there; the score is max_j d_(T-1)[j].
+ * The caller owns the emissions: with valid A and pi (below) a recording without -inf emissions has an optimal path that uses
+ * allowed moves only.  A step whose four emissions are all -inf makes the score NEG (INT64_MIN) and the path the one the tie
+ * rule yields (every comparison from there on is a tie): defined, and meaningless.
+ * HSSFSST_EINVAL before any device work: a NULL pointer other than scores, count < 0, offsets[0] != 0 or an offset that does not
+ * increase (the message names the index), a NaN in transitions or initial, a row of transitions or the whole of initial all -inf
+ * (a state without a successor / no state to start in), device < 0, logp not 16-byte aligned.  HSSFSST_EUNSUPPORTED: a recording
+ * of more than 2^26 steps (hssfsst_decode_info: max_steps), more than 2^31 - 1 steps in all.  count == 0 returns 0 and does nothing.
+ * A recording's result does not depend on its neighbours or its place in the list.  Enqueued on `stream` (hipStream_t, NULL =
+ * default) without synchronising: one launch per 256 recordings, one workgroup per recording, no scratch memory -- a step's four
+ * backpointers are kept as one byte in `states` itself until the backtrace overwrites it with the state. */
+int hssfsst_decode_states(const float* logp, const int64_t* offsets, int64_t count, const float* transitions, const float* initial,
+                          uint8_t* states, int64_t* scores, int device, void* stream);
+
+/* The decoder's geometry, no device needed: segment_steps = steps a workgroup stages at a time (a recording is walked in
+ * segments of that many steps from its step 1 on), max_steps = the longest recording (2^26).  Either pointer may be NULL. */
+int hssfsst_decode_info(int* segment_steps, int64_t* max_steps);
+
 /* One DIFFERENTIABLE bidirectional LSTM layer (batch first, nn.LSTM's cell and gate order): the unit a training program stacks
  * under autograd -- the segmenter is two of them.  The plan holds the layer's current weights in the kernels' layouts and the
  * scratch of its calls; the caller owns inputs, outputs and the stash.  Every pointer below is a DEVICE pointer on the plan's
