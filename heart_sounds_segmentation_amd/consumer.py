@@ -93,6 +93,47 @@ _LSTM_KEYS = ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0",
 _DTYPES = {torch.float32: _lib.DTYPE_F32, torch.float16: _lib.DTYPE_F16, torch.bfloat16: _lib.DTYPE_BF16}
 
 
+def _ragged_features(name: str, feats, input_size: int, device):
+    """The features of a ``ragged`` call as ``(data, offs)``: the ``(sum T, input_size)`` arena (a list is packed with one
+    ``torch.cat``, which carries the items' autograd graph; an empty one gives an empty arena on ``device``) and the host list
+    of B + 1 offsets.  ``name`` prefixes the messages."""
+    if isinstance(feats, RaggedFeatures):
+        if feats._raw:
+            raise ValueError(f"{name}: raw (complex, frequency-major) features; the segmenter takes abs or stack features")
+        data, offs = feats.data, list(feats._off)
+    elif isinstance(feats, (list, tuple)):
+        for i, f in enumerate(feats):
+            if not isinstance(f, torch.Tensor) or f.dim() != 2 or f.shape[0] < 1:
+                raise ValueError(f"{name}: item {i} is not a (T, {input_size}) tensor with T >= 1")
+        if len({(f.device, f.dtype, int(f.shape[1])) for f in feats}) > 1:
+            raise ValueError(f"{name}: the items differ in device, dtype or width")
+        offs = [0]
+        for f in feats:
+            offs.append(offs[-1] + int(f.shape[0]))
+        data = torch.cat(list(feats)) if feats else torch.empty((0, input_size), device=device)
+    else:
+        raise ValueError(f"{name}: a RaggedFeatures or a list of (T, F) tensors expected")
+    if data.dim() != 2 or data.shape[1] != input_size or data.shape[0] != offs[-1]:
+        raise ValueError(f"{name}: features of shape (sum T, {input_size}) expected, got {tuple(data.shape)}")
+    return data, offs
+
+
+def _ragged_state(name: str, module_h0, module_c0, h0, c0, B: int, H: int):
+    """``(h0, c0)`` of a ``ragged`` call on B recordings, checked: the call's own, of shape (2, B, H) or (2, 1, H) and as they
+    came (the caller moves them to its device), or the module's when their batch is B or 1."""
+    if (h0 is None) != (c0 is None):
+        raise ValueError(f"{name}: pass both h0 and c0, or neither")
+    if h0 is None:
+        if module_h0.shape[1] not in (B, 1) and B:
+            raise ValueError(f"{name}: {B} recordings, but the module's h0 / c0 were made for batch {module_h0.shape[1]} "
+                             "(pass h0 and c0 of shape (2, B, H) or (2, 1, H) to the call)")
+        return module_h0, module_c0
+    ok = ((2, B, H), (2, 1, H))
+    if tuple(h0.shape) not in ok or tuple(c0.shape) != tuple(h0.shape):
+        raise ValueError(f"{name}: h0 and c0 of shape {ok[0]} or {ok[1]} expected, got {tuple(h0.shape)} and {tuple(c0.shape)}")
+    return h0, c0
+
+
 class HipSegmenter:
     """What ``SegmenterHead.hip()`` returns.  ``seg(feats)``: feats a (B, T, F) float32 / float16 / bfloat16 tensor on
     the plan's GPU -> (B, T, 4) float32 log-probs on the same device, no autograd graph, enqueued on the current stream.
@@ -185,40 +226,16 @@ class HipSegmenter:
         recording is a group of its own), all writing into the one output arena; the result does not depend on it.  The layer
         outputs take 2 x steps x 2H x 4 bytes: 2 x 8.4 M x 480 x 4 B = 32 GB at the default with hidden 240 (plus at most
         128 MiB of projected inputs and 16 KiB of state per 16 recordings); lower it on a device that is shared."""
-        if isinstance(feats, RaggedFeatures):
-            if feats._raw:
-                raise ValueError("HipSegmenter.ragged: raw (complex, frequency-major) features; the segmenter takes abs or stack features")
-            data, offs = feats.data, list(feats._off)
-        elif isinstance(feats, (list, tuple)):
-            for i, f in enumerate(feats):
-                if not isinstance(f, torch.Tensor) or f.dim() != 2 or f.shape[0] < 1:
-                    raise ValueError(f"HipSegmenter.ragged: item {i} is not a (T, {self.input_size}) tensor with T >= 1")
-            if len({(f.device, f.dtype, int(f.shape[1])) for f in feats}) > 1:
-                raise ValueError("HipSegmenter.ragged: the items differ in device, dtype or width")
-            offs = [0]
-            for f in feats:
-                offs.append(offs[-1] + int(f.shape[0]))
-            data = torch.cat([f.detach() for f in feats]) if feats else torch.empty((0, self.input_size), device=self.device)
-        else:
-            raise ValueError("HipSegmenter.ragged: a RaggedFeatures or a list of (T, F) tensors expected")
+        name = "HipSegmenter.ragged"
+        data, offs = _ragged_features(name, feats, self.input_size, self.device)
         B = len(offs) - 1
-        if data.dim() != 2 or data.shape[1] != self.input_size or data.shape[0] != offs[-1]:
-            raise ValueError(f"HipSegmenter.ragged: features of shape (sum T, {self.input_size}) expected, got {tuple(data.shape)}")
         if data.device != self.device:
-            raise ValueError(f"HipSegmenter.ragged: features on {data.device}, the plan on {self.device}")
+            raise ValueError(f"{name}: features on {data.device}, the plan on {self.device}")
         if data.dtype not in _DTYPES:
-            raise ValueError(f"HipSegmenter.ragged: float32, float16 or bfloat16 features expected, got {data.dtype}")
-        if (h0 is None) != (c0 is None):
-            raise ValueError("HipSegmenter.ragged: pass both h0 and c0, or neither")
-        if h0 is None:
-            if self.h0.shape[1] not in (B, 1) and B:
-                raise ValueError(f"HipSegmenter.ragged: {B} recordings, but the module's h0 / c0 were made for batch {self.h0.shape[1]} "
-                                 "(pass h0 and c0 of shape (2, B, H) or (2, 1, H) to the call)")
-            h0, c0 = self.h0, self.c0
-        else:
-            ok = ((2, B, self.hidden_size), (2, 1, self.hidden_size))
-            if tuple(h0.shape) not in ok or tuple(c0.shape) != tuple(h0.shape):
-                raise ValueError(f"HipSegmenter.ragged: h0 and c0 of shape {ok[0]} or {ok[1]} expected, got {tuple(h0.shape)} and {tuple(c0.shape)}")
+            raise ValueError(f"{name}: float32, float16 or bfloat16 features expected, got {data.dtype}")
+        own = h0 is not None
+        h0, c0 = _ragged_state(name, self.h0, self.c0, h0, c0, B, self.hidden_size)
+        if own:
             h0 = h0.detach().to(self.device, torch.float32).contiguous()
             c0 = c0.detach().to(self.device, torch.float32).contiguous()
         if max_steps < 1:
@@ -246,6 +263,49 @@ class HipSegmenter:
         return result
 
 
+# What the dense and the ragged autograd Function of HipBiLSTM share; their saved state and their calls differ.
+def _forward_outputs(x, y_shape, B: int, H: int):
+    """``(y, hn, cn)`` of a forward, uninitialised."""
+    y = torch.empty(y_shape, dtype=torch.float32, device=x.device)
+    hn = torch.empty((2, B, H), dtype=torch.float32, device=x.device)
+    return y, hn, torch.empty_like(hn)
+
+
+def _backward_inputs(ctx, dy, dhn, dcn):
+    """The saved tensors of a backward whose layer still holds the forward's weights, and its seeds as the ABI takes them:
+    ``dy`` contiguous (zeros for None), ``dhn`` / ``dcn`` contiguous or None (the ABI's NULL: zero)."""
+    if ctx.layer._serial != ctx.serial:
+        raise RuntimeError("HipBiLSTM: the layer's weights were repacked for other values between this forward and its "
+                           "backward; the backward recurrence would run against the wrong W_hh")
+    x, h0, c0, y, stash, *weights = ctx.saved_tensors
+    dy = torch.zeros_like(y) if dy is None else dy.contiguous()
+    dhn = None if dhn is None else dhn.contiguous()
+    dcn = None if dcn is None else dcn.contiguous()
+    return x, h0, c0, y, stash, weights, dy, dhn, dcn
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _backward_outputs(x, dgates_shape, B: int, H: int):
+    """``(dgates, dh0, dc0)`` of a backward, uninitialised."""
+    dgates = torch.empty(dgates_shape, dtype=torch.float32, device=x.device)
+    dh0 = torch.empty((2, B, H), dtype=torch.float32, device=x.device)
+    return dgates, dh0, torch.empty_like(dh0)
+
+
+def _weight_grads(g_fwd, g_rev, x2d, hprev_fwd, hprev_rev, weights, need_dx: bool):
+    """The time-parallel products of a backward over ``rows`` = all steps of all recordings: ``g_*`` (rows, 4H) the directions'
+    gate gradients, ``x2d`` (rows, F), ``hprev_*`` (rows, H) the h before each step.  Returns ``(dx (rows, F) or None, the eight
+    parameter gradients in _LSTM_KEYS order)``."""
+    grads = []
+    for g, hprev in ((g_fwd, hprev_fwd), (g_rev, hprev_rev)):
+        db = g.sum(0)
+        grads += [g.t() @ x2d, g.t() @ hprev, db, db.clone()]
+    return (g_fwd @ weights[0] + g_rev @ weights[4] if need_dx else None), grads
+
+
 class _BiLSTMFunction(torch.autograd.Function):
     """forward: hssfsst_bilstm_forward (projection + recurrence kernels, which also fill the stash); backward:
     hssfsst_bilstm_backward (the backward recurrence, which is sequential) and then the time-parallel products as torch.matmul."""
@@ -259,9 +319,7 @@ class _BiLSTMFunction(torch.autograd.Function):
         floats = ctypes.c_int64()
         _lib.check(L.hssfsst_bilstm_stash_floats(plan, B, T, ctypes.byref(floats)), "hssfsst_bilstm_stash_floats")
         stash = torch.empty(floats.value, dtype=torch.float32, device=x.device)
-        y = torch.empty((B, T, 2 * H), dtype=torch.float32, device=x.device)
-        hn = torch.empty((2, B, H), dtype=torch.float32, device=x.device)
-        cn = torch.empty_like(hn)
+        y, hn, cn = _forward_outputs(x, (B, T, 2 * H), B, H)
         stream = torch.cuda.current_stream(x.device).cuda_stream
         _lib.check(L.hssfsst_bilstm_forward(plan, x.data_ptr(), B, T, h0.data_ptr(), c0.data_ptr(), y.data_ptr(), hn.data_ptr(),
                                             cn.data_ptr(), stash.data_ptr(), stream), "hssfsst_bilstm_forward")
@@ -271,35 +329,19 @@ class _BiLSTMFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy, dhn, dcn):
-        layer = ctx.layer
-        if layer._serial != ctx.serial:
-            raise RuntimeError("HipBiLSTM: the layer's weights were repacked for other values between this forward and its "
-                               "backward; the backward recurrence would run against the wrong W_hh")
-        x, h0, c0, y, stash, *weights = ctx.saved_tensors
-        B, T, H = int(x.shape[0]), int(x.shape[1]), layer.hidden_size
-        dy = torch.zeros_like(y) if dy is None else dy.contiguous()
-        dhn = None if dhn is None else dhn.contiguous()
-        dcn = None if dcn is None else dcn.contiguous()
-        dgates = torch.empty((2, B, T, 4 * H), dtype=torch.float32, device=x.device)
-        dh0 = torch.empty((2, B, H), dtype=torch.float32, device=x.device)
-        dc0 = torch.empty_like(dh0)
+        x, h0, c0, y, stash, weights, dy, dhn, dcn = _backward_inputs(ctx, dy, dhn, dcn)
+        B, T, H = int(x.shape[0]), int(x.shape[1]), ctx.layer.hidden_size
+        dgates, dh0, dc0 = _backward_outputs(x, (2, B, T, 4 * H), B, H)
         stream = torch.cuda.current_stream(x.device).cuda_stream
-        _lib.check(_lib.lib().hssfsst_bilstm_backward(layer._plan, stash.data_ptr(), c0.data_ptr(), dy.data_ptr(),
-                                                      None if dhn is None else dhn.data_ptr(),
-                                                      None if dcn is None else dcn.data_ptr(), B, T, dgates.data_ptr(),
-                                                      dh0.data_ptr(), dc0.data_ptr(), stream), "hssfsst_bilstm_backward")
+        _lib.check(_lib.lib().hssfsst_bilstm_backward(ctx.layer._plan, stash.data_ptr(), c0.data_ptr(), dy.data_ptr(), _ptr(dhn), _ptr(dcn),
+                                                      B, T, dgates.data_ptr(), dh0.data_ptr(), dc0.data_ptr(), stream),
+                   "hssfsst_bilstm_backward")
         # h before each step: y shifted one step towards the direction's start, with h0 in front
-        hprev = (torch.cat((h0[0].unsqueeze(1), y[:, :-1, :H]), dim=1), torch.cat((y[:, 1:, H:], h0[1].unsqueeze(1)), dim=1))
-        xf = x.reshape(B * T, -1)
-        grads = []
-        for d in range(2):
-            g = dgates[d].reshape(B * T, 4 * H)
-            db = g.sum(0)
-            grads += [g.t() @ xf, g.t() @ hprev[d].reshape(B * T, H), db, db.clone()]
-        dx = None
-        if ctx.needs_input_grad[1]:
-            dx = (dgates[0].reshape(B * T, 4 * H) @ weights[0] + dgates[1].reshape(B * T, 4 * H) @ weights[4]).reshape(x.shape)
-        return (None, dx, dh0, dc0, *grads)
+        hf = torch.cat((h0[0].unsqueeze(1), y[:, :-1, :H]), dim=1)
+        hr = torch.cat((y[:, 1:, H:], h0[1].unsqueeze(1)), dim=1)
+        dx, grads = _weight_grads(dgates[0].reshape(B * T, 4 * H), dgates[1].reshape(B * T, 4 * H), x.reshape(B * T, -1),
+                                  hf.reshape(B * T, H), hr.reshape(B * T, H), weights, ctx.needs_input_grad[1])
+        return (None, None if dx is None else dx.reshape(x.shape), dh0, dc0, *grads)
 
 
 class _RaggedBiLSTMFunction(torch.autograd.Function):
@@ -316,9 +358,7 @@ class _RaggedBiLSTMFunction(torch.autograd.Function):
         floats = ctypes.c_int64()
         _lib.check(L.hssfsst_bilstm_stash_floats_ragged(plan, optr, B, ctypes.byref(floats)), "hssfsst_bilstm_stash_floats_ragged")
         stash = torch.empty(floats.value, dtype=torch.float32, device=x.device)
-        y = torch.empty((total, 2 * H), dtype=torch.float32, device=x.device)
-        hn = torch.empty((2, B, H), dtype=torch.float32, device=x.device)
-        cn = torch.empty_like(hn)
+        y, hn, cn = _forward_outputs(x, (total, 2 * H), B, H)
         stream = torch.cuda.current_stream(x.device).cuda_stream
         _lib.check(L.hssfsst_bilstm_forward_ragged(plan, x.data_ptr(), optr, B, h0.data_ptr(), c0.data_ptr(), y.data_ptr(),
                                                    hn.data_ptr(), cn.data_ptr(), stash.data_ptr(), stream), "hssfsst_bilstm_forward_ragged")
@@ -328,37 +368,22 @@ class _RaggedBiLSTMFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy, dhn, dcn):
-        layer, offs = ctx.layer, ctx.offs
-        if layer._serial != ctx.serial:
-            raise RuntimeError("HipBiLSTM: the layer's weights were repacked for other values between this forward and its "
-                               "backward; the backward recurrence would run against the wrong W_hh")
-        x, h0, c0, y, stash, *weights = ctx.saved_tensors
-        B, total, H = len(offs) - 1, int(x.shape[0]), layer.hidden_size
-        dy = torch.zeros_like(y) if dy is None else dy.contiguous()
-        dhn = None if dhn is None else dhn.contiguous()
-        dcn = None if dcn is None else dcn.contiguous()
-        dgates = torch.empty((2, total, 4 * H), dtype=torch.float32, device=x.device)
-        dh0 = torch.empty((2, B, H), dtype=torch.float32, device=x.device)
-        dc0 = torch.empty_like(dh0)
+        x, h0, c0, y, stash, weights, dy, dhn, dcn = _backward_inputs(ctx, dy, dhn, dcn)
+        offs = ctx.offs
+        B, total, H = len(offs) - 1, int(x.shape[0]), ctx.layer.hidden_size
+        dgates, dh0, dc0 = _backward_outputs(x, (2, total, 4 * H), B, H)
         stream = torch.cuda.current_stream(x.device).cuda_stream
-        _lib.check(_lib.lib().hssfsst_bilstm_backward_ragged(layer._plan, stash.data_ptr(), c0.data_ptr(), dy.data_ptr(),
-                                                             None if dhn is None else dhn.data_ptr(),
-                                                             None if dcn is None else dcn.data_ptr(),
-                                                             offs.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), B, dgates.data_ptr(),
-                                                             dh0.data_ptr(), dc0.data_ptr(), stream), "hssfsst_bilstm_backward_ragged")
+        _lib.check(_lib.lib().hssfsst_bilstm_backward_ragged(ctx.layer._plan, stash.data_ptr(), c0.data_ptr(), dy.data_ptr(), _ptr(dhn),
+                                                             _ptr(dcn), offs.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), B,
+                                                             dgates.data_ptr(), dh0.data_ptr(), dc0.data_ptr(), stream),
+                   "hssfsst_bilstm_backward_ragged")
         # h before each step: y shifted by one arena row, with h0 written at each recording's first (reverse: last) row
         edges = torch.from_numpy(offs).to(x.device)
         hf = torch.cat((y.new_zeros(1, H), y[:-1, :H]))
         hf[edges[:-1]] = h0[0]
         hr = torch.cat((y[1:, H:], y.new_zeros(1, H)))
         hr[edges[1:] - 1] = h0[1]
-        grads = []
-        for g, hprev in ((dgates[0], hf), (dgates[1], hr)):
-            db = g.sum(0)
-            grads += [g.t() @ x, g.t() @ hprev, db, db.clone()]
-        dx = None
-        if ctx.needs_input_grad[2]:
-            dx = dgates[0] @ weights[0] + dgates[1] @ weights[4]
+        dx, grads = _weight_grads(dgates[0], dgates[1], x, hf, hr, weights, ctx.needs_input_grad[2])
         return (None, None, dx, dh0, dc0, *grads)
 
 
@@ -376,13 +401,14 @@ class HipBiLSTM(nn.Module):
 
     def __init__(self, input_size: int, hidden_size: int):
         super().__init__()
-        self.input_size, self.hidden_size = int(input_size), int(hidden_size)
         self._take(nn.LSTM(input_size=input_size, hidden_size=hidden_size, bidirectional=True, batch_first=True))
-        self._plan, self._plan_device, self._packed, self._serial = None, None, None, 0
 
     def _take(self, lstm: nn.LSTM) -> None:
+        """The sizes and the parameters of ``lstm``; no plan yet."""
+        self.input_size, self.hidden_size = int(lstm.input_size), int(lstm.hidden_size)
         for k in _LSTM_KEYS:
             self.register_parameter(k, getattr(lstm, k))
+        self._plan, self._plan_device, self._packed, self._serial = None, None, None, 0
 
     @classmethod
     def from_lstm(cls, lstm: nn.LSTM) -> "HipBiLSTM":
@@ -391,9 +417,7 @@ class HipBiLSTM(nn.Module):
             raise ValueError("HipBiLSTM.from_lstm: a one-layer, bidirectional, batch-first nn.LSTM with biases expected")
         self = cls.__new__(cls)
         nn.Module.__init__(self)
-        self.input_size, self.hidden_size = lstm.input_size, lstm.hidden_size
         self._take(lstm)
-        self._plan, self._plan_device, self._packed, self._serial = None, None, None, 0
         return self
 
     def __getstate__(self):                                  # (a copy or a pickle makes its own plan on first use)
@@ -429,26 +453,32 @@ class HipBiLSTM(nn.Module):
             self._serial += 1
         return self._plan
 
-    def forward(self, x: torch.Tensor, state):
+    @staticmethod
+    def _check_layer_inputs(name: str, x, h0, c0, weights) -> None:
+        """What the dense and the ragged call ask of their tensors whatever the shapes: the library, a GPU, one device, float32,
+        contiguous parameters.  ``name`` prefixes the messages."""
         L = _lib.lib()                                       # (a missing library is said first)
         del L
         _lib.guard_fork()
         if not torch.cuda.is_available():
             raise RuntimeError("HipBiLSTM: no GPU; the BiLSTM kernels have no CPU path")
+        if x.device.type != "cuda" or any(t.device != x.device for t in (h0, c0, *weights)):
+            raise RuntimeError(f"{name}: input, state and parameters must be on one GPU (input on {x.device}, "
+                               f"parameters on {weights[0].device}); there is no CPU path")
+        if any(t.dtype != torch.float32 for t in (x, h0, c0, *weights)):
+            raise ValueError(f"{name}: float32 input, state and parameters expected (cast half-precision features first)")
+        if any(not w.is_contiguous() for w in weights):
+            raise ValueError(f"{name}: contiguous parameters expected")
+
+    def forward(self, x: torch.Tensor, state):
         h0, c0 = state
         weights = [getattr(self, k) for k in _LSTM_KEYS]
-        if x.device.type != "cuda" or any(t.device != x.device for t in (h0, c0, *weights)):
-            raise RuntimeError(f"HipBiLSTM: input, state and parameters must be on one GPU (input on {x.device}, "
-                               f"parameters on {weights[0].device}); there is no CPU path")
+        self._check_layer_inputs("HipBiLSTM", x, h0, c0, weights)
         if x.dim() != 3 or x.shape[2] != self.input_size or x.shape[0] < 1 or x.shape[1] < 1:
             raise ValueError(f"HipBiLSTM: input of shape (B, T, {self.input_size}) expected, got {tuple(x.shape)}")
         want = (2, int(x.shape[0]), self.hidden_size)
         if tuple(h0.shape) != want or tuple(c0.shape) != want:
             raise ValueError(f"HipBiLSTM: h0 and c0 of shape {want} expected, got {tuple(h0.shape)} and {tuple(c0.shape)}")
-        if any(t.dtype != torch.float32 for t in (x, h0, c0, *weights)):
-            raise ValueError("HipBiLSTM: float32 input, state and parameters expected (cast half-precision features first)")
-        if any(not w.is_contiguous() for w in weights):
-            raise ValueError("HipBiLSTM: contiguous parameters expected")
         y, hn, cn = _BiLSTMFunction.apply(self, x, h0, c0, *weights)
         return y, (hn, cn)
 
@@ -463,16 +493,9 @@ class HipBiLSTM(nn.Module):
         the rounding of a longer sum.)  The stash costs 2 x (sum over tiles of 16 recordings, longest first, of the tile's longest
         recording) x 80 KiB per layer and call: 5.8 GB per layer for one tile of 35 500-step recordings.  An empty list gives
         empty results.  ``|h0| < 64``, as for the dense call."""
-        L = _lib.lib()
-        del L
-        _lib.guard_fork()
-        if not torch.cuda.is_available():
-            raise RuntimeError("HipBiLSTM: no GPU; the BiLSTM kernels have no CPU path")
         h0, c0 = state
         weights = [getattr(self, k) for k in _LSTM_KEYS]
-        if x.device.type != "cuda" or any(t.device != x.device for t in (h0, c0, *weights)):
-            raise RuntimeError(f"HipBiLSTM.ragged: input, state and parameters must be on one GPU (input on {x.device}, "
-                               f"parameters on {weights[0].device}); there is no CPU path")
+        self._check_layer_inputs("HipBiLSTM.ragged", x, h0, c0, weights)
         offs = np.ascontiguousarray(offsets.detach().cpu().numpy() if isinstance(offsets, torch.Tensor) else offsets, dtype=np.int64)
         if offs.ndim != 1 or offs.shape[0] < 1:
             raise ValueError("HipBiLSTM.ragged: offsets must be a 1-D sequence of B + 1 step offsets")
@@ -483,10 +506,6 @@ class HipBiLSTM(nn.Module):
         want = (2, B, self.hidden_size)
         if tuple(h0.shape) != want or tuple(c0.shape) != want:
             raise ValueError(f"HipBiLSTM.ragged: h0 and c0 of shape {want} expected, got {tuple(h0.shape)} and {tuple(c0.shape)}")
-        if any(t.dtype != torch.float32 for t in (x, h0, c0, *weights)):
-            raise ValueError("HipBiLSTM.ragged: float32 input, state and parameters expected (cast half-precision features first)")
-        if any(not w.is_contiguous() for w in weights):
-            raise ValueError("HipBiLSTM.ragged: contiguous parameters expected")
         if B == 0:
             return x.new_empty((0, 2 * self.hidden_size)), (h0.clone(), c0.clone())
         y, hn, cn = _RaggedBiLSTMFunction.apply(self, offs, x, h0, c0, *weights)
@@ -526,41 +545,16 @@ class HipSegmenterHead(SegmenterHead):
         if not torch.cuda.is_available():
             raise RuntimeError(f"{name}: no GPU; the BiLSTM kernels have no CPU path")
         device = self.linear.weight.device
-        if isinstance(feats, RaggedFeatures):
-            if feats._raw:
-                raise ValueError(f"{name}: raw (complex, frequency-major) features; the segmenter takes abs or stack features")
-            data, offs = feats.data, [int(o) for o in feats._off]
-        elif isinstance(feats, (list, tuple)):
-            for i, f in enumerate(feats):
-                if not isinstance(f, torch.Tensor) or f.dim() != 2 or f.shape[0] < 1:
-                    raise ValueError(f"{name}: item {i} is not a (T, {F}) tensor with T >= 1")
-            if len({(f.device, f.dtype, int(f.shape[1])) for f in feats}) > 1:
-                raise ValueError(f"{name}: the items differ in device, dtype or width")
-            offs = [0]
-            for f in feats:
-                offs.append(offs[-1] + int(f.shape[0]))
-            data = torch.cat(list(feats)) if feats else torch.empty((0, F), device=device)
-        else:
-            raise ValueError(f"{name}: a RaggedFeatures or a list of (T, F) tensors expected")
+        data, offs = _ragged_features(name, feats, F, device)
         B = len(offs) - 1
-        if data.dim() != 2 or data.shape[1] != F or data.shape[0] != offs[-1]:
-            raise ValueError(f"{name}: features of shape (sum T, {F}) expected, got {tuple(data.shape)}")
         if data.device != device:
             raise ValueError(f"{name}: features on {data.device}, the module on {device}")
         if data.dtype not in _DTYPES:
             raise ValueError(f"{name}: float32, float16 or bfloat16 features expected, got {data.dtype}")
-        if (h0 is None) != (c0 is None):
-            raise ValueError(f"{name}: pass both h0 and c0, or neither")
-        if h0 is None:
-            if self.h0.shape[1] not in (B, 1) and B:
-                raise ValueError(f"{name}: {B} recordings, but the module's h0 / c0 were made for batch {self.h0.shape[1]} "
-                                 "(pass h0 and c0 of shape (2, B, H) or (2, 1, H) to the call)")
-            h0, c0 = self.h0, self.c0
-        else:
-            ok = ((2, B, H), (2, 1, H))
-            if tuple(h0.shape) not in ok or tuple(c0.shape) != tuple(h0.shape):
-                raise ValueError(f"{name}: h0 and c0 of shape {ok[0]} or {ok[1]} expected, got {tuple(h0.shape)} and {tuple(c0.shape)}")
-            h0, c0 = h0.to(device, torch.float32), c0.to(device, torch.float32)
+        own = h0 is not None
+        h0, c0 = _ragged_state(name, self.h0, self.c0, h0, c0, B, H)
+        if own:
+            h0, c0 = h0.to(device, torch.float32), c0.to(device, torch.float32)     # (carries the autograd graph)
         offsets = torch.tensor(offs, dtype=torch.int64)
         if B == 0:
             return RaggedFeatures(torch.empty((0, 4), dtype=torch.float32, device=device), offsets, 4, False)

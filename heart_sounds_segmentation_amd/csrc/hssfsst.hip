@@ -2322,35 +2322,82 @@ int hssfsst_stream_step(hssfsst_plan* p, float* tape, int64_t tape_len, int64_t 
 
 // BiLSTM segmenter (hssfsst.h: hssfsst_segmenter_create): the model's weights, uploaded once in the layouts the kernels of
 // csrc/segmenter_lstm.hpp consume, plus the scratch of its execs (owned by the plan, grown on demand, freed with it).
+namespace {
+
+// The forward tables of one BiLSTM layer, as the kernels of csrc/segmenter_lstm.hpp consume them (seglayout::wt_source,
+// gate_col_row, fwd_stream_source): made on the host by seg_upload_layer or on the device by seg_pack_kernel.
+struct SegLayer {
+    int F = 0, Fp = 0;                                   // input width and its multiple of 32
+    DevBuf<float> d_wt;                                  // [dir][Fp][4 Hp]: W_ih^T, columns in (unit tile, gate, unit) order
+    DevBuf<float> d_bias;                                // [dir][4 Hp]: b_ih + b_hh, same order
+    DevBuf<hssfsst::seg_h8> d_whh;                       // [dir][wave][K block][tile x gate][lane]{hi, lo}: W_hh x wscale, split f16
+};
+
+// The list of a ragged call on the device: its layout (segmenter_layout.hpp) and the layout's tables in one block
+// (seglayout::table_block), made and uploaded only when the offsets differ from the last call's.
+struct SegListTables {
+    struct Views {
+        const long long *off, *base;
+        const int *len, *rec, *walk;
+        int slots;
+        long long walked;                                // base[tiles]: the steps one direction walks
+    };
+    hssfsst::seglayout::Layout lay;                      // (of tab's key: rebuilt between its begin and commit)
+    UploadedTable tab;
+    explicit SegListTables(const char* what) : tab(what) {}
+    // offsets: checked by seg_check_list.  May throw std::bad_alloc.
+    int acquire(const int64_t* offsets, int64_t count, hipStream_t st, Views* out)
+    {
+        namespace seglayout = hssfsst::seglayout;
+        const seglayout::TableBlock b = seglayout::table_block(count);
+        auto key = [&](size_t i) { return offsets[i]; };
+        if (!tab.same(static_cast<size_t>(count + 1), key)) {
+            unsigned char* h = nullptr;
+            if (int rc = tab.begin(b.bytes, &h)) return rc;
+            seglayout::build(offsets, count, lay);
+            const std::vector<long long> base = seglayout::tile_base(lay);
+            std::memcpy(h + b.o_off, lay.slot_off.data(), b.slots * sizeof(long long));
+            std::memcpy(h + b.o_base, base.data(), (b.tiles + 1) * sizeof(long long));
+            std::memcpy(h + b.o_len, lay.slot_len.data(), b.slots * sizeof(int));
+            std::memcpy(h + b.o_rec, lay.slot_rec.data(), b.slots * sizeof(int));
+            std::memcpy(h + b.o_walk, lay.tile_walk.data(), b.tiles * sizeof(int));
+            if (int rc = tab.commit(st, static_cast<size_t>(count + 1), key)) return rc;
+        }
+        out->off = reinterpret_cast<const long long*>(tab.get() + b.o_off);
+        out->base = reinterpret_cast<const long long*>(tab.get() + b.o_base);
+        out->len = reinterpret_cast<const int*>(tab.get() + b.o_len);
+        out->rec = reinterpret_cast<const int*>(tab.get() + b.o_rec);
+        out->walk = reinterpret_cast<const int*>(tab.get() + b.o_walk);
+        out->slots = static_cast<int>(b.slots);
+        out->walked = seglayout::stash_floats_ragged(lay) / (2 * seglayout::kStashStepFloats);
+        return 0;
+    }
+};
+
+}  // namespace
+
 struct hssfsst_segmenter {
     int device = -1;
     int F = 0, H = 0;
-    struct Layer {
-        int F = 0, Fp = 0;                               // input width and its multiple of 32
-        DevBuf<float> d_wt;                              // [dir][Fp][4 Hp]: W_ih^T, columns in (unit tile, gate, unit) order
-        DevBuf<float> d_bias;                            // [dir][4 Hp]: b_ih + b_hh, same order
-        DevBuf<hssfsst::seg_h8> d_whh;                   // [dir][wave][K block][tile x gate][lane]{hi, lo}: W_hh x wscale, split f16
+    struct Layer : SegLayer {
         float inv_scale = 1.0f;                          // 1 / (wscale x kSegHScale)
     } layer[2];
     DevBuf<float> d_lin;                                 // linear.weight (4, 2H) | linear.bias (4)
     DevBuf<float> d_pre;                                 // [dir][batch tile][Tc][gate tile][lane][4]: one chunk's input projection
     DevBuf<float> d_y1, d_y2;                            // (B, T, 2H): the layers' outputs
     DevBuf<float> d_state;                               // [h, c][dir][Bp][Hp]: carried from chunk to chunk and from layer 1 to layer 2
-    // hssfsst_segmenter_exec_ragged: the list's layout (segmenter_layout.hpp) and its device tables -- slot_off long long[slots],
-    // slot_len int[slots], slot_rec int[slots], tile_walk int[tiles] -- in one block, kept while the next call has the same offsets
-    hssfsst::seglayout::Layout lay;                      // (of tab's key: rebuilt between its begin and commit)
-    UploadedTable tab{"segmenter_exec_ragged"};
+    SegListTables list{"segmenter_exec_ragged"};         // hssfsst_segmenter_exec_ragged: kept while the next call has the same offsets
 };
 
 namespace {
 
-// src: {weight_ih, weight_hh, bias_ih, bias_hh} x {forward, reverse} of one nn.LSTM layer, as in its state_dict
+// src: {weight_ih, weight_hh, bias_ih, bias_hh} x {forward, reverse} of one nn.LSTM layer, as in its state_dict.  Every table is
+// filled by its output index through the functions seg_pack_kernel uses; the scale is seg_pack_scale_kernel's.
 int seg_upload_layer(hssfsst_segmenter::Layer& L, int F, int H, const float* const* src)
 {
-    constexpr int Hp = hssfsst::kSegHp, N = 4 * Hp;
+    namespace sl = hssfsst::seglayout;
     L.F = F;
     L.Fp = (F + 31) / 32 * 32;
-    std::vector<float> wt(static_cast<size_t>(2) * L.Fp * N, 0.0f), bias(static_cast<size_t>(2) * N, 0.0f);
     float wmax = 0.0f;
     for (int d = 0; d < 2; ++d) {
         const float* whh = src[4 * d + 1];
@@ -2362,34 +2409,30 @@ int seg_upload_layer(hssfsst_segmenter::Layer& L, int F, int H, const float* con
     float wscale = 1.0f;
     if (wmax > 0.0f && std::isfinite(wmax)) { (void)std::frexp(wmax, &e); wscale = std::ldexp(1.0f, 13 - e); }
     L.inv_scale = 1.0f / (wscale * hssfsst::kSegHScale);
-    std::vector<_Float16> stream(static_cast<size_t>(2) * hssfsst::kSegWaves * hssfsst::kSegKb * 8 * 64 * 16, static_cast<_Float16>(0.0f));
+    const long long per_wt = static_cast<long long>(L.Fp) * sl::kGateCols, per_f = sl::kWtStreamHalves / 2;
+    std::vector<float> wt(static_cast<size_t>(2 * per_wt)), bias(static_cast<size_t>(2) * sl::kGateCols);
+    std::vector<_Float16> stream(static_cast<size_t>(2 * per_f));
     for (int d = 0; d < 2; ++d) {
         const float *wih = src[4 * d], *whh = src[4 * d + 1], *bih = src[4 * d + 2], *bhh = src[4 * d + 3];
-        for (int ut = 0; ut < Hp / 16; ++ut)
-            for (int g = 0; g < 4; ++g)
-                for (int c = 0; c < 16; ++c) {
-                    const int u = ut * 16 + c, n = (ut * 4 + g) * 16 + c;
-                    if (u >= H) continue;
-                    const size_t row = static_cast<size_t>(g) * H + u;
-                    bias[static_cast<size_t>(d) * N + n] = bih[row] + bhh[row];
-                    for (int k = 0; k < F; ++k) wt[(static_cast<size_t>(d) * L.Fp + k) * N + n] = wih[row * F + k];
-                }
-        for (int w = 0; w < hssfsst::kSegWaves; ++w)
-            for (int kb = 0; kb < hssfsst::kSegKb; ++kb)
-                for (int q = 0; q < 8; ++q)
-                    for (int lane = 0; lane < 64; ++lane) {
-                        const int u = (w * 2 + (q >> 2)) * 16 + (lane & 15), g = q & 3;
-                        if (u >= H) continue;
-                        _Float16* dst = stream.data() + ((((static_cast<size_t>(d) * hssfsst::kSegWaves + w) * hssfsst::kSegKb + kb) * 8 + q) * 64 + lane) * 16;
-                        for (int j = 0; j < 8; ++j) {
-                            const int k = kb * 32 + 8 * (lane >> 4) + j;
-                            if (k >= H) continue;
-                            const float v = whh[(static_cast<size_t>(g) * H + u) * H + k] * wscale;
-                            const _Float16 hi = static_cast<_Float16>(v);
-                            dst[j] = hi;
-                            dst[8 + j] = static_cast<_Float16>(v - static_cast<float>(hi));
-                        }
-                    }
+        for (long long i = 0; i < per_wt; ++i) {
+            const long long s = sl::wt_source(i, F, H);
+            wt[static_cast<size_t>(d * per_wt + i)] = s >= 0 ? wih[s] : 0.0f;
+        }
+        for (int n = 0; n < sl::kGateCols; ++n) {
+            const long long row = sl::gate_col_row(n, H);
+            bias[static_cast<size_t>(d) * sl::kGateCols + n] = row >= 0 ? bih[row] + bhh[row] : 0.0f;
+        }
+        for (long long i = 0; i < per_f; ++i) {
+            int lo = 0;
+            const long long s = sl::fwd_stream_source(i, H, &lo);
+            _Float16 out = static_cast<_Float16>(0.0f);
+            if (s >= 0) {
+                const float v = whh[s] * wscale;
+                const _Float16 hi = static_cast<_Float16>(v);
+                out = lo ? static_cast<_Float16>(v - static_cast<float>(hi)) : hi;
+            }
+            stream[static_cast<size_t>(d * per_f + i)] = out;
+        }
     }
     if (int rc = L.d_wt.upload(wt.data(), wt.size())) return rc;
     if (int rc = L.d_bias.upload(bias.data(), bias.size())) return rc;
@@ -2430,51 +2473,91 @@ int seg_check_list(const char* what, const int64_t* offsets, int64_t count)
     return 0;
 }
 
-// the scratch of an exec, in elements: projection, the two layers' outputs, carried state
-int seg_grow_scratch(hssfsst_segmenter* p, size_t pre, size_t y1, size_t y2, size_t state)
+// The geometry of a call as the forward kernels take it.  Dense: B rows of T steps, Bp padded rows.  Ragged: the list's tables.
+void seg_dense_args(int B, int T, int Bp, hssfsst::SegProjArgs* pa, hssfsst::SegRecArgs* ra)
 {
-    if (int rc = p->d_pre.grow(pre)) return rc;
-    if (int rc = p->d_y1.grow(y1)) return rc;
-    if (int rc = p->d_y2.grow(y2)) return rc;
-    return p->d_state.grow(state);
+    pa->B = ra->B = B;
+    pa->T = ra->T = T;
+    ra->Bp = Bp;
+}
+void seg_ragged_args(const SegListTables::Views& t, hssfsst::SegProjArgs* pa, hssfsst::SegRecArgs* ra)
+{
+    ra->Bp = t.slots;
+    pa->slot_off = ra->slot_off = t.off;
+    pa->slot_len = ra->slot_len = t.len;
+    pa->tile_walk = ra->tile_walk = t.walk;
+    ra->tile_base = t.base;                              // (read by the TRAIN kernels only)
+    ra->walked = t.walked;
 }
 
-// The two layers of an exec, each one launch pair per chunk.  pa0 / ra0 carry the call's own fields (dense: B, T, Bp; ragged: the
-// slot count and the layout's device tables); the plan's, the layer's and the chunk's are filled in here.
-template <bool RAGGED>
-int seg_run_layers(hssfsst_segmenter* p, hipStream_t st, const void* feats, int feats_dtype, const hssfsst::SegProjArgs& pa0,
-                   const hssfsst::SegRecArgs& ra0, const std::vector<hssfsst::seglayout::Chunk>& chunks)
+// state [2][dir][Bp][Hp] <- (p0, p1): grown, then seeded by seg_pair_init_kernel.  slot_rec: the slots' recordings of a ragged call
+// (B: the rows of p0 / p1), NULL for a dense one.
+int seg_seed_state(const char* what, hipStream_t st, DevBuf<float>& state, const float* p0, const float* p1, int B, int H, int Bp,
+                   const int* slot_rec)
 {
-    for (int l = 0; l < 2; ++l) {
-        const hssfsst_segmenter::Layer& L = p->layer[l];
-        hssfsst::SegProjArgs pa = pa0;
-        pa.x = l ? static_cast<const void*>(p->d_y1.get()) : feats;
-        pa.x_dtype = l ? HSSFSST_DTYPE_F32 : feats_dtype;
-        pa.relu = l;
-        pa.F = L.F; pa.Fp = L.Fp;
-        pa.wt = L.d_wt.get(); pa.bias = L.d_bias.get(); pa.pre = p->d_pre.get();
-        hssfsst::SegRecArgs ra = ra0;
-        ra.pre = p->d_pre.get(); ra.whh = L.d_whh.get(); ra.state = p->d_state.get();
-        ra.y = l ? p->d_y2.get() : p->d_y1.get();
-        ra.H = p->H; ra.inv_scale = L.inv_scale;
-        for (const hssfsst::seglayout::Chunk& c : chunks) {
-            pa.n = ra.n = c.n;
-            pa.Tc = ra.Tc = c.Tc;
-            if constexpr (RAGGED) {
-                pa.s0 = ra.s0 = c.s0;
-            } else {
-                // the forward direction takes its chunks upwards, the reverse direction the mirrored ones downwards
-                pa.t0[0] = ra.t0[0] = c.s0;
-                pa.t0[1] = ra.t0[1] = ra.T - c.s0 - c.n;
-            }
-            hipLaunchKernelGGL(hssfsst::seg_proj_kernel<RAGGED>, dim3(4 * hssfsst::kSegHp / 64, static_cast<unsigned>(c.tiles * ((c.n + 7) / 8)), 2),
-                               dim3(256), 0, st, pa);
-            if (int rc = launch_check("segmenter_exec", RAGGED ? "seg_proj_kernel<ragged>" : "seg_proj_kernel")) return rc;
-            hipLaunchKernelGGL(hssfsst::seg_rec_kernel<RAGGED>, dim3(static_cast<unsigned>(c.tiles), 2), dim3(64 * hssfsst::kSegWaves), 0, st, ra);
-            if (int rc = launch_check("segmenter_exec", RAGGED ? "seg_rec_kernel<ragged>" : "seg_rec_kernel")) return rc;
+    const size_t nstate = static_cast<size_t>(4) * Bp * hssfsst::kSegHp;
+    if (int rc = state.grow(nstate)) return rc;
+    hipLaunchKernelGGL((slot_rec ? hssfsst::seg_pair_init_kernel<true> : hssfsst::seg_pair_init_kernel<false>),
+                       dim3(static_cast<unsigned>((nstate + 255) / 256)), dim3(256), 0, st, p0, p1, state.get(), B, H, Bp, slot_rec);
+    return launch_check(what, slot_rec ? "seg_pair_init_kernel<ragged>" : "seg_pair_init_kernel");
+}
+
+// One layer, forwards: a launch pair (projection, recurrence) per chunk.  pa / ra come with the call's fields -- the geometry
+// (seg_dense_args, seg_ragged_args), x and y, the scratch, H, the scale and, for TRAIN, the stash; the layer's and the chunk's are
+// filled in here.  `what`: the entry point, for errors.
+template <bool RAGGED, bool TRAIN>
+int seg_forward_layer(const char* what, hipStream_t st, const SegLayer& L, hssfsst::SegProjArgs pa, hssfsst::SegRecArgs ra,
+                      const std::vector<hssfsst::seglayout::Chunk>& chunks)
+{
+    pa.F = L.F; pa.Fp = L.Fp;
+    pa.wt = L.d_wt.get(); pa.bias = L.d_bias.get();
+    ra.whh = L.d_whh.get();
+    for (const hssfsst::seglayout::Chunk& c : chunks) {
+        pa.n = ra.n = c.n;
+        pa.Tc = ra.Tc = c.Tc;
+        if constexpr (RAGGED) {
+            pa.s0 = ra.s0 = c.s0;
+        } else {
+            // the forward direction takes its chunks upwards, the reverse direction the mirrored ones downwards
+            pa.t0[0] = ra.t0[0] = c.s0;
+            pa.t0[1] = ra.t0[1] = ra.T - c.s0 - c.n;
         }
+        hipLaunchKernelGGL(hssfsst::seg_proj_kernel<RAGGED>, dim3(4 * hssfsst::kSegHp / 64, static_cast<unsigned>(c.tiles * ((c.n + 7) / 8)), 2),
+                           dim3(256), 0, st, pa);
+        if (int rc = launch_check(what, RAGGED ? "seg_proj_kernel<ragged>" : "seg_proj_kernel")) return rc;
+        hipLaunchKernelGGL((hssfsst::seg_rec_kernel<RAGGED, TRAIN>), dim3(static_cast<unsigned>(c.tiles), 2), dim3(64 * hssfsst::kSegWaves), 0, st, ra);
+        if (int rc = launch_check(what, RAGGED ? (TRAIN ? "seg_rec_kernel<ragged, train>" : "seg_rec_kernel<ragged>")
+                                               : (TRAIN ? "seg_rec_kernel<train>" : "seg_rec_kernel"))) return rc;
     }
     return 0;
+}
+
+// The two layers of an inference exec and its head: layer 2 reads layer 1's output rectified and starts from its final state.
+// pa / ra: the call's geometry; rows: B T, or the list's steps.
+template <bool RAGGED>
+int seg_run_layers(hssfsst_segmenter* p, hipStream_t st, const void* feats, int feats_dtype, hssfsst::SegProjArgs pa, hssfsst::SegRecArgs ra,
+                   const std::vector<hssfsst::seglayout::Chunk>& chunks, long long rows, float* logp)
+{
+    ra.pre = pa.pre = p->d_pre.get();
+    ra.state = p->d_state.get();
+    ra.H = p->H;
+    pa.x = feats; pa.x_dtype = feats_dtype; pa.relu = 0;
+    ra.y = p->d_y1.get(); ra.inv_scale = p->layer[0].inv_scale;
+    if (int rc = seg_forward_layer<RAGGED, false>("segmenter_exec", st, p->layer[0], pa, ra, chunks)) return rc;
+    pa.x = p->d_y1.get(); pa.x_dtype = HSSFSST_DTYPE_F32; pa.relu = 1;
+    ra.y = p->d_y2.get(); ra.inv_scale = p->layer[1].inv_scale;
+    if (int rc = seg_forward_layer<RAGGED, false>("segmenter_exec", st, p->layer[1], pa, ra, chunks)) return rc;
+    hipLaunchKernelGGL(hssfsst::seg_head_kernel, dim3(static_cast<unsigned>((rows + 3) / 4)), dim3(256), 0, st, p->d_y2.get(), p->d_lin.get(),
+                       p->d_lin.get() + static_cast<size_t>(8) * p->H, logp, rows, 2 * p->H);
+    return launch_check("segmenter_exec", "seg_head_kernel");
+}
+
+// the scratch of an inference exec, in elements: one chunk's projection and the two layers' outputs of ylen elements each
+int seg_grow_scratch(hssfsst_segmenter* p, size_t pre, size_t ylen)
+{
+    if (int rc = p->d_pre.grow(pre)) return rc;
+    if (int rc = p->d_y1.grow(ylen)) return rc;
+    return p->d_y2.grow(ylen);
 }
 
 }  // namespace
@@ -2549,21 +2632,12 @@ int hssfsst_segmenter_exec(hssfsst_segmenter* p, const void* feats, int feats_dt
     } catch (const std::bad_alloc&) {
         return fail(HSSFSST_ENOMEM, "segmenter_exec: out of host memory");
     }
-    int rc;
-    const size_t ylen = static_cast<size_t>(B) * T * 2 * H, nstate = static_cast<size_t>(4) * Bp * hssfsst::kSegHp;
-    if ((rc = seg_grow_scratch(p, hssfsst::seglayout::pre_floats(chunks, kSegTileStepBytes), ylen, ylen, nstate)) != 0) return rc;
-    hipLaunchKernelGGL(hssfsst::seg_state_init_kernel<false>, dim3(static_cast<unsigned>((nstate + 255) / 256)), dim3(256), 0, st, h0, c0,
-                       p->d_state.get(), B, H, Bp, static_cast<const int*>(nullptr));
-    if ((rc = launch_check("segmenter_exec", "seg_state_init_kernel")) != 0) return rc;
+    if (int rc = seg_grow_scratch(p, hssfsst::seglayout::pre_floats(chunks, kSegTileStepBytes), static_cast<size_t>(B) * T * 2 * H)) return rc;
+    if (int rc = seg_seed_state("segmenter_exec", st, p->d_state, h0, c0, B, H, Bp, nullptr)) return rc;
     hssfsst::SegProjArgs pa{};
-    pa.B = B; pa.T = T;
     hssfsst::SegRecArgs ra{};
-    ra.B = B; ra.T = T; ra.Bp = Bp;
-    if ((rc = seg_run_layers<false>(p, st, feats, feats_dtype, pa, ra, chunks)) != 0) return rc;
-    const long long rows = static_cast<long long>(B) * T;
-    hipLaunchKernelGGL(hssfsst::seg_head_kernel, dim3(static_cast<unsigned>((rows + 3) / 4)), dim3(256), 0, st, p->d_y2.get(), p->d_lin.get(),
-                       p->d_lin.get() + static_cast<size_t>(8) * H, logp, rows, 2 * H);
-    return launch_check("segmenter_exec", "seg_head_kernel");
+    seg_dense_args(B, T, Bp, &pa, &ra);
+    return seg_run_layers<false>(p, st, feats, feats_dtype, pa, ra, chunks, static_cast<long long>(B) * T, logp);
 }
 
 int hssfsst_segmenter_exec_ragged(hssfsst_segmenter* p, const void* feats, int feats_dtype, const int64_t* offsets, int64_t count,
@@ -2583,49 +2657,22 @@ int hssfsst_segmenter_exec_ragged(hssfsst_segmenter* p, const void* feats, int f
     DEVICE_SCOPE(p->device);
     const hipStream_t st = static_cast<hipStream_t>(stream);
     const int H = p->H;
-    int rc;
-
-    // the tables (kept while the offsets stay the same): their sizes follow from count alone
-    const size_t tiles = static_cast<size_t>((count + seglayout::kSlotRows - 1) / seglayout::kSlotRows), slots = tiles * seglayout::kSlotRows;
-    const size_t o_len = slots * sizeof(long long), o_rec = o_len + slots * sizeof(int), o_walk = o_rec + slots * sizeof(int);
-    const seglayout::Layout& lay = p->lay;
-    auto key = [&](size_t i) { return offsets[i]; };
+    const seglayout::Layout& lay = p->list.lay;
+    SegListTables::Views t{};
     std::vector<seglayout::Chunk> chunks;
     try {
-        if (!p->tab.same(static_cast<size_t>(count + 1), key)) {
-            unsigned char* h = nullptr;
-            if ((rc = p->tab.begin(o_walk + tiles * sizeof(int), &h)) != 0) return rc;
-            seglayout::build(offsets, count, p->lay);
-            std::memcpy(h, lay.slot_off.data(), o_len);
-            std::memcpy(h + o_len, lay.slot_len.data(), slots * sizeof(int));
-            std::memcpy(h + o_rec, lay.slot_rec.data(), slots * sizeof(int));
-            std::memcpy(h + o_walk, lay.tile_walk.data(), tiles * sizeof(int));
-            if ((rc = p->tab.commit(st, static_cast<size_t>(count + 1), key)) != 0) return rc;
-        }
+        if (int rc = p->list.acquire(offsets, count, st, &t)) return rc;
         const int mib = debug_switches().seg_ragged_pre_mib;          // (A-B switch of tools/segmenter_ragged_bench.py: same bits)
         chunks = seglayout::ragged_chunks(lay, kSegTileStepBytes, mib > 0 ? static_cast<size_t>(mib) << 20 : seglayout::kSegPreBytes);
     } catch (const std::bad_alloc&) {
         return fail(HSSFSST_ENOMEM, "segmenter_exec_ragged: out of host memory");
     }
-    const auto* d_off = reinterpret_cast<const long long*>(p->tab.get());
-    const int* d_len = reinterpret_cast<const int*>(p->tab.get() + o_len);
-    const int* d_rec = reinterpret_cast<const int*>(p->tab.get() + o_rec);
-    const int* d_walk = reinterpret_cast<const int*>(p->tab.get() + o_walk);
-
-    const size_t ylen = static_cast<size_t>(lay.total) * 2 * H, nstate = static_cast<size_t>(4) * slots * hssfsst::kSegHp;
-    if ((rc = seg_grow_scratch(p, seglayout::pre_floats(chunks, kSegTileStepBytes), ylen, ylen, nstate)) != 0) return rc;
-    hipLaunchKernelGGL(hssfsst::seg_state_init_kernel<true>, dim3(static_cast<unsigned>((nstate + 255) / 256)), dim3(256), 0, st, h0, c0,
-                       p->d_state.get(), state_rows, H, static_cast<int>(slots), d_rec);
-    if ((rc = launch_check("segmenter_exec", "seg_state_init_kernel<ragged>")) != 0) return rc;
+    if (int rc = seg_grow_scratch(p, seglayout::pre_floats(chunks, kSegTileStepBytes), static_cast<size_t>(lay.total) * 2 * H)) return rc;
+    if (int rc = seg_seed_state("segmenter_exec", st, p->d_state, h0, c0, state_rows, H, t.slots, t.rec)) return rc;
     hssfsst::SegProjArgs pa{};
-    pa.slot_off = d_off; pa.slot_len = d_len; pa.tile_walk = d_walk;
     hssfsst::SegRecArgs ra{};
-    ra.Bp = static_cast<int>(slots);
-    ra.slot_off = d_off; ra.slot_len = d_len; ra.tile_walk = d_walk;
-    if ((rc = seg_run_layers<true>(p, st, feats, feats_dtype, pa, ra, chunks)) != 0) return rc;
-    hipLaunchKernelGGL(hssfsst::seg_head_kernel, dim3(static_cast<unsigned>((lay.total + 3) / 4)), dim3(256), 0, st, p->d_y2.get(), p->d_lin.get(),
-                       p->d_lin.get() + static_cast<size_t>(8) * H, logp, lay.total, 2 * H);
-    return launch_check("segmenter_exec", "seg_head_kernel");
+    seg_ragged_args(t, &pa, &ra);
+    return seg_run_layers<true>(p, st, feats, feats_dtype, pa, ra, chunks, lay.total, logp);
 }
 
 }  // extern "C"
@@ -2697,18 +2744,14 @@ int hssfsst_decode_states(const float* logp, const int64_t* offsets, int64_t cou
 // hssfsst_bilstm_set_weights (csrc/segmenter_train.hpp), and the scratch of its forward and backward calls.
 struct hssfsst_bilstm {
     int device = -1;
-    int F = 0, Fp = 0, H = 0;
+    int H = 0;
     bool packed = false;
-    DevBuf<float> d_wt, d_bias;                          // as hssfsst_segmenter::Layer's
-    DevBuf<hssfsst::seg_h8> d_whh;                       // forward stream: W_hh x wscale, split f16
+    SegLayer layer;                                      // the forward tables, of the weights set last
     DevBuf<hssfsst::seg_b8> d_bwd;                       // backward stream: W_hh, split bf16, as the B operand of dG . W_hh
     DevBuf<float> d_scale;                               // {wscale, inv_scale}: made and read on the device only
     DevBuf<float> d_pre;                                 // one chunk's input projection
     DevBuf<float> d_state;                               // forward [h, c][dir][Bp][Hp]; backward [dh_rec, dc][dir][Bp][Hp]
-    // hssfsst_bilstm_*_ragged: the list's layout and its device tables -- slot_off long long[slots], tile_base long long[tiles + 1],
-    // slot_len int[slots], slot_rec int[slots], tile_walk int[tiles] -- in one block, kept while the next call has the same offsets
-    hssfsst::seglayout::Layout lay;                      // (of tab's key: rebuilt between its begin and commit)
-    UploadedTable tab{"bilstm_ragged"};
+    SegListTables list{"bilstm_ragged"};                 // hssfsst_bilstm_*_ragged: kept while the next call has the same offsets
 };
 
 namespace {
@@ -2722,41 +2765,39 @@ int bilstm_check_shape(const char* what, int64_t batch, int64_t steps)
     return 0;
 }
 
-// The device tables of a ragged call's list, made and uploaded only when the offsets differ from the last call's (the owner
-// convention of hssfsst_segmenter::tab).  May throw std::bad_alloc.
-struct BilstmTables {
-    const long long *off, *base;
-    const int *len, *rec, *walk;
-    int slots;
-    long long walked;
-};
-int bilstm_ragged_tables(hssfsst_bilstm* p, const int64_t* offsets, int64_t count, hipStream_t st, BilstmTables* out)
+// out0, out1 (2, B, H) <- the state seg_seed_state made, after the launches chained through it; slot_rec as there
+int bilstm_state_out(const char* what, hipStream_t st, const hssfsst_bilstm* p, float* out0, float* out1, int B, int Bp, const int* slot_rec)
 {
-    namespace seglayout = hssfsst::seglayout;
-    const size_t tiles = static_cast<size_t>((count + seglayout::kSlotRows - 1) / seglayout::kSlotRows), slots = tiles * seglayout::kSlotRows;
-    const size_t o_base = slots * sizeof(long long), o_len = o_base + (tiles + 1) * sizeof(long long);
-    const size_t o_rec = o_len + slots * sizeof(int), o_walk = o_rec + slots * sizeof(int);
-    auto key = [&](size_t i) { return offsets[i]; };
-    if (!p->tab.same(static_cast<size_t>(count + 1), key)) {
-        unsigned char* h = nullptr;
-        if (int rc = p->tab.begin(o_walk + tiles * sizeof(int), &h)) return rc;
-        seglayout::build(offsets, count, p->lay);
-        const std::vector<long long> base = seglayout::tile_base(p->lay);
-        std::memcpy(h, p->lay.slot_off.data(), o_base);
-        std::memcpy(h + o_base, base.data(), (tiles + 1) * sizeof(long long));
-        std::memcpy(h + o_len, p->lay.slot_len.data(), slots * sizeof(int));
-        std::memcpy(h + o_rec, p->lay.slot_rec.data(), slots * sizeof(int));
-        std::memcpy(h + o_walk, p->lay.tile_walk.data(), tiles * sizeof(int));
-        if (int rc = p->tab.commit(st, static_cast<size_t>(count + 1), key)) return rc;
-    }
-    out->off = reinterpret_cast<const long long*>(p->tab.get());
-    out->base = reinterpret_cast<const long long*>(p->tab.get() + o_base);
-    out->len = reinterpret_cast<const int*>(p->tab.get() + o_len);
-    out->rec = reinterpret_cast<const int*>(p->tab.get() + o_rec);
-    out->walk = reinterpret_cast<const int*>(p->tab.get() + o_walk);
-    out->slots = static_cast<int>(slots);
-    out->walked = seglayout::stash_floats_ragged(p->lay) / (2 * seglayout::kStashStepFloats);
-    return 0;
+    const size_t nout = static_cast<size_t>(4) * (slot_rec ? Bp : B) * p->H;
+    hipLaunchKernelGGL((slot_rec ? hssfsst::seg_pair_out_kernel<true> : hssfsst::seg_pair_out_kernel<false>),
+                       dim3(static_cast<unsigned>((nout + 255) / 256)), dim3(256), 0, st, p->d_state.get(), out0, out1, B, p->H, Bp, slot_rec);
+    return launch_check(what, slot_rec ? "seg_pair_out_kernel<ragged>" : "seg_pair_out_kernel");
+}
+
+// A training forward: (h0, c0) in, the layer over the chunks with its stash, (hn, cn) out.  pa / ra: the call's geometry
+// (seg_dense_args, seg_ragged_args); B: the rows of the states; slot_rec as in seg_seed_state.
+template <bool RAGGED>
+int bilstm_forward(const char* what, hssfsst_bilstm* p, hipStream_t st, const float* x, const float* h0, const float* c0, float* y, float* hn,
+                   float* cn, float* stash, int B, const int* slot_rec, hssfsst::SegProjArgs pa, hssfsst::SegRecArgs ra,
+                   const std::vector<hssfsst::seglayout::Chunk>& chunks)
+{
+    if (int rc = p->d_pre.grow(hssfsst::seglayout::pre_floats(chunks, kSegTileStepBytes))) return rc;
+    if (int rc = seg_seed_state(what, st, p->d_state, h0, c0, B, p->H, ra.Bp, slot_rec)) return rc;
+    pa.x = x; pa.x_dtype = HSSFSST_DTYPE_F32; pa.relu = 0;
+    ra.pre = pa.pre = p->d_pre.get();
+    ra.state = p->d_state.get(); ra.y = y; ra.H = p->H;
+    ra.stash = stash; ra.inv_scale_dev = p->d_scale.get() + 1;
+    if (int rc = seg_forward_layer<RAGGED, true>(what, st, p->layer, pa, ra, chunks)) return rc;
+    return bilstm_state_out(what, st, p, hn, cn, B, ra.Bp, slot_rec);
+}
+
+// what both backwards give seg_bwd_rec_kernel; the state is seeded by then
+hssfsst::SegBwdArgs bilstm_bwd_args(const hssfsst_bilstm* p, const float* stash, const float* c0, const float* dy, float* dgates, int B, int Bp)
+{
+    hssfsst::SegBwdArgs a{};
+    a.stash = stash; a.c0 = c0; a.dy = dy; a.wbwd = p->d_bwd.get(); a.state = p->d_state.get(); a.dgates = dgates;
+    a.B = B; a.H = p->H; a.Bp = Bp;
+    return a;
 }
 
 }  // namespace
@@ -2776,12 +2817,14 @@ int hssfsst_bilstm_create(hssfsst_bilstm** out, int device, int input_size, int 
     DEVICE_SCOPE(device);
     std::unique_ptr<hssfsst_bilstm> p(new (std::nothrow) hssfsst_bilstm());
     if (!p) return fail(HSSFSST_ENOMEM, "bilstm_create: host allocation failed");
-    p->device = device; p->F = input_size; p->H = hidden;
-    p->Fp = (input_size + 31) / 32 * 32;
+    p->device = device; p->H = hidden;
+    SegLayer& L = p->layer;
+    L.F = input_size;
+    L.Fp = (input_size + 31) / 32 * 32;
     namespace sl = hssfsst::seglayout;
-    if (int rc = p->d_wt.grow(static_cast<size_t>(2) * p->Fp * sl::kGateCols)) return rc;
-    if (int rc = p->d_bias.grow(static_cast<size_t>(2) * sl::kGateCols)) return rc;
-    if (int rc = p->d_whh.grow(static_cast<size_t>(sl::kWtStreamHalves / 8))) return rc;
+    if (int rc = L.d_wt.grow(static_cast<size_t>(2) * L.Fp * sl::kGateCols)) return rc;
+    if (int rc = L.d_bias.grow(static_cast<size_t>(2) * sl::kGateCols)) return rc;
+    if (int rc = L.d_whh.grow(static_cast<size_t>(sl::kWtStreamHalves / 8))) return rc;
     if (int rc = p->d_bwd.grow(static_cast<size_t>(sl::kBwdStreamHalves / 8))) return rc;
     if (int rc = p->d_scale.grow(2)) return rc;
     *out = p.release();
@@ -2806,13 +2849,14 @@ int hssfsst_bilstm_set_weights(hssfsst_bilstm* p, const float* const* weights, v
     namespace sl = hssfsst::seglayout;
     hssfsst::SegPackArgs a{};
     for (int i = 0; i < 8; ++i) a.src[i] = weights[i];
-    a.F = p->F; a.Fp = p->Fp; a.H = p->H;
-    a.scale = p->d_scale.get(); a.wt = p->d_wt.get(); a.bias = p->d_bias.get();
-    a.whh = reinterpret_cast<_Float16*>(p->d_whh.get());
+    const SegLayer& L = p->layer;
+    a.F = L.F; a.Fp = L.Fp; a.H = p->H;
+    a.scale = p->d_scale.get(); a.wt = L.d_wt.get(); a.bias = L.d_bias.get();
+    a.whh = reinterpret_cast<_Float16*>(L.d_whh.get());
     a.bwd = reinterpret_cast<__bf16*>(p->d_bwd.get());
     hipLaunchKernelGGL(hssfsst::seg_pack_scale_kernel, dim3(1), dim3(1024), 0, st, a);
     if (int rc = launch_check("bilstm_set_weights", "seg_pack_scale_kernel")) return rc;
-    const long long most = std::max<long long>(static_cast<long long>(2) * p->Fp * sl::kGateCols, std::max(sl::kWtStreamHalves, sl::kBwdStreamHalves));
+    const long long most = std::max<long long>(static_cast<long long>(2) * L.Fp * sl::kGateCols, std::max(sl::kWtStreamHalves, sl::kBwdStreamHalves));
     hipLaunchKernelGGL(hssfsst::seg_pack_kernel, dim3(static_cast<unsigned>((most + 255) / 256)), dim3(256), 0, st, a);
     if (int rc = launch_check("bilstm_set_weights", "seg_pack_kernel")) return rc;
     p->packed = true;
@@ -2840,7 +2884,7 @@ int hssfsst_bilstm_forward(hssfsst_bilstm* p, const float* x, int64_t batch, int
     if (!p->packed) return fail(HSSFSST_EINVAL, "bilstm_forward: no weights yet (call hssfsst_bilstm_set_weights first)");
     DEVICE_SCOPE(p->device);
     const hipStream_t st = static_cast<hipStream_t>(stream);
-    const int B = static_cast<int>(batch), T = static_cast<int>(steps), H = p->H;
+    const int B = static_cast<int>(batch), T = static_cast<int>(steps);
     const int nbt = (B + hssfsst::kSegRows - 1) / hssfsst::kSegRows, Bp = nbt * hssfsst::kSegRows;
     std::vector<hssfsst::seglayout::Chunk> chunks;
     try {
@@ -2848,36 +2892,10 @@ int hssfsst_bilstm_forward(hssfsst_bilstm* p, const float* x, int64_t batch, int
     } catch (const std::bad_alloc&) {
         return fail(HSSFSST_ENOMEM, "bilstm_forward: out of host memory");
     }
-    int rc;
-    const size_t nstate = static_cast<size_t>(4) * Bp * hssfsst::kSegHp;
-    if ((rc = p->d_pre.grow(hssfsst::seglayout::pre_floats(chunks, kSegTileStepBytes))) != 0) return rc;
-    if ((rc = p->d_state.grow(nstate)) != 0) return rc;
-    hipLaunchKernelGGL(hssfsst::seg_state_init_kernel<false>, dim3(static_cast<unsigned>((nstate + 255) / 256)), dim3(256), 0, st, h0, c0,
-                       p->d_state.get(), B, H, Bp, static_cast<const int*>(nullptr));
-    if ((rc = launch_check("bilstm_forward", "seg_state_init_kernel")) != 0) return rc;
     hssfsst::SegProjArgs pa{};
-    pa.x = x; pa.x_dtype = HSSFSST_DTYPE_F32; pa.relu = 0;
-    pa.B = B; pa.T = T; pa.F = p->F; pa.Fp = p->Fp;
-    pa.wt = p->d_wt.get(); pa.bias = p->d_bias.get(); pa.pre = p->d_pre.get();
     hssfsst::SegRecArgs ra{};
-    ra.B = B; ra.T = T; ra.H = H; ra.Bp = Bp;
-    ra.pre = p->d_pre.get(); ra.whh = p->d_whh.get(); ra.state = p->d_state.get(); ra.y = y;
-    ra.stash = stash; ra.inv_scale_dev = p->d_scale.get() + 1;
-    for (const hssfsst::seglayout::Chunk& c : chunks) {
-        pa.n = ra.n = c.n;
-        pa.Tc = ra.Tc = c.Tc;
-        pa.t0[0] = ra.t0[0] = c.s0;
-        pa.t0[1] = ra.t0[1] = T - c.s0 - c.n;
-        hipLaunchKernelGGL(hssfsst::seg_proj_kernel<false>, dim3(4 * hssfsst::kSegHp / 64, static_cast<unsigned>(c.tiles * ((c.n + 7) / 8)), 2),
-                           dim3(256), 0, st, pa);
-        if ((rc = launch_check("bilstm_forward", "seg_proj_kernel")) != 0) return rc;
-        hipLaunchKernelGGL((hssfsst::seg_rec_kernel<false, true>), dim3(static_cast<unsigned>(c.tiles), 2), dim3(64 * hssfsst::kSegWaves), 0, st, ra);
-        if ((rc = launch_check("bilstm_forward", "seg_rec_kernel<train>")) != 0) return rc;
-    }
-    const size_t nout = static_cast<size_t>(4) * B * H;
-    hipLaunchKernelGGL(hssfsst::seg_pair_out_kernel<false>, dim3(static_cast<unsigned>((nout + 255) / 256)), dim3(256), 0, st, p->d_state.get(), hn, cn,
-                       B, H, Bp, static_cast<const int*>(nullptr));
-    return launch_check("bilstm_forward", "seg_pair_out_kernel");
+    seg_dense_args(B, T, Bp, &pa, &ra);
+    return bilstm_forward<false>("bilstm_forward", p, st, x, h0, c0, y, hn, cn, stash, B, nullptr, pa, ra, chunks);
 }
 
 int hssfsst_bilstm_backward(hssfsst_bilstm* p, const float* stash, const float* c0, const float* dy, const float* dhn, const float* dcn,
@@ -2891,28 +2909,19 @@ int hssfsst_bilstm_backward(hssfsst_bilstm* p, const float* stash, const float* 
     if (!p->packed) return fail(HSSFSST_EINVAL, "bilstm_backward: no weights yet (call hssfsst_bilstm_set_weights first)");
     DEVICE_SCOPE(p->device);
     const hipStream_t st = static_cast<hipStream_t>(stream);
-    const int B = static_cast<int>(batch), T = static_cast<int>(steps), H = p->H;
+    const int B = static_cast<int>(batch), T = static_cast<int>(steps);
     const int nbt = (B + hssfsst::kSegRows - 1) / hssfsst::kSegRows, Bp = nbt * hssfsst::kSegRows;
-    int rc;
-    const size_t nstate = static_cast<size_t>(4) * Bp * hssfsst::kSegHp;
-    if ((rc = p->d_state.grow(nstate)) != 0) return rc;
-    hipLaunchKernelGGL(hssfsst::seg_pair_init_kernel<false>, dim3(static_cast<unsigned>((nstate + 255) / 256)), dim3(256), 0, st, dhn, dcn,
-                       p->d_state.get(), B, H, Bp, static_cast<const int*>(nullptr));
-    if ((rc = launch_check("bilstm_backward", "seg_pair_init_kernel")) != 0) return rc;
-    hssfsst::SegBwdArgs a{};
-    a.stash = stash; a.c0 = c0; a.dy = dy; a.wbwd = p->d_bwd.get(); a.state = p->d_state.get(); a.dgates = dgates;
-    a.B = B; a.T = T; a.H = H; a.Bp = Bp;
+    if (int rc = seg_seed_state("bilstm_backward", st, p->d_state, dhn, dcn, B, p->H, Bp, nullptr)) return rc;
+    hssfsst::SegBwdArgs a = bilstm_bwd_args(p, stash, c0, dy, dgates, B, Bp);
+    a.T = T;
     // at most kSegMaxChunk steps per launch, chained through the carried (dh_rec, dc)
     for (int s0 = 0; s0 < T; s0 += hssfsst::seglayout::kSegMaxChunk) {
         a.s0 = s0;
         a.n = std::min(hssfsst::seglayout::kSegMaxChunk, T - s0);
         hipLaunchKernelGGL(hssfsst::seg_bwd_rec_kernel<false>, dim3(static_cast<unsigned>(nbt), 2), dim3(64 * hssfsst::kSegWaves), 0, st, a);
-        if ((rc = launch_check("bilstm_backward", "seg_bwd_rec_kernel")) != 0) return rc;
+        if (int rc = launch_check("bilstm_backward", "seg_bwd_rec_kernel")) return rc;
     }
-    const size_t nout = static_cast<size_t>(4) * B * H;
-    hipLaunchKernelGGL(hssfsst::seg_pair_out_kernel<false>, dim3(static_cast<unsigned>((nout + 255) / 256)), dim3(256), 0, st, p->d_state.get(), dh0, dc0,
-                       B, H, Bp, static_cast<const int*>(nullptr));
-    return launch_check("bilstm_backward", "seg_pair_out_kernel");
+    return bilstm_state_out("bilstm_backward", st, p, dh0, dc0, B, Bp, nullptr);
 }
 
 int hssfsst_bilstm_stash_floats_ragged(const hssfsst_bilstm* p, const int64_t* offsets, int64_t count, int64_t* floats)
@@ -2948,46 +2957,18 @@ int hssfsst_bilstm_forward_ragged(hssfsst_bilstm* p, const float* x, const int64
     if (!p->packed) return fail(HSSFSST_EINVAL, "bilstm_forward_ragged: no weights yet (call hssfsst_bilstm_set_weights first)");
     DEVICE_SCOPE(p->device);
     const hipStream_t st = static_cast<hipStream_t>(stream);
-    BilstmTables t{};
+    SegListTables::Views t{};
     std::vector<seglayout::Chunk> chunks;
-    int rc;
     try {
-        if ((rc = bilstm_ragged_tables(p, offsets, count, st, &t)) != 0) return rc;
-        chunks = seglayout::ragged_chunks(p->lay, kSegTileStepBytes, seglayout::kSegPreBytes);
+        if (int rc = p->list.acquire(offsets, count, st, &t)) return rc;
+        chunks = seglayout::ragged_chunks(p->list.lay, kSegTileStepBytes, seglayout::kSegPreBytes);
     } catch (const std::bad_alloc&) {
         return fail(HSSFSST_ENOMEM, "bilstm_forward_ragged: out of host memory");
     }
-    const int H = p->H, B = static_cast<int>(count);
-    const size_t nstate = static_cast<size_t>(4) * t.slots * hssfsst::kSegHp;
-    if ((rc = p->d_pre.grow(seglayout::pre_floats(chunks, kSegTileStepBytes))) != 0) return rc;
-    if ((rc = p->d_state.grow(nstate)) != 0) return rc;
-    hipLaunchKernelGGL(hssfsst::seg_state_init_kernel<true>, dim3(static_cast<unsigned>((nstate + 255) / 256)), dim3(256), 0, st, h0, c0,
-                       p->d_state.get(), B, H, t.slots, t.rec);
-    if ((rc = launch_check("bilstm_forward_ragged", "seg_state_init_kernel<ragged>")) != 0) return rc;
     hssfsst::SegProjArgs pa{};
-    pa.x = x; pa.x_dtype = HSSFSST_DTYPE_F32; pa.relu = 0;
-    pa.F = p->F; pa.Fp = p->Fp;
-    pa.wt = p->d_wt.get(); pa.bias = p->d_bias.get(); pa.pre = p->d_pre.get();
-    pa.slot_off = t.off; pa.slot_len = t.len; pa.tile_walk = t.walk;
     hssfsst::SegRecArgs ra{};
-    ra.H = H; ra.Bp = t.slots;
-    ra.pre = p->d_pre.get(); ra.whh = p->d_whh.get(); ra.state = p->d_state.get(); ra.y = y;
-    ra.stash = stash; ra.inv_scale_dev = p->d_scale.get() + 1;
-    ra.slot_off = t.off; ra.slot_len = t.len; ra.tile_walk = t.walk; ra.tile_base = t.base; ra.walked = t.walked;
-    for (const seglayout::Chunk& c : chunks) {
-        pa.n = ra.n = c.n;
-        pa.Tc = ra.Tc = c.Tc;
-        pa.s0 = ra.s0 = c.s0;
-        hipLaunchKernelGGL(hssfsst::seg_proj_kernel<true>, dim3(4 * hssfsst::kSegHp / 64, static_cast<unsigned>(c.tiles * ((c.n + 7) / 8)), 2),
-                           dim3(256), 0, st, pa);
-        if ((rc = launch_check("bilstm_forward_ragged", "seg_proj_kernel<ragged>")) != 0) return rc;
-        hipLaunchKernelGGL((hssfsst::seg_rec_kernel<true, true>), dim3(static_cast<unsigned>(c.tiles), 2), dim3(64 * hssfsst::kSegWaves), 0, st, ra);
-        if ((rc = launch_check("bilstm_forward_ragged", "seg_rec_kernel<ragged, train>")) != 0) return rc;
-    }
-    const size_t nout = static_cast<size_t>(4) * t.slots * H;
-    hipLaunchKernelGGL(hssfsst::seg_pair_out_kernel<true>, dim3(static_cast<unsigned>((nout + 255) / 256)), dim3(256), 0, st, p->d_state.get(), hn, cn,
-                       B, H, t.slots, t.rec);
-    return launch_check("bilstm_forward_ragged", "seg_pair_out_kernel<ragged>");
+    seg_ragged_args(t, &pa, &ra);
+    return bilstm_forward<true>("bilstm_forward_ragged", p, st, x, h0, c0, y, hn, cn, stash, static_cast<int>(count), t.rec, pa, ra, chunks);
 }
 
 int hssfsst_bilstm_backward_ragged(hssfsst_bilstm* p, const float* stash, const float* c0, const float* dy, const float* dhn, const float* dcn,
@@ -3004,37 +2985,27 @@ int hssfsst_bilstm_backward_ragged(hssfsst_bilstm* p, const float* stash, const 
     if (!p->packed) return fail(HSSFSST_EINVAL, "bilstm_backward_ragged: no weights yet (call hssfsst_bilstm_set_weights first)");
     DEVICE_SCOPE(p->device);
     const hipStream_t st = static_cast<hipStream_t>(stream);
-    BilstmTables t{};
+    SegListTables::Views t{};
     std::vector<seglayout::BwdChunk> chunks;
-    int rc;
     try {
-        if ((rc = bilstm_ragged_tables(p, offsets, count, st, &t)) != 0) return rc;
-        chunks = seglayout::ragged_bwd_chunks(p->lay);
+        if (int rc = p->list.acquire(offsets, count, st, &t)) return rc;
+        chunks = seglayout::ragged_bwd_chunks(p->list.lay);
     } catch (const std::bad_alloc&) {
         return fail(HSSFSST_ENOMEM, "bilstm_backward_ragged: out of host memory");
     }
-    const int H = p->H, B = static_cast<int>(count);
-    const size_t nstate = static_cast<size_t>(4) * t.slots * hssfsst::kSegHp;
-    if ((rc = p->d_state.grow(nstate)) != 0) return rc;
-    hipLaunchKernelGGL(hssfsst::seg_pair_init_kernel<true>, dim3(static_cast<unsigned>((nstate + 255) / 256)), dim3(256), 0, st, dhn, dcn,
-                       p->d_state.get(), B, H, t.slots, t.rec);
-    if ((rc = launch_check("bilstm_backward_ragged", "seg_pair_init_kernel<ragged>")) != 0) return rc;
-    hssfsst::SegBwdArgs a{};
-    a.stash = stash; a.c0 = c0; a.dy = dy; a.wbwd = p->d_bwd.get(); a.state = p->d_state.get(); a.dgates = dgates;
-    a.B = B; a.H = H; a.Bp = t.slots;
+    const int B = static_cast<int>(count);
+    if (int rc = seg_seed_state("bilstm_backward_ragged", st, p->d_state, dhn, dcn, B, p->H, t.slots, t.rec)) return rc;
+    hssfsst::SegBwdArgs a = bilstm_bwd_args(p, stash, c0, dy, dgates, B, t.slots);
     a.slot_off = t.off; a.slot_len = t.len; a.slot_rec = t.rec; a.tile_walk = t.walk; a.tile_base = t.base;
-    a.walked = t.walked; a.total = p->lay.total;
+    a.walked = t.walked; a.total = p->list.lay.total;
     // highest steps first, at most kSegMaxChunk per launch, chained through the carried (dh_rec, dc); a tile joins at its last step
     for (const seglayout::BwdChunk& c : chunks) {
         a.s0 = c.s0;
         a.n = c.n;
         hipLaunchKernelGGL(hssfsst::seg_bwd_rec_kernel<true>, dim3(static_cast<unsigned>(c.tiles), 2), dim3(64 * hssfsst::kSegWaves), 0, st, a);
-        if ((rc = launch_check("bilstm_backward_ragged", "seg_bwd_rec_kernel<ragged>")) != 0) return rc;
+        if (int rc = launch_check("bilstm_backward_ragged", "seg_bwd_rec_kernel<ragged>")) return rc;
     }
-    const size_t nout = static_cast<size_t>(4) * t.slots * H;
-    hipLaunchKernelGGL(hssfsst::seg_pair_out_kernel<true>, dim3(static_cast<unsigned>((nout + 255) / 256)), dim3(256), 0, st, p->d_state.get(), dh0, dc0,
-                       B, H, t.slots, t.rec);
-    return launch_check("bilstm_backward_ragged", "seg_pair_out_kernel<ragged>");
+    return bilstm_state_out("bilstm_backward_ragged", st, p, dh0, dc0, B, t.slots, t.rec);
 }
 
 }  // extern "C"

@@ -195,6 +195,24 @@ inline long long stash_floats_ragged(const Layout& l)
     for (int w : l.tile_walk) walked += w;
     return 2 * walked * kStashStepFloats;
 }
+
+// The device tables of a list, in one block: slot_off long long[slots] | tile_base long long[tiles + 1] | slot_len int[slots] |
+// slot_rec int[slots] | tile_walk int[tiles].  Byte offsets of the five arrays and the size of the block; they follow from count
+// alone.  The 8-byte arrays come first, so every array is aligned to its element in a block that is.
+struct TableBlock { size_t tiles, slots, o_off, o_base, o_len, o_rec, o_walk, bytes; };
+inline TableBlock table_block(int64_t count)
+{
+    TableBlock b{};
+    b.tiles = static_cast<size_t>((count + kSlotRows - 1) / kSlotRows);
+    b.slots = b.tiles * kSlotRows;
+    b.o_off = 0;
+    b.o_base = b.o_off + b.slots * sizeof(long long);
+    b.o_len = b.o_base + (b.tiles + 1) * sizeof(long long);
+    b.o_rec = b.o_len + b.slots * sizeof(int);
+    b.o_walk = b.o_rec + b.slots * sizeof(int);
+    b.bytes = b.o_walk + b.tiles * sizeof(int);
+    return b;
+}
 // walked: tile_base[tiles]; base: tile_base[tile]; s < the tile's walk
 HSSFSST_SEG_HD inline long long stash_index_ragged(long long walked, long long base, int dir, long long s, int w, int tl, int q, int lane, int r)
 {

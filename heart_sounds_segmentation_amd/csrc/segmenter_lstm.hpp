@@ -146,11 +146,12 @@ __global__ __launch_bounds__(256) void seg_proj_kernel(SegProjArgs a)
     }
 }
 
-// state[0 = h, 1 = c][dir][padded batch][Hp] <- h0, c0 (2, B, H); the padding is zero.  RAGGED: row b is a slot and takes the state
-// of its recording slot_rec[b] (none: a padding slot, zero); B is the rows of h0 / c0, 1 = the same state for every recording.
+// state[0][dir][padded batch][Hp] <- p0, state[1] <- p1, both (2, B, H), either NULL for zero; the padding is zero.  The forwards
+// seed (h, c) with it, the backwards (dh_rec, dc).  RAGGED: row b is a slot and takes the row of its recording slot_rec[b] (none:
+// a padding slot, zero); B is the rows of p0 / p1, 1 = the same row for every recording.
 template <bool RAGGED>
-__global__ __launch_bounds__(256) void seg_state_init_kernel(const float* h0, const float* c0, float* state, int B, int H, int Bp,
-                                                             const int* slot_rec)
+__global__ __launch_bounds__(256) void seg_pair_init_kernel(const float* p0, const float* p1, float* state, int B, int H, int Bp,
+                                                            const int* slot_rec)
 {
     const size_t per = static_cast<size_t>(2) * Bp * kSegHp;
     const size_t i = static_cast<size_t>(blockIdx.x) * 256 + threadIdx.x;
@@ -160,14 +161,13 @@ __global__ __launch_bounds__(256) void seg_state_init_kernel(const float* h0, co
     const int u = static_cast<int>(r % kSegHp);
     const int b = static_cast<int>((r / kSegHp) % Bp);
     const int dir = static_cast<int>(r / (static_cast<size_t>(kSegHp) * Bp));
-    float v = 0.0f;
+    const float* src = which ? p1 : p0;
+    int row = b;
     if constexpr (RAGGED) {
-        const int rec = slot_rec[b];
-        if (rec >= 0 && u < H) v = (which ? c0 : h0)[(static_cast<size_t>(dir) * B + (B == 1 ? 0 : rec)) * H + u];
-    } else {
-        if (b < B && u < H) v = (which ? c0 : h0)[(static_cast<size_t>(dir) * B + b) * H + u];
+        row = slot_rec[b];
+        if (B == 1 && row > 0) row = 0;
     }
-    state[i] = v;
+    state[i] = src != nullptr && row >= 0 && row < B && u < H ? src[(static_cast<size_t>(dir) * B + row) * H + u] : 0.0f;
 }
 
 struct SegRecArgs {

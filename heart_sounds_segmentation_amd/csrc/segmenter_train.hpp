@@ -3,7 +3,7 @@
 //
 //   seg_pack_scale_kernel   max|W_hh| of both directions -> {wscale, inv_scale} in device memory (seg_upload_layer's arithmetic);
 //   seg_pack_kernel         one layer's eight nn.LSTM tensors (device pointers) -> wt, bias and the split-f16 W_hh stream of the
-//                           forward kernels, element for element what seg_upload_layer makes on the host, plus the bf16 hi + lo
+//                           forward kernels, through the index functions seg_upload_layer walks on the host, plus the bf16 hi + lo
 //                           stream of W_hh as the B operand of the backward product (seglayout::bwd_stream_source);
 //   seg_rec_kernel<., true>   (segmenter_lstm.hpp) the forward recurrence, which also stores i, f, g, o, c of every step;
 //   seg_bwd_rec_kernel      the backward recurrence: one workgroup per (direction, 16 batch rows), 8 waves, walks the steps against
@@ -103,28 +103,8 @@ __global__ __launch_bounds__(256) void seg_pack_kernel(SegPackArgs a)
     }
 }
 
-// state[0][dir][Bp][Hp] <- p0, state[1] <- p1, both (2, B, H), either NULL for zero; the padding is zero.  RAGGED: row b is a slot
-// and takes the row of its recording slot_rec[b] (none: a padding slot, zero).
-template <bool RAGGED>
-__global__ __launch_bounds__(256) void seg_pair_init_kernel(const float* p0, const float* p1, float* state, int B, int H, int Bp,
-                                                            const int* slot_rec)
-{
-    const size_t per = static_cast<size_t>(2) * Bp * kSegHp;
-    const size_t i = static_cast<size_t>(blockIdx.x) * 256 + threadIdx.x;
-    if (i >= 2 * per) return;
-    const int which = static_cast<int>(i / per);
-    const size_t r = i - which * per;
-    const int u = static_cast<int>(r % kSegHp);
-    const int b = static_cast<int>((r / kSegHp) % Bp);
-    const int dir = static_cast<int>(r / (static_cast<size_t>(kSegHp) * Bp));
-    const float* src = which ? p1 : p0;
-    int row = b;
-    if constexpr (RAGGED) row = slot_rec[b];
-    state[i] = src != nullptr && row >= 0 && row < B && u < H ? src[(static_cast<size_t>(dir) * B + row) * H + u] : 0.0f;
-}
-
-// out0, out1 (2, B, H) <- state[0], state[1].  RAGGED: one thread per (slot, unit); slot b's state goes to row slot_rec[b] of the
-// outputs, which are in list order.
+// out0, out1 (2, B, H) <- state[0], state[1]: what seg_pair_init_kernel (segmenter_lstm.hpp) seeded, after the launches chained
+// through it.  RAGGED: one thread per (slot, unit); slot b's state goes to row slot_rec[b] of the outputs, which are in list order.
 template <bool RAGGED>
 __global__ __launch_bounds__(256) void seg_pair_out_kernel(const float* state, float* out0, float* out1, int B, int H, int Bp,
                                                            const int* slot_rec)

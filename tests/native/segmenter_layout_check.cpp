@@ -118,6 +118,36 @@ static void run_ragged(const char* name, const std::vector<int>& lens, size_t ti
     std::printf("%-24s %zu launches per layer\n", name, chunks.size());
 }
 
+// the block of a list's device tables: five arrays in the stated order, back to back, each aligned to its element, and the byte
+// offsets as they stood inline in the ragged BiLSTM's table builder before table_block() was a function
+static void run_table_block(int64_t count)
+{
+    char name[64];
+    std::snprintf(name, sizeof(name), "table block count=%lld", static_cast<long long>(count));
+    const sl::TableBlock b = sl::table_block(count);
+    const size_t tiles = static_cast<size_t>((count + sl::kSlotRows - 1) / sl::kSlotRows), slots = tiles * sl::kSlotRows;
+    const size_t o_base = slots * sizeof(long long), o_len = o_base + (tiles + 1) * sizeof(long long);
+    const size_t o_rec = o_len + slots * sizeof(int), o_walk = o_rec + slots * sizeof(int);
+    CHECK(b.tiles == tiles && b.slots == slots, "%zu tiles, %zu slots", b.tiles, b.slots);
+    CHECK(b.o_off == 0 && b.o_base == o_base && b.o_len == o_len && b.o_rec == o_rec && b.o_walk == o_walk,
+          "offsets {%zu, %zu, %zu, %zu, %zu}, the inline arithmetic made {0, %zu, %zu, %zu, %zu}", b.o_off, b.o_base, b.o_len, b.o_rec, b.o_walk,
+          o_base, o_len, o_rec, o_walk);
+    CHECK(b.bytes == o_walk + tiles * sizeof(int), "%zu bytes, the inline arithmetic made %zu", b.bytes, o_walk + tiles * sizeof(int));
+    // slot_off | tile_base | slot_len | slot_rec | tile_walk: each starts where the one before ends
+    const size_t start[5] = {b.o_off, b.o_base, b.o_len, b.o_rec, b.o_walk};
+    const size_t size[5] = {slots * sizeof(long long), (tiles + 1) * sizeof(long long), slots * sizeof(int), slots * sizeof(int), tiles * sizeof(int)};
+    const size_t align[5] = {8, 8, 4, 4, 4};
+    size_t end = 0, sum = 0;
+    for (int i = 0; i < 5; ++i) {
+        CHECK(start[i] == end, "array %d starts at byte %zu, the one before ends at %zu", i, start[i], end);
+        CHECK(start[i] % align[i] == 0, "array %d at byte %zu is not %zu-byte aligned", i, start[i], align[i]);
+        end = start[i] + size[i];
+        sum += size[i];
+    }
+    CHECK(b.bytes == end && b.bytes == sum, "%zu bytes, the arrays end at %zu and sum to %zu", b.bytes, end, sum);
+    std::printf("%-24s %zu bytes\n", name, b.bytes);
+}
+
 int main()
 {
     run_case("one", {1});
@@ -150,6 +180,8 @@ int main()
     run_ragged("ragged random1k", many, tile_step, sl::kSegPreBytes);
     run_ragged("ragged random1k small", many, 1024, sl::kSegPreBytes);
     run_ragged("ragged one", {1}, tile_step, size_t(1) << 16);       // the bound below one step of one tile: Tc = 1
+
+    for (int64_t count : {1, 16, 17, 33, 1000}) run_table_block(count);
 
     // what the entry point refuses, and at which index
     const char* name = "bad";

@@ -1,6 +1,7 @@
 // Stand-alone check of the trainable BiLSTM layer's index arithmetic (csrc/segmenter_layout.hpp: host only, no HIP), built with
 // -fsanitize=address,undefined by tests/test_segmenter_train.py.  The stash and the backward weight stream are in bounds and
-// one-to-one; the forward tables' index functions equal the loops of seg_upload_layer (csrc/hssfsst.hip), restated here.
+// one-to-one; the forward tables' index functions, which seg_upload_layer (csrc/hssfsst.hip) and seg_pack_kernel both walk, equal
+// the nested loops that seg_upload_layer was before it called them, kept here as the independent statement of the layout.
 // Any failed property or sanitizer report ends the run non-zero.
 #include "segmenter_layout.hpp"
 
@@ -74,7 +75,8 @@ static void check_bwd_stream(int H)
     for (size_t s = 0; s < used.size(); ++s) CHECK(used[s] == 2, "W_hh[%zu] is streamed %d times, not as one hi and one lo", s, used[s]);
 }
 
-// seg_upload_layer's loops, writing source indices instead of values (-1: the zero the tables start with)
+// the layout as nested loops over (unit tile, gate, unit) and (wave, K block, tile x gate, lane, j), writing source indices instead
+// of values (-1: the zero the tables start with)
 static void check_forward_tables(int H, int F)
 {
     constexpr int Hp = sl::kHp, N = 4 * Hp, kWaves = 8, kKb = Hp / 32;

@@ -137,7 +137,7 @@ def test_layout_functions_under_sanitizers(tmp_path):
     """csrc/segmenter_layout.hpp alone, in a program of its own (tests/native/segmenter_train_layout_check.cpp) built with
     -fsanitize=address,undefined: for H in {1, 5, 16, 240, 256} the stash and backward-stream index functions are in bounds and
     one-to-one, every W_hh element is streamed as exactly one hi and one lo, and the forward tables' index functions equal the
-    loops of seg_upload_layer."""
+    layout restated there as nested loops."""
     cxx = shutil.which("g++")
     if cxx is None:
         pytest.skip("no g++")

@@ -466,6 +466,54 @@ def test_dropout_and_training():
 
 
 @pytest.mark.gpu
+def test_null_seeds_are_zero_seeds():
+    """dhn = dcn = NULL is dhn = dcn = 0, bit for bit in dgates, dh0 and dc0, through the raw ABI of both backwards.  17 recordings
+    of 1..3 steps (dense: B 17, T 3) at H 5, F 3: two tiles, the second with 15 padding slots, and 251 padded units -- the smallest
+    shape at which the state-init kernel meets a NULL source, a padding slot and a padded unit."""
+    L, H, F, B, T = _lib.lib(), 5, 3, 17, 3
+    torch.manual_seed(5)
+    layer = HipBiLSTM(F, H).cuda()
+    plan = raw_plan(layer, torch.device("cuda", torch.cuda.current_device()))
+    g = torch.Generator().manual_seed(6)
+    lens = [1 + i % 3 for i in range(B)]
+    offs, n = offsets_of(lens), ctypes.c_int64()
+    h0, c0 = torch.randn(2, B, H, generator=g).cuda(), torch.randn(2, B, H, generator=g).cuda()
+    zeros = torch.zeros(2, B, H).cuda()
+
+    def backwards(stash, dy, dg_shape, call):
+        out = []
+        for seed in (None, zeros.data_ptr()):
+            dg, dh0, dc0 = (torch.full(shape, float("nan")).cuda() for shape in (dg_shape, (2, B, H), (2, B, H)))
+            _lib.check(call(stash.data_ptr(), c0.data_ptr(), dy.data_ptr(), seed, seed, dg.data_ptr(), dh0.data_ptr(), dc0.data_ptr()), "backward")
+            torch.cuda.synchronize()
+            out.append((dg, dh0, dc0))
+        for a, b, what in zip(out[0], out[1], ("dgates", "dh0", "dc0")):
+            assert torch.isfinite(a).all() and torch.equal(a, b), what
+        return out[0]
+
+    # ragged
+    total, o = offs[-1], i64(offs)
+    x, dy = torch.randn(total, F, generator=g).cuda(), torch.randn(total, 2 * H, generator=g).cuda()
+    assert L.hssfsst_bilstm_stash_floats_ragged(plan, o, B, ctypes.byref(n)) == 0
+    stash, y = torch.zeros(n.value).cuda(), torch.empty(total, 2 * H).cuda()
+    hn, cn = torch.empty(2, B, H).cuda(), torch.empty(2, B, H).cuda()
+    _lib.check(L.hssfsst_bilstm_forward_ragged(plan, x.data_ptr(), o, B, h0.data_ptr(), c0.data_ptr(), y.data_ptr(), hn.data_ptr(),
+                                               cn.data_ptr(), stash.data_ptr(), None), "forward_ragged")
+    dg, _, _ = backwards(stash, dy, (2, total, 4 * H),
+                         lambda s, c, d, dh, dc, g_, a, b: L.hssfsst_bilstm_backward_ragged(plan, s, c, d, dh, dc, o, B, g_, a, b, None))
+    assert dg.abs().max() > 0
+    # dense
+    x, dy = torch.randn(B, T, F, generator=g).cuda(), torch.randn(B, T, 2 * H, generator=g).cuda()
+    assert L.hssfsst_bilstm_stash_floats(plan, B, T, ctypes.byref(n)) == 0
+    stash, y = torch.zeros(n.value).cuda(), torch.empty(B, T, 2 * H).cuda()
+    _lib.check(L.hssfsst_bilstm_forward(plan, x.data_ptr(), B, T, h0.data_ptr(), c0.data_ptr(), y.data_ptr(), hn.data_ptr(), cn.data_ptr(),
+                                        stash.data_ptr(), None), "forward")
+    dg, _, _ = backwards(stash, dy, (2, B, T, 4 * H),
+                         lambda s, c, d, dh, dc, g_, a, b: L.hssfsst_bilstm_backward(plan, s, c, d, dh, dc, B, T, g_, a, b, None))
+    assert dg.abs().max() > 0
+
+
+@pytest.mark.gpu
 def test_determinism_and_contract(mixed):
     m, B = mixed, len(LENS)
     order = list(range(B))
