@@ -295,6 +295,11 @@ def lib():
         L.hssfsst_decode_states.argtypes = [vp, ctypes.POINTER(c_i64), c_i64, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
                                             vp, vp, c_int, vp]
         L.hssfsst_decode_states.restype = c_int
+        fp = ctypes.POINTER(ctypes.c_float)
+        L.hssfsst_decode_durations_info.argtypes = [ip, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]
+        L.hssfsst_decode_durations_info.restype = c_int
+        L.hssfsst_decode_durations.argtypes = [vp, ctypes.POINTER(c_i64), c_i64, fp, fp, fp, fp, c_int, vp, vp, vp, c_i64, c_int, vp]
+        L.hssfsst_decode_durations.restype = c_int
         L.hssfsst_bilstm_create.argtypes = [ctypes.POINTER(vp), c_int, c_int, c_int]
         L.hssfsst_bilstm_create.restype = c_int
         L.hssfsst_bilstm_destroy.argtypes = [vp]

@@ -22,6 +22,9 @@ have a ``ragged`` form that trains on whole recordings of different lengths in o
 ``decode_states`` turns log-probs into state sequences: Viterbi decoding under a transition constraint (by default the cardiac
 cycle: stay or advance), one HIP call for a whole list of recordings (hssfsst_decode_states; csrc/segmenter_decode.hpp), with
 ``cyclic_transitions`` / ``transitions_from_labels`` for the transitions and ``state_runs`` for the boundaries.
+``decode_durations`` is the same with a score for how long each run lasts (explicit-duration, semi-Markov Viterbi:
+hssfsst_decode_durations; csrc/segmenter_decode_durations.hpp), with ``gaussian_durations`` / ``durations_from_labels`` /
+``edge_durations`` for its tables.
 """
 from __future__ import annotations
 
@@ -573,17 +576,20 @@ def segment(fsst, head, windows: torch.Tensor) -> torch.Tensor:
     return head(fsst.batch(windows))
 
 
-def segment_recordings(fsst, seg: HipSegmenter, recordings, decode=None, **kw) -> RaggedFeatures:
+def segment_recordings(fsst, seg: HipSegmenter, recordings, decode=None, durations=None, **kw) -> RaggedFeatures:
     """Whole recordings of different lengths (a list of 1-D signals on the GPU) -> ``FSST.ragged`` features, kept on the device
     -> a ``RaggedFeatures`` of ``(T_i, 4)`` log-probs: ``segment()`` for whole recordings.  ``kw`` goes to
     ``HipSegmenter.ragged`` (h0, c0, max_steps).  ``decode=True`` or ``decode=(A, pi)``: the log-probs go on to ``decode_states``
-    (default or given transitions) and the ``RaggedStates`` of ``(T_i,)`` uint8 state sequences is returned instead."""
+    (default or given transitions) and the ``RaggedStates`` of ``(T_i,)`` uint8 state sequences is returned instead; with
+    ``durations=dur`` (4, D) they go to ``decode_durations`` under that table, its default ``edge`` and the same transitions."""
+    if durations is not None and (decode is None or decode is False):
+        raise ValueError("segment_recordings: durations are for decoding: pass decode=True or decode=(A, pi) with them")
     logp = seg.ragged(fsst.ragged(recordings), **kw)
     if decode is None or decode is False:
         return logp
-    if decode is True:
-        return decode_states(logp)
-    A, pi = decode
+    A, pi = (None, None) if decode is True else decode
+    if durations is not None:
+        return decode_durations(logp, durations, A, pi)
     return decode_states(logp, A, pi)
 
 
@@ -649,6 +655,50 @@ def decode_info():
     return seg.value, mx.value
 
 
+def _decode_input(name: str, logp):
+    """The three input kinds of the decoders -> (the (sum T, 4) arena, the step offsets as a list, the kind)."""
+    if isinstance(logp, RaggedFeatures):
+        if logp._raw:
+            raise ValueError(f"{name}: raw features are not log-probs")
+        data, offs, kind = logp.data, [int(o) for o in logp._off], "ragged"
+    elif isinstance(logp, torch.Tensor) and logp.dim() == 3:
+        B, T = int(logp.shape[0]), int(logp.shape[1])
+        data, offs, kind = logp.reshape(B * T, -1) if B * T else logp.reshape(0, logp.shape[2]), [i * T for i in range(B + 1)], "batch"
+        if B and T < 1:
+            raise ValueError(f"{name}: (B, T, 4) log-probs with T >= 1 expected, got {tuple(logp.shape)}")
+    elif isinstance(logp, torch.Tensor) and logp.dim() == 2:
+        data, offs, kind = logp, [0, int(logp.shape[0])], "single"
+        if logp.shape[0] < 1:
+            raise ValueError(f"{name}: (T, 4) log-probs with T >= 1 expected, got {tuple(logp.shape)}")
+    else:
+        raise ValueError(f"{name}: a RaggedFeatures, a (B, T, 4) or a (T, 4) tensor expected")
+    if data.dim() != 2 or data.shape[1] != 4 or data.shape[0] != offs[-1]:
+        raise ValueError(f"{name}: log-probs over 4 states expected, got an arena of shape {tuple(data.shape)}")
+    if data.dtype != torch.float32:
+        raise ValueError(f"{name}: float32 log-probs expected, got {data.dtype}")
+    if data.device.type != "cuda":
+        raise ValueError(f"{name}: log-probs on a GPU expected, got {data.device}; the decoder has no CPU path")
+    return data, offs, kind
+
+
+def _decode_output(logp, kind: str, states, offs, scores):
+    """The states in the kind of the input; with ``scores`` (int64 on the device, or None) also the float64 scores on the host."""
+    if kind == "ragged":
+        out = RaggedStates(states, torch.tensor(offs, dtype=torch.int64))
+    elif kind == "batch":
+        out = states.view(int(logp.shape[0]), int(logp.shape[1]))
+    else:
+        out = states
+    if scores is None:
+        return out
+    # (NEG, the score of a recording with an all -inf step, reads as -inf)
+    sc = scores.cpu()
+    val = torch.where(sc == torch.iinfo(torch.int64).min, torch.tensor(float("-inf"), dtype=torch.float64), sc.double() / float(1 << 20))
+    if kind == "ragged":
+        out.scores = val
+    return out, (val[0] if kind == "single" else val)
+
+
 def decode_states(logp, transitions=None, initial=None, return_scores: bool = False):
     """Viterbi decoding on the device (``hssfsst_decode_states``): log-probs -> the best state sequence 0..3 (S1, systole, S2,
     diastole) under log transitions ``transitions`` (4, 4) and log initial scores ``initial`` (4,); ``-inf`` = forbidden; default
@@ -673,27 +723,7 @@ def decode_states(logp, transitions=None, initial=None, return_scores: bool = Fa
     pi = np.ascontiguousarray(initial.detach().cpu().numpy() if isinstance(initial, torch.Tensor) else initial, dtype=np.float32)
     if A.shape != (4, 4) or pi.shape != (4,):
         raise ValueError(f"{name}: transitions (4, 4) and initial (4,) expected, got {A.shape} and {pi.shape}")
-    if isinstance(logp, RaggedFeatures):
-        if logp._raw:
-            raise ValueError(f"{name}: raw features are not log-probs")
-        data, offs, kind = logp.data, [int(o) for o in logp._off], "ragged"
-    elif isinstance(logp, torch.Tensor) and logp.dim() == 3:
-        B, T = int(logp.shape[0]), int(logp.shape[1])
-        data, offs, kind = logp.reshape(B * T, -1) if B * T else logp.reshape(0, logp.shape[2]), [i * T for i in range(B + 1)], "batch"
-        if B and T < 1:
-            raise ValueError(f"{name}: (B, T, 4) log-probs with T >= 1 expected, got {tuple(logp.shape)}")
-    elif isinstance(logp, torch.Tensor) and logp.dim() == 2:
-        data, offs, kind = logp, [0, int(logp.shape[0])], "single"
-        if logp.shape[0] < 1:
-            raise ValueError(f"{name}: (T, 4) log-probs with T >= 1 expected, got {tuple(logp.shape)}")
-    else:
-        raise ValueError(f"{name}: a RaggedFeatures, a (B, T, 4) or a (T, 4) tensor expected")
-    if data.dim() != 2 or data.shape[1] != 4 or data.shape[0] != offs[-1]:
-        raise ValueError(f"{name}: log-probs over 4 states expected, got an arena of shape {tuple(data.shape)}")
-    if data.dtype != torch.float32:
-        raise ValueError(f"{name}: float32 log-probs expected, got {data.dtype}")
-    if data.device.type != "cuda":
-        raise ValueError(f"{name}: log-probs on a GPU expected, got {data.device}; the decoder has no CPU path")
+    data, offs, kind = _decode_input(name, logp)
     L = _lib.lib()
     _lib.guard_fork()
     device = data.device
@@ -709,20 +739,129 @@ def decode_states(logp, transitions=None, initial=None, return_scores: bool = Fa
                                                A.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), pi.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
                                                states.data_ptr(), scores.data_ptr() if return_scores else None, device.index, stream),
                        "hssfsst_decode_states")
-    if kind == "ragged":
-        out = RaggedStates(states, torch.tensor(offs, dtype=torch.int64))
-    elif kind == "batch":
-        out = states.view(int(logp.shape[0]), int(logp.shape[1]))
-    else:
-        out = states
-    if not return_scores:
-        return out
-    # (NEG, the score of a recording with an all -inf step, reads as -inf)
-    sc = scores.cpu()
-    val = torch.where(sc == torch.iinfo(torch.int64).min, torch.tensor(float("-inf"), dtype=torch.float64), sc.double() / float(1 << 20))
-    if kind == "ragged":
-        out.scores = val
-    return out, (val[0] if kind == "single" else val)
+    return _decode_output(logp, kind, states, offs, scores)
+
+
+def decode_durations_info():
+    """``(max_duration, max_steps, workspace_bytes_per_step)`` of the explicit-duration decoder
+    (``hssfsst_decode_durations_info``).  No device needed."""
+    D, mx, per = ctypes.c_int(0), ctypes.c_int64(0), ctypes.c_int64(0)
+    _lib.check(_lib.lib().hssfsst_decode_durations_info(ctypes.byref(D), ctypes.byref(mx), ctypes.byref(per)), "hssfsst_decode_durations_info")
+    return D.value, mx.value, per.value
+
+
+def _host_table(name: str, what: str, v, shape=None):
+    a = np.ascontiguousarray(v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v, dtype=np.float32)
+    if (shape is not None and a.shape != shape) or (shape is None and (a.ndim != 2 or a.shape[0] != 4 or a.shape[1] < 1)):
+        raise ValueError(f"{name}: {what} {shape if shape is not None else '(4, D)'} expected, got {a.shape}")
+    return a
+
+
+def edge_durations(dur):
+    """The default ``edge`` table of ``decode_durations``: the running maximum of ``dur`` (4, D) from the right, so that a run
+    the recording's end cuts off after d steps scores as the best run of at least d steps.  float32 numpy (4, D)."""
+    d = _host_table("edge_durations", "durations", dur)
+    return np.ascontiguousarray(np.maximum.accumulate(d[:, ::-1], axis=1)[:, ::-1])
+
+
+def gaussian_durations(mean, std, max_duration: int, min_duration: int = 1):
+    """``dur`` (4, max_duration) float32: per state the log of a normal density with the given ``mean`` and ``std`` (steps; a
+    scalar or four values each), discretised at d = min_duration .. max_duration and normalised over that support; ``-inf``
+    outside it."""
+    D, lo = int(max_duration), int(min_duration)
+    if not 1 <= lo <= D:
+        raise ValueError(f"gaussian_durations: 1 <= min_duration <= max_duration expected, got {lo} and {D}")
+    mean = np.broadcast_to(np.asarray(mean, dtype=np.float64), (4,))
+    std = np.broadcast_to(np.asarray(std, dtype=np.float64), (4,))
+    if not (std > 0).all():
+        raise ValueError("gaussian_durations: std > 0 expected")
+    d = np.arange(1, D + 1, dtype=np.float64)
+    logit = -0.5 * ((d[None, :] - mean[:, None]) / std[:, None]) ** 2
+    logit[:, :lo - 1] = -np.inf
+    top = logit.max(axis=1, keepdims=True)
+    with np.errstate(divide="ignore"):
+        out = logit - top - np.log(np.exp(logit - top).sum(axis=1, keepdims=True))
+    return out.astype(np.float32)
+
+
+def durations_from_labels(labels, max_duration: int, fit: str = "gaussian"):
+    """``dur`` (4, max_duration) float32 from the INTERIOR runs of label sequences (a list of 1-D integer tensors or arrays with
+    values 0..3): the first and the last run of every sequence are cut off by its ends (censored) and left out.
+    ``fit="gaussian"``: ``gaussian_durations`` of each state's mean and standard deviation (population; at least half a step);
+    ``fit="histogram"``: the log of the relative frequencies, ``-inf`` where never seen.  A run longer than ``max_duration`` or
+    a state without an interior run raises ValueError."""
+    D = int(max_duration)
+    if fit not in ("gaussian", "histogram"):
+        raise ValueError(f"durations_from_labels: fit 'gaussian' or 'histogram' expected, got {fit!r}")
+    seen = [[] for _ in range(4)]
+    for k, lab in enumerate(labels):
+        a = lab.detach().cpu().numpy() if isinstance(lab, torch.Tensor) else np.asarray(lab)
+        if a.ndim != 1 or a.size < 1 or a.dtype.kind not in "iu":
+            raise ValueError(f"durations_from_labels: item {k} is not a non-empty 1-D integer sequence")
+        a = a.astype(np.int64)
+        if a.min() < 0 or a.max() > 3:
+            raise ValueError(f"durations_from_labels: item {k} has labels outside 0..3")
+        cut = np.flatnonzero(np.diff(a)) + 1
+        starts, ends = np.concatenate([[0], cut]), np.concatenate([cut, [a.size]])
+        for s, e in list(zip(starts, ends))[1:-1]:
+            if e - s > D:
+                raise ValueError(f"durations_from_labels: item {k} has a run of {e - s} steps, over max_duration {D}")
+            seen[a[s]].append(int(e - s))
+    if any(not r for r in seen):
+        raise ValueError(f"durations_from_labels: state {[i for i, r in enumerate(seen) if not r][0]} has no interior run")
+    if fit == "gaussian":
+        return gaussian_durations([np.mean(r) for r in seen], [max(np.std(r), 0.5) for r in seen], D)
+    out = np.full((4, D), -np.inf, dtype=np.float64)
+    for j, r in enumerate(seen):
+        counts = np.bincount(np.asarray(r), minlength=D + 1)[1:].astype(np.float64)
+        with np.errstate(divide="ignore"):
+            out[j] = np.log(counts / counts.sum())
+    return out.astype(np.float32)
+
+
+def decode_durations(logp, durations, transitions=None, initial=None, edge=None, return_scores: bool = False):
+    """Explicit-duration (semi-Markov) Viterbi decoding on the device (``hssfsst_decode_durations``): ``decode_states`` with a
+    log score ``durations[j][d - 1]`` for an interior run of state j lasting d = 1 .. D steps, D = ``durations.shape[1]`` <= 2048;
+    ``-inf`` = forbidden, so no decoded run is longer than D or shorter than the table allows.  ``edge`` (4, D): the same for the
+    first and the last run of a recording, which its ends cut off; default ``edge_durations(durations)``.  ``transitions``,
+    ``initial``: as for ``decode_states`` (default ``cyclic_transitions()``), but the diagonal of ``transitions`` is ignored: a
+    run is never followed by a run of the same state.
+
+    ``logp`` and the result are ``decode_states``' three kinds.  One call, enqueued on the current stream; the workspace (8 bytes
+    per step) is allocated here.  A recording no segmentation fits gets the score -inf and the state 0 at every step.
+
+    Exact arithmetic (include/hssfsst.h), with one difference from ``decode_states``: an emission of ``-inf`` or NaN counts as
+    -32768 instead of forbidding its state, because the decoder works on prefix sums of the emissions."""
+    name = "decode_durations"
+    if (transitions is None) != (initial is None):
+        raise ValueError(f"{name}: pass both transitions and initial, or neither")
+    if transitions is None:
+        transitions, initial = cyclic_transitions()
+    A, pi = _host_table(name, "transitions", transitions, (4, 4)), _host_table(name, "initial", initial, (4,))
+    dur = _host_table(name, "durations", durations)
+    D = dur.shape[1]
+    eg = edge_durations(dur) if edge is None else _host_table(name, "edge", edge, (4, D))
+    data, offs, kind = _decode_input(name, logp)
+    L = _lib.lib()
+    _lib.guard_fork()
+    device = data.device
+    data = data.detach().contiguous()
+    count = len(offs) - 1
+    states = torch.empty((offs[-1],), dtype=torch.uint8, device=device)
+    scores = torch.empty((count,), dtype=torch.int64, device=device) if return_scores else None
+    if count:
+        o = np.asarray(offs, dtype=np.int64)
+        per = decode_durations_info()[2]
+        work = torch.empty((per * (offs[-1] + 8 * D),), dtype=torch.uint8, device=device)
+        fp = ctypes.POINTER(ctypes.c_float)
+        with torch.cuda.device(device):
+            stream = torch.cuda.current_stream(device).cuda_stream
+            _lib.check(L.hssfsst_decode_durations(data.data_ptr(), o.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), count,
+                                                  A.ctypes.data_as(fp), pi.ctypes.data_as(fp), dur.ctypes.data_as(fp), eg.ctypes.data_as(fp), D,
+                                                  states.data_ptr(), scores.data_ptr() if return_scores else None, work.data_ptr(),
+                                                  work.numel(), device.index, stream),
+                       "hssfsst_decode_durations")
+    return _decode_output(logp, kind, states, offs, scores)
 
 
 def state_runs(states: torch.Tensor):

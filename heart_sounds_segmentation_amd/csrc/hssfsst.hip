@@ -40,8 +40,10 @@
 #include "segmenter_lstm.hpp"
 #include "segmenter_layout.hpp"
 #include "segmenter_train.hpp"
+#include "decode_durations_layout.hpp"
 #include "decode_layout.hpp"
 #include "segmenter_decode.hpp"
+#include "segmenter_decode_durations.hpp"
 #include "fsst_tables.hpp"
 
 namespace tables = hssfsst::tables;
@@ -2734,6 +2736,109 @@ int hssfsst_decode_states(const float* logp, const int64_t* offsets, int64_t cou
         hipLaunchKernelGGL(hssfsst::seg_decode_kernel, dim3(static_cast<unsigned>(nrec)), dim3(dl::kLanes), 0, st, logp, states,
                            scores ? reinterpret_cast<long long*>(scores) + r0 : nullptr, args);
         if (int rc = launch_check("decode_states", "seg_decode_kernel")) return rc;
+    }
+    return 0;
+}
+
+}  // extern "C"
+
+// Explicit-duration Viterbi decoding (hssfsst.h: hssfsst_decode_durations; csrc/segmenter_decode_durations.hpp).  Stateless: the
+// quantised transitions and the launch's offsets travel as kernel arguments, kDurDecodeBatch recordings per launch; the two
+// duration tables travel as the arguments of fill launches into the head of the caller's workspace, so nothing is copied from
+// host memory and every launch is stream-ordered.
+extern "C" {
+
+int hssfsst_decode_durations_info(int* max_duration, int64_t* max_steps, int64_t* workspace_bytes_per_step)
+{
+    if (max_duration) *max_duration = hssfsst::durlayout::kMaxDuration;
+    if (max_steps) *max_steps = hssfsst::durlayout::kMaxSteps;
+    if (workspace_bytes_per_step) *workspace_bytes_per_step = hssfsst::durlayout::kWorkspaceBytesPerStep;
+    return 0;
+}
+
+int hssfsst_decode_durations(const float* logp, const int64_t* offsets, int64_t count, const float* transitions, const float* initial,
+                             const float* durations, const float* edge, int max_duration, uint8_t* states, int64_t* scores,
+                             void* workspace, int64_t workspace_bytes, int device, void* stream)
+{
+    namespace dl = hssfsst::declayout;
+    namespace ul = hssfsst::durlayout;
+    constexpr const char* kEntry = "decode_durations";
+    if (count < 0) return fail(HSSFSST_EINVAL, "%s: count %lld is negative", kEntry, static_cast<long long>(count));
+    if (!logp || !offsets || !transitions || !initial || !durations || !edge || !states || !workspace)
+        return fail(HSSFSST_EINVAL, "%s: bad argument (%s is NULL)", kEntry,
+                    !logp ? "logp" : !offsets ? "offsets" : !transitions ? "transitions" : !initial ? "initial" : !durations ? "durations"
+                    : !edge ? "edge" : !states ? "states" : "workspace");
+    if (device < 0) return fail(HSSFSST_EINVAL, "%s: device %d is negative", kEntry, device);
+    if (max_duration < 1 || max_duration > ul::kMaxDuration)
+        return fail(HSSFSST_EINVAL, "%s: max_duration %d is outside 1..%d", kEntry, max_duration, ul::kMaxDuration);
+    const int D = max_duration;
+    if (reinterpret_cast<uintptr_t>(logp) % 16 != 0) return fail(HSSFSST_EINVAL, "%s: logp is not 16-byte aligned", kEntry);
+    if (reinterpret_cast<uintptr_t>(workspace) % 16 != 0) return fail(HSSFSST_EINVAL, "%s: workspace is not 16-byte aligned", kEntry);
+    for (int i = 0; i < 16; ++i)
+        if (transitions[i] != transitions[i]) return fail(HSSFSST_EINVAL, "%s: transitions[%d][%d] is NaN", kEntry, i / 4, i % 4);
+    for (int i = 0; i < 4; ++i)
+        if (initial[i] != initial[i]) return fail(HSSFSST_EINVAL, "%s: initial[%d] is NaN", kEntry, i);
+    for (int which = 0; which < 2; ++which) {
+        const float* tab = which ? edge : durations;
+        const char* tname = which ? "edge" : "durations";
+        for (int j = 0; j < 4; ++j) {
+            bool any = false;
+            for (int d = 1; d <= D; ++d) {
+                const float v = tab[static_cast<size_t>(j) * D + (d - 1)];
+                if (v != v) return fail(HSSFSST_EINVAL, "%s: %s[%d][%d] is NaN (duration %d)", kEntry, tname, j, d - 1, d);
+                any = any || dl::quantise(v) != dl::kNeg;
+            }
+            if (!any) return fail(HSSFSST_EINVAL, "%s: row %d of %s is all -inf: state %d has no allowed duration", kEntry, j, tname, j);
+        }
+    }
+    hssfsst::DurDecodeArgs args{};
+    args.tb = ul::quantise_tables(transitions, initial);
+    args.D = D;
+    for (int i = 0; i < 4; ++i) {
+        bool any = false;
+        for (int j = 0; j < 4; ++j) any = any || (j != i && args.tb.A[i][j] != dl::kNeg);
+        if (!any)
+            return fail(HSSFSST_EINVAL, "%s: row %d of transitions has no finite off-diagonal entry: state %d has no successor", kEntry, i, i);
+    }
+    if (args.tb.pi[0] == dl::kNeg && args.tb.pi[1] == dl::kNeg && args.tb.pi[2] == dl::kNeg && args.tb.pi[3] == dl::kNeg)
+        return fail(HSSFSST_EINVAL, "%s: initial is all -inf: no state to start in", kEntry);
+    if (offsets[0] != 0) return fail(HSSFSST_EINVAL, "%s: offsets[0] is %lld, not 0", kEntry, static_cast<long long>(offsets[0]));
+    for (int64_t i = 0; i < count; ++i)
+        if (offsets[i + 1] <= offsets[i])
+            return fail(HSSFSST_EINVAL, "%s: offsets do not increase at index %lld (offsets[%lld] = %lld, offsets[%lld] = %lld)", kEntry,
+                        static_cast<long long>(i + 1), static_cast<long long>(i), static_cast<long long>(offsets[i]),
+                        static_cast<long long>(i + 1), static_cast<long long>(offsets[i + 1]));
+    for (int64_t i = 0; i < count; ++i)
+        if (offsets[i + 1] - offsets[i] > ul::kMaxSteps)
+            return fail(HSSFSST_EUNSUPPORTED, "%s: recording %lld has %lld steps, over the limit of %lld", kEntry, static_cast<long long>(i),
+                        static_cast<long long>(offsets[i + 1] - offsets[i]), static_cast<long long>(ul::kMaxSteps));
+    if (offsets[count] > 0x7fffffffLL)
+        return fail(HSSFSST_EUNSUPPORTED, "%s: %lld steps in all, over the limit of 2^31 - 1", kEntry, static_cast<long long>(offsets[count]));
+    const int64_t need = ul::kWorkspaceBytesPerStep * ul::workspace_steps(offsets[count], D);
+    if (workspace_bytes < need)
+        return fail(HSSFSST_EINVAL, "%s: workspace of %lld bytes is too small: %lld steps and max_duration %d need %lld", kEntry,
+                    static_cast<long long>(workspace_bytes), static_cast<long long>(offsets[count]), D, static_cast<long long>(need));
+    if (count == 0) return 0;
+    if (int rc = check_device(kEntry, device)) return rc;
+    DEVICE_SCOPE(device);
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    long long* table = static_cast<long long*>(workspace);
+    unsigned short* back = reinterpret_cast<unsigned short*>(table + ul::table_words(D));
+    hssfsst::DurFillArgs fa{};
+    fa.D = D;
+    for (int first = 0; first < 8 * D; first += hssfsst::kDurFillValues) {
+        fa.first = first;
+        fa.n = std::min(hssfsst::kDurFillValues, 8 * D - first);
+        for (int i = 0; i < fa.n; ++i) fa.v[i] = first + i < 4 * D ? durations[first + i] : edge[first + i - 4 * D];
+        hipLaunchKernelGGL(hssfsst::seg_durations_fill_kernel, dim3(1), dim3(hssfsst::kDurFillValues), 0, st, table, fa);
+        if (int rc = launch_check(kEntry, "seg_durations_fill_kernel")) return rc;
+    }
+    for (int64_t r0 = 0; r0 < count; r0 += hssfsst::kDurDecodeBatch) {
+        const int nrec = static_cast<int>(std::min<int64_t>(hssfsst::kDurDecodeBatch, count - r0));
+        for (int i = 0; i <= nrec; ++i) args.off[i] = offsets[r0 + i];
+        hipLaunchKernelGGL(hssfsst::seg_decode_durations_kernel, dim3(static_cast<unsigned>(nrec)), dim3(ul::kLanes), 0, st, logp, states,
+                           scores ? reinterpret_cast<long long*>(scores) + r0 : nullptr, back, table, args);
+        if (int rc = launch_check(kEntry, "seg_decode_durations_kernel")) return rc;
     }
     return 0;
 }

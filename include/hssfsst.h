@@ -428,6 +428,43 @@ int hssfsst_decode_states(const float* logp, const int64_t* offsets, int64_t cou
  * segments of that many steps from its step 1 on), max_steps = the longest recording (2^26).  Either pointer may be NULL. */
 int hssfsst_decode_info(int* segment_steps, int64_t* max_steps);
 
+/* Explicit-duration (semi-Markov) Viterbi decoding: hssfsst_decode_states with a score for how long each run of a state lasts,
+ * so that a decoded S1 cannot last 3 ms nor a systole 4 s (csrc/segmenter_decode_durations.hpp; the arithmetic, the sequential
+ * loop that defines the result bit for bit and the kernel's geometry as plain functions: csrc/decode_durations_layout.hpp).
+ * logp, offsets, count, states, scores, device, stream: as for hssfsst_decode_states.  Further
+ *   transitions   A (4, 4) float32, HOST: the DIAGONAL IS IGNORED -- a run is never followed by a run of the same state
+ *   initial       pi (4) float32, HOST
+ *   durations     dur (4, max_duration) float32, HOST: dur[j][d - 1] = log score of an interior run of state j lasting d steps
+ *   edge          (4, max_duration) float32, HOST: the same for the first and the last run of a recording, which its ends cut off
+ *   max_duration  D, 1 .. 2048 (hssfsst_decode_durations_info): no run is longer
+ *   workspace     DEVICE, 16-byte aligned, workspace_bytes >= workspace_bytes_per_step x (sum T + 8 D): the quantised tables
+ *                 (64 D bytes) and a step's four 16-bit duration backpointers (8 bytes); contents undefined afterwards
+ * A recording of T steps is cut into runs (s_1, d_1) .. (s_K, d_K), sum d_k = T, 1 <= d_k <= D, s_k != s_(k+1); its score is
+ *   q(pi[s_1]) + sum_k len_k + sum_k q(A[s_k][s_(k+1)]) + sum_t qe(e[t][s(t)]),
+ * len_k = q(edge[s_k][d_k]) for k = 1 and k = K (once when K = 1), q(dur[s_k][d_k]) otherwise.  q is hssfsst_decode_states'
+ * quantiser and -inf in pi, A, dur, edge means "forbidden".  THE EMISSIONS DIFFER from hssfsst_decode_states: qe(x) = q(x) except
+ * that -inf and NaN count as -32768 -- the decoder works on prefix sums of the emissions, and an absorbing element cannot sit
+ * inside one.  Everything after the quantisers is int64 add and max: with T <= 2^24 steps no sum exceeds 2^62 (at most 4 T + 3
+ * terms of 2^35), and the result is decode_durations_reference()'s, the best segmentation with ties to the smallest duration,
+ * then the smallest predecessor state, at the end to the smallest state, then the smallest duration.  A recording that no
+ * segmentation fits (e.g. T > D under an edge table that allows nothing) gets the score NEG (INT64_MIN) and the state 0 at
+ * every step.  The result does not depend on the smallest allowed duration: dur[j][0] may be finite.
+ * HSSFSST_EINVAL before any device work: a NULL pointer other than scores, count < 0, bad offsets (as hssfsst_decode_states), a
+ * NaN in any table (the message names the entry), max_duration outside 1 .. 2048, a row of durations or edge all -inf, a row of
+ * transitions with no finite off-diagonal entry, initial all -inf, device < 0, logp or workspace not 16-byte aligned, a workspace
+ * that is too small.  HSSFSST_EUNSUPPORTED: a recording of more than 2^24 steps, more than 2^31 - 1 steps in all.  count == 0
+ * returns 0 and does nothing.
+ * A recording's result does not depend on its neighbours or its place in the list.  Enqueued on `stream` without synchronising
+ * and without a copy from host memory (the tables travel as kernel arguments): ceil(8 D / 896) small launches that fill the
+ * tables, then one launch per 256 recordings, one workgroup of 512 lanes per recording, 102 KiB of LDS, no scratch memory. */
+int hssfsst_decode_durations(const float* logp, const int64_t* offsets, int64_t count, const float* transitions, const float* initial,
+                             const float* durations, const float* edge, int max_duration, uint8_t* states, int64_t* scores,
+                             void* workspace, int64_t workspace_bytes, int device, void* stream);
+
+/* Its limits, no device needed: max_duration = the largest D (2048), max_steps = the longest recording (2^24),
+ * workspace_bytes_per_step = 8.  Any pointer may be NULL. */
+int hssfsst_decode_durations_info(int* max_duration, int64_t* max_steps, int64_t* workspace_bytes_per_step);
+
 /* One DIFFERENTIABLE bidirectional LSTM layer (batch first, nn.LSTM's cell and gate order): the unit a training program stacks
  * under autograd -- the segmenter is two of them.  The plan holds the layer's current weights in the kernels' layouts and the
  * scratch of its calls; the caller owns inputs, outputs and the stash.  Every pointer below is a DEVICE pointer on the plan's
