@@ -3,7 +3,7 @@
 from . import moments, transforms  # noqa: F401
 from .transforms import FSST, Resample  # noqa: F401
 from .consumer import (cyclic_transitions, decode_durations, decode_states, durations_from_labels, edge_durations,  # noqa: F401
-                       gaussian_durations, state_runs, transitions_from_labels)
+                       gaussian_durations, sequence_nll, state_posteriors, state_runs, transitions_from_labels)
 
 __all__ = ["FSST", "Resample", "moments", "transforms", "decode_states", "cyclic_transitions", "transitions_from_labels", "state_runs",
-           "decode_durations", "edge_durations", "gaussian_durations", "durations_from_labels"]
+           "decode_durations", "edge_durations", "gaussian_durations", "durations_from_labels", "state_posteriors", "sequence_nll"]

@@ -300,6 +300,10 @@ def lib():
         L.hssfsst_decode_durations_info.restype = c_int
         L.hssfsst_decode_durations.argtypes = [vp, ctypes.POINTER(c_i64), c_i64, fp, fp, fp, fp, c_int, vp, vp, vp, c_i64, c_int, vp]
         L.hssfsst_decode_durations.restype = c_int
+        L.hssfsst_posteriors_info.argtypes = [ip, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]
+        L.hssfsst_posteriors_info.restype = c_int
+        L.hssfsst_posteriors.argtypes = [vp, ctypes.POINTER(c_i64), c_i64, vp, vp, vp, vp, vp, vp, vp, vp, c_i64, c_int, vp]
+        L.hssfsst_posteriors.restype = c_int
         L.hssfsst_bilstm_create.argtypes = [ctypes.POINTER(vp), c_int, c_int, c_int]
         L.hssfsst_bilstm_create.restype = c_int
         L.hssfsst_bilstm_destroy.argtypes = [vp]

@@ -25,6 +25,9 @@ cycle: stay or advance), one HIP call for a whole list of recordings (hssfsst_de
 ``decode_durations`` is the same with a score for how long each run lasts (explicit-duration, semi-Markov Viterbi:
 hssfsst_decode_durations; csrc/segmenter_decode_durations.hpp), with ``gaussian_durations`` / ``durations_from_labels`` /
 ``edge_durations`` for its tables.
+``state_posteriors`` is the smoothed counterpart of ``decode_states``' path, the per-step state posteriors under the same
+transitions, and ``sequence_nll`` the linear-chain sequence loss whose gradient they are: one forward-backward kernel for both
+(hssfsst_posteriors; csrc/segmenter_posteriors.hpp).
 """
 from __future__ import annotations
 
@@ -576,15 +579,23 @@ def segment(fsst, head, windows: torch.Tensor) -> torch.Tensor:
     return head(fsst.batch(windows))
 
 
-def segment_recordings(fsst, seg: HipSegmenter, recordings, decode=None, durations=None, **kw) -> RaggedFeatures:
+def segment_recordings(fsst, seg: HipSegmenter, recordings, decode=None, durations=None, posteriors=None, **kw) -> RaggedFeatures:
     """Whole recordings of different lengths (a list of 1-D signals on the GPU) -> ``FSST.ragged`` features, kept on the device
     -> a ``RaggedFeatures`` of ``(T_i, 4)`` log-probs: ``segment()`` for whole recordings.  ``kw`` goes to
     ``HipSegmenter.ragged`` (h0, c0, max_steps).  ``decode=True`` or ``decode=(A, pi)``: the log-probs go on to ``decode_states``
     (default or given transitions) and the ``RaggedStates`` of ``(T_i,)`` uint8 state sequences is returned instead; with
-    ``durations=dur`` (4, D) they go to ``decode_durations`` under that table, its default ``edge`` and the same transitions."""
+    ``durations=dur`` (4, D) they go to ``decode_durations`` under that table, its default ``edge`` and the same transitions.
+    ``posteriors=True`` or ``posteriors=(A, pi)``: they go on to ``state_posteriors`` instead and the ``RaggedFeatures`` of
+    ``(T_i, 4)`` float32 posteriors is returned; not together with ``decode`` (ValueError)."""
+    want_post = not (posteriors is None or posteriors is False)
+    if want_post and (not (decode is None or decode is False) or durations is not None):
+        raise ValueError("segment_recordings: posteriors and decode exclude each other: one call returns one of them")
     if durations is not None and (decode is None or decode is False):
         raise ValueError("segment_recordings: durations are for decoding: pass decode=True or decode=(A, pi) with them")
     logp = seg.ragged(fsst.ragged(recordings), **kw)
+    if want_post:
+        A, pi = (None, None) if posteriors is True else posteriors
+        return state_posteriors(logp, A, pi)
     if decode is None or decode is False:
         return logp
     A, pi = (None, None) if decode is True else decode
@@ -862,6 +873,199 @@ def decode_durations(logp, durations, transitions=None, initial=None, edge=None,
                                                   work.numel(), device.index, stream),
                        "hssfsst_decode_durations")
     return _decode_output(logp, kind, states, offs, scores)
+
+
+# ------------------------------------------------------------------- log-probs -> state posteriors and the sequence loss
+def posteriors_info():
+    """``(segment_steps, max_steps, work_bytes_per_step, work_bytes_per_recording)`` of the forward-backward kernel
+    (``hssfsst_posteriors_info``).  No device needed."""
+    seg, mx, per, rec = ctypes.c_int(0), ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+    _lib.check(_lib.lib().hssfsst_posteriors_info(ctypes.byref(seg), ctypes.byref(mx), ctypes.byref(per), ctypes.byref(rec)),
+               "hssfsst_posteriors_info")
+    return seg.value, mx.value, per.value, rec.value
+
+
+def _posterior_tables(name: str, transitions, initial, device):
+    """``(A, pi)`` as given (default ``cyclic_transitions()``) -> the tensors ``A (4, 4)``, ``pi (4,)`` on ``device``: tensors
+    already there are kept (they may carry a gradient), anything else is uploaded as float32."""
+    if (transitions is None) != (initial is None):
+        raise ValueError(f"{name}: pass both transitions and initial, or neither")
+    if transitions is None:
+        transitions, initial = cyclic_transitions()
+    out = []
+    for what, v, shape in (("transitions", transitions, (4, 4)), ("initial", initial, (4,))):
+        if isinstance(v, torch.Tensor) and v.device == device:
+            if not v.is_floating_point():
+                raise ValueError(f"{name}: floating-point {what} expected, got {v.dtype}")
+            t = v
+        else:
+            t = torch.from_numpy(np.ascontiguousarray(v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v, dtype=np.float32)).to(device)
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{name}: {what} {shape} expected, got {tuple(t.shape)}")
+        out.append(t)
+    return out[0], out[1]
+
+
+def _posteriors_run(data, offs, a_pi, labels=None, tables_grad: bool = False):
+    """One ``hssfsst_posteriors`` call on the current stream -> ``(gamma, loglik, score, xi, gamma0)``; ``score`` only with
+    ``labels`` (a uint8 arena on the device), ``xi`` and ``gamma0`` only with ``tables_grad``; None otherwise."""
+    L = _lib.lib()
+    _lib.guard_fork()
+    device = data.device
+    count, total = len(offs) - 1, offs[-1]
+    f64 = dict(dtype=torch.float64, device=device)
+    gamma = torch.empty((total, 4), dtype=torch.float32, device=device)
+    loglik = torch.empty((count,), **f64)
+    score = torch.empty((count,), **f64) if labels is not None else None
+    xi = torch.empty((count, 16), **f64) if tables_grad else None
+    gamma0 = torch.empty((count, 4), **f64) if tables_grad else None
+    if count:
+        _, _, per, rec = posteriors_info()
+        work = torch.empty((per * total + rec * count,), dtype=torch.uint8, device=device)
+        o = np.asarray(offs, dtype=np.int64)
+        with torch.cuda.device(device):
+            stream = torch.cuda.current_stream(device).cuda_stream
+            _lib.check(L.hssfsst_posteriors(data.data_ptr(), o.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), count, a_pi.data_ptr(),
+                                            labels.data_ptr() if labels is not None else None, gamma.data_ptr(), loglik.data_ptr(),
+                                            score.data_ptr() if score is not None else None, xi.data_ptr() if xi is not None else None,
+                                            gamma0.data_ptr() if gamma0 is not None else None, work.data_ptr(), work.numel(),
+                                            device.index, stream),
+                       "hssfsst_posteriors")
+    return gamma, loglik, score, xi, gamma0
+
+
+def _a_pi(A: torch.Tensor, pi: torch.Tensor) -> torch.Tensor:
+    return torch.cat([A.detach().reshape(16).to(torch.float32), pi.detach().reshape(4).to(torch.float32)]).contiguous()
+
+
+def state_posteriors(logp, transitions=None, initial=None, return_loglik: bool = False):
+    """Forward-backward on the device (``hssfsst_posteriors``): log-probs -> the per-step state posteriors ``gamma_t(j) =
+    P(state_t = j | the whole recording, A, pi)`` under log transitions ``transitions`` (4, 4) and log initial scores ``initial``
+    (4,); ``-inf`` = forbidden; default ``cyclic_transitions()``.  The smoothed counterpart of ``decode_states``' path: a score
+    per step and state that respects the cardiac cycle (per-class AUROC, a confidence for a decoded path).
+
+    ``logp``: ``decode_states``' three kinds.  Returns the same kind in float32: a ``RaggedFeatures`` of ``(T_i, 4)``, a
+    ``(B, T, 4)`` or a ``(T, 4)`` tensor.  ``return_loglik=True``: also ``logZ``, float64 ``(B,)`` ON THE DEVICE (a 0-d tensor for
+    ``(T, 4)``): nothing here waits for the device.  One call, enqueued on the current stream.  Not differentiable (see
+    ``sequence_nll``).  The tables may be numpy arrays or tensors; those on the host are uploaded.
+
+    float64 inside, scaled by exact powers of two (include/hssfsst.h): a path more than ~700 nats below the best one reaching the
+    same step is dropped; NaN emissions count as ``-inf``; a recording no path fits gets ``logZ = -inf`` and ``gamma = 0``."""
+    name = "state_posteriors"
+    data, offs, kind = _decode_input(name, logp)
+    A, pi = _posterior_tables(name, transitions, initial, data.device)
+    gamma, loglik, _, _, _ = _posteriors_run(data.detach().contiguous(), offs, _a_pi(A, pi))
+    if kind == "ragged":
+        out = RaggedFeatures(gamma, torch.tensor(offs, dtype=torch.int64), 4, False)
+    elif kind == "batch":
+        out = gamma.view(int(logp.shape[0]), int(logp.shape[1]), 4)
+    else:
+        out = gamma
+    if not return_loglik:
+        return out
+    return out, (loglik[0] if kind == "single" else loglik)
+
+
+def _nll_labels(name: str, labels, offs, kind: str, device) -> torch.Tensor:
+    """The labels of ``sequence_nll`` -> one uint8 arena ``(sum T,)`` on ``device``.  Lengths are checked always; values are
+    checked (0..3) where the labels are on the HOST -- labels on the device are not read back (no synchronisation): the kernel
+    looks at their two low bits only."""
+    total, count = offs[-1], len(offs) - 1
+
+    def values(t, what):
+        if isinstance(t, np.ndarray):
+            t = torch.from_numpy(t)
+        if not isinstance(t, torch.Tensor) or t.is_floating_point() or t.is_complex() or t.dtype == torch.bool:
+            raise ValueError(f"{name}: {what}: integer labels expected")
+        if t.device.type == "cpu" and t.numel() and (int(t.min()) < 0 or int(t.max()) > 3):
+            raise ValueError(f"{name}: {what} has labels outside 0..3")
+        return t
+
+    if isinstance(labels, RaggedFeatures):
+        if [int(o) for o in labels._off] != list(offs) or labels.data.dim() != 1:
+            raise ValueError(f"{name}: the labels' offsets do not match the log-probs'")
+        arena = values(labels.data, "labels")
+    elif isinstance(labels, (list, tuple)):
+        if len(labels) != count:
+            raise ValueError(f"{name}: {len(labels)} label sequences for {count} recordings")
+        items = []
+        for i, lab in enumerate(labels):
+            t = values(lab, f"item {i}")
+            if t.dim() != 1 or t.shape[0] != offs[i + 1] - offs[i]:
+                raise ValueError(f"{name}: item {i} has labels of shape {tuple(t.shape)} for {offs[i + 1] - offs[i]} steps")
+            items.append(t.to(device=device, dtype=torch.uint8))
+        arena = torch.cat(items) if items else torch.empty((0,), dtype=torch.uint8, device=device)
+    else:
+        t = values(labels, "labels")
+        if kind == "batch" and t.dim() == 2 and t.shape[0] == count and t.shape[0] * t.shape[1] == total:
+            arena = t.reshape(total)
+        elif t.dim() == 1 and t.shape[0] == total:
+            arena = t
+        else:
+            raise ValueError(f"{name}: labels of shape {tuple(t.shape)} do not match {count} recordings of {total} steps in all")
+    return arena.to(device=device, dtype=torch.uint8).contiguous()
+
+
+class _SequenceNLL(torch.autograd.Function):
+    """``(B,)`` float64 ``logZ - score(labels)`` from one ``hssfsst_posteriors`` call; the backward is a scale of what that call
+    left: ``gamma - onehot``, ``Xi - counts``, ``gamma_0 - onehot_0``."""
+
+    @staticmethod
+    def forward(ctx, data, A, pi, labels, offs):
+        tables_grad = A.requires_grad or pi.requires_grad
+        gamma, loglik, score, xi, gamma0 = _posteriors_run(data.detach().contiguous(), offs, _a_pi(A, pi), labels, tables_grad)
+        ctx.offs = offs
+        ctx.tables_grad = tables_grad
+        ctx.dtypes = (A.dtype, pi.dtype)
+        ctx.save_for_backward(gamma, xi, gamma0, torch.isinf(A.detach()), torch.isinf(pi.detach()))
+        return loglik - score
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        gamma, xi, gamma0, a_forbidden, pi_forbidden = ctx.saved_tensors
+        offs = ctx.offs
+        g = g.to(torch.float64)
+        d_data = d_A = d_pi = None
+        if ctx.needs_input_grad[0]:
+            lens = torch.tensor([offs[i + 1] - offs[i] for i in range(len(offs) - 1)], dtype=torch.int64).to(g.device, non_blocking=True)
+            per_step = torch.repeat_interleave(g, lens, output_size=offs[-1])
+            d_data = (gamma.to(torch.float64) * per_step[:, None]).to(torch.float32)
+        if ctx.tables_grad and ctx.needs_input_grad[1]:
+            d_A = (xi * g[:, None]).sum(dim=0).view(4, 4).masked_fill(a_forbidden, 0.0).to(ctx.dtypes[0])
+        if ctx.tables_grad and ctx.needs_input_grad[2]:
+            d_pi = (gamma0 * g[:, None]).sum(dim=0).masked_fill(pi_forbidden, 0.0).to(ctx.dtypes[1])
+        return d_data, d_A, d_pi, None, None
+
+
+def sequence_nll(logp, labels, transitions=None, initial=None, reduction: str = "mean"):
+    """The linear-chain sequence loss ``logZ - score(labels)`` under the transition model the segmenter is decoded with
+    (``hssfsst_posteriors``): the negative log-probability of the whole label sequence given ``A``, ``pi`` and the emissions,
+    where the per-step ``nll_loss`` never tells the network that impossible sequences cost nothing at inference.
+
+    ``logp``: ``decode_states``' three kinds (the arena of a ``RaggedFeatures`` may carry a gradient: ``HipSegmenterHead.ragged``).
+    ``labels``: a list of 1-D integer tensors (one per recording), a ``RaggedStates`` or a uint8 arena ``(sum T,)`` with matching
+    offsets, or a ``(B, T)`` / ``(T,)`` tensor.  Mismatched lengths raise ValueError; values outside 0..3 raise ValueError where
+    the labels are on the host -- labels on the device are not read back (that would wait for the device) and only their two low
+    bits count.  ``reduction``: ``"mean"`` = ``sum_i nll_i / sum_i T_i``, per step and so comparable with ``nll_loss``; ``"sum"``;
+    ``"none"`` = ``(B,)``.  The value is float64, cast to float32 for ``"mean"`` and ``"sum"``.
+
+    Differentiable (once) in ``logp`` and, where they are tensors on the log-probs' device that require grad, in ``transitions``
+    and ``initial``: ``gamma - onehot(y)``, ``Xi - counts(y)`` and ``gamma_0 - onehot(y_0)`` times the incoming gradient and the
+    reduction's factor; forbidden (``-inf``) entries of the tables get gradient 0.  The forward is one kernel call; the backward
+    launches no recurrence.  The tables reach the kernel in float32 whatever their dtype."""
+    name = "sequence_nll"
+    if reduction not in ("mean", "sum", "none"):
+        raise ValueError(f"{name}: reduction 'mean', 'sum' or 'none' expected, got {reduction!r}")
+    data, offs, kind = _decode_input(name, logp)
+    A, pi = _posterior_tables(name, transitions, initial, data.device)
+    arena = _nll_labels(name, labels, offs, kind, data.device)
+    nll = _SequenceNLL.apply(data, A, pi, arena, offs)
+    if reduction == "none":
+        return nll
+    if reduction == "sum":
+        return nll.sum().to(torch.float32)
+    return (nll.sum() / max(offs[-1], 1)).to(torch.float32)
 
 
 def state_runs(states: torch.Tensor):

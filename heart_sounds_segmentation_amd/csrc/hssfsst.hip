@@ -44,6 +44,8 @@
 #include "decode_layout.hpp"
 #include "segmenter_decode.hpp"
 #include "segmenter_decode_durations.hpp"
+#include "posterior_layout.hpp"
+#include "segmenter_posteriors.hpp"
 #include "fsst_tables.hpp"
 
 namespace tables = hssfsst::tables;
@@ -2839,6 +2841,74 @@ int hssfsst_decode_durations(const float* logp, const int64_t* offsets, int64_t 
         hipLaunchKernelGGL(hssfsst::seg_decode_durations_kernel, dim3(static_cast<unsigned>(nrec)), dim3(ul::kLanes), 0, st, logp, states,
                            scores ? reinterpret_cast<long long*>(scores) + r0 : nullptr, back, table, args);
         if (int rc = launch_check(kEntry, "seg_decode_durations_kernel")) return rc;
+    }
+    return 0;
+}
+
+}  // extern "C"
+
+// Forward-backward under the transition model (hssfsst.h: hssfsst_posteriors; csrc/segmenter_posteriors.hpp).  Stateless: the
+// launch's offsets travel as kernel arguments, kPostBatch recordings per launch; the tables are read from device memory.
+extern "C" {
+
+int hssfsst_posteriors_info(int* segment_steps, int64_t* max_steps, int64_t* work_bytes_per_step, int64_t* work_bytes_per_recording)
+{
+    if (segment_steps) *segment_steps = hssfsst::postlayout::kSegSteps;
+    if (max_steps) *max_steps = hssfsst::postlayout::kMaxSteps;
+    if (work_bytes_per_step) *work_bytes_per_step = hssfsst::postlayout::kWorkBytesPerStep;
+    if (work_bytes_per_recording) *work_bytes_per_recording = hssfsst::postlayout::kWorkBytesPerRecording;
+    return 0;
+}
+
+int hssfsst_posteriors(const float* logp, const int64_t* offsets, int64_t count, const float* a_pi, const uint8_t* labels, float* gamma,
+                       double* loglik, double* score, double* xi, double* gamma0, void* work, int64_t work_bytes, int device, void* stream)
+{
+    namespace pl = hssfsst::postlayout;
+    constexpr const char* kEntry = "posteriors";
+    if (count < 0) return fail(HSSFSST_EINVAL, "%s: count %lld is negative", kEntry, static_cast<long long>(count));
+    if (!logp || !offsets || !a_pi || !gamma || !loglik || !work)
+        return fail(HSSFSST_EINVAL, "%s: bad argument (%s is NULL)", kEntry,
+                    !logp ? "logp" : !offsets ? "offsets" : !a_pi ? "a_pi" : !gamma ? "gamma" : !loglik ? "loglik" : "work");
+    if (score && !labels) return fail(HSSFSST_EINVAL, "%s: bad argument (labels is NULL while score is not)", kEntry);
+    if (device < 0) return fail(HSSFSST_EINVAL, "%s: device %d is negative", kEntry, device);
+    if (reinterpret_cast<uintptr_t>(logp) % 16 != 0) return fail(HSSFSST_EINVAL, "%s: logp is not 16-byte aligned", kEntry);
+    if (reinterpret_cast<uintptr_t>(gamma) % 16 != 0) return fail(HSSFSST_EINVAL, "%s: gamma is not 16-byte aligned", kEntry);
+    if (reinterpret_cast<uintptr_t>(work) % 16 != 0) return fail(HSSFSST_EINVAL, "%s: work is not 16-byte aligned", kEntry);
+    if (reinterpret_cast<uintptr_t>(a_pi) % 4 != 0) return fail(HSSFSST_EINVAL, "%s: a_pi is not 4-byte aligned", kEntry);
+    if (reinterpret_cast<uintptr_t>(loglik) % 8 != 0 || reinterpret_cast<uintptr_t>(score) % 8 != 0 || reinterpret_cast<uintptr_t>(xi) % 8 != 0 ||
+        reinterpret_cast<uintptr_t>(gamma0) % 8 != 0)
+        return fail(HSSFSST_EINVAL, "%s: %s is not 8-byte aligned", kEntry,
+                    reinterpret_cast<uintptr_t>(loglik) % 8 != 0 ? "loglik" : reinterpret_cast<uintptr_t>(score) % 8 != 0 ? "score"
+                    : reinterpret_cast<uintptr_t>(xi) % 8 != 0 ? "xi" : "gamma0");
+    if (offsets[0] != 0) return fail(HSSFSST_EINVAL, "%s: offsets[0] is %lld, not 0", kEntry, static_cast<long long>(offsets[0]));
+    for (int64_t i = 0; i < count; ++i)
+        if (offsets[i + 1] <= offsets[i])
+            return fail(HSSFSST_EINVAL, "%s: offsets do not increase at index %lld (offsets[%lld] = %lld, offsets[%lld] = %lld)", kEntry,
+                        static_cast<long long>(i + 1), static_cast<long long>(i), static_cast<long long>(offsets[i]),
+                        static_cast<long long>(i + 1), static_cast<long long>(offsets[i + 1]));
+    for (int64_t i = 0; i < count; ++i)
+        if (offsets[i + 1] - offsets[i] > pl::kMaxSteps)
+            return fail(HSSFSST_EUNSUPPORTED, "%s: recording %lld has %lld steps, over the limit of %lld", kEntry, static_cast<long long>(i),
+                        static_cast<long long>(offsets[i + 1] - offsets[i]), static_cast<long long>(pl::kMaxSteps));
+    if (offsets[count] > 0x7fffffffLL)
+        return fail(HSSFSST_EUNSUPPORTED, "%s: %lld steps in all, over the limit of 2^31 - 1", kEntry, static_cast<long long>(offsets[count]));
+    const int64_t need = pl::workspace_bytes(offsets[count], count);
+    if (work_bytes < need)
+        return fail(HSSFSST_EINVAL, "%s: work of %lld bytes is too small: %lld steps in %lld recordings need %lld", kEntry,
+                    static_cast<long long>(work_bytes), static_cast<long long>(offsets[count]), static_cast<long long>(count),
+                    static_cast<long long>(need));
+    if (count == 0) return 0;
+    if (int rc = check_device(kEntry, device)) return rc;
+    DEVICE_SCOPE(device);
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    hssfsst::PostArgs args{};
+    for (int64_t r0 = 0; r0 < count; r0 += hssfsst::kPostBatch) {
+        const int nrec = static_cast<int>(std::min<int64_t>(hssfsst::kPostBatch, count - r0));
+        for (int i = 0; i <= nrec; ++i) args.off[i] = offsets[r0 + i];
+        args.rec0 = r0;
+        hipLaunchKernelGGL(hssfsst::seg_posteriors_kernel, dim3(static_cast<unsigned>(nrec)), dim3(pl::kLanes), 0, st, logp, a_pi, labels, gamma,
+                           loglik + r0, score ? score + r0 : nullptr, xi ? xi + 16 * r0 : nullptr, gamma0 ? gamma0 + 4 * r0 : nullptr, static_cast<double*>(work), args);
+        if (int rc = launch_check(kEntry, "seg_posteriors_kernel")) return rc;
     }
     return 0;
 }

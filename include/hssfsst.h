@@ -465,6 +465,47 @@ int hssfsst_decode_durations(const float* logp, const int64_t* offsets, int64_t 
  * workspace_bytes_per_step = 8.  Any pointer may be NULL. */
 int hssfsst_decode_durations_info(int* max_duration, int64_t* max_steps, int64_t* workspace_bytes_per_step);
 
+/* Forward-backward under the transition model of hssfsst_decode_states: the smoothed counterpart of the Viterbi path, for a LIST
+ * of recordings in one call (csrc/segmenter_posteriors.hpp; the arithmetic, the sequential loop that is the specification and the
+ * kernel's geometry as plain functions: csrc/posterior_layout.hpp).  Stateless: no plan.  logp, offsets, count, device, stream: as
+ * for hssfsst_decode_states.  Further
+ *   a_pi     20 float32, DEVICE, 4-byte aligned: A (4, 4) row-major, then pi (4); -inf = forbidden; read by the kernel, so a
+ *            learnable table costs no host synchronisation.  Entries must be -inf or below ~700 (exp in float64); unchecked
+ *   labels   (sum T) uint8, DEVICE, or NULL: a state 0..3 per step (only the two low bits are looked at)
+ *   gamma    (sum T, 4) float32, DEVICE, 16-byte aligned: gamma_t[j] = P(state_t = j | the whole recording, A, pi); WITH labels
+ *            gamma - onehot(labels) instead, the gradient of logZ - score in the emissions
+ *   loglik   (count) float64, DEVICE: logZ = log of the sum over all 4^T paths of exp w(path),
+ *            w(path) = pi[s_0] + sum_t e[t][s_t] + sum_(t >= 1) A[s_(t-1)][s_t]  (the diagonal of A counts)
+ *   score    (count) float64, DEVICE, or NULL: w(labels); needs labels
+ *   xi       (count, 16) float64, DEVICE, or NULL: Xi[i][j] = sum_(t >= 1) P(s_(t-1) = i, s_t = j | ...), the expected transition
+ *            counts (the gradient of logZ in A); WITH labels Xi - counts(labels)
+ *   gamma0   (count, 4) float64, DEVICE, or NULL: row offsets[i] of gamma before its rounding to float32 -- the step-0 posteriors,
+ *            the gradient of logZ in pi (WITH labels minus onehot(labels[0])); it may as well be read from gamma in float32
+ *   work     DEVICE, 16-byte aligned, work_bytes >= work_bytes_per_step x sum T + work_bytes_per_recording x count
+ *            (hssfsst_posteriors_info); contents undefined afterwards
+ * Arithmetic: float64 in the linear domain, gamma rounded to float32 at the end.  With b_t[j] = exp(e[t][j] - max_j e[t][j]),
+ * P = exp(A), p0 = exp(pi) every running vector and 4 x 4 transfer matrix is a float64 mantissa with an integer exponent,
+ * renormalised by an exact power of two after every step and every product; there is no subtraction, and gamma and the terms of
+ * Xi are normalised per step.  logZ = log sum_j alpha_(T-1)[j] + exponent ln 2 + sum_t max_j e[t][j].
+ * THE LIMIT: a path whose weight falls more than about 700 nats (float64 underflow) below the best path reaching the same step is
+ * dropped.  Emissions within 200 of their step's maximum can never trigger this with four states (3 x 200 < 708); a float32
+ * log_softmax stays within about 104.  NaN emissions count as -inf.  A recording with Z = 0 (e.g. a step whose four emissions are
+ * -inf) gets logZ = -inf, gamma = 0 and Xi = 0 (minus the labels' terms when labels are given).
+ * HSSFSST_EINVAL before any device work: a NULL pointer other than labels, score, xi, gamma0; labels NULL while score is not; count < 0;
+ * bad offsets (as hssfsst_decode_states); device < 0; logp, gamma or work not 16-byte aligned, a_pi not 4-byte, loglik, score, xi or
+ * gamma0 not 8-byte aligned; a work that is too small.  HSSFSST_EUNSUPPORTED: a recording of more than 2^20 steps, more than 2^31 - 1
+ * steps in all.  count == 0 returns 0 and does nothing.
+ * A recording's outputs do not depend on its neighbours or its place in the list, bit for bit, and two calls give the same bits.
+ * Enqueued on `stream` without synchronising: one launch per 256 recordings, one workgroup of 256 lanes per recording (a single
+ * long recording uses one CU), 70 KiB of LDS, no scratch memory. */
+int hssfsst_posteriors(const float* logp, const int64_t* offsets, int64_t count, const float* a_pi, const uint8_t* labels, float* gamma,
+                       double* loglik, double* score, double* xi, double* gamma0, void* work, int64_t work_bytes, int device, void* stream);
+
+/* Its geometry and limits, no device needed: segment_steps = steps a workgroup stages at a time (2048 = 256 lanes x 8 steps; a
+ * recording is walked in segments from its step 1 on), max_steps = the longest recording (2^20), and the two factors of the
+ * workspace size.  Any pointer may be NULL. */
+int hssfsst_posteriors_info(int* segment_steps, int64_t* max_steps, int64_t* work_bytes_per_step, int64_t* work_bytes_per_recording);
+
 /* One DIFFERENTIABLE bidirectional LSTM layer (batch first, nn.LSTM's cell and gate order): the unit a training program stacks
  * under autograd -- the segmenter is two of them.  The plan holds the layer's current weights in the kernels' layouts and the
  * scratch of its calls; the caller owns inputs, outputs and the stash.  Every pointer below is a DEVICE pointer on the plan's
