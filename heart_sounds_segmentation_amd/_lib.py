@@ -304,6 +304,11 @@ def lib():
         L.hssfsst_posteriors_info.restype = c_int
         L.hssfsst_posteriors.argtypes = [vp, ctypes.POINTER(c_i64), c_i64, vp, vp, vp, vp, vp, vp, vp, vp, c_i64, c_int, vp]
         L.hssfsst_posteriors.restype = c_int
+        L.hssfsst_posteriors_durations_info.argtypes = [ip, ip] + [ctypes.POINTER(c_i64)] * 4
+        L.hssfsst_posteriors_durations_info.restype = c_int
+        L.hssfsst_posteriors_durations.argtypes = [vp, ctypes.POINTER(c_i64), c_i64, vp, vp, vp, c_int, vp, vp, vp, vp, vp, vp, vp, vp, c_i64,
+                                                   c_int, vp]
+        L.hssfsst_posteriors_durations.restype = c_int
         L.hssfsst_bilstm_create.argtypes = [ctypes.POINTER(vp), c_int, c_int, c_int]
         L.hssfsst_bilstm_create.restype = c_int
         L.hssfsst_bilstm_destroy.argtypes = [vp]

@@ -586,15 +586,20 @@ def segment_recordings(fsst, seg: HipSegmenter, recordings, decode=None, duratio
     (default or given transitions) and the ``RaggedStates`` of ``(T_i,)`` uint8 state sequences is returned instead; with
     ``durations=dur`` (4, D) they go to ``decode_durations`` under that table, its default ``edge`` and the same transitions.
     ``posteriors=True`` or ``posteriors=(A, pi)``: they go on to ``state_posteriors`` instead and the ``RaggedFeatures`` of
-    ``(T_i, 4)`` float32 posteriors is returned; not together with ``decode`` (ValueError)."""
+    ``(T_i, 4)`` float32 posteriors is returned, with ``durations=dur`` those of ``duration_posteriors`` under that table and its
+    default ``edge``; not together with ``decode`` (ValueError).  ``durations`` without either raises ValueError."""
     want_post = not (posteriors is None or posteriors is False)
-    if want_post and (not (decode is None or decode is False) or durations is not None):
+    want_decode = not (decode is None or decode is False)
+    if want_post and want_decode:
         raise ValueError("segment_recordings: posteriors and decode exclude each other: one call returns one of them")
-    if durations is not None and (decode is None or decode is False):
-        raise ValueError("segment_recordings: durations are for decoding: pass decode=True or decode=(A, pi) with them")
+    if durations is not None and not (want_decode or want_post):
+        raise ValueError("segment_recordings: durations are for decoding or posteriors: pass decode=True, decode=(A, pi), "
+                         "posteriors=True or posteriors=(A, pi) with them")
     logp = seg.ragged(fsst.ragged(recordings), **kw)
     if want_post:
         A, pi = (None, None) if posteriors is True else posteriors
+        if durations is not None:
+            return duration_posteriors(logp, durations, A, pi)
         return state_posteriors(logp, A, pi)
     if decode is None or decode is False:
         return logp
@@ -1061,6 +1066,171 @@ def sequence_nll(logp, labels, transitions=None, initial=None, reduction: str = 
     A, pi = _posterior_tables(name, transitions, initial, data.device)
     arena = _nll_labels(name, labels, offs, kind, data.device)
     nll = _SequenceNLL.apply(data, A, pi, arena, offs)
+    if reduction == "none":
+        return nll
+    if reduction == "sum":
+        return nll.sum().to(torch.float32)
+    return (nll.sum() / max(offs[-1], 1)).to(torch.float32)
+
+
+# ------------------------------------------------- log-probs -> posteriors and the sequence loss under duration scores
+def duration_posteriors_info():
+    """``(max_duration, segment_steps, max_steps, work_bytes_per_step, work_bytes_per_recording, work_bytes_per_duration)`` of the
+    explicit-duration forward-backward kernel (``hssfsst_posteriors_durations_info``).  No device needed."""
+    D, seg = ctypes.c_int(0), ctypes.c_int(0)
+    mx, per, rec, dur = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+    _lib.check(_lib.lib().hssfsst_posteriors_durations_info(ctypes.byref(D), ctypes.byref(seg), ctypes.byref(mx), ctypes.byref(per),
+                                                            ctypes.byref(rec), ctypes.byref(dur)), "hssfsst_posteriors_durations_info")
+    return D.value, seg.value, mx.value, per.value, rec.value, dur.value
+
+
+def _duration_tables(name: str, durations, edge, device):
+    """``dur``, ``edge`` (default ``edge_durations(dur)``) -> two contiguous float32 ``(4, D)`` tensors on ``device``.  They are
+    constants of the model: one that requires grad raises ValueError."""
+    for what, v in (("durations", durations), ("edge", edge)):
+        if isinstance(v, torch.Tensor) and v.requires_grad:
+            raise ValueError(f"{name}: {what} requires grad, but the duration tables are constants: there is no gradient in them")
+    if isinstance(durations, torch.Tensor) and durations.device == device and edge is not None:
+        dur = durations.detach().to(torch.float32).contiguous()
+        if dur.dim() != 2 or dur.shape[0] != 4 or dur.shape[1] < 1:
+            raise ValueError(f"{name}: durations (4, D) expected, got {tuple(dur.shape)}")
+    else:
+        host = _host_table(name, "durations", durations)
+        if edge is None:
+            edge = edge_durations(host)
+        dur = torch.from_numpy(host).to(device)
+    D = int(dur.shape[1])
+    if isinstance(edge, torch.Tensor) and edge.device == device:
+        eg = edge.detach().to(torch.float32).contiguous()
+        if tuple(eg.shape) != (4, D):
+            raise ValueError(f"{name}: edge {(4, D)} expected, got {tuple(eg.shape)}")
+    else:
+        eg = torch.from_numpy(_host_table(name, "edge", edge, (4, D))).to(device)
+    if D > duration_posteriors_info()[0]:
+        raise ValueError(f"{name}: max_duration {D} is over the limit of {duration_posteriors_info()[0]}")
+    return dur, eg
+
+
+def _duration_posteriors_run(data, offs, a_pi, dur, edge, labels=None, tables_grad: bool = False, want_onsets: bool = False):
+    """One ``hssfsst_posteriors_durations`` call on the current stream -> ``(gamma, loglik, score, xi, s0, onsets)``; ``score``
+    only with ``labels`` (a uint8 arena on the device), ``xi`` and ``s0`` only with ``tables_grad``, ``onsets`` only when wanted;
+    None otherwise."""
+    L = _lib.lib()
+    _lib.guard_fork()
+    device = data.device
+    count, total, D = len(offs) - 1, offs[-1], int(dur.shape[1])
+    f64 = dict(dtype=torch.float64, device=device)
+    gamma = torch.empty((total, 4), dtype=torch.float32, device=device)
+    onsets = torch.empty((total, 4), dtype=torch.float32, device=device) if want_onsets else None
+    loglik = torch.empty((count,), **f64)
+    score = torch.empty((count,), **f64) if labels is not None else None
+    xi = torch.empty((count, 16), **f64) if tables_grad else None
+    s0 = torch.empty((count, 4), **f64) if tables_grad else None
+    if count:
+        _, _, _, per, rec, per_d = duration_posteriors_info()
+        work = torch.empty((per * total + rec * count + per_d * D,), dtype=torch.uint8, device=device)
+        o = np.asarray(offs, dtype=np.int64)
+        opt = lambda t: t.data_ptr() if t is not None else None       # noqa: E731
+        with torch.cuda.device(device):
+            stream = torch.cuda.current_stream(device).cuda_stream
+            _lib.check(L.hssfsst_posteriors_durations(data.data_ptr(), o.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), count, a_pi.data_ptr(),
+                                                      dur.data_ptr(), edge.data_ptr(), D, opt(labels), gamma.data_ptr(), opt(onsets),
+                                                      loglik.data_ptr(), opt(score), opt(xi), opt(s0), work.data_ptr(), work.numel(),
+                                                      device.index, stream),
+                       "hssfsst_posteriors_durations")
+    return gamma, loglik, score, xi, s0, onsets
+
+
+def duration_posteriors(logp, durations, transitions=None, initial=None, edge=None, return_loglik: bool = False,
+                        return_onsets: bool = False):
+    """Forward-backward under the explicit-duration (semi-Markov) model of ``decode_durations``
+    (``hssfsst_posteriors_durations``): log-probs -> ``gamma_t(j) = P(state_t = j | the whole recording, the tables)``, summed over
+    every segmentation into runs of 1 .. D steps that ``decode_durations`` picks the best of.  ``durations`` (4, D), ``edge``
+    (default ``edge_durations(durations)``), ``transitions`` (diagonal ignored), ``initial``: as for ``decode_durations``; numpy
+    arrays or tensors, those on the host are uploaded; none is read back, except a ``durations`` on the device given without an
+    ``edge``, from which the default ``edge`` is made on the host.
+
+    ``logp``: ``decode_states``' three kinds.  Returns the same kind in float32, like ``state_posteriors``.
+    ``return_loglik=True``: also ``logZ``, float64 ``(B,)`` on the device (0-d for ``(T, 4)``).  ``return_onsets=True``: also the
+    run-onset posteriors ``S_t(j) = P(a run of j starts at step t)`` in the kind of ``gamma`` -- where the S1 onset is, and how
+    sure.  The order is ``(gamma[, logZ][, onsets])``.  One call on the current stream, nothing waits for the device.  Not
+    differentiable (see ``duration_nll``).
+
+    float64 mantissas with integer exponents inside (include/hssfsst.h): nothing underflows, the prefix sums of the emissions must
+    stay within +-3.7e8, and the relative error grows with them (x 2^-53).  An emission of ``-inf`` or NaN counts as -32768, as in
+    ``decode_durations``; a recording no segmentation fits gets ``logZ = -inf`` and ``gamma = 0``."""
+    name = "duration_posteriors"
+    data, offs, kind = _decode_input(name, logp)
+    A, pi = _posterior_tables(name, transitions, initial, data.device)
+    dur, eg = _duration_tables(name, durations, edge, data.device)
+    gamma, loglik, _, _, _, onsets = _duration_posteriors_run(data.detach().contiguous(), offs, _a_pi(A, pi), dur, eg,
+                                                              want_onsets=return_onsets)
+
+    def shaped(t):
+        if kind == "ragged":
+            return RaggedFeatures(t, torch.tensor(offs, dtype=torch.int64), 4, False)
+        return t.view(int(logp.shape[0]), int(logp.shape[1]), 4) if kind == "batch" else t
+    out = [shaped(gamma)]
+    if return_loglik:
+        out.append(loglik[0] if kind == "single" else loglik)
+    if return_onsets:
+        out.append(shaped(onsets))
+    return out[0] if len(out) == 1 else tuple(out)
+
+
+class _DurationNLL(torch.autograd.Function):
+    """``(B,)`` float64 ``logZ - score(labels)`` from one ``hssfsst_posteriors_durations`` call; the backward is a scale of what
+    that call left: ``gamma - onehot``, ``Xi - counts(label runs)``, ``S_0 - onehot_0``."""
+
+    @staticmethod
+    def forward(ctx, data, A, pi, dur, edge, labels, offs):
+        tables_grad = A.requires_grad or pi.requires_grad
+        gamma, loglik, score, xi, s0, _ = _duration_posteriors_run(data.detach().contiguous(), offs, _a_pi(A, pi), dur, edge, labels, tables_grad)
+        ctx.offs = offs
+        ctx.tables_grad = tables_grad
+        ctx.dtypes = (A.dtype, pi.dtype)
+        forbidden = torch.isinf(A.detach()) | torch.eye(4, dtype=torch.bool, device=A.device)      # (the diagonal is never read)
+        ctx.save_for_backward(gamma, xi, s0, forbidden, torch.isinf(pi.detach()))
+        return loglik - score
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        gamma, xi, s0, a_forbidden, pi_forbidden = ctx.saved_tensors
+        offs = ctx.offs
+        g = g.to(torch.float64)
+        d_data = d_A = d_pi = None
+        if ctx.needs_input_grad[0]:
+            lens = torch.tensor([offs[i + 1] - offs[i] for i in range(len(offs) - 1)], dtype=torch.int64).to(g.device, non_blocking=True)
+            per_step = torch.repeat_interleave(g, lens, output_size=offs[-1])
+            d_data = (gamma.to(torch.float64) * per_step[:, None]).to(torch.float32)
+        if ctx.tables_grad and ctx.needs_input_grad[1]:
+            d_A = (xi * g[:, None]).sum(dim=0).view(4, 4).masked_fill(a_forbidden, 0.0).to(ctx.dtypes[0])
+        if ctx.tables_grad and ctx.needs_input_grad[2]:
+            d_pi = (s0 * g[:, None]).sum(dim=0).masked_fill(pi_forbidden, 0.0).to(ctx.dtypes[1])
+        return d_data, d_A, d_pi, None, None, None, None
+
+
+def duration_nll(logp, labels, durations, transitions=None, initial=None, edge=None, reduction: str = "mean"):
+    """The semi-Markov sequence loss ``logZ - score(labels)`` under the model ``decode_durations`` decodes with
+    (``hssfsst_posteriors_durations``): the negative log-probability of the labelled segmentation -- the runs of equal labels --
+    given the tables and the emissions.  Where ``sequence_nll`` trains against a first-order chain, under which the decoder's
+    minimum run costs nothing, this one trains against the duration scores.  ``+inf`` where a labelled run is longer than D or
+    forbidden by a table.
+
+    ``logp``, ``labels``, ``reduction`` and the value's dtype: as for ``sequence_nll``.  ``durations``, ``edge``, ``transitions``,
+    ``initial``: as for ``duration_posteriors``.  Differentiable (once) in ``logp`` and, where they are tensors on the log-probs'
+    device that require grad, in ``transitions`` (the diagonal and forbidden entries get gradient 0) and ``initial``.  The duration
+    tables are constants: a ``durations`` or ``edge`` that requires grad raises ValueError.  The forward is one kernel call; the
+    backward launches nothing beyond scaling what the forward left."""
+    name = "duration_nll"
+    if reduction not in ("mean", "sum", "none"):
+        raise ValueError(f"{name}: reduction 'mean', 'sum' or 'none' expected, got {reduction!r}")
+    data, offs, kind = _decode_input(name, logp)
+    A, pi = _posterior_tables(name, transitions, initial, data.device)
+    dur, eg = _duration_tables(name, durations, edge, data.device)
+    arena = _nll_labels(name, labels, offs, kind, data.device)
+    nll = _DurationNLL.apply(data, A, pi, dur, eg, arena, offs)
     if reduction == "none":
         return nll
     if reduction == "sum":

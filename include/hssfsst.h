@@ -506,6 +506,51 @@ int hssfsst_posteriors(const float* logp, const int64_t* offsets, int64_t count,
  * workspace size.  Any pointer may be NULL. */
 int hssfsst_posteriors_info(int* segment_steps, int64_t* max_steps, int64_t* work_bytes_per_step, int64_t* work_bytes_per_recording);
 
+/* Forward-backward under the explicit-duration (semi-Markov) model of hssfsst_decode_durations, un-quantised: the sum over all
+ * segmentations where the decoder takes the best one (csrc/segmenter_duration_posteriors.hpp; the arithmetic, the sequential loop
+ * that is the specification and the kernel's geometry as plain functions: csrc/duration_posterior_layout.hpp).  Stateless.  logp,
+ * offsets, count, labels, loglik, work, device, stream: as for hssfsst_posteriors.  Further
+ *   a_pi          20 float32, DEVICE: A (4, 4) row-major, then pi (4); the DIAGONAL of A IS IGNORED; -inf (or NaN) = forbidden
+ *   durations     dur (4, max_duration) float32, DEVICE: dur[j][d - 1] = log score of an interior run of state j lasting d steps
+ *   edge          (4, max_duration) float32, DEVICE: the same for the first and the last run of a recording
+ *   max_duration  D, 1 .. 2048
+ *   gamma         (sum T, 4) float32, DEVICE, 16-byte aligned: gamma_t[j] = P(state_t = j | the recording, the tables), clamped to
+ *                 [0, 1]; WITH labels gamma - onehot(labels)
+ *   onsets        (sum T, 4) float32, DEVICE, 16-byte aligned, or NULL: S_t[j] = P(a run of j starts at step t | ...); never changed
+ *                 by labels
+ *   score         (count) float64, DEVICE, or NULL: the log weight of the labelled segmentation (the runs of equal labels), -inf if
+ *                 a labelled run is longer than D or uses a forbidden entry; needs labels
+ *   xi            (count, 16) float64, DEVICE, or NULL: Xi[i][j] = the expected number of run changes i -> j (diagonal 0), the
+ *                 gradient of logZ in A; WITH labels Xi - counts(label runs)
+ *   s0            (count, 4) float64, DEVICE, or NULL: S_0, the step-0 posterior, the gradient of logZ in pi; WITH labels minus
+ *                 onehot(labels[0])
+ *   work          DEVICE, 16-byte aligned, work_bytes >= work_bytes_per_step x sum T + work_bytes_per_recording x count +
+ *                 work_bytes_per_duration x D (hssfsst_posteriors_durations_info); contents undefined afterwards
+ * The weight of a segmentation (s_1, d_1) .. (s_K, d_K) is hssfsst_decode_durations' without the quantiser:
+ *   pi[s_1] + sum_k len_k + sum_k A[s_k][s_(k+1)] + sum_t e[t][s(t)],  len_k = edge for k = 1 and k = K, dur otherwise,
+ * and an emission of -inf or NaN counts as -32768 (the decoder's rule).  logZ is the log of the sum of exp(weight).
+ * Arithmetic: linear domain; every quantity is a float64 mantissa with a 32-bit exponent, exp(x) enters as the floor of x / ln 2 and the exponential
+ * of what is left (a fixed polynomial, the same bits on host and device), sums align exponents with ldexp, the order of every sum is fixed (the sources of a ring word arrive in order
+ * of falling duration).  THE LIMITS: the prefix sums sum_(u<t) e[u][j] must stay within +-3.7e8 (emissions within +-350 at 2^20
+ * steps; at most ~11 000 -inf / NaN emissions of one state in a recording), and the relative error of the outputs grows with
+ * |prefix sum| x 2^-53.  Nothing else underflows.  A recording no segmentation fits gets logZ = -inf, gamma = 0, Xi = 0.
+ * HSSFSST_EINVAL before any device work: a NULL pointer other than labels, onsets, score, xi, s0; labels NULL while score is not;
+ * count < 0; bad offsets; max_duration outside 1 .. 2048; device < 0; logp, gamma, onsets or work not 16-byte aligned, a table not
+ * 4-byte, loglik, score, xi or s0 not 8-byte aligned; a work that is too small.  HSSFSST_EUNSUPPORTED: a recording of more than
+ * 2^20 steps, more than 2^31 - 1 steps in all.  count == 0 returns 0 and does nothing.  The tables' values are not checked.
+ * A recording's outputs do not depend on its neighbours or its place in the list, bit for bit, and two calls give the same bits.
+ * Enqueued on `stream` without synchronising and without reading a table on the host: one small launch that turns dur and edge
+ * into the linear tables at the head of the workspace, then one launch per 256 recordings, one workgroup of 512 lanes per recording
+ * (a single long recording uses one CU; each step costs O(4 D) twice), 129 KiB of LDS, no scratch memory. */
+int hssfsst_posteriors_durations(const float* logp, const int64_t* offsets, int64_t count, const float* a_pi, const float* durations,
+                                 const float* edge, int max_duration, const uint8_t* labels, float* gamma, float* onsets, double* loglik,
+                                 double* score, double* xi, double* s0, void* work, int64_t work_bytes, int device, void* stream);
+
+/* Its geometry and limits, no device needed: max_duration = the largest D (2048), segment_steps = steps staged at a time (256),
+ * max_steps = the longest recording (2^20), and the three factors of the workspace size (49, 32, 96).  Any pointer may be NULL. */
+int hssfsst_posteriors_durations_info(int* max_duration, int* segment_steps, int64_t* max_steps, int64_t* work_bytes_per_step,
+                                      int64_t* work_bytes_per_recording, int64_t* work_bytes_per_duration);
+
 /* One DIFFERENTIABLE bidirectional LSTM layer (batch first, nn.LSTM's cell and gate order): the unit a training program stacks
  * under autograd -- the segmenter is two of them.  The plan holds the layer's current weights in the kernels' layouts and the
  * scratch of its calls; the caller owns inputs, outputs and the stash.  Every pointer below is a DEVICE pointer on the plan's
