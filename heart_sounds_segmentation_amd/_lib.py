@@ -309,6 +309,11 @@ def lib():
         L.hssfsst_posteriors_durations.argtypes = [vp, ctypes.POINTER(c_i64), c_i64, vp, vp, vp, c_int, vp, vp, vp, vp, vp, vp, vp, vp, c_i64,
                                                    c_int, vp]
         L.hssfsst_posteriors_durations.restype = c_int
+        L.hssfsst_posteriors_durations_counts_info.argtypes = [ctypes.POINTER(c_i64)] * 3 + [ip]
+        L.hssfsst_posteriors_durations_counts_info.restype = c_int
+        L.hssfsst_posteriors_durations_counts.argtypes = [vp, ctypes.POINTER(c_i64), c_i64, vp, vp, vp, c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                                          c_i64, c_int, vp]
+        L.hssfsst_posteriors_durations_counts.restype = c_int
         L.hssfsst_bilstm_create.argtypes = [ctypes.POINTER(vp), c_int, c_int, c_int]
         L.hssfsst_bilstm_create.restype = c_int
         L.hssfsst_bilstm_destroy.argtypes = [vp]

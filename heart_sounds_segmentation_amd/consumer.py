@@ -835,6 +835,38 @@ def durations_from_labels(labels, max_duration: int, fit: str = "gaussian"):
     return out.astype(np.float32)
 
 
+def durations_from_counts(counts, fit: str = "gaussian"):
+    """The M-step to ``duration_posteriors(..., return_counts=True)``'s E-step, mirroring ``durations_from_labels``: ``dur``
+    (4, D) float32 from expected run-length counts ``(4, D)``, or ``(2, 4, D)`` of which the INTERIOR table ``counts[0]`` is used
+    (the first and the last run of a recording are cut off by its ends) -- sum the counts of a corpus over its recordings first.
+    A tensor or an array; negative entries (rounding) count as 0.  ``fit="gaussian"``: ``gaussian_durations`` of each state's mean
+    and standard deviation of d under its counts (population; at least half a step); ``fit="histogram"``: the log of the relative
+    mass, ``-inf`` where there is none.  A state without mass raises ValueError.  The scores are not a normalised generative
+    model: iterating this with the E-step is the caller's loop, and no convergence is promised."""
+    if fit not in ("gaussian", "histogram"):
+        raise ValueError(f"durations_from_counts: fit 'gaussian' or 'histogram' expected, got {fit!r}")
+    c = np.asarray(counts.detach().cpu().numpy() if isinstance(counts, torch.Tensor) else counts, dtype=np.float64)
+    if c.ndim == 3 and c.shape[0] == 2:
+        c = c[0]
+    if c.ndim != 2 or c.shape[0] != 4 or c.shape[1] < 1:
+        raise ValueError(f"durations_from_counts: counts (4, D) or (2, 4, D) expected, got {c.shape}")
+    if np.isnan(c).any():
+        raise ValueError("durations_from_counts: counts hold NaN")
+    c = np.maximum(c, 0.0)
+    D = c.shape[1]
+    mass = c.sum(axis=1)
+    if not (mass > 0).all():
+        raise ValueError(f"durations_from_counts: state {int(np.flatnonzero(~(mass > 0))[0])} has no mass")
+    p = c / mass[:, None]
+    if fit == "gaussian":
+        d = np.arange(1, D + 1, dtype=np.float64)
+        mean = (p * d).sum(axis=1)
+        std = np.sqrt((p * (d[None, :] - mean[:, None]) ** 2).sum(axis=1))
+        return gaussian_durations(mean, np.maximum(std, 0.5), D)
+    with np.errstate(divide="ignore"):
+        return np.log(p).astype(np.float32)
+
+
 def decode_durations(logp, durations, transitions=None, initial=None, edge=None, return_scores: bool = False):
     """Explicit-duration (semi-Markov) Viterbi decoding on the device (``hssfsst_decode_durations``): ``decode_states`` with a
     log score ``durations[j][d - 1]`` for an interior run of state j lasting d = 1 .. D steps, D = ``durations.shape[1]`` <= 2048;
@@ -1084,6 +1116,32 @@ def duration_posteriors_info():
     return D.value, seg.value, mx.value, per.value, rec.value, dur.value
 
 
+def duration_counts_info():
+    """``(work_bytes_per_step, work_bytes_per_recording, work_bytes_per_duration, durations_per_group)`` of the run-length counts
+    call (``hssfsst_posteriors_durations_counts_info``); the other limits are ``duration_posteriors_info()``'s.  No device needed."""
+    per, rec, dur, grp = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int(0)
+    _lib.check(_lib.lib().hssfsst_posteriors_durations_counts_info(ctypes.byref(per), ctypes.byref(rec), ctypes.byref(dur), ctypes.byref(grp)),
+               "hssfsst_posteriors_durations_counts_info")
+    return per.value, rec.value, dur.value, grp.value
+
+
+def _learnable_duration_tables(name: str, durations, edge, device):
+    """``duration_nll(learn_durations=True)``: both tables are given as ``(4, D)`` tensors on ``device``, float32 or float64, and
+    either may require grad; they are returned as they are (the autograd function rounds them to float32 for the kernel)."""
+    for what, v in (("durations", durations), ("edge", edge)):
+        if not isinstance(v, torch.Tensor) or v.device != device or v.dtype not in (torch.float32, torch.float64):
+            raise ValueError(f"{name}: with learn_durations, {what} must be a float32 or float64 tensor on {device}"
+                             + (" (no default edge is made: tie it to durations in torch if that is wanted)" if v is None else ""))
+    if durations.dim() != 2 or durations.shape[0] != 4 or durations.shape[1] < 1:
+        raise ValueError(f"{name}: durations (4, D) expected, got {tuple(durations.shape)}")
+    D = int(durations.shape[1])
+    if tuple(edge.shape) != (4, D):
+        raise ValueError(f"{name}: edge {(4, D)} expected, got {tuple(edge.shape)}")
+    if D > duration_posteriors_info()[0]:
+        raise ValueError(f"{name}: max_duration {D} is over the limit of {duration_posteriors_info()[0]}")
+    return durations, edge
+
+
 def _duration_tables(name: str, durations, edge, device):
     """``dur``, ``edge`` (default ``edge_durations(dur)``) -> two contiguous float32 ``(4, D)`` tensors on ``device``.  They are
     constants of the model: one that requires grad raises ValueError."""
@@ -1111,10 +1169,12 @@ def _duration_tables(name: str, durations, edge, device):
     return dur, eg
 
 
-def _duration_posteriors_run(data, offs, a_pi, dur, edge, labels=None, tables_grad: bool = False, want_onsets: bool = False):
-    """One ``hssfsst_posteriors_durations`` call on the current stream -> ``(gamma, loglik, score, xi, s0, onsets)``; ``score``
-    only with ``labels`` (a uint8 arena on the device), ``xi`` and ``s0`` only with ``tables_grad``, ``onsets`` only when wanted;
-    None otherwise."""
+def _duration_posteriors_run(data, offs, a_pi, dur, edge, labels=None, tables_grad: bool = False, want_onsets: bool = False,
+                             want_counts: bool = False):
+    """One ``hssfsst_posteriors_durations`` call on the current stream -> ``(gamma, loglik, score, xi, s0, onsets, counts)``;
+    ``score`` only with ``labels`` (a uint8 arena on the device), ``xi`` and ``s0`` only with ``tables_grad``, ``onsets`` only when
+    wanted; None otherwise.  ``want_counts``: one ``hssfsst_posteriors_durations_counts`` call instead, and ``counts``
+    ``(count, 2, 4, D)`` float64."""
     L = _lib.lib()
     _lib.guard_fork()
     device = data.device
@@ -1126,23 +1186,26 @@ def _duration_posteriors_run(data, offs, a_pi, dur, edge, labels=None, tables_gr
     score = torch.empty((count,), **f64) if labels is not None else None
     xi = torch.empty((count, 16), **f64) if tables_grad else None
     s0 = torch.empty((count, 4), **f64) if tables_grad else None
+    counts = torch.empty((count, 2, 4, D), **f64) if want_counts else None
     if count:
-        _, _, _, per, rec, per_d = duration_posteriors_info()
+        per, rec, per_d = duration_counts_info()[:3] if want_counts else duration_posteriors_info()[3:]
         work = torch.empty((per * total + rec * count + per_d * D,), dtype=torch.uint8, device=device)
         o = np.asarray(offs, dtype=np.int64)
         opt = lambda t: t.data_ptr() if t is not None else None       # noqa: E731
         with torch.cuda.device(device):
             stream = torch.cuda.current_stream(device).cuda_stream
-            _lib.check(L.hssfsst_posteriors_durations(data.data_ptr(), o.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), count, a_pi.data_ptr(),
-                                                      dur.data_ptr(), edge.data_ptr(), D, opt(labels), gamma.data_ptr(), opt(onsets),
-                                                      loglik.data_ptr(), opt(score), opt(xi), opt(s0), work.data_ptr(), work.numel(),
-                                                      device.index, stream),
-                       "hssfsst_posteriors_durations")
-    return gamma, loglik, score, xi, s0, onsets
+            head = (data.data_ptr(), o.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), count, a_pi.data_ptr(), dur.data_ptr(), edge.data_ptr(), D,
+                    opt(labels), gamma.data_ptr(), opt(onsets), loglik.data_ptr(), opt(score), opt(xi), opt(s0))
+            tail = (work.data_ptr(), work.numel(), device.index, stream)
+            if want_counts:
+                _lib.check(L.hssfsst_posteriors_durations_counts(*head, counts.data_ptr(), *tail), "hssfsst_posteriors_durations_counts")
+            else:
+                _lib.check(L.hssfsst_posteriors_durations(*head, *tail), "hssfsst_posteriors_durations")
+    return gamma, loglik, score, xi, s0, onsets, counts
 
 
 def duration_posteriors(logp, durations, transitions=None, initial=None, edge=None, return_loglik: bool = False,
-                        return_onsets: bool = False):
+                        return_onsets: bool = False, return_counts: bool = False):
     """Forward-backward under the explicit-duration (semi-Markov) model of ``decode_durations``
     (``hssfsst_posteriors_durations``): log-probs -> ``gamma_t(j) = P(state_t = j | the whole recording, the tables)``, summed over
     every segmentation into runs of 1 .. D steps that ``decode_durations`` picks the best of.  ``durations`` (4, D), ``edge``
@@ -1153,8 +1216,12 @@ def duration_posteriors(logp, durations, transitions=None, initial=None, edge=No
     ``logp``: ``decode_states``' three kinds.  Returns the same kind in float32, like ``state_posteriors``.
     ``return_loglik=True``: also ``logZ``, float64 ``(B,)`` on the device (0-d for ``(T, 4)``).  ``return_onsets=True``: also the
     run-onset posteriors ``S_t(j) = P(a run of j starts at step t)`` in the kind of ``gamma`` -- where the S1 onset is, and how
-    sure.  The order is ``(gamma[, logZ][, onsets])``.  One call on the current stream, nothing waits for the device.  Not
-    differentiable (see ``duration_nll``).
+    sure.  ``return_counts=True`` (``hssfsst_posteriors_durations_counts``): also the expected run-length counts, float64
+    ``(B, 2, 4, D)`` on the device (``(2, 4, D)`` for ``(T, 4)``): ``counts[.., 0, j, d - 1]`` = the expected number of interior runs
+    of state j lasting exactly d steps, ``counts[.., 1, j, d - 1]`` the same for the first and the last run -- the gradients of logZ
+    in ``durations`` and ``edge``, and what ``durations_from_counts`` fits a new table to; 64 D bytes per recording (128 KiB at
+    D = 2048).  The order is ``(gamma[, logZ][, onsets][, counts])``.  One call on the current stream, nothing waits for the
+    device.  Not differentiable (see ``duration_nll``).
 
     float64 mantissas with integer exponents inside (include/hssfsst.h): nothing underflows, the prefix sums of the emissions must
     stay within +-3.7e8, and the relative error grows with them (x 2^-53).  An emission of ``-inf`` or NaN counts as -32768, as in
@@ -1163,8 +1230,8 @@ def duration_posteriors(logp, durations, transitions=None, initial=None, edge=No
     data, offs, kind = _decode_input(name, logp)
     A, pi = _posterior_tables(name, transitions, initial, data.device)
     dur, eg = _duration_tables(name, durations, edge, data.device)
-    gamma, loglik, _, _, _, onsets = _duration_posteriors_run(data.detach().contiguous(), offs, _a_pi(A, pi), dur, eg,
-                                                              want_onsets=return_onsets)
+    gamma, loglik, _, _, _, onsets, counts = _duration_posteriors_run(data.detach().contiguous(), offs, _a_pi(A, pi), dur, eg,
+                                                                      want_onsets=return_onsets, want_counts=return_counts)
 
     def shaped(t):
         if kind == "ragged":
@@ -1175,31 +1242,39 @@ def duration_posteriors(logp, durations, transitions=None, initial=None, edge=No
         out.append(loglik[0] if kind == "single" else loglik)
     if return_onsets:
         out.append(shaped(onsets))
+    if return_counts:
+        out.append(counts[0] if kind == "single" else counts)
     return out[0] if len(out) == 1 else tuple(out)
 
 
 class _DurationNLL(torch.autograd.Function):
     """``(B,)`` float64 ``logZ - score(labels)`` from one ``hssfsst_posteriors_durations`` call; the backward is a scale of what
-    that call left: ``gamma - onehot``, ``Xi - counts(label runs)``, ``S_0 - onehot_0``."""
+    that call left: ``gamma - onehot``, ``Xi - counts(label runs)``, ``S_0 - onehot_0`` and, where a duration table requires grad
+    (``learn_durations``), the run-length counts less the label runs' (``hssfsst_posteriors_durations_counts``)."""
 
     @staticmethod
     def forward(ctx, data, A, pi, dur, edge, labels, offs):
         tables_grad = A.requires_grad or pi.requires_grad
-        gamma, loglik, score, xi, s0, _ = _duration_posteriors_run(data.detach().contiguous(), offs, _a_pi(A, pi), dur, edge, labels, tables_grad)
+        durations_grad = dur.requires_grad or edge.requires_grad
+        d32, e32 = (t.detach().to(torch.float32).contiguous() for t in (dur, edge))
+        gamma, loglik, score, xi, s0, _, counts = _duration_posteriors_run(data.detach().contiguous(), offs, _a_pi(A, pi), d32, e32, labels,
+                                                                           tables_grad, want_counts=durations_grad)
         ctx.offs = offs
         ctx.tables_grad = tables_grad
-        ctx.dtypes = (A.dtype, pi.dtype)
+        ctx.durations_grad = durations_grad
+        ctx.dtypes = (A.dtype, pi.dtype, dur.dtype, edge.dtype)
         forbidden = torch.isinf(A.detach()) | torch.eye(4, dtype=torch.bool, device=A.device)      # (the diagonal is never read)
-        ctx.save_for_backward(gamma, xi, s0, forbidden, torch.isinf(pi.detach()))
+        none = torch.isinf(torch.stack([d32, e32])) if durations_grad else None
+        ctx.save_for_backward(gamma, xi, s0, forbidden, torch.isinf(pi.detach()), counts, none)
         return loglik - score
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
-        gamma, xi, s0, a_forbidden, pi_forbidden = ctx.saved_tensors
+        gamma, xi, s0, a_forbidden, pi_forbidden, counts, dur_forbidden = ctx.saved_tensors
         offs = ctx.offs
         g = g.to(torch.float64)
-        d_data = d_A = d_pi = None
+        d_data = d_A = d_pi = d_dur = d_edge = None
         if ctx.needs_input_grad[0]:
             lens = torch.tensor([offs[i + 1] - offs[i] for i in range(len(offs) - 1)], dtype=torch.int64).to(g.device, non_blocking=True)
             per_step = torch.repeat_interleave(g, lens, output_size=offs[-1])
@@ -1208,10 +1283,17 @@ class _DurationNLL(torch.autograd.Function):
             d_A = (xi * g[:, None]).sum(dim=0).view(4, 4).masked_fill(a_forbidden, 0.0).to(ctx.dtypes[0])
         if ctx.tables_grad and ctx.needs_input_grad[2]:
             d_pi = (s0 * g[:, None]).sum(dim=0).masked_fill(pi_forbidden, 0.0).to(ctx.dtypes[1])
-        return d_data, d_A, d_pi, None, None, None, None
+        if ctx.durations_grad and (ctx.needs_input_grad[3] or ctx.needs_input_grad[4]):
+            both = (counts * g[:, None, None, None]).sum(dim=0).masked_fill(dur_forbidden, 0.0)
+            if ctx.needs_input_grad[3]:
+                d_dur = both[0].to(ctx.dtypes[2])
+            if ctx.needs_input_grad[4]:
+                d_edge = both[1].to(ctx.dtypes[3])
+        return d_data, d_A, d_pi, d_dur, d_edge, None, None
 
 
-def duration_nll(logp, labels, durations, transitions=None, initial=None, edge=None, reduction: str = "mean"):
+def duration_nll(logp, labels, durations, transitions=None, initial=None, edge=None, reduction: str = "mean",
+                 learn_durations: bool = False):
     """The semi-Markov sequence loss ``logZ - score(labels)`` under the model ``decode_durations`` decodes with
     (``hssfsst_posteriors_durations``): the negative log-probability of the labelled segmentation -- the runs of equal labels --
     given the tables and the emissions.  Where ``sequence_nll`` trains against a first-order chain, under which the decoder's
@@ -1220,15 +1302,22 @@ def duration_nll(logp, labels, durations, transitions=None, initial=None, edge=N
 
     ``logp``, ``labels``, ``reduction`` and the value's dtype: as for ``sequence_nll``.  ``durations``, ``edge``, ``transitions``,
     ``initial``: as for ``duration_posteriors``.  Differentiable (once) in ``logp`` and, where they are tensors on the log-probs'
-    device that require grad, in ``transitions`` (the diagonal and forbidden entries get gradient 0) and ``initial``.  The duration
-    tables are constants: a ``durations`` or ``edge`` that requires grad raises ValueError.  The forward is one kernel call; the
-    backward launches nothing beyond scaling what the forward left."""
+    device that require grad, in ``transitions`` (the diagonal and forbidden entries get gradient 0) and ``initial``.  By default
+    the duration tables are constants: a ``durations`` or ``edge`` that requires grad raises ValueError.
+
+    ``learn_durations=True``: ``durations`` and ``edge`` are both given as ``(4, D)`` tensors on the log-probs' device, float32 or
+    float64, and either may require grad (no default ``edge`` is made: tie it to ``durations`` in torch if that is wanted, e.g.
+    ``edge=torch.flip(torch.cummax(torch.flip(dur, [1]), 1).values, [1])``).  Their gradients are the expected run-length counts
+    less the label runs' (``duration_posteriors(return_counts=True)``), in the table's dtype, 0 at ``-inf`` entries; the kernel
+    sees the tables rounded to float32.  The forward is then the counts call, which costs 64 D bytes per recording.
+
+    The forward is one call; the backward launches nothing beyond scaling what the forward left."""
     name = "duration_nll"
     if reduction not in ("mean", "sum", "none"):
         raise ValueError(f"{name}: reduction 'mean', 'sum' or 'none' expected, got {reduction!r}")
     data, offs, kind = _decode_input(name, logp)
     A, pi = _posterior_tables(name, transitions, initial, data.device)
-    dur, eg = _duration_tables(name, durations, edge, data.device)
+    dur, eg = (_learnable_duration_tables if learn_durations else _duration_tables)(name, durations, edge, data.device)
     arena = _nll_labels(name, labels, offs, kind, data.device)
     nll = _DurationNLL.apply(data, A, pi, dur, eg, arena, offs)
     if reduction == "none":

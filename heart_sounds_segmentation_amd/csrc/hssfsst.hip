@@ -47,6 +47,7 @@
 #include "posterior_layout.hpp"
 #include "segmenter_posteriors.hpp"
 #include "segmenter_duration_posteriors.hpp"
+#include "segmenter_duration_counts.hpp"
 #include "fsst_tables.hpp"
 
 namespace tables = hssfsst::tables;
@@ -2919,6 +2920,108 @@ int hssfsst_posteriors(const float* logp, const int64_t* offsets, int64_t count,
 // Forward-backward under the explicit-duration model (hssfsst.h: hssfsst_posteriors_durations;
 // csrc/segmenter_duration_posteriors.hpp).  Stateless: the launch's offsets travel as kernel arguments, kDurPostBatch recordings per
 // launch; all four tables are read from device memory, the two duration tables through a fill launch into the workspace's head.
+// hssfsst_posteriors_durations_counts is the same call with the runs variant of the sweeps (it also leaves g and 1 / Z in a
+// workspace that is larger by csrc/duration_counts_layout.hpp's parts) and, behind them, the counts launches
+// (csrc/segmenter_duration_counts.hpp).
+namespace {
+
+// both entries: `with_counts` is the second one, whose `counts` is required
+int posteriors_durations_run(const char* kEntry, bool with_counts, const float* logp, const int64_t* offsets, int64_t count, const float* a_pi,
+                             const float* durations, const float* edge, int max_duration, const uint8_t* labels, float* gamma, float* onsets,
+                             double* loglik, double* score, double* xi, double* s0, double* counts, void* work, int64_t work_bytes, int device,
+                             void* stream)
+{
+    namespace dp = hssfsst::dplayout;
+    namespace dc = hssfsst::dclayout;
+    auto misaligned = [](const void* p, unsigned a) { return reinterpret_cast<uintptr_t>(p) % a != 0; };
+    if (count < 0) return fail(HSSFSST_EINVAL, "%s: count %lld is negative", kEntry, static_cast<long long>(count));
+    if (!logp || !offsets || !a_pi || !durations || !edge || !gamma || !loglik || (with_counts && !counts) || !work)
+        return fail(HSSFSST_EINVAL, "%s: bad argument (%s is NULL)", kEntry,
+                    !logp ? "logp" : !offsets ? "offsets" : !a_pi ? "a_pi" : !durations ? "durations" : !edge ? "edge" : !gamma ? "gamma"
+                    : !loglik ? "loglik" : !work ? "work" : "counts");
+    if (score && !labels) return fail(HSSFSST_EINVAL, "%s: bad argument (labels is NULL while score is not)", kEntry);
+    if (device < 0) return fail(HSSFSST_EINVAL, "%s: device %d is negative", kEntry, device);
+    if (max_duration < 1 || max_duration > dp::kMaxDuration)
+        return fail(HSSFSST_EINVAL, "%s: max_duration %d is outside 1..%d", kEntry, max_duration, dp::kMaxDuration);
+    const int D = max_duration;
+    if (misaligned(logp, 16) || misaligned(gamma, 16) || misaligned(onsets, 16) || misaligned(work, 16))
+        return fail(HSSFSST_EINVAL, "%s: %s is not 16-byte aligned", kEntry,
+                    misaligned(logp, 16) ? "logp" : misaligned(gamma, 16) ? "gamma" : misaligned(onsets, 16) ? "onsets" : "work");
+    if (misaligned(a_pi, 4) || misaligned(durations, 4) || misaligned(edge, 4))
+        return fail(HSSFSST_EINVAL, "%s: %s is not 4-byte aligned", kEntry, misaligned(a_pi, 4) ? "a_pi" : misaligned(durations, 4) ? "durations" : "edge");
+    if (misaligned(loglik, 8) || misaligned(score, 8) || misaligned(xi, 8) || misaligned(s0, 8) || misaligned(counts, 8))
+        return fail(HSSFSST_EINVAL, "%s: %s is not 8-byte aligned", kEntry,
+                    misaligned(loglik, 8) ? "loglik" : misaligned(score, 8) ? "score" : misaligned(xi, 8) ? "xi" : misaligned(s0, 8) ? "s0" : "counts");
+    if (offsets[0] != 0) return fail(HSSFSST_EINVAL, "%s: offsets[0] is %lld, not 0", kEntry, static_cast<long long>(offsets[0]));
+    for (int64_t i = 0; i < count; ++i)
+        if (offsets[i + 1] <= offsets[i])
+            return fail(HSSFSST_EINVAL, "%s: offsets do not increase at index %lld (offsets[%lld] = %lld, offsets[%lld] = %lld)", kEntry,
+                        static_cast<long long>(i + 1), static_cast<long long>(i), static_cast<long long>(offsets[i]),
+                        static_cast<long long>(i + 1), static_cast<long long>(offsets[i + 1]));
+    for (int64_t i = 0; i < count; ++i)
+        if (offsets[i + 1] - offsets[i] > dp::kMaxSteps)
+            return fail(HSSFSST_EUNSUPPORTED, "%s: recording %lld has %lld steps, over the limit of %lld", kEntry, static_cast<long long>(i),
+                        static_cast<long long>(offsets[i + 1] - offsets[i]), static_cast<long long>(dp::kMaxSteps));
+    if (offsets[count] > 0x7fffffffLL)
+        return fail(HSSFSST_EUNSUPPORTED, "%s: %lld steps in all, over the limit of 2^31 - 1", kEntry, static_cast<long long>(offsets[count]));
+    const int64_t need = with_counts ? dc::workspace_bytes(offsets[count], count, D) : dp::workspace_bytes(offsets[count], count, D);
+    if (work_bytes < need)
+        return fail(HSSFSST_EINVAL, "%s: work of %lld bytes is too small: %lld steps in %lld recordings and max_duration %d need %lld", kEntry,
+                    static_cast<long long>(work_bytes), static_cast<long long>(offsets[count]), static_cast<long long>(count), D,
+                    static_cast<long long>(need));
+    if (count == 0) return 0;
+    if (int rc = check_device(kEntry, device)) return rc;
+    DEVICE_SCOPE(device);
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const dc::Workspace wc = dc::workspace(offsets[count], count, D);
+    const dp::Workspace& ws = wc.sweeps;                 // (dp::workspace(): the plain entry uses nothing behind it)
+    char* w = static_cast<char*>(work);
+    double* tabm = reinterpret_cast<double*>(w + ws.table_mant);
+    int* tabe = reinterpret_cast<int*>(w + ws.table_exp);
+    double* stash_m = reinterpret_cast<double*>(w + ws.stash_mant);
+    int* stash_e = reinterpret_cast<int*>(w + ws.stash_exp);
+    double* checkpoints = reinterpret_cast<double*>(w + ws.checkpoints);
+    hipLaunchKernelGGL(hssfsst::seg_duration_posteriors_fill_kernel,
+                       dim3(static_cast<unsigned>((8 * D + hssfsst::kDurPostFillLanes - 1) / hssfsst::kDurPostFillLanes)),
+                       dim3(hssfsst::kDurPostFillLanes), 0, st, durations, edge, tabm, tabe, D);
+    if (int rc = launch_check(kEntry, "seg_duration_posteriors_fill_kernel")) return rc;
+    hssfsst::DurPostArgs args{};
+    args.D = D;
+    auto runs_of = [&](int64_t r0) {                     // what the launch of the recordings r0 .. sees of the second stash
+        return hssfsst::DurRunsOut{reinterpret_cast<double*>(w + wc.g_mant), reinterpret_cast<int*>(w + wc.g_exp),
+                                   reinterpret_cast<double*>(w + wc.invz_mant) + r0, reinterpret_cast<int*>(w + wc.invz_exp) + r0};
+    };
+    for (int64_t r0 = 0; r0 < count; r0 += hssfsst::kDurPostBatch) {
+        const int nrec = static_cast<int>(std::min<int64_t>(hssfsst::kDurPostBatch, count - r0));
+        for (int i = 0; i <= nrec; ++i) args.off[i] = offsets[r0 + i];
+        args.rec0 = r0;
+        if (with_counts) {
+            hipLaunchKernelGGL(hssfsst::seg_duration_runs_sweep_kernel, dim3(static_cast<unsigned>(nrec)), dim3(dp::kLanes), 0, st, logp, a_pi,
+                               durations, edge, labels, gamma, onsets, loglik + r0, score ? score + r0 : nullptr, xi ? xi + 16 * r0 : nullptr,
+                               s0 ? s0 + 4 * r0 : nullptr, tabm, tabe, stash_m, stash_e, checkpoints, runs_of(r0), args);
+            if (int rc = launch_check(kEntry, "seg_duration_runs_sweep_kernel")) return rc;
+        } else {
+            hipLaunchKernelGGL(hssfsst::seg_duration_posteriors_kernel, dim3(static_cast<unsigned>(nrec)), dim3(dp::kLanes), 0, st, logp, a_pi,
+                               durations, edge, labels, gamma, onsets, loglik + r0, score ? score + r0 : nullptr, xi ? xi + 16 * r0 : nullptr,
+                               s0 ? s0 + 4 * r0 : nullptr, tabm, tabe, stash_m, stash_e, checkpoints, args);
+            if (int rc = launch_check(kEntry, "seg_duration_posteriors_kernel")) return rc;
+        }
+    }
+    if (!with_counts) return 0;
+    for (int64_t r0 = 0; r0 < count; r0 += hssfsst::kDurPostBatch) {
+        const int nrec = static_cast<int>(std::min<int64_t>(hssfsst::kDurPostBatch, count - r0));
+        for (int i = 0; i <= nrec; ++i) args.off[i] = offsets[r0 + i];
+        args.rec0 = r0;
+        hipLaunchKernelGGL(hssfsst::seg_duration_run_counts_kernel, dim3(static_cast<unsigned>(nrec), static_cast<unsigned>(dc::groups(D))),
+                           dim3(dc::kLanes), 0, st, logp, a_pi, labels, counts + dc::counts_index(r0, 0, 0, 1, D), tabm, tabe, stash_m, stash_e,
+                           checkpoints, runs_of(r0), args);
+        if (int rc = launch_check(kEntry, "seg_duration_run_counts_kernel")) return rc;
+    }
+    return 0;
+}
+
+}  // namespace
+
 extern "C" {
 
 int hssfsst_posteriors_durations_info(int* max_duration, int* segment_steps, int64_t* max_steps, int64_t* work_bytes_per_step,
@@ -2938,69 +3041,28 @@ int hssfsst_posteriors_durations(const float* logp, const int64_t* offsets, int6
                                  const float* edge, int max_duration, const uint8_t* labels, float* gamma, float* onsets, double* loglik,
                                  double* score, double* xi, double* s0, void* work, int64_t work_bytes, int device, void* stream)
 {
-    namespace dp = hssfsst::dplayout;
-    constexpr const char* kEntry = "posteriors_durations";
-    auto misaligned = [](const void* p, unsigned a) { return reinterpret_cast<uintptr_t>(p) % a != 0; };
-    if (count < 0) return fail(HSSFSST_EINVAL, "%s: count %lld is negative", kEntry, static_cast<long long>(count));
-    if (!logp || !offsets || !a_pi || !durations || !edge || !gamma || !loglik || !work)
-        return fail(HSSFSST_EINVAL, "%s: bad argument (%s is NULL)", kEntry,
-                    !logp ? "logp" : !offsets ? "offsets" : !a_pi ? "a_pi" : !durations ? "durations" : !edge ? "edge" : !gamma ? "gamma"
-                    : !loglik ? "loglik" : "work");
-    if (score && !labels) return fail(HSSFSST_EINVAL, "%s: bad argument (labels is NULL while score is not)", kEntry);
-    if (device < 0) return fail(HSSFSST_EINVAL, "%s: device %d is negative", kEntry, device);
-    if (max_duration < 1 || max_duration > dp::kMaxDuration)
-        return fail(HSSFSST_EINVAL, "%s: max_duration %d is outside 1..%d", kEntry, max_duration, dp::kMaxDuration);
-    const int D = max_duration;
-    if (misaligned(logp, 16) || misaligned(gamma, 16) || misaligned(onsets, 16) || misaligned(work, 16))
-        return fail(HSSFSST_EINVAL, "%s: %s is not 16-byte aligned", kEntry,
-                    misaligned(logp, 16) ? "logp" : misaligned(gamma, 16) ? "gamma" : misaligned(onsets, 16) ? "onsets" : "work");
-    if (misaligned(a_pi, 4) || misaligned(durations, 4) || misaligned(edge, 4))
-        return fail(HSSFSST_EINVAL, "%s: %s is not 4-byte aligned", kEntry, misaligned(a_pi, 4) ? "a_pi" : misaligned(durations, 4) ? "durations" : "edge");
-    if (misaligned(loglik, 8) || misaligned(score, 8) || misaligned(xi, 8) || misaligned(s0, 8))
-        return fail(HSSFSST_EINVAL, "%s: %s is not 8-byte aligned", kEntry,
-                    misaligned(loglik, 8) ? "loglik" : misaligned(score, 8) ? "score" : misaligned(xi, 8) ? "xi" : "s0");
-    if (offsets[0] != 0) return fail(HSSFSST_EINVAL, "%s: offsets[0] is %lld, not 0", kEntry, static_cast<long long>(offsets[0]));
-    for (int64_t i = 0; i < count; ++i)
-        if (offsets[i + 1] <= offsets[i])
-            return fail(HSSFSST_EINVAL, "%s: offsets do not increase at index %lld (offsets[%lld] = %lld, offsets[%lld] = %lld)", kEntry,
-                        static_cast<long long>(i + 1), static_cast<long long>(i), static_cast<long long>(offsets[i]),
-                        static_cast<long long>(i + 1), static_cast<long long>(offsets[i + 1]));
-    for (int64_t i = 0; i < count; ++i)
-        if (offsets[i + 1] - offsets[i] > dp::kMaxSteps)
-            return fail(HSSFSST_EUNSUPPORTED, "%s: recording %lld has %lld steps, over the limit of %lld", kEntry, static_cast<long long>(i),
-                        static_cast<long long>(offsets[i + 1] - offsets[i]), static_cast<long long>(dp::kMaxSteps));
-    if (offsets[count] > 0x7fffffffLL)
-        return fail(HSSFSST_EUNSUPPORTED, "%s: %lld steps in all, over the limit of 2^31 - 1", kEntry, static_cast<long long>(offsets[count]));
-    const int64_t need = dp::workspace_bytes(offsets[count], count, D);
-    if (work_bytes < need)
-        return fail(HSSFSST_EINVAL, "%s: work of %lld bytes is too small: %lld steps in %lld recordings and max_duration %d need %lld", kEntry,
-                    static_cast<long long>(work_bytes), static_cast<long long>(offsets[count]), static_cast<long long>(count), D,
-                    static_cast<long long>(need));
-    if (count == 0) return 0;
-    if (int rc = check_device(kEntry, device)) return rc;
-    DEVICE_SCOPE(device);
-    const hipStream_t st = static_cast<hipStream_t>(stream);
-    const dp::Workspace ws = dp::workspace(offsets[count], count, D);
-    char* w = static_cast<char*>(work);
-    double* tabm = reinterpret_cast<double*>(w + ws.table_mant);
-    int* tabe = reinterpret_cast<int*>(w + ws.table_exp);
-    hipLaunchKernelGGL(hssfsst::seg_duration_posteriors_fill_kernel,
-                       dim3(static_cast<unsigned>((8 * D + hssfsst::kDurPostFillLanes - 1) / hssfsst::kDurPostFillLanes)),
-                       dim3(hssfsst::kDurPostFillLanes), 0, st, durations, edge, tabm, tabe, D);
-    if (int rc = launch_check(kEntry, "seg_duration_posteriors_fill_kernel")) return rc;
-    hssfsst::DurPostArgs args{};
-    args.D = D;
-    for (int64_t r0 = 0; r0 < count; r0 += hssfsst::kDurPostBatch) {
-        const int nrec = static_cast<int>(std::min<int64_t>(hssfsst::kDurPostBatch, count - r0));
-        for (int i = 0; i <= nrec; ++i) args.off[i] = offsets[r0 + i];
-        args.rec0 = r0;
-        hipLaunchKernelGGL(hssfsst::seg_duration_posteriors_kernel, dim3(static_cast<unsigned>(nrec)), dim3(dp::kLanes), 0, st, logp, a_pi,
-                           durations, edge, labels, gamma, onsets, loglik + r0, score ? score + r0 : nullptr, xi ? xi + 16 * r0 : nullptr,
-                           s0 ? s0 + 4 * r0 : nullptr, tabm, tabe, reinterpret_cast<double*>(w + ws.stash_mant),
-                           reinterpret_cast<int*>(w + ws.stash_exp), reinterpret_cast<double*>(w + ws.checkpoints), args);
-        if (int rc = launch_check(kEntry, "seg_duration_posteriors_kernel")) return rc;
-    }
+    return posteriors_durations_run("posteriors_durations", false, logp, offsets, count, a_pi, durations, edge, max_duration, labels, gamma,
+                                    onsets, loglik, score, xi, s0, nullptr, work, work_bytes, device, stream);
+}
+
+int hssfsst_posteriors_durations_counts_info(int64_t* work_bytes_per_step, int64_t* work_bytes_per_recording, int64_t* work_bytes_per_duration,
+                                             int* durations_per_group)
+{
+    namespace dc = hssfsst::dclayout;
+    if (work_bytes_per_step) *work_bytes_per_step = dc::kWorkBytesPerStep;
+    if (work_bytes_per_recording) *work_bytes_per_recording = dc::kWorkBytesPerRecording;
+    if (work_bytes_per_duration) *work_bytes_per_duration = dc::kWorkBytesPerDuration;
+    if (durations_per_group) *durations_per_group = dc::kDurationsPerGroup;
     return 0;
+}
+
+int hssfsst_posteriors_durations_counts(const float* logp, const int64_t* offsets, int64_t count, const float* a_pi, const float* durations,
+                                        const float* edge, int max_duration, const uint8_t* labels, float* gamma, float* onsets,
+                                        double* loglik, double* score, double* xi, double* s0, double* counts, void* work, int64_t work_bytes,
+                                        int device, void* stream)
+{
+    return posteriors_durations_run("posteriors_durations_counts", true, logp, offsets, count, a_pi, durations, edge, max_duration, labels,
+                                    gamma, onsets, loglik, score, xi, s0, counts, work, work_bytes, device, stream);
 }
 
 }  // extern "C"

@@ -16,6 +16,8 @@
 //   from the workspace, its E(u) from the checkpoint and the staged emissions (lanes 0 .. 3, one state each, in the forward order).
 //   Every step forms N_u, the Xi terms, S_u and the running gamma; gamma and the onsets are staged and written float4 by float4.
 // A lane's state is a run-time number: vectors are indexed by selects (pick4) and unrolled loops, never by it: no scratch.
+// The body is seg_duration_sweeps<kRuns>; seg_duration_posteriors_kernel is its plain instantiation, and
+// seg_duration_runs_sweep_kernel the one that also stores g_u and 1 / Z for the run-length counts (segmenter_duration_counts.hpp).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -50,12 +52,26 @@ __global__ __launch_bounds__(kDurPostFillLanes) void seg_duration_posteriors_fil
     tabe[at] = x.e;
 }
 
-__global__ __launch_bounds__(dplayout::kLanes) void seg_duration_posteriors_kernel(
+// what the runs variant of the sweeps leaves for the counts kernel (segmenter_duration_counts.hpp; the layout is
+// csrc/duration_counts_layout.hpp's): g_u(j), u = T .. 1, in row u - 1 of a second stash, and 1 / Z of each recording of the launch
+struct DurRunsOut {
+    double* g_m;
+    int* g_e;
+    double* invz_m;
+    int* invz_e;
+};
+
+// Both sweeps of one recording.  kRuns: also leave DurRunsOut -- every other output is bit for bit that of the plain instantiation.
+// static and NOT __forceinline__: each instantiation has one caller, so the inliner folds it into its kernel anyway (no call is
+// left), but after the body has been simplified on its own -- which gives the plain kernel the code it had as a kernel body (the
+// same instruction mix to three instructions).  Forced inlining happens before that and cost 3.5 % at D = 2048 (more SGPR spills).
+template <bool kRuns>
+static __device__ void seg_duration_sweeps(
     const float* __restrict__ logp, const float* __restrict__ a_pi, const float* __restrict__ dur, const float* __restrict__ edge,
     const uint8_t* __restrict__ labels, float* __restrict__ gamma, float* __restrict__ onsets, double* __restrict__ loglik,
     double* __restrict__ score, double* __restrict__ xi_out, double* __restrict__ s0_out, const double* __restrict__ tabm,
     const int* __restrict__ tabe, double* __restrict__ stash_m, int* __restrict__ stash_e, double* __restrict__ checkpoints,
-    const DurPostArgs args)
+    const DurPostArgs& args, const DurRunsOut runs)
 {
     namespace dp = dplayout;
     using dp::i64;
@@ -199,6 +215,10 @@ __global__ __launch_bounds__(dplayout::kLanes) void seg_duration_posteriors_kern
     if (tid == 0) {
         loglik[blockIdx.x] = dp::log_of(Z);
         if (score) score[blockIdx.x] = sc;
+        if constexpr (kRuns) {
+            runs.invz_m[blockIdx.x] = invz.m;
+            runs.invz_e[blockIdx.x] = invz.e;
+        }
     }
 
     // ---- reverse sweep
@@ -276,6 +296,11 @@ __global__ __launch_bounds__(dplayout::kLanes) void seg_duration_posteriors_kern
         if (tid < 4) {
             gst[s][j] = static_cast<float>(dp::clamp01(gam));
             ost[s][j] = static_cast<float>(S);           // (row u; there is no row T: the flush leaves it out)
+            if constexpr (kRuns) {                       // g_u(j) into row u - 1 of the second stash
+                const i64 at = 4 * (base + r) + j;
+                runs.g_m[at] = g.m;
+                runs.g_e[at] = g.e;
+            }
         }
         push(g, cur, u, u == T);
         cur = cur + 1 == R ? 0 : cur + 1;
@@ -295,6 +320,29 @@ __global__ __launch_bounds__(dplayout::kLanes) void seg_duration_posteriors_kern
             }
         }
     }
+}
+
+__global__ __launch_bounds__(dplayout::kLanes) void seg_duration_posteriors_kernel(
+    const float* __restrict__ logp, const float* __restrict__ a_pi, const float* __restrict__ dur, const float* __restrict__ edge,
+    const uint8_t* __restrict__ labels, float* __restrict__ gamma, float* __restrict__ onsets, double* __restrict__ loglik,
+    double* __restrict__ score, double* __restrict__ xi_out, double* __restrict__ s0_out, const double* __restrict__ tabm,
+    const int* __restrict__ tabe, double* __restrict__ stash_m, int* __restrict__ stash_e, double* __restrict__ checkpoints,
+    const DurPostArgs args)
+{
+    seg_duration_sweeps<false>(logp, a_pi, dur, edge, labels, gamma, onsets, loglik, score, xi_out, s0_out, tabm, tabe, stash_m, stash_e,
+                               checkpoints, args, DurRunsOut{});
+}
+
+// the same two sweeps, which also leave g and 1 / Z for seg_duration_run_counts_kernel (hssfsst_posteriors_durations_counts)
+__global__ __launch_bounds__(dplayout::kLanes) void seg_duration_runs_sweep_kernel(
+    const float* __restrict__ logp, const float* __restrict__ a_pi, const float* __restrict__ dur, const float* __restrict__ edge,
+    const uint8_t* __restrict__ labels, float* __restrict__ gamma, float* __restrict__ onsets, double* __restrict__ loglik,
+    double* __restrict__ score, double* __restrict__ xi_out, double* __restrict__ s0_out, const double* __restrict__ tabm,
+    const int* __restrict__ tabe, double* __restrict__ stash_m, int* __restrict__ stash_e, double* __restrict__ checkpoints,
+    const DurRunsOut runs, const DurPostArgs args)
+{
+    seg_duration_sweeps<true>(logp, a_pi, dur, edge, labels, gamma, onsets, loglik, score, xi_out, s0_out, tabm, tabe, stash_m, stash_e,
+                              checkpoints, args, runs);
 }
 
 }  // namespace hssfsst

@@ -551,6 +551,38 @@ int hssfsst_posteriors_durations(const float* logp, const int64_t* offsets, int6
 int hssfsst_posteriors_durations_info(int* max_duration, int* segment_steps, int64_t* max_steps, int64_t* work_bytes_per_step,
                                       int64_t* work_bytes_per_recording, int64_t* work_bytes_per_duration);
 
+/* hssfsst_posteriors_durations, and with it the sufficient statistic of the two duration tables: the expected run-length counts
+ * (csrc/segmenter_duration_counts.hpp; arithmetic, ownership, workspace and the sequential loop that is the specification:
+ * csrc/duration_counts_layout.hpp).  The 18 arguments of hssfsst_posteriors_durations, with the same meaning and the same bits in
+ * every one of its outputs, and before work
+ *   counts        (count, 2, 4, max_duration) float64, DEVICE, 8-byte aligned, required:
+ *                 counts[i][0][j][d - 1] = E[number of INTERIOR runs of state j lasting exactly d steps | recording i, the tables],
+ *                 counts[i][1][j][d - 1] = the same for the first and the last run (those edge scores) -- the gradients of logZ in
+ *                 durations and in edge, the E-step of the explicit-duration Baum-Welch; WITH labels counts - counts(label runs):
+ *                 a labelled run of d <= max_duration steps takes 1 off its entry, a longer one (score = -inf) takes nothing off.
+ *                 THE COST: 64 x max_duration bytes per recording -- 128 KiB per recording at max_duration 2048, 100 MiB for 792
+ *                 recordings -- whatever their lengths.
+ *   work          as there, with the factors of hssfsst_posteriors_durations_counts_info (97, 48, 96): the sweeps also leave
+ *                 g_u (48 bytes a step) and 1 / Z
+ * The posterior of the run of j that starts at step t and lasts d steps is b_t(j) L(j, d) g_(t+d)(j) / Z in the notation of
+ * csrc/duration_posterior_layout.hpp; each term is formed in the scaled arithmetic and added to a float64 sum in order of
+ * ascending t.  A recording no segmentation fits (Z = 0) gets counts 0 (minus the labels' terms).  Errors: those of
+ * hssfsst_posteriors_durations, before any device work; counts NULL or not 8-byte aligned: HSSFSST_EINVAL.
+ * A recording's counts do not depend on its neighbours or its place in the list, bit for bit, and two calls give the same bits:
+ * no atomics, no partial sums.  Enqueued on `stream` without synchronising: the fill launch, one sweep launch per 256 recordings
+ * (seg_duration_runs_sweep_kernel, the same two sweeps), then one counts launch per 256 recordings with one workgroup of 512 lanes
+ * per recording and block of 128 durations -- lane l for state l mod 4 and one duration, the steps walked in ascending order in
+ * segments of 256 --, 55 KiB of LDS, no scratch memory. */
+int hssfsst_posteriors_durations_counts(const float* logp, const int64_t* offsets, int64_t count, const float* a_pi, const float* durations,
+                                        const float* edge, int max_duration, const uint8_t* labels, float* gamma, float* onsets,
+                                        double* loglik, double* score, double* xi, double* s0, double* counts, void* work, int64_t work_bytes,
+                                        int device, void* stream);
+
+/* Its three workspace factors (bytes per step 97, per recording 48, per duration 96) and the durations one workgroup of the counts
+ * launch covers (128); the other limits are hssfsst_posteriors_durations_info's.  No device needed; any pointer may be NULL. */
+int hssfsst_posteriors_durations_counts_info(int64_t* work_bytes_per_step, int64_t* work_bytes_per_recording, int64_t* work_bytes_per_duration,
+                                             int* durations_per_group);
+
 /* One DIFFERENTIABLE bidirectional LSTM layer (batch first, nn.LSTM's cell and gate order): the unit a training program stacks
  * under autograd -- the segmenter is two of them.  The plan holds the layer's current weights in the kernels' layouts and the
  * scratch of its calls; the caller owns inputs, outputs and the stash.  Every pointer below is a DEVICE pointer on the plan's
