@@ -3,15 +3,23 @@
 Not in the reference (which only transforms stored recordings, hss/datasets/heart_sounds.py:155-184);
 built from the same path: per channel the last ``nwin - 1`` samples are kept, every ``step`` of
 ``chunk`` new samples emits the ``chunk`` FSST columns whose full frames are now available (look-ahead
-latency ``nwin/2 - 1`` samples) through ``hssfsst_exec_frames`` (no frame touches zero padding), and
+latency ``nwin - 1 - nwin // 2`` samples: ``nwin/2 - 1`` for an even window, ``(nwin - 1)/2`` for an odd
+one) through ``hssfsst_exec_frames`` (no frame touches zero padding), and
 -- because a per-signal z-score has no streaming meaning -- normalises with RUNNING mean / unbiased
 std of the real and imaginary blocks, kept on the device by ``hssfsst_moments_merge`` (the chunked
 form of ``hss.moments.update_mean / update_variance``, hss/moments/__init__.py:1-36).
 
 Concatenating the un-normalised outputs of consecutive steps (zero initial history; ``step`` returns a fresh tensor
 unless called with ``copy=False``, which hands out the object's single output buffer) reproduces the
-offline transform's columns ``-nwin/2 + 1, ..`` exactly: column tau of the offline, zero-padded FSST
-is column ``tau + nwin/2 - 1`` of the stream.
+offline transform's columns ``-(nwin - 1 - nwin // 2), ..``: column tau of the offline, zero-padded FSST
+is column ``tau + nwin - 1 - nwin // 2`` of the stream.  Bit for bit on the generic and the any-length kernel (window lengths
+other than 128 / 256 / 512).  On the MFMA kernels bit for bit as long as both round every column alike, which they need not: these
+kernels decide per group of frames what they redo in float64 (a 16-frame group whose kept band holds only leakage, as under a
+low-sidelobe window), and the canonical-band kernel of 128-point windows scales each 64-frame tile by that tile's own energy; a
+step's groups and tiles are not always the offline signal's.  On the shapes of tests/test_streaming.py the bits are equal at 256 and
+512 points under the Kaiser(0.5) window and at 128 points with an odd band; they differ -- by float32 rounding, at most 2.2e-7 of
+the largest feature, each side within the parity gate of the float64 oracle -- at 128 points with the canonical band and at 512
+points under a Hann window with ``chunk = 13`` (not with ``chunk = 16``: then the groups are the same).
 
 No allocation per step: the history lives in ONE preallocated device buffer per channel of
 ``nwin - 1 + slots * chunk`` samples that is written like a tape -- each step appends its chunk and
@@ -54,7 +62,7 @@ class StreamingFSST:
         self._wrap = torch.empty((self.channels, self.hist), dtype=torch.float32, device=self.device)
         self.pos = self.hist                               # where the next chunk goes (history = zeros before it)
         self.state = torch.zeros((self.channels, 6), dtype=torch.float64, device=self.device)
-        self.latency_samples = self.nwin // 2 - 1
+        self.latency_samples = self.nwin - 1 - self.nwin // 2     # (a frame holds nwin // 2 samples before its centre)
         self._plan = self.tf._plan(dev, _lib.MODE_STACK_UNNORM)
         self.K = self._plan.K
         self.out = torch.empty((self.channels, self.chunk, 2 * self.K), dtype=torch.float32, device=self.device)
@@ -97,7 +105,7 @@ class StreamingFSST:
 
     def step(self, x_new: torch.Tensor, copy: bool = True) -> torch.Tensor:
         """``x_new``: ``(channels, chunk)`` newest samples (device tensor preferred).  Returns
-        ``(channels, chunk, 2K)`` features of the columns centred ``nwin/2 - 1`` samples before the
+        ``(channels, chunk, 2K)`` features of the columns centred ``latency_samples`` samples before the
         newest sample and earlier.
 
         ``copy=True`` (default) returns a fresh tensor, so ``[st.step(x) for x in chunks]`` or ``torch.cat`` over collected

@@ -461,7 +461,7 @@ from heart_sounds_segmentation_amd.streaming import StreamingFSST
 outs = []
 for fs, N, chunk, ch, steps in ((4000, 512, 128, 64, 5), (1000, 256, 48, 3, 6), (4000, 512, 80, 300, 3), (4000, 512, 128, 9, 4)):
     w = get_window(("kaiser", 0.5), N, fftbins=False) if ch != 9 else get_window("hann", N, fftbins=False)
-    band = (25, 200) if N == 512 else (30, 50)           # even bands of <= 24 rows: the wide-store epilogue
+    band = (25, 200) if N == 512 else (30, 50)           # 22 rows: the wide-store epilogue; 5 rows (odd): the general one, three launches
     x = synth.pcg_windows(ch, chunk * steps, fs=fs, seed=N + ch) + 0.1
     if ch == 9:                                          # tones under a Hann window: many sources move into the same cells (the order
         t = np.arange(chunk * steps) / fs                # of the additions into the displaced plane matters to the last bit), more
@@ -484,8 +484,11 @@ np.savez(sys.argv[1], *outs)
 def test_stream_step_variants_are_bit_identical(tmp_path):
     """One launch per step (fsst_core128_kernel<STREAM>: tape append, transform, the groups' float64 sums, the channel's last block
     merges and normalises), with and without wave pairs, and the three-launch route give the same bits -- features and running
-    moments -- on BASELINE config 5's shape, on a 256-point window with a ragged last group and on more channels than CUs
-    (one block per channel, several tickets per wave region)."""
+    moments -- on BASELINE config 5's shape and on 9 channels of tones under a Hann window.  The other two shapes take three
+    launches whatever the switches (last_kernel() on the device): the 256-point window's band (30, 50) keeps 5 rows, and an odd
+    band has no one-launch step; 300 channels x 5 groups = 1500 group slots are more than the 1024 the one-launch kernel takes.
+    One launch on a 256-point window, and with one block per channel on more channels than CUs (300 x 3 groups):
+    tests/test_streaming.py."""
     res = {}
     for tag, env in (("default", {}), ("no_pair", {"HSSFSST_NO_PAIR": "1"}), ("three_launches", {"HSSFSST_NO_STREAM_FUSE": "1"})):
         out = str(tmp_path / f"{tag}.npz")
@@ -529,7 +532,9 @@ def test_stream_step_pageable_host_buffers():
 @pytest.mark.parametrize("band,n,batch", [((25, 200), 1, 3), ((25, 200), 17, 2), ((25, 210), 100, 2), ((25, 210), 2000, 3), ((25, 200), 1029, 1)])
 def test_moments_merge_any_shape(band, n, batch):
     """hssfsst_moments_merge sums a chunk in the order of the transform kernels' 16-frame pieces (fsst_kernels.hpp,
-    chunk_moments): any number of frames, even and odd bands, against float64 numpy; two chunks merged == one."""
+    chunk_moments): any number of frames, even and odd bands, against float64 numpy; then the SAME chunk merged a second time
+    (counts and M2 double, the mean stays: the Chan cross term is zero here -- two different chunks are
+    tests/test_streaming.py::test_moments_merge_two_different_chunks)."""
     tf = FSST(1000, KAISER, truncate_freq=band, stack=True)
     plan = tf._plan(0, _lib.MODE_STACK_UNNORM)
     K = plan.K
