@@ -2,7 +2,7 @@
 ``hss.transforms.FSST`` + ``hss.moments``).  See DESIGN.md and INTEGRATION.md."""
 from . import moments, transforms  # noqa: F401
 from .transforms import FSST, Resample  # noqa: F401
-from .consumer import (cyclic_transitions, decode_durations, decode_states, duration_counts_info, duration_nll,  # noqa: F401
+from .sequence import (cyclic_transitions, decode_durations, decode_states, duration_counts_info, duration_nll,  # noqa: F401
                        duration_posteriors, duration_posteriors_info, durations_from_counts, durations_from_labels, edge_durations,
                        gaussian_durations, sequence_nll, state_posteriors, state_runs, transitions_from_labels)
 

@@ -42,6 +42,7 @@
 #include "segmenter_train.hpp"
 #include "decode_durations_layout.hpp"
 #include "decode_layout.hpp"
+#include "sequence_args.hpp"
 #include "segmenter_decode.hpp"
 #include "segmenter_decode_durations.hpp"
 #include "posterior_layout.hpp"
@@ -2326,6 +2327,89 @@ int hssfsst_stream_step(hssfsst_plan* p, float* tape, int64_t tape_len, int64_t 
 
 }  // extern "C"
 
+// What the sequence-model entry points (hssfsst_decode_states .. hssfsst_posteriors_durations_counts) share: the decisions of
+// csrc/sequence_args.hpp put into words -- every text stands here, once -- and the loop over a list's launches.  Each entry
+// calls the checks in its own order: that order is which of two errors a caller sees.
+namespace {
+
+namespace seqargs = hssfsst::seqargs;
+
+int seq_check_list(const char* entry, const int64_t* offsets, int64_t count, int64_t max_steps)
+{
+    using Fault = seqargs::ListFault;
+    const seqargs::ListFinding f = seqargs::check_list(offsets, count, max_steps);
+    const long long i = f.index, limit = max_steps;
+    if (f.fault == Fault::kNone) return 0;
+    if (f.fault == Fault::kFirstNotZero) return fail(HSSFSST_EINVAL, "%s: offsets[0] is %lld, not 0", entry, static_cast<long long>(offsets[0]));
+    if (f.fault == Fault::kTooManySteps)
+        return fail(HSSFSST_EUNSUPPORTED, "%s: %lld steps in all, over the limit of 2^31 - 1", entry, static_cast<long long>(offsets[i]));
+    const long long from = offsets[i], to = offsets[i + 1];
+    if (f.fault == Fault::kNotIncreasing)
+        return fail(HSSFSST_EINVAL, "%s: offsets do not increase at index %lld (offsets[%lld] = %lld, offsets[%lld] = %lld)", entry, i + 1, i,
+                    from, i + 1, to);
+    return fail(HSSFSST_EUNSUPPORTED, "%s: recording %lld has %lld steps, over the limit of %lld", entry, i, to - from, limit);
+}
+
+int seq_check_nonnull(const char* entry, std::initializer_list<seqargs::NamedPointer> required)
+{
+    if (const char* name = seqargs::first_null(required)) return fail(HSSFSST_EINVAL, "%s: bad argument (%s is NULL)", entry, name);
+    return 0;
+}
+
+int seq_check_aligned(const char* entry, std::initializer_list<seqargs::NamedPointer> pointers)
+{
+    const seqargs::NamedPointer p = seqargs::first_misaligned(pointers);
+    if (p.name) return fail(HSSFSST_EINVAL, "%s: %s is not %u-byte aligned", entry, p.name, p.alignment);
+    return 0;
+}
+
+int seq_check_duration_table(const char* entry, const char* name, const float* table, int D)
+{
+    const seqargs::TableFinding f = seqargs::check_duration_table(table, D);
+    if (f.fault == seqargs::TableFault::kNaN)
+        return fail(HSSFSST_EINVAL, "%s: %s[%d][%d] is NaN (duration %d)", entry, name, f.row, f.column, f.column + 1);
+    if (f.fault == seqargs::TableFault::kDeadRow)
+        return fail(HSSFSST_EINVAL, "%s: row %d of %s is all -inf: state %d has no allowed duration", entry, f.row, name, f.row);
+    return 0;
+}
+
+// (transitions, initial) and, with `durations`, the host tables of the explicit-duration model, whose diagonal is not read: the
+// NaNs of the first two, then the two duration tables, then what the first two leave of a path.
+int seq_check_model(const char* entry, const float* transitions, const float* initial, const float* durations = nullptr,
+                    const float* edge = nullptr, int D = 0)
+{
+    const seqargs::ModelFinding f = seqargs::check_model(transitions, initial, durations != nullptr);
+    if (f.nan_at >= 16) return fail(HSSFSST_EINVAL, "%s: initial[%d] is NaN", entry, f.nan_at - 16);
+    if (f.nan_at >= 0) return fail(HSSFSST_EINVAL, "%s: transitions[%d][%d] is NaN", entry, f.nan_at / 4, f.nan_at % 4);
+    if (durations) {
+        if (int rc = seq_check_duration_table(entry, "durations", durations, D)) return rc;
+        if (int rc = seq_check_duration_table(entry, "edge", edge, D)) return rc;
+    }
+    if (f.dead_row >= 0)
+        return fail(HSSFSST_EINVAL,
+                    durations ? "%s: row %d of transitions has no finite off-diagonal entry: state %d has no successor"
+                              : "%s: row %d of transitions is all -inf: state %d has no successor", entry, f.dead_row, f.dead_row);
+    if (f.no_start) return fail(HSSFSST_EINVAL, "%s: initial is all -inf: no state to start in", entry);
+    return 0;
+}
+
+// The recordings of a list, `batch` per launch (the kernel's k*Batch: their offsets travel as kernel arguments).  For the
+// recordings r0 .. r0 + nrec of each launch args.off[] is filled, launch(r0, nrec) enqueues `kernel` -- after setting args.rec0,
+// where the kernel has one -- and the launch is checked.
+template <class Args, class Launch>
+int seq_for_each_batch(const char* entry, const char* kernel, const int64_t* offsets, int64_t count, int batch, Args& args, Launch launch)
+{
+    for (int64_t r0 = 0; r0 < count; r0 += batch) {
+        const int nrec = static_cast<int>(std::min<int64_t>(batch, count - r0));
+        for (int i = 0; i <= nrec; ++i) args.off[i] = offsets[r0 + i];
+        launch(r0, nrec);
+        if (int rc = launch_check(entry, kernel)) return rc;
+    }
+    return 0;
+}
+
+}  // namespace
+
 // BiLSTM segmenter (hssfsst.h: hssfsst_segmenter_create): the model's weights, uploaded once in the layouts the kernels of
 // csrc/segmenter_lstm.hpp consume, plus the scratch of its execs (owned by the plan, grown on demand, freed with it).
 namespace {
@@ -2698,50 +2782,25 @@ int hssfsst_decode_states(const float* logp, const int64_t* offsets, int64_t cou
                           uint8_t* states, int64_t* scores, int device, void* stream)
 {
     namespace dl = hssfsst::declayout;
-    if (count < 0) return fail(HSSFSST_EINVAL, "decode_states: count %lld is negative", static_cast<long long>(count));
-    if (!logp || !offsets || !transitions || !initial || !states)
-        return fail(HSSFSST_EINVAL, "decode_states: bad argument (%s is NULL)",
-                    !logp ? "logp" : !offsets ? "offsets" : !transitions ? "transitions" : !initial ? "initial" : "states");
-    if (device < 0) return fail(HSSFSST_EINVAL, "decode_states: device %d is negative", device);
-    if (reinterpret_cast<uintptr_t>(logp) % 16 != 0) return fail(HSSFSST_EINVAL, "decode_states: logp is not 16-byte aligned");
-    for (int i = 0; i < 16; ++i)
-        if (transitions[i] != transitions[i]) return fail(HSSFSST_EINVAL, "decode_states: transitions[%d][%d] is NaN", i / 4, i % 4);
-    for (int i = 0; i < 4; ++i)
-        if (initial[i] != initial[i]) return fail(HSSFSST_EINVAL, "decode_states: initial[%d] is NaN", i);
-    const hssfsst::declayout::Mat qa = dl::quantise_transitions(transitions);
-    const hssfsst::declayout::Vec qp = dl::quantise4(initial);
-    for (int i = 0; i < 4; ++i)
-        if (qa.m[i][0] == dl::kNeg && qa.m[i][1] == dl::kNeg && qa.m[i][2] == dl::kNeg && qa.m[i][3] == dl::kNeg)
-            return fail(HSSFSST_EINVAL, "decode_states: row %d of transitions is all -inf: state %d has no successor", i, i);
-    if (qp.v[0] == dl::kNeg && qp.v[1] == dl::kNeg && qp.v[2] == dl::kNeg && qp.v[3] == dl::kNeg)
-        return fail(HSSFSST_EINVAL, "decode_states: initial is all -inf: no state to start in");
-    if (offsets[0] != 0) return fail(HSSFSST_EINVAL, "decode_states: offsets[0] is %lld, not 0", static_cast<long long>(offsets[0]));
-    for (int64_t i = 0; i < count; ++i)
-        if (offsets[i + 1] <= offsets[i])
-            return fail(HSSFSST_EINVAL, "decode_states: offsets do not increase at index %lld (offsets[%lld] = %lld, offsets[%lld] = %lld)",
-                        static_cast<long long>(i + 1), static_cast<long long>(i), static_cast<long long>(offsets[i]),
-                        static_cast<long long>(i + 1), static_cast<long long>(offsets[i + 1]));
-    for (int64_t i = 0; i < count; ++i)
-        if (offsets[i + 1] - offsets[i] > dl::kMaxSteps)
-            return fail(HSSFSST_EUNSUPPORTED, "decode_states: recording %lld has %lld steps, over the limit of %lld", static_cast<long long>(i),
-                        static_cast<long long>(offsets[i + 1] - offsets[i]), static_cast<long long>(dl::kMaxSteps));
-    if (offsets[count] > 0x7fffffffLL)
-        return fail(HSSFSST_EUNSUPPORTED, "decode_states: %lld steps in all, over the limit of 2^31 - 1", static_cast<long long>(offsets[count]));
+    constexpr const char* kEntry = "decode_states";
+    if (count < 0) return fail(HSSFSST_EINVAL, "%s: count %lld is negative", kEntry, static_cast<long long>(count));
+    if (int rc = seq_check_nonnull(kEntry, {{"logp", logp}, {"offsets", offsets}, {"transitions", transitions}, {"initial", initial},
+                                            {"states", states}})) return rc;
+    if (device < 0) return fail(HSSFSST_EINVAL, "%s: device %d is negative", kEntry, device);
+    if (int rc = seq_check_aligned(kEntry, {{"logp", logp, 16}})) return rc;
+    if (int rc = seq_check_model(kEntry, transitions, initial)) return rc;
+    if (int rc = seq_check_list(kEntry, offsets, count, dl::kMaxSteps)) return rc;
     if (count == 0) return 0;
-    if (int rc = check_device("decode_states", device)) return rc;
+    if (int rc = check_device(kEntry, device)) return rc;
     DEVICE_SCOPE(device);
     const hipStream_t st = static_cast<hipStream_t>(stream);
     hssfsst::DecodeArgs args{};
-    args.A = qa;
-    args.pi = qp;
-    for (int64_t r0 = 0; r0 < count; r0 += hssfsst::kDecodeBatch) {
-        const int nrec = static_cast<int>(std::min<int64_t>(hssfsst::kDecodeBatch, count - r0));
-        for (int i = 0; i <= nrec; ++i) args.off[i] = offsets[r0 + i];
+    args.A = dl::quantise_transitions(transitions);
+    args.pi = dl::quantise4(initial);
+    return seq_for_each_batch(kEntry, "seg_decode_kernel", offsets, count, hssfsst::kDecodeBatch, args, [&](int64_t r0, int nrec) {
         hipLaunchKernelGGL(hssfsst::seg_decode_kernel, dim3(static_cast<unsigned>(nrec)), dim3(dl::kLanes), 0, st, logp, states,
                            scores ? reinterpret_cast<long long*>(scores) + r0 : nullptr, args);
-        if (int rc = launch_check("decode_states", "seg_decode_kernel")) return rc;
-    }
-    return 0;
+    });
 }
 
 }  // extern "C"
@@ -2768,56 +2827,16 @@ int hssfsst_decode_durations(const float* logp, const int64_t* offsets, int64_t 
     namespace ul = hssfsst::durlayout;
     constexpr const char* kEntry = "decode_durations";
     if (count < 0) return fail(HSSFSST_EINVAL, "%s: count %lld is negative", kEntry, static_cast<long long>(count));
-    if (!logp || !offsets || !transitions || !initial || !durations || !edge || !states || !workspace)
-        return fail(HSSFSST_EINVAL, "%s: bad argument (%s is NULL)", kEntry,
-                    !logp ? "logp" : !offsets ? "offsets" : !transitions ? "transitions" : !initial ? "initial" : !durations ? "durations"
-                    : !edge ? "edge" : !states ? "states" : "workspace");
+    if (int rc = seq_check_nonnull(kEntry, {{"logp", logp}, {"offsets", offsets}, {"transitions", transitions}, {"initial", initial},
+                                            {"durations", durations}, {"edge", edge}, {"states", states}, {"workspace", workspace}}))
+        return rc;
     if (device < 0) return fail(HSSFSST_EINVAL, "%s: device %d is negative", kEntry, device);
     if (max_duration < 1 || max_duration > ul::kMaxDuration)
         return fail(HSSFSST_EINVAL, "%s: max_duration %d is outside 1..%d", kEntry, max_duration, ul::kMaxDuration);
     const int D = max_duration;
-    if (reinterpret_cast<uintptr_t>(logp) % 16 != 0) return fail(HSSFSST_EINVAL, "%s: logp is not 16-byte aligned", kEntry);
-    if (reinterpret_cast<uintptr_t>(workspace) % 16 != 0) return fail(HSSFSST_EINVAL, "%s: workspace is not 16-byte aligned", kEntry);
-    for (int i = 0; i < 16; ++i)
-        if (transitions[i] != transitions[i]) return fail(HSSFSST_EINVAL, "%s: transitions[%d][%d] is NaN", kEntry, i / 4, i % 4);
-    for (int i = 0; i < 4; ++i)
-        if (initial[i] != initial[i]) return fail(HSSFSST_EINVAL, "%s: initial[%d] is NaN", kEntry, i);
-    for (int which = 0; which < 2; ++which) {
-        const float* tab = which ? edge : durations;
-        const char* tname = which ? "edge" : "durations";
-        for (int j = 0; j < 4; ++j) {
-            bool any = false;
-            for (int d = 1; d <= D; ++d) {
-                const float v = tab[static_cast<size_t>(j) * D + (d - 1)];
-                if (v != v) return fail(HSSFSST_EINVAL, "%s: %s[%d][%d] is NaN (duration %d)", kEntry, tname, j, d - 1, d);
-                any = any || dl::quantise(v) != dl::kNeg;
-            }
-            if (!any) return fail(HSSFSST_EINVAL, "%s: row %d of %s is all -inf: state %d has no allowed duration", kEntry, j, tname, j);
-        }
-    }
-    hssfsst::DurDecodeArgs args{};
-    args.tb = ul::quantise_tables(transitions, initial);
-    args.D = D;
-    for (int i = 0; i < 4; ++i) {
-        bool any = false;
-        for (int j = 0; j < 4; ++j) any = any || (j != i && args.tb.A[i][j] != dl::kNeg);
-        if (!any)
-            return fail(HSSFSST_EINVAL, "%s: row %d of transitions has no finite off-diagonal entry: state %d has no successor", kEntry, i, i);
-    }
-    if (args.tb.pi[0] == dl::kNeg && args.tb.pi[1] == dl::kNeg && args.tb.pi[2] == dl::kNeg && args.tb.pi[3] == dl::kNeg)
-        return fail(HSSFSST_EINVAL, "%s: initial is all -inf: no state to start in", kEntry);
-    if (offsets[0] != 0) return fail(HSSFSST_EINVAL, "%s: offsets[0] is %lld, not 0", kEntry, static_cast<long long>(offsets[0]));
-    for (int64_t i = 0; i < count; ++i)
-        if (offsets[i + 1] <= offsets[i])
-            return fail(HSSFSST_EINVAL, "%s: offsets do not increase at index %lld (offsets[%lld] = %lld, offsets[%lld] = %lld)", kEntry,
-                        static_cast<long long>(i + 1), static_cast<long long>(i), static_cast<long long>(offsets[i]),
-                        static_cast<long long>(i + 1), static_cast<long long>(offsets[i + 1]));
-    for (int64_t i = 0; i < count; ++i)
-        if (offsets[i + 1] - offsets[i] > ul::kMaxSteps)
-            return fail(HSSFSST_EUNSUPPORTED, "%s: recording %lld has %lld steps, over the limit of %lld", kEntry, static_cast<long long>(i),
-                        static_cast<long long>(offsets[i + 1] - offsets[i]), static_cast<long long>(ul::kMaxSteps));
-    if (offsets[count] > 0x7fffffffLL)
-        return fail(HSSFSST_EUNSUPPORTED, "%s: %lld steps in all, over the limit of 2^31 - 1", kEntry, static_cast<long long>(offsets[count]));
+    if (int rc = seq_check_aligned(kEntry, {{"logp", logp, 16}, {"workspace", workspace, 16}})) return rc;
+    if (int rc = seq_check_model(kEntry, transitions, initial, durations, edge, D)) return rc;
+    if (int rc = seq_check_list(kEntry, offsets, count, ul::kMaxSteps)) return rc;
     const int64_t need = ul::kWorkspaceBytesPerStep * ul::workspace_steps(offsets[count], D);
     if (workspace_bytes < need)
         return fail(HSSFSST_EINVAL, "%s: workspace of %lld bytes is too small: %lld steps and max_duration %d need %lld", kEntry,
@@ -2837,14 +2856,13 @@ int hssfsst_decode_durations(const float* logp, const int64_t* offsets, int64_t 
         hipLaunchKernelGGL(hssfsst::seg_durations_fill_kernel, dim3(1), dim3(hssfsst::kDurFillValues), 0, st, table, fa);
         if (int rc = launch_check(kEntry, "seg_durations_fill_kernel")) return rc;
     }
-    for (int64_t r0 = 0; r0 < count; r0 += hssfsst::kDurDecodeBatch) {
-        const int nrec = static_cast<int>(std::min<int64_t>(hssfsst::kDurDecodeBatch, count - r0));
-        for (int i = 0; i <= nrec; ++i) args.off[i] = offsets[r0 + i];
+    hssfsst::DurDecodeArgs args{};
+    args.tb = ul::quantise_tables(transitions, initial);
+    args.D = D;
+    return seq_for_each_batch(kEntry, "seg_decode_durations_kernel", offsets, count, hssfsst::kDurDecodeBatch, args, [&](int64_t r0, int nrec) {
         hipLaunchKernelGGL(hssfsst::seg_decode_durations_kernel, dim3(static_cast<unsigned>(nrec)), dim3(ul::kLanes), 0, st, logp, states,
                            scores ? reinterpret_cast<long long*>(scores) + r0 : nullptr, back, table, args);
-        if (int rc = launch_check(kEntry, "seg_decode_durations_kernel")) return rc;
-    }
-    return 0;
+    });
 }
 
 }  // extern "C"
@@ -2868,32 +2886,13 @@ int hssfsst_posteriors(const float* logp, const int64_t* offsets, int64_t count,
     namespace pl = hssfsst::postlayout;
     constexpr const char* kEntry = "posteriors";
     if (count < 0) return fail(HSSFSST_EINVAL, "%s: count %lld is negative", kEntry, static_cast<long long>(count));
-    if (!logp || !offsets || !a_pi || !gamma || !loglik || !work)
-        return fail(HSSFSST_EINVAL, "%s: bad argument (%s is NULL)", kEntry,
-                    !logp ? "logp" : !offsets ? "offsets" : !a_pi ? "a_pi" : !gamma ? "gamma" : !loglik ? "loglik" : "work");
+    if (int rc = seq_check_nonnull(kEntry, {{"logp", logp}, {"offsets", offsets}, {"a_pi", a_pi}, {"gamma", gamma}, {"loglik", loglik},
+                                            {"work", work}})) return rc;
     if (score && !labels) return fail(HSSFSST_EINVAL, "%s: bad argument (labels is NULL while score is not)", kEntry);
     if (device < 0) return fail(HSSFSST_EINVAL, "%s: device %d is negative", kEntry, device);
-    if (reinterpret_cast<uintptr_t>(logp) % 16 != 0) return fail(HSSFSST_EINVAL, "%s: logp is not 16-byte aligned", kEntry);
-    if (reinterpret_cast<uintptr_t>(gamma) % 16 != 0) return fail(HSSFSST_EINVAL, "%s: gamma is not 16-byte aligned", kEntry);
-    if (reinterpret_cast<uintptr_t>(work) % 16 != 0) return fail(HSSFSST_EINVAL, "%s: work is not 16-byte aligned", kEntry);
-    if (reinterpret_cast<uintptr_t>(a_pi) % 4 != 0) return fail(HSSFSST_EINVAL, "%s: a_pi is not 4-byte aligned", kEntry);
-    if (reinterpret_cast<uintptr_t>(loglik) % 8 != 0 || reinterpret_cast<uintptr_t>(score) % 8 != 0 || reinterpret_cast<uintptr_t>(xi) % 8 != 0 ||
-        reinterpret_cast<uintptr_t>(gamma0) % 8 != 0)
-        return fail(HSSFSST_EINVAL, "%s: %s is not 8-byte aligned", kEntry,
-                    reinterpret_cast<uintptr_t>(loglik) % 8 != 0 ? "loglik" : reinterpret_cast<uintptr_t>(score) % 8 != 0 ? "score"
-                    : reinterpret_cast<uintptr_t>(xi) % 8 != 0 ? "xi" : "gamma0");
-    if (offsets[0] != 0) return fail(HSSFSST_EINVAL, "%s: offsets[0] is %lld, not 0", kEntry, static_cast<long long>(offsets[0]));
-    for (int64_t i = 0; i < count; ++i)
-        if (offsets[i + 1] <= offsets[i])
-            return fail(HSSFSST_EINVAL, "%s: offsets do not increase at index %lld (offsets[%lld] = %lld, offsets[%lld] = %lld)", kEntry,
-                        static_cast<long long>(i + 1), static_cast<long long>(i), static_cast<long long>(offsets[i]),
-                        static_cast<long long>(i + 1), static_cast<long long>(offsets[i + 1]));
-    for (int64_t i = 0; i < count; ++i)
-        if (offsets[i + 1] - offsets[i] > pl::kMaxSteps)
-            return fail(HSSFSST_EUNSUPPORTED, "%s: recording %lld has %lld steps, over the limit of %lld", kEntry, static_cast<long long>(i),
-                        static_cast<long long>(offsets[i + 1] - offsets[i]), static_cast<long long>(pl::kMaxSteps));
-    if (offsets[count] > 0x7fffffffLL)
-        return fail(HSSFSST_EUNSUPPORTED, "%s: %lld steps in all, over the limit of 2^31 - 1", kEntry, static_cast<long long>(offsets[count]));
+    if (int rc = seq_check_aligned(kEntry, {{"logp", logp, 16}, {"gamma", gamma, 16}, {"work", work, 16}, {"a_pi", a_pi, 4}, {"loglik", loglik, 8},
+                                            {"score", score, 8}, {"xi", xi, 8}, {"gamma0", gamma0, 8}})) return rc;
+    if (int rc = seq_check_list(kEntry, offsets, count, pl::kMaxSteps)) return rc;
     const int64_t need = pl::workspace_bytes(offsets[count], count);
     if (work_bytes < need)
         return fail(HSSFSST_EINVAL, "%s: work of %lld bytes is too small: %lld steps in %lld recordings need %lld", kEntry,
@@ -2904,15 +2903,12 @@ int hssfsst_posteriors(const float* logp, const int64_t* offsets, int64_t count,
     DEVICE_SCOPE(device);
     const hipStream_t st = static_cast<hipStream_t>(stream);
     hssfsst::PostArgs args{};
-    for (int64_t r0 = 0; r0 < count; r0 += hssfsst::kPostBatch) {
-        const int nrec = static_cast<int>(std::min<int64_t>(hssfsst::kPostBatch, count - r0));
-        for (int i = 0; i <= nrec; ++i) args.off[i] = offsets[r0 + i];
+    return seq_for_each_batch(kEntry, "seg_posteriors_kernel", offsets, count, hssfsst::kPostBatch, args, [&](int64_t r0, int nrec) {
         args.rec0 = r0;
         hipLaunchKernelGGL(hssfsst::seg_posteriors_kernel, dim3(static_cast<unsigned>(nrec)), dim3(pl::kLanes), 0, st, logp, a_pi, labels, gamma,
-                           loglik + r0, score ? score + r0 : nullptr, xi ? xi + 16 * r0 : nullptr, gamma0 ? gamma0 + 4 * r0 : nullptr, static_cast<double*>(work), args);
-        if (int rc = launch_check(kEntry, "seg_posteriors_kernel")) return rc;
-    }
-    return 0;
+                           loglik + r0, score ? score + r0 : nullptr, xi ? xi + 16 * r0 : nullptr, gamma0 ? gamma0 + 4 * r0 : nullptr,
+                           static_cast<double*>(work), args);
+    });
 }
 
 }  // extern "C"
@@ -2933,37 +2929,20 @@ int posteriors_durations_run(const char* kEntry, bool with_counts, const float* 
 {
     namespace dp = hssfsst::dplayout;
     namespace dc = hssfsst::dclayout;
-    auto misaligned = [](const void* p, unsigned a) { return reinterpret_cast<uintptr_t>(p) % a != 0; };
     if (count < 0) return fail(HSSFSST_EINVAL, "%s: count %lld is negative", kEntry, static_cast<long long>(count));
-    if (!logp || !offsets || !a_pi || !durations || !edge || !gamma || !loglik || (with_counts && !counts) || !work)
-        return fail(HSSFSST_EINVAL, "%s: bad argument (%s is NULL)", kEntry,
-                    !logp ? "logp" : !offsets ? "offsets" : !a_pi ? "a_pi" : !durations ? "durations" : !edge ? "edge" : !gamma ? "gamma"
-                    : !loglik ? "loglik" : !work ? "work" : "counts");
+    if (int rc = seq_check_nonnull(kEntry, {{"logp", logp}, {"offsets", offsets}, {"a_pi", a_pi}, {"durations", durations}, {"edge", edge},
+                                            {"gamma", gamma}, {"loglik", loglik}, {"work", work}})) return rc;
+    if (with_counts)
+        if (int rc = seq_check_nonnull(kEntry, {{"counts", counts}})) return rc;
     if (score && !labels) return fail(HSSFSST_EINVAL, "%s: bad argument (labels is NULL while score is not)", kEntry);
     if (device < 0) return fail(HSSFSST_EINVAL, "%s: device %d is negative", kEntry, device);
     if (max_duration < 1 || max_duration > dp::kMaxDuration)
         return fail(HSSFSST_EINVAL, "%s: max_duration %d is outside 1..%d", kEntry, max_duration, dp::kMaxDuration);
     const int D = max_duration;
-    if (misaligned(logp, 16) || misaligned(gamma, 16) || misaligned(onsets, 16) || misaligned(work, 16))
-        return fail(HSSFSST_EINVAL, "%s: %s is not 16-byte aligned", kEntry,
-                    misaligned(logp, 16) ? "logp" : misaligned(gamma, 16) ? "gamma" : misaligned(onsets, 16) ? "onsets" : "work");
-    if (misaligned(a_pi, 4) || misaligned(durations, 4) || misaligned(edge, 4))
-        return fail(HSSFSST_EINVAL, "%s: %s is not 4-byte aligned", kEntry, misaligned(a_pi, 4) ? "a_pi" : misaligned(durations, 4) ? "durations" : "edge");
-    if (misaligned(loglik, 8) || misaligned(score, 8) || misaligned(xi, 8) || misaligned(s0, 8) || misaligned(counts, 8))
-        return fail(HSSFSST_EINVAL, "%s: %s is not 8-byte aligned", kEntry,
-                    misaligned(loglik, 8) ? "loglik" : misaligned(score, 8) ? "score" : misaligned(xi, 8) ? "xi" : misaligned(s0, 8) ? "s0" : "counts");
-    if (offsets[0] != 0) return fail(HSSFSST_EINVAL, "%s: offsets[0] is %lld, not 0", kEntry, static_cast<long long>(offsets[0]));
-    for (int64_t i = 0; i < count; ++i)
-        if (offsets[i + 1] <= offsets[i])
-            return fail(HSSFSST_EINVAL, "%s: offsets do not increase at index %lld (offsets[%lld] = %lld, offsets[%lld] = %lld)", kEntry,
-                        static_cast<long long>(i + 1), static_cast<long long>(i), static_cast<long long>(offsets[i]),
-                        static_cast<long long>(i + 1), static_cast<long long>(offsets[i + 1]));
-    for (int64_t i = 0; i < count; ++i)
-        if (offsets[i + 1] - offsets[i] > dp::kMaxSteps)
-            return fail(HSSFSST_EUNSUPPORTED, "%s: recording %lld has %lld steps, over the limit of %lld", kEntry, static_cast<long long>(i),
-                        static_cast<long long>(offsets[i + 1] - offsets[i]), static_cast<long long>(dp::kMaxSteps));
-    if (offsets[count] > 0x7fffffffLL)
-        return fail(HSSFSST_EUNSUPPORTED, "%s: %lld steps in all, over the limit of 2^31 - 1", kEntry, static_cast<long long>(offsets[count]));
+    if (int rc = seq_check_aligned(kEntry, {{"logp", logp, 16}, {"gamma", gamma, 16}, {"onsets", onsets, 16}, {"work", work, 16}, {"a_pi", a_pi, 4},
+                                            {"durations", durations, 4}, {"edge", edge, 4}, {"loglik", loglik, 8}, {"score", score, 8},
+                                            {"xi", xi, 8}, {"s0", s0, 8}, {"counts", counts, 8}})) return rc;
+    if (int rc = seq_check_list(kEntry, offsets, count, dp::kMaxSteps)) return rc;
     const int64_t need = with_counts ? dc::workspace_bytes(offsets[count], count, D) : dp::workspace_bytes(offsets[count], count, D);
     if (work_bytes < need)
         return fail(HSSFSST_EINVAL, "%s: work of %lld bytes is too small: %lld steps in %lld recordings and max_duration %d need %lld", kEntry,
@@ -2991,33 +2970,25 @@ int posteriors_durations_run(const char* kEntry, bool with_counts, const float* 
         return hssfsst::DurRunsOut{reinterpret_cast<double*>(w + wc.g_mant), reinterpret_cast<int*>(w + wc.g_exp),
                                    reinterpret_cast<double*>(w + wc.invz_mant) + r0, reinterpret_cast<int*>(w + wc.invz_exp) + r0};
     };
-    for (int64_t r0 = 0; r0 < count; r0 += hssfsst::kDurPostBatch) {
-        const int nrec = static_cast<int>(std::min<int64_t>(hssfsst::kDurPostBatch, count - r0));
-        for (int i = 0; i <= nrec; ++i) args.off[i] = offsets[r0 + i];
+    const char* sweep = with_counts ? "seg_duration_runs_sweep_kernel" : "seg_duration_posteriors_kernel";
+    int rc = seq_for_each_batch(kEntry, sweep, offsets, count, hssfsst::kDurPostBatch, args, [&](int64_t r0, int nrec) {
         args.rec0 = r0;
-        if (with_counts) {
+        if (with_counts)
             hipLaunchKernelGGL(hssfsst::seg_duration_runs_sweep_kernel, dim3(static_cast<unsigned>(nrec)), dim3(dp::kLanes), 0, st, logp, a_pi,
                                durations, edge, labels, gamma, onsets, loglik + r0, score ? score + r0 : nullptr, xi ? xi + 16 * r0 : nullptr,
                                s0 ? s0 + 4 * r0 : nullptr, tabm, tabe, stash_m, stash_e, checkpoints, runs_of(r0), args);
-            if (int rc = launch_check(kEntry, "seg_duration_runs_sweep_kernel")) return rc;
-        } else {
+        else
             hipLaunchKernelGGL(hssfsst::seg_duration_posteriors_kernel, dim3(static_cast<unsigned>(nrec)), dim3(dp::kLanes), 0, st, logp, a_pi,
                                durations, edge, labels, gamma, onsets, loglik + r0, score ? score + r0 : nullptr, xi ? xi + 16 * r0 : nullptr,
                                s0 ? s0 + 4 * r0 : nullptr, tabm, tabe, stash_m, stash_e, checkpoints, args);
-            if (int rc = launch_check(kEntry, "seg_duration_posteriors_kernel")) return rc;
-        }
-    }
-    if (!with_counts) return 0;
-    for (int64_t r0 = 0; r0 < count; r0 += hssfsst::kDurPostBatch) {
-        const int nrec = static_cast<int>(std::min<int64_t>(hssfsst::kDurPostBatch, count - r0));
-        for (int i = 0; i <= nrec; ++i) args.off[i] = offsets[r0 + i];
+    });
+    if (rc || !with_counts) return rc;
+    return seq_for_each_batch(kEntry, "seg_duration_run_counts_kernel", offsets, count, hssfsst::kDurPostBatch, args, [&](int64_t r0, int nrec) {
         args.rec0 = r0;
         hipLaunchKernelGGL(hssfsst::seg_duration_run_counts_kernel, dim3(static_cast<unsigned>(nrec), static_cast<unsigned>(dc::groups(D))),
                            dim3(dc::kLanes), 0, st, logp, a_pi, labels, counts + dc::counts_index(r0, 0, 0, 1, D), tabm, tabe, stash_m, stash_e,
                            checkpoints, runs_of(r0), args);
-        if (int rc = launch_check(kEntry, "seg_duration_run_counts_kernel")) return rc;
-    }
-    return 0;
+    });
 }
 
 }  // namespace
