@@ -382,7 +382,8 @@ class _RaggedBiLSTMFunction(torch.autograd.Function):
                                                              dgates.data_ptr(), dh0.data_ptr(), dc0.data_ptr(), stream),
                    "hssfsst_bilstm_backward_ragged")
         # h before each step: y shifted by one arena row, with h0 written at each recording's first (reverse: last) row
-        edges = torch.from_numpy(offs).to(x.device)
+        # (from pinned memory and not blocking: a pageable copy would make the host wait for everything queued on the stream)
+        edges = torch.from_numpy(offs).pin_memory().to(x.device, non_blocking=True)
         hf = torch.cat((y.new_zeros(1, H), y[:-1, :H]))
         hf[edges[:-1]] = h0[0]
         hr = torch.cat((y[1:, H:], y.new_zeros(1, H)))

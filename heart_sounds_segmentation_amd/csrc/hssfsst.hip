@@ -226,22 +226,29 @@ struct PinnedBuf {
     }
 };
 
-// A table that is made on the host for a list and read on the device: a pinned (not mapped) host block, a device block, the event
-// of the last upload (the host block is not rewritten before that copy is done) and the key of the list the device block holds.
+// A table that is made on the host for a list and read on the device: a ring of kRing pinned (not mapped) host blocks, a device
+// block, per host block the event of its last upload (a host block is not rewritten before that copy is done) and the key of the
+// list the device block holds.
 //   if (!t.same(n, key)) { t.begin(bytes, &h); ...fill h...; t.commit(stream, n, key); }     key(i): the i-th of n 64-bit words
 // begin() drops the key first and commit() stores it last, behind the queued copy: whatever fails in between, the next call with
 // the same list makes the table again.  A user without a key (n = 0) uploads at every call.  `what`: the entry point, for errors.
+// Why a ring: with ONE host block a call whose list differs from the previous call's had to wait on the host for the previous
+// upload, i.e. for everything queued on the stream before it -- a caller that walks groups of a long list (HipSegmenter.ragged
+// with max_steps) behind other work stalled at its second group.  With the ring only the upload kRing list changes back is waited
+// for.  The device block is one: the uploads and the kernels that read it are ordered by the plan's one stream.
 struct UploadedTable {
+    static constexpr int kRing = 4;
     const char* what;
-    PinnedBuf<unsigned char> h{false};
+    PinnedBuf<unsigned char> h[kRing];
     DevBuf<unsigned char> d;
-    hipEvent_t ev = nullptr;
+    hipEvent_t ev[kRing] = {};
+    int cur = 0;
     std::vector<int64_t> key;
     size_t bytes = 0;
-    explicit UploadedTable(const char* what_) : what(what_) {}
+    explicit UploadedTable(const char* what_) : what(what_) { for (auto& b : h) b.mapped = false; }
     UploadedTable(const UploadedTable&) = delete;
     UploadedTable& operator=(const UploadedTable&) = delete;
-    ~UploadedTable() { if (ev) (void)hipEventDestroy(ev); }
+    ~UploadedTable() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
     const unsigned char* get() const { return d.get(); }
     template <class Key>
     bool same(size_t n, Key&& at) const
@@ -253,19 +260,20 @@ struct UploadedTable {
     int begin(size_t nbytes, unsigned char** host)
     {
         key.clear();
-        if (ev) HIP_TRY(hipEventSynchronize(ev));          // (the previous upload may still read the host block)
-        if (int rc = h.grow(nbytes, 1)) return rc;
+        cur = (cur + 1) % kRing;
+        if (ev[cur]) HIP_TRY(hipEventSynchronize(ev[cur]));  // (the upload kRing changes back may still read this host block)
+        if (int rc = h[cur].grow(nbytes, 1)) return rc;
         if (int rc = d.grow(nbytes)) return rc;
         bytes = nbytes;
-        *host = h.h;
+        *host = h[cur].h;
         return 0;
     }
     template <class Key>
     int commit(hipStream_t st, size_t n, Key&& at)
     {
-        if (!ev) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        HIP_TRY(hipMemcpyAsync(d.get(), h.h, bytes, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipEventRecord(ev, st));
+        if (!ev[cur]) HIP_TRY(hipEventCreateWithFlags(&ev[cur], hipEventDisableTiming));
+        HIP_TRY(hipMemcpyAsync(d.get(), h[cur].h, bytes, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipEventRecord(ev[cur], st));
         try {
             key.resize(n);
         } catch (const std::bad_alloc&) {

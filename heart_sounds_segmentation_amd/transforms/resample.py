@@ -46,7 +46,7 @@ class _ResamplePlan:
              y: Optional[torch.Tensor], labels: Optional[torch.Tensor]) -> None:
         """x: float32 / float64 samples (its data pointer is the buffer's start); y / labels on x's side (host or device)."""
         on_dev = x.is_cuda
-        stream = torch.cuda.current_stream(self.device).cuda_stream if on_dev else None
+        stream = torch.cuda.current_stream(self.device).cuda_stream     # (host buffers too: staged and waited for on this stream)
         ydt = _lib.DTYPE_F64 if (y is not None and y.dtype == torch.float64) else _lib.DTYPE_F32
         rc = self._L.hssfsst_resample_exec(
             self.handle, ctypes.c_void_p(x.data_ptr()), _lib.DTYPE_F64 if x.dtype == torch.float64 else _lib.DTYPE_F32,
@@ -82,7 +82,7 @@ class _RaggedResamplePlan:
              labels: Optional[torch.Tensor]) -> None:
         """x: one float32 / float64 buffer (host or device); starts / lens: int64 host arrays; y / labels on x's side."""
         on_dev = x.is_cuda
-        stream = torch.cuda.current_stream(self.device).cuda_stream if on_dev else None
+        stream = torch.cuda.current_stream(self.device).cuda_stream     # (host buffers too: staged and waited for on this stream)
         ydt = _lib.DTYPE_F64 if (y is not None and y.dtype == torch.float64) else _lib.DTYPE_F32
         rc = self._L.hssfsst_resample_exec_ragged(
             self.handle, ctypes.c_void_p(x.data_ptr()), _lib.DTYPE_F64 if x.dtype == torch.float64 else _lib.DTYPE_F32,

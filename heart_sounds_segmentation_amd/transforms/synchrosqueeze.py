@@ -267,7 +267,7 @@ class FSST:
             raise ValueError(f"FSST: out must be a contiguous {dt} tensor of shape {shape} on {odev}")
         if B == 0 or K == 0:
             return out
-        stream = torch.cuda.current_stream(dev).cuda_stream if on_dev else None
+        stream = torch.cuda.current_stream(dev).cuda_stream     # (host buffers too: staged and waited for on this stream)
         rc = _lib.lib().hssfsst_exec_frames(plan.handle, ctypes.c_void_p(X.data_ptr()), int(B), int(n_in), xstride,
                                             int(col0), int(n), 1 if on_dev else 0,
                                             ctypes.c_void_p(out.data_ptr()), 1 if on_dev else 0,
@@ -390,7 +390,7 @@ class FSST:
         if B == 0 or K == 0:
             return out
         on_dev = x.is_cuda
-        stream = torch.cuda.current_stream(dev).cuda_stream if on_dev else None
+        stream = torch.cuda.current_stream(dev).cuda_stream     # (host buffers too: staged and waited for on this stream)
         rc = _lib.lib().hssfsst_exec_list(plan.handle, ctypes.c_void_p(x.data_ptr()), T, ctypes.c_void_p(starts.data_ptr()),
                                           1 if starts.is_cuda else 0, B, n, 1 if on_dev else 0,
                                           ctypes.c_void_p(out.data_ptr()), 1 if on_dev else 0,
@@ -484,7 +484,7 @@ class FSST:
         if out is None:
             out = torch.empty(shape, dtype=dt, device=odev)
         if K > 0:
-            stream = torch.cuda.current_stream(dev).cuda_stream if on_dev else None
+            stream = torch.cuda.current_stream(dev).cuda_stream     # (host buffers too: staged and waited for on this stream)
             lens_c = np.ascontiguousarray(lens)
             starts_c = np.ascontiguousarray(starts, dtype=np.int64)
             rc = L.hssfsst_exec_ragged(plan.handle, ctypes.c_void_p(X.data_ptr()), int(X.numel()), ctypes.c_void_p(starts_c.ctypes.data),

@@ -14,7 +14,9 @@
  *   - HIP is touched for the first time inside hssfsst_plan_create(), in the calling process
  *     (fork-safe for DataLoader workers: create the plan after the fork);
  *   - a plan is SINGLE-STREAM: its execs must be queued on one stream at a time (scratch buffers, the team kernel's arrival
- *     numbers and mailboxes belong to the plan); use one plan per stream.
+ *     numbers and mailboxes belong to the plan); use one plan per stream.  "At a time" is meant in DEVICE order: a plan may be
+ *     handed from one stream to another behind a host synchronisation or behind an event the new stream waits for (no host wait),
+ *     as long as every exec queued earlier is ordered before the first exec on the new stream (tests/test_stream_order.py);
  *   - hssfsst_exec() enqueues on `stream` (a hipStream_t, NULL = default stream) and returns
  *     without synchronising when both buffers are device buffers; with a host buffer on either
  *     side it stages through the plan's device scratch and synchronises before returning;
