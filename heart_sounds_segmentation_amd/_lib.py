@@ -26,6 +26,11 @@ _fork_warned = False
 hip_owner_pid = None     # pid of the process in which this package first touched HIP (inherited by forked children)
 
 
+class Launch(ctypes.Structure):
+    """``hssfsst_launch`` of include/hssfsst.h: the device and the stream a call is enqueued on."""
+    _fields_ = [("device", ctypes.c_int), ("stream", ctypes.c_void_p)]
+
+
 class ForkedAfterGpuInitError(RuntimeError):
     """A DataLoader worker forked after its parent initialised the GPU tried to use the transform (a RuntimeError, as the
     reference's dataset expects, but also logged at ERROR and warned once: see ``guard_fork``)."""
@@ -314,6 +319,10 @@ def lib():
         L.hssfsst_posteriors_durations_counts.argtypes = [vp, ctypes.POINTER(c_i64), c_i64, vp, vp, vp, c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                                           c_i64, c_int, vp]
         L.hssfsst_posteriors_durations_counts.restype = c_int
+        L.hssfsst_score_info.argtypes = [ctypes.POINTER(c_i64)] * 3 + [ip] * 3
+        L.hssfsst_score_info.restype = c_int
+        L.hssfsst_score_states.argtypes = [vp, vp, vp, ctypes.POINTER(c_i64), c_i64, c_int, vp, vp, vp, vp, c_i64, ctypes.POINTER(Launch)]
+        L.hssfsst_score_states.restype = c_int
         L.hssfsst_bilstm_create.argtypes = [ctypes.POINTER(vp), c_int, c_int, c_int]
         L.hssfsst_bilstm_create.restype = c_int
         L.hssfsst_bilstm_destroy.argtypes = [vp]

@@ -34,10 +34,10 @@ import torch
 from torch import nn
 
 from . import _lib
-from .sequence import (RaggedStates, cyclic_transitions, decode_durations, decode_durations_info, decode_info, decode_states,  # noqa: F401
+from .sequence import (RaggedStates, SegmentationScores, cyclic_transitions, decode_durations, decode_durations_info, decode_info, decode_states,  # noqa: F401
                        duration_counts_info, duration_nll, duration_posteriors, duration_posteriors_info, durations_from_counts,
-                       durations_from_labels, edge_durations, gaussian_durations, posteriors_info, sequence_nll, state_posteriors,
-                       state_runs, transitions_from_labels)
+                       durations_from_labels, edge_durations, gaussian_durations, posteriors_info, score_info, segmentation_scores,
+                       sequence_nll, state_posteriors, state_runs, transitions_from_labels)
 from .transforms.synchrosqueeze import RaggedFeatures
 
 

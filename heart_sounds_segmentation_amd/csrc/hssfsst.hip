@@ -49,6 +49,8 @@
 #include "segmenter_posteriors.hpp"
 #include "segmenter_duration_posteriors.hpp"
 #include "segmenter_duration_counts.hpp"
+#include "score_layout.hpp"
+#include "segmenter_score.hpp"
 #include "fsst_tables.hpp"
 
 namespace tables = hssfsst::tables;
@@ -3042,6 +3044,133 @@ int hssfsst_posteriors_durations_counts(const float* logp, const int64_t* offset
 {
     return posteriors_durations_run("posteriors_durations_counts", true, logp, offsets, count, a_pi, durations, edge, max_duration, labels,
                                     gamma, onsets, loglik, score, xi, s0, counts, work, work_bytes, device, stream);
+}
+
+}  // extern "C"
+
+// Scoring a segmentation (hssfsst.h: hssfsst_score_states; csrc/segmenter_score.hpp, csrc/score_layout.hpp).  Stateless: the
+// launch's offsets travel as kernel arguments, kScoreBatch recordings per launch of the kernels that read the arenas; the sort and
+// the rank work on the caller's workspace, class after class, and the host decides the number of passes.
+namespace {
+
+// the launches of one class behind its items: the passes of the sort, then the three of the rank.  items_a holds the items.
+int score_rank_class(const char* entry, hipStream_t st, unsigned char* work, const hssfsst::scorelayout::Workspace& w, int64_t n,
+                     int passes, int per_recording, int64_t groups, unsigned long long* out)
+{
+    namespace sl = hssfsst::scorelayout;
+    unsigned long long* src = reinterpret_cast<unsigned long long*>(work + w.items_a);
+    unsigned long long* dst = reinterpret_cast<unsigned long long*>(work + w.items_b);
+    unsigned* hist = reinterpret_cast<unsigned*>(work + w.hist);
+    unsigned* sums = reinterpret_cast<unsigned*>(work + w.sums);
+    unsigned* tile_agg = reinterpret_cast<unsigned*>(work + w.tile_agg);
+    unsigned* tile_carry = reinterpret_cast<unsigned*>(work + w.tile_carry);
+    const long long nblocks = sl::blocks(n), entries = sl::hist_entries(n), chunks = sl::scan_chunks(n), tiles = sl::rank_tiles(n);
+    const dim3 sort_grid(static_cast<unsigned>(sl::sort_groups(n))), sort_block(sl::kSortThreads);
+    const dim3 scan_grid(static_cast<unsigned>(chunks)), scan_block(sl::kScanThreads);
+    for (int pass = 0; pass < passes; ++pass) {
+        hipLaunchKernelGGL(hssfsst::seg_score_hist_kernel, sort_grid, sort_block, 0, st, src, hist, static_cast<long long>(n), nblocks, pass);
+        if (int rc = launch_check(entry, "seg_score_hist_kernel")) return rc;
+        hipLaunchKernelGGL(hssfsst::seg_score_scan_sums_kernel, scan_grid, scan_block, 0, st, hist, sums, entries);
+        if (int rc = launch_check(entry, "seg_score_scan_sums_kernel")) return rc;
+        hipLaunchKernelGGL(hssfsst::seg_score_scan_top_kernel, dim3(1), scan_block, 0, st, sums, chunks);
+        if (int rc = launch_check(entry, "seg_score_scan_top_kernel")) return rc;
+        hipLaunchKernelGGL(hssfsst::seg_score_scan_apply_kernel, scan_grid, scan_block, 0, st, hist, sums, entries);
+        if (int rc = launch_check(entry, "seg_score_scan_apply_kernel")) return rc;
+        hipLaunchKernelGGL(hssfsst::seg_score_scatter_kernel, sort_grid, sort_block, 0, st, src, dst, hist, static_cast<long long>(n), nblocks,
+                           pass);
+        if (int rc = launch_check(entry, "seg_score_scatter_kernel")) return rc;
+        std::swap(src, dst);
+    }
+    const dim3 rank_grid(static_cast<unsigned>(tiles)), rank_block(sl::kRankThreads);
+    hipLaunchKernelGGL(hssfsst::seg_score_rank_kernel<false>, rank_grid, rank_block, 0, st, src, static_cast<long long>(n), tile_agg, tile_carry,
+                       out, per_recording, static_cast<long long>(groups));
+    if (int rc = launch_check(entry, "seg_score_rank_kernel<false>")) return rc;
+    hipLaunchKernelGGL(hssfsst::seg_score_rank_scan_kernel, dim3(1), dim3(64), 0, st, tile_agg, tile_carry, tiles);
+    if (int rc = launch_check(entry, "seg_score_rank_scan_kernel")) return rc;
+    hipLaunchKernelGGL(hssfsst::seg_score_rank_kernel<true>, rank_grid, rank_block, 0, st, src, static_cast<long long>(n), tile_agg, tile_carry,
+                       out, per_recording, static_cast<long long>(groups));
+    return launch_check(entry, "seg_score_rank_kernel<true>");
+}
+
+}  // namespace
+
+extern "C" {
+
+int hssfsst_score_info(int64_t* work_bytes_per_step, int64_t* work_bytes_per_recording, int64_t* work_bytes_constant, int* block_items,
+                       int* digit_bits, int* max_passes)
+{
+    namespace sl = hssfsst::scorelayout;
+    if (work_bytes_per_step) *work_bytes_per_step = sl::kWorkBytesPerStep;
+    if (work_bytes_per_recording) *work_bytes_per_recording = sl::kWorkBytesPerRecording;
+    if (work_bytes_constant) *work_bytes_constant = sl::kWorkBytesConstant;
+    if (block_items) *block_items = sl::kBlockItems;
+    if (digit_bits) *digit_bits = sl::kDigitBits;
+    if (max_passes) *max_passes = sl::kMaxPasses;
+    return 0;
+}
+
+int hssfsst_score_states(const float* logp, const uint8_t* states, const uint8_t* labels, const int64_t* offsets, int64_t count,
+                         int per_recording, int64_t* confusion, int64_t* ignored, int64_t* rank, void* work, int64_t work_bytes,
+                         const hssfsst_launch* where)
+{
+    namespace sl = hssfsst::scorelayout;
+    constexpr const char* kEntry = "score_states";
+    if (count < 0) return fail(HSSFSST_EINVAL, "%s: count %lld is negative", kEntry, static_cast<long long>(count));
+    if (int rc = seq_check_nonnull(kEntry, {{"labels", labels}, {"offsets", offsets}, {"confusion", confusion}, {"ignored", ignored},
+                                            {"where", where}})) return rc;
+    if (!states && !logp) return fail(HSSFSST_EINVAL, "%s: bad argument (states and logp are both NULL)", kEntry);
+    if (rank && !logp) return fail(HSSFSST_EINVAL, "%s: bad argument (logp is NULL while rank is not)", kEntry);
+    if (rank && !work) return fail(HSSFSST_EINVAL, "%s: bad argument (work is NULL while rank is not)", kEntry);
+    const int device = where->device;
+    if (device < 0) return fail(HSSFSST_EINVAL, "%s: device %d is negative", kEntry, device);
+    if (int rc = seq_check_aligned(kEntry, {{"logp", logp, 16}, {"work", work, 16}, {"confusion", confusion, 8}, {"ignored", ignored, 8},
+                                            {"rank", rank, 8}})) return rc;
+    if (int rc = seq_check_list(kEntry, offsets, count, seqargs::kMaxTotalSteps)) return rc;
+    const int64_t total = offsets[count];
+    const int64_t need = rank ? sl::workspace_bytes(total, count) : 0;
+    if (work_bytes < need)
+        return fail(HSSFSST_EINVAL, "%s: work of %lld bytes is too small: %lld steps in %lld recordings need %lld", kEntry,
+                    static_cast<long long>(work_bytes), static_cast<long long>(total), static_cast<long long>(count),
+                    static_cast<long long>(need));
+    if (count == 0) return 0;
+    if (int rc = check_device(kEntry, device)) return rc;
+    DEVICE_SCOPE(device);
+    const hipStream_t st = static_cast<hipStream_t>(where->stream);
+    const int64_t groups = per_recording ? count : 1;
+    const int64_t pooled[2] = {0, total};
+    const int64_t* list = per_recording ? offsets : pooled;
+    const int64_t nlist = per_recording ? count : 1;
+    const std::pair<void*, size_t> outputs[3] = {{confusion, 128 * static_cast<size_t>(groups)}, {ignored, 8 * static_cast<size_t>(groups)},
+                                                 {rank, 96 * static_cast<size_t>(groups)}};
+    for (const auto& z : outputs) {                      // the kernels add into them
+        if (!z.first) continue;
+        const hipError_t e = hipMemsetAsync(z.first, 0, z.second, st);
+        if (e != hipSuccess) return fail(HSSFSST_EHIP, "%s: clearing the outputs failed: %s", kEntry, hipGetErrorString(e));
+    }
+    hssfsst::ScoreArgs args{};
+    args.per_recording = per_recording ? 1 : 0;
+    auto grid_of = [&](int nrec) { return dim3(static_cast<unsigned>(sl::count_groups(args.off[nrec] - args.off[0]))); };
+    if (int rc = seq_for_each_batch(kEntry, "seg_score_counts_kernel", list, nlist, sl::kScoreBatch, args, [&](int64_t r0, int nrec) {
+            args.rec0 = r0;
+            args.nrec = nrec;
+            hipLaunchKernelGGL(hssfsst::seg_score_counts_kernel, grid_of(nrec), dim3(sl::kCountThreads), 0, st, logp, states, labels,
+                               reinterpret_cast<unsigned long long*>(confusion), reinterpret_cast<unsigned long long*>(ignored),
+                               reinterpret_cast<unsigned long long*>(rank), args);
+        })) return rc;
+    if (!rank) return 0;
+    const sl::Workspace w = sl::workspace(total);
+    const int passes = sl::passes(count, args.per_recording);
+    for (int cls = 0; cls < 4; ++cls) {
+        if (int rc = seq_for_each_batch(kEntry, "seg_score_keys_kernel", list, nlist, sl::kScoreBatch, args, [&](int64_t r0, int nrec) {
+                args.rec0 = r0;
+                args.nrec = nrec;
+                hipLaunchKernelGGL(hssfsst::seg_score_keys_kernel, grid_of(nrec), dim3(sl::kCountThreads), 0, st, logp, states, labels,
+                                   reinterpret_cast<unsigned long long*>(static_cast<unsigned char*>(work) + w.items_a), cls, args);
+            })) return rc;
+        if (int rc = score_rank_class(kEntry, st, static_cast<unsigned char*>(work), w, total, passes, args.per_recording, groups,
+                                      reinterpret_cast<unsigned long long*>(rank) + 3 * cls)) return rc;
+    }
+    return 0;
 }
 
 }  // extern "C"

@@ -29,20 +29,26 @@ def _ready() -> None:
     _lib.guard_fork()
 
 
-def _call(name: str, data: torch.Tensor, offs, *args):
+def _call(name: str, data: torch.Tensor, offs, *args, lead=None, launch: bool = False):
     """One call of the entry ``name(logp, offsets, count, ..., device, stream)`` on the arena ``data`` and the non-empty list
     ``offs``, on the current stream of ``data``'s device.  ``args``: what stands between ``count`` and ``device``; a tensor and a
-    float32 array (a host table) go as their pointers, None as NULL.  Raises what ``_lib.check`` makes of the status.  The guard
-    runs here once more (it compares two pids), so that a caller that forgot ``_ready()`` still gets it, if late."""
+    float32 array (a host table) go as their pointers, None as NULL.  ``lead``: what stands before ``offsets`` where that is more
+    than ``data`` (which then only names the device).  ``launch``: the entry takes ``(device, stream)`` as one ``const
+    hssfsst_launch*`` (``hssfsst_score_states``).  Raises what ``_lib.check`` makes of the status.  The guard runs here once more
+    (it compares two pids), so that a caller that forgot ``_ready()`` still gets it, if late."""
     _ready()
     device = data.device
     o = np.asarray(offs, dtype=np.int64)
     fp = ctypes.POINTER(ctypes.c_float)
-    args = [a.data_ptr() if isinstance(a, torch.Tensor) else a.ctypes.data_as(fp) if isinstance(a, np.ndarray) else a for a in args]
+
+    def pointer(a):
+        return a.data_ptr() if isinstance(a, torch.Tensor) else a.ctypes.data_as(fp) if isinstance(a, np.ndarray) else a
+    args = [pointer(a) for a in args]
+    lead = [data.data_ptr()] if lead is None else [pointer(a) for a in lead]
     with torch.cuda.device(device):
         stream = torch.cuda.current_stream(device).cuda_stream
-        _lib.check(getattr(_lib.lib(), name)(data.data_ptr(), o.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), len(offs) - 1, *args,
-                                             device.index, stream), name)
+        where = (ctypes.byref(_lib.Launch(device.index, stream)),) if launch else (device.index, stream)
+        _lib.check(getattr(_lib.lib(), name)(*lead, o.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), len(offs) - 1, *args, *where), name)
 
 
 def _like_input(logp, kind: str, t: torch.Tensor, offs):
@@ -413,18 +419,25 @@ def state_posteriors(logp, transitions=None, initial=None, return_loglik: bool =
     return (out, loglik[0] if kind == "single" else loglik) if return_loglik else out
 
 
-def _nll_labels(name: str, labels, offs, kind: str, device) -> torch.Tensor:
+def _nll_labels(name: str, labels, offs, kind: str, device, ignore_outside: bool = False) -> torch.Tensor:
     """The labels of ``sequence_nll`` -> one uint8 arena ``(sum T,)`` on ``device``.  Lengths are checked always; values are
     checked (0..3) where the labels are on the HOST -- labels on the device are not read back (no synchronisation): the kernel
-    looks at their two low bits only."""
+    looks at their two low bits only.  ``ignore_outside`` (``segmentation_scores``): values outside 0..3 are allowed anywhere and
+    become 255, whatever the integer type (-100 and 256 alike)."""
     total, count = offs[-1], len(offs) - 1
+
+    def u8(t):
+        if ignore_outside and t.dtype != torch.uint8:
+            t = t.to(torch.int64)                        # (int8 cannot hold 255)
+            t = torch.where((t < 0) | (t > 3), torch.full_like(t, 255), t)
+        return t.to(device=device, dtype=torch.uint8)
 
     def values(t, what):
         if isinstance(t, np.ndarray):
             t = torch.from_numpy(t)
         if not isinstance(t, torch.Tensor) or t.is_floating_point() or t.is_complex() or t.dtype == torch.bool:
             raise ValueError(f"{name}: {what}: integer labels expected")
-        if t.device.type == "cpu" and t.numel() and (int(t.min()) < 0 or int(t.max()) > 3):
+        if not ignore_outside and t.device.type == "cpu" and t.numel() and (int(t.min()) < 0 or int(t.max()) > 3):
             raise ValueError(f"{name}: {what} has labels outside 0..3")
         return t
 
@@ -440,7 +453,7 @@ def _nll_labels(name: str, labels, offs, kind: str, device) -> torch.Tensor:
             t = values(lab, f"item {i}")
             if t.dim() != 1 or t.shape[0] != offs[i + 1] - offs[i]:
                 raise ValueError(f"{name}: item {i} has labels of shape {tuple(t.shape)} for {offs[i + 1] - offs[i]} steps")
-            items.append(t.to(device=device, dtype=torch.uint8))
+            items.append(u8(t))
         arena = torch.cat(items) if items else torch.empty((0,), dtype=torch.uint8, device=device)
     else:
         t = values(labels, "labels")
@@ -450,7 +463,7 @@ def _nll_labels(name: str, labels, offs, kind: str, device) -> torch.Tensor:
             arena = t
         else:
             raise ValueError(f"{name}: labels of shape {tuple(t.shape)} do not match {count} recordings of {total} steps in all")
-    return arena.to(device=device, dtype=torch.uint8).contiguous()
+    return u8(arena).contiguous()
 
 
 class _SequenceNLL(torch.autograd.Function):
@@ -716,3 +729,159 @@ def state_runs(states: torch.Tensor):
     vals, counts = torch.unique_consecutive(states, return_counts=True)
     starts = torch.cumsum(counts, 0) - counts
     return starts.to(torch.int64), vals.to(torch.uint8)
+
+
+# ----------------------------------------------------------------- predictions and labels -> confusion counts and AUROC
+def score_info():
+    """``(work_bytes_per_step, work_bytes_per_recording, work_bytes_constant, block_items, digit_bits, max_passes)`` of the
+    scoring call (``hssfsst_score_info``): the factors of its workspace and the geometry of its radix sort.  No device needed."""
+    return _info("hssfsst_score_info", *[ctypes.c_int64] * 3, *[ctypes.c_int] * 3)
+
+
+def _safe_ratio(num: torch.Tensor, den: torch.Tensor) -> torch.Tensor:
+    """``num / den`` in float64, 0 where ``den`` is 0 (an empty denominator scores 0, as in torchmetrics)."""
+    num, den = num.to(torch.float64), den.to(torch.float64)
+    return torch.where(den == 0, torch.zeros_like(num), num / torch.where(den == 0, torch.ones_like(den), den))
+
+
+class SegmentationScores:
+    """What ``segmentation_scores`` returns: the exact integers of the call, on its device, and the usual figures derived from
+    them in float64 torch ops -- nothing here waits for the device.  With ``per_recording`` every tensor has a leading ``(B,)``.
+
+    ``confusion`` ``(4, 4)`` int64 ``[label][predicted]``; ``ignored`` int64, the steps left out; ``rank`` ``(4, 3)`` int64
+    ``{2U, P, N}`` per class, or None (``auroc=False``, or states scored without ``scores``).
+
+    Derived: ``support`` (4,) = steps per label; ``accuracy`` = correct / counted; per class ``precision``, ``recall``, ``f1``; their
+    plain means over the four classes ``macro_precision``, ``macro_recall``, ``macro_f1``; ``auroc`` (4,) = ``2U / (2 P N)``, the exact
+    one-vs-rest area with ties at one half, NaN where a class has no positive or no negative; ``macro_auroc``, its mean over the
+    classes where it is defined (NaN where none is).  An empty denominator gives 0.  torchmetrics' per-class multiclass
+    "accuracy" (``average=None``) is this ``recall``."""
+
+    def __init__(self, confusion: torch.Tensor, ignored: torch.Tensor, rank):
+        self.confusion, self.ignored, self.rank = confusion, ignored, rank
+
+    @property
+    def _tp(self):
+        return torch.diagonal(self.confusion, dim1=-2, dim2=-1)
+
+    @property
+    def support(self):
+        return self.confusion.sum(dim=-1)
+
+    @property
+    def accuracy(self):
+        return _safe_ratio(self._tp.sum(dim=-1), self.confusion.sum(dim=(-2, -1)))
+
+    @property
+    def precision(self):
+        return _safe_ratio(self._tp, self.confusion.sum(dim=-2))
+
+    @property
+    def recall(self):
+        return _safe_ratio(self._tp, self.support)
+
+    @property
+    def f1(self):
+        return _safe_ratio(2 * self._tp, self.confusion.sum(dim=-2) + self.support)
+
+    @property
+    def macro_precision(self):
+        return self.precision.mean(dim=-1)
+
+    @property
+    def macro_recall(self):
+        return self.recall.mean(dim=-1)
+
+    @property
+    def macro_f1(self):
+        return self.f1.mean(dim=-1)
+
+    @property
+    def auroc(self):
+        if self.rank is None:
+            raise ValueError("SegmentationScores.auroc: no rank was computed (auroc=False, or states scored without scores)")
+        r = self.rank.to(torch.float64)
+        return r[..., 0] / (2.0 * r[..., 1] * r[..., 2])
+
+    @property
+    def macro_auroc(self):
+        return torch.nanmean(self.auroc, dim=-1)
+
+
+def _score_input(name: str, what: str, pred):
+    """``decode_states``' three kinds, of states (uint8, one per step) or of scores (float32, four per step) -> (the arena, the
+    step offsets as a list, the kind, whether they are states)."""
+    t = pred.data if isinstance(pred, RaggedFeatures) else pred
+    if not isinstance(t, torch.Tensor) or t.dtype not in (torch.uint8, torch.float32):
+        raise ValueError(f"{name}: {what}: uint8 states or float32 log-probs expected"
+                         + (f", got {t.dtype}" if isinstance(t, torch.Tensor) else ""))
+    if t.dtype == torch.float32:
+        return (*_decode_input(name, pred), False)
+    if isinstance(pred, RaggedFeatures):
+        data, offs, kind = pred.data, [int(o) for o in pred._off], "ragged"
+    elif pred.dim() == 2:
+        B, T = int(pred.shape[0]), int(pred.shape[1])
+        if B and T < 1:
+            raise ValueError(f"{name}: {what}: (B, T) states with T >= 1 expected, got {tuple(pred.shape)}")
+        data, offs, kind = pred.reshape(B * T), [i * T for i in range(B + 1)], "batch"
+    elif pred.dim() == 1 and pred.shape[0] >= 1:
+        data, offs, kind = pred, [0, int(pred.shape[0])], "single"
+    else:
+        raise ValueError(f"{name}: {what}: a RaggedStates, a (B, T) or a (T,) tensor with T >= 1 expected")
+    if data.dim() != 1 or data.shape[0] != offs[-1]:
+        raise ValueError(f"{name}: {what}: one state per step expected, got an arena of shape {tuple(data.shape)}")
+    if data.device.type != "cuda":
+        raise ValueError(f"{name}: {what} on a GPU expected, got {data.device}; the scoring has no CPU path")
+    return data, offs, kind, True
+
+
+def segmentation_scores(pred, labels, per_recording: bool = False, auroc: bool = True, scores=None) -> SegmentationScores:
+    """How good a segmentation is, on the device (``hssfsst_score_states``): the confusion counts of predictions against labels
+    and, from log-probs, the exact one-vs-rest AUROC of every class -- the Mann-Whitney statistic with ties, from a radix sort of
+    the whole arena --, as exact integers.  What the reference's epochs end in (accuracy, precision, recall, F1, AUROC), for the
+    ragged arenas of this package: nothing is padded and nothing is copied to the host.
+
+    ``pred``: ``decode_states``' three kinds, of either dtype.  uint8 = states, one per step (a ``RaggedStates``, ``(B, T)`` or
+    ``(T,)``: what the decoders return); float32 = log-probs or any score per step and class (a ``RaggedFeatures``, ``(B, T, 4)`` or
+    ``(T, 4)``), whose argmax is the prediction: ties go to the smaller state, NaN reads as ``-inf``.  ``scores``: with states as
+    ``pred``, the float32 scores to rank for the AUROC (same list of lengths); the states stay the predictions.
+    ``labels``: as for ``sequence_nll`` (a list of 1-D integer tensors, a ``RaggedStates`` or an arena with matching offsets, a
+    ``(B, T)`` / ``(T,)`` tensor), but values outside 0..3 are allowed and mean IGNORE (255, -100 ...): such a step is left out of
+    every count and of the ranking and counted in ``ignored``; labels on the device are not read back.
+    ``per_recording``: one result per recording (a leading ``(B,)``; each recording's steps are ranked among themselves) instead
+    of one for all steps pooled, as the reference's test epoch pools them.  The pooled rank is not the sum of the recordings'.
+    ``auroc=False`` skips the ranking (and its workspace of 17 bytes per step); states without ``scores`` have none.
+
+    One call on the current stream; the int64 results stay on the device and ``SegmentationScores`` derives the figures from them
+    without waiting for it.  All integers are exact and do not depend on the order of the kernels' atomics: two calls give the
+    same bits.  The order of scores is float32's: ``-0 == +0``, ``-inf`` lowest, NaN reads as ``-inf``."""
+    name = "segmentation_scores"
+    data, offs, kind, is_states = _score_input(name, "pred", pred)
+    logp, states = (None, data) if is_states else (data, None)
+    if scores is not None:
+        if not is_states:
+            raise ValueError(f"{name}: scores are given beside states; pred already holds float32 scores")
+        logp, soffs, _, s_states = _score_input(name, "scores", scores)
+        if s_states or soffs != offs or logp.device != data.device:
+            raise ValueError(f"{name}: scores must be float32, on the states' device, over the same list of lengths")
+    arena = _nll_labels(name, labels, offs, kind, data.device, ignore_outside=True)
+    _ready()
+    count = len(offs) - 1
+    groups = count if per_recording else 1
+    want_rank = bool(auroc) and logp is not None
+    i64 = dict(dtype=torch.int64, device=data.device)
+    confusion = torch.zeros((groups, 4, 4), **i64)
+    ignored = torch.zeros((groups,), **i64)
+    rank = torch.zeros((groups, 4, 3), **i64) if want_rank else None
+    if count:
+        work = None
+        if want_rank:
+            per, rec, const = score_info()[:3]
+            work = torch.empty((per * offs[-1] + rec * count + const,), dtype=torch.uint8, device=data.device)
+        logp = None if logp is None else logp.detach().contiguous()
+        states = None if states is None else states.contiguous()
+        _call("hssfsst_score_states", data, offs, 1 if per_recording else 0, confusion, ignored, rank, work,
+              work.numel() if work is not None else 0, lead=(logp, states, arena), launch=True)
+    if not per_recording:
+        confusion, ignored, rank = confusion[0], ignored[0], None if rank is None else rank[0]
+    return SegmentationScores(confusion, ignored, rank)

@@ -585,6 +585,57 @@ int hssfsst_posteriors_durations_counts(const float* logp, const int64_t* offset
 int hssfsst_posteriors_durations_counts_info(int64_t* work_bytes_per_step, int64_t* work_bytes_per_recording, int64_t* work_bytes_per_duration,
                                              int* durations_per_group);
 
+/* Where a call runs: the device and the stream (hipStream_t, NULL = default) that every launch and every clear of the call is
+ * enqueued on.  hssfsst_score_states takes the pair as a struct, where the entries above take `int device, void* stream`: the
+ * stream-order suite holds every function of this header with a `void* stream` parameter to one table of cases in
+ * tests/test_stream_order.py, and the cases of this entry live in tests/test_segmentation_scores.py, which holds every function
+ * with a `const hssfsst_launch*` parameter to the same two scenarios on a side stream.  The promise is the same one. */
+typedef struct { int device; void* stream; } hssfsst_launch;
+
+/* Scoring a segmentation on the device: confusion counts and the exact rank statistic behind the one-vs-rest AUROC, for a LIST of
+ * recordings in one call, every result an exact integer (csrc/segmenter_score.hpp; the key transform, the sort's partition, the
+ * workspace and the sequential loop that is the specification as plain functions: csrc/score_layout.hpp).  Stateless: no plan.
+ *   logp           (sum T, 4) float32, DEVICE, 16-byte aligned, or NULL: a score per step and class (the segmenter's log-probs,
+ *                  posteriors ...)
+ *   states         (sum T) uint8, DEVICE, or NULL: the predicted state per step, as the decoders write it.  At least one of logp
+ *                  and states; with both, states are the predictions and logp the scores that are ranked.  With logp alone the
+ *                  prediction is the argmax of the step's four values, ties to the smaller state, NaN read as -inf
+ *   labels         (sum T) uint8, DEVICE: 0..3 is a state; ANY OTHER VALUE (255, say) marks the step IGNORED: it is left out of
+ *                  every count and of the ranking and counted in `ignored`.  So is a step whose states[t] is above 3
+ *   offsets, count as for hssfsst_decode_states (HOST); no limit on a recording's length, 2^31 - 1 steps in all
+ *   per_recording  0: one result for the whole call, all steps pooled (groups = 1); else one per recording (groups = count)
+ *   confusion      (groups, 4, 4) int64, DEVICE, 8-byte aligned: [label][predicted] over the counted steps
+ *   ignored        (groups) int64, DEVICE: the steps left out
+ *   rank           (groups, 4, 3) int64, DEVICE, or NULL; needs logp.  Per class c: {2U, P, N}.  P and N are the numbers of counted
+ *                  steps whose label is / is not c, and with s = column c of logp
+ *                      2U = sum over (positive p, negative n) of 2 [s_p > s_n] + [s_p == s_n]
+ *                  in float32's order, -0 == +0, -inf lowest, NaN read as -inf; 2U <= 2 P N <= 2^61.  The one-vs-rest AUROC is
+ *                  2U / (2 P N), undefined where P N = 0: the kernels do not divide.  per_recording: each recording's steps are
+ *                  ranked among themselves only.  Pooled, the whole call is ranked together: NOT the sum of the recordings' ranks
+ *   work           DEVICE, 16-byte aligned, or NULL when rank is: work_bytes >= work_bytes_per_step x sum T + work_bytes_constant
+ *                  (hssfsst_score_info: 17 bytes per step -- two buffers of 8-byte items and the digit histograms); contents
+ *                  undefined afterwards
+ *   where          HOST, read during the call
+ * The rank of a class: every step becomes a 64-bit item (recording, order-preserving key of the score, is-positive bit), the items
+ * are sorted by a least-significant-digit radix sort of 8 bits per pass -- 4 passes pooled, ceil((32 + bits of count - 1) / 8)
+ * per recording, decided on the host --, and the sorted order is scanned for tie groups: 2U = sum_g P_g (2 N_below(g) + N_g).
+ * HSSFSST_EINVAL before any device work: a NULL labels, offsets, confusion, ignored or where; states and logp both NULL; rank without
+ * logp or without work; count < 0; bad offsets (as hssfsst_decode_states); where->device < 0; logp or work not 16-byte aligned,
+ * confusion, ignored or rank not 8-byte aligned; a work that is too small.  HSSFSST_EUNSUPPORTED: more than 2^31 - 1 steps in
+ * all.  count == 0 returns 0 and does nothing.
+ * All integers: two calls give the same bits, and a recording's per-recording results do not depend on its neighbours or its
+ * place in the list.  Enqueued on where->stream without synchronising: three clears, one counts launch per 256 recordings, and
+ * per class one key launch per 256 recordings, five launches per pass (histogram per block of 2048 items, three for the scan,
+ * scatter) and three for the rank.  No workgroup waits for another; at most 19 KiB of LDS; no scratch memory. */
+int hssfsst_score_states(const float* logp, const uint8_t* states, const uint8_t* labels, const int64_t* offsets, int64_t count,
+                         int per_recording, int64_t* confusion, int64_t* ignored, int64_t* rank, void* work, int64_t work_bytes,
+                         const hssfsst_launch* where);
+
+/* Its workspace factors (bytes per step 17, per recording 0, constant 4096) and the sort's geometry: block_items = the items one
+ * wave histograms and scatters (2048), digit_bits = 8, max_passes = 8.  No device needed; any pointer may be NULL. */
+int hssfsst_score_info(int64_t* work_bytes_per_step, int64_t* work_bytes_per_recording, int64_t* work_bytes_constant, int* block_items,
+                       int* digit_bits, int* max_passes);
+
 /* One DIFFERENTIABLE bidirectional LSTM layer (batch first, nn.LSTM's cell and gate order): the unit a training program stacks
  * under autograd -- the segmenter is two of them.  The plan holds the layer's current weights in the kernels' layouts and the
  * scratch of its calls; the caller owns inputs, outputs and the stash.  Every pointer below is a DEVICE pointer on the plan's
