@@ -10,6 +10,7 @@ float64 resolution: a different summation order may round it the other way) and 
 a fragile column that agrees is just a column: tools/fuzz_parity.py seed 13 drew a signal with three of them, all within
 8e-8 of the oracle -- and inside them the error must still be explainable by a moved cell (|err| bounded by twice the
 signal's largest feature).
+What the kernels are held to beyond this contract -- 8 x float32's own error per 64-column block: tests/test_fsst_precision.py.
 """
 import numpy as np
 
