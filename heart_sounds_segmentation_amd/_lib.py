@@ -19,6 +19,7 @@ HEADER = os.path.join(os.path.dirname(_PKG), "include", "hssfsst.h")
 MODE_RAW, MODE_ABS, MODE_STACK, MODE_STACK_UNNORM = 0, 1, 2, 3
 E_INVAL, E_NODEVICE, E_UNSUPPORTED, E_NOMEM, E_HIP = -1, -2, -3, -4, -5
 DTYPE_F32, DTYPE_F64, DTYPE_F16, DTYPE_BF16 = 0, 1, 2, 3
+STITCH_PROB, STITCH_LOGP, STITCH_SELECT = 0, 1, 2
 
 _lock = threading.Lock()
 _lib = None
@@ -323,6 +324,8 @@ def lib():
         L.hssfsst_score_info.restype = c_int
         L.hssfsst_score_states.argtypes = [vp, vp, vp, ctypes.POINTER(c_i64), c_i64, c_int, vp, vp, vp, vp, c_i64, ctypes.POINTER(Launch)]
         L.hssfsst_score_states.restype = c_int
+        L.hssfsst_stitch_windows.argtypes = [vp, ctypes.POINTER(c_i64), c_i64, ctypes.POINTER(c_i64), c_i64, c_int, c_int, vp, c_int, vp, vp, Launch]
+        L.hssfsst_stitch_windows.restype = c_int
         L.hssfsst_bilstm_create.argtypes = [ctypes.POINTER(vp), c_int, c_int, c_int]
         L.hssfsst_bilstm_create.restype = c_int
         L.hssfsst_bilstm_destroy.argtypes = [vp]

@@ -13,7 +13,8 @@ was produced by the reference class itself (tests/golden/make_golden.py).
 hssfsst_segmenter_exec; csrc/segmenter_lstm.hpp), inference only: ``segment(fsst, head.hip(), windows)`` is
 config 4 with nothing leaving the device and no torch op between the FSST kernel and the log-probs.  Whole recordings of
 different lengths go through ``segment_recordings(fsst, head.hip(), recordings)`` (``HipSegmenter.ragged``,
-hssfsst_segmenter_exec_ragged) in one call.
+hssfsst_segmenter_exec_ragged) in one call, or window by window, as the reference trains its model, through
+``segment_windowed(fsst, head.hip(), recordings)``, which stitches the windows' log-probs on the device (hssfsst_stitch_windows).
 
 ``HipBiLSTM`` is one differentiable bidirectional layer on the HIP recurrences (hssfsst_bilstm_*; csrc/segmenter_train.hpp) and
 ``HipSegmenterHead`` the same model built from two of them: what a training script uses instead of the ``nn.LSTM`` model.  Both
@@ -34,10 +35,11 @@ import torch
 from torch import nn
 
 from . import _lib
+from .framing import cover_starts
 from .sequence import (RaggedStates, SegmentationScores, cyclic_transitions, decode_durations, decode_durations_info, decode_info, decode_states,  # noqa: F401
                        duration_counts_info, duration_nll, duration_posteriors, duration_posteriors_info, durations_from_counts,
                        durations_from_labels, edge_durations, gaussian_durations, posteriors_info, score_info, segmentation_scores,
-                       sequence_nll, state_posteriors, state_runs, transitions_from_labels)
+                       sequence_nll, state_posteriors, state_runs, stitch_windows, transitions_from_labels, window_weights)
 from .transforms.synchrosqueeze import RaggedFeatures
 
 
@@ -587,14 +589,24 @@ def segment_recordings(fsst, seg: HipSegmenter, recordings, decode=None, duratio
     ``posteriors=True`` or ``posteriors=(A, pi)``: they go on to ``state_posteriors`` instead and the ``RaggedFeatures`` of
     ``(T_i, 4)`` float32 posteriors is returned, with ``durations=dur`` those of ``duration_posteriors`` under that table and its
     default ``edge``; not together with ``decode`` (ValueError).  ``durations`` without either raises ValueError."""
+    _check_route("segment_recordings", decode, durations, posteriors)
+    return _route(seg.ragged(fsst.ragged(recordings), **kw), decode, durations, posteriors)
+
+
+def _check_route(name: str, decode, durations, posteriors) -> None:
+    """What ``decode``, ``durations`` and ``posteriors`` may be together, said before any work."""
     want_post = not (posteriors is None or posteriors is False)
     want_decode = not (decode is None or decode is False)
     if want_post and want_decode:
-        raise ValueError("segment_recordings: posteriors and decode exclude each other: one call returns one of them")
+        raise ValueError(f"{name}: posteriors and decode exclude each other: one call returns one of them")
     if durations is not None and not (want_decode or want_post):
-        raise ValueError("segment_recordings: durations are for decoding or posteriors: pass decode=True, decode=(A, pi), "
+        raise ValueError(f"{name}: durations are for decoding or posteriors: pass decode=True, decode=(A, pi), "
                          "posteriors=True or posteriors=(A, pi) with them")
-    logp = seg.ragged(fsst.ragged(recordings), **kw)
+
+
+def _route(logp: RaggedFeatures, decode, durations, posteriors):
+    """The log-probs of a list of recordings, on to the decoder or the posteriors that was asked for, or as they are."""
+    want_post = not (posteriors is None or posteriors is False)
     if want_post:
         A, pi = (None, None) if posteriors is True else posteriors
         if durations is not None:
@@ -606,3 +618,80 @@ def segment_recordings(fsst, seg: HipSegmenter, recordings, decode=None, duratio
     if durations is not None:
         return decode_durations(logp, durations, A, pi)
     return decode_states(logp, A, pi)
+
+
+def segment_windowed(fsst, seg: HipSegmenter, recordings, stride: int = 1000, n: int = 2000, weights="triangular", mode: str = "prob",
+                     h0: Optional[torch.Tensor] = None, c0: Optional[torch.Tensor] = None, max_windows: int = 1024, decode=None,
+                     durations=None, posteriors=None, return_dissent: bool = False):
+    """Whole recordings of different lengths (a list of 1-D signals on the GPU), segmented WINDOW BY WINDOW as the reference
+    trains its model -- every ``n``-sample window z-scored on its own and started from its own initial state -- and stitched back
+    into one ``RaggedFeatures`` of ``(T_i, 4)`` log-probs on the device.  This is the way to run a reference-trained checkpoint on
+    a whole recording; ``segment_recordings`` z-scores the recording as one signal and walks one recurrence over all of it, so the
+    two differ by design.
+
+    The windows are ``framing.cover_starts(T_i, stride, n)``: they cover every sample (``frame_starts``, the training set, drops
+    the tail).  The recordings are packed into one buffer; every full window of every recording goes through ``fsst.frames`` and
+    ``seg(...)`` in chunks of at most ``max_windows`` windows (the result does not depend on it: a window's row does not depend
+    on its batch); the recordings shorter than ``n`` go through ``fsst.ragged`` and ``seg.ragged`` as one window each; both
+    results are laid into one window arena and stitched by ``stitch_windows`` under ``weights`` (a ``window_weights`` kind, None,
+    or ``(n,)`` weights) and ``mode``.  ``h0`` / ``c0``: ``(2, 1, H)``, the state every window starts from; omitted, the module's
+    own are used when their batch is 1, else ValueError.  ``decode``, ``durations``, ``posteriors``: as for ``segment_recordings``,
+    through the same functions.  ``return_dissent``: also ``stitch_windows``' per-step count of disagreeing windows, second."""
+    name = "segment_windowed"
+    _check_route(name, decode, durations, posteriors)
+    n, stride, max_windows = int(n), int(stride), int(max_windows)
+    if n < 1 or not 1 <= stride <= n:
+        raise ValueError(f"{name}: n >= 1 and 1 <= stride <= n expected, got n {n} and stride {stride}")
+    if max_windows < 1:
+        raise ValueError(f"{name}: max_windows {max_windows} must be positive")
+    recs = []
+    for i, x in enumerate(recordings):
+        if isinstance(x, torch.Tensor) and x.dim() == 2 and x.shape[1] == 1:
+            x = x[:, 0]
+        if not isinstance(x, torch.Tensor) or x.dim() != 1 or x.shape[0] < 1 or x.is_complex():
+            raise ValueError(f"{name}: recording {i} is not a real 1-D tensor with at least one sample")
+        if x.device != seg.device:
+            raise ValueError(f"{name}: recording {i} on {x.device}, the plan on {seg.device}")
+        recs.append(x.detach().to(torch.float32))
+    H = seg.hidden_size
+    if (h0 is None) != (c0 is None):
+        raise ValueError(f"{name}: pass both h0 and c0, or neither")
+    if h0 is None:
+        if seg.h0.shape[1] != 1:
+            raise ValueError(f"{name}: every window starts from one state, but the module's h0 / c0 were made for batch {seg.h0.shape[1]} "
+                             "(pass h0 and c0 of shape (2, 1, H) to the call)")
+        h0, c0 = seg.h0, seg.c0
+    elif tuple(h0.shape) != (2, 1, H) or tuple(c0.shape) != (2, 1, H):
+        raise ValueError(f"{name}: h0 and c0 of shape {(2, 1, H)} expected, got {tuple(h0.shape)} and {tuple(c0.shape)}")
+    h0 = h0.detach().to(seg.device, torch.float32).contiguous()
+    c0 = c0.detach().to(seg.device, torch.float32).contiguous()
+    if isinstance(weights, str):
+        weights = window_weights(n, weights, seg.device)
+    lens = [int(x.shape[0]) for x in recs]
+    at = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    full = [i for i, T in enumerate(lens) if T >= n]
+    short = [i for i, T in enumerate(lens) if T < n]
+    first = np.zeros(len(recs), dtype=np.int64)
+    starts, row = [], 0
+    for i in full:
+        first[i] = row
+        starts.append(cover_starts(lens[i], stride, n)[0] + at[i])
+        row += n * int(starts[-1].shape[0])
+    starts = np.concatenate(starts) if starts else np.zeros(0, dtype=np.int64)
+    for i in short:
+        first[i] = row
+        row += lens[i]
+    parts = []
+    if full:
+        buf = torch.cat(recs) if len(recs) > 1 else recs[0].contiguous()
+        for a in range(0, int(starts.shape[0]), max_windows):
+            chunk = starts[a:a + max_windows]
+            B = int(chunk.shape[0])
+            parts.append(seg(fsst.frames(buf, chunk, n), h0.expand(2, B, H), c0.expand(2, B, H)).view(B * n, 4))
+    if short:
+        parts.append(seg.ragged(fsst.ragged([recs[i] for i in short]), h0, c0).data)
+    win = (torch.cat(parts) if len(parts) > 1 else parts[0]) if parts else torch.empty((0, 4), dtype=torch.float32, device=seg.device)
+    out = stitch_windows(win, first, lens, n, stride, weights=weights, mode=mode, return_dissent=return_dissent)
+    if return_dissent:
+        return _route(out[0], decode, durations, posteriors), out[1]
+    return _route(out, decode, durations, posteriors)

@@ -51,6 +51,8 @@
 #include "segmenter_duration_counts.hpp"
 #include "score_layout.hpp"
 #include "segmenter_score.hpp"
+#include "stitch_layout.hpp"
+#include "segmenter_stitch.hpp"
 #include "fsst_tables.hpp"
 
 namespace tables = hssfsst::tables;
@@ -3171,6 +3173,70 @@ int hssfsst_score_states(const float* logp, const uint8_t* states, const uint8_t
                                       reinterpret_cast<unsigned long long*>(rank) + 3 * cls)) return rc;
     }
     return 0;
+}
+
+}  // extern "C"
+
+// Stitching overlapping windows' log-probs (hssfsst.h: hssfsst_stitch_windows; csrc/segmenter_stitch.hpp, csrc/stitch_layout.hpp).
+// Stateless: the launch's offsets and window blocks travel as kernel arguments, kStitchBatch recordings per launch; nothing is
+// copied from host memory and nothing waits.
+namespace {
+
+template <int MODE>
+void stitch_launch(bool weighted, dim3 grid, hipStream_t st, const float* win, const float* weights, float* out, unsigned char* dissent,
+                   const hssfsst::StitchArgs& args)
+{
+    const dim3 block(hssfsst::stitchlayout::kThreads);
+    if (weighted) hipLaunchKernelGGL((hssfsst::seg_stitch_kernel<MODE, true>), grid, block, 0, st, win, weights, out, dissent, args);
+    else hipLaunchKernelGGL((hssfsst::seg_stitch_kernel<MODE, false>), grid, block, 0, st, win, weights, out, dissent, args);
+}
+
+}  // namespace
+
+extern "C" {
+
+int hssfsst_stitch_windows(const float* win_logp, const int64_t* win_first, int64_t win_steps, const int64_t* offsets, int64_t count,
+                           int n, int stride, const float* weights, int mode, float* out, uint8_t* dissent, hssfsst_launch where)
+{
+    namespace stl = hssfsst::stitchlayout;
+    constexpr const char* kEntry = "stitch_windows";
+    if (count < 0) return fail(HSSFSST_EINVAL, "%s: count %lld is negative", kEntry, static_cast<long long>(count));
+    if (int rc = seq_check_nonnull(kEntry, {{"win_logp", win_logp}, {"win_first", win_first}, {"offsets", offsets}, {"out", out}})) return rc;
+    if (win_steps < 0) return fail(HSSFSST_EINVAL, "%s: win_steps %lld is negative", kEntry, static_cast<long long>(win_steps));
+    if (n < 1) return fail(HSSFSST_EINVAL, "%s: window length %d is not positive", kEntry, n);
+    if (stride < 1 || stride > n) return fail(HSSFSST_EINVAL, "%s: stride %d is outside 1 .. %d", kEntry, stride, n);
+    if (mode != HSSFSST_STITCH_PROB && mode != HSSFSST_STITCH_LOGP && mode != HSSFSST_STITCH_SELECT)
+        return fail(HSSFSST_EINVAL, "%s: unknown mode %d", kEntry, mode);
+    const int device = where.device;
+    if (device < 0) return fail(HSSFSST_EINVAL, "%s: device %d is negative", kEntry, device);
+    if (int rc = seq_check_aligned(kEntry, {{"win_logp", win_logp, 16}, {"out", out, 16}, {"weights", weights, 4}})) return rc;
+    if (int rc = seq_check_list(kEntry, offsets, count, seqargs::kMaxTotalSteps)) return rc;
+    for (int64_t i = 0; i < count; ++i) {
+        const int64_t rows = stl::window_rows(offsets[i + 1] - offsets[i], n, stride);
+        if (win_first[i] < 0 || win_first[i] > win_steps - rows)
+            return fail(HSSFSST_EINVAL, "%s: win_first[%lld] = %lld: the %lld window rows of recording %lld do not lie within the %lld of the arena",
+                        kEntry, static_cast<long long>(i), static_cast<long long>(win_first[i]), static_cast<long long>(rows),
+                        static_cast<long long>(i), static_cast<long long>(win_steps));
+    }
+    if (!stl::supported(n, stride))
+        return fail(HSSFSST_EUNSUPPORTED, "%s: windows of %d steps at stride %d overlap %d-fold, over the limit of %d", kEntry, n, stride,
+                    stl::ratio(n, stride), stl::kMaxRatio);
+    if (count == 0) return 0;
+    if (int rc = check_device(kEntry, device)) return rc;
+    DEVICE_SCOPE(device);
+    const hipStream_t st = static_cast<hipStream_t>(where.stream);
+    hssfsst::StitchArgs args{};
+    args.n = n;
+    args.stride = stride;
+    // (args.off is int: seq_check_list has held the list to 2^31 - 1 steps)
+    return seq_for_each_batch(kEntry, "seg_stitch_kernel", offsets, count, stl::kStitchBatch, args, [&](int64_t r0, int nrec) {
+        for (int i = 0; i < nrec; ++i) args.first[i] = win_first[r0 + i];
+        args.nrec = nrec;
+        const dim3 grid(static_cast<unsigned>(stl::launch_groups(offsets[r0 + nrec] - offsets[r0])));
+        if (mode == HSSFSST_STITCH_PROB) stitch_launch<stl::kProb>(weights != nullptr, grid, st, win_logp, weights, out, dissent, args);
+        else if (mode == HSSFSST_STITCH_LOGP) stitch_launch<stl::kLogp>(weights != nullptr, grid, st, win_logp, weights, out, dissent, args);
+        else stitch_launch<stl::kSelect>(weights != nullptr, grid, st, win_logp, weights, out, dissent, args);
+    });
 }
 
 }  // extern "C"

@@ -23,6 +23,23 @@ def frame_starts(T: int, stride: int, n: int) -> Tuple[np.ndarray, np.ndarray]:
     return np.arange(L, dtype=np.int64) * stride, np.full(L, n, dtype=np.int64)
 
 
+def cover_starts(T: int, stride: int, n: int) -> Tuple[np.ndarray, np.ndarray]:
+    """Start index and length of every window of the COVERING set of a length-T recording, in ascending start order: what
+    inference stitches back together (``sequence.stitch_windows``; csrc/stitch_layout.hpp), where ``frame_starts`` restates the
+    reference's training set, which drops a recording's tail.  ``T <= n``: one window ``[0, T)``.  ``T > n``: the
+    ``floor((T - n) / stride) + 1`` regular windows ``[i*stride, i*stride + n)`` and, if ``(T - n) % stride != 0``, one tail window
+    ``[T - n, T)``.  ``T >= 1``, ``n >= 1`` and ``1 <= stride <= n``, else ValueError."""
+    T, stride, n = int(T), int(stride), int(n)
+    if T < 1 or n < 1 or not 1 <= stride <= n:
+        raise ValueError(f"cover_starts: T >= 1, n >= 1 and 1 <= stride <= n expected, got T {T}, stride {stride}, n {n}")
+    if T <= n:
+        return np.zeros(1, dtype=np.int64), np.asarray([T], dtype=np.int64)
+    starts = np.arange((T - n) // stride + 1, dtype=np.int64) * stride
+    if (T - n) % stride:
+        starts = np.concatenate([starts, np.asarray([T - n], dtype=np.int64)])
+    return starts, np.full(starts.shape[0], n, dtype=np.int64)
+
+
 def frame_batch(x: torch.Tensor, stride: int = 1000, n: int = 2000) -> torch.Tensor:
     """``(L, n)`` zero-copy strided view of a 1-D (or ``(T, 1)``) recording holding exactly the
     frames of ``frame_signal``; recordings shorter than ``n`` give one ``(1, T)`` frame."""

@@ -1,7 +1,8 @@
 """What becomes of the segmenter's log-probs, one HIP call each for a whole list of recordings: the Viterbi decoders
 (``decode_states``, ``decode_durations``), the posteriors and sequence losses under the same models (``state_posteriors``,
-``sequence_nll``, ``duration_posteriors``, ``duration_nll``) and the helpers that make their tables.  ``consumer`` imports the
-public names back."""
+``sequence_nll``, ``duration_posteriors``, ``duration_nll``), the scores (``segmentation_scores``), the stitching of overlapping
+windows' log-probs into one sequence per recording (``stitch_windows``) and the helpers that make their tables.  ``consumer``
+imports the public names back."""
 from __future__ import annotations
 
 import ctypes
@@ -33,21 +34,27 @@ def _call(name: str, data: torch.Tensor, offs, *args, lead=None, launch: bool = 
     """One call of the entry ``name(logp, offsets, count, ..., device, stream)`` on the arena ``data`` and the non-empty list
     ``offs``, on the current stream of ``data``'s device.  ``args``: what stands between ``count`` and ``device``; a tensor and a
     float32 array (a host table) go as their pointers, None as NULL.  ``lead``: what stands before ``offsets`` where that is more
-    than ``data`` (which then only names the device).  ``launch``: the entry takes ``(device, stream)`` as one ``const
-    hssfsst_launch*`` (``hssfsst_score_states``).  Raises what ``_lib.check`` makes of the status.  The guard runs here once more
-    (it compares two pids), so that a caller that forgot ``_ready()`` still gets it, if late."""
+    than ``data`` (which then only names the device); an int64 array among them goes as an ``int64_t*``.  ``launch``: True -- the
+    entry takes ``(device, stream)`` as one ``const hssfsst_launch*`` (``hssfsst_score_states``); ``"value"`` -- as one
+    ``hssfsst_launch`` by value (``hssfsst_stitch_windows``).  Raises what ``_lib.check`` makes of the status.  The guard runs here
+    once more (it compares two pids), so that a caller that forgot ``_ready()`` still gets it, if late."""
     _ready()
     device = data.device
     o = np.asarray(offs, dtype=np.int64)
-    fp = ctypes.POINTER(ctypes.c_float)
+    fp, ip = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int64)
 
     def pointer(a):
-        return a.data_ptr() if isinstance(a, torch.Tensor) else a.ctypes.data_as(fp) if isinstance(a, np.ndarray) else a
+        if isinstance(a, np.ndarray):
+            return a.ctypes.data_as(ip if a.dtype == np.int64 else fp)
+        return a.data_ptr() if isinstance(a, torch.Tensor) else a
     args = [pointer(a) for a in args]
     lead = [data.data_ptr()] if lead is None else [pointer(a) for a in lead]
     with torch.cuda.device(device):
         stream = torch.cuda.current_stream(device).cuda_stream
-        where = (ctypes.byref(_lib.Launch(device.index, stream)),) if launch else (device.index, stream)
+        if launch == "value":
+            where = (_lib.Launch(device.index, stream),)
+        else:
+            where = (ctypes.byref(_lib.Launch(device.index, stream)),) if launch else (device.index, stream)
         _lib.check(getattr(_lib.lib(), name)(*lead, o.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), len(offs) - 1, *args, *where), name)
 
 
@@ -885,3 +892,110 @@ def segmentation_scores(pred, labels, per_recording: bool = False, auroc: bool =
     if not per_recording:
         confusion, ignored, rank = confusion[0], ignored[0], None if rank is None else rank[0]
     return SegmentationScores(confusion, ignored, rank)
+
+
+# --------------------------------------------------------------------- overlapping windows' log-probs -> one sequence per recording
+STITCH_MODES = {"prob": _lib.STITCH_PROB, "logp": _lib.STITCH_LOGP, "select": _lib.STITCH_SELECT}
+STITCH_MAX_RATIO = 15                                    # ceil(n / stride) at most (csrc/stitch_layout.hpp: kMaxRatio)
+
+
+def window_weights(n: int, kind: str = "triangular", device=None) -> torch.Tensor:
+    """``(n,)`` float32 weights of a window's positions for ``stitch_windows``, strictly positive: ``"triangular"`` =
+    ``min(p + 1, n - p)``, which trusts a window most in its middle, where the BiLSTM has context on both sides; ``"hann"`` =
+    ``sin^2(pi (p + 1/2) / n)``; ``"flat"`` = ones (what ``weights=None`` means).  On ``device`` when given, else on the host."""
+    n = int(n)
+    if n < 1:
+        raise ValueError(f"window_weights: n >= 1 expected, got {n}")
+    p = np.arange(n, dtype=np.float64)
+    if kind == "triangular":
+        w = np.minimum(p + 1, n - p)
+    elif kind == "hann":
+        w = np.sin(np.pi * (p + 0.5) / n) ** 2
+    elif kind == "flat":
+        w = np.ones(n)
+    else:
+        raise ValueError(f"window_weights: kind 'triangular', 'flat' or 'hann' expected, got {kind!r}")
+    t = torch.from_numpy(w.astype(np.float32))
+    return t if device is None else t.to(device)
+
+
+def _stitch_rows(T: int, n: int, stride: int) -> int:
+    """The rows the windows of a T-step recording take in the window arena (csrc/stitch_layout.hpp: window_rows)."""
+    return T if T <= n else ((T - n) // stride + 1 + (1 if (T - n) % stride else 0)) * n
+
+
+def stitch_windows(win_logp: torch.Tensor, win_first, lengths_or_offsets, n: int, stride: int, weights=None, mode: str = "prob",
+                   return_dissent: bool = False):
+    """The log-probs of overlapping windows -> one sequence of log-probs per recording, on the device
+    (``hssfsst_stitch_windows``): what turns a model trained on ``n``-step windows into a segmenter of whole recordings.
+
+    The window set of a ``T``-step recording is ``framing.cover_starts(T, stride, n)``: it covers every step.  ``win_logp``: the
+    ``(W, 4)`` float32 arena of the windows' log-probs on a GPU -- a full window takes ``n`` rows, the one window of a ``T <= n``
+    recording ``T`` rows.  ``win_first``: per recording the arena row at which its windows start; they lie back to back in ascending
+    start order, the recordings' blocks anywhere.  ``lengths_or_offsets``: the recordings' lengths (as many as ``win_first``) or
+    their offsets from 0 (one more).  ``weights``: None (all ones), or ``(n,)`` weights of a window's positions
+    (``window_weights``): given on the host they are checked (positive, finite) and uploaded, which waits for the stream; given
+    on the device they are used as they are, unchecked.  ``mode``: ``"prob"`` -- the weighted mean of the covering windows'
+    probabilities, renormalised; ``"logp"`` -- the weighted mean of their log-probs (the geometric mean), renormalised;
+    ``"select"`` -- the row of the covering window with the largest weight, ties to the earlier window.  A step that one window
+    covers is copied bit for bit.  float64 inside, rounded once; NaN and ``-inf`` follow IEEE (include/hssfsst.h).
+
+    Returns a ``RaggedFeatures`` over the ``(sum T, 4)`` arena; with ``return_dissent`` also a ``RaggedStates``-shaped uint8 arena:
+    per step the number of covering windows whose own argmax is not the stitched row's -- where the windows disagree.  One call
+    on the current stream, nothing waits for the device.  ``ceil(n / stride) <= 15``, else RuntimeError."""
+    name = "stitch_windows"
+    if mode not in STITCH_MODES:
+        raise ValueError(f"{name}: mode 'prob', 'logp' or 'select' expected, got {mode!r}")
+    n, stride = int(n), int(stride)
+    if n < 1 or not 1 <= stride <= n:
+        raise ValueError(f"{name}: n >= 1 and 1 <= stride <= n expected, got n {n} and stride {stride}")
+    if not isinstance(win_logp, torch.Tensor) or win_logp.dim() != 2 or win_logp.shape[1] != 4:
+        raise ValueError(f"{name}: a (W, 4) arena of window log-probs expected")
+    if win_logp.dtype != torch.float32:
+        raise ValueError(f"{name}: float32 log-probs expected, got {win_logp.dtype}")
+    first = np.ascontiguousarray(win_first.cpu().numpy() if isinstance(win_first, torch.Tensor) else win_first, dtype=np.int64).reshape(-1)
+    lo = np.asarray(lengths_or_offsets.cpu().numpy() if isinstance(lengths_or_offsets, torch.Tensor) else lengths_or_offsets,
+                    dtype=np.int64).reshape(-1)
+    if lo.size == first.size + 1 and int(lo[0]) == 0:
+        offs = [int(v) for v in lo]
+    elif lo.size == first.size:
+        offs = [0] + [int(v) for v in np.cumsum(lo)]
+    else:
+        raise ValueError(f"{name}: {first.size} recordings by win_first, but {lo.size} lengths or offsets (as many lengths, or one "
+                         "more offset from 0, expected)")
+    W = int(win_logp.shape[0])
+    for i in range(first.size):
+        T = offs[i + 1] - offs[i]
+        if T < 1:
+            raise ValueError(f"{name}: recording {i} has {T} steps")
+        if first[i] < 0 or first[i] + _stitch_rows(T, n, stride) > W:
+            raise ValueError(f"{name}: win_first[{i}] = {int(first[i])}: the {_stitch_rows(T, n, stride)} window rows of recording {i} "
+                             f"do not lie within the {W} of the arena")
+    if -(-n // stride) > STITCH_MAX_RATIO:
+        raise RuntimeError(f"{name}: windows of {n} steps at stride {stride} overlap {-(-n // stride)}-fold, over the limit of "
+                           f"{STITCH_MAX_RATIO}")
+    w = None
+    if weights is not None:
+        on_device = isinstance(weights, torch.Tensor) and weights.is_cuda
+        w = weights if on_device else torch.from_numpy(_host_array(weights))
+        if tuple(w.shape) != (n,):
+            raise ValueError(f"{name}: weights ({n},) expected, got {tuple(w.shape)}")
+        if on_device and w.dtype != torch.float32:
+            raise ValueError(f"{name}: float32 weights expected, got {w.dtype}")
+        if not on_device and not bool((torch.isfinite(w) & (w > 0)).all()):
+            raise ValueError(f"{name}: positive, finite weights expected")
+    if win_logp.device.type != "cuda":
+        raise ValueError(f"{name}: log-probs on a GPU expected, got {win_logp.device}; the stitch has no CPU path")
+    if w is not None and w.is_cuda and w.device != win_logp.device:
+        raise ValueError(f"{name}: weights on {w.device}, the log-probs on {win_logp.device}")
+    _ready()
+    device = win_logp.device
+    w = None if w is None else w.detach().to(device).contiguous()
+    out = torch.empty((offs[-1], 4), dtype=torch.float32, device=device)
+    dissent = torch.empty((offs[-1],), dtype=torch.uint8, device=device) if return_dissent else None
+    if len(offs) > 1:
+        data = win_logp.detach().contiguous()
+        _call("hssfsst_stitch_windows", data, offs, n, stride, w, STITCH_MODES[mode], out, dissent, lead=(data, first, W), launch="value")
+    off = torch.tensor(offs, dtype=torch.int64)
+    res = RaggedFeatures(out, off, 4, False)
+    return (res, RaggedStates(dissent, off)) if return_dissent else res

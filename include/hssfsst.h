@@ -589,7 +589,10 @@ int hssfsst_posteriors_durations_counts_info(int64_t* work_bytes_per_step, int64
  * enqueued on.  hssfsst_score_states takes the pair as a struct, where the entries above take `int device, void* stream`: the
  * stream-order suite holds every function of this header with a `void* stream` parameter to one table of cases in
  * tests/test_stream_order.py, and the cases of this entry live in tests/test_segmentation_scores.py, which holds every function
- * with a `const hssfsst_launch*` parameter to the same two scenarios on a side stream.  The promise is the same one. */
+ * with a `const hssfsst_launch*` parameter to the same two scenarios on a side stream.  The promise is the same one.
+ * hssfsst_stitch_windows takes the struct BY VALUE for the same reason once more: both of those files are closed tables, and an
+ * entry of either shape without a case in them fails them.  tests/test_stitch_windows.py holds every function of this header with
+ * a by-value `hssfsst_launch` parameter to the two scenarios, and fails for one without a case there. */
 typedef struct { int device; void* stream; } hssfsst_launch;
 
 /* Scoring a segmentation on the device: confusion counts and the exact rank statistic behind the one-vs-rest AUROC, for a LIST of
@@ -635,6 +638,47 @@ int hssfsst_score_states(const float* logp, const uint8_t* states, const uint8_t
  * wave histograms and scatters (2048), digit_bits = 8, max_passes = 8.  No device needed; any pointer may be NULL. */
 int hssfsst_score_info(int64_t* work_bytes_per_step, int64_t* work_bytes_per_recording, int64_t* work_bytes_constant, int* block_items,
                        int* digit_bits, int* max_passes);
+
+/* Stitching: the log-probs of OVERLAPPING WINDOWS of a list of recordings -> one sequence of log-probs per recording, so that a
+ * model trained on n-step windows segments whole recordings window by window (csrc/segmenter_stitch.hpp; the window set, the
+ * arithmetic of a step and the sequential loop that is the specification as plain functions: csrc/stitch_layout.hpp).  Stateless.
+ * The window set of a recording of T >= 1 steps, windows of n steps at stride 1 <= stride <= n, covers every step:
+ *   T <= n   one window [0, T)
+ *   T >  n   the floor((T - n) / stride) + 1 regular windows [i stride, i stride + n) and, if (T - n) % stride != 0, one tail
+ *            window [T - n, T)
+ *   win_logp     (win_steps, 4) float32, DEVICE, 16-byte aligned: the windows' log-probs; a full window takes n rows, the single
+ *                window of a T <= n recording T rows
+ *   win_first    (count) int64, HOST: recording i's windows lie back to back, in ascending start order, from row win_first[i] on;
+ *                the blocks of different recordings may lie anywhere in the arena, in any order
+ *   win_steps    the arena's rows: every block must end within them
+ *   offsets, count as for hssfsst_decode_states (HOST): the OUTPUT recordings; no limit on a recording's length
+ *   n, stride    n >= 1, 1 <= stride <= n, ceil(n / stride) <= 15: a step has at most 16 covering windows
+ *   weights      (n) float32, DEVICE, or NULL (all ones): w[p] > 0 weighs position p of a window; the short window of a T <= n
+ *                recording uses w[0 .. T).  The values are device memory and are not checked
+ *   mode         HSSFSST_STITCH_PROB, _LOGP or _SELECT
+ *   out          (sum T, 4) float32, DEVICE, 16-byte aligned
+ *   dissent      (sum T) uint8, DEVICE, or NULL: how many of the step's covering windows have an argmax other than that of out[t];
+ *                the argmax is hssfsst_score_states': ties to the smaller state, NaN read as -inf
+ *   where        the device and the stream, by value
+ * Arithmetic.  The covering windows of step t in ascending start order are k = 1 .. m; window k gives the row v_k at its position
+ * p_k, with weight w_k = w[p_k].  m == 1, or SELECT: a row is copied bit for bit; SELECT takes the largest w_k, ties to the earlier
+ * start.  PROB: with M the largest of the 4 m values, a_j = log(sum_k w_k exp(v_kj - M) / sum_k w_k) + M, the weighted mean of the
+ * probabilities.  LOGP: a_j = sum_k w_k v_kj / sum_k w_k, the weighted geometric mean.  Both: out_j = a_j - logsumexp_j(a), in
+ * float64, the sums over k in ascending start order, rounded to float32 once.  IEEE rules do the rest: a NaN among a step's values
+ * makes its four outputs NaN; a class that is -inf in every covering window (PROB) or in any (LOGP) comes out -inf; a step with no
+ * mass at all gets four NaN.
+ * HSSFSST_EINVAL before any device work: a NULL win_logp, win_first, offsets or out; count < 0; win_steps < 0; n < 1; stride outside
+ * 1 .. n; an unknown mode; where.device < 0; win_logp or out not 16-byte aligned, weights not 4-byte; bad offsets (as
+ * hssfsst_decode_states); a win_first[i] that is negative or whose block ends past win_steps.  HSSFSST_EUNSUPPORTED: more than
+ * 2^31 - 1 steps in all; ceil(n / stride) > 15.  count == 0 returns 0 and does nothing.
+ * A recording's result does not depend on its neighbours or its place in the list, bit for bit, and two calls give the same bits.
+ * Enqueued on where.stream without synchronising and without a copy from host memory: one launch per 256 recordings (offsets and
+ * win_first travel as kernel arguments), one lane per step, no atomics, no LDS, no scratch memory. */
+#define HSSFSST_STITCH_PROB 0
+#define HSSFSST_STITCH_LOGP 1
+#define HSSFSST_STITCH_SELECT 2
+int hssfsst_stitch_windows(const float* win_logp, const int64_t* win_first, int64_t win_steps, const int64_t* offsets, int64_t count,
+                           int n, int stride, const float* weights, int mode, float* out, uint8_t* dissent, hssfsst_launch where);
 
 /* One DIFFERENTIABLE bidirectional LSTM layer (batch first, nn.LSTM's cell and gate order): the unit a training program stacks
  * under autograd -- the segmenter is two of them.  The plan holds the layer's current weights in the kernels' layouts and the
