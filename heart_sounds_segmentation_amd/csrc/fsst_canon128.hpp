@@ -130,14 +130,23 @@ constexpr float kMeanTheta = 0.5f;                       // the mean is taken ou
 // from the tile's energy (max |x| <= sqrt(sum x^2) < 2^hb => |x| 2^(14 - hb) < 2^14 < 65504), which the error bound needs anyway.
 // OFFS = false (fsst_team16_kernel, which has no register to spare for the offset term): such a tile is only REPORTED -- mean_s is a
 // NaN, nothing is staged -- and the caller hands the whole exec to the kernels that have it.
-template <bool OFFS = true>
+// FINITE (fsst_canon_kernel): E and S1 are taken over the tile's finite samples.  A tile that reads a NaN or an infinite sample has
+// a non-finite energy, whose exponent 255 would send the whole tile to scale 1 -- and the up to 63 columns whose windows do NOT hold
+// that sample to records that are mostly subnormal on a quiet signal.  The sample itself keeps its value in the records: its own
+// columns come out non-finite, as the float64 transform has them.  A tile of finite samples takes the same operations on the same
+// values.  (The team kernel stays as it is: its output is z-scored, so such a signal is NaN throughout.)
+__device__ __forceinline__ float canon_finite(float v) { return fabsf(v) < __builtin_inff() ? v : 0.0f; }
+template <bool OFFS = true, bool FINITE = false>
 __device__ __forceinline__ CanonTile canon_land(const float (&sreg)[3], u2* xrec, float r2scale_s, float inv_c, int lane, int t0, int n)
 {
     // (samples outside the signal are zeros in sreg: canon_fetch; how many of the tile's 192 slots lie inside it is wave-uniform
     //  arithmetic -- the per-lane count that used to ride through the reduction cost 12 instructions per tile)
     float e2 = 0.0f, s1 = 0.0f;
 #pragma unroll
-    for (int k = 0; k < 3; ++k) { e2 = fmaf(sreg[k], sreg[k], e2); s1 += sreg[k]; }
+    for (int k = 0; k < 3; ++k) {
+        const float v = FINITE ? canon_finite(sreg[k]) : sreg[k];
+        e2 = fmaf(v, v, e2); s1 += v;
+    }
     const int inside = min(t0 + 128, n) - max(t0 - 64, 0);
     TileEnergy te = tile_energy(e2, s1, 0.0f);           // (E and S1: the reduction of every canonical-band kernel; the count does not ride along)
     te.C = static_cast<float>(max(inside, 0));
@@ -173,7 +182,8 @@ __device__ __forceinline__ CanonTile canon_land(const float (&sreg)[3], u2* xrec
         for (int k = 0; k < 3; ++k) {
             const int gi = t0 + lane + 64 * k - 64;
             x[k] = (gi >= 0 && gi < n) ? sreg[k] - mean : 0.0f;
-            ea = fmaf(x[k], x[k], ea);
+            const float v = FINITE ? canon_finite(x[k]) : x[k];
+            ea = fmaf(v, v, ea);
         }
         const float E = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(piece_sums(ea, 0.0f, 0.0f, 0.0f))));     // (recomputed: E - S1^2 / n cancels)
         // (a tile that is nothing but its mean has E = 0: the scale then comes from the mean, whose spectrum is all there is)
@@ -807,7 +817,7 @@ __global__ __launch_bounds__(64 * 16, 4) void fsst_canon_kernel(CanonParams p)
         int lane_t = lane;                               // opaque per tile / per group: nothing derived from the lane id is
         asm volatile("" : "+v"(lane_t));                 // hoisted out of these loops, held across the transform and spilled
         canon_fetch(xsig, n, tbase * 16, lane_t, sreg);
-        const CanonTile tile = canon_land(sreg, xrec, p.r2scale_s, p.inv_c, lane_t, tbase * 16, n);
+        const CanonTile tile = canon_land<true, true>(sreg, xrec, p.r2scale_s, p.inv_c, lane_t, tbase * 16, n);
         for (int gidx = gcur; gidx < gstop; ++gidx) {
             int lane_o = lane;
             asm volatile("" : "+v"(lane_o));

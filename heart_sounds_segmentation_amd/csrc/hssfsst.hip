@@ -2611,7 +2611,7 @@ template <bool RAGGED, bool TRAIN>
 int seg_forward_layer(const char* what, hipStream_t st, const SegLayer& L, hssfsst::SegProjArgs pa, hssfsst::SegRecArgs ra,
                       const std::vector<hssfsst::seglayout::Chunk>& chunks)
 {
-    pa.F = L.F; pa.Fp = L.Fp;
+    pa.F = L.F; pa.Fp = L.Fp; pa.H = ra.H;
     pa.wt = L.d_wt.get(); pa.bias = L.d_bias.get();
     ra.whh = L.d_whh.get();
     for (const hssfsst::seglayout::Chunk& c : chunks) {

@@ -13,7 +13,8 @@
 //   seg_head_kernel   ReLU -> Linear -> log_softmax, one wave per (b, t).
 //
 // Every hidden size runs on the one padded geometry kSegHp = 256 units (16 unit tiles x 4 gates, K = 256): padded units have zero
-// weights and zero state, so they stay exactly zero (i = f = o = 1/2, g = 0, c' = c / 2 = 0).
+// weights and zero state, so they stay exactly zero (i = f = o = 1/2, g = 0, c' = c / 2 = 0); the projection writes their gate
+// columns as zero whatever x holds (seg_proj_kernel's epilogue), so an infinite feature does not reach them as 0 . Inf.
 //
 // RAGGED instantiations (hssfsst_segmenter_exec_ragged): the 16 rows of a tile are SLOTS, each holding a whole recording of its own
 // length from an arena (segmenter_layout.hpp: longest first, so the tiles still walking are a prefix).  Everything is indexed by the
@@ -47,10 +48,15 @@ __device__ __forceinline__ float seg_load_x(const void* x, size_t i, int dtype)
     return static_cast<const float*>(x)[i];
 }
 
+// ReLU as torch.relu has it: a NaN stays a NaN (fmaxf(NaN, 0) is 0, which made a row without a single valid number look like a
+// confident one).  One compare and one select; every other value keeps its bits.
+__device__ __forceinline__ float seg_relu(float v) { return v < 0.0f ? 0.0f : v; }
+
 struct SegProjArgs {
     const void* x;          // (B, T, F) of x_dtype
     int x_dtype, relu;      // relu: rectify on load (layer 2 reads layer 1's un-rectified output)
     int B, T, F, Fp;        // Fp = F rounded up to 32: rows of wt
+    int H;                  // hidden size: the gate columns of units H .. Hp - 1 are padding and are written as zero
     const float* wt;        // [dir][Fp][4 Hp]: W_ih transposed, columns permuted to (unit tile, gate, unit), zero padded
     const float* bias;      // [dir][4 Hp]: b_ih + b_hh, same column order
     float* pre;             // [dir][batch tile][Tc][gate tile][lane][4]
@@ -101,11 +107,11 @@ __global__ __launch_bounds__(256) void seg_proj_kernel(SegProjArgs a)
                 if (s < len && k < a.F) {
                     const long long row = a.slot_off[b] + (dir ? len - 1 - s : s);
                     v = seg_load_x(a.x, static_cast<size_t>(row) * a.F + k, a.x_dtype);
-                    if (a.relu) v = fmaxf(v, 0.0f);
+                    if (a.relu) v = seg_relu(v);
                 }
             } else if (tl < a.n && b < a.B && k < a.F) {
                 v = seg_load_x(a.x, (static_cast<size_t>(b) * a.T + (a.t0[dir] + tl)) * a.F + k, a.x_dtype);
-                if (a.relu) v = fmaxf(v, 0.0f);
+                if (a.relu) v = seg_relu(v);
             }
             As[m * AS + (tid & 31)] = v;
         }
@@ -137,10 +143,13 @@ __global__ __launch_bounds__(256) void seg_proj_kernel(SegProjArgs a)
         float* dst = a.pre + ((static_cast<size_t>(dir) * nbt + bt) * a.Tc + tl) * (kSegGateTiles * kSegTileFloats);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const int col = n0 + i * 16;
+            const int col = n0 + i * 16, unit0 = (col >> 6) * 16;           // column = (unit tile x 4 + gate) x 16 + unit
             const float bv = a.bias[dir * (4 * kSegHp) + col + (lane & 15)];
             seg_f4 v = acc[j][i];
             v += bv;
+            // a padded unit's column holds zero weights and a zero bias: 0 for every finite x, but 0 . Inf = NaN, and a NaN in a
+            // padded unit's h reaches every real unit of the row through the zero rows of W_hh.  Written as the zero it stands for.
+            if (unit0 + (lane & 15) >= a.H) v = seg_f4{0.0f, 0.0f, 0.0f, 0.0f};
             *reinterpret_cast<seg_f4*>(dst + (col >> 4) * kSegTileFloats + lane * 4) = v;
         }
     }
@@ -431,7 +440,7 @@ __global__ __launch_bounds__(256) void seg_head_kernel(const float* y, const flo
     const float* yr = y + row * H2;
     float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;
     for (int k = lane; k < H2; k += 64) {
-        const float v = fmaxf(yr[k], 0.0f);
+        const float v = seg_relu(yr[k]);
         s0 = fmaf(v, lw[k], s0);
         s1 = fmaf(v, lw[H2 + k], s1);
         s2 = fmaf(v, lw[2 * H2 + k], s2);

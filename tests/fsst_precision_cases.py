@@ -201,7 +201,7 @@ def block_span(j, n, N):
     return max(BLOCK * j - m, 0), min(BLOCK * j + BLOCK - 1 + N - 1 - m + 1, n)
 
 
-def split_f16(x, window, rws, klo, K, drop_x2=False, drop_c2=False, drop_c2_tap=None, one_scale=False):
+def split_f16(x, window, rws, klo, K, drop_x2=False, drop_c2=False, drop_c2_tap=None, one_scale=False, finite_energy=False):
     """The split-f16 emulation.  Per aligned 64-frame tile one power-of-two scale from the sum of squares of the samples its frames
     read; samples x = x1 + x2 and constants c = c1 + c2 (c = window x twiddle, scaled by one power of two into [2^13, 2^14)), each
     half rounded to float16; the four products x1 c1 + x1 c2 + x2 c1 + x2 c2 over all taps accumulated in float32 by one float32
@@ -212,7 +212,9 @@ def split_f16(x, window, rws, klo, K, drop_x2=False, drop_c2=False, drop_c2_tap=
     the whole DFT as one product.  Agreement is to a small multiple of float32, not to the bit.
 
     Defects, one thing each: D1 ``drop_x2``; D2 ``drop_c2``; D3 ``drop_c2_tap=N // 2`` (the lo constants of one tap);
-    D4 ``one_scale`` (one scale from the whole signal's energy instead of one per tile)."""
+    D4 ``one_scale`` (one scale from the whole signal's energy instead of one per tile).
+    A tile whose energy is not finite (it reads a NaN or an infinite sample) takes scale 1, as canon_land does; ``finite_energy``
+    takes the energy over the tile's finite samples instead (tests/nonfinite_cases.py)."""
     x = np.asarray(x)
     assert x.dtype == np.float32
     w = np.asarray(window, dtype=np.float64).ravel()
@@ -231,10 +233,13 @@ def split_f16(x, window, rws, klo, K, drop_x2=False, drop_c2=False, drop_c2_tap=
     F = frames(x, N)
     x64 = x.astype(np.float64)
     V = np.empty((N, n), dtype=np.complex64)
-    whole = _pow2_scale(float((x64 * x64).sum()))
+    sq = x64 * x64
+    if finite_energy:
+        sq = np.where(np.isfinite(x64), sq, 0.0)
+    whole = _pow2_scale(float(sq.sum()))
     for j in range((n + BLOCK - 1) // BLOCK):
         lo, hi = block_span(j, n, N)
-        sx = whole if one_scale else _pow2_scale(float((x64[lo:hi] * x64[lo:hi]).sum()))
+        sx = whole if one_scale else _pow2_scale(float(sq[lo:hi].sum()))
         t0, t1 = BLOCK * j, min(BLOCK * j + BLOCK, n)
         x1, x2 = _f16_halves(F[t0:t1] * np.float32(sx))
         if drop_x2:

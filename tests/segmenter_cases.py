@@ -111,14 +111,26 @@ def _split16(t):
     return hi, _f16(t - hi)
 
 
-def twin_layer(lstm, x, h0, c0, terms=0):
+def _relu(t, relu):
+    """'torch': torch.relu, which keeps a NaN; 'fmax': max(x, 0) as C's fmaxf has it, which turns a NaN into 0"""
+    if relu == "torch":
+        return torch.relu(t)
+    if relu != "fmax":
+        raise ValueError(relu)
+    return torch.where(t > 0.0, t, torch.zeros_like(t))
+
+
+def twin_layer(lstm, x, h0, c0, terms=0, relu=None):
     """One bidirectional layer in float64, step by step.  lstm: anything with nn.LSTM's parameter names; x (B, T, F), h0 / c0
     (2, B, H).  terms: 0 = exact recurrent product; 2 = the kernels' operands, h x 2^10 and W_hh x wscale (the power of two that
     puts the layer's largest |W_hh| in [2^12, 2^13)) each split into f16 hi + lo, products hi.hi + hi.lo + lo.hi; 1 = hi.hi only.
+    relu: None = x as it is; 'torch' / 'fmax' = x rectified on load, as seg_proj_kernel reads layer 2's input (see _relu).
     Returns y (B, T, 2H), hn, cn (2, B, H) and {'pre_min', 'pre_max': extremes of the gate pre-activations, 'saturated': share of
     i / f / o gates outside [0.02, 0.98]}."""
     H = lstm.hidden_size
     x, h0, c0 = x.double(), h0.double(), c0.double()
+    if relu is not None:
+        x = _relu(x, relu)
     B, T = x.shape[0], x.shape[1]
     W = [{k: getattr(lstm, f"{k}_l0{s}").detach().double().cpu() for k in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")}
          for s in _SUFFIXES]
@@ -162,15 +174,16 @@ def twin_layer(lstm, x, h0, c0, terms=0):
     return y, hn, cn, {"pre_min": lo, "pre_max": hi, "saturated": sat / cnt}
 
 
-def twin_forward(head, x, terms=0, h0=None, c0=None):
+def twin_forward(head, x, terms=0, h0=None, c0=None, relu="torch"):
     """The whole model in float64 on twin_layer: layer 1 from (h0, c0) (the module's own by default) -> ReLU -> layer 2 seeded with
-    layer 1's (hn, cn) -> ReLU -> linear -> log_softmax; dropout is the identity.  Returns the (B, T, 4) log-probs and
+    layer 1's (hn, cn) -> ReLU -> linear -> log_softmax; dropout is the identity.  ``relu``: see _relu; 'fmax' is the defect of a
+    kernel that rectifies with fmaxf (tests/test_nonfinite.py).  Returns the (B, T, 4) log-probs and
     {'pre_min', 'pre_max': over both layers, 'layers': the two layers' own figures}."""
     h0 = head.h0 if h0 is None else h0
     c0 = head.c0 if c0 is None else c0
     y1, hn, cn, s1 = twin_layer(head.lstm_1, x, h0.detach().cpu(), c0.detach().cpu(), terms)
-    y2, _, _, s2 = twin_layer(head.lstm_2, torch.relu(y1), hn, cn, terms)
-    z = torch.relu(y2) @ head.linear.weight.detach().double().cpu().t() + head.linear.bias.detach().double().cpu()
+    y2, _, _, s2 = twin_layer(head.lstm_2, y1, hn, cn, terms, relu=relu)
+    z = _relu(y2, relu) @ head.linear.weight.detach().double().cpu().t() + head.linear.bias.detach().double().cpu()
     info = {"pre_min": min(s1["pre_min"], s2["pre_min"]), "pre_max": max(s1["pre_max"], s2["pre_max"]), "layers": [s1, s2]}
     return torch.log_softmax(z, dim=2), info
 
