@@ -13,7 +13,9 @@ import threading
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG, "libhssfsst.so")
-SRC = os.path.join(_PKG, "csrc", "hssfsst.hip")
+# the library's translation units, one per subsystem (each kernel header is included by exactly one of them)
+SOURCES = [os.path.join(_PKG, "csrc", f) for f in ("hssfsst.hip", "resample.hip", "segmenter.hip", "sequence.hip", "host_io.hip")]
+BUILD_DIR = os.path.join(_PKG, "build")
 HEADER = os.path.join(os.path.dirname(_PKG), "include", "hssfsst.h")
 
 MODE_RAW, MODE_ABS, MODE_STACK, MODE_STACK_UNNORM = 0, 1, 2, 3
@@ -74,21 +76,38 @@ def guard_fork() -> None:
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
-    """Compile csrc/hssfsst.hip for gfx950 into libhssfsst.so (cross-compiles without a GPU)."""
-    csrc = os.path.join(_PKG, "csrc")
-    # every source under csrc/ (the MFMA core, the generic kernels, the host helpers) plus the C header
-    deps = sorted(os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".hip", ".hpp", ".h"))) + [HEADER]
-    if (not force and os.path.exists(LIB_PATH)
-            and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(d) for d in deps)):
-        return LIB_PATH
+    """Compile the units of SOURCES for gfx950, each into an object under build/, and link them into libhssfsst.so (cross-compiles
+    without a GPU).  An object is rebuilt when it is older than its own unit, any header of csrc/ or the C header; the units that
+    need it compile concurrently.  A failed unit raises after the others have finished, and nothing is linked.  A library that is
+    newer than every unit and header is current whether or not the objects are there (a copy of the tree without build/)."""
+    from concurrent.futures import ThreadPoolExecutor
+    csrc = os.path.dirname(SOURCES[0])
+    headers = sorted(os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".hpp", ".h"))) + [HEADER]
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC",
-           "-o", LIB_PATH, SRC]
-    res = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    if verbose or res.returncode != 0:
-        print(res.stdout)
-    if res.returncode != 0:
-        raise RuntimeError(f"hipcc failed ({res.returncode}): {' '.join(cmd)}\n{res.stdout}")
+
+    def older(target: str, deps) -> bool:
+        return not os.path.exists(target) or any(os.path.getmtime(target) < os.path.getmtime(d) for d in deps)
+
+    def run(cmd) -> None:
+        res = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+        if verbose or res.returncode != 0:
+            print(res.stdout)
+        if res.returncode != 0:
+            raise RuntimeError(f"hipcc failed ({res.returncode}): {' '.join(cmd)}\n{res.stdout}")
+
+    if not force and not older(LIB_PATH, SOURCES + headers):
+        return LIB_PATH
+    objects = [os.path.join(BUILD_DIR, os.path.splitext(os.path.basename(src))[0] + ".o") for src in SOURCES]
+    stale = [(src, obj) for src, obj in zip(SOURCES, objects) if force or older(obj, [src] + headers)]
+    if stale:
+        os.makedirs(BUILD_DIR, exist_ok=True)
+        jobs = min([len(SOURCES), 16] + ([max(int(os.environ["MAX_JOBS"]), 1)] if os.environ.get("MAX_JOBS", "").isdigit() else []))
+        with ThreadPoolExecutor(max_workers=jobs) as pool:
+            done = [pool.submit(run, [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-c", "-o", obj, src])
+                    for src, obj in stale]
+        for d in done:                                     # (all of them have finished: the first failure is raised)
+            d.result()
+    run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB_PATH] + objects)      # (it is missing, or older than an object)
     return LIB_PATH
 
 
@@ -104,13 +123,29 @@ def _llvm_tools(*names) -> dict:
     return tools
 
 
-def _unbundle(tools: dict, path: str, td: str) -> str:
-    """The gfx950 code object inside the library ``path``, written into the directory ``td``."""
-    fat, obj = os.path.join(td, "fat.bin"), os.path.join(td, "code.o")
+def _unbundle(tools: dict, path: str, td: str) -> list:
+    """The gfx950 code objects inside the library ``path``, written into the directory ``td``: one per translation unit.  The
+    library's .hip_fatbin section holds the units' bundles back to back and the unbundler reads only the first of a file, so the
+    section is cut at every bundle header."""
+    magic = b"__CLANG_OFFLOAD_BUNDLE__"
+    fat = os.path.join(td, "fat.bin")
     subprocess.run([tools["objcopy"], "-O", "binary", "--only-section=.hip_fatbin", path, fat], check=True, capture_output=True)
-    subprocess.run([tools["clang-offload-bundler"], "--unbundle", "--type=o", f"--input={fat}", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950",
-                    f"--output={obj}"], check=True, capture_output=True)
-    return obj
+    with open(fat, "rb") as f:
+        data = f.read()
+    cuts, at = [], data.find(magic)
+    while at >= 0:
+        cuts.append(at)
+        at = data.find(magic, at + len(magic))
+    cuts.append(len(data))
+    objs = []
+    for k, (lo, hi) in enumerate(zip(cuts, cuts[1:])):
+        piece, obj = os.path.join(td, f"fat{k}.bin"), os.path.join(td, f"code{k}.o")
+        with open(piece, "wb") as f:
+            f.write(data[lo:hi])
+        subprocess.run([tools["clang-offload-bundler"], "--unbundle", "--type=o", f"--input={piece}",
+                        "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={obj}"], check=True, capture_output=True)
+        objs.append(obj)
+    return objs
 
 
 def kernel_resources(match: str, path: str = None) -> dict:
@@ -121,8 +156,8 @@ def kernel_resources(match: str, path: str = None) -> dict:
     import tempfile
     tools = _llvm_tools("clang-offload-bundler", "llvm-readelf")
     with tempfile.TemporaryDirectory() as td:
-        obj = _unbundle(tools, path or LIB_PATH, td)
-        notes = subprocess.run([tools["llvm-readelf"], "--notes", obj], check=True, capture_output=True, text=True).stdout
+        notes = "".join(subprocess.run([tools["llvm-readelf"], "--notes", obj], check=True, capture_output=True, text=True).stdout
+                        for obj in _unbundle(tools, path or LIB_PATH, td))
     out = {}
     fields = ("vgpr_count", "agpr_count", "sgpr_count", "private_segment_fixed_size", "group_segment_fixed_size")
     for blk in re.split(r"\n\s*- \.agpr_count:", notes)[1:]:
@@ -144,9 +179,13 @@ def check_code_object(path: str = None) -> dict:
     path = path or LIB_PATH
     tools = _llvm_tools("clang-offload-bundler", "llvm-objdump", "llvm-readelf")
     with tempfile.TemporaryDirectory() as td:
-        obj = _unbundle(tools, path, td)
-        dis = subprocess.run([tools["llvm-objdump"], "-d", "--mcpu=gfx950", obj], check=True, capture_output=True, text=True).stdout.split("\n")
-        notes = subprocess.run([tools["llvm-readelf"], "--notes", obj], check=True, capture_output=True, text=True).stdout
+        dis, notes = [], ""
+        for obj in _unbundle(tools, path, td):               # the unit whose code object holds the team kernels
+            n = subprocess.run([tools["llvm-readelf"], "--notes", obj], check=True, capture_output=True, text=True).stdout
+            if "fsst_team16_kernel" not in n:
+                continue
+            dis += subprocess.run([tools["llvm-objdump"], "-d", "--mcpu=gfx950", obj], check=True, capture_output=True, text=True).stdout.split("\n")
+            notes += n
     starts = [i for i, ln in enumerate(dis) if re.match(r"^[0-9a-f]+ <_ZN7hssfsst18fsst_team16_kernel.*>:", ln)]
     if len(starts) < 2:
         raise RuntimeError("check_code_object: the team kernels are not in the code object")

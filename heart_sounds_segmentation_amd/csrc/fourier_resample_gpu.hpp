@@ -2,7 +2,7 @@
 // signals of n samples, in fp64 on the device whatever the input / output dtypes.
 //
 // Same algorithm as the host helper: both DFTs run as Bluestein chirp-z convolutions on power-of-two FFTs.  Everything that
-// depends only on (n, num) is made once on the host, in fp64, by the plan (hssfsst.hip: hssfsst_resample_plan_create):
+// depends only on (n, num) is made once on the host, in fp64, by the plan (resample.hip: hssfsst_resample_plan_create):
 //   c1[m] = conj(w1[m]), m < n          w1[m] = exp(+i pi (m^2 mod 2n) / n)        forward chirp (N = n)
 //   B1[j] = FFT_M1(b1)[bitrev(j)] / M1  b1 = w1 wrapped symmetrically into M1 >= 2n - 1 points
 //   c2, B2: the same for the inverse DFT (N = num, chirp sign flipped, M2 >= 2 num - 1)

@@ -60,6 +60,16 @@ inline void bluestein_tables(int64_t N, int M, double sgn, resample_detail::cd* 
     }
 }
 
+// twiddle table of the resample plans' convolutions on Mt points: exp(-2 pi i k / Mt), k < max(Mt / 2, 1)
+inline size_t twiddle_count(int Mt) { return static_cast<size_t>(Mt > 1 ? Mt / 2 : 1); }
+inline void twiddle_table(int Mt, resample_detail::cd* tw)
+{
+    for (size_t k = 0; k < twiddle_count(Mt); ++k) {
+        const double ang = -2.0 * M_PI * static_cast<double>(k) / static_cast<double>(Mt);
+        tw[k] = resample_detail::cd(std::cos(ang), std::sin(ang));
+    }
+}
+
 // dense large tier: signals per chunk, each with Mw elements of work
 inline long long dense_chunk(long long budget, long long Mw, long long batch)
 {

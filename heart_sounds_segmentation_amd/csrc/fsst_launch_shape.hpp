@@ -12,7 +12,7 @@
 
 namespace hssfsst {
 
-constexpr int kMaxLdsBytes = 160 * 1024;        // LDS of a CU: what a block may ask for (hssfsst.hip raises every kernel's limit to it)
+constexpr int kMaxLdsBytes = 160 * 1024;        // LDS of a CU: what a block may ask for (allow_full_lds of host_common.hpp raises a kernel's limit to it)
 constexpr int kFpw128 = 64;                  // frames per wave tile of the MFMA kernels
 constexpr int kPartFloats = 8;               // a statistics partial (fsst_kernels.hpp "Statistics")
 

@@ -294,14 +294,4 @@ inline std::vector<float> canon_table(const double* window, const double* dwb, i
     return t16;
 }
 
-// twiddle table of the resample plans' convolutions on Mt points: exp(-2 pi i k / Mt), k < max(Mt / 2, 1)
-inline size_t twiddle_count(int Mt) { return static_cast<size_t>(Mt > 1 ? Mt / 2 : 1); }
-inline void twiddle_table(int Mt, resample_detail::cd* tw)
-{
-    for (size_t k = 0; k < twiddle_count(Mt); ++k) {
-        const double ang = -2.0 * M_PI * static_cast<double>(k) / static_cast<double>(Mt);
-        tw[k] = resample_detail::cd(std::cos(ang), std::sin(ang));
-    }
-}
-
 }  // namespace hssfsst::tables

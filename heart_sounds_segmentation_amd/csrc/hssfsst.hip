@@ -1,27 +1,19 @@
-// hssfsst.hip -- host side of libhssfsst.so: the C ABI declared in include/hssfsst.h.
+// hssfsst.hip -- the FSST unit of libhssfsst.so's host side: the plan and everything that takes one (C ABI: include/hssfsst.h).
 // Plan creation does, once and in fp64, everything of the reference's `ssq.fsst(x, fs, window)`
 // (call site /root/reference/hss/transforms/synchrosqueeze.py:48) that depends only on
 // (fs, window); exec launches the gfx950 kernels of fsst_kernels.hpp.
 // There is no CPU compute path here by design (the CPU restatement is oracle/, test-only).
-#include "../../include/hssfsst.h"
-
-#include <hip/hip_runtime.h>
+// The other units: resample.hip, segmenter.hip, sequence.hip, host_io.hip; what they share: host_common.hpp.
+#include "host_common.hpp"
 
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
-#include <chrono>
 #include <mutex>
-#include <dlfcn.h>
 #include <cstdlib>
 #include <array>
 #include <atomic>
 #include <memory>
-#include <new>
-#include <thread>
-#include <vector>
 #include <type_traits>
 #include <utility>
 
@@ -33,64 +25,18 @@
 #include "fsst_gather.hpp"
 #include "fsst_ragged.hpp"
 #include "fsst_half.hpp"
-#include "fourier_resample.hpp"
-#include "fourier_resample_layout.hpp"
-#include "fourier_resample_gpu.hpp"
-#include "fourier_resample_ragged.hpp"
-#include "segmenter_lstm.hpp"
-#include "segmenter_layout.hpp"
-#include "segmenter_train.hpp"
-#include "decode_durations_layout.hpp"
-#include "decode_layout.hpp"
-#include "sequence_args.hpp"
-#include "segmenter_decode.hpp"
-#include "segmenter_decode_durations.hpp"
-#include "posterior_layout.hpp"
-#include "segmenter_posteriors.hpp"
-#include "segmenter_duration_posteriors.hpp"
-#include "segmenter_duration_counts.hpp"
-#include "score_layout.hpp"
-#include "segmenter_score.hpp"
-#include "stitch_layout.hpp"
-#include "segmenter_stitch.hpp"
 #include "fsst_tables.hpp"
 
 namespace tables = hssfsst::tables;
-namespace rslayout = hssfsst::rslayout;
+using namespace hssfsst::host;
 
 namespace {
-
-thread_local char g_err[512] = "";
-
-int fail(int code, const char* fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                          \
-    do {                                                                                       \
-        hipError_t e_ = (expr);                                                                \
-        if (e_ != hipSuccess)                                                                  \
-            return fail(HSSFSST_EHIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_),   \
-                        __FILE__, __LINE__);                                                   \
-    } while (0)
-
-// behind a kernel launch of the entry point `entry`
-int launch_check(const char* entry, const char* what)
-{
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(HSSFSST_EHIP, "%s: launch of %s failed: %s", entry, what, hipGetErrorString(e));
-    return 0;
-}
 
 // A-B and test switches, read ONCE per process (first use) from the environment, one variable per key: HSSFSST_<KEY in capitals>
 // is on when set to an empty string, a non-zero number or a word that starts with y or t (HSSFSST_FORCE_GENERIC: a value that
 // starts with 1).  Defaults are the measured best; no switch changes a result (every path gives the same bits, which is what most
-// of them exist to show).  Nothing else in the library reads the environment.
+// of them exist to show).  Nothing else in the library reads the environment, but for the segmenter's one switch, read the same
+// way in segmenter.hip (seg_ragged_pre_mib).
 struct DebugSwitches {
     bool no_fused = false;        // z-score always as a second kernel
     bool no_canon = false;        // the canonical band on the general kernels (fsst_mfma128.hpp)
@@ -101,7 +47,6 @@ struct DebugSwitches {
     bool force_generic = false;   // every radix length on the generic VALU kernel
     bool no_stream_fuse = false;  // a streaming step as copy + transform + merge-and-normalise launches
     bool no_pair = false;         // nwin 256 / 512: one wave per wave region (no wave pairs)
-    int seg_ragged_pre_mib = 0;   // ragged segmenter: bound of the projection scratch in MiB (a number; 0 or unset: the dense call's 128)
 };
 const DebugSwitches& debug_switches()
 {
@@ -121,173 +66,13 @@ const DebugSwitches& debug_switches()
         d.force_generic = fg != nullptr && fg[0] == '1';
         d.no_stream_fuse = on("HSSFSST_NO_STREAM_FUSE");
         d.no_pair = on("HSSFSST_NO_PAIR");
-        const char* pm = std::getenv("HSSFSST_SEG_RAGGED_PRE_MIB");
-        d.seg_ragged_pre_mib = pm != nullptr ? std::min(std::max(std::atoi(pm), 0), 1 << 16) : 0;
         return d;
     }();
     return sw;
 }
 
-// Makes `device` current for the scope and restores the caller's device on every exit path (a process
-// that drives several GPUs must not find its current HIP device changed by a library call).
-struct DeviceGuard {
-    int prev = -1;
-    bool switched = false;
-    hipError_t err = hipSuccess;
-    explicit DeviceGuard(int device)
-    {
-        err = hipGetDevice(&prev);
-        if (err == hipSuccess && prev != device) {
-            err = hipSetDevice(device);
-            switched = (err == hipSuccess);
-        }
-    }
-    ~DeviceGuard() { if (switched) (void)hipSetDevice(prev); }
-    DeviceGuard(const DeviceGuard&) = delete;
-    DeviceGuard& operator=(const DeviceGuard&) = delete;
-};
-#define DEVICE_SCOPE(dev)                                                                      \
-    DeviceGuard device_guard_(dev);                                                            \
-    if (device_guard_.err != hipSuccess)                                                       \
-        return fail(HSSFSST_EHIP, "selecting device %d failed: %s", (dev), hipGetErrorString(device_guard_.err))
-
-// the plan creates' device argument: a HIP device must exist (this library has no CPU path) and `device` must be one
-int check_device(const char* what, int device)
-{
-    int ndev = 0;
-    const hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev <= 0) {
-        (void)hipGetLastError();
-        return fail(HSSFSST_ENODEVICE, "%s: no HIP device (%s); this library has no CPU path", what,
-                    e == hipSuccess ? "device count 0" : hipGetErrorString(e));
-    }
-    if (device < 0 || device >= ndev) return fail(HSSFSST_EINVAL, "%s: device %d out of range [0,%d)", what, device, ndev);
-    return 0;
-}
-
 constexpr int kTile = 64;
 using hssfsst::kFpw128;
-
-// A plan's device buffer: capacity in elements of T; grow() frees the old block and allocates a larger one (contents are not
-// kept), upload() makes a fresh block holding a host table.  Freed with its owner.
-template <class T>
-struct DevBuf {
-    T* p = nullptr;
-    size_t cap = 0;
-    DevBuf() = default;
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    T* get() const { return p; }
-    int grow(size_t need)
-    {
-        if (need <= cap) return 0;
-        if (p) { HIP_TRY(hipFree(p)); p = nullptr; cap = 0; }
-        void* v = nullptr;
-        const hipError_t e = hipMalloc(&v, need * sizeof(T));
-        if (e != hipSuccess) return fail(HSSFSST_ENOMEM, "hipMalloc(%zu B): %s", need * sizeof(T), hipGetErrorString(e));
-        p = static_cast<T*>(v);
-        cap = need;
-        return 0;
-    }
-    int upload(const T* host, size_t n)                 // (into an empty or smaller buffer: grow() makes it fresh)
-    {
-        if (int rc = grow(n)) return rc;
-        HIP_TRY(hipMemcpy(p, host, n * sizeof(T), hipMemcpyHostToDevice));
-        return 0;
-    }
-};
-
-// A plan's pinned host buffer.  Mapped (the staging of small execs, the lent pool): hipHostMallocMapped with its device alias d,
-// a power of two from 4096 elements; otherwise default flags, no alias, 1.5x what is needed.  Capacity in elements of es bytes.
-template <class T>
-struct PinnedBuf {
-    T* h = nullptr;
-    T* d = nullptr;
-    size_t cap = 0;
-    bool mapped = true;
-    PinnedBuf() = default;
-    explicit PinnedBuf(bool mapped_) : mapped(mapped_) {}
-    PinnedBuf(const PinnedBuf&) = delete;
-    PinnedBuf& operator=(const PinnedBuf&) = delete;
-    ~PinnedBuf() { if (h) (void)hipHostFree(h); }
-    int grow(size_t need, size_t es)
-    {
-        if (need <= cap) return 0;
-        if (h) { HIP_TRY(hipHostFree(h)); h = nullptr; d = nullptr; cap = 0; }
-        size_t c = need + need / 2;
-        if (mapped) for (c = size_t(1) << 12; c < need; c *= 2) {}
-        void* hp = nullptr;
-        HIP_TRY(hipHostMalloc(&hp, c * es, mapped ? hipHostMallocMapped : hipHostMallocDefault));
-        void* dp = nullptr;
-        const hipError_t e = mapped ? hipHostGetDevicePointer(&dp, hp, 0) : hipSuccess;
-        if (e != hipSuccess) {
-            (void)hipHostFree(hp);
-            return fail(HSSFSST_EHIP, "hipHostGetDevicePointer: %s", hipGetErrorString(e));
-        }
-        h = static_cast<T*>(hp); d = static_cast<T*>(dp); cap = c;
-        return 0;
-    }
-};
-
-// A table that is made on the host for a list and read on the device: a ring of kRing pinned (not mapped) host blocks, a device
-// block, per host block the event of its last upload (a host block is not rewritten before that copy is done) and the key of the
-// list the device block holds.
-//   if (!t.same(n, key)) { t.begin(bytes, &h); ...fill h...; t.commit(stream, n, key); }     key(i): the i-th of n 64-bit words
-// begin() drops the key first and commit() stores it last, behind the queued copy: whatever fails in between, the next call with
-// the same list makes the table again.  A user without a key (n = 0) uploads at every call.  `what`: the entry point, for errors.
-// Why a ring: with ONE host block a call whose list differs from the previous call's had to wait on the host for the previous
-// upload, i.e. for everything queued on the stream before it -- a caller that walks groups of a long list (HipSegmenter.ragged
-// with max_steps) behind other work stalled at its second group.  With the ring only the upload kRing list changes back is waited
-// for.  The device block is one: the uploads and the kernels that read it are ordered by the plan's one stream.
-struct UploadedTable {
-    static constexpr int kRing = 4;
-    const char* what;
-    PinnedBuf<unsigned char> h[kRing];
-    DevBuf<unsigned char> d;
-    hipEvent_t ev[kRing] = {};
-    int cur = 0;
-    std::vector<int64_t> key;
-    size_t bytes = 0;
-    explicit UploadedTable(const char* what_) : what(what_) { for (auto& b : h) b.mapped = false; }
-    UploadedTable(const UploadedTable&) = delete;
-    UploadedTable& operator=(const UploadedTable&) = delete;
-    ~UploadedTable() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
-    const unsigned char* get() const { return d.get(); }
-    template <class Key>
-    bool same(size_t n, Key&& at) const
-    {
-        if (key.empty() || key.size() != n) return false;
-        for (size_t i = 0; i < n; ++i) if (key[i] != at(i)) return false;
-        return true;
-    }
-    int begin(size_t nbytes, unsigned char** host)
-    {
-        key.clear();
-        cur = (cur + 1) % kRing;
-        if (ev[cur]) HIP_TRY(hipEventSynchronize(ev[cur]));  // (the upload kRing changes back may still read this host block)
-        if (int rc = h[cur].grow(nbytes, 1)) return rc;
-        if (int rc = d.grow(nbytes)) return rc;
-        bytes = nbytes;
-        *host = h[cur].h;
-        return 0;
-    }
-    template <class Key>
-    int commit(hipStream_t st, size_t n, Key&& at)
-    {
-        if (!ev[cur]) HIP_TRY(hipEventCreateWithFlags(&ev[cur], hipEventDisableTiming));
-        HIP_TRY(hipMemcpyAsync(d.get(), h[cur].h, bytes, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipEventRecord(ev[cur], st));
-        try {
-            key.resize(n);
-        } catch (const std::bad_alloc&) {
-            return fail(HSSFSST_ENOMEM, "%s: out of host memory", what);
-        }
-        for (size_t i = 0; i < n; ++i) key[i] = at(i);
-        return 0;
-    }
-    int commit(hipStream_t st) { return commit(st, 0, [](size_t) { return int64_t(0); }); }
-};
 
 constexpr size_t kPinPoolMax = 64;                       // hssfsst_exec_pinned: buffers lent at a time (hssfsst.h)
 
@@ -366,19 +151,7 @@ struct hssfsst_plan {
 
 namespace {
 
-// The dynamic-LDS limit is a property of the kernel instantiation (per device), not of a plan: raise it ONCE to
-// the full 160 KiB, so that plans with different band widths sharing an instantiation cannot lower it under each
-// other and the hot path makes no driver call for it.
 using hssfsst::kMaxLdsBytes;
-template <class Kern>
-int allow_full_lds(Kern kern, int device, std::atomic<unsigned long long>& done)
-{
-    const unsigned long long bit = 1ull << (device & 63);
-    if (done.load(std::memory_order_acquire) & bit) return 0;
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLdsBytes));
-    done.fetch_or(bit, std::memory_order_release);
-    return 0;
-}
 
 // Resident blocks of `kern` (threads per block, dynamic LDS) on the plan's device, asked once and kept in `cache` (0 = not asked
 // yet; launchers that share a cache share the first answer).  whole_cus: one block per CU -- the CU count, or -1 when the kernel
@@ -1186,69 +959,6 @@ int hssfsst_plan_last_kernel(const hssfsst_plan* p, char* buf, int len)
     return 0;
 }
 
-// ---- hssfsst_allgather: ncclAllGather through dlopen (no link-time dependency on RCCL)
-namespace {
-struct RcclApi {
-    void* handle = nullptr;
-    int (*all_gather)(const void*, void*, size_t, int, void*, hipStream_t) = nullptr;
-    const char* (*error_string)(int) = nullptr;
-    bool tried = false;
-    std::string why;                                     // why RCCL is not available (dlerror() answers once: kept)
-};
-RcclApi& rccl_api()
-{
-    static RcclApi api;
-    static std::mutex mu;
-    std::lock_guard<std::mutex> lock(mu);
-    if (!api.tried) {
-        api.tried = true;
-        for (const char* name : {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"}) {
-            api.handle = dlopen(name, RTLD_NOW | RTLD_LOCAL);
-            if (api.handle) break;
-            const char* e = dlerror();
-            if (e && api.why.empty()) api.why = e;
-        }
-        if (api.handle) api.why = "symbol ncclAllGather missing";
-        if (api.handle) {
-            api.all_gather = reinterpret_cast<decltype(api.all_gather)>(dlsym(api.handle, "ncclAllGather"));
-            api.error_string = reinterpret_cast<decltype(api.error_string)>(dlsym(api.handle, "ncclGetErrorString"));
-        }
-    }
-    return api;
-}
-}  // namespace
-
-int hssfsst_allgather(const float* sendbuf, float* recvbuf, int64_t count, void* nccl_comm, void* stream, int timeout_ms)
-{
-    if (!sendbuf || !recvbuf || !nccl_comm || count < 0 || timeout_ms < 0) return fail(HSSFSST_EINVAL, "allgather: bad argument");
-    if (count == 0) return 0;
-    RcclApi& api = rccl_api();
-    if (!api.all_gather) return fail(HSSFSST_EUNSUPPORTED, "allgather: RCCL (librccl.so.1: ncclAllGather) is not available: %s", api.why.empty() ? "dlopen failed" : api.why.c_str());
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    constexpr int kNcclFloat32 = 7;                      // ncclFloat (rccl.h)
-    const int rc = api.all_gather(sendbuf, recvbuf, static_cast<size_t>(count), kNcclFloat32, nccl_comm, st);
-    if (rc != 0) return fail(HSSFSST_EHIP, "allgather: ncclAllGather: %s", api.error_string ? api.error_string(rc) : "error");
-    if (timeout_ms == 0) return 0;
-    hipEvent_t ev = nullptr;
-    HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    hipError_t e = hipEventRecord(ev, st);
-    const auto t0 = std::chrono::steady_clock::now();
-    while (e == hipSuccess) {
-        e = hipEventQuery(ev);
-        if (e == hipSuccess) break;
-        if (e != hipErrorNotReady) break;
-        e = hipSuccess;
-        if (std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - t0).count() > timeout_ms) {
-            (void)hipEventDestroy(ev);
-            return fail(HSSFSST_EHIP, "allgather: the collective did not complete within %d ms (a rank is missing?); it is still enqueued on the stream and owns both buffers", timeout_ms);
-        }
-        std::this_thread::yield();
-    }
-    (void)hipEventDestroy(ev);
-    if (e != hipSuccess) return fail(HSSFSST_EHIP, "allgather: %s", hipGetErrorString(e));
-    return 0;
-}
-
 int hssfsst_plan_fallbacks(hssfsst_plan* p)
 {
     if (!p) return fail(HSSFSST_EINVAL, "plan_fallbacks: plan is NULL");
@@ -1752,484 +1462,6 @@ int hssfsst_moments_merge(hssfsst_plan* p, const float* feats, int64_t batch, in
     return 0;
 }
 
-}  // extern "C"
-
-// Device resampler (hssfsst.h: hssfsst_resample_plan_create): the chirps, the convolution kernels' spectra and the twiddle
-// table of one (n, num), made on the host in fp64 (csrc/fourier_resample_gpu.hpp), plus the staging of host buffers.
-struct hssfsst_resample_plan {
-    int device = -1;
-    int64_t n = 0, num = 0;
-    int M1 = 1, M2 = 1, Mt = 1;
-    DevBuf<double2> d_tab;                               // c1[n] | B1[M1] | c2[num] | B2[M2] | tw[max(Mt / 2, 1)]
-    const double2 *c1 = nullptr, *B1 = nullptr, *c2 = nullptr, *B2 = nullptr, *tw = nullptr;
-    DevBuf<unsigned char> d_x, d_y;                      // a host input / output, staged
-    DevBuf<long long> d_lab, d_starts;                   // host labels / frame starts, staged
-    DevBuf<double2> d_work;                              // the large tier's convolutions [chunk][max(M1, M2)]
-    // ragged plans (hssfsst_resample_plan_create_ragged, n = 0): d_tab holds c2 | B2 only; the twiddle table is its own buffer,
-    // grown to the largest M of a call; the list's descriptors are made on the host and uploaded once per call
-    bool ragged = false;
-    DevBuf<double2> d_tw; int tw_M = 0;                  // tw[k] = exp(-2 pi i k / tw_M), k < tw_M / 2
-    UploadedTable desc{"resample_exec_ragged"};          // RaggedResampleSig[count] | table lengths (int64); no key: made at every call
-};
-
-namespace {
-
-constexpr int64_t kRsMaxLen = int64_t(1) << 26;          // n, num: convolutions of up to 2^27 points (2 GiB per signal)
-using rslayout::bluestein_tables;                        // (the resampler's host arithmetic: csrc/fourier_resample_layout.hpp)
-using rslayout::pow2_at_least;
-constexpr long long kRsWorkElems = static_cast<long long>(rslayout::kRsWorkBytes / sizeof(double2));
-
-unsigned rs_grid(long long total) { return static_cast<unsigned>((total + hssfsst::kRsThreads - 1) / hssfsst::kRsThreads); }
-
-int rs_check_dtypes(const char* what, int x_dtype, const void* y, int y_dtype)
-{
-    if ((x_dtype != HSSFSST_DTYPE_F32 && x_dtype != HSSFSST_DTYPE_F64) || (y && y_dtype != HSSFSST_DTYPE_F32 && y_dtype != HSSFSST_DTYPE_F64))
-        return fail(HSSFSST_EINVAL, "%s: unknown dtype (x %d, y %d)", what, x_dtype, y_dtype);
-    return 0;
-}
-
-// A resample exec's host buffers: x_bytes of x staged in front of the launches; y (nout elements of ysz bytes) and labels (nout) given
-// device buffers that rs_finish copies back.  Args: ResampleArgs or RaggedResampleArgs.
-template <class Args>
-int rs_stage(hssfsst_resample_plan* p, Args& a, const void* x, size_t x_bytes, int x_on_device, void* y, size_t ysz, int64_t* labels,
-             size_t nout, int out_on_device, hipStream_t st)
-{
-    int rc;
-    a.x = x;
-    if (!x_on_device) {
-        if ((rc = p->d_x.grow(x_bytes)) != 0) return rc;
-        HIP_TRY(hipMemcpyAsync(p->d_x.get(), x, x_bytes, hipMemcpyHostToDevice, st));
-        a.x = p->d_x.get();
-    }
-    a.y = y;
-    a.labels = reinterpret_cast<long long*>(labels);
-    if (!out_on_device) {
-        if (y) {
-            if ((rc = p->d_y.grow(nout * ysz)) != 0) return rc;
-            a.y = p->d_y.get();
-        }
-        if (labels) {
-            if ((rc = p->d_lab.grow(nout)) != 0) return rc;
-            a.labels = p->d_lab.get();
-        }
-    }
-    return 0;
-}
-
-template <class Args>
-int rs_finish(const Args& a, void* y, size_t ysz, int64_t* labels, size_t nout, int x_on_device, int out_on_device, hipStream_t st)
-{
-    if (!out_on_device) {
-        if (y) HIP_TRY(hipMemcpyAsync(y, a.y, nout * ysz, hipMemcpyDeviceToHost, st));
-        if (labels) HIP_TRY(hipMemcpyAsync(labels, a.labels, nout * sizeof(long long), hipMemcpyDeviceToHost, st));
-    }
-    if (!out_on_device || !x_on_device) HIP_TRY(hipStreamSynchronize(st));
-    return 0;
-}
-
-// Convolutions of M points, cnt of them at w (stride Mw), against a twiddle table of twM points: global DIF stages down to the block
-// length S, the block kernel, global DIT stages back up.  entry: the entry point, for errors
-int rs_dif(const char* entry, hipStream_t st, double2* w, long long Mw, long long cnt, int M, const double2* tw, int twM)
-{
-    const int S = M < hssfsst::kRsBlock ? M : hssfsst::kRsBlock;
-    const long long nb = cnt * (M / 2);
-    for (int len = M; len > S; len >>= 1) {
-        hipLaunchKernelGGL(hssfsst::resample_dif_pass_kernel, dim3(rs_grid(nb)), dim3(hssfsst::kRsThreads), 0, st, w, Mw, M, len, tw, twM, nb);
-        if (int r = launch_check(entry, "resample_dif_pass_kernel")) return r;
-    }
-    return 0;
-}
-int rs_dit(const char* entry, hipStream_t st, double2* w, long long Mw, long long cnt, int M, const double2* tw, int twM)
-{
-    const int S = M < hssfsst::kRsBlock ? M : hssfsst::kRsBlock;
-    const long long nb = cnt * (M / 2);
-    for (int len = 2 * S; len <= M; len <<= 1) {
-        hipLaunchKernelGGL(hssfsst::resample_dit_pass_kernel, dim3(rs_grid(nb)), dim3(hssfsst::kRsThreads), 0, st, w, Mw, M, len, tw, twM, nb);
-        if (int r = launch_check(entry, "resample_dit_pass_kernel")) return r;
-    }
-    return 0;
-}
-// BS: RsSharedB (named by the caller: deduction drops its __restrict__) or RsRaggedB
-template <class BS>
-int rs_conv(const char* entry, hipStream_t st, double2* w, long long Mw, long long cnt, int M, BS B, const double2* tw, int twM)
-{
-    const int S = M < hssfsst::kRsBlock ? M : hssfsst::kRsBlock;
-    if (int r = rs_dif(entry, st, w, Mw, cnt, M, tw, twM)) return r;
-    hipLaunchKernelGGL(hssfsst::resample_block_kernel<BS>, dim3(static_cast<unsigned>(cnt * (M / S))), dim3(hssfsst::kRsThreads), 0, st,
-                       w, Mw, M, S, B, tw, twM);
-    if (int r = launch_check(entry, "resample_block_kernel")) return r;
-    return rs_dit(entry, st, w, Mw, cnt, M, tw, twM);
-}
-
-// The inverse half of a large-tier chunk, cnt signals (a: ResampleArgs or RaggedResampleArgs) whose first convolutions stand in work:
-// the half spectrum in place, the second convolution (M2 points, the plan's B2), the samples and labels
-template <class Args>
-int rs_inverse_half(const char* entry, hipStream_t st, const Args& a, double2* work, long long Mw, long long cnt, const double2* B2,
-                    const double2* tw, int twM)
-{
-    const long long t2 = cnt * a.M2, t3 = cnt * a.num;
-    hipLaunchKernelGGL(hssfsst::resample_mid_kernel<Args>, dim3(rs_grid(t2)), dim3(hssfsst::kRsThreads), 0, st, a, work, Mw, t2);
-    if (int r = launch_check(entry, "resample_mid_kernel")) return r;
-    if (int r = rs_conv<hssfsst::RsSharedB>(entry, st, work, Mw, cnt, a.M2, B2, tw, twM)) return r;
-    hipLaunchKernelGGL(hssfsst::resample_store_kernel<Args>, dim3(rs_grid(t3)), dim3(hssfsst::kRsThreads), 0, st, a, work, Mw, t3);
-    return launch_check(entry, "resample_store_kernel");
-}
-
-// The two creates behind their argument checks: the plan on `device` with its tables c1[n] | B1[M1] | c2[num] | B2[M2] | tw[Mt / 2],
-// made on the host and uploaded in one piece.  n = 0: a ragged plan, which holds c2 | B2 only (its twiddles: rs_ragged_twiddles).
-int rs_plan_create(const char* what, hssfsst_resample_plan** out, int device, int64_t n, int64_t num)
-{
-    if (int rc = check_device(what, device)) return rc;
-    DEVICE_SCOPE(device);
-    using hssfsst::resample_detail::cd;
-    static_assert(sizeof(cd) == sizeof(double2), "std::complex<double> and double2 share a layout");
-    std::unique_ptr<hssfsst_resample_plan> p(new (std::nothrow) hssfsst_resample_plan());
-    if (!p) return fail(HSSFSST_ENOMEM, "%s: host allocation failed", what);
-    p->device = device; p->n = n; p->num = num; p->ragged = n == 0;
-    p->M1 = p->ragged ? 0 : pow2_at_least(2 * n - 1); p->M2 = pow2_at_least(2 * num - 1);
-    p->Mt = p->M1 > p->M2 ? p->M1 : p->M2;
-    const size_t o_B1 = static_cast<size_t>(n), o_c2 = o_B1 + p->M1, o_B2 = o_c2 + static_cast<size_t>(num), o_tw = o_B2 + p->M2;
-    const size_t total = o_tw + (p->ragged ? 0 : tables::twiddle_count(p->Mt));
-    try {
-        std::vector<cd> tab(total);
-        if (!p->ragged) {
-            bluestein_tables(n, p->M1, 1.0, tab.data(), tab.data() + o_B1);
-            tables::twiddle_table(p->Mt, tab.data() + o_tw);
-        }
-        bluestein_tables(num, p->M2, -1.0, tab.data() + o_c2, tab.data() + o_B2);
-        if (int rc = p->d_tab.upload(reinterpret_cast<const double2*>(tab.data()), total)) return rc;
-    } catch (const std::bad_alloc&) {
-        return fail(HSSFSST_ENOMEM, "%s: out of host memory", what);
-    }
-    const double2* t = p->d_tab.get();
-    if (!p->ragged) { p->c1 = t; p->B1 = t + o_B1; p->tw = t + o_tw; }
-    p->c2 = t + o_c2; p->B2 = t + o_B2;
-    *out = p.release();
-    return 0;
-}
-
-// the ragged plan's twiddle table, grown to Mt points: exp(-2 pi i k / Mt), k < Mt / 2, made on the host as the dense plan's.
-// A larger table holds the same bits at the indices a smaller one uses (k 2^j / (Mt 2^j) is exact): results do not depend on it.
-int rs_ragged_twiddles(hssfsst_resample_plan* p, int Mt)
-{
-    if (Mt <= p->tw_M) return 0;
-    try {
-        std::vector<hssfsst::resample_detail::cd> tw(tables::twiddle_count(Mt));
-        tables::twiddle_table(Mt, tw.data());
-        p->tw_M = 0;                                     // (upload's hipFree of the old table waits for the device: no earlier launch still reads it)
-        if (int rc = p->d_tw.upload(reinterpret_cast<const double2*>(tw.data()), tw.size())) return rc;
-    } catch (const std::bad_alloc&) {
-        return fail(HSSFSST_ENOMEM, "resample_exec_ragged: out of host memory");
-    }
-    p->tw_M = Mt;
-    return 0;
-}
-
-// The forward half of a ragged call's chunk (a.sig: its descriptors; tn: the call's table lengths on the device): B1 / M1 of every
-// distinct length, the chirp-weighted signals, the first convolutions -- tables and convolutions one class of equal M1 at a time
-int rs_ragged_forward_half(hssfsst_resample_plan* p, const rslayout::RaggedPlan& lay, const rslayout::Chunk& ch,
-                           const hssfsst::RaggedResampleArgs& a, const long long* tn, hipStream_t st)
-{
-    constexpr const char* kEntry = "resample_exec_ragged";
-    const double2* tw = p->d_tw.get();
-    const int twM = p->tw_M;
-    double2* work = p->d_work.get();
-    double2* tabs = work + ch.cnt * ch.Mw;
-    int rc;
-    for (long long u = ch.t0; u < ch.t0 + ch.ntab;) {
-        long long v = u;
-        const int M = static_cast<int>(lay.tabs[static_cast<size_t>(u)].M), S = M < hssfsst::kRsBlock ? M : hssfsst::kRsBlock;
-        while (v < ch.t0 + ch.ntab && lay.tabs[static_cast<size_t>(v)].M == M) ++v;
-        double2* t0 = tabs + lay.tabs[static_cast<size_t>(u)].off;
-        const long long tot = (v - u) * M;
-        hipLaunchKernelGGL(hssfsst::resample_ragged_table_kernel, dim3(rs_grid(tot)), dim3(hssfsst::kRsThreads), 0, st, t0, tn + u, M, tot);
-        if ((rc = launch_check(kEntry, "resample_ragged_table_kernel")) != 0) return rc;
-        if ((rc = rs_dif(kEntry, st, t0, M, v - u, M, tw, twM)) != 0) return rc;
-        hipLaunchKernelGGL(hssfsst::resample_ragged_table_block_kernel, dim3(static_cast<unsigned>((v - u) * (M / S))), dim3(hssfsst::kRsThreads),
-                           0, st, t0, M, S, tw, twM);
-        if ((rc = launch_check(kEntry, "resample_ragged_table_block_kernel")) != 0) return rc;
-        u = v;
-    }
-    const long long t1 = ch.cnt * ch.Mw;
-    hipLaunchKernelGGL(hssfsst::resample_load_kernel<hssfsst::RaggedResampleArgs>, dim3(rs_grid(t1)), dim3(hssfsst::kRsThreads), 0, st, a, work, ch.Mw, t1);
-    if ((rc = launch_check(kEntry, "resample_load_kernel")) != 0) return rc;
-    const hssfsst::RaggedResampleSig* sig = lay.sig.data() + ch.d0;
-    for (long long e0 = 0; e0 < ch.cnt;) {
-        long long e1 = e0;
-        const int M = static_cast<int>(sig[e0].M1);
-        while (e1 < ch.cnt && sig[e1].M1 == M) ++e1;
-        if ((rc = rs_conv(kEntry, st, work + e0 * ch.Mw, ch.Mw, e1 - e0, M, hssfsst::RsRaggedB{a.sig + e0, tabs}, tw, twM)) != 0) return rc;
-        e0 = e1;
-    }
-    return 0;
-}
-
-}  // namespace
-
-extern "C" {
-
-int hssfsst_resample_plan_create(hssfsst_resample_plan** out, int device, int64_t n, int64_t num)
-{
-    if (!out) return fail(HSSFSST_EINVAL, "resample_plan_create: out is NULL");
-    *out = nullptr;
-    if (n < 1 || num < 1 || device < 0)
-        return fail(HSSFSST_EINVAL, "resample_plan_create: bad argument (device=%d n=%lld num=%lld)", device, static_cast<long long>(n),
-                    static_cast<long long>(num));
-    if (n > kRsMaxLen || num > kRsMaxLen)
-        return fail(HSSFSST_EUNSUPPORTED, "resample_plan_create: lengths above %lld samples are not supported (n=%lld num=%lld)",
-                    static_cast<long long>(kRsMaxLen), static_cast<long long>(n), static_cast<long long>(num));
-    return rs_plan_create("resample_plan_create", out, device, n, num);
-}
-
-int hssfsst_resample_plan_destroy(hssfsst_resample_plan* p)
-{
-    if (!p) return 0;
-    DeviceGuard device_guard_(p->device);
-    delete p;                                            // (the buffers free themselves)
-    return 0;
-}
-
-int hssfsst_resample_plan_info(const hssfsst_resample_plan* p, int64_t* n, int64_t* num, int* m1, int* m2, int* lds_tier, int* device)
-{
-    if (!p) return fail(HSSFSST_EINVAL, "resample_plan_info: plan is NULL");
-    if (n) *n = p->n;
-    if (num) *num = p->num;
-    if (m1) *m1 = p->ragged ? 0 : p->M1;
-    if (m2) *m2 = p->M2;
-    if (lds_tier) *lds_tier = !p->ragged && p->Mt <= hssfsst::kRsLdsMax ? 1 : 0;
-    if (device) *device = p->device;
-    return 0;
-}
-
-int hssfsst_resample_exec(hssfsst_resample_plan* p, const void* x, int x_dtype, int64_t x_len, int64_t x_stride,
-                          const int64_t* starts, int starts_on_device, int64_t batch, int x_on_device,
-                          void* y, int y_dtype, int64_t* labels, int out_on_device, void* stream)
-{
-    if (!p || !x || (!y && !labels) || batch < 0 || x_len < 1)
-        return fail(HSSFSST_EINVAL, "resample_exec: bad argument (batch=%lld x_len=%lld)", static_cast<long long>(batch),
-                    static_cast<long long>(x_len));
-    if (int rc = rs_check_dtypes("resample_exec", x_dtype, y, y_dtype)) return rc;
-    if (batch > 0x7fffffffLL) return fail(HSSFSST_EINVAL, "resample_exec: batch %lld too large", static_cast<long long>(batch));
-    if (p->ragged) return fail(HSSFSST_EINVAL, "resample_exec: a ragged plan (hssfsst_resample_plan_create_ragged) takes hssfsst_resample_exec_ragged");
-    const int64_t n = p->n, num = p->num;
-    if (batch == 0) return 0;
-    if (!starts) {
-        if (batch > 1 && x_stride < 1) return fail(HSSFSST_EINVAL, "resample_exec: signal stride %lld < 1", static_cast<long long>(x_stride));
-        const int64_t span = (batch - 1) * (batch > 1 ? x_stride : 0) + n;
-        if (span > x_len)
-            return fail(HSSFSST_EINVAL, "resample_exec: %lld signals of %lld samples, stride %lld, need %lld samples, x holds %lld",
-                        static_cast<long long>(batch), static_cast<long long>(n), static_cast<long long>(x_stride),
-                        static_cast<long long>(span), static_cast<long long>(x_len));
-        if (!x_on_device) x_len = span;                  // (only that much is staged)
-    } else if (!starts_on_device) {
-        if (x_len < n) return fail(HSSFSST_EINVAL, "resample_exec: x holds %lld samples, a signal %lld", static_cast<long long>(x_len),
-                                   static_cast<long long>(n));
-        for (int64_t b = 0; b < batch; ++b)
-            if (starts[b] < 0 || starts[b] > x_len - n)
-                return fail(HSSFSST_EINVAL, "resample_exec: signal %lld starts at %lld, outside [0, %lld]", static_cast<long long>(b),
-                            static_cast<long long>(starts[b]), static_cast<long long>(x_len - n));
-    }
-    DEVICE_SCOPE(p->device);
-    const hipStream_t st = static_cast<hipStream_t>(stream);
-    const size_t xsz = x_dtype == HSSFSST_DTYPE_F64 ? sizeof(double) : sizeof(float);
-    const size_t ysz = y_dtype == HSSFSST_DTYPE_F64 ? sizeof(double) : sizeof(float);
-    const size_t nout = static_cast<size_t>(batch) * static_cast<size_t>(num);
-    int rc;
-    hssfsst::ResampleArgs a{};
-    if ((rc = rs_stage(p, a, x, static_cast<size_t>(x_len) * xsz, x_on_device, y, ysz, labels, nout, out_on_device, st)) != 0) return rc;
-    a.starts = reinterpret_cast<const long long*>(starts);
-    if (starts && !starts_on_device) {
-        if ((rc = p->d_starts.grow(static_cast<size_t>(batch))) != 0) return rc;
-        HIP_TRY(hipMemcpyAsync(p->d_starts.get(), starts, static_cast<size_t>(batch) * sizeof(long long), hipMemcpyHostToDevice, st));
-        a.starts = p->d_starts.get();
-    }
-    a.x_stride = x_stride;
-    a.n = n; a.num = num;
-    const int64_t N = n < num ? n : num;
-    a.nyq = N / 2 + 1;
-    a.nyq_bin = (N % 2 == 0 && n != num) ? N / 2 : -1;
-    a.nyq_scale = num < n ? 2.0 : 0.5;
-    a.inv_n = 1.0 / static_cast<double>(n);
-    a.x_f64 = x_dtype == HSSFSST_DTYPE_F64; a.y_f64 = y_dtype == HSSFSST_DTYPE_F64; a.num_even = num % 2 == 0;
-    a.M1 = p->M1; a.M2 = p->M2; a.Mt = p->Mt;
-    a.c1 = p->c1; a.B1 = p->B1; a.c2 = p->c2; a.B2 = p->B2; a.tw = p->tw;
-    a.b0 = 0;
-    if (p->Mt <= hssfsst::kRsLdsMax) {
-        static std::atomic<unsigned long long> lds_ok{0};
-        if ((rc = allow_full_lds(hssfsst::resample_lds_kernel, p->device, lds_ok)) != 0) return rc;
-        hipLaunchKernelGGL(hssfsst::resample_lds_kernel, dim3(static_cast<unsigned>(batch)), dim3(hssfsst::kRsThreads),
-                           static_cast<size_t>(p->Mt) * sizeof(double2), st, a);
-        if ((rc = launch_check("resample_exec", "resample_lds_kernel")) != 0) return rc;
-    } else {
-        const long long Mw = p->Mt;
-        const long long chunk = rslayout::dense_chunk(kRsWorkElems, Mw, batch);
-        if ((rc = p->d_work.grow(static_cast<size_t>(chunk) * static_cast<size_t>(Mw))) != 0) return rc;
-        double2* work = p->d_work.get();
-        for (long long b0 = 0; b0 < batch; b0 += chunk) {
-            const long long cb = batch - b0 < chunk ? batch - b0 : chunk, t1 = cb * p->M1;
-            a.b0 = b0;
-            hipLaunchKernelGGL(hssfsst::resample_load_kernel<hssfsst::ResampleArgs>, dim3(rs_grid(t1)), dim3(hssfsst::kRsThreads), 0, st, a, work, Mw, t1);
-            if ((rc = launch_check("resample_exec", "resample_load_kernel")) != 0) return rc;
-            if ((rc = rs_conv<hssfsst::RsSharedB>("resample_exec", st, work, Mw, cb, p->M1, p->B1, p->tw, p->Mt)) != 0) return rc;
-            if ((rc = rs_inverse_half("resample_exec", st, a, work, Mw, cb, p->B2, p->tw, p->Mt)) != 0) return rc;
-        }
-    }
-    return rs_finish(a, y, ysz, labels, nout, x_on_device, out_on_device, st);
-}
-
-int hssfsst_resample_plan_create_ragged(hssfsst_resample_plan** out, int device, int64_t num)
-{
-    if (!out) return fail(HSSFSST_EINVAL, "resample_plan_create_ragged: out is NULL");
-    *out = nullptr;
-    if (num < 1 || device < 0)
-        return fail(HSSFSST_EINVAL, "resample_plan_create_ragged: bad argument (device=%d num=%lld)", device, static_cast<long long>(num));
-    if (num > kRsMaxLen)
-        return fail(HSSFSST_EUNSUPPORTED, "resample_plan_create_ragged: lengths above %lld samples are not supported (num=%lld)",
-                    static_cast<long long>(kRsMaxLen), static_cast<long long>(num));
-    return rs_plan_create("resample_plan_create_ragged", out, device, 0, num);
-}
-
-int hssfsst_resample_exec_ragged(hssfsst_resample_plan* p, const void* x, int x_dtype, int64_t x_len, const int64_t* starts,
-                                 const int64_t* lens, int64_t count, int x_on_device, void* y, int y_dtype, int64_t* labels,
-                                 int out_on_device, void* stream)
-{
-    if (!p || !x || !starts || !lens || (!y && !labels) || count < 0 || x_len < 0)
-        return fail(HSSFSST_EINVAL, "resample_exec_ragged: bad argument (count=%lld x_len=%lld)", static_cast<long long>(count),
-                    static_cast<long long>(x_len));
-    if (!p->ragged) return fail(HSSFSST_EINVAL, "resample_exec_ragged: a dense plan (hssfsst_resample_plan_create) takes hssfsst_resample_exec");
-    if (int rc = rs_check_dtypes("resample_exec_ragged", x_dtype, y, y_dtype)) return rc;
-    if (count > 0x7fffffffLL) return fail(HSSFSST_EINVAL, "resample_exec_ragged: count %lld too large", static_cast<long long>(count));
-    bool too_long = false;
-    long long xlo = x_len, xhi = 0;
-    for (int64_t i = 0; i < count; ++i) {
-        if (lens[i] < 1) return fail(HSSFSST_EINVAL, "resample_exec_ragged: signal %lld has %lld samples", static_cast<long long>(i),
-                                     static_cast<long long>(lens[i]));
-        if (starts[i] < 0 || starts[i] > x_len - lens[i])
-            return fail(HSSFSST_EINVAL, "resample_exec_ragged: signal %lld spans [%lld, %lld), outside [0, %lld]", static_cast<long long>(i),
-                        static_cast<long long>(starts[i]), static_cast<long long>(starts[i]) + static_cast<long long>(lens[i]),
-                        static_cast<long long>(x_len));
-        too_long = too_long || lens[i] > kRsMaxLen;
-        xlo = std::min<long long>(xlo, starts[i]);
-        xhi = std::max<long long>(xhi, starts[i] + lens[i]);
-    }
-    if (too_long) return fail(HSSFSST_EUNSUPPORTED, "resample_exec_ragged: signals above %lld samples are not supported", static_cast<long long>(kRsMaxLen));
-    if (count == 0) return 0;
-    if (x_on_device) xlo = 0;
-    const int64_t num = p->num;
-    const int M2 = p->M2;
-    DEVICE_SCOPE(p->device);
-    const hipStream_t st = static_cast<hipStream_t>(stream);
-    int rc;
-    // the call's plan (chunks, tables, descriptors), made on the host and uploaded; the twiddles and the work grown to it
-    rslayout::RaggedPlan lay;
-    if (!rslayout::plan_ragged(starts, lens, count, M2, xlo, kRsWorkElems, lay))
-        return fail(HSSFSST_ENOMEM, "resample_exec_ragged: out of host memory");
-    unsigned char* h_desc = nullptr;
-    if ((rc = p->desc.begin(lay.desc_bytes(), &h_desc)) != 0) return rc;
-    rslayout::write_descriptors(lay, h_desc);
-    if ((rc = rs_ragged_twiddles(p, lay.Mt)) != 0) return rc;
-    if ((rc = p->desc.commit(st)) != 0) return rc;
-    const auto* dsig = reinterpret_cast<const hssfsst::RaggedResampleSig*>(p->desc.get());
-    const auto* dtn = reinterpret_cast<const long long*>(p->desc.get() + lay.sig_bytes());
-    if ((rc = p->d_work.grow(static_cast<size_t>(lay.max_elems))) != 0) return rc;
-    // staging of host buffers, as hssfsst_resample_exec
-    const size_t xsz = x_dtype == HSSFSST_DTYPE_F64 ? sizeof(double) : sizeof(float);
-    const size_t ysz = y_dtype == HSSFSST_DTYPE_F64 ? sizeof(double) : sizeof(float);
-    const size_t nout = static_cast<size_t>(count) * static_cast<size_t>(num);
-    hssfsst::RaggedResampleArgs a{};
-    if ((rc = rs_stage(p, a, static_cast<const unsigned char*>(x) + (x_on_device ? 0 : static_cast<size_t>(xlo) * xsz), static_cast<size_t>(xhi - xlo) * xsz,
-                       x_on_device, y, ysz, labels, nout, out_on_device, st)) != 0) return rc;
-    a.num = num; a.M2 = M2; a.c2 = p->c2;
-    a.x_f64 = x_dtype == HSSFSST_DTYPE_F64; a.y_f64 = y_dtype == HSSFSST_DTYPE_F64; a.num_even = num % 2 == 0;
-    for (const rslayout::Chunk& ch : lay.chunks) {
-        a.sig = dsig + ch.d0;
-        if ((rc = rs_ragged_forward_half(p, lay, ch, a, dtn, st)) != 0) return rc;
-        if ((rc = rs_inverse_half("resample_exec_ragged", st, a, p->d_work.get(), ch.Mw, ch.cnt, p->B2, p->d_tw.get(), p->tw_M)) != 0) return rc;
-    }
-    return rs_finish(a, y, ysz, labels, nout, x_on_device, out_on_device, st);
-}
-
-int hssfsst_resample(const double* x, int64_t n, int64_t num, double* y)
-{
-    if (!x || !y || n < 1 || num < 1) return fail(HSSFSST_EINVAL, "hssfsst_resample: bad argument (n=%lld num=%lld)",
-                                                   static_cast<long long>(n), static_cast<long long>(num));
-    try {
-        if (!hssfsst::fourier_resample(x, n, num, y)) return fail(HSSFSST_EINVAL, "hssfsst_resample: bad argument");
-    } catch (const std::bad_alloc&) {
-        return fail(HSSFSST_ENOMEM, "hssfsst_resample: out of host memory");
-    }
-    return 0;
-}
-
-int64_t hssfsst_pack_recordings(const float* const* ptrs, const int64_t* lens, int64_t count, int stride, int n,
-                                float* stage, int64_t stage_cap, int64_t* starts, int64_t starts_cap, int threads)
-{
-    if (!ptrs || !lens || !stage || !starts || count < 0 || stride < 1 || n < 1)
-        return fail(HSSFSST_EINVAL, "pack_recordings: bad argument");
-    std::vector<int64_t> pos(static_cast<size_t>(count) + 1, 0);
-    int64_t nf = 0;
-    for (int64_t i = 0; i < count; ++i) {
-        const int64_t T = lens[i];
-        if (T < 0 || !ptrs[i]) return fail(HSSFSST_EINVAL, "pack_recordings: recording %lld is NULL or negative", static_cast<long long>(i));
-        pos[i + 1] = pos[i] + T;
-        // frame_signal: L = floor((T - n) / stride) frames, one fewer than fit; L <= 0 -> the single frame x[:n]
-        int64_t L = (T - n >= 0) ? (T - n) / stride : -1;
-        if (L <= 0) L = 1;
-        if (nf + L > starts_cap) return fail(HSSFSST_EINVAL, "pack_recordings: more than %lld frames", static_cast<long long>(starts_cap));
-        for (int64_t k = 0; k < L; ++k) starts[nf + k] = pos[i] + k * stride;
-        nf += L;
-    }
-    const int64_t total = pos[count];
-    if (total > stage_cap) return fail(HSSFSST_EINVAL, "pack_recordings: %lld samples exceed the staging capacity %lld",
-                                       static_cast<long long>(total), static_cast<long long>(stage_cap));
-    int nt = threads > 0 ? threads : static_cast<int>(total / (1 << 20)) + 1;     // one thread per 4 MB of float32
-    if (nt > 8) nt = 8;
-    if (nt > count) nt = static_cast<int>(count > 0 ? count : 1);
-    auto work = [&](int t) {
-        // thread t copies the recordings whose first sample falls into its share of the staging buffer
-        const int64_t lo = total * t / nt, hi = total * (t + 1) / nt;
-        for (int64_t i = 0; i < count; ++i)
-            if (pos[i] >= lo && pos[i] < hi && lens[i] > 0) std::memcpy(stage + pos[i], ptrs[i], static_cast<size_t>(lens[i]) * sizeof(float));
-    };
-    if (nt <= 1) work(0);
-    else {
-        std::vector<std::thread> th;
-        for (int t = 1; t < nt; ++t) th.emplace_back(work, t);
-        work(0);
-        for (auto& x : th) x.join();
-    }
-    return nf;
-}
-
-int64_t hssfsst_parse_signal_csv(const char* text, int64_t len, float* signals, int64_t* labels, int64_t cap)
-{
-    if (!text || len < 0 || cap < 0 || (cap > 0 && (!signals || !labels))) return fail(HSSFSST_EINVAL, "parse_signal_csv: bad argument");
-    const char* p = text;
-    const char* end = text + len;
-    while (p < end && *p != '\n') ++p;                  // skiprows=1
-    if (p < end) ++p;
-    int64_t rows = 0;
-    while (p < end) {
-        const char* eol = p;
-        while (eol < end && *eol != '\n') ++eol;
-        const char* q = p;
-        while (q < eol && (*q == ' ' || *q == '\t' || *q == '\r')) ++q;
-        if (q < eol) {                                  // non-empty line
-            char* stop = nullptr;
-            const double sig = std::strtod(q, &stop);
-            if (stop == q || stop >= eol || *stop != ',')
-                return fail(HSSFSST_EINVAL, "parse_signal_csv: malformed row %lld", static_cast<long long>(rows + 2));
-            const char* l0 = stop + 1;
-            const double lab = std::strtod(l0, &stop);
-            if (stop == l0) return fail(HSSFSST_EINVAL, "parse_signal_csv: malformed label in row %lld", static_cast<long long>(rows + 2));
-            if (rows < cap) { signals[rows] = static_cast<float>(sig); labels[rows] = static_cast<int64_t>(lab); }
-            ++rows;
-        }
-        p = (eol < end) ? eol + 1 : end;
-    }
-    return rows;
-}
-
 int hssfsst_normalize_running(hssfsst_plan* p, float* feats, int64_t batch, int n, const double* state, void* stream)
 {
     if (!p || !feats || !state || batch < 0 || n < 1) return fail(HSSFSST_EINVAL, "normalize_running: bad argument");
@@ -2335,1178 +1567,6 @@ int hssfsst_stream_step(hssfsst_plan* p, float* tape, int64_t tape_len, int64_t 
         HIP_TRY(hipStreamSynchronize(st));
     }
     return 0;
-}
-
-}  // extern "C"
-
-// What the sequence-model entry points (hssfsst_decode_states .. hssfsst_posteriors_durations_counts) share: the decisions of
-// csrc/sequence_args.hpp put into words -- every text stands here, once -- and the loop over a list's launches.  Each entry
-// calls the checks in its own order: that order is which of two errors a caller sees.
-namespace {
-
-namespace seqargs = hssfsst::seqargs;
-
-int seq_check_list(const char* entry, const int64_t* offsets, int64_t count, int64_t max_steps)
-{
-    using Fault = seqargs::ListFault;
-    const seqargs::ListFinding f = seqargs::check_list(offsets, count, max_steps);
-    const long long i = f.index, limit = max_steps;
-    if (f.fault == Fault::kNone) return 0;
-    if (f.fault == Fault::kFirstNotZero) return fail(HSSFSST_EINVAL, "%s: offsets[0] is %lld, not 0", entry, static_cast<long long>(offsets[0]));
-    if (f.fault == Fault::kTooManySteps)
-        return fail(HSSFSST_EUNSUPPORTED, "%s: %lld steps in all, over the limit of 2^31 - 1", entry, static_cast<long long>(offsets[i]));
-    const long long from = offsets[i], to = offsets[i + 1];
-    if (f.fault == Fault::kNotIncreasing)
-        return fail(HSSFSST_EINVAL, "%s: offsets do not increase at index %lld (offsets[%lld] = %lld, offsets[%lld] = %lld)", entry, i + 1, i,
-                    from, i + 1, to);
-    return fail(HSSFSST_EUNSUPPORTED, "%s: recording %lld has %lld steps, over the limit of %lld", entry, i, to - from, limit);
-}
-
-int seq_check_nonnull(const char* entry, std::initializer_list<seqargs::NamedPointer> required)
-{
-    if (const char* name = seqargs::first_null(required)) return fail(HSSFSST_EINVAL, "%s: bad argument (%s is NULL)", entry, name);
-    return 0;
-}
-
-int seq_check_aligned(const char* entry, std::initializer_list<seqargs::NamedPointer> pointers)
-{
-    const seqargs::NamedPointer p = seqargs::first_misaligned(pointers);
-    if (p.name) return fail(HSSFSST_EINVAL, "%s: %s is not %u-byte aligned", entry, p.name, p.alignment);
-    return 0;
-}
-
-int seq_check_duration_table(const char* entry, const char* name, const float* table, int D)
-{
-    const seqargs::TableFinding f = seqargs::check_duration_table(table, D);
-    if (f.fault == seqargs::TableFault::kNaN)
-        return fail(HSSFSST_EINVAL, "%s: %s[%d][%d] is NaN (duration %d)", entry, name, f.row, f.column, f.column + 1);
-    if (f.fault == seqargs::TableFault::kDeadRow)
-        return fail(HSSFSST_EINVAL, "%s: row %d of %s is all -inf: state %d has no allowed duration", entry, f.row, name, f.row);
-    return 0;
-}
-
-// (transitions, initial) and, with `durations`, the host tables of the explicit-duration model, whose diagonal is not read: the
-// NaNs of the first two, then the two duration tables, then what the first two leave of a path.
-int seq_check_model(const char* entry, const float* transitions, const float* initial, const float* durations = nullptr,
-                    const float* edge = nullptr, int D = 0)
-{
-    const seqargs::ModelFinding f = seqargs::check_model(transitions, initial, durations != nullptr);
-    if (f.nan_at >= 16) return fail(HSSFSST_EINVAL, "%s: initial[%d] is NaN", entry, f.nan_at - 16);
-    if (f.nan_at >= 0) return fail(HSSFSST_EINVAL, "%s: transitions[%d][%d] is NaN", entry, f.nan_at / 4, f.nan_at % 4);
-    if (durations) {
-        if (int rc = seq_check_duration_table(entry, "durations", durations, D)) return rc;
-        if (int rc = seq_check_duration_table(entry, "edge", edge, D)) return rc;
-    }
-    if (f.dead_row >= 0)
-        return fail(HSSFSST_EINVAL,
-                    durations ? "%s: row %d of transitions has no finite off-diagonal entry: state %d has no successor"
-                              : "%s: row %d of transitions is all -inf: state %d has no successor", entry, f.dead_row, f.dead_row);
-    if (f.no_start) return fail(HSSFSST_EINVAL, "%s: initial is all -inf: no state to start in", entry);
-    return 0;
-}
-
-// The recordings of a list, `batch` per launch (the kernel's k*Batch: their offsets travel as kernel arguments).  For the
-// recordings r0 .. r0 + nrec of each launch args.off[] is filled, launch(r0, nrec) enqueues `kernel` -- after setting args.rec0,
-// where the kernel has one -- and the launch is checked.
-template <class Args, class Launch>
-int seq_for_each_batch(const char* entry, const char* kernel, const int64_t* offsets, int64_t count, int batch, Args& args, Launch launch)
-{
-    for (int64_t r0 = 0; r0 < count; r0 += batch) {
-        const int nrec = static_cast<int>(std::min<int64_t>(batch, count - r0));
-        for (int i = 0; i <= nrec; ++i) args.off[i] = offsets[r0 + i];
-        launch(r0, nrec);
-        if (int rc = launch_check(entry, kernel)) return rc;
-    }
-    return 0;
-}
-
-}  // namespace
-
-// BiLSTM segmenter (hssfsst.h: hssfsst_segmenter_create): the model's weights, uploaded once in the layouts the kernels of
-// csrc/segmenter_lstm.hpp consume, plus the scratch of its execs (owned by the plan, grown on demand, freed with it).
-namespace {
-
-// The forward tables of one BiLSTM layer, as the kernels of csrc/segmenter_lstm.hpp consume them (seglayout::wt_source,
-// gate_col_row, fwd_stream_source): made on the host by seg_upload_layer or on the device by seg_pack_kernel.
-struct SegLayer {
-    int F = 0, Fp = 0;                                   // input width and its multiple of 32
-    DevBuf<float> d_wt;                                  // [dir][Fp][4 Hp]: W_ih^T, columns in (unit tile, gate, unit) order
-    DevBuf<float> d_bias;                                // [dir][4 Hp]: b_ih + b_hh, same order
-    DevBuf<hssfsst::seg_h8> d_whh;                       // [dir][wave][K block][tile x gate][lane]{hi, lo}: W_hh x wscale, split f16
-};
-
-// The list of a ragged call on the device: its layout (segmenter_layout.hpp) and the layout's tables in one block
-// (seglayout::table_block), made and uploaded only when the offsets differ from the last call's.
-struct SegListTables {
-    struct Views {
-        const long long *off, *base;
-        const int *len, *rec, *walk;
-        int slots;
-        long long walked;                                // base[tiles]: the steps one direction walks
-    };
-    hssfsst::seglayout::Layout lay;                      // (of tab's key: rebuilt between its begin and commit)
-    UploadedTable tab;
-    explicit SegListTables(const char* what) : tab(what) {}
-    // offsets: checked by seg_check_list.  May throw std::bad_alloc.
-    int acquire(const int64_t* offsets, int64_t count, hipStream_t st, Views* out)
-    {
-        namespace seglayout = hssfsst::seglayout;
-        const seglayout::TableBlock b = seglayout::table_block(count);
-        auto key = [&](size_t i) { return offsets[i]; };
-        if (!tab.same(static_cast<size_t>(count + 1), key)) {
-            unsigned char* h = nullptr;
-            if (int rc = tab.begin(b.bytes, &h)) return rc;
-            seglayout::build(offsets, count, lay);
-            const std::vector<long long> base = seglayout::tile_base(lay);
-            std::memcpy(h + b.o_off, lay.slot_off.data(), b.slots * sizeof(long long));
-            std::memcpy(h + b.o_base, base.data(), (b.tiles + 1) * sizeof(long long));
-            std::memcpy(h + b.o_len, lay.slot_len.data(), b.slots * sizeof(int));
-            std::memcpy(h + b.o_rec, lay.slot_rec.data(), b.slots * sizeof(int));
-            std::memcpy(h + b.o_walk, lay.tile_walk.data(), b.tiles * sizeof(int));
-            if (int rc = tab.commit(st, static_cast<size_t>(count + 1), key)) return rc;
-        }
-        out->off = reinterpret_cast<const long long*>(tab.get() + b.o_off);
-        out->base = reinterpret_cast<const long long*>(tab.get() + b.o_base);
-        out->len = reinterpret_cast<const int*>(tab.get() + b.o_len);
-        out->rec = reinterpret_cast<const int*>(tab.get() + b.o_rec);
-        out->walk = reinterpret_cast<const int*>(tab.get() + b.o_walk);
-        out->slots = static_cast<int>(b.slots);
-        out->walked = seglayout::stash_floats_ragged(lay) / (2 * seglayout::kStashStepFloats);
-        return 0;
-    }
-};
-
-}  // namespace
-
-struct hssfsst_segmenter {
-    int device = -1;
-    int F = 0, H = 0;
-    struct Layer : SegLayer {
-        float inv_scale = 1.0f;                          // 1 / (wscale x kSegHScale)
-    } layer[2];
-    DevBuf<float> d_lin;                                 // linear.weight (4, 2H) | linear.bias (4)
-    DevBuf<float> d_pre;                                 // [dir][batch tile][Tc][gate tile][lane][4]: one chunk's input projection
-    DevBuf<float> d_y1, d_y2;                            // (B, T, 2H): the layers' outputs
-    DevBuf<float> d_state;                               // [h, c][dir][Bp][Hp]: carried from chunk to chunk and from layer 1 to layer 2
-    SegListTables list{"segmenter_exec_ragged"};         // hssfsst_segmenter_exec_ragged: kept while the next call has the same offsets
-};
-
-namespace {
-
-// src: {weight_ih, weight_hh, bias_ih, bias_hh} x {forward, reverse} of one nn.LSTM layer, as in its state_dict.  Every table is
-// filled by its output index through the functions seg_pack_kernel uses; the scale is seg_pack_scale_kernel's.
-int seg_upload_layer(hssfsst_segmenter::Layer& L, int F, int H, const float* const* src)
-{
-    namespace sl = hssfsst::seglayout;
-    L.F = F;
-    L.Fp = (F + 31) / 32 * 32;
-    float wmax = 0.0f;
-    for (int d = 0; d < 2; ++d) {
-        const float* whh = src[4 * d + 1];
-        for (size_t i = 0; i < static_cast<size_t>(4) * H * H; ++i) wmax = std::fmax(wmax, std::fabs(whh[i]));
-    }
-    // power-of-two scale that puts the largest |W_hh| in [2^12, 2^13): the lo halves of the split are normal f16 numbers down to
-    // weights 2^-26 times the largest one, and a sum of 256 products with |h| x 2^10 stays far below the f32 range
-    int e = 0;
-    float wscale = 1.0f;
-    if (wmax > 0.0f && std::isfinite(wmax)) { (void)std::frexp(wmax, &e); wscale = std::ldexp(1.0f, 13 - e); }
-    L.inv_scale = 1.0f / (wscale * hssfsst::kSegHScale);
-    const long long per_wt = static_cast<long long>(L.Fp) * sl::kGateCols, per_f = sl::kWtStreamHalves / 2;
-    std::vector<float> wt(static_cast<size_t>(2 * per_wt)), bias(static_cast<size_t>(2) * sl::kGateCols);
-    std::vector<_Float16> stream(static_cast<size_t>(2 * per_f));
-    for (int d = 0; d < 2; ++d) {
-        const float *wih = src[4 * d], *whh = src[4 * d + 1], *bih = src[4 * d + 2], *bhh = src[4 * d + 3];
-        for (long long i = 0; i < per_wt; ++i) {
-            const long long s = sl::wt_source(i, F, H);
-            wt[static_cast<size_t>(d * per_wt + i)] = s >= 0 ? wih[s] : 0.0f;
-        }
-        for (int n = 0; n < sl::kGateCols; ++n) {
-            const long long row = sl::gate_col_row(n, H);
-            bias[static_cast<size_t>(d) * sl::kGateCols + n] = row >= 0 ? bih[row] + bhh[row] : 0.0f;
-        }
-        for (long long i = 0; i < per_f; ++i) {
-            int lo = 0;
-            const long long s = sl::fwd_stream_source(i, H, &lo);
-            _Float16 out = static_cast<_Float16>(0.0f);
-            if (s >= 0) {
-                const float v = whh[s] * wscale;
-                const _Float16 hi = static_cast<_Float16>(v);
-                out = lo ? static_cast<_Float16>(v - static_cast<float>(hi)) : hi;
-            }
-            stream[static_cast<size_t>(d * per_f + i)] = out;
-        }
-    }
-    if (int rc = L.d_wt.upload(wt.data(), wt.size())) return rc;
-    if (int rc = L.d_bias.upload(bias.data(), bias.size())) return rc;
-    return L.d_whh.upload(reinterpret_cast<const hssfsst::seg_h8*>(stream.data()), stream.size() / 8);
-}
-
-constexpr int64_t kSegMaxSteps = 0x7fffffffLL / 8;       // steps of one dense exec, and of one recording of a ragged one
-constexpr int64_t kSegMaxBatch = 16 * 32768;
-static_assert(hssfsst::seglayout::kSlotRows == hssfsst::kSegRows, "a tile of the layout is the recurrence workgroup's rows");
-
-constexpr size_t kSegTileStepBytes = static_cast<size_t>(2) * hssfsst::kSegGateTiles * hssfsst::kSegTileFloats * sizeof(float);   // seglayout::Chunk
-
-int seg_check_dtype(const char* what, int feats_dtype)
-{
-    if (feats_dtype != HSSFSST_DTYPE_F32 && feats_dtype != HSSFSST_DTYPE_F16 && feats_dtype != HSSFSST_DTYPE_BF16)
-        return fail(HSSFSST_EINVAL, "%s: unknown feature dtype %d", what, feats_dtype);
-    return 0;
-}
-
-// The list of a ragged call (count >= 1): count + 1 host offsets from 0, strictly increasing, no recording over the dense step
-// limit, fewer than 2^31 steps in all.  One text for every entry point that takes such a list.
-int seg_check_list(const char* what, const int64_t* offsets, int64_t count)
-{
-    namespace seglayout = hssfsst::seglayout;
-    if (!offsets) return fail(HSSFSST_EINVAL, "%s: offsets is NULL", what);
-    if (count > kSegMaxBatch) return fail(HSSFSST_EINVAL, "%s: count %lld too large", what, static_cast<long long>(count));
-    if (offsets[0] != 0) return fail(HSSFSST_EINVAL, "%s: offsets[0] is %lld, not 0", what, static_cast<long long>(offsets[0]));
-    if (const int64_t i = seglayout::first_bad_length(offsets, count, kSegMaxSteps); i >= 0) {
-        if (offsets[i + 1] <= offsets[i])
-            return fail(HSSFSST_EINVAL, "%s: offsets do not increase at index %lld (offsets[%lld] = %lld, offsets[%lld] = %lld)", what,
-                        static_cast<long long>(i + 1), static_cast<long long>(i), static_cast<long long>(offsets[i]),
-                        static_cast<long long>(i + 1), static_cast<long long>(offsets[i + 1]));
-        return fail(HSSFSST_EINVAL, "%s: recording %lld has %lld steps, over the limit of %lld", what, static_cast<long long>(i),
-                    static_cast<long long>(offsets[i + 1] - offsets[i]), static_cast<long long>(kSegMaxSteps));
-    }
-    if (offsets[count] > 0x7fffffffLL)
-        return fail(HSSFSST_EINVAL, "%s: %lld steps in all, over the limit of 2^31 - 1", what, static_cast<long long>(offsets[count]));
-    return 0;
-}
-
-// The geometry of a call as the forward kernels take it.  Dense: B rows of T steps, Bp padded rows.  Ragged: the list's tables.
-void seg_dense_args(int B, int T, int Bp, hssfsst::SegProjArgs* pa, hssfsst::SegRecArgs* ra)
-{
-    pa->B = ra->B = B;
-    pa->T = ra->T = T;
-    ra->Bp = Bp;
-}
-void seg_ragged_args(const SegListTables::Views& t, hssfsst::SegProjArgs* pa, hssfsst::SegRecArgs* ra)
-{
-    ra->Bp = t.slots;
-    pa->slot_off = ra->slot_off = t.off;
-    pa->slot_len = ra->slot_len = t.len;
-    pa->tile_walk = ra->tile_walk = t.walk;
-    ra->tile_base = t.base;                              // (read by the TRAIN kernels only)
-    ra->walked = t.walked;
-}
-
-// state [2][dir][Bp][Hp] <- (p0, p1): grown, then seeded by seg_pair_init_kernel.  slot_rec: the slots' recordings of a ragged call
-// (B: the rows of p0 / p1), NULL for a dense one.
-int seg_seed_state(const char* what, hipStream_t st, DevBuf<float>& state, const float* p0, const float* p1, int B, int H, int Bp,
-                   const int* slot_rec)
-{
-    const size_t nstate = static_cast<size_t>(4) * Bp * hssfsst::kSegHp;
-    if (int rc = state.grow(nstate)) return rc;
-    hipLaunchKernelGGL((slot_rec ? hssfsst::seg_pair_init_kernel<true> : hssfsst::seg_pair_init_kernel<false>),
-                       dim3(static_cast<unsigned>((nstate + 255) / 256)), dim3(256), 0, st, p0, p1, state.get(), B, H, Bp, slot_rec);
-    return launch_check(what, slot_rec ? "seg_pair_init_kernel<ragged>" : "seg_pair_init_kernel");
-}
-
-// One layer, forwards: a launch pair (projection, recurrence) per chunk.  pa / ra come with the call's fields -- the geometry
-// (seg_dense_args, seg_ragged_args), x and y, the scratch, H, the scale and, for TRAIN, the stash; the layer's and the chunk's are
-// filled in here.  `what`: the entry point, for errors.
-template <bool RAGGED, bool TRAIN>
-int seg_forward_layer(const char* what, hipStream_t st, const SegLayer& L, hssfsst::SegProjArgs pa, hssfsst::SegRecArgs ra,
-                      const std::vector<hssfsst::seglayout::Chunk>& chunks)
-{
-    pa.F = L.F; pa.Fp = L.Fp; pa.H = ra.H;
-    pa.wt = L.d_wt.get(); pa.bias = L.d_bias.get();
-    ra.whh = L.d_whh.get();
-    for (const hssfsst::seglayout::Chunk& c : chunks) {
-        pa.n = ra.n = c.n;
-        pa.Tc = ra.Tc = c.Tc;
-        if constexpr (RAGGED) {
-            pa.s0 = ra.s0 = c.s0;
-        } else {
-            // the forward direction takes its chunks upwards, the reverse direction the mirrored ones downwards
-            pa.t0[0] = ra.t0[0] = c.s0;
-            pa.t0[1] = ra.t0[1] = ra.T - c.s0 - c.n;
-        }
-        hipLaunchKernelGGL(hssfsst::seg_proj_kernel<RAGGED>, dim3(4 * hssfsst::kSegHp / 64, static_cast<unsigned>(c.tiles * ((c.n + 7) / 8)), 2),
-                           dim3(256), 0, st, pa);
-        if (int rc = launch_check(what, RAGGED ? "seg_proj_kernel<ragged>" : "seg_proj_kernel")) return rc;
-        hipLaunchKernelGGL((hssfsst::seg_rec_kernel<RAGGED, TRAIN>), dim3(static_cast<unsigned>(c.tiles), 2), dim3(64 * hssfsst::kSegWaves), 0, st, ra);
-        if (int rc = launch_check(what, RAGGED ? (TRAIN ? "seg_rec_kernel<ragged, train>" : "seg_rec_kernel<ragged>")
-                                               : (TRAIN ? "seg_rec_kernel<train>" : "seg_rec_kernel"))) return rc;
-    }
-    return 0;
-}
-
-// The two layers of an inference exec and its head: layer 2 reads layer 1's output rectified and starts from its final state.
-// pa / ra: the call's geometry; rows: B T, or the list's steps.
-template <bool RAGGED>
-int seg_run_layers(hssfsst_segmenter* p, hipStream_t st, const void* feats, int feats_dtype, hssfsst::SegProjArgs pa, hssfsst::SegRecArgs ra,
-                   const std::vector<hssfsst::seglayout::Chunk>& chunks, long long rows, float* logp)
-{
-    ra.pre = pa.pre = p->d_pre.get();
-    ra.state = p->d_state.get();
-    ra.H = p->H;
-    pa.x = feats; pa.x_dtype = feats_dtype; pa.relu = 0;
-    ra.y = p->d_y1.get(); ra.inv_scale = p->layer[0].inv_scale;
-    if (int rc = seg_forward_layer<RAGGED, false>("segmenter_exec", st, p->layer[0], pa, ra, chunks)) return rc;
-    pa.x = p->d_y1.get(); pa.x_dtype = HSSFSST_DTYPE_F32; pa.relu = 1;
-    ra.y = p->d_y2.get(); ra.inv_scale = p->layer[1].inv_scale;
-    if (int rc = seg_forward_layer<RAGGED, false>("segmenter_exec", st, p->layer[1], pa, ra, chunks)) return rc;
-    hipLaunchKernelGGL(hssfsst::seg_head_kernel, dim3(static_cast<unsigned>((rows + 3) / 4)), dim3(256), 0, st, p->d_y2.get(), p->d_lin.get(),
-                       p->d_lin.get() + static_cast<size_t>(8) * p->H, logp, rows, 2 * p->H);
-    return launch_check("segmenter_exec", "seg_head_kernel");
-}
-
-// the scratch of an inference exec, in elements: one chunk's projection and the two layers' outputs of ylen elements each
-int seg_grow_scratch(hssfsst_segmenter* p, size_t pre, size_t ylen)
-{
-    if (int rc = p->d_pre.grow(pre)) return rc;
-    if (int rc = p->d_y1.grow(ylen)) return rc;
-    return p->d_y2.grow(ylen);
-}
-
-}  // namespace
-
-extern "C" {
-
-int hssfsst_segmenter_create(hssfsst_segmenter** out, int device, int input_size, int hidden, const float* const* lstm_1,
-                             const float* const* lstm_2, const float* linear_weight, const float* linear_bias)
-{
-    if (!out) return fail(HSSFSST_EINVAL, "segmenter_create: out is NULL");
-    *out = nullptr;
-    if (input_size < 1 || hidden < 1 || device < 0 || !lstm_1 || !lstm_2 || !linear_weight || !linear_bias)
-        return fail(HSSFSST_EINVAL, "segmenter_create: bad argument (device=%d input_size=%d hidden=%d, or a NULL array)", device, input_size, hidden);
-    for (int i = 0; i < 8; ++i)
-        if (!lstm_1[i] || !lstm_2[i]) return fail(HSSFSST_EINVAL, "segmenter_create: bad argument (weight array %d of a layer is NULL)", i);
-    if (hidden > hssfsst::kSegHp)
-        return fail(HSSFSST_EUNSUPPORTED, "segmenter_create: hidden sizes above %d are not supported (hidden=%d)", hssfsst::kSegHp, hidden);
-    if (input_size > (1 << 20)) return fail(HSSFSST_EUNSUPPORTED, "segmenter_create: input sizes above 2^20 are not supported (input_size=%d)", input_size);
-    if (int rc = check_device("segmenter_create", device)) return rc;
-    DEVICE_SCOPE(device);
-    std::unique_ptr<hssfsst_segmenter> p(new (std::nothrow) hssfsst_segmenter());
-    if (!p) return fail(HSSFSST_ENOMEM, "segmenter_create: host allocation failed");
-    p->device = device; p->F = input_size; p->H = hidden;
-    try {
-        if (int rc = seg_upload_layer(p->layer[0], input_size, hidden, lstm_1)) return rc;
-        if (int rc = seg_upload_layer(p->layer[1], 2 * hidden, hidden, lstm_2)) return rc;
-        std::vector<float> lin(static_cast<size_t>(8) * hidden + 4);
-        std::memcpy(lin.data(), linear_weight, static_cast<size_t>(8) * hidden * sizeof(float));
-        std::memcpy(lin.data() + static_cast<size_t>(8) * hidden, linear_bias, 4 * sizeof(float));
-        if (int rc = p->d_lin.upload(lin.data(), lin.size())) return rc;
-    } catch (const std::bad_alloc&) {
-        return fail(HSSFSST_ENOMEM, "segmenter_create: out of host memory");
-    }
-    *out = p.release();
-    return 0;
-}
-
-int hssfsst_segmenter_destroy(hssfsst_segmenter* p)
-{
-    if (!p) return 0;
-    DeviceGuard device_guard_(p->device);
-    delete p;                                            // (the buffers free themselves)
-    return 0;
-}
-
-int hssfsst_segmenter_info(const hssfsst_segmenter* p, int* input_size, int* hidden, int* max_hidden, int* device)
-{
-    if (max_hidden) *max_hidden = hssfsst::kSegHp;       // (a property of the library: answered for a NULL plan too)
-    if (!p) return fail(HSSFSST_EINVAL, "segmenter_info: plan is NULL");
-    if (input_size) *input_size = p->F;
-    if (hidden) *hidden = p->H;
-    if (device) *device = p->device;
-    return 0;
-}
-
-int hssfsst_segmenter_exec(hssfsst_segmenter* p, const void* feats, int feats_dtype, int64_t batch, int64_t steps, const float* h0,
-                           const float* c0, float* logp, void* stream)
-{
-    if (!p || !feats || !h0 || !c0 || !logp || batch < 1 || steps < 1)
-        return fail(HSSFSST_EINVAL, "segmenter_exec: bad argument (batch=%lld steps=%lld, or a NULL pointer)", static_cast<long long>(batch),
-                    static_cast<long long>(steps));
-    if (int rc = seg_check_dtype("segmenter_exec", feats_dtype)) return rc;
-    if (batch > kSegMaxBatch || steps > kSegMaxSteps)
-        return fail(HSSFSST_EINVAL, "segmenter_exec: batch %lld or steps %lld too large", static_cast<long long>(batch), static_cast<long long>(steps));
-    DEVICE_SCOPE(p->device);
-    const hipStream_t st = static_cast<hipStream_t>(stream);
-    const int B = static_cast<int>(batch), T = static_cast<int>(steps), H = p->H;
-    const int nbt = (B + hssfsst::kSegRows - 1) / hssfsst::kSegRows, Bp = nbt * hssfsst::kSegRows;
-    std::vector<hssfsst::seglayout::Chunk> chunks;
-    try {
-        chunks = hssfsst::seglayout::dense_chunks(T, nbt, kSegTileStepBytes, hssfsst::seglayout::kSegPreBytes);
-    } catch (const std::bad_alloc&) {
-        return fail(HSSFSST_ENOMEM, "segmenter_exec: out of host memory");
-    }
-    if (int rc = seg_grow_scratch(p, hssfsst::seglayout::pre_floats(chunks, kSegTileStepBytes), static_cast<size_t>(B) * T * 2 * H)) return rc;
-    if (int rc = seg_seed_state("segmenter_exec", st, p->d_state, h0, c0, B, H, Bp, nullptr)) return rc;
-    hssfsst::SegProjArgs pa{};
-    hssfsst::SegRecArgs ra{};
-    seg_dense_args(B, T, Bp, &pa, &ra);
-    return seg_run_layers<false>(p, st, feats, feats_dtype, pa, ra, chunks, static_cast<long long>(B) * T, logp);
-}
-
-int hssfsst_segmenter_exec_ragged(hssfsst_segmenter* p, const void* feats, int feats_dtype, const int64_t* offsets, int64_t count,
-                                  const float* h0, const float* c0, int state_rows, float* logp, void* stream)
-{
-    namespace seglayout = hssfsst::seglayout;
-    // the list first: what is wrong with it is said before the plan is looked at
-    if (count < 0) return fail(HSSFSST_EINVAL, "segmenter_exec_ragged: count %lld is negative", static_cast<long long>(count));
-    if (count == 0) return 0;
-    if (int rc = seg_check_list("segmenter_exec_ragged", offsets, count)) return rc;
-    if (state_rows != 1 && state_rows != count)
-        return fail(HSSFSST_EINVAL, "segmenter_exec_ragged: state_rows %d is neither 1 nor count %lld", state_rows, static_cast<long long>(count));
-    if (int rc = seg_check_dtype("segmenter_exec_ragged", feats_dtype)) return rc;
-    if (!p || !feats || !h0 || !c0 || !logp)
-        return fail(HSSFSST_EINVAL, "segmenter_exec_ragged: bad argument (%s is NULL)",
-                    !p ? "plan" : !feats ? "feats" : !h0 ? "h0" : !c0 ? "c0" : "logp");
-    DEVICE_SCOPE(p->device);
-    const hipStream_t st = static_cast<hipStream_t>(stream);
-    const int H = p->H;
-    const seglayout::Layout& lay = p->list.lay;
-    SegListTables::Views t{};
-    std::vector<seglayout::Chunk> chunks;
-    try {
-        if (int rc = p->list.acquire(offsets, count, st, &t)) return rc;
-        const int mib = debug_switches().seg_ragged_pre_mib;          // (A-B switch of tools/segmenter_ragged_bench.py: same bits)
-        chunks = seglayout::ragged_chunks(lay, kSegTileStepBytes, mib > 0 ? static_cast<size_t>(mib) << 20 : seglayout::kSegPreBytes);
-    } catch (const std::bad_alloc&) {
-        return fail(HSSFSST_ENOMEM, "segmenter_exec_ragged: out of host memory");
-    }
-    if (int rc = seg_grow_scratch(p, seglayout::pre_floats(chunks, kSegTileStepBytes), static_cast<size_t>(lay.total) * 2 * H)) return rc;
-    if (int rc = seg_seed_state("segmenter_exec", st, p->d_state, h0, c0, state_rows, H, t.slots, t.rec)) return rc;
-    hssfsst::SegProjArgs pa{};
-    hssfsst::SegRecArgs ra{};
-    seg_ragged_args(t, &pa, &ra);
-    return seg_run_layers<true>(p, st, feats, feats_dtype, pa, ra, chunks, lay.total, logp);
-}
-
-}  // extern "C"
-
-// Viterbi decoding of log-probs into state sequences (hssfsst.h: hssfsst_decode_states; csrc/segmenter_decode.hpp).  Stateless: the
-// quantised transitions and the launch's offsets travel as kernel arguments, kDecodeBatch recordings per launch.
-extern "C" {
-
-int hssfsst_decode_info(int* segment_steps, int64_t* max_steps)
-{
-    if (segment_steps) *segment_steps = hssfsst::declayout::kSegSteps;
-    if (max_steps) *max_steps = hssfsst::declayout::kMaxSteps;
-    return 0;
-}
-
-int hssfsst_decode_states(const float* logp, const int64_t* offsets, int64_t count, const float* transitions, const float* initial,
-                          uint8_t* states, int64_t* scores, int device, void* stream)
-{
-    namespace dl = hssfsst::declayout;
-    constexpr const char* kEntry = "decode_states";
-    if (count < 0) return fail(HSSFSST_EINVAL, "%s: count %lld is negative", kEntry, static_cast<long long>(count));
-    if (int rc = seq_check_nonnull(kEntry, {{"logp", logp}, {"offsets", offsets}, {"transitions", transitions}, {"initial", initial},
-                                            {"states", states}})) return rc;
-    if (device < 0) return fail(HSSFSST_EINVAL, "%s: device %d is negative", kEntry, device);
-    if (int rc = seq_check_aligned(kEntry, {{"logp", logp, 16}})) return rc;
-    if (int rc = seq_check_model(kEntry, transitions, initial)) return rc;
-    if (int rc = seq_check_list(kEntry, offsets, count, dl::kMaxSteps)) return rc;
-    if (count == 0) return 0;
-    if (int rc = check_device(kEntry, device)) return rc;
-    DEVICE_SCOPE(device);
-    const hipStream_t st = static_cast<hipStream_t>(stream);
-    hssfsst::DecodeArgs args{};
-    args.A = dl::quantise_transitions(transitions);
-    args.pi = dl::quantise4(initial);
-    return seq_for_each_batch(kEntry, "seg_decode_kernel", offsets, count, hssfsst::kDecodeBatch, args, [&](int64_t r0, int nrec) {
-        hipLaunchKernelGGL(hssfsst::seg_decode_kernel, dim3(static_cast<unsigned>(nrec)), dim3(dl::kLanes), 0, st, logp, states,
-                           scores ? reinterpret_cast<long long*>(scores) + r0 : nullptr, args);
-    });
-}
-
-}  // extern "C"
-
-// Explicit-duration Viterbi decoding (hssfsst.h: hssfsst_decode_durations; csrc/segmenter_decode_durations.hpp).  Stateless: the
-// quantised transitions and the launch's offsets travel as kernel arguments, kDurDecodeBatch recordings per launch; the two
-// duration tables travel as the arguments of fill launches into the head of the caller's workspace, so nothing is copied from
-// host memory and every launch is stream-ordered.
-extern "C" {
-
-int hssfsst_decode_durations_info(int* max_duration, int64_t* max_steps, int64_t* workspace_bytes_per_step)
-{
-    if (max_duration) *max_duration = hssfsst::durlayout::kMaxDuration;
-    if (max_steps) *max_steps = hssfsst::durlayout::kMaxSteps;
-    if (workspace_bytes_per_step) *workspace_bytes_per_step = hssfsst::durlayout::kWorkspaceBytesPerStep;
-    return 0;
-}
-
-int hssfsst_decode_durations(const float* logp, const int64_t* offsets, int64_t count, const float* transitions, const float* initial,
-                             const float* durations, const float* edge, int max_duration, uint8_t* states, int64_t* scores,
-                             void* workspace, int64_t workspace_bytes, int device, void* stream)
-{
-    namespace dl = hssfsst::declayout;
-    namespace ul = hssfsst::durlayout;
-    constexpr const char* kEntry = "decode_durations";
-    if (count < 0) return fail(HSSFSST_EINVAL, "%s: count %lld is negative", kEntry, static_cast<long long>(count));
-    if (int rc = seq_check_nonnull(kEntry, {{"logp", logp}, {"offsets", offsets}, {"transitions", transitions}, {"initial", initial},
-                                            {"durations", durations}, {"edge", edge}, {"states", states}, {"workspace", workspace}}))
-        return rc;
-    if (device < 0) return fail(HSSFSST_EINVAL, "%s: device %d is negative", kEntry, device);
-    if (max_duration < 1 || max_duration > ul::kMaxDuration)
-        return fail(HSSFSST_EINVAL, "%s: max_duration %d is outside 1..%d", kEntry, max_duration, ul::kMaxDuration);
-    const int D = max_duration;
-    if (int rc = seq_check_aligned(kEntry, {{"logp", logp, 16}, {"workspace", workspace, 16}})) return rc;
-    if (int rc = seq_check_model(kEntry, transitions, initial, durations, edge, D)) return rc;
-    if (int rc = seq_check_list(kEntry, offsets, count, ul::kMaxSteps)) return rc;
-    const int64_t need = ul::kWorkspaceBytesPerStep * ul::workspace_steps(offsets[count], D);
-    if (workspace_bytes < need)
-        return fail(HSSFSST_EINVAL, "%s: workspace of %lld bytes is too small: %lld steps and max_duration %d need %lld", kEntry,
-                    static_cast<long long>(workspace_bytes), static_cast<long long>(offsets[count]), D, static_cast<long long>(need));
-    if (count == 0) return 0;
-    if (int rc = check_device(kEntry, device)) return rc;
-    DEVICE_SCOPE(device);
-    const hipStream_t st = static_cast<hipStream_t>(stream);
-    long long* table = static_cast<long long*>(workspace);
-    unsigned short* back = reinterpret_cast<unsigned short*>(table + ul::table_words(D));
-    hssfsst::DurFillArgs fa{};
-    fa.D = D;
-    for (int first = 0; first < 8 * D; first += hssfsst::kDurFillValues) {
-        fa.first = first;
-        fa.n = std::min(hssfsst::kDurFillValues, 8 * D - first);
-        for (int i = 0; i < fa.n; ++i) fa.v[i] = first + i < 4 * D ? durations[first + i] : edge[first + i - 4 * D];
-        hipLaunchKernelGGL(hssfsst::seg_durations_fill_kernel, dim3(1), dim3(hssfsst::kDurFillValues), 0, st, table, fa);
-        if (int rc = launch_check(kEntry, "seg_durations_fill_kernel")) return rc;
-    }
-    hssfsst::DurDecodeArgs args{};
-    args.tb = ul::quantise_tables(transitions, initial);
-    args.D = D;
-    return seq_for_each_batch(kEntry, "seg_decode_durations_kernel", offsets, count, hssfsst::kDurDecodeBatch, args, [&](int64_t r0, int nrec) {
-        hipLaunchKernelGGL(hssfsst::seg_decode_durations_kernel, dim3(static_cast<unsigned>(nrec)), dim3(ul::kLanes), 0, st, logp, states,
-                           scores ? reinterpret_cast<long long*>(scores) + r0 : nullptr, back, table, args);
-    });
-}
-
-}  // extern "C"
-
-// Forward-backward under the transition model (hssfsst.h: hssfsst_posteriors; csrc/segmenter_posteriors.hpp).  Stateless: the
-// launch's offsets travel as kernel arguments, kPostBatch recordings per launch; the tables are read from device memory.
-extern "C" {
-
-int hssfsst_posteriors_info(int* segment_steps, int64_t* max_steps, int64_t* work_bytes_per_step, int64_t* work_bytes_per_recording)
-{
-    if (segment_steps) *segment_steps = hssfsst::postlayout::kSegSteps;
-    if (max_steps) *max_steps = hssfsst::postlayout::kMaxSteps;
-    if (work_bytes_per_step) *work_bytes_per_step = hssfsst::postlayout::kWorkBytesPerStep;
-    if (work_bytes_per_recording) *work_bytes_per_recording = hssfsst::postlayout::kWorkBytesPerRecording;
-    return 0;
-}
-
-int hssfsst_posteriors(const float* logp, const int64_t* offsets, int64_t count, const float* a_pi, const uint8_t* labels, float* gamma,
-                       double* loglik, double* score, double* xi, double* gamma0, void* work, int64_t work_bytes, int device, void* stream)
-{
-    namespace pl = hssfsst::postlayout;
-    constexpr const char* kEntry = "posteriors";
-    if (count < 0) return fail(HSSFSST_EINVAL, "%s: count %lld is negative", kEntry, static_cast<long long>(count));
-    if (int rc = seq_check_nonnull(kEntry, {{"logp", logp}, {"offsets", offsets}, {"a_pi", a_pi}, {"gamma", gamma}, {"loglik", loglik},
-                                            {"work", work}})) return rc;
-    if (score && !labels) return fail(HSSFSST_EINVAL, "%s: bad argument (labels is NULL while score is not)", kEntry);
-    if (device < 0) return fail(HSSFSST_EINVAL, "%s: device %d is negative", kEntry, device);
-    if (int rc = seq_check_aligned(kEntry, {{"logp", logp, 16}, {"gamma", gamma, 16}, {"work", work, 16}, {"a_pi", a_pi, 4}, {"loglik", loglik, 8},
-                                            {"score", score, 8}, {"xi", xi, 8}, {"gamma0", gamma0, 8}})) return rc;
-    if (int rc = seq_check_list(kEntry, offsets, count, pl::kMaxSteps)) return rc;
-    const int64_t need = pl::workspace_bytes(offsets[count], count);
-    if (work_bytes < need)
-        return fail(HSSFSST_EINVAL, "%s: work of %lld bytes is too small: %lld steps in %lld recordings need %lld", kEntry,
-                    static_cast<long long>(work_bytes), static_cast<long long>(offsets[count]), static_cast<long long>(count),
-                    static_cast<long long>(need));
-    if (count == 0) return 0;
-    if (int rc = check_device(kEntry, device)) return rc;
-    DEVICE_SCOPE(device);
-    const hipStream_t st = static_cast<hipStream_t>(stream);
-    hssfsst::PostArgs args{};
-    return seq_for_each_batch(kEntry, "seg_posteriors_kernel", offsets, count, hssfsst::kPostBatch, args, [&](int64_t r0, int nrec) {
-        args.rec0 = r0;
-        hipLaunchKernelGGL(hssfsst::seg_posteriors_kernel, dim3(static_cast<unsigned>(nrec)), dim3(pl::kLanes), 0, st, logp, a_pi, labels, gamma,
-                           loglik + r0, score ? score + r0 : nullptr, xi ? xi + 16 * r0 : nullptr, gamma0 ? gamma0 + 4 * r0 : nullptr,
-                           static_cast<double*>(work), args);
-    });
-}
-
-}  // extern "C"
-
-// Forward-backward under the explicit-duration model (hssfsst.h: hssfsst_posteriors_durations;
-// csrc/segmenter_duration_posteriors.hpp).  Stateless: the launch's offsets travel as kernel arguments, kDurPostBatch recordings per
-// launch; all four tables are read from device memory, the two duration tables through a fill launch into the workspace's head.
-// hssfsst_posteriors_durations_counts is the same call with the runs variant of the sweeps (it also leaves g and 1 / Z in a
-// workspace that is larger by csrc/duration_counts_layout.hpp's parts) and, behind them, the counts launches
-// (csrc/segmenter_duration_counts.hpp).
-namespace {
-
-// both entries: `with_counts` is the second one, whose `counts` is required
-int posteriors_durations_run(const char* kEntry, bool with_counts, const float* logp, const int64_t* offsets, int64_t count, const float* a_pi,
-                             const float* durations, const float* edge, int max_duration, const uint8_t* labels, float* gamma, float* onsets,
-                             double* loglik, double* score, double* xi, double* s0, double* counts, void* work, int64_t work_bytes, int device,
-                             void* stream)
-{
-    namespace dp = hssfsst::dplayout;
-    namespace dc = hssfsst::dclayout;
-    if (count < 0) return fail(HSSFSST_EINVAL, "%s: count %lld is negative", kEntry, static_cast<long long>(count));
-    if (int rc = seq_check_nonnull(kEntry, {{"logp", logp}, {"offsets", offsets}, {"a_pi", a_pi}, {"durations", durations}, {"edge", edge},
-                                            {"gamma", gamma}, {"loglik", loglik}, {"work", work}})) return rc;
-    if (with_counts)
-        if (int rc = seq_check_nonnull(kEntry, {{"counts", counts}})) return rc;
-    if (score && !labels) return fail(HSSFSST_EINVAL, "%s: bad argument (labels is NULL while score is not)", kEntry);
-    if (device < 0) return fail(HSSFSST_EINVAL, "%s: device %d is negative", kEntry, device);
-    if (max_duration < 1 || max_duration > dp::kMaxDuration)
-        return fail(HSSFSST_EINVAL, "%s: max_duration %d is outside 1..%d", kEntry, max_duration, dp::kMaxDuration);
-    const int D = max_duration;
-    if (int rc = seq_check_aligned(kEntry, {{"logp", logp, 16}, {"gamma", gamma, 16}, {"onsets", onsets, 16}, {"work", work, 16}, {"a_pi", a_pi, 4},
-                                            {"durations", durations, 4}, {"edge", edge, 4}, {"loglik", loglik, 8}, {"score", score, 8},
-                                            {"xi", xi, 8}, {"s0", s0, 8}, {"counts", counts, 8}})) return rc;
-    if (int rc = seq_check_list(kEntry, offsets, count, dp::kMaxSteps)) return rc;
-    const int64_t need = with_counts ? dc::workspace_bytes(offsets[count], count, D) : dp::workspace_bytes(offsets[count], count, D);
-    if (work_bytes < need)
-        return fail(HSSFSST_EINVAL, "%s: work of %lld bytes is too small: %lld steps in %lld recordings and max_duration %d need %lld", kEntry,
-                    static_cast<long long>(work_bytes), static_cast<long long>(offsets[count]), static_cast<long long>(count), D,
-                    static_cast<long long>(need));
-    if (count == 0) return 0;
-    if (int rc = check_device(kEntry, device)) return rc;
-    DEVICE_SCOPE(device);
-    const hipStream_t st = static_cast<hipStream_t>(stream);
-    const dc::Workspace wc = dc::workspace(offsets[count], count, D);
-    const dp::Workspace& ws = wc.sweeps;                 // (dp::workspace(): the plain entry uses nothing behind it)
-    char* w = static_cast<char*>(work);
-    double* tabm = reinterpret_cast<double*>(w + ws.table_mant);
-    int* tabe = reinterpret_cast<int*>(w + ws.table_exp);
-    double* stash_m = reinterpret_cast<double*>(w + ws.stash_mant);
-    int* stash_e = reinterpret_cast<int*>(w + ws.stash_exp);
-    double* checkpoints = reinterpret_cast<double*>(w + ws.checkpoints);
-    hipLaunchKernelGGL(hssfsst::seg_duration_posteriors_fill_kernel,
-                       dim3(static_cast<unsigned>((8 * D + hssfsst::kDurPostFillLanes - 1) / hssfsst::kDurPostFillLanes)),
-                       dim3(hssfsst::kDurPostFillLanes), 0, st, durations, edge, tabm, tabe, D);
-    if (int rc = launch_check(kEntry, "seg_duration_posteriors_fill_kernel")) return rc;
-    hssfsst::DurPostArgs args{};
-    args.D = D;
-    auto runs_of = [&](int64_t r0) {                     // what the launch of the recordings r0 .. sees of the second stash
-        return hssfsst::DurRunsOut{reinterpret_cast<double*>(w + wc.g_mant), reinterpret_cast<int*>(w + wc.g_exp),
-                                   reinterpret_cast<double*>(w + wc.invz_mant) + r0, reinterpret_cast<int*>(w + wc.invz_exp) + r0};
-    };
-    const char* sweep = with_counts ? "seg_duration_runs_sweep_kernel" : "seg_duration_posteriors_kernel";
-    int rc = seq_for_each_batch(kEntry, sweep, offsets, count, hssfsst::kDurPostBatch, args, [&](int64_t r0, int nrec) {
-        args.rec0 = r0;
-        if (with_counts)
-            hipLaunchKernelGGL(hssfsst::seg_duration_runs_sweep_kernel, dim3(static_cast<unsigned>(nrec)), dim3(dp::kLanes), 0, st, logp, a_pi,
-                               durations, edge, labels, gamma, onsets, loglik + r0, score ? score + r0 : nullptr, xi ? xi + 16 * r0 : nullptr,
-                               s0 ? s0 + 4 * r0 : nullptr, tabm, tabe, stash_m, stash_e, checkpoints, runs_of(r0), args);
-        else
-            hipLaunchKernelGGL(hssfsst::seg_duration_posteriors_kernel, dim3(static_cast<unsigned>(nrec)), dim3(dp::kLanes), 0, st, logp, a_pi,
-                               durations, edge, labels, gamma, onsets, loglik + r0, score ? score + r0 : nullptr, xi ? xi + 16 * r0 : nullptr,
-                               s0 ? s0 + 4 * r0 : nullptr, tabm, tabe, stash_m, stash_e, checkpoints, args);
-    });
-    if (rc || !with_counts) return rc;
-    return seq_for_each_batch(kEntry, "seg_duration_run_counts_kernel", offsets, count, hssfsst::kDurPostBatch, args, [&](int64_t r0, int nrec) {
-        args.rec0 = r0;
-        hipLaunchKernelGGL(hssfsst::seg_duration_run_counts_kernel, dim3(static_cast<unsigned>(nrec), static_cast<unsigned>(dc::groups(D))),
-                           dim3(dc::kLanes), 0, st, logp, a_pi, labels, counts + dc::counts_index(r0, 0, 0, 1, D), tabm, tabe, stash_m, stash_e,
-                           checkpoints, runs_of(r0), args);
-    });
-}
-
-}  // namespace
-
-extern "C" {
-
-int hssfsst_posteriors_durations_info(int* max_duration, int* segment_steps, int64_t* max_steps, int64_t* work_bytes_per_step,
-                                      int64_t* work_bytes_per_recording, int64_t* work_bytes_per_duration)
-{
-    namespace dp = hssfsst::dplayout;
-    if (max_duration) *max_duration = dp::kMaxDuration;
-    if (segment_steps) *segment_steps = dp::kSegSteps;
-    if (max_steps) *max_steps = dp::kMaxSteps;
-    if (work_bytes_per_step) *work_bytes_per_step = dp::kWorkBytesPerStep;
-    if (work_bytes_per_recording) *work_bytes_per_recording = dp::kWorkBytesPerRecording;
-    if (work_bytes_per_duration) *work_bytes_per_duration = dp::kWorkBytesPerDuration;
-    return 0;
-}
-
-int hssfsst_posteriors_durations(const float* logp, const int64_t* offsets, int64_t count, const float* a_pi, const float* durations,
-                                 const float* edge, int max_duration, const uint8_t* labels, float* gamma, float* onsets, double* loglik,
-                                 double* score, double* xi, double* s0, void* work, int64_t work_bytes, int device, void* stream)
-{
-    return posteriors_durations_run("posteriors_durations", false, logp, offsets, count, a_pi, durations, edge, max_duration, labels, gamma,
-                                    onsets, loglik, score, xi, s0, nullptr, work, work_bytes, device, stream);
-}
-
-int hssfsst_posteriors_durations_counts_info(int64_t* work_bytes_per_step, int64_t* work_bytes_per_recording, int64_t* work_bytes_per_duration,
-                                             int* durations_per_group)
-{
-    namespace dc = hssfsst::dclayout;
-    if (work_bytes_per_step) *work_bytes_per_step = dc::kWorkBytesPerStep;
-    if (work_bytes_per_recording) *work_bytes_per_recording = dc::kWorkBytesPerRecording;
-    if (work_bytes_per_duration) *work_bytes_per_duration = dc::kWorkBytesPerDuration;
-    if (durations_per_group) *durations_per_group = dc::kDurationsPerGroup;
-    return 0;
-}
-
-int hssfsst_posteriors_durations_counts(const float* logp, const int64_t* offsets, int64_t count, const float* a_pi, const float* durations,
-                                        const float* edge, int max_duration, const uint8_t* labels, float* gamma, float* onsets,
-                                        double* loglik, double* score, double* xi, double* s0, double* counts, void* work, int64_t work_bytes,
-                                        int device, void* stream)
-{
-    return posteriors_durations_run("posteriors_durations_counts", true, logp, offsets, count, a_pi, durations, edge, max_duration, labels,
-                                    gamma, onsets, loglik, score, xi, s0, counts, work, work_bytes, device, stream);
-}
-
-}  // extern "C"
-
-// Scoring a segmentation (hssfsst.h: hssfsst_score_states; csrc/segmenter_score.hpp, csrc/score_layout.hpp).  Stateless: the
-// launch's offsets travel as kernel arguments, kScoreBatch recordings per launch of the kernels that read the arenas; the sort and
-// the rank work on the caller's workspace, class after class, and the host decides the number of passes.
-namespace {
-
-// the launches of one class behind its items: the passes of the sort, then the three of the rank.  items_a holds the items.
-int score_rank_class(const char* entry, hipStream_t st, unsigned char* work, const hssfsst::scorelayout::Workspace& w, int64_t n,
-                     int passes, int per_recording, int64_t groups, unsigned long long* out)
-{
-    namespace sl = hssfsst::scorelayout;
-    unsigned long long* src = reinterpret_cast<unsigned long long*>(work + w.items_a);
-    unsigned long long* dst = reinterpret_cast<unsigned long long*>(work + w.items_b);
-    unsigned* hist = reinterpret_cast<unsigned*>(work + w.hist);
-    unsigned* sums = reinterpret_cast<unsigned*>(work + w.sums);
-    unsigned* tile_agg = reinterpret_cast<unsigned*>(work + w.tile_agg);
-    unsigned* tile_carry = reinterpret_cast<unsigned*>(work + w.tile_carry);
-    const long long nblocks = sl::blocks(n), entries = sl::hist_entries(n), chunks = sl::scan_chunks(n), tiles = sl::rank_tiles(n);
-    const dim3 sort_grid(static_cast<unsigned>(sl::sort_groups(n))), sort_block(sl::kSortThreads);
-    const dim3 scan_grid(static_cast<unsigned>(chunks)), scan_block(sl::kScanThreads);
-    for (int pass = 0; pass < passes; ++pass) {
-        hipLaunchKernelGGL(hssfsst::seg_score_hist_kernel, sort_grid, sort_block, 0, st, src, hist, static_cast<long long>(n), nblocks, pass);
-        if (int rc = launch_check(entry, "seg_score_hist_kernel")) return rc;
-        hipLaunchKernelGGL(hssfsst::seg_score_scan_sums_kernel, scan_grid, scan_block, 0, st, hist, sums, entries);
-        if (int rc = launch_check(entry, "seg_score_scan_sums_kernel")) return rc;
-        hipLaunchKernelGGL(hssfsst::seg_score_scan_top_kernel, dim3(1), scan_block, 0, st, sums, chunks);
-        if (int rc = launch_check(entry, "seg_score_scan_top_kernel")) return rc;
-        hipLaunchKernelGGL(hssfsst::seg_score_scan_apply_kernel, scan_grid, scan_block, 0, st, hist, sums, entries);
-        if (int rc = launch_check(entry, "seg_score_scan_apply_kernel")) return rc;
-        hipLaunchKernelGGL(hssfsst::seg_score_scatter_kernel, sort_grid, sort_block, 0, st, src, dst, hist, static_cast<long long>(n), nblocks,
-                           pass);
-        if (int rc = launch_check(entry, "seg_score_scatter_kernel")) return rc;
-        std::swap(src, dst);
-    }
-    const dim3 rank_grid(static_cast<unsigned>(tiles)), rank_block(sl::kRankThreads);
-    hipLaunchKernelGGL(hssfsst::seg_score_rank_kernel<false>, rank_grid, rank_block, 0, st, src, static_cast<long long>(n), tile_agg, tile_carry,
-                       out, per_recording, static_cast<long long>(groups));
-    if (int rc = launch_check(entry, "seg_score_rank_kernel<false>")) return rc;
-    hipLaunchKernelGGL(hssfsst::seg_score_rank_scan_kernel, dim3(1), dim3(64), 0, st, tile_agg, tile_carry, tiles);
-    if (int rc = launch_check(entry, "seg_score_rank_scan_kernel")) return rc;
-    hipLaunchKernelGGL(hssfsst::seg_score_rank_kernel<true>, rank_grid, rank_block, 0, st, src, static_cast<long long>(n), tile_agg, tile_carry,
-                       out, per_recording, static_cast<long long>(groups));
-    return launch_check(entry, "seg_score_rank_kernel<true>");
-}
-
-}  // namespace
-
-extern "C" {
-
-int hssfsst_score_info(int64_t* work_bytes_per_step, int64_t* work_bytes_per_recording, int64_t* work_bytes_constant, int* block_items,
-                       int* digit_bits, int* max_passes)
-{
-    namespace sl = hssfsst::scorelayout;
-    if (work_bytes_per_step) *work_bytes_per_step = sl::kWorkBytesPerStep;
-    if (work_bytes_per_recording) *work_bytes_per_recording = sl::kWorkBytesPerRecording;
-    if (work_bytes_constant) *work_bytes_constant = sl::kWorkBytesConstant;
-    if (block_items) *block_items = sl::kBlockItems;
-    if (digit_bits) *digit_bits = sl::kDigitBits;
-    if (max_passes) *max_passes = sl::kMaxPasses;
-    return 0;
-}
-
-int hssfsst_score_states(const float* logp, const uint8_t* states, const uint8_t* labels, const int64_t* offsets, int64_t count,
-                         int per_recording, int64_t* confusion, int64_t* ignored, int64_t* rank, void* work, int64_t work_bytes,
-                         const hssfsst_launch* where)
-{
-    namespace sl = hssfsst::scorelayout;
-    constexpr const char* kEntry = "score_states";
-    if (count < 0) return fail(HSSFSST_EINVAL, "%s: count %lld is negative", kEntry, static_cast<long long>(count));
-    if (int rc = seq_check_nonnull(kEntry, {{"labels", labels}, {"offsets", offsets}, {"confusion", confusion}, {"ignored", ignored},
-                                            {"where", where}})) return rc;
-    if (!states && !logp) return fail(HSSFSST_EINVAL, "%s: bad argument (states and logp are both NULL)", kEntry);
-    if (rank && !logp) return fail(HSSFSST_EINVAL, "%s: bad argument (logp is NULL while rank is not)", kEntry);
-    if (rank && !work) return fail(HSSFSST_EINVAL, "%s: bad argument (work is NULL while rank is not)", kEntry);
-    const int device = where->device;
-    if (device < 0) return fail(HSSFSST_EINVAL, "%s: device %d is negative", kEntry, device);
-    if (int rc = seq_check_aligned(kEntry, {{"logp", logp, 16}, {"work", work, 16}, {"confusion", confusion, 8}, {"ignored", ignored, 8},
-                                            {"rank", rank, 8}})) return rc;
-    if (int rc = seq_check_list(kEntry, offsets, count, seqargs::kMaxTotalSteps)) return rc;
-    const int64_t total = offsets[count];
-    const int64_t need = rank ? sl::workspace_bytes(total, count) : 0;
-    if (work_bytes < need)
-        return fail(HSSFSST_EINVAL, "%s: work of %lld bytes is too small: %lld steps in %lld recordings need %lld", kEntry,
-                    static_cast<long long>(work_bytes), static_cast<long long>(total), static_cast<long long>(count),
-                    static_cast<long long>(need));
-    if (count == 0) return 0;
-    if (int rc = check_device(kEntry, device)) return rc;
-    DEVICE_SCOPE(device);
-    const hipStream_t st = static_cast<hipStream_t>(where->stream);
-    const int64_t groups = per_recording ? count : 1;
-    const int64_t pooled[2] = {0, total};
-    const int64_t* list = per_recording ? offsets : pooled;
-    const int64_t nlist = per_recording ? count : 1;
-    const std::pair<void*, size_t> outputs[3] = {{confusion, 128 * static_cast<size_t>(groups)}, {ignored, 8 * static_cast<size_t>(groups)},
-                                                 {rank, 96 * static_cast<size_t>(groups)}};
-    for (const auto& z : outputs) {                      // the kernels add into them
-        if (!z.first) continue;
-        const hipError_t e = hipMemsetAsync(z.first, 0, z.second, st);
-        if (e != hipSuccess) return fail(HSSFSST_EHIP, "%s: clearing the outputs failed: %s", kEntry, hipGetErrorString(e));
-    }
-    hssfsst::ScoreArgs args{};
-    args.per_recording = per_recording ? 1 : 0;
-    auto grid_of = [&](int nrec) { return dim3(static_cast<unsigned>(sl::count_groups(args.off[nrec] - args.off[0]))); };
-    if (int rc = seq_for_each_batch(kEntry, "seg_score_counts_kernel", list, nlist, sl::kScoreBatch, args, [&](int64_t r0, int nrec) {
-            args.rec0 = r0;
-            args.nrec = nrec;
-            hipLaunchKernelGGL(hssfsst::seg_score_counts_kernel, grid_of(nrec), dim3(sl::kCountThreads), 0, st, logp, states, labels,
-                               reinterpret_cast<unsigned long long*>(confusion), reinterpret_cast<unsigned long long*>(ignored),
-                               reinterpret_cast<unsigned long long*>(rank), args);
-        })) return rc;
-    if (!rank) return 0;
-    const sl::Workspace w = sl::workspace(total);
-    const int passes = sl::passes(count, args.per_recording);
-    for (int cls = 0; cls < 4; ++cls) {
-        if (int rc = seq_for_each_batch(kEntry, "seg_score_keys_kernel", list, nlist, sl::kScoreBatch, args, [&](int64_t r0, int nrec) {
-                args.rec0 = r0;
-                args.nrec = nrec;
-                hipLaunchKernelGGL(hssfsst::seg_score_keys_kernel, grid_of(nrec), dim3(sl::kCountThreads), 0, st, logp, states, labels,
-                                   reinterpret_cast<unsigned long long*>(static_cast<unsigned char*>(work) + w.items_a), cls, args);
-            })) return rc;
-        if (int rc = score_rank_class(kEntry, st, static_cast<unsigned char*>(work), w, total, passes, args.per_recording, groups,
-                                      reinterpret_cast<unsigned long long*>(rank) + 3 * cls)) return rc;
-    }
-    return 0;
-}
-
-}  // extern "C"
-
-// Stitching overlapping windows' log-probs (hssfsst.h: hssfsst_stitch_windows; csrc/segmenter_stitch.hpp, csrc/stitch_layout.hpp).
-// Stateless: the launch's offsets and window blocks travel as kernel arguments, kStitchBatch recordings per launch; nothing is
-// copied from host memory and nothing waits.
-namespace {
-
-template <int MODE>
-void stitch_launch(bool weighted, dim3 grid, hipStream_t st, const float* win, const float* weights, float* out, unsigned char* dissent,
-                   const hssfsst::StitchArgs& args)
-{
-    const dim3 block(hssfsst::stitchlayout::kThreads);
-    if (weighted) hipLaunchKernelGGL((hssfsst::seg_stitch_kernel<MODE, true>), grid, block, 0, st, win, weights, out, dissent, args);
-    else hipLaunchKernelGGL((hssfsst::seg_stitch_kernel<MODE, false>), grid, block, 0, st, win, weights, out, dissent, args);
-}
-
-}  // namespace
-
-extern "C" {
-
-int hssfsst_stitch_windows(const float* win_logp, const int64_t* win_first, int64_t win_steps, const int64_t* offsets, int64_t count,
-                           int n, int stride, const float* weights, int mode, float* out, uint8_t* dissent, hssfsst_launch where)
-{
-    namespace stl = hssfsst::stitchlayout;
-    constexpr const char* kEntry = "stitch_windows";
-    if (count < 0) return fail(HSSFSST_EINVAL, "%s: count %lld is negative", kEntry, static_cast<long long>(count));
-    if (int rc = seq_check_nonnull(kEntry, {{"win_logp", win_logp}, {"win_first", win_first}, {"offsets", offsets}, {"out", out}})) return rc;
-    if (win_steps < 0) return fail(HSSFSST_EINVAL, "%s: win_steps %lld is negative", kEntry, static_cast<long long>(win_steps));
-    if (n < 1) return fail(HSSFSST_EINVAL, "%s: window length %d is not positive", kEntry, n);
-    if (stride < 1 || stride > n) return fail(HSSFSST_EINVAL, "%s: stride %d is outside 1 .. %d", kEntry, stride, n);
-    if (mode != HSSFSST_STITCH_PROB && mode != HSSFSST_STITCH_LOGP && mode != HSSFSST_STITCH_SELECT)
-        return fail(HSSFSST_EINVAL, "%s: unknown mode %d", kEntry, mode);
-    const int device = where.device;
-    if (device < 0) return fail(HSSFSST_EINVAL, "%s: device %d is negative", kEntry, device);
-    if (int rc = seq_check_aligned(kEntry, {{"win_logp", win_logp, 16}, {"out", out, 16}, {"weights", weights, 4}})) return rc;
-    if (int rc = seq_check_list(kEntry, offsets, count, seqargs::kMaxTotalSteps)) return rc;
-    for (int64_t i = 0; i < count; ++i) {
-        const int64_t rows = stl::window_rows(offsets[i + 1] - offsets[i], n, stride);
-        if (win_first[i] < 0 || win_first[i] > win_steps - rows)
-            return fail(HSSFSST_EINVAL, "%s: win_first[%lld] = %lld: the %lld window rows of recording %lld do not lie within the %lld of the arena",
-                        kEntry, static_cast<long long>(i), static_cast<long long>(win_first[i]), static_cast<long long>(rows),
-                        static_cast<long long>(i), static_cast<long long>(win_steps));
-    }
-    if (!stl::supported(n, stride))
-        return fail(HSSFSST_EUNSUPPORTED, "%s: windows of %d steps at stride %d overlap %d-fold, over the limit of %d", kEntry, n, stride,
-                    stl::ratio(n, stride), stl::kMaxRatio);
-    if (count == 0) return 0;
-    if (int rc = check_device(kEntry, device)) return rc;
-    DEVICE_SCOPE(device);
-    const hipStream_t st = static_cast<hipStream_t>(where.stream);
-    hssfsst::StitchArgs args{};
-    args.n = n;
-    args.stride = stride;
-    // (args.off is int: seq_check_list has held the list to 2^31 - 1 steps)
-    return seq_for_each_batch(kEntry, "seg_stitch_kernel", offsets, count, stl::kStitchBatch, args, [&](int64_t r0, int nrec) {
-        for (int i = 0; i < nrec; ++i) args.first[i] = win_first[r0 + i];
-        args.nrec = nrec;
-        const dim3 grid(static_cast<unsigned>(stl::launch_groups(offsets[r0 + nrec] - offsets[r0])));
-        if (mode == HSSFSST_STITCH_PROB) stitch_launch<stl::kProb>(weights != nullptr, grid, st, win_logp, weights, out, dissent, args);
-        else if (mode == HSSFSST_STITCH_LOGP) stitch_launch<stl::kLogp>(weights != nullptr, grid, st, win_logp, weights, out, dissent, args);
-        else stitch_launch<stl::kSelect>(weights != nullptr, grid, st, win_logp, weights, out, dissent, args);
-    });
-}
-
-}  // extern "C"
-
-// One trainable BiLSTM layer (hssfsst.h: hssfsst_bilstm_create): the tables of its current weights, packed on the device by
-// hssfsst_bilstm_set_weights (csrc/segmenter_train.hpp), and the scratch of its forward and backward calls.
-struct hssfsst_bilstm {
-    int device = -1;
-    int H = 0;
-    bool packed = false;
-    SegLayer layer;                                      // the forward tables, of the weights set last
-    DevBuf<hssfsst::seg_b8> d_bwd;                       // backward stream: W_hh, split bf16, as the B operand of dG . W_hh
-    DevBuf<float> d_scale;                               // {wscale, inv_scale}: made and read on the device only
-    DevBuf<float> d_pre;                                 // one chunk's input projection
-    DevBuf<float> d_state;                               // forward [h, c][dir][Bp][Hp]; backward [dh_rec, dc][dir][Bp][Hp]
-    SegListTables list{"bilstm_ragged"};                 // hssfsst_bilstm_*_ragged: kept while the next call has the same offsets
-};
-
-namespace {
-
-int bilstm_check_shape(const char* what, int64_t batch, int64_t steps)
-{
-    if (batch < 1 || steps < 1)
-        return fail(HSSFSST_EINVAL, "%s: bad argument (batch=%lld steps=%lld)", what, static_cast<long long>(batch), static_cast<long long>(steps));
-    if (batch > kSegMaxBatch || steps > kSegMaxSteps)
-        return fail(HSSFSST_EINVAL, "%s: batch %lld or steps %lld too large", what, static_cast<long long>(batch), static_cast<long long>(steps));
-    return 0;
-}
-
-// out0, out1 (2, B, H) <- the state seg_seed_state made, after the launches chained through it; slot_rec as there
-int bilstm_state_out(const char* what, hipStream_t st, const hssfsst_bilstm* p, float* out0, float* out1, int B, int Bp, const int* slot_rec)
-{
-    const size_t nout = static_cast<size_t>(4) * (slot_rec ? Bp : B) * p->H;
-    hipLaunchKernelGGL((slot_rec ? hssfsst::seg_pair_out_kernel<true> : hssfsst::seg_pair_out_kernel<false>),
-                       dim3(static_cast<unsigned>((nout + 255) / 256)), dim3(256), 0, st, p->d_state.get(), out0, out1, B, p->H, Bp, slot_rec);
-    return launch_check(what, slot_rec ? "seg_pair_out_kernel<ragged>" : "seg_pair_out_kernel");
-}
-
-// A training forward: (h0, c0) in, the layer over the chunks with its stash, (hn, cn) out.  pa / ra: the call's geometry
-// (seg_dense_args, seg_ragged_args); B: the rows of the states; slot_rec as in seg_seed_state.
-template <bool RAGGED>
-int bilstm_forward(const char* what, hssfsst_bilstm* p, hipStream_t st, const float* x, const float* h0, const float* c0, float* y, float* hn,
-                   float* cn, float* stash, int B, const int* slot_rec, hssfsst::SegProjArgs pa, hssfsst::SegRecArgs ra,
-                   const std::vector<hssfsst::seglayout::Chunk>& chunks)
-{
-    if (int rc = p->d_pre.grow(hssfsst::seglayout::pre_floats(chunks, kSegTileStepBytes))) return rc;
-    if (int rc = seg_seed_state(what, st, p->d_state, h0, c0, B, p->H, ra.Bp, slot_rec)) return rc;
-    pa.x = x; pa.x_dtype = HSSFSST_DTYPE_F32; pa.relu = 0;
-    ra.pre = pa.pre = p->d_pre.get();
-    ra.state = p->d_state.get(); ra.y = y; ra.H = p->H;
-    ra.stash = stash; ra.inv_scale_dev = p->d_scale.get() + 1;
-    if (int rc = seg_forward_layer<RAGGED, true>(what, st, p->layer, pa, ra, chunks)) return rc;
-    return bilstm_state_out(what, st, p, hn, cn, B, ra.Bp, slot_rec);
-}
-
-// what both backwards give seg_bwd_rec_kernel; the state is seeded by then
-hssfsst::SegBwdArgs bilstm_bwd_args(const hssfsst_bilstm* p, const float* stash, const float* c0, const float* dy, float* dgates, int B, int Bp)
-{
-    hssfsst::SegBwdArgs a{};
-    a.stash = stash; a.c0 = c0; a.dy = dy; a.wbwd = p->d_bwd.get(); a.state = p->d_state.get(); a.dgates = dgates;
-    a.B = B; a.H = p->H; a.Bp = Bp;
-    return a;
-}
-
-}  // namespace
-
-extern "C" {
-
-int hssfsst_bilstm_create(hssfsst_bilstm** out, int device, int input_size, int hidden)
-{
-    if (!out) return fail(HSSFSST_EINVAL, "bilstm_create: out is NULL");
-    *out = nullptr;
-    if (input_size < 1 || hidden < 1 || device < 0)
-        return fail(HSSFSST_EINVAL, "bilstm_create: bad argument (device=%d input_size=%d hidden=%d)", device, input_size, hidden);
-    if (hidden > hssfsst::kSegHp)
-        return fail(HSSFSST_EUNSUPPORTED, "bilstm_create: hidden sizes above %d are not supported (hidden=%d)", hssfsst::kSegHp, hidden);
-    if (input_size > (1 << 20)) return fail(HSSFSST_EUNSUPPORTED, "bilstm_create: input sizes above 2^20 are not supported (input_size=%d)", input_size);
-    if (int rc = check_device("bilstm_create", device)) return rc;
-    DEVICE_SCOPE(device);
-    std::unique_ptr<hssfsst_bilstm> p(new (std::nothrow) hssfsst_bilstm());
-    if (!p) return fail(HSSFSST_ENOMEM, "bilstm_create: host allocation failed");
-    p->device = device; p->H = hidden;
-    SegLayer& L = p->layer;
-    L.F = input_size;
-    L.Fp = (input_size + 31) / 32 * 32;
-    namespace sl = hssfsst::seglayout;
-    if (int rc = L.d_wt.grow(static_cast<size_t>(2) * L.Fp * sl::kGateCols)) return rc;
-    if (int rc = L.d_bias.grow(static_cast<size_t>(2) * sl::kGateCols)) return rc;
-    if (int rc = L.d_whh.grow(static_cast<size_t>(sl::kWtStreamHalves / 8))) return rc;
-    if (int rc = p->d_bwd.grow(static_cast<size_t>(sl::kBwdStreamHalves / 8))) return rc;
-    if (int rc = p->d_scale.grow(2)) return rc;
-    *out = p.release();
-    return 0;
-}
-
-int hssfsst_bilstm_destroy(hssfsst_bilstm* p)
-{
-    if (!p) return 0;
-    DeviceGuard device_guard_(p->device);
-    delete p;
-    return 0;
-}
-
-int hssfsst_bilstm_set_weights(hssfsst_bilstm* p, const float* const* weights, void* stream)
-{
-    if (!p || !weights) return fail(HSSFSST_EINVAL, "bilstm_set_weights: bad argument (%s is NULL)", !p ? "plan" : "weights");
-    for (int i = 0; i < 8; ++i)
-        if (!weights[i]) return fail(HSSFSST_EINVAL, "bilstm_set_weights: bad argument (weight array %d is NULL)", i);
-    DEVICE_SCOPE(p->device);
-    const hipStream_t st = static_cast<hipStream_t>(stream);
-    namespace sl = hssfsst::seglayout;
-    hssfsst::SegPackArgs a{};
-    for (int i = 0; i < 8; ++i) a.src[i] = weights[i];
-    const SegLayer& L = p->layer;
-    a.F = L.F; a.Fp = L.Fp; a.H = p->H;
-    a.scale = p->d_scale.get(); a.wt = L.d_wt.get(); a.bias = L.d_bias.get();
-    a.whh = reinterpret_cast<_Float16*>(L.d_whh.get());
-    a.bwd = reinterpret_cast<__bf16*>(p->d_bwd.get());
-    hipLaunchKernelGGL(hssfsst::seg_pack_scale_kernel, dim3(1), dim3(1024), 0, st, a);
-    if (int rc = launch_check("bilstm_set_weights", "seg_pack_scale_kernel")) return rc;
-    const long long most = std::max<long long>(static_cast<long long>(2) * L.Fp * sl::kGateCols, std::max(sl::kWtStreamHalves, sl::kBwdStreamHalves));
-    hipLaunchKernelGGL(hssfsst::seg_pack_kernel, dim3(static_cast<unsigned>((most + 255) / 256)), dim3(256), 0, st, a);
-    if (int rc = launch_check("bilstm_set_weights", "seg_pack_kernel")) return rc;
-    p->packed = true;
-    return 0;
-}
-
-int hssfsst_bilstm_stash_floats(const hssfsst_bilstm* p, int64_t batch, int64_t steps, int64_t* floats)
-{
-    if (!floats) return fail(HSSFSST_EINVAL, "bilstm_stash_floats: floats is NULL");
-    *floats = 0;
-    (void)p;                                             // (every hidden size runs on the padded geometry: answered for a NULL plan too)
-    if (int rc = bilstm_check_shape("bilstm_stash_floats", batch, steps)) return rc;
-    *floats = hssfsst::seglayout::stash_floats(batch, steps);
-    return 0;
-}
-
-int hssfsst_bilstm_forward(hssfsst_bilstm* p, const float* x, int64_t batch, int64_t steps, const float* h0, const float* c0, float* y,
-                           float* hn, float* cn, float* stash, void* stream)
-{
-    if (!p) return fail(HSSFSST_EINVAL, "bilstm_forward: plan is NULL");
-    if (int rc = bilstm_check_shape("bilstm_forward", batch, steps)) return rc;
-    if (!x || !h0 || !c0 || !y || !hn || !cn || !stash)
-        return fail(HSSFSST_EINVAL, "bilstm_forward: bad argument (%s is NULL)",
-                    !x ? "x" : !h0 ? "h0" : !c0 ? "c0" : !y ? "y" : !hn ? "hn" : !cn ? "cn" : "stash");
-    if (!p->packed) return fail(HSSFSST_EINVAL, "bilstm_forward: no weights yet (call hssfsst_bilstm_set_weights first)");
-    DEVICE_SCOPE(p->device);
-    const hipStream_t st = static_cast<hipStream_t>(stream);
-    const int B = static_cast<int>(batch), T = static_cast<int>(steps);
-    const int nbt = (B + hssfsst::kSegRows - 1) / hssfsst::kSegRows, Bp = nbt * hssfsst::kSegRows;
-    std::vector<hssfsst::seglayout::Chunk> chunks;
-    try {
-        chunks = hssfsst::seglayout::dense_chunks(T, nbt, kSegTileStepBytes, hssfsst::seglayout::kSegPreBytes);
-    } catch (const std::bad_alloc&) {
-        return fail(HSSFSST_ENOMEM, "bilstm_forward: out of host memory");
-    }
-    hssfsst::SegProjArgs pa{};
-    hssfsst::SegRecArgs ra{};
-    seg_dense_args(B, T, Bp, &pa, &ra);
-    return bilstm_forward<false>("bilstm_forward", p, st, x, h0, c0, y, hn, cn, stash, B, nullptr, pa, ra, chunks);
-}
-
-int hssfsst_bilstm_backward(hssfsst_bilstm* p, const float* stash, const float* c0, const float* dy, const float* dhn, const float* dcn,
-                            int64_t batch, int64_t steps, float* dgates, float* dh0, float* dc0, void* stream)
-{
-    if (!p) return fail(HSSFSST_EINVAL, "bilstm_backward: plan is NULL");
-    if (int rc = bilstm_check_shape("bilstm_backward", batch, steps)) return rc;
-    if (!stash || !c0 || !dy || !dgates || !dh0 || !dc0)
-        return fail(HSSFSST_EINVAL, "bilstm_backward: bad argument (%s is NULL)",
-                    !stash ? "stash" : !c0 ? "c0" : !dy ? "dy" : !dgates ? "dgates" : !dh0 ? "dh0" : "dc0");
-    if (!p->packed) return fail(HSSFSST_EINVAL, "bilstm_backward: no weights yet (call hssfsst_bilstm_set_weights first)");
-    DEVICE_SCOPE(p->device);
-    const hipStream_t st = static_cast<hipStream_t>(stream);
-    const int B = static_cast<int>(batch), T = static_cast<int>(steps);
-    const int nbt = (B + hssfsst::kSegRows - 1) / hssfsst::kSegRows, Bp = nbt * hssfsst::kSegRows;
-    if (int rc = seg_seed_state("bilstm_backward", st, p->d_state, dhn, dcn, B, p->H, Bp, nullptr)) return rc;
-    hssfsst::SegBwdArgs a = bilstm_bwd_args(p, stash, c0, dy, dgates, B, Bp);
-    a.T = T;
-    // at most kSegMaxChunk steps per launch, chained through the carried (dh_rec, dc)
-    for (int s0 = 0; s0 < T; s0 += hssfsst::seglayout::kSegMaxChunk) {
-        a.s0 = s0;
-        a.n = std::min(hssfsst::seglayout::kSegMaxChunk, T - s0);
-        hipLaunchKernelGGL(hssfsst::seg_bwd_rec_kernel<false>, dim3(static_cast<unsigned>(nbt), 2), dim3(64 * hssfsst::kSegWaves), 0, st, a);
-        if (int rc = launch_check("bilstm_backward", "seg_bwd_rec_kernel")) return rc;
-    }
-    return bilstm_state_out("bilstm_backward", st, p, dh0, dc0, B, Bp, nullptr);
-}
-
-int hssfsst_bilstm_stash_floats_ragged(const hssfsst_bilstm* p, const int64_t* offsets, int64_t count, int64_t* floats)
-{
-    if (!floats) return fail(HSSFSST_EINVAL, "bilstm_stash_floats_ragged: floats is NULL");
-    *floats = 0;
-    (void)p;                                             // (as hssfsst_bilstm_stash_floats: answered for a NULL plan too)
-    if (count < 0) return fail(HSSFSST_EINVAL, "bilstm_stash_floats_ragged: count %lld is negative", static_cast<long long>(count));
-    if (count == 0) return 0;
-    if (int rc = seg_check_list("bilstm_stash_floats_ragged", offsets, count)) return rc;
-    try {
-        hssfsst::seglayout::Layout lay;
-        hssfsst::seglayout::build(offsets, count, lay);
-        *floats = hssfsst::seglayout::stash_floats_ragged(lay);
-    } catch (const std::bad_alloc&) {
-        return fail(HSSFSST_ENOMEM, "bilstm_stash_floats_ragged: out of host memory");
-    }
-    return 0;
-}
-
-int hssfsst_bilstm_forward_ragged(hssfsst_bilstm* p, const float* x, const int64_t* offsets, int64_t count, const float* h0, const float* c0,
-                                  float* y, float* hn, float* cn, float* stash, void* stream)
-{
-    namespace seglayout = hssfsst::seglayout;
-    // the list first: what is wrong with it is said before the plan is looked at
-    if (count < 0) return fail(HSSFSST_EINVAL, "bilstm_forward_ragged: count %lld is negative", static_cast<long long>(count));
-    if (count == 0) return 0;
-    if (int rc = seg_check_list("bilstm_forward_ragged", offsets, count)) return rc;
-    if (!p) return fail(HSSFSST_EINVAL, "bilstm_forward_ragged: plan is NULL");
-    if (!x || !h0 || !c0 || !y || !hn || !cn || !stash)
-        return fail(HSSFSST_EINVAL, "bilstm_forward_ragged: bad argument (%s is NULL)",
-                    !x ? "x" : !h0 ? "h0" : !c0 ? "c0" : !y ? "y" : !hn ? "hn" : !cn ? "cn" : "stash");
-    if (!p->packed) return fail(HSSFSST_EINVAL, "bilstm_forward_ragged: no weights yet (call hssfsst_bilstm_set_weights first)");
-    DEVICE_SCOPE(p->device);
-    const hipStream_t st = static_cast<hipStream_t>(stream);
-    SegListTables::Views t{};
-    std::vector<seglayout::Chunk> chunks;
-    try {
-        if (int rc = p->list.acquire(offsets, count, st, &t)) return rc;
-        chunks = seglayout::ragged_chunks(p->list.lay, kSegTileStepBytes, seglayout::kSegPreBytes);
-    } catch (const std::bad_alloc&) {
-        return fail(HSSFSST_ENOMEM, "bilstm_forward_ragged: out of host memory");
-    }
-    hssfsst::SegProjArgs pa{};
-    hssfsst::SegRecArgs ra{};
-    seg_ragged_args(t, &pa, &ra);
-    return bilstm_forward<true>("bilstm_forward_ragged", p, st, x, h0, c0, y, hn, cn, stash, static_cast<int>(count), t.rec, pa, ra, chunks);
-}
-
-int hssfsst_bilstm_backward_ragged(hssfsst_bilstm* p, const float* stash, const float* c0, const float* dy, const float* dhn, const float* dcn,
-                                   const int64_t* offsets, int64_t count, float* dgates, float* dh0, float* dc0, void* stream)
-{
-    namespace seglayout = hssfsst::seglayout;
-    if (count < 0) return fail(HSSFSST_EINVAL, "bilstm_backward_ragged: count %lld is negative", static_cast<long long>(count));
-    if (count == 0) return 0;
-    if (int rc = seg_check_list("bilstm_backward_ragged", offsets, count)) return rc;
-    if (!p) return fail(HSSFSST_EINVAL, "bilstm_backward_ragged: plan is NULL");
-    if (!stash || !c0 || !dy || !dgates || !dh0 || !dc0)
-        return fail(HSSFSST_EINVAL, "bilstm_backward_ragged: bad argument (%s is NULL)",
-                    !stash ? "stash" : !c0 ? "c0" : !dy ? "dy" : !dgates ? "dgates" : !dh0 ? "dh0" : "dc0");
-    if (!p->packed) return fail(HSSFSST_EINVAL, "bilstm_backward_ragged: no weights yet (call hssfsst_bilstm_set_weights first)");
-    DEVICE_SCOPE(p->device);
-    const hipStream_t st = static_cast<hipStream_t>(stream);
-    SegListTables::Views t{};
-    std::vector<seglayout::BwdChunk> chunks;
-    try {
-        if (int rc = p->list.acquire(offsets, count, st, &t)) return rc;
-        chunks = seglayout::ragged_bwd_chunks(p->list.lay);
-    } catch (const std::bad_alloc&) {
-        return fail(HSSFSST_ENOMEM, "bilstm_backward_ragged: out of host memory");
-    }
-    const int B = static_cast<int>(count);
-    if (int rc = seg_seed_state("bilstm_backward_ragged", st, p->d_state, dhn, dcn, B, p->H, t.slots, t.rec)) return rc;
-    hssfsst::SegBwdArgs a = bilstm_bwd_args(p, stash, c0, dy, dgates, B, t.slots);
-    a.slot_off = t.off; a.slot_len = t.len; a.slot_rec = t.rec; a.tile_walk = t.walk; a.tile_base = t.base;
-    a.walked = t.walked; a.total = p->list.lay.total;
-    // highest steps first, at most kSegMaxChunk per launch, chained through the carried (dh_rec, dc); a tile joins at its last step
-    for (const seglayout::BwdChunk& c : chunks) {
-        a.s0 = c.s0;
-        a.n = c.n;
-        hipLaunchKernelGGL(hssfsst::seg_bwd_rec_kernel<true>, dim3(static_cast<unsigned>(c.tiles), 2), dim3(64 * hssfsst::kSegWaves), 0, st, a);
-        if (int rc = launch_check("bilstm_backward_ragged", "seg_bwd_rec_kernel<ragged>")) return rc;
-    }
-    return bilstm_state_out("bilstm_backward_ragged", st, p, dh0, dc0, B, t.slots, t.rec);
 }
 
 }  // extern "C"

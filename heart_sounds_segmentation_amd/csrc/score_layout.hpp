@@ -1,6 +1,6 @@
 // score_layout.hpp -- scoring a segmentation (hssfsst.h: hssfsst_score_states): the key transform, the digit of a sort pass, the
 // pass count, the block partition, the workspace and a sequential reference of the whole computation, as plain functions shared by
-// the kernels (segmenter_score.hpp), the entry (hssfsst.hip) and a CPU check (tests/native/score_layout_check.cpp).  No HIP call
+// the kernels (segmenter_score.hpp), the entry (sequence.hip) and a CPU check (tests/native/score_layout_check.cpp).  No HIP call
 // here.  score_reference() is the specification: the kernels give its integers.
 //
 // The quantities.  A step with a label 0..3 is COUNTED, any other label makes it IGNORED.  Its predicted state is states[t] where

@@ -1,6 +1,6 @@
 // sequence_args.hpp -- what the sequence-model entry points (hssfsst.h: hssfsst_decode_states .. hssfsst_posteriors_durations_counts)
 // decide about their arguments before any device work, as plain functions that return what they found: the wording and the error
-// code are the caller's (hssfsst.hip: seq_check_*).  No HIP type and no HIP call here, so all of it also compiles into a
+// code are the caller's (sequence.hip: seq_check_*).  No HIP type and no HIP call here, so all of it also compiles into a
 // stand-alone program (tests/native/sequence_args_check.cpp).  "Forbidden" is decode_layout.hpp's: a value that quantises to kNeg.
 #pragma once
 

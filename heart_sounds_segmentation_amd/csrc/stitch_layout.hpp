@@ -1,7 +1,7 @@
 // stitch_layout.hpp -- stitching overlapping windows' log-probs back into one sequence per recording (hssfsst.h:
 // hssfsst_stitch_windows): the covering window set, where a window's rows lie, the covering windows of a step, the arithmetic of
 // one step and a sequential reference of the whole call, as plain functions shared by the kernel (segmenter_stitch.hpp), the entry
-// (hssfsst.hip) and a CPU check (tests/native/stitch_layout_check.cpp).  No HIP call here.  stitch_reference() is the
+// (sequence.hip) and a CPU check (tests/native/stitch_layout_check.cpp).  No HIP call here.  stitch_reference() is the
 // specification: the kernel runs stitch_step() on the same rows in the same order.
 //
 // The window set.  A recording of T >= 1 steps, windows of n >= 1 steps, 1 <= stride <= n:

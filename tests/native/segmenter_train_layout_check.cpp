@@ -1,6 +1,6 @@
 // Stand-alone check of the trainable BiLSTM layer's index arithmetic (csrc/segmenter_layout.hpp: host only, no HIP), built with
 // -fsanitize=address,undefined by tests/test_segmenter_train.py.  The stash and the backward weight stream are in bounds and
-// one-to-one; the forward tables' index functions, which seg_upload_layer (csrc/hssfsst.hip) and seg_pack_kernel both walk, equal
+// one-to-one; the forward tables' index functions, which seg_upload_layer (csrc/segmenter.hip) and seg_pack_kernel both walk, equal
 // the nested loops that seg_upload_layer was before it called them, kept here as the independent statement of the layout.
 // Any failed property or sanitizer report ends the run non-zero.
 #include "segmenter_layout.hpp"

@@ -8,7 +8,7 @@ operands would still pass the 2e-5 gate (tests/test_segmenter_conditioned.py mea
                                                         still follows float64 (W_hh x 2 is contractive; x 2.5 is not any more);
   twin_layer / twin_forward                             the forward pass written out step by step in float64, the recurrent operands
                                                         exact, split f16 (hi + lo, as csrc/segmenter_lstm.hpp: seg_put_h and
-                                                        hssfsst.hip: seg_upload_layer round them) or single f16 (the lo halves lost);
+                                                        segmenter.hip: seg_upload_layer round them) or single f16 (the lo halves lost);
   features / large_state                                inputs: randn, randn with +-300 spikes, randn x 30; states up to +-63;
   dense_case / ragged_case                              the cases of the tests with their float64 and float32 CPU results, each
                                                         computed once and never changed;

@@ -246,6 +246,39 @@ def test_shipped_code_object_keeps_the_fixed_registers(built_lib):
     assert out["kernels"] >= 2 and out["metadata_checked"] >= 2 and out["accessor_instructions"] >= 100, out
 
 
+def test_translation_units():
+    """The library's units (csrc/*.hip) are the ones _lib.SOURCES builds, and every header that holds a kernel is reached -- by the
+    ``#include "..."`` lines, followed through the headers -- from exactly ONE of them: a kernel in two units is defined twice (a
+    template: compiled twice, and whichever copy the loader registers last wins).  host_common.hpp, which every unit includes, holds
+    no kernel.  Compiles nothing."""
+    import os
+    import re
+    from heart_sounds_segmentation_amd import _lib
+    csrc = os.path.join(os.path.dirname(_lib.__file__), "csrc")
+    units = sorted(f for f in os.listdir(csrc) if f.endswith(".hip"))
+    assert units == sorted(os.path.basename(s) for s in _lib.SOURCES)
+    assert all(os.path.dirname(s) == csrc for s in _lib.SOURCES) and len(set(_lib.SOURCES)) == len(_lib.SOURCES)
+
+    def text(name):
+        with open(os.path.join(csrc, name)) as fh:
+            return fh.read()
+
+    def reached(name, seen):
+        for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', text(name), re.M):
+            inc = os.path.normpath(inc)
+            if os.path.exists(os.path.join(csrc, inc)) and inc not in seen:     # (../../include/hssfsst.h: not under csrc/)
+                seen.add(inc)
+                reached(inc, seen)
+        return seen
+
+    by_unit = {u: reached(u, set()) for u in units}
+    assert "__global__" not in text("host_common.hpp")
+    for h in sorted(f for f in os.listdir(csrc) if f.endswith((".hpp", ".h"))):
+        if "__global__" in text(h):
+            users = [u for u in units if h in by_unit[u]]
+            assert len(users) == 1, f"{h} holds a kernel and is reached from {users or 'no unit'}"
+
+
 def test_lent_buffer_goes_back_when_the_last_view_dies():
     """The drop-in call's result is a tensor over a pinned pool buffer the library LENT (hssfsst_exec_pinned): the ctypes array the tensor is made of
     hands the buffer back from its ``__del__`` -- once, with the buffer's address, and only when the last view of the result is gone."""
