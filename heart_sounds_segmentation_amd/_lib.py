@@ -13,8 +13,11 @@ import threading
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG, "libhssfsst.so")
-# the library's translation units, one per subsystem (each kernel header is included by exactly one of them)
-SOURCES = [os.path.join(_PKG, "csrc", f) for f in ("hssfsst.hip", "resample.hip", "segmenter.hip", "sequence.hip", "host_io.hip")]
+# the library's translation units: the FSST plan and its routing, one unit per FSST kernel family (the MFMA core in four, by transform
+# length: the longest compiles first), and one per other subsystem.  No kernel is compiled into two of them (kernel_units)
+SOURCES = [os.path.join(_PKG, "csrc", f) for f in (
+    "fsst_core128_n512.hip", "fsst_core128_n512_pairs.hip", "fsst_core128_n256.hip", "fsst_generic.hip", "fsst_team.hip",
+    "fsst_core128_n128.hip", "hssfsst.hip", "resample.hip", "segmenter.hip", "sequence.hip", "host_io.hip")]
 BUILD_DIR = os.path.join(_PKG, "build")
 HEADER = os.path.join(os.path.dirname(_PKG), "include", "hssfsst.h")
 
@@ -75,14 +78,32 @@ def guard_fork() -> None:
     hip_owner_pid = pid
 
 
+def include_closure(unit: str) -> set:
+    """The files of csrc/ that the unit (or header) ``unit`` reaches through its ``#include "..."`` lines, followed through the
+    headers: names relative to csrc/, the unit itself not among them.  (../../include/hssfsst.h lies outside csrc/ and is not
+    listed: every unit depends on it.)"""
+    import re
+    csrc = os.path.join(_PKG, "csrc")
+    seen, todo = set(), [os.path.basename(unit)]
+    while todo:
+        with open(os.path.join(csrc, todo.pop())) as fh:
+            for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', fh.read(), re.M):
+                inc = os.path.normpath(inc)
+                if inc not in seen and os.path.exists(os.path.join(csrc, inc)):
+                    seen.add(inc)
+                    todo.append(inc)
+    return seen
+
+
 def build(force: bool = False, verbose: bool = False) -> str:
     """Compile the units of SOURCES for gfx950, each into an object under build/, and link them into libhssfsst.so (cross-compiles
-    without a GPU).  An object is rebuilt when it is older than its own unit, any header of csrc/ or the C header; the units that
-    need it compile concurrently.  A failed unit raises after the others have finished, and nothing is linked.  A library that is
-    newer than every unit and header is current whether or not the objects are there (a copy of the tree without build/)."""
+    without a GPU).  An object is rebuilt when it is older than its own unit, a header of csrc/ that the unit reaches
+    (include_closure) or the C header; the units that need it compile concurrently.  A failed unit raises after the others have
+    finished, and nothing is linked.  A library that is newer than every unit and every header they reach is current whether or not
+    the objects are there (a copy of the tree without build/)."""
     from concurrent.futures import ThreadPoolExecutor
     csrc = os.path.dirname(SOURCES[0])
-    headers = sorted(os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".hpp", ".h"))) + [HEADER]
+    deps = {src: [src, HEADER] + sorted(os.path.join(csrc, h) for h in include_closure(src)) for src in SOURCES}
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
     def older(target: str, deps) -> bool:
@@ -95,10 +116,10 @@ def build(force: bool = False, verbose: bool = False) -> str:
         if res.returncode != 0:
             raise RuntimeError(f"hipcc failed ({res.returncode}): {' '.join(cmd)}\n{res.stdout}")
 
-    if not force and not older(LIB_PATH, SOURCES + headers):
+    if not force and not older(LIB_PATH, [d for src in SOURCES for d in deps[src]]):
         return LIB_PATH
     objects = [os.path.join(BUILD_DIR, os.path.splitext(os.path.basename(src))[0] + ".o") for src in SOURCES]
-    stale = [(src, obj) for src, obj in zip(SOURCES, objects) if force or older(obj, [src] + headers)]
+    stale = [(src, obj) for src, obj in zip(SOURCES, objects) if force or older(obj, deps[src])]
     if stale:
         os.makedirs(BUILD_DIR, exist_ok=True)
         jobs = min([len(SOURCES), 16] + ([max(int(os.environ["MAX_JOBS"]), 1)] if os.environ.get("MAX_JOBS", "").isdigit() else []))
@@ -165,7 +186,25 @@ def kernel_resources(match: str, path: str = None) -> dict:
         name = re.search(r"\.name:\s+(\S+)", blk)
         if not name or match not in name.group(1):
             continue
+        if name.group(1) in out:                          # (compiled into two code objects: the loader registers both, the last one wins)
+            raise RuntimeError(f"kernel_resources: {name.group(1)} is defined in two code objects")
         out[name.group(1)] = {f: int(re.search(r"\." + f + r":\s+(\d+)", blk).group(1)) for f in fields}
+    return out
+
+
+def kernel_units(path: str = None) -> dict:
+    """Where the SHIPPED library's kernels are defined: {kernel symbol: [index of each code object -- one per translation unit that
+    holds kernels -- whose metadata names it]}.  A kernel in two code objects was compiled twice (a template instantiated from two
+    units); the loader registers both and the last one wins.  RuntimeError without the llvm tools."""
+    import re
+    import tempfile
+    tools = _llvm_tools("clang-offload-bundler", "llvm-readelf")
+    out = {}
+    with tempfile.TemporaryDirectory() as td:
+        for k, obj in enumerate(_unbundle(tools, path or LIB_PATH, td)):
+            notes = subprocess.run([tools["llvm-readelf"], "--notes", obj], check=True, capture_output=True, text=True).stdout
+            for name in re.findall(r"^\s*\.name:\s+(\S+)\s*$\n\s*\.private_segment_fixed_size:", notes, re.M):
+                out.setdefault(name, []).append(k)
     return out
 
 

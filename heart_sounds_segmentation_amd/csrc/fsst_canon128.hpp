@@ -20,7 +20,7 @@
 //    margin): a source that moves without reaching the band changes nothing, which for the canonical band takes the
 //    upper half of the spectrum out of the rare path altogether.
 #pragma once
-#include "fsst_mfma128.hpp"
+#include "fsst_mfma128_device.hpp"
 
 namespace hssfsst {
 
@@ -116,13 +116,7 @@ struct CanonTile {
 // for signals shorter than a window: ones = left + right - interior).  32 packed multiply-adds per lane and group, for such
 // tiles only, in one block between the spectra and the source stage.  (The mean's FOLD as the matrix instructions' C operand was tried first: its taps are as large as the offset,
 // they cancel only in the 16-point spectra -- in float32, at the offset's scale: 2.5e-4 on pcg + 100.)
-constexpr int kCanonYcGroup = 33;                         // float2 per lane group: za[0..15] | zb[0..15] | pad (the four lane groups of a wave read 264 bytes apart: different LDS banks)
-constexpr int kCanonYcFrame = 4 * kCanonYcGroup * 2;      // floats per frame: [lane group][za[0..15] | zb[0..15] | -] as float2 (the lane's two 16-point spectra)
-constexpr int kCanonYcRight = 80;                         // right-edge frames tabulated: 0..62 samples to the end, then 17 copies of the interior (a group of 16 frames that
-                                                          // reaches into the last 63 columns reads one table whatever its first frame)
-// interior [lane group][33] | left edge [lane group][entry][output column 0..63] | right edge [lane group][entry][samples to the end 0..79], float2 each:
-// the 16 lanes of a lane group (consecutive frames) read consecutive words of the edge tables
-constexpr int kCanonZcFloats = kCanonYcFrame + 4 * 32 * 64 * 2 + 4 * 32 * kCanonYcRight * 2;
+// (kCanonYcGroup, kCanonYcFrame, kCanonYcRight, kCanonZcFloats -- the table's layout, which the host builds: fsst_launch_shape.hpp)
 constexpr float kMeanTheta = 0.5f;                       // the mean is taken out when S1^2 >= kMeanTheta n E
 
 // Stores the tile's 191 samples (three per lane, sreg[k] = sample lane + 64 k of the aligned tile that starts at output column
@@ -511,7 +505,7 @@ __device__ __forceinline__ void canon_group(const u2* xrec, const float* atab, f
         HSS_RARE_VMEM_DONE();
     }
 }
-// Statistics partial of the group in the own plane (see "Statistics" in fsst_kernels.hpp): pivoted sums over the kept cells
+// Statistics partial of the group in the own plane (see "Statistics" in fsst_device.hpp): pivoted sums over the kept cells
 // of the nvalid valid frames, computed on the SCALED plane values and scaled back afterwards -- a power of two, so the
 // result is the one the unscaled cells would give.  Returns piece_sums' w (row q of the wave: S1re / S2re / S1im / S2im)
 // and the pivot, both in feature units.
@@ -523,7 +517,7 @@ __device__ __forceinline__ float canon_stats(const f2* own_base, int nvalid, flo
     //  compare and two selects, with it only the one row group that is partial across lanes)
     const int g = (lane_o >> 4) & 3, j = lane_o & 15;
     const f2* src = own_base + j * C::LD + C::KOFF + g;
-    // (pivot: median of frame 0's first, middle and last kept row -- pivot_med3, fsst_kernels.hpp; three broadcast reads)
+    // (pivot: median of frame 0's first, middle and last kept row -- pivot_med3, fsst_device.hpp; three broadcast reads)
     const f2 pv0 = own_base[C::KOFF], pv1 = own_base[C::KOFF + KC / 2], pv2 = own_base[C::KOFF + KC - 1];
     const f2 piv = f2{pivot_med3(pv0.x, pv1.x, pv2.x), pivot_med3(pv0.y, pv1.y, pv2.y)};
     constexpr int NU = (KC + 3) / 4, UF = KC / 4;        // rows g + 4 u: u < UF valid in every lane group, u == UF for g < KC - 4 UF

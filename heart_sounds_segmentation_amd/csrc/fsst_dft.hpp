@@ -18,8 +18,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "fsst_kernels.hpp"
-#include "fsst_mfma128.hpp"
+#include "fsst_mfma128_device.hpp"
 
 namespace hssfsst {
 
@@ -216,7 +215,7 @@ __global__ __launch_bounds__(512) void fsst_dft_kernel(DftParams p)
             float mxc = 0.0f;
             for (int i = lane; i < F * LDP; i += 64) { const f2 v = plane[i]; mxc = fmaxf(mxc, fmaf(v.x, v.x, v.y * v.y)); }
             const bool quiet = __builtin_amdgcn_ballot_w64(mxc > kExactTheta2 * R2) == 0ull && R2 > 0.0f;
-            if (quiet || (te.dcdom && R2 > 0.0f) || q_all > kDftTieQueue) {      // (te.dcdom: an offset with little on top, fsst_kernels.hpp)
+            if (quiet || (te.dcdom && R2 > 0.0f) || q_all > kDftTieQueue) {      // (te.dcdom: an offset with little on top, fsst_device.hpp)
                 wave_sync();
                 for (int i = lane; i < F * LDP; i += 64) plane[i] = f2{0.0f, 0.0f};
                 wave_sync();

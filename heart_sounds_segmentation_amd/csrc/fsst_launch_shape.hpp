@@ -14,7 +14,7 @@ namespace hssfsst {
 
 constexpr int kMaxLdsBytes = 160 * 1024;        // LDS of a CU: what a block may ask for (allow_full_lds of host_common.hpp raises a kernel's limit to it)
 constexpr int kFpw128 = 64;                  // frames per wave tile of the MFMA kernels
-constexpr int kPartFloats = 8;               // a statistics partial (fsst_kernels.hpp "Statistics")
+constexpr int kPartFloats = 8;               // a statistics partial (fsst_device.hpp "Statistics")
 
 // ---- Chunk pattern ------------------------------------------------------------------------------------------------------
 // Work distribution: one persistent block of 16 waves per CU.  The launch is cut into CHUNKS of consecutive 16-frame
@@ -68,6 +68,7 @@ inline Core128Regions core128_regions(int ngroups, long long nsig = -1)
 }
 constexpr int core128_chunks_per_signal(const Core128Regions& r) { return r.npc[0] + r.npc[1] + r.npc[2]; }
 
+constexpr long long kRaggedUnitFloats = 1 << 16;       // floats of a ragged exec's z-score unit, fsst_ragged.hpp (256 kB: 64 float4 per thread)
 constexpr int kRaggedGroupBits = 24;         // groups of a signal below 2^24 (n < 2^28: the host allows n * 2 nf < 2^31)
 struct alignas(8) RaggedChunk {              // the kernels read it as int2 (hssfsst.hip asserts size and alignment)
     int sig;                                 // signal
@@ -111,6 +112,24 @@ constexpr int own_ld(int klo, int K, int rq = 8)
 }
 // MFMA A-operand constants: [pass][nt taps][k-step][64 lanes] floats, rq / 8 passes of rq / 4 k-steps
 constexpr int core128_atab_floats(int rq = 8, int nt = 16) { return (rq / 8) * nt * (rq / 4) * 64; }
+// the float64 fold constants of an "exact group" (resolve_group_f64, fsst_mfma128.hpp): [pass][tap][k-step][lane]
+constexpr int fold64_doubles(int rq, int nt) { return (rq / 8) * nt * (rq / 4) * 64; }
+// FAST epilogue: byte offsets, inside a wave's own plane, of the two (re,re) / (im,im) pairs that make up
+// float4 number f = lane + 64 i of a 16-frame group's contiguous [16][2K] output image (K even, K <= 24).
+// tab[i][lane] = first pair, tab[3 + i][lane] = second pair; a pair's second element is 8 bytes further.
+inline void core128_store_offsets(int klo, int K, int* tab /* [6][64] */, int rq = 8)
+{
+    const int Q = (K >> 1) > 0 ? (K >> 1) : 1;
+    const int old = own_ld(klo, K, rq), koff0 = klo - rq * own_s0(klo, rq);
+    for (int i = 0; i < 3; ++i)
+        for (int lane = 0; lane < 64; ++lane) {
+            const int f = lane + 64 * i;
+            const int jj = (f / Q < 15) ? f / Q : 15, c = 4 * (f - (f / Q) * Q);
+            const int rowb = jj * old + koff0;
+            tab[i * 64 + lane] = (c < K) ? (rowb + c) * 8 : (rowb + c - K) * 8 + 4;
+            tab[(3 + i) * 64 + lane] = (c + 2 < K) ? (rowb + c + 2) * 8 : (rowb + c + 2 - K) * 8 + 4;
+        }
+}
 constexpr int kCtlFloats = 16 + 192;         // block control words in LDS: [0] work counter, [16..207] the wide-store offset
                                              // table (3 words per lane: held in registers it costs the 16-wave kernels a spill)
 // FUSED kernel: [0] ticket counter, [1..2] groups delivered per signal slot (monotone), [3] a wait gave up, [4..7] epoch
@@ -146,6 +165,14 @@ constexpr int dft_wave_lds_floats(int nk4, int K, int G = 1)
 constexpr int kCanonOpFloats = 16 * 64 * 4;              // f16 A operand: [16 taps][64 lanes][8 halves] = 16 kB
 constexpr int kCanonAtabFloats = kCanonOpFloats + 4 * 128;   // + {cos, sin}(2 pi m / 128) as float64 (rounding-tie path), 2 kB
 constexpr int kCanonLdsTabFloats = kCanonAtabFloats + 4 * 33 * 2;   // what the kernels keep in LDS: + the interior frame of the offset table ("Offsets"), 1 kB
+// the offset table behind the operand table (fsst_canon128.hpp "Offsets"; built by fsst_tables.hpp canon_offset_spectra)
+constexpr int kCanonYcGroup = 33;                         // float2 per lane group: za[0..15] | zb[0..15] | pad (the four lane groups of a wave read 264 bytes apart: different LDS banks)
+constexpr int kCanonYcFrame = 4 * kCanonYcGroup * 2;      // floats per frame: [lane group][za[0..15] | zb[0..15] | -] as float2 (the lane's two 16-point spectra)
+constexpr int kCanonYcRight = 80;                         // right-edge frames tabulated: 0..62 samples to the end, then 17 copies of the interior (a group of 16 frames that
+                                                          // reaches into the last 63 columns reads one table whatever its first frame)
+// interior [lane group][33] | left edge [lane group][entry][output column 0..63] | right edge [lane group][entry][samples to the end 0..79], float2 each:
+// the 16 lanes of a lane group (consecutive frames) read consecutive words of the edge tables
+constexpr int kCanonZcFloats = kCanonYcFrame + 4 * 32 * 64 * 2 + 4 * 32 * kCanonYcRight * 2;
 constexpr size_t canon_lds_bytes(int ctl_floats, int wave_floats, int wpb = 16)
 {
     return (kCanonLdsTabFloats + ctl_floats + static_cast<size_t>(wpb) * wave_floats) * sizeof(float);

@@ -6,12 +6,11 @@
 // results are bit-identical to a single exec of each signal, whichever path that takes.
 #pragma once
 
-#include "fsst_kernels.hpp"
-#include "fsst_mfma128.hpp"
+#include "fsst_mfma128_device.hpp"
 
 namespace hssfsst {
 
-constexpr long long kRaggedUnitFloats = 1 << 16;       // floats of a z-score unit (256 kB: 64 float4 per thread)
+// (kRaggedUnitFloats, the floats of a z-score unit: fsst_launch_shape.hpp -- the host cuts the list into units with it)
 
 // stats[s] = {mean_re, 1/std_re, mean_im, 1/std_im} of signal s; one wave per signal
 __global__ __launch_bounds__(64) void fsst_ragged_stats_kernel(const float* partials, const RaggedSignal* sig, float4* stats, int K)

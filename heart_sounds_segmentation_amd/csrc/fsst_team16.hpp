@@ -22,7 +22,7 @@
 //     write-back);
 //   * the rest of the statistics runs ONCE per signal and CU: the first wave of a CU that cannot go on without a signal's
 //     statistics claims it (LDS), fetches the signal's <= 32 block sums from the mailbox -- two per lane, straight into the lane
-//     that adds them -- and finishes as stats_from_blocks() does (fsst_kernels.hpp: the same instructions on the same numbers as
+//     that adds them -- and finishes as stats_from_blocks() does (fsst_device.hpp: the same instructions on the same numbers as
 //     the two-launch path), leaving {mean, 1/std} x 2 in LDS for its 15 siblings.
 // What limits it (profiles/r04_team_occupancy.txt, profiles/r05_team_diet.txt): instruction issue -- 527 vector + 16 matrix
 // instructions per group on a SIMD that four waves share, a third of a wave's cycles spent waiting for an issue slot -- and, for
@@ -58,7 +58,6 @@
 // same bits, no error (hssfsst_plan_fallbacks counts).  A plan is single-stream: two launches of one plan on different
 // streams interleave their arrivals; a block that finds its identity outside the grid gives the launch up.
 #pragma once
-#include "fsst_mfma128.hpp"
 #include "fsst_canon128.hpp"
 
 namespace hssfsst {

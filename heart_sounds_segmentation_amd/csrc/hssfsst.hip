@@ -1,203 +1,23 @@
-// hssfsst.hip -- the FSST unit of libhssfsst.so's host side: the plan and everything that takes one (C ABI: include/hssfsst.h).
-// Plan creation does, once and in fp64, everything of the reference's `ssq.fsst(x, fs, window)`
+// hssfsst.hip -- the FSST unit of libhssfsst.so's host side: the plan (fsst_plan.hpp) and every entry point that takes one (C ABI:
+// include/hssfsst.h).  Plan creation does, once and in fp64, everything of the reference's `ssq.fsst(x, fs, window)`
 // (call site /root/reference/hss/transforms/synchrosqueeze.py:48) that depends only on
-// (fs, window); exec launches the gfx950 kernels of fsst_kernels.hpp.
+// (fs, window); exec routes to the launchers of the gfx950 kernels, which live in the kernel families' own units -- fsst_team.hip,
+// fsst_core128_n128.hip / _n256.hip / _n512.hip / _n512_pairs.hip, fsst_generic.hip -- so no kernel is compiled here.
 // There is no CPU compute path here by design (the CPU restatement is oracle/, test-only).
-// The other units: resample.hip, segmenter.hip, sequence.hip, host_io.hip; what they share: host_common.hpp.
-#include "host_common.hpp"
+// The other units: resample.hip, segmenter.hip, sequence.hip, host_io.hip; what all share: host_common.hpp.
+#include "fsst_plan.hpp"
 
-#include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstring>
-#include <mutex>
-#include <cstdlib>
-#include <array>
-#include <atomic>
 #include <memory>
-#include <type_traits>
-#include <utility>
 
-#include "fsst_kernels.hpp"
-#include "fsst_mfma128.hpp"
-#include "fsst_canon128.hpp"
-#include "fsst_team16.hpp"
-#include "fsst_dft.hpp"
-#include "fsst_gather.hpp"
-#include "fsst_ragged.hpp"
-#include "fsst_half.hpp"
 #include "fsst_tables.hpp"
 
 namespace tables = hssfsst::tables;
 using namespace hssfsst::host;
 
 namespace {
-
-// A-B and test switches, read ONCE per process (first use) from the environment, one variable per key: HSSFSST_<KEY in capitals>
-// is on when set to an empty string, a non-zero number or a word that starts with y or t (HSSFSST_FORCE_GENERIC: a value that
-// starts with 1).  Defaults are the measured best; no switch changes a result (every path gives the same bits, which is what most
-// of them exist to show).  Nothing else in the library reads the environment, but for the segmenter's one switch, read the same
-// way in segmenter.hip (seg_ragged_pre_mib).
-struct DebugSwitches {
-    bool no_fused = false;        // z-score always as a second kernel
-    bool no_canon = false;        // the canonical band on the general kernels (fsst_mfma128.hpp)
-    bool no_team = false;         // never the team kernel
-    bool team_only = false;       // the team kernel or two launches, never one CU per signal
-    bool team_force_fallback = false;   // every team launch finds itself given up (tests of the gated fallback)
-    bool force_dft = false;       // every window length on the any-length kernel
-    bool force_generic = false;   // every radix length on the generic VALU kernel
-    bool no_stream_fuse = false;  // a streaming step as copy + transform + merge-and-normalise launches
-    bool no_pair = false;         // nwin 256 / 512: one wave per wave region (no wave pairs)
-};
-const DebugSwitches& debug_switches()
-{
-    static const DebugSwitches sw = [] {
-        auto on = [](const char* name) {
-            const char* v = std::getenv(name);
-            return v != nullptr && (v[0] == '\0' || std::atoi(v) != 0 || v[0] == 'y' || v[0] == 't');
-        };
-        DebugSwitches d;
-        d.no_fused = on("HSSFSST_NO_FUSED");
-        d.no_canon = on("HSSFSST_NO_CANON");
-        d.no_team = on("HSSFSST_NO_TEAM");
-        d.team_only = on("HSSFSST_TEAM_ONLY");
-        d.team_force_fallback = on("HSSFSST_TEAM_FORCE_FALLBACK");
-        d.force_dft = on("HSSFSST_FORCE_DFT");
-        const char* fg = std::getenv("HSSFSST_FORCE_GENERIC");
-        d.force_generic = fg != nullptr && fg[0] == '1';
-        d.no_stream_fuse = on("HSSFSST_NO_STREAM_FUSE");
-        d.no_pair = on("HSSFSST_NO_PAIR");
-        return d;
-    }();
-    return sw;
-}
-
-constexpr int kTile = 64;
-using hssfsst::kFpw128;
-
-constexpr size_t kPinPoolMax = 64;                       // hssfsst_exec_pinned: buffers lent at a time (hssfsst.h)
-
-// The kernels a plan runs (choose_family): generic VALU (nwin 32 / 64, and the fallback of 128 / 256 / 512), any-length, MFMA
-enum class Family { Generic, Dft, Mfma };
-
-}  // namespace
-
-struct hssfsst_plan {
-    int device = -1;
-    int nwin = 0, R = 0, nf = 0, klo = 0, K = 0, mode = 0;
-    int out_dtype = HSSFSST_DTYPE_F32;                       // HSSFSST_DTYPE_F32, or F16 / BF16 (STACK only): element type of every exec's `out`
-    size_t out_es = sizeof(float);                           // ... its size in bytes
-    DevBuf<float> d_f32;                                     // half plans: float32 features of the paths whose z-score is a second sweep
-    DevBuf<float> d_ctab;         // generic kernel: class-folded scalar tables
-    DevBuf<float> d_dtab;         // any-length kernel (fsst_dft.hpp): A operand [source block][k-step][64 lanes]
-    Family family = Family::Generic;
-    float r2scale = 0.0f;         // 4 nwin max |(w + i dw') / 2|^2: error-bound scale of the rounding-tie path
-    DevBuf<double> d_wtab;        // float64 {w, dw' in bin units}[nwin], then {cos, sin}(2 pi m / nwin)[nwin]: rounding-tie path
-    DevBuf<float> d_atab;         // nwin == 128 / 256 / 512: MFMA A-operand constants [pass][taps][64 lanes][k-step]
-    DevBuf<float> d_atab16;       // canonical-band kernels (fsst_canon128.hpp): f16 split A operand [16 taps][64 lanes][8 halves]
-    float canon_inv_c = 0.0f;     // ... 1 / (power-of-two scale of those constants)
-    float canon_r2s = 0.0f;       // ... r2scale x scale^2
-    int canon_slots = 0;          // resident blocks of fsst_canon_kernel<.., false> (0 = not queried yet)
-    // what follows from the fields above, stated once at creation (choose_family, set_derived_facts):
-    hssfsst::MfmaFacts mf;        // nt, rq, fast, stripes03 and the LDS bytes (fsst_launch_shape.hpp; rq = 0 unless Family::Mfma)
-    int plain_row = -1;           // MFMA plans: the row of kCore128Plain that the two-launch path runs, dense and ragged (-1: none fits)
-    int canon_idx = -1;           // index of the band in kCanonBands when the canonical-band kernels apply, else -1
-    DevBuf<float> d_partials;                                // kPartFloats per statistics piece
-    unsigned* d_status = nullptr;                            // fused z-score: status word (0 = ok) as the device sees it ...
-    volatile unsigned* h_status = nullptr;                   // ... and the same word in pinned host memory: read without a sync
-    DevBuf<unsigned long long> d_mail;                       // team kernel: mailboxes [teams][slots][32 blocks][8] (8-byte words)
-    unsigned team_seq = 0;                                   // launch sequence number (upper half of the mailbox tags)
-    DevBuf<unsigned> d_arrive; unsigned arrive_total = 0;    // team kernel: [0] arrival counter (and its value after the launches so far), [1] abort word, [2] blocks done
-    unsigned done_total = 0;                                 // ... [2]'s value after the flagged launches so far
-    unsigned team_launch = 0;                                // identity of the last team launch (never 0)
-    volatile unsigned* h_fallback = nullptr; unsigned* d_fallback = nullptr;   // pinned host word: identity of the last team launch that gave up
-    unsigned seen_fallback = 0; int fallbacks = 0;           // ... as last seen by the host, and how many distinct ones
-    int giveups_in_a_row = 0, team_pause = 0;                // a GPU shared with many processes: after kTeamGiveUps give-ups in a row the team kernel sits out
-                                                             // the plan's next kTeamPause execs that would take it (each give-up costs its 0.5 ms bound first)
-    int team16_cus = 0;                                      // CUs usable by the team kernel (fsst_team16.hpp; 0 = not queried yet, -1 = none)
-    char last_kernel[112] = "";                              // the transform kernel of the last exec: instantiation, waves per block, grid (hssfsst_plan_last_kernel)
-    int last_fused = 0;                                      // the last exec ran a single-launch z-score kernel
-    int zpath_pref = 0;                                      // HSSFSST_ZPATH_*: preference among the z-score paths
-    int last_zpath = 0;                                      // ... which one: 1 = one CU per signal, 2 = team kernel
-    int core128_slots = 0;                    // resident blocks of the core kernel on this device (0 = not queried yet)
-    int ragged_slots = 0;                     // the same for its ragged instantiation
-    int stream_slots = 0;                     // the same for the streaming-step kernel
-    DevBuf<unsigned> d_stream_arrive;         // streaming step: blocks delivered per channel
-    DevBuf<double> d_stream_pieces;           // and the groups' float64 sums [channels][groups][4]
-    int fused_slots = 0;                      // CUs usable by the fused kernel (0 = not queried yet, -1 = none)
-    DevBuf<float> d_stats;                                   // 4 per signal
-    DevBuf<float> d_xstage, d_ostage;                        // a host input / output, staged
-    // small host-to-host execs (the unchanged dataset loop: one 2000-sample frame per call): pinned, device-mapped staging that the
-    // kernels read and write in place
-    PinnedBuf<float> xpin, opin;
-    struct PoolBuf { PinnedBuf<float> buf; bool used = false; };
-    std::array<PoolBuf, kPinPoolMax> pin_pool;              // hssfsst_exec_pinned: pinned, device-mapped result buffers lent to the caller
-    std::mutex pin_mu;                                       // ... guards `used` and the buffers' replacement (hssfsst_pinned_release may
-                                                             // come from another host thread)
-    DevBuf<long long> d_starts;                              // frame-list staging (hssfsst_exec_list with host starts)
-    DevBuf<float> d_frames;                                  // frames gathered from a list, dense [batch][n]
-    // hssfsst_exec_ragged: the list's tables -- RaggedSignal[batch], z-score unit starts int[batch + 1], chunk list int2[] -- in one
-    // block, kept while the next list has the same lengths and offsets; where they lie in it and how many they are
-    UploadedTable rtab{"exec_ragged"};
-    struct RaggedTabs {
-        size_t unit = 0, chunk = 0, bytes = 0;               // byte offsets of the unit starts and of the chunk list, and the block's size
-        long long nchunks = 0, nunits = 0;
-    } rtabs;                                                 // (of rtab's key: written behind its commit)
-    int timing_every = 0;         // hssfsst_plan_set_timing(n): every n-th exec is timed (0: off)
-    unsigned timing_seq = 0;
-    std::vector<hipEvent_t> ev;   // per timed exec: (before, after) per core launch + one closing event
-    size_t ev_used = 0;           // events used since timing was enabled
-    std::vector<int> ev_chunks;   // core launches of each timed exec
-};
-
-namespace {
-
-using hssfsst::kMaxLdsBytes;
-
-// Resident blocks of `kern` (threads per block, dynamic LDS) on the plan's device, asked once and kept in `cache` (0 = not asked
-// yet; launchers that share a cache share the first answer).  whole_cus: one block per CU -- the CU count, or -1 when the kernel
-// does not fit; otherwise blocks per CU x CUs, each factor at least 1.
-template <class Kern>
-int resident_blocks(const hssfsst_plan* pl, int& cache, Kern kern, int threads, size_t lds, bool whole_cus)
-{
-    if (cache != 0) return 0;
-    int per_cu = 0, cus = 0;
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kern), threads, lds));
-    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, pl->device));
-    cache = whole_cus ? ((per_cu >= 1 && cus >= 1) ? cus : -1) : std::max(per_cu, 1) * std::max(cus, 1);
-    return 0;
-}
-
-// One exec's launch state: made on the stack by exec_impl / hssfsst_exec_ragged and handed to the launchers.  Nothing of it
-// outlives the exec; what the C ABI reports afterwards goes to the plan in one place (exec_report).
-struct ExecCtx {
-    hipStream_t st = nullptr;
-    // in
-    int zpref = HSSFSST_ZPATH_AUTO;           // the z-score path preference this exec runs under (the plan's; ONE_CU for a redo)
-    bool host_waits = false;                  // this exec synchronises before it returns: no gated launches behind a team launch, the host
-                                              // looks at the pinned give-up word afterwards and redoes the exec itself
-    bool want_done_word = false;              // the team launch is asked to say in pinned host memory (h_fallback[2]) when its last wave is done
-    // set by launch_core128 behind a team launch: the kernels that follow it in the same exec are its gated fallback
-    const unsigned* gate = nullptr; unsigned gate_val = 0;
-    // out
-    unsigned team_launch = 0;                 // identity of this exec's team launch (at most one), or 0
-    unsigned flagged_launch = 0;              // ... when it was asked for its done word, else 0
-    bool fused = false;                       // the z-score was part of the launches so far (no statistics + z-score launches to add)
-    int zpath = 0;                            // ... by which path: 1 = one CU per signal, 2 = team kernel
-    char kernel[sizeof(hssfsst_plan::last_kernel)] = "";     // the transform kernel: instantiation, waves per block, grid
-    bool timing = false;                      // this exec records kernel events
-    bool timing_closed = false;               // ... and has recorded its closing kernel event already (team path: right behind the team kernel)
-};
-
-// which kernel instantiation the exec that is being queued runs (hssfsst_plan_last_kernel: the dispatch made observable)
-void name_kernel(char (&name)[sizeof(hssfsst_plan::last_kernel)], int waves, long long grid, const char* fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    const int k = vsnprintf(name, sizeof(name), fmt, ap);
-    va_end(ap);
-    if (k > 0 && static_cast<size_t>(k) < sizeof(name))
-        snprintf(name + k, sizeof(name) - static_cast<size_t>(k), " [%d waves/block, grid %lld]", waves, grid);
-}
 
 void exec_report(hssfsst_plan* p, const ExecCtx& cx)
 {
@@ -207,334 +27,6 @@ void exec_report(hssfsst_plan* p, const ExecCtx& cx)
 }
 
 int out_floats_per_sample(const hssfsst_plan* p) { return p->mode == HSSFSST_MODE_ABS ? p->K : 2 * p->K; }
-
-template <int R>
-int launch_core(hssfsst_plan* pl, ExecCtx& cx, hssfsst::CoreParams cp, long long nblocks)
-{
-    constexpr int NWIN = 32 * R;
-    constexpr int XS = ((kTile + NWIN - 1 + 3) / 4) * 4;
-    size_t lds = (static_cast<size_t>(XS) + static_cast<size_t>(4 * pl->K) * (kTile + 1)) * sizeof(float);
-    cp.oneplane = 0;
-    // wide band: own and displaced values share one plane.  Needed above 160 KiB (nwin 512, > ~150 kept rows) and
-    // already worth it above 40 KiB, where LDS is what limits the resident waves (measured, 1024 x 2000, band
-    // [25,200] Hz: nwin 256 core 2.25 -> 1.44 ms, nwin 512 18.9 -> 9.4 ms)
-    if (lds > 40 * 1024) {
-        lds = (static_cast<size_t>(XS) + static_cast<size_t>(2 * pl->K) * (kTile + 1)) * sizeof(float);
-        cp.oneplane = 1;
-    }
-    if (lds > 160 * 1024) return fail(HSSFSST_EUNSUPPORTED, "LDS request %zu B exceeds 160 KiB", lds);
-    auto kern = hssfsst::fsst_core_kernel<R, kTile>;
-    static std::atomic<unsigned long long> lds_ok{0};
-    if (int rc = allow_full_lds(kern, pl->device, lds_ok)) return rc;
-    name_kernel(cx.kernel, 1, nblocks, "fsst_core_kernel<%d, %d>", R, kTile);
-    hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(nblocks)), dim3(kTile), lds, cx.st, cp);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-inline size_t core128_lds_bytes(const hssfsst_plan* pl, int wpb, bool pair) { return hssfsst::core128_lds_bytes(pl->mf, wpb, pair); }
-
-// the Core128Params every launch of an MFMA plan starts from: the plan-constant fields
-hssfsst::Core128Params core128_params(const hssfsst_plan* pl)
-{
-    hssfsst::Core128Params cp{};
-    cp.atab = pl->d_atab.get(); cp.wtab = pl->d_wtab.get(); cp.twtab = pl->d_wtab.get() + 2 * pl->nwin; cp.r2scale = pl->r2scale;
-    cp.klo = pl->klo; cp.K = pl->K; cp.mode = pl->mode;
-    return cp;
-}
-
-int ensure_status(hssfsst_plan* pl);
-template <int NT, int RQ, bool FAST, int WPB, int S1C = -1, bool PAIR = false, bool RAGGED = false>
-int launch_core128_wpb(hssfsst_plan* pl, ExecCtx& cx, const hssfsst::Core128Params& cp, int64_t nchunks)
-{
-    size_t lds = core128_lds_bytes(pl, WPB, PAIR);
-    auto kern = hssfsst::fsst_core128_kernel<NT, RQ, kFpw128, FAST, WPB, S1C, false, false, PAIR, RAGGED>;
-    static std::atomic<unsigned long long> lds_ok{0};
-    if (int rc = allow_full_lds(kern, pl->device, lds_ok)) return rc;
-    int& slots = RAGGED ? pl->ragged_slots : pl->core128_slots;
-    if (int rc = resident_blocks(pl, slots, kern, 64 * WPB, lds, false)) return rc;     // persistent grid = what is resident at once
-    int64_t blocks = nchunks;                            // small launches: one chunk per block, spread over the CUs
-    if (blocks > slots) blocks = slots;
-    name_kernel(cx.kernel, WPB, blocks, "fsst_core128_kernel<%d, %d, %d, %s, %d, %d, false%s%s>", NT, RQ, kFpw128, FAST ? "true" : "false", WPB, S1C,
-                PAIR ? ", pairs" : "", RAGGED ? ", ragged" : "");
-    hssfsst::Core128Params cq = cp;
-    if constexpr (PAIR) {                                // (a pair's bounded wait reports through the status word)
-        if (int rcs = ensure_status(pl)) return rcs;
-        cq.status = pl->d_status;
-    }
-    hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(blocks)), dim3(64 * WPB), lds, cx.st, cq);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-// One rolling step in ONE launch (fsst_core128_kernel<.., STREAM>, fsst_mfma128.hpp): the chunk's groups, one per ticket, blocks
-// bound to channels; tape append, transform, running-moments merge and normalisation.  Returns 1 when it launched, 0 when the
-// step should take the three-launch route (a shape whose plain transform would not be this kernel's one-group chunks).
-template <int NT, int RQ, int WPB, bool PAIR>
-int launch_stream(hssfsst_plan* pl, float* tape_at, long long tape_len, const float* x_new_dev, long long x_stride, int channels, int chunk,
-                  float* out, double* state, float* mirror, hipStream_t st)
-{
-    const int ngroups = (chunk + 15) / 16;
-    const hssfsst::Core128Regions reg = hssfsst::core128_regions(ngroups, channels);
-    if (!(reg.npc[0] == 0 && reg.npc[1] == 0 && reg.gpc[2] == 1)) return 0;      // (the plain kernel's chunks are not single groups)
-    const size_t lds = core128_lds_bytes(pl, WPB, PAIR);
-    if (lds > kMaxLdsBytes) return 0;
-    auto kern = hssfsst::fsst_core128_kernel<NT, RQ, kFpw128, true, WPB, -1, false, true, PAIR>;
-    static std::atomic<unsigned long long> lds_ok{0};
-    if (int rc = allow_full_lds(kern, pl->device, lds_ok)) return rc;
-    if (int rc = resident_blocks(pl, pl->stream_slots, kern, 64 * WPB, lds, false)) return rc;
-    if (state && pl->d_stream_arrive.cap < static_cast<size_t>(channels)) {
-        if (int rc = pl->d_stream_arrive.grow(static_cast<size_t>(channels))) return rc;
-        HIP_TRY(hipMemsetAsync(pl->d_stream_arrive.get(), 0, static_cast<size_t>(channels) * sizeof(unsigned), st));
-    }
-    if (state) {
-        if (int rc = pl->d_stream_pieces.grow(static_cast<size_t>(channels) * ngroups * 4)) return rc;
-    }
-    if (int rcs = ensure_status(pl)) return rcs;
-    int bpc = pl->stream_slots / channels;                // blocks per channel: spread a small step over the chip
-    if (bpc > ngroups) bpc = ngroups;
-    if (bpc < 1) bpc = 1;
-    hssfsst::Core128Params cp = core128_params(pl);
-    cp.x = tape_at; cp.xstride = tape_len; cp.out = out; cp.partials = nullptr;
-    cp.n = pl->nwin - 1 + chunk; cp.nsig = channels; cp.col0 = pl->nwin / 2; cp.ncols = chunk; cp.reg = reg;
-    cp.xnew = x_new_dev; cp.xnew_stride = x_stride; cp.hist = pl->nwin - 1; cp.bpc = bpc; cp.state = state; cp.arrive = pl->d_stream_arrive.get(); cp.pieces = pl->d_stream_pieces.get(); cp.mirror = mirror;
-    const long long grid = static_cast<long long>(channels) * bpc;
-    cp.status = pl->d_status;
-    name_kernel(pl->last_kernel, WPB, grid, "fsst_core128_kernel<%d, %d, %d, true, %d, -1, false, stream%s>", NT, RQ, kFpw128, WPB, PAIR ? ", pairs" : "");
-    hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(grid)), dim3(64 * WPB), lds, st, cp);
-    HIP_TRY(hipGetLastError());
-    return 1;
-}
-
-// Fused z-score launch (STACK; fsst_mfma128.hpp "Fused z-score"): one persistent block per CU, every CU owns whole signals.  FAST: the
-// wide-store epilogue (nwin 128, even K <= 24); otherwise the general one (any K: nwin 256, or nwin 128 with an odd or wide band), whose
-// z-score tickets sweep a chunk as float4s: every signal's feature block has to start on a 16-byte boundary.  Returns 1 when it launched, 0 when
-// this exec should take the two-kernel path (signal too long for the LDS partials, or a batch that would leave CUs idle for a whole signal), < 0 on error.
-template <int NT, int RQ, bool FAST, int WPB, int S1C>
-int launch_fused(hssfsst_plan* pl, ExecCtx& cx, hssfsst::Core128Params cp, int64_t batch, int ngroups)
-{
-    if (ngroups > hssfsst::kFusedMaxGroups || (ngroups + kFpw128 / 16 - 1) / (kFpw128 / 16) < hssfsst::kFusedMinChunks) return 0;
-    if (!FAST && (((static_cast<long long>(cp.ncols) * 2 * pl->K) & 3) != 0 || (reinterpret_cast<uintptr_t>(cp.out) & 15) != 0)) return 0;
-    const size_t lds = core128_lds_bytes(pl, WPB, false) + (FAST ? hssfsst::kCtlFusedFloats - hssfsst::kCtlFloats : 0) * sizeof(float);
-    if (lds > static_cast<size_t>(kMaxLdsBytes)) return 0;
-    auto kern = hssfsst::fsst_core128_kernel<NT, RQ, kFpw128, FAST, WPB, S1C, true>;
-    static std::atomic<unsigned long long> lds_ok{0};
-    if (int rc = allow_full_lds(kern, pl->device, lds_ok)) return rc;
-    if (int rc = resident_blocks(pl, pl->fused_slots, kern, 64 * WPB, lds, true)) return rc;       // one block per CU
-    if (pl->fused_slots < 1) return 0;
-    const int64_t grid = pl->fused_slots;
-    if (!hssfsst::fused_rounds_full(batch, grid)) return 0;
-    if (int rcs = ensure_status(pl)) return rcs;
-    cp.status = pl->d_status;
-    name_kernel(cx.kernel, WPB, grid, "fsst_core128_kernel<%d, %d, %d, %s, %d, %d, true>", NT, RQ, kFpw128, FAST ? "true" : "false", WPB, S1C);
-    hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(grid)), dim3(64 * WPB), lds, cx.st, cp);
-    HIP_TRY(hipGetLastError());
-    return 1;
-}
-
-// The status word of the in-kernel waits lives in pinned, device-mapped host memory: a kernel that gave up writes it
-// with a system-scope store, and the host looks at it without synchronising (at the start of the next exec, in
-// hssfsst_plan_check after a synchronisation, at plan destruction).
-int ensure_status(hssfsst_plan* pl)
-{
-    if (pl->d_status) return 0;
-    void* h = nullptr;
-    HIP_TRY(hipHostMalloc(&h, sizeof(unsigned), hipHostMallocMapped));
-    *static_cast<volatile unsigned*>(h) = 0u;
-    void* d = nullptr;
-    HIP_TRY(hipHostGetDevicePointer(&d, h, 0));
-    pl->h_status = static_cast<volatile unsigned*>(h);
-    pl->d_status = static_cast<unsigned*>(d);
-    return 0;
-}
-
-// Team kernels: [0] arrival counter, [1] abort word on the device; the identity of the last launch that gave up in pinned host memory.
-int ensure_team_words(hssfsst_plan* pl, hipStream_t st)
-{
-    if (pl->d_arrive.get()) return 0;
-    if (int rc = pl->d_arrive.grow(4)) return rc;
-    HIP_TRY(hipMemsetAsync(pl->d_arrive.get(), 0, 4 * sizeof(unsigned), st));
-    pl->arrive_total = 0;
-    pl->done_total = 0;
-    void* h = nullptr;
-    HIP_TRY(hipHostMalloc(&h, 4 * sizeof(unsigned), hipHostMallocMapped));
-    for (int i = 0; i < 4; ++i) static_cast<volatile unsigned*>(h)[i] = 0u;
-    void* d = nullptr;
-    HIP_TRY(hipHostGetDevicePointer(&d, h, 0));
-    pl->h_fallback = static_cast<volatile unsigned*>(h);
-    pl->d_fallback = static_cast<unsigned*>(d);
-    return 0;
-}
-
-// Team kernel at four waves per SIMD (fsst_team16.hpp): canonical band, STACK, one 16-frame group per ticket, one group image
-// held in registers.  Returns 1 when it launched, 0 when this exec should take another path, < 0 on error.
-// the team kernel of output type OT: the float32 kernel, or the half-precision one (fsst_team16.hpp)
-template <int KLO, int KC, int WPB, int DEPTH, class OT>
-constexpr auto team16_kernel()
-{
-    return &hssfsst::fsst_team16_kernel<KLO, KC, WPB, DEPTH, OT>;
-}
-template <class OT>
-constexpr const char* out_type_suffix() { return sizeof(OT) == 4 ? "" : std::is_same<OT, _Float16>::value ? ", f16" : ", bf16"; }
-
-// OT = _Float16 / __bf16: a half plan's team launch; it stores its z-scores as 2-byte elements at hout (8-byte aligned, else 0)
-template <int KLO, int KC, int WPB, int DEPTH, class OT = float>
-int launch_team16(hssfsst_plan* pl, ExecCtx& cx, const hssfsst::Core128Params& cp, int64_t batch, int ngroups, void* hout = nullptr)
-{
-    using namespace hssfsst;
-    hipStream_t st = cx.st;
-    if constexpr (sizeof(OT) == 2) {
-        if (hout == nullptr || (reinterpret_cast<uintptr_t>(hout) & 7) != 0) return 0;
-    }
-    // (at least 84 KiB: one block per CU whatever its size -- the teams count on it)
-    constexpr int PSLOTS = t16_pslots<KLO, KC>();        // signals whose partials a CU keeps in LDS at a time
-    constexpr int MS = t16_slots<KLO, KC>();             // statistics / mailbox slots the kernel's LDS has room for
-    size_t lds = canon_lds_bytes(t16_ctl_floats(PSLOTS, MS), CanonCfg<KLO, KC>::wave_floats(), WPB);
-    if (lds > static_cast<size_t>(kMaxLdsBytes)) return 0;
-    if (lds < 84 * 1024) lds = 84 * 1024;
-    auto kern = team16_kernel<KLO, KC, WPB, DEPTH, OT>();
-    static std::atomic<unsigned long long> lds_ok{0};
-    if (int rc = allow_full_lds(kern, pl->device, lds_ok)) return rc;
-    if (int rc = resident_blocks(pl, pl->team16_cus, kern, 64 * WPB, lds, true)) return rc;
-    if (pl->team16_cus < 1) return 0;
-    const Team16Geometry geo = team16_geometry(ngroups, batch, cp.xstride, pl->team16_cus, WPB, DEPTH, PSLOTS, MS);
-    if (!geo.ok) return 0;
-    const int T = geo.T, nteams = geo.nteams, grid = geo.grid, slots = geo.slots;
-    int rc;
-    if ((rc = ensure_status(pl)) != 0) return rc;
-    const size_t words = static_cast<size_t>(nteams) * slots * kT16SlotWords;
-    if (words > pl->d_mail.cap) {
-        if ((rc = pl->d_mail.grow(words)) != 0) return rc;
-        HIP_TRY(hipMemsetAsync(pl->d_mail.get(), 0, pl->d_mail.cap * sizeof(unsigned long long), st));
-        pl->team_seq = 0;
-    }
-    if (++pl->team_seq > 0xffffu) {                      // tags would repeat: start over from clean mailboxes
-        HIP_TRY(hipMemsetAsync(pl->d_mail.get(), 0, pl->d_mail.cap * sizeof(unsigned long long), st));
-        pl->team_seq = 1;
-    }
-    Team16Params tp{};
-    tp.x = cp.x; tp.out = sizeof(OT) == 4 ? cp.out : static_cast<float*>(hout); tp.atab = pl->d_atab16.get(); tp.wtab = cp.wtab; tp.twtab = cp.twtab;
-    tp.mail = pl->d_mail.get(); tp.status = pl->d_status; tp.r2scale_s = pl->canon_r2s; tp.inv_c = pl->canon_inv_c;
-    tp.n = cp.n; tp.nsig = cp.nsig; tp.col0 = cp.col0; tp.ncols = cp.ncols; tp.xstride = cp.xstride;
-    tp.team = T; tp.cpc_shift = geo.cpc_shift; tp.slots = slots; tp.seq = pl->team_seq;
-    {   // the two float64 divisions of stats_finish (correctly rounded here as there: the same bits)
-        const double total = static_cast<double>(KC) * static_cast<double>(cp.ncols);
-        tp.inv_total = 1.0 / total; tp.inv_total1 = 1.0 / (total - 1.0);
-    }
-    tp.spin_ticks = 500u * 100u;                         // a wait gives up after 500 us (100 MHz ticks)
-    if ((rc = ensure_team_words(pl, st)) != 0) return rc;
-    if (++pl->team_launch == 0u) pl->team_launch = 1u;
-    tp.abort_word = pl->d_arrive.get() + 1; tp.fallbacks = pl->d_fallback; tp.launch = pl->team_launch;
-    const bool force_fallback = debug_switches().team_force_fallback;   // tests: every team launch finds itself given up
-    if (force_fallback) {
-        HIP_TRY(hipMemcpyAsync(pl->d_arrive.get() + 1, &pl->team_launch, sizeof(unsigned), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(pl->d_fallback, &pl->team_launch, sizeof(unsigned), hipMemcpyHostToDevice, st));
-    }
-    tp.arrive = pl->d_arrive.get(); tp.arrive_base = pl->arrive_total;
-    pl->arrive_total += static_cast<unsigned>(grid);     // (a plan is single-stream: every block of the earlier launches has arrived)
-    if (cx.want_done_word && !force_fallback) {          // (hssfsst_exec_pinned & co: the host waits for this exec alone)
-        tp.done = pl->d_arrive.get() + 2; tp.done_base = pl->done_total; tp.host_done = pl->d_fallback + 2;
-        pl->done_total += static_cast<unsigned>(grid);
-        cx.flagged_launch = pl->team_launch;
-    }
-    name_kernel(cx.kernel, WPB, grid, "fsst_team16_kernel<%d, %d, %d, %d%s> teams of %d", KLO, KC, WPB, DEPTH, out_type_suffix<OT>(), T);
-    hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(grid)), dim3(64 * WPB), lds, st, tp);
-    HIP_TRY(hipGetLastError());
-    cx.team_launch = pl->team_launch;
-    return 1;
-}
-
-// Canonical-class kernels (fsst_canon128.hpp): nwin = 128, STACK / STACK_UNNORM, the kept band a compile-time constant.  Two bands
-// are instantiated: rows 4..25 = [25, 200] Hz at fs = 1000 (/root/reference/main.py:153-158, the reference's own configuration) and
-// rows 2..25 = [25, 400] Hz at fs = 2000 -- the pass band of the Springer / Schmidt heart-sound segmenters on recordings at
-// PhysioNet 2016's native rate (/root/reference/hss/datasets/heart_sounds.py:36-113 loads them un-resampled).  Every other band keeps
-// fsst_core128_kernel.  (A third band is one line here: the template takes any even band of <= 24 rows inside rows 0..31.)
-constexpr int kCanonBands[][2] = {{4, 22}, {2, 24}};
-
-bool plan_is_canon(const hssfsst_plan* pl) { return pl->canon_idx >= 0; }
-// f(KLO, KC) with the plan's band as integral constants
-template <class F>
-int canon_dispatch(const hssfsst_plan* pl, F&& f)
-{
-    switch (pl->canon_idx) {
-    case 0: return f(std::integral_constant<int, kCanonBands[0][0]>{}, std::integral_constant<int, kCanonBands[0][1]>{});
-    case 1: return f(std::integral_constant<int, kCanonBands[1][0]>{}, std::integral_constant<int, kCanonBands[1][1]>{});
-    default: return fail(HSSFSST_EINVAL, "canon_dispatch: not a canonical-class plan");
-    }
-}
-
-hssfsst::CanonParams canon_params(const hssfsst_plan* pl, const ExecCtx& cx, const hssfsst::Core128Params& cp)
-{
-    hssfsst::CanonParams q{};
-    q.x = cp.x; q.out = cp.out; q.partials = cp.partials; q.atab = pl->d_atab16.get(); q.wtab = cp.wtab; q.twtab = cp.twtab;
-    q.r2scale_s = pl->canon_r2s; q.inv_c = pl->canon_inv_c;
-    q.n = cp.n; q.mode = cp.mode; q.nsig = cp.nsig; q.col0 = cp.col0; q.ncols = cp.ncols; q.xstride = cp.xstride; q.reg = cp.reg;
-    q.status = cp.status;
-    q.gate = cx.gate; q.gate_val = cx.gate_val;
-    return q;
-}
-
-template <int KLO, int KC, bool RAGGED = false>
-int launch_canon_band(hssfsst_plan* pl, ExecCtx& cx, const hssfsst::Core128Params& cp, int64_t nchunks)
-{
-    constexpr int WPB = 16;
-    constexpr size_t lds = hssfsst::canon_lds_bytes(hssfsst::kCanonCtlFloats, hssfsst::CanonCfg<KLO, KC>::wave_floats(), WPB);
-    static_assert(lds <= static_cast<size_t>(kMaxLdsBytes), "16 wave regions must fit");
-    auto kern = hssfsst::fsst_canon_kernel<KLO, KC, false, RAGGED>;
-    static std::atomic<unsigned long long> lds_ok{0};
-    if (int rc = allow_full_lds(kern, pl->device, lds_ok)) return rc;
-    int& slots = RAGGED ? pl->ragged_slots : pl->canon_slots;
-    if (int rc = resident_blocks(pl, slots, kern, 64 * WPB, lds, false)) return rc;
-    int64_t blocks = nchunks < slots ? nchunks : slots;
-    // (a gated launch -- the fallback behind a team launch -- almost always finds its gate closed: a quarter of the chip keeps
-    //  the empty launch at ~2 us instead of ~4; when it does run, the GPU is shared anyway)
-    if (cx.gate != nullptr && blocks > 64) blocks = 64;
-    if (cx.gate == nullptr) name_kernel(cx.kernel, WPB, blocks, "fsst_canon_kernel<%d, %d, false%s>", KLO, KC, RAGGED ? ", ragged" : "");
-    hssfsst::CanonParams q = canon_params(pl, cx, cp);
-    if constexpr (RAGGED) { q.rsig = cp.rsig; q.rchunk = cp.rchunk; q.rnchunks = cp.rnchunks; }
-    hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(blocks)), dim3(64 * WPB), lds, cx.st, q);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-int launch_canon(hssfsst_plan* pl, ExecCtx& cx, const hssfsst::Core128Params& cp, int64_t nchunks)
-{
-    return canon_dispatch(pl, [&](auto KL, auto KN) { return launch_canon_band<decltype(KL)::value, decltype(KN)::value>(pl, cx, cp, nchunks); });
-}
-
-// One CU per signal with the z-score in the same launch (see launch_fused): 1 = launched, 0 = take another path
-// gated = the fallback queued behind a team launch (cx.gate set): any batch size -- the block count is what a launch that
-// almost always finds its gate closed should cost, not what would be fast.
-template <int KLO, int KC>
-int launch_canon_fused_band(hssfsst_plan* pl, ExecCtx& cx, hssfsst::Core128Params cp, int64_t batch, int ngroups)
-{
-    const bool gated = cx.gate != nullptr;
-    constexpr int WPB = 16, GPC = hssfsst::kCanonTileFrames / 16;
-    if (ngroups > hssfsst::kFusedMaxGroups || (ngroups + GPC - 1) / GPC < hssfsst::kFusedMinChunks) return 0;
-    constexpr size_t lds = hssfsst::canon_lds_bytes(hssfsst::kCanonCtlFusedFloats, hssfsst::CanonCfg<KLO, KC>::wave_floats(), WPB);
-    // (rows 2..25: 16 wave regions of 8.6 kB and the two signals' partials do not fit the 160 KiB together: team kernel or two launches)
-    if constexpr (lds > static_cast<size_t>(kMaxLdsBytes)) return 0;
-    else {
-    auto kern = hssfsst::fsst_canon_kernel<KLO, KC, true>;
-    static std::atomic<unsigned long long> lds_ok{0};
-    if (int rc = allow_full_lds(kern, pl->device, lds_ok)) return rc;
-    if (int rc = resident_blocks(pl, pl->fused_slots, kern, 64 * WPB, lds, true)) return rc;
-    if (pl->fused_slots < 1) return 0;
-    int64_t grid = pl->fused_slots;
-    // (gated = behind a team launch: almost always the gate is closed and 64 blocks keep the empty launch short)
-    if (gated) grid = batch < 64 ? batch : 64;
-    else if (!hssfsst::fused_rounds_full(batch, grid)) return 0;
-    if (int rcs = ensure_status(pl)) return rcs;
-    cp.status = pl->d_status;
-    if (!gated) name_kernel(cx.kernel, WPB, grid, "fsst_canon_kernel<%d, %d, true>", KLO, KC);
-    hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(grid)), dim3(64 * WPB), lds, cx.st, canon_params(pl, cx, cp));
-    HIP_TRY(hipGetLastError());
-    return 1;
-    }
-}
-int launch_canon_fused(hssfsst_plan* pl, ExecCtx& cx, const hssfsst::Core128Params& cp, int64_t batch, int ngroups)
-{
-    return canon_dispatch(pl, [&](auto KL, auto KN) { return launch_canon_fused_band<decltype(KL)::value, decltype(KN)::value>(pl, cx, cp, batch, ngroups); });
-}
 
 // What the host has just learnt about the plan's team launches: `gave_up` of them (seen since the last look) among `total` it knows to have
 // finished.  kTeamGiveUps give-ups without a success in between -> the next kTeamPause execs skip the team kernel (hssfsst.h).
@@ -581,15 +73,6 @@ int timing_end(hssfsst_plan* p, const ExecCtx& cx, bool one_kernel)
         if (int rc = timing_event(p, cx)) return rc;
     p->ev_chunks.push_back(one_kernel ? -1 : 1);
     return 0;
-}
-
-// f(o) with an exec's output `out` as what the plan says it holds: float*, _Float16* or __bf16*
-template <class F>
-void out_dispatch(const hssfsst_plan* p, void* out, F&& f)
-{
-    if (p->out_dtype == HSSFSST_DTYPE_F16) f(static_cast<_Float16*>(out));
-    else if (p->out_dtype == HSSFSST_DTYPE_BF16) f(static_cast<__bf16*>(out));
-    else f(static_cast<float*>(out));
 }
 
 // The tables of a ragged exec's list, into the host block h (laid out by t): signal i reads x at starts[i] - xlo, its features
@@ -640,65 +123,21 @@ int ragged_tables(hssfsst_plan* p, const int64_t* starts, const int64_t* lens, i
     return 0;
 }
 
-// The z-score of a dense STACK exec whose core launch left it to do: `feats` = the un-normalised float32 features [batch][ncols][2K]
-// with their statistics partials in d_partials, `out` = the exec's output in the plan's element type (float32: feats itself, swept
-// in place; a half plan: out of place from its float32 scratch).  (cx.gate non-null: a team launch went first; these launches are
-// its gated fallback.)
-int launch_zscore(hssfsst_plan* p, const ExecCtx& cx, const float* feats, void* out, int64_t batch, int nblk, int fpp, int ncols)
-{
-    float4* stats = reinterpret_cast<float4*>(p->d_stats.get());
-    const float* partials = p->d_partials.get();
-    const hssfsst::ZscoreShape z = hssfsst::zscore_shape(batch);
-    if (!z.fused)
-        hipLaunchKernelGGL(hssfsst::fsst_stats_kernel, dim3(static_cast<unsigned>(batch)), dim3(64), 0, cx.st,
-                           partials, stats, nblk, fpp, ncols, p->K, cx.gate, cx.gate_val);
-    out_dispatch(p, out, [&](auto* o) {
-        hipLaunchKernelGGL(hssfsst::fsst_normalize_kernel<std::remove_pointer_t<decltype(o)>>, dim3(static_cast<unsigned>(z.grid)), dim3(256), 0, cx.st,
-                           feats, o, stats, z.fused ? partials : nullptr, nblk, fpp, ncols, p->K, static_cast<int>(batch), z.slices,
-                           cx.gate, cx.gate_val);
-    });
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-// The z-score of a ragged STACK exec (fsst_ragged.hpp): per-signal statistics, then one sweep over the list's `nunits` units;
-// feats and out as in launch_zscore, rsig and unit0 the list's device tables
-int launch_zscore_ragged(hssfsst_plan* p, const ExecCtx& cx, const float* feats, void* out, int64_t batch,
-                         const hssfsst::RaggedSignal* rsig, const int* unit0, long long nunits)
-{
-    float4* stats = reinterpret_cast<float4*>(p->d_stats.get());
-    hipLaunchKernelGGL(hssfsst::fsst_ragged_stats_kernel, dim3(static_cast<unsigned>(batch)), dim3(64), 0, cx.st, p->d_partials.get(), rsig, stats, p->K);
-    const long long zgrid = std::min<long long>(nunits, 65536);
-    out_dispatch(p, out, [&](auto* o) {
-        hipLaunchKernelGGL(hssfsst::fsst_ragged_normalize_kernel<std::remove_pointer_t<decltype(o)>>, dim3(static_cast<unsigned>(zgrid)), dim3(256), 0, cx.st,
-                           feats, o, rsig, unit0, stats, static_cast<int>(batch), p->K);
-    });
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
 // The plain (two-launch) core kernel of an MFMA plan: the row of kCore128Plain (fsst_launch_shape.hpp) that plan creation
-// chose, turned into its instantiation by expanding that same table.  RAGGED: the instantiations of hssfsst_exec_ragged (the
-// same rows, chunk list from the host).
-template <bool RAGGED, size_t... I>
-int launch_core128_row(hssfsst_plan* pl, ExecCtx& cx, const hssfsst::Core128Params& cp, int64_t nchunks, std::index_sequence<I...>)
-{
-    using hssfsst::kCore128Plain;
-    int rc = 0;
-    (void)((static_cast<size_t>(pl->plain_row) == I
-            && (rc = launch_core128_wpb<kCore128Plain[I].nt, kCore128Plain[I].rq, kCore128Plain[I].fast, kCore128Plain[I].wpb, kCore128Plain[I].s1c,
-                                        kCore128Plain[I].pair, RAGGED>(pl, cx, cp, nchunks), true)) || ...);
-    return rc;
-}
-template <bool RAGGED>
-int launch_core128_plain(hssfsst_plan* pl, ExecCtx& cx, const hssfsst::Core128Params& cp, int64_t nchunks)
+// chose, in the unit that holds the instantiations of its length (512 points: of its length and pairing).  ragged: the
+// instantiations of hssfsst_exec_ragged (the same rows, chunk list from the host).
+int launch_core128_plain(hssfsst_plan* pl, ExecCtx& cx, const hssfsst::Core128Params& cp, int64_t nchunks, bool ragged)
 {
     // (not reached: mfma_facts calls a plan MFMA only when 4 wave regions fit, 2 at 512 points, and the table has a row of that
     //  many waves for every (nt, rq, fast) -- at 128 points with the wide-store epilogue K <= 24 and 16 regions fit;
     //  tests/native/launch_shape_check.cpp sweeps every band)
     if (pl->plain_row < 0) return fail(HSSFSST_EUNSUPPORTED, "LDS request %zu B per wave exceeds the 160 KiB budget", pl->mf.lds_per_wave);
-    return launch_core128_row<RAGGED>(pl, cx, cp, nchunks, std::make_index_sequence<hssfsst::kCore128PlainRows>{});
+    if (pl->mf.nt == 32)
+        return hssfsst::kCore128Plain[pl->plain_row].pair ? launch_core128_plain_n512_pairs(pl, cx, cp, nchunks, ragged)
+                                                          : launch_core128_plain_n512(pl, cx, cp, nchunks, ragged);
+    return pl->mf.rq == 16 ? launch_core128_plain_n256(pl, cx, cp, nchunks, ragged) : launch_core128_plain_n128(pl, cx, cp, nchunks, ragged);
 }
+
 
 // Is the team kernel wanted for a STACK exec of columns [col0, col0 + ncols) under the preference zpref?  Stated once: exec_impl
 // asks before it decides where the features are written, launch_core128 before it launches.  Yes: the canonical band, a range that
@@ -746,12 +185,7 @@ int launch_core128(hssfsst_plan* pl, ExecCtx& cx, const float* dx, long long xst
         const Team team = team_wanted(pl, cx.zpref, col0, ncols, team_only);
         if (team == Team::Paused) --pl->team_pause;
         if (team == Team::Yes) {
-            rc = canon_dispatch(pl, [&](auto KL, auto KN) {      // (16 waves per block, two held groups per wave)
-                constexpr int kl = decltype(KL)::value, kn = decltype(KN)::value;
-                if (pl->out_dtype == HSSFSST_DTYPE_F16) return launch_team16<kl, kn, 16, 2, _Float16>(pl, cx, cp, batch, ngroups, hout);
-                if (pl->out_dtype == HSSFSST_DTYPE_BF16) return launch_team16<kl, kn, 16, 2, __bf16>(pl, cx, cp, batch, ngroups, hout);
-                return launch_team16<kl, kn, 16, 2>(pl, cx, cp, batch, ngroups);
-            });
+            rc = launch_team(pl, cx, cp, batch, ngroups, hout);
             if (rc == 1) {
                 // the team kernel may give the launch up (its blocks wait for each other; other processes on the GPU can keep
                 // them apart: fsst_team16.hpp "Progress"): the same exec is queued behind it, every kernel of it gated on the
@@ -775,8 +209,7 @@ int launch_core128(hssfsst_plan* pl, ExecCtx& cx, const float* dx, long long xst
             if (rc < 0) return rc;
         }
         if (!team_only && !half) {
-            rc = canon16 ? launch_canon_fused(pl, cx, cp, batch, ngroups)
-                 : canon ? launch_fused<16, 8, true, 16, 3>(pl, cx, cp, batch, ngroups) : launch_fused<16, 8, true, 16, -1>(pl, cx, cp, batch, ngroups);
+            rc = canon16 ? launch_canon_fused(pl, cx, cp, batch, ngroups) : launch_fused_n128(pl, cx, cp, batch, ngroups, true, canon);
         }
         if (rc < 0) return rc;
         if (rc == 1) { cx.fused = true; cx.zpath = 1; return 0; }
@@ -786,14 +219,13 @@ int launch_core128(hssfsst_plan* pl, ExecCtx& cx, const float* dx, long long xst
         // not take (odd K or K > 24): 16 waves per block; nwin 256: as on the two-launch path (what fits the LDS: 8 for the canonical band).
         // (512 points: two launches, on wave pairs: 2.6 ms per 1024 windows against 3.0 for the single launch, whose instantiations are gone)
         int rc = 0;
-        if (rq == 8 && core128_lds_bytes(pl, 16, false) <= kMaxLdsBytes) rc = launch_fused<16, 8, false, 16, -1>(pl, cx, cp, batch, ngroups);
-        else if (rq == 16 && core128_lds_bytes(pl, 8, false) <= kMaxLdsBytes)
-            rc = canon ? launch_fused<16, 16, false, 8, 3>(pl, cx, cp, batch, ngroups) : launch_fused<16, 16, false, 8, -1>(pl, cx, cp, batch, ngroups);
+        if (rq == 8 && core128_lds_bytes(pl, 16, false) <= kMaxLdsBytes) rc = launch_fused_n128(pl, cx, cp, batch, ngroups, false, false);
+        else if (rq == 16 && core128_lds_bytes(pl, 8, false) <= kMaxLdsBytes) rc = launch_fused_n256(pl, cx, cp, batch, ngroups, canon);
         if (rc < 0) return rc;
         if (rc == 1) { cx.fused = true; cx.zpath = 1; return 0; }
     }
     if (canon16) return launch_canon(pl, cx, cp, nchunks);
-    return launch_core128_plain<false>(pl, cx, cp, nchunks);
+    return launch_core128_plain(pl, cx, cp, nchunks, false);
 }
 
 // Plan creation, step 1: which kernels the plan runs, with the MFMA kernels' shape nwin = nt x rq and LDS bytes (mfma_facts).
@@ -1100,30 +532,6 @@ static int exec_finish(hssfsst_plan* p, void* out, const void* dout, size_t byte
     return 0;
 }
 
-// The any-length kernel (fsst_dft.hpp) for one exec: its tile search and launch
-static int launch_dft(hssfsst_plan* p, ExecCtx& cx, const float* dx, float* kout, int64_t batch, int n, int64_t x_stride, int col0, int ncols)
-{
-    hssfsst::DftParams dp{};
-    dp.x = dx; dp.out = kout; dp.partials = p->d_partials.get(); dp.atab = p->d_dtab.get();
-    dp.wtab = p->d_wtab.get(); dp.twtab = p->d_wtab.get() + 2 * p->nwin;
-    dp.n = n; dp.nwin = p->nwin; dp.nf = p->nf; dp.klo = p->klo; dp.K = p->K; dp.mode = p->mode; dp.col0 = col0; dp.ncols = ncols;
-    dp.nk4 = (p->nwin + 3) / 4; dp.nblk4 = (p->nf + 3) / 4;
-    dp.xstride = x_stride; dp.r2scale = p->r2scale;
-    const hssfsst::DftShape sh = hssfsst::dft_shape(dp.nk4, p->K, ncols, batch);
-    const int G = sh.G, waves = sh.waves;
-    const size_t per_wave = static_cast<size_t>(hssfsst::dft_wave_lds_floats(dp.nk4, p->K, G)) * sizeof(float);
-    if (waves < 1) return fail(HSSFSST_EUNSUPPORTED, "exec: LDS request %zu B per wave exceeds 160 KiB", per_wave);
-    dp.nitems = sh.nitems;
-    auto launch = [&](auto kern) -> int {
-        static std::atomic<unsigned long long> lds_ok{0};
-        if (int r2 = allow_full_lds(kern, p->device, lds_ok)) return r2;
-        name_kernel(cx.kernel, waves, sh.blocks, "fsst_dft_kernel<%d>", G);
-        hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(sh.blocks)), dim3(64 * waves), per_wave * waves, cx.st, dp);
-        return (hipGetLastError() == hipSuccess) ? 0 : fail(HSSFSST_EHIP, "exec: fsst_dft_kernel launch failed");
-    };
-    return (G == 4) ? launch(hssfsst::fsst_dft_kernel<4>) : (G == 2) ? launch(hssfsst::fsst_dft_kernel<2>) : launch(hssfsst::fsst_dft_kernel<1>);
-}
-
 // The end of an exec whose kernels stored the features to pinned host memory (exec_impl: tiny_out): waits for them.  *redo: the
 // exec's team launch gave itself up and the caller computes the exec again without the team kernel.
 static int finish_pinned_exec(hssfsst_plan* p, const ExecCtx& cx, bool* redo)
@@ -1232,12 +640,7 @@ static int exec_impl(hssfsst_plan* p, const float* x, int64_t batch, int n, int6
     if (d_starts) {
         const size_t nd = static_cast<size_t>(batch) * n;
         if ((rc = p->d_frames.grow(nd)) != 0) return rc;
-        const long long quads = (static_cast<long long>(n) + 3) / 4;
-        long long blocks = (static_cast<long long>(batch) * quads + 255) / 256;
-        if (blocks > 65536) blocks = 65536;
-        hipLaunchKernelGGL(hssfsst::fsst_gather_frames_kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, st,
-                           dx, d_starts, p->d_frames.get(), static_cast<long long>(batch), n);
-        HIP_TRY(hipGetLastError());
+        if ((rc = launch_gather_frames(dx, d_starts, p->d_frames.get(), batch, n, st)) != 0) return rc;
         dx = p->d_frames.get();
         x_stride = n;
     }
@@ -1274,13 +677,8 @@ static int exec_impl(hssfsst_plan* p, const float* x, int64_t batch, int n, int6
     } else if (p->family == Family::Mfma) {
         rc = launch_core128(p, cx, dx, x_stride, kout, cp.partials, n, col0, ncols, batch, !no_fused && cx.zpref != HSSFSST_ZPATH_TWO_LAUNCH,
                             half ? dout : nullptr);
-    } else switch (p->R) {
-        case 1: rc = launch_core<1>(p, cx, cp, nblocks); break;
-        case 2: rc = launch_core<2>(p, cx, cp, nblocks); break;
-        case 4: rc = launch_core<4>(p, cx, cp, nblocks); break;
-        case 8: rc = launch_core<8>(p, cx, cp, nblocks); break;
-        case 16: rc = launch_core<16>(p, cx, cp, nblocks); break;
-        default: rc = fail(HSSFSST_EUNSUPPORTED, "exec: unsupported radix %d", p->R);
+    } else {
+        rc = launch_core_radix(p, cx, cp, nblocks);
     }
     if (rc != 0) return rc;
     if ((rc = timing_core_done(p, cx)) != 0) return rc;
@@ -1439,9 +837,9 @@ int hssfsst_exec_ragged(hssfsst_plan* p, const float* x, int64_t x_len, const in
     // (the canonical-class band in STACK modes takes the canonical kernel's arithmetic, as every single exec of it does; the
     //  general kernels give other -- equally accurate -- bits there)
     if (p->mf.fast && p->mf.nt == 16 && p->mf.rq == 8 && plan_is_canon(p))
-        rc = canon_dispatch(p, [&](auto KL, auto KN) { return launch_canon_band<decltype(KL)::value, decltype(KN)::value, true>(p, cx, cp, t.nchunks); });
+        rc = launch_canon_ragged(p, cx, cp, t.nchunks);
     else
-        rc = launch_core128_plain<true>(p, cx, cp, t.nchunks);
+        rc = launch_core128_plain(p, cx, cp, t.nchunks, true);
     if (rc != 0) return rc;
     if ((rc = timing_core_done(p, cx)) != 0) return rc;
     if (p->mode == HSSFSST_MODE_STACK && (rc = launch_zscore_ragged(p, cx, kout, dout, batch, d_rsig, d_unit0, t.nunits)) != 0) return rc;
@@ -1456,10 +854,7 @@ int hssfsst_moments_merge(hssfsst_plan* p, const float* feats, int64_t batch, in
     if (batch == 0 || p->K == 0) return 0;
     if (batch > 0x7fffffffLL || static_cast<long long>(n) * 2 * p->K >= 0x7fffffffLL) return fail(HSSFSST_EINVAL, "moments_merge: too large");
     DEVICE_SCOPE(p->device);
-    hipLaunchKernelGGL(hssfsst::fsst_moments_merge_kernel, dim3(static_cast<unsigned>(batch)), dim3(hssfsst::kMomThreads), 0,
-                       static_cast<hipStream_t>(stream), feats, state, n, p->K);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return launch_moments_merge(p, feats, batch, n, state, static_cast<hipStream_t>(stream));
 }
 
 int hssfsst_normalize_running(hssfsst_plan* p, float* feats, int64_t batch, int n, const double* state, void* stream)
@@ -1470,15 +865,7 @@ int hssfsst_normalize_running(hssfsst_plan* p, float* feats, int64_t batch, int 
     DEVICE_SCOPE(p->device);
     int rc;
     if ((rc = p->d_stats.grow(static_cast<size_t>(batch) * 4)) != 0) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    float4* stats = reinterpret_cast<float4*>(p->d_stats.get());
-    hipLaunchKernelGGL(hssfsst::fsst_stats_from_state_kernel, dim3(static_cast<unsigned>((batch + 63) / 64)), dim3(64), 0, st,
-                       state, stats, static_cast<int>(batch));
-    const int64_t zgrid = batch < 4096 ? batch : 4096;
-    hipLaunchKernelGGL(hssfsst::fsst_normalize_kernel<float>, dim3(static_cast<unsigned>(zgrid)), dim3(256), 0, st,
-                       static_cast<const float*>(feats), feats, stats, static_cast<const float*>(nullptr), 0, 0, n, p->K, static_cast<int>(batch), 1);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return launch_normalize_running(p, feats, batch, n, state, reinterpret_cast<float4*>(p->d_stats.get()), static_cast<hipStream_t>(stream));
 }
 
 int hssfsst_stream_step(hssfsst_plan* p, float* tape, int64_t tape_len, int64_t pos, const float* x_new, int64_t x_stride,
@@ -1534,12 +921,11 @@ int hssfsst_stream_step(hssfsst_plan* p, float* tape, int64_t tape_len, int64_t 
             else (void)hipGetLastError();
         }
         // (wave pairs: the step's latency is one group's; regions of a block = 2)
-        if (debug_switches().no_pair)
-            launched = (p->mf.nt == 32) ? launch_stream<32, 16, 4, false>(p, tape + (pos - hist), tape_len, xd, x_stride, channels, chunk, out, state, mirror, st)
-                                     : launch_stream<16, 16, 4, false>(p, tape + (pos - hist), tape_len, xd, x_stride, channels, chunk, out, state, mirror, st);
-        else
-            launched = (p->mf.nt == 32) ? launch_stream<32, 16, 4, true>(p, tape + (pos - hist), tape_len, xd, x_stride, channels, chunk, out, state, mirror, st)
-                                     : launch_stream<16, 16, 4, true>(p, tape + (pos - hist), tape_len, xd, x_stride, channels, chunk, out, state, mirror, st);
+        float* tape_at = tape + (pos - hist);
+        const bool pair = !debug_switches().no_pair;
+        if (p->mf.nt != 32) launched = launch_stream_n256(p, tape_at, tape_len, xd, x_stride, channels, chunk, out, state, mirror, st, pair);
+        else launched = pair ? launch_stream_n512_pairs(p, tape_at, tape_len, xd, x_stride, channels, chunk, out, state, mirror, st)
+                             : launch_stream_n512(p, tape_at, tape_len, xd, x_stride, channels, chunk, out, state, mirror, st);
         if (launched < 0) return launched;
         if (launched == 0 && xd)                         // (not this kernel's shape after all: the chunk goes into the tape by a copy)
             HIP_TRY(hipMemcpy2DAsync(tape + pos, static_cast<size_t>(tape_len) * sizeof(float), x_new, static_cast<size_t>(x_stride) * sizeof(float),
@@ -1556,8 +942,7 @@ int hssfsst_stream_step(hssfsst_plan* p, float* tape, int64_t tape_len, int64_t 
         int rc = hssfsst_exec_frames(p, tape + (pos - hist), channels, static_cast<int>(hist + chunk), tape_len, p->nwin / 2, chunk, 1, out, 1, stream);
         if (rc != 0) return rc;
         if (state) {
-            hipLaunchKernelGGL(hssfsst::fsst_stream_finish_kernel, dim3(static_cast<unsigned>(channels)), dim3(hssfsst::kMomThreads), 0, st, out, state, chunk, p->K);
-            HIP_TRY(hipGetLastError());
+            if ((rc = launch_stream_finish(p, out, state, channels, chunk, st)) != 0) return rc;
         }
     }
     if (out_host && launched == 1 && mirror) {

@@ -139,7 +139,7 @@ static_assert(hssfsst::seglayout::kSlotRows == hssfsst::kSegRows, "a tile of the
 
 constexpr size_t kSegTileStepBytes = static_cast<size_t>(2) * hssfsst::kSegGateTiles * hssfsst::kSegTileFloats * sizeof(float);   // seglayout::Chunk
 
-// The segmenter's A-B switch, read ONCE per process (first use) from the environment like the FSST switches (hssfsst.hip:
+// The segmenter's A-B switch, read ONCE per process (first use) from the environment like the FSST switches (fsst_plan.hpp:
 // debug_switches): HSSFSST_SEG_RAGGED_PRE_MIB, the ragged exec's bound of the projection scratch in MiB (a number; 0 or unset: the
 // dense call's 128).  It changes no result.
 int seg_ragged_pre_mib()

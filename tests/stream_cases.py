@@ -5,7 +5,7 @@ un-normalised column it has emitted, the columns of the first steps (whose frame
 normalised output is ``(v - mean) / sqrt(M2 / (count - 1))`` with the state AFTER that step.  Three restatements of the state:
 
 * ``running_reference``: two passes over everything seen so far, float64.  The truth.
-* ``chan_reference``: the Chan merge of per-chunk ``{sum, sum of squares}`` -- what ``merge_state`` (csrc/fsst_kernels.hpp) says it does.
+* ``chan_reference``: the Chan merge of per-chunk ``{sum, sum of squares}`` -- what ``merge_state`` (csrc/fsst_device.hpp) says it does.
 * ``welford_reference``: element by element through ``moments.update_mean`` / ``update_variance``, the mirror of the reference
   project's ``hss.moments``.
 

@@ -532,7 +532,7 @@ def test_stream_step_pageable_host_buffers():
 
 @pytest.mark.parametrize("band,n,batch", [((25, 200), 1, 3), ((25, 200), 17, 2), ((25, 210), 100, 2), ((25, 210), 2000, 3), ((25, 200), 1029, 1)])
 def test_moments_merge_any_shape(band, n, batch):
-    """hssfsst_moments_merge sums a chunk in the order of the transform kernels' 16-frame pieces (fsst_kernels.hpp,
+    """hssfsst_moments_merge sums a chunk in the order of the transform kernels' 16-frame pieces (fsst_device.hpp,
     chunk_moments): any number of frames, even and odd bands, against float64 numpy; then the SAME chunk merged a second time
     (counts and M2 double, the mean stays: the Chan cross term is zero here -- two different chunks are
     tests/test_streaming.py::test_moments_merge_two_different_chunks)."""
@@ -1205,7 +1205,7 @@ def test_team_kernel_repeated_launches_and_shapes():
 def test_dc_offset_statistics(oracle_mod, band, n, batch):
     """A recording with a DC offset 50x its spread, bands that contain row 0: mean^2 >> variance in the real block, the
     case in which a single-pass float32 sum x, sum x^2 loses the variance (round 1's statistics did).  The partials are
-    pivoted sums (fsst_kernels.hpp "Statistics"), so the z-score still meets the 1e-4 gate -- on the two-kernel path
+    pivoted sums (fsst_device.hpp "Statistics"), so the z-score still meets the 1e-4 gate -- on the two-kernel path
     (batch 3) and on the fused kernel (batch 512)."""
     X = (synth.noise_windows(batch, n, seed=31) + 50.0).astype(np.float32)
     tf = FSST(1000, KAISER, truncate_freq=band, stack=True)

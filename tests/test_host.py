@@ -246,11 +246,30 @@ def test_shipped_code_object_keeps_the_fixed_registers(built_lib):
     assert out["kernels"] >= 2 and out["metadata_checked"] >= 2 and out["accessor_instructions"] >= 100, out
 
 
+def test_every_kernel_is_compiled_into_one_code_object(built_lib):
+    """No kernel is compiled twice: the SHIPPED library's code objects (one per translation unit that holds kernels) are read and
+    every kernel symbol is defined in exactly one of them -- a template kernel instantiated from two units would be in two, and
+    whichever copy the loader registers last would win.  137 kernels in all; per family the counts of _lib.kernel_resources, which
+    itself refuses a symbol it meets twice."""
+    import os
+    from heart_sounds_segmentation_amd import _lib
+    if not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-objdump"):
+        pytest.skip("no llvm-objdump")
+    units = _lib.kernel_units()
+    twice = {k: v for k, v in units.items() if len(v) != 1}
+    assert not twice, twice
+    assert len(units) == 137
+    assert {m: len(_lib.kernel_resources(m)) for m in ("fsst_", "seg_", "resample")} == {"fsst_": 85, "seg_": 39, "resample": 13}
+
+
 def test_translation_units():
-    """The library's units (csrc/*.hip) are the ones _lib.SOURCES builds, and every header that holds a kernel is reached -- by the
-    ``#include "..."`` lines, followed through the headers -- from exactly ONE of them: a kernel in two units is defined twice (a
-    template: compiled twice, and whichever copy the loader registers last wins).  host_common.hpp, which every unit includes, holds
-    no kernel.  Compiles nothing."""
+    """The library's units (csrc/*.hip) are the ones _lib.SOURCES builds.  What the ``#include "..."`` lines, followed through the
+    headers (_lib.include_closure, the walk build() dates its objects by), can decide about kernels: host_common.hpp and
+    fsst_plan.hpp, which the FSST units share, hold none; a header that holds a kernel that is no template is reached from exactly
+    ONE unit (it would be defined in every unit that reaches it); and hssfsst.hip, which routes to the launchers' units, reaches no
+    header with a kernel at all.  (A template kernel's header may be reached from several units -- the MFMA core's is, one unit per
+    transform length; that no instantiation is compiled twice is checked on the built library:
+    test_every_kernel_is_compiled_into_one_code_object.)  Compiles nothing."""
     import os
     import re
     from heart_sounds_segmentation_amd import _lib
@@ -263,20 +282,23 @@ def test_translation_units():
         with open(os.path.join(csrc, name)) as fh:
             return fh.read()
 
-    def reached(name, seen):
-        for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', text(name), re.M):
-            inc = os.path.normpath(inc)
-            if os.path.exists(os.path.join(csrc, inc)) and inc not in seen:     # (../../include/hssfsst.h: not under csrc/)
-                seen.add(inc)
-                reached(inc, seen)
-        return seen
+    by_unit = {u: _lib.include_closure(u) for u in units}
+    assert "__global__" not in text("host_common.hpp") and "__global__" not in text("fsst_plan.hpp")
+    assert all("host_common.hpp" in by_unit[u] for u in units) and "fsst_plan.hpp" in by_unit["hssfsst.hip"]
+    def kernels(name):
+        """per ``__global__`` of the file: is it a template?  (a ``template <...>`` head, comments apart, directly in front of it)"""
+        code = re.sub(r"//[^\n]*", "", text(name))
+        return [m.group(1) is not None for m in re.finditer(r"(template\s*<[^;{}]*>\s*)?__global__", code)]
 
-    by_unit = {u: reached(u, set()) for u in units}
-    assert "__global__" not in text("host_common.hpp")
-    for h in sorted(f for f in os.listdir(csrc) if f.endswith((".hpp", ".h"))):
-        if "__global__" in text(h):
-            users = [u for u in units if h in by_unit[u]]
-            assert len(users) == 1, f"{h} holds a kernel and is reached from {users or 'no unit'}"
+    for h in sorted(f for f in os.listdir(csrc) if f.endswith((".hpp", ".h", ".hip"))):
+        ks = kernels(h)
+        users = [u for u in units if h == u or h in by_unit[u]]
+        if ks:
+            assert users, f"{h} holds a kernel and no unit reaches it"
+            assert "hssfsst.hip" not in users, f"{h} holds a kernel and hssfsst.hip reaches it"
+        if not all(ks):
+            assert len(users) == 1, f"{h} holds a kernel that is no template and is reached from {users}"
+    assert kernels("fsst_mfma128.hpp") == [True] and kernels("fsst_team16.hpp") == [True] and False in kernels("fsst_kernels.hpp")
 
 
 def test_lent_buffer_goes_back_when_the_last_view_dies():

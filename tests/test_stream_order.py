@@ -531,7 +531,7 @@ def test_gated_fallback_on_a_held_side_stream(tmp_path):
     launches): the bits of the plain child on the default stream.
 
     The forced call is a blocking one, so there is no query() assertion here: the switch itself uploads the launch's identity from
-    pageable host memory (hssfsst.hip, launch_team16), and such a copy makes the host wait for the stream.  Measured: under a 30 ms
+    pageable host memory (fsst_team.hip, launch_team16), and such a copy makes the host wait for the stream.  Measured: under a 30 ms
     delay the forced call returned after 30.1 ms, the plain one after 0.08 ms (profiles/stream_order.txt).  The plain team launch on
     a held side stream is the LAUNCH_CASES rows above, which do assert it."""
     cycles = int(1e3 * ss.DEFAULT_DELAY_S * ss.calibrate())
