@@ -519,8 +519,17 @@ static int exec_buffers(hssfsst_plan* p, size_t no, bool stage_out, size_t piece
     return 0;
 }
 
-// The end of an exec: a host output is copied back, the stream synchronised and the plan checked; a host input is only waited for
-// (the caller may reuse it)
+// A device `out` of 4-byte elements that is not 16-byte aligned (a view one float into a tensor, say): every float32 kernel stores
+// float4s relative to `out` and the in-place z-score sweeps load them, so such an exec runs on the plan's own output staging, as a
+// host-output exec does, and a device copy on the exec's stream puts the features where the caller wants them (exec_finish).  The
+// 2-byte outputs of a half plan look at their own alignment in the kernels (fsst_half.hpp) and are not staged.
+static bool out_needs_staging(const hssfsst_plan* p, const void* out, int out_on_device)
+{
+    return out_on_device && p->out_es == sizeof(float) && (reinterpret_cast<uintptr_t>(out) & 15) != 0;
+}
+
+// The end of an exec: a host output is copied back, the stream synchronised and the plan checked; a device output that was staged
+// (out_needs_staging) is copied on the stream, nothing waits; a host input is only waited for (the caller may reuse it)
 static int exec_finish(hssfsst_plan* p, void* out, const void* dout, size_t bytes, int x_on_device, int out_on_device, hipStream_t st)
 {
     if (!out_on_device) {
@@ -528,6 +537,7 @@ static int exec_finish(hssfsst_plan* p, void* out, const void* dout, size_t byte
         HIP_TRY(hipStreamSynchronize(st));
         return hssfsst_plan_check(p);
     }
+    if (dout != out) HIP_TRY(hipMemcpyAsync(out, dout, bytes, hipMemcpyDeviceToDevice, st));
     if (!x_on_device) HIP_TRY(hipStreamSynchronize(st));
     return 0;
 }
@@ -654,7 +664,8 @@ static int exec_impl(hssfsst_plan* p, const float* x, int64_t batch, int n, int6
         cx.host_waits = cx.zpref != HSSFSST_ZPATH_ONE_CU && !d_starts;
     }
     float* kout = nullptr;
-    if ((rc = exec_buffers(p, no, !tiny_out && !out_on_device, static_cast<size_t>(nblocks), batch, &dout, &kout)) != 0) return rc;
+    if ((rc = exec_buffers(p, no, (!tiny_out && !out_on_device) || out_needs_staging(p, out, out_on_device), static_cast<size_t>(nblocks), batch,
+                           &dout, &kout)) != 0) return rc;
 
     timing_begin(p, cx);
     // STACK: core (FP32-issue-bound) then the z-score sweep (HBM-bound, in place).  Measured and rejected (git history, DESIGN.md
@@ -824,7 +835,7 @@ int hssfsst_exec_ragged(hssfsst_plan* p, const float* x, int64_t x_len, const in
     float* dout = out;
     float* kout = nullptr;
     if (!x_on_device && (rc = stage_input(p, x + xlo, static_cast<size_t>(xhi - xlo), &dx, st)) != 0) return rc;
-    if ((rc = exec_buffers(p, no, !out_on_device, static_cast<size_t>(groups), batch, &dout, &kout)) != 0) return rc;
+    if ((rc = exec_buffers(p, no, !out_on_device || out_needs_staging(p, out, out_on_device), static_cast<size_t>(groups), batch, &dout, &kout)) != 0) return rc;
 
     ExecCtx cx;
     cx.st = st;

@@ -158,6 +158,15 @@ int seg_check_dtype(const char* what, int feats_dtype)
     return 0;
 }
 
+// The one pointer of each entry point here that a kernel touches sixteen bytes at a time: logp (seg_head_kernel stores a row as one
+// float4) and the training stash (seg_rec_kernel<.., TRAIN> and seg_bwd_rec_kernel move it in float4s).  Every other tensor is read
+// and written one element at a time and may sit at any float.  The text is the sequence entries' (sequence.hip: seq_check_aligned).
+int seg_check_aligned16(const char* what, const char* name, const void* ptr)
+{
+    if ((reinterpret_cast<uintptr_t>(ptr) & 15) != 0) return fail(HSSFSST_EINVAL, "%s: %s is not 16-byte aligned", what, name);
+    return 0;
+}
+
 // The list of a ragged call (count >= 1): count + 1 host offsets from 0, strictly increasing, no recording over the dense step
 // limit, fewer than 2^31 steps in all.  One text for every entry point that takes such a list.
 int seg_check_list(const char* what, const int64_t* offsets, int64_t count)
@@ -328,6 +337,7 @@ int hssfsst_segmenter_exec(hssfsst_segmenter* p, const void* feats, int feats_dt
     if (int rc = seg_check_dtype("segmenter_exec", feats_dtype)) return rc;
     if (batch > kSegMaxBatch || steps > kSegMaxSteps)
         return fail(HSSFSST_EINVAL, "segmenter_exec: batch %lld or steps %lld too large", static_cast<long long>(batch), static_cast<long long>(steps));
+    if (int rc = seg_check_aligned16("segmenter_exec", "logp", logp)) return rc;
     DEVICE_SCOPE(p->device);
     const hipStream_t st = static_cast<hipStream_t>(stream);
     const int B = static_cast<int>(batch), T = static_cast<int>(steps), H = p->H;
@@ -360,6 +370,7 @@ int hssfsst_segmenter_exec_ragged(hssfsst_segmenter* p, const void* feats, int f
     if (!p || !feats || !h0 || !c0 || !logp)
         return fail(HSSFSST_EINVAL, "segmenter_exec_ragged: bad argument (%s is NULL)",
                     !p ? "plan" : !feats ? "feats" : !h0 ? "h0" : !c0 ? "c0" : "logp");
+    if (int rc = seg_check_aligned16("segmenter_exec_ragged", "logp", logp)) return rc;
     DEVICE_SCOPE(p->device);
     const hipStream_t st = static_cast<hipStream_t>(stream);
     const int H = p->H;
@@ -524,6 +535,7 @@ int hssfsst_bilstm_forward(hssfsst_bilstm* p, const float* x, int64_t batch, int
     if (!x || !h0 || !c0 || !y || !hn || !cn || !stash)
         return fail(HSSFSST_EINVAL, "bilstm_forward: bad argument (%s is NULL)",
                     !x ? "x" : !h0 ? "h0" : !c0 ? "c0" : !y ? "y" : !hn ? "hn" : !cn ? "cn" : "stash");
+    if (int rc = seg_check_aligned16("bilstm_forward", "stash", stash)) return rc;
     if (!p->packed) return fail(HSSFSST_EINVAL, "bilstm_forward: no weights yet (call hssfsst_bilstm_set_weights first)");
     DEVICE_SCOPE(p->device);
     const hipStream_t st = static_cast<hipStream_t>(stream);
@@ -549,6 +561,7 @@ int hssfsst_bilstm_backward(hssfsst_bilstm* p, const float* stash, const float* 
     if (!stash || !c0 || !dy || !dgates || !dh0 || !dc0)
         return fail(HSSFSST_EINVAL, "bilstm_backward: bad argument (%s is NULL)",
                     !stash ? "stash" : !c0 ? "c0" : !dy ? "dy" : !dgates ? "dgates" : !dh0 ? "dh0" : "dc0");
+    if (int rc = seg_check_aligned16("bilstm_backward", "stash", stash)) return rc;
     if (!p->packed) return fail(HSSFSST_EINVAL, "bilstm_backward: no weights yet (call hssfsst_bilstm_set_weights first)");
     DEVICE_SCOPE(p->device);
     const hipStream_t st = static_cast<hipStream_t>(stream);
@@ -597,6 +610,7 @@ int hssfsst_bilstm_forward_ragged(hssfsst_bilstm* p, const float* x, const int64
     if (!x || !h0 || !c0 || !y || !hn || !cn || !stash)
         return fail(HSSFSST_EINVAL, "bilstm_forward_ragged: bad argument (%s is NULL)",
                     !x ? "x" : !h0 ? "h0" : !c0 ? "c0" : !y ? "y" : !hn ? "hn" : !cn ? "cn" : "stash");
+    if (int rc = seg_check_aligned16("bilstm_forward_ragged", "stash", stash)) return rc;
     if (!p->packed) return fail(HSSFSST_EINVAL, "bilstm_forward_ragged: no weights yet (call hssfsst_bilstm_set_weights first)");
     DEVICE_SCOPE(p->device);
     const hipStream_t st = static_cast<hipStream_t>(stream);
@@ -625,6 +639,7 @@ int hssfsst_bilstm_backward_ragged(hssfsst_bilstm* p, const float* stash, const 
     if (!stash || !c0 || !dy || !dgates || !dh0 || !dc0)
         return fail(HSSFSST_EINVAL, "bilstm_backward_ragged: bad argument (%s is NULL)",
                     !stash ? "stash" : !c0 ? "c0" : !dy ? "dy" : !dgates ? "dgates" : !dh0 ? "dh0" : "dc0");
+    if (int rc = seg_check_aligned16("bilstm_backward_ragged", "stash", stash)) return rc;
     if (!p->packed) return fail(HSSFSST_EINVAL, "bilstm_backward_ragged: no weights yet (call hssfsst_bilstm_set_weights first)");
     DEVICE_SCOPE(p->device);
     const hipStream_t st = static_cast<hipStream_t>(stream);

@@ -542,14 +542,14 @@ class FSST:
                    "hssfsst_plan_timing")
         return float(ms[0]), float(ms[1]), cnt.value
 
-    def unnormalized(self, X: torch.Tensor, cols: Optional[tuple] = None) -> torch.Tensor:
+    def unnormalized(self, X: torch.Tensor, cols: Optional[tuple] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Extension (streaming): ``(B, n, 2K)`` [real | imag] features
         WITHOUT the per-signal z-score, for use with running moments.  ``cols=(col0, ncols)``
-        computes only those frame centres."""
+        computes only those frame centres.  ``out`` optionally receives the result, as in ``batch``."""
         X = self._as_f32(X, frames=True)
         if X.ndim == 1:
             X = X.unsqueeze(0)
-        return self._run(X, _lib.MODE_STACK_UNNORM, cols=cols)
+        return self._run(X, _lib.MODE_STACK_UNNORM, out=out, cols=cols)
 
     # ------------------------------------------------------------------ reference helper kept for its contract
     def _truncate_frequencies(self, s: torch.Tensor, f: torch.Tensor):

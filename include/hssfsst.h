@@ -20,7 +20,14 @@
  *   - hssfsst_exec() enqueues on `stream` (a hipStream_t, NULL = default stream) and returns
  *     without synchronising when both buffers are device buffers; with a host buffer on either
  *     side it stages through the plan's device scratch and synchronises before returning;
- *   - one plan may be used from one host thread at a time.
+ *   - one plan may be used from one host thread at a time;
+ *   - ALIGNMENT: every pointer is aligned to its own element type (4 bytes for float32, 8 for float64 / int64 / complex64, 2 for
+ *     the 2-byte elements of a half plan), and that is all an entry point asks unless its comment states more.  Where a comment
+ *     states 16 bytes, the entry returns HSSFSST_EINVAL and names the argument before any device work.  Everywhere else a buffer
+ *     may start at any element -- a view one float into a tensor, say -- and the result has the bits of the 16-byte aligned call:
+ *     no kernel touches a caller's buffer with an access wider than the alignment the buffer has.  No entry point reads or writes
+ *     outside the extents its comment gives; workspaces and the training stash are used up to their stated minimum and no
+ *     further (tests/test_guard_bands.py walks every entry point through a guard arena to hold both).
  */
 #ifndef HSSFSST_H
 #define HSSFSST_H
@@ -57,7 +64,8 @@ typedef struct hssfsst_plan hssfsst_plan;
  *              (synchrosqueeze.py:48): 32 / 64 / 128 / 256 / 512 run the radix kernels, every other length the
  *              any-length kernel (windowed DFT on the fp32 matrix pipe, csrc/fsst_dft.hpp)
  *   has_band   0: keep all nwin/2+1 rows; 1: keep rows with f_lo <= k*fs/nwin <= f_hi
- *   mode       HSSFSST_MODE_* */
+ *   mode       HSSFSST_MODE_*
+ * Alignment: window (host, read here and not again) at any double. */
 int hssfsst_plan_create(hssfsst_plan** out, int device, int nwin, const double* window, double fs,
                         int has_band, double f_lo, double f_hi, int mode);
 int hssfsst_plan_destroy(hssfsst_plan* plan);
@@ -101,7 +109,10 @@ int hssfsst_plan_info(const hssfsst_plan* plan, int* nwin, int* nf, int* klo, in
  * device, 0 = host pointer.  stream: hipStream_t or NULL.
  * A call with a host `out` returns when the features are in `out`.  For small execs (the dataset loop's one frame per call) it learns that
  * from a word the kernel's last block stores to pinned host memory behind a system-scope release of all stores, not from the stream:
- * `stream` may still be retiring that launch for a few microseconds after the return (later work on it queues behind, as always). */
+ * `stream` may still be retiring that launch for a few microseconds after the return (later work on it queues behind, as always).
+ * Alignment: x and out at any element, host or device.  The float32 kernels store 16 bytes at a time relative to `out`; a device `out`
+ * that is not 16-byte aligned is therefore written through the plan's own output staging (the buffer a host `out` goes through) and
+ * one device-to-device copy on `stream` -- same bits, nothing waits.  This holds for every exec entry point below. */
 int hssfsst_exec(hssfsst_plan* plan, const float* x, int64_t batch, int n, int x_on_device,
                  float* out, int out_on_device, void* stream);
 
@@ -109,7 +120,8 @@ int hssfsst_exec(hssfsst_plan* plan, const float* x, int64_t batch, int n, int x
  * of every signal; `out` then holds batch * ncols * out_floats_per_sample floats and the STACK
  * statistics run over those columns.  hssfsst_exec(...) == hssfsst_exec_cols(..., 0, n, ...).
  * With col0 >= nwin/2 and col0 + ncols <= n - nwin/2 + 1 no frame touches the zero padding, which is
- * what a rolling transform over a ring buffer needs (SURVEY section 8f row 3 / BASELINE config 5). */
+ * what a rolling transform over a ring buffer needs (SURVEY section 8f row 3 / BASELINE config 5).
+ * Alignment: x and out at any element, as hssfsst_exec. */
 int hssfsst_exec_cols(hssfsst_plan* plan, const float* x, int64_t batch, int n, int col0, int ncols,
                       int x_on_device, float* out, int out_on_device, void* stream);
 
@@ -117,7 +129,8 @@ int hssfsst_exec_cols(hssfsst_plan* plan, const float* x, int64_t batch, int n, 
  * (x_stride < n: overlapping frames).  Replaces the reference's framing + per-frame transform loop
  * (hss/utils/preprocess.py:40-52 frame_signal -> hss/datasets/heart_sounds.py:166-168): a recording is uploaded once
  * and its stride-1000 / length-2000 frames are read in place.  x spans (batch-1)*x_stride + n floats.
- * hssfsst_exec_cols(...) == hssfsst_exec_frames(..., x_stride = n, ...). */
+ * hssfsst_exec_cols(...) == hssfsst_exec_frames(..., x_stride = n, ...).
+ * Alignment: x at any element (so is every frame: x_stride is any number of samples); out at any element, as hssfsst_exec. */
 int hssfsst_exec_frames(hssfsst_plan* plan, const float* x, int64_t batch, int n, int64_t x_stride, int col0, int ncols,
                         int x_on_device, float* out, int out_on_device, void* stream);
 
@@ -128,7 +141,8 @@ int hssfsst_exec_frames(hssfsst_plan* plan, const float* x, int64_t batch, int n
  * Returns 0; 1 (no error, *out = NULL) when every pool buffer is still lent out or the exec is not one whose features are written
  * exactly once (then call hssfsst_exec); < 0 on error.  The Python class hands the buffer out as the returned tensor's storage and
  * releases it when that tensor dies; a caller that keeps every result (the in-memory dataset) falls back to the copying call
- * after 64 frames. */
+ * after 64 frames.
+ * Alignment: x (host) at any element; the lent buffer is the plan's and 16-byte aligned. */
 int hssfsst_exec_pinned(hssfsst_plan* plan, const float* x, int n, float** out);
 int hssfsst_pinned_release(hssfsst_plan* plan, float* buf);
 
@@ -137,7 +151,8 @@ int hssfsst_pinned_release(hssfsst_plan* plan, float* buf);
  * dataset loop hss/datasets/heart_sounds.py:155-169 over MANY recordings: the recordings sit back to back in `x`
  * (one upload), `starts` lists every frame of every recording (hss/utils/preprocess.py:40-52), one call transforms
  * them all: the frames are gathered into a dense batch on the device (8 kB per 2000-sample frame against 360 kB of
- * features) and take the kernels of hssfsst_exec.  out: [batch][n][...] as hssfsst_exec. */
+ * features) and take the kernels of hssfsst_exec.  out: [batch][n][...] as hssfsst_exec.
+ * Alignment: x and out at any element, as hssfsst_exec; starts at any int64. */
 int hssfsst_exec_list(hssfsst_plan* plan, const float* x, int64_t x_len, const int64_t* starts, int starts_on_device,
                       int64_t batch, int n, int x_on_device, float* out, int out_on_device, void* stream);
 
@@ -154,7 +169,9 @@ int hssfsst_exec_list(hssfsst_plan* plan, const float* x, int64_t x_len, const i
  * makes both DMA).  Plans of the MFMA kernel (window length 128 / 256 / 512, every band and mode): one transform launch for
  * the whole list (chunk list made on the host, kept while the next call has the same lengths and offsets) and, for STACK, one
  * statistics and one z-score launch.  Other window lengths (the generic nwin 32 / 64 kernel, the any-length kernel): one
- * hssfsst_exec per signal on `stream`, inside the library -- correct, not batched.  Synchronisation as hssfsst_exec. */
+ * hssfsst_exec per signal on `stream`, inside the library -- correct, not batched.  Synchronisation as hssfsst_exec.
+ * Alignment: x and out at any element, as hssfsst_exec (a signal's own block inside `out` starts wherever the lengths before it put
+ * it); starts and lens (host) at any int64. */
 int hssfsst_exec_ragged(hssfsst_plan* plan, const float* x, int64_t x_len, const int64_t* starts, const int64_t* lens,
                         int64_t batch, int x_on_device, float* out, int out_on_device, void* stream);
 
@@ -221,7 +238,8 @@ int hssfsst_plan_set_timing(hssfsst_plan* plan, int enable);
 int hssfsst_plan_timing(hssfsst_plan* plan, float ms_sum[2], int* nexec);
 
 /* Host helper, no device needed: derivative window of ssq.fsst's IF estimator
- * (dtwin: not-a-knot cubic spline through (1..n, w), analytic derivative at the knots, * fs/2pi). */
+ * (dtwin: not-a-knot cubic spline through (1..n, w), analytic derivative at the knots, * fs/2pi).  window and dwindow: nwin doubles
+ * each, at any double. */
 int hssfsst_dtwin(const double* window, int nwin, double fs, double* dwindow);
 
 /* Host helper, no device needed: kept band of _truncate_frequencies (synchrosqueeze.py:91-111). */
@@ -235,12 +253,14 @@ double hssfsst_update_variance(double x, double m, double var, int64_t k);
  * (count, mean, M2) of the real and imaginary feature blocks with the statistics of a new STACK-less
  * chunk (Chan's pairwise form of the update above).  state: float64 [batch][6] =
  * {count_re, mean_re, M2_re, count_im, mean_im, M2_im} on the device.  feats: float32
- * [batch][n][2K] un-normalised [real | imag] features on the device. */
+ * [batch][n][2K] un-normalised [real | imag] features on the device.
+ * Alignment: feats at any float (a signal's block is read 16 bytes at a time only where it is 16-byte aligned), state at any double. */
 int hssfsst_moments_merge(hssfsst_plan* plan, const float* feats, int64_t batch, int n,
                           double* state, void* stream);
 
 /* Streaming z-score: normalises un-normalised features IN PLACE with the running statistics in
- * `state` (as maintained by hssfsst_moments_merge): (v - mean) / sqrt(M2 / (count - 1)) per block. */
+ * `state` (as maintained by hssfsst_moments_merge): (v - mean) / sqrt(M2 / (count - 1)) per block.
+ * Alignment: feats at any float (16-byte accesses only where a signal's block is 16-byte aligned), state at any double. */
 int hssfsst_normalize_running(hssfsst_plan* plan, float* feats, int64_t batch, int n,
                               const double* state, void* stream);
 
@@ -260,7 +280,10 @@ int hssfsst_normalize_running(hssfsst_plan* plan, float* feats, int64_t batch, i
  * tape when it is full.
  * For window lengths 256 / 512 with an even band of <= 24 rows (config 5) steps 1-4 are ONE kernel launch: x_new in device or
  * PINNED host memory is read by the kernel where it lies (it must stay untouched until the step has run, as for the copy), a
- * pinned, 16-byte aligned out_host is written by the kernel itself; pageable memory is copied.  Same results either way. */
+ * pinned, 16-byte aligned out_host is written by the kernel itself; pageable memory is copied.  Same results either way.
+ * Alignment: tape, x_new, out and out_host at any float, state at any double.  The one-launch step needs a 16-byte aligned `out`
+ * (and, to write out_host itself, a 16-byte aligned out_host): with another `out` the step is the copy, the exec -- through the
+ * plan's staging, as hssfsst_exec -- and the merge-and-normalise launch; another out_host is filled by a copy.  Same bits. */
 int hssfsst_stream_step(hssfsst_plan* plan, float* tape, int64_t tape_len, int64_t pos, const float* x_new,
                         int64_t x_stride, int x_on_device, int channels, int chunk, float* out, double* state,
                         float* out_host, void* stream);
@@ -314,7 +337,8 @@ int hssfsst_resample_plan_info(const hssfsst_resample_plan* plan, int64_t* n, in
  * minus 1.  At least one of y / labels.  x_on_device / out_on_device (for y and labels alike): 1 = device pointers on the plan's
  * device, 0 = host pointers, staged through the plan's device buffers.  Enqueued on `stream` (hipStream_t, NULL = default)
  * without synchronising when every buffer is on the device; with a host buffer the call returns when the results are in
- * place. */
+ * place.
+ * Alignment: x, y, labels and starts at any element of their types, host or device (the kernels move one element at a time). */
 int hssfsst_resample_exec(hssfsst_resample_plan* plan, const void* x, int x_dtype, int64_t x_len, int64_t x_stride,
                           const int64_t* starts, int starts_on_device, int64_t batch, int x_on_device,
                           void* y, int y_dtype, int64_t* labels, int out_on_device, void* stream);
@@ -333,7 +357,8 @@ int hssfsst_resample_plan_create_ragged(hssfsst_resample_plan** out, int device,
  * forward table comes from a host FFT), and deterministic: the same bits whatever its neighbours, its place in the list and the
  * chunking.  Argument errors (NULL pointers, lens[i] < 1, a span outside [0, x_len], an unknown dtype, neither y nor labels, a
  * dense plan) return HSSFSST_EINVAL, a length above 2^26 HSSFSST_EUNSUPPORTED, before any device work; count == 0 does nothing.
- * A ragged plan passed to hssfsst_resample_exec returns HSSFSST_EINVAL. */
+ * A ragged plan passed to hssfsst_resample_exec returns HSSFSST_EINVAL.
+ * Alignment: x, y, labels, starts and lens at any element of their types, as hssfsst_resample_exec. */
 int hssfsst_resample_exec_ragged(hssfsst_resample_plan* plan, const void* x, int x_dtype, int64_t x_len, const int64_t* starts,
                                  const int64_t* lens, int64_t count, int x_on_device, void* y, int y_dtype, int64_t* labels,
                                  int out_on_device, void* stream);
@@ -353,7 +378,8 @@ int hssfsst_resample_exec_ragged(hssfsst_resample_plan* plan, const void* x, int
  * NULL pointers, input_size < 1, hidden < 1 or device < 0 return HSSFSST_EINVAL, hidden > 256 HSSFSST_EUNSUPPORTED, both before
  * any device is touched.  Single-stream and single-thread like the other plans; its scratch belongs to it: one chunk of projected
  * inputs (at most 128 MiB, or one time step if that is more), both layers' outputs (2 x batch x steps x 2 hidden x 4 bytes) and
- * the carried state, grown on demand and kept. */
+ * the carried state, grown on demand and kept.
+ * Alignment: every weight array, and the two arrays of pointers, at any element (host memory, read here and not again). */
 typedef struct hssfsst_segmenter hssfsst_segmenter;
 int hssfsst_segmenter_create(hssfsst_segmenter** out, int device, int input_size, int hidden, const float* const* lstm_1,
                              const float* const* lstm_2, const float* linear_weight, const float* linear_bias);
@@ -371,7 +397,10 @@ int hssfsst_segmenter_info(const hssfsst_segmenter* plan, int* input_size, int* 
  * LIMIT: |h0| < 64 in every element (c0: any finite value).  h enters the recurrent product as h x 1024 in float16, which is
  * sized for an LSTM's own |h| < 1; an h0 element of magnitude 64 or more (exactly: from 64 - 2^-6 on) becomes infinite there
  * and its batch row is NaN from the first step on.  Nothing checks this: h0 is device memory and the call does not synchronise.
- * Tested up to +-63. */
+ * Tested up to +-63.
+ * Alignment: feats (of any of the three types), h0 and c0 at any element.  logp must be 16-byte aligned -- a row of four log-probs is
+ * one 16-byte store, and the decoders that read it ask the same -- or the call returns HSSFSST_EINVAL ("logp is not 16-byte aligned")
+ * before any device work. */
 int hssfsst_segmenter_exec(hssfsst_segmenter* plan, const void* feats, int feats_dtype, int64_t batch, int64_t steps,
                            const float* h0, const float* c0, float* logp, void* stream);
 
@@ -393,7 +422,9 @@ int hssfsst_segmenter_exec(hssfsst_segmenter* plan, const void* feats, int feats
  * returns 0.  The device tables are kept while the next call has the same offsets.
  * Scratch (the plan's, grown on demand and kept, shared with hssfsst_segmenter_exec): both layers' outputs, 2 x sum T x 2 hidden
  * x 4 bytes; one chunk of projected inputs, at most 128 MiB, or one step of every tile (128 KiB each) if that is more; the
- * state, 16 KiB per tile.  Enqueued on `stream` without synchronising. */
+ * state, 16 KiB per tile.  Enqueued on `stream` without synchronising.
+ * Alignment: as hssfsst_segmenter_exec -- feats, h0, c0 at any element, offsets (host) at any int64; logp must be 16-byte aligned, or
+ * HSSFSST_EINVAL ("logp is not 16-byte aligned") before any device work, after the list's and the NULL checks. */
 int hssfsst_segmenter_exec_ragged(hssfsst_segmenter* plan, const void* feats, int feats_dtype, const int64_t* offsets,
                                   int64_t count, const float* h0, const float* c0, int state_rows, float* logp, void* stream);
 
@@ -704,7 +735,11 @@ int hssfsst_stitch_windows(const float* win_logp, const int64_t* win_first, int6
  *                recurrent product dgates . W_hh runs on split-bf16 operands (hi.hi + hi.lo + lo.hi) with float32 accumulation.
  *                The plan's weights must still be those of the forward call.
  * NULL pointers, batch < 1 or steps < 1 and sizes over the limits of hssfsst_segmenter_exec return HSSFSST_EINVAL before any
- * device work. */
+ * device work.
+ * Alignment: every tensor -- the weight arrays behind set_weights' table, x, h0, c0, y, hn, cn, dy, dhn, dcn, dgates, dh0, dc0 -- at any
+ * float: the kernels read and write them one element at a time.  The stash must be 16-byte aligned in forward and backward, dense
+ * and ragged -- it is moved 16 bytes at a time -- or the call returns HSSFSST_EINVAL ("stash is not 16-byte aligned") before any
+ * device work.  Forward writes, and backward reads, exactly the first stash_floats (stash_floats_ragged) floats of it. */
 typedef struct hssfsst_bilstm hssfsst_bilstm;
 int hssfsst_bilstm_create(hssfsst_bilstm** out, int device, int input_size, int hidden);
 int hssfsst_bilstm_destroy(hssfsst_bilstm* plan);
@@ -728,7 +763,9 @@ int hssfsst_bilstm_backward(hssfsst_bilstm* plan, const float* stash, const floa
  *                        step: 5.8 GB for one tile of 35 500-step recordings); equal lengths give hssfsst_bilstm_stash_floats.
  *                        Host only; the plan may be NULL.
  * The plan keeps the list's device tables while the next call has the same offsets; a backward call must be given the offsets of
- * its forward call. */
+ * its forward call.
+ * Alignment: as the dense pair -- every tensor at any float, offsets (host) at any int64; the stash must be 16-byte aligned, or
+ * HSSFSST_EINVAL ("stash is not 16-byte aligned") before any device work, after the list's and the NULL checks. */
 int hssfsst_bilstm_stash_floats_ragged(const hssfsst_bilstm* plan, const int64_t* offsets, int64_t count, int64_t* floats);
 int hssfsst_bilstm_forward_ragged(hssfsst_bilstm* plan, const float* x, const int64_t* offsets, int64_t count, const float* h0,
                                   const float* c0, float* y, float* hn, float* cn, float* stash, void* stream);
